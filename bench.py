@@ -5,10 +5,16 @@ One "step" = one generate_actions pass over one batch of synthetic frames on eve
 projector -> LLaMA-2-7B prefill (256 patches + 512 prompt tokens) -> 512 greedy decode steps (EOS disabled so every step
 does the full work) -> action de-tokenisation (+ one RCCL all_gather of the results when N > 1).
 Workload at N=1 = BASELINE.json configs[1] (one frame); N>1 = configs[2]'s shard on every rank: 8 frames per GPU (64 frames over
-8 GPUs), weak scaling, data parallel, the line then carries `rccl_ranks` (counted by a real collective), `gather_ms` and its share.
+8 GPUs), weak scaling, data parallel, the line then carries `gather_ms` and its share.
 
-Prints ONE JSON line (rank 0) with the driver's contract + `roofline` (dominant kernel = gate/up decode GEMV, timed
-live with HIP events through emmax_profile_decode_stage) + `cpu_baseline` (the oracle timed on the host cores, N=1 only).
+A plain run sets up, warms up, times `--steps` steps and prints ONE JSON line (rank 0) with the driver's contract (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  `--dump-outputs DIR` then writes what the last timed step returned to its
+caller (actions, generated ids, lengths) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+
+`--full` adds everything else, after the timed steps: the per-stage decode launch times and the `roofline` of the dominant kernel
+(gate/up decode GEMV, timed live with HIP events through emmax_profile_decode_stage), the whole-decode-step HBM rate, `cpu_baseline`
+(the oracle timed on the host cores, N=1 only), and at N > 1 the rank count from a real collective (`rccl_ranks`) plus the live
+one-GPU baseline of the same shard (`single_gpu_same_workload`, `scaling_efficiency`).
 """
 
 import argparse
@@ -222,7 +228,12 @@ def main():
     ap.add_argument("--prompt-tokens", type=int, default=512)
     ap.add_argument("--new-tokens", type=int, default=512)
     ap.add_argument("--tiny", action="store_true", help="tiny config (plumbing check only; NOT a valid headline number)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-stage launch times + roofline, decode-step HBM rate, "
+                         "cpu_baseline (N=1), rccl_ranks and the live one-GPU baseline (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (actions, ids, lens) as DIR/<name>.npy (float32/float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--graph", action="store_true", help="replay the decode step as a hipGraph (EMMAX_GRAPH=1) instead of eager launch-ahead")
     ap.add_argument("--fp8", action="store_true", help="BASELINE config 5: fp8-e4m3 decode weights (NOT the bf16 headline)")
     ap.add_argument("--kv-fp8", action="store_true", help="opt-in fp8-e4m3 KV cache, one scale per (token, head) row (NOT the bf16 headline)")
@@ -230,10 +241,12 @@ def main():
                                                          "the reference's fp32 CPU arithmetic; batch 1-2 (a conformance mode: the line says so)")
     ap.add_argument("--exact-fp32kv", action="store_true", help="--exact with an fp32 K / V cache (tuning switch exact = 2) instead of the 24-bit one: the A/B partner")
     ap.add_argument("--scale-baseline", type=float, default=None,
-                    help="N > 1 only: actions/s of ONE GPU on the same per-GPU workload, measured elsewhere; default: rank 0 measures it "
+                    help="N > 1 with --full: actions/s of ONE GPU on the same per-GPU workload, measured elsewhere; default: rank 0 measures it "
                          "live (alone on its GPU, the other ranks parked at a barrier) before the group run")
-    ap.add_argument("--alone-steps", type=int, default=2, help="N > 1 only: steps of the live one-GPU baseline run on rank 0")
+    ap.add_argument("--alone-steps", type=int, default=2, help="N > 1 with --full: steps of the live one-GPU baseline run on rank 0")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.kv_fp8:
         os.environ["EMMAX_KV_FP8"] = "1"   # (as EMMAX_GRAPH: read once at library start-up, inherited by self-launched ranks)
     if args.exact_fp32kv:
@@ -276,7 +289,7 @@ def main():
     frames = torch.from_numpy(rng.integers(0, 256, size=(B, 224, 224, 3), dtype=np.uint8)).to(dev)
     prompts = [[1] + [int(x) for x in rng.integers(3, 31744, size=P - 1)] for _ in range(B)]
 
-    alone = _alone_baseline(args, model, frames, prompts, T, rank, world, B)
+    alone = _alone_baseline(args, model, frames, prompts, T, rank, world, B) if args.full else None
     gather_s = []
 
     last_lens = []
@@ -295,14 +308,15 @@ def main():
     for _ in range(args.warmup):
         step()
     gather_s.clear()
-    rccl_ranks = edist.collective_world_size(dev)     # counted by an actual all_reduce, not read from the environment
+    # --full: counted by an actual all_reduce, not read from the environment
+    rccl_ranks = edist.collective_world_size(dev) if args.full else None
     edist.barrier()
     torch.cuda.synchronize()
     lat = []
     t0 = time.perf_counter()
     for _ in range(args.steps):
         s0 = time.perf_counter()
-        step()
+        last_out = step()
         torch.cuda.synchronize()
         lat.append(time.perf_counter() - s0)
     edist.barrier()
@@ -314,8 +328,46 @@ def main():
     if last_lens and int(last_lens[0].min()) != T:
         raise SystemExit("bench: a row stopped after %d of %d tokens -- the timed steps did not do the full work" % (int(last_lens[0].min()), T))
 
-    # ---- stage breakdown + roofline of the dominant kernel (rank 0) ----
+    if rank == 0 and args.dump_outputs:
+        _dump_outputs(args.dump_outputs, last_out)
+
     out = None
+    if rank == 0:
+        eng = model.engine
+        ctx = cfg.n_patches + P
+        out = {
+            "metric": "actions/sec", "value": round(actions_per_s, 4), "unit": "actions/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 2), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": ("bf16 weights x two-term bf16 activations (fp32-equivalent), fp32 accumulate" if args.exact else "bf16") if not args.fp8 else "bf16 activations / fp8-e4m3 decode weights", "data": "synthetic",
+            "cmd": "python bench.py --gpus %d --steps %d --warmup %d --batch-per-gpu %d --prompt-tokens %d --new-tokens %d%s%s%s%s"
+                   % (world, args.steps, args.warmup, B, P, T, " --fp8" if args.fp8 else "", (" --graph" if args.graph else "") + (" --kv-fp8" if args.kv_fp8 else "") + (" --exact-fp32kv" if args.exact_fp32kv else " --exact" if args.exact else ""), " --tiny" if args.tiny else "", " --full" if args.full else ""),
+            "config": {"workload": _workload(args, world, B, P, T),
+                       "batch_per_gpu": B, "global_batch": B * world, "prompt_tokens": P, "new_tokens": T, "context": ctx + T,
+                       "parallelism": f"dp{world}", "hipgraph": eng.graph_active(), "exact_numerics": bool(eng.exact)},
+            "value_per_gpu": round(actions_per_s / world, 4), "dist_backend": edist.backend_name(),
+            "gather_ms": round(gather_ms, 4), "gather_share": round(gather_ms / ms_per_step, 6),
+            "p50_latency_ms": round(float(np.median(lat)) * 1e3, 2),
+        }
+    if args.full:
+        _full_measurements(args, out, model, cfg, frames, prompts, rank, world, B, P, T, wbytes, alone, rccl_ranks)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    edist.barrier()
+
+
+def _dump_outputs(d, outs):
+    """What the last timed step returned to its caller: actions f32 [B,7], generated ids [B,T] and lengths [B] (int32, stored as exact
+    float64); at N > 1 the gathered whole batch."""
+    os.makedirs(d, exist_ok=True)
+    acts, ids, lens = (torch.as_tensor(x).detach().cpu().numpy() for x in outs)
+    for name, a, dt in (("actions", acts, np.float32), ("token_ids", ids, np.float64), ("lens", lens, np.float64)):
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=dt))
+
+
+def _full_measurements(args, out, model, cfg, frames, prompts, rank, world, B, P, T, wbytes, alone, rccl_ranks):
+    """--full: stage breakdown + roofline of the dominant kernel, whole-decode-step HBM rate, cpu_baseline (rank 0), the N > 1 scaling
+    fields.  Runs after the timed steps; adds its keys to the rank-0 line `out`."""
+    # ---- stage breakdown + roofline of the dominant kernel (rank 0) ----
     if rank == 0:
         eng = model.engine
         L = cfg.llm
@@ -355,20 +407,10 @@ def main():
                                  + 2 * L.hidden_size) + L.hidden_size + L.vocab_size * L.hidden_size) * wbytes
         kv_bytes = L.num_layers * B * 2 * (ctx + nsteps // 2) * (kvd * (1 if args.kv_fp8 else (4 if args.exact_fp32kv else 3) if args.exact else 2) + (L.num_kv_heads * 4 if args.kv_fp8 else 0))
         step_gbs = (w_llm + kv_bytes) / (step_ms * 1e-3) / 1e9
-        out = {
-            "metric": "actions/sec", "value": round(actions_per_s, 4), "unit": "actions/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 2), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": ("bf16 weights x two-term bf16 activations (fp32-equivalent), fp32 accumulate" if args.exact else "bf16") if not args.fp8 else "bf16 activations / fp8-e4m3 decode weights", "data": "synthetic",
-            "cmd": "python bench.py --gpus %d --steps %d --warmup %d --batch-per-gpu %d --prompt-tokens %d --new-tokens %d%s%s%s"
-                   % (world, args.steps, args.warmup, B, P, T, " --fp8" if args.fp8 else "", (" --graph" if args.graph else "") + (" --kv-fp8" if args.kv_fp8 else "") + (" --exact-fp32kv" if args.exact_fp32kv else " --exact" if args.exact else ""), " --tiny" if args.tiny else ""),
-            "config": {"workload": _workload(args, world, B, P, T),
-                       "batch_per_gpu": B, "global_batch": B * world, "prompt_tokens": P, "new_tokens": T, "context": ctx + T,
-                       "parallelism": f"dp{world}", "hipgraph": eng.graph_active(), "exact_numerics": bool(eng.exact)},
-            "value_per_gpu": round(actions_per_s / world, 4), "single_gpu_same_workload": alone,
-            "scaling_efficiency": round(actions_per_s / (world * alone["value"]), 4) if alone else None,
-            "rccl_ranks": rccl_ranks, "dist_backend": edist.backend_name(),
-            "gather_ms": round(gather_ms, 4), "gather_share": round(gather_ms / ms_per_step, 6),
-            "p50_latency_ms": round(float(np.median(lat)) * 1e3, 2),
+        out.update({
+            "single_gpu_same_workload": alone,
+            "scaling_efficiency": round(out["value"] / (world * alone["value"]), 4) if alone else None,
+            "rccl_ranks": rccl_ranks,
             "decode_ms_per_token": round(step_ms, 4), "decode_tokens_per_s": round(B * 1e3 / step_ms, 1),
             "decode_step_hbm_gbs": round(step_gbs, 1), "decode_step_hbm_frac": round(step_gbs / HBM_PEAK_GBS, 4),
             "weights": {"arena_gb": round(eng.arena.numel() / 1e9, 2), "aux_gb_batch_ge_3": round((eng.weight_bytes() - eng.arena.numel()) / 1e9, 2),
@@ -379,11 +421,9 @@ def main():
                          "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                          "bytes_per_launch": stage_bytes[dom], "us_per_launch": round(stage_us[dom], 2), "traffic": traffic,
                          "traffic_source": "profiles/%s (rocprofv3 --pmc, offline)" % pmc_name if traffic else None},
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, P, T)
-        print(json.dumps(out), flush=True)
-    edist.barrier()
 
 
 if __name__ == "__main__":

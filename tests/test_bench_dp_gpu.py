@@ -28,7 +28,7 @@ def test_bench_two_ranks_tiny_gloo(device):
     env = dict(os.environ, EMMAX_FORCE_DEVICE="0", EMMAX_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--tiny",
-           "--prompt-tokens", "24", "--new-tokens", "12"]
+           "--prompt-tokens", "24", "--new-tokens", "12", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -60,7 +60,7 @@ def test_bench_self_launch_two_ranks_tiny_gloo(device):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--tiny",
-           "--prompt-tokens", "24", "--new-tokens", "12", "--batch-per-gpu", "3"]
+           "--prompt-tokens", "24", "--new-tokens", "12", "--batch-per-gpu", "3", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -84,7 +84,7 @@ def test_bench_one_rank_rccl_singleton(device):
     env.pop("EMMAX_DIST_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--tiny",
-           "--prompt-tokens", "24", "--new-tokens", "12", "--batch-per-gpu", "3", "--no-cpu-baseline"]
+           "--prompt-tokens", "24", "--new-tokens", "12", "--batch-per-gpu", "3", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

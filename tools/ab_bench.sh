@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 for spec in "$@"; do
   set -- $spec
   label=$1; shift
-  envs=(); flags=()
+  envs=(); flags=(--full)
   for a in "$@"; do case $a in *=*) envs+=("$a");; *) flags+=("$a");; esac; done
   env "${envs[@]}" timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline "${flags[@]}" 2>&1 | tail -1 > gpurun_out/ab_$label.json
   python - "$label" <<'PY'

@@ -11,20 +11,20 @@ O=gpurun_out/prof_$ROUND; mkdir -p $O
 parts=${*:-bench rocprof variants stage serve gemm pmc pmcgemm pmcattn}
 for part in $parts; do
   case $part in
-    bench)    timeout 900 python bench.py --steps 50 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err ;;
-    rocprof)  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof -o bench -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/rocprof_bench.log 2>&1
+    bench)    timeout 900 python bench.py --steps 50 --warmup 5 --full > $O/bench_n1.json 2> $O/bench_n1.err ;;
+    rocprof)  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof -o bench -- python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline > $O/rocprof_bench.log 2>&1
               rm -f $O/rocprof/*/*kernel_trace.csv $O/rocprof/*kernel_trace.csv
-              timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof_exact -o bench -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --exact > $O/rocprof_bench_exact.log 2>&1
+              timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof_exact -o bench -- python bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --exact > $O/rocprof_bench_exact.log 2>&1
               rm -f $O/rocprof_exact/*/*kernel_trace.csv $O/rocprof_exact/*kernel_trace.csv
-              timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof_b32 -o bench -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --batch-per-gpu 32 > $O/rocprof_bench_b32.log 2>&1
+              timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof_b32 -o bench -- python bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --batch-per-gpu 32 > $O/rocprof_bench_b32.log 2>&1
               rm -f $O/rocprof_b32/*/*kernel_trace.csv $O/rocprof_b32/*kernel_trace.csv ;;
     variants) : > $O/bench_variants.jsonl
               for v in "--exact" "--exact-fp32kv" "--exact --graph" "--exact --batch-per-gpu 2" "--exact --batch-per-gpu 8" "--graph" "--batch-per-gpu 8" "--batch-per-gpu 16" "--batch-per-gpu 32" "--fp8" "--fp8 --batch-per-gpu 8" "--fp8 --batch-per-gpu 8 --graph" "--fp8 --batch-per-gpu 16" \
                        "--batch-per-gpu 8 --kv-fp8" "--batch-per-gpu 16 --kv-fp8" "--batch-per-gpu 32 --kv-fp8" "--fp8 --batch-per-gpu 8 --kv-fp8" "--fp8 --batch-per-gpu 16 --kv-fp8" \
                        "--batch-per-gpu 64" "--batch-per-gpu 64 --kv-fp8" "--fp8 --batch-per-gpu 32 --kv-fp8" "--fp8 --batch-per-gpu 64 --kv-fp8"; do
-                timeout 400 python bench.py --steps 2 --warmup 1 --no-cpu-baseline $v 2>/dev/null | tail -1 >> $O/bench_variants.jsonl
+                timeout 400 python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline $v 2>/dev/null | tail -1 >> $O/bench_variants.jsonl
               done
-              EMMAX_DIST_SINGLETON=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --steps 2 --warmup 1 --batch-per-gpu 8 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_rccl_singleton_b8.json ;;
+              EMMAX_DIST_SINGLETON=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --steps 2 --warmup 1 --batch-per-gpu 8 --full --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_rccl_singleton_b8.json ;;
     stage)    timeout 600 python tools/stage_bench.py 2>/dev/null | tail -1 > $O/stage_bench.json
               rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof_stage -o stage -- python tools/stage_bench.py --vision-batches 256 --prefill-batches 1,8 > $O/rocprof_stage.log 2>&1
               rm -f $O/rocprof_stage/*/*kernel_trace.csv $O/rocprof_stage/*kernel_trace.csv ;;
