@@ -310,6 +310,21 @@ struct FinishParams {
     int is_prefill;
 };
 int launch_decode_finish(const FinishParams& p, hipStream_t stream);
+// ---- sample.hip: seeded temperature / top-k / top-p sampling over fp32 logit rows (emmax_op_sample, include/emmax.h) ----
+#define EMMAX_SAMPLE_MAX_V 32768    // entries of one row: 1024 lanes x 32 registers
+struct SampleParams {
+    const float* logits;        // f32 [B, ld]
+    int ld, V;
+    const float* temperature;   // per row: 0 = greedy (argmax, lowest id on ties)
+    const int32_t* top_k;       // 0 = off
+    const float* top_p;         // 1 = off
+    const uint64_t* seed;
+    const uint32_t* subseq;
+    const int32_t* step;        // per-row Philox step
+    int32_t* tok_out;           // [B]
+    float* logprob_out;         // [B]: l_tok - logsumexp(l)
+};
+int launch_sample(const SampleParams& p, int B, hipStream_t stream);
 int launch_set_tokens(int32_t* cur_tok, const int32_t* toks, int B, int32_t* done, int32_t* stop_m, int32_t* stop_after, int32_t* max_new,
                       int budget, hipStream_t stream);
 

@@ -1975,6 +1975,18 @@ int emmax_profile_decode_stage(emmax_session* s, int stage, int reps, float* avg
 }
 
 // ---- single-kernel entry points --------------------------------------------------------------------------------------
+int emmax_op_sample(const float* logits, int ld, int B, int V, const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seed,
+                    const uint32_t* subseq, const int32_t* step, int32_t* tok_out, float* logprob_out, emmax_stream stream) {
+    if (!logits || !temperature || !top_k || !top_p || !seed || !subseq || !step || !tok_out || !logprob_out) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (B < 1 || V < 1 || V > EMMAX_SAMPLE_MAX_V || ld < V)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_sample: B %d (>= 1), V %d (1..%d), ld %d (>= V)", B, V, EMMAX_SAMPLE_MAX_V, ld);
+    SampleParams p;
+    memset(&p, 0, sizeof(p));
+    p.logits = logits; p.ld = ld; p.V = V; p.temperature = temperature; p.top_k = top_k; p.top_p = top_p; p.seed = seed; p.subseq = subseq;
+    p.step = step; p.tok_out = tok_out; p.logprob_out = logprob_out;
+    KCHK(launch_sample(p, B, (hipStream_t)stream));
+    return 0;
+}
 int emmax_op_gemm(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K, const void* bias, int act,
                   const void* scale, const void* residual, int ldr, int out_f32, emmax_stream st) {
     GemmParams p = gp(A, lda, W, ldw, C, ldc, M, N, K);

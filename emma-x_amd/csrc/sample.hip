@@ -1,0 +1,282 @@
+// sample.hip -- seeded temperature / top-k / top-p sampling over rows of fp32 logits (emmax_op_sample, include/emmax.h).
+//
+// One 1024-thread workgroup per row; the row (V <= 32768) sits in registers, 32 entries per lane as 8 groups of 4 consecutive ids
+// (entry i = 4 (g * 1024 + tid) + c), so one Philox4x32-10 call gives the noise of a lane's four entries.  Per row:
+//   1. row maximum and logsumexp of the raw logits (wave butterflies, then the 16 wave results in a fixed order): the log-probability
+//      l_tok - logsumexp(l) of the emitted token;
+//   2. temperature 0: the token is the argmax, lowest id on ties;
+//   3. z = l / T; top-k threshold = the k-th largest z, top-p threshold over the kept entries with integer masses
+//      W_i = floor(exp(z_i - max z) 2^32): both by one radix walk over the order-preserving uint32 key of z (8-bit digits, per-wave LDS
+//      histograms of 64-bit integer masses, integer atomics only -- the kept set does not depend on the order work arrives in);
+//   4. Gumbel-max over the kept entries: token = argmax z_i + g_i, g_i = -log(-log u_i), u_i from Philox4x32-10 with key = seed and
+//      counter (i / 4, step, subseq, 0) -- noise that depends on (seed, subseq, step, i) only, not on the row's place in the batch.
+// No float atomics anywhere: every reduction has a fixed order, and two launches on the same inputs agree bit for bit.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "common.h"
+#include "kernels.h"
+
+namespace {
+
+constexpr int ST = 1024;            // threads per row
+constexpr int SWV = ST / EMMAX_WAVE;
+constexpr int SG = EMMAX_SAMPLE_MAX_V / (4 * ST);   // groups of four entries per lane
+
+// order-preserving key: a < b  <=>  fkey(a) < fkey(b) (finite values and infinities)
+__device__ __forceinline__ uint32_t fkey(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants), counter c, key (k0, k1)
+__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        if (r) {
+            k0 += 0x9E3779B9u;
+            k1 += 0xBB67AE85u;
+        }
+        const uint32_t lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
+        const uint32_t lo1 = 0xCD9E8D57u * c[2], hi1 = __umulhi(0xCD9E8D57u, c[2]);
+        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
+    }
+}
+
+// g = -log(-log u), u = ((x >> 8) + 0.5) 2^-24.  -log u is evaluated on exactly representable floats: -logf(u) below 1/2,
+// -log1pf(-(1 - u)) above (u itself would round to 1 at the top of the range and give an infinite g)
+__device__ __forceinline__ float gumbel_of(uint32_t x) {
+    const uint32_t k = x >> 8;
+    const float e = (k < (1u << 23)) ? -logf((float)(2u * k + 1u) * 0x1p-25f) : -log1pf(-(float)((1u << 25) - 2u * k - 1u) * 0x1p-25f);
+    return -logf(e);
+}
+
+// top-p mass of an entry: floor(exp(z - max z) 2^32) (exact scaling by 2^32, truncating conversion)
+__device__ __forceinline__ unsigned long long mass_of(float z, float zmax) { return (unsigned long long)(expf(z - zmax) * 4294967296.0f); }
+
+__device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+struct SampleShared {
+    unsigned long long hist[SWV][256];
+    unsigned long long tot[256];
+    float rf[SWV];
+    int ri[SWV];
+    unsigned long long ru[SWV];
+    unsigned long long sel_a;
+    int sel_d;
+};
+
+// block reductions: wave butterfly (every lane of a wave ends with the same value), then the 16 wave values in wave order
+__device__ float block_max(float v, SampleShared& sh, int lane, int wave) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    if (lane == 0) sh.rf[wave] = v;
+    __syncthreads();
+    float r = sh.rf[0];
+#pragma unroll
+    for (int w = 1; w < SWV; ++w) r = fmaxf(r, sh.rf[w]);
+    __syncthreads();
+    return r;
+}
+__device__ float block_sum(float v, SampleShared& sh, int lane, int wave) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (lane == 0) sh.rf[wave] = v;
+    __syncthreads();
+    float r = sh.rf[0];
+#pragma unroll
+    for (int w = 1; w < SWV; ++w) r += sh.rf[w];
+    __syncthreads();
+    return r;
+}
+__device__ unsigned long long block_sum_u64(unsigned long long v, SampleShared& sh, int lane, int wave) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (lane == 0) sh.ru[wave] = v;
+    __syncthreads();
+    unsigned long long r = 0;
+#pragma unroll
+    for (int w = 0; w < SWV; ++w) r += sh.ru[w];
+    __syncthreads();
+    return r;
+}
+// (value, index) argmax, ties to the lowest index
+__device__ int block_argmax(float v, int i, SampleShared& sh, int lane, int wave) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(v, o);
+        const int oi = __shfl_xor(i, o);
+        if (better(ov, oi, v, i)) { v = ov; i = oi; }
+    }
+    if (lane == 0) { sh.rf[wave] = v; sh.ri[wave] = i; }
+    __syncthreads();
+    float bv = sh.rf[0];
+    int bi = sh.ri[0];
+#pragma unroll
+    for (int w = 1; w < SWV; ++w)
+        if (better(sh.rf[w], sh.ri[w], bv, bi)) { bv = sh.rf[w]; bi = sh.ri[w]; }
+    __syncthreads();
+    return bi;
+}
+
+// Radix walk over the keys of the entries with key >= lo (entry mass: 1, or floor(w 2^32) when MASS).  Returns the threshold key t:
+// the entries with key >= t are exactly those whose mass strictly above them, sum_{key_j > key_i} mass_j, is below `target`
+// (or zero: the maximum is always kept).  With unit masses and target k that is "key >= the k-th largest key" (ties kept).
+template <bool MASS>
+__device__ uint32_t radix_threshold(const float (&z)[SG * 4], float zmax, int tid, int V, uint32_t lo, double target,
+                                    SampleShared& sh, int lane, int wave) {
+    uint32_t prefix = 0, mask = 0;
+    unsigned long long above = 0;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        for (int j = lane; j < 256; j += EMMAX_WAVE) sh.hist[wave][j] = 0;
+        __syncthreads();
+#pragma unroll
+        for (int g = 0; g < SG; ++g)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int i = (g * ST + tid) * 4 + c;
+                const uint32_t key = fkey(z[g * 4 + c]);
+                if (i < V && key >= lo && (key & mask) == prefix) {
+                    const unsigned long long m = MASS ? mass_of(z[g * 4 + c], zmax) : 1ull;
+                    atomicAdd(&sh.hist[wave][(key >> shift) & 255u], m);
+                }
+            }
+        __syncthreads();
+        if (tid < 256) {
+            unsigned long long s = 0;
+#pragma unroll
+            for (int v = 0; v < SWV; ++v) s += sh.hist[v][tid];
+            sh.tot[tid] = s;
+        }
+        __syncthreads();
+        if (wave == 0) {   // lane l holds bins 4l .. 4l + 3; S(d) = mass in the bins above d
+            const unsigned long long c0 = sh.tot[4 * lane], c1 = sh.tot[4 * lane + 1], c2 = sh.tot[4 * lane + 2], c3 = sh.tot[4 * lane + 3];
+            const unsigned long long mine = c0 + c1 + c2 + c3;
+            unsigned long long incl = mine;   // inclusive suffix sum over lanes lane .. 63
+#pragma unroll
+            for (int o = 1; o < EMMAX_WAVE; o <<= 1) {
+                const unsigned long long t = __shfl_down(incl, o);
+                if (lane + o < EMMAX_WAVE) incl += t;
+            }
+            const unsigned long long up = above + (incl - mine);
+            const unsigned long long s3 = up, s2 = up + c3, s1 = s2 + c2, s0 = s1 + c1;
+            auto ok = [&](unsigned long long s) { return s == 0 || (double)s < target; };
+            // the satisfying bins are a top range (S falls as d rises): the lowest one of the lowest lane that has one
+            const int dl = ok(s0) ? 0 : ok(s1) ? 1 : ok(s2) ? 2 : ok(s3) ? 3 : -1;
+            const unsigned long long sd = dl == 0 ? s0 : dl == 1 ? s1 : dl == 2 ? s2 : s3;
+            const unsigned long long bal = __ballot(dl >= 0);
+            const int L = __ffsll((long long)bal) - 1;   // bin 255 always qualifies (S = the mass above the prefix, which qualified)
+            if (lane == L) {
+                sh.sel_d = 4 * lane + dl;
+                sh.sel_a = sd;
+            }
+        }
+        __syncthreads();
+        prefix |= (uint32_t)sh.sel_d << shift;
+        mask |= 255u << shift;
+        above = sh.sel_a;
+        __syncthreads();
+    }
+    return prefix;
+}
+
+__global__ __launch_bounds__(ST) void emmax_sample_kernel(SampleParams p) {
+    __shared__ SampleShared sh;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (EMMAX_WAVE - 1), wave = tid / EMMAX_WAVE;
+    const int V = p.V, step = p.step[b];
+    const float* row = p.logits + (size_t)b * p.ld;
+    const bool vec = ((uintptr_t)row & 15) == 0;
+    float z[SG * 4];
+#pragma unroll
+    for (int g = 0; g < SG; ++g) {
+        const int i0 = (g * ST + tid) * 4;
+        if (vec && i0 + 3 < V) {
+            const f32x4_t v = *(const f32x4_t*)(row + i0);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) z[g * 4 + c] = v[c];
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) z[g * 4 + c] = (i0 + c < V) ? row[i0 + c] : -INFINITY;
+        }
+    }
+    // logsumexp of the raw logits, fixed order
+    float mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < SG * 4; ++j) mx = fmaxf(mx, z[j]);
+    mx = block_max(mx, sh, lane, wave);
+    float se = 0.f;
+#pragma unroll
+    for (int j = 0; j < SG * 4; ++j) se += expf(z[j] - mx);
+    se = block_sum(se, sh, lane, wave);
+    const float lse = mx + logf(se);
+
+    const float T = p.temperature[b];
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    if (!(T > 0.f)) {   // greedy: argmax, lowest id on ties
+#pragma unroll
+        for (int g = 0; g < SG; ++g)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int i = (g * ST + tid) * 4 + c;
+                if (i < V && better(z[g * 4 + c], i, bv, bi)) { bv = z[g * 4 + c]; bi = i; }
+            }
+    } else {
+#pragma unroll
+        for (int j = 0; j < SG * 4; ++j) z[j] = z[j] / T;
+        const float zmax = mx / T;
+        const int k = p.top_k[b];
+        const float tp = p.top_p[b];
+        uint32_t thr = 0;   // kept: key(z) >= thr
+        if (k > 0 && k < V) thr = radix_threshold<false>(z, zmax, tid, V, 0u, (double)k, sh, lane, wave);
+        if (tp < 1.f) {
+            unsigned long long tot = 0;
+#pragma unroll
+            for (int g = 0; g < SG; ++g)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int i = (g * ST + tid) * 4 + c;
+                    if (i < V && fkey(z[g * 4 + c]) >= thr) tot += mass_of(z[g * 4 + c], zmax);
+                }
+            tot = block_sum_u64(tot, sh, lane, wave);
+            thr = radix_threshold<true>(z, zmax, tid, V, thr, (double)tp * (double)tot, sh, lane, wave);
+        }
+        // Gumbel-max over the kept entries; Philox only for groups with a kept entry
+        const uint32_t k0 = (uint32_t)p.seed[b], k1 = (uint32_t)(p.seed[b] >> 32), sub = p.subseq[b];
+#pragma unroll
+        for (int g = 0; g < SG; ++g) {
+            const int q = g * ST + tid;
+            bool any = false;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) any |= (4 * q + c < V) && fkey(z[g * 4 + c]) >= thr;
+            if (!any) continue;
+            uint32_t x[4] = {(uint32_t)q, (uint32_t)step, sub, 0u};
+            philox4x32_10(x, k0, k1);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int i = 4 * q + c;
+                if (i < V && fkey(z[g * 4 + c]) >= thr) {
+                    const float s = z[g * 4 + c] + gumbel_of(x[c]);
+                    if (better(s, i, bv, bi)) { bv = s; bi = i; }
+                }
+            }
+        }
+    }
+    const int tok = block_argmax(bv, bi, sh, lane, wave);
+    if (tid == 0) {
+        // (an all-NaN row keeps no entry: the token is -1, its log-probability NaN)
+        const bool ok = tok >= 0 && tok < V;
+        p.tok_out[b] = ok ? tok : -1;
+        p.logprob_out[b] = ok ? row[tok] - lse : __int_as_float(0x7fc00000);
+    }
+}
+
+}  // namespace
+
+int launch_sample(const SampleParams& p, int B, hipStream_t stream) {
+    if (B < 1 || p.V < 1 || p.V > EMMAX_SAMPLE_MAX_V || p.ld < p.V) return -1;
+    hipLaunchKernelGGL(emmax_sample_kernel, dim3(B), dim3(ST), 0, stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}

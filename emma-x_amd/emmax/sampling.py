@@ -1,0 +1,95 @@
+"""Seeded temperature / top-k / top-p sampling over rows of logits on the device (include/emmax.h: emmax_op_sample; the kernel:
+emma-x_amd/csrc/sample.hip).
+
+The defaults of SamplingParams are the HF GenerationConfig defaults (temperature 1.0, top-k 50, top-p 1.0).  A draw is reproducible
+from its (seed, subseq, step): the noise of token id i is word i % 4 of Philox4x32-10 with key = seed and counter (i / 4, step, subseq, 0),
+whatever the batch.  Temperature 0 is the argmax.  With the engine's cached step this makes a sampling loop::
+
+    toks, lps = sample_logits(engine.last_logits(), params, seeds, steps=[t] * B)
+    engine.set_current_tokens(toks.tolist()); engine.decode_step()
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import Optional, Sequence, Tuple, Union
+
+import torch
+
+from . import _lib
+
+_U64 = (1 << 64) - 1
+MAX_VOCAB = 32768   # EMMAX_SAMPLE_MAX_V (emma-x_amd/csrc/kernels.h): entries of one row
+
+
+@dataclass(frozen=True)
+class SamplingParams:
+    temperature: float = 1.0   # finite, >= 0; 0 = greedy (top_k / top_p ignored)
+    top_k: int = 50            # 0 = off
+    top_p: float = 1.0         # (0, 1]; 1 = off
+    seed: Optional[int] = None   # 64-bit; None = drawn from torch's default CPU generator (draw_seed)
+
+    def __post_init__(self):
+        t = float(self.temperature)
+        if not math.isfinite(t) or t < 0.0:
+            raise ValueError(f"temperature must be finite and >= 0, got {self.temperature}")
+        if int(self.top_k) != self.top_k or int(self.top_k) < 0:
+            raise ValueError(f"top_k must be an integer >= 0, got {self.top_k}")
+        p = float(self.top_p)
+        if not (0.0 < p <= 1.0):
+            raise ValueError(f"top_p must lie in (0, 1], got {self.top_p}")
+        if self.seed is not None and not (0 <= int(self.seed) <= _U64):
+            raise ValueError(f"seed must be a 64-bit unsigned integer, got {self.seed}")
+
+
+def draw_seed(generator: Optional[torch.Generator] = None) -> int:
+    """A 64-bit seed from `generator` (default: torch's global CPU generator, so torch.manual_seed(s) fixes it)."""
+    hi = int(torch.randint(0, 1 << 32, (1,), generator=generator, dtype=torch.int64))
+    lo = int(torch.randint(0, 1 << 32, (1,), generator=generator, dtype=torch.int64))
+    return (hi << 32) | lo
+
+
+def _per_row(v, B: int, what: str) -> list:
+    vals = list(v) if isinstance(v, (list, tuple, range)) else [v] * B
+    if len(vals) != B:
+        raise ValueError(f"{what}: {len(vals)} values for {B} rows")
+    return vals
+
+
+def sample_logits(logits: torch.Tensor, params: Union[SamplingParams, Sequence[SamplingParams]], seeds=None, subseqs=0, steps=0,
+                  generator: Optional[torch.Generator] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Draw one token per row of `logits` (fp32 [B, V] on the device, V <= 32768, rows contiguous) on the current stream.
+    params: one SamplingParams for all rows or one per row; seeds / subseqs / steps: one value for all rows or one per row (seeds default to
+    each row's SamplingParams.seed, else a draw from `generator`).  Returns (tokens int32 [B], log-probabilities fp32 [B]) on the device:
+    the log-probability is log_softmax(logits)[token] (T = 1, unfiltered)."""
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.device.type != "cuda":
+        raise ValueError("sample_logits: logits must be a 2-D float32 tensor on a HIP device")
+    B, V = logits.shape
+    if B < 1 or not 1 <= V <= MAX_VOCAB:
+        raise ValueError(f"sample_logits: {B} rows of {V} entries (1..{MAX_VOCAB})")
+    if logits.stride(1) != 1 or (B > 1 and logits.stride(0) < V):
+        logits = logits.contiguous()
+    ld = logits.stride(0) if B > 1 else V
+    ps = _per_row(params, B, "params")
+    if not all(isinstance(p, SamplingParams) for p in ps):
+        raise ValueError("sample_logits: params must be SamplingParams")
+    if seeds is None:
+        seeds = [p.seed if p.seed is not None else draw_seed(generator) for p in ps]
+    seeds = [int(s) & _U64 for s in _per_row(seeds, B, "seeds")]
+    subseqs = [int(s) & 0xFFFFFFFF for s in _per_row(subseqs, B, "subseqs")]
+    steps = [int(s) for s in _per_row(steps, B, "steps")]
+    if any(not 0 <= s < 1 << 31 for s in steps):
+        raise ValueError("sample_logits: steps must lie in 0 .. 2^31 - 1")
+    dev = logits.device
+    temp = torch.tensor([float(p.temperature) for p in ps], dtype=torch.float32).to(dev)
+    top_k = torch.tensor([min(int(p.top_k), V) for p in ps], dtype=torch.int32).to(dev)
+    top_p = torch.tensor([float(p.top_p) for p in ps], dtype=torch.float32).to(dev)
+    seed_t = torch.tensor([s - (1 << 64) if s >= 1 << 63 else s for s in seeds], dtype=torch.int64).to(dev)
+    sub_t = torch.tensor([s - (1 << 32) if s >= 1 << 31 else s for s in subseqs], dtype=torch.int32).to(dev)
+    step_t = torch.tensor(steps, dtype=torch.int32).to(dev)
+    tok = torch.empty(B, dtype=torch.int32, device=dev)
+    lp = torch.empty(B, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    _lib.check(lib.emmax_op_sample(logits.data_ptr(), ld, B, V, temp.data_ptr(), top_k.data_ptr(), top_p.data_ptr(), seed_t.data_ptr(),
+                                   sub_t.data_ptr(), step_t.data_ptr(), tok.data_ptr(), lp.data_ptr(), _lib.current_stream()), "emmax_op_sample")
+    return tok, lp

@@ -35,8 +35,9 @@ extern "C" {
 /* Bumped whenever emmax_config / emmax_tower_config change layout or an entry point changes signature.
  *   1: rounds 1-2;  2: emmax_config grew `decode_fp8` (round 2, not bumped then);  3: round 4 -- emmax_config_size / emmax_tuning_*
  *   added, the lab-only entry points (persistent layer chain, in-attention split merge) removed;  4: round 5 -- emmax_session_*_ex (staging rows
- *   are asked for, the plain calls give none), decode batches / slot counts up to 64 (emmax_model_max_decode_batch). */
-#define EMMAX_ABI_VERSION 5
+ *   are asked for, the plain calls give none), decode batches / slot counts up to 64 (emmax_model_max_decode_batch);  5: exact numerics (emmax_session_exact, emmax_op_x_*);
+ *   6: emmax_op_sample (seeded sampling over rows of logits). */
+#define EMMAX_ABI_VERSION 6
 
 typedef enum emmax_status {
     EMMAX_OK = 0,
@@ -232,6 +233,25 @@ int emmax_slots_state(emmax_session* s, int32_t* done_dev, int32_t* n_out_dev, e
 int emmax_slot_output(emmax_session* s, int slot, int32_t* ids_dev, int n, emmax_stream stream);
 /* Mark `slot` idle again (empty context: its share of a batched step then reads no K/V). */
 int emmax_slot_release(emmax_session* s, int slot, emmax_stream stream);
+
+/* ---- seeded sampling over rows of logits (ABI 6) --------------------------------------------------------------------
+ * emmax_op_sample draws one token per row of logits_dev [B][ld] (fp32, V <= 32768 entries, ld >= V) and returns it with its
+ * log-probability.  Per-row parameters and steps are device arrays of B entries.  The decode step itself stays greedy; a caller samples
+ * the rows of emmax_last_logits and feeds the tokens back with emmax_set_current_tokens (emmax/sampling.py: sample_logits).
+ *   temperature 0     greedy: the argmax, lowest id on ties (top_k / top_p ignored);
+ *   temperature T > 0 z = l / T (fp32); top_k > 0 keeps z_i >= the k-th largest z (ties kept); top_p < 1 then keeps, over those, the i with
+ *                     sum_{kept j, z_j > z_i} W_j < top_p * sum_{kept j} W_j, W_j = floor(exp(z_j - max z) 2^32) as 64-bit integers
+ *                     (the argmax always stays); token = argmax over the kept i of z_i + g_i (Gumbel-max: an exact draw from softmax(z)
+ *                     renormalised over the kept set), lowest id on ties;
+ *   noise             g_i = -log(-log u_i), u_i = ((x >> 8) + 0.5) 2^-24, x = word i % 4 of Philox4x32-10 with key (seed low, seed high
+ *                     32 bits) and counter (i / 4, step, subseq, 0).  Nothing else enters: not the row's place in the batch or B;
+ *   log-probability   l_tok - logsumexp(l) over the raw logits (T = 1, unfiltered): HF compute_transition_scores(normalize_logits=True).
+ * Every reduction has a fixed order and only integer atomics are used: the same inputs give the same bits.  An all-NaN row gives
+ * token -1.  EMMAX_ERR_INVALID for a null pointer, B < 1, V outside 1..32768 or ld < V.  The values of the parameter arrays are the
+ * caller's to check (emmax/sampling.py: SamplingParams): temperature finite and >= 0, 0 <= top_k, 0 < top_p <= 1. */
+int emmax_op_sample(const float* logits_dev, int ld, int B, int V, const float* temperature_dev, const int32_t* top_k_dev, const float* top_p_dev,
+                    const uint64_t* seed_dev, const uint32_t* subseq_dev, const int32_t* step_dev, int32_t* tok_out_dev, float* logprob_out_dev,
+                    emmax_stream stream);
 
 /* ---- single-kernel entry points (parity tests + micro-benchmarks) -------------------------------------------------- */
 /* C[M,N] = epilogue(A[M,K] @ W[N,K]^T): bf16 in, fp32 accumulate on MFMA.  K % 64 == 0, N % 128 == 0.
