@@ -122,6 +122,11 @@ struct CommitParams {
     int n, max_pages, max_out;
     int slot[EMMAX_MAX_DECODE_BATCH], src[EMMAX_MAX_DECODE_BATCH];
     int32_t *cur_tok, *ctx_len, *done, *n_out, *max_new, *stop_m, *stop_after, *out_ids, *page_table;
+    // sampling on (else all null): the rows' sampling parameters and their log-probability rows [][max_out] move with them
+    float *temperature, *top_p, *logprob;
+    int32_t* top_k;
+    uint64_t* seed;
+    uint32_t* subseq;
 };
 int launch_slots_commit(const CommitParams& c, hipStream_t stream);
 int launch_set_int(int32_t* p, int32_t v, hipStream_t stream);
@@ -310,6 +315,58 @@ struct FinishParams {
     int is_prefill;
 };
 int launch_decode_finish(const FinishParams& p, hipStream_t stream);
+// The bookkeeping of row b once its token is known (one thread; the greedy finish of decode.hip and the sampled finish of sample.hip both
+// end here): token budget, `ctx_len`, output row (cleared at a prefill), EOS / budget / stop rule / cache end, next current token.
+// lp_row (sampled finish only, else null): the row's log-probabilities beside out_ids, written at the token's place; stop_row: the row is
+// done after this token whatever it is (an all-NaN logit row in a sampled step).
+__device__ __forceinline__ void emmax_finish_row(const FinishParams& p, int b, int tok, float* lp_row, float lp, bool stop_row) {
+    int was_done = p.done[b];
+    int n = p.n_out[b];
+    const int budget_n = p.max_new_p[b];
+    if (!p.is_prefill && !was_done && n >= budget_n) {   // token budget already spent before this step
+        was_done = 1;
+        p.done[b] = 1;
+    }
+    if (!p.is_prefill && !was_done) p.ctx_len[b] += 1;   // the token consumed by this step now sits in the cache
+    if (p.is_prefill)   // fresh sequence: clear the output row
+        for (int i = 0; i < p.max_out; ++i) {
+            p.out_ids[(size_t)b * p.max_out + i] = p.pad_id;
+            if (lp_row) lp_row[i] = 0.f;
+        }
+    if (was_done) {
+        tok = p.pad_id;
+    } else {
+        if (n < p.max_out) {
+            p.out_ids[(size_t)b * p.max_out + n] = tok;
+            if (lp_row) lp_row[n] = lp;
+        }
+        n += 1;
+        p.n_out[b] = n;
+        // stop on EOS, on the token budget, or when the next append would overflow the cache
+        const bool budget = !p.is_prefill && n >= budget_n;
+        // early exit: n_after tokens after the trigger id sequence (e.g. "POLICIES:" + the 8 action-line tokens)
+        bool stop = false;
+        const int n_trig = p.stop_cfg[0];
+        if (n_trig > 0) {
+            int aft = p.stop_after[b];
+            if (aft >= 0) {
+                aft += 1;
+            } else {
+                int mp = p.stop_m[b];
+                mp = (tok == p.stop_ids[mp]) ? mp + 1 : ((tok == p.stop_ids[0]) ? 1 : 0);   // single-restart matcher
+                if (mp == n_trig) {
+                    aft = 0;
+                    mp = 0;
+                }
+                p.stop_m[b] = mp;
+            }
+            p.stop_after[b] = aft;
+            stop = aft >= 0 && aft >= p.stop_cfg[1];
+        }
+        if (tok == p.eos_id || budget || stop || p.ctx_len[b] + 1 >= p.max_ctx || stop_row) p.done[b] = 1;
+    }
+    p.cur_tok[b] = tok;
+}
 // ---- sample.hip: seeded temperature / top-k / top-p sampling over fp32 logit rows (emmax_op_sample, include/emmax.h) ----
 #define EMMAX_SAMPLE_MAX_V 32768    // entries of one row: 1024 lanes x 32 registers
 struct SampleParams {
@@ -325,6 +382,21 @@ struct SampleParams {
     float* logprob_out;         // [B]: l_tok - logsumexp(l)
 };
 int launch_sample(const SampleParams& p, int B, hipStream_t stream);
+// the finish of a SAMPLED step (sampling on, include/emmax.h: emmax_session_set_sampling): one 1024-thread block per row draws the row's
+// token from its fp32 logits exactly as emmax_sample_kernel does (step = the row's n_out: its generation index) and ends in
+// emmax_finish_row; done / idle rows draw nothing.  Replaces launch_decode_finish in a sampled step (same launch count).
+struct SampleFinishParams {
+    FinishParams f;             // rows f.B; part_val / part_idx / n_part unused
+    const float* logits;        // f32 [B, ld]: complete rows of the lm-head launch this finish follows
+    int ld, V;
+    const float* temperature;   // [B] (as SampleParams)
+    const int32_t* top_k;
+    const float* top_p;
+    const uint64_t* seed;
+    const uint32_t* subseq;
+    float* logprob;             // [B][f.max_out], beside f.out_ids
+};
+int launch_sample_finish(const SampleFinishParams& p, hipStream_t stream);
 int launch_set_tokens(int32_t* cur_tok, const int32_t* toks, int B, int32_t* done, int32_t* stop_m, int32_t* stop_after, int32_t* max_new,
                       int budget, hipStream_t stream);
 

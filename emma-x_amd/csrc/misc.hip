@@ -322,6 +322,8 @@ __global__ void emmax_slots_idle_kernel(int n, int32_t* cur_tok, int32_t* ctx_le
 __global__ __launch_bounds__(256) void emmax_slots_commit_kernel(CommitParams c) {
     const int i = blockIdx.x, src = c.src[i], dst = c.slot[i], tid = threadIdx.x;
     for (int k = tid; k < c.max_out; k += 256) c.out_ids[(size_t)dst * c.max_out + k] = c.out_ids[(size_t)src * c.max_out + k];
+    if (c.logprob)
+        for (int k = tid; k < c.max_out; k += 256) c.logprob[(size_t)dst * c.max_out + k] = c.logprob[(size_t)src * c.max_out + k];
     for (int k = tid; k < c.max_pages; k += 256) {
         const int32_t a = c.page_table[(size_t)src * c.max_pages + k], b = c.page_table[(size_t)dst * c.max_pages + k];
         c.page_table[(size_t)dst * c.max_pages + k] = a;
@@ -331,6 +333,10 @@ __global__ __launch_bounds__(256) void emmax_slots_commit_kernel(CommitParams c)
         c.cur_tok[dst] = c.cur_tok[src]; c.ctx_len[dst] = c.ctx_len[src]; c.n_out[dst] = c.n_out[src]; c.max_new[dst] = c.max_new[src];
         c.stop_m[dst] = c.stop_m[src]; c.stop_after[dst] = c.stop_after[src];
         c.done[dst] = c.done[src];
+        if (c.logprob) {
+            c.temperature[dst] = c.temperature[src]; c.top_k[dst] = c.top_k[src]; c.top_p[dst] = c.top_p[src];
+            c.seed[dst] = c.seed[src]; c.subseq[dst] = c.subseq[src];
+        }
         c.done[src] = 1; c.ctx_len[src] = 0;
     }
 }

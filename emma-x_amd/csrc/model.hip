@@ -343,7 +343,16 @@ struct emmax_session {
     // decode
     bf16 *dh, *dq, *datt, *dact;
     float* dh32;                // the decode step's residual stream in fp32 (tuning switch resid32; GemvParams::h32), [rows_total][H]
-    float *part, *part_val, *logits, *part_val2 /* lm-head argmax partials of a staged prefill */;
+    float *part, *part_val, *part_val2 /* lm-head argmax partials of a staged prefill */;
+    // SAMPLING (emmax_session_set_sampling; the sampled finish, sample.hip): per-row parameters of every row, staging rows included; the
+    // fp32 logit rows of every row an lm-head can emit into (a staged prefill's rows are its own: it runs beside the live step); the
+    // log-probability rows beside out_ids.  sampling = false: none of it is touched and a step launches what a greedy session launches
+    float* logits;              // f32 [rows_total][vocab]
+    float *samp_t, *samp_p, *logprob /* [rows_total][max_out] */;
+    int32_t* samp_k;
+    uint64_t* samp_seed;
+    uint32_t* samp_sub;
+    bool sampling = false;
     int32_t *part_idx2;
     int32_t *part_idx, *cur_tok, *ctx_len, *done, *n_out, *out_ids, *max_new_d /* [max_batch] */, *page_table;
     // EXACT NUMERICS (round 6; tuning switch `exact` at emmax_session_create): fp32 activations end to end.  x32a: the fp32 result of the GEMM
@@ -385,6 +394,7 @@ struct emmax_session {
     int last_step_graph = 0;   // the most recent decode step was a graph replay (what emmax_session_graph_active reports)
     hipEvent_t ev = nullptr;
     int graph_epoch = -1;      // emmax_tune().epoch the graph was captured under (a changed switch re-captures)
+    bool graph_sampling = false;   // the captured step ends in the sampled finish (the parameters are device words: a change re-captures nothing)
     hipStream_t own_stream = nullptr;   // used by emmax_generate when the caller's stream is the (uncapturable) legacy stream
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
     std::string graph_err;
@@ -461,7 +471,13 @@ static void plan_session(emmax_session* s, SBump& b) {
     s->part_idx = (int32_t*)b.take((int64_t)s->n_lm_blocks * Bd * 4);
     s->part_val2 = (float*)b.take((int64_t)s->n_lm_blocks * Bd * 4);
     s->part_idx2 = (int32_t*)b.take((int64_t)s->n_lm_blocks * Bd * 4);
-    s->logits = (float*)b.take((int64_t)Bd * m->vocab * 4);
+    s->logits = (float*)b.take((int64_t)Br * m->vocab * 4);
+    s->samp_t = (float*)b.take(Br * 4);
+    s->samp_p = (float*)b.take(Br * 4);
+    s->samp_k = (int32_t*)b.take(Br * 4);
+    s->samp_seed = (uint64_t*)b.take(Br * 8);
+    s->samp_sub = (uint32_t*)b.take(Br * 4);
+    s->logprob = (float*)b.take((int64_t)Br * s->max_out * 4);
     s->cur_tok = (int32_t*)b.take(Br * 4);
     s->ctx_len = (int32_t*)b.take(Br * 4);
     s->done = (int32_t*)b.take(Br * 4);
@@ -833,9 +849,19 @@ static float* vscale_of(emmax_session* s, int layer) { return kscale_of(s, layer
 static int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* logits_out, bool do_finish, hipStream_t st, int slot0 = 0);
 static int launch_finish_step(emmax_session* s, int B, bool is_prefill, int n_part, int slot0, hipStream_t st);
 
+// the per-row state of rows slot0 .. slot0 + B that a finish updates
+static void finish_rows(emmax_session* s, int B, bool is_prefill, int slot0, FinishParams& f) {
+    emmax_model* m = s->m;
+    f.B = B;
+    f.cur_tok = s->cur_tok + slot0; f.ctx_len = s->ctx_len + slot0; f.done = s->done + slot0; f.n_out = s->n_out + slot0;
+    f.out_ids = s->out_ids + (size_t)slot0 * s->max_out;
+    f.max_new_p = s->max_new_d + slot0; f.max_out = s->max_out; f.max_ctx = s->max_ctx;
+    f.stop_ids = s->stop_ids; f.stop_cfg = s->stop_cfg; f.stop_m = s->stop_m + slot0; f.stop_after = s->stop_after + slot0;
+    f.eos_id = m->cfg.eos_id; f.pad_id = m->cfg.pad_id; f.is_prefill = is_prefill ? 1 : 0;
+}
+
 // finish of a step over rows slot0 .. slot0 + B: argmax over the n_part lm-head partials, EOS / budget / stop rule, next token
 static int launch_finish_step(emmax_session* s, int B, bool is_prefill, int n_part, int slot0, hipStream_t st) {
-    emmax_model* m = s->m;
     FinishParams f;
     memset(&f, 0, sizeof(f));
     // the partial count is the grid the launch really used (every launcher reports it): a count modelled separately went
@@ -843,13 +869,22 @@ static int launch_finish_step(emmax_session* s, int B, bool is_prefill, int n_pa
     if (n_part <= 0 || n_part > s->n_lm_blocks) return fail(EMMAX_ERR_STATE, "lm-head launch reported no partial count");
     const bool stg = slot0 >= s->stg0;   // a staged prefill runs beside the live batch's decode steps: its own partial buffers
     f.part_val = stg ? s->part_val2 : s->part_val; f.part_idx = stg ? s->part_idx2 : s->part_idx; f.n_part = n_part;
-    f.B = B;
-    f.cur_tok = s->cur_tok + slot0; f.ctx_len = s->ctx_len + slot0; f.done = s->done + slot0; f.n_out = s->n_out + slot0;
-    f.out_ids = s->out_ids + (size_t)slot0 * s->max_out;
-    f.max_new_p = s->max_new_d + slot0; f.max_out = s->max_out; f.max_ctx = s->max_ctx;
-    f.stop_ids = s->stop_ids; f.stop_cfg = s->stop_cfg; f.stop_m = s->stop_m + slot0; f.stop_after = s->stop_after + slot0;
-    f.eos_id = m->cfg.eos_id; f.pad_id = m->cfg.pad_id; f.is_prefill = is_prefill ? 1 : 0;
+    finish_rows(s, B, is_prefill, slot0, f);
     KCHK(launch_decode_finish(f, st));
+    return 0;
+}
+
+// finish of a SAMPLED step over rows slot0 .. slot0 + B: each row's draw from its complete fp32 logit row (the lm-head launch just before
+// wrote them, on the same stream), then the same bookkeeping
+static int launch_sampled_finish_step(emmax_session* s, int B, bool is_prefill, int slot0, const float* logits, hipStream_t st) {
+    SampleFinishParams p;
+    memset(&p, 0, sizeof(p));
+    finish_rows(s, B, is_prefill, slot0, p.f);
+    p.logits = logits; p.ld = s->m->vocab; p.V = s->m->vocab;
+    p.temperature = s->samp_t + slot0; p.top_k = s->samp_k + slot0; p.top_p = s->samp_p + slot0;
+    p.seed = s->samp_seed + slot0; p.subseq = s->samp_sub + slot0;
+    p.logprob = s->logprob + (size_t)slot0 * s->max_out;
+    KCHK(launch_sample_finish(p, st));
     return 0;
 }
 
@@ -863,10 +898,14 @@ static int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* log
         if (r) return r;
         return run_lm_head_step(s, B - chunk, is_prefill, logits_out ? logits_out + (size_t)chunk * m->vocab : nullptr, do_finish, st, slot0 + chunk);
     }
+    // sampling on: a step's lm-head also writes the fp32 logit rows of its B rows, and the sampled finish draws from them
+    const bool sampled = do_finish && s->sampling;
+    if (sampled) logits_out = s->logits + (size_t)slot0 * m->vocab;
     GemvParams p;
     lmhead_params(s, slot0, logits_out, p);
     int lm_grid = 0;
     KCHK(launch_proj(GEMV_LMHEAD, p, m->lm_head, m->lm_head_fm, B, st, &lm_grid, m->lm_head_sc, m->lm_head_r8, F8_LMHEAD, m->lm_head_fm, m->lm_head_sc));
+    if (sampled) return launch_sampled_finish_step(s, B, is_prefill, slot0, logits_out, st);
     if (do_finish) return launch_finish_step(s, B, is_prefill, lm_grid, slot0, st);
     return 0;
 }
@@ -1236,7 +1275,8 @@ static int ensure_graph(emmax_session* s, int B, hipStream_t st) {
     // cannot be kept free).
     s->last_step_graph = 0;   // set again by launch_graph_step when a replay really runs
     if (!emmax_tune().graph) return 1;   // eager step: a captured graph stays valid for the next caller that wants replay
-    if (s->graph_exec && s->graph_B == B && s->graph_stream_cap == st && s->graph_epoch == emmax_tune().epoch) return 0;
+    if (s->graph_exec && s->graph_B == B && s->graph_stream_cap == st && s->graph_epoch == emmax_tune().epoch && s->graph_sampling == s->sampling)
+        return 0;
     drop_graph(s);
     if (s->graph_failed) return 1;
     hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
@@ -1255,6 +1295,7 @@ static int ensure_graph(emmax_session* s, int B, hipStream_t st) {
         return graph_fail(s, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
     }
     s->graph = g; s->graph_exec = ge; s->graph_B = B; s->graph_stream_cap = st; s->graph_epoch = emmax_tune().epoch;
+    s->graph_sampling = s->sampling;
     return 0;
 }
 
@@ -1873,6 +1914,10 @@ int emmax_slots_commit(emmax_session* s, const int32_t* staged_idx_host, const i
     c.n = n; c.max_pages = s->max_pages; c.max_out = s->max_out;
     c.cur_tok = s->cur_tok; c.ctx_len = s->ctx_len; c.done = s->done; c.n_out = s->n_out; c.max_new = s->max_new_d;
     c.stop_m = s->stop_m; c.stop_after = s->stop_after; c.out_ids = s->out_ids; c.page_table = s->page_table;
+    if (s->sampling) {
+        c.temperature = s->samp_t; c.top_k = s->samp_k; c.top_p = s->samp_p; c.seed = s->samp_seed; c.subseq = s->samp_sub;
+        c.logprob = s->logprob;
+    }
     hipStream_t user = (hipStream_t)stream, st;
     int r = slot_enter(s, user, &st);
     if (r) return r;
@@ -1928,6 +1973,99 @@ int emmax_slot_release(emmax_session* s, int slot, emmax_stream stream) {
     if (r) return r;
     KCHK(launch_slots_idle(1, s->cur_tok + slot, s->ctx_len + slot, s->done + slot, s->n_out + slot, s->m->cfg.pad_id, st));
     s->S[slot] = 0;
+    return slot_leave(s, user, st);
+}
+
+// ---- sampling in the decode step (ABI 7) ------------------------------------------------------------------------------
+// rows r0 .. r0 + n of the session (decode rows, or the staging rows from stg0): host values checked here, uploaded through the pinned
+// words 2112.. (emmax_session_set_stop uses 2048 .. 2065, the done read-back of emmax_generate the first 64)
+static int set_sampling_rows(emmax_session* s, int r0, int n, const float* T, const int32_t* top_k, const float* top_p, const uint64_t* seed,
+                             const uint32_t* subseq, hipStream_t st) {
+    if (s->m->vocab > EMMAX_SAMPLE_MAX_V) return fail(EMMAX_ERR_INVALID, "sampling takes vocabularies of up to %d entries (%d)", EMMAX_SAMPLE_MAX_V, s->m->vocab);
+    for (int i = 0; i < n; ++i) {
+        if (!std::isfinite(T[i]) || T[i] < 0.f) return fail(EMMAX_ERR_INVALID, "row %d: temperature %g (finite and >= 0)", r0 + i, (double)T[i]);
+        if (top_k[i] < 0) return fail(EMMAX_ERR_INVALID, "row %d: top_k %d (>= 0)", r0 + i, top_k[i]);
+        if (!(top_p[i] > 0.f && top_p[i] <= 1.f)) return fail(EMMAX_ERR_INVALID, "row %d: top_p %g (0 < top_p <= 1)", r0 + i, (double)top_p[i]);
+    }
+    char* h = (char*)(s->pinned + 2112);
+    HIPCHK(hipStreamSynchronize(st));   // the pinned staging words may still feed an earlier upload
+    for (int c0 = 0; c0 < n; c0 += 256) {
+        const int c = std::min(256, n - c0);
+        float* hT = (float*)h;
+        int32_t* hk = (int32_t*)(h + 1024);
+        float* hp = (float*)(h + 2048);
+        uint32_t* hs = (uint32_t*)(h + 3072);
+        uint64_t* hseed = (uint64_t*)(h + 4096);
+        for (int i = 0; i < c; ++i) {
+            hT[i] = T[c0 + i]; hk[i] = top_k[c0 + i]; hp[i] = top_p[c0 + i]; hs[i] = subseq[c0 + i]; hseed[i] = seed[c0 + i];
+        }
+        const int r = r0 + c0;
+        HIPCHK(hipMemcpyAsync(s->samp_t + r, hT, c * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(s->samp_k + r, hk, c * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(s->samp_p + r, hp, c * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(s->samp_sub + r, hs, c * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(s->samp_seed + r, hseed, c * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    s->sampling = true;
+    return 0;
+}
+
+int emmax_session_set_sampling(emmax_session* s, int row0, int n, const float* temperature_host, const int32_t* top_k_host, const float* top_p_host,
+                               const uint64_t* seed_host, const uint32_t* subseq_host, emmax_stream stream) {
+    if (!s || !temperature_host || !top_k_host || !top_p_host || !seed_host || !subseq_host) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (n < 1 || row0 < 0 || row0 + n > s->max_batch) return fail(EMMAX_ERR_INVALID, "rows %d..%d outside 0..%d", row0, row0 + n - 1, s->max_batch - 1);
+    hipStream_t user = (hipStream_t)stream, st;
+    int r = slot_enter(s, user, &st);
+    if (r) return r;
+    r = set_sampling_rows(s, row0, n, temperature_host, top_k_host, top_p_host, seed_host, subseq_host, st);
+    if (r) return r;
+    return slot_leave(s, user, st);
+}
+
+int emmax_slots_set_sampling_staged(emmax_session* s, int n, const float* temperature_host, const int32_t* top_k_host, const float* top_p_host,
+                                    const uint64_t* seed_host, const uint32_t* subseq_host, emmax_stream stream) {
+    if (!s || !temperature_host || !top_k_host || !top_p_host || !seed_host || !subseq_host) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (n < 1 || n > s->n_stg) return fail(EMMAX_ERR_INVALID, "%d staged requests outside 1..%d (the session's staging rows)", n, s->n_stg);
+    hipStream_t user = (hipStream_t)stream, st;
+    int r = slot_enter(s, user, &st);
+    if (r) return r;
+    r = set_sampling_rows(s, s->stg0, n, temperature_host, top_k_host, top_p_host, seed_host, subseq_host, st);
+    if (r) return r;
+    return slot_leave(s, user, st);
+}
+
+int emmax_session_clear_sampling(emmax_session* s, emmax_stream stream) {
+    (void)stream;
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    s->sampling = false;
+    return 0;
+}
+
+int emmax_session_sampling(const emmax_session* s) { return s ? (s->sampling ? 1 : 0) : -1; }
+
+int emmax_session_logprobs(emmax_session* s, int max_new, float* out_dev, emmax_stream stream) {
+    if (!s || !out_dev) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->sampling) return fail(EMMAX_ERR_STATE, "log-probabilities exist in a sampling session only (emmax_session_set_sampling)");
+    if (!s->prefilled) return fail(EMMAX_ERR_STATE, "no generation has run");
+    if (max_new < 1 || max_new > s->max_out) return fail(EMMAX_ERR_INVALID, "max_new_tokens %d outside 1..%d", max_new, s->max_out);
+    hipStream_t user = (hipStream_t)stream, st;
+    int r = slot_enter(s, user, &st);
+    if (r) return r;
+    HIPCHK(hipMemcpy2DAsync(out_dev, (size_t)max_new * 4, s->logprob, (size_t)s->max_out * 4, (size_t)max_new * 4, s->cur_B,
+                            hipMemcpyDeviceToDevice, st));
+    return slot_leave(s, user, st);
+}
+
+int emmax_slot_logprobs(emmax_session* s, int slot, float* out_dev, int n, emmax_stream stream) {
+    if (!s || !out_dev) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->sampling) return fail(EMMAX_ERR_STATE, "log-probabilities exist in a sampling session only (emmax_session_set_sampling)");
+    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slot_logprobs before emmax_slots_open");
+    if (slot < 0 || slot >= s->cur_B || n < 0 || n > s->max_out) return fail(EMMAX_ERR_INVALID, "slot %d / %d values out of range", slot, n);
+    hipStream_t user = (hipStream_t)stream, st;
+    int r = slot_enter(s, user, &st);
+    if (r) return r;
+    if (n > 0) HIPCHK(hipMemcpyAsync(out_dev, s->logprob + (size_t)slot * s->max_out, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     return slot_leave(s, user, st);
 }
 

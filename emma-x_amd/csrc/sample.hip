@@ -15,6 +15,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -182,11 +184,28 @@ __device__ uint32_t radix_threshold(const float (&z)[SG * 4], float zmax, int ti
     return prefix;
 }
 
-__global__ __launch_bounds__(ST) void emmax_sample_kernel(SampleParams p) {
+// the Philox step of row b: the caller's (emmax_op_sample), or the row's generation index n_out (the finish of a sampled decode step: 0 for
+// the token a prefill emits)
+__device__ __forceinline__ int row_step(const SampleParams& p, int b) { return p.step[b]; }
+__device__ __forceinline__ int row_step(const SampleFinishParams& p, int b) { return p.f.n_out[b]; }
+
+// One kernel body for both uses, so the draw exists once: P = SampleParams is emmax_op_sample (token and log-probability out); P =
+// SampleFinishParams is the finish of a sampled step (kernels.h), whose row then ends in the bookkeeping every finish shares.  (A template
+// kernel rather than a shared device function: inlining the draw into two kernels raised the spills of this one from 75 to 88 VGPRs.)
+template <class P>
+__global__ __launch_bounds__(ST) void emmax_sample_kernel(P p) {
+    constexpr bool FIN = std::is_same<P, SampleFinishParams>::value;
     __shared__ SampleShared sh;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (EMMAX_WAVE - 1), wave = tid / EMMAX_WAVE;
-    const int V = p.V, step = p.step[b];
+    const int V = p.V, step = row_step(p, b);
     const float* row = p.logits + (size_t)b * p.ld;
+    if constexpr (FIN) {   // a row that is done, idle or out of budget reads no logits and draws nothing (block-uniform: one word per row)
+        const FinishParams& f = p.f;
+        if (!f.is_prefill && (f.done[b] != 0 || step >= f.max_new_p[b])) {
+            if (tid == 0) emmax_finish_row(f, b, f.pad_id, p.logprob + (size_t)b * f.max_out, 0.f, false);
+            return;
+        }
+    }
     const bool vec = ((uintptr_t)row & 15) == 0;
     float z[SG * 4];
 #pragma unroll
@@ -266,10 +285,16 @@ __global__ __launch_bounds__(ST) void emmax_sample_kernel(SampleParams p) {
     }
     const int tok = block_argmax(bv, bi, sh, lane, wave);
     if (tid == 0) {
-        // (an all-NaN row keeps no entry: the token is -1, its log-probability NaN)
+        // (an all-NaN row keeps no entry: the token is -1, its log-probability NaN.  In a step -1 never reaches cur_tok, whose row the next
+        // step's embedding gather reads: the row emits pad and is done)
         const bool ok = tok >= 0 && tok < V;
-        p.tok_out[b] = ok ? tok : -1;
-        p.logprob_out[b] = ok ? row[tok] - lse : __int_as_float(0x7fc00000);
+        const float lp = ok ? row[tok] - lse : __int_as_float(0x7fc00000);
+        if constexpr (FIN) {
+            emmax_finish_row(p.f, b, ok ? tok : p.f.pad_id, p.logprob + (size_t)b * p.f.max_out, lp, !ok);
+        } else {
+            p.tok_out[b] = ok ? tok : -1;
+            p.logprob_out[b] = lp;
+        }
     }
 }
 
@@ -277,6 +302,12 @@ __global__ __launch_bounds__(ST) void emmax_sample_kernel(SampleParams p) {
 
 int launch_sample(const SampleParams& p, int B, hipStream_t stream) {
     if (B < 1 || p.V < 1 || p.V > EMMAX_SAMPLE_MAX_V || p.ld < p.V) return -1;
-    hipLaunchKernelGGL(emmax_sample_kernel, dim3(B), dim3(ST), 0, stream, p);
+    hipLaunchKernelGGL(emmax_sample_kernel<SampleParams>, dim3(B), dim3(ST), 0, stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+int launch_sample_finish(const SampleFinishParams& p, hipStream_t stream) {
+    if (p.f.B < 1 || p.V < 1 || p.V > EMMAX_SAMPLE_MAX_V || p.ld < p.V) return -1;
+    hipLaunchKernelGGL(emmax_sample_kernel<SampleFinishParams>, dim3(p.f.B), dim3(ST), 0, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }

@@ -43,7 +43,7 @@ class ConfigC(C.Structure):
     ]
 
 
-ABI_VERSION = 6   # EMMAX_ABI_VERSION of include/emmax.h this binding was written against
+ABI_VERSION = 7   # EMMAX_ABI_VERSION of include/emmax.h this binding was written against
 
 # name -> (restype, argtypes): exactly the entry points of include/emmax.h
 SIGNATURES = {
@@ -121,6 +121,12 @@ SIGNATURES = {
     "emmax_op_x_join": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
     "emmax_op_x_decode_attention": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _vp]),
     "emmax_op_sample": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "emmax_session_set_sampling": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "emmax_slots_set_sampling_staged": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "emmax_session_clear_sampling": (C.c_int, [_vp, _vp]),
+    "emmax_session_sampling": (C.c_int, [_vp]),
+    "emmax_session_logprobs": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "emmax_slot_logprobs": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -275,14 +275,65 @@ class EmmaxEngine:
         _lib.check(self.lib.emmax_set_current_tokens(self._session, t.data_ptr(), _lib.current_stream()), "emmax_set_current_tokens")
         torch.cuda.current_stream().synchronize()   # `t` must outlive the copy
 
-    def generate(self, max_new_tokens: int, stop_on_eos: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Greedy loop after prefill. Returns (ids int32 [B,max_new] padded with pad_id, lens int32 [B]) on device."""
+    def generate(self, max_new_tokens: int, stop_on_eos: bool = True, return_logprobs: bool = False):
+        """The decode loop after prefill: greedy, or sampled per row once set_sampling ran.  Returns (ids int32 [B,max_new] padded with pad_id,
+        lens int32 [B]) on device; with return_logprobs (sampling on only) also the fp32 [B,max_new] log-probabilities of the emitted tokens."""
         B = self._last_B
         out = torch.empty(B, max_new_tokens, dtype=torch.int32, device=self.device)
         lens = torch.empty(B, dtype=torch.int32, device=self.device)
         _lib.check(self.lib.emmax_generate(self._session, max_new_tokens, int(stop_on_eos), out.data_ptr(), lens.data_ptr(),
                                            _lib.current_stream()), "emmax_generate")
-        return out, lens
+        if not return_logprobs:
+            return out, lens
+        lp = torch.empty(B, max_new_tokens, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.emmax_session_logprobs(self._session, max_new_tokens, lp.data_ptr(), _lib.current_stream()), "emmax_session_logprobs")
+        return out, lens, lp
+
+    # ---- sampling inside the decode step (include/emmax.h, ABI 7) -------------------------------------------------------
+    @staticmethod
+    def _sampling_arrays(params, seeds, subseqs, n: Optional[int] = None, generator=None):
+        """Host arrays (temperature, top_k, top_p, seed, subseq) of len(params) rows: one SamplingParams for all rows needs `n`.  Seeds default
+        to each SamplingParams.seed, else draw_seed(generator); subseqs default to the row index."""
+        from .sampling import SamplingParams, _per_row, draw_seed
+
+        ps = _per_row(params, n if n is not None else (len(params) if isinstance(params, (list, tuple)) else 1), "params")
+        if not all(isinstance(p, SamplingParams) for p in ps):
+            raise ValueError("set_sampling: params must be SamplingParams")
+        k = len(ps)
+        if seeds is None:
+            seeds = [p.seed if p.seed is not None else draw_seed(generator) for p in ps]
+        seeds = [int(x) & ((1 << 64) - 1) for x in _per_row(seeds, k, "seeds")]
+        subseqs = list(range(k)) if subseqs is None else [int(x) & 0xFFFFFFFF for x in _per_row(subseqs, k, "subseqs")]
+        return (k, (C.c_float * k)(*[float(p.temperature) for p in ps]), (C.c_int32 * k)(*[int(p.top_k) for p in ps]),
+                (C.c_float * k)(*[float(p.top_p) for p in ps]), (C.c_uint64 * k)(*seeds), (C.c_uint32 * k)(*subseqs))
+
+    def set_sampling(self, params, seeds=None, subseqs=None, row0: int = 0, n: Optional[int] = None, generator=None) -> None:
+        """Sample rows row0.. in the decode step from now on (turns sampling on): one SamplingParams per row (or one for `n` rows), seeds
+        (default: each params' seed, else drawn from `generator`), subseqs (default: 0, 1, ... in row order).  Precedes the prefill whose
+        first token it governs."""
+        k, T, tk, tp, sd, sb = self._sampling_arrays(params, seeds, subseqs, n, generator)
+        _lib.check(self.lib.emmax_session_set_sampling(self._session, int(row0), k, T, tk, tp, sd, sb, _lib.current_stream()),
+                   "emmax_session_set_sampling")
+
+    def set_sampling_staged(self, params, seeds=None, subseqs=None, n: Optional[int] = None, generator=None) -> None:
+        """set_sampling for the requests of the next slots_prefill_staged (call inside `with engine.admission():`, before it)."""
+        k, T, tk, tp, sd, sb = self._sampling_arrays(params, seeds, subseqs, n, generator)
+        _lib.check(self.lib.emmax_slots_set_sampling_staged(self._session, k, T, tk, tp, sd, sb, _lib.current_stream()),
+                   "emmax_slots_set_sampling_staged")
+
+    def clear_sampling(self) -> None:
+        """Greedy again: the session launches exactly the kernels of one that never sampled."""
+        _lib.check(self.lib.emmax_session_clear_sampling(self._session, _lib.current_stream()), "emmax_session_clear_sampling")
+
+    @property
+    def sampling(self) -> bool:
+        return self.lib.emmax_session_sampling(self._session) == 1
+
+    def slot_logprobs(self, slot: int, n: int) -> List[float]:
+        """Log-probabilities of the first n tokens of `slot` (sampling on)."""
+        out = torch.empty(max(1, n), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.emmax_slot_logprobs(self._session, int(slot), out.data_ptr(), int(n), _lib.current_stream()), "emmax_slot_logprobs")
+        return out[:n].cpu().tolist()
 
     # ---- early exit + slot serving (include/emmax.h "slot serving") ----------------------------------------------------
     def set_stop(self, trigger_ids: Sequence[int] = (), n_after: int = 0) -> None:

@@ -27,6 +27,7 @@ from .config import EmmaXConfig, default_norm_stats
 from .engine import EmmaxEngine
 from .policy_parser import Solver
 from .processing import BatchFeature, EmmaXImageProcessor
+from .sampling import SamplingParams, draw_seed
 from .prompting import PurePromptBuilder
 from .tokenizer_stub import StubTokenizer
 from .weights import load_hf_state_dict, remap_native_state_dict, synthetic_state_dict, validate_state_dict
@@ -219,7 +220,7 @@ class EmmaXForActionPrediction:
             pixel_values = torch.cat([pixel_values["dino"], pixel_values["siglip"]], dim=1)
         return eng.vision_encode_pixels(pixel_values)
 
-    def _prefill(self, rows: List[List[int]], pixel_values=None, frames_u8=None, max_new: int = 0) -> torch.Tensor:
+    def _prefill(self, rows: List[List[int]], pixel_values=None, frames_u8=None, max_new: int = 0, sampling=None) -> torch.Tensor:
         eng = self._need_engine()
         B = len(rows)
         src = pixel_values if pixel_values is not None else frames_u8
@@ -232,8 +233,32 @@ class EmmaXForActionPrediction:
             P = self.config.llm.max_position
         eng.ensure_capacity(B, P, max(max_new, 1))
         patches = self._encode_images(pixel_values, frames_u8)
+        self._set_sampling(eng, B, sampling)
         eng.prefill(rows, patches)
         return patches
+
+    @staticmethod
+    def _set_sampling(eng, B: int, sampling) -> None:
+        """Before a prefill: sampling = one SamplingParams for every row or one per row (row b draws with subseq b; a params without a seed
+        gets one from draw_seed), None = greedy -- which also clears what an earlier sampled call left in the session."""
+        if sampling is not None:
+            eng.set_sampling(sampling, n=B)
+        elif getattr(eng, "sampling", False):
+            eng.clear_sampling()
+
+    @staticmethod
+    def _sampling_args(do_sample: bool, temperature=None, top_k=None, top_p=None, seed=None, generator=None) -> Optional[SamplingParams]:
+        """HF generate's sampling arguments -> the SamplingParams every row draws with (None: greedy).  Unset values take the HF defaults
+        (temperature 1.0, top_k 50, top_p 1.0; top_k 0 = off); seed None = draw_seed(generator), so torch.manual_seed fixes a call.  Greedy
+        calls consume no torch RNG."""
+        if not do_sample:
+            return None
+        t = 1.0 if temperature is None else float(temperature)
+        if not t > 0.0:
+            raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float when do_sample=True")
+        p = SamplingParams(temperature=t, top_k=50 if top_k is None else top_k, top_p=1.0 if top_p is None else top_p,
+                           seed=seed)   # (validates top_k / top_p / seed)
+        return p if seed is not None else SamplingParams(p.temperature, p.top_k, p.top_p, draw_seed(generator))
 
     def forward(self, input_ids=None, attention_mask=None, pixel_values=None, labels=None, inputs_embeds=None,
                 past_key_values=None, use_cache=None, output_attentions=None, output_hidden_states=None,
@@ -282,11 +307,15 @@ class EmmaXForActionPrediction:
 
     @torch.inference_mode()
     def generate_ids(self, rows: List[List[int]], pixel_values=None, frames_u8=None, max_new_tokens: int = 512,
-                     stop_on_eos: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Greedy decode for every row. Returns device tensors (new_ids int32 [B,max_new] pad-filled, lens int32 [B])."""
+                     stop_on_eos: bool = True, sampling=None, return_logprobs: bool = False):
+        """Decode every row: greedy, or sampled in the step with `sampling` (one SamplingParams for all rows or one per row; row b draws
+        with subseq b).  Returns device tensors (new_ids int32 [B,max_new] pad-filled, lens int32 [B]), and with return_logprobs (sampling
+        only) the fp32 [B,max_new] log-probabilities of the emitted tokens."""
         eng = self._need_engine()
-        self._prefill(rows, pixel_values, frames_u8, max_new=max_new_tokens)
-        return eng.generate(max_new_tokens, stop_on_eos)
+        if return_logprobs and sampling is None:
+            raise ValueError("return_logprobs needs sampling (log-probabilities are kept by the sampled step only)")
+        self._prefill(rows, pixel_values, frames_u8, max_new=max_new_tokens, sampling=sampling)
+        return eng.generate(max_new_tokens, stop_on_eos, return_logprobs=return_logprobs)
 
     def _max_new(self, rows, max_new_tokens, max_length, min_length, had_max_new: bool = True) -> int:
         """HF length semantics: `max_length` counts the PROMPT too (as HF counts it: the text ids, not the patch rows) and only
@@ -304,15 +333,18 @@ class EmmaXForActionPrediction:
 
     @torch.inference_mode()
     def generate(self, input_ids=None, pixel_values=None, attention_mask=None, max_new_tokens: Optional[int] = None, do_sample: bool = False,
-                 min_length: int = 1, temperature: float = 0.0, frames_u8=None, **kwargs) -> torch.Tensor:
-        """HF-style: returns LongTensor [B, P + T] = prompt ++ generated (right-padded with pad_token_id)."""
-        if do_sample:
-            raise NotImplementedError("only greedy decoding (do_sample=False) is on the hot path")
+                 min_length: int = 1, temperature: Optional[float] = None, frames_u8=None, top_k: Optional[int] = None,
+                 top_p: Optional[float] = None, seed: Optional[int] = None, generator: Optional[torch.Generator] = None,
+                 **kwargs) -> torch.Tensor:
+        """HF-style: returns LongTensor [B, P + T] = prompt ++ generated (right-padded with pad_token_id).  do_sample=True draws every token
+        in the decode step (include/emmax.h: emmax_session_set_sampling) with temperature / top_k / top_p (HF defaults 1.0 / 50 / 1.0 when
+        unset); row b draws with (seed, subseq b), seed None = draw_seed(generator)."""
         if kwargs.get("num_beams", 1) != 1:
             raise NotImplementedError("beam search is outside the hot path")
+        sampling = self._sampling_args(do_sample, temperature, top_k, top_p, seed, generator)
         rows = self._rows(input_ids, attention_mask)
         max_new_tokens = self._max_new(rows, max_new_tokens, kwargs.get("max_length"), min_length)
-        new_ids, lens = self.generate_ids(rows, pixel_values, frames_u8, max_new_tokens)
+        new_ids, lens = self.generate_ids(rows, pixel_values, frames_u8, max_new_tokens, sampling=sampling)
         new_ids, lens = new_ids.cpu(), lens.cpu().tolist()
         T = max(lens)
         P = max(len(r) for r in rows)
@@ -334,7 +366,12 @@ class EmmaXForActionPrediction:
         if rows[0][-1] != PREFIX_TOKEN_ID:
             rows[0] = rows[0] + [PREFIX_TOKEN_ID]
         dim = self.get_action_dim(unnorm_key)
-        new_ids, lens = self.generate_ids(rows, kwargs.get("pixel_values"), kwargs.get("frames_u8"), max_new_tokens=dim)
+        if kwargs.get("num_beams", 1) != 1:
+            raise NotImplementedError("beam search is outside the hot path")
+        # the reference forwards **kwargs to HF generate (modeling_prismatic.py:519): do_sample / temperature / top_k / top_p are honoured
+        sampling = self._sampling_args(bool(kwargs.get("do_sample", False)), kwargs.get("temperature"), kwargs.get("top_k"), kwargs.get("top_p"),
+                                       kwargs.get("seed"), kwargs.get("generator"))
+        new_ids, lens = self.generate_ids(rows, kwargs.get("pixel_values"), kwargs.get("frames_u8"), max_new_tokens=dim, sampling=sampling)
         full = rows[0] + new_ids[0, : int(lens[0])].cpu().tolist()
         predicted = np.array(full[-dim:])
         normalized = token_ids_to_actions(predicted, self.vocab_size, self.bin_centers)
@@ -419,12 +456,12 @@ class EmmaXForActionPrediction:
 
     @torch.inference_mode()
     def generate_actions_batch(self, frames_u8: torch.Tensor, prompt_rows: Sequence[Sequence[int]], max_new_tokens: int = 512,
-                               stop_on_eos: bool = True, tokenizer=None):
+                               stop_on_eos: bool = True, tokenizer=None, sampling=None):
         """Batched extension: returns (actions f32 [B,7], new_ids int32 [B,T], lens int32 [B]).
 
         With `tokenizer` each row goes ids -> text -> Solver exactly like the bs=1 path; without it the ids-level
-        stand-in `actions_from_ids` is used (synthetic weights / throughput runs)."""
-        new_ids, lens = self.generate_ids([list(r) for r in prompt_rows], None, frames_u8, max_new_tokens, stop_on_eos)
+        stand-in `actions_from_ids` is used (synthetic weights / throughput runs).  `sampling`: as generate_ids (None = greedy)."""
+        new_ids, lens = self.generate_ids([list(r) for r in prompt_rows], None, frames_u8, max_new_tokens, stop_on_eos, sampling=sampling)
         ids_h, lens_h = new_ids.cpu(), lens.cpu().tolist()
         acts = np.zeros((len(lens_h), 7), dtype=np.float32)
         stats = self.get_action_stats(None)

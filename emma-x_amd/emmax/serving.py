@@ -27,6 +27,7 @@ class Request:
     frame: Any
     prompt_ids: Sequence[int]
     max_new_tokens: int = 512
+    sampling: Any = None   # emmax.sampling.SamplingParams: drawn in the decode step with the request's seed (None: draw_seed()) and subseq 0; None = greedy
 
 
 @dataclass
@@ -37,6 +38,7 @@ class Result:
     t_submit: float
     t_admit: float
     t_done: float
+    logprobs: Optional[List[float]] = None   # sampled requests: the log-probability of every emitted token
 
     @property
     def latency_s(self) -> float:
@@ -99,6 +101,7 @@ class SlotScheduler:
         self.stage_batch = max(1, min(int(stage_batch) if stage_batch else max(1, n_slots // 2), n_slots))
         self._pending = None                         # [staged handle, [(request, t_submit), ...], committed so far] of the staged batch
         self.overlapped_admissions = 0
+        self._sampling = False                       # some request of the current run samples (run)
         # a staged batch is at most max(stage_batch, free slots) <= n_slots requests: the session needs that many staging rows
         # (they cost KV pages, so a session only has them when a scheduler asks: engine.ensure_stage_rows re-creates it if needed)
         if self.overlap and hasattr(engine, "ensure_stage_rows"):
@@ -110,6 +113,30 @@ class SlotScheduler:
         if len(req.prompt_ids) < 1:
             raise ValueError("empty prompt")
         self.queue.append((req, self.clock()))
+
+    def _sampling_rows(self, reqs):
+        """(params, seeds, subseqs) of requests about to be prefilled: greedy ones at temperature 0, each request with its own seed and subseq 0."""
+        from .sampling import SamplingParams, draw_seed
+
+        params, seeds = [], []
+        for r in reqs:
+            p = r.sampling if r.sampling is not None else SamplingParams(temperature=0.0, top_k=0, top_p=1.0, seed=0)
+            if p.seed is None:
+                p = SamplingParams(p.temperature, p.top_k, p.top_p, draw_seed())
+                r.sampling = p   # the seed the request was served with
+            params.append(p)
+            seeds.append(p.seed)
+        return params, seeds, [0] * len(reqs)
+
+    def _set_sampling(self, reqs, row0: int = 0, staged: bool = False) -> None:
+        """A serve where some request samples: every prefill is preceded by its rows' parameters.  Greedy-only serves call nothing here."""
+        if not self._sampling:
+            return
+        params, seeds, subs = self._sampling_rows(reqs)
+        if staged:
+            self.engine.set_sampling_staged(params, seeds, subs)
+        else:
+            self.engine.set_sampling(params, seeds, subs, row0=row0)
 
     def _admit(self) -> int:
         free = [s for s in range(self.n_slots) if s not in self.active]
@@ -127,10 +154,12 @@ class SlotScheduler:
             while j < take and slots[j] == slots[j - 1] + 1:
                 j += 1
             if j - i > 1 and hasattr(self.engine, "slots_prefill"):
+                self._set_sampling([batch[k][0] for k in range(i, j)], row0=slots[i])
                 self.engine.slots_prefill(slots[i], [list(batch[k][0].prompt_ids) for k in range(i, j)], embeds[i:j] if embeds[i] is not None else None,
                                           [batch[k][0].max_new_tokens for k in range(i, j)])
             else:
                 for k in range(i, j):
+                    self._set_sampling([batch[k][0]], row0=slots[k])
                     self.engine.slot_prefill(slots[k], list(batch[k][0].prompt_ids), embeds[k], batch[k][0].max_new_tokens)
             t_adm = self.clock()
             for k in range(i, j):
@@ -161,6 +190,7 @@ class SlotScheduler:
         try:
             with self.engine.admission():
                 embeds = self._encode_for(batch)
+                self._set_sampling([r for r, _ in batch], staged=True)
                 staged = self.engine.slots_prefill_staged([list(r.prompt_ids) for r, _ in batch], embeds if embeds[0] is not None else None,
                                                           [r.max_new_tokens for r, _ in batch])
         except Exception:
@@ -204,13 +234,23 @@ class SlotScheduler:
             if done[slot]:
                 a = self.active.pop(slot)
                 ids = self.engine.slot_output(slot, int(n_out[slot]))
+                lps = self.engine.slot_logprobs(slot, int(n_out[slot])) if a.req.sampling is not None else None
                 self.engine.slot_release(slot)
-                self.results.append(Result(a.req.rid, ids, slot, a.t_submit, a.t_admit, self.clock()))
+                self.results.append(Result(a.req.rid, ids, slot, a.t_submit, a.t_admit, self.clock(), lps))
                 n += 1
         return n
 
     def run(self) -> List[Result]:
-        """Serve until the queue is empty and every slot is idle.  Returns the results in completion order."""
+        """Serve until the queue is empty and every slot is idle.  Returns the results in completion order.  When some queued request
+        samples, the session samples for the whole run (greedy requests at temperature 0: their greedy ids) and is greedy again after it."""
+        self._sampling = any(r.sampling is not None for r, _ in self.queue)
+        try:
+            return self._run()
+        finally:
+            if self._sampling:
+                self.engine.clear_sampling()
+
+    def _run(self) -> List[Result]:
         if self.overlap:
             while self.queue or self.active or self._pending is not None:
                 self._start_admission()

@@ -36,8 +36,9 @@ extern "C" {
  *   1: rounds 1-2;  2: emmax_config grew `decode_fp8` (round 2, not bumped then);  3: round 4 -- emmax_config_size / emmax_tuning_*
  *   added, the lab-only entry points (persistent layer chain, in-attention split merge) removed;  4: round 5 -- emmax_session_*_ex (staging rows
  *   are asked for, the plain calls give none), decode batches / slot counts up to 64 (emmax_model_max_decode_batch);  5: exact numerics (emmax_session_exact, emmax_op_x_*);
- *   6: emmax_op_sample (seeded sampling over rows of logits). */
-#define EMMAX_ABI_VERSION 6
+ *   6: emmax_op_sample (seeded sampling over rows of logits);  7: sampling inside the decode step (emmax_session_set_sampling and the calls
+ *   around it), the workspace grew the per-row sampling state. */
+#define EMMAX_ABI_VERSION 7
 
 typedef enum emmax_status {
     EMMAX_OK = 0,
@@ -236,8 +237,9 @@ int emmax_slot_release(emmax_session* s, int slot, emmax_stream stream);
 
 /* ---- seeded sampling over rows of logits (ABI 6) --------------------------------------------------------------------
  * emmax_op_sample draws one token per row of logits_dev [B][ld] (fp32, V <= 32768 entries, ld >= V) and returns it with its
- * log-probability.  Per-row parameters and steps are device arrays of B entries.  The decode step itself stays greedy; a caller samples
- * the rows of emmax_last_logits and feeds the tokens back with emmax_set_current_tokens (emmax/sampling.py: sample_logits).
+ * log-probability.  Per-row parameters and steps are device arrays of B entries.  Since ABI 7 the decode step draws the same way itself
+ * (emmax_session_set_sampling below); an external loop samples the rows of emmax_last_logits and feeds the tokens back with
+ * emmax_set_current_tokens (emmax/sampling.py: sample_logits).
  *   temperature 0     greedy: the argmax, lowest id on ties (top_k / top_p ignored);
  *   temperature T > 0 z = l / T (fp32); top_k > 0 keeps z_i >= the k-th largest z (ties kept); top_p < 1 then keeps, over those, the i with
  *                     sum_{kept j, z_j > z_i} W_j < top_p * sum_{kept j} W_j, W_j = floor(exp(z_j - max z) 2^32) as 64-bit integers
@@ -252,6 +254,35 @@ int emmax_slot_release(emmax_session* s, int slot, emmax_stream stream);
 int emmax_op_sample(const float* logits_dev, int ld, int B, int V, const float* temperature_dev, const int32_t* top_k_dev, const float* top_p_dev,
                     const uint64_t* seed_dev, const uint32_t* subseq_dev, const int32_t* step_dev, int32_t* tok_out_dev, float* logprob_out_dev,
                     emmax_stream stream);
+
+/* ---- sampling inside the decode step (ABI 7) ------------------------------------------------------------------------
+ * A session samples once emmax_session_set_sampling (or emmax_slots_set_sampling_staged) has run: from then on every lm-head that emits a
+ * token -- prefills (emmax_prefill*, emmax_slot_prefill, emmax_slots_prefill*), decode steps eager and replayed, emmax_generate,
+ * emmax_slots_step -- also writes the fp32 logits of its rows to the session's own logit rows, and the step's finish draws each row's token
+ * from them exactly as emmax_op_sample does (the same token and log-probability bits) with step = the row's generation index (0 for the
+ * token a prefill emits) and the row's (temperature, top_k, top_p, seed, subseq).  A sampled step has the launch count of a greedy one;
+ * the captured step graph is keyed on sampling on / off, and changed parameters re-capture nothing (they are device words).  Rows at
+ * temperature 0 take the argmax of those fp32 logits: the greedy token.  A row whose logits are all NaN emits pad_id and is done.
+ * Parameters are per row and stay until set again; a row's parameters must be set before the prefill whose first token they govern.
+ * emmax_session_clear_sampling turns sampling off: the session launches exactly what a session that never sampled launches.
+ *   emmax_session_set_sampling       decode rows row0 .. row0 + n - 1 (slots when request slots are open); host arrays of n values, checked
+ *                                    here: temperature finite and >= 0, top_k >= 0 (0 = off), 0 < top_p <= 1 -- else EMMAX_ERR_INVALID.
+ *                                    Synchronises the stream (the values pass through pinned memory).  Turns sampling on.
+ *   emmax_slots_set_sampling_staged  the same for the n requests of the next emmax_slots_prefill_staged (call it on that prefill's stream);
+ *                                    emmax_slots_commit moves a request's parameters and log-probabilities with the rest of its state.
+ *   emmax_session_sampling           1 = sampling on, 0 = off, -1 = null session.
+ *   emmax_session_logprobs           after emmax_generate: out_dev fp32 [B][max_new], the log-probability of every emitted token
+ *                                    (l_tok - logsumexp(l) over the raw logits, T = 1, unfiltered: emmax_op_sample's); entries past a
+ *                                    row's length are 0.  emmax_slot_logprobs: the first n of one slot (as emmax_slot_output).
+ *                                    Both EMMAX_ERR_STATE while sampling is off. */
+int emmax_session_set_sampling(emmax_session* s, int row0, int n, const float* temperature_host, const int32_t* top_k_host, const float* top_p_host,
+                               const uint64_t* seed_host, const uint32_t* subseq_host, emmax_stream stream);
+int emmax_slots_set_sampling_staged(emmax_session* s, int n, const float* temperature_host, const int32_t* top_k_host, const float* top_p_host,
+                                    const uint64_t* seed_host, const uint32_t* subseq_host, emmax_stream stream);
+int emmax_session_clear_sampling(emmax_session* s, emmax_stream stream);
+int emmax_session_sampling(const emmax_session* s);
+int emmax_session_logprobs(emmax_session* s, int max_new, float* out_dev, emmax_stream stream);
+int emmax_slot_logprobs(emmax_session* s, int slot, float* out_dev, int n, emmax_stream stream);
 
 /* ---- single-kernel entry points (parity tests + micro-benchmarks) -------------------------------------------------- */
 /* C[M,N] = epilogue(A[M,K] @ W[N,K]^T): bf16 in, fp32 accumulate on MFMA.  K % 64 == 0, N % 128 == 0.

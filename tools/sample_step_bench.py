@@ -1,0 +1,67 @@
+"""ms per decode step of generate with sampling in the step (include/emmax.h ABI 7) against the greedy step, at the shapes of the headline
+bench (Emma-X-7B synthetic weights, 512-token prompts, 512 new tokens) and batches 1, 8 and 64.
+
+  greedy   sampling off: the kernels of a session that never sampled
+  t0       sampling on, every row at temperature 0 (the argmax of the fp32 logit rows)
+  hf       temperature 1, top-k 50 (the HF defaults)
+  topp     temperature 1, top-p 0.9
+
+EOS is disabled (as in bench.py), so every row decodes every step.  The time of one generate call after its prefill, divided by its decode
+steps (new tokens - 1), median over --reps calls.  Prints one JSON line per (batch, mode)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "emma-x_amd")]
+import numpy as np
+import torch
+
+from emmax.config import EmmaXConfig
+from emmax.modeling import EmmaXForActionPrediction
+from emmax.sampling import SamplingParams
+
+MODES = {"greedy": None, "t0": SamplingParams(0.0, 0, 1.0, seed=1), "hf": SamplingParams(1.0, 50, 1.0, seed=1),
+         "topp": SamplingParams(1.0, 0, 0.9, seed=1)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="1,8,64")
+    ap.add_argument("--prompt-tokens", type=int, default=512)
+    ap.add_argument("--new-tokens", type=int, default=512)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--modes", default=",".join(MODES))
+    ap.add_argument("--tiny", action="store_true")
+    args = ap.parse_args()
+    dev = "cuda:0"
+    batches = [int(b) for b in args.batches.split(",")]
+    cfg = EmmaXConfig.tiny() if args.tiny else EmmaXConfig.emma_x_7b()
+    cfg.eos_token_id = -1
+    P, T = args.prompt_tokens, args.new_tokens
+    model = EmmaXForActionPrediction.from_synthetic(cfg, seed=0, device=dev, max_batch=max(batches), max_prompt=P, max_ctx=cfg.n_patches + P + T + 1)
+    eng = model.engine
+    rng = np.random.default_rng(1234)
+    frames = torch.from_numpy(rng.integers(0, 256, size=(max(batches), 224, 224, 3), dtype=np.uint8)).to(dev)
+    prompts = [[1] + [int(x) for x in rng.integers(3, 31744, size=P - 1)] for _ in range(max(batches))]
+    for B in batches:
+        for mode in args.modes.split(","):
+            times = []
+            for rep in range(args.reps + 1):   # (the first call warms up: graph capture, first-touch of the logit rows)
+                model._prefill(prompts[:B], frames_u8=frames[:B], max_new=T, sampling=MODES[mode])
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ids, lens = eng.generate(T, stop_on_eos=False)
+                torch.cuda.synchronize()
+                if rep:
+                    times.append(time.perf_counter() - t0)
+            assert int(lens.min()) == T, "a row ended early"
+            ms = 1e3 * float(np.median(times)) / (T - 1)
+            print(json.dumps({"batch": B, "mode": mode, "ms_per_step": round(ms, 4), "prompt": P, "new_tokens": T, "reps": args.reps}), flush=True)
+    eng.clear_sampling()
+
+
+if __name__ == "__main__":
+    main()
