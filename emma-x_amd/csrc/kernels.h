@@ -127,6 +127,10 @@ struct CommitParams {
     int32_t* top_k;
     uint64_t* seed;
     uint32_t* subseq;
+    // logits processing on (else all null): the rows' processor parameters and prompt ids [][max_prompt] (+ their lengths) move too
+    float* penalty;
+    int32_t *ngram, *min_new, *hist, *hist_len;
+    int max_prompt;
 };
 int launch_slots_commit(const CommitParams& c, hipStream_t stream);
 int launch_set_int(int32_t* p, int32_t v, hipStream_t stream);
@@ -397,6 +401,30 @@ struct SampleFinishParams {
     float* logprob;             // [B][f.max_out], beside f.out_ids
 };
 int launch_sample_finish(const SampleFinishParams& p, hipStream_t stream);
+// the finish of a step with LOGITS PROCESSING or SCORES on (include/emmax.h: emmax_session_set_processing / emmax_session_set_scores): the
+// same kernel body again, which first applies the row's repetition penalty, n-gram ban and min-new-tokens EOS ban to its fp32 logits (history
+// = the row's prompt ids, then out_ids[0 .. n_out)), then draws (sampling on) or takes the argmax (sampling off: temperature null) and
+// stores the row's processed scores / raw logits at its generation index when scores are bound.  Replaces the greedy or sampled finish.
+#define EMMAX_MAX_NGRAM 32
+struct ProcFinishParams : SampleFinishParams {
+    int row0;                   // the session row of block 0 (the scores' batch index of block b is row0 + b)
+    const float* penalty;       // [B] repetition penalty (1 = off); penalty / ngram / min_new null: processing off (scores only)
+    const int32_t* ngram;       // [B] no_repeat_ngram_size, 0 = off, <= EMMAX_MAX_NGRAM
+    const int32_t* min_new;     // [B] EOS is -inf while n_out < min_new
+    const int32_t* hist;        // [B][max_prompt] the rows' prompt ids (text ids as the prefill got them)
+    const int32_t* hist_len;    // [B]
+    int max_prompt;
+    const uint64_t* score_words;   // null: no scores.  Else device words {scores f32*, logits f32*, max_new, rows}: buffers [max_new][rows][V]
+};
+int launch_proc_finish(const ProcFinishParams& p, hipStream_t stream);
+// the prompt ids of rows 0 .. B of a prefill (ids [B][P_max]) into dst [B][max_prompt], their lengths into dst_len
+struct HistParams {
+    const int32_t* ids;
+    int P_max, B, max_prompt;
+    int32_t *dst, *dst_len;
+    int len[EMMAX_MAX_DECODE_BATCH];
+};
+int launch_hist_fill(const HistParams& h, hipStream_t stream);
 int launch_set_tokens(int32_t* cur_tok, const int32_t* toks, int B, int32_t* done, int32_t* stop_m, int32_t* stop_after, int32_t* max_new,
                       int budget, hipStream_t stream);
 

@@ -324,6 +324,8 @@ __global__ __launch_bounds__(256) void emmax_slots_commit_kernel(CommitParams c)
     for (int k = tid; k < c.max_out; k += 256) c.out_ids[(size_t)dst * c.max_out + k] = c.out_ids[(size_t)src * c.max_out + k];
     if (c.logprob)
         for (int k = tid; k < c.max_out; k += 256) c.logprob[(size_t)dst * c.max_out + k] = c.logprob[(size_t)src * c.max_out + k];
+    if (c.penalty)
+        for (int k = tid; k < c.max_prompt; k += 256) c.hist[(size_t)dst * c.max_prompt + k] = c.hist[(size_t)src * c.max_prompt + k];
     for (int k = tid; k < c.max_pages; k += 256) {
         const int32_t a = c.page_table[(size_t)src * c.max_pages + k], b = c.page_table[(size_t)dst * c.max_pages + k];
         c.page_table[(size_t)dst * c.max_pages + k] = a;
@@ -337,11 +339,29 @@ __global__ __launch_bounds__(256) void emmax_slots_commit_kernel(CommitParams c)
             c.temperature[dst] = c.temperature[src]; c.top_k[dst] = c.top_k[src]; c.top_p[dst] = c.top_p[src];
             c.seed[dst] = c.seed[src]; c.subseq[dst] = c.subseq[src];
         }
+        if (c.penalty) {
+            c.penalty[dst] = c.penalty[src]; c.ngram[dst] = c.ngram[src]; c.min_new[dst] = c.min_new[src];
+            c.hist_len[dst] = c.hist_len[src];
+        }
         c.done[src] = 1; c.ctx_len[src] = 0;
     }
 }
 
+__global__ __launch_bounds__(256) void emmax_hist_fill_kernel(HistParams h) {
+    const int b = blockIdx.x, n = h.len[b];
+    for (int k = threadIdx.x; k < n; k += 256) h.dst[(size_t)b * h.max_prompt + k] = h.ids[(size_t)b * h.P_max + k];
+    if (threadIdx.x == 0) h.dst_len[b] = n;
+}
+
 }  // namespace
+
+int launch_hist_fill(const HistParams& h, hipStream_t stream) {
+    if (h.B < 1 || h.B > EMMAX_MAX_DECODE_BATCH) return -1;
+    for (int b = 0; b < h.B; ++b)
+        if (h.len[b] < 0 || h.len[b] > h.P_max || h.len[b] > h.max_prompt) return -1;
+    hipLaunchKernelGGL(emmax_hist_fill_kernel, dim3(h.B), dim3(256), 0, stream, h);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
 
 int launch_slots_commit(const CommitParams& c, hipStream_t stream) {
     if (c.n < 1 || c.n > EMMAX_MAX_DECODE_BATCH) return -1;

@@ -353,6 +353,15 @@ struct emmax_session {
     uint64_t* samp_seed;
     uint32_t* samp_sub;
     bool sampling = false;
+    // LOGITS PROCESSING (emmax_session_set_processing; the processing finish, sample.hip): per-row repetition penalty, n-gram size and
+    // min-new-tokens of every row, staging rows included, and each row's prompt ids (every prefill fills them while processing is on).
+    // SCORES (emmax_session_set_scores): device words {scores, logits, max_new, rows} the processing finish stores through.  Either on: the
+    // step runs on the logit rows and ends in the processing finish.  Both off: none of it is touched
+    float* proc_pen;
+    int32_t *proc_ng, *proc_mn, *hist /* [rows_total][max_prompt] */, *hist_len;
+    uint64_t* score_words;
+    bool processing = false, scores_on = false;
+    int scores_rows = 0;   // rows of the bound score buffers: the batch of the first prefill after the binding (0: none yet)
     int32_t *part_idx2;
     int32_t *part_idx, *cur_tok, *ctx_len, *done, *n_out, *out_ids, *max_new_d /* [max_batch] */, *page_table;
     // EXACT NUMERICS (round 6; tuning switch `exact` at emmax_session_create): fp32 activations end to end.  x32a: the fp32 result of the GEMM
@@ -394,7 +403,7 @@ struct emmax_session {
     int last_step_graph = 0;   // the most recent decode step was a graph replay (what emmax_session_graph_active reports)
     hipEvent_t ev = nullptr;
     int graph_epoch = -1;      // emmax_tune().epoch the graph was captured under (a changed switch re-captures)
-    bool graph_sampling = false;   // the captured step ends in the sampled finish (the parameters are device words: a change re-captures nothing)
+    int graph_mode = 0;   // finish_mode() the step was captured under (the parameters and score buffers are device words: a change re-captures nothing)
     hipStream_t own_stream = nullptr;   // used by emmax_generate when the caller's stream is the (uncapturable) legacy stream
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
     std::string graph_err;
@@ -478,6 +487,12 @@ static void plan_session(emmax_session* s, SBump& b) {
     s->samp_seed = (uint64_t*)b.take(Br * 8);
     s->samp_sub = (uint32_t*)b.take(Br * 4);
     s->logprob = (float*)b.take((int64_t)Br * s->max_out * 4);
+    s->proc_pen = (float*)b.take(Br * 4);
+    s->proc_ng = (int32_t*)b.take(Br * 4);
+    s->proc_mn = (int32_t*)b.take(Br * 4);
+    s->hist = (int32_t*)b.take((int64_t)Br * s->max_prompt * 4);
+    s->hist_len = (int32_t*)b.take(Br * 4);
+    s->score_words = (uint64_t*)b.take(4 * 8);
     s->cur_tok = (int32_t*)b.take(Br * 4);
     s->ctx_len = (int32_t*)b.take(Br * 4);
     s->done = (int32_t*)b.take(Br * 4);
@@ -847,6 +862,9 @@ static float* kscale_of(emmax_session* s, int layer) { return (float*)(kv_layer(
 static float* vscale_of(emmax_session* s, int layer) { return kscale_of(s, layer) + kv_rows(s); }
 
 static int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* logits_out, bool do_finish, hipStream_t st, int slot0 = 0);
+// how a step ends (the captured graph is keyed on it: the finish's parameters differ in each): bit 0 sampling, bit 1 processing, bit 2
+// scores.  0: the greedy finish (lm-head argmax partials); 1: the sampled finish; bit 1 or 2 set: the processing finish
+static int finish_mode(const emmax_session* s) { return (s->sampling ? 1 : 0) | (s->processing ? 2 : 0) | (s->scores_on ? 4 : 0); }
 static int launch_finish_step(emmax_session* s, int B, bool is_prefill, int n_part, int slot0, hipStream_t st);
 
 // the per-row state of rows slot0 .. slot0 + B that a finish updates
@@ -888,6 +906,27 @@ static int launch_sampled_finish_step(emmax_session* s, int B, bool is_prefill, 
     return 0;
 }
 
+// finish of a step with logits processing or scores on: the processors, then the draw (sampling on) or the argmax, then the scores store
+static int launch_proc_finish_step(emmax_session* s, int B, bool is_prefill, int slot0, const float* logits, hipStream_t st) {
+    ProcFinishParams p;
+    memset(&p, 0, sizeof(p));
+    finish_rows(s, B, is_prefill, slot0, p.f);
+    p.logits = logits; p.ld = s->m->vocab; p.V = s->m->vocab;
+    if (s->sampling) {   // else temperature stays null: every row greedy
+        p.temperature = s->samp_t + slot0; p.top_k = s->samp_k + slot0; p.top_p = s->samp_p + slot0;
+        p.seed = s->samp_seed + slot0; p.subseq = s->samp_sub + slot0;
+    }
+    p.logprob = s->logprob + (size_t)slot0 * s->max_out;
+    p.row0 = slot0;
+    if (s->processing) {
+        p.penalty = s->proc_pen + slot0; p.ngram = s->proc_ng + slot0; p.min_new = s->proc_mn + slot0;
+        p.hist = s->hist + (size_t)slot0 * s->max_prompt; p.hist_len = s->hist_len + slot0; p.max_prompt = s->max_prompt;
+    }
+    if (s->scores_on) p.score_words = s->score_words;
+    KCHK(launch_proc_finish(p, st));
+    return 0;
+}
+
 static void lmhead_params(emmax_session* s, int slot0, float* logits_out, GemvParams& p);
 // slot0: first row of the B rows this call covers (slot prefill: one row in the middle of a live batch)
 static int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* logits_out, bool do_finish, hipStream_t st, int slot0) {
@@ -898,13 +937,16 @@ static int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* log
         if (r) return r;
         return run_lm_head_step(s, B - chunk, is_prefill, logits_out ? logits_out + (size_t)chunk * m->vocab : nullptr, do_finish, st, slot0 + chunk);
     }
-    // sampling on: a step's lm-head also writes the fp32 logit rows of its B rows, and the sampled finish draws from them
-    const bool sampled = do_finish && s->sampling;
+    // sampling, processing or scores on: a step's lm-head also writes the fp32 logit rows of its B rows, and the sampled or processing finish
+    // reads them
+    const int mode = do_finish ? finish_mode(s) : 0;
+    const bool sampled = mode != 0;
     if (sampled) logits_out = s->logits + (size_t)slot0 * m->vocab;
     GemvParams p;
     lmhead_params(s, slot0, logits_out, p);
     int lm_grid = 0;
     KCHK(launch_proj(GEMV_LMHEAD, p, m->lm_head, m->lm_head_fm, B, st, &lm_grid, m->lm_head_sc, m->lm_head_r8, F8_LMHEAD, m->lm_head_fm, m->lm_head_sc));
+    if (mode & 6) return launch_proc_finish_step(s, B, is_prefill, slot0, logits_out, st);
     if (sampled) return launch_sampled_finish_step(s, B, is_prefill, slot0, logits_out, st);
     if (do_finish) return launch_finish_step(s, B, is_prefill, lm_grid, slot0, st);
     return 0;
@@ -952,6 +994,22 @@ static int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens
     }
     if (total > s->max_rows) return fail(EMMAX_ERR_NOMEM, "packed prefill rows %d exceed capacity %d", total, s->max_rows);
     KCHK(launch_prefill_state(ps, s->cu, s->ctx_len + r0, s->done + r0, s->n_out + r0, s->max_new_d + r0, s->stop_m + r0, s->stop_after + r0, st));
+    if (s->scores_on && !slot_mode) {   // the score buffers' rows: the first prefill after the binding's; another batch size unbinds them
+        if (s->scores_rows == 0) {
+            s->scores_rows = B;
+            KCHK(launch_set_int((int32_t*)(s->score_words + 3), B, st));
+        } else if (s->scores_rows != B) {
+            s->scores_on = false;
+        }
+    }
+    if (s->processing) {   // the rows' prompt ids: the history the processors read
+        HistParams h;
+        memset(&h, 0, sizeof(h));
+        h.ids = ids; h.P_max = P_max; h.B = B; h.max_prompt = s->max_prompt;
+        h.dst = s->hist + (size_t)r0 * s->max_prompt; h.dst_len = s->hist_len + r0;
+        for (int b = 0; b < B; ++b) h.len[b] = lens[b];
+        KCHK(launch_hist_fill(h, st));
+    }
     if (!slot_mode) { s->cur_B = B; s->dec_steps = 0; }
     s->total_rows = total; s->max_seqlen = maxS;
     if (s->exact) return run_prefill_x(s, ids, B, P_max, patches, np, total, maxS, r0, st);
@@ -1275,7 +1333,7 @@ static int ensure_graph(emmax_session* s, int B, hipStream_t st) {
     // cannot be kept free).
     s->last_step_graph = 0;   // set again by launch_graph_step when a replay really runs
     if (!emmax_tune().graph) return 1;   // eager step: a captured graph stays valid for the next caller that wants replay
-    if (s->graph_exec && s->graph_B == B && s->graph_stream_cap == st && s->graph_epoch == emmax_tune().epoch && s->graph_sampling == s->sampling)
+    if (s->graph_exec && s->graph_B == B && s->graph_stream_cap == st && s->graph_epoch == emmax_tune().epoch && s->graph_mode == finish_mode(s))
         return 0;
     drop_graph(s);
     if (s->graph_failed) return 1;
@@ -1295,7 +1353,7 @@ static int ensure_graph(emmax_session* s, int B, hipStream_t st) {
         return graph_fail(s, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
     }
     s->graph = g; s->graph_exec = ge; s->graph_B = B; s->graph_stream_cap = st; s->graph_epoch = emmax_tune().epoch;
-    s->graph_sampling = s->sampling;
+    s->graph_mode = finish_mode(s);
     return 0;
 }
 
@@ -1732,6 +1790,7 @@ int emmax_set_current_tokens(emmax_session* s, const int32_t* toks, emmax_stream
     if (!s || !toks) return fail(EMMAX_ERR_INVALID, "null argument");
     if (!s->prefilled) return fail(EMMAX_ERR_STATE, "no active sequences");
     if (s->slots_open) return fail(EMMAX_ERR_STATE, "caller-supplied tokens are not supported while request slots are open");
+    if (s->processing) return fail(EMMAX_ERR_STATE, "caller-supplied tokens are not supported while logits processing is on (they would be missing from the history)");
     // the rows decode again (done flag cleared): the next step appends at position <= S_b + dec_steps, which must exist
     int maxS = 0;
     for (int b = 0; b < s->cur_B && b < (int)s->S.size(); ++b) maxS = std::max(maxS, s->S[b]);
@@ -1843,6 +1902,7 @@ int emmax_slots_open(emmax_session* s, int n_slots, emmax_stream stream) {
     s->cur_B = n_slots;
     s->S.assign(s->rows_total, 0);
     s->slots_open = true;
+    s->scores_on = false;   // no scores in slot serving (the bound buffers were a generate call's)
     s->prefilled = true;   // decode steps are legal: idle slots are rows that are already done
     return slot_leave(s, user, st);
 }
@@ -1917,6 +1977,10 @@ int emmax_slots_commit(emmax_session* s, const int32_t* staged_idx_host, const i
     if (s->sampling) {
         c.temperature = s->samp_t; c.top_k = s->samp_k; c.top_p = s->samp_p; c.seed = s->samp_seed; c.subseq = s->samp_sub;
         c.logprob = s->logprob;
+    }
+    if (s->processing) {
+        c.penalty = s->proc_pen; c.ngram = s->proc_ng; c.min_new = s->proc_mn; c.hist = s->hist; c.hist_len = s->hist_len;
+        c.max_prompt = s->max_prompt;
     }
     hipStream_t user = (hipStream_t)stream, st;
     int r = slot_enter(s, user, &st);
@@ -2066,6 +2130,88 @@ int emmax_slot_logprobs(emmax_session* s, int slot, float* out_dev, int n, emmax
     int r = slot_enter(s, user, &st);
     if (r) return r;
     if (n > 0) HIPCHK(hipMemcpyAsync(out_dev, s->logprob + (size_t)slot * s->max_out, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    return slot_leave(s, user, st);
+}
+
+// ---- logits processing and scores in the decode step (ABI 8) --------------------------------------------------------------
+// rows r0 .. r0 + n of the session: host values checked here, uploaded through the pinned words 2112.. (as set_sampling_rows)
+static int set_processing_rows(emmax_session* s, int r0, int n, const float* pen, const int32_t* ng, const int32_t* mn, hipStream_t st) {
+    if (s->m->vocab > EMMAX_SAMPLE_MAX_V) return fail(EMMAX_ERR_INVALID, "logits processing takes vocabularies of up to %d entries (%d)", EMMAX_SAMPLE_MAX_V, s->m->vocab);
+    for (int i = 0; i < n; ++i) {
+        if (!std::isfinite(pen[i]) || !(pen[i] > 0.f)) return fail(EMMAX_ERR_INVALID, "row %d: repetition penalty %g (finite and > 0)", r0 + i, (double)pen[i]);
+        if (ng[i] < 0 || ng[i] > EMMAX_MAX_NGRAM) return fail(EMMAX_ERR_INVALID, "row %d: no_repeat_ngram_size %d outside 0..%d", r0 + i, ng[i], EMMAX_MAX_NGRAM);
+        if (mn[i] < 0) return fail(EMMAX_ERR_INVALID, "row %d: min_new_tokens %d (>= 0)", r0 + i, mn[i]);
+    }
+    char* h = (char*)(s->pinned + 2112);
+    HIPCHK(hipStreamSynchronize(st));   // the pinned staging words may still feed an earlier upload
+    for (int c0 = 0; c0 < n; c0 += 256) {
+        const int c = std::min(256, n - c0);
+        float* hp = (float*)h;
+        int32_t* hn = (int32_t*)(h + 1024);
+        int32_t* hm = (int32_t*)(h + 2048);
+        for (int i = 0; i < c; ++i) { hp[i] = pen[c0 + i]; hn[i] = ng[c0 + i]; hm[i] = mn[c0 + i]; }
+        const int r = r0 + c0;
+        HIPCHK(hipMemcpyAsync(s->proc_pen + r, hp, c * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(s->proc_ng + r, hn, c * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(s->proc_mn + r, hm, c * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    s->processing = true;
+    return 0;
+}
+
+int emmax_session_set_processing(emmax_session* s, int row0, int n, const float* penalty_host, const int32_t* ngram_host, const int32_t* min_new_host,
+                                 emmax_stream stream) {
+    if (!s || !penalty_host || !ngram_host || !min_new_host) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (n < 1 || row0 < 0 || row0 + n > s->max_batch) return fail(EMMAX_ERR_INVALID, "rows %d..%d outside 0..%d", row0, row0 + n - 1, s->max_batch - 1);
+    hipStream_t user = (hipStream_t)stream, st;
+    int r = slot_enter(s, user, &st);
+    if (r) return r;
+    r = set_processing_rows(s, row0, n, penalty_host, ngram_host, min_new_host, st);
+    if (r) return r;
+    return slot_leave(s, user, st);
+}
+
+int emmax_slots_set_processing_staged(emmax_session* s, int n, const float* penalty_host, const int32_t* ngram_host, const int32_t* min_new_host,
+                                      emmax_stream stream) {
+    if (!s || !penalty_host || !ngram_host || !min_new_host) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (n < 1 || n > s->n_stg) return fail(EMMAX_ERR_INVALID, "%d staged requests outside 1..%d (the session's staging rows)", n, s->n_stg);
+    hipStream_t user = (hipStream_t)stream, st;
+    int r = slot_enter(s, user, &st);
+    if (r) return r;
+    r = set_processing_rows(s, s->stg0, n, penalty_host, ngram_host, min_new_host, st);
+    if (r) return r;
+    return slot_leave(s, user, st);
+}
+
+int emmax_session_clear_processing(emmax_session* s, emmax_stream stream) {
+    (void)stream;
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    s->processing = false;
+    return 0;
+}
+
+int emmax_session_processing(const emmax_session* s) { return s ? (s->processing ? 1 : 0) : -1; }
+
+int emmax_session_set_scores(emmax_session* s, float* scores_dev, float* logits_dev, int max_new, emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (s->slots_open) return fail(EMMAX_ERR_STATE, "scores are not kept in slot serving (emmax_slots_open)");
+    if (!scores_dev && !logits_dev) {
+        s->scores_on = false;
+        return 0;
+    }
+    if (s->m->vocab > EMMAX_SAMPLE_MAX_V) return fail(EMMAX_ERR_INVALID, "scores take vocabularies of up to %d entries (%d)", EMMAX_SAMPLE_MAX_V, s->m->vocab);
+    if (max_new < 1 || max_new > s->max_out) return fail(EMMAX_ERR_INVALID, "max_new_tokens %d outside 1..%d", max_new, s->max_out);
+    hipStream_t user = (hipStream_t)stream, st;
+    int r = slot_enter(s, user, &st);
+    if (r) return r;
+    uint64_t* h = (uint64_t*)(s->pinned + 2112);
+    HIPCHK(hipStreamSynchronize(st));   // the pinned staging words may still feed an earlier upload
+    h[0] = (uint64_t)(uintptr_t)scores_dev; h[1] = (uint64_t)(uintptr_t)logits_dev; h[2] = (uint64_t)max_new; h[3] = 0;   // rows: set by the next prefill
+    HIPCHK(hipMemcpyAsync(s->score_words, h, 4 * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    s->scores_on = true;
+    s->scores_rows = 0;
     return slot_leave(s, user, st);
 }
 

@@ -188,13 +188,80 @@ __device__ uint32_t radix_threshold(const float (&z)[SG * 4], float zmax, int ti
 // the token a prefill emits)
 __device__ __forceinline__ int row_step(const SampleParams& p, int b) { return p.step[b]; }
 __device__ __forceinline__ int row_step(const SampleFinishParams& p, int b) { return p.f.n_out[b]; }
+// the row's temperature: a processing / scores finish with sampling off has none (every row greedy, whatever samp_t still holds)
+__device__ __forceinline__ float row_temperature(const SampleParams& p, int b) { return p.temperature[b]; }
+__device__ __forceinline__ float row_temperature(const SampleFinishParams& p, int b) { return p.temperature[b]; }
+__device__ __forceinline__ float row_temperature(const ProcFinishParams& p, int b) { return p.temperature ? p.temperature[b] : 0.f; }
 
-// One kernel body for both uses, so the draw exists once: P = SampleParams is emmax_op_sample (token and log-probability out); P =
-// SampleFinishParams is the finish of a sampled step (kernels.h), whose row then ends in the bookkeeping every finish shares.  (A template
-// kernel rather than a shared device function: inlining the draw into two kernels raised the spills of this one from 75 to 88 VGPRs.)
+// id j of row b's history: the prompt ids, then the ids the row has emitted
+__device__ __forceinline__ int hist_id(const int32_t* prompt, int plen, const int32_t* out, int j) { return j < plen ? prompt[j] : out[j - plen]; }
+
+// The logits processors of a processing finish (include/emmax.h), in HF's order, on the row held in z (entry i = 4 (g * ST + tid) + c):
+// repetition penalty over the distinct ids of the history, n-gram ban, EOS ban while n_out < min_new.  The presence and ban bitmaps are
+// LDS words set with integer atomicOr only, so the processed row does not depend on the order work arrives in.
+__device__ void process_row(const ProcFinishParams& p, int b, int tid, int V, int n_out, float (&z)[SG * 4], uint32_t* pres, uint32_t* ban) {
+    const float pen = p.penalty[b];
+    const int ng = p.ngram[b], mn = p.min_new[b];
+    const int plen = min(max(p.hist_len[b], 0), p.max_prompt);
+    const int32_t* prompt = p.hist + (size_t)b * p.max_prompt;
+    const int32_t* out = p.f.out_ids + (size_t)b * p.f.max_out;
+    const int L = plen + min(n_out, p.f.max_out);
+    const int W = (V + 31) / 32;
+    for (int w = tid; w < W; w += ST) { pres[w] = 0u; ban[w] = 0u; }
+    __syncthreads();
+    if (pen != 1.f)
+        for (int j = tid; j < L; j += ST) {
+            const int id = hist_id(prompt, plen, out, j);
+            if (id >= 0 && id < V) atomicOr(&pres[id >> 5], 1u << (id & 31));
+        }
+    if (ng > 0 && L >= ng)   // start j: H[j .. j + ng - 2] == H[L - ng + 1 .. L - 1] bans H[j + ng - 1]
+        for (int j = tid; j + ng <= L; j += ST) {
+            bool same = true;
+            for (int k = 0; k < ng - 1 && same; ++k) same = hist_id(prompt, plen, out, j + k) == hist_id(prompt, plen, out, L - ng + 1 + k);
+            if (same) {
+                const int id = hist_id(prompt, plen, out, j + ng - 1);
+                if (id >= 0 && id < V) atomicOr(&ban[id >> 5], 1u << (id & 31));
+            }
+        }
+    __syncthreads();
+    const int eos = n_out < mn ? p.f.eos_id : -1;
+#pragma unroll
+    for (int g = 0; g < SG; ++g)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int i = (g * ST + tid) * 4 + c;
+            if (i >= V) continue;
+            float x = z[g * 4 + c];
+            if ((pres[i >> 5] >> (i & 31)) & 1u) x = x < 0.f ? x * pen : x / pen;
+            if (((ban[i >> 5] >> (i & 31)) & 1u) || i == eos) x = -INFINITY;
+            z[g * 4 + c] = x;
+        }
+}
+
+// a row of z (entry i = 4 (g * ST + tid) + c; the first V entries) to dst
+__device__ __forceinline__ void store_row(float* dst, const float (&z)[SG * 4], int tid, int V) {
+    const bool vec = ((uintptr_t)dst & 15) == 0;
+#pragma unroll
+    for (int g = 0; g < SG; ++g) {
+        const int i0 = (g * ST + tid) * 4;
+        if (vec && i0 + 3 < V) {
+            *(f32x4_t*)(dst + i0) = f32x4_t{z[g * 4], z[g * 4 + 1], z[g * 4 + 2], z[g * 4 + 3]};
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (i0 + c < V) dst[i0 + c] = z[g * 4 + c];
+        }
+    }
+}
+
+// One kernel body for all three uses, so the draw exists once: P = SampleParams is emmax_op_sample (token and log-probability out); P =
+// SampleFinishParams is the finish of a sampled step (kernels.h), whose row then ends in the bookkeeping every finish shares; P =
+// ProcFinishParams is that finish with the logits processors before the draw and the scores store after it.  (A template kernel rather
+// than a shared device function: inlining the draw into two kernels raised the spills of this one from 75 to 88 VGPRs.)
 template <class P>
 __global__ __launch_bounds__(ST) void emmax_sample_kernel(P p) {
-    constexpr bool FIN = std::is_same<P, SampleFinishParams>::value;
+    constexpr bool PROC = std::is_same<P, ProcFinishParams>::value;
+    constexpr bool FIN = std::is_same<P, SampleFinishParams>::value || PROC;
     __shared__ SampleShared sh;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (EMMAX_WAVE - 1), wave = tid / EMMAX_WAVE;
     const int V = p.V, step = row_step(p, b);
@@ -231,10 +298,24 @@ __global__ __launch_bounds__(ST) void emmax_sample_kernel(P p) {
     se = block_sum(se, sh, lane, wave);
     const float lse = mx + logf(se);
 
-    const float T = p.temperature[b];
+    const float T = row_temperature(p, b);
+    bool dead = false;   // (processing finish) no finite entry is left: the row emits pad and is done
+    if constexpr (PROC) {
+        if (p.penalty) {
+            __shared__ uint32_t pres[EMMAX_SAMPLE_MAX_V / 32], ban[EMMAX_SAMPLE_MAX_V / 32];
+            process_row(p, b, tid, V, step, z, pres, ban);
+            mx = -INFINITY;   // the maximum of the processed row (z / T's is mx / T: division by T > 0 keeps the order)
+#pragma unroll
+            for (int j = 0; j < SG * 4; ++j) mx = fmaxf(mx, z[j]);
+            mx = block_max(mx, sh, lane, wave);
+            dead = !(mx > -INFINITY);
+        }
+    }
     float bv = -INFINITY;
     int bi = 0x7fffffff;
-    if (!(T > 0.f)) {   // greedy: argmax, lowest id on ties
+    uint32_t kept = 0;   // (processing finish, T > 0) the kept set: key(z) >= kept
+    if (dead) {
+    } else if (!(T > 0.f)) {   // greedy: argmax, lowest id on ties
 #pragma unroll
         for (int g = 0; g < SG; ++g)
 #pragma unroll
@@ -262,6 +343,7 @@ __global__ __launch_bounds__(ST) void emmax_sample_kernel(P p) {
             tot = block_sum_u64(tot, sh, lane, wave);
             thr = radix_threshold<true>(z, zmax, tid, V, thr, (double)tp * (double)tot, sh, lane, wave);
         }
+        kept = thr;
         // Gumbel-max over the kept entries; Philox only for groups with a kept entry
         const uint32_t k0 = (uint32_t)p.seed[b], k1 = (uint32_t)(p.seed[b] >> 32), sub = p.subseq[b];
 #pragma unroll
@@ -284,6 +366,24 @@ __global__ __launch_bounds__(ST) void emmax_sample_kernel(P p) {
         }
     }
     const int tok = block_argmax(bv, bi, sh, lane, wave);
+    if constexpr (PROC) {   // HF scores (the processed row; z / T on the kept set and -inf off it when sampling) and logits at index step
+        if (p.score_words) {
+            float* sc = (float*)p.score_words[0];
+            float* lg = (float*)p.score_words[1];
+            const int t_max = (int)p.score_words[2], rows = (int)p.score_words[3], r = p.row0 + b;
+            if (step < t_max && r < rows) {
+                const size_t off = ((size_t)step * rows + r) * V;
+                if (sc) {
+                    if (T > 0.f && !dead)
+#pragma unroll
+                        for (int j = 0; j < SG * 4; ++j) z[j] = fkey(z[j]) >= kept ? z[j] : -INFINITY;
+                    store_row(sc + off, z, tid, V);
+                }
+                if (lg)
+                    for (int i = tid; i < V; i += ST) lg[off + i] = row[i];
+            }
+        }
+    }
     if (tid == 0) {
         // (an all-NaN row keeps no entry: the token is -1, its log-probability NaN.  In a step -1 never reaches cur_tok, whose row the next
         // step's embedding gather reads: the row emits pad and is done)
@@ -303,6 +403,13 @@ __global__ __launch_bounds__(ST) void emmax_sample_kernel(P p) {
 int launch_sample(const SampleParams& p, int B, hipStream_t stream) {
     if (B < 1 || p.V < 1 || p.V > EMMAX_SAMPLE_MAX_V || p.ld < p.V) return -1;
     hipLaunchKernelGGL(emmax_sample_kernel<SampleParams>, dim3(B), dim3(ST), 0, stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+int launch_proc_finish(const ProcFinishParams& p, hipStream_t stream) {
+    if (p.f.B < 1 || p.V < 1 || p.V > EMMAX_SAMPLE_MAX_V || p.ld < p.V) return -1;
+    if (p.penalty && (!p.ngram || !p.min_new || !p.hist || !p.hist_len || p.max_prompt < 1)) return -1;
+    hipLaunchKernelGGL(emmax_sample_kernel<ProcFinishParams>, dim3(p.f.B), dim3(ST), 0, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

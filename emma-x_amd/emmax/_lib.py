@@ -43,7 +43,7 @@ class ConfigC(C.Structure):
     ]
 
 
-ABI_VERSION = 7   # EMMAX_ABI_VERSION of include/emmax.h this binding was written against
+ABI_VERSION = 8   # EMMAX_ABI_VERSION of include/emmax.h this binding was written against
 
 # name -> (restype, argtypes): exactly the entry points of include/emmax.h
 SIGNATURES = {
@@ -127,6 +127,11 @@ SIGNATURES = {
     "emmax_session_sampling": (C.c_int, [_vp]),
     "emmax_session_logprobs": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "emmax_slot_logprobs": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp]),
+    "emmax_session_set_processing": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "emmax_slots_set_processing_staged": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "emmax_session_clear_processing": (C.c_int, [_vp, _vp]),
+    "emmax_session_processing": (C.c_int, [_vp]),
+    "emmax_session_set_scores": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

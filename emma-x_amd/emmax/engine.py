@@ -125,6 +125,7 @@ class EmmaxEngine:
                                                         ws.value, self.kv.data_ptr(), kv.value, C.byref(self._session)),
                        "emmax_session_create_ex")
         assert bool(self.lib.emmax_session_exact(self._session)) == bool(self.exact)
+        self._score_bufs = None   # a new session binds no scores
         self.max_batch, self.max_prompt, self.max_ctx, self.stage_rows = max_batch, max_prompt, max_ctx, int(stage_rows)
 
     def ensure_stage_rows(self, n: int) -> None:
@@ -329,6 +330,65 @@ class EmmaxEngine:
     def sampling(self) -> bool:
         return self.lib.emmax_session_sampling(self._session) == 1
 
+    # ---- logits processors and scores inside the decode step (include/emmax.h, ABI 8) --------------------------------------
+    @staticmethod
+    def _processing_arrays(params, n: Optional[int] = None):
+        """Host arrays (penalty, ngram, min_new) of len(params) rows: one LogitsProcessing for all rows needs `n`."""
+        from .sampling import LogitsProcessing, _per_row
+
+        ps = _per_row(params, n if n is not None else (len(params) if isinstance(params, (list, tuple)) else 1), "processing")
+        if not all(isinstance(p, LogitsProcessing) for p in ps):
+            raise ValueError("set_processing: params must be LogitsProcessing")
+        k = len(ps)
+        return (k, (C.c_float * k)(*[float(p.repetition_penalty) for p in ps]), (C.c_int32 * k)(*[int(p.no_repeat_ngram_size) for p in ps]),
+                (C.c_int32 * k)(*[int(p.min_new_tokens) for p in ps]))
+
+    def set_processing(self, params, row0: int = 0, n: Optional[int] = None) -> None:
+        """Apply the logits processors to rows row0.. in the decode step from now on (turns processing on): one LogitsProcessing per row
+        (or one for `n` rows).  Precedes the prefill whose tokens it governs (the prefill keeps the rows' prompt ids)."""
+        k, pen, ng, mn = self._processing_arrays(params, n)
+        _lib.check(self.lib.emmax_session_set_processing(self._session, int(row0), k, pen, ng, mn, _lib.current_stream()),
+                   "emmax_session_set_processing")
+
+    def set_processing_staged(self, params, n: Optional[int] = None) -> None:
+        """set_processing for the requests of the next slots_prefill_staged (call inside `with engine.admission():`, before it)."""
+        k, pen, ng, mn = self._processing_arrays(params, n)
+        _lib.check(self.lib.emmax_slots_set_processing_staged(self._session, k, pen, ng, mn, _lib.current_stream()),
+                   "emmax_slots_set_processing_staged")
+
+    def clear_processing(self) -> None:
+        """Processing off: with scores unbound and sampling off the session launches exactly what a greedy session launches."""
+        _lib.check(self.lib.emmax_session_clear_processing(self._session, _lib.current_stream()), "emmax_session_clear_processing")
+
+    @property
+    def processing(self) -> bool:
+        return self.lib.emmax_session_processing(self._session) == 1
+
+    def set_scores(self, scores: Optional[torch.Tensor], logits: Optional[torch.Tensor], max_new: int = 0, rows: int = 0) -> None:
+        """Bind fp32 [max_new, rows, vocab] device buffers that the decode step fills with HF's `scores` (processed rows) / `logits` (raw
+        rows) at each emitted token's index; `rows` must be the batch of the next prefill (the step stores row b of that batch at [t, b]).
+        Either buffer may be None, both None unbinds.  The engine keeps the tensors alive while they are bound."""
+        if scores is None and logits is None:
+            _lib.check(self.lib.emmax_session_set_scores(self._session, None, None, 0, _lib.current_stream()), "emmax_session_set_scores")
+            self._score_bufs = None
+            return
+        V = self.cfg.llm.vocab_size
+        if int(rows) < 1 or int(max_new) < 1:
+            raise ValueError(f"set_scores: max_new ({max_new}) and rows ({rows}) must be >= 1")
+        for t in (scores, logits):
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (int(max_new), int(rows), V)
+                                  or t.device != torch.device(self.device)):
+                raise ValueError(f"set_scores: buffers must be contiguous fp32 [max_new={max_new}, rows={rows}, {V}] tensors on {self.device}, "
+                                 f"got {tuple(t.shape)} {t.dtype} on {t.device}")
+        _lib.check(self.lib.emmax_session_set_scores(self._session, scores.data_ptr() if scores is not None else None,
+                                                     logits.data_ptr() if logits is not None else None, int(max_new), _lib.current_stream()),
+                   "emmax_session_set_scores")
+        self._score_bufs = (scores, logits)
+
+    @property
+    def scores_bound(self) -> bool:
+        return getattr(self, "_score_bufs", None) is not None
+
     def slot_logprobs(self, slot: int, n: int) -> List[float]:
         """Log-probabilities of the first n tokens of `slot` (sampling on)."""
         out = torch.empty(max(1, n), dtype=torch.float32, device=self.device)
@@ -346,6 +406,7 @@ class EmmaxEngine:
     def slots_open(self, n_slots: int) -> None:
         self.ensure_decode_batch(int(n_slots))
         _lib.check(self.lib.emmax_slots_open(self._session, int(n_slots), _lib.current_stream()), "emmax_slots_open")
+        self._score_bufs = None   # (emmax_slots_open unbinds scores)
         self._n_slots = int(n_slots)
         self._slot_state = torch.empty(2, n_slots, dtype=torch.int32, device=self.device)
 

@@ -27,7 +27,7 @@ from .config import EmmaXConfig, default_norm_stats
 from .engine import EmmaxEngine
 from .policy_parser import Solver
 from .processing import BatchFeature, EmmaXImageProcessor
-from .sampling import SamplingParams, draw_seed
+from .sampling import LogitsProcessing, SamplingParams, draw_seed
 from .prompting import PurePromptBuilder
 from .tokenizer_stub import StubTokenizer
 from .weights import load_hf_state_dict, remap_native_state_dict, synthetic_state_dict, validate_state_dict
@@ -55,6 +55,18 @@ class EmmaXCausalLMOutputWithPast:
     hidden_states: Optional[Tuple[torch.Tensor, ...]] = None
     attentions: Optional[Tuple[torch.Tensor]] = None
     projector_features: Optional[torch.Tensor] = None
+
+
+@dataclass
+class EmmaXGenerateOutput:
+    """generate(..., return_dict_in_generate=True): the fields of HF's GenerateDecoderOnlyOutput this model fills.  scores / logits: one
+    fp32 [B, vocab] device tensor per generated position (output_scores / output_logits), NaN past a row's length; else None."""
+    sequences: torch.Tensor
+    scores: Optional[Tuple[torch.Tensor, ...]] = None
+    logits: Optional[Tuple[torch.Tensor, ...]] = None
+
+    def __getitem__(self, key: str):
+        return getattr(self, key)
 
 
 class KVHandle:
@@ -220,7 +232,8 @@ class EmmaXForActionPrediction:
             pixel_values = torch.cat([pixel_values["dino"], pixel_values["siglip"]], dim=1)
         return eng.vision_encode_pixels(pixel_values)
 
-    def _prefill(self, rows: List[List[int]], pixel_values=None, frames_u8=None, max_new: int = 0, sampling=None) -> torch.Tensor:
+    def _prefill(self, rows: List[List[int]], pixel_values=None, frames_u8=None, max_new: int = 0, sampling=None, processing=None,
+                 scores=None, logits=None) -> torch.Tensor:
         eng = self._need_engine()
         B = len(rows)
         src = pixel_values if pixel_values is not None else frames_u8
@@ -233,9 +246,52 @@ class EmmaXForActionPrediction:
             P = self.config.llm.max_position
         eng.ensure_capacity(B, P, max(max_new, 1))
         patches = self._encode_images(pixel_values, frames_u8)
+        self._set_processing(eng, B, processing, scores, logits, max_new)
         self._set_sampling(eng, B, sampling)
         eng.prefill(rows, patches)
         return patches
+
+    @staticmethod
+    def _set_processing(eng, B: int, processing, scores=None, logits=None, max_new: int = 0) -> None:
+        """Before a prefill: processing = one LogitsProcessing for every row or one per row, None = off; scores / logits = the buffers
+        the step fills (engine.set_scores), None = unbound.  What the call does not ask for is cleared from the session."""
+        if scores is not None or logits is not None:
+            EmmaXForActionPrediction._check_score_buffers(scores, logits, max_new, B, eng.cfg.llm.vocab_size)
+        if processing is not None:
+            eng.set_processing(processing, n=B)
+        elif getattr(eng, "processing", False):
+            eng.clear_processing()
+        if scores is not None or logits is not None:
+            eng.set_scores(scores, logits, max_new, rows=B)
+        elif getattr(eng, "scores_bound", False):
+            eng.set_scores(None, None)
+
+    @staticmethod
+    def _check_score_buffers(scores, logits, max_new: int, B: int, V: int) -> None:
+        """scores / logits must be fp32 [max_new, B, V] tensors: the step stores row b's entry t at [t, b], so any other batch dimension
+        would be written past its end or scrambled."""
+        for name, t in (("scores", scores), ("logits", logits)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (int(max_new), B, V):
+                got = f"{tuple(t.shape)} {t.dtype}" if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"{name} must be a contiguous fp32 [max_new_tokens={max_new}, B={B}, vocab={V}] tensor, got {got}")
+
+    @staticmethod
+    def _processing_args(rows, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None,
+                         min_length=None) -> Optional[LogitsProcessing]:
+        """HF generate's processor arguments -> the LogitsProcessing every row gets (None: HF would add no processor).  min_length L (a
+        total, prompt included) becomes min_new_tokens max(min_new_tokens, L - P_max), P_max the longest prompt, as HF counts it on a
+        padded batch."""
+        proc = LogitsProcessing(repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty,
+                                no_repeat_ngram_size=0 if no_repeat_ngram_size is None else no_repeat_ngram_size,
+                                min_new_tokens=0 if min_new_tokens is None else min_new_tokens)   # (validates)
+        if min_length is not None:
+            if isinstance(min_length, bool) or not isinstance(min_length, (int, np.integer)) or min_length < 0:
+                raise ValueError(f"min_length must be an integer >= 0, got {min_length}")
+            m = max(int(proc.min_new_tokens), int(min_length) - max(len(r) for r in rows))
+            proc = LogitsProcessing(proc.repetition_penalty, proc.no_repeat_ngram_size, m)
+        return None if proc.neutral else proc
 
     @staticmethod
     def _set_sampling(eng, B: int, sampling) -> None:
@@ -290,6 +346,7 @@ class EmmaXForActionPrediction:
             assert inputs_embeds is None, "Missing `input_ids` in language-only forward!"
             assert past_key_values is None, "Unexpected key `past_key_values` provided during language-only forward!"
             eng.ensure_capacity(len(rows), max(len(r) for r in rows), self.cache_reserve if use_cache else 1)
+            self._set_processing(eng, len(rows), None)   # (as _prefill: what an earlier generate left in the session is cleared)
             eng.prefill(rows, None)
             per_row = eng.prefill_logits()
             same = len({t.shape[0] for t in per_row}) == 1
@@ -307,15 +364,27 @@ class EmmaXForActionPrediction:
 
     @torch.inference_mode()
     def generate_ids(self, rows: List[List[int]], pixel_values=None, frames_u8=None, max_new_tokens: int = 512,
-                     stop_on_eos: bool = True, sampling=None, return_logprobs: bool = False):
+                     stop_on_eos: bool = True, sampling=None, return_logprobs: bool = False, processing=None, scores=None, logits=None):
         """Decode every row: greedy, or sampled in the step with `sampling` (one SamplingParams for all rows or one per row; row b draws
-        with subseq b).  Returns device tensors (new_ids int32 [B,max_new] pad-filled, lens int32 [B]), and with return_logprobs (sampling
-        only) the fp32 [B,max_new] log-probabilities of the emitted tokens."""
+        with subseq b).  `processing` (one LogitsProcessing for all rows or one per row) applies HF's repetition penalty / n-gram ban /
+        min-new-tokens in the step first.  `scores` / `logits`: fp32 [max_new, B, vocab] device buffers the step fills with HF's scores /
+        raw logits at each emitted token's index (others are not written); any other shape is refused before the engine is touched, and
+        the buffers are unbound again when the call returns.  Returns device tensors (new_ids int32 [B,max_new] pad-filled,
+        lens int32 [B]), and with return_logprobs (sampling only) the fp32 [B,max_new] log-probabilities of the emitted tokens."""
         eng = self._need_engine()
         if return_logprobs and sampling is None:
             raise ValueError("return_logprobs needs sampling (log-probabilities are kept by the sampled step only)")
-        self._prefill(rows, pixel_values, frames_u8, max_new=max_new_tokens, sampling=sampling)
-        return eng.generate(max_new_tokens, stop_on_eos, return_logprobs=return_logprobs)
+        if processing is not None:
+            ps = processing if isinstance(processing, (list, tuple)) else [processing]
+            if not all(isinstance(p, LogitsProcessing) for p in ps):
+                raise ValueError("processing must be LogitsProcessing (one, or one per row)")
+        self._check_score_buffers(scores, logits, max_new_tokens, len(rows), self.config.llm.vocab_size)
+        self._prefill(rows, pixel_values, frames_u8, max_new=max_new_tokens, sampling=sampling, processing=processing, scores=scores,
+                      logits=logits)
+        out = eng.generate(max_new_tokens, stop_on_eos, return_logprobs=return_logprobs)
+        if scores is not None or logits is not None:
+            eng.set_scores(None, None)   # the buffers are the caller's now: no later step or prefill writes into them
+        return out
 
     def _max_new(self, rows, max_new_tokens, max_length, min_length, had_max_new: bool = True) -> int:
         """HF length semantics: `max_length` counts the PROMPT too (as HF counts it: the text ids, not the patch rows) and only
@@ -335,16 +404,29 @@ class EmmaXForActionPrediction:
     def generate(self, input_ids=None, pixel_values=None, attention_mask=None, max_new_tokens: Optional[int] = None, do_sample: bool = False,
                  min_length: int = 1, temperature: Optional[float] = None, frames_u8=None, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, seed: Optional[int] = None, generator: Optional[torch.Generator] = None,
-                 **kwargs) -> torch.Tensor:
+                 repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
+                 output_scores: bool = False, output_logits: bool = False, return_dict_in_generate: bool = False, **kwargs):
         """HF-style: returns LongTensor [B, P + T] = prompt ++ generated (right-padded with pad_token_id).  do_sample=True draws every token
         in the decode step (include/emmax.h: emmax_session_set_sampling) with temperature / top_k / top_p (HF defaults 1.0 / 50 / 1.0 when
-        unset); row b draws with (seed, subseq b), seed None = draw_seed(generator)."""
+        unset); row b draws with (seed, subseq b), seed None = draw_seed(generator).  repetition_penalty / no_repeat_ngram_size /
+        min_new_tokens / min_length are applied in the step as HF's processors (emmax_session_set_processing).  return_dict_in_generate=True
+        returns an EmmaXGenerateOutput: `sequences` (the tensor), and with output_scores / output_logits a tuple of T = max(lens) fp32
+        [B, vocab] device tensors each (NaN past a row's length)."""
         if kwargs.get("num_beams", 1) != 1:
             raise NotImplementedError("beam search is outside the hot path")
         sampling = self._sampling_args(do_sample, temperature, top_k, top_p, seed, generator)
         rows = self._rows(input_ids, attention_mask)
-        max_new_tokens = self._max_new(rows, max_new_tokens, kwargs.get("max_length"), min_length)
-        new_ids, lens = self.generate_ids(rows, pixel_values, frames_u8, max_new_tokens, sampling=sampling)
+        processing = self._processing_args(rows, repetition_penalty, no_repeat_ngram_size, min_new_tokens, min_length)
+        max_new_tokens = self._max_new(rows, max_new_tokens, kwargs.get("max_length"), None)   # (min_length is in `processing`)
+        want_sc, want_lg = bool(return_dict_in_generate and output_scores), bool(return_dict_in_generate and output_logits)
+        sc = lg = None
+        if want_sc or want_lg:
+            eng = self._need_engine()
+            shape = (max_new_tokens, len(rows), self.config.llm.vocab_size)
+            sc = torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device) if want_sc else None
+            lg = torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device) if want_lg else None
+        new_ids, lens = self.generate_ids(rows, pixel_values, frames_u8, max_new_tokens, sampling=sampling, processing=processing, scores=sc,
+                                          logits=lg)
         new_ids, lens = new_ids.cpu(), lens.cpu().tolist()
         T = max(lens)
         P = max(len(r) for r in rows)
@@ -352,7 +434,15 @@ class EmmaXForActionPrediction:
         for b, r in enumerate(rows):
             seq = r + new_ids[b, : lens[b]].tolist()
             out[b, : len(seq)] = torch.tensor(seq, dtype=torch.long)
-        return out
+        if not return_dict_in_generate:
+            return out
+        return EmmaXGenerateOutput(sequences=out, scores=tuple(sc[t] for t in range(T)) if want_sc else None,
+                                   logits=tuple(lg[t] for t in range(T)) if want_lg else None)
+
+    def _kw_processing(self, rows, kwargs) -> Optional[LogitsProcessing]:
+        """The processor arguments of a **kwargs that the reference forwards to HF generate."""
+        return self._processing_args(rows, kwargs.get("repetition_penalty"), kwargs.get("no_repeat_ngram_size"), kwargs.get("min_new_tokens"),
+                                     kwargs.get("min_length"))
 
     # ------------------------------------------------------------------------------------------------------------------
     # action APIs
@@ -371,7 +461,9 @@ class EmmaXForActionPrediction:
         # the reference forwards **kwargs to HF generate (modeling_prismatic.py:519): do_sample / temperature / top_k / top_p are honoured
         sampling = self._sampling_args(bool(kwargs.get("do_sample", False)), kwargs.get("temperature"), kwargs.get("top_k"), kwargs.get("top_p"),
                                        kwargs.get("seed"), kwargs.get("generator"))
-        new_ids, lens = self.generate_ids(rows, kwargs.get("pixel_values"), kwargs.get("frames_u8"), max_new_tokens=dim, sampling=sampling)
+        processing = self._kw_processing(rows, kwargs)
+        new_ids, lens = self.generate_ids(rows, kwargs.get("pixel_values"), kwargs.get("frames_u8"), max_new_tokens=dim, sampling=sampling,
+                                          processing=processing)
         full = rows[0] + new_ids[0, : int(lens[0])].cpu().tolist()
         predicted = np.array(full[-dim:])
         normalized = token_ids_to_actions(predicted, self.vocab_size, self.bin_centers)
@@ -422,9 +514,10 @@ class EmmaXForActionPrediction:
             rows = self._rows(inputs["input_ids"], inputs.get("attention_mask"))
             if len(rows) != 1:
                 raise ValueError("Generation with batch size > 1 is not currently supported!")
-            max_new = self._max_new(rows, kwargs.get("max_new_tokens", None if "max_length" in kwargs else 512), kwargs.get("max_length"),
-                                    kwargs.get("min_length"))
-            new_ids, lens = self.generate_ids(rows, inputs.get("pixel_values"), inputs.get("frames_u8"), max_new_tokens=max_new)
+            processing = self._kw_processing(rows, kwargs)
+            max_new = self._max_new(rows, kwargs.get("max_new_tokens", None if "max_length" in kwargs else 512), kwargs.get("max_length"), None)
+            new_ids, lens = self.generate_ids(rows, inputs.get("pixel_values"), inputs.get("frames_u8"), max_new_tokens=max_new,
+                                              processing=processing)
             actions, text = self._postprocess(new_ids[0, : int(lens[0])].cpu().tolist(), tokenizer, "act")
             return actions[0], text
         # native form
@@ -449,19 +542,21 @@ class EmmaXForActionPrediction:
             raise ValueError(f"Unsupported generate_actions type `{vals['type']}` (expected 'act' or 'pos')")
         enc = tokenizer(vals["prompt_text"], truncation=True, return_tensors="pt")
         rows = self._rows(enc.input_ids)
-        max_new = self._max_new(rows, kwargs.get("max_new_tokens"), kwargs.get("max_length"), kwargs.get("min_length"))
+        processing = self._kw_processing(rows, kwargs)
+        max_new = self._max_new(rows, kwargs.get("max_new_tokens"), kwargs.get("max_length"), None)
         feat = self.image_transform(vals["image"])
-        new_ids, lens = self.generate_ids(rows, feat["pixel_values"], feat.get("frames_u8"), max_new_tokens=max_new)
+        new_ids, lens = self.generate_ids(rows, feat["pixel_values"], feat.get("frames_u8"), max_new_tokens=max_new, processing=processing)
         return self._postprocess(new_ids[0, : int(lens[0])].cpu().tolist(), tokenizer, vals["type"])
 
     @torch.inference_mode()
     def generate_actions_batch(self, frames_u8: torch.Tensor, prompt_rows: Sequence[Sequence[int]], max_new_tokens: int = 512,
-                               stop_on_eos: bool = True, tokenizer=None, sampling=None):
+                               stop_on_eos: bool = True, tokenizer=None, sampling=None, processing=None):
         """Batched extension: returns (actions f32 [B,7], new_ids int32 [B,T], lens int32 [B]).
 
         With `tokenizer` each row goes ids -> text -> Solver exactly like the bs=1 path; without it the ids-level
-        stand-in `actions_from_ids` is used (synthetic weights / throughput runs).  `sampling`: as generate_ids (None = greedy)."""
-        new_ids, lens = self.generate_ids([list(r) for r in prompt_rows], None, frames_u8, max_new_tokens, stop_on_eos, sampling=sampling)
+        stand-in `actions_from_ids` is used (synthetic weights / throughput runs).  `sampling` / `processing`: as generate_ids (None = off)."""
+        new_ids, lens = self.generate_ids([list(r) for r in prompt_rows], None, frames_u8, max_new_tokens, stop_on_eos, sampling=sampling,
+                                          processing=processing)
         ids_h, lens_h = new_ids.cpu(), lens.cpu().tolist()
         acts = np.zeros((len(lens_h), 7), dtype=np.float32)
         stats = self.get_action_stats(None)

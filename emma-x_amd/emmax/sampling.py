@@ -42,6 +42,34 @@ class SamplingParams:
             raise ValueError(f"seed must be a 64-bit unsigned integer, got {self.seed}")
 
 
+MAX_NGRAM = 32   # EMMAX_MAX_NGRAM (emma-x_amd/csrc/kernels.h): the largest no_repeat_ngram_size
+
+
+@dataclass(frozen=True)
+class LogitsProcessing:
+    """HF generate's repetition_penalty / no_repeat_ngram_size / min_new_tokens, applied in the decode step before the warpers
+    (include/emmax.h: emmax_session_set_processing).  The defaults are HF's neutral values: processing off."""
+    repetition_penalty: float = 1.0   # finite, > 0; 1 = off
+    no_repeat_ngram_size: int = 0     # 0 = off, <= MAX_NGRAM
+    min_new_tokens: int = 0           # EOS is banned while fewer tokens were emitted
+
+    def __post_init__(self):
+        p = float(self.repetition_penalty)
+        if not math.isfinite(p) or not p > 0.0:
+            raise ValueError(f"repetition_penalty must be a finite float > 0, got {self.repetition_penalty}")
+        n = self.no_repeat_ngram_size
+        if isinstance(n, bool) or int(n) != n or not 0 <= int(n) <= MAX_NGRAM:
+            raise ValueError(f"no_repeat_ngram_size must be an integer in 0..{MAX_NGRAM}, got {n}")
+        m = self.min_new_tokens
+        if isinstance(m, bool) or int(m) != m or int(m) < 0:
+            raise ValueError(f"min_new_tokens must be an integer >= 0, got {m}")
+
+    @property
+    def neutral(self) -> bool:
+        """No processor would change a row (HF adds none for these values)."""
+        return float(self.repetition_penalty) == 1.0 and int(self.no_repeat_ngram_size) == 0 and int(self.min_new_tokens) == 0
+
+
 def draw_seed(generator: Optional[torch.Generator] = None) -> int:
     """A 64-bit seed from `generator` (default: torch's global CPU generator, so torch.manual_seed(s) fixes it)."""
     hi = int(torch.randint(0, 1 << 32, (1,), generator=generator, dtype=torch.int64))

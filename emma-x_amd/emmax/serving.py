@@ -28,6 +28,7 @@ class Request:
     prompt_ids: Sequence[int]
     max_new_tokens: int = 512
     sampling: Any = None   # emmax.sampling.SamplingParams: drawn in the decode step with the request's seed (None: draw_seed()) and subseq 0; None = greedy
+    processing: Any = None   # emmax.sampling.LogitsProcessing: HF's repetition penalty / n-gram ban / min-new-tokens in the decode step; None = off
 
 
 @dataclass
@@ -102,6 +103,7 @@ class SlotScheduler:
         self._pending = None                         # [staged handle, [(request, t_submit), ...], committed so far] of the staged batch
         self.overlapped_admissions = 0
         self._sampling = False                       # some request of the current run samples (run)
+        self._processing = False                     # some request of the current run has logits processing (run)
         # a staged batch is at most max(stage_batch, free slots) <= n_slots requests: the session needs that many staging rows
         # (they cost KV pages, so a session only has them when a scheduler asks: engine.ensure_stage_rows re-creates it if needed)
         if self.overlap and hasattr(engine, "ensure_stage_rows"):
@@ -127,6 +129,19 @@ class SlotScheduler:
             params.append(p)
             seeds.append(p.seed)
         return params, seeds, [0] * len(reqs)
+
+    def _set_processing(self, reqs, row0: int = 0, staged: bool = False) -> None:
+        """A serve where some request has processing: every prefill is preceded by its rows' processors (neutral ones for the others).
+        Other serves call nothing here.  Runs before _set_sampling, so sampling's call still comes right before the prefill."""
+        if not self._processing:
+            return
+        from .sampling import LogitsProcessing
+
+        params = [r.processing if r.processing is not None else LogitsProcessing() for r in reqs]
+        if staged:
+            self.engine.set_processing_staged(params)
+        else:
+            self.engine.set_processing(params, row0=row0)
 
     def _set_sampling(self, reqs, row0: int = 0, staged: bool = False) -> None:
         """A serve where some request samples: every prefill is preceded by its rows' parameters.  Greedy-only serves call nothing here."""
@@ -154,11 +169,13 @@ class SlotScheduler:
             while j < take and slots[j] == slots[j - 1] + 1:
                 j += 1
             if j - i > 1 and hasattr(self.engine, "slots_prefill"):
+                self._set_processing([batch[k][0] for k in range(i, j)], row0=slots[i])
                 self._set_sampling([batch[k][0] for k in range(i, j)], row0=slots[i])
                 self.engine.slots_prefill(slots[i], [list(batch[k][0].prompt_ids) for k in range(i, j)], embeds[i:j] if embeds[i] is not None else None,
                                           [batch[k][0].max_new_tokens for k in range(i, j)])
             else:
                 for k in range(i, j):
+                    self._set_processing([batch[k][0]], row0=slots[k])
                     self._set_sampling([batch[k][0]], row0=slots[k])
                     self.engine.slot_prefill(slots[k], list(batch[k][0].prompt_ids), embeds[k], batch[k][0].max_new_tokens)
             t_adm = self.clock()
@@ -190,6 +207,7 @@ class SlotScheduler:
         try:
             with self.engine.admission():
                 embeds = self._encode_for(batch)
+                self._set_processing([r for r, _ in batch], staged=True)
                 self._set_sampling([r for r, _ in batch], staged=True)
                 staged = self.engine.slots_prefill_staged([list(r.prompt_ids) for r, _ in batch], embeds if embeds[0] is not None else None,
                                                           [r.max_new_tokens for r, _ in batch])
@@ -242,11 +260,14 @@ class SlotScheduler:
 
     def run(self) -> List[Result]:
         """Serve until the queue is empty and every slot is idle.  Returns the results in completion order.  When some queued request
-        samples, the session samples for the whole run (greedy requests at temperature 0: their greedy ids) and is greedy again after it."""
+        samples, the session samples for the whole run (greedy requests at temperature 0: their greedy ids) and is greedy again after it.  Logits processing likewise (requests without it get neutral processors)."""
         self._sampling = any(r.sampling is not None for r, _ in self.queue)
+        self._processing = any(getattr(r, "processing", None) is not None for r, _ in self.queue)
         try:
             return self._run()
         finally:
+            if self._processing:
+                self.engine.clear_processing()
             if self._sampling:
                 self.engine.clear_sampling()
 

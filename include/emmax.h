@@ -37,8 +37,10 @@ extern "C" {
  *   added, the lab-only entry points (persistent layer chain, in-attention split merge) removed;  4: round 5 -- emmax_session_*_ex (staging rows
  *   are asked for, the plain calls give none), decode batches / slot counts up to 64 (emmax_model_max_decode_batch);  5: exact numerics (emmax_session_exact, emmax_op_x_*);
  *   6: emmax_op_sample (seeded sampling over rows of logits);  7: sampling inside the decode step (emmax_session_set_sampling and the calls
- *   around it), the workspace grew the per-row sampling state. */
-#define EMMAX_ABI_VERSION 7
+ *   around it), the workspace grew the per-row sampling state;  8: logits processors and scores inside the decode step
+ *   (emmax_session_set_processing, emmax_session_set_scores and the calls around them), the workspace grew the per-row processing state and
+ *   prompt ids. */
+#define EMMAX_ABI_VERSION 8
 
 typedef enum emmax_status {
     EMMAX_OK = 0,
@@ -283,6 +285,43 @@ int emmax_session_clear_sampling(emmax_session* s, emmax_stream stream);
 int emmax_session_sampling(const emmax_session* s);
 int emmax_session_logprobs(emmax_session* s, int max_new, float* out_dev, emmax_stream stream);
 int emmax_slot_logprobs(emmax_session* s, int slot, float* out_dev, int n, emmax_stream stream);
+
+/* ---- logits processors and scores inside the decode step (ABI 8) ----------------------------------------------------
+ * The semantics of transformers 5.15's processors (generation/utils.py: _get_logits_processor), applied in HF's order before the warpers
+ * and the draw of ABI 7.  Per row, the history H is the row's prompt ids (the text ids its prefill got, BOS included; the patch rows carry
+ * no ids) followed by the ids the row has emitted (out_ids[0 .. n_out)):
+ *   repetition penalty p   every distinct id of H: x < 0 ? x * p : x / p (fp32, p as fp32), once per id.  p = 1: off.
+ *   no_repeat_ngram_size n every id that would complete an n-gram already in H is -inf.  n = 0: off; n <= EMMAX_MAX_NGRAM (32).
+ *   min_new_tokens m       the EOS logit (eos_id) is -inf while n_out < m.  (HF min_length L is m = max(min_new_tokens, L - P_max), P_max
+ *                          the longest prompt of the call: the Python layer folds it.)
+ * Then temperature / top_k / top_p and the draw as in ABI 7 (sampling on), else the argmax of the processed row.  Log-probabilities keep
+ * their ABI 7 meaning: l_tok - logsumexp(l) over the RAW logits.  A row with no finite entry left emits pad_id and is done.  Known
+ * differences from HF: H is each row's own, unpadded; the patch rows are not in it (HF's input_ids for this model hold none either).
+ * A session processes once emmax_session_set_processing (or emmax_slots_set_processing_staged) has run, and keeps scores once
+ * emmax_session_set_scores bound a buffer.  Either way every lm-head that emits a token writes the rows' fp32 logits and the step ends in
+ * the processing finish (same launch count); the captured step graph is keyed on greedy / sampled / processing, and changed parameters or
+ * score buffers re-capture nothing (they are device words).  With processing and scores off the session launches exactly what it launched
+ * before.  Every prefill (emmax_prefill*, emmax_slot_prefill, emmax_slots_prefill*) keeps its rows' prompt ids while processing is on:
+ * set processing before the prefill whose tokens it governs.
+ *   emmax_session_set_processing       rows row0 .. row0 + n - 1 (slots when request slots are open); host arrays of n values, checked here:
+ *                                      penalty finite and > 0, 0 <= ngram <= 32, min_new >= 0 -- else EMMAX_ERR_INVALID.  Synchronises the
+ *                                      stream.  Turns processing on.
+ *   emmax_slots_set_processing_staged  the same for the n requests of the next emmax_slots_prefill_staged; emmax_slots_commit moves a
+ *                                      request's parameters and prompt ids with the rest of its state.
+ *   emmax_session_clear_processing     processing off.  emmax_session_processing: 1 on, 0 off, -1 null session.
+ *   emmax_session_set_scores           binds fp32 [max_new][B][vocab] buffers for the next generation (B = the rows of the next prefill; bind
+ *                                      before it: the prefill emits token 0; a later prefill of another batch size unbinds them).  scores[t][b] = HF's `scores`: the processed row of a greedy
+ *                                      row; z / T on the kept set and -inf elsewhere for a sampled one.  logits[t][b] = the raw lm-head row.
+ *                                      t = the row's generation index; entries of tokens not emitted are not written.  Either may be NULL;
+ *                                      both NULL unbinds.  EMMAX_ERR_STATE while request slots are open; emmax_slots_open unbinds.
+ * While processing is on, emmax_set_current_tokens returns EMMAX_ERR_STATE (forced tokens would be missing from H). */
+int emmax_session_set_processing(emmax_session* s, int row0, int n, const float* penalty_host, const int32_t* ngram_host, const int32_t* min_new_host,
+                                 emmax_stream stream);
+int emmax_slots_set_processing_staged(emmax_session* s, int n, const float* penalty_host, const int32_t* ngram_host, const int32_t* min_new_host,
+                                      emmax_stream stream);
+int emmax_session_clear_processing(emmax_session* s, emmax_stream stream);
+int emmax_session_processing(const emmax_session* s);
+int emmax_session_set_scores(emmax_session* s, float* scores_dev, float* logits_dev, int max_new, emmax_stream stream);
 
 /* ---- single-kernel entry points (parity tests + micro-benchmarks) -------------------------------------------------- */
 /* C[M,N] = epilogue(A[M,K] @ W[N,K]^T): bf16 in, fp32 accumulate on MFMA.  K % 64 == 0, N % 128 == 0.

@@ -1,10 +1,13 @@
-"""ms per decode step of generate with sampling in the step (include/emmax.h ABI 7) against the greedy step, at the shapes of the headline
-bench (Emma-X-7B synthetic weights, 512-token prompts, 512 new tokens) and batches 1, 8 and 64.
+"""ms per decode step of generate with sampling (include/emmax.h ABI 7) or logits processing / scores (ABI 8) in the step against the
+greedy step, at the shapes of the headline bench (Emma-X-7B synthetic weights, 512-token prompts, 512 new tokens) and batches 1, 8 and 64.
 
   greedy   sampling off: the kernels of a session that never sampled
   t0       sampling on, every row at temperature 0 (the argmax of the fp32 logit rows)
   hf       temperature 1, top-k 50 (the HF defaults)
   topp     temperature 1, top-p 0.9
+  pgreedy  repetition penalty 1.1 and no_repeat_ngram_size 3, greedy (the processing finish)
+  phf      the same with the HF-default draw
+  pscores  pgreedy with output_scores: the processed rows stored at every step ([new tokens, B, vocab] fp32)
 
 EOS is disabled (as in bench.py), so every row decodes every step.  The time of one generate call after its prefill, divided by its decode
 steps (new tokens - 1), median over --reps calls.  Prints one JSON line per (batch, mode)."""
@@ -21,10 +24,14 @@ import torch
 
 from emmax.config import EmmaXConfig
 from emmax.modeling import EmmaXForActionPrediction
-from emmax.sampling import SamplingParams
+from emmax.sampling import LogitsProcessing, SamplingParams
 
-MODES = {"greedy": None, "t0": SamplingParams(0.0, 0, 1.0, seed=1), "hf": SamplingParams(1.0, 50, 1.0, seed=1),
-         "topp": SamplingParams(1.0, 0, 0.9, seed=1)}
+HF = SamplingParams(1.0, 50, 1.0, seed=1)
+PROC = LogitsProcessing(1.1, 3, 0)
+# mode -> (sampling, processing, scores)
+MODES = {"greedy": (None, None, False), "t0": (SamplingParams(0.0, 0, 1.0, seed=1), None, False), "hf": (HF, None, False),
+         "topp": (SamplingParams(1.0, 0, 0.9, seed=1), None, False), "pgreedy": (None, PROC, False), "phf": (HF, PROC, False),
+         "pscores": (None, PROC, True)}
 
 
 def main():
@@ -49,8 +56,10 @@ def main():
     for B in batches:
         for mode in args.modes.split(","):
             times = []
+            samp, proc, want_scores = MODES[mode]
+            sc = torch.empty(T, B, cfg.llm.vocab_size, dtype=torch.float32, device=dev) if want_scores else None
             for rep in range(args.reps + 1):   # (the first call warms up: graph capture, first-touch of the logit rows)
-                model._prefill(prompts[:B], frames_u8=frames[:B], max_new=T, sampling=MODES[mode])
+                model._prefill(prompts[:B], frames_u8=frames[:B], max_new=T, sampling=samp, processing=proc, scores=sc)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 ids, lens = eng.generate(T, stop_on_eos=False)
@@ -60,7 +69,10 @@ def main():
             assert int(lens.min()) == T, "a row ended early"
             ms = 1e3 * float(np.median(times)) / (T - 1)
             print(json.dumps({"batch": B, "mode": mode, "ms_per_step": round(ms, 4), "prompt": P, "new_tokens": T, "reps": args.reps}), flush=True)
+            del sc
+            eng.set_scores(None, None)
     eng.clear_sampling()
+    eng.clear_processing()
 
 
 if __name__ == "__main__":
