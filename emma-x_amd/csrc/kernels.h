@@ -417,6 +417,67 @@ struct ProcFinishParams : SampleFinishParams {
     const uint64_t* score_words;   // null: no scores.  Else device words {scores f32*, logits f32*, max_new, rows}: buffers [max_new][rows][V]
 };
 int launch_proc_finish(const ProcFinishParams& p, hipStream_t stream);
+// ---- beam.hip: beam search in the decode step (include/emmax.h, ABI 9) ----
+#ifndef EMMAX_MAX_BEAMS
+#define EMMAX_MAX_BEAMS 8
+#endif
+// per-row candidates: block b reads logits row b, writes its lse and its best 2K (acc, token) pairs, best first, at slot b (prefill form:
+// block g reads the prefill's row g with score 0 and writes slot g * K)
+struct BeamRowParams {
+    const float* logits;        // f32 [blocks][ld]
+    int ld, V, K, is_prefill;
+    const float* run_score;     // [rows] running scores (not read at a prefill)
+    const int32_t* done;        // [rows]: a done group's rows are skipped
+    const int32_t* n_out;       // [rows]: the step's index
+    float* cand_acc;            // [rows][2 EMMAX_MAX_BEAMS]
+    int32_t* cand_tok;          // ... token, -1 = no candidate
+    float* row_lse;             // [rows]
+    const uint64_t* score_words;   // null, or the device words of emmax_session_set_scores: the raw row goes to logits[step][slot]
+};
+int launch_beam_rows(const BeamRowParams& p, int blocks, hipStream_t stream);
+// per-group merge + HF's beam state + trace + per-row decode state + page-table gather (one wave per group)
+struct BeamMergeParams {
+    int K, V, is_prefill, eos_id, pad_id, max_pages, max_out, tr_ld;
+    int es_mode;                // early_stopping: 0 False, 1 True, 2 "never"
+    int lp_pos;                 // length_penalty > 0
+    const float* pw;            // [max_out + 1]: fp32(n ** length_penalty)
+    const float* cand_acc;
+    const int32_t* cand_tok;
+    const float* row_lse;
+    float *run_score, *fin_score;
+    int32_t *fin_flag, *fin_t, *fin_par, *fin_tok;   // the kept hypotheses: finished flag, the step, parent beam and token they ended with
+    int32_t* grp_state;         // [groups][4]: {early-stop heuristic unsatisfied, done, next free page, -}
+    int32_t *cur_tok, *ctx_len, *done, *n_out;
+    const int32_t* max_new_p;
+    int32_t *page_table, *spare, *copy_src, *copy_dst, *copy_ntok;
+    int32_t *tr_tok, *tr_par;   // [max_out][tr_ld]
+    float *tr_score, *tr_lse;
+    int32_t* tc_idx;            // [max_out][2 tr_ld]
+    float* tc_acc;
+    int S[EMMAX_MAX_DECODE_BATCH];   // prefill form: the groups' prompt contexts
+};
+int launch_beam_merge(const BeamMergeParams& p, int groups, hipStream_t stream);
+// the partial-page copies the merge listed, over every plane of every layer of the paged cache
+struct BeamCopyParams {
+    char* kv;
+    long long layer_stride;     // bytes
+    int n_planes, Hkv, n_pages;
+    long long plane_off[4];     // bytes from the layer's base
+    int plane_rb[4];            // bytes per (token, kv head) row
+    const int32_t *copy_src, *copy_dst, *copy_ntok;
+};
+int launch_beam_copy(const BeamCopyParams& p, int rows, int n_layers, hipStream_t stream);
+int launch_beam_reset(int rows, int K, float* run_score, float* fin_score, int32_t* fin_flag, int32_t* fin_t, int32_t* fin_par, int32_t* fin_tok,
+                      int32_t* grp_state, int32_t* copy_src, hipStream_t stream);
+int launch_beam_pages(int32_t* pt, int rows, int max_pages, int step, hipStream_t stream);
+struct BeamResolveParams {
+    int rows, K, max_out, max_new, tr_ld, pad_id;
+    const int32_t *fin_t, *fin_par, *fin_tok, *tr_tok, *tr_par;
+    const float* fin_score;
+    int32_t *seq, *bidx, *len;  // [rows][max_out], [rows][max_out], [rows]
+    float* score;
+};
+int launch_beam_resolve(const BeamResolveParams& p, hipStream_t stream);
 // the prompt ids of rows 0 .. B of a prefill (ids [B][P_max]) into dst [B][max_prompt], their lengths into dst_len
 struct HistParams {
     const int32_t* ids;

@@ -362,6 +362,14 @@ struct emmax_session {
     uint64_t* score_words;
     bool processing = false, scores_on = false;
     int scores_rows = 0;   // rows of the bound score buffers: the batch of the first prefill after the binding (0: none yet)
+    // BEAM SEARCH (emmax_session_set_beams; beam.hip): K = beam_K beams per group, 0 = off.  Rows g K + k are the running beams of group g;
+    // the per-row candidate lists of a step, HF's running / finished state, the groups' words, the page bookkeeping (spare page and copy
+    // list per row), the trace [max_out][max_batch] and the resolved result.  Beams off: none of it is touched
+    int beam_K = 0, beam_G = 0, beam_es = 0, beam_lp_pos = 0, beam_eos = -1, beam_max_new = 0;
+    bool beam_forked = false, beam_ready = false, scores_has_scores = false;
+    float *bm_cand_acc, *bm_row_lse, *bm_run, *bm_fin_score, *bm_pw, *bm_tr_score, *bm_tr_lse, *bm_tc_acc, *bm_res_score;
+    int32_t *bm_cand_tok, *bm_fin_flag, *bm_fin_t, *bm_fin_par, *bm_fin_tok, *bm_grp, *bm_spare, *bm_csrc, *bm_cdst, *bm_cntok, *bm_tr_tok, *bm_tr_par,
+        *bm_tc_idx, *bm_res_bidx, *bm_res_len;
     int32_t *part_idx2;
     int32_t *part_idx, *cur_tok, *ctx_len, *done, *n_out, *out_ids, *max_new_d /* [max_batch] */, *page_table;
     // EXACT NUMERICS (round 6; tuning switch `exact` at emmax_session_create): fp32 activations end to end.  x32a: the fp32 result of the GEMM
@@ -510,6 +518,33 @@ static void plan_session(emmax_session* s, SBump& b) {
     s->splitk_ws = (float*)b.take(s->splitk_bytes);
     s->cos_t = (float*)b.take((int64_t)s->max_ctx * (m->cfg.head_dim / 2) * 4);
     s->sin_t = (float*)b.take((int64_t)s->max_ctx * (m->cfg.head_dim / 2) * 4);
+    {   // beam search: rows are decode rows only (no beams on staging rows)
+        const int64_t Rb = std::min(Bd, EMMAX_MAX_DECODE_BATCH), T = s->max_out;
+        s->bm_cand_acc = (float*)b.take(Rb * 2 * EMMAX_MAX_BEAMS * 4);
+        s->bm_cand_tok = (int32_t*)b.take(Rb * 2 * EMMAX_MAX_BEAMS * 4);
+        s->bm_row_lse = (float*)b.take(Rb * 4);
+        s->bm_run = (float*)b.take(Rb * 4);
+        s->bm_fin_score = (float*)b.take(Rb * 4);
+        s->bm_fin_flag = (int32_t*)b.take(Rb * 4);
+        s->bm_fin_t = (int32_t*)b.take(Rb * 4);
+        s->bm_fin_par = (int32_t*)b.take(Rb * 4);
+        s->bm_fin_tok = (int32_t*)b.take(Rb * 4);
+        s->bm_grp = (int32_t*)b.take(Rb * 4 * 4);
+        s->bm_spare = (int32_t*)b.take(Rb * 4);
+        s->bm_csrc = (int32_t*)b.take(Rb * 4);
+        s->bm_cdst = (int32_t*)b.take(Rb * 4);
+        s->bm_cntok = (int32_t*)b.take(Rb * 4);
+        s->bm_pw = (float*)b.take((T + 1) * 4);
+        s->bm_tr_tok = (int32_t*)b.take(T * Rb * 4);
+        s->bm_tr_par = (int32_t*)b.take(T * Rb * 4);
+        s->bm_tr_score = (float*)b.take(T * Rb * 4);
+        s->bm_tr_lse = (float*)b.take(T * Rb * 4);
+        s->bm_tc_idx = (int32_t*)b.take(T * Rb * 2 * 4);
+        s->bm_tc_acc = (float*)b.take(T * Rb * 2 * 4);
+        s->bm_res_bidx = (int32_t*)b.take(T * Rb * 4);
+        s->bm_res_len = (int32_t*)b.take(Rb * 4);
+        s->bm_res_score = (float*)b.take(Rb * 4);
+    }
     if (s->exact) {
         const int64_t npr = (int64_t)Bv * np;
         auto mx = [](int64_t a, int64_t b2) { return a > b2 ? a : b2; };
@@ -864,7 +899,12 @@ static float* vscale_of(emmax_session* s, int layer) { return kscale_of(s, layer
 static int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* logits_out, bool do_finish, hipStream_t st, int slot0 = 0);
 // how a step ends (the captured graph is keyed on it: the finish's parameters differ in each): bit 0 sampling, bit 1 processing, bit 2
 // scores.  0: the greedy finish (lm-head argmax partials); 1: the sampled finish; bit 1 or 2 set: the processing finish
-static int finish_mode(const emmax_session* s) { return (s->sampling ? 1 : 0) | (s->processing ? 2 : 0) | (s->scores_on ? 4 : 0); }
+// beams on: bit 3, stop_on_eos in bit 4, K and the early-stopping mode above (the beam finish holds them by value)
+static int finish_mode(const emmax_session* s) {
+    return (s->sampling ? 1 : 0) | (s->processing ? 2 : 0) | (s->scores_on ? 4 : 0) |
+           (s->beam_K ? (8 | (s->beam_eos >= 0 ? 16 : 0) | (s->beam_K << 5) | (s->beam_es << 10) | (s->beam_lp_pos << 12)) : 0);
+}
+static int launch_beam_finish(emmax_session* s, bool is_prefill, hipStream_t st);
 static int launch_finish_step(emmax_session* s, int B, bool is_prefill, int n_part, int slot0, hipStream_t st);
 
 // the per-row state of rows slot0 .. slot0 + B that a finish updates
@@ -927,10 +967,83 @@ static int launch_proc_finish_step(emmax_session* s, int B, bool is_prefill, int
     return 0;
 }
 
+// pages a group of K beams uses for a context of S tokens and max_new generated ones, against the K rows' share (include/emmax.h): the
+// prompt's pages, a private page per beam from the prompt's partial page on, one more per beam at every page boundary, K spares
+static bool beam_pages_fit(const emmax_session* s, int S, int max_new) {
+    const int K = s->beam_K, rem = S % PAGE;
+    long long need = (S + PAGE - 1) / PAGE + (rem > 0 ? K - 1 : K) + K;
+    for (int L = S + 1; L <= S + max_new - 1; ++L)
+        if (L % PAGE == 0) need += K;
+    return S + max_new <= s->max_ctx && need <= (long long)K * s->max_pages;
+}
+
+// the tail of a step with beams on (beam.hip): per-row candidates, the groups' merge + state + page-table gather, the partial-page copies.
+// is_prefill: the first beam step, from the prefill's one logit row per group, and the fork
+static int launch_beam_finish(emmax_session* s, bool is_prefill, hipStream_t st) {
+    emmax_model* m = s->m;
+    const int K = s->beam_K, G = s->beam_G, rows = G * K;
+    BeamRowParams r;
+    memset(&r, 0, sizeof(r));
+    r.logits = s->logits; r.ld = m->vocab; r.V = m->vocab; r.K = K; r.is_prefill = is_prefill ? 1 : 0;
+    r.run_score = s->bm_run; r.done = s->done; r.n_out = s->n_out;
+    r.cand_acc = s->bm_cand_acc; r.cand_tok = s->bm_cand_tok; r.row_lse = s->bm_row_lse;
+    r.score_words = s->scores_on ? s->score_words : nullptr;
+    KCHK(launch_beam_rows(r, is_prefill ? G : rows, st));
+    BeamMergeParams g;
+    memset(&g, 0, sizeof(g));
+    g.K = K; g.V = m->vocab; g.is_prefill = r.is_prefill; g.eos_id = s->beam_eos; g.pad_id = m->cfg.pad_id; g.max_pages = s->max_pages;
+    g.max_out = s->max_out; g.tr_ld = std::min(s->max_batch, EMMAX_MAX_DECODE_BATCH); g.es_mode = s->beam_es; g.lp_pos = s->beam_lp_pos;
+    g.pw = s->bm_pw; g.cand_acc = s->bm_cand_acc; g.cand_tok = s->bm_cand_tok; g.row_lse = s->bm_row_lse;
+    g.run_score = s->bm_run; g.fin_score = s->bm_fin_score; g.fin_flag = s->bm_fin_flag; g.fin_t = s->bm_fin_t; g.fin_par = s->bm_fin_par;
+    g.fin_tok = s->bm_fin_tok; g.grp_state = s->bm_grp;
+    g.cur_tok = s->cur_tok; g.ctx_len = s->ctx_len; g.done = s->done; g.n_out = s->n_out; g.max_new_p = s->max_new_d;
+    g.page_table = s->page_table; g.spare = s->bm_spare; g.copy_src = s->bm_csrc; g.copy_dst = s->bm_cdst; g.copy_ntok = s->bm_cntok;
+    g.tr_tok = s->bm_tr_tok; g.tr_par = s->bm_tr_par; g.tr_score = s->bm_tr_score; g.tr_lse = s->bm_tr_lse; g.tc_idx = s->bm_tc_idx;
+    g.tc_acc = s->bm_tc_acc;
+    if (is_prefill)
+        for (int i = 0; i < G; ++i) g.S[i] = s->S[i];
+    KCHK(launch_beam_merge(g, G, st));
+    BeamCopyParams c;
+    memset(&c, 0, sizeof(c));
+    const long long kvr = kv_rows(s), hd = m->cfg.head_dim;
+    c.kv = (char*)s->kv; c.layer_stride = s->kv_layer_stride; c.Hkv = m->cfg.n_kv_heads; c.n_pages = s->rows_total * s->max_pages;
+    c.copy_src = s->bm_csrc; c.copy_dst = s->bm_cdst; c.copy_ntok = s->bm_cntok;
+    auto plane = [&](long long off, int rb) { c.plane_off[c.n_planes] = off; c.plane_rb[c.n_planes] = rb; c.n_planes += 1; };
+    switch (s->kv_fmt) {
+    case KV_FP8:   // K bytes, V bytes, K scales, V scales
+        plane(0, (int)hd); plane(kvr * hd, (int)hd); plane(2 * kvr * hd, 4); plane(2 * kvr * hd + kvr * 4, 4);
+        break;
+    case KV_X24:   // per operand a bf16 plane and its 8-bit extension plane
+        plane(0, (int)hd * 2); plane(kvr * hd * 2, (int)hd); plane(kvr * hd * 3, (int)hd * 2); plane(kvr * hd * 5, (int)hd);
+        break;
+    case KV_F32:
+        plane(0, (int)hd * 4); plane(kvr * hd * 4, (int)hd * 4);
+        break;
+    default:
+        plane(0, (int)hd * 2); plane(kvr * hd * 2, (int)hd * 2);
+    }
+    KCHK(launch_beam_copy(c, rows, m->cfg.n_layers, st));
+    return 0;
+}
+
 static void lmhead_params(emmax_session* s, int slot0, float* logits_out, GemvParams& p);
 // slot0: first row of the B rows this call covers (slot prefill: one row in the middle of a live batch)
 static int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* logits_out, bool do_finish, hipStream_t st, int slot0) {
     emmax_model* m = s->m;
+    if (do_finish && s->beam_K) {   // beams on: every chunk's lm-head writes its logit rows, then ONE beam finish over all rows (a prefill's
+                                    // rows wait for emmax_generate, which knows the token budget the first beam step needs)
+        if (is_prefill && s->exact) {   // exact numerics: a group's first row must not depend on how many groups were prefilled with it, and
+                                        // lm-heads of 1-2 and of 3-8 rows are different kernels -- one row per launch
+            for (int b = 0; b < B; ++b) {
+                const int r = run_lm_head_step(s, 1, true, s->logits + (size_t)(slot0 + b) * m->vocab, false, st, slot0 + b);
+                if (r) return r;
+            }
+            return 0;
+        }
+        const int r = run_lm_head_step(s, B, is_prefill, s->logits + (size_t)slot0 * m->vocab, false, st, slot0);
+        if (r || is_prefill) return r;
+        return launch_beam_finish(s, false, st);
+    }
     const int chunk = s->exact ? 8 : EMMAX_KMP_ROWS;   // (exact numerics: the two-term MFMA kernels hold 8 rows)
     if (B > chunk) {   // 33-64 rows: launches of <= 32 rows (each with its own finish: the argmax partials are laid out per launch)
         int r = run_lm_head_step(s, chunk, is_prefill, logits_out, do_finish, st, slot0);
@@ -969,6 +1082,19 @@ static int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens
     const int np = patches ? m->tw[0].n_patches : 0;
     const bool slot_mode = slot0 >= 0;
     const int r0 = slot_mode ? slot0 : 0;
+    if (s->beam_K) {   // beams on: B groups, one prefilled row each, forked into B x K rows by emmax_generate
+        if (slot_mode) return fail(EMMAX_ERR_STATE, "request slots are not served while beams are on");
+        const int rows = B * s->beam_K;
+        if (rows > s->max_batch || rows > max_rows)
+            return fail(EMMAX_ERR_INVALID, "%d groups x %d beams exceed min(max_batch=%d, %d) rows", B, s->beam_K, s->max_batch, max_rows);
+        if (rows >= EMMAX_MFMA_MIN_BATCH && !m->aux_built)
+            return fail(EMMAX_ERR_STATE, "%d beam rows decode on the fragment-major weight copies: call emmax_model_build_aux first", rows);
+        for (int b = 0; b < B; ++b)
+            if (lens[b] >= 1 && !beam_pages_fit(s, np + lens[b], 1))
+                return fail(EMMAX_ERR_NOMEM, "group %d: a context of %d tokens leaves its %d beams no spare pages (%d pages per row)", b, np + lens[b], s->beam_K, s->max_pages);
+        KCHK(launch_beam_pages(s->page_table, B, s->max_pages, s->beam_K, st));   // row g over the pool of group g: the pages of rows g K ..
+        s->beam_G = B; s->beam_forked = false; s->beam_ready = false;
+    }
     if (slot_mode) {
         if (!s->slots_open) return fail(EMMAX_ERR_STATE, "slot prefill before emmax_slots_open");
         if (r0 >= s->stg0) {   // staging rows
@@ -994,7 +1120,7 @@ static int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens
     }
     if (total > s->max_rows) return fail(EMMAX_ERR_NOMEM, "packed prefill rows %d exceed capacity %d", total, s->max_rows);
     KCHK(launch_prefill_state(ps, s->cu, s->ctx_len + r0, s->done + r0, s->n_out + r0, s->max_new_d + r0, s->stop_m + r0, s->stop_after + r0, st));
-    if (s->scores_on && !slot_mode) {   // the score buffers' rows: the first prefill after the binding's; another batch size unbinds them
+    if (s->scores_on && !slot_mode && !s->beam_K) {   // the score buffers' rows: the first prefill after the binding's; another batch size unbinds them
         if (s->scores_rows == 0) {
             s->scores_rows = B;
             KCHK(launch_set_int((int32_t*)(s->score_words + 3), B, st));
@@ -1074,6 +1200,7 @@ static int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens
     int r = run_lm_head_step(s, B, true, nullptr, true, st, r0);
     if (r) return r;
     s->prefilled = true;
+    s->beam_ready = s->beam_K != 0;
     return 0;
 }
 
@@ -1115,6 +1242,7 @@ static int run_prefill_x(emmax_session* s, const int32_t* ids, int B, int P_max,
     int r = run_lm_head_step(s, B, true, nullptr, true, st, r0);
     if (r) return r;
     s->prefilled = true;
+    s->beam_ready = s->beam_K != 0;
     return 0;
 }
 
@@ -1762,6 +1890,7 @@ int emmax_prefill_logits(emmax_session* s, float* out, emmax_stream stream) {
 int emmax_last_logits(emmax_session* s, float* out, emmax_stream stream) {
     if (!s || !out) return fail(EMMAX_ERR_INVALID, "null argument");
     if (!s->prefilled) return fail(EMMAX_ERR_STATE, "prefill has not run");
+    if (s->beam_K) return fail(EMMAX_ERR_STATE, "emmax_last_logits is not served while beams are on (bind a logits buffer: emmax_session_set_scores)");
     return run_lm_head_step(s, s->cur_B, false, out, false, (hipStream_t)stream);
 }
 
@@ -1773,6 +1902,7 @@ static int slot_leave(emmax_session* s, hipStream_t user, hipStream_t st);
 int emmax_decode_step(emmax_session* s, emmax_stream stream) {
     if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
     if (!s->prefilled) return fail(EMMAX_ERR_STATE, "decode before prefill");
+    if (s->beam_K) return fail(EMMAX_ERR_STATE, "with beams on the decode steps run inside emmax_generate");
     s->dec_steps += 1;
     if (emmax_tune().graph) {   // the step is a replay of the captured hipGraph (as in emmax_generate / emmax_slots_step)
         hipStream_t user = (hipStream_t)stream, st;
@@ -1790,6 +1920,7 @@ int emmax_set_current_tokens(emmax_session* s, const int32_t* toks, emmax_stream
     if (!s || !toks) return fail(EMMAX_ERR_INVALID, "null argument");
     if (!s->prefilled) return fail(EMMAX_ERR_STATE, "no active sequences");
     if (s->slots_open) return fail(EMMAX_ERR_STATE, "caller-supplied tokens are not supported while request slots are open");
+    if (s->beam_K) return fail(EMMAX_ERR_STATE, "caller-supplied tokens are not supported while beams are on");
     if (s->processing) return fail(EMMAX_ERR_STATE, "caller-supplied tokens are not supported while logits processing is on (they would be missing from the history)");
     // the rows decode again (done flag cleared): the next step appends at position <= S_b + dec_steps, which must exist
     int maxS = 0;
@@ -1804,6 +1935,13 @@ int emmax_generate(emmax_session* s, int max_new, int stop_on_eos, int32_t* out_
     if (!s || !out_ids || !out_lens) return fail(EMMAX_ERR_INVALID, "null argument");
     if (!s->prefilled) return fail(EMMAX_ERR_STATE, "generate before prefill");
     if (max_new < 1 || max_new > s->max_out) return fail(EMMAX_ERR_INVALID, "max_new_tokens %d outside 1..%d", max_new, s->max_out);
+    if (s->beam_K) {
+        if (!s->beam_ready || s->beam_forked) return fail(EMMAX_ERR_STATE, "with beams on emmax_generate runs once per prefill (the prefill must follow emmax_session_set_beams)");
+        for (int g = 0; g < s->beam_G; ++g)
+            if (!beam_pages_fit(s, s->S[g], max_new))
+                return fail(EMMAX_ERR_NOMEM, "group %d: context %d + %d new tokens x %d beams do not fit max_ctx %d / the %d pages of its rows", g, s->S[g], max_new,
+                            s->beam_K, s->max_ctx, s->beam_K * s->max_pages);
+    }
     hipStream_t user = (hipStream_t)stream, st = user;
     // the legacy / per-thread default streams cannot be captured: run the loop on the session's own stream, ordered
     // after everything already queued on the caller's stream and before anything queued on it afterwards
@@ -1813,8 +1951,31 @@ int emmax_generate(emmax_session* s, int max_new, int stop_on_eos, int32_t* out_
         HIPCHK(hipEventRecord(s->ev_in, user));
         HIPCHK(hipStreamWaitEvent(st, s->ev_in, 0));
     }
+    if (s->beam_K) {   // the first beam step from the prefill's logit rows, and the fork into G x K rows
+        const int rows = s->beam_G * s->beam_K, ld = std::min(s->max_batch, EMMAX_MAX_DECODE_BATCH);
+        s->beam_eos = stop_on_eos ? s->m->cfg.eos_id : -1;
+        s->beam_max_new = max_new;
+        KCHK(launch_set_ints(s->max_new_d, rows, max_new, st));
+        KCHK(launch_beam_reset(rows, s->beam_K, s->bm_run, s->bm_fin_score, s->bm_fin_flag, s->bm_fin_t, s->bm_fin_par, s->bm_fin_tok, s->bm_grp,
+                               s->bm_csrc, st));
+        const size_t n1 = (size_t)max_new * ld * 4;
+        HIPCHK(hipMemsetAsync(s->bm_tr_tok, 0xff, n1, st));
+        HIPCHK(hipMemsetAsync(s->bm_tr_par, 0xff, n1, st));
+        HIPCHK(hipMemsetAsync(s->bm_tr_score, 0, n1, st));
+        HIPCHK(hipMemsetAsync(s->bm_tr_lse, 0, n1, st));
+        HIPCHK(hipMemsetAsync(s->bm_tc_idx, 0xff, 2 * n1, st));
+        HIPCHK(hipMemsetAsync(s->bm_tc_acc, 0, 2 * n1, st));
+        if (s->scores_on) KCHK(launch_set_int((int32_t*)(s->score_words + 3), rows, st));
+        int r = launch_beam_finish(s, true, st);
+        if (r) return r;
+        for (int g = s->beam_G - 1; g >= 0; --g)
+            for (int k = 0; k < s->beam_K; ++k) s->S[g * s->beam_K + k] = s->S[g];
+        s->cur_B = rows;
+        s->beam_forked = true;
+        s->beam_ready = false;
+    }
     const int B = s->cur_B;
-    KCHK(launch_set_ints(s->max_new_d, B, max_new, st));
+    if (!s->beam_K) KCHK(launch_set_ints(s->max_new_d, B, max_new, st));
     const bool use_graph = (max_new > 2) && ensure_graph(s, B, st) == 0;
     const int CHK = 16;
     int32_t* done_host = s->pinned;
@@ -1840,9 +2001,18 @@ int emmax_generate(emmax_session* s, int max_new, int stop_on_eos, int32_t* out_
             pending = true;
         }
     }
+    if (s->beam_K) {   // the kept hypotheses, best first per group, out of the token / parent tables
+        BeamResolveParams q;
+        memset(&q, 0, sizeof(q));
+        q.rows = B; q.K = s->beam_K; q.max_out = s->max_out; q.max_new = max_new; q.tr_ld = std::min(s->max_batch, EMMAX_MAX_DECODE_BATCH);
+        q.pad_id = s->m->cfg.pad_id;
+        q.fin_t = s->bm_fin_t; q.fin_par = s->bm_fin_par; q.fin_tok = s->bm_fin_tok; q.tr_tok = s->bm_tr_tok; q.tr_par = s->bm_tr_par;
+        q.fin_score = s->bm_fin_score; q.seq = s->out_ids; q.bidx = s->bm_res_bidx; q.len = s->bm_res_len; q.score = s->bm_res_score;
+        KCHK(launch_beam_resolve(q, st));
+    }
     HIPCHK(hipMemcpy2DAsync(out_ids, (size_t)max_new * 4, s->out_ids, (size_t)s->max_out * 4, (size_t)max_new * 4, B,
                             hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(out_lens, s->n_out, B * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(out_lens, s->beam_K ? s->bm_res_len : s->n_out, B * 4, hipMemcpyDeviceToDevice, st));
     if (special) {
         HIPCHK(hipEventRecord(s->ev_out, st));
         HIPCHK(hipStreamWaitEvent(user, s->ev_out, 0));
@@ -1890,6 +2060,7 @@ int emmax_session_set_stop(emmax_session* s, const int32_t* trigger_ids, int n_t
 
 int emmax_slots_open(emmax_session* s, int n_slots, emmax_stream stream) {
     if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (s->beam_K) return fail(EMMAX_ERR_STATE, "request slots are not served while beams are on (emmax_session_clear_beams)");
     const int max_rows = s->exact ? EMMAX_MAX_DECODE_BATCH : model_max_decode_batch(s->m);
     if (n_slots < 1 || n_slots > s->max_batch || n_slots > max_rows)
         return fail(EMMAX_ERR_INVALID, "%d slots outside 1..min(max_batch=%d, %d)", n_slots, s->max_batch, max_rows);
@@ -2079,6 +2250,7 @@ int emmax_session_set_sampling(emmax_session* s, int row0, int n, const float* t
                                const uint64_t* seed_host, const uint32_t* subseq_host, emmax_stream stream) {
     if (!s || !temperature_host || !top_k_host || !top_p_host || !seed_host || !subseq_host) return fail(EMMAX_ERR_INVALID, "null argument");
     if (n < 1 || row0 < 0 || row0 + n > s->max_batch) return fail(EMMAX_ERR_INVALID, "rows %d..%d outside 0..%d", row0, row0 + n - 1, s->max_batch - 1);
+    if (s->beam_K) return fail(EMMAX_ERR_STATE, "sampling is not available while beams are on");
     hipStream_t user = (hipStream_t)stream, st;
     int r = slot_enter(s, user, &st);
     if (r) return r;
@@ -2164,6 +2336,7 @@ int emmax_session_set_processing(emmax_session* s, int row0, int n, const float*
                                  emmax_stream stream) {
     if (!s || !penalty_host || !ngram_host || !min_new_host) return fail(EMMAX_ERR_INVALID, "null argument");
     if (n < 1 || row0 < 0 || row0 + n > s->max_batch) return fail(EMMAX_ERR_INVALID, "rows %d..%d outside 0..%d", row0, row0 + n - 1, s->max_batch - 1);
+    if (s->beam_K) return fail(EMMAX_ERR_STATE, "logits processing is not available while beams are on");
     hipStream_t user = (hipStream_t)stream, st;
     int r = slot_enter(s, user, &st);
     if (r) return r;
@@ -2198,8 +2371,10 @@ int emmax_session_set_scores(emmax_session* s, float* scores_dev, float* logits_
     if (s->slots_open) return fail(EMMAX_ERR_STATE, "scores are not kept in slot serving (emmax_slots_open)");
     if (!scores_dev && !logits_dev) {
         s->scores_on = false;
+        s->scores_has_scores = false;
         return 0;
     }
+    if (s->beam_K && scores_dev) return fail(EMMAX_ERR_STATE, "processed scores are not kept while beams are on (bind the raw logits buffer only)");
     if (s->m->vocab > EMMAX_SAMPLE_MAX_V) return fail(EMMAX_ERR_INVALID, "scores take vocabularies of up to %d entries (%d)", EMMAX_SAMPLE_MAX_V, s->m->vocab);
     if (max_new < 1 || max_new > s->max_out) return fail(EMMAX_ERR_INVALID, "max_new_tokens %d outside 1..%d", max_new, s->max_out);
     hipStream_t user = (hipStream_t)stream, st;
@@ -2211,7 +2386,84 @@ int emmax_session_set_scores(emmax_session* s, float* scores_dev, float* logits_
     HIPCHK(hipMemcpyAsync(s->score_words, h, 4 * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
     s->scores_on = true;
+    s->scores_has_scores = scores_dev != nullptr;
     s->scores_rows = 0;
+    return slot_leave(s, user, st);
+}
+
+// ---- beam search in the decode step (ABI 9) ---------------------------------------------------------------------------
+int emmax_session_set_beams(emmax_session* s, int num_beams, double length_penalty, int early_stopping, emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    const int max_rows = s->exact ? EMMAX_MAX_DECODE_BATCH : model_max_decode_batch(s->m);
+    if (num_beams < 2 || num_beams > EMMAX_MAX_BEAMS || num_beams > s->max_batch || num_beams > max_rows)
+        return fail(EMMAX_ERR_INVALID, "num_beams %d outside 2..min(%d, max_batch=%d, %d)", num_beams, EMMAX_MAX_BEAMS, s->max_batch, max_rows);
+    if (!std::isfinite(length_penalty)) return fail(EMMAX_ERR_INVALID, "length_penalty must be finite");
+    if (early_stopping < 0 || early_stopping > 2) return fail(EMMAX_ERR_INVALID, "early_stopping %d: 0 False, 1 True, 2 never", early_stopping);
+    if (s->m->vocab > EMMAX_SAMPLE_MAX_V || s->m->vocab < 2 * num_beams)
+        return fail(EMMAX_ERR_INVALID, "beams take vocabularies of %d..%d entries (%d)", 2 * num_beams, EMMAX_SAMPLE_MAX_V, s->m->vocab);
+    if (s->slots_open) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while request slots are open");
+    if (s->sampling || s->processing) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while sampling or logits processing is on");
+    if (s->scores_on && s->scores_has_scores) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while a scores buffer is bound");
+    hipStream_t user = (hipStream_t)stream, st;
+    int r = slot_enter(s, user, &st);
+    if (r) return r;
+    std::vector<float> pw((size_t)s->max_out + 1);
+    for (size_t n = 0; n < pw.size(); ++n) pw[n] = (float)pow((double)n, length_penalty);
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(s->bm_pw, pw.data(), pw.size() * 4, hipMemcpyHostToDevice));
+    s->beam_K = num_beams; s->beam_es = early_stopping; s->beam_lp_pos = length_penalty > 0.0 ? 1 : 0;
+    s->beam_G = 0; s->beam_forked = false; s->beam_ready = false;
+    s->prefilled = false;   // rows of an earlier batch do not continue as beams
+    return slot_leave(s, user, st);
+}
+
+int emmax_session_clear_beams(emmax_session* s, emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->beam_K) return 0;
+    hipStream_t user = (hipStream_t)stream, st;
+    int r = slot_enter(s, user, &st);
+    if (r) return r;
+    KCHK(launch_beam_pages(s->page_table, s->rows_total, s->max_pages, 1, st));   // static assignment again: row b owns its own pages
+    s->beam_K = 0; s->beam_G = 0; s->beam_forked = false; s->beam_ready = false;
+    s->prefilled = false;
+    return slot_leave(s, user, st);
+}
+
+int emmax_session_beams(const emmax_session* s) { return s ? s->beam_K : -1; }
+
+int emmax_session_beam_result(emmax_session* s, int max_new, int32_t* seq_dev, int32_t* len_dev, float* score_dev, int32_t* bidx_dev, emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->beam_K || !s->beam_forked) return fail(EMMAX_ERR_STATE, "no beam generation to report");
+    if (max_new < 1 || max_new > s->beam_max_new) return fail(EMMAX_ERR_INVALID, "max_new %d outside 1..%d (the generation's)", max_new, s->beam_max_new);
+    hipStream_t user = (hipStream_t)stream, st;
+    int r = slot_enter(s, user, &st);
+    if (r) return r;
+    const int rows = s->beam_G * s->beam_K;
+    if (seq_dev) HIPCHK(hipMemcpy2DAsync(seq_dev, (size_t)max_new * 4, s->out_ids, (size_t)s->max_out * 4, (size_t)max_new * 4, rows, hipMemcpyDeviceToDevice, st));
+    if (bidx_dev) HIPCHK(hipMemcpy2DAsync(bidx_dev, (size_t)max_new * 4, s->bm_res_bidx, (size_t)s->max_out * 4, (size_t)max_new * 4, rows, hipMemcpyDeviceToDevice, st));
+    if (len_dev) HIPCHK(hipMemcpyAsync(len_dev, s->bm_res_len, rows * 4, hipMemcpyDeviceToDevice, st));
+    if (score_dev) HIPCHK(hipMemcpyAsync(score_dev, s->bm_res_score, rows * 4, hipMemcpyDeviceToDevice, st));
+    return slot_leave(s, user, st);
+}
+
+int emmax_session_beam_trace(emmax_session* s, int max_new, int32_t* tok_dev, int32_t* parent_dev, float* score_dev, float* lse_dev, int32_t* cand_idx_dev,
+                             float* cand_acc_dev, emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->beam_K || !s->beam_forked) return fail(EMMAX_ERR_STATE, "no beam generation to report");
+    if (max_new < 1 || max_new > s->beam_max_new) return fail(EMMAX_ERR_INVALID, "max_new %d outside 1..%d (the generation's)", max_new, s->beam_max_new);
+    hipStream_t user = (hipStream_t)stream, st;
+    int r = slot_enter(s, user, &st);
+    if (r) return r;
+    const size_t rows = (size_t)s->beam_G * s->beam_K, ld = (size_t)std::min(s->max_batch, EMMAX_MAX_DECODE_BATCH);
+    auto out = [&](void* dst, const void* src, size_t mul) -> hipError_t {
+        return dst ? hipMemcpy2DAsync(dst, rows * mul * 4, src, ld * mul * 4, rows * mul * 4, (size_t)max_new, hipMemcpyDeviceToDevice, st) : hipSuccess;
+    };
+    HIPCHK(out(tok_dev, s->bm_tr_tok, 1));
+    HIPCHK(out(parent_dev, s->bm_tr_par, 1));
+    HIPCHK(out(score_dev, s->bm_tr_score, 1));
+    HIPCHK(out(lse_dev, s->bm_tr_lse, 1));
+    HIPCHK(out(cand_idx_dev, s->bm_tc_idx, 2));
+    HIPCHK(out(cand_acc_dev, s->bm_tc_acc, 2));
     return slot_leave(s, user, st);
 }
 

@@ -43,7 +43,7 @@ class ConfigC(C.Structure):
     ]
 
 
-ABI_VERSION = 8   # EMMAX_ABI_VERSION of include/emmax.h this binding was written against
+ABI_VERSION = 9   # EMMAX_ABI_VERSION of include/emmax.h this binding was written against
 
 # name -> (restype, argtypes): exactly the entry points of include/emmax.h
 SIGNATURES = {
@@ -132,6 +132,11 @@ SIGNATURES = {
     "emmax_session_clear_processing": (C.c_int, [_vp, _vp]),
     "emmax_session_processing": (C.c_int, [_vp]),
     "emmax_session_set_scores": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
+    "emmax_session_set_beams": (C.c_int, [_vp, C.c_int, C.c_double, C.c_int, _vp]),
+    "emmax_session_clear_beams": (C.c_int, [_vp, _vp]),
+    "emmax_session_beams": (C.c_int, [_vp]),
+    "emmax_session_beam_result": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "emmax_session_beam_trace": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -126,6 +126,7 @@ class EmmaxEngine:
                        "emmax_session_create_ex")
         assert bool(self.lib.emmax_session_exact(self._session)) == bool(self.exact)
         self._score_bufs = None   # a new session binds no scores
+        self._beam_K = 0          # ... and has beams off
         self.max_batch, self.max_prompt, self.max_ctx, self.stage_rows = max_batch, max_prompt, max_ctx, int(stage_rows)
 
     def ensure_stage_rows(self, n: int) -> None:
@@ -234,7 +235,8 @@ class EmmaxEngine:
     def prefill(self, input_ids: Sequence[Sequence[int]], patch_embeds: torch.Tensor) -> List[int]:
         """Ragged prompts (row b = list of ids starting with BOS). Returns per-row packed lengths S_b = 256 + P_b."""
         B = len(input_ids)
-        self.ensure_decode_batch(B)
+        K = getattr(self, "_beam_K", 0)
+        self.ensure_decode_batch(B * K if K else B)   # beams on: B groups decode as B x K rows
         lens = [len(r) for r in input_ids]
         P_max = max(lens)
         ids = torch.full((B, P_max), self.cfg.pad_token_id, dtype=torch.int32)
@@ -278,8 +280,10 @@ class EmmaxEngine:
 
     def generate(self, max_new_tokens: int, stop_on_eos: bool = True, return_logprobs: bool = False):
         """The decode loop after prefill: greedy, or sampled per row once set_sampling ran.  Returns (ids int32 [B,max_new] padded with pad_id,
-        lens int32 [B]) on device; with return_logprobs (sampling on only) also the fp32 [B,max_new] log-probabilities of the emitted tokens."""
-        B = self._last_B
+        lens int32 [B]) on device; with return_logprobs (sampling on only) also the fp32 [B,max_new] log-probabilities of the emitted tokens.
+        Beams on: B = groups x num_beams rows, row g K + k = the k-th best kept hypothesis of group g (beam_result has the scores)."""
+        B = self._last_B * (getattr(self, "_beam_K", 0) or 1)
+        self._beam_T = int(max_new_tokens)
         out = torch.empty(B, max_new_tokens, dtype=torch.int32, device=self.device)
         lens = torch.empty(B, dtype=torch.int32, device=self.device)
         _lib.check(self.lib.emmax_generate(self._session, max_new_tokens, int(stop_on_eos), out.data_ptr(), lens.data_ptr(),
@@ -384,6 +388,48 @@ class EmmaxEngine:
                                                      logits.data_ptr() if logits is not None else None, int(max_new), _lib.current_stream()),
                    "emmax_session_set_scores")
         self._score_bufs = (scores, logits)
+
+    # ---- beam search inside the decode step (include/emmax.h, ABI 9) ------------------------------------------------------
+    def set_beams(self, params) -> None:
+        """Beams on (sampling.BeamParams): the next prefill takes G groups and generate() decodes them as G x num_beams rows on shared KV
+        pages.  The session must hold G x num_beams rows (ensure_capacity first)."""
+        es = {False: 0, True: 1, "never": 2}[params.early_stopping]
+        _lib.check(self.lib.emmax_session_set_beams(self._session, int(params.num_beams), float(params.length_penalty), es, _lib.current_stream()),
+                   "emmax_session_set_beams")
+        self._beam_K = int(params.num_beams)
+
+    def clear_beams(self) -> None:
+        """Beams off: the session launches exactly what a greedy session launches, on the static page assignment."""
+        _lib.check(self.lib.emmax_session_clear_beams(self._session, _lib.current_stream()), "emmax_session_clear_beams")
+        self._beam_K = 0
+
+    @property
+    def beams(self) -> int:
+        return max(int(self.lib.emmax_session_beams(self._session)), 0)
+
+    def beam_result(self):
+        """After generate() with beams on: (sequences int32 [G, K, T], lengths int32 [G, K], sequences_scores fp32 [G, K], beam_indices
+        int32 [G, K, T]) on device, best first per group; T = the generation's max_new_tokens."""
+        G, K, T = self._last_B, self._beam_K, self._beam_T
+        seq = torch.empty(G, K, T, dtype=torch.int32, device=self.device)
+        bix = torch.empty(G, K, T, dtype=torch.int32, device=self.device)
+        lens = torch.empty(G, K, dtype=torch.int32, device=self.device)
+        sc = torch.empty(G, K, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.emmax_session_beam_result(self._session, T, seq.data_ptr(), lens.data_ptr(), sc.data_ptr(), bix.data_ptr(),
+                                                      _lib.current_stream()), "emmax_session_beam_result")
+        return seq, lens, sc, bix
+
+    def beam_trace(self):
+        """After generate() with beams on: dict of device tensors -- tok, parent int32 [T, G, K]; score, lse fp32 [T, G, K]; cand_idx int32
+        and cand_acc fp32 [T, G, 2K] (include/emmax.h: emmax_session_beam_trace)."""
+        G, K, T = self._last_B, self._beam_K, self._beam_T
+        i32 = lambda *sh: torch.empty(*sh, dtype=torch.int32, device=self.device)
+        f32 = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=self.device)
+        tr = {"tok": i32(T, G, K), "parent": i32(T, G, K), "score": f32(T, G, K), "lse": f32(T, G, K), "cand_idx": i32(T, G, 2 * K),
+              "cand_acc": f32(T, G, 2 * K)}
+        _lib.check(self.lib.emmax_session_beam_trace(self._session, T, *[tr[k].data_ptr() for k in ("tok", "parent", "score", "lse", "cand_idx", "cand_acc")],
+                                                     _lib.current_stream()), "emmax_session_beam_trace")
+        return tr
 
     @property
     def scores_bound(self) -> bool:

@@ -27,7 +27,7 @@ from .config import EmmaXConfig, default_norm_stats
 from .engine import EmmaxEngine
 from .policy_parser import Solver
 from .processing import BatchFeature, EmmaXImageProcessor
-from .sampling import LogitsProcessing, SamplingParams, draw_seed
+from .sampling import BeamParams, LogitsProcessing, SamplingParams, draw_seed
 from .prompting import PurePromptBuilder
 from .tokenizer_stub import StubTokenizer
 from .weights import load_hf_state_dict, remap_native_state_dict, synthetic_state_dict, validate_state_dict
@@ -64,6 +64,11 @@ class EmmaXGenerateOutput:
     sequences: torch.Tensor
     scores: Optional[Tuple[torch.Tensor, ...]] = None
     logits: Optional[Tuple[torch.Tensor, ...]] = None
+    # beam search (num_beams > 1; HF's GenerateBeamDecoderOnlyOutput): the returned hypotheses' scores [B * num_return_sequences] and, per
+    # generated position, the row (group * num_beams + beam) each token was continued from, -1 behind the end; `logits` rows are then
+    # [B * num_beams, vocab]: the rows the running beams read at each step
+    sequences_scores: Optional[torch.Tensor] = None
+    beam_indices: Optional[torch.Tensor] = None
 
     def __getitem__(self, key: str):
         return getattr(self, key)
@@ -233,7 +238,7 @@ class EmmaXForActionPrediction:
         return eng.vision_encode_pixels(pixel_values)
 
     def _prefill(self, rows: List[List[int]], pixel_values=None, frames_u8=None, max_new: int = 0, sampling=None, processing=None,
-                 scores=None, logits=None) -> torch.Tensor:
+                 scores=None, logits=None, beams: Optional[BeamParams] = None) -> torch.Tensor:
         eng = self._need_engine()
         B = len(rows)
         src = pixel_values if pixel_values is not None else frames_u8
@@ -244,12 +249,52 @@ class EmmaXForActionPrediction:
         if P > self.config.llm.max_position:
             rows = [r[: self.config.llm.max_position] for r in rows]   # tokenizer truncation at llm_max_length
             P = self.config.llm.max_position
-        eng.ensure_capacity(B, P, max(max_new, 1))
+        K = beams.num_beams if beams is not None else 1
+        if B * K > eng.max_decode_batch():
+            raise ValueError(f"{B} prompts x {K} beams exceed the {eng.max_decode_batch()} rows of a decode batch")
+        eng.ensure_capacity(B * K, P, max(max_new, 1))
         patches = self._encode_images(pixel_values, frames_u8)
-        self._set_processing(eng, B, processing, scores, logits, max_new)
-        self._set_sampling(eng, B, sampling)
+        if beams is None and getattr(eng, "beams", 0):
+            eng.clear_beams()   # (first: sampling / processing cannot be set while beams are on)
+        self._set_processing(eng, B * K, processing, scores, logits, max_new)
+        self._set_sampling(eng, B * K, sampling)
+        if beams is not None:   # B groups prefill once each and decode as B x K rows on shared KV pages
+            eng.set_beams(beams)
         eng.prefill(rows, patches)
         return patches
+
+    @staticmethod
+    def _beam_args(num_beams=None, num_return_sequences=None, length_penalty=None, early_stopping=None, do_sample: bool = False,
+                   processing=None, output_scores: bool = False) -> Optional[BeamParams]:
+        """HF generate's beam arguments -> BeamParams (None: num_beams 1, today's greedy / sampled path).  Beam sampling, processors on
+        beam log-probabilities and `scores` with beams are not built: they raise before the engine is touched."""
+        k = 1 if num_beams is None else num_beams
+        nrs = 1 if num_return_sequences is None else num_return_sequences
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError(f"num_beams must be an integer >= 1, got {num_beams}")
+        if int(k) == 1:
+            if not do_sample and nrs != 1:
+                raise ValueError(f"Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {nrs}).")
+            return None
+        if do_sample:
+            raise NotImplementedError("beam sampling (num_beams > 1 with do_sample=True) is outside the hot path")
+        if processing is not None:
+            raise NotImplementedError("logits processors on beam log-probabilities (repetition_penalty / no_repeat_ngram_size / min_new_tokens "
+                                      "with num_beams > 1) are outside the hot path")
+        if output_scores:
+            raise NotImplementedError("output_scores with num_beams > 1 is outside the hot path (output_logits is served)")
+        return BeamParams(int(k), 1.0 if length_penalty is None else length_penalty, False if early_stopping is None else early_stopping,
+                          int(nrs) if isinstance(nrs, (int, np.integer)) and not isinstance(nrs, bool) else nrs)
+
+    @staticmethod
+    def _beam_kw(beams) -> Dict[str, Any]:
+        """generate_ids' `beams` argument, passed only when there are beams (a greedy call is spelled exactly as before)."""
+        return {} if beams is None else {"beams": beams}
+
+    def _kw_beams(self, kwargs, processing=None) -> Optional[BeamParams]:
+        """The beam arguments of a **kwargs that the reference forwards to HF generate."""
+        return self._beam_args(kwargs.get("num_beams"), kwargs.get("num_return_sequences"), kwargs.get("length_penalty"),
+                               kwargs.get("early_stopping"), bool(kwargs.get("do_sample", False)), processing, bool(kwargs.get("output_scores", False)))
 
     @staticmethod
     def _set_processing(eng, B: int, processing, scores=None, logits=None, max_new: int = 0) -> None:
@@ -364,23 +409,33 @@ class EmmaXForActionPrediction:
 
     @torch.inference_mode()
     def generate_ids(self, rows: List[List[int]], pixel_values=None, frames_u8=None, max_new_tokens: int = 512,
-                     stop_on_eos: bool = True, sampling=None, return_logprobs: bool = False, processing=None, scores=None, logits=None):
+                     stop_on_eos: bool = True, sampling=None, return_logprobs: bool = False, processing=None, scores=None, logits=None,
+                     beams: Optional[BeamParams] = None):
         """Decode every row: greedy, or sampled in the step with `sampling` (one SamplingParams for all rows or one per row; row b draws
         with subseq b).  `processing` (one LogitsProcessing for all rows or one per row) applies HF's repetition penalty / n-gram ban /
         min-new-tokens in the step first.  `scores` / `logits`: fp32 [max_new, B, vocab] device buffers the step fills with HF's scores /
         raw logits at each emitted token's index (others are not written); any other shape is refused before the engine is touched, and
         the buffers are unbound again when the call returns.  Returns device tensors (new_ids int32 [B,max_new] pad-filled,
-        lens int32 [B]), and with return_logprobs (sampling only) the fp32 [B,max_new] log-probabilities of the emitted tokens."""
+        lens int32 [B]), and with return_logprobs (sampling only) the fp32 [B,max_new] log-probabilities of the emitted tokens.
+        `beams` (BeamParams; no sampling, processing or scores with it): beam search in the step.  The B rows are groups, the result has
+        B x num_beams rows -- row g K + k = the k-th best hypothesis of group g -- and `logits` is [max_new, B x num_beams, vocab];
+        engine.beam_result() / beam_trace() hold the scores, beam_indices and the per-step trace."""
         eng = self._need_engine()
+        if beams is not None:
+            if not isinstance(beams, BeamParams):
+                raise ValueError("beams must be BeamParams")
+            if sampling is not None or processing is not None or scores is not None:
+                raise ValueError("beams run without sampling, logits processing and scores")
         if return_logprobs and sampling is None:
             raise ValueError("return_logprobs needs sampling (log-probabilities are kept by the sampled step only)")
         if processing is not None:
             ps = processing if isinstance(processing, (list, tuple)) else [processing]
             if not all(isinstance(p, LogitsProcessing) for p in ps):
                 raise ValueError("processing must be LogitsProcessing (one, or one per row)")
-        self._check_score_buffers(scores, logits, max_new_tokens, len(rows), self.config.llm.vocab_size)
+        self._check_score_buffers(scores, logits, max_new_tokens, len(rows) * (beams.num_beams if beams is not None else 1),
+                                  self.config.llm.vocab_size)
         self._prefill(rows, pixel_values, frames_u8, max_new=max_new_tokens, sampling=sampling, processing=processing, scores=scores,
-                      logits=logits)
+                      logits=logits, beams=beams)
         out = eng.generate(max_new_tokens, stop_on_eos, return_logprobs=return_logprobs)
         if scores is not None or logits is not None:
             eng.set_scores(None, None)   # the buffers are the caller's now: no later step or prefill writes into them
@@ -412,21 +467,38 @@ class EmmaXForActionPrediction:
         min_new_tokens / min_length are applied in the step as HF's processors (emmax_session_set_processing).  return_dict_in_generate=True
         returns an EmmaXGenerateOutput: `sequences` (the tensor), and with output_scores / output_logits a tuple of T = max(lens) fp32
         [B, vocab] device tensors each (NaN past a row's length)."""
-        if kwargs.get("num_beams", 1) != 1:
-            raise NotImplementedError("beam search is outside the hot path")
-        sampling = self._sampling_args(do_sample, temperature, top_k, top_p, seed, generator)
         rows = self._rows(input_ids, attention_mask)
         processing = self._processing_args(rows, repetition_penalty, no_repeat_ngram_size, min_new_tokens, min_length)
+        beams = self._beam_args(kwargs.get("num_beams"), kwargs.get("num_return_sequences"), kwargs.get("length_penalty"),
+                                kwargs.get("early_stopping"), do_sample, processing, bool(return_dict_in_generate and output_scores))
+        sampling = self._sampling_args(do_sample, temperature, top_k, top_p, seed, generator)
         max_new_tokens = self._max_new(rows, max_new_tokens, kwargs.get("max_length"), None)   # (min_length is in `processing`)
         want_sc, want_lg = bool(return_dict_in_generate and output_scores), bool(return_dict_in_generate and output_logits)
         sc = lg = None
+        K = beams.num_beams if beams is not None else 1
         if want_sc or want_lg:
             eng = self._need_engine()
-            shape = (max_new_tokens, len(rows), self.config.llm.vocab_size)
+            shape = (max_new_tokens, len(rows) * K, self.config.llm.vocab_size)
             sc = torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device) if want_sc else None
             lg = torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device) if want_lg else None
         new_ids, lens = self.generate_ids(rows, pixel_values, frames_u8, max_new_tokens, sampling=sampling, processing=processing, scores=sc,
-                                          logits=lg)
+                                          logits=lg, **self._beam_kw(beams))
+        if beams is not None:   # HF's layout: [B * num_return_sequences, P + T], best first per prompt
+            R = beams.num_return_sequences
+            keep = [g * K + k for g in range(len(rows)) for k in range(R)]
+            new_ids, lens = new_ids.cpu()[keep], lens.cpu()[keep].tolist()
+            T = max(max(lens), 1)
+            P = max(len(r) for r in rows)
+            out = torch.full((len(keep), P + T), self.config.pad_token_id, dtype=torch.long)
+            for i, r in enumerate(keep):
+                seq = rows[r // K] + new_ids[i, : lens[i]].tolist()
+                out[i, : len(seq)] = torch.tensor(seq, dtype=torch.long)
+            if not return_dict_in_generate:
+                return out
+            _, _, scores_d, bidx_d = self._need_engine().beam_result()
+            Tl = int(torch.isfinite(lg).any(dim=2).any(dim=1).sum()) if want_lg else 0
+            return EmmaXGenerateOutput(sequences=out, logits=tuple(lg[t] for t in range(Tl)) if want_lg else None,
+                                       sequences_scores=scores_d[:, :R].reshape(-1), beam_indices=bidx_d[:, :R, :T].reshape(len(keep), T))
         new_ids, lens = new_ids.cpu(), lens.cpu().tolist()
         T = max(lens)
         P = max(len(r) for r in rows)
@@ -456,14 +528,14 @@ class EmmaXForActionPrediction:
         if rows[0][-1] != PREFIX_TOKEN_ID:
             rows[0] = rows[0] + [PREFIX_TOKEN_ID]
         dim = self.get_action_dim(unnorm_key)
-        if kwargs.get("num_beams", 1) != 1:
-            raise NotImplementedError("beam search is outside the hot path")
-        # the reference forwards **kwargs to HF generate (modeling_prismatic.py:519): do_sample / temperature / top_k / top_p are honoured
+        # the reference forwards **kwargs to HF generate (modeling_prismatic.py:519): do_sample / temperature / top_k / top_p are honoured, and
+        # num_beams / length_penalty / early_stopping decode the best of the beams (row 0 of the group)
+        processing = self._kw_processing(rows, kwargs)
+        beams = self._kw_beams(kwargs, processing)
         sampling = self._sampling_args(bool(kwargs.get("do_sample", False)), kwargs.get("temperature"), kwargs.get("top_k"), kwargs.get("top_p"),
                                        kwargs.get("seed"), kwargs.get("generator"))
-        processing = self._kw_processing(rows, kwargs)
         new_ids, lens = self.generate_ids(rows, kwargs.get("pixel_values"), kwargs.get("frames_u8"), max_new_tokens=dim, sampling=sampling,
-                                          processing=processing)
+                                          processing=processing, **self._beam_kw(beams))
         full = rows[0] + new_ids[0, : int(lens[0])].cpu().tolist()
         predicted = np.array(full[-dim:])
         normalized = token_ids_to_actions(predicted, self.vocab_size, self.bin_centers)
@@ -504,8 +576,6 @@ class EmmaXForActionPrediction:
             inputs = args.pop(0)   # dict, our BatchFeature, or transformers.BatchFeature (a UserDict: processing_prismatic.py:216)
         if kwargs.get("do_sample", False):
             raise NotImplementedError("only greedy decoding (do_sample=False) is on the hot path")
-        if kwargs.get("num_beams", 1) != 1:
-            raise NotImplementedError("beam search is outside the hot path")
         if inputs is not None:   # README form
             tokenizer = args.pop(0) if args else kwargs.pop("tokenizer", None)
             tokenizer = tokenizer if tokenizer is not None else self.tokenizer
@@ -515,9 +585,10 @@ class EmmaXForActionPrediction:
             if len(rows) != 1:
                 raise ValueError("Generation with batch size > 1 is not currently supported!")
             processing = self._kw_processing(rows, kwargs)
+            beams = self._kw_beams(kwargs, processing)   # num_beams > 1: the best hypothesis (row 0 of the group) is decoded
             max_new = self._max_new(rows, kwargs.get("max_new_tokens", None if "max_length" in kwargs else 512), kwargs.get("max_length"), None)
             new_ids, lens = self.generate_ids(rows, inputs.get("pixel_values"), inputs.get("frames_u8"), max_new_tokens=max_new,
-                                              processing=processing)
+                                              processing=processing, **self._beam_kw(beams))
             actions, text = self._postprocess(new_ids[0, : int(lens[0])].cpu().tolist(), tokenizer, "act")
             return actions[0], text
         # native form
@@ -543,20 +614,24 @@ class EmmaXForActionPrediction:
         enc = tokenizer(vals["prompt_text"], truncation=True, return_tensors="pt")
         rows = self._rows(enc.input_ids)
         processing = self._kw_processing(rows, kwargs)
+        beams = self._kw_beams(kwargs, processing)
         max_new = self._max_new(rows, kwargs.get("max_new_tokens"), kwargs.get("max_length"), None)
         feat = self.image_transform(vals["image"])
-        new_ids, lens = self.generate_ids(rows, feat["pixel_values"], feat.get("frames_u8"), max_new_tokens=max_new, processing=processing)
+        new_ids, lens = self.generate_ids(rows, feat["pixel_values"], feat.get("frames_u8"), max_new_tokens=max_new, processing=processing,
+                                          **self._beam_kw(beams))
         return self._postprocess(new_ids[0, : int(lens[0])].cpu().tolist(), tokenizer, vals["type"])
 
     @torch.inference_mode()
     def generate_actions_batch(self, frames_u8: torch.Tensor, prompt_rows: Sequence[Sequence[int]], max_new_tokens: int = 512,
-                               stop_on_eos: bool = True, tokenizer=None, sampling=None, processing=None):
+                               stop_on_eos: bool = True, tokenizer=None, sampling=None, processing=None, beams: Optional[BeamParams] = None):
         """Batched extension: returns (actions f32 [B,7], new_ids int32 [B,T], lens int32 [B]).
 
         With `tokenizer` each row goes ids -> text -> Solver exactly like the bs=1 path; without it the ids-level
         stand-in `actions_from_ids` is used (synthetic weights / throughput runs).  `sampling` / `processing`: as generate_ids (None = off)."""
         new_ids, lens = self.generate_ids([list(r) for r in prompt_rows], None, frames_u8, max_new_tokens, stop_on_eos, sampling=sampling,
-                                          processing=processing)
+                                          processing=processing, **self._beam_kw(beams))
+        if beams is not None:   # the best hypothesis of every prompt
+            new_ids, lens = new_ids[:: beams.num_beams].contiguous(), lens[:: beams.num_beams].contiguous()
         ids_h, lens_h = new_ids.cpu(), lens.cpu().tolist()
         acts = np.zeros((len(lens_h), 7), dtype=np.float32)
         stats = self.get_action_stats(None)

@@ -70,6 +70,35 @@ class LogitsProcessing:
         return float(self.repetition_penalty) == 1.0 and int(self.no_repeat_ngram_size) == 0 and int(self.min_new_tokens) == 0
 
 
+MAX_BEAMS = 8   # EMMAX_MAX_BEAMS (include/emmax.h)
+
+
+@dataclass(frozen=True)
+class BeamParams:
+    """HF generate's beam search arguments (do_sample = False), run inside the decode step on shared KV pages (include/emmax.h:
+    emmax_session_set_beams).  The checks are GenerationConfig.validate's."""
+    num_beams: int = 2                  # 2 .. MAX_BEAMS (1 is not a beam run: it takes the greedy path)
+    length_penalty: float = 1.0         # finite; hypotheses are ranked by score / length ** length_penalty
+    early_stopping: Union[bool, str] = False   # False, True or "never"
+    num_return_sequences: int = 1       # <= num_beams, best first
+
+    def __post_init__(self):
+        k = self.num_beams
+        if isinstance(k, bool) or not isinstance(k, int) or not 2 <= k <= MAX_BEAMS:
+            raise ValueError(f"num_beams must be an integer in 2..{MAX_BEAMS}, got {k}")
+        lp = self.length_penalty
+        if isinstance(lp, bool) or not isinstance(lp, (int, float)) or not math.isfinite(float(lp)):
+            raise ValueError(f"length_penalty must be a finite float, got {lp}")
+        es = self.early_stopping
+        if not (es is True or es is False or es == "never"):
+            raise ValueError(f"`early_stopping` must be a boolean or 'never', but is {es}.")
+        n = self.num_return_sequences
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"num_return_sequences must be an integer >= 1, got {n}")
+        if n > k:
+            raise ValueError(f"`num_return_sequences` ({n}) has to be smaller or equal to `num_beams` ({k}).")
+
+
 def draw_seed(generator: Optional[torch.Generator] = None) -> int:
     """A 64-bit seed from `generator` (default: torch's global CPU generator, so torch.manual_seed(s) fixes it)."""
     hi = int(torch.randint(0, 1 << 32, (1,), generator=generator, dtype=torch.int64))

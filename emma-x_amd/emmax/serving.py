@@ -29,6 +29,7 @@ class Request:
     max_new_tokens: int = 512
     sampling: Any = None   # emmax.sampling.SamplingParams: drawn in the decode step with the request's seed (None: draw_seed()) and subseq 0; None = greedy
     processing: Any = None   # emmax.sampling.LogitsProcessing: HF's repetition penalty / n-gram ban / min-new-tokens in the decode step; None = off
+    beams: Any = None        # beam groups are not served as slots: a request with emmax.sampling.BeamParams is refused at submit
 
 
 @dataclass
@@ -109,11 +110,16 @@ class SlotScheduler:
         if self.overlap and hasattr(engine, "ensure_stage_rows"):
             engine.ensure_stage_rows(n_slots)
         engine.set_stop(list(stop_trigger), stop_after)
+        if getattr(engine, "beams", 0):   # a beam generation ran on this session: slots are served with beams off
+            engine.clear_beams()
         engine.slots_open(n_slots)
 
     def submit(self, req: Request) -> None:
         if len(req.prompt_ids) < 1:
             raise ValueError("empty prompt")
+        if getattr(req, "beams", None) is not None:
+            raise NotImplementedError("beam search is not served as request slots: a beam group is num_beams rows that reorder together -- "
+                                      "use model.generate(num_beams=...) / generate_ids(beams=...)")
         self.queue.append((req, self.clock()))
 
     def _sampling_rows(self, reqs):

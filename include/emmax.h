@@ -39,8 +39,9 @@ extern "C" {
  *   6: emmax_op_sample (seeded sampling over rows of logits);  7: sampling inside the decode step (emmax_session_set_sampling and the calls
  *   around it), the workspace grew the per-row sampling state;  8: logits processors and scores inside the decode step
  *   (emmax_session_set_processing, emmax_session_set_scores and the calls around them), the workspace grew the per-row processing state and
- *   prompt ids. */
-#define EMMAX_ABI_VERSION 8
+ *   prompt ids;  9: beam search inside the decode step (emmax_session_set_beams and the calls around it), the workspace grew the beam
+ *   state and trace; the paged KV region did not grow. */
+#define EMMAX_ABI_VERSION 9
 
 typedef enum emmax_status {
     EMMAX_OK = 0,
@@ -322,6 +323,74 @@ int emmax_slots_set_processing_staged(emmax_session* s, int n, const float* pena
 int emmax_session_clear_processing(emmax_session* s, emmax_stream stream);
 int emmax_session_processing(const emmax_session* s);
 int emmax_session_set_scores(emmax_session* s, float* scores_dev, float* logits_dev, int max_new, emmax_stream stream);
+
+/* ---- beam search inside the decode step (ABI 9) ----------------------------------------------------------------------
+ * The semantics of transformers 5.15's GenerationMixin._beam_search (_get_top_k_continuations, _get_running_beams_for_next_iteration,
+ * _update_finished_beams, _check_early_stop_heuristic, _beam_search_has_unfinished_sequences) for do_sample = False, one EOS id and no
+ * logits processor.  A GROUP is one request (one prompt, one frame) with K = num_beams beams; a session decodes G groups as G x K rows
+ * (row g K + k = running beam k of group g), G x K <= min(max_batch, emmax_model_max_decode_batch).  2 <= K <= EMMAX_MAX_BEAMS (8); K = 1
+ * is not a beam run.  The arithmetic is pinned so that a host can replay it bit for bit (tests/beam_ref.py does):
+ *   lse            per running row, one fp32 log-sum-exp of the raw fp32 logit row: m = max l, s = sum expf(l_i - m) in the fixed order of
+ *                  the sampling kernel (entry i = 4 (g 1024 + lane) + c summed over (g, c) per lane, the 64 lanes of a wave by xor
+ *                  butterfly 32 .. 1, the 16 waves in order), lse = m + logf(s).  The trace returns it: a replay takes it from there.
+ *   candidates     acc = fp32(fp32(l - lse) + score), score = the row's running score: two correctly rounded fp32 operations.
+ *   masks          HF's -1e9 masks are fp32 additions of -1e9f, applied in HF's order; a mask that is off adds nothing.
+ *   length penalty never pow on the device: emmax_session_set_beams uploads pw[n] = fp32(pow((double)n, (double)length_penalty)) for
+ *                  n = 0 .. max_ctx, and the device divides (score / pw[n], correctly rounded).
+ *   top 2K         per group the best 2K of the K x V candidates (beams_to_keep = 2K), acc descending; EQUAL acc (as fp32 values) are
+ *                  ordered by the lower flat index beam V + token.  (torch.topk leaves the order of equal values open.)
+ *   running beams  the best K of the 2K by fp32(acc + -1e9f [the candidate stopped]), ties to the lower place in the list.  A candidate
+ *                  stops when its token is eos_id (stop_on_eos) or it is the max_new-th generated token.
+ *   finished set   HF's merge: the kept K followed by the 2K candidates scored fp32(acc / pw[n]) + masks (all K kept are finished and
+ *                  early_stopping is True; the heuristic is no longer unsatisfied; the candidate is not a just-finished one among the TOP K),
+ *                  best K, ties to the lower place in the merged list.  n = the candidate's generated length.
+ *   early stop     early_stopping 0 = False, 1 = True, 2 = "never", HF's heuristic with pw[] (best running score / pw[n], or / pw[max_new]
+ *                  for "never" with a positive penalty, against min kept score where finished, else -1e9f).
+ *   first step     taken from the prefill's one logit row per group with running score 0.  HF's initial scores [0, -1e9, ...] select the
+ *                  same candidates whenever that row has 2K entries above -inf.
+ *   NaN            a NaN never compares greater: a row with a NaN logit has lse = NaN and contributes no candidate; a group with no
+ *                  candidate left is done and keeps what it has.
+ * Known differences from HF: lengths enter only as generated-token counts (HF left-pads a batch, these rows are packed: a group's result
+ * does not depend on the other groups' prompt lengths); the trigger stop rule of emmax_session_set_stop is not applied to beams.
+ *
+ * THE CACHE FOLLOWS THE BEAMS ON THE PAGE TABLE.  Complete pages (64 tokens) are immutable and shared by reference; only the page a beam
+ * is filling is private.  After every step beam j continues parent p(j): page-table row j takes p(j)'s entries, and where p(j) != j the
+ * parent's partial page is copied (every layer, K and V, every plane of the cache format) into j's SPARE page, which then swaps with j's
+ * old one -- never in place, because that old page may be another beam's source in the same step.  A page that the step completed is shared
+ * instead of copied.  The prefill runs ONE row per group and forks it: K page-table rows over the prompt's complete pages, the partial
+ * page copied K - 1 times.  Group g lives on the pages of rows g K .. g K + K - 1; pages of a dead lineage are not reclaimed within a run:
+ * a group uses  floor(S / 64) shared prompt pages + K x (pages from floor(S / 64) to the last generated position) + K spares,  S = patches +
+ * prompt ids.  Where that exceeds K x max_pages emmax_generate returns EMMAX_ERR_NOMEM before it decodes anything (emmax_prefill* checks
+ * the same for max_new = 1).  emmax_session_bytes is the same for the same max_batch: the KV region does not grow.
+ *
+ *   emmax_session_set_beams    K = num_beams, length_penalty finite, early_stopping in {0, 1, 2}; 2 <= K <= min(8, max_batch), vocab >= 2K
+ *                              and <= 32768 -- else EMMAX_ERR_INVALID.  EMMAX_ERR_STATE while request slots are open, sampling or
+ *                              processing is on, or a `scores` buffer is bound (a raw `logits` buffer may stay: [max_new][G K][vocab],
+ *                              row g K + k at step t = the row running beam k read at that step, before the step's reorder; the prefill's
+ *                              row is written at [0][g K]).  Synchronises the stream.
+ *   emmax_session_clear_beams  beams off; the page table is the identity again.  With beams off a session launches exactly what it
+ *                              launched before ABI 9.  emmax_session_beams: K, 0 = off, -1 null session.
+ * With beams on: emmax_prefill* takes G rows (G x K must fit); emmax_generate(max_new, ...) runs the first beam step, the fork and the
+ * decode steps of G x K rows (the step graph is keyed on beams on / off and K; parents, scores and pages are device words), resolves the
+ * kept hypotheses and returns them in out_ids [G K][max_new] / out_lens [G K], best first per group, pad_id behind the end; it runs once per
+ * prefill.  emmax_decode_step, emmax_set_current_tokens, emmax_last_logits, the slot calls, emmax_session_set_sampling /
+ * _set_processing and emmax_session_set_scores with a `scores` buffer return EMMAX_ERR_STATE.
+ *   emmax_session_beam_result  after emmax_generate: seq [G K][max_new] (as out_ids), len [G K], score [G K] fp32 = HF's sequences_scores
+ *                              of all K kept hypotheses, beam_indices [G K][max_new] (HF's meaning: the session row g K + parent beam each
+ *                              token was continued from, -1 behind the end).  Device pointers; any may be NULL.
+ *   emmax_session_beam_trace   per step t < max_new and running beam: tok, parent [max_new][G K] int32, score (the running score after
+ *                              the step), lse (of the row the step read for this beam slot; step 0 read one row per group: slot k > 0
+ *                              holds 0) [max_new][G K] fp32; and the step's candidate list the finished-set update consumed: cand_idx
+ *                              [max_new][G 2K] int32 (flat index beam V + token, -1 = none) and cand_acc fp32.  Steps a group did not run
+ *                              hold tok = parent = cand_idx = -1 and zeros.  Device pointers; any may be NULL. */
+#define EMMAX_MAX_BEAMS 8
+int emmax_session_set_beams(emmax_session* s, int num_beams, double length_penalty, int early_stopping, emmax_stream stream);
+int emmax_session_clear_beams(emmax_session* s, emmax_stream stream);
+int emmax_session_beams(const emmax_session* s);
+int emmax_session_beam_result(emmax_session* s, int max_new, int32_t* seq_dev, int32_t* len_dev, float* score_dev, int32_t* beam_indices_dev,
+                              emmax_stream stream);
+int emmax_session_beam_trace(emmax_session* s, int max_new, int32_t* tok_dev, int32_t* parent_dev, float* score_dev, float* lse_dev,
+                             int32_t* cand_idx_dev, float* cand_acc_dev, emmax_stream stream);
 
 /* ---- single-kernel entry points (parity tests + micro-benchmarks) -------------------------------------------------- */
 /* C[M,N] = epilogue(A[M,K] @ W[N,K]^T): bf16 in, fp32 accumulate on MFMA.  K % 64 == 0, N % 128 == 0.

@@ -9,6 +9,10 @@ greedy step, at the shapes of the headline bench (Emma-X-7B synthetic weights, 5
   phf      the same with the HF-default draw
   pscores  pgreedy with output_scores: the processed rows stored at every step ([new tokens, B, vocab] fp32)
 
+--beams K1,K2,..  (ABI 9) instead: one K-beam group (`generate(num_beams=K)`: G = 1, K rows on shared KV pages) against K independent greedy
+rows of the same prompt -- ms per step, time to the first token (prefill + first step: the beam group prefills ONE row) and end-to-end
+`generate_actions_batch`; one JSON line per K.  For the kernel split run it under `rocprofv3 --kernel-trace --stats`.
+
 EOS is disabled (as in bench.py), so every row decodes every step.  The time of one generate call after its prefill, divided by its decode
 steps (new tokens - 1), median over --reps calls.  Prints one JSON line per (batch, mode)."""
 import argparse
@@ -42,9 +46,11 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--modes", default=",".join(MODES))
     ap.add_argument("--tiny", action="store_true")
+    ap.add_argument("--beams", default="", help="comma list of num_beams: measure one beam group against as many greedy rows")
     args = ap.parse_args()
     dev = "cuda:0"
-    batches = [int(b) for b in args.batches.split(",")]
+    beam_ks = [int(k) for k in args.beams.split(",") if k]
+    batches = [int(b) for b in args.batches.split(",")] if not beam_ks else [max(beam_ks)]
     cfg = EmmaXConfig.tiny() if args.tiny else EmmaXConfig.emma_x_7b()
     cfg.eos_token_id = -1
     P, T = args.prompt_tokens, args.new_tokens
@@ -53,6 +59,8 @@ def main():
     rng = np.random.default_rng(1234)
     frames = torch.from_numpy(rng.integers(0, 256, size=(max(batches), 224, 224, 3), dtype=np.uint8)).to(dev)
     prompts = [[1] + [int(x) for x in rng.integers(3, 31744, size=P - 1)] for _ in range(max(batches))]
+    if beam_ks:
+        return bench_beams(model, eng, cfg, frames, prompts, beam_ks, P, T, args.reps)
     for B in batches:
         for mode in args.modes.split(","):
             times = []
@@ -73,6 +81,44 @@ def main():
             eng.set_scores(None, None)
     eng.clear_sampling()
     eng.clear_processing()
+
+
+def bench_beams(model, eng, cfg, frames, prompts, ks, P, T, reps):
+    from emmax.sampling import BeamParams
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    def med(fn, prep=None):
+        out = []
+        for rep in range(reps + 1):   # (the first call warms up)
+            if prep:
+                prep()
+            t = timed(fn)
+            if rep:
+                out.append(t)
+        return 1e3 * float(np.median(out))
+
+    for K in ks:
+        same = [prompts[0]] * K
+        fr_k = frames[:1].expand(K, -1, -1, -1).contiguous()
+        bp = BeamParams(K, 1.0, False, 1)
+        rec = {"num_beams": K, "prompt": P, "new_tokens": T, "reps": reps}
+        # ms per step: generate after its prefill (the beam call includes the first beam step, the fork and the final resolve)
+        rec["greedy_rows_ms_per_step"] = round(med(lambda: eng.generate(T, stop_on_eos=False), lambda: model._prefill(same, frames_u8=fr_k, max_new=T)) / (T - 1), 4)
+        rec["beam_ms_per_step"] = round(med(lambda: eng.generate(T, stop_on_eos=False), lambda: model._prefill(prompts[:1], frames_u8=frames[:1], max_new=T, beams=bp)) / (T - 1), 4)
+        # time to the first token: vision + prefill + the first step
+        rec["beam_first_token_ms"] = round(med(lambda: (model._prefill(prompts[:1], frames_u8=frames[:1], max_new=T, beams=bp), eng.generate(1, stop_on_eos=False))), 3)
+        rec["greedy_rows_first_token_ms"] = round(med(lambda: (model._prefill(same, frames_u8=fr_k, max_new=T), eng.generate(1, stop_on_eos=False))), 3)
+        # end to end: frames + prompts -> actions
+        rec["beam_actions_ms"] = round(med(lambda: model.generate_actions_batch(frames[:1], prompts[:1], T, stop_on_eos=False, beams=bp)), 2)
+        rec["greedy_rows_actions_ms"] = round(med(lambda: model.generate_actions_batch(fr_k, same, T, stop_on_eos=False)), 2)
+        print(json.dumps(rec), flush=True)
+    eng.clear_beams()
 
 
 if __name__ == "__main__":
