@@ -1,0 +1,264 @@
+// generate.hip -- the calls that drive decode steps: emmax_decode_step, emmax_generate (greedy / sampled / processing / beams), the last
+// logits, and slot serving (continuous batching: open, prefill into slots or staging rows, commit, step, state, output, release).
+#include "session.h"
+
+extern "C" {
+
+int emmax_last_logits(emmax_session* s, float* out, emmax_stream stream) {
+    if (!s || !out) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->prefilled) return fail(EMMAX_ERR_STATE, "prefill has not run");
+    if (s->beam.K) return fail(EMMAX_ERR_STATE, "emmax_last_logits is not served while beams are on (bind a logits buffer: emmax_session_set_scores)");
+    return run_lm_head_step(s, s->cur_B, false, out, false, (hipStream_t)stream);
+}
+
+int emmax_decode_step(emmax_session* s, emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->prefilled) return fail(EMMAX_ERR_STATE, "decode before prefill");
+    if (s->beam.K) return fail(EMMAX_ERR_STATE, "with beams on the decode steps run inside emmax_generate");
+    s->dec_steps += 1;
+    if (emmax_tune().graph) {   // the step is a replay of the captured hipGraph (as in emmax_generate / emmax_slots_step)
+        StreamScope sc(s, stream);
+        if (sc.error()) return sc.error();
+        const hipStream_t st = sc.stream();
+        if (int r = ensure_graph(s, s->cur_B, st) == 0 ? launch_graph_step(s, s->cur_B, st) : run_decode_step(s, s->cur_B, st)) return r;
+        return sc.leave();
+    }
+    s->last_step_graph = 0;   // eager mode: emmax_session_graph_active() reports what the steps really do; the graph is kept
+    return run_decode_step(s, s->cur_B, (hipStream_t)stream);
+}
+
+int emmax_set_current_tokens(emmax_session* s, const int32_t* toks, emmax_stream st) {
+    if (!s || !toks) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->prefilled) return fail(EMMAX_ERR_STATE, "no active sequences");
+    if (s->slots_open) return fail(EMMAX_ERR_STATE, "caller-supplied tokens are not supported while request slots are open");
+    if (s->beam.K) return fail(EMMAX_ERR_STATE, "caller-supplied tokens are not supported while beams are on");
+    if (s->proc.on) return fail(EMMAX_ERR_STATE, "caller-supplied tokens are not supported while logits processing is on (they would be missing from the history)");
+    // the rows decode again (done flag cleared): the next step appends at position <= S_b + dec_steps, which must exist
+    int maxS = 0;
+    for (int b = 0; b < s->cur_B && b < (int)s->S.size(); ++b) maxS = std::max(maxS, s->S[b]);
+    if (maxS + s->dec_steps + 1 >= s->max_ctx)
+        return fail(EMMAX_ERR_NOMEM, "context %d + 1 reaches max_ctx %d: no room to decode a caller-supplied token", maxS + s->dec_steps, s->max_ctx);
+    KCHK(launch_set_tokens(s->cur_tok, toks, s->cur_B, s->done, s->stop_m, s->stop_after, s->max_new_d, s->max_out, (hipStream_t)st));
+    return 0;
+}
+
+int emmax_generate(emmax_session* s, int max_new, int stop_on_eos, int32_t* out_ids, int32_t* out_lens, emmax_stream stream) {
+    if (!s || !out_ids || !out_lens) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->prefilled) return fail(EMMAX_ERR_STATE, "generate before prefill");
+    if (max_new < 1 || max_new > s->max_out) return fail(EMMAX_ERR_INVALID, "max_new_tokens %d outside 1..%d", max_new, s->max_out);
+    if (s->beam.K) {
+        if (!s->beam.ready || s->beam.forked) return fail(EMMAX_ERR_STATE, "with beams on emmax_generate runs once per prefill (the prefill must follow emmax_session_set_beams)");
+        for (int g = 0; g < s->beam.G; ++g)
+            if (!beam_pages_fit(s, s->S[g], max_new))
+                return fail(EMMAX_ERR_NOMEM, "group %d: context %d + %d new tokens x %d beams do not fit max_ctx %d / the %d pages of its rows", g, s->S[g], max_new,
+                            s->beam.K, s->max_ctx, s->beam.K * s->max_pages);
+    }
+    StreamScope sc(s, stream);   // (the loop may replay a captured graph)
+    if (sc.error()) return sc.error();
+    const hipStream_t st = sc.stream();
+    if (s->beam.K) {   // the first beam step from the prefill's logit rows, and the fork into G x K rows
+        const int rows = s->beam.G * s->beam.K, ld = std::min(s->max_batch, EMMAX_MAX_DECODE_BATCH);
+        s->beam.eos = stop_on_eos ? s->m->cfg.eos_id : -1;
+        s->beam.max_new = max_new;
+        KCHK(launch_set_ints(s->max_new_d, rows, max_new, st));
+        KCHK(launch_beam_reset(rows, s->beam.K, s->beam.run, s->beam.fin_score, s->beam.fin_flag, s->beam.fin_t, s->beam.fin_par, s->beam.fin_tok, s->beam.grp,
+                               s->beam.csrc, st));
+        const size_t n1 = (size_t)max_new * ld * 4;
+        HIPCHK(hipMemsetAsync(s->beam.tr_tok, 0xff, n1, st));
+        HIPCHK(hipMemsetAsync(s->beam.tr_par, 0xff, n1, st));
+        HIPCHK(hipMemsetAsync(s->beam.tr_score, 0, n1, st));
+        HIPCHK(hipMemsetAsync(s->beam.tr_lse, 0, n1, st));
+        HIPCHK(hipMemsetAsync(s->beam.tc_idx, 0xff, 2 * n1, st));
+        HIPCHK(hipMemsetAsync(s->beam.tc_acc, 0, 2 * n1, st));
+        if (s->scores.on) KCHK(launch_set_int((int32_t*)(s->scores.words + 3), rows, st));
+        if (int r = launch_beam_finish(s, true, st)) return r;
+        for (int g = s->beam.G - 1; g >= 0; --g)
+            for (int k = 0; k < s->beam.K; ++k) s->S[g * s->beam.K + k] = s->S[g];
+        s->cur_B = rows;
+        s->beam.forked = true;
+        s->beam.ready = false;
+    }
+    const int B = s->cur_B;
+    if (!s->beam.K) KCHK(launch_set_ints(s->max_new_d, B, max_new, st));
+    const bool use_graph = (max_new > 2) && ensure_graph(s, B, st) == 0;
+    const int CHK = 16;
+    int32_t* done_host = s->pinned->done;
+    bool pending = false;
+    for (int i = 1; i < max_new; ++i) {
+        s->dec_steps += 1;
+        if (int r = use_graph ? launch_graph_step(s, B, st) : run_decode_step(s, B, st)) return r;
+        if (stop_on_eos && (i % CHK) == 0) {
+            if (pending) {   // the previous read-back is certainly complete once its event fired
+                HIPCHK(hipEventSynchronize(s->ev));
+                bool all = true;
+                for (int b = 0; b < B; ++b) all = all && (done_host[b] != 0);
+                if (all) { pending = false; break; }
+            }
+            HIPCHK(hipMemcpyAsync(done_host, s->done, B * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipEventRecord(s->ev, st));
+            pending = true;
+        }
+    }
+    if (s->beam.K) {   // the kept hypotheses, best first per group, out of the token / parent tables
+        BeamResolveParams q;
+        memset(&q, 0, sizeof(q));
+        q.rows = B; q.K = s->beam.K; q.max_out = s->max_out; q.max_new = max_new; q.tr_ld = std::min(s->max_batch, EMMAX_MAX_DECODE_BATCH);
+        q.pad_id = s->m->cfg.pad_id;
+        q.fin_t = s->beam.fin_t; q.fin_par = s->beam.fin_par; q.fin_tok = s->beam.fin_tok; q.tr_tok = s->beam.tr_tok; q.tr_par = s->beam.tr_par;
+        q.fin_score = s->beam.fin_score; q.seq = s->out_ids; q.bidx = s->beam.res_bidx; q.len = s->beam.res_len; q.score = s->beam.res_score;
+        KCHK(launch_beam_resolve(q, st));
+    }
+    HIPCHK(hipMemcpy2DAsync(out_ids, (size_t)max_new * 4, s->out_ids, (size_t)s->max_out * 4, (size_t)max_new * 4, B,
+                            hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(out_lens, s->beam.K ? s->beam.res_len : s->n_out, B * 4, hipMemcpyDeviceToDevice, st));
+    return sc.leave();
+}
+
+int emmax_slots_open(emmax_session* s, int n_slots, emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (s->beam.K) return fail(EMMAX_ERR_STATE, "request slots are not served while beams are on (emmax_session_clear_beams)");
+    const int max_rows = s->exact ? EMMAX_MAX_DECODE_BATCH : model_max_decode_batch(s->m);
+    if (n_slots < 1 || n_slots > s->max_batch || n_slots > max_rows)
+        return fail(EMMAX_ERR_INVALID, "%d slots outside 1..min(max_batch=%d, %d)", n_slots, s->max_batch, max_rows);
+    if (n_slots >= EMMAX_MFMA_MIN_BATCH && !s->m->aux_built)
+        return fail(EMMAX_ERR_STATE, "%d slots decode on the fragment-major weight copies: call emmax_model_build_aux first", n_slots);
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    KCHK(launch_slots_idle(n_slots, s->cur_tok, s->ctx_len, s->done, s->n_out, s->m->cfg.pad_id, sc.stream()));
+    s->cur_B = n_slots;
+    s->S.assign(s->rows_total, 0);
+    s->slots_open = true;
+    s->scores.on = false;   // no scores in slot serving (the bound buffers were a generate call's)
+    s->prefilled = true;   // decode steps are legal: idle slots are rows that are already done
+    return sc.leave();
+}
+
+int emmax_slot_prefill(emmax_session* s, int slot, const int32_t* ids, int len, const void* patches, int max_new, emmax_stream stream) {
+    if (!s || !ids) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slot_prefill before emmax_slots_open");
+    if (slot < 0 || slot >= s->cur_B) return fail(EMMAX_ERR_INVALID, "slot %d outside 0..%d", slot, s->cur_B - 1);
+    if (max_new < 1 || max_new > s->max_out) return fail(EMMAX_ERR_INVALID, "max_new_tokens %d outside 1..%d", max_new, s->max_out);
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    if (int r = run_prefill(s, ids, &len, 1, len, patches, sc.stream(), slot)) return r;
+    KCHK(launch_set_ints(s->max_new_d + slot, 1, max_new, sc.stream()));
+    return sc.leave();
+}
+
+int emmax_slots_prefill(emmax_session* s, int slot0, int n, const int32_t* ids, int P_max, const int32_t* lens_host, const void* patches,
+                        const int32_t* max_new_host, emmax_stream stream) {
+    if (!s || !ids || !lens_host || !max_new_host) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slots_prefill before emmax_slots_open");
+    if (n < 1 || slot0 < 0 || slot0 + n > s->cur_B) return fail(EMMAX_ERR_INVALID, "slots %d..%d outside 0..%d", slot0, slot0 + n - 1, s->cur_B - 1);
+    for (int i = 0; i < n; ++i)
+        if (max_new_host[i] < 1 || max_new_host[i] > s->max_out)
+            return fail(EMMAX_ERR_INVALID, "slot %d: max_new_tokens %d outside 1..%d", slot0 + i, max_new_host[i], s->max_out);
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    if (int r = run_prefill(s, ids, lens_host, n, P_max, patches, sc.stream(), slot0)) return r;   // one packed pass over the n requests (ragged lengths)
+    for (int i = 0; i < n; ++i) KCHK(launch_set_ints(s->max_new_d + slot0 + i, 1, max_new_host[i], sc.stream()));
+    return sc.leave();
+}
+
+int emmax_slots_prefill_staged(emmax_session* s, int n, const int32_t* ids, int P_max, const int32_t* lens_host, const void* patches,
+                               const int32_t* max_new_host, emmax_stream stream) {
+    if (!s || !ids || !lens_host || !max_new_host) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slots_prefill_staged before emmax_slots_open");
+    if (s->n_stg == 0)
+        return fail(EMMAX_ERR_INVALID, "session created without staging rows: use emmax_session_create_ex(..., stage_rows > 0) (a plain emmax_session_create gives none since ABI 4)");
+    if (n < 1 || n > s->n_stg)
+        return fail(EMMAX_ERR_INVALID, "%d staged requests outside 1..%d (the session's staging rows: emmax_session_create_ex)", n, s->n_stg);
+    if ((uintptr_t)stream <= 2) return fail(EMMAX_ERR_INVALID, "a staged prefill needs its own (non-default) stream: it runs beside the decode steps");
+    for (int i = 0; i < n; ++i)
+        if (max_new_host[i] < 1 || max_new_host[i] > s->max_out)
+            return fail(EMMAX_ERR_INVALID, "staged request %d: max_new_tokens %d outside 1..%d", i, max_new_host[i], s->max_out);
+    hipStream_t st = (hipStream_t)stream;
+    if (int r = run_prefill(s, ids, lens_host, n, P_max, patches, st, s->stg0)) return r;
+    for (int i = 0; i < n; ++i) KCHK(launch_set_ints(s->max_new_d + s->stg0 + i, 1, max_new_host[i], st));
+    return 0;
+}
+
+int emmax_slots_commit(emmax_session* s, const int32_t* staged_idx_host, const int32_t* slots_host, int n, emmax_stream stream) {
+    if (!s || !slots_host || !staged_idx_host) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slots_commit before emmax_slots_open");
+    if (n < 1 || n > s->n_stg) return fail(EMMAX_ERR_INVALID, "%d commits outside 1..%d", n, s->n_stg);
+    CommitParams c;
+    memset(&c, 0, sizeof(c));
+    for (int i = 0; i < n; ++i) {
+        if (slots_host[i] < 0 || slots_host[i] >= s->cur_B) return fail(EMMAX_ERR_INVALID, "slot %d outside 0..%d", slots_host[i], s->cur_B - 1);
+        if (staged_idx_host[i] < 0 || staged_idx_host[i] >= s->n_stg) return fail(EMMAX_ERR_INVALID, "staged request %d outside 0..%d", staged_idx_host[i], s->n_stg - 1);
+        for (int j = 0; j < i; ++j)
+            if (slots_host[j] == slots_host[i] || staged_idx_host[j] == staged_idx_host[i]) return fail(EMMAX_ERR_INVALID, "slot / staged request named twice");
+        c.slot[i] = slots_host[i];
+        c.src[i] = s->stg0 + staged_idx_host[i];
+    }
+    c.n = n; c.max_pages = s->max_pages; c.max_out = s->max_out;
+    c.cur_tok = s->cur_tok; c.ctx_len = s->ctx_len; c.done = s->done; c.n_out = s->n_out; c.max_new = s->max_new_d;
+    c.stop_m = s->stop_m; c.stop_after = s->stop_after; c.out_ids = s->out_ids; c.page_table = s->page_table;
+    if (s->samp.on) {
+        c.temperature = s->samp.t; c.top_k = s->samp.k; c.top_p = s->samp.p; c.seed = s->samp.seed; c.subseq = s->samp.sub;
+        c.logprob = s->samp.logprob;
+    }
+    if (s->proc.on) {
+        c.penalty = s->proc.pen; c.ngram = s->proc.ng; c.min_new = s->proc.mn; c.hist = s->proc.hist; c.hist_len = s->proc.hist_len;
+        c.max_prompt = s->max_prompt;
+    }
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    KCHK(launch_slots_commit(c, sc.stream()));
+    for (int i = 0; i < n; ++i) s->S[slots_host[i]] = s->S[s->stg0 + staged_idx_host[i]];
+    return sc.leave();
+}
+
+int emmax_slots_step(emmax_session* s, int n_steps, emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slots_step before emmax_slots_open");
+    if (n_steps < 1) return fail(EMMAX_ERR_INVALID, "n_steps %d < 1", n_steps);
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    const hipStream_t st = sc.stream();
+    const int B = s->cur_B;
+    const bool use_graph = ensure_graph(s, B, st) == 0;
+    for (int i = 0; i < n_steps; ++i) {
+        if (int r = use_graph ? launch_graph_step(s, B, st) : run_decode_step(s, B, st)) return r;
+    }
+    return sc.leave();
+}
+
+int emmax_slots_state(emmax_session* s, int32_t* done_out, int32_t* n_out_out, emmax_stream stream) {
+    if (!s || !done_out || !n_out_out) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slots_state before emmax_slots_open");
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    HIPCHK(hipMemcpyAsync(done_out, s->done, s->cur_B * 4, hipMemcpyDeviceToDevice, sc.stream()));
+    HIPCHK(hipMemcpyAsync(n_out_out, s->n_out, s->cur_B * 4, hipMemcpyDeviceToDevice, sc.stream()));
+    return sc.leave();
+}
+
+int emmax_slot_output(emmax_session* s, int slot, int32_t* ids_out, int n, emmax_stream stream) {
+    if (!s || !ids_out) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slot_output before emmax_slots_open");
+    if (slot < 0 || slot >= s->cur_B || n < 0 || n > s->max_out) return fail(EMMAX_ERR_INVALID, "slot %d / %d ids out of range", slot, n);
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    if (n > 0) HIPCHK(hipMemcpyAsync(ids_out, s->out_ids + (size_t)slot * s->max_out, (size_t)n * 4, hipMemcpyDeviceToDevice, sc.stream()));
+    return sc.leave();
+}
+
+int emmax_slot_release(emmax_session* s, int slot, emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slot_release before emmax_slots_open");
+    if (slot < 0 || slot >= s->cur_B) return fail(EMMAX_ERR_INVALID, "slot %d outside 0..%d", slot, s->cur_B - 1);
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    KCHK(launch_slots_idle(1, s->cur_tok + slot, s->ctx_len + slot, s->done + slot, s->n_out + slot, s->m->cfg.pad_id, sc.stream()));
+    s->S[slot] = 0;
+    return sc.leave();
+}
+
+int emmax_session_graph_active(emmax_session* s) {
+    if (s && !s->graph_exec && !s->graph_err.empty()) g_err = s->graph_err;   // why the capture was refused
+    return s && s->graph_exec && s->last_step_graph ? 1 : 0;
+}
+
+}  // extern "C"

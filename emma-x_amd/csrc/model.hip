@@ -1,28 +1,20 @@
-// model.hip -- host side of libemmax_hip.so: weight binding + re-layout (finalize), session buffers, the stage
-// orchestration (vision encode / prefill / decode step / generate with a captured hipGraph) and the C ABI of
-// include/emmax.h.  No device code lives here; kernels are in gemm / norm / attention / misc / decode .hip.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
+// model.hip -- the model half of the host side of libemmax_hip.so: the tuning table, weight binding + re-layout into the arenas
+// (finalize, build_aux) and the emmax_model_* / emmax_tuning_* part of the C ABI of include/emmax.h.  The session and the stages that
+// run on it are in session / vision / prefill / step / generate / modes / ops .hip (session.h).  No device code lives here; kernels
+// are in gemm / norm / attention / misc / decode .hip.
+#include <array>
 #include <cctype>
-#include <cstring>
+#include <cstdarg>
+#include <cstdlib>
 #include <mutex>
-#include <string>
-#include <unordered_map>
-#include <vector>
 
-#include "../../include/emmax.h"
-#include "common.h"
-#include "kernels.h"
+#include "session.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // errors
 // ---------------------------------------------------------------------------------------------------------------------
-static thread_local std::string g_err;
-static int fail(int code, const char* fmt, ...) {
+thread_local std::string g_err;
+int fail(int code, const char* fmt, ...) {
     char buf[1024];
     va_list ap;
     va_start(ap, fmt);
@@ -31,16 +23,6 @@ static int fail(int code, const char* fmt, ...) {
     g_err = buf;
     return code;
 }
-#define HIPCHK(x)                                                                                                   \
-    do {                                                                                                            \
-        hipError_t e_ = (x);                                                                                        \
-        if (e_ != hipSuccess) return fail(EMMAX_ERR_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-#define KCHK(x)                                                                                                     \
-    do {                                                                                                            \
-        int r_ = (x);                                                                                               \
-        if (r_ != 0) return fail(r_ == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "%s failed (%d) (%s:%d)", #x, r_, __FILE__, __LINE__); \
-    } while (0)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // tuning switches: one table, read from the environment once (kernels.h: EmmaxTune)
@@ -90,60 +72,6 @@ const EmmaxTune& emmax_tune() {
 // does (emmax/__init__.py sets the same variable at import).  VERDICT r05 next #6.
 __attribute__((constructor)) static void emmax_export_runtime_switches() { setenv("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0", 0); }
 
-static inline int pad_to(int x, int m) { return (x + m - 1) / m * m; }
-static const int PAGE = 64;   // KV page: 64 tokens x head_dim bf16 per kv head
-
-typedef uint16_t bf16;
-
-// ---------------------------------------------------------------------------------------------------------------------
-// model
-// ---------------------------------------------------------------------------------------------------------------------
-struct Bound {
-    const void* ptr;
-    int dtype;
-    std::vector<int64_t> shape;
-    int64_t numel() const {
-        int64_t n = 1;
-        for (auto s : shape) n *= s;
-        return n;
-    }
-};
-
-struct BlockW {
-    bf16 *n1w, *n1b, *qkv_w, *qkv_b, *proj_w, *proj_b, *ls1, *n2w, *n2b, *fc1_w, *fc1_b, *fc2_w, *fc2_b, *ls2;
-    float *ln1_s, *ln1_c, *ln2_s, *ln2_c;   // LayerNorm folded into qkv / fc1 (kernels.h: GemmParams::ln_*): column sums of W' and the constant term
-};
-struct TowerW {
-    int D, Dp, D3p, M, Mp, N, n_prefix, n_patches, hd, Kpe, n_blocks;
-    bf16 *patch_w, *patch_b, *pos, *cls, *reg;
-    std::vector<BlockW> blk;
-};
-struct LayerW {
-    bf16 *ln1, *wqkv, *wo, *ln2, *wgu, *wdown;
-    bf16 *wqkv_fm, *wo_fm, *wgu_fm, *wdown_fm;   // MFMA-fragment-major copies for the B >= 3 decode path (fp8 mode: e4m3 tiles)
-    bf16 *wqkv_km, *wgu_km;                      // ... in the row orders of decode_km.hip (RoPE pairs / (gate, up) pairs inside a 16-row tile)
-    float *wqkv_km_sc, *wgu_km_sc;               // fp8 mode: their per-row scales, in the same row order
-    float *wqkv_sc, *wo_sc, *wgu_sc, *wdown_sc;  // fp8 mode: per-row scales (null otherwise)
-    bf16 *wqkv_r8, *wo_r8, *wgu_r8, *wdown_r8;   // fp8 mode: the same e4m3 values as rows in the GEMV's span order (batch 1-2)
-};
-
-struct emmax_model {
-    emmax_config cfg;
-    std::unordered_map<std::string, Bound> bound;
-    bool finalized = false;
-    // derived dims
-    int H, inter, inter_p, q_dim, kv_dim, qkv_dim, vocab, vocab_p, V, Vp, P1, P1p;
-    TowerW tw[2];
-    bf16 *pj1_w, *pj1_b, *pj2_w, *pj2_b, *pj3_w, *pj3_b;
-    bf16 *embed, *final_norm, *lm_head, *lm_head_fm, *lm_head_r8 = nullptr;
-    float* lm_head_sc = nullptr;
-    bool fp8 = false;
-    bool ln_folded = false;      // the ViT LayerNorms are folded into the qkv / fc1 weights (tuning switch gemm_lnfuse at finalize)
-    bool aux_built = false;      // the batch >= 3 copies exist (fp8 models: always, they are part of the main arena)
-    bool aux_ab = false;         // ... including decode_mfma.hip's qkv / gate-up pair
-    std::vector<LayerW> layers;
-};
-
 static int check_config(const emmax_config& c) {
     for (int t = 0; t < 2; ++t) {
         const auto& w = c.tower[t];
@@ -165,6 +93,14 @@ static int check_config(const emmax_config& c) {
     if (c.vocab % 8) return fail(EMMAX_ERR_INVALID, "vocab must be a multiple of 8");
     if (c.decode_fp8 && (c.hidden % 64 || (c.n_heads * c.head_dim) % 64)) return fail(EMMAX_ERR_INVALID, "fp8 decode needs K % 64 == 0");
     return 0;
+}
+
+// the four projections of a decoder layer, in the order of their stages: rows N and columns K of the matrix, the row order of decode_km.hip's
+// copy (launch_repack_km's perm / head_dim; 0: natural -- that kernel reads the fragment-major copy) and how the step launches it (ProjW)
+struct ProjDim { int stage; int64_t N, K; int perm, perm_hd, gemv_mode, f8bit; };
+static std::array<ProjDim, 4> layer_projs(const emmax_model* m) {
+    return {{{STAGE_QKV, m->qkv_dim, m->H, 1, m->cfg.head_dim, GEMV_QKV, F8_QKV}, {STAGE_OPROJ, m->H, m->q_dim, 0, 0, GEMV_RESID, F8_OPROJ},
+             {STAGE_GATEUP, 2 * (int64_t)m->inter_p, m->H, 2, 0, GEMV_GATEUP, F8_GATEUP}, {STAGE_DOWN, m->H, m->inter_p, 0, 0, GEMV_RESID, F8_DOWN}}};
 }
 
 static void derive(emmax_model* m) {
@@ -198,22 +134,14 @@ static void derive(emmax_model* m) {
         T.blk.resize(T.n_blocks);
     }
     m->layers.resize(c.n_layers);
-    for (auto& L : m->layers) memset(&L, 0, sizeof(L));
-    m->lm_head_fm = nullptr;
+    for (auto& L : m->layers) {
+        memset(&L, 0, sizeof(L));
+        for (const ProjDim& d : layer_projs(m)) { L.proj[d.stage].gemv_mode = d.gemv_mode; L.proj[d.stage].f8bit = d.f8bit; }
+    }
+    m->lm_head_w = ProjW{};
+    m->lm_head_w.gemv_mode = GEMV_LMHEAD; m->lm_head_w.f8bit = F8_LMHEAD;
     m->fp8 = c.decode_fp8 != 0;
 }
-
-// Arena plan.  `base == nullptr` only sizes.  Every tensor is 256-byte aligned.
-struct Bump {
-    char* base;
-    int64_t off = 0;
-    bf16* take(int64_t elems) {
-        off = (off + 255) / 256 * 256;
-        bf16* p = base ? (bf16*)(base + off) : nullptr;
-        off += elems * 2;
-        return p;
-    }
-};
 
 static void plan_arena(emmax_model* m, Bump& b) {
     for (int t = 0; t < 2; ++t) {
@@ -241,42 +169,34 @@ static void plan_arena(emmax_model* m, Bump& b) {
     m->pj3_w = b.take((int64_t)m->H * m->H); m->pj3_b = b.take(m->H);
     m->embed = b.take((int64_t)m->vocab * m->H);
     for (auto& L : m->layers) {
+        const auto dims = layer_projs(m);   // [0..3]: qkv, o-proj, gate-up, down
+        ProjW *const q = &L.proj[STAGE_QKV], *const o = &L.proj[STAGE_OPROJ], *const g = &L.proj[STAGE_GATEUP], *const d = &L.proj[STAGE_DOWN];
         L.ln1 = b.take(m->H);
-        L.wqkv = b.take((int64_t)m->qkv_dim * m->H);
-        L.wo = b.take((int64_t)m->H * m->q_dim);
+        q->rm = b.take(dims[0].N * dims[0].K);
+        o->rm = b.take(dims[1].N * dims[1].K);
         L.ln2 = b.take(m->H);
-        L.wgu = b.take((int64_t)2 * m->inter_p * m->H);
-        L.wdown = b.take((int64_t)m->H * m->inter_p);
+        g->rm = b.take(dims[2].N * dims[2].K);
+        d->rm = b.take(dims[3].N * dims[3].K);
+        for (const ProjDim& p : dims) { ProjW& w = L.proj[p.stage]; w.r8 = nullptr; w.sc = w.km_sc = nullptr; }
         if (m->fp8) {   // fp8 tiles take half the bytes; every batch regime reads some of them, so they live in the main arena
-            L.wqkv_fm = b.take((int64_t)m->qkv_dim * m->H / 2);
-            L.wo_fm = b.take((int64_t)m->H * m->q_dim / 2);
-            L.wgu_fm = b.take((int64_t)2 * m->inter_p * m->H / 2);
-            L.wdown_fm = b.take((int64_t)m->H * m->inter_p / 2);
-            L.wqkv_km = b.take((int64_t)m->qkv_dim * m->H / 2);
-            L.wgu_km = b.take((int64_t)2 * m->inter_p * m->H / 2);
-        }
-        L.wqkv_km_sc = L.wgu_km_sc = nullptr;
-        L.wqkv_sc = L.wo_sc = L.wgu_sc = L.wdown_sc = nullptr;
-        L.wqkv_r8 = L.wo_r8 = L.wgu_r8 = L.wdown_r8 = nullptr;
-        if (m->fp8) {
-            L.wqkv_r8 = b.take((int64_t)m->qkv_dim * m->H / 2);
-            L.wo_r8 = b.take((int64_t)m->H * m->q_dim / 2);
-            L.wgu_r8 = b.take((int64_t)2 * m->inter_p * m->H / 2);
-            L.wdown_r8 = b.take((int64_t)m->H * m->inter_p / 2);
-            L.wqkv_sc = (float*)b.take(2 * (int64_t)m->qkv_dim);
-            L.wo_sc = (float*)b.take(2 * (int64_t)m->H);
-            L.wgu_sc = (float*)b.take(4 * (int64_t)m->inter_p);
-            L.wdown_sc = (float*)b.take(2 * (int64_t)m->H);
-            L.wqkv_km_sc = (float*)b.take(2 * (int64_t)m->qkv_dim);
-            L.wgu_km_sc = (float*)b.take(4 * (int64_t)m->inter_p);
+            for (const ProjDim& p : dims) L.proj[p.stage].fm = b.take(p.N * p.K / 2);
+            q->km = b.take(dims[0].N * dims[0].K / 2);
+            g->km = b.take(dims[2].N * dims[2].K / 2);
+            for (const ProjDim& p : dims) L.proj[p.stage].r8 = b.take(p.N * p.K / 2);
+            for (const ProjDim& p : dims) L.proj[p.stage].sc = (float*)b.take(2 * p.N);
+            q->km_sc = (float*)b.take(2 * dims[0].N);
+            g->km_sc = (float*)b.take(2 * dims[2].N);
+            o->km = o->fm; o->km_sc = o->sc;
+            d->km = d->fm; d->km_sc = d->sc;
         }
     }
     m->final_norm = b.take(m->H);
-    m->lm_head = b.take((int64_t)m->vocab_p * m->H);
+    ProjW& lm = m->lm_head_w;
+    lm.rm = b.take((int64_t)m->vocab_p * m->H);
     if (m->fp8) {
-        m->lm_head_fm = b.take((int64_t)m->vocab_p * m->H / 2);
-        m->lm_head_sc = (float*)b.take(2 * (int64_t)m->vocab_p);
-        m->lm_head_r8 = b.take((int64_t)m->vocab_p * m->H / 2);
+        lm.km = lm.fm = b.take((int64_t)m->vocab_p * m->H / 2);
+        lm.km_sc = lm.sc = (float*)b.take(2 * (int64_t)m->vocab_p);
+        lm.r8 = b.take((int64_t)m->vocab_p * m->H / 2);
     }
 }
 
@@ -286,14 +206,16 @@ static void plan_arena(emmax_model* m, Bump& b) {
 // partner of decode_km.hip and is built only when the tuning switch km is 0 at build time (+9 GB).
 static void plan_aux(emmax_model* m, Bump& b, bool with_ab_partner) {
     for (auto& L : m->layers) {
-        L.wqkv_km = b.take((int64_t)m->qkv_dim * m->H);
-        L.wgu_km = b.take((int64_t)2 * m->inter_p * m->H);
-        L.wo_fm = b.take((int64_t)m->H * m->q_dim);
-        L.wdown_fm = b.take((int64_t)m->H * m->inter_p);
-        L.wqkv_fm = with_ab_partner ? b.take((int64_t)m->qkv_dim * m->H) : nullptr;
-        L.wgu_fm = with_ab_partner ? b.take((int64_t)2 * m->inter_p * m->H) : nullptr;
+        const auto dims = layer_projs(m);   // [0..3]: qkv, o-proj, gate-up, down
+        ProjW *const q = &L.proj[STAGE_QKV], *const o = &L.proj[STAGE_OPROJ], *const g = &L.proj[STAGE_GATEUP], *const d = &L.proj[STAGE_DOWN];
+        q->km = b.take(dims[0].N * dims[0].K);
+        g->km = b.take(dims[2].N * dims[2].K);
+        o->km = o->fm = b.take(dims[1].N * dims[1].K);
+        d->km = d->fm = b.take(dims[3].N * dims[3].K);
+        q->fm = with_ab_partner ? b.take(dims[0].N * dims[0].K) : nullptr;
+        g->fm = with_ab_partner ? b.take(dims[2].N * dims[2].K) : nullptr;
     }
-    m->lm_head_fm = b.take((int64_t)m->vocab_p * m->H);
+    m->lm_head_w.km = m->lm_head_w.fm = b.take((int64_t)m->vocab_p * m->H);
 }
 
 // copy a bound [rows, cols] bf16 matrix into dst (row pitch dst_ld elements) starting at dst row `row0`
@@ -310,1186 +232,6 @@ static int put2d(emmax_model* m, const std::string& key, int rows, int cols, bf1
     return 0;
 }
 static int put1d(emmax_model* m, const std::string& key, int n, bf16* dst, hipStream_t st) { return put2d(m, key, 1, n, dst, n, 0, st); }
-
-// ---------------------------------------------------------------------------------------------------------------------
-// session
-// ---------------------------------------------------------------------------------------------------------------------
-struct emmax_session {
-    emmax_model* m;
-    int max_batch, max_prompt, max_ctx, max_pages, max_rows /* packed prefill rows */, max_out;
-    // STAGING rows (overlapped admission, emmax_slots_prefill_staged): every per-row array and the paged KV region hold
-    // rows_total = max_batch + n_stg rows; rows stg0 .. are never part of a decode batch -- a request is prefilled into them on a
-    // second stream while the live rows keep decoding, and emmax_slots_commit moves it into its slot between two decode steps
-    // (state copied, page-table rows swapped: no K/V moves)
-    int rows_total, stg0, n_stg;
-    // vision scratch
-    bf16 *vA, *vpe, *vtok, *vln, *vqkv, *vatt, *vmlp, *feats, *pj1, *pj2, *patch_embeds;
-    float* vstats;              // LayerNorm (mean, rstd) of every token row, f32 [rows][2]
-    int32_t* cu_vit[2];
-    // a SECOND set of tower scratch for up to vis2_B frames (round 5): the two towers do not depend on each other, and at small batches each
-    // is a chain of under-filled, launch-latency-bound kernels (one frame: ~360 launches of ~14 us) -- tower 1 runs on the session's vision
-    // stream beside tower 0 (run_vision; tuning switch vis_streams)
-    bf16 *v2A, *v2pe, *v2tok, *v2ln, *v2qkv, *v2att, *v2mlp;
-    float *v2stats, *v2splitk_ws;
-    int64_t v2splitk_bytes;
-    int vis2_B = 0;
-    hipStream_t vis_stream = nullptr;
-    hipEvent_t ev_vfork = nullptr, ev_vjoin = nullptr;
-    // prefill scratch
-    bf16 *ph, *pxn, *pqkv, *patt, *pact;
-    float* ph32;                // the prefill's residual stream in fp32 (tuning switch resid32 = 1), [max_rows][H]
-    bool p32 = false;           // the last prefill ran on ph32 (what emmax_prefill_logits normalises)
-    int32_t* cu;
-    // decode
-    bf16 *dh, *dq, *datt, *dact;
-    float* dh32;                // the decode step's residual stream in fp32 (tuning switch resid32; GemvParams::h32), [rows_total][H]
-    float *part, *part_val, *part_val2 /* lm-head argmax partials of a staged prefill */;
-    // SAMPLING (emmax_session_set_sampling; the sampled finish, sample.hip): per-row parameters of every row, staging rows included; the
-    // fp32 logit rows of every row an lm-head can emit into (a staged prefill's rows are its own: it runs beside the live step); the
-    // log-probability rows beside out_ids.  sampling = false: none of it is touched and a step launches what a greedy session launches
-    float* logits;              // f32 [rows_total][vocab]
-    float *samp_t, *samp_p, *logprob /* [rows_total][max_out] */;
-    int32_t* samp_k;
-    uint64_t* samp_seed;
-    uint32_t* samp_sub;
-    bool sampling = false;
-    // LOGITS PROCESSING (emmax_session_set_processing; the processing finish, sample.hip): per-row repetition penalty, n-gram size and
-    // min-new-tokens of every row, staging rows included, and each row's prompt ids (every prefill fills them while processing is on).
-    // SCORES (emmax_session_set_scores): device words {scores, logits, max_new, rows} the processing finish stores through.  Either on: the
-    // step runs on the logit rows and ends in the processing finish.  Both off: none of it is touched
-    float* proc_pen;
-    int32_t *proc_ng, *proc_mn, *hist /* [rows_total][max_prompt] */, *hist_len;
-    uint64_t* score_words;
-    bool processing = false, scores_on = false;
-    int scores_rows = 0;   // rows of the bound score buffers: the batch of the first prefill after the binding (0: none yet)
-    // BEAM SEARCH (emmax_session_set_beams; beam.hip): K = beam_K beams per group, 0 = off.  Rows g K + k are the running beams of group g;
-    // the per-row candidate lists of a step, HF's running / finished state, the groups' words, the page bookkeeping (spare page and copy
-    // list per row), the trace [max_out][max_batch] and the resolved result.  Beams off: none of it is touched
-    int beam_K = 0, beam_G = 0, beam_es = 0, beam_lp_pos = 0, beam_eos = -1, beam_max_new = 0;
-    bool beam_forked = false, beam_ready = false, scores_has_scores = false;
-    float *bm_cand_acc, *bm_row_lse, *bm_run, *bm_fin_score, *bm_pw, *bm_tr_score, *bm_tr_lse, *bm_tc_acc, *bm_res_score;
-    int32_t *bm_cand_tok, *bm_fin_flag, *bm_fin_t, *bm_fin_par, *bm_fin_tok, *bm_grp, *bm_spare, *bm_csrc, *bm_cdst, *bm_cntok, *bm_tr_tok, *bm_tr_par,
-        *bm_tc_idx, *bm_res_bidx, *bm_res_len;
-    int32_t *part_idx2;
-    int32_t *part_idx, *cur_tok, *ctx_len, *done, *n_out, *out_ids, *max_new_d /* [max_batch] */, *page_table;
-    // EXACT NUMERICS (round 6; tuning switch `exact` at emmax_session_create): fp32 activations end to end.  x32a: the fp32 result of the GEMM
-    // in flight (qkv rows, SwiGLU product, fc1 output ...); xhla / xhlb: the two-term bf16 ("HL") A operands, ping-pong; xtok32: the ViT's fp32
-    // token rows; xfeats32 / xpe32: fp32 tower features / projected patch embeddings; dq32 / dact32: the decode step's fp32 q rows and SwiGLU
-    // product.  The paged KV region holds fp32 rows (twice the bytes of the bf16 cache).
-    bool exact = false;
-    int kv_fmt = 0;             // KV_BF16 / KV_FP8 / KV_F32 / KV_X24 (kv_format_now() at emmax_session_create)
-    long long kv24 = 0;         // KV_X24: elements of one operand's plane of a layer (GemvParams::kv24), else 0
-    float *x32a = nullptr, *xtok32 = nullptr, *xfeats32 = nullptr, *xpe32 = nullptr, *dq32 = nullptr, *dact32 = nullptr;
-    bf16 *xhla = nullptr, *xhlb = nullptr;
-    float* splitk_ws;           // fp32 partial tiles of split-K GEMMs (gemm.hip)
-    int64_t splitk_bytes;
-    unsigned long long* sk_ws = nullptr;     // device: stream-K granules of the MFMA decode projections (decode_mfma.hip), all zero between launches
-    unsigned long long* sk_ws2 = nullptr;    // ... of a STAGED prefill's lm-head: it runs on a second stream beside the live decode steps, and the
-                                             // granules are indexed by block id only -- two concurrent launches on one workspace would consume or
-                                             // clear each other's partial sums
-    int32_t *stop_ids /* [EMMAX_MAX_STOP_IDS] */, *stop_cfg /* {n_trigger, n_after} */, *stop_m, *stop_after;
-    bool slots_open = false;    // slot serving mode: rows are independent request slots (emmax_slots_open)
-    float *cos_t, *sin_t;
-    int n_lm_blocks;
-    // kv
-    bf16* kv;
-    int64_t kv_layer_stride;   // BYTES between layers.  bf16 cache: K at +0, V at +stride/2.  fp8 cache (kv8): K bytes, V bytes, K scales, V scales
-    bool kv8 = false;          // the cache holds e4m3 rows + one fp32 scale per (token, kv head) row (tuning switch kv_fp8 at emmax_session_create)
-    bf16* kv_stage = nullptr;  // kv8: the step's new K / V rows, bf16 [rows_total][Hkv][2][head_dim] (qkv launch -> attention launch)
-    // host state
-    int cur_B = 0, total_rows = 0, max_seqlen = 0, vision_B = 0;
-    int dec_steps = 0;          // decode steps issued since the last full prefill (upper bound of every row's context growth)
-    bool prefilled = false;
-    std::vector<int> S;         // per-row prefill lengths
-    int32_t* pinned = nullptr;  // small pinned host buffer for control uploads / done read-backs
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
-    hipStream_t graph_stream_cap = nullptr;  // stream the graphs were captured on
-    int graph_B = 0;
-    hipStream_t graph_stream = nullptr;
-    int graph_failed = 0;
-    int last_step_graph = 0;   // the most recent decode step was a graph replay (what emmax_session_graph_active reports)
-    hipEvent_t ev = nullptr;
-    int graph_epoch = -1;      // emmax_tune().epoch the graph was captured under (a changed switch re-captures)
-    int graph_mode = 0;   // finish_mode() the step was captured under (the parameters and score buffers are device words: a change re-captures nothing)
-    hipStream_t own_stream = nullptr;   // used by emmax_generate when the caller's stream is the (uncapturable) legacy stream
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
-    std::string graph_err;
-};
-
-struct SBump {
-    char* base;
-    int64_t off = 0;
-    void* take(int64_t bytes) {
-        off = (off + 255) / 256 * 256;
-        void* p = base ? (void*)(base + off) : nullptr;
-        off += bytes;
-        return p;
-    }
-};
-
-static void plan_session(emmax_session* s, SBump& b) {
-    emmax_model* m = s->m;
-    const int Bv = s->max_batch;
-    int maxN = 0, maxDp = 0, maxD3p = 0, maxMp = 0, maxK = 0;
-    for (int t = 0; t < 2; ++t) {
-        const TowerW& T = m->tw[t];
-        maxN = std::max(maxN, T.N); maxDp = std::max(maxDp, T.Dp); maxD3p = std::max(maxD3p, T.D3p);
-        maxMp = std::max(maxMp, T.Mp); maxK = std::max(maxK, T.Kpe);
-    }
-    const int np = m->tw[0].n_patches;
-    const int64_t vr = (int64_t)Bv * maxN;
-    s->vA = (bf16*)b.take((int64_t)Bv * np * maxK * 2);
-    s->vpe = (bf16*)b.take((int64_t)Bv * np * maxDp * 2);
-    s->vtok = (bf16*)b.take(vr * maxDp * 2);
-    s->vln = (bf16*)b.take(vr * maxDp * 2);
-    s->vstats = (float*)b.take(vr * 2 * 4);
-    s->vqkv = (bf16*)b.take(vr * maxD3p * 2);
-    s->vatt = (bf16*)b.take(vr * maxDp * 2);
-    s->vmlp = (bf16*)b.take(vr * maxMp * 2);
-    s->feats = (bf16*)b.take((int64_t)Bv * np * m->Vp * 2);
-    s->pj1 = (bf16*)b.take((int64_t)Bv * np * m->P1p * 2);
-    s->pj2 = (bf16*)b.take((int64_t)Bv * np * m->H * 2);
-    s->patch_embeds = (bf16*)b.take((int64_t)Bv * np * m->H * 2);
-    for (int t = 0; t < 2; ++t) s->cu_vit[t] = (int32_t*)b.take((Bv + 1) * 4);
-    {   // tower 1's own scratch for the two-stream form (sized for tower 1 alone, up to 256 frames: ~5 MB per frame)
-        const TowerW& T1 = m->tw[1];
-        s->vis2_B = std::min(Bv, 256);
-        const int64_t B2 = s->vis2_B, r2 = B2 * T1.N;
-        s->v2A = (bf16*)b.take(B2 * np * T1.Kpe * 2);
-        s->v2pe = (bf16*)b.take(B2 * np * T1.Dp * 2);
-        s->v2tok = (bf16*)b.take(r2 * T1.Dp * 2);
-        s->v2ln = (bf16*)b.take(r2 * T1.Dp * 2);
-        s->v2stats = (float*)b.take(r2 * 2 * 4);
-        s->v2qkv = (bf16*)b.take(r2 * T1.D3p * 2);
-        s->v2att = (bf16*)b.take(r2 * T1.Dp * 2);
-        s->v2mlp = (bf16*)b.take(r2 * T1.Mp * 2);
-        s->v2splitk_bytes = (int64_t)64 << 20;   // the same budget as the session's split-K scratch: the same plans, bit-identical towers
-        s->v2splitk_ws = (float*)b.take(s->v2splitk_bytes);
-    }
-    const int64_t R = s->max_rows;
-    s->ph = (bf16*)b.take(R * m->H * 2);
-    s->ph32 = (float*)b.take(R * m->H * 4);
-    s->pxn = (bf16*)b.take(R * m->H * 2);
-    s->pqkv = (bf16*)b.take(R * m->qkv_dim * 2);
-    s->patt = (bf16*)b.take(R * m->q_dim * 2);
-    s->pact = (bf16*)b.take(R * m->inter_p * 2);
-    s->cu = (int32_t*)b.take((s->max_batch + 1) * 4);
-    const int Bd = s->max_batch, Br = s->rows_total;   // decode batch rows / all rows incl. the staging rows
-    s->dh = (bf16*)b.take((int64_t)Br * m->H * 2);
-    s->dh32 = (float*)b.take((int64_t)Br * m->H * 4);
-    s->kv_stage = (bf16*)b.take((int64_t)Br * 2 * m->kv_dim * 2);
-    s->dq = (bf16*)b.take((int64_t)Bd * m->q_dim * 2);
-    s->datt = (bf16*)b.take((int64_t)Bd * m->q_dim * 2);
-    s->dact = (bf16*)b.take((int64_t)Bd * m->inter_p * 2);
-    s->part = (float*)b.take((int64_t)Bd * m->cfg.n_heads * 16 * 132 * 4);
-    s->n_lm_blocks = 512;   // persistent lm-head grid: one argmax partial per block
-    s->part_val = (float*)b.take((int64_t)s->n_lm_blocks * Bd * 4);
-    s->part_idx = (int32_t*)b.take((int64_t)s->n_lm_blocks * Bd * 4);
-    s->part_val2 = (float*)b.take((int64_t)s->n_lm_blocks * Bd * 4);
-    s->part_idx2 = (int32_t*)b.take((int64_t)s->n_lm_blocks * Bd * 4);
-    s->logits = (float*)b.take((int64_t)Br * m->vocab * 4);
-    s->samp_t = (float*)b.take(Br * 4);
-    s->samp_p = (float*)b.take(Br * 4);
-    s->samp_k = (int32_t*)b.take(Br * 4);
-    s->samp_seed = (uint64_t*)b.take(Br * 8);
-    s->samp_sub = (uint32_t*)b.take(Br * 4);
-    s->logprob = (float*)b.take((int64_t)Br * s->max_out * 4);
-    s->proc_pen = (float*)b.take(Br * 4);
-    s->proc_ng = (int32_t*)b.take(Br * 4);
-    s->proc_mn = (int32_t*)b.take(Br * 4);
-    s->hist = (int32_t*)b.take((int64_t)Br * s->max_prompt * 4);
-    s->hist_len = (int32_t*)b.take(Br * 4);
-    s->score_words = (uint64_t*)b.take(4 * 8);
-    s->cur_tok = (int32_t*)b.take(Br * 4);
-    s->ctx_len = (int32_t*)b.take(Br * 4);
-    s->done = (int32_t*)b.take(Br * 4);
-    s->n_out = (int32_t*)b.take(Br * 4);
-    s->out_ids = (int32_t*)b.take((int64_t)Br * s->max_out * 4);
-    s->max_new_d = (int32_t*)b.take(Br * 4);
-    s->stop_ids = (int32_t*)b.take(EMMAX_MAX_STOP_IDS * 4);
-    s->stop_cfg = (int32_t*)b.take(2 * 4);
-    s->stop_m = (int32_t*)b.take(Br * 4);
-    s->stop_after = (int32_t*)b.take(Br * 4);
-    s->page_table = (int32_t*)b.take((int64_t)Br * s->max_pages * 4);
-    s->sk_ws = (unsigned long long*)b.take((int64_t)256 * 2 * 256 * 8);
-    s->sk_ws2 = (unsigned long long*)b.take((int64_t)256 * 2 * 256 * 8);
-    s->splitk_bytes = (int64_t)64 << 20;   // e.g. 4 slices of a 768 x 4096 prefill GEMM = 50 MB; smaller budgets just split less
-    s->splitk_ws = (float*)b.take(s->splitk_bytes);
-    s->cos_t = (float*)b.take((int64_t)s->max_ctx * (m->cfg.head_dim / 2) * 4);
-    s->sin_t = (float*)b.take((int64_t)s->max_ctx * (m->cfg.head_dim / 2) * 4);
-    {   // beam search: rows are decode rows only (no beams on staging rows)
-        const int64_t Rb = std::min(Bd, EMMAX_MAX_DECODE_BATCH), T = s->max_out;
-        s->bm_cand_acc = (float*)b.take(Rb * 2 * EMMAX_MAX_BEAMS * 4);
-        s->bm_cand_tok = (int32_t*)b.take(Rb * 2 * EMMAX_MAX_BEAMS * 4);
-        s->bm_row_lse = (float*)b.take(Rb * 4);
-        s->bm_run = (float*)b.take(Rb * 4);
-        s->bm_fin_score = (float*)b.take(Rb * 4);
-        s->bm_fin_flag = (int32_t*)b.take(Rb * 4);
-        s->bm_fin_t = (int32_t*)b.take(Rb * 4);
-        s->bm_fin_par = (int32_t*)b.take(Rb * 4);
-        s->bm_fin_tok = (int32_t*)b.take(Rb * 4);
-        s->bm_grp = (int32_t*)b.take(Rb * 4 * 4);
-        s->bm_spare = (int32_t*)b.take(Rb * 4);
-        s->bm_csrc = (int32_t*)b.take(Rb * 4);
-        s->bm_cdst = (int32_t*)b.take(Rb * 4);
-        s->bm_cntok = (int32_t*)b.take(Rb * 4);
-        s->bm_pw = (float*)b.take((T + 1) * 4);
-        s->bm_tr_tok = (int32_t*)b.take(T * Rb * 4);
-        s->bm_tr_par = (int32_t*)b.take(T * Rb * 4);
-        s->bm_tr_score = (float*)b.take(T * Rb * 4);
-        s->bm_tr_lse = (float*)b.take(T * Rb * 4);
-        s->bm_tc_idx = (int32_t*)b.take(T * Rb * 2 * 4);
-        s->bm_tc_acc = (float*)b.take(T * Rb * 2 * 4);
-        s->bm_res_bidx = (int32_t*)b.take(T * Rb * 4);
-        s->bm_res_len = (int32_t*)b.take(Rb * 4);
-        s->bm_res_score = (float*)b.take(Rb * 4);
-    }
-    if (s->exact) {
-        const int64_t npr = (int64_t)Bv * np;
-        auto mx = [](int64_t a, int64_t b2) { return a > b2 ? a : b2; };
-        const int64_t n32 = mx(mx(vr * mx(maxD3p, maxMp), npr * mx(mx(m->P1p, m->H), maxDp)), R * mx(m->qkv_dim, m->inter_p));
-        const int64_t nhla = mx(mx(npr * maxK, vr * maxDp), mx(npr * mx(m->Vp, m->H), R * m->H));
-        const int64_t nhlb = mx(mx(vr * mx(maxDp, maxMp), npr * m->P1p), R * mx(m->q_dim, m->inter_p));
-        s->x32a = (float*)b.take(n32 * 4);
-        s->xhla = (bf16*)b.take(nhla * 4);   // two bf16 terms per element
-        s->xhlb = (bf16*)b.take(nhlb * 4);
-        s->xtok32 = (float*)b.take(vr * maxDp * 4);
-        s->xfeats32 = (float*)b.take(npr * m->Vp * 4);
-        s->xpe32 = (float*)b.take(npr * m->H * 4);
-        s->dq32 = (float*)b.take((int64_t)Bd * m->q_dim * 4);
-        s->dact32 = (float*)b.take((int64_t)Bd * m->inter_p * 4);
-    }
-}
-
-// paged KV region: per layer K and V, rows x pages x kv heads x 64 tokens x head_dim elements -- bf16, or (kv8) e4m3 bytes + a 4-byte scale per row
-static int64_t kv_rows_per_layer(const emmax_model* m, int rows, int max_pages) { return (int64_t)rows * max_pages * m->cfg.n_kv_heads * PAGE; }
-// format of the paged cache: bf16 rows; e4m3 rows + a scale (kv_fp8); exact numerics: 24-bit rows (exact = 1: a bf16 plane + an 8-bit extension plane per
-// operand = the top 24 bits of the fp32 value, 2^-16 relative, 1.5 x the bf16 bytes) or fp32 rows (exact = 2: 2 x the bytes -- the A/B partner)
-enum { KV_BF16 = 0, KV_FP8 = 1, KV_F32 = 2, KV_X24 = 3 };
-static int kv_format_now() { return emmax_tune().exact >= 2 ? KV_F32 : emmax_tune().exact == 1 ? KV_X24 : (emmax_tune().kv_fp8 ? KV_FP8 : KV_BF16); }
-static int kv_elem_bytes(const emmax_model* m, int fmt) { return fmt == KV_F32 ? 4 : fmt == KV_X24 ? 3 : fmt == KV_FP8 ? 1 : 2; }
-static int64_t kv_layer_bytes(const emmax_model* m, int rows, int max_pages, int fmt) {
-    return 2 * kv_rows_per_layer(m, rows, max_pages) * (m->cfg.head_dim * kv_elem_bytes(m, fmt) + (fmt == KV_FP8 ? 4 : 0));
-}
-static int64_t kv_bytes_for(const emmax_model* m, int max_batch, int max_pages, int fmt) {
-    return (int64_t)m->cfg.n_layers * kv_layer_bytes(m, max_batch, max_pages, fmt);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// stages
-// ---------------------------------------------------------------------------------------------------------------------
-static GemmParams gp(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K) {
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.N_store = N;
-    return p;
-}
-
-// GEMM parameters of a session stage: as gp(), plus the session's split-K scratch
-static GemmParams gps(emmax_session* s, const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K) {
-    GemmParams p = gp(A, lda, W, ldw, C, ldc, M, N, K);
-    p.ws = s->splitk_ws;
-    p.ws_bytes = s->splitk_bytes;
-    return p;
-}
-
-// one tower's scratch (run_vision): set 0 = the session's shared buffers (either tower, any batch), set 1 = tower 1's own (two-stream form)
-struct VisScratch {
-    bf16 *vA, *vpe, *vtok, *vln, *vqkv, *vatt, *vmlp;
-    float *vstats, *ws;
-    int64_t ws_bytes;
-};
-
-// blocks [i0, i1) of tower t; i0 == 0: the patch embedding in front of them, i1 == n_blocks: the feature copy behind them
-static int run_tower(emmax_session* s, int t, const VisScratch& v, bool from_u8, const void* src, int B, int col_off, hipStream_t st, int i0 = 0,
-                     int i1 = 1 << 30) {
-    emmax_model* m = s->m;
-    const int np = m->tw[0].n_patches;
-    auto gpv = [&](const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K) {
-        GemmParams p = gp(A, lda, W, ldw, C, ldc, M, N, K);
-        p.ws = v.ws;
-        p.ws_bytes = v.ws_bytes;
-        return p;
-    };
-    {
-        const TowerW& T = m->tw[t];
-        const emmax_tower_config& tc = m->cfg.tower[t];
-        GemmParams g;
-        i1 = std::min(i1, T.n_blocks);
-        if (i0 == 0) {
-            KCHK(launch_patch_gather(from_u8, src, v.vA, B, tc.image_size, tc.patch, T.Kpe, 3 * t, tc.mean, tc.std, st));
-            g = gpv(v.vA, T.Kpe, T.patch_w, T.Kpe, v.vpe, T.Dp, B * np, T.Dp, T.Kpe);
-            g.bias = T.patch_b;
-            KCHK(launch_gemm(g, st));
-            KCHK(launch_assemble_tokens(v.vpe, T.pos, T.cls, T.reg, v.vtok, B, np, T.n_prefix, tc.has_cls, T.D, T.Dp, st));
-        }
-        const int rows = B * T.N;
-        for (int i = i0; i < i1; ++i) {
-            const BlockW& k = T.blk[i];
-            // LayerNorm folded into the projection: only the row statistics are computed here, the GEMM reads the raw rows and
-            // its epilogue finishes the algebra (kernels.h) -- no normalised copy of the tokens is ever written or re-read
-            if (m->ln_folded) {
-                KCHK(launch_row_stats(v.vtok, v.vstats, rows, T.D, T.Dp, tc.ln_eps, st));
-                g = gpv(v.vtok, T.Dp, k.qkv_w, T.Dp, v.vqkv, T.D3p, rows, T.D3p, T.Dp);
-                g.ln_stats = v.vstats; g.ln_s = k.ln1_s; g.ln_c = k.ln1_c;
-            } else {
-                KCHK(launch_layernorm(v.vtok, v.vln, k.n1w, k.n1b, rows, T.D, T.Dp, T.Dp, tc.ln_eps, st));
-                g = gpv(v.vln, T.Dp, k.qkv_w, T.Dp, v.vqkv, T.D3p, rows, T.D3p, T.Dp);
-                g.bias = k.qkv_b;
-            }
-            KCHK(launch_gemm(g, st));
-            AttnParams a;
-            a.qkv = v.vqkv; a.out = v.vatt; a.cu_seqlens = s->cu_vit[t];
-            a.ld_qkv = T.D3p; a.q_off = 0; a.k_off = T.D; a.v_off = 2 * T.D; a.ld_out = T.Dp;
-            a.B = B; a.max_seqlen = T.N; a.Hq = tc.num_heads; a.Hkv = tc.num_heads;
-            a.scale = 1.0f / sqrtf((float)T.hd); a.causal = 0;
-            KCHK(launch_attention(a, T.hd, st));
-            g = gpv(v.vatt, T.Dp, k.proj_w, T.Dp, v.vtok, T.Dp, rows, T.Dp, T.Dp);
-            g.bias = k.proj_b; g.scale = tc.layerscale ? k.ls1 : nullptr; g.residual = v.vtok; g.ldr = T.Dp;
-            KCHK(launch_gemm(g, st));
-            if (m->ln_folded) {
-                KCHK(launch_row_stats(v.vtok, v.vstats, rows, T.D, T.Dp, tc.ln_eps, st));
-                g = gpv(v.vtok, T.Dp, k.fc1_w, T.Dp, v.vmlp, T.Mp, rows, T.Mp, T.Dp);
-                g.ln_stats = v.vstats; g.ln_s = k.ln2_s; g.ln_c = k.ln2_c;
-            } else {
-                KCHK(launch_layernorm(v.vtok, v.vln, k.n2w, k.n2b, rows, T.D, T.Dp, T.Dp, tc.ln_eps, st));
-                g = gpv(v.vln, T.Dp, k.fc1_w, T.Dp, v.vmlp, T.Mp, rows, T.Mp, T.Dp);
-                g.bias = k.fc1_b;
-            }
-            g.act = 1;
-            KCHK(launch_gemm(g, st));
-            g = gpv(v.vmlp, T.Mp, k.fc2_w, T.Mp, v.vtok, T.Dp, rows, T.Dp, T.Mp);
-            g.bias = k.fc2_b; g.scale = tc.layerscale ? k.ls2 : nullptr; g.residual = v.vtok; g.ldr = T.Dp;
-            KCHK(launch_gemm(g, st));
-        }
-        // drop prefix tokens, no final norm, concat along the feature axis (modeling_prismatic.py:120-123)
-        if (i1 == T.n_blocks) KCHK(launch_copy_rows(v.vtok, T.Dp, s->feats, B, T.N, T.n_prefix, np, T.D, m->Vp, col_off, st));
-    }
-    return 0;
-}
-
-// ---- exact numerics (tuning switch exact; exact.hip): the same stages on fp32 activations --------------------------------------------
-// C[M, N] f32 = A (HL rows, K real columns padded to Kp) . W^T: both bf16 terms of A through the bf16 MFMAs (GemmParams::a_hl)
-static GemmParams gpx(emmax_session* s, const void* A_hl, int Kp, const void* W, int ldw, float* C, int ldc, int M, int N) {
-    GemmParams p = gps(s, A_hl, 2 * Kp, W, ldw, C, ldc, M, N, 2 * Kp);
-    p.a_hl = 1;
-    p.out_f32 = 1;
-    return p;
-}
-
-static int run_tower_x(emmax_session* s, int t, bool from_u8, const void* src, int B, int col_off, hipStream_t st) {
-    emmax_model* m = s->m;
-    const TowerW& T = m->tw[t];
-    const emmax_tower_config& tc = m->cfg.tower[t];
-    const int np = m->tw[0].n_patches, rows = B * T.N;
-    KCHK(launch_x_patch_gather(from_u8, src, s->xhla, B, tc.image_size, tc.patch, T.Kpe, 3 * t, tc.mean, tc.std, st));
-    GemmParams g = gpx(s, s->xhla, T.Kpe, T.patch_w, T.Kpe, s->x32a, T.Dp, B * np, T.Dp);
-    g.bias = T.patch_b;
-    KCHK(launch_gemm(g, st));
-    KCHK(launch_x_assemble_tokens(s->x32a, T.pos, T.cls, T.reg, s->xtok32, B, np, T.n_prefix, tc.has_cls, T.D, T.Dp, st));
-    if (T.Dp != T.D) HIPCHK(hipMemsetAsync(s->xhlb, 0, (size_t)rows * 2 * T.Dp * 2, st));   // the attention writes the real columns only
-    auto into_tokens = [&](GemmParams& q, const void* bias, const void* ls) {   // tokens += LayerScale . (A W^T + bias), fp32 rows
-        q.C = s->xtok32; q.ldc = T.Dp; q.bias = bias; q.scale = tc.layerscale ? ls : nullptr;
-        q.residual = s->xtok32; q.res_f32 = 1; q.ldr = T.Dp;
-    };
-    for (int i = 0; i < T.n_blocks; ++i) {
-        const BlockW& k = T.blk[i];
-        KCHK(launch_x_layernorm(s->xtok32, s->xhla, k.n1w, k.n1b, rows, T.D, T.Dp, T.Dp, 2 * T.Dp, tc.ln_eps, st));
-        g = gpx(s, s->xhla, T.Dp, k.qkv_w, T.Dp, s->x32a, T.D3p, rows, T.D3p);
-        g.bias = k.qkv_b;
-        KCHK(launch_gemm(g, st));
-        AttnParams a;
-        a.qkv = s->x32a; a.out = s->xhlb; a.cu_seqlens = s->cu_vit[t];
-        a.ld_qkv = T.D3p; a.q_off = 0; a.k_off = T.D; a.v_off = 2 * T.D; a.ld_out = 2 * T.Dp;
-        a.B = B; a.max_seqlen = T.N; a.Hq = tc.num_heads; a.Hkv = tc.num_heads;
-        a.scale = 1.0f / sqrtf((float)T.hd); a.causal = 0;
-        KCHK(launch_x_attention(a, T.hd, st));
-        g = gpx(s, s->xhlb, T.Dp, k.proj_w, T.Dp, nullptr, 0, rows, T.Dp);
-        into_tokens(g, k.proj_b, k.ls1);
-        KCHK(launch_gemm(g, st));
-        KCHK(launch_x_layernorm(s->xtok32, s->xhla, k.n2w, k.n2b, rows, T.D, T.Dp, T.Dp, 2 * T.Dp, tc.ln_eps, st));
-        g = gpx(s, s->xhla, T.Dp, k.fc1_w, T.Dp, s->x32a, T.Mp, rows, T.Mp);
-        g.bias = k.fc1_b; g.act = 1;
-        KCHK(launch_gemm(g, st));
-        KCHK(launch_x_split_rows(s->x32a, s->xhlb, rows, T.Mp, T.Mp, T.Mp, 2 * T.Mp, st));
-        g = gpx(s, s->xhlb, T.Mp, k.fc2_w, T.Mp, nullptr, 0, rows, T.Dp);
-        into_tokens(g, k.fc2_b, k.ls2);
-        KCHK(launch_gemm(g, st));
-    }
-    // drop prefix tokens, no final norm, concat along the feature axis (modeling_prismatic.py:120-123): fp32 rows
-    for (int b = 0; b < B; ++b)
-        HIPCHK(hipMemcpy2DAsync(s->xfeats32 + (size_t)b * np * m->Vp + col_off, (size_t)m->Vp * 4, s->xtok32 + ((size_t)b * T.N + T.n_prefix) * T.Dp,
-                                (size_t)T.Dp * 4, (size_t)T.D * 4, np, hipMemcpyDeviceToDevice, st));
-    return 0;
-}
-
-static int run_vision_x(emmax_session* s, bool from_u8, const void* src, int B, void* out, hipStream_t st) {
-    emmax_model* m = s->m;
-    const int np = m->tw[0].n_patches, R = B * np;
-    if (m->ln_folded) return fail(EMMAX_ERR_STATE, "exact numerics: the model was finalized with folded LayerNorms (set exact = 1 before emmax_model_finalize)");
-    int col_off = 0;
-    for (int t = 0; t < 2; ++t) {
-        const int r = run_tower_x(s, t, from_u8, src, B, col_off, st);
-        if (r) return r;
-        col_off += m->tw[t].D;
-    }
-    KCHK(launch_x_split_rows(s->xfeats32, s->xhla, R, m->Vp, m->Vp, m->Vp, 2 * m->Vp, st));
-    GemmParams g = gpx(s, s->xhla, m->Vp, m->pj1_w, m->Vp, s->x32a, m->P1p, R, m->P1p);
-    g.bias = m->pj1_b; g.act = 1;
-    KCHK(launch_gemm(g, st));
-    KCHK(launch_x_split_rows(s->x32a, s->xhlb, R, m->P1p, m->P1p, m->P1p, 2 * m->P1p, st));
-    g = gpx(s, s->xhlb, m->P1p, m->pj2_w, m->P1p, s->x32a, m->H, R, m->H);
-    g.bias = m->pj2_b; g.act = 1;
-    KCHK(launch_gemm(g, st));
-    KCHK(launch_x_split_rows(s->x32a, s->xhla, R, m->H, m->H, m->H, 2 * m->H, st));
-    g = gpx(s, s->xhla, m->H, m->pj3_w, m->H, s->xpe32, m->H, R, m->H);
-    g.bias = m->pj3_b;
-    KCHK(launch_gemm(g, st));
-    // an exact session exchanges patch embeddings as FP32 rows [B, n_patches, hidden] (include/emmax.h): the caller's copy, if it wants one
-    if (out && out != (void*)s->xpe32) HIPCHK(hipMemcpyAsync(out, s->xpe32, (size_t)R * m->H * 4, hipMemcpyDeviceToDevice, st));
-    s->vision_B = B;
-    return 0;
-}
-
-static int run_vision(emmax_session* s, bool from_u8, const void* src, int B, void* out, hipStream_t st) {
-    emmax_model* m = s->m;
-    if (!m->finalized) return fail(EMMAX_ERR_STATE, "model not finalized");
-    if (B <= 0 || B > s->max_batch) return fail(EMMAX_ERR_INVALID, "vision batch %d outside 1..%d", B, s->max_batch);
-    if (s->exact) return run_vision_x(s, from_u8, src, B, out, st);
-    const int np = m->tw[0].n_patches;
-    const VisScratch v0 = {s->vA, s->vpe, s->vtok, s->vln, s->vqkv, s->vatt, s->vmlp, s->vstats, s->splitk_ws, s->splitk_bytes};
-    // Two streams (round 5; tuning switch vis_streams: 1 = on, the default; 0 = one stream): the towers share nothing but the frames and write
-    // disjoint columns of `feats`; at one frame each is a chain of ~180 under-filled, launch-latency-bound kernels, and side by side they take
-    // the time of the longer chain -- 5.01 -> 3.14 ms at one frame, 7.03 -> 5.36 at 8, 16.6 -> 13.9 at 32, 54.4 -> 52.5 at 128, 106.0 -> 104.8
-    // at 256 (one tower's tile tails and launch ramps under the other's kernels; profiles/r05_vision_two_streams.txt).  Identical results:
-    // same kernels, same plans (tower 1 has a split-K scratch of the session's size).
-    const int vsw = emmax_tune().vis_streams;
-    const bool two = s->vis_stream && B <= s->vis2_B && vsw != 0;
-    if (two) {
-        const VisScratch v1 = {s->v2A, s->v2pe, s->v2tok, s->v2ln, s->v2qkv, s->v2att, s->v2mlp, s->v2stats, s->v2splitk_ws, s->v2splitk_bytes};
-        HIPCHK(hipEventRecord(s->ev_vfork, st));
-        HIPCHK(hipStreamWaitEvent(s->vis_stream, s->ev_vfork, 0));
-        // the launches of the two chains ENQUEUED alternately, block by block: one host thread feeds both streams, and with tower 1's ~180
-        // launches enqueued first tower 0 started ~0.6 ms late at one frame
-        int r = 0;
-        const int nb = std::max(m->tw[0].n_blocks, m->tw[1].n_blocks);
-        for (int i = 0; i < nb && r == 0; ++i) {
-            if (i < m->tw[1].n_blocks) r = run_tower(s, 1, v1, from_u8, src, B, m->tw[0].D, s->vis_stream, i, i + 1);
-            if (r == 0 && i < m->tw[0].n_blocks) r = run_tower(s, 0, v0, from_u8, src, B, 0, st, i, i + 1);
-        }
-        // (joined even on an error: the caller's stream must not run ahead of work queued on ours)
-        HIPCHK(hipEventRecord(s->ev_vjoin, s->vis_stream));
-        HIPCHK(hipStreamWaitEvent(st, s->ev_vjoin, 0));
-        if (r) return r;
-    } else {
-        int col_off = 0;
-        for (int t = 0; t < 2; ++t) {
-            const int r = run_tower(s, t, v0, from_u8, src, B, col_off, st);
-            if (r) return r;
-            col_off += m->tw[t].D;
-        }
-    }
-    GemmParams g = gps(s, s->feats, m->Vp, m->pj1_w, m->Vp, s->pj1, m->P1p, B * np, m->P1p, m->Vp);
-    g.bias = m->pj1_b; g.act = 1;
-    KCHK(launch_gemm(g, st));
-    g = gps(s, s->pj1, m->P1p, m->pj2_w, m->P1p, s->pj2, m->H, B * np, m->H, m->P1p);
-    g.bias = m->pj2_b; g.act = 1;
-    KCHK(launch_gemm(g, st));
-    g = gps(s, s->pj2, m->H, m->pj3_w, m->H, s->patch_embeds, m->H, B * np, m->H, m->H);
-    g.bias = m->pj3_b;
-    KCHK(launch_gemm(g, st));
-    if (out && out != s->patch_embeds)
-        HIPCHK(hipMemcpyAsync(out, s->patch_embeds, (size_t)B * np * m->H * 2, hipMemcpyDeviceToDevice, st));
-    s->vision_B = B;
-    return 0;
-}
-
-// tuning switch streamk = 0 gives every MFMA decode block whole tasks (the split before stream-K)
-static bool streamk_on() { return emmax_tune().streamk != 0; }
-
-// tuning switch fp8_gemv = bit mask of the batch 1-2 fp8 projections that run as dot-product GEMV over the e4m3 row copy
-// (1 qkv, 2 o-proj, 4 gate/up, 8 down, 16 lm-head); the others go through the MFMA kernels like every larger batch.
-// Default (round 3, once the K-split MFMA kernels of decode_km.hip existed): the o-proj, and at batch 1 the lm-head.  Per launch
-// at B = 1 / B = 2, row GEMV against decode_km.hip (one box, tools/ab_bench.sh): qkv 14.1 / 17.3 against 12.5 / 12.7 us, gate/up
-// 17.9 / 20.3 against 17.1 / 17.1, down (always MFMA) 11.9, o-proj 7.7 / 9.8 against 8.4 / 10.7, lm-head 25.0 / 28.7 against
-// 25.7 / 24.4: step 1.939 -> 1.886 ms/token at B = 1 with everything on the MFMA kernels, 2.287 -> 2.028 at B = 2.
-enum { F8_QKV = 1, F8_OPROJ = 2, F8_GATEUP = 4, F8_DOWN = 8, F8_LMHEAD = 16 };
-static int fp8_gemv_mask(int B) {
-    const int mask = emmax_tune().fp8_gemv;
-    if (mask >= 0) return mask & 31;
-    return B == 1 ? (F8_OPROJ | F8_LMHEAD) : F8_OPROJ;
-}
-
-// B <= 2: per-lane dot-product GEMV over the row-major weights (fp8 mode: over the e4m3 row copy w_r8);
-// B >= 3: MFMA over the fragment-major copy
-// w_km / km_scale: the matrix in decode_km.hip's layout (null: that kernel does not serve this projection)
-static int launch_proj(int mode, GemvParams& p, const void* w_rm, const void* w_fm, int B, hipStream_t st, int* grid_out = nullptr,
-                       const float* w_scale = nullptr, const void* w_r8 = nullptr, int f8bit = 0, const void* w_km = nullptr,
-                       const float* km_scale = nullptr) {
-    if (p.exact) {   // exact numerics: the two-term forms or nothing -- decode_ks.hip at batch 1-2, decode_km.hip's EX kernels at batch 3-8
-        int r = -2;
-        if (!w_scale && B < EMMAX_MFMA_MIN_BATCH) {
-            p.W = w_rm;
-            r = launch_decode_ks(mode, p, B, st, grid_out);
-        } else if (!w_scale && w_km) {
-            GemvParams q = p;
-            q.W = w_km;
-            r = launch_decode_km(mode, q, B, st, grid_out);
-        }
-        return r == -2 ? fail(EMMAX_ERR_INVALID, "exact numerics: no two-term kernel for this projection (batch %d, K %d)", B, p.K) : r;
-    }
-    if (B < EMMAX_MFMA_MIN_BATCH && w_scale && w_r8 && (fp8_gemv_mask(B) & f8bit) && decode_gemv_fp8_fits(B, p.K)) {
-        p.W = w_r8;
-        p.wscale = w_scale;
-        p.ldw = p.K;   // bytes per row
-        return launch_decode_gemv(mode, p, B, st, grid_out);
-    }
-    if (B >= EMMAX_MFMA_MIN_BATCH || w_scale) {
-        // K-split MFMA kernel (decode_km.hip): batch >= 3, and with fp8 weights every batch the row GEMV above did not take
-        if ((B >= EMMAX_MFMA_MIN_BATCH || w_scale) && w_km && decode_km_enabled()) {
-            GemvParams q = p;
-            q.W = w_km;
-            q.wscale = w_scale ? km_scale : nullptr;
-            const int r = launch_decode_km(mode, q, B, st, grid_out);
-            if (r != -2) return r;
-        }
-        if (!w_fm) return fail(EMMAX_ERR_STATE, "decode_mfma.hip's copy of this matrix was not built (tuning switch km was 1 at emmax_model_build_aux)");
-        p.W = w_fm;
-        p.wscale = w_scale;
-        return launch_decode_mfma(mode, p, B, st, grid_out);
-    }
-    p.W = w_rm;
-    return launch_decode_gemv(mode, p, B, st, grid_out);
-}
-
-// the hidden rows of a decode step: the fp32 stream (tuning switch resid32, the default) or the bf16 rows of rounds 1-4
-// (resid32: 0 = bf16 rows everywhere, 1 = fp32 stream in the prefill and the decode step, 2 = in the decode step only)
-static float* h32_of(emmax_session* s, int slot0 = 0) { return emmax_tune().resid32 ? s->dh32 + (size_t)slot0 * s->m->H : nullptr; }
-
-// Decode batches of 9-16 rows exist on decode_km.hip only (decode_mfma.hip, the fallback for other shapes, stages eight rows): the
-// model's projections must be shapes that kernel takes -- K a multiple of 256 and <= 4096 for qkv / o-proj / gate-up / lm-head, at
-// most 8 tiles per block (N <= 32768), the down projection within four phases of 12 fragments per wave (K <= 12288).
-static int model_max_decode_batch(const emmax_model* m) {
-    const auto& c = m->cfg;
-    const bool k_ok = m->H % 256 == 0 && m->H <= 4096 && m->q_dim % 256 == 0 && m->q_dim <= 4096;
-    const bool n_ok = m->qkv_dim % 16 == 0 && m->qkv_dim <= 32768 && 2 * m->inter_p <= 32768 && m->vocab_p <= 32768 && m->H % 16 == 0 && c.head_dim % 16 == 0;
-    const int kd = m->fp8 ? 64 : 32;
-    const bool d_ok = m->inter_p % kd == 0 && m->inter_p / kd >= 8 && (m->inter_p / kd + 7) / 8 <= (m->fp8 ? 24 : 48) && m->inter_p > 4096;
-    if (!(k_ok && n_ok && d_ok && decode_km_enabled() && emmax_tune().km_down)) return 8;
-    // 17-32 rows: decode_kmp.hip -- the down projection within eleven phases of 128 elements per wave (K in whole load steps of 32
-    // elements, 64 with fp8 tiles; the widest wave share <= 1408 elements: K <= 11264), one tile per block there (H <= 4096)
-    const bool p_ok = ((m->inter_p / kd + 7) / 8) * kd <= 11 * 128 && m->H <= 4096 && m->H / 16 <= 256;
-    // batches of 9-32 rows exist in the ONE-split direct attention form only: with split partials (tuning switches attn_direct = 0 or a
-    // forced attn_nsplit > 1) the o-proj would carry p.attn_part, which the bf16 decode_km / decode_kmp kernels do not take
-    if (emmax_tune().attn_direct == 0 || decode_attn_nsplit(9, c.n_kv_heads) != 1) return 8;
-    return p_ok ? EMMAX_MAX_DECODE_BATCH : 16;
-}
-
-static int run_prefill_x(emmax_session* s, const int32_t* ids, int B, int P_max, const void* patches, int np, int total, int maxS, int r0, hipStream_t st);
-static char* kv_layer(emmax_session* s, int layer) { return (char*)s->kv + (size_t)layer * s->kv_layer_stride; }
-static int64_t kv_rows(emmax_session* s) { return kv_rows_per_layer(s->m, s->rows_total, s->max_pages); }
-static bf16* kcache_of(emmax_session* s, int layer) { return (bf16*)kv_layer(s, layer); }
-static bf16* vcache_of(emmax_session* s, int layer) {
-    return (bf16*)(kv_layer(s, layer) + kv_rows(s) * s->m->cfg.head_dim * kv_elem_bytes(s->m, s->kv_fmt));
-}
-static float* kscale_of(emmax_session* s, int layer) { return (float*)(kv_layer(s, layer) + 2 * kv_rows(s) * s->m->cfg.head_dim); }   // kv8 only
-static float* vscale_of(emmax_session* s, int layer) { return kscale_of(s, layer) + kv_rows(s); }
-
-static int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* logits_out, bool do_finish, hipStream_t st, int slot0 = 0);
-// how a step ends (the captured graph is keyed on it: the finish's parameters differ in each): bit 0 sampling, bit 1 processing, bit 2
-// scores.  0: the greedy finish (lm-head argmax partials); 1: the sampled finish; bit 1 or 2 set: the processing finish
-// beams on: bit 3, stop_on_eos in bit 4, K and the early-stopping mode above (the beam finish holds them by value)
-static int finish_mode(const emmax_session* s) {
-    return (s->sampling ? 1 : 0) | (s->processing ? 2 : 0) | (s->scores_on ? 4 : 0) |
-           (s->beam_K ? (8 | (s->beam_eos >= 0 ? 16 : 0) | (s->beam_K << 5) | (s->beam_es << 10) | (s->beam_lp_pos << 12)) : 0);
-}
-static int launch_beam_finish(emmax_session* s, bool is_prefill, hipStream_t st);
-static int launch_finish_step(emmax_session* s, int B, bool is_prefill, int n_part, int slot0, hipStream_t st);
-
-// the per-row state of rows slot0 .. slot0 + B that a finish updates
-static void finish_rows(emmax_session* s, int B, bool is_prefill, int slot0, FinishParams& f) {
-    emmax_model* m = s->m;
-    f.B = B;
-    f.cur_tok = s->cur_tok + slot0; f.ctx_len = s->ctx_len + slot0; f.done = s->done + slot0; f.n_out = s->n_out + slot0;
-    f.out_ids = s->out_ids + (size_t)slot0 * s->max_out;
-    f.max_new_p = s->max_new_d + slot0; f.max_out = s->max_out; f.max_ctx = s->max_ctx;
-    f.stop_ids = s->stop_ids; f.stop_cfg = s->stop_cfg; f.stop_m = s->stop_m + slot0; f.stop_after = s->stop_after + slot0;
-    f.eos_id = m->cfg.eos_id; f.pad_id = m->cfg.pad_id; f.is_prefill = is_prefill ? 1 : 0;
-}
-
-// finish of a step over rows slot0 .. slot0 + B: argmax over the n_part lm-head partials, EOS / budget / stop rule, next token
-static int launch_finish_step(emmax_session* s, int B, bool is_prefill, int n_part, int slot0, hipStream_t st) {
-    FinishParams f;
-    memset(&f, 0, sizeof(f));
-    // the partial count is the grid the launch really used (every launcher reports it): a count modelled separately went
-    // stale when a launcher capped its grid (fp8 row GEMV shapes 1/2, EMMAX_GEMV_GRID) and stale partials could win the argmax
-    if (n_part <= 0 || n_part > s->n_lm_blocks) return fail(EMMAX_ERR_STATE, "lm-head launch reported no partial count");
-    const bool stg = slot0 >= s->stg0;   // a staged prefill runs beside the live batch's decode steps: its own partial buffers
-    f.part_val = stg ? s->part_val2 : s->part_val; f.part_idx = stg ? s->part_idx2 : s->part_idx; f.n_part = n_part;
-    finish_rows(s, B, is_prefill, slot0, f);
-    KCHK(launch_decode_finish(f, st));
-    return 0;
-}
-
-// finish of a SAMPLED step over rows slot0 .. slot0 + B: each row's draw from its complete fp32 logit row (the lm-head launch just before
-// wrote them, on the same stream), then the same bookkeeping
-static int launch_sampled_finish_step(emmax_session* s, int B, bool is_prefill, int slot0, const float* logits, hipStream_t st) {
-    SampleFinishParams p;
-    memset(&p, 0, sizeof(p));
-    finish_rows(s, B, is_prefill, slot0, p.f);
-    p.logits = logits; p.ld = s->m->vocab; p.V = s->m->vocab;
-    p.temperature = s->samp_t + slot0; p.top_k = s->samp_k + slot0; p.top_p = s->samp_p + slot0;
-    p.seed = s->samp_seed + slot0; p.subseq = s->samp_sub + slot0;
-    p.logprob = s->logprob + (size_t)slot0 * s->max_out;
-    KCHK(launch_sample_finish(p, st));
-    return 0;
-}
-
-// finish of a step with logits processing or scores on: the processors, then the draw (sampling on) or the argmax, then the scores store
-static int launch_proc_finish_step(emmax_session* s, int B, bool is_prefill, int slot0, const float* logits, hipStream_t st) {
-    ProcFinishParams p;
-    memset(&p, 0, sizeof(p));
-    finish_rows(s, B, is_prefill, slot0, p.f);
-    p.logits = logits; p.ld = s->m->vocab; p.V = s->m->vocab;
-    if (s->sampling) {   // else temperature stays null: every row greedy
-        p.temperature = s->samp_t + slot0; p.top_k = s->samp_k + slot0; p.top_p = s->samp_p + slot0;
-        p.seed = s->samp_seed + slot0; p.subseq = s->samp_sub + slot0;
-    }
-    p.logprob = s->logprob + (size_t)slot0 * s->max_out;
-    p.row0 = slot0;
-    if (s->processing) {
-        p.penalty = s->proc_pen + slot0; p.ngram = s->proc_ng + slot0; p.min_new = s->proc_mn + slot0;
-        p.hist = s->hist + (size_t)slot0 * s->max_prompt; p.hist_len = s->hist_len + slot0; p.max_prompt = s->max_prompt;
-    }
-    if (s->scores_on) p.score_words = s->score_words;
-    KCHK(launch_proc_finish(p, st));
-    return 0;
-}
-
-// pages a group of K beams uses for a context of S tokens and max_new generated ones, against the K rows' share (include/emmax.h): the
-// prompt's pages, a private page per beam from the prompt's partial page on, one more per beam at every page boundary, K spares
-static bool beam_pages_fit(const emmax_session* s, int S, int max_new) {
-    const int K = s->beam_K, rem = S % PAGE;
-    long long need = (S + PAGE - 1) / PAGE + (rem > 0 ? K - 1 : K) + K;
-    for (int L = S + 1; L <= S + max_new - 1; ++L)
-        if (L % PAGE == 0) need += K;
-    return S + max_new <= s->max_ctx && need <= (long long)K * s->max_pages;
-}
-
-// the tail of a step with beams on (beam.hip): per-row candidates, the groups' merge + state + page-table gather, the partial-page copies.
-// is_prefill: the first beam step, from the prefill's one logit row per group, and the fork
-static int launch_beam_finish(emmax_session* s, bool is_prefill, hipStream_t st) {
-    emmax_model* m = s->m;
-    const int K = s->beam_K, G = s->beam_G, rows = G * K;
-    BeamRowParams r;
-    memset(&r, 0, sizeof(r));
-    r.logits = s->logits; r.ld = m->vocab; r.V = m->vocab; r.K = K; r.is_prefill = is_prefill ? 1 : 0;
-    r.run_score = s->bm_run; r.done = s->done; r.n_out = s->n_out;
-    r.cand_acc = s->bm_cand_acc; r.cand_tok = s->bm_cand_tok; r.row_lse = s->bm_row_lse;
-    r.score_words = s->scores_on ? s->score_words : nullptr;
-    KCHK(launch_beam_rows(r, is_prefill ? G : rows, st));
-    BeamMergeParams g;
-    memset(&g, 0, sizeof(g));
-    g.K = K; g.V = m->vocab; g.is_prefill = r.is_prefill; g.eos_id = s->beam_eos; g.pad_id = m->cfg.pad_id; g.max_pages = s->max_pages;
-    g.max_out = s->max_out; g.tr_ld = std::min(s->max_batch, EMMAX_MAX_DECODE_BATCH); g.es_mode = s->beam_es; g.lp_pos = s->beam_lp_pos;
-    g.pw = s->bm_pw; g.cand_acc = s->bm_cand_acc; g.cand_tok = s->bm_cand_tok; g.row_lse = s->bm_row_lse;
-    g.run_score = s->bm_run; g.fin_score = s->bm_fin_score; g.fin_flag = s->bm_fin_flag; g.fin_t = s->bm_fin_t; g.fin_par = s->bm_fin_par;
-    g.fin_tok = s->bm_fin_tok; g.grp_state = s->bm_grp;
-    g.cur_tok = s->cur_tok; g.ctx_len = s->ctx_len; g.done = s->done; g.n_out = s->n_out; g.max_new_p = s->max_new_d;
-    g.page_table = s->page_table; g.spare = s->bm_spare; g.copy_src = s->bm_csrc; g.copy_dst = s->bm_cdst; g.copy_ntok = s->bm_cntok;
-    g.tr_tok = s->bm_tr_tok; g.tr_par = s->bm_tr_par; g.tr_score = s->bm_tr_score; g.tr_lse = s->bm_tr_lse; g.tc_idx = s->bm_tc_idx;
-    g.tc_acc = s->bm_tc_acc;
-    if (is_prefill)
-        for (int i = 0; i < G; ++i) g.S[i] = s->S[i];
-    KCHK(launch_beam_merge(g, G, st));
-    BeamCopyParams c;
-    memset(&c, 0, sizeof(c));
-    const long long kvr = kv_rows(s), hd = m->cfg.head_dim;
-    c.kv = (char*)s->kv; c.layer_stride = s->kv_layer_stride; c.Hkv = m->cfg.n_kv_heads; c.n_pages = s->rows_total * s->max_pages;
-    c.copy_src = s->bm_csrc; c.copy_dst = s->bm_cdst; c.copy_ntok = s->bm_cntok;
-    auto plane = [&](long long off, int rb) { c.plane_off[c.n_planes] = off; c.plane_rb[c.n_planes] = rb; c.n_planes += 1; };
-    switch (s->kv_fmt) {
-    case KV_FP8:   // K bytes, V bytes, K scales, V scales
-        plane(0, (int)hd); plane(kvr * hd, (int)hd); plane(2 * kvr * hd, 4); plane(2 * kvr * hd + kvr * 4, 4);
-        break;
-    case KV_X24:   // per operand a bf16 plane and its 8-bit extension plane
-        plane(0, (int)hd * 2); plane(kvr * hd * 2, (int)hd); plane(kvr * hd * 3, (int)hd * 2); plane(kvr * hd * 5, (int)hd);
-        break;
-    case KV_F32:
-        plane(0, (int)hd * 4); plane(kvr * hd * 4, (int)hd * 4);
-        break;
-    default:
-        plane(0, (int)hd * 2); plane(kvr * hd * 2, (int)hd * 2);
-    }
-    KCHK(launch_beam_copy(c, rows, m->cfg.n_layers, st));
-    return 0;
-}
-
-static void lmhead_params(emmax_session* s, int slot0, float* logits_out, GemvParams& p);
-// slot0: first row of the B rows this call covers (slot prefill: one row in the middle of a live batch)
-static int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* logits_out, bool do_finish, hipStream_t st, int slot0) {
-    emmax_model* m = s->m;
-    if (do_finish && s->beam_K) {   // beams on: every chunk's lm-head writes its logit rows, then ONE beam finish over all rows (a prefill's
-                                    // rows wait for emmax_generate, which knows the token budget the first beam step needs)
-        if (is_prefill && s->exact) {   // exact numerics: a group's first row must not depend on how many groups were prefilled with it, and
-                                        // lm-heads of 1-2 and of 3-8 rows are different kernels -- one row per launch
-            for (int b = 0; b < B; ++b) {
-                const int r = run_lm_head_step(s, 1, true, s->logits + (size_t)(slot0 + b) * m->vocab, false, st, slot0 + b);
-                if (r) return r;
-            }
-            return 0;
-        }
-        const int r = run_lm_head_step(s, B, is_prefill, s->logits + (size_t)slot0 * m->vocab, false, st, slot0);
-        if (r || is_prefill) return r;
-        return launch_beam_finish(s, false, st);
-    }
-    const int chunk = s->exact ? 8 : EMMAX_KMP_ROWS;   // (exact numerics: the two-term MFMA kernels hold 8 rows)
-    if (B > chunk) {   // 33-64 rows: launches of <= 32 rows (each with its own finish: the argmax partials are laid out per launch)
-        int r = run_lm_head_step(s, chunk, is_prefill, logits_out, do_finish, st, slot0);
-        if (r) return r;
-        return run_lm_head_step(s, B - chunk, is_prefill, logits_out ? logits_out + (size_t)chunk * m->vocab : nullptr, do_finish, st, slot0 + chunk);
-    }
-    // sampling, processing or scores on: a step's lm-head also writes the fp32 logit rows of its B rows, and the sampled or processing finish
-    // reads them
-    const int mode = do_finish ? finish_mode(s) : 0;
-    const bool sampled = mode != 0;
-    if (sampled) logits_out = s->logits + (size_t)slot0 * m->vocab;
-    GemvParams p;
-    lmhead_params(s, slot0, logits_out, p);
-    int lm_grid = 0;
-    KCHK(launch_proj(GEMV_LMHEAD, p, m->lm_head, m->lm_head_fm, B, st, &lm_grid, m->lm_head_sc, m->lm_head_r8, F8_LMHEAD, m->lm_head_fm, m->lm_head_sc));
-    if (mode & 6) return launch_proc_finish_step(s, B, is_prefill, slot0, logits_out, st);
-    if (sampled) return launch_sampled_finish_step(s, B, is_prefill, slot0, logits_out, st);
-    if (do_finish) return launch_finish_step(s, B, is_prefill, lm_grid, slot0, st);
-    return 0;
-}
-
-// patches == nullptr: language-only forward (no patch rows are spliced in; modeling_prismatic.py:343-359)
-// slot0 >= 0: slot serving -- the B (= 1) rows land in rows slot0.. of the live decode batch, whose other rows are untouched
-static int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B, int P_max, const void* patches,
-                       hipStream_t st, int slot0 = -1) {
-    emmax_model* m = s->m;
-    const auto& c = m->cfg;
-    if (!m->finalized) return fail(EMMAX_ERR_STATE, "model not finalized");
-    // (an exact session was checked against the shapes its two-term kernels take when it was created, and chunks larger batches: check_exact)
-    const int max_rows = s->exact ? EMMAX_MAX_DECODE_BATCH : model_max_decode_batch(m);
-    if (B <= 0 || B > s->max_batch || B > max_rows)
-        return fail(EMMAX_ERR_INVALID, "prefill batch %d outside 1..min(max_batch=%d, %d) (decode batches above 8 need the shapes decode_km.hip takes: emmax_model_max_decode_batch)",
-                    B, s->max_batch, max_rows);
-    if (B >= EMMAX_MFMA_MIN_BATCH && !m->aux_built)
-        return fail(EMMAX_ERR_STATE, "batch %d decodes on the fragment-major weight copies: call emmax_model_build_aux first", B);
-    const int np = patches ? m->tw[0].n_patches : 0;
-    const bool slot_mode = slot0 >= 0;
-    const int r0 = slot_mode ? slot0 : 0;
-    if (s->beam_K) {   // beams on: B groups, one prefilled row each, forked into B x K rows by emmax_generate
-        if (slot_mode) return fail(EMMAX_ERR_STATE, "request slots are not served while beams are on");
-        const int rows = B * s->beam_K;
-        if (rows > s->max_batch || rows > max_rows)
-            return fail(EMMAX_ERR_INVALID, "%d groups x %d beams exceed min(max_batch=%d, %d) rows", B, s->beam_K, s->max_batch, max_rows);
-        if (rows >= EMMAX_MFMA_MIN_BATCH && !m->aux_built)
-            return fail(EMMAX_ERR_STATE, "%d beam rows decode on the fragment-major weight copies: call emmax_model_build_aux first", rows);
-        for (int b = 0; b < B; ++b)
-            if (lens[b] >= 1 && !beam_pages_fit(s, np + lens[b], 1))
-                return fail(EMMAX_ERR_NOMEM, "group %d: a context of %d tokens leaves its %d beams no spare pages (%d pages per row)", b, np + lens[b], s->beam_K, s->max_pages);
-        KCHK(launch_beam_pages(s->page_table, B, s->max_pages, s->beam_K, st));   // row g over the pool of group g: the pages of rows g K ..
-        s->beam_G = B; s->beam_forked = false; s->beam_ready = false;
-    }
-    if (slot_mode) {
-        if (!s->slots_open) return fail(EMMAX_ERR_STATE, "slot prefill before emmax_slots_open");
-        if (r0 >= s->stg0) {   // staging rows
-            if (r0 + B > s->rows_total) return fail(EMMAX_ERR_INVALID, "%d requests exceed the %d staging rows", B, s->n_stg);
-        } else if (r0 + B > s->cur_B) return fail(EMMAX_ERR_INVALID, "slot %d outside the %d open slots", r0, s->cur_B);
-        if ((int)s->S.size() < s->rows_total) s->S.resize(s->rows_total, 0);
-    } else {
-        s->S.assign(s->rows_total, 0);
-        s->slots_open = false;
-    }
-    int total = 0, maxS = 0;
-    PrefillState ps;
-    ps.B = B;
-    for (int b = 0; b < B; ++b) {
-        if (lens[b] < 1 || lens[b] > P_max || lens[b] > s->max_prompt)
-            return fail(EMMAX_ERR_INVALID, "row %d: prompt length %d outside 1..min(P_max=%d, max_prompt=%d)", b, lens[b], P_max, s->max_prompt);
-        const int Sb = np + lens[b];
-        if (Sb + 1 > s->max_ctx) return fail(EMMAX_ERR_NOMEM, "row %d: %d prompt+patch tokens do not fit max_ctx %d", b, Sb, s->max_ctx);
-        s->S[r0 + b] = Sb;
-        ps.S[b] = Sb;
-        total += Sb;
-        maxS = std::max(maxS, Sb);
-    }
-    if (total > s->max_rows) return fail(EMMAX_ERR_NOMEM, "packed prefill rows %d exceed capacity %d", total, s->max_rows);
-    KCHK(launch_prefill_state(ps, s->cu, s->ctx_len + r0, s->done + r0, s->n_out + r0, s->max_new_d + r0, s->stop_m + r0, s->stop_after + r0, st));
-    if (s->scores_on && !slot_mode && !s->beam_K) {   // the score buffers' rows: the first prefill after the binding's; another batch size unbinds them
-        if (s->scores_rows == 0) {
-            s->scores_rows = B;
-            KCHK(launch_set_int((int32_t*)(s->score_words + 3), B, st));
-        } else if (s->scores_rows != B) {
-            s->scores_on = false;
-        }
-    }
-    if (s->processing) {   // the rows' prompt ids: the history the processors read
-        HistParams h;
-        memset(&h, 0, sizeof(h));
-        h.ids = ids; h.P_max = P_max; h.B = B; h.max_prompt = s->max_prompt;
-        h.dst = s->hist + (size_t)r0 * s->max_prompt; h.dst_len = s->hist_len + r0;
-        for (int b = 0; b < B; ++b) h.len[b] = lens[b];
-        KCHK(launch_hist_fill(h, st));
-    }
-    if (!slot_mode) { s->cur_B = B; s->dec_steps = 0; }
-    s->total_rows = total; s->max_seqlen = maxS;
-    if (s->exact) return run_prefill_x(s, ids, B, P_max, patches, np, total, maxS, r0, st);
-
-    // fp32 residual stream (tuning switch resid32 = 1; 2 = the decode step only): o-proj and down add into fp32 rows -- through the
-    // split-K reduce passes of a one-frame prefill, through the direct fp32 epilogue of the big GEMMs otherwise -- and the RMSNorms read
-    // them; the stream is rounded to bf16 only where a GEMM consumes the normalised rows
-    const bool p32 = emmax_tune().resid32 == 1;
-    s->p32 = p32;
-    KCHK(launch_embed_splice(ids, P_max, s->cu, m->embed, patches, s->ph, B, maxS, np, m->H, m->vocab, st, p32 ? s->ph32 : nullptr));
-    auto input_norm = [&](const void* w) {
-        return p32 ? launch_rmsnorm_f32(s->ph32, s->pxn, w, total, m->H, m->H, m->H, c.rms_eps, st)
-                   : launch_rmsnorm(s->ph, s->pxn, w, total, m->H, m->H, m->H, c.rms_eps, st);
-    };
-    auto into_stream = [&](GemmParams& g) {   // C = residual stream += A W^T
-        if (p32) { g.C = s->ph32; g.out_f32 = 1; g.residual = s->ph32; g.res_f32 = 1; }
-        else { g.residual = s->ph; }
-        g.ldr = m->H;
-    };
-    // the RMSNorm behind a projection whose partial tiles meet in a split-K reduce pass (one-frame prefill: o-proj, down) is applied
-    // by that pass (gemm_fuses_norm); otherwise it is its own launch
-    auto with_norm = [&](GemmParams& g, const void* w) {
-        g.norm_w = w; g.norm_out = s->pxn; g.ld_norm = m->H; g.norm_eps = c.rms_eps;
-        if (gemm_fuses_norm(g)) return true;
-        g.norm_w = nullptr; g.norm_out = nullptr;
-        return false;
-    };
-    bool normed = false;   // s->pxn already holds ln1 of the current layer
-    for (int li = 0; li < c.n_layers; ++li) {
-        const LayerW& L = m->layers[li];
-        if (!normed) KCHK(input_norm(L.ln1));
-        GemmParams g = gps(s, s->pxn, m->H, L.wqkv, m->H, s->pqkv, m->qkv_dim, total, m->qkv_dim, m->H);
-        KCHK(launch_gemm(g, st));
-        // (fp8 KV cache: the pass rotates q / k in place only, the quantising pass appends K and V as e4m3 rows + scales)
-        KCHK(launch_rope_kv_write(s->pqkv, m->qkv_dim, 0, m->q_dim, m->q_dim + m->kv_dim, s->cu, B, total, s->cos_t, s->sin_t,
-                                  s->kv8 ? nullptr : kcache_of(s, li), s->kv8 ? nullptr : vcache_of(s, li), s->page_table + (size_t)r0 * s->max_pages,
-                                  s->max_pages, c.n_heads, c.n_kv_heads, c.head_dim, PAGE, st));
-        if (s->kv8)
-            KCHK(launch_kv_quant_rows(s->pqkv, m->qkv_dim, m->q_dim, m->q_dim + m->kv_dim, s->cu, B, total, kcache_of(s, li), vcache_of(s, li),
-                                      kscale_of(s, li), vscale_of(s, li), s->page_table + (size_t)r0 * s->max_pages, s->max_pages, c.n_kv_heads,
-                                      c.head_dim, PAGE, st));
-        AttnParams a;
-        a.qkv = s->pqkv; a.out = s->patt; a.cu_seqlens = s->cu;
-        a.ld_qkv = m->qkv_dim; a.q_off = 0; a.k_off = m->q_dim; a.v_off = m->q_dim + m->kv_dim; a.ld_out = m->q_dim;
-        a.B = B; a.max_seqlen = maxS; a.Hq = c.n_heads; a.Hkv = c.n_kv_heads;
-        a.scale = 1.0f / sqrtf((float)c.head_dim); a.causal = 1;
-        KCHK(launch_attention(a, c.head_dim, st));
-        g = gps(s, s->patt, m->q_dim, L.wo, m->q_dim, s->ph, m->H, total, m->H, m->q_dim);
-        into_stream(g);
-        normed = with_norm(g, L.ln2);
-        KCHK(launch_gemm(g, st));
-        if (!normed) KCHK(input_norm(L.ln2));
-        g = gps(s, s->pxn, m->H, L.wgu, m->H, s->pact, m->inter_p, total, 2 * m->inter_p, m->H);
-        g.act = 2;
-        KCHK(launch_gemm(g, st));
-        g = gps(s, s->pact, m->inter_p, L.wdown, m->inter_p, s->ph, m->H, total, m->H, m->inter_p);
-        into_stream(g);
-        normed = li + 1 < c.n_layers && with_norm(g, m->layers[li + 1].ln1);
-        KCHK(launch_gemm(g, st));
-    }
-    KCHK(launch_gather_last_rows(s->ph, s->dh + (size_t)r0 * m->H, s->cu, B, m->H, st, h32_of(s, r0), p32 ? s->ph32 : nullptr));
-    int r = run_lm_head_step(s, B, true, nullptr, true, st, r0);
-    if (r) return r;
-    s->prefilled = true;
-    s->beam_ready = s->beam_K != 0;
-    return 0;
-}
-
-// the prefill in exact numerics: fp32 residual rows (ph32), every GEMM over two-term A operands with fp32 results, fp32 RoPE, fp32 K / V
-// into the fp32 cache, fp32-MFMA causal attention; semantics as run_prefill (modeling_prismatic.py:362-415, HF LlamaDecoderLayer)
-static int run_prefill_x(emmax_session* s, const int32_t* ids, int B, int P_max, const void* patches, int np, int total, int maxS, int r0, hipStream_t st) {
-    emmax_model* m = s->m;
-    const auto& c = m->cfg;
-    // patch rows: fp32 [B, n_patches, hidden] -- what emmax_vision_encode* hands out in an exact session (the session's own copy when the caller passes none)
-    KCHK(launch_x_embed_splice(ids, P_max, s->cu, m->embed, (const float*)patches, nullptr, s->ph32, B, maxS, np, m->H, m->vocab, st));
-    s->p32 = true;
-    auto into_stream = [&](GemmParams& g) { g.C = s->ph32; g.ldc = m->H; g.residual = s->ph32; g.res_f32 = 1; g.ldr = m->H; };
-    for (int li = 0; li < c.n_layers; ++li) {
-        const LayerW& L = m->layers[li];
-        KCHK(launch_x_rmsnorm(s->ph32, s->xhla, L.ln1, total, m->H, m->H, 2 * m->H, c.rms_eps, st));
-        GemmParams g = gpx(s, s->xhla, m->H, L.wqkv, m->H, s->x32a, m->qkv_dim, total, m->qkv_dim);
-        KCHK(launch_gemm(g, st));
-        KCHK(launch_x_rope_kv_write(s->x32a, m->qkv_dim, 0, m->q_dim, m->q_dim + m->kv_dim, s->cu, B, total, s->cos_t, s->sin_t, kcache_of(s, li),
-                                    vcache_of(s, li), s->kv24, s->page_table + (size_t)r0 * s->max_pages, s->max_pages, c.n_heads, c.n_kv_heads, c.head_dim, PAGE, st));
-        AttnParams a;
-        a.qkv = s->x32a; a.out = s->xhlb; a.cu_seqlens = s->cu;
-        a.ld_qkv = m->qkv_dim; a.q_off = 0; a.k_off = m->q_dim; a.v_off = m->q_dim + m->kv_dim; a.ld_out = 2 * m->q_dim;
-        a.B = B; a.max_seqlen = maxS; a.Hq = c.n_heads; a.Hkv = c.n_kv_heads;
-        a.scale = 1.0f / sqrtf((float)c.head_dim); a.causal = 1;
-        KCHK(launch_x_attention(a, c.head_dim, st));
-        g = gpx(s, s->xhlb, m->q_dim, L.wo, m->q_dim, nullptr, 0, total, m->H);
-        into_stream(g);
-        KCHK(launch_gemm(g, st));
-        KCHK(launch_x_rmsnorm(s->ph32, s->xhla, L.ln2, total, m->H, m->H, 2 * m->H, c.rms_eps, st));
-        g = gpx(s, s->xhla, m->H, L.wgu, m->H, s->x32a, m->inter_p, total, 2 * m->inter_p);
-        g.act = 2;
-        KCHK(launch_gemm(g, st));
-        KCHK(launch_x_split_rows(s->x32a, s->xhlb, total, m->inter_p, m->inter_p, m->inter_p, 2 * m->inter_p, st));
-        g = gpx(s, s->xhlb, m->inter_p, L.wdown, m->inter_p, nullptr, 0, total, m->H);
-        into_stream(g);
-        KCHK(launch_gemm(g, st));
-    }
-    KCHK(launch_gather_last_rows(s->ph, s->dh + (size_t)r0 * m->H, s->cu, B, m->H, st, s->dh32 + (size_t)r0 * m->H, s->ph32));
-    int r = run_lm_head_step(s, B, true, nullptr, true, st, r0);
-    if (r) return r;
-    s->prefilled = true;
-    s->beam_ready = s->beam_K != 0;
-    return 0;
-}
-
-enum { STAGE_QKV = 0, STAGE_ATTN = 1, STAGE_OPROJ = 2, STAGE_GATEUP = 3, STAGE_DOWN = 4, STAGE_LMHEAD = 5 };
-
-// one KV split per (row, head) (batch >= 5 at 32 heads): nothing to merge -- the attention launch normalises and writes the bf16 row
-// itself and the o-proj is a plain projection; otherwise the o-proj prologue merges the split partials.
-static bool attn_direct_on(const emmax_session* s, int B) {
-    // exact numerics: the fp32 row in place over the q rows, at batch >= 3 (decode_km.hip's EX o-proj takes fp32 rows; decode_ks.hip's merges the partials)
-    if (s->exact && B < EMMAX_MFMA_MIN_BATCH) return false;
-    return decode_attn_nsplit(B, s->m->cfg.n_kv_heads) == 1 && emmax_tune().attn_direct != 0;
-}
-
-// GemvParams of a projection stage of decoder layer `li` (qkv / o-proj / gate-up / down), as every launcher takes them
-static void stage_params(emmax_session* s, int B, int li, int stage, GemvParams& p) {
-    emmax_model* m = s->m;
-    const auto& c = m->cfg;
-    const LayerW& L = m->layers[li];
-    memset(&p, 0, sizeof(p));
-    p.sk_ws = streamk_on() ? s->sk_ws : nullptr;
-    if (stage != STAGE_ATTN) { p.h32 = h32_of(s); p.ldh = m->H; }   // qkv / gate-up read the hidden rows, o-proj / down add into them
-    if (s->exact) { p.exact = 1; p.h32 = s->dh32; p.ldh = m->H; }
-    switch (stage) {
-        case STAGE_QKV:
-            p.x = s->dh; p.ldx = m->H; p.ldw = m->H; p.K = m->H; p.norm_w = L.ln1; p.eps = c.rms_eps;
-            p.y = s->dq; p.ldy = m->q_dim; p.n_rows = m->qkv_dim;
-            p.head_dim = c.head_dim; p.Hq = c.n_heads; p.Hkv = c.n_kv_heads; p.page = PAGE; p.max_pages = s->max_pages;
-            p.ctx_len = s->ctx_len; p.page_table = s->page_table; p.cos_t = s->cos_t; p.sin_t = s->sin_t;
-            p.kcache = kcache_of(s, li); p.vcache = vcache_of(s, li);
-            p.kv_stage = s->kv8 ? s->kv_stage : nullptr;   // fp8 KV cache: the new rows wait as bf16 for the attention launch
-            if (s->exact) { p.y = s->dq32; p.kv24 = s->kv24; }   // fp32 q rows; kcache / vcache are the 24-bit (or fp32) cache
-            break;
-        case STAGE_OPROJ:
-            p.x = s->datt; p.ldx = m->q_dim; p.ldw = m->q_dim; p.K = m->q_dim; p.y = s->dh; p.ldy = m->H; p.n_rows = m->H;
-            if (!attn_direct_on(s, B)) {   // split merge fused into the staging
-                p.attn_part = s->part; p.nsplit = decode_attn_nsplit(B, c.n_kv_heads); p.Hq = c.n_heads;
-            } else if (s->exact) {
-                p.x = s->dq32;             // the attention launch left the normalised fp32 rows in place of the q rows
-            }
-            break;
-        case STAGE_GATEUP:
-            p.x = s->dh; p.ldx = m->H; p.ldw = m->H; p.K = m->H; p.norm_w = L.ln2; p.eps = c.rms_eps;
-            p.y = s->dact; p.ldy = m->inter_p; p.n_rows = 2 * m->inter_p;
-            if (s->exact) p.y = s->dact32;
-            break;
-        case STAGE_DOWN:
-            p.x = s->dact; p.ldx = m->inter_p; p.ldw = m->inter_p; p.K = m->inter_p; p.y = s->dh; p.ldy = m->H; p.n_rows = m->H;
-            if (s->exact) p.x = s->dact32;
-            break;
-        default: break;
-    }
-}
-static void lmhead_params(emmax_session* s, int slot0, float* logits_out, GemvParams& p) {
-    emmax_model* m = s->m;
-    memset(&p, 0, sizeof(p));
-    p.sk_ws = streamk_on() ? (slot0 >= s->stg0 ? s->sk_ws2 : s->sk_ws) : nullptr;
-    p.x = s->dh + (size_t)slot0 * m->H; p.ldx = m->H; p.ldw = m->H; p.K = m->H; p.norm_w = m->final_norm; p.eps = m->cfg.rms_eps;
-    p.h32 = h32_of(s, slot0); p.ldh = m->H;
-    if (s->exact) { p.exact = 1; p.h32 = s->dh32 + (size_t)slot0 * m->H; }
-    const bool stg = slot0 >= s->stg0;
-    p.n_rows = m->vocab; p.max_parts = s->n_lm_blocks; p.part_val = stg ? s->part_val2 : s->part_val; p.part_idx = stg ? s->part_idx2 : s->part_idx;
-    p.logits_out = logits_out;
-}
-
-// one stage of decoder layer `li` (the unit the profiler times); the step is stages 0..4 of every layer + lm head
-// exact numerics, batches above 8 rows: the two-term MFMA kernels hold 8 rows (decode_km.hip EX: the two terms of a row in the sixteen batch columns), so a
-// projection stage runs in chunks of 8 rows -- each chunk streams the weights again: the conformance mode covers every batch the default path serves, at
-// ceil(B / 8) times its weight traffic.  (The attention launch takes any batch; the lm-head chunks in run_lm_head_step.)
-#define EMMAX_EXACT_ROWS 8
-static int run_decode_stage_x_chunks(emmax_session* s, int B, int li, int stage, hipStream_t st) {
-    emmax_model* m = s->m;
-    const LayerW& L = m->layers[li];
-    GemvParams p0;
-    stage_params(s, B, li, stage, p0);
-    for (int r = 0; r < B; r += EMMAX_EXACT_ROWS) {
-        GemvParams p = p0;
-        const int n = std::min(EMMAX_EXACT_ROWS, B - r);
-        int grid = 0;
-        if (p.h32) p.h32 += (size_t)r * p.ldh;
-        switch (stage) {
-            case STAGE_QKV:
-                p.y = (float*)p.y + (size_t)r * p.ldy;
-                p.ctx_len += r; p.page_table += (size_t)r * p.max_pages;
-                KCHK(launch_proj(GEMV_QKV, p, L.wqkv, L.wqkv_fm, n, st, &grid, L.wqkv_sc, L.wqkv_r8, F8_QKV, L.wqkv_km, L.wqkv_km_sc));
-                break;
-            case STAGE_OPROJ:
-                if (p.attn_part) p.attn_part += (size_t)r * p.Hq * p.nsplit * EMMAX_PSTRIDE;
-                else p.x = (const float*)p.x + (size_t)r * p.ldx;
-                p.y = (bf16*)p.y + (size_t)r * p.ldy;
-                KCHK(launch_proj(GEMV_RESID, p, L.wo, L.wo_fm, n, st, &grid, L.wo_sc, L.wo_r8, F8_OPROJ, L.wo_fm, L.wo_sc));
-                break;
-            case STAGE_GATEUP:
-                p.y = (float*)p.y + (size_t)r * p.ldy;
-                KCHK(launch_proj(GEMV_GATEUP, p, L.wgu, L.wgu_fm, n, st, &grid, L.wgu_sc, L.wgu_r8, F8_GATEUP, L.wgu_km, L.wgu_km_sc));
-                break;
-            case STAGE_DOWN:
-                p.x = (const float*)p.x + (size_t)r * p.ldx;
-                p.y = (bf16*)p.y + (size_t)r * p.ldy;
-                KCHK(launch_proj(GEMV_RESID, p, L.wdown, L.wdown_fm, n, st, &grid, L.wdown_sc, L.wdown_r8, F8_DOWN, L.wdown_fm, L.wdown_sc));
-                break;
-            default: return fail(EMMAX_ERR_INVALID, "unknown decode stage %d", stage);
-        }
-    }
-    return 0;
-}
-
-static int run_decode_stage(emmax_session* s, int B, int li, int stage, hipStream_t st) {
-    emmax_model* m = s->m;
-    const auto& c = m->cfg;
-    const LayerW& L = m->layers[li];
-    GemvParams p;
-    int grid = 0;
-    if (s->exact && B > EMMAX_EXACT_ROWS && stage != STAGE_ATTN) return run_decode_stage_x_chunks(s, B, li, stage, st);
-    switch (stage) {
-        case STAGE_QKV:
-            stage_params(s, B, li, stage, p);
-            KCHK(launch_proj(GEMV_QKV, p, L.wqkv, L.wqkv_fm, B, st, &grid, L.wqkv_sc, L.wqkv_r8, F8_QKV, L.wqkv_km, L.wqkv_km_sc));
-            return 0;
-        case STAGE_ATTN: {
-            DecodeAttnParams a;
-            memset(&a, 0, sizeof(a));
-            a.q = s->dq; a.ldq = m->q_dim; a.kcache = kcache_of(s, li); a.vcache = vcache_of(s, li);
-            if (s->kv8) { a.kv_stage = s->kv_stage; a.kscale = kscale_of(s, li); a.vscale = vscale_of(s, li); }
-            a.page_table = s->page_table; a.ctx_len = s->ctx_len; a.done = s->done; a.part = s->part; a.Hkv = c.n_kv_heads; a.page = PAGE;
-            a.max_pages = s->max_pages; a.scale = 1.0f / sqrtf((float)c.head_dim);
-            a.o_out = attn_direct_on(s, B) ? s->datt : nullptr;
-            const int ns = decode_attn_nsplit(B, c.n_kv_heads);
-            if (s->exact) {
-                a.q = s->dq32; a.kv24 = s->kv24;
-                a.o_out = attn_direct_on(s, B) ? (void*)s->dq32 : nullptr;
-                KCHK(launch_x_decode_attn(a, B, c.n_heads, c.head_dim, ns, st));
-                return 0;
-            }
-            KCHK(launch_decode_attn(a, B, c.n_heads, c.head_dim, ns, st));
-            return 0;
-        }
-        case STAGE_OPROJ:
-            stage_params(s, B, li, stage, p);
-            // (batch >= 3: the K-split MFMA kernel takes the o-proj with fp8 weights only, see decode_km.hip)
-            KCHK(launch_proj(GEMV_RESID, p, L.wo, L.wo_fm, B, st, &grid, L.wo_sc, L.wo_r8, F8_OPROJ, L.wo_fm, L.wo_sc));
-            return 0;
-        case STAGE_GATEUP:
-            stage_params(s, B, li, stage, p);
-            KCHK(launch_proj(GEMV_GATEUP, p, L.wgu, L.wgu_fm, B, st, &grid, L.wgu_sc, L.wgu_r8, F8_GATEUP, L.wgu_km, L.wgu_km_sc));
-            return 0;
-        case STAGE_DOWN:
-            stage_params(s, B, li, stage, p);
-            if (B > EMMAX_KMP_ROWS) {   // 33-64 rows: K = 11008 does not fit the eight phases of a four-way split -- two launches of <= 32 rows
-                GemvParams q = p;
-                KCHK(launch_proj(GEMV_RESID, q, L.wdown, L.wdown_fm, EMMAX_KMP_ROWS, st, &grid, L.wdown_sc, L.wdown_r8, F8_DOWN, L.wdown_fm, L.wdown_sc));
-                q = p;
-                q.x = (const bf16*)q.x + (size_t)EMMAX_KMP_ROWS * q.ldx;
-                q.y = (bf16*)q.y + (size_t)EMMAX_KMP_ROWS * q.ldy;
-                if (q.h32) q.h32 += (size_t)EMMAX_KMP_ROWS * q.ldh;
-                KCHK(launch_proj(GEMV_RESID, q, L.wdown, L.wdown_fm, B - EMMAX_KMP_ROWS, st, &grid, L.wdown_sc, L.wdown_r8, F8_DOWN, L.wdown_fm, L.wdown_sc));
-                return 0;
-            }
-            KCHK(launch_proj(GEMV_RESID, p, L.wdown, L.wdown_fm, B, st, &grid, L.wdown_sc, L.wdown_r8, F8_DOWN, L.wdown_fm, L.wdown_sc));
-            return 0;
-        default:
-            return fail(EMMAX_ERR_INVALID, "unknown decode stage %d", stage);
-    }
-}
-
-// layer 0's qkv with the embedding gather folded in (K-split kernel; anything else: embed launch + the plain stage)
-static int run_qkv0_with_embed(emmax_session* s, int B, hipStream_t st) {
-    emmax_model* m = s->m;
-    GemvParams p;
-    stage_params(s, B, 0, STAGE_QKV, p);
-    p.W = m->layers[0].wqkv;
-    p.x = m->embed; p.x_tok = s->cur_tok; p.x_copy = s->dh; p.x_vocab = m->vocab;
-    int r = launch_decode_ks(GEMV_QKV, p, B, st, nullptr);
-    if (r == -2) {
-        KCHK(launch_decode_embed(s->cur_tok, m->embed, s->dh, B, m->H, m->vocab, st, s->exact ? s->dh32 : h32_of(s)));
-        return run_decode_stage(s, B, 0, STAGE_QKV, st);
-    }
-    return r ? fail(EMMAX_ERR_HIP, "qkv launch of layer 0 failed (code %d)", r) : 0;
-}
-
-static int run_decode_step(emmax_session* s, int B, hipStream_t st) {
-    emmax_model* m = s->m;
-    // batch 1-2 on bf16 weights: the embedding row is read by layer 0's qkv launch itself (K-split kernel) -- one launch fewer
-    const bool fold_embed = B < EMMAX_MFMA_MIN_BATCH && !m->fp8 && decode_ks_enabled() && m->H % 64 == 0 && m->H <= 12288 &&
-                            emmax_tune().fold_embed != 0;
-    if (!fold_embed) KCHK(launch_decode_embed(s->cur_tok, m->embed, s->dh, B, m->H, m->vocab, st, s->exact ? s->dh32 : h32_of(s)));
-    for (int li = 0; li < m->cfg.n_layers; ++li)
-        for (int stage = STAGE_QKV; stage <= STAGE_DOWN; ++stage) {
-            int r = (li == 0 && stage == STAGE_QKV && fold_embed) ? run_qkv0_with_embed(s, B, st) : run_decode_stage(s, B, li, stage, st);
-            if (r) return r;
-        }
-    return run_lm_head_step(s, B, false, nullptr, true, st);
-}
-
-static void drop_graph(emmax_session* s) {
-    if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
-    if (s->graph) (void)hipGraphDestroy(s->graph);
-    s->graph_exec = nullptr;
-    s->graph = nullptr;
-    s->graph_B = 0;
-}
-
-static int graph_fail(emmax_session* s, const std::string& why) {
-    s->graph_failed = 1;
-    s->graph_err = why;
-    (void)hipGetLastError();
-    return 1;
-}
-
-// Capture one decode step into a hipGraph.
-static int ensure_graph(emmax_session* s, int B, hipStream_t st) {
-    // Default: eager launch-ahead.  One step is 163 launches for >= 2.6 ms of GPU time, so a single host thread stays far
-    // ahead of the device, and measured on MI355X / ROCm 7.2 the replayed graph is the SLOWER option: 3.05 vs 2.95 ms/token
-    // at B = 1 (~0.6 us more per kernel node than a same-stream launch; round 3: 2.73 vs 2.62, and neither hipGraphUpload, the
-    // instantiate flags, DEBUG_HIP_GRAPH_BATCH_SIZE / DEBUG_HIP_FORCE_GRAPH_QUEUES nor the kernarg placement move it).
-    // Tuning switch graph = 1 (EMMAX_GRAPH=1 at start-up, or emmax_tuning_set) selects graph replay (a host whose launch thread
-    // cannot be kept free).
-    s->last_step_graph = 0;   // set again by launch_graph_step when a replay really runs
-    if (!emmax_tune().graph) return 1;   // eager step: a captured graph stays valid for the next caller that wants replay
-    if (s->graph_exec && s->graph_B == B && s->graph_stream_cap == st && s->graph_epoch == emmax_tune().epoch && s->graph_mode == finish_mode(s))
-        return 0;
-    drop_graph(s);
-    if (s->graph_failed) return 1;
-    hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-    if (e != hipSuccess) return graph_fail(s, std::string("hipStreamBeginCapture: ") + hipGetErrorString(e));
-    const int r = run_decode_step(s, B, st);
-    hipGraph_t g = nullptr;
-    e = hipStreamEndCapture(st, &g);
-    if (r != 0 || e != hipSuccess || !g) {
-        if (g) (void)hipGraphDestroy(g);
-        return graph_fail(s, r != 0 ? ("launch during capture: " + g_err) : (std::string("hipStreamEndCapture: ") + hipGetErrorString(e)));
-    }
-    hipGraphExec_t ge = nullptr;
-    e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-    if (e != hipSuccess) {
-        (void)hipGraphDestroy(g);
-        return graph_fail(s, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
-    }
-    s->graph = g; s->graph_exec = ge; s->graph_B = B; s->graph_stream_cap = st; s->graph_epoch = emmax_tune().epoch;
-    s->graph_mode = finish_mode(s);
-    return 0;
-}
-
-static int launch_graph_step(emmax_session* s, int B, hipStream_t st) {
-    s->last_step_graph = 1;
-    HIPCHK(hipGraphLaunch(s->graph_exec, st));
-    return 0;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // C ABI
@@ -1600,10 +342,10 @@ int emmax_model_finalize(emmax_model* m, void* arena, int64_t arena_bytes, emmax
         LayerW& L = m->layers[li];
         const std::string P = "language_model.model.layers." + std::to_string(li) + ".";
         PUT1(P + "input_layernorm.weight", m->H, L.ln1);
-        PUT2(P + "self_attn.q_proj.weight", m->q_dim, m->H, L.wqkv, m->H, 0);
-        PUT2(P + "self_attn.k_proj.weight", m->kv_dim, m->H, L.wqkv, m->H, m->q_dim);
-        PUT2(P + "self_attn.v_proj.weight", m->kv_dim, m->H, L.wqkv, m->H, m->q_dim + m->kv_dim);
-        PUT2(P + "self_attn.o_proj.weight", m->H, m->q_dim, L.wo, m->q_dim, 0);
+        PUT2(P + "self_attn.q_proj.weight", m->q_dim, m->H, L.proj[STAGE_QKV].rm, m->H, 0);
+        PUT2(P + "self_attn.k_proj.weight", m->kv_dim, m->H, L.proj[STAGE_QKV].rm, m->H, m->q_dim);
+        PUT2(P + "self_attn.v_proj.weight", m->kv_dim, m->H, L.proj[STAGE_QKV].rm, m->H, m->q_dim + m->kv_dim);
+        PUT2(P + "self_attn.o_proj.weight", m->H, m->q_dim, L.proj[STAGE_OPROJ].rm, m->q_dim, 0);
         PUT1(P + "post_attention_layernorm.weight", m->H, L.ln2);
         // gate/up interleaved in 16-row groups: dst rows [32j, 32j+16) = gate rows [16j, 16j+16), next 16 = up
         {
@@ -1613,28 +355,24 @@ int emmax_model_finalize(emmax_model* m, void* arena, int64_t arena_bytes, emmax
             if (ig->second.numel() != (int64_t)m->inter * m->H || iu->second.numel() != (int64_t)m->inter * m->H)
                 return fail(EMMAX_ERR_INVALID, "gate/up of layer %d have the wrong size", li);
             const size_t grp = (size_t)16 * m->H * 2;
-            HIPCHK(hipMemcpy2DAsync(L.wgu, 2 * grp, ig->second.ptr, grp, grp, m->inter / 16, hipMemcpyDeviceToDevice, st));
-            HIPCHK(hipMemcpy2DAsync((char*)L.wgu + grp, 2 * grp, iu->second.ptr, grp, grp, m->inter / 16, hipMemcpyDeviceToDevice, st));
+            HIPCHK(hipMemcpy2DAsync(L.proj[STAGE_GATEUP].rm, 2 * grp, ig->second.ptr, grp, grp, m->inter / 16, hipMemcpyDeviceToDevice, st));
+            HIPCHK(hipMemcpy2DAsync((char*)L.proj[STAGE_GATEUP].rm + grp, 2 * grp, iu->second.ptr, grp, grp, m->inter / 16, hipMemcpyDeviceToDevice, st));
         }
-        PUT2(P + "mlp.down_proj.weight", m->H, m->inter, L.wdown, m->inter_p, 0);
+        PUT2(P + "mlp.down_proj.weight", m->H, m->inter, L.proj[STAGE_DOWN].rm, m->inter_p, 0);
         if (m->fp8) {
-            KCHK(launch_quant_fm8(L.wqkv, m->H, L.wqkv_fm, L.wqkv_sc, m->qkv_dim, m->H, st));
-            KCHK(launch_quant_fm8(L.wo, m->q_dim, L.wo_fm, L.wo_sc, m->H, m->q_dim, st));
-            KCHK(launch_quant_fm8(L.wgu, m->H, L.wgu_fm, L.wgu_sc, 2 * m->inter_p, m->H, st));
-            KCHK(launch_quant_fm8(L.wdown, m->inter_p, L.wdown_fm, L.wdown_sc, m->H, m->inter_p, st));
-            KCHK(launch_quant_rm8(L.wqkv, m->H, L.wqkv_r8, L.wqkv_sc, m->qkv_dim, m->H, st));   // (writes the same scales again)
-            KCHK(launch_quant_rm8(L.wo, m->q_dim, L.wo_r8, L.wo_sc, m->H, m->q_dim, st));
-            KCHK(launch_quant_rm8(L.wgu, m->H, L.wgu_r8, L.wgu_sc, 2 * m->inter_p, m->H, st));
-            KCHK(launch_quant_rm8(L.wdown, m->inter_p, L.wdown_r8, L.wdown_sc, m->H, m->inter_p, st));
-            KCHK(launch_quant_fm8(L.wqkv, m->H, L.wqkv_km, L.wqkv_km_sc, m->qkv_dim, m->H, st, 1, m->cfg.head_dim));
-            KCHK(launch_quant_fm8(L.wgu, m->H, L.wgu_km, L.wgu_km_sc, 2 * m->inter_p, m->H, st, 2, 0));
+            const auto dims = layer_projs(m);
+            for (const ProjDim& d : dims) KCHK(launch_quant_fm8(L.proj[d.stage].rm, (int)d.K, L.proj[d.stage].fm, L.proj[d.stage].sc, (int)d.N, (int)d.K, st));
+            for (const ProjDim& d : dims)   // (writes the same scales again)
+                KCHK(launch_quant_rm8(L.proj[d.stage].rm, (int)d.K, L.proj[d.stage].r8, L.proj[d.stage].sc, (int)d.N, (int)d.K, st));
+            for (const ProjDim& d : dims)
+                if (d.perm) KCHK(launch_quant_fm8(L.proj[d.stage].rm, (int)d.K, L.proj[d.stage].km, L.proj[d.stage].km_sc, (int)d.N, (int)d.K, st, d.perm, d.perm_hd));
         }
     }
     PUT1("language_model.model.norm.weight", m->H, m->final_norm);
-    PUT2("language_model.lm_head.weight", m->vocab, m->H, m->lm_head, m->H, 0);
+    PUT2("language_model.lm_head.weight", m->vocab, m->H, m->lm_head_w.rm, m->H, 0);
     if (m->fp8) {
-        KCHK(launch_quant_fm8(m->lm_head, m->H, m->lm_head_fm, m->lm_head_sc, m->vocab_p, m->H, st));
-        KCHK(launch_quant_rm8(m->lm_head, m->H, m->lm_head_r8, m->lm_head_sc, m->vocab_p, m->H, st));
+        KCHK(launch_quant_fm8(m->lm_head_w.rm, m->H, m->lm_head_w.fm, m->lm_head_w.sc, m->vocab_p, m->H, st));
+        KCHK(launch_quant_rm8(m->lm_head_w.rm, m->H, m->lm_head_w.r8, m->lm_head_w.sc, m->vocab_p, m->H, st));
     }
 #undef PUT2
 #undef PUT1
@@ -1671,1120 +409,18 @@ int emmax_model_build_aux(emmax_model* m, void* aux, int64_t aux_bytes, emmax_st
     Bump b{(char*)aux};
     plan_aux(m, b, ab);
     for (auto& L : m->layers) {
-        KCHK(launch_repack_km(L.wqkv, m->H, L.wqkv_km, m->qkv_dim, m->H, 1, m->cfg.head_dim, st));
-        KCHK(launch_repack_km(L.wgu, m->H, L.wgu_km, 2 * m->inter_p, m->H, 2, 0, st));
-        KCHK(launch_repack_fm(L.wo, m->q_dim, L.wo_fm, m->H, m->q_dim, st));
-        KCHK(launch_repack_fm(L.wdown, m->inter_p, L.wdown_fm, m->H, m->inter_p, st));
-        if (ab) {
-            KCHK(launch_repack_fm(L.wqkv, m->H, L.wqkv_fm, m->qkv_dim, m->H, st));
-            KCHK(launch_repack_fm(L.wgu, m->H, L.wgu_fm, 2 * m->inter_p, m->H, st));
-        }
+        const auto dims = layer_projs(m);
+        for (const ProjDim& d : dims)
+            if (d.perm) KCHK(launch_repack_km(L.proj[d.stage].rm, (int)d.K, L.proj[d.stage].km, (int)d.N, (int)d.K, d.perm, d.perm_hd, st));
+        for (const ProjDim& d : dims)
+            if (!d.perm) KCHK(launch_repack_fm(L.proj[d.stage].rm, (int)d.K, L.proj[d.stage].fm, (int)d.N, (int)d.K, st));
+        for (const ProjDim& d : dims)
+            if (d.perm && ab) KCHK(launch_repack_fm(L.proj[d.stage].rm, (int)d.K, L.proj[d.stage].fm, (int)d.N, (int)d.K, st));
     }
-    KCHK(launch_repack_fm(m->lm_head, m->H, m->lm_head_fm, m->vocab_p, m->H, st));
+    KCHK(launch_repack_fm(m->lm_head_w.rm, m->H, m->lm_head_w.fm, m->vocab_p, m->H, st));
     HIPCHK(hipStreamSynchronize(st));
     m->aux_built = true;
     m->aux_ab = ab;
-    return 0;
-}
-
-static int session_dims(const emmax_model* m, int max_batch, int max_prompt, int max_ctx, int* max_pages, int* max_rows) {
-    if (!m) return fail(EMMAX_ERR_INVALID, "null model");
-    if (max_batch < 1 || max_batch > 256) return fail(EMMAX_ERR_INVALID, "max_batch outside 1..256");
-    const int np = m->tw[0].n_patches;
-    if (max_prompt < 1) return fail(EMMAX_ERR_INVALID, "max_prompt < 1");
-    if (max_ctx < np + max_prompt + 1) return fail(EMMAX_ERR_INVALID, "max_ctx %d < patches %d + max_prompt %d + 1", max_ctx, np, max_prompt);
-    *max_pages = (max_ctx + PAGE - 1) / PAGE;
-    *max_rows = max_batch * (np + max_prompt);
-    return 0;
-}
-
-// stage_rows: staging rows for overlapped admissions (emmax_slots_prefill_staged), 0 .. min(max_batch, EMMAX_MAX_DECODE_BATCH).  They
-// cost per-row state AND their share of the paged KV region; a session that never stages (emmax_prefill / emmax_generate, the bench)
-// asks for none (round 4 gave every session min(max_batch, 8) of them and doubled the KV region of small sessions).
-static int check_stage_rows(int max_batch, int stage_rows) {
-    if (stage_rows < 0 || stage_rows > max_batch || stage_rows > EMMAX_MAX_DECODE_BATCH)
-        return fail(EMMAX_ERR_INVALID, "stage_rows %d outside 0..min(max_batch=%d, %d)", stage_rows, max_batch, EMMAX_MAX_DECODE_BATCH);
-    return 0;
-}
-// what an exact-numerics session needs of its model and its shape
-static int check_exact(const emmax_model* m, int max_batch, int stage_rows) {
-    if (m->fp8) return fail(EMMAX_ERR_INVALID, "exact numerics (tuning switch exact) runs on bf16 weights: this model streams fp8 decode weights");
-    if (m->finalized && m->ln_folded)
-        return fail(EMMAX_ERR_STATE, "exact numerics needs the ViT LayerNorms unfolded: set the tuning switch exact = 1 BEFORE emmax_model_finalize");
-    // batch 1-2: decode_ks.hip's two-term dot products; batch 3-8: decode_km.hip's EX kernels (the two terms of a row in the MFMA's sixteen batch
-    // columns), which need the shapes that file takes: K a multiple of 256 and <= 4096 for qkv / o-proj / gate-up / lm-head, at most 8 tiles per block,
-    // the down projection within four phases of 12 fragments per wave
-    // (batches above 8 rows run their projections in chunks of 8: run_decode_stage_x_chunks)
-    if (max_batch > EMMAX_MAX_DECODE_BATCH) return fail(EMMAX_ERR_INVALID, "exact numerics serves batches of 1-%d rows; max_batch %d", EMMAX_MAX_DECODE_BATCH, max_batch);
-    if (max_batch > 2) {
-        const bool k_ok = m->H % 256 == 0 && m->H <= 4096 && m->q_dim % 256 == 0 && m->q_dim <= 4096 && m->q_dim == m->cfg.n_heads * 128;
-        const bool n_ok = m->qkv_dim % 16 == 0 && m->qkv_dim <= 32768 && 2 * m->inter_p <= 32768 && m->vocab_p <= 32768 && m->H % 16 == 0 && m->cfg.head_dim % 16 == 0;
-        const bool d_ok = m->inter_p % 32 == 0 && m->inter_p / 32 >= 8 && (m->inter_p / 32 + 7) / 8 <= 48;
-        if (!(k_ok && n_ok && d_ok && decode_km_enabled()))
-            return fail(EMMAX_ERR_INVALID, "exact numerics at batch >= 3 needs the shapes decode_km.hip takes (hidden / q widths in multiples of 256 up to 4096, head_dim 128); max_batch %d", max_batch);
-    }
-    if (m->H % 64 || m->q_dim % 64) return fail(EMMAX_ERR_INVALID, "exact numerics needs hidden and q widths in multiples of 64");
-    return 0;
-}
-int emmax_session_bytes(const emmax_model* m, int max_batch, int max_prompt, int max_ctx, int64_t* ws, int64_t* kv) {
-    return emmax_session_bytes_ex(m, max_batch, max_prompt, max_ctx, 0, ws, kv);
-}
-int emmax_session_bytes_ex(const emmax_model* m, int max_batch, int max_prompt, int max_ctx, int stage_rows, int64_t* ws, int64_t* kv) {
-    int mp, mr, r;
-    if ((r = session_dims(m, max_batch, max_prompt, max_ctx, &mp, &mr))) return r;
-    if ((r = check_stage_rows(max_batch, stage_rows))) return r;
-    emmax_session tmp;
-    tmp.m = const_cast<emmax_model*>(m);
-    tmp.max_batch = max_batch; tmp.max_prompt = max_prompt; tmp.max_ctx = max_ctx; tmp.max_pages = mp; tmp.max_rows = mr;
-    tmp.max_out = max_ctx;
-    tmp.n_stg = stage_rows; tmp.stg0 = max_batch; tmp.rows_total = max_batch + tmp.n_stg;
-    tmp.exact = emmax_tune().exact != 0;
-    if (tmp.exact && (r = check_exact(m, max_batch, stage_rows))) return r;
-    SBump b{nullptr};
-    plan_session(&tmp, b);
-    if (ws) *ws = b.off + 256;
-    if (kv) *kv = kv_bytes_for(m, tmp.rows_total, mp, kv_format_now());
-    return 0;
-}
-
-int emmax_session_create(emmax_model* m, int max_batch, int max_prompt, int max_ctx, void* ws, int64_t ws_bytes, void* kv,
-                         int64_t kvb, emmax_session** out) {
-    return emmax_session_create_ex(m, max_batch, max_prompt, max_ctx, 0, ws, ws_bytes, kv, kvb, out);
-}
-int emmax_session_stage_rows(const emmax_session* s) { return s ? s->n_stg : -1; }
-int emmax_session_exact(const emmax_session* s) { return s ? (s->exact ? 1 : 0) : -1; }
-int emmax_session_create_ex(emmax_model* m, int max_batch, int max_prompt, int max_ctx, int stage_rows, void* ws, int64_t ws_bytes, void* kv,
-                            int64_t kvb, emmax_session** out) {
-    if (!m || !ws || !kv || !out) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (!m->finalized) return fail(EMMAX_ERR_STATE, "model not finalized");
-    int64_t need_ws, need_kv;
-    int r = emmax_session_bytes_ex(m, max_batch, max_prompt, max_ctx, stage_rows, &need_ws, &need_kv);
-    if (r) return r;
-    if (ws_bytes < need_ws || kvb < need_kv)
-        return fail(EMMAX_ERR_NOMEM, "session memory too small: workspace %lld/%lld, kv %lld/%lld", (long long)ws_bytes,
-                    (long long)need_ws, (long long)kvb, (long long)need_kv);
-    if (((uintptr_t)ws % 256) || ((uintptr_t)kv % 256)) return fail(EMMAX_ERR_INVALID, "workspace / kv must be 256-byte aligned");
-    if (decode_mfma_init() != 0 || decode_km_init() != 0 || decode_kmp_init() != 0)
-        return fail(EMMAX_ERR_HIP, "could not raise the dynamic LDS limit of the MFMA decode kernels");
-    emmax_session* s = new emmax_session();
-    s->m = m;
-    s->max_batch = max_batch; s->max_prompt = max_prompt; s->max_ctx = max_ctx;
-    session_dims(m, max_batch, max_prompt, max_ctx, &s->max_pages, &s->max_rows);
-    s->max_out = max_ctx;
-    s->n_stg = stage_rows; s->stg0 = max_batch; s->rows_total = max_batch + s->n_stg;
-    s->exact = emmax_tune().exact != 0;
-    SBump b{(char*)ws};
-    plan_session(s, b);
-    s->kv = (bf16*)kv;
-    s->kv8 = !s->exact && emmax_tune().kv_fp8 != 0;
-    s->kv_fmt = kv_format_now();
-    s->kv_layer_stride = kv_layer_bytes(m, s->rows_total, s->max_pages, s->kv_fmt);
-    s->kv24 = s->kv_fmt == KV_X24 ? (long long)kv_rows_per_layer(m, s->rows_total, s->max_pages) * m->cfg.head_dim : 0;
-    HIPCHK(hipMemset(ws, 0, need_ws));   // padding columns of every activation buffer stay zero forever
-    HIPCHK(hipMemset(kv, 0, need_kv));
-    HIPCHK(hipDeviceSynchronize());
-    if (decode_gemv_init() != 0) return fail(EMMAX_ERR_HIP, "could not raise the dynamic LDS limit of the GEMV kernels");
-    HIPCHK(hipHostMalloc((void**)&s->pinned, 4096 * 4, hipHostMallocDefault));
-    HIPCHK(hipEventCreateWithFlags(&s->ev, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&s->ev_in, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&s->ev_out, hipEventDisableTiming));
-    HIPCHK(hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&s->vis_stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&s->ev_vfork, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&s->ev_vjoin, hipEventDisableTiming));
-    // static page assignment: row b owns pages [b*max_pages, (b+1)*max_pages)
-    {
-        std::vector<int32_t> pt((size_t)s->rows_total * s->max_pages);
-        for (size_t i = 0; i < pt.size(); ++i) pt[i] = (int32_t)i;
-        HIPCHK(hipMemcpy(s->page_table, pt.data(), pt.size() * 4, hipMemcpyHostToDevice));
-        for (int t = 0; t < 2; ++t) {
-            std::vector<int32_t> cu(max_batch + 1);
-            for (int i = 0; i <= max_batch; ++i) cu[i] = i * m->tw[t].N;
-            HIPCHK(hipMemcpy(s->cu_vit[t], cu.data(), cu.size() * 4, hipMemcpyHostToDevice));
-        }
-        // RoPE tables, fp32, HF LlamaRotaryEmbedding order of operations (inv_freq fp32, pos*inv_freq fp32, cos/sin)
-        const int half = m->cfg.head_dim / 2;
-        std::vector<float> cs((size_t)max_ctx * half), sn((size_t)max_ctx * half);
-        for (int i = 0; i < half; ++i) {
-            const float inv = 1.0f / powf(m->cfg.rope_theta, (float)(2 * i) / (float)m->cfg.head_dim);
-            for (int p = 0; p < max_ctx; ++p) {
-                const float f = (float)p * inv;
-                cs[(size_t)p * half + i] = (float)cos((double)f);
-                sn[(size_t)p * half + i] = (float)sin((double)f);
-            }
-        }
-        HIPCHK(hipMemcpy(s->cos_t, cs.data(), cs.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(s->sin_t, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
-    }
-    *out = s;
-    return 0;
-}
-
-void emmax_session_destroy(emmax_session* s) {
-    if (!s) return;
-    drop_graph(s);
-    if (s->pinned) (void)hipHostFree(s->pinned);
-    if (s->ev) (void)hipEventDestroy(s->ev);
-    if (s->ev_in) (void)hipEventDestroy(s->ev_in);
-    if (s->ev_out) (void)hipEventDestroy(s->ev_out);
-    if (s->own_stream) (void)hipStreamDestroy(s->own_stream);
-    if (s->vis_stream) (void)hipStreamDestroy(s->vis_stream);
-    if (s->ev_vfork) (void)hipEventDestroy(s->ev_vfork);
-    if (s->ev_vjoin) (void)hipEventDestroy(s->ev_vjoin);
-    delete s;
-}
-
-int emmax_vision_encode(emmax_session* s, const uint8_t* frames, int B, void* out, emmax_stream st) {
-    if (!s || !frames) return fail(EMMAX_ERR_INVALID, "null argument");
-    return run_vision(s, true, frames, B, out, (hipStream_t)st);
-}
-int emmax_vision_encode_pixels(emmax_session* s, const void* px, int B, void* out, emmax_stream st) {
-    if (!s || !px) return fail(EMMAX_ERR_INVALID, "null argument");
-    return run_vision(s, false, px, B, out, (hipStream_t)st);
-}
-int emmax_vision_features(emmax_session* s, int B, void* out, emmax_stream st) {
-    if (!s || !out) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (B != s->vision_B) return fail(EMMAX_ERR_STATE, "no vision result for batch %d", B);
-    emmax_model* m = s->m;
-    if (s->exact) {   // the fp32 features, rounded for the caller
-        KCHK(launch_x_to_bf16(s->xfeats32, m->Vp, out, m->V, B * m->tw[0].n_patches, m->V, (hipStream_t)st));
-        return 0;
-    }
-    HIPCHK(hipMemcpy2DAsync(out, (size_t)m->V * 2, s->feats, (size_t)m->Vp * 2, (size_t)m->V * 2, (size_t)B * m->tw[0].n_patches,
-                            hipMemcpyDeviceToDevice, (hipStream_t)st));
-    return 0;
-}
-
-int emmax_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B, int P_max, const void* patches, emmax_stream st) {
-    if (!s || !ids || !lens) return fail(EMMAX_ERR_INVALID, "null argument");
-    const void* pe = patches ? patches : (s->exact ? (const void*)s->xpe32 : (const void*)s->patch_embeds);
-    if (!patches && s->vision_B != B) return fail(EMMAX_ERR_STATE, "no patch embeddings for batch %d (call emmax_vision_encode first)", B);
-    return run_prefill(s, ids, lens, B, P_max, pe, (hipStream_t)st);
-}
-
-int emmax_prefill_text(emmax_session* s, const int32_t* ids, const int32_t* lens, int B, int P_max, emmax_stream st) {
-    if (!s || !ids || !lens) return fail(EMMAX_ERR_INVALID, "null argument");
-    return run_prefill(s, ids, lens, B, P_max, nullptr, (hipStream_t)st);
-}
-
-int emmax_prefill_logits(emmax_session* s, float* out, emmax_stream stream) {
-    if (!s || !out) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (!s->prefilled) return fail(EMMAX_ERR_STATE, "prefill has not run");
-    emmax_model* m = s->m;
-    hipStream_t st = (hipStream_t)stream;
-    if (s->exact) {
-        KCHK(launch_x_rmsnorm(s->ph32, s->xhla, m->final_norm, s->total_rows, m->H, m->H, 2 * m->H, m->cfg.rms_eps, st));
-        GemmParams gx = gpx(s, s->xhla, m->H, m->lm_head, m->H, out, m->vocab, s->total_rows, m->vocab_p);
-        gx.N_store = m->vocab;
-        KCHK(launch_gemm(gx, st));
-        return 0;
-    }
-    if (s->p32) KCHK(launch_rmsnorm_f32(s->ph32, s->pxn, m->final_norm, s->total_rows, m->H, m->H, m->H, m->cfg.rms_eps, st));
-    else KCHK(launch_rmsnorm(s->ph, s->pxn, m->final_norm, s->total_rows, m->H, m->H, m->H, m->cfg.rms_eps, st));
-    GemmParams g = gps(s, s->pxn, m->H, m->lm_head, m->H, out, m->vocab, s->total_rows, m->vocab_p, m->H);
-    g.N_store = m->vocab; g.out_f32 = 1;
-    KCHK(launch_gemm(g, st));
-    return 0;
-}
-
-int emmax_last_logits(emmax_session* s, float* out, emmax_stream stream) {
-    if (!s || !out) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (!s->prefilled) return fail(EMMAX_ERR_STATE, "prefill has not run");
-    if (s->beam_K) return fail(EMMAX_ERR_STATE, "emmax_last_logits is not served while beams are on (bind a logits buffer: emmax_session_set_scores)");
-    return run_lm_head_step(s, s->cur_B, false, out, false, (hipStream_t)stream);
-}
-
-// the legacy / per-thread default streams cannot be captured: graph replays run on the session's own stream, ordered after
-// everything already queued on the caller's stream (enter) and before anything queued on it afterwards (leave)
-static int slot_enter(emmax_session* s, hipStream_t user, hipStream_t* st);
-static int slot_leave(emmax_session* s, hipStream_t user, hipStream_t st);
-
-int emmax_decode_step(emmax_session* s, emmax_stream stream) {
-    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (!s->prefilled) return fail(EMMAX_ERR_STATE, "decode before prefill");
-    if (s->beam_K) return fail(EMMAX_ERR_STATE, "with beams on the decode steps run inside emmax_generate");
-    s->dec_steps += 1;
-    if (emmax_tune().graph) {   // the step is a replay of the captured hipGraph (as in emmax_generate / emmax_slots_step)
-        hipStream_t user = (hipStream_t)stream, st;
-        int r = slot_enter(s, user, &st);
-        if (r) return r;
-        r = ensure_graph(s, s->cur_B, st) == 0 ? launch_graph_step(s, s->cur_B, st) : run_decode_step(s, s->cur_B, st);
-        if (r) return r;
-        return slot_leave(s, user, st);
-    }
-    s->last_step_graph = 0;   // eager mode: emmax_session_graph_active() reports what the steps really do; the graph is kept
-    return run_decode_step(s, s->cur_B, (hipStream_t)stream);
-}
-
-int emmax_set_current_tokens(emmax_session* s, const int32_t* toks, emmax_stream st) {
-    if (!s || !toks) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (!s->prefilled) return fail(EMMAX_ERR_STATE, "no active sequences");
-    if (s->slots_open) return fail(EMMAX_ERR_STATE, "caller-supplied tokens are not supported while request slots are open");
-    if (s->beam_K) return fail(EMMAX_ERR_STATE, "caller-supplied tokens are not supported while beams are on");
-    if (s->processing) return fail(EMMAX_ERR_STATE, "caller-supplied tokens are not supported while logits processing is on (they would be missing from the history)");
-    // the rows decode again (done flag cleared): the next step appends at position <= S_b + dec_steps, which must exist
-    int maxS = 0;
-    for (int b = 0; b < s->cur_B && b < (int)s->S.size(); ++b) maxS = std::max(maxS, s->S[b]);
-    if (maxS + s->dec_steps + 1 >= s->max_ctx)
-        return fail(EMMAX_ERR_NOMEM, "context %d + 1 reaches max_ctx %d: no room to decode a caller-supplied token", maxS + s->dec_steps, s->max_ctx);
-    KCHK(launch_set_tokens(s->cur_tok, toks, s->cur_B, s->done, s->stop_m, s->stop_after, s->max_new_d, s->max_out, (hipStream_t)st));
-    return 0;
-}
-
-int emmax_generate(emmax_session* s, int max_new, int stop_on_eos, int32_t* out_ids, int32_t* out_lens, emmax_stream stream) {
-    if (!s || !out_ids || !out_lens) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (!s->prefilled) return fail(EMMAX_ERR_STATE, "generate before prefill");
-    if (max_new < 1 || max_new > s->max_out) return fail(EMMAX_ERR_INVALID, "max_new_tokens %d outside 1..%d", max_new, s->max_out);
-    if (s->beam_K) {
-        if (!s->beam_ready || s->beam_forked) return fail(EMMAX_ERR_STATE, "with beams on emmax_generate runs once per prefill (the prefill must follow emmax_session_set_beams)");
-        for (int g = 0; g < s->beam_G; ++g)
-            if (!beam_pages_fit(s, s->S[g], max_new))
-                return fail(EMMAX_ERR_NOMEM, "group %d: context %d + %d new tokens x %d beams do not fit max_ctx %d / the %d pages of its rows", g, s->S[g], max_new,
-                            s->beam_K, s->max_ctx, s->beam_K * s->max_pages);
-    }
-    hipStream_t user = (hipStream_t)stream, st = user;
-    // the legacy / per-thread default streams cannot be captured: run the loop on the session's own stream, ordered
-    // after everything already queued on the caller's stream and before anything queued on it afterwards
-    const bool special = (uintptr_t)user <= 2;
-    if (special) {
-        st = s->own_stream;
-        HIPCHK(hipEventRecord(s->ev_in, user));
-        HIPCHK(hipStreamWaitEvent(st, s->ev_in, 0));
-    }
-    if (s->beam_K) {   // the first beam step from the prefill's logit rows, and the fork into G x K rows
-        const int rows = s->beam_G * s->beam_K, ld = std::min(s->max_batch, EMMAX_MAX_DECODE_BATCH);
-        s->beam_eos = stop_on_eos ? s->m->cfg.eos_id : -1;
-        s->beam_max_new = max_new;
-        KCHK(launch_set_ints(s->max_new_d, rows, max_new, st));
-        KCHK(launch_beam_reset(rows, s->beam_K, s->bm_run, s->bm_fin_score, s->bm_fin_flag, s->bm_fin_t, s->bm_fin_par, s->bm_fin_tok, s->bm_grp,
-                               s->bm_csrc, st));
-        const size_t n1 = (size_t)max_new * ld * 4;
-        HIPCHK(hipMemsetAsync(s->bm_tr_tok, 0xff, n1, st));
-        HIPCHK(hipMemsetAsync(s->bm_tr_par, 0xff, n1, st));
-        HIPCHK(hipMemsetAsync(s->bm_tr_score, 0, n1, st));
-        HIPCHK(hipMemsetAsync(s->bm_tr_lse, 0, n1, st));
-        HIPCHK(hipMemsetAsync(s->bm_tc_idx, 0xff, 2 * n1, st));
-        HIPCHK(hipMemsetAsync(s->bm_tc_acc, 0, 2 * n1, st));
-        if (s->scores_on) KCHK(launch_set_int((int32_t*)(s->score_words + 3), rows, st));
-        int r = launch_beam_finish(s, true, st);
-        if (r) return r;
-        for (int g = s->beam_G - 1; g >= 0; --g)
-            for (int k = 0; k < s->beam_K; ++k) s->S[g * s->beam_K + k] = s->S[g];
-        s->cur_B = rows;
-        s->beam_forked = true;
-        s->beam_ready = false;
-    }
-    const int B = s->cur_B;
-    if (!s->beam_K) KCHK(launch_set_ints(s->max_new_d, B, max_new, st));
-    const bool use_graph = (max_new > 2) && ensure_graph(s, B, st) == 0;
-    const int CHK = 16;
-    int32_t* done_host = s->pinned;
-    bool pending = false;
-    for (int i = 1; i < max_new; ++i) {
-        s->dec_steps += 1;
-        if (use_graph) {
-            int r = launch_graph_step(s, B, st);
-            if (r) return r;
-        } else {
-            int r = run_decode_step(s, B, st);
-            if (r) return r;
-        }
-        if (stop_on_eos && (i % CHK) == 0) {
-            if (pending) {   // the previous read-back is certainly complete once its event fired
-                HIPCHK(hipEventSynchronize(s->ev));
-                bool all = true;
-                for (int b = 0; b < B; ++b) all = all && (done_host[b] != 0);
-                if (all) { pending = false; break; }
-            }
-            HIPCHK(hipMemcpyAsync(done_host, s->done, B * 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipEventRecord(s->ev, st));
-            pending = true;
-        }
-    }
-    if (s->beam_K) {   // the kept hypotheses, best first per group, out of the token / parent tables
-        BeamResolveParams q;
-        memset(&q, 0, sizeof(q));
-        q.rows = B; q.K = s->beam_K; q.max_out = s->max_out; q.max_new = max_new; q.tr_ld = std::min(s->max_batch, EMMAX_MAX_DECODE_BATCH);
-        q.pad_id = s->m->cfg.pad_id;
-        q.fin_t = s->bm_fin_t; q.fin_par = s->bm_fin_par; q.fin_tok = s->bm_fin_tok; q.tr_tok = s->bm_tr_tok; q.tr_par = s->bm_tr_par;
-        q.fin_score = s->bm_fin_score; q.seq = s->out_ids; q.bidx = s->bm_res_bidx; q.len = s->bm_res_len; q.score = s->bm_res_score;
-        KCHK(launch_beam_resolve(q, st));
-    }
-    HIPCHK(hipMemcpy2DAsync(out_ids, (size_t)max_new * 4, s->out_ids, (size_t)s->max_out * 4, (size_t)max_new * 4, B,
-                            hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(out_lens, s->beam_K ? s->bm_res_len : s->n_out, B * 4, hipMemcpyDeviceToDevice, st));
-    if (special) {
-        HIPCHK(hipEventRecord(s->ev_out, st));
-        HIPCHK(hipStreamWaitEvent(user, s->ev_out, 0));
-    }
-    return 0;
-}
-
-// ---- early exit + slot serving (continuous batching) ----------------------------------------------------------------
-// the legacy / per-thread default streams cannot be captured: slot calls run on the session's own stream, ordered after
-// everything already queued on the caller's stream (enter) and before anything queued on it afterwards (leave)
-static int slot_enter(emmax_session* s, hipStream_t user, hipStream_t* st) {
-    *st = user;
-    if ((uintptr_t)user <= 2) {
-        *st = s->own_stream;
-        HIPCHK(hipEventRecord(s->ev_in, user));
-        HIPCHK(hipStreamWaitEvent(*st, s->ev_in, 0));
-    }
-    return 0;
-}
-static int slot_leave(emmax_session* s, hipStream_t user, hipStream_t st) {
-    if (st != user) {
-        HIPCHK(hipEventRecord(s->ev_out, st));
-        HIPCHK(hipStreamWaitEvent(user, s->ev_out, 0));
-    }
-    return 0;
-}
-
-int emmax_session_set_stop(emmax_session* s, const int32_t* trigger_ids, int n_trigger, int n_after, emmax_stream stream) {
-    if (!s || (n_trigger > 0 && !trigger_ids)) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (n_trigger < 0 || n_trigger > EMMAX_MAX_STOP_IDS || n_after < 0)
-        return fail(EMMAX_ERR_INVALID, "stop rule: %d trigger ids (max %d), %d tokens after", n_trigger, EMMAX_MAX_STOP_IDS, n_after);
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    int32_t* h = s->pinned + 2048;
-    HIPCHK(hipStreamSynchronize(st));   // the pinned staging words may still feed an earlier upload
-    for (int i = 0; i < n_trigger; ++i) h[i] = trigger_ids[i];
-    h[EMMAX_MAX_STOP_IDS] = n_trigger;
-    h[EMMAX_MAX_STOP_IDS + 1] = n_after;
-    if (n_trigger > 0) HIPCHK(hipMemcpyAsync(s->stop_ids, h, n_trigger * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(s->stop_cfg, h + EMMAX_MAX_STOP_IDS, 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return slot_leave(s, user, st);
-}
-
-int emmax_slots_open(emmax_session* s, int n_slots, emmax_stream stream) {
-    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (s->beam_K) return fail(EMMAX_ERR_STATE, "request slots are not served while beams are on (emmax_session_clear_beams)");
-    const int max_rows = s->exact ? EMMAX_MAX_DECODE_BATCH : model_max_decode_batch(s->m);
-    if (n_slots < 1 || n_slots > s->max_batch || n_slots > max_rows)
-        return fail(EMMAX_ERR_INVALID, "%d slots outside 1..min(max_batch=%d, %d)", n_slots, s->max_batch, max_rows);
-    if (n_slots >= EMMAX_MFMA_MIN_BATCH && !s->m->aux_built)
-        return fail(EMMAX_ERR_STATE, "%d slots decode on the fragment-major weight copies: call emmax_model_build_aux first", n_slots);
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    KCHK(launch_slots_idle(n_slots, s->cur_tok, s->ctx_len, s->done, s->n_out, s->m->cfg.pad_id, st));
-    s->cur_B = n_slots;
-    s->S.assign(s->rows_total, 0);
-    s->slots_open = true;
-    s->scores_on = false;   // no scores in slot serving (the bound buffers were a generate call's)
-    s->prefilled = true;   // decode steps are legal: idle slots are rows that are already done
-    return slot_leave(s, user, st);
-}
-
-int emmax_slot_prefill(emmax_session* s, int slot, const int32_t* ids, int len, const void* patches, int max_new, emmax_stream stream) {
-    if (!s || !ids) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slot_prefill before emmax_slots_open");
-    if (slot < 0 || slot >= s->cur_B) return fail(EMMAX_ERR_INVALID, "slot %d outside 0..%d", slot, s->cur_B - 1);
-    if (max_new < 1 || max_new > s->max_out) return fail(EMMAX_ERR_INVALID, "max_new_tokens %d outside 1..%d", max_new, s->max_out);
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    r = run_prefill(s, ids, &len, 1, len, patches, st, slot);
-    if (r) return r;
-    KCHK(launch_set_ints(s->max_new_d + slot, 1, max_new, st));
-    return slot_leave(s, user, st);
-}
-
-int emmax_slots_prefill(emmax_session* s, int slot0, int n, const int32_t* ids, int P_max, const int32_t* lens_host, const void* patches,
-                        const int32_t* max_new_host, emmax_stream stream) {
-    if (!s || !ids || !lens_host || !max_new_host) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slots_prefill before emmax_slots_open");
-    if (n < 1 || slot0 < 0 || slot0 + n > s->cur_B) return fail(EMMAX_ERR_INVALID, "slots %d..%d outside 0..%d", slot0, slot0 + n - 1, s->cur_B - 1);
-    for (int i = 0; i < n; ++i)
-        if (max_new_host[i] < 1 || max_new_host[i] > s->max_out)
-            return fail(EMMAX_ERR_INVALID, "slot %d: max_new_tokens %d outside 1..%d", slot0 + i, max_new_host[i], s->max_out);
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    r = run_prefill(s, ids, lens_host, n, P_max, patches, st, slot0);   // one packed pass over the n requests (ragged lengths)
-    if (r) return r;
-    for (int i = 0; i < n; ++i) KCHK(launch_set_ints(s->max_new_d + slot0 + i, 1, max_new_host[i], st));
-    return slot_leave(s, user, st);
-}
-
-int emmax_slots_prefill_staged(emmax_session* s, int n, const int32_t* ids, int P_max, const int32_t* lens_host, const void* patches,
-                               const int32_t* max_new_host, emmax_stream stream) {
-    if (!s || !ids || !lens_host || !max_new_host) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slots_prefill_staged before emmax_slots_open");
-    if (s->n_stg == 0)
-        return fail(EMMAX_ERR_INVALID, "session created without staging rows: use emmax_session_create_ex(..., stage_rows > 0) (a plain emmax_session_create gives none since ABI 4)");
-    if (n < 1 || n > s->n_stg)
-        return fail(EMMAX_ERR_INVALID, "%d staged requests outside 1..%d (the session's staging rows: emmax_session_create_ex)", n, s->n_stg);
-    if ((uintptr_t)stream <= 2) return fail(EMMAX_ERR_INVALID, "a staged prefill needs its own (non-default) stream: it runs beside the decode steps");
-    for (int i = 0; i < n; ++i)
-        if (max_new_host[i] < 1 || max_new_host[i] > s->max_out)
-            return fail(EMMAX_ERR_INVALID, "staged request %d: max_new_tokens %d outside 1..%d", i, max_new_host[i], s->max_out);
-    hipStream_t st = (hipStream_t)stream;
-    int r = run_prefill(s, ids, lens_host, n, P_max, patches, st, s->stg0);
-    if (r) return r;
-    for (int i = 0; i < n; ++i) KCHK(launch_set_ints(s->max_new_d + s->stg0 + i, 1, max_new_host[i], st));
-    return 0;
-}
-
-int emmax_slots_commit(emmax_session* s, const int32_t* staged_idx_host, const int32_t* slots_host, int n, emmax_stream stream) {
-    if (!s || !slots_host || !staged_idx_host) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slots_commit before emmax_slots_open");
-    if (n < 1 || n > s->n_stg) return fail(EMMAX_ERR_INVALID, "%d commits outside 1..%d", n, s->n_stg);
-    CommitParams c;
-    memset(&c, 0, sizeof(c));
-    for (int i = 0; i < n; ++i) {
-        if (slots_host[i] < 0 || slots_host[i] >= s->cur_B) return fail(EMMAX_ERR_INVALID, "slot %d outside 0..%d", slots_host[i], s->cur_B - 1);
-        if (staged_idx_host[i] < 0 || staged_idx_host[i] >= s->n_stg) return fail(EMMAX_ERR_INVALID, "staged request %d outside 0..%d", staged_idx_host[i], s->n_stg - 1);
-        for (int j = 0; j < i; ++j)
-            if (slots_host[j] == slots_host[i] || staged_idx_host[j] == staged_idx_host[i]) return fail(EMMAX_ERR_INVALID, "slot / staged request named twice");
-        c.slot[i] = slots_host[i];
-        c.src[i] = s->stg0 + staged_idx_host[i];
-    }
-    c.n = n; c.max_pages = s->max_pages; c.max_out = s->max_out;
-    c.cur_tok = s->cur_tok; c.ctx_len = s->ctx_len; c.done = s->done; c.n_out = s->n_out; c.max_new = s->max_new_d;
-    c.stop_m = s->stop_m; c.stop_after = s->stop_after; c.out_ids = s->out_ids; c.page_table = s->page_table;
-    if (s->sampling) {
-        c.temperature = s->samp_t; c.top_k = s->samp_k; c.top_p = s->samp_p; c.seed = s->samp_seed; c.subseq = s->samp_sub;
-        c.logprob = s->logprob;
-    }
-    if (s->processing) {
-        c.penalty = s->proc_pen; c.ngram = s->proc_ng; c.min_new = s->proc_mn; c.hist = s->hist; c.hist_len = s->hist_len;
-        c.max_prompt = s->max_prompt;
-    }
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    KCHK(launch_slots_commit(c, st));
-    for (int i = 0; i < n; ++i) s->S[slots_host[i]] = s->S[s->stg0 + staged_idx_host[i]];
-    return slot_leave(s, user, st);
-}
-
-int emmax_slots_step(emmax_session* s, int n_steps, emmax_stream stream) {
-    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slots_step before emmax_slots_open");
-    if (n_steps < 1) return fail(EMMAX_ERR_INVALID, "n_steps %d < 1", n_steps);
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    const int B = s->cur_B;
-    const bool use_graph = ensure_graph(s, B, st) == 0;
-    for (int i = 0; i < n_steps; ++i) {
-        r = use_graph ? launch_graph_step(s, B, st) : run_decode_step(s, B, st);
-        if (r) return r;
-    }
-    return slot_leave(s, user, st);
-}
-
-int emmax_slots_state(emmax_session* s, int32_t* done_out, int32_t* n_out_out, emmax_stream stream) {
-    if (!s || !done_out || !n_out_out) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slots_state before emmax_slots_open");
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    HIPCHK(hipMemcpyAsync(done_out, s->done, s->cur_B * 4, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(n_out_out, s->n_out, s->cur_B * 4, hipMemcpyDeviceToDevice, st));
-    return slot_leave(s, user, st);
-}
-
-int emmax_slot_output(emmax_session* s, int slot, int32_t* ids_out, int n, emmax_stream stream) {
-    if (!s || !ids_out) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slot_output before emmax_slots_open");
-    if (slot < 0 || slot >= s->cur_B || n < 0 || n > s->max_out) return fail(EMMAX_ERR_INVALID, "slot %d / %d ids out of range", slot, n);
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    if (n > 0) HIPCHK(hipMemcpyAsync(ids_out, s->out_ids + (size_t)slot * s->max_out, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-    return slot_leave(s, user, st);
-}
-
-int emmax_slot_release(emmax_session* s, int slot, emmax_stream stream) {
-    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slot_release before emmax_slots_open");
-    if (slot < 0 || slot >= s->cur_B) return fail(EMMAX_ERR_INVALID, "slot %d outside 0..%d", slot, s->cur_B - 1);
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    KCHK(launch_slots_idle(1, s->cur_tok + slot, s->ctx_len + slot, s->done + slot, s->n_out + slot, s->m->cfg.pad_id, st));
-    s->S[slot] = 0;
-    return slot_leave(s, user, st);
-}
-
-// ---- sampling in the decode step (ABI 7) ------------------------------------------------------------------------------
-// rows r0 .. r0 + n of the session (decode rows, or the staging rows from stg0): host values checked here, uploaded through the pinned
-// words 2112.. (emmax_session_set_stop uses 2048 .. 2065, the done read-back of emmax_generate the first 64)
-static int set_sampling_rows(emmax_session* s, int r0, int n, const float* T, const int32_t* top_k, const float* top_p, const uint64_t* seed,
-                             const uint32_t* subseq, hipStream_t st) {
-    if (s->m->vocab > EMMAX_SAMPLE_MAX_V) return fail(EMMAX_ERR_INVALID, "sampling takes vocabularies of up to %d entries (%d)", EMMAX_SAMPLE_MAX_V, s->m->vocab);
-    for (int i = 0; i < n; ++i) {
-        if (!std::isfinite(T[i]) || T[i] < 0.f) return fail(EMMAX_ERR_INVALID, "row %d: temperature %g (finite and >= 0)", r0 + i, (double)T[i]);
-        if (top_k[i] < 0) return fail(EMMAX_ERR_INVALID, "row %d: top_k %d (>= 0)", r0 + i, top_k[i]);
-        if (!(top_p[i] > 0.f && top_p[i] <= 1.f)) return fail(EMMAX_ERR_INVALID, "row %d: top_p %g (0 < top_p <= 1)", r0 + i, (double)top_p[i]);
-    }
-    char* h = (char*)(s->pinned + 2112);
-    HIPCHK(hipStreamSynchronize(st));   // the pinned staging words may still feed an earlier upload
-    for (int c0 = 0; c0 < n; c0 += 256) {
-        const int c = std::min(256, n - c0);
-        float* hT = (float*)h;
-        int32_t* hk = (int32_t*)(h + 1024);
-        float* hp = (float*)(h + 2048);
-        uint32_t* hs = (uint32_t*)(h + 3072);
-        uint64_t* hseed = (uint64_t*)(h + 4096);
-        for (int i = 0; i < c; ++i) {
-            hT[i] = T[c0 + i]; hk[i] = top_k[c0 + i]; hp[i] = top_p[c0 + i]; hs[i] = subseq[c0 + i]; hseed[i] = seed[c0 + i];
-        }
-        const int r = r0 + c0;
-        HIPCHK(hipMemcpyAsync(s->samp_t + r, hT, c * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(s->samp_k + r, hk, c * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(s->samp_p + r, hp, c * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(s->samp_sub + r, hs, c * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(s->samp_seed + r, hseed, c * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    s->sampling = true;
-    return 0;
-}
-
-int emmax_session_set_sampling(emmax_session* s, int row0, int n, const float* temperature_host, const int32_t* top_k_host, const float* top_p_host,
-                               const uint64_t* seed_host, const uint32_t* subseq_host, emmax_stream stream) {
-    if (!s || !temperature_host || !top_k_host || !top_p_host || !seed_host || !subseq_host) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (n < 1 || row0 < 0 || row0 + n > s->max_batch) return fail(EMMAX_ERR_INVALID, "rows %d..%d outside 0..%d", row0, row0 + n - 1, s->max_batch - 1);
-    if (s->beam_K) return fail(EMMAX_ERR_STATE, "sampling is not available while beams are on");
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    r = set_sampling_rows(s, row0, n, temperature_host, top_k_host, top_p_host, seed_host, subseq_host, st);
-    if (r) return r;
-    return slot_leave(s, user, st);
-}
-
-int emmax_slots_set_sampling_staged(emmax_session* s, int n, const float* temperature_host, const int32_t* top_k_host, const float* top_p_host,
-                                    const uint64_t* seed_host, const uint32_t* subseq_host, emmax_stream stream) {
-    if (!s || !temperature_host || !top_k_host || !top_p_host || !seed_host || !subseq_host) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (n < 1 || n > s->n_stg) return fail(EMMAX_ERR_INVALID, "%d staged requests outside 1..%d (the session's staging rows)", n, s->n_stg);
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    r = set_sampling_rows(s, s->stg0, n, temperature_host, top_k_host, top_p_host, seed_host, subseq_host, st);
-    if (r) return r;
-    return slot_leave(s, user, st);
-}
-
-int emmax_session_clear_sampling(emmax_session* s, emmax_stream stream) {
-    (void)stream;
-    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
-    s->sampling = false;
-    return 0;
-}
-
-int emmax_session_sampling(const emmax_session* s) { return s ? (s->sampling ? 1 : 0) : -1; }
-
-int emmax_session_logprobs(emmax_session* s, int max_new, float* out_dev, emmax_stream stream) {
-    if (!s || !out_dev) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (!s->sampling) return fail(EMMAX_ERR_STATE, "log-probabilities exist in a sampling session only (emmax_session_set_sampling)");
-    if (!s->prefilled) return fail(EMMAX_ERR_STATE, "no generation has run");
-    if (max_new < 1 || max_new > s->max_out) return fail(EMMAX_ERR_INVALID, "max_new_tokens %d outside 1..%d", max_new, s->max_out);
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    HIPCHK(hipMemcpy2DAsync(out_dev, (size_t)max_new * 4, s->logprob, (size_t)s->max_out * 4, (size_t)max_new * 4, s->cur_B,
-                            hipMemcpyDeviceToDevice, st));
-    return slot_leave(s, user, st);
-}
-
-int emmax_slot_logprobs(emmax_session* s, int slot, float* out_dev, int n, emmax_stream stream) {
-    if (!s || !out_dev) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (!s->sampling) return fail(EMMAX_ERR_STATE, "log-probabilities exist in a sampling session only (emmax_session_set_sampling)");
-    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slot_logprobs before emmax_slots_open");
-    if (slot < 0 || slot >= s->cur_B || n < 0 || n > s->max_out) return fail(EMMAX_ERR_INVALID, "slot %d / %d values out of range", slot, n);
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    if (n > 0) HIPCHK(hipMemcpyAsync(out_dev, s->logprob + (size_t)slot * s->max_out, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-    return slot_leave(s, user, st);
-}
-
-// ---- logits processing and scores in the decode step (ABI 8) --------------------------------------------------------------
-// rows r0 .. r0 + n of the session: host values checked here, uploaded through the pinned words 2112.. (as set_sampling_rows)
-static int set_processing_rows(emmax_session* s, int r0, int n, const float* pen, const int32_t* ng, const int32_t* mn, hipStream_t st) {
-    if (s->m->vocab > EMMAX_SAMPLE_MAX_V) return fail(EMMAX_ERR_INVALID, "logits processing takes vocabularies of up to %d entries (%d)", EMMAX_SAMPLE_MAX_V, s->m->vocab);
-    for (int i = 0; i < n; ++i) {
-        if (!std::isfinite(pen[i]) || !(pen[i] > 0.f)) return fail(EMMAX_ERR_INVALID, "row %d: repetition penalty %g (finite and > 0)", r0 + i, (double)pen[i]);
-        if (ng[i] < 0 || ng[i] > EMMAX_MAX_NGRAM) return fail(EMMAX_ERR_INVALID, "row %d: no_repeat_ngram_size %d outside 0..%d", r0 + i, ng[i], EMMAX_MAX_NGRAM);
-        if (mn[i] < 0) return fail(EMMAX_ERR_INVALID, "row %d: min_new_tokens %d (>= 0)", r0 + i, mn[i]);
-    }
-    char* h = (char*)(s->pinned + 2112);
-    HIPCHK(hipStreamSynchronize(st));   // the pinned staging words may still feed an earlier upload
-    for (int c0 = 0; c0 < n; c0 += 256) {
-        const int c = std::min(256, n - c0);
-        float* hp = (float*)h;
-        int32_t* hn = (int32_t*)(h + 1024);
-        int32_t* hm = (int32_t*)(h + 2048);
-        for (int i = 0; i < c; ++i) { hp[i] = pen[c0 + i]; hn[i] = ng[c0 + i]; hm[i] = mn[c0 + i]; }
-        const int r = r0 + c0;
-        HIPCHK(hipMemcpyAsync(s->proc_pen + r, hp, c * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(s->proc_ng + r, hn, c * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(s->proc_mn + r, hm, c * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    s->processing = true;
-    return 0;
-}
-
-int emmax_session_set_processing(emmax_session* s, int row0, int n, const float* penalty_host, const int32_t* ngram_host, const int32_t* min_new_host,
-                                 emmax_stream stream) {
-    if (!s || !penalty_host || !ngram_host || !min_new_host) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (n < 1 || row0 < 0 || row0 + n > s->max_batch) return fail(EMMAX_ERR_INVALID, "rows %d..%d outside 0..%d", row0, row0 + n - 1, s->max_batch - 1);
-    if (s->beam_K) return fail(EMMAX_ERR_STATE, "logits processing is not available while beams are on");
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    r = set_processing_rows(s, row0, n, penalty_host, ngram_host, min_new_host, st);
-    if (r) return r;
-    return slot_leave(s, user, st);
-}
-
-int emmax_slots_set_processing_staged(emmax_session* s, int n, const float* penalty_host, const int32_t* ngram_host, const int32_t* min_new_host,
-                                      emmax_stream stream) {
-    if (!s || !penalty_host || !ngram_host || !min_new_host) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (n < 1 || n > s->n_stg) return fail(EMMAX_ERR_INVALID, "%d staged requests outside 1..%d (the session's staging rows)", n, s->n_stg);
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    r = set_processing_rows(s, s->stg0, n, penalty_host, ngram_host, min_new_host, st);
-    if (r) return r;
-    return slot_leave(s, user, st);
-}
-
-int emmax_session_clear_processing(emmax_session* s, emmax_stream stream) {
-    (void)stream;
-    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
-    s->processing = false;
-    return 0;
-}
-
-int emmax_session_processing(const emmax_session* s) { return s ? (s->processing ? 1 : 0) : -1; }
-
-int emmax_session_set_scores(emmax_session* s, float* scores_dev, float* logits_dev, int max_new, emmax_stream stream) {
-    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (s->slots_open) return fail(EMMAX_ERR_STATE, "scores are not kept in slot serving (emmax_slots_open)");
-    if (!scores_dev && !logits_dev) {
-        s->scores_on = false;
-        s->scores_has_scores = false;
-        return 0;
-    }
-    if (s->beam_K && scores_dev) return fail(EMMAX_ERR_STATE, "processed scores are not kept while beams are on (bind the raw logits buffer only)");
-    if (s->m->vocab > EMMAX_SAMPLE_MAX_V) return fail(EMMAX_ERR_INVALID, "scores take vocabularies of up to %d entries (%d)", EMMAX_SAMPLE_MAX_V, s->m->vocab);
-    if (max_new < 1 || max_new > s->max_out) return fail(EMMAX_ERR_INVALID, "max_new_tokens %d outside 1..%d", max_new, s->max_out);
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    uint64_t* h = (uint64_t*)(s->pinned + 2112);
-    HIPCHK(hipStreamSynchronize(st));   // the pinned staging words may still feed an earlier upload
-    h[0] = (uint64_t)(uintptr_t)scores_dev; h[1] = (uint64_t)(uintptr_t)logits_dev; h[2] = (uint64_t)max_new; h[3] = 0;   // rows: set by the next prefill
-    HIPCHK(hipMemcpyAsync(s->score_words, h, 4 * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    s->scores_on = true;
-    s->scores_has_scores = scores_dev != nullptr;
-    s->scores_rows = 0;
-    return slot_leave(s, user, st);
-}
-
-// ---- beam search in the decode step (ABI 9) ---------------------------------------------------------------------------
-int emmax_session_set_beams(emmax_session* s, int num_beams, double length_penalty, int early_stopping, emmax_stream stream) {
-    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
-    const int max_rows = s->exact ? EMMAX_MAX_DECODE_BATCH : model_max_decode_batch(s->m);
-    if (num_beams < 2 || num_beams > EMMAX_MAX_BEAMS || num_beams > s->max_batch || num_beams > max_rows)
-        return fail(EMMAX_ERR_INVALID, "num_beams %d outside 2..min(%d, max_batch=%d, %d)", num_beams, EMMAX_MAX_BEAMS, s->max_batch, max_rows);
-    if (!std::isfinite(length_penalty)) return fail(EMMAX_ERR_INVALID, "length_penalty must be finite");
-    if (early_stopping < 0 || early_stopping > 2) return fail(EMMAX_ERR_INVALID, "early_stopping %d: 0 False, 1 True, 2 never", early_stopping);
-    if (s->m->vocab > EMMAX_SAMPLE_MAX_V || s->m->vocab < 2 * num_beams)
-        return fail(EMMAX_ERR_INVALID, "beams take vocabularies of %d..%d entries (%d)", 2 * num_beams, EMMAX_SAMPLE_MAX_V, s->m->vocab);
-    if (s->slots_open) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while request slots are open");
-    if (s->sampling || s->processing) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while sampling or logits processing is on");
-    if (s->scores_on && s->scores_has_scores) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while a scores buffer is bound");
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    std::vector<float> pw((size_t)s->max_out + 1);
-    for (size_t n = 0; n < pw.size(); ++n) pw[n] = (float)pow((double)n, length_penalty);
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipMemcpy(s->bm_pw, pw.data(), pw.size() * 4, hipMemcpyHostToDevice));
-    s->beam_K = num_beams; s->beam_es = early_stopping; s->beam_lp_pos = length_penalty > 0.0 ? 1 : 0;
-    s->beam_G = 0; s->beam_forked = false; s->beam_ready = false;
-    s->prefilled = false;   // rows of an earlier batch do not continue as beams
-    return slot_leave(s, user, st);
-}
-
-int emmax_session_clear_beams(emmax_session* s, emmax_stream stream) {
-    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (!s->beam_K) return 0;
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    KCHK(launch_beam_pages(s->page_table, s->rows_total, s->max_pages, 1, st));   // static assignment again: row b owns its own pages
-    s->beam_K = 0; s->beam_G = 0; s->beam_forked = false; s->beam_ready = false;
-    s->prefilled = false;
-    return slot_leave(s, user, st);
-}
-
-int emmax_session_beams(const emmax_session* s) { return s ? s->beam_K : -1; }
-
-int emmax_session_beam_result(emmax_session* s, int max_new, int32_t* seq_dev, int32_t* len_dev, float* score_dev, int32_t* bidx_dev, emmax_stream stream) {
-    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (!s->beam_K || !s->beam_forked) return fail(EMMAX_ERR_STATE, "no beam generation to report");
-    if (max_new < 1 || max_new > s->beam_max_new) return fail(EMMAX_ERR_INVALID, "max_new %d outside 1..%d (the generation's)", max_new, s->beam_max_new);
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    const int rows = s->beam_G * s->beam_K;
-    if (seq_dev) HIPCHK(hipMemcpy2DAsync(seq_dev, (size_t)max_new * 4, s->out_ids, (size_t)s->max_out * 4, (size_t)max_new * 4, rows, hipMemcpyDeviceToDevice, st));
-    if (bidx_dev) HIPCHK(hipMemcpy2DAsync(bidx_dev, (size_t)max_new * 4, s->bm_res_bidx, (size_t)s->max_out * 4, (size_t)max_new * 4, rows, hipMemcpyDeviceToDevice, st));
-    if (len_dev) HIPCHK(hipMemcpyAsync(len_dev, s->bm_res_len, rows * 4, hipMemcpyDeviceToDevice, st));
-    if (score_dev) HIPCHK(hipMemcpyAsync(score_dev, s->bm_res_score, rows * 4, hipMemcpyDeviceToDevice, st));
-    return slot_leave(s, user, st);
-}
-
-int emmax_session_beam_trace(emmax_session* s, int max_new, int32_t* tok_dev, int32_t* parent_dev, float* score_dev, float* lse_dev, int32_t* cand_idx_dev,
-                             float* cand_acc_dev, emmax_stream stream) {
-    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (!s->beam_K || !s->beam_forked) return fail(EMMAX_ERR_STATE, "no beam generation to report");
-    if (max_new < 1 || max_new > s->beam_max_new) return fail(EMMAX_ERR_INVALID, "max_new %d outside 1..%d (the generation's)", max_new, s->beam_max_new);
-    hipStream_t user = (hipStream_t)stream, st;
-    int r = slot_enter(s, user, &st);
-    if (r) return r;
-    const size_t rows = (size_t)s->beam_G * s->beam_K, ld = (size_t)std::min(s->max_batch, EMMAX_MAX_DECODE_BATCH);
-    auto out = [&](void* dst, const void* src, size_t mul) -> hipError_t {
-        return dst ? hipMemcpy2DAsync(dst, rows * mul * 4, src, ld * mul * 4, rows * mul * 4, (size_t)max_new, hipMemcpyDeviceToDevice, st) : hipSuccess;
-    };
-    HIPCHK(out(tok_dev, s->bm_tr_tok, 1));
-    HIPCHK(out(parent_dev, s->bm_tr_par, 1));
-    HIPCHK(out(score_dev, s->bm_tr_score, 1));
-    HIPCHK(out(lse_dev, s->bm_tr_lse, 1));
-    HIPCHK(out(cand_idx_dev, s->bm_tc_idx, 2));
-    HIPCHK(out(cand_acc_dev, s->bm_tc_acc, 2));
-    return slot_leave(s, user, st);
-}
-
-int emmax_session_graph_active(emmax_session* s) {
-    if (s && !s->graph_exec && !s->graph_err.empty()) g_err = s->graph_err;   // why the capture was refused
-    return s && s->graph_exec && s->last_step_graph ? 1 : 0;
-}
-
-int emmax_profile_decode_stage(emmax_session* s, int stage, int reps, float* avg_us, emmax_stream stream) {
-    if (!s || !avg_us || reps < 1) return fail(EMMAX_ERR_INVALID, "bad argument");
-    if (!s->prefilled) return fail(EMMAX_ERR_STATE, "profile needs an active (prefilled) session");
-    hipStream_t st = (hipStream_t)stream;
-    emmax_model* m = s->m;
-    const int B = s->cur_B, nl = m->cfg.n_layers;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    int launches = 0, r = 0;
-    // one untimed sweep (instruction cache, clocks), then `reps` timed sweeps over all layers: every launch streams a
-    // different layer's weights, so nothing is served from the 256 MiB Infinity Cache that a real step would not get
-    for (int pass = 0; pass < 2 && r == 0; ++pass) {
-        if (pass == 1) HIPCHK(hipEventRecord(e0, st));
-        const int n = pass == 0 ? 1 : reps;
-        for (int i = 0; i < n && r == 0; ++i) {
-            if (stage == STAGE_LMHEAD) {
-                r = run_lm_head_step(s, B, false, nullptr, false, st);
-                launches += pass;
-            } else {
-                for (int li = 0; li < nl && r == 0; ++li) {
-                    r = run_decode_stage(s, B, li, stage, st);
-                    launches += pass;
-                }
-            }
-        }
-    }
-    if (r) return r;
-    HIPCHK(hipEventRecord(e1, st));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    *avg_us = ms * 1000.0f / (float)launches;
-    return 0;
-}
-
-// ---- single-kernel entry points --------------------------------------------------------------------------------------
-int emmax_op_sample(const float* logits, int ld, int B, int V, const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seed,
-                    const uint32_t* subseq, const int32_t* step, int32_t* tok_out, float* logprob_out, emmax_stream stream) {
-    if (!logits || !temperature || !top_k || !top_p || !seed || !subseq || !step || !tok_out || !logprob_out) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (B < 1 || V < 1 || V > EMMAX_SAMPLE_MAX_V || ld < V)
-        return fail(EMMAX_ERR_INVALID, "emmax_op_sample: B %d (>= 1), V %d (1..%d), ld %d (>= V)", B, V, EMMAX_SAMPLE_MAX_V, ld);
-    SampleParams p;
-    memset(&p, 0, sizeof(p));
-    p.logits = logits; p.ld = ld; p.V = V; p.temperature = temperature; p.top_k = top_k; p.top_p = top_p; p.seed = seed; p.subseq = subseq;
-    p.step = step; p.tok_out = tok_out; p.logprob_out = logprob_out;
-    KCHK(launch_sample(p, B, (hipStream_t)stream));
-    return 0;
-}
-int emmax_op_gemm(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K, const void* bias, int act,
-                  const void* scale, const void* residual, int ldr, int out_f32, emmax_stream st) {
-    GemmParams p = gp(A, lda, W, ldw, C, ldc, M, N, K);
-    p.bias = bias; p.act = act; p.scale = scale; p.residual = residual; p.ldr = ldr; p.out_f32 = out_f32;
-    int r = launch_gemm(p, (hipStream_t)st);
-    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_gemm: unsupported shape (K%%64, N%%128, ld%%8) or launch failure");
-    return 0;
-}
-int emmax_op_gemm_splitk(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K, const void* bias, int act,
-                         const void* scale, const void* residual, int ldr, int out_f32, int ksplit, void* ws, int64_t ws_bytes,
-                         emmax_stream st) {
-    GemmParams p = gp(A, lda, W, ldw, C, ldc, M, N, K);
-    p.bias = bias; p.act = act; p.scale = scale; p.residual = residual; p.ldr = ldr; p.out_f32 = out_f32;
-    p.ws = (float*)ws; p.ws_bytes = ws_bytes;
-    // ksplit = 0: the launch plan of a session stage with this scratch (whole tiles, split-K, or a column remainder through split-K)
-    int r = ksplit == 0 ? launch_gemm(p, (hipStream_t)st) : launch_gemm_splitk(p, ksplit, (hipStream_t)st, emmax_tune().gemm_sk_big > 0 ? 1 : 0);   // (tools: explicit slices, geometry by switch)
-    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID,
-                       "emmax_op_gemm_splitk: unsupported (ksplit = 0 or 2 <= ksplit <= K/64, ws >= ksplit*M*N*4 bytes, K%%64, N%%128; SwiGLU: bf16 output)");
-    return 0;
-}
-int emmax_gemm_plan(int M, int N, int K, int act, int out_f32, int has_ln, int has_residual, int with_norm, int64_t ws_bytes, char* text_out,
-                    int text_len) {
-    if (!text_out || text_len < 16) return fail(EMMAX_ERR_INVALID, "emmax_gemm_plan: text buffer of at least 16 bytes");
-    void* const any = (void*)(uintptr_t)256;   // the plan looks at sizes, alignments and which operands exist -- never through a pointer
-    GemmParams p = gp(any, K, any, K, any, act == 2 ? N / 2 : N, M, N, K);
-    p.act = act; p.out_f32 = out_f32;
-    if (has_residual) { p.residual = any; p.ldr = N; p.res_f32 = has_residual == 2; }   // 2: the fp32 residual stream (with out_f32)
-    if (has_ln) { p.ln_stats = (const float*)any; p.ln_s = (const float*)any; p.ln_c = (const float*)any; }
-    if (ws_bytes > 0) { p.ws = (float*)any; p.ws_bytes = ws_bytes; }
-    if (with_norm) { p.norm_w = any; p.norm_out = any; p.ld_norm = N; p.norm_eps = 1e-5f; }
-    if (with_norm && !gemm_fuses_norm(p)) { p.norm_w = nullptr; p.norm_out = nullptr; }   // (what the prefill does: a separate norm launch)
-    const int r = gemm_plan_describe(p, text_out, text_len);
-    if (r < 0) return fail(EMMAX_ERR_INVALID, "emmax_gemm_plan: unsupported shape (K%%64, N%%128)");
-    return 0;
-}
-int emmax_op_gemm_ln(const void* X, int ldx, void* W, int ldw, void* C, int ldc, int M, int N, int K, const void* gamma, const void* beta,
-                     const void* bias, float eps, int act, float* stats_ws, float* ln_s_ws, float* ln_c_ws, emmax_stream stream) {
-    if (!X || !W || !C || !gamma || !stats_ws || !ln_s_ws || !ln_c_ws) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_ln: null argument");
-    if (((uintptr_t)stats_ws & 7) || (((uintptr_t)ln_s_ws | (uintptr_t)ln_c_ws) & 3))   // (mean, rstd) pairs are read as 8 bytes
-        return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_ln: workspaces must be 8-byte (stats) / 4-byte (ln_s, ln_c) aligned");
-    hipStream_t st = (hipStream_t)stream;
-    KCHK(launch_ln_fold(W, ldw, N, K, gamma, beta, bias, ln_s_ws, ln_c_ws, st));
-    KCHK(launch_row_stats(X, stats_ws, M, K, ldx, eps, st));
-    GemmParams p = gp(X, ldx, W, ldw, C, ldc, M, N, K);
-    p.act = act; p.ln_stats = stats_ws; p.ln_s = ln_s_ws; p.ln_c = ln_c_ws;
-    int r = launch_gemm(p, st);
-    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_gemm_ln: unsupported shape (K%%64, N%%128, ld%%8, act in {0,1})");
-    return 0;
-}
-int emmax_op_layernorm(const void* x, void* y, const void* w, const void* b, int rows, int D, float eps, emmax_stream st) {
-    int r = launch_layernorm(x, y, w, b, rows, D, D, D, eps, (hipStream_t)st);
-    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_layernorm: unsupported shape");
-    return 0;
-}
-int emmax_op_rmsnorm(const void* x, void* y, const void* w, int rows, int D, float eps, emmax_stream st) {
-    int r = launch_rmsnorm(x, y, w, rows, D, D, D, eps, (hipStream_t)st);
-    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_rmsnorm: unsupported shape");
-    return 0;
-}
-int emmax_op_attention(const void* qkv, int ld_qkv, int q_off, int k_off, int v_off, void* out, int ld_out, const int32_t* cu, int B,
-                       int max_seqlen, int Hq, int Hkv, int head_dim, float scale, int causal, emmax_stream st) {
-    AttnParams a;
-    a.qkv = qkv; a.out = out; a.cu_seqlens = cu; a.ld_qkv = ld_qkv; a.q_off = q_off; a.k_off = k_off; a.v_off = v_off;
-    a.ld_out = ld_out; a.B = B; a.max_seqlen = max_seqlen; a.Hq = Hq; a.Hkv = Hkv; a.scale = scale; a.causal = causal;
-    int r = launch_attention(a, head_dim, (hipStream_t)st);
-    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_attention: unsupported head_dim/strides");
-    return 0;
-}
-int emmax_op_decode_attention(const void* q, const void* kcache, const void* vcache, const int32_t* page_table, const int32_t* ctx_len,
-                              const int32_t* done, float* part_out, int B, int Hq, int Hkv, int page, int max_pages, int nsplit, float scale,
-                              int* nsplit_out, emmax_stream st) {
-    if (!q || !kcache || !vcache || !page_table || !ctx_len || !part_out) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_attention: null argument");
-    if (B < 1 || B > EMMAX_MAX_DECODE_BATCH || Hkv < 1 || Hq % Hkv) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_attention: bad B / heads");
-    DecodeAttnParams a;
-    memset(&a, 0, sizeof(a));
-    a.q = q; a.ldq = Hq * 128; a.kcache = kcache; a.vcache = vcache; a.page_table = page_table; a.ctx_len = ctx_len; a.done = done;
-    a.part = part_out; a.Hkv = Hkv; a.page = page; a.max_pages = max_pages; a.scale = scale;
-    const int ns = nsplit > 0 ? nsplit : decode_attn_nsplit(B, Hkv);
-    if (nsplit_out) *nsplit_out = ns;
-    if (ns > 16) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_attention: nsplit %d > 16", ns);
-    int r = launch_decode_attn(a, B, Hq, 128, ns, (hipStream_t)st);
-    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_decode_attention: unsupported (GQA group in {1,2,4,8}, page = 2^k, max_pages <= 512, nsplit = 2^k)");
-    return 0;
-}
-int emmax_op_decode_attention_direct(const void* q, const void* kcache, const void* vcache, const int32_t* page_table, const int32_t* ctx_len,
-                                     const int32_t* done, void* o_out, int B, int Hq, int Hkv, int page, int max_pages, float scale,
-                                     emmax_stream st) {
-    if (!q || !kcache || !vcache || !page_table || !ctx_len || !o_out) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_attention_direct: null argument");
-    if (B < 1 || B > EMMAX_MAX_DECODE_BATCH || Hkv < 1 || Hq % Hkv) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_attention_direct: bad B / heads");
-    DecodeAttnParams a;
-    memset(&a, 0, sizeof(a));
-    a.q = q; a.ldq = Hq * 128; a.kcache = kcache; a.vcache = vcache; a.page_table = page_table; a.ctx_len = ctx_len; a.done = done;
-    a.part = nullptr; a.Hkv = Hkv; a.page = page; a.max_pages = max_pages; a.scale = scale; a.o_out = o_out;
-    int r = launch_decode_attn(a, B, Hq, 128, 1, (hipStream_t)st);
-    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_decode_attention_direct: unsupported (GQA group in {1,2,4,8}, page = 2^k, max_pages <= 512)");
-    return 0;
-}
-int emmax_op_decode_attention_kv8(const void* q, void* kcache8, void* vcache8, float* kscale, float* vscale, const void* kv_stage,
-                                  const int32_t* page_table, const int32_t* ctx_len, const int32_t* done, float* part_out, void* o_out, int B, int Hq,
-                                  int Hkv, int page, int max_pages, int nsplit, float scale, emmax_stream st) {
-    if (!q || !kcache8 || !vcache8 || !kscale || !vscale || !kv_stage || !page_table || !ctx_len || (!part_out && !o_out))
-        return fail(EMMAX_ERR_INVALID, "emmax_op_decode_attention_kv8: null argument");
-    if (B < 1 || B > EMMAX_MAX_DECODE_BATCH || Hkv < 1 || Hq % Hkv) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_attention_kv8: bad B / heads");
-    DecodeAttnParams a;
-    memset(&a, 0, sizeof(a));
-    a.q = q; a.ldq = Hq * 128; a.kcache = kcache8; a.vcache = vcache8; a.kscale = kscale; a.vscale = vscale; a.kv_stage = kv_stage;
-    a.page_table = page_table; a.ctx_len = ctx_len; a.done = done; a.part = part_out; a.o_out = o_out;
-    a.Hkv = Hkv; a.page = page; a.max_pages = max_pages; a.scale = scale;
-    const int ns = o_out ? 1 : (nsplit > 0 ? nsplit : decode_attn_nsplit(B, Hkv));
-    if (ns > 16) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_attention_kv8: nsplit %d > 16", ns);
-    int r = launch_decode_attn(a, B, Hq, 128, ns, (hipStream_t)st);
-    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_decode_attention_kv8: unsupported (GQA group in {1,2,4,8}, page = 2^k, max_pages <= 512, nsplit = 2^k)");
-    return 0;
-}
-// ---- exact numerics: single-kernel entry points (fp32 in, fp32 out; hl_ws: caller scratch for the two-term image of the operand) ----
-int emmax_op_x_gemm(const float* A32, int lda, const void* W, int ldw, float* C32, int ldc, int M, int N, int K, const void* bias, int act,
-                    const float* residual32, int ldr, void* hl_ws, void* ws, int64_t ws_bytes, emmax_stream stream) {
-    if (!A32 || !W || !C32 || !hl_ws) return fail(EMMAX_ERR_INVALID, "emmax_op_x_gemm: null argument");
-    if (K % 64 || N % 128) return fail(EMMAX_ERR_INVALID, "emmax_op_x_gemm: K %% 64, N %% 128 required");
-    hipStream_t st = (hipStream_t)stream;
-    KCHK(launch_x_split_rows(A32, hl_ws, M, K, K, lda, 2 * K, st));
-    GemmParams p = gp(hl_ws, 2 * K, W, ldw, C32, ldc, M, N, 2 * K);
-    p.a_hl = 1; p.out_f32 = 1; p.bias = bias; p.act = act;
-    if (act == 2) p.N_store = N;
-    if (residual32) { p.residual = residual32; p.res_f32 = 1; p.ldr = ldr; }
-    if (ws) { p.ws = (float*)ws; p.ws_bytes = ws_bytes; }
-    int r = launch_gemm(p, st);
-    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_x_gemm: unsupported shape or launch failure");
-    return 0;
-}
-int emmax_op_x_rownorm(int mode, const float* x, float* y32, const void* w, const void* b, int rows, int D, float eps, void* hl_ws, emmax_stream stream) {
-    if (!x || !y32 || !hl_ws || (mode != 0 && !w) || (mode == 2 && !b)) return fail(EMMAX_ERR_INVALID, "emmax_op_x_rownorm: null argument");
-    hipStream_t st = (hipStream_t)stream;
-    const int Dp = pad_to(D, 64);
-    int r = mode == 0 ? launch_x_split_rows(x, hl_ws, rows, D, Dp, D, 2 * Dp, st)
-          : mode == 1 ? (D % 64 ? -1 : launch_x_rmsnorm(x, hl_ws, w, rows, D, D, 2 * Dp, eps, st))
-                      : launch_x_layernorm(x, hl_ws, w, b, rows, D, Dp, D, 2 * Dp, eps, st);
-    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_x_rownorm: unsupported shape (D %% 8; RMSNorm: D %% 64)");
-    KCHK(launch_x_join_rows(hl_ws, y32, rows, D, 2 * Dp, D, st));
-    return 0;
-}
-int emmax_op_x_attention(const float* qkv32, int ld_qkv, int q_off, int k_off, int v_off, const int32_t* cu, int B,
-                         int max_seqlen, int Hq, int Hkv, int head_dim, float scale, int causal, void* hl_ws, emmax_stream stream) {
-    if (!qkv32 || !cu || !hl_ws) return fail(EMMAX_ERR_INVALID, "emmax_op_x_attention: null argument");
-    hipStream_t st = (hipStream_t)stream;
-    const int Dq = Hq * head_dim, Dp = pad_to(Dq, 64);
-    AttnParams a;
-    a.qkv = qkv32; a.out = hl_ws; a.cu_seqlens = cu; a.ld_qkv = ld_qkv; a.q_off = q_off; a.k_off = k_off; a.v_off = v_off;
-    a.ld_out = 2 * Dp; a.B = B; a.max_seqlen = max_seqlen; a.Hq = Hq; a.Hkv = Hkv; a.scale = scale; a.causal = causal;
-    int r = launch_x_attention(a, head_dim, st);
-    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_x_attention: unsupported head_dim (64, 72, 128) / strides");
-    return 0;   // the result stays in hl_ws as HL rows of pitch 2 * pad64(Hq * head_dim): emmax_op_x_join widens them
-}
-int emmax_op_x_join(const void* hl, float* out32, int rows, int D, emmax_stream stream) {
-    if (!hl || !out32) return fail(EMMAX_ERR_INVALID, "emmax_op_x_join: null argument");
-    const int Dp = pad_to(D, 64);
-    KCHK(launch_x_join_rows(hl, out32, rows, D, 2 * Dp, D, (hipStream_t)stream));
-    return 0;
-}
-int emmax_op_x_decode_attention(const float* q32, const void* kcache32, const void* vcache32, int64_t kv24_elems, const int32_t* page_table,
-                                const int32_t* ctx_len, const int32_t* done, float* part_out, int B, int Hq, int Hkv, int page, int max_pages, int nsplit,
-                                float scale, emmax_stream st) {
-    if (!q32 || !kcache32 || !vcache32 || !page_table || !ctx_len || !part_out) return fail(EMMAX_ERR_INVALID, "emmax_op_x_decode_attention: null argument");
-    if (B < 1 || B > EMMAX_MAX_DECODE_BATCH || Hkv < 1 || Hq % Hkv) return fail(EMMAX_ERR_INVALID, "emmax_op_x_decode_attention: bad B / heads");
-    DecodeAttnParams a;
-    memset(&a, 0, sizeof(a));
-    a.q = q32; a.ldq = Hq * 128; a.kcache = kcache32; a.vcache = vcache32; a.page_table = page_table; a.ctx_len = ctx_len; a.done = done;
-    a.part = part_out; a.Hkv = Hkv; a.page = page; a.max_pages = max_pages; a.scale = scale; a.kv24 = kv24_elems;
-    int r = launch_x_decode_attn(a, B, Hq, 128, nsplit, (hipStream_t)st);
-    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_x_decode_attention: unsupported (GQA group in {1,2,4,8}, page = 2^k, max_pages <= 512, nsplit = 2^k)");
-    return 0;
-}
-int emmax_op_gemv(const void* x, const void* W, void* y, int B, int N, int K, emmax_stream st) {
-    GemvParams p;
-    memset(&p, 0, sizeof(p));
-    p.x = x; p.ldx = K; p.W = W; p.ldw = K; p.K = K; p.y = y; p.ldy = N; p.n_rows = N;
-    if (decode_gemv_init() != 0) return fail(EMMAX_ERR_HIP, "could not raise the dynamic LDS limit of the GEMV kernels");
-    int r = launch_decode_gemv(GEMV_PLAIN, p, B, (hipStream_t)st);
-    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_gemv: unsupported shape (B<=8, K%%8)");
-    return 0;
-}
-
-int emmax_op_resize_bicubic_u8(const uint8_t* src, int B, int H, int W, uint8_t* dst, int OH, int OW, uint8_t* tmp,
-                               const int32_t* bounds_h, const int32_t* kk_h, int ksize_h, const int32_t* bounds_v, const int32_t* kk_v,
-                               int ksize_v, emmax_stream st) {
-    if (!src || !dst || B < 1 || H < 1 || W < 1 || OH < 1 || OW < 1) return fail(EMMAX_ERR_INVALID, "emmax_op_resize_bicubic_u8: bad argument");
-    if ((W != OW && (!bounds_h || !kk_h)) || (H != OH && (!bounds_v || !kk_v)) || (W != OW && H != OH && !tmp))
-        return fail(EMMAX_ERR_INVALID, "emmax_op_resize_bicubic_u8: missing tables / scratch");
-    int r = launch_resize_bicubic_u8(src, B, H, W, dst, OH, OW, tmp, bounds_h, kk_h, ksize_h, bounds_v, kk_v, ksize_v, (hipStream_t)st);
-    if (r) return fail(EMMAX_ERR_HIP, "emmax_op_resize_bicubic_u8: launch failed");
-    return 0;
-}
-int emmax_op_quant_fm8(const void* W, int ld, void* W8, float* scales, int N, int K, emmax_stream st) {
-    int r = launch_quant_fm8(W, ld, W8, scales, N, K, (hipStream_t)st);
-    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_quant_fm8: N %% 16, K %% 64, ld %% 8 required");
-    return 0;
-}
-int emmax_op_quant_rm8(const void* W, int ld, void* W8, float* scales, int N, int K, emmax_stream st) {
-    int r = launch_quant_rm8(W, ld, W8, scales, N, K, (hipStream_t)st);
-    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_quant_rm8: K %% 16, ld %% 8 required");
-    return 0;
-}
-int emmax_op_gemv_fp8(const void* x, const void* W8, const float* scales, void* y, int B, int N, int K, emmax_stream st) {
-    if (B < 1 || B > 2) return fail(EMMAX_ERR_INVALID, "emmax_op_gemv_fp8: batch must be 1..2");
-    if (!scales) return fail(EMMAX_ERR_INVALID, "emmax_op_gemv_fp8: scales required");
-    if (decode_gemv_init()) return fail(EMMAX_ERR_HIP, "emmax_op_gemv_fp8: init failed");
-    GemvParams p;
-    memset(&p, 0, sizeof(p));
-    p.x = x; p.ldx = K; p.W = W8; p.ldw = K; p.K = K; p.y = y; p.ldy = N; p.n_rows = N; p.wscale = scales;
-    int r = launch_decode_gemv(GEMV_PLAIN, p, B, (hipStream_t)st);
-    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_gemv_fp8: unsupported shape (K %% 16, B * K * 2 bytes of LDS)");
-    return 0;
-}
-int emmax_op_gemm_small_fp8(const void* x, const void* W8, const float* scales, void* y, int B, int N, int K, emmax_stream st) {
-    GemvParams p;
-    memset(&p, 0, sizeof(p));
-    p.x = x; p.ldx = K; p.W = W8; p.ldw = K; p.K = K; p.y = y; p.ldy = N; p.n_rows = N; p.wscale = scales;
-    if (!scales) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_small_fp8: scales required");
-    int r;
-    if (B <= 8) {   // decode_mfma.hip stages eight rows
-        if (decode_mfma_init() != 0) return fail(EMMAX_ERR_HIP, "could not raise the dynamic LDS limit of the MFMA decode kernels");
-        r = launch_decode_mfma(GEMV_PLAIN, p, B, (hipStream_t)st);
-    } else if (K > 4096) {   // 9-32 rows: the K-split kernels (natural row order: the same e4m3 tiles); the phased down form is y = h + W x: h = 0
-        HIPCHK(hipMemsetAsync(y, 0, (size_t)B * N * 2, (hipStream_t)st));
-        r = launch_decode_km(GEMV_RESID, p, B, (hipStream_t)st);
-    } else {
-        r = launch_decode_km(GEMV_PLAIN, p, B, (hipStream_t)st);
-    }
-    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_gemm_small_fp8: unsupported shape (N %% 16, K %% 64; 1 <= B <= 8; 9 <= B <= 32: the shapes of emmax_op_gemm_small_km)");
-    return 0;
-}
-int emmax_op_repack_fm(const void* W, int ld, void* W_fm, int N, int K, emmax_stream st) {
-    int r = launch_repack_fm(W, ld, W_fm, N, K, (hipStream_t)st);
-    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_repack_fm: N %% 16, K %% 32, ld %% 8 required");
-    return 0;
-}
-int emmax_op_repack_km(const void* W, int ld, void* W_km, int N, int K, int perm, int head_dim, emmax_stream st) {
-    int r = launch_repack_km(W, ld, W_km, N, K, perm, head_dim, (hipStream_t)st);
-    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_repack_km: N %% 16, K %% 32, ld %% 8 (perm 1: N %% head_dim, head_dim %% 16; perm 2: N %% 32) required");
-    return 0;
-}
-int emmax_op_gemm_small_km(const void* x, const void* W_km, void* y, int B, int N, int K, emmax_stream st) {
-    GemvParams p;
-    memset(&p, 0, sizeof(p));
-    p.x = x; p.ldx = K; p.W = W_km; p.ldw = K; p.K = K; p.y = y; p.ldy = N; p.n_rows = N;
-    int r;
-    if (K > 4096) {   // the phased kernel of the down projection (y = h + W x): h = 0
-        HIPCHK(hipMemsetAsync(y, 0, (size_t)B * N * 2, (hipStream_t)st));
-        r = launch_decode_km(GEMV_RESID, p, B, (hipStream_t)st);
-    } else {
-        r = launch_decode_km(GEMV_PLAIN, p, B, (hipStream_t)st);
-    }
-    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_gemm_small_km: unsupported shape (1 <= B <= 32, N %% 16; K %% 256 and K <= 4096 and N <= 32768, or the phased form: K %% 32, K <= 11264 at B <= 8, 12288 at B <= 16; B > 16: K %% 32, K <= 11264, N <= 4096 there)");
-    return 0;
-}
-int emmax_op_gemm_small(const void* x, const void* W_fm, void* y, int B, int N, int K, emmax_stream st) {
-    GemvParams p;
-    memset(&p, 0, sizeof(p));
-    p.x = x; p.ldx = K; p.W = W_fm; p.ldw = K; p.K = K; p.y = y; p.ldy = N; p.n_rows = N;
-    if (decode_mfma_init() != 0) return fail(EMMAX_ERR_HIP, "could not raise the dynamic LDS limit of the MFMA decode kernels");
-    int r = launch_decode_mfma(GEMV_PLAIN, p, B, (hipStream_t)st);
-    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_small: unsupported shape (1 <= B <= 8, N %% 16, K %% 32)");
     return 0;
 }
 

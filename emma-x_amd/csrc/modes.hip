@@ -1,0 +1,245 @@
+// modes.hip -- how a session's steps end, configured: the stop rule, sampling, logits processing, scores and beam search -- the host checks,
+// the upload of the per-row parameters, and the calls that hand the results back (log-probabilities, beam result and trace).
+#include <initializer_list>
+
+#include "session.h"
+
+// One column of a per-row upload: elements of `esize` bytes, from a host array to rows r0 .. of a device array
+struct Column { void* dev; const void* host; int esize; };
+
+// rows r0 .. r0 + n of every column: the caller's arrays are pageable, so they go through the pinned upload area, UPLOAD_ROWS rows at a time
+static int upload_rows(emmax_session* s, int r0, int n, hipStream_t st, std::initializer_list<Column> cols) {
+    char* const h = s->pinned->upload;
+    const int chunk = std::min(n, (int)UPLOAD_ROWS);
+    auto span = [&](const Column& k) { return ((size_t)chunk * k.esize + 7) / 8 * 8; };   // a column's share of the area
+    size_t need = 0;
+    for (const Column& k : cols) need += span(k);
+    if (need > sizeof(s->pinned->upload)) return fail(EMMAX_ERR_STATE, "an upload of %zu bytes per chunk exceeds the pinned area", need);
+    HIPCHK(hipStreamSynchronize(st));   // the pinned staging words may still feed an earlier upload
+    for (int c0 = 0; c0 < n; c0 += chunk) {
+        const int c = std::min(chunk, n - c0);
+        size_t off = 0;
+        for (const Column& k : cols) {
+            const size_t bytes = (size_t)c * k.esize;
+            if (bytes) {   // (the stop rule may name no trigger ids)
+                memcpy(h + off, (const char*)k.host + (size_t)c0 * k.esize, bytes);
+                HIPCHK(hipMemcpyAsync((char*)k.dev + (size_t)(r0 + c0) * k.esize, h + off, bytes, hipMemcpyHostToDevice, st));
+            }
+            off += span(k);
+        }
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    return 0;
+}
+
+// the rows a per-row configuration call names: n decode rows from row0 (emmax_session_set_*), or the first n staging rows (emmax_slots_set_*_staged)
+static int check_rows(const emmax_session* s, int row0, int n, bool staged) {
+    if (staged) return n < 1 || n > s->n_stg ? fail(EMMAX_ERR_INVALID, "%d staged requests outside 1..%d (the session's staging rows)", n, s->n_stg) : 0;
+    return n < 1 || row0 < 0 || row0 + n > s->max_batch ? fail(EMMAX_ERR_INVALID, "rows %d..%d outside 0..%d", row0, row0 + n - 1, s->max_batch - 1) : 0;
+}
+
+// ---- sampling in the decode step (ABI 7) ------------------------------------------------------------------------------
+static int set_sampling_rows(emmax_session* s, int row0, int n, bool staged, const float* T, const int32_t* top_k, const float* top_p, const uint64_t* seed,
+                             const uint32_t* subseq, emmax_stream stream) {
+    if (!s || !T || !top_k || !top_p || !seed || !subseq) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (int r = check_rows(s, row0, n, staged)) return r;
+    if (!staged && s->beam.K) return fail(EMMAX_ERR_STATE, "sampling is not available while beams are on");
+    const int r0 = staged ? s->stg0 : row0;
+    if (s->m->vocab > EMMAX_SAMPLE_MAX_V) return fail(EMMAX_ERR_INVALID, "sampling takes vocabularies of up to %d entries (%d)", EMMAX_SAMPLE_MAX_V, s->m->vocab);
+    for (int i = 0; i < n; ++i) {
+        if (!std::isfinite(T[i]) || T[i] < 0.f) return fail(EMMAX_ERR_INVALID, "row %d: temperature %g (finite and >= 0)", r0 + i, (double)T[i]);
+        if (top_k[i] < 0) return fail(EMMAX_ERR_INVALID, "row %d: top_k %d (>= 0)", r0 + i, top_k[i]);
+        if (!(top_p[i] > 0.f && top_p[i] <= 1.f)) return fail(EMMAX_ERR_INVALID, "row %d: top_p %g (0 < top_p <= 1)", r0 + i, (double)top_p[i]);
+    }
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    if (int r = upload_rows(s, r0, n, sc.stream(), {{s->samp.t, T, 4}, {s->samp.k, top_k, 4}, {s->samp.p, top_p, 4}, {s->samp.sub, subseq, 4}, {s->samp.seed, seed, 8}})) return r;
+    s->samp.on = true;
+    return sc.leave();
+}
+
+// ---- logits processing and scores in the decode step (ABI 8) --------------------------------------------------------------
+static int set_processing_rows(emmax_session* s, int row0, int n, bool staged, const float* pen, const int32_t* ng, const int32_t* mn, emmax_stream stream) {
+    if (!s || !pen || !ng || !mn) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (int r = check_rows(s, row0, n, staged)) return r;
+    if (!staged && s->beam.K) return fail(EMMAX_ERR_STATE, "logits processing is not available while beams are on");
+    const int r0 = staged ? s->stg0 : row0;
+    if (s->m->vocab > EMMAX_SAMPLE_MAX_V) return fail(EMMAX_ERR_INVALID, "logits processing takes vocabularies of up to %d entries (%d)", EMMAX_SAMPLE_MAX_V, s->m->vocab);
+    for (int i = 0; i < n; ++i) {
+        if (!std::isfinite(pen[i]) || !(pen[i] > 0.f)) return fail(EMMAX_ERR_INVALID, "row %d: repetition penalty %g (finite and > 0)", r0 + i, (double)pen[i]);
+        if (ng[i] < 0 || ng[i] > EMMAX_MAX_NGRAM) return fail(EMMAX_ERR_INVALID, "row %d: no_repeat_ngram_size %d outside 0..%d", r0 + i, ng[i], EMMAX_MAX_NGRAM);
+        if (mn[i] < 0) return fail(EMMAX_ERR_INVALID, "row %d: min_new_tokens %d (>= 0)", r0 + i, mn[i]);
+    }
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    if (int r = upload_rows(s, r0, n, sc.stream(), {{s->proc.pen, pen, 4}, {s->proc.ng, ng, 4}, {s->proc.mn, mn, 4}})) return r;
+    s->proc.on = true;
+    return sc.leave();
+}
+
+extern "C" {
+
+int emmax_session_set_stop(emmax_session* s, const int32_t* trigger_ids, int n_trigger, int n_after, emmax_stream stream) {
+    if (!s || (n_trigger > 0 && !trigger_ids)) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (n_trigger < 0 || n_trigger > EMMAX_MAX_STOP_IDS || n_after < 0)
+        return fail(EMMAX_ERR_INVALID, "stop rule: %d trigger ids (max %d), %d tokens after", n_trigger, EMMAX_MAX_STOP_IDS, n_after);
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    const int32_t cfg[2] = {n_trigger, n_after};
+    if (int r = upload_rows(s, 0, 1, sc.stream(), {{s->stop_ids, trigger_ids, n_trigger * 4}, {s->stop_cfg, cfg, 8}})) return r;
+    return sc.leave();
+}
+
+int emmax_session_set_sampling(emmax_session* s, int row0, int n, const float* temperature_host, const int32_t* top_k_host, const float* top_p_host,
+                               const uint64_t* seed_host, const uint32_t* subseq_host, emmax_stream stream) {
+    return set_sampling_rows(s, row0, n, false, temperature_host, top_k_host, top_p_host, seed_host, subseq_host, stream);
+}
+
+int emmax_slots_set_sampling_staged(emmax_session* s, int n, const float* temperature_host, const int32_t* top_k_host, const float* top_p_host,
+                                    const uint64_t* seed_host, const uint32_t* subseq_host, emmax_stream stream) {
+    return set_sampling_rows(s, 0, n, true, temperature_host, top_k_host, top_p_host, seed_host, subseq_host, stream);
+}
+
+int emmax_session_clear_sampling(emmax_session* s, emmax_stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    s->samp.on = false;
+    return 0;
+}
+
+int emmax_session_sampling(const emmax_session* s) { return s ? (s->samp.on ? 1 : 0) : -1; }
+
+int emmax_session_logprobs(emmax_session* s, int max_new, float* out_dev, emmax_stream stream) {
+    if (!s || !out_dev) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->samp.on) return fail(EMMAX_ERR_STATE, "log-probabilities exist in a sampling session only (emmax_session_set_sampling)");
+    if (!s->prefilled) return fail(EMMAX_ERR_STATE, "no generation has run");
+    if (max_new < 1 || max_new > s->max_out) return fail(EMMAX_ERR_INVALID, "max_new_tokens %d outside 1..%d", max_new, s->max_out);
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    HIPCHK(hipMemcpy2DAsync(out_dev, (size_t)max_new * 4, s->samp.logprob, (size_t)s->max_out * 4, (size_t)max_new * 4, s->cur_B,
+                            hipMemcpyDeviceToDevice, sc.stream()));
+    return sc.leave();
+}
+
+int emmax_slot_logprobs(emmax_session* s, int slot, float* out_dev, int n, emmax_stream stream) {
+    if (!s || !out_dev) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->samp.on) return fail(EMMAX_ERR_STATE, "log-probabilities exist in a sampling session only (emmax_session_set_sampling)");
+    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slot_logprobs before emmax_slots_open");
+    if (slot < 0 || slot >= s->cur_B || n < 0 || n > s->max_out) return fail(EMMAX_ERR_INVALID, "slot %d / %d values out of range", slot, n);
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    if (n > 0) HIPCHK(hipMemcpyAsync(out_dev, s->samp.logprob + (size_t)slot * s->max_out, (size_t)n * 4, hipMemcpyDeviceToDevice, sc.stream()));
+    return sc.leave();
+}
+
+int emmax_session_set_processing(emmax_session* s, int row0, int n, const float* penalty_host, const int32_t* ngram_host, const int32_t* min_new_host,
+                                 emmax_stream stream) {
+    return set_processing_rows(s, row0, n, false, penalty_host, ngram_host, min_new_host, stream);
+}
+
+int emmax_slots_set_processing_staged(emmax_session* s, int n, const float* penalty_host, const int32_t* ngram_host, const int32_t* min_new_host,
+                                      emmax_stream stream) {
+    return set_processing_rows(s, 0, n, true, penalty_host, ngram_host, min_new_host, stream);
+}
+
+int emmax_session_clear_processing(emmax_session* s, emmax_stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    s->proc.on = false;
+    return 0;
+}
+
+int emmax_session_processing(const emmax_session* s) { return s ? (s->proc.on ? 1 : 0) : -1; }
+
+int emmax_session_set_scores(emmax_session* s, float* scores_dev, float* logits_dev, int max_new, emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (s->slots_open) return fail(EMMAX_ERR_STATE, "scores are not kept in slot serving (emmax_slots_open)");
+    if (!scores_dev && !logits_dev) {
+        s->scores.on = s->scores.has_scores = false;
+        return 0;
+    }
+    if (s->beam.K && scores_dev) return fail(EMMAX_ERR_STATE, "processed scores are not kept while beams are on (bind the raw logits buffer only)");
+    if (s->m->vocab > EMMAX_SAMPLE_MAX_V) return fail(EMMAX_ERR_INVALID, "scores take vocabularies of up to %d entries (%d)", EMMAX_SAMPLE_MAX_V, s->m->vocab);
+    if (max_new < 1 || max_new > s->max_out) return fail(EMMAX_ERR_INVALID, "max_new_tokens %d outside 1..%d", max_new, s->max_out);
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    const uint64_t words[4] = {(uint64_t)(uintptr_t)scores_dev, (uint64_t)(uintptr_t)logits_dev, (uint64_t)max_new, 0};   // rows: set by the next prefill
+    if (int r = upload_rows(s, 0, 1, sc.stream(), {{s->scores.words, words, 4 * 8}})) return r;
+    s->scores.on = true;
+    s->scores.has_scores = scores_dev != nullptr;
+    s->scores.rows = 0;
+    return sc.leave();
+}
+
+// ---- beam search in the decode step (ABI 9) ---------------------------------------------------------------------------
+int emmax_session_set_beams(emmax_session* s, int num_beams, double length_penalty, int early_stopping, emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    const int max_rows = s->exact ? EMMAX_MAX_DECODE_BATCH : model_max_decode_batch(s->m);
+    if (num_beams < 2 || num_beams > EMMAX_MAX_BEAMS || num_beams > s->max_batch || num_beams > max_rows)
+        return fail(EMMAX_ERR_INVALID, "num_beams %d outside 2..min(%d, max_batch=%d, %d)", num_beams, EMMAX_MAX_BEAMS, s->max_batch, max_rows);
+    if (!std::isfinite(length_penalty)) return fail(EMMAX_ERR_INVALID, "length_penalty must be finite");
+    if (early_stopping < 0 || early_stopping > 2) return fail(EMMAX_ERR_INVALID, "early_stopping %d: 0 False, 1 True, 2 never", early_stopping);
+    if (s->m->vocab > EMMAX_SAMPLE_MAX_V || s->m->vocab < 2 * num_beams)
+        return fail(EMMAX_ERR_INVALID, "beams take vocabularies of %d..%d entries (%d)", 2 * num_beams, EMMAX_SAMPLE_MAX_V, s->m->vocab);
+    if (s->slots_open) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while request slots are open");
+    if (s->samp.on || s->proc.on) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while sampling or logits processing is on");
+    if (s->scores.on && s->scores.has_scores) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while a scores buffer is bound");
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    std::vector<float> pw((size_t)s->max_out + 1);
+    for (size_t n = 0; n < pw.size(); ++n) pw[n] = (float)pow((double)n, length_penalty);
+    HIPCHK(hipStreamSynchronize(sc.stream()));
+    HIPCHK(hipMemcpy(s->beam.pw, pw.data(), pw.size() * 4, hipMemcpyHostToDevice));
+    s->beam.K = num_beams; s->beam.es = early_stopping; s->beam.lp_pos = length_penalty > 0.0 ? 1 : 0;
+    s->beam.G = 0; s->beam.forked = false; s->beam.ready = false;
+    s->prefilled = false;   // rows of an earlier batch do not continue as beams
+    return sc.leave();
+}
+
+int emmax_session_clear_beams(emmax_session* s, emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->beam.K) return 0;
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    KCHK(launch_beam_pages(s->page_table, s->rows_total, s->max_pages, 1, sc.stream()));   // static assignment again: row b owns its own pages
+    s->beam.K = 0; s->beam.G = 0; s->beam.forked = false; s->beam.ready = false;
+    s->prefilled = false;
+    return sc.leave();
+}
+
+int emmax_session_beams(const emmax_session* s) { return s ? s->beam.K : -1; }
+
+int emmax_session_beam_result(emmax_session* s, int max_new, int32_t* seq_dev, int32_t* len_dev, float* score_dev, int32_t* bidx_dev, emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->beam.K || !s->beam.forked) return fail(EMMAX_ERR_STATE, "no beam generation to report");
+    if (max_new < 1 || max_new > s->beam.max_new) return fail(EMMAX_ERR_INVALID, "max_new %d outside 1..%d (the generation's)", max_new, s->beam.max_new);
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    const hipStream_t st = sc.stream();
+    const int rows = s->beam.G * s->beam.K;
+    if (seq_dev) HIPCHK(hipMemcpy2DAsync(seq_dev, (size_t)max_new * 4, s->out_ids, (size_t)s->max_out * 4, (size_t)max_new * 4, rows, hipMemcpyDeviceToDevice, st));
+    if (bidx_dev) HIPCHK(hipMemcpy2DAsync(bidx_dev, (size_t)max_new * 4, s->beam.res_bidx, (size_t)s->max_out * 4, (size_t)max_new * 4, rows, hipMemcpyDeviceToDevice, st));
+    if (len_dev) HIPCHK(hipMemcpyAsync(len_dev, s->beam.res_len, rows * 4, hipMemcpyDeviceToDevice, st));
+    if (score_dev) HIPCHK(hipMemcpyAsync(score_dev, s->beam.res_score, rows * 4, hipMemcpyDeviceToDevice, st));
+    return sc.leave();
+}
+
+int emmax_session_beam_trace(emmax_session* s, int max_new, int32_t* tok_dev, int32_t* parent_dev, float* score_dev, float* lse_dev, int32_t* cand_idx_dev,
+                             float* cand_acc_dev, emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->beam.K || !s->beam.forked) return fail(EMMAX_ERR_STATE, "no beam generation to report");
+    if (max_new < 1 || max_new > s->beam.max_new) return fail(EMMAX_ERR_INVALID, "max_new %d outside 1..%d (the generation's)", max_new, s->beam.max_new);
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    const size_t rows = (size_t)s->beam.G * s->beam.K, ld = (size_t)std::min(s->max_batch, EMMAX_MAX_DECODE_BATCH);
+    auto out = [&](void* dst, const void* src, size_t mul) -> hipError_t {
+        return dst ? hipMemcpy2DAsync(dst, rows * mul * 4, src, ld * mul * 4, rows * mul * 4, (size_t)max_new, hipMemcpyDeviceToDevice, sc.stream()) : hipSuccess;
+    };
+    HIPCHK(out(tok_dev, s->beam.tr_tok, 1));
+    HIPCHK(out(parent_dev, s->beam.tr_par, 1));
+    HIPCHK(out(score_dev, s->beam.tr_score, 1));
+    HIPCHK(out(lse_dev, s->beam.tr_lse, 1));
+    HIPCHK(out(cand_idx_dev, s->beam.tc_idx, 2));
+    HIPCHK(out(cand_acc_dev, s->beam.tc_acc, 2));
+    return sc.leave();
+}
+
+}  // extern "C"

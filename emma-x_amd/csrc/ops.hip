@@ -1,0 +1,322 @@
+// ops.hip -- the entry points that run one piece on its own: the decode-stage profiler and the single-kernel emmax_op_* calls the tests
+// and tools drive.
+#include "session.h"
+
+// y[B, N] = x[B, K] . W^T, nothing fused: the parameters of the single-projection entry points
+static GemvParams plain_gemv(const void* x, const void* W, void* y, int N, int K, const float* wscale = nullptr) {
+    GemvParams p;
+    memset(&p, 0, sizeof(p));
+    p.x = x; p.ldx = K; p.W = W; p.ldw = K; p.K = K; p.y = y; p.ldy = N; p.n_rows = N; p.wscale = wscale;
+    return p;
+}
+
+extern "C" {
+
+int emmax_profile_decode_stage(emmax_session* s, int stage, int reps, float* avg_us, emmax_stream stream) {
+    if (!s || !avg_us || reps < 1) return fail(EMMAX_ERR_INVALID, "bad argument");
+    if (!s->prefilled) return fail(EMMAX_ERR_STATE, "profile needs an active (prefilled) session");
+    hipStream_t st = (hipStream_t)stream;
+    emmax_model* m = s->m;
+    const int B = s->cur_B, nl = m->cfg.n_layers;
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    int launches = 0, r = 0;
+    // one untimed sweep (instruction cache, clocks), then `reps` timed sweeps over all layers: every launch streams a
+    // different layer's weights, so nothing is served from the 256 MiB Infinity Cache that a real step would not get
+    for (int pass = 0; pass < 2 && r == 0; ++pass) {
+        if (pass == 1) HIPCHK(hipEventRecord(e0, st));
+        const int n = pass == 0 ? 1 : reps;
+        for (int i = 0; i < n && r == 0; ++i) {
+            if (stage == STAGE_LMHEAD) {
+                r = run_lm_head_step(s, B, false, nullptr, false, st);
+                launches += pass;
+            } else {
+                for (int li = 0; li < nl && r == 0; ++li) {
+                    r = run_decode_stage(s, B, li, stage, st);
+                    launches += pass;
+                }
+            }
+        }
+    }
+    if (r) return r;
+    HIPCHK(hipEventRecord(e1, st));
+    HIPCHK(hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    *avg_us = ms * 1000.0f / (float)launches;
+    return 0;
+}
+
+// ---- single-kernel entry points --------------------------------------------------------------------------------------
+int emmax_op_sample(const float* logits, int ld, int B, int V, const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seed,
+                    const uint32_t* subseq, const int32_t* step, int32_t* tok_out, float* logprob_out, emmax_stream stream) {
+    if (!logits || !temperature || !top_k || !top_p || !seed || !subseq || !step || !tok_out || !logprob_out) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (B < 1 || V < 1 || V > EMMAX_SAMPLE_MAX_V || ld < V)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_sample: B %d (>= 1), V %d (1..%d), ld %d (>= V)", B, V, EMMAX_SAMPLE_MAX_V, ld);
+    SampleParams p;
+    memset(&p, 0, sizeof(p));
+    p.logits = logits; p.ld = ld; p.V = V; p.temperature = temperature; p.top_k = top_k; p.top_p = top_p; p.seed = seed; p.subseq = subseq;
+    p.step = step; p.tok_out = tok_out; p.logprob_out = logprob_out;
+    KCHK(launch_sample(p, B, (hipStream_t)stream));
+    return 0;
+}
+int emmax_op_gemm(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K, const void* bias, int act,
+                  const void* scale, const void* residual, int ldr, int out_f32, emmax_stream st) {
+    GemmParams p = gp(A, lda, W, ldw, C, ldc, M, N, K);
+    p.bias = bias; p.act = act; p.scale = scale; p.residual = residual; p.ldr = ldr; p.out_f32 = out_f32;
+    int r = launch_gemm(p, (hipStream_t)st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_gemm: unsupported shape (K%%64, N%%128, ld%%8) or launch failure");
+    return 0;
+}
+int emmax_op_gemm_splitk(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K, const void* bias, int act,
+                         const void* scale, const void* residual, int ldr, int out_f32, int ksplit, void* ws, int64_t ws_bytes,
+                         emmax_stream st) {
+    GemmParams p = gp(A, lda, W, ldw, C, ldc, M, N, K);
+    p.bias = bias; p.act = act; p.scale = scale; p.residual = residual; p.ldr = ldr; p.out_f32 = out_f32;
+    p.ws = (float*)ws; p.ws_bytes = ws_bytes;
+    // ksplit = 0: the launch plan of a session stage with this scratch (whole tiles, split-K, or a column remainder through split-K)
+    int r = ksplit == 0 ? launch_gemm(p, (hipStream_t)st) : launch_gemm_splitk(p, ksplit, (hipStream_t)st, emmax_tune().gemm_sk_big > 0 ? 1 : 0);   // (tools: explicit slices, geometry by switch)
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID,
+                       "emmax_op_gemm_splitk: unsupported (ksplit = 0 or 2 <= ksplit <= K/64, ws >= ksplit*M*N*4 bytes, K%%64, N%%128; SwiGLU: bf16 output)");
+    return 0;
+}
+int emmax_gemm_plan(int M, int N, int K, int act, int out_f32, int has_ln, int has_residual, int with_norm, int64_t ws_bytes, char* text_out,
+                    int text_len) {
+    if (!text_out || text_len < 16) return fail(EMMAX_ERR_INVALID, "emmax_gemm_plan: text buffer of at least 16 bytes");
+    void* const any = (void*)(uintptr_t)256;   // the plan looks at sizes, alignments and which operands exist -- never through a pointer
+    GemmParams p = gp(any, K, any, K, any, act == 2 ? N / 2 : N, M, N, K);
+    p.act = act; p.out_f32 = out_f32;
+    if (has_residual) { p.residual = any; p.ldr = N; p.res_f32 = has_residual == 2; }   // 2: the fp32 residual stream (with out_f32)
+    if (has_ln) { p.ln_stats = (const float*)any; p.ln_s = (const float*)any; p.ln_c = (const float*)any; }
+    if (ws_bytes > 0) { p.ws = (float*)any; p.ws_bytes = ws_bytes; }
+    if (with_norm) { p.norm_w = any; p.norm_out = any; p.ld_norm = N; p.norm_eps = 1e-5f; }
+    if (with_norm && !gemm_fuses_norm(p)) { p.norm_w = nullptr; p.norm_out = nullptr; }   // (what the prefill does: a separate norm launch)
+    const int r = gemm_plan_describe(p, text_out, text_len);
+    if (r < 0) return fail(EMMAX_ERR_INVALID, "emmax_gemm_plan: unsupported shape (K%%64, N%%128)");
+    return 0;
+}
+int emmax_op_gemm_ln(const void* X, int ldx, void* W, int ldw, void* C, int ldc, int M, int N, int K, const void* gamma, const void* beta,
+                     const void* bias, float eps, int act, float* stats_ws, float* ln_s_ws, float* ln_c_ws, emmax_stream stream) {
+    if (!X || !W || !C || !gamma || !stats_ws || !ln_s_ws || !ln_c_ws) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_ln: null argument");
+    if (((uintptr_t)stats_ws & 7) || (((uintptr_t)ln_s_ws | (uintptr_t)ln_c_ws) & 3))   // (mean, rstd) pairs are read as 8 bytes
+        return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_ln: workspaces must be 8-byte (stats) / 4-byte (ln_s, ln_c) aligned");
+    hipStream_t st = (hipStream_t)stream;
+    KCHK(launch_ln_fold(W, ldw, N, K, gamma, beta, bias, ln_s_ws, ln_c_ws, st));
+    KCHK(launch_row_stats(X, stats_ws, M, K, ldx, eps, st));
+    GemmParams p = gp(X, ldx, W, ldw, C, ldc, M, N, K);
+    p.act = act; p.ln_stats = stats_ws; p.ln_s = ln_s_ws; p.ln_c = ln_c_ws;
+    int r = launch_gemm(p, st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_gemm_ln: unsupported shape (K%%64, N%%128, ld%%8, act in {0,1})");
+    return 0;
+}
+int emmax_op_layernorm(const void* x, void* y, const void* w, const void* b, int rows, int D, float eps, emmax_stream st) {
+    int r = launch_layernorm(x, y, w, b, rows, D, D, D, eps, (hipStream_t)st);
+    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_layernorm: unsupported shape");
+    return 0;
+}
+int emmax_op_rmsnorm(const void* x, void* y, const void* w, int rows, int D, float eps, emmax_stream st) {
+    int r = launch_rmsnorm(x, y, w, rows, D, D, D, eps, (hipStream_t)st);
+    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_rmsnorm: unsupported shape");
+    return 0;
+}
+int emmax_op_attention(const void* qkv, int ld_qkv, int q_off, int k_off, int v_off, void* out, int ld_out, const int32_t* cu, int B,
+                       int max_seqlen, int Hq, int Hkv, int head_dim, float scale, int causal, emmax_stream st) {
+    AttnParams a;
+    a.qkv = qkv; a.out = out; a.cu_seqlens = cu; a.ld_qkv = ld_qkv; a.q_off = q_off; a.k_off = k_off; a.v_off = v_off;
+    a.ld_out = ld_out; a.B = B; a.max_seqlen = max_seqlen; a.Hq = Hq; a.Hkv = Hkv; a.scale = scale; a.causal = causal;
+    int r = launch_attention(a, head_dim, (hipStream_t)st);
+    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_attention: unsupported head_dim/strides");
+    return 0;
+}
+int emmax_op_decode_attention(const void* q, const void* kcache, const void* vcache, const int32_t* page_table, const int32_t* ctx_len,
+                              const int32_t* done, float* part_out, int B, int Hq, int Hkv, int page, int max_pages, int nsplit, float scale,
+                              int* nsplit_out, emmax_stream st) {
+    if (!q || !kcache || !vcache || !page_table || !ctx_len || !part_out) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_attention: null argument");
+    if (B < 1 || B > EMMAX_MAX_DECODE_BATCH || Hkv < 1 || Hq % Hkv) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_attention: bad B / heads");
+    DecodeAttnParams a;
+    memset(&a, 0, sizeof(a));
+    a.q = q; a.ldq = Hq * 128; a.kcache = kcache; a.vcache = vcache; a.page_table = page_table; a.ctx_len = ctx_len; a.done = done;
+    a.part = part_out; a.Hkv = Hkv; a.page = page; a.max_pages = max_pages; a.scale = scale;
+    const int ns = nsplit > 0 ? nsplit : decode_attn_nsplit(B, Hkv);
+    if (nsplit_out) *nsplit_out = ns;
+    if (ns > 16) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_attention: nsplit %d > 16", ns);
+    int r = launch_decode_attn(a, B, Hq, 128, ns, (hipStream_t)st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_decode_attention: unsupported (GQA group in {1,2,4,8}, page = 2^k, max_pages <= 512, nsplit = 2^k)");
+    return 0;
+}
+int emmax_op_decode_attention_direct(const void* q, const void* kcache, const void* vcache, const int32_t* page_table, const int32_t* ctx_len,
+                                     const int32_t* done, void* o_out, int B, int Hq, int Hkv, int page, int max_pages, float scale,
+                                     emmax_stream st) {
+    if (!q || !kcache || !vcache || !page_table || !ctx_len || !o_out) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_attention_direct: null argument");
+    if (B < 1 || B > EMMAX_MAX_DECODE_BATCH || Hkv < 1 || Hq % Hkv) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_attention_direct: bad B / heads");
+    DecodeAttnParams a;
+    memset(&a, 0, sizeof(a));
+    a.q = q; a.ldq = Hq * 128; a.kcache = kcache; a.vcache = vcache; a.page_table = page_table; a.ctx_len = ctx_len; a.done = done;
+    a.part = nullptr; a.Hkv = Hkv; a.page = page; a.max_pages = max_pages; a.scale = scale; a.o_out = o_out;
+    int r = launch_decode_attn(a, B, Hq, 128, 1, (hipStream_t)st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_decode_attention_direct: unsupported (GQA group in {1,2,4,8}, page = 2^k, max_pages <= 512)");
+    return 0;
+}
+int emmax_op_decode_attention_kv8(const void* q, void* kcache8, void* vcache8, float* kscale, float* vscale, const void* kv_stage,
+                                  const int32_t* page_table, const int32_t* ctx_len, const int32_t* done, float* part_out, void* o_out, int B, int Hq,
+                                  int Hkv, int page, int max_pages, int nsplit, float scale, emmax_stream st) {
+    if (!q || !kcache8 || !vcache8 || !kscale || !vscale || !kv_stage || !page_table || !ctx_len || (!part_out && !o_out))
+        return fail(EMMAX_ERR_INVALID, "emmax_op_decode_attention_kv8: null argument");
+    if (B < 1 || B > EMMAX_MAX_DECODE_BATCH || Hkv < 1 || Hq % Hkv) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_attention_kv8: bad B / heads");
+    DecodeAttnParams a;
+    memset(&a, 0, sizeof(a));
+    a.q = q; a.ldq = Hq * 128; a.kcache = kcache8; a.vcache = vcache8; a.kscale = kscale; a.vscale = vscale; a.kv_stage = kv_stage;
+    a.page_table = page_table; a.ctx_len = ctx_len; a.done = done; a.part = part_out; a.o_out = o_out;
+    a.Hkv = Hkv; a.page = page; a.max_pages = max_pages; a.scale = scale;
+    const int ns = o_out ? 1 : (nsplit > 0 ? nsplit : decode_attn_nsplit(B, Hkv));
+    if (ns > 16) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_attention_kv8: nsplit %d > 16", ns);
+    int r = launch_decode_attn(a, B, Hq, 128, ns, (hipStream_t)st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_decode_attention_kv8: unsupported (GQA group in {1,2,4,8}, page = 2^k, max_pages <= 512, nsplit = 2^k)");
+    return 0;
+}
+// ---- exact numerics: single-kernel entry points (fp32 in, fp32 out; hl_ws: caller scratch for the two-term image of the operand) ----
+int emmax_op_x_gemm(const float* A32, int lda, const void* W, int ldw, float* C32, int ldc, int M, int N, int K, const void* bias, int act,
+                    const float* residual32, int ldr, void* hl_ws, void* ws, int64_t ws_bytes, emmax_stream stream) {
+    if (!A32 || !W || !C32 || !hl_ws) return fail(EMMAX_ERR_INVALID, "emmax_op_x_gemm: null argument");
+    if (K % 64 || N % 128) return fail(EMMAX_ERR_INVALID, "emmax_op_x_gemm: K %% 64, N %% 128 required");
+    hipStream_t st = (hipStream_t)stream;
+    KCHK(launch_x_split_rows(A32, hl_ws, M, K, K, lda, 2 * K, st));
+    GemmParams p = gp(hl_ws, 2 * K, W, ldw, C32, ldc, M, N, 2 * K);
+    p.a_hl = 1; p.out_f32 = 1; p.bias = bias; p.act = act;
+    if (act == 2) p.N_store = N;
+    if (residual32) { p.residual = residual32; p.res_f32 = 1; p.ldr = ldr; }
+    if (ws) { p.ws = (float*)ws; p.ws_bytes = ws_bytes; }
+    int r = launch_gemm(p, st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_x_gemm: unsupported shape or launch failure");
+    return 0;
+}
+int emmax_op_x_rownorm(int mode, const float* x, float* y32, const void* w, const void* b, int rows, int D, float eps, void* hl_ws, emmax_stream stream) {
+    if (!x || !y32 || !hl_ws || (mode != 0 && !w) || (mode == 2 && !b)) return fail(EMMAX_ERR_INVALID, "emmax_op_x_rownorm: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int Dp = pad_to(D, 64);
+    int r = mode == 0 ? launch_x_split_rows(x, hl_ws, rows, D, Dp, D, 2 * Dp, st)
+          : mode == 1 ? (D % 64 ? -1 : launch_x_rmsnorm(x, hl_ws, w, rows, D, D, 2 * Dp, eps, st))
+                      : launch_x_layernorm(x, hl_ws, w, b, rows, D, Dp, D, 2 * Dp, eps, st);
+    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_x_rownorm: unsupported shape (D %% 8; RMSNorm: D %% 64)");
+    KCHK(launch_x_join_rows(hl_ws, y32, rows, D, 2 * Dp, D, st));
+    return 0;
+}
+int emmax_op_x_attention(const float* qkv32, int ld_qkv, int q_off, int k_off, int v_off, const int32_t* cu, int B,
+                         int max_seqlen, int Hq, int Hkv, int head_dim, float scale, int causal, void* hl_ws, emmax_stream stream) {
+    if (!qkv32 || !cu || !hl_ws) return fail(EMMAX_ERR_INVALID, "emmax_op_x_attention: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int Dq = Hq * head_dim, Dp = pad_to(Dq, 64);
+    AttnParams a;
+    a.qkv = qkv32; a.out = hl_ws; a.cu_seqlens = cu; a.ld_qkv = ld_qkv; a.q_off = q_off; a.k_off = k_off; a.v_off = v_off;
+    a.ld_out = 2 * Dp; a.B = B; a.max_seqlen = max_seqlen; a.Hq = Hq; a.Hkv = Hkv; a.scale = scale; a.causal = causal;
+    int r = launch_x_attention(a, head_dim, st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_x_attention: unsupported head_dim (64, 72, 128) / strides");
+    return 0;   // the result stays in hl_ws as HL rows of pitch 2 * pad64(Hq * head_dim): emmax_op_x_join widens them
+}
+int emmax_op_x_join(const void* hl, float* out32, int rows, int D, emmax_stream stream) {
+    if (!hl || !out32) return fail(EMMAX_ERR_INVALID, "emmax_op_x_join: null argument");
+    const int Dp = pad_to(D, 64);
+    KCHK(launch_x_join_rows(hl, out32, rows, D, 2 * Dp, D, (hipStream_t)stream));
+    return 0;
+}
+int emmax_op_x_decode_attention(const float* q32, const void* kcache32, const void* vcache32, int64_t kv24_elems, const int32_t* page_table,
+                                const int32_t* ctx_len, const int32_t* done, float* part_out, int B, int Hq, int Hkv, int page, int max_pages, int nsplit,
+                                float scale, emmax_stream st) {
+    if (!q32 || !kcache32 || !vcache32 || !page_table || !ctx_len || !part_out) return fail(EMMAX_ERR_INVALID, "emmax_op_x_decode_attention: null argument");
+    if (B < 1 || B > EMMAX_MAX_DECODE_BATCH || Hkv < 1 || Hq % Hkv) return fail(EMMAX_ERR_INVALID, "emmax_op_x_decode_attention: bad B / heads");
+    DecodeAttnParams a;
+    memset(&a, 0, sizeof(a));
+    a.q = q32; a.ldq = Hq * 128; a.kcache = kcache32; a.vcache = vcache32; a.page_table = page_table; a.ctx_len = ctx_len; a.done = done;
+    a.part = part_out; a.Hkv = Hkv; a.page = page; a.max_pages = max_pages; a.scale = scale; a.kv24 = kv24_elems;
+    int r = launch_x_decode_attn(a, B, Hq, 128, nsplit, (hipStream_t)st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_x_decode_attention: unsupported (GQA group in {1,2,4,8}, page = 2^k, max_pages <= 512, nsplit = 2^k)");
+    return 0;
+}
+int emmax_op_gemv(const void* x, const void* W, void* y, int B, int N, int K, emmax_stream st) {
+    GemvParams p = plain_gemv(x, W, y, N, K);
+    if (decode_gemv_init() != 0) return fail(EMMAX_ERR_HIP, "could not raise the dynamic LDS limit of the GEMV kernels");
+    int r = launch_decode_gemv(GEMV_PLAIN, p, B, (hipStream_t)st);
+    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_gemv: unsupported shape (B<=8, K%%8)");
+    return 0;
+}
+
+int emmax_op_resize_bicubic_u8(const uint8_t* src, int B, int H, int W, uint8_t* dst, int OH, int OW, uint8_t* tmp,
+                               const int32_t* bounds_h, const int32_t* kk_h, int ksize_h, const int32_t* bounds_v, const int32_t* kk_v,
+                               int ksize_v, emmax_stream st) {
+    if (!src || !dst || B < 1 || H < 1 || W < 1 || OH < 1 || OW < 1) return fail(EMMAX_ERR_INVALID, "emmax_op_resize_bicubic_u8: bad argument");
+    if ((W != OW && (!bounds_h || !kk_h)) || (H != OH && (!bounds_v || !kk_v)) || (W != OW && H != OH && !tmp))
+        return fail(EMMAX_ERR_INVALID, "emmax_op_resize_bicubic_u8: missing tables / scratch");
+    int r = launch_resize_bicubic_u8(src, B, H, W, dst, OH, OW, tmp, bounds_h, kk_h, ksize_h, bounds_v, kk_v, ksize_v, (hipStream_t)st);
+    if (r) return fail(EMMAX_ERR_HIP, "emmax_op_resize_bicubic_u8: launch failed");
+    return 0;
+}
+int emmax_op_quant_fm8(const void* W, int ld, void* W8, float* scales, int N, int K, emmax_stream st) {
+    int r = launch_quant_fm8(W, ld, W8, scales, N, K, (hipStream_t)st);
+    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_quant_fm8: N %% 16, K %% 64, ld %% 8 required");
+    return 0;
+}
+int emmax_op_quant_rm8(const void* W, int ld, void* W8, float* scales, int N, int K, emmax_stream st) {
+    int r = launch_quant_rm8(W, ld, W8, scales, N, K, (hipStream_t)st);
+    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_quant_rm8: K %% 16, ld %% 8 required");
+    return 0;
+}
+int emmax_op_gemv_fp8(const void* x, const void* W8, const float* scales, void* y, int B, int N, int K, emmax_stream st) {
+    if (B < 1 || B > 2) return fail(EMMAX_ERR_INVALID, "emmax_op_gemv_fp8: batch must be 1..2");
+    if (!scales) return fail(EMMAX_ERR_INVALID, "emmax_op_gemv_fp8: scales required");
+    if (decode_gemv_init()) return fail(EMMAX_ERR_HIP, "emmax_op_gemv_fp8: init failed");
+    GemvParams p = plain_gemv(x, W8, y, N, K, scales);
+    int r = launch_decode_gemv(GEMV_PLAIN, p, B, (hipStream_t)st);
+    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_gemv_fp8: unsupported shape (K %% 16, B * K * 2 bytes of LDS)");
+    return 0;
+}
+int emmax_op_gemm_small_fp8(const void* x, const void* W8, const float* scales, void* y, int B, int N, int K, emmax_stream st) {
+    GemvParams p = plain_gemv(x, W8, y, N, K, scales);
+    if (!scales) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_small_fp8: scales required");
+    int r;
+    if (B <= 8) {   // decode_mfma.hip stages eight rows
+        if (decode_mfma_init() != 0) return fail(EMMAX_ERR_HIP, "could not raise the dynamic LDS limit of the MFMA decode kernels");
+        r = launch_decode_mfma(GEMV_PLAIN, p, B, (hipStream_t)st);
+    } else if (K > 4096) {   // 9-32 rows: the K-split kernels (natural row order: the same e4m3 tiles); the phased down form is y = h + W x: h = 0
+        HIPCHK(hipMemsetAsync(y, 0, (size_t)B * N * 2, (hipStream_t)st));
+        r = launch_decode_km(GEMV_RESID, p, B, (hipStream_t)st);
+    } else {
+        r = launch_decode_km(GEMV_PLAIN, p, B, (hipStream_t)st);
+    }
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_gemm_small_fp8: unsupported shape (N %% 16, K %% 64; 1 <= B <= 8; 9 <= B <= 32: the shapes of emmax_op_gemm_small_km)");
+    return 0;
+}
+int emmax_op_repack_fm(const void* W, int ld, void* W_fm, int N, int K, emmax_stream st) {
+    int r = launch_repack_fm(W, ld, W_fm, N, K, (hipStream_t)st);
+    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_repack_fm: N %% 16, K %% 32, ld %% 8 required");
+    return 0;
+}
+int emmax_op_repack_km(const void* W, int ld, void* W_km, int N, int K, int perm, int head_dim, emmax_stream st) {
+    int r = launch_repack_km(W, ld, W_km, N, K, perm, head_dim, (hipStream_t)st);
+    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_repack_km: N %% 16, K %% 32, ld %% 8 (perm 1: N %% head_dim, head_dim %% 16; perm 2: N %% 32) required");
+    return 0;
+}
+int emmax_op_gemm_small_km(const void* x, const void* W_km, void* y, int B, int N, int K, emmax_stream st) {
+    GemvParams p = plain_gemv(x, W_km, y, N, K);
+    int r;
+    if (K > 4096) {   // the phased kernel of the down projection (y = h + W x): h = 0
+        HIPCHK(hipMemsetAsync(y, 0, (size_t)B * N * 2, (hipStream_t)st));
+        r = launch_decode_km(GEMV_RESID, p, B, (hipStream_t)st);
+    } else {
+        r = launch_decode_km(GEMV_PLAIN, p, B, (hipStream_t)st);
+    }
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_gemm_small_km: unsupported shape (1 <= B <= 32, N %% 16; K %% 256 and K <= 4096 and N <= 32768, or the phased form: K %% 32, K <= 11264 at B <= 8, 12288 at B <= 16; B > 16: K %% 32, K <= 11264, N <= 4096 there)");
+    return 0;
+}
+int emmax_op_gemm_small(const void* x, const void* W_fm, void* y, int B, int N, int K, emmax_stream st) {
+    GemvParams p = plain_gemv(x, W_fm, y, N, K);
+    if (decode_mfma_init() != 0) return fail(EMMAX_ERR_HIP, "could not raise the dynamic LDS limit of the MFMA decode kernels");
+    int r = launch_decode_mfma(GEMV_PLAIN, p, B, (hipStream_t)st);
+    if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_small: unsupported shape (1 <= B <= 8, N %% 16, K %% 32)");
+    return 0;
+}
+
+
+}  // extern "C"

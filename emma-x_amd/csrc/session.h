@@ -1,0 +1,306 @@
+// session.h -- what the host files of libemmax_hip.so share (model / session / vision / prefill / step / generate / modes / ops .hip): the
+// model and session structs, the error helpers, the KV-cache accessors, the way into and out of the session's stream, and the prototypes of
+// the functions that cross files.  Internal: not installed, no device code.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "../../include/emmax.h"
+#include "common.h"
+#include "kernels.h"
+
+// ---- errors (model.hip) --------------------------------------------------------------------------------------------
+#pragma GCC visibility push(hidden)   // what crosses the host files stays out of the library's exported symbols (as does the last section)
+extern thread_local std::string g_err;   // what emmax_last_error reports
+int fail(int code, const char* fmt, ...);
+#pragma GCC visibility pop
+#define HIPCHK(x)                                                                                                   \
+    do {                                                                                                            \
+        hipError_t e_ = (x);                                                                                        \
+        if (e_ != hipSuccess) return fail(EMMAX_ERR_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+#define KCHK(x)                                                                                                     \
+    do {                                                                                                            \
+        int r_ = (x);                                                                                               \
+        if (r_ != 0) return fail(r_ == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "%s failed (%d) (%s:%d)", #x, r_, __FILE__, __LINE__); \
+    } while (0)
+
+static inline int pad_to(int x, int m) { return (x + m - 1) / m * m; }
+static const int PAGE = 64;   // KV page: 64 tokens x head_dim bf16 per kv head
+
+typedef uint16_t bf16;
+
+// Bump plan of the weight arenas and the session workspace.  `base == nullptr` only sizes.  Every tensor is 256-byte aligned.
+struct Bump {
+    char* base;
+    int64_t off = 0;
+    void* bytes(int64_t n) {
+        off = (off + 255) / 256 * 256;
+        void* p = base ? (void*)(base + off) : nullptr;
+        off += n;
+        return p;
+    }
+    bf16* take(int64_t elems) { return (bf16*)bytes(elems * 2); }
+};
+
+// ---- model ---------------------------------------------------------------------------------------------------------
+struct Bound {
+    const void* ptr;
+    int dtype;
+    std::vector<int64_t> shape;
+    int64_t numel() const {
+        int64_t n = 1;
+        for (auto s : shape) n *= s;
+        return n;
+    }
+};
+
+struct BlockW {
+    bf16 *n1w, *n1b, *qkv_w, *qkv_b, *proj_w, *proj_b, *ls1, *n2w, *n2b, *fc1_w, *fc1_b, *fc2_w, *fc2_b, *ls2;
+    float *ln1_s, *ln1_c, *ln2_s, *ln2_c;   // LayerNorm folded into qkv / fc1 (kernels.h: GemmParams::ln_*): column sums of W' and the constant term
+};
+struct TowerW {
+    int D, Dp, D3p, M, Mp, N, n_prefix, n_patches, hd, Kpe, n_blocks;
+    bf16 *patch_w, *patch_b, *pos, *cls, *reg;
+    std::vector<BlockW> blk;
+};
+
+// the stages of a decoder layer (the unit the profiler times); the step is stages 0..4 of every layer + the lm-head
+enum { STAGE_QKV = 0, STAGE_ATTN = 1, STAGE_OPROJ = 2, STAGE_GATEUP = 3, STAGE_DOWN = 4, STAGE_LMHEAD = 5 };
+// bits of the tuning switch fp8_gemv (step.hip: fp8_gemv_mask)
+enum { F8_QKV = 1, F8_OPROJ = 2, F8_GATEUP = 4, F8_DOWN = 8, F8_LMHEAD = 16 };
+
+// One decode projection: every copy of its matrix, and how the step launches it (step.hip: launch_proj)
+struct ProjW {
+    bf16 *rm, *fm;   // row-major (prefill GEMMs, batch 1-2 GEMV); MFMA-fragment-major for the B >= 3 decode path (fp8 mode: e4m3 tiles)
+    bf16* km;        // ... in the row order of decode_km.hip (qkv: RoPE pairs, gate-up: (gate, up) pairs inside a 16-row tile); o-proj / down /
+                     // lm-head: that kernel reads the natural order -- the same pointer as fm
+    bf16* r8;        // fp8 mode: the same e4m3 values as rows in the GEMV's span order (batch 1-2)
+    float *sc, *km_sc;      // fp8 mode: per-row scales (null otherwise), and those of km in its row order
+    int gemv_mode, f8bit;   // GEMV_QKV / GEMV_RESID / GEMV_GATEUP / GEMV_LMHEAD, and its bit of the tuning switch fp8_gemv
+};
+struct LayerW {
+    bf16 *ln1, *ln2;
+    ProjW proj[STAGE_DOWN + 1];   // by stage: STAGE_QKV, STAGE_OPROJ, STAGE_GATEUP, STAGE_DOWN
+};
+
+struct emmax_model {
+    emmax_config cfg;
+    std::unordered_map<std::string, Bound> bound;
+    bool finalized = false;
+    // derived dims
+    int H, inter, inter_p, q_dim, kv_dim, qkv_dim, vocab, vocab_p, V, Vp, P1, P1p;
+    TowerW tw[2];
+    bf16 *pj1_w, *pj1_b, *pj2_w, *pj2_b, *pj3_w, *pj3_b;
+    bf16 *embed, *final_norm;
+    ProjW lm_head_w = {};
+    bool fp8 = false;
+    bool ln_folded = false;      // the ViT LayerNorms are folded into the qkv / fc1 weights (tuning switch gemm_lnfuse at finalize)
+    bool aux_built = false;      // the batch >= 3 copies exist (fp8 models: always, they are part of the main arena)
+    bool aux_ab = false;         // ... including decode_mfma.hip's qkv / gate-up pair
+    std::vector<LayerW> layers;
+};
+
+// ---- session -------------------------------------------------------------------------------------------------------
+// The small pinned host buffer: the done read-back of emmax_generate, and the staging area that every control upload goes through
+// (modes.hip: upload_rows) -- UPLOAD_ROWS rows of the widest parameter set, sampling's four 4-byte columns and its 8-byte seed.
+enum { UPLOAD_ROWS = 256, PINNED_BYTES = 4096 * 4 };
+struct Pinned {
+    int32_t done[EMMAX_MAX_DECODE_BATCH];
+    alignas(8) char upload[UPLOAD_ROWS * (4 * 4 + 8)];
+};
+static_assert(sizeof(Pinned) <= PINNED_BYTES, "the pinned buffer's layout outgrew its allocation");
+
+// SAMPLING (emmax_session_set_sampling; the sampled finish, sample.hip): per-row parameters of every row, staging rows included, and the
+// log-probability rows beside out_ids.  Off: none of it is touched and a step launches what a greedy session launches
+struct Sampling {
+    bool on = false;
+    float *t, *p, *logprob /* [rows_total][max_out] */;
+    int32_t* k;
+    uint64_t* seed;
+    uint32_t* sub;
+};
+// LOGITS PROCESSING (emmax_session_set_processing; the processing finish, sample.hip): per-row repetition penalty, n-gram size and
+// min-new-tokens of every row, staging rows included, and each row's prompt ids (every prefill fills them while processing is on).
+struct Processing {
+    bool on = false;
+    float* pen;
+    int32_t *ng, *mn, *hist /* [rows_total][max_prompt] */, *hist_len;
+};
+// SCORES (emmax_session_set_scores): device words {scores, logits, max_new, rows} the processing finish stores through.  Processing or scores
+// on: the step runs on the logit rows and ends in the processing finish.  Both off: none of it is touched
+struct Scores {
+    bool on = false, has_scores = false;
+    int rows = 0;   // rows of the bound score buffers: the batch of the first prefill after the binding (0: none yet)
+    uint64_t* words;
+};
+// BEAM SEARCH (emmax_session_set_beams; beam.hip): K beams per group, 0 = off.  Rows g K + k are the running beams of group g; the per-row
+// candidate lists of a step, HF's running / finished state, the groups' words, the page bookkeeping (spare page and copy list per row), the
+// trace [max_out][max_batch] and the resolved result.  Beams off: none of it is touched
+struct Beams {
+    int K = 0, G = 0, es = 0, lp_pos = 0, eos = -1, max_new = 0;
+    bool forked = false, ready = false;
+    float *cand_acc, *row_lse, *run, *fin_score, *pw, *tr_score, *tr_lse, *tc_acc, *res_score;
+    int32_t *cand_tok, *fin_flag, *fin_t, *fin_par, *fin_tok, *grp, *spare, *csrc, *cdst, *cntok, *tr_tok, *tr_par, *tc_idx, *res_bidx, *res_len;
+};
+
+struct emmax_session {
+    emmax_model* m;
+    int max_batch, max_prompt, max_ctx, max_pages, max_rows /* packed prefill rows */, max_out;
+    // STAGING rows (overlapped admission, emmax_slots_prefill_staged): every per-row array and the paged KV region hold
+    // rows_total = max_batch + n_stg rows; rows stg0 .. are never part of a decode batch -- a request is prefilled into them on a
+    // second stream while the live rows keep decoding, and emmax_slots_commit moves it into its slot between two decode steps
+    // (state copied, page-table rows swapped: no K/V moves)
+    int rows_total, stg0, n_stg;
+    // vision scratch
+    bf16 *vA, *vpe, *vtok, *vln, *vqkv, *vatt, *vmlp, *feats, *pj1, *pj2, *patch_embeds;
+    float* vstats;              // LayerNorm (mean, rstd) of every token row, f32 [rows][2]
+    int32_t* cu_vit[2];
+    // a SECOND set of tower scratch for up to vis2_B frames (round 5): the two towers do not depend on each other, and at small batches each
+    // is a chain of under-filled, launch-latency-bound kernels (one frame: ~360 launches of ~14 us) -- tower 1 runs on the session's vision
+    // stream beside tower 0 (run_vision; tuning switch vis_streams)
+    bf16 *v2A, *v2pe, *v2tok, *v2ln, *v2qkv, *v2att, *v2mlp;
+    float *v2stats, *v2splitk_ws;
+    int64_t v2splitk_bytes;
+    int vis2_B = 0;
+    hipStream_t vis_stream = nullptr;
+    hipEvent_t ev_vfork = nullptr, ev_vjoin = nullptr;
+    // prefill scratch
+    bf16 *ph, *pxn, *pqkv, *patt, *pact;
+    float* ph32;                // the prefill's residual stream in fp32 (tuning switch resid32 = 1), [max_rows][H]
+    bool p32 = false;           // the last prefill ran on ph32 (what emmax_prefill_logits normalises)
+    int32_t* cu;
+    // decode
+    bf16 *dh, *dq, *datt, *dact;
+    float* dh32;                // the decode step's residual stream in fp32 (tuning switch resid32; GemvParams::h32), [rows_total][H]
+    float *part, *part_val, *part_val2 /* lm-head argmax partials of a staged prefill */;
+    // the fp32 logit rows of every row an lm-head can emit into (a staged prefill's rows are its own: it runs beside the live step): what the
+    // sampled, processing and beam finishes read
+    float* logits;              // f32 [rows_total][vocab]
+    Sampling samp;
+    Processing proc;
+    Scores scores;
+    Beams beam;
+    int32_t *part_idx2;
+    int32_t *part_idx, *cur_tok, *ctx_len, *done, *n_out, *out_ids, *max_new_d /* [max_batch] */, *page_table;
+    // EXACT NUMERICS (round 6; tuning switch `exact` at emmax_session_create): fp32 activations end to end.  x32a: the fp32 result of the GEMM
+    // in flight (qkv rows, SwiGLU product, fc1 output ...); xhla / xhlb: the two-term bf16 ("HL") A operands, ping-pong; xtok32: the ViT's fp32
+    // token rows; xfeats32 / xpe32: fp32 tower features / projected patch embeddings; dq32 / dact32: the decode step's fp32 q rows and SwiGLU
+    // product.  The paged KV region holds fp32 rows (twice the bytes of the bf16 cache).
+    bool exact = false;
+    int kv_fmt = 0;             // KV_BF16 / KV_FP8 / KV_F32 / KV_X24 (kv_format_now() at emmax_session_create)
+    long long kv24 = 0;         // KV_X24: elements of one operand's plane of a layer (GemvParams::kv24), else 0
+    float *x32a = nullptr, *xtok32 = nullptr, *xfeats32 = nullptr, *xpe32 = nullptr, *dq32 = nullptr, *dact32 = nullptr;
+    bf16 *xhla = nullptr, *xhlb = nullptr;
+    float* splitk_ws;           // fp32 partial tiles of split-K GEMMs (gemm.hip)
+    int64_t splitk_bytes;
+    unsigned long long* sk_ws = nullptr;     // device: stream-K granules of the MFMA decode projections (decode_mfma.hip), all zero between launches
+    unsigned long long* sk_ws2 = nullptr;    // ... of a STAGED prefill's lm-head: it runs on a second stream beside the live decode steps, and the
+                                             // granules are indexed by block id only -- two concurrent launches on one workspace would consume or
+                                             // clear each other's partial sums
+    int32_t *stop_ids /* [EMMAX_MAX_STOP_IDS] */, *stop_cfg /* {n_trigger, n_after} */, *stop_m, *stop_after;
+    bool slots_open = false;    // slot serving mode: rows are independent request slots (emmax_slots_open)
+    float *cos_t, *sin_t;
+    int n_lm_blocks;
+    // kv
+    bf16* kv;
+    int64_t kv_layer_stride;   // BYTES between layers.  bf16 cache: K at +0, V at +stride/2.  fp8 cache (kv8): K bytes, V bytes, K scales, V scales
+    bool kv8 = false;          // the cache holds e4m3 rows + one fp32 scale per (token, kv head) row (tuning switch kv_fp8 at emmax_session_create)
+    bf16* kv_stage = nullptr;  // kv8: the step's new K / V rows, bf16 [rows_total][Hkv][2][head_dim] (qkv launch -> attention launch)
+    // host state
+    int cur_B = 0, total_rows = 0, max_seqlen = 0, vision_B = 0;
+    int dec_steps = 0;          // decode steps issued since the last full prefill (upper bound of every row's context growth)
+    bool prefilled = false;
+    std::vector<int> S;         // per-row prefill lengths
+    Pinned* pinned = nullptr;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t graph_exec = nullptr;
+    hipStream_t graph_stream_cap = nullptr;  // stream the graphs were captured on
+    int graph_B = 0;
+    int graph_failed = 0;
+    int last_step_graph = 0;   // the most recent decode step was a graph replay (what emmax_session_graph_active reports)
+    hipEvent_t ev = nullptr;
+    int graph_epoch = -1;      // emmax_tune().epoch the graph was captured under (a changed switch re-captures)
+    int graph_mode = 0;   // finish_mode() the step was captured under (the parameters and score buffers are device words: a change re-captures nothing)
+    hipStream_t own_stream = nullptr;   // where a call made on the (uncapturable) legacy stream runs: StreamScope
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    std::string graph_err;
+};
+
+// paged KV region: per layer K and V, rows x pages x kv heads x 64 tokens x head_dim elements -- bf16, or (kv8) e4m3 bytes + a 4-byte scale per row
+// format of the paged cache: bf16 rows; e4m3 rows + a scale (kv_fp8); exact numerics: 24-bit rows (exact = 1: a bf16 plane + an 8-bit extension plane per
+// operand = the top 24 bits of the fp32 value, 2^-16 relative, 1.5 x the bf16 bytes) or fp32 rows (exact = 2: 2 x the bytes -- the A/B partner)
+enum { KV_BF16 = 0, KV_FP8 = 1, KV_F32 = 2, KV_X24 = 3 };
+static inline int kv_elem_bytes(int fmt) { return fmt == KV_F32 ? 4 : fmt == KV_X24 ? 3 : fmt == KV_FP8 ? 1 : 2; }
+static inline int64_t kv_rows_per_layer(const emmax_model* m, int rows, int max_pages) { return (int64_t)rows * max_pages * m->cfg.n_kv_heads * PAGE; }
+static inline char* kv_layer(emmax_session* s, int layer) { return (char*)s->kv + (size_t)layer * s->kv_layer_stride; }
+static inline int64_t kv_rows(emmax_session* s) { return kv_rows_per_layer(s->m, s->rows_total, s->max_pages); }
+static inline bf16* kcache_of(emmax_session* s, int layer) { return (bf16*)kv_layer(s, layer); }
+static inline bf16* vcache_of(emmax_session* s, int layer) { return (bf16*)(kv_layer(s, layer) + kv_rows(s) * s->m->cfg.head_dim * kv_elem_bytes(s->kv_fmt)); }
+static inline float* kscale_of(emmax_session* s, int layer) { return (float*)(kv_layer(s, layer) + 2 * kv_rows(s) * s->m->cfg.head_dim); }   // kv8 only
+static inline float* vscale_of(emmax_session* s, int layer) { return kscale_of(s, layer) + kv_rows(s); }
+// the hidden rows of a decode step: the fp32 stream (tuning switch resid32, the default) or the bf16 rows of rounds 1-4
+// (resid32: 0 = bf16 rows everywhere, 1 = fp32 stream in the prefill and the decode step, 2 = in the decode step only)
+static inline float* h32_of(emmax_session* s, int slot0 = 0) { return emmax_tune().resid32 ? s->dh32 + (size_t)slot0 * s->m->H : nullptr; }
+
+// ---- the way into the session's stream, and the functions that cross files -----------------------------------------
+#pragma GCC visibility push(hidden)
+// The way into and out of the session's stream.  The legacy / per-thread default streams cannot be captured: a call made on one of them runs on
+// the session's own stream, ordered after everything already queued on the caller's stream (the constructor) and before anything queued on it
+// afterwards (leave).  A call that returns early with an error never reaches leave(): the destructor re-joins the caller's stream then, so
+// that it does not run ahead of what the call had queued (errors ignored)
+class StreamScope {
+public:
+    StreamScope(emmax_session* s, emmax_stream user) : s_(s), user_((hipStream_t)user), st_(user_) { err_ = enter(); }
+    StreamScope(const StreamScope&) = delete;   // (one way in, one way out)
+    ~StreamScope() { if (st_ != user_ && hipEventRecord(s_->ev_out, st_) == hipSuccess) (void)hipStreamWaitEvent(user_, s_->ev_out, 0); }
+    int error() const { return err_; }   // of the way in: nothing was queued, the call returns it
+    hipStream_t stream() const { return st_; }
+    int leave() {
+        const hipStream_t st = st_;
+        st_ = user_;   // joined below, or failing: nothing left for the destructor
+        if (st != user_) {
+            HIPCHK(hipEventRecord(s_->ev_out, st));
+            HIPCHK(hipStreamWaitEvent(user_, s_->ev_out, 0));
+        }
+        return 0;
+    }
+
+private:
+    int enter() {
+        if ((uintptr_t)user_ > 2) return 0;
+        HIPCHK(hipEventRecord(s_->ev_in, user_));
+        HIPCHK(hipStreamWaitEvent(s_->own_stream, s_->ev_in, 0));
+        st_ = s_->own_stream;
+        return 0;
+    }
+    emmax_session* s_;
+    hipStream_t user_, st_;
+    int err_;
+};
+
+// vision.hip: GEMM parameters -- plain; of a session stage (with the session's split-K scratch); of an exact-numerics stage (HL rows in, fp32 out)
+GemmParams gp(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K);
+GemmParams gps(emmax_session* s, const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K);
+GemmParams gpx(emmax_session* s, const void* A_hl, int Kp, const void* W, int ldw, float* C, int ldc, int M, int N);
+// prefill.hip
+int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B, int P_max, const void* patches, hipStream_t st, int slot0 = -1);
+// step.hip
+int model_max_decode_batch(const emmax_model* m);
+bool beam_pages_fit(const emmax_session* s, int S, int max_new);
+int launch_beam_finish(emmax_session* s, bool is_prefill, hipStream_t st);
+int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* logits_out, bool do_finish, hipStream_t st, int slot0 = 0);
+int run_decode_stage(emmax_session* s, int B, int li, int stage, hipStream_t st);
+int run_decode_step(emmax_session* s, int B, hipStream_t st);
+int ensure_graph(emmax_session* s, int B, hipStream_t st);
+int launch_graph_step(emmax_session* s, int B, hipStream_t st);
+void drop_graph(emmax_session* s);
+
+#pragma GCC visibility pop

@@ -1,0 +1,461 @@
+// step.hip -- one decode step: the projection dispatch (launch_proj), the stages of a decoder layer, the lm-head step and the four ways
+// a step ends (greedy / sampled / processing / beam finish), and the capture and replay of the step as a hipGraph.
+#include "session.h"
+
+// tuning switch streamk = 0 gives every MFMA decode block whole tasks (the split before stream-K)
+static bool streamk_on() { return emmax_tune().streamk != 0; }
+
+// tuning switch fp8_gemv = bit mask of the batch 1-2 fp8 projections that run as dot-product GEMV over the e4m3 row copy
+// (1 qkv, 2 o-proj, 4 gate/up, 8 down, 16 lm-head); the others go through the MFMA kernels like every larger batch.
+// Default (round 3, once the K-split MFMA kernels of decode_km.hip existed): the o-proj, and at batch 1 the lm-head.  Per launch
+// at B = 1 / B = 2, row GEMV against decode_km.hip (one box, tools/ab_bench.sh): qkv 14.1 / 17.3 against 12.5 / 12.7 us, gate/up
+// 17.9 / 20.3 against 17.1 / 17.1, down (always MFMA) 11.9, o-proj 7.7 / 9.8 against 8.4 / 10.7, lm-head 25.0 / 28.7 against
+// 25.7 / 24.4: step 1.939 -> 1.886 ms/token at B = 1 with everything on the MFMA kernels, 2.287 -> 2.028 at B = 2.
+static int fp8_gemv_mask(int B) {
+    const int mask = emmax_tune().fp8_gemv;
+    if (mask >= 0) return mask & 31;
+    return B == 1 ? (F8_OPROJ | F8_LMHEAD) : F8_OPROJ;
+}
+
+// One projection of the step (ProjW, session.h).  B <= 2: per-lane dot-product GEMV over the row-major weights (fp8 mode: over the e4m3 row
+// copy w.r8); B >= 3: MFMA over the fragment-major copy.  w.km / w.km_sc: the matrix in decode_km.hip's layout (null: that kernel does not
+// serve this projection)
+static int launch_proj(const ProjW& w, GemvParams& p, int B, hipStream_t st, int* grid_out) {
+    const int mode = w.gemv_mode;
+    if (p.exact) {   // exact numerics: the two-term forms or nothing -- decode_ks.hip at batch 1-2, decode_km.hip's EX kernels at batch 3-8
+        int r = -2;
+        if (!w.sc && B < EMMAX_MFMA_MIN_BATCH) {
+            p.W = w.rm;
+            r = launch_decode_ks(mode, p, B, st, grid_out);
+        } else if (!w.sc && w.km) {
+            GemvParams q = p;
+            q.W = w.km;
+            r = launch_decode_km(mode, q, B, st, grid_out);
+        }
+        return r == -2 ? fail(EMMAX_ERR_INVALID, "exact numerics: no two-term kernel for this projection (batch %d, K %d)", B, p.K) : r;
+    }
+    if (B < EMMAX_MFMA_MIN_BATCH && w.sc && w.r8 && (fp8_gemv_mask(B) & w.f8bit) && decode_gemv_fp8_fits(B, p.K)) {
+        p.W = w.r8;
+        p.wscale = w.sc;
+        p.ldw = p.K;   // bytes per row
+        return launch_decode_gemv(mode, p, B, st, grid_out);
+    }
+    if (B >= EMMAX_MFMA_MIN_BATCH || w.sc) {
+        // K-split MFMA kernel (decode_km.hip): batch >= 3, and with fp8 weights every batch the row GEMV above did not take
+        if ((B >= EMMAX_MFMA_MIN_BATCH || w.sc) && w.km && decode_km_enabled()) {
+            GemvParams q = p;
+            q.W = w.km;
+            q.wscale = w.sc ? w.km_sc : nullptr;
+            const int r = launch_decode_km(mode, q, B, st, grid_out);
+            if (r != -2) return r;
+        }
+        if (!w.fm) return fail(EMMAX_ERR_STATE, "decode_mfma.hip's copy of this matrix was not built (tuning switch km was 1 at emmax_model_build_aux)");
+        p.W = w.fm;
+        p.wscale = w.sc;
+        return launch_decode_mfma(mode, p, B, st, grid_out);
+    }
+    p.W = w.rm;
+    return launch_decode_gemv(mode, p, B, st, grid_out);
+}
+
+// Decode batches of 9-16 rows exist on decode_km.hip only (decode_mfma.hip, the fallback for other shapes, stages eight rows): the
+// model's projections must be shapes that kernel takes -- K a multiple of 256 and <= 4096 for qkv / o-proj / gate-up / lm-head, at
+// most 8 tiles per block (N <= 32768), the down projection within four phases of 12 fragments per wave (K <= 12288).
+int model_max_decode_batch(const emmax_model* m) {
+    const auto& c = m->cfg;
+    const bool k_ok = m->H % 256 == 0 && m->H <= 4096 && m->q_dim % 256 == 0 && m->q_dim <= 4096;
+    const bool n_ok = m->qkv_dim % 16 == 0 && m->qkv_dim <= 32768 && 2 * m->inter_p <= 32768 && m->vocab_p <= 32768 && m->H % 16 == 0 && c.head_dim % 16 == 0;
+    const int kd = m->fp8 ? 64 : 32;
+    const bool d_ok = m->inter_p % kd == 0 && m->inter_p / kd >= 8 && (m->inter_p / kd + 7) / 8 <= (m->fp8 ? 24 : 48) && m->inter_p > 4096;
+    if (!(k_ok && n_ok && d_ok && decode_km_enabled() && emmax_tune().km_down)) return 8;
+    // 17-32 rows: decode_kmp.hip -- the down projection within eleven phases of 128 elements per wave (K in whole load steps of 32
+    // elements, 64 with fp8 tiles; the widest wave share <= 1408 elements: K <= 11264), one tile per block there (H <= 4096)
+    const bool p_ok = ((m->inter_p / kd + 7) / 8) * kd <= 11 * 128 && m->H <= 4096 && m->H / 16 <= 256;
+    // batches of 9-32 rows exist in the ONE-split direct attention form only: with split partials (tuning switches attn_direct = 0 or a
+    // forced attn_nsplit > 1) the o-proj would carry p.attn_part, which the bf16 decode_km / decode_kmp kernels do not take
+    if (emmax_tune().attn_direct == 0 || decode_attn_nsplit(9, c.n_kv_heads) != 1) return 8;
+    return p_ok ? EMMAX_MAX_DECODE_BATCH : 16;
+}
+
+// one KV split per (row, head) (batch >= 5 at 32 heads): nothing to merge -- the attention launch normalises and writes the bf16 row
+// itself and the o-proj is a plain projection; otherwise the o-proj prologue merges the split partials.
+static bool attn_direct_on(const emmax_session* s, int B) {
+    // exact numerics: the fp32 row in place over the q rows, at batch >= 3 (decode_km.hip's EX o-proj takes fp32 rows; decode_ks.hip's merges the partials)
+    if (s->exact && B < EMMAX_MFMA_MIN_BATCH) return false;
+    return decode_attn_nsplit(B, s->m->cfg.n_kv_heads) == 1 && emmax_tune().attn_direct != 0;
+}
+
+// GemvParams of a projection stage of decoder layer `li` (qkv / o-proj / gate-up / down), as every launcher takes them
+static void stage_params(emmax_session* s, int B, int li, int stage, GemvParams& p) {
+    emmax_model* m = s->m;
+    const auto& c = m->cfg;
+    const LayerW& L = m->layers[li];
+    memset(&p, 0, sizeof(p));
+    p.sk_ws = streamk_on() ? s->sk_ws : nullptr;
+    if (stage != STAGE_ATTN) { p.h32 = h32_of(s); p.ldh = m->H; }   // qkv / gate-up read the hidden rows, o-proj / down add into them
+    if (s->exact) { p.exact = 1; p.h32 = s->dh32; p.ldh = m->H; }
+    switch (stage) {
+        case STAGE_QKV:
+            p.x = s->dh; p.ldx = m->H; p.ldw = m->H; p.K = m->H; p.norm_w = L.ln1; p.eps = c.rms_eps;
+            p.y = s->dq; p.ldy = m->q_dim; p.n_rows = m->qkv_dim;
+            p.head_dim = c.head_dim; p.Hq = c.n_heads; p.Hkv = c.n_kv_heads; p.page = PAGE; p.max_pages = s->max_pages;
+            p.ctx_len = s->ctx_len; p.page_table = s->page_table; p.cos_t = s->cos_t; p.sin_t = s->sin_t;
+            p.kcache = kcache_of(s, li); p.vcache = vcache_of(s, li);
+            p.kv_stage = s->kv8 ? s->kv_stage : nullptr;   // fp8 KV cache: the new rows wait as bf16 for the attention launch
+            if (s->exact) { p.y = s->dq32; p.kv24 = s->kv24; }   // fp32 q rows; kcache / vcache are the 24-bit (or fp32) cache
+            break;
+        case STAGE_OPROJ:
+            p.x = s->datt; p.ldx = m->q_dim; p.ldw = m->q_dim; p.K = m->q_dim; p.y = s->dh; p.ldy = m->H; p.n_rows = m->H;
+            if (!attn_direct_on(s, B)) {   // split merge fused into the staging
+                p.attn_part = s->part; p.nsplit = decode_attn_nsplit(B, c.n_kv_heads); p.Hq = c.n_heads;
+            } else if (s->exact) {
+                p.x = s->dq32;             // the attention launch left the normalised fp32 rows in place of the q rows
+            }
+            break;
+        case STAGE_GATEUP:
+            p.x = s->dh; p.ldx = m->H; p.ldw = m->H; p.K = m->H; p.norm_w = L.ln2; p.eps = c.rms_eps;
+            p.y = s->dact; p.ldy = m->inter_p; p.n_rows = 2 * m->inter_p;
+            if (s->exact) p.y = s->dact32;
+            break;
+        case STAGE_DOWN:
+            p.x = s->dact; p.ldx = m->inter_p; p.ldw = m->inter_p; p.K = m->inter_p; p.y = s->dh; p.ldy = m->H; p.n_rows = m->H;
+            if (s->exact) p.x = s->dact32;
+            break;
+        default: break;
+    }
+}
+static void lmhead_params(emmax_session* s, int slot0, float* logits_out, GemvParams& p) {
+    emmax_model* m = s->m;
+    memset(&p, 0, sizeof(p));
+    p.sk_ws = streamk_on() ? (slot0 >= s->stg0 ? s->sk_ws2 : s->sk_ws) : nullptr;
+    p.x = s->dh + (size_t)slot0 * m->H; p.ldx = m->H; p.ldw = m->H; p.K = m->H; p.norm_w = m->final_norm; p.eps = m->cfg.rms_eps;
+    p.h32 = h32_of(s, slot0); p.ldh = m->H;
+    if (s->exact) { p.exact = 1; p.h32 = s->dh32 + (size_t)slot0 * m->H; }
+    const bool stg = slot0 >= s->stg0;
+    p.n_rows = m->vocab; p.max_parts = s->n_lm_blocks; p.part_val = stg ? s->part_val2 : s->part_val; p.part_idx = stg ? s->part_idx2 : s->part_idx;
+    p.logits_out = logits_out;
+}
+
+// how a step ends (the captured graph is keyed on it: the finish's parameters differ in each): bit 0 sampling, bit 1 processing, bit 2
+// scores.  0: the greedy finish (lm-head argmax partials); 1: the sampled finish; bit 1 or 2 set: the processing finish
+// beams on: bit 3, stop_on_eos in bit 4, K and the early-stopping mode above (the beam finish holds them by value)
+static int finish_mode(const emmax_session* s) {
+    return (s->samp.on ? 1 : 0) | (s->proc.on ? 2 : 0) | (s->scores.on ? 4 : 0) |
+           (s->beam.K ? (8 | (s->beam.eos >= 0 ? 16 : 0) | (s->beam.K << 5) | (s->beam.es << 10) | (s->beam.lp_pos << 12)) : 0);
+}
+
+// the per-row state of rows slot0 .. slot0 + B that a finish updates
+static void finish_rows(emmax_session* s, int B, bool is_prefill, int slot0, FinishParams& f) {
+    emmax_model* m = s->m;
+    f.B = B;
+    f.cur_tok = s->cur_tok + slot0; f.ctx_len = s->ctx_len + slot0; f.done = s->done + slot0; f.n_out = s->n_out + slot0;
+    f.out_ids = s->out_ids + (size_t)slot0 * s->max_out;
+    f.max_new_p = s->max_new_d + slot0; f.max_out = s->max_out; f.max_ctx = s->max_ctx;
+    f.stop_ids = s->stop_ids; f.stop_cfg = s->stop_cfg; f.stop_m = s->stop_m + slot0; f.stop_after = s->stop_after + slot0;
+    f.eos_id = m->cfg.eos_id; f.pad_id = m->cfg.pad_id; f.is_prefill = is_prefill ? 1 : 0;
+}
+
+// finish of a step over rows slot0 .. slot0 + B: argmax over the n_part lm-head partials, EOS / budget / stop rule, next token
+static int launch_finish_step(emmax_session* s, int B, bool is_prefill, int n_part, int slot0, hipStream_t st) {
+    FinishParams f;
+    memset(&f, 0, sizeof(f));
+    // the partial count is the grid the launch really used (every launcher reports it): a count modelled separately went
+    // stale when a launcher capped its grid (fp8 row GEMV shapes 1/2, EMMAX_GEMV_GRID) and stale partials could win the argmax
+    if (n_part <= 0 || n_part > s->n_lm_blocks) return fail(EMMAX_ERR_STATE, "lm-head launch reported no partial count");
+    const bool stg = slot0 >= s->stg0;   // a staged prefill runs beside the live batch's decode steps: its own partial buffers
+    f.part_val = stg ? s->part_val2 : s->part_val; f.part_idx = stg ? s->part_idx2 : s->part_idx; f.n_part = n_part;
+    finish_rows(s, B, is_prefill, slot0, f);
+    KCHK(launch_decode_finish(f, st));
+    return 0;
+}
+
+// the sampling parameters of rows slot0 .. in a finish's parameter struct (SampleFinishParams / ProcFinishParams: the same five fields)
+template <class P>
+static void sampling_rows(emmax_session* s, int slot0, P& p) {
+    p.temperature = s->samp.t + slot0; p.top_k = s->samp.k + slot0; p.top_p = s->samp.p + slot0;
+    p.seed = s->samp.seed + slot0; p.subseq = s->samp.sub + slot0;
+}
+
+// finish of a SAMPLED step over rows slot0 .. slot0 + B: each row's draw from its complete fp32 logit row (the lm-head launch just before
+// wrote them, on the same stream), then the same bookkeeping
+static int launch_sampled_finish_step(emmax_session* s, int B, bool is_prefill, int slot0, const float* logits, hipStream_t st) {
+    SampleFinishParams p;
+    memset(&p, 0, sizeof(p));
+    finish_rows(s, B, is_prefill, slot0, p.f);
+    p.logits = logits; p.ld = s->m->vocab; p.V = s->m->vocab;
+    sampling_rows(s, slot0, p);
+    p.logprob = s->samp.logprob + (size_t)slot0 * s->max_out;
+    KCHK(launch_sample_finish(p, st));
+    return 0;
+}
+
+// finish of a step with logits processing or scores on: the processors, then the draw (sampling on) or the argmax, then the scores store
+static int launch_proc_finish_step(emmax_session* s, int B, bool is_prefill, int slot0, const float* logits, hipStream_t st) {
+    ProcFinishParams p;
+    memset(&p, 0, sizeof(p));
+    finish_rows(s, B, is_prefill, slot0, p.f);
+    p.logits = logits; p.ld = s->m->vocab; p.V = s->m->vocab;
+    if (s->samp.on) sampling_rows(s, slot0, p);   // else temperature stays null: every row greedy
+    p.logprob = s->samp.logprob + (size_t)slot0 * s->max_out;
+    p.row0 = slot0;
+    if (s->proc.on) {
+        p.penalty = s->proc.pen + slot0; p.ngram = s->proc.ng + slot0; p.min_new = s->proc.mn + slot0;
+        p.hist = s->proc.hist + (size_t)slot0 * s->max_prompt; p.hist_len = s->proc.hist_len + slot0; p.max_prompt = s->max_prompt;
+    }
+    if (s->scores.on) p.score_words = s->scores.words;
+    KCHK(launch_proc_finish(p, st));
+    return 0;
+}
+
+// pages a group of K beams uses for a context of S tokens and max_new generated ones, against the K rows' share (include/emmax.h): the
+// prompt's pages, a private page per beam from the prompt's partial page on, one more per beam at every page boundary, K spares
+bool beam_pages_fit(const emmax_session* s, int S, int max_new) {
+    const int K = s->beam.K, rem = S % PAGE;
+    long long need = (S + PAGE - 1) / PAGE + (rem > 0 ? K - 1 : K) + K;
+    for (int L = S + 1; L <= S + max_new - 1; ++L)
+        if (L % PAGE == 0) need += K;
+    return S + max_new <= s->max_ctx && need <= (long long)K * s->max_pages;
+}
+
+// the tail of a step with beams on (beam.hip): per-row candidates, the groups' merge + state + page-table gather, the partial-page copies.
+// is_prefill: the first beam step, from the prefill's one logit row per group, and the fork
+int launch_beam_finish(emmax_session* s, bool is_prefill, hipStream_t st) {
+    emmax_model* m = s->m;
+    const int K = s->beam.K, G = s->beam.G, rows = G * K;
+    BeamRowParams r;
+    memset(&r, 0, sizeof(r));
+    r.logits = s->logits; r.ld = m->vocab; r.V = m->vocab; r.K = K; r.is_prefill = is_prefill ? 1 : 0;
+    r.run_score = s->beam.run; r.done = s->done; r.n_out = s->n_out;
+    r.cand_acc = s->beam.cand_acc; r.cand_tok = s->beam.cand_tok; r.row_lse = s->beam.row_lse;
+    r.score_words = s->scores.on ? s->scores.words : nullptr;
+    KCHK(launch_beam_rows(r, is_prefill ? G : rows, st));
+    BeamMergeParams g;
+    memset(&g, 0, sizeof(g));
+    g.K = K; g.V = m->vocab; g.is_prefill = r.is_prefill; g.eos_id = s->beam.eos; g.pad_id = m->cfg.pad_id; g.max_pages = s->max_pages;
+    g.max_out = s->max_out; g.tr_ld = std::min(s->max_batch, EMMAX_MAX_DECODE_BATCH); g.es_mode = s->beam.es; g.lp_pos = s->beam.lp_pos;
+    g.pw = s->beam.pw; g.cand_acc = s->beam.cand_acc; g.cand_tok = s->beam.cand_tok; g.row_lse = s->beam.row_lse;
+    g.run_score = s->beam.run; g.fin_score = s->beam.fin_score; g.fin_flag = s->beam.fin_flag; g.fin_t = s->beam.fin_t; g.fin_par = s->beam.fin_par;
+    g.fin_tok = s->beam.fin_tok; g.grp_state = s->beam.grp;
+    g.cur_tok = s->cur_tok; g.ctx_len = s->ctx_len; g.done = s->done; g.n_out = s->n_out; g.max_new_p = s->max_new_d;
+    g.page_table = s->page_table; g.spare = s->beam.spare; g.copy_src = s->beam.csrc; g.copy_dst = s->beam.cdst; g.copy_ntok = s->beam.cntok;
+    g.tr_tok = s->beam.tr_tok; g.tr_par = s->beam.tr_par; g.tr_score = s->beam.tr_score; g.tr_lse = s->beam.tr_lse; g.tc_idx = s->beam.tc_idx;
+    g.tc_acc = s->beam.tc_acc;
+    if (is_prefill)
+        for (int i = 0; i < G; ++i) g.S[i] = s->S[i];
+    KCHK(launch_beam_merge(g, G, st));
+    BeamCopyParams c;
+    memset(&c, 0, sizeof(c));
+    const long long kvr = kv_rows(s), hd = m->cfg.head_dim;
+    c.kv = (char*)s->kv; c.layer_stride = s->kv_layer_stride; c.Hkv = m->cfg.n_kv_heads; c.n_pages = s->rows_total * s->max_pages;
+    c.copy_src = s->beam.csrc; c.copy_dst = s->beam.cdst; c.copy_ntok = s->beam.cntok;
+    auto plane = [&](long long off, int rb) { c.plane_off[c.n_planes] = off; c.plane_rb[c.n_planes] = rb; c.n_planes += 1; };
+    switch (s->kv_fmt) {
+    case KV_FP8:   // K bytes, V bytes, K scales, V scales
+        plane(0, (int)hd); plane(kvr * hd, (int)hd); plane(2 * kvr * hd, 4); plane(2 * kvr * hd + kvr * 4, 4);
+        break;
+    case KV_X24:   // per operand a bf16 plane and its 8-bit extension plane
+        plane(0, (int)hd * 2); plane(kvr * hd * 2, (int)hd); plane(kvr * hd * 3, (int)hd * 2); plane(kvr * hd * 5, (int)hd);
+        break;
+    case KV_F32:
+        plane(0, (int)hd * 4); plane(kvr * hd * 4, (int)hd * 4);
+        break;
+    default:
+        plane(0, (int)hd * 2); plane(kvr * hd * 2, (int)hd * 2);
+    }
+    KCHK(launch_beam_copy(c, rows, m->cfg.n_layers, st));
+    return 0;
+}
+
+// slot0: first row of the B rows this call covers (slot prefill: one row in the middle of a live batch)
+int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* logits_out, bool do_finish, hipStream_t st, int slot0) {
+    emmax_model* m = s->m;
+    if (do_finish && s->beam.K) {   // beams on: every chunk's lm-head writes its logit rows, then ONE beam finish over all rows (a prefill's
+                                    // rows wait for emmax_generate, which knows the token budget the first beam step needs)
+        if (is_prefill && s->exact) {   // exact numerics: a group's first row must not depend on how many groups were prefilled with it, and
+                                        // lm-heads of 1-2 and of 3-8 rows are different kernels -- one row per launch
+            for (int b = 0; b < B; ++b) {
+                if (int r = run_lm_head_step(s, 1, true, s->logits + (size_t)(slot0 + b) * m->vocab, false, st, slot0 + b)) return r;
+            }
+            return 0;
+        }
+        const int r = run_lm_head_step(s, B, is_prefill, s->logits + (size_t)slot0 * m->vocab, false, st, slot0);
+        if (r || is_prefill) return r;
+        return launch_beam_finish(s, false, st);
+    }
+    const int chunk = s->exact ? 8 : EMMAX_KMP_ROWS;   // (exact numerics: the two-term MFMA kernels hold 8 rows)
+    if (B > chunk) {   // 33-64 rows: launches of <= 32 rows (each with its own finish: the argmax partials are laid out per launch)
+        if (int r = run_lm_head_step(s, chunk, is_prefill, logits_out, do_finish, st, slot0)) return r;
+        return run_lm_head_step(s, B - chunk, is_prefill, logits_out ? logits_out + (size_t)chunk * m->vocab : nullptr, do_finish, st, slot0 + chunk);
+    }
+    // sampling, processing or scores on: a step's lm-head also writes the fp32 logit rows of its B rows, and the sampled or processing finish
+    // reads them
+    const int mode = do_finish ? finish_mode(s) : 0;
+    const bool sampled = mode != 0;
+    if (sampled) logits_out = s->logits + (size_t)slot0 * m->vocab;
+    GemvParams p;
+    lmhead_params(s, slot0, logits_out, p);
+    int lm_grid = 0;
+    KCHK(launch_proj(m->lm_head_w, p, B, st, &lm_grid));
+    if (mode & 6) return launch_proc_finish_step(s, B, is_prefill, slot0, logits_out, st);
+    if (sampled) return launch_sampled_finish_step(s, B, is_prefill, slot0, logits_out, st);
+    if (do_finish) return launch_finish_step(s, B, is_prefill, lm_grid, slot0, st);
+    return 0;
+}
+
+// one stage of decoder layer `li` (the unit the profiler times); the step is stages 0..4 of every layer + lm head
+// exact numerics, batches above 8 rows: the two-term MFMA kernels hold 8 rows (decode_km.hip EX: the two terms of a row in the sixteen batch columns), so a
+// projection stage runs in chunks of 8 rows -- each chunk streams the weights again: the conformance mode covers every batch the default path serves, at
+// ceil(B / 8) times its weight traffic.  (The attention launch takes any batch; the lm-head chunks in run_lm_head_step.)
+#define EMMAX_EXACT_ROWS 8
+static int run_decode_stage_x_chunks(emmax_session* s, int B, int li, int stage, hipStream_t st) {
+    GemvParams p0;
+    stage_params(s, B, li, stage, p0);
+    for (int r = 0; r < B; r += EMMAX_EXACT_ROWS) {
+        GemvParams p = p0;
+        const int n = std::min(EMMAX_EXACT_ROWS, B - r);
+        int grid = 0;
+        if (p.h32) p.h32 += (size_t)r * p.ldh;
+        switch (stage) {   // the chunk's rows of the stage's operands
+            case STAGE_QKV:
+                p.y = (float*)p.y + (size_t)r * p.ldy;
+                p.ctx_len += r; p.page_table += (size_t)r * p.max_pages;
+                break;
+            case STAGE_OPROJ:
+                if (p.attn_part) p.attn_part += (size_t)r * p.Hq * p.nsplit * EMMAX_PSTRIDE;
+                else p.x = (const float*)p.x + (size_t)r * p.ldx;
+                p.y = (bf16*)p.y + (size_t)r * p.ldy;
+                break;
+            case STAGE_GATEUP: p.y = (float*)p.y + (size_t)r * p.ldy; break;
+            default:   // STAGE_DOWN
+                p.x = (const float*)p.x + (size_t)r * p.ldx;
+                p.y = (bf16*)p.y + (size_t)r * p.ldy;
+        }
+        KCHK(launch_proj(s->m->layers[li].proj[stage], p, n, st, &grid));
+    }
+    return 0;
+}
+
+int run_decode_stage(emmax_session* s, int B, int li, int stage, hipStream_t st) {
+    emmax_model* m = s->m;
+    const auto& c = m->cfg;
+    if (stage == STAGE_ATTN) {
+        DecodeAttnParams a;
+        memset(&a, 0, sizeof(a));
+        a.q = s->dq; a.ldq = m->q_dim; a.kcache = kcache_of(s, li); a.vcache = vcache_of(s, li);
+        if (s->kv8) { a.kv_stage = s->kv_stage; a.kscale = kscale_of(s, li); a.vscale = vscale_of(s, li); }
+        a.page_table = s->page_table; a.ctx_len = s->ctx_len; a.done = s->done; a.part = s->part; a.Hkv = c.n_kv_heads; a.page = PAGE;
+        a.max_pages = s->max_pages; a.scale = 1.0f / sqrtf((float)c.head_dim);
+        a.o_out = attn_direct_on(s, B) ? s->datt : nullptr;
+        const int ns = decode_attn_nsplit(B, c.n_kv_heads);
+        if (s->exact) {
+            a.q = s->dq32; a.kv24 = s->kv24;
+            a.o_out = attn_direct_on(s, B) ? (void*)s->dq32 : nullptr;
+            KCHK(launch_x_decode_attn(a, B, c.n_heads, c.head_dim, ns, st));
+            return 0;
+        }
+        KCHK(launch_decode_attn(a, B, c.n_heads, c.head_dim, ns, st));
+        return 0;
+    }
+    if (stage < STAGE_QKV || stage > STAGE_DOWN) return fail(EMMAX_ERR_INVALID, "unknown decode stage %d", stage);
+    if (s->exact && B > EMMAX_EXACT_ROWS) return run_decode_stage_x_chunks(s, B, li, stage, st);
+    // (o-proj at batch >= 3: the K-split MFMA kernel takes it with fp8 weights only, see decode_km.hip)
+    const ProjW& w = m->layers[li].proj[stage];
+    GemvParams p;
+    int grid = 0;
+    stage_params(s, B, li, stage, p);
+    if (stage == STAGE_DOWN && B > EMMAX_KMP_ROWS) {   // 33-64 rows: K = 11008 does not fit the eight phases of a four-way split -- two launches of <= 32 rows
+        GemvParams q = p;
+        KCHK(launch_proj(w, q, EMMAX_KMP_ROWS, st, &grid));
+        q = p;
+        q.x = (const bf16*)q.x + (size_t)EMMAX_KMP_ROWS * q.ldx;
+        q.y = (bf16*)q.y + (size_t)EMMAX_KMP_ROWS * q.ldy;
+        if (q.h32) q.h32 += (size_t)EMMAX_KMP_ROWS * q.ldh;
+        KCHK(launch_proj(w, q, B - EMMAX_KMP_ROWS, st, &grid));
+        return 0;
+    }
+    KCHK(launch_proj(w, p, B, st, &grid));
+    return 0;
+}
+
+// layer 0's qkv with the embedding gather folded in (K-split kernel; anything else: embed launch + the plain stage)
+static int run_qkv0_with_embed(emmax_session* s, int B, hipStream_t st) {
+    emmax_model* m = s->m;
+    GemvParams p;
+    stage_params(s, B, 0, STAGE_QKV, p);
+    p.W = m->layers[0].proj[STAGE_QKV].rm;
+    p.x = m->embed; p.x_tok = s->cur_tok; p.x_copy = s->dh; p.x_vocab = m->vocab;
+    int r = launch_decode_ks(GEMV_QKV, p, B, st, nullptr);
+    if (r == -2) {
+        KCHK(launch_decode_embed(s->cur_tok, m->embed, s->dh, B, m->H, m->vocab, st, s->exact ? s->dh32 : h32_of(s)));
+        return run_decode_stage(s, B, 0, STAGE_QKV, st);
+    }
+    return r ? fail(EMMAX_ERR_HIP, "qkv launch of layer 0 failed (code %d)", r) : 0;
+}
+
+int run_decode_step(emmax_session* s, int B, hipStream_t st) {
+    emmax_model* m = s->m;
+    // batch 1-2 on bf16 weights: the embedding row is read by layer 0's qkv launch itself (K-split kernel) -- one launch fewer
+    const bool fold_embed = B < EMMAX_MFMA_MIN_BATCH && !m->fp8 && decode_ks_enabled() && m->H % 64 == 0 && m->H <= 12288 &&
+                            emmax_tune().fold_embed != 0;
+    if (!fold_embed) KCHK(launch_decode_embed(s->cur_tok, m->embed, s->dh, B, m->H, m->vocab, st, s->exact ? s->dh32 : h32_of(s)));
+    for (int li = 0; li < m->cfg.n_layers; ++li)
+        for (int stage = STAGE_QKV; stage <= STAGE_DOWN; ++stage) {
+            if (int r = (li == 0 && stage == STAGE_QKV && fold_embed) ? run_qkv0_with_embed(s, B, st) : run_decode_stage(s, B, li, stage, st)) return r;
+        }
+    return run_lm_head_step(s, B, false, nullptr, true, st);
+}
+
+void drop_graph(emmax_session* s) {
+    if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
+    if (s->graph) (void)hipGraphDestroy(s->graph);
+    s->graph_exec = nullptr;
+    s->graph = nullptr;
+    s->graph_B = 0;
+}
+
+static int graph_fail(emmax_session* s, const std::string& why) {
+    s->graph_failed = 1;
+    s->graph_err = why;
+    (void)hipGetLastError();
+    return 1;
+}
+
+// Capture one decode step into a hipGraph.
+int ensure_graph(emmax_session* s, int B, hipStream_t st) {
+    // Default: eager launch-ahead.  One step is 163 launches for >= 2.6 ms of GPU time, so a single host thread stays far
+    // ahead of the device, and measured on MI355X / ROCm 7.2 the replayed graph is the SLOWER option: 3.05 vs 2.95 ms/token
+    // at B = 1 (~0.6 us more per kernel node than a same-stream launch; round 3: 2.73 vs 2.62).  What was tried against that,
+    // and what each runtime setting did, is recorded in profiles/r05_graph_switches.txt.
+    // Tuning switch graph = 1 (EMMAX_GRAPH=1 at start-up, or emmax_tuning_set) selects graph replay (a host whose launch thread
+    // cannot be kept free).
+    s->last_step_graph = 0;   // set again by launch_graph_step when a replay really runs
+    if (!emmax_tune().graph) return 1;   // eager step: a captured graph stays valid for the next caller that wants replay
+    if (s->graph_exec && s->graph_B == B && s->graph_stream_cap == st && s->graph_epoch == emmax_tune().epoch && s->graph_mode == finish_mode(s))
+        return 0;
+    drop_graph(s);
+    if (s->graph_failed) return 1;
+    hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
+    if (e != hipSuccess) return graph_fail(s, std::string("hipStreamBeginCapture: ") + hipGetErrorString(e));
+    const int r = run_decode_step(s, B, st);
+    hipGraph_t g = nullptr;
+    e = hipStreamEndCapture(st, &g);
+    if (r != 0 || e != hipSuccess || !g) {
+        if (g) (void)hipGraphDestroy(g);
+        return graph_fail(s, r != 0 ? ("launch during capture: " + g_err) : (std::string("hipStreamEndCapture: ") + hipGetErrorString(e)));
+    }
+    hipGraphExec_t ge = nullptr;
+    e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+    if (e != hipSuccess) {
+        (void)hipGraphDestroy(g);
+        return graph_fail(s, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+    }
+    s->graph = g; s->graph_exec = ge; s->graph_B = B; s->graph_stream_cap = st; s->graph_epoch = emmax_tune().epoch;
+    s->graph_mode = finish_mode(s);
+    return 0;
+}
+
+int launch_graph_step(emmax_session* s, int B, hipStream_t st) {
+    s->last_step_graph = 1;
+    HIPCHK(hipGraphLaunch(s->graph_exec, st));
+    return 0;
+}

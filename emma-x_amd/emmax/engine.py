@@ -103,6 +103,9 @@ class EmmaxEngine:
         del keep
         self.aux_arena: Optional[torch.Tensor] = None    # the batch >= 3 weight copies, built when a batch >= 3 first decodes
         self.max_batch = self.max_prompt = self.max_ctx = 0
+        self._resize_tables: Dict[Tuple[int, int, int], tuple] = {}   # bicubic tables per (H, W, size): resize_frames
+        self._adm_stream = None     # the admission stream and the last commit on the decode stream: admission
+        self._commit_event = None
         self.new_session(max_batch, max_prompt, max_ctx)
 
     # ------------------------------------------------------------------------------------------------------------------
@@ -132,7 +135,7 @@ class EmmaxEngine:
     def ensure_stage_rows(self, n: int) -> None:
         """Slot serving with overlapped admission stages up to `n` requests at a time: re-create the session with that many staging
         rows if it has fewer (drops any state of the current session -- call before slots_open)."""
-        if n > getattr(self, "stage_rows", 0):
+        if n > self.stage_rows:
             # staging rows are bounded by the decode batch: grow that first, so that n_slots > max_batch surfaces as what it is (ADVICE r05)
             self.new_session(max(self.max_batch, int(n)), self.max_prompt, self.max_ctx, stage_rows=int(n))
 
@@ -167,7 +170,7 @@ class EmmaxEngine:
         need_ctx = self.cfg.n_patches + prompt + max_new + 1
         if batch > self.max_batch or prompt > self.max_prompt or need_ctx > self.max_ctx:
             self.new_session(max(batch, self.max_batch), max(prompt, self.max_prompt), max(need_ctx, self.max_ctx),
-                             stage_rows=getattr(self, "stage_rows", 0))
+                             stage_rows=self.stage_rows)
 
     def close(self) -> None:
         if getattr(self, "_session", None):
@@ -204,8 +207,6 @@ class EmmaxEngine:
             return frames_u8
         assert frames_u8.dtype == torch.uint8 and frames_u8.is_cuda and frames_u8.is_contiguous()
         key = (H, W, size)
-        if not hasattr(self, "_resize_tables"):
-            self._resize_tables = {}
         if key not in self._resize_tables:
             bh, kh, nh = bicubic_coeffs(W, size)
             bv, kv, nv = bicubic_coeffs(H, size)
@@ -232,17 +233,28 @@ class EmmaxEngine:
         _lib.check(self.lib.emmax_vision_features(self._session, B, out.data_ptr(), _lib.current_stream()), "emmax_vision_features")
         return out
 
+    def _pack_prompts(self, who: str, prompts: Sequence[Sequence[int]], pad: int, patch_embeds: Optional[Sequence[torch.Tensor]] = None):
+        """Ragged prompts as one int32 [n, P_max] device tensor padded with `pad`, their lengths and P_max; `patch_embeds` (one tensor per
+        prompt) stacked into one [n, n_patches, hidden] tensor, else None."""
+        lens = [len(p) for p in prompts]
+        P_max = max(lens)
+        ids = torch.full((len(prompts), P_max), pad, dtype=torch.int32)
+        for i, p in enumerate(prompts):
+            ids[i, : lens[i]] = torch.as_tensor(list(p), dtype=torch.int32)
+        pe = None
+        if patch_embeds is not None:
+            if len(patch_embeds) != len(prompts):
+                raise ValueError(f"{who}: one patch-embedding tensor per prompt")
+            pe = torch.stack([t.reshape(self.cfg.n_patches, self.cfg.llm.hidden_size) for t in patch_embeds]).contiguous()
+            assert pe.dtype == self.patch_dtype
+        return ids.to(self.device), lens, P_max, pe
+
     def prefill(self, input_ids: Sequence[Sequence[int]], patch_embeds: torch.Tensor) -> List[int]:
         """Ragged prompts (row b = list of ids starting with BOS). Returns per-row packed lengths S_b = 256 + P_b."""
         B = len(input_ids)
-        K = getattr(self, "_beam_K", 0)
+        K = self._beam_K
         self.ensure_decode_batch(B * K if K else B)   # beams on: B groups decode as B x K rows
-        lens = [len(r) for r in input_ids]
-        P_max = max(lens)
-        ids = torch.full((B, P_max), self.cfg.pad_token_id, dtype=torch.int32)
-        for b, r in enumerate(input_ids):
-            ids[b, : len(r)] = torch.as_tensor(list(r), dtype=torch.int32)
-        ids_d = ids.to(self.device)
+        ids_d, lens, P_max, _ = self._pack_prompts("prefill", input_ids, self.cfg.pad_token_id)
         lens_c = (C.c_int32 * B)(*lens)
         if patch_embeds is None:   # language-only forward
             _lib.check(self.lib.emmax_prefill_text(self._session, ids_d.data_ptr(), lens_c, B, P_max, _lib.current_stream()),
@@ -282,7 +294,7 @@ class EmmaxEngine:
         """The decode loop after prefill: greedy, or sampled per row once set_sampling ran.  Returns (ids int32 [B,max_new] padded with pad_id,
         lens int32 [B]) on device; with return_logprobs (sampling on only) also the fp32 [B,max_new] log-probabilities of the emitted tokens.
         Beams on: B = groups x num_beams rows, row g K + k = the k-th best kept hypothesis of group g (beam_result has the scores)."""
-        B = self._last_B * (getattr(self, "_beam_K", 0) or 1)
+        B = self._last_B * (self._beam_K or 1)
         self._beam_T = int(max_new_tokens)
         out = torch.empty(B, max_new_tokens, dtype=torch.int32, device=self.device)
         lens = torch.empty(B, dtype=torch.int32, device=self.device)
@@ -433,7 +445,7 @@ class EmmaxEngine:
 
     @property
     def scores_bound(self) -> bool:
-        return getattr(self, "_score_bufs", None) is not None
+        return self._score_bufs is not None
 
     def slot_logprobs(self, slot: int, n: int) -> List[float]:
         """Log-probabilities of the first n tokens of `slot` (sampling on)."""
@@ -473,18 +485,7 @@ class EmmaxEngine:
         n = len(prompts)
         if n < 1 or len(max_new_tokens) != n:
             raise ValueError("slots_prefill: one token budget per prompt, at least one prompt")
-        lens = [len(p) for p in prompts]
-        P = max(lens)
-        ids = torch.zeros(n, P, dtype=torch.int32)
-        for i, p in enumerate(prompts):
-            ids[i, : lens[i]] = torch.as_tensor(list(p), dtype=torch.int32)
-        ids_d = ids.to(self.device)
-        pe = None
-        if patch_embeds is not None:
-            if len(patch_embeds) != n:
-                raise ValueError("slots_prefill: one patch-embedding tensor per prompt")
-            pe = torch.stack([t.reshape(self.cfg.n_patches, self.cfg.llm.hidden_size) for t in patch_embeds]).contiguous()
-            assert pe.dtype == self.patch_dtype
+        ids_d, lens, P, pe = self._pack_prompts("slots_prefill", prompts, 0, patch_embeds)
         lens_c = (C.c_int32 * n)(*lens)
         budget_c = (C.c_int32 * n)(*[int(v) for v in max_new_tokens])
         _lib.check(self.lib.emmax_slots_prefill(self._session, int(slot0), n, ids_d.data_ptr(), P, lens_c, _lib.ptr(pe), budget_c,
@@ -495,9 +496,8 @@ class EmmaxEngine:
     def admission(self):
         """Context manager: everything issued inside (frame encode, staged prefill, their uploads) runs on the engine's admission
         stream, beside the decode steps of the current stream; ordered after the previous commit."""
-        if getattr(self, "_adm_stream", None) is None:
+        if self._adm_stream is None:
             self._adm_stream = torch.cuda.Stream(device=self.device)
-            self._commit_event = None
         if self._commit_event is not None:
             self._adm_stream.wait_event(self._commit_event)
         return torch.cuda.stream(self._adm_stream)
@@ -509,18 +509,7 @@ class EmmaxEngine:
         n = len(prompts)
         if n < 1 or len(max_new_tokens) != n:
             raise ValueError("slots_prefill_staged: one token budget per prompt, at least one prompt")
-        lens = [len(p) for p in prompts]
-        P = max(lens)
-        ids = torch.zeros(n, P, dtype=torch.int32)
-        for i, p in enumerate(prompts):
-            ids[i, : lens[i]] = torch.as_tensor(list(p), dtype=torch.int32)
-        ids_d = ids.to(self.device)
-        pe = None
-        if patch_embeds is not None:
-            if len(patch_embeds) != n:
-                raise ValueError("slots_prefill_staged: one patch-embedding tensor per prompt")
-            pe = torch.stack([t.reshape(self.cfg.n_patches, self.cfg.llm.hidden_size) for t in patch_embeds]).contiguous()
-            assert pe.dtype == self.patch_dtype
+        ids_d, lens, P, pe = self._pack_prompts("slots_prefill_staged", prompts, 0, patch_embeds)
         lens_c = (C.c_int32 * n)(*lens)
         budget_c = (C.c_int32 * n)(*[int(v) for v in max_new_tokens])
         _lib.check(self.lib.emmax_slots_prefill_staged(self._session, n, ids_d.data_ptr(), P, lens_c, _lib.ptr(pe), budget_c,

@@ -691,7 +691,7 @@ def test_fp8_row_gemv(device, B, N, K):
 def test_fp8_row_gemv_refuses_what_it_cannot_stage(device):
     """The fp8-row GEMV stages whole activation rows in LDS (one K phase) and serves batch 1-2: a third row, a K that is not a
     multiple of 16 or rows beyond the LDS budget are refused with an error code and a message (the session then keeps such a
-    projection on the MFMA kernel, model.hip: launch_proj), never run wrong."""
+    projection on the MFMA kernel, step.hip: launch_proj), never run wrong."""
     L, lib = _lib()
     x = torch.zeros(3, 65536, dtype=torch.bfloat16, device=device)
     W8 = torch.zeros(16 * 65536, dtype=torch.uint8, device=device)
