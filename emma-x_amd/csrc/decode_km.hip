@@ -527,8 +527,11 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_kmd_kernel(GemvParams p
 
     // ---- activation row slices of a phase: lane l holds chunks l (and l + 64) of the phase's slice, for every batch row ----
     auto phase_steps = [&](int ph) { return max(0, min(NST, k_n - ph * NST)); };
-    auto load_rows = [&](int ph, u32x4_t (&r)[NB][CH]) {
-        const int nch = phase_steps(ph) * (KS / 8);             // 16-byte chunks in the slice
+    auto load_rows = [&](int ph_in, u32x4_t (&r)[NB][CH]) {
+        const int nch = phase_steps(ph_in) * (KS / 8);          // 16-byte chunks in the slice
+        // a phase past the wave's slice (a short K: 4160 = 17 steps per wave leaves NB = 16's phases 2 and 3 empty) loads phase 0's first chunk
+        // again: its address would lie past the row -- past the buffer for the last row -- and store_rows writes zeros for it anyway
+        const int ph = nch > 0 ? ph_in : 0;
         if constexpr (EX) {
             static_assert(!EX || CH == 1, "one chunk per lane and row");
             const float* b32 = (const float*)p.x + (size_t)(k_lo + ph * NST) * KS + (size_t)min(lane, max(nch - 1, 0)) * 8;

@@ -266,7 +266,8 @@ __device__ __forceinline__ void gemv_kv_store_x(const GemvParams& p, bool is_v, 
         ((float*)base)[idx] = v;
     }
 }
-int launch_decode_gemv(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out = nullptr);
+// staged_out (optional): 1 when decode.hip's own LDS-staged kernel served the call, 0 when decode_ks.hip took it
+int launch_decode_gemv(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out = nullptr, int* staged_out = nullptr);
 // decode_ks.hip: the batch 1-2 bf16 projections with K split across the waves of a block (activation slice in registers, no
 // block-wide stage); returns -2 for a shape it does not take.  launch_decode_gemv tries it first (tuning switch `ks` = 0: never).
 int launch_decode_ks(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out = nullptr);

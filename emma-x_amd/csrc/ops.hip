@@ -235,6 +235,186 @@ int emmax_op_x_decode_attention(const float* q32, const void* kcache32, const vo
     if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_x_decode_attention: unsupported (GQA group in {1,2,4,8}, page = 2^k, max_pages <= 512, nsplit = 2^k)");
     return 0;
 }
+// ---- one decode stage through the product's own dispatch (tests/test_decode_stages_gpu.py) ----------------------------
+// e4m3 (OCP: bias 7, no infinities, 0x7f / 0xff = NaN) as the fp8 KV cache holds it
+static float e4m3_to_float(uint8_t v) {
+    const int e = (v >> 3) & 15, mant = v & 7;
+    float f;
+    if (e == 15 && mant == 7) f = NAN;
+    else if (e == 0) f = ldexpf((float)mant, -9);
+    else f = ldexpf((float)(8 + mant), e - 10);
+    return (v & 0x80) ? -f : f;
+}
+static float bits_to_float(uint32_t u) {
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+// the session's own per-row state swapped for the op's scratch rows while a stage runs (host pointers only: nothing on the device moves)
+namespace {
+struct OpRows {
+    emmax_session* s;
+    int32_t *cur_tok, *ctx_len, *done, *n_out, *out_ids, *max_new_d, *stop_m, *stop_after;
+    explicit OpRows(emmax_session* s_) : s(s_), cur_tok(s_->cur_tok), ctx_len(s_->ctx_len), done(s_->done), n_out(s_->n_out), out_ids(s_->out_ids),
+                                         max_new_d(s_->max_new_d), stop_m(s_->stop_m), stop_after(s_->stop_after) {
+        const int R = s->op_rows;
+        s->ctx_len = s->op_state; s->cur_tok = s->op_state + R; s->done = s->op_state + 2 * R; s->n_out = s->op_state + 3 * R;
+        s->max_new_d = s->op_state + 4 * R; s->stop_m = s->op_state + 5 * R; s->stop_after = s->op_state + 6 * R; s->out_ids = s->op_out;
+    }
+    OpRows(const OpRows&) = delete;
+    ~OpRows() {
+        s->cur_tok = cur_tok; s->ctx_len = ctx_len; s->done = done; s->n_out = n_out; s->out_ids = out_ids; s->max_new_d = max_new_d;
+        s->stop_m = stop_m; s->stop_after = stop_after;
+    }
+};
+}  // namespace
+
+static int decode_stage_run(emmax_session* s, int layer, int stage, int B, const void* h_in, const float* h32_in, const int32_t* ctx_host,
+                            const int32_t* pt_host, const void* x_in, void* h_out, float* h32_out, void* y_out, int32_t* tok_out, int* via_out,
+                            hipStream_t st) {
+    emmax_model* m = s->m;
+    const int R = s->op_rows, H = m->H;
+    const size_t x4 = s->exact ? 4 : 2;   // bytes of an activation element the stages hand on
+    if (h_in) HIPCHK(hipMemcpyAsync(s->dh, h_in, (size_t)R * H * 2, hipMemcpyDeviceToDevice, st));
+    if (h32_in) HIPCHK(hipMemcpyAsync(s->dh32, h32_in, (size_t)R * H * 4, hipMemcpyDeviceToDevice, st));
+    OpRows swap(s);
+    HIPCHK(hipMemsetAsync(s->op_state, 0, (size_t)R * 8 * 4, st));
+    KCHK(launch_set_ints(s->max_new_d, R, 1 << 30, st));
+    KCHK(launch_set_ints(s->stop_after, R, -1, st));
+    int r = 0;
+    s->last_via = EMMAX_VIA_NONE;
+    if (stage == STAGE_QKV) {
+        HIPCHK(hipMemcpyAsync(s->ctx_len, ctx_host, (size_t)B * 4, hipMemcpyHostToDevice, st));
+        if (pt_host) HIPCHK(hipMemcpyAsync(s->page_table, pt_host, (size_t)B * s->max_pages * 4, hipMemcpyHostToDevice, st));
+        r = run_decode_stage(s, B, layer, stage, st);
+        if (pt_host) {   // the identity table again, whatever the launch did
+            std::vector<int32_t> id((size_t)B * s->max_pages);
+            for (size_t i = 0; i < id.size(); ++i) id[i] = (int32_t)i;
+            HIPCHK(hipMemcpyAsync(s->page_table, id.data(), id.size() * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(hipStreamSynchronize(st));   // (`id` is pageable host memory)
+        }
+        if (r == 0 && y_out) HIPCHK(hipMemcpyAsync(y_out, s->exact ? (void*)s->dq32 : (void*)s->dq, (size_t)B * m->q_dim * x4, hipMemcpyDeviceToDevice, st));
+    } else if (stage == STAGE_OPROJ) {
+        int ns = 1;
+        const int form = decode_oproj_form(s, B, &ns);
+        if (form == 1) HIPCHK(hipMemcpyAsync(s->part, x_in, (size_t)B * m->cfg.n_heads * ns * EMMAX_PSTRIDE * 4, hipMemcpyDeviceToDevice, st));
+        else if (form == 2) HIPCHK(hipMemcpyAsync(s->dq32, x_in, (size_t)B * m->q_dim * 4, hipMemcpyDeviceToDevice, st));
+        else HIPCHK(hipMemcpyAsync(s->datt, x_in, (size_t)B * m->q_dim * 2, hipMemcpyDeviceToDevice, st));
+        r = run_decode_stage(s, B, layer, stage, st);
+    } else if (stage == STAGE_GATEUP) {
+        r = run_decode_stage(s, B, layer, stage, st);
+        if (r == 0 && y_out) HIPCHK(hipMemcpyAsync(y_out, s->exact ? (void*)s->dact32 : (void*)s->dact, (size_t)B * m->inter_p * x4, hipMemcpyDeviceToDevice, st));
+    } else if (stage == STAGE_DOWN) {
+        HIPCHK(hipMemcpyAsync(s->exact ? (void*)s->dact32 : (void*)s->dact, x_in, (size_t)B * m->inter_p * x4, hipMemcpyDeviceToDevice, st));
+        r = run_decode_stage(s, B, layer, stage, st);
+    } else {   // STAGE_LMHEAD: the logit rows and the greedy finish over the session's partial buffers, against the op's own per-row state
+        r = run_lm_head_step(s, B, false, (float*)y_out, true, st, 0);
+        if (r == 0 && tok_out) HIPCHK(hipMemcpyAsync(tok_out, s->cur_tok, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+    }
+    if (via_out) *via_out = s->last_via;
+    if (r) return r;
+    if (h_out) HIPCHK(hipMemcpyAsync(h_out, s->dh, (size_t)R * H * 2, hipMemcpyDeviceToDevice, st));
+    if (h32_out) HIPCHK(hipMemcpyAsync(h32_out, s->dh32, (size_t)R * H * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int emmax_op_decode_stage(emmax_session* s, int layer, int stage, int B, const void* h_in, const float* h32_in, const int32_t* ctx_len_host,
+                          const int32_t* page_table_host, const void* x_in, void* h_out, float* h32_out, void* y_out, int32_t* tok_out, int* via_out,
+                          int* oproj_form_out, int* nsplit_out, emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_stage: null session");
+    emmax_model* m = s->m;
+    if (stage != STAGE_QKV && stage != STAGE_OPROJ && stage != STAGE_GATEUP && stage != STAGE_DOWN && stage != STAGE_LMHEAD)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_decode_stage: stage %d is not a projection stage (0 qkv, 2 o-proj, 3 gate/up, 4 down, 5 lm-head)", stage);
+    if (B < 1 || B > s->op_rows) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_stage: B %d outside 1..%d", B, s->op_rows);
+    if (stage != STAGE_LMHEAD && (layer < 0 || layer >= m->cfg.n_layers))
+        return fail(EMMAX_ERR_INVALID, "emmax_op_decode_stage: layer %d outside 0..%d", layer, m->cfg.n_layers - 1);
+    int ns = 1;
+    const int form = decode_oproj_form(s, B, &ns);
+    if (oproj_form_out) *oproj_form_out = form;
+    if (nsplit_out) *nsplit_out = ns;
+    if (via_out) *via_out = EMMAX_VIA_NONE;
+    if (stage == STAGE_OPROJ && !x_in && !h_in && !h32_in) return 0;   // the query form: which input the o-proj of B rows reads, nothing launched
+    if (s->samp.on || s->proc.on || s->scores.on || s->beam.K || s->slots_open)
+        return fail(EMMAX_ERR_STATE, "emmax_op_decode_stage: the session must be greedy (no sampling, processing, scores, beams or open slots)");
+    if (B >= EMMAX_MFMA_MIN_BATCH && !m->aux_built)
+        return fail(EMMAX_ERR_STATE, "%d rows decode on the fragment-major weight copies: call emmax_model_build_aux first", B);
+    if (!h_in || (!h32_in && (s->exact || emmax_tune().resid32))) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_stage: the hidden rows (bf16 and the fp32 stream) are required");
+    if ((stage == STAGE_OPROJ || stage == STAGE_DOWN) && !x_in) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_stage: the stage's input rows are required");
+    if (stage == STAGE_LMHEAD && !y_out) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_stage: the logit rows are required");
+    if (stage == STAGE_QKV) {
+        if (!ctx_len_host) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_stage: ctx_len is required");
+        for (int b = 0; b < B; ++b)
+            if (ctx_len_host[b] < 0 || ctx_len_host[b] > s->max_ctx - 2)
+                return fail(EMMAX_ERR_INVALID, "emmax_op_decode_stage: ctx_len[%d] = %d outside 0..%d", b, ctx_len_host[b], s->max_ctx - 2);
+        if (page_table_host) {   // together a permutation of the pages rows 0 .. B own
+            const int n = B * s->max_pages;
+            std::vector<char> seen((size_t)n, 0);
+            for (int i = 0; i < n; ++i) {
+                const int pg = page_table_host[i];
+                if (pg < 0 || pg >= n || seen[pg]) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_stage: page_table is not a permutation of pages 0..%d (entry %d = %d)", n - 1, i, pg);
+                seen[pg] = 1;
+            }
+        }
+    }
+    return decode_stage_run(s, layer, stage, B, h_in, h32_in, ctx_len_host, page_table_host, x_in, h_out, h32_out, y_out, tok_out, via_out, (hipStream_t)stream);
+}
+
+int emmax_op_decode_kv_read(emmax_session* s, int layer, int row, int p0, int n, const int32_t* page_row_host, int from_stage, float* k_out_host,
+                            float* v_out_host, emmax_stream stream) {
+    if (!s || !k_out_host || !v_out_host) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_kv_read: null argument");
+    emmax_model* m = s->m;
+    const int Hkv = m->cfg.n_kv_heads, hd = m->cfg.head_dim;
+    if (layer < 0 || layer >= m->cfg.n_layers || row < 0 || row >= s->rows_total) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_kv_read: layer / row out of range");
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    if (from_stage) {   // fp8 KV cache: the step's new rows as the qkv launch left them, bf16 [rows][Hkv][2][hd]
+        if (!s->kv8) return fail(EMMAX_ERR_STATE, "emmax_op_decode_kv_read: the session has no kv_stage rows (tuning switch kv_fp8 at emmax_session_create)");
+        std::vector<bf16> raw((size_t)Hkv * 2 * hd);
+        HIPCHK(hipMemcpy(raw.data(), s->kv_stage + (size_t)row * Hkv * 2 * hd, raw.size() * 2, hipMemcpyDeviceToHost));
+        for (int hk = 0; hk < Hkv; ++hk)
+            for (int d = 0; d < hd; ++d) {
+                k_out_host[hk * hd + d] = bits_to_float((uint32_t)raw[((size_t)hk * 2) * hd + d] << 16);
+                v_out_host[hk * hd + d] = bits_to_float((uint32_t)raw[((size_t)hk * 2 + 1) * hd + d] << 16);
+            }
+        return 0;
+    }
+    if (n < 1 || p0 < 0 || p0 + n > s->max_ctx) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_kv_read: positions %d..%d outside 0..%d", p0, p0 + n - 1, s->max_ctx - 1);
+    std::vector<int32_t> pt((size_t)s->max_pages);
+    if (page_row_host) memcpy(pt.data(), page_row_host, pt.size() * 4);
+    else HIPCHK(hipMemcpy(pt.data(), s->page_table + (size_t)row * s->max_pages, pt.size() * 4, hipMemcpyDeviceToHost));
+    const int64_t n_pages = (int64_t)s->rows_total * s->max_pages;
+    const int eb = kv_elem_bytes(s->kv_fmt);
+    std::vector<uint8_t> raw((size_t)hd * 4), ext((size_t)hd);
+    for (int i = 0; i < n; ++i) {
+        const int pos = p0 + i, pg = pt[pos / PAGE];
+        if (pg < 0 || pg >= n_pages) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_kv_read: page id %d outside 0..%lld", pg, (long long)n_pages - 1);
+        for (int hk = 0; hk < Hkv; ++hk) {
+            const size_t rowi = ((size_t)pg * Hkv + hk) * PAGE + pos % PAGE;
+            for (int is_v = 0; is_v < 2; ++is_v) {
+                float* out = (is_v ? v_out_host : k_out_host) + ((size_t)i * Hkv + hk) * hd;
+                const char* base = (const char*)(is_v ? vcache_of(s, layer) : kcache_of(s, layer));
+                if (s->kv_fmt == KV_X24) {
+                    HIPCHK(hipMemcpy(raw.data(), base + rowi * hd * 2, (size_t)hd * 2, hipMemcpyDeviceToHost));
+                    HIPCHK(hipMemcpy(ext.data(), base + (size_t)s->kv24 * 2 + rowi * hd, (size_t)hd, hipMemcpyDeviceToHost));
+                    for (int d = 0; d < hd; ++d) out[d] = bits_to_float(((uint32_t)((const uint16_t*)raw.data())[d] << 16) | ((uint32_t)ext[d] << 8));
+                    continue;
+                }
+                HIPCHK(hipMemcpy(raw.data(), base + rowi * hd * eb, (size_t)hd * eb, hipMemcpyDeviceToHost));
+                if (s->kv_fmt == KV_F32) {
+                    memcpy(out, raw.data(), (size_t)hd * 4);
+                } else if (s->kv_fmt == KV_FP8) {
+                    float sc = 0.f;
+                    HIPCHK(hipMemcpy(&sc, (is_v ? vscale_of(s, layer) : kscale_of(s, layer)) + rowi, 4, hipMemcpyDeviceToHost));
+                    for (int d = 0; d < hd; ++d) out[d] = e4m3_to_float(raw[d]) * sc;
+                } else {
+                    for (int d = 0; d < hd; ++d) out[d] = bits_to_float((uint32_t)((const uint16_t*)raw.data())[d] << 16);
+                }
+            }
+        }
+    }
+    return 0;
+}
+
 int emmax_op_gemv(const void* x, const void* W, void* y, int B, int N, int K, emmax_stream st) {
     GemvParams p = plain_gemv(x, W, y, N, K);
     if (decode_gemv_init() != 0) return fail(EMMAX_ERR_HIP, "could not raise the dynamic LDS limit of the GEMV kernels");

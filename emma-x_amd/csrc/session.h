@@ -226,6 +226,11 @@ struct emmax_session {
     int graph_B = 0;
     int graph_failed = 0;
     int last_step_graph = 0;   // the most recent decode step was a graph replay (what emmax_session_graph_active reports)
+    int last_via = 0;          // launcher family of the most recent projection launch (step.hip: launch_proj; EMMAX_VIA_*)
+    // emmax_op_decode_stage (ops.hip): per-row state of its own for the rows it runs -- 8 int32 columns of op_rows rows (ctx_len, cur_tok, done,
+    // n_out, max_new, stop_m, stop_after, -) and an output row each -- so that a single stage never touches the session's generation state
+    int op_rows = 0;
+    int32_t *op_state = nullptr, *op_out = nullptr;
     hipEvent_t ev = nullptr;
     int graph_epoch = -1;      // emmax_tune().epoch the graph was captured under (a changed switch re-captures)
     int graph_mode = 0;   // finish_mode() the step was captured under (the parameters and score buffers are device words: a change re-captures nothing)
@@ -298,6 +303,7 @@ bool beam_pages_fit(const emmax_session* s, int S, int max_new);
 int launch_beam_finish(emmax_session* s, bool is_prefill, hipStream_t st);
 int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* logits_out, bool do_finish, hipStream_t st, int slot0 = 0);
 int run_decode_stage(emmax_session* s, int B, int li, int stage, hipStream_t st);
+int decode_oproj_form(const emmax_session* s, int B, int* nsplit);
 int run_decode_step(emmax_session* s, int B, hipStream_t st);
 int ensure_graph(emmax_session* s, int B, hipStream_t st);
 int launch_graph_step(emmax_session* s, int B, hipStream_t st);

@@ -119,6 +119,9 @@ static void plan_session(emmax_session* s, Bump& b) {
         s->beam.res_len = (int32_t*)b.bytes(Rb * 4);
         s->beam.res_score = (float*)b.bytes(Rb * 4);
     }
+    s->op_rows = std::min(Bd, EMMAX_MAX_DECODE_BATCH);
+    s->op_state = (int32_t*)b.bytes((int64_t)s->op_rows * 8 * 4);
+    s->op_out = (int32_t*)b.bytes((int64_t)s->op_rows * s->max_out * 4);
     if (s->exact) {
         const int64_t npr = (int64_t)Bv * np;
         auto mx = [](int64_t a, int64_t b2) { return a > b2 ? a : b2; };

@@ -20,17 +20,23 @@ static int fp8_gemv_mask(int B) {
 // One projection of the step (ProjW, session.h).  B <= 2: per-lane dot-product GEMV over the row-major weights (fp8 mode: over the e4m3 row
 // copy w.r8); B >= 3: MFMA over the fragment-major copy.  w.km / w.km_sc: the matrix in decode_km.hip's layout (null: that kernel does not
 // serve this projection)
-static int launch_proj(const ProjW& w, GemvParams& p, int B, hipStream_t st, int* grid_out) {
+// via (optional): which launcher family took the call (include/emmax.h: EMMAX_VIA_*), what emmax_op_decode_stage reports
+static int launch_proj(const ProjW& w, GemvParams& p, int B, hipStream_t st, int* grid_out, int* via = nullptr) {
     const int mode = w.gemv_mode;
+    int via_tmp = 0;
+    if (!via) via = &via_tmp;
+    *via = EMMAX_VIA_NONE;
     if (p.exact) {   // exact numerics: the two-term forms or nothing -- decode_ks.hip at batch 1-2, decode_km.hip's EX kernels at batch 3-8
         int r = -2;
         if (!w.sc && B < EMMAX_MFMA_MIN_BATCH) {
             p.W = w.rm;
             r = launch_decode_ks(mode, p, B, st, grid_out);
+            *via = EMMAX_VIA_KS;
         } else if (!w.sc && w.km) {
             GemvParams q = p;
             q.W = w.km;
             r = launch_decode_km(mode, q, B, st, grid_out);
+            *via = EMMAX_VIA_KM;   // (exact numerics: at most 8 rows per launch, never decode_kmp.hip)
         }
         return r == -2 ? fail(EMMAX_ERR_INVALID, "exact numerics: no two-term kernel for this projection (batch %d, K %d)", B, p.K) : r;
     }
@@ -38,6 +44,7 @@ static int launch_proj(const ProjW& w, GemvParams& p, int B, hipStream_t st, int
         p.W = w.r8;
         p.wscale = w.sc;
         p.ldw = p.K;   // bytes per row
+        *via = EMMAX_VIA_GEMV_FP8;
         return launch_decode_gemv(mode, p, B, st, grid_out);
     }
     if (B >= EMMAX_MFMA_MIN_BATCH || w.sc) {
@@ -47,15 +54,20 @@ static int launch_proj(const ProjW& w, GemvParams& p, int B, hipStream_t st, int
             q.W = w.km;
             q.wscale = w.sc ? w.km_sc : nullptr;
             const int r = launch_decode_km(mode, q, B, st, grid_out);
+            *via = B > 16 ? EMMAX_VIA_KMP : EMMAX_VIA_KM;   // (launch_decode_km hands 17-64 rows to decode_kmp.hip)
             if (r != -2) return r;
         }
         if (!w.fm) return fail(EMMAX_ERR_STATE, "decode_mfma.hip's copy of this matrix was not built (tuning switch km was 1 at emmax_model_build_aux)");
         p.W = w.fm;
         p.wscale = w.sc;
+        *via = EMMAX_VIA_MFMA;
         return launch_decode_mfma(mode, p, B, st, grid_out);
     }
     p.W = w.rm;
-    return launch_decode_gemv(mode, p, B, st, grid_out);
+    int staged = 0;
+    const int r = launch_decode_gemv(mode, p, B, st, grid_out, &staged);
+    *via = staged ? EMMAX_VIA_GEMV : EMMAX_VIA_KS;
+    return r;
 }
 
 // Decode batches of 9-16 rows exist on decode_km.hip only (decode_mfma.hip, the fallback for other shapes, stages eight rows): the
@@ -83,6 +95,14 @@ static bool attn_direct_on(const emmax_session* s, int B) {
     // exact numerics: the fp32 row in place over the q rows, at batch >= 3 (decode_km.hip's EX o-proj takes fp32 rows; decode_ks.hip's merges the partials)
     if (s->exact && B < EMMAX_MFMA_MIN_BATCH) return false;
     return decode_attn_nsplit(B, s->m->cfg.n_kv_heads) == 1 && emmax_tune().attn_direct != 0;
+}
+
+// what the o-proj of a B-row step reads (emmax_op_decode_stage feeds it): 0 = the bf16 attention rows, 1 = split partials (*nsplit of them per
+// (row, head)), 2 = exact numerics, the fp32 rows the one-split attention launch left over the q rows
+int decode_oproj_form(const emmax_session* s, int B, int* nsplit) {
+    const bool direct = attn_direct_on(s, B);
+    if (nsplit) *nsplit = direct ? 1 : decode_attn_nsplit(B, s->m->cfg.n_kv_heads);
+    return !direct ? 1 : (s->exact ? 2 : 0);
 }
 
 // GemvParams of a projection stage of decoder layer `li` (qkv / o-proj / gate-up / down), as every launcher takes them
@@ -295,7 +315,7 @@ int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* logits_out
     GemvParams p;
     lmhead_params(s, slot0, logits_out, p);
     int lm_grid = 0;
-    KCHK(launch_proj(m->lm_head_w, p, B, st, &lm_grid));
+    KCHK(launch_proj(m->lm_head_w, p, B, st, &lm_grid, &s->last_via));
     if (mode & 6) return launch_proc_finish_step(s, B, is_prefill, slot0, logits_out, st);
     if (sampled) return launch_sampled_finish_step(s, B, is_prefill, slot0, logits_out, st);
     if (do_finish) return launch_finish_step(s, B, is_prefill, lm_grid, slot0, st);
@@ -330,7 +350,7 @@ static int run_decode_stage_x_chunks(emmax_session* s, int B, int li, int stage,
                 p.x = (const float*)p.x + (size_t)r * p.ldx;
                 p.y = (bf16*)p.y + (size_t)r * p.ldy;
         }
-        KCHK(launch_proj(s->m->layers[li].proj[stage], p, n, st, &grid));
+        KCHK(launch_proj(s->m->layers[li].proj[stage], p, n, st, &grid, &s->last_via));
     }
     return 0;
 }
@@ -365,15 +385,15 @@ int run_decode_stage(emmax_session* s, int B, int li, int stage, hipStream_t st)
     stage_params(s, B, li, stage, p);
     if (stage == STAGE_DOWN && B > EMMAX_KMP_ROWS) {   // 33-64 rows: K = 11008 does not fit the eight phases of a four-way split -- two launches of <= 32 rows
         GemvParams q = p;
-        KCHK(launch_proj(w, q, EMMAX_KMP_ROWS, st, &grid));
+        KCHK(launch_proj(w, q, EMMAX_KMP_ROWS, st, &grid, &s->last_via));
         q = p;
         q.x = (const bf16*)q.x + (size_t)EMMAX_KMP_ROWS * q.ldx;
         q.y = (bf16*)q.y + (size_t)EMMAX_KMP_ROWS * q.ldy;
         if (q.h32) q.h32 += (size_t)EMMAX_KMP_ROWS * q.ldh;
-        KCHK(launch_proj(w, q, B - EMMAX_KMP_ROWS, st, &grid));
+        KCHK(launch_proj(w, q, B - EMMAX_KMP_ROWS, st, &grid, &s->last_via));
         return 0;
     }
-    KCHK(launch_proj(w, p, B, st, &grid));
+    KCHK(launch_proj(w, p, B, st, &grid, &s->last_via));
     return 0;
 }
 

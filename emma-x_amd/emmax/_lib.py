@@ -43,7 +43,7 @@ class ConfigC(C.Structure):
     ]
 
 
-ABI_VERSION = 9   # EMMAX_ABI_VERSION of include/emmax.h this binding was written against
+ABI_VERSION = 10   # EMMAX_ABI_VERSION of include/emmax.h this binding was written against
 
 # name -> (restype, argtypes): exactly the entry points of include/emmax.h
 SIGNATURES = {
@@ -137,6 +137,9 @@ SIGNATURES = {
     "emmax_session_beams": (C.c_int, [_vp]),
     "emmax_session_beam_result": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "emmax_session_beam_trace": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "emmax_op_decode_stage": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _c_i32p, _c_i32p, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int), C.POINTER(C.c_int), _vp]),
+    "emmax_op_decode_kv_read": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _c_i32p, C.c_int, _c_f32p, _c_f32p, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -200,6 +203,10 @@ class tuning:
         for k, v in self.old.items():
             tuning_set(k, v)
         return False
+
+
+# launcher families emmax_op_decode_stage reports (include/emmax.h: EMMAX_VIA_*)
+VIA_NONE, VIA_KS, VIA_GEMV, VIA_GEMV_FP8, VIA_KM, VIA_KMP, VIA_MFMA = range(7)
 
 
 def check(status: int, what: str = "") -> None:

@@ -40,8 +40,9 @@ extern "C" {
  *   around it), the workspace grew the per-row sampling state;  8: logits processors and scores inside the decode step
  *   (emmax_session_set_processing, emmax_session_set_scores and the calls around them), the workspace grew the per-row processing state and
  *   prompt ids;  9: beam search inside the decode step (emmax_session_set_beams and the calls around it), the workspace grew the beam
- *   state and trace; the paged KV region did not grow. */
-#define EMMAX_ABI_VERSION 9
+ *   state and trace; the paged KV region did not grow;  10: emmax_op_decode_stage / emmax_op_decode_kv_read (one decode stage through the step's
+ *   own dispatch), the workspace grew that op's per-row scratch. */
+#define EMMAX_ABI_VERSION 10
 
 typedef enum emmax_status {
     EMMAX_OK = 0,
@@ -489,6 +490,39 @@ int emmax_op_gemv_fp8(const void* x_dev, const void* W8_rows_dev, const float* s
  * emmax_op_repack_fm produces from a row-major [N,ld] matrix (N % 16 == 0, K % 32 == 0); 1 <= B <= 8. */
 int emmax_op_repack_fm(const void* W_dev, int ld, void* W_fm_out_dev, int N, int K, emmax_stream stream);
 int emmax_op_gemm_small(const void* x_dev, const void* W_fm_dev, void* y_dev, int B, int N, int K, emmax_stream stream);
+
+/* ---- one stage of a decode step through the step's own dispatch (ABI 10; tests/test_decode_stages_gpu.py) ------------------------------
+ * emmax_op_decode_stage runs ONE projection stage -- 0 qkv, 2 o-proj, 3 gate/up, 4 down of decoder layer `layer`, or 5 the lm-head with the
+ * greedy finish -- for rows 0 .. B - 1 of a created session (no prefill needed) exactly as emmax_decode_step would: the step's routing, the
+ * weight copies emmax_model_finalize / emmax_model_build_aux built, its two-launch splits (down / lm-head above 32 rows, chunks of 8 rows in
+ * exact numerics).  The caller's rows are copied into the session's buffers, the stage runs, the results are copied back; the stream is
+ * synchronised.  R = min(max_batch, 64) below.  Greedy sessions only (EMMAX_ERR_STATE with sampling, processing, scores, beams or open slots).
+ *   h_in_dev, h32_in_dev    the hidden rows: bf16 [R][hidden] and the fp32 stream [R][hidden] -- ALL R rows go in, the stage runs on B
+ *   h_out_dev, h32_out_dev  the same R rows afterwards (any may be NULL): rows B .. R - 1 must come back bit-unchanged
+ *   ctx_len_host            qkv: int32 [B], the position each row's K / V go to; a value outside 0 .. max_ctx - 2 is EMMAX_ERR_INVALID
+ *                           before anything is launched
+ *   page_table_host         qkv, optional: int32 [B][max_pages], rows 0 .. B - 1 of the page table for this launch; together they must be a
+ *                           permutation of pages 0 .. B * max_pages - 1 (what those rows own), else EMMAX_ERR_INVALID.  The identity table
+ *                           is back afterwards.  NULL: the session's table as it is
+ *   x_in_dev                o-proj: what *oproj_form_out says -- 0: the bf16 attention rows [B][Hq * 128]; 1: split partials f32
+ *                           [B][Hq][*nsplit_out][132] = {o[128] un-normalised, m, l, pad}; 2 (exact numerics, one split): fp32 rows
+ *                           [B][Hq * 128].  down: the activation rows [B][inter_p], inter_p = inter padded to 64 (bf16; fp32 in exact numerics).
+ *                           A call with stage 2 and h_in_dev = h32_in_dev = x_in_dev = NULL only reports form and nsplit for B rows
+ *   y_out_dev               qkv: the q rows [B][Hq * 128] (bf16; fp32 in exact numerics); gate/up: the activation rows [B][inter_p] (bf16;
+ *                           fp32 in exact numerics); lm-head: f32 [B][vocab] logits (required there)
+ *   tok_out_dev             lm-head: int32 [B], the token the greedy finish picks per row -- run against per-row state of the op's own, not
+ *                           the session's generation state
+ *   via_out                 the launcher family that served the LAST launch of the stage (EMMAX_VIA_*)
+ * emmax_op_decode_kv_read decodes the K and V rows of (layer, row, positions p0 .. p0 + n - 1) of the paged cache to fp32 on the HOST:
+ * k_out_host / v_out_host float [n][Hkv][head_dim], whatever the cache format (bf16, e4m3 + scale, 24-bit, fp32).  page_row_host: int32
+ * [max_pages], the row's page-table row to look positions up in (NULL: the session's).  from_stage = 1 (fp8 KV cache only): the row's entry
+ * of the staging rows the qkv launch writes instead of the cache, [1][Hkv][head_dim] each (p0 / n ignored). */
+enum { EMMAX_VIA_NONE = 0, EMMAX_VIA_KS = 1, EMMAX_VIA_GEMV = 2, EMMAX_VIA_GEMV_FP8 = 3, EMMAX_VIA_KM = 4, EMMAX_VIA_KMP = 5, EMMAX_VIA_MFMA = 6 };
+int emmax_op_decode_stage(emmax_session* s, int layer, int stage, int B, const void* h_in_dev, const float* h32_in_dev, const int32_t* ctx_len_host,
+                          const int32_t* page_table_host, const void* x_in_dev, void* h_out_dev, float* h32_out_dev, void* y_out_dev,
+                          int32_t* tok_out_dev, int* via_out, int* oproj_form_out, int* nsplit_out, emmax_stream stream);
+int emmax_op_decode_kv_read(emmax_session* s, int layer, int row, int p0, int n, const int32_t* page_row_host, int from_stage, float* k_out_host,
+                            float* v_out_host, emmax_stream stream);
 
 /* ---- exact numerics (tuning switch exact), kernel by kernel: fp32 operands in, fp32 results out (tests/test_exact_gpu.py).
  * hl_ws: device scratch for the two-term bf16 image of the activation operand, 4 bytes per (padded) element.
