@@ -195,6 +195,22 @@ __device__ __forceinline__ void x24_unpack8(const u32x4_t& hi, const u32x2_t& ex
 // position of element c of a row inside its HL image (per 64 elements: 64 hi, then 64 lo)
 __host__ __device__ __forceinline__ int hl_col(int c) { return ((c >> 6) << 7) + (c & 63); }
 
+// non-temporal 16-byte load: the weight streams (every byte is read once per launch)
+__device__ __forceinline__ u32x4_t ld_nt(const u32x4_t* p) { return __builtin_nontemporal_load(p); }
+
+// fp8 e4m3 weights -> bf16 in registers (exact: e4m3 fits bf16): v_cvt_scalef32_pk_bf16_fp8 with scale 1, two values (the low or the high half
+// of a dword) per instruction; 8 values = two dwords.  (Through v_cvt_pk_f32_fp8 + repacking it was three to four instructions per pair, and
+// VALU work is not free next to the MFMAs -- MFMA and VALU instructions of one SIMD do not overlap, tools/mfma_valu_overlap.hip -- the fp8
+// projections were bound by this conversion, not by HBM.)
+template <bool HI>
+__device__ __forceinline__ uint32_t fp8x2_to_bf16x2(uint32_t v) {
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v, 1.0f, HI));
+}
+__device__ __forceinline__ bf16x8_t fp8x8_to_bf16x8(uint32_t lo, uint32_t hi) {
+    const u32x4_t v = {fp8x2_to_bf16x2<false>(lo), fp8x2_to_bf16x2<true>(lo), fp8x2_to_bf16x2<false>(hi), fp8x2_to_bf16x2<true>(hi)};
+    return __builtin_bit_cast(bf16x8_t, v);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Activation accesses with a block-uniform `coh` switch: plain under ordinary stream ordering; agent-scope (sc1: past the
 // XCD-private L2) where a kernel reads what ANOTHER block of the same launch wrote (the in-attention split merge, decode.hip).
@@ -320,6 +336,23 @@ __device__ __forceinline__ u32x4_t attn_merge_chunk_loop(const float* __restrict
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = pack_bf16x2(a8[2 * j] * inv, a8[2 * j + 1] * inv);
     return v;
+}
+
+// o-proj prologue of the MFMA kernels (decode_mfma.hip, decode_km.hip): merge the NS split partials of head (cg >> 4) for every batch row into
+// staged bf16 rows, two rows per iteration so that the loads of both are in flight together; dst = LDS address of chunk cg of row 0
+template <int NS>
+__device__ __forceinline__ void stage_attn_rows(const float* __restrict__ attn_part, unsigned char* dst, int pitch, int B, int Hq, int cg) {
+    const float* pp0 = attn_part + (size_t)(cg >> 4) * NS * EMMAX_PSTRIDE;
+    const size_t row = (size_t)Hq * NS * EMMAX_PSTRIDE;
+    const int d0 = (cg & 15) * 8;
+    int b = 0;
+    for (; b + 1 < B; b += 2) {
+        const u32x4_t v0 = attn_merge_chunk<NS>(pp0 + (size_t)b * row, d0);
+        const u32x4_t v1 = attn_merge_chunk<NS>(pp0 + (size_t)(b + 1) * row, d0);
+        *(u32x4_t*)(dst + (size_t)b * pitch) = v0;
+        *(u32x4_t*)(dst + (size_t)(b + 1) * pitch) = v1;
+    }
+    if (b < B) *(u32x4_t*)(dst + (size_t)b * pitch) = attn_merge_chunk<NS>(pp0 + (size_t)b * row, d0);
 }
 
 // row of the SOURCE matrix (row-major, decode.hip's orders) that row r of tile t of the permuted copy holds

@@ -21,12 +21,9 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "decode_epilogue.h"
 
 namespace {
-
-enum { MODE_QKV = 0, MODE_RESID = 1, MODE_GATEUP = 2, MODE_LMHEAD = 3, MODE_PLAIN = 4 };
-
-__device__ __forceinline__ u32x4_t ld_nt(const u32x4_t* p) { return __builtin_nontemporal_load(p); }
 
 constexpr int PSTRIDE = EMMAX_PSTRIDE;   // floats per attention split partial: 128 o + m + l + 2 pad (16-byte aligned rows)
 
@@ -40,12 +37,6 @@ constexpr int PSTRIDE = EMMAX_PSTRIDE;   // floats per attention split partial: 
 // (tools/gemv_sweep.hip: this structure streams 180 MB at ~6.1 TB/s, 97 % of a read-only kernel with the same pattern.)
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int GW = 8;   // waves per GEMV block
-
-// two fp8 e4m3 (the low or the high half of a dword) -> two bf16, exact
-template <bool HI>
-__device__ __forceinline__ uint32_t fp8x2_to_bf16x2(uint32_t v) {
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v, 1.0f, HI));
-}
 
 // row-major bf16 [N, ld] -> fp8 e4m3 (OCP) rows of K bytes in the GEMV's span order + one fp32 scale per row (amax / 448, the
 // values of emmax_quant_fm8_kernel).  A row is cut into spans of 128 chunks of 8 elements (the last one shorter: nc chunks, nc
@@ -124,12 +115,12 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
     const int rounds = (g_hi - g_lo + GW - 1) / GW;
 
     auto pair_rows = [&](int g, int& r0, int& r1) {   // g: pair index (= group index on the bf16 path)
-        if (MODE == MODE_QKV) {
+        if (MODE == GEMV_QKV) {
             const int half = p.head_dim >> 1;
             const int hb = g / half, d = g - hb * half;
             r0 = hb * p.head_dim + d;
             r1 = r0 + half;
-        } else if (MODE == MODE_GATEUP) {
+        } else if (MODE == GEMV_GATEUP) {
             r0 = (g >> 4) * 32 + (g & 15);
             r1 = r0 + 16;
         } else {
@@ -237,7 +228,7 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
     const bool plain_first = false;
     // fp8: every one-pass prologue goes first -- the first burst is most of the matrix, the refills cannot go out before x is
     // staged, and x requested behind the burst arrived 7 us into a 19 us gate/up launch (tools/gemv_lab.hip)
-    const bool head_first = !((one_pass && (MODE == MODE_QKV || FP8)) || XATTN || plain_first);
+    const bool head_first = !((one_pass && (MODE == GEMV_QKV || FP8)) || XATTN || plain_first);
     if (head_first) issue_head(false);
 
     // chunk c (8 elements) of activation row b of a NORM mode: from the fp32 residual stream when the step keeps one (GemvParams::h32;
@@ -450,10 +441,7 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
     for (int i = 0; i < NP; ++i) pre_a[i] = pre_b[i] = 0.f;
 #pragma unroll
     for (int r = 0; r < NR; ++r) wsc[r] = 1.f;
-    if (MODE == MODE_QKV) {
-        pre_pos = p.ctx_len[eb];
-        pre_pg = p.page_table[(size_t)eb * p.max_pages + pre_pos / p.page];
-    }
+    if (MODE == GEMV_QKV) qkv_row_pos(p, eb, pre_pos, pre_pg);
     auto prefetch_epilogue = [&](int rd) {
         const int g = g_lo + rd * GW + wave;
         if (g >= g_hi) return;
@@ -470,24 +458,14 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
             const int pg = FP8 ? min(g * NP + i, p.n_pairs - 1) : g;
-            if (MODE == MODE_RESID) {
+            if (MODE == GEMV_RESID) {
                 int r0, r1;
                 pair_rows(pg, r0, r1);
-                if (p.h32) {
-                    pre_a[i] = p.h32[(size_t)eb * p.ldh + r0];
-                    pre_b[i] = p.h32[(size_t)eb * p.ldh + r1];
-                } else {
-                    const bf16_t* hp = (const bf16_t*)p.y + (size_t)eb * p.ldy;
-                    pre_a[i] = bf2f(ld_act_bf16(hp + r0, coh));
-                    pre_b[i] = bf2f(ld_act_bf16(hp + r1, coh));
-                }
-            } else if (MODE == MODE_QKV) {
-                const int half = p.head_dim >> 1;
-                const int hb = pg / half, d = pg - hb * half;
-                if (hb < p.Hq + p.Hkv) {
-                    pre_a[i] = p.cos_t[(size_t)pre_pos * half + d];
-                    pre_b[i] = p.sin_t[(size_t)pre_pos * half + d];
-                }
+                pre_a[i] = resid_fetch(p, eb, r0, p.h32 != nullptr, coh);
+                pre_b[i] = resid_fetch(p, eb, r1, p.h32 != nullptr, coh);
+            } else if (MODE == GEMV_QKV) {
+                const int half = p.head_dim >> 1, hb = pg / half;
+                qkv_rope_fetch(p, pre_pos, hb, pg - hb * half, pre_a[i], pre_b[i]);
             }
         }
     };
@@ -599,14 +577,14 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
         }
         int r0, r1;
         pair_rows(pg, r0, r1);
-        if (MODE == MODE_PLAIN) {
+        if (MODE == GEMV_PLAIN) {
 #pragma unroll
             for (int b = 0; b < B; ++b)
                 if (lane == b) {
                     st_act_bf16((bf16_t*)p.y + (size_t)b * p.ldy + r0, f2bf(red0[b]), coh);
                     if (2 * pg + 1 < p.n_rows) st_act_bf16((bf16_t*)p.y + (size_t)b * p.ldy + r1, f2bf(red1[b]), coh);
                 }
-        } else if (MODE == MODE_RESID) {
+        } else if (MODE == GEMV_RESID) {
 #pragma unroll
             for (int b = 0; b < B; ++b)
                 if (lane == b) {
@@ -619,11 +597,11 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
                     st_act_bf16(hp + r0, f2bf(pre_a[i] + red0[b]), coh);
                     if (2 * pg + 1 < p.n_rows) st_act_bf16(hp + r1, f2bf(pre_b[i] + red1[b]), coh);
                 }
-        } else if (MODE == MODE_GATEUP) {
+        } else if (MODE == GEMV_GATEUP) {
 #pragma unroll
             for (int b = 0; b < B; ++b)
-                if (lane == b) st_act_bf16((bf16_t*)p.y + (size_t)b * p.ldy + pg, f2bf(silu(red0[b]) * red1[b]), coh);
-        } else if (MODE == MODE_QKV) {
+                if (lane == b) swiglu_finish<false>(p, b, pg, red0[b], red1[b], coh);
+        } else if (MODE == GEMV_QKV) {
             const int hd = p.head_dim, half = hd >> 1;
             const int hb = pg / half, d = pg - hb * half;
 #pragma unroll
@@ -652,7 +630,7 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
                         st_act_bf16(vc + d + half, f2bf(x1), coh);
                     }
                 }
-        } else if (MODE == MODE_LMHEAD) {
+        } else if (MODE == GEMV_LMHEAD) {
 #pragma unroll
             for (int b = 0; b < B; ++b) {
 #pragma unroll
@@ -660,10 +638,7 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
                     const int row = r == 0 ? r0 : r1;
                     if (r == 1 && 2 * pg + 1 >= p.n_rows) continue;
                     const float v = r == 0 ? red0[b] : red1[b];
-                    if (v > best[b] || (v == best[b] && row < besti[b])) {
-                        best[b] = v;
-                        besti[b] = row;
-                    }
+                    lmhead_take(v, row, best[b], besti[b]);
                     if (p.logits_out && lane == 0) p.logits_out[(size_t)b * p.n_rows + row] = v;
                 }
             }
@@ -672,7 +647,7 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
     }
 
     GEMV_STAMP(4);
-    if (MODE == MODE_LMHEAD) {
+    if (MODE == GEMV_LMHEAD) {
         // block best; first index wins ties (torch.argmax semantics); one partial per block
         __shared__ float bv[GW][B];
         __shared__ int bi[GW][B];
@@ -684,20 +659,10 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
             }
         }
         __syncthreads();
+        // thread b: the eight waves' candidates of batch row b, starting from wave 0's
         if (tid < B) {
-            float v0 = bv[0][tid];
-            int i0 = bi[0][tid];
-#pragma unroll
-            for (int w = 1; w < GW; ++w) {
-                const float v = bv[w][tid];
-                const int ii = bi[w][tid];
-                if (v > v0 || (v == v0 && ii < i0)) {
-                    v0 = v;
-                    i0 = ii;
-                }
-            }
-            st_act_f32(p.part_val + (size_t)blockIdx.x * B + tid, v0, coh);
-            st_act_i32(p.part_idx + (size_t)blockIdx.x * B + tid, i0, coh);
+            const auto slot = [&](int k) { return (k + 1) * B + tid; };
+            lmhead_col_finish(p, B, tid, &bv[0][0], &bi[0][0], GW - 1, slot, bv[0][tid], bi[0][tid], coh);
         }
     }
 }
@@ -1090,7 +1055,7 @@ template <int B, int MODE, bool NORM, bool XATTN = false, int F8 = 0>
 static int launch_gemv_t(const GemvParams& p, hipStream_t stream, int* grid_out) {
     const size_t smem = (size_t)B * (p.kc * 2 + 16);
     int grid = gemv_grid(B, smem, p.n_groups, (F8 == 1 || F8 == 2) ? 256 : p.max_grid);
-    if (MODE == MODE_LMHEAD) grid = min(grid, p.max_parts);
+    if (MODE == GEMV_LMHEAD) grid = min(grid, p.max_parts);
     if (grid_out) *grid_out = grid;
     auto kern = emmax_decode_gemv_kernel<B, MODE, NORM, XATTN, F8>;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(GW * 64), smem, stream, p);
@@ -1103,8 +1068,8 @@ static int launch_gemv_mode(GemvParams p, int B, hipStream_t stream, int* grid_o
     const int cap = (128 * 1024 / 2 / B) & ~511;
     p.kc = p.K <= cap ? p.K : (cdiv(cdiv(p.K, cdiv(p.K, cap)), 512) * 512);
     if (NORM && p.kc != p.K) return -1;
-    if (MODE == MODE_QKV) p.n_groups = p.n_rows / 2;
-    else if (MODE == MODE_GATEUP) p.n_groups = p.n_rows / 2;
+    if (MODE == GEMV_QKV) p.n_groups = p.n_rows / 2;
+    else if (MODE == GEMV_GATEUP) p.n_groups = p.n_rows / 2;
     else p.n_groups = (p.n_rows + 1) / 2;
     p.n_pairs = p.n_groups;
     if (p.wscale) {   // fp8 rows (batch 1-2, one K phase)
@@ -1139,12 +1104,12 @@ static int gemv_init_mode() {
 int decode_gemv_init() {
     static int done = -1;
     if (done == 0) return 0;
-    int r = gemv_init_mode<MODE_QKV, true>();
-    if (!r) r = gemv_init_mode<MODE_RESID, false>();
-    if (!r) r = gemv_init_mode<MODE_RESID, false, true>();
-    if (!r) r = gemv_init_mode<MODE_GATEUP, true>();
-    if (!r) r = gemv_init_mode<MODE_LMHEAD, true>();
-    if (!r) r = gemv_init_mode<MODE_PLAIN, false>();
+    int r = gemv_init_mode<GEMV_QKV, true>();
+    if (!r) r = gemv_init_mode<GEMV_RESID, false>();
+    if (!r) r = gemv_init_mode<GEMV_RESID, false, true>();
+    if (!r) r = gemv_init_mode<GEMV_GATEUP, true>();
+    if (!r) r = gemv_init_mode<GEMV_LMHEAD, true>();
+    if (!r) r = gemv_init_mode<GEMV_PLAIN, false>();
     done = r;
     return r;
 }
@@ -1171,13 +1136,13 @@ int launch_decode_gemv(int mode, const GemvParams& p, int B, hipStream_t stream,
     }
     if (staged_out) *staged_out = 1;
     switch (mode) {
-        case MODE_QKV: return launch_gemv_mode<MODE_QKV, true>(p, B, stream, grid_out);
-        case MODE_RESID:
-            return p.attn_part ? launch_gemv_mode<MODE_RESID, false, true>(p, B, stream, grid_out)
-                               : launch_gemv_mode<MODE_RESID, false>(p, B, stream, grid_out);
-        case MODE_GATEUP: return launch_gemv_mode<MODE_GATEUP, true>(p, B, stream, grid_out);
-        case MODE_LMHEAD: return launch_gemv_mode<MODE_LMHEAD, true>(p, B, stream, grid_out);
-        case MODE_PLAIN: return launch_gemv_mode<MODE_PLAIN, false>(p, B, stream, grid_out);
+        case GEMV_QKV: return launch_gemv_mode<GEMV_QKV, true>(p, B, stream, grid_out);
+        case GEMV_RESID:
+            return p.attn_part ? launch_gemv_mode<GEMV_RESID, false, true>(p, B, stream, grid_out)
+                               : launch_gemv_mode<GEMV_RESID, false>(p, B, stream, grid_out);
+        case GEMV_GATEUP: return launch_gemv_mode<GEMV_GATEUP, true>(p, B, stream, grid_out);
+        case GEMV_LMHEAD: return launch_gemv_mode<GEMV_LMHEAD, true>(p, B, stream, grid_out);
+        case GEMV_PLAIN: return launch_gemv_mode<GEMV_PLAIN, false>(p, B, stream, grid_out);
         default: return -1;
     }
 }

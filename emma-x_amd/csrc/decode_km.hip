@@ -25,6 +25,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "decode_epilogue.h"
 
 namespace {
 
@@ -33,16 +34,6 @@ constexpr int KM_NT = KM_WAVES * 64;
 constexpr int KM_STEPS = 16;      // bf16 k-steps (32 elements) per tile and wave: K <= 8 * 16 * 32 = 4096
 constexpr int KM_MAX_TILES = 8;   // tiles per block the LDS partial sums hold
 constexpr int PSTRIDE = EMMAX_PSTRIDE;
-
-// two fp8 e4m3 pairs (the low / high half of a dword) -> two bf16, exact
-template <bool HI>
-__device__ __forceinline__ uint32_t km_fp8x2(uint32_t v) {
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v, 1.0f, HI));
-}
-__device__ __forceinline__ bf16x8_t km_fp8x8(uint32_t lo, uint32_t hi) {
-    const u32x4_t v = {km_fp8x2<false>(lo), km_fp8x2<true>(lo), km_fp8x2<false>(hi), km_fp8x2<true>(hi)};
-    return __builtin_bit_cast(bf16x8_t, v);
-}
 
 // row-major [N, ld] -> fragment-major tiles in the km row order (N % 16 == 0, K % 32 == 0)
 __global__ __launch_bounds__(256) void emmax_repack_km_kernel(const bf16_t* __restrict__ src, int ld, u32x4_t* __restrict__ dst, int N, int K,
@@ -55,23 +46,6 @@ __global__ __launch_bounds__(256) void emmax_repack_km_kernel(const bf16_t* __re
         const int n = km_src_row(perm, head_dim, nt, lane & 15), k = kt * 32 + (lane >> 4) * 8;
         dst[c] = *(const u32x4_t*)(src + (size_t)n * ld + k);
     }
-}
-
-// o-proj prologue: merge the NS split partials of head (cg >> 4) for every batch row into the staged rows [B][K] bf16, two rows per
-// iteration so that the loads of both are in flight together (branch-free merge: attn_merge_chunk, common.h)
-template <int NS>
-__device__ __forceinline__ void km_merge_rows(const float* __restrict__ attn_part, unsigned char* dst, int pitch, int B, int Hq, int cg) {
-    const float* pp0 = attn_part + (size_t)(cg >> 4) * NS * PSTRIDE;
-    const size_t row = (size_t)Hq * NS * PSTRIDE;
-    const int d0 = (cg & 15) * 8;
-    int b = 0;
-    for (; b + 1 < B; b += 2) {
-        const u32x4_t v0 = attn_merge_chunk<NS>(pp0 + (size_t)b * row, d0);
-        const u32x4_t v1 = attn_merge_chunk<NS>(pp0 + (size_t)(b + 1) * row, d0);
-        *(u32x4_t*)(dst + (size_t)b * pitch) = v0;
-        *(u32x4_t*)(dst + (size_t)(b + 1) * pitch) = v1;
-    }
-    if (b < B) *(u32x4_t*)(dst + (size_t)b * pitch) = attn_merge_chunk<NS>(pp0 + (size_t)b * row, d0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -130,31 +104,7 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
     const int e_tile = t_lo + min(e_tl, max(ntb - 1, 0));
     float pre_a[4] = {0.f, 0.f, 0.f, 0.f}, pre_b[4] = {0.f, 0.f, 0.f, 0.f};
     int pre_pos = 0, pre_pg = 0;
-    if (e_on) {
-        if (MODE == GEMV_RESID) {
-            if constexpr (R32) {
-                const f32x4_t hv = *(const f32x4_t*)(p.h32 + (size_t)e_c * p.ldh + e_tile * 16 + 4 * e_rq);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) pre_a[j] = hv[j];
-            } else {
-                const bf16_t* hp = (const bf16_t*)p.y + (size_t)e_c * p.ldy + e_tile * 16 + 4 * e_rq;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) pre_a[j] = bf2f(hp[j]);
-            }
-        } else if (MODE == GEMV_QKV) {
-            pre_pos = p.ctx_len[e_c];
-            pre_pg = p.page_table[(size_t)e_c * p.max_pages + pre_pos / p.page];
-            const int hd = p.head_dim, half = hd >> 1, tph = hd / 16;
-            const int hb = e_tile / tph, d0 = 8 * (e_tile - hb * tph) + 4 * e_rq;
-            if (hb < p.Hq + p.Hkv) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    pre_a[j] = p.cos_t[(size_t)pre_pos * half + d0 + j];
-                    pre_b[j] = p.sin_t[(size_t)pre_pos * half + d0 + j];
-                }
-            }
-        }
-    }
+    if (e_on) tile4_prefetch<MODE, R32>(p, e_c, e_tile, e_rq, pre_a, pre_b, pre_pos, pre_pg);
 
     // ---- weight stream: buffer loads, the (tile, step) offset in an SGPR, the lane's 16 bytes in the VGPR offset ----
     const unsigned w_bytes = (unsigned)((size_t)p.n_groups * 16 * (size_t)K * (FP8 ? 1 : 2));
@@ -201,10 +151,10 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
                 continue;
             }
             switch (p.nsplit) {
-                case 1: km_merge_rows<1>(p.attn_part, dst, K * 2, B, p.Hq, c); break;
-                case 2: km_merge_rows<2>(p.attn_part, dst, K * 2, B, p.Hq, c); break;
-                case 4: km_merge_rows<4>(p.attn_part, dst, K * 2, B, p.Hq, c); break;
-                case 8: km_merge_rows<8>(p.attn_part, dst, K * 2, B, p.Hq, c); break;
+                case 1: stage_attn_rows<1>(p.attn_part, dst, K * 2, B, p.Hq, c); break;
+                case 2: stage_attn_rows<2>(p.attn_part, dst, K * 2, B, p.Hq, c); break;
+                case 4: stage_attn_rows<4>(p.attn_part, dst, K * 2, B, p.Hq, c); break;
+                case 8: stage_attn_rows<8>(p.attn_part, dst, K * 2, B, p.Hq, c); break;
                 default:
                     for (int b = 0; b < B; ++b)
                         *(u32x4_t*)(dst + (size_t)b * K * 2) =
@@ -302,8 +252,8 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
 #pragma unroll
         for (int s = 0; s < NSTEP; ++s) {
             if constexpr (FP8) {
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(km_fp8x8(w[s][0], w[s][1]), xf[2 * s], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(km_fp8x8(w[s][2], w[s][3]), xf[2 * s + 1], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fp8x8_to_bf16x8(w[s][0], w[s][1]), xf[2 * s], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fp8x8_to_bf16x8(w[s][2], w[s][3]), xf[2 * s + 1], acc, 0, 0, 0);
             } else {
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, w[s]), xf[s], acc, 0, 0, 0);
             }
@@ -359,6 +309,8 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
             for (int w = 0; w < KM_WAVES; ++w) t += sumsq[w * 16 + e_c];
             sc = rsqrtf(t / (float)K + p.eps);
         }
+        // (rstd and the row's weight scale are multiplied TOGETHER first here; decode_kmp.hip applies them one after the other -- two
+        // roundings in another order, so the scaling is not part of the shared tile finish)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float sv = sc, su = sc;
@@ -372,27 +324,8 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
     }
     float best = -INFINITY;
     int besti = 0x7fffffff;
-    if (e_on) {
-        const int row0 = e_tile * 16 + 4 * e_rq;   // natural-order matrices
-        if (MODE == GEMV_PLAIN) {
-            bf16_t* yp = (bf16_t*)p.y + (size_t)e_c * p.ldy + row0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) yp[j] = f2bf(v[j]);
-        } else if (MODE == GEMV_RESID) {
-            if constexpr (R32)
-                *(f32x4_t*)(p.h32 + (size_t)e_c * p.ldh + row0) = (f32x4_t){pre_a[0] + v[0], pre_a[1] + v[1], pre_a[2] + v[2], pre_a[3] + v[3]};
-            bf16_t* hp = (bf16_t*)p.y + (size_t)e_c * p.ldy + row0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) hp[j] = f2bf(pre_a[j] + v[j]);
-        } else if (MODE == GEMV_GATEUP && EX) {
-            float* yp = (float*)p.y + (size_t)e_c * p.ldy + 8 * e_tile + 4 * e_rq;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) yp[j] = silu_precise(v[j]) * u[j];
-        } else if (MODE == GEMV_GATEUP) {
-            bf16_t* yp = (bf16_t*)p.y + (size_t)e_c * p.ldy + 8 * e_tile + 4 * e_rq;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) yp[j] = f2bf(silu(v[j]) * u[j]);
-        } else if (MODE == GEMV_QKV && EX) {
+    if (e_on && MODE == GEMV_QKV) {
+        if constexpr (EX) {
             // nothing is rounded to bf16: fp32 RoPE (every product rounded on its own, as torch does), fp32 q rows, 24-bit / fp32 cache rows
             const int hd = p.head_dim, half = hd >> 1, tph = hd / 16;
             const int hb = e_tile / tph, d0 = 8 * (e_tile - hb * tph) + 4 * e_rq;
@@ -415,7 +348,7 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
                     gemv_kv_store_x(p, true, pre_pg, pre_pos, hb - p.Hq - p.Hkv, d + half, u[j]);
                 }
             }
-        } else if (MODE == GEMV_QKV) {
+        } else {
             const int hd = p.head_dim, half = hd >> 1, tph = hd / 16;
             const int hb = e_tile / tph, d0 = 8 * (e_tile - hb * tph) + 4 * e_rq;
 #pragma unroll
@@ -440,16 +373,9 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
                     vc[d + half] = f2bf(x1);
                 }
             }
-        } else if (MODE == GEMV_LMHEAD) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int row = row0 + j;
-                if (row < p.n_rows) {
-                    if (v[j] > best) { best = v[j]; besti = row; }   // rows ascend: the first index wins ties
-                    if (p.logits_out) p.logits_out[(size_t)e_c * p.n_rows + row] = v[j];
-                }
-            }
         }
+    } else if (e_on) {
+        tile4_finish<MODE, R32, EX>(p, e_c, e_tile, e_rq, v, u, pre_a, best, besti);
     }
     if (MODE == GEMV_LMHEAD) {
         // block best per batch column: the 32 slots (tile, row quarter) of a column through LDS; first index wins ties
@@ -460,17 +386,8 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
         bi[tid] = besti;
         __syncthreads();
         if (tid < B) {
-            float v0 = -INFINITY;
-            int i0 = 0x7fffffff;
-            for (int tl = 0; tl < KM_WAVES; ++tl)
-                for (int rq = 0; rq < 4; ++rq) {
-                    const int e = tl * 64 + rq * 16 + tid;
-                    const float x = bv[e];
-                    const int ii = bi[e];
-                    if (x > v0 || (x == v0 && ii < i0)) { v0 = x; i0 = ii; }
-                }
-            p.part_val[(size_t)bid * B + tid] = v0;
-            p.part_idx[(size_t)bid * B + tid] = i0;
+            const auto slot = [&](int k) { return (k >> 2) * 64 + (k & 3) * 16 + tid; };
+            lmhead_col_finish(p, B, tid, bv, bi, KM_WAVES * 4, slot, -INFINITY, 0x7fffffff);
         }
     }
 }
@@ -513,17 +430,7 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_kmd_kernel(GemvParams p
     // epilogue operands of thread (lane l of wave 0): rows 4 (l >> 4) + j, batch column l & 15
     const bool e_on = tid < 64 && c16 < B && (!EX || c16 < 8);
     float pre[4] = {0.f, 0.f, 0.f, 0.f};
-    if (e_on) {
-        if constexpr (R32) {
-            const f32x4_t hv = *(const f32x4_t*)(p.h32 + (size_t)c16 * p.ldh + tile * 16 + 4 * g4);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) pre[j] = hv[j];
-        } else {
-            const bf16_t* hp = (const bf16_t*)p.y + (size_t)c16 * p.ldy + tile * 16 + 4 * g4;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) pre[j] = bf2f(hp[j]);
-        }
-    }
+    if (e_on) tile4_resid_prefetch<R32>(p, c16, tile * 16 + 4 * g4, pre);
 
     // ---- activation row slices of a phase: lane l holds chunks l (and l + 64) of the phase's slice, for every batch row ----
     auto phase_steps = [&](int ph) { return max(0, min(NST, k_n - ph * NST)); };
@@ -611,8 +518,8 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_kmd_kernel(GemvParams p
     };
     auto mfma_step = [&](int s) {
         if constexpr (FP8) {
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(km_fp8x8(w[s][0], w[s][1]), frag(2 * s), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(km_fp8x8(w[s][2], w[s][3]), frag(2 * s + 1), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fp8x8_to_bf16x8(w[s][0], w[s][1]), frag(2 * s), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fp8x8_to_bf16x8(w[s][2], w[s][3]), frag(2 * s + 1), acc, 0, 0, 0);
         } else {
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, w[s]), frag(s), acc, 0, 0, 0);
         }
@@ -651,15 +558,11 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_kmd_kernel(GemvParams p
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] += vl[j];
         }
+        if constexpr (FP8) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if constexpr (FP8) v[j] *= p.wscale[tile * 16 + 4 * g4 + j];
-            v[j] += pre[j];
+            for (int j = 0; j < 4; ++j) v[j] *= p.wscale[tile * 16 + 4 * g4 + j];
         }
-        if constexpr (R32) *(f32x4_t*)(p.h32 + (size_t)c16 * p.ldh + tile * 16 + 4 * g4) = (f32x4_t){v[0], v[1], v[2], v[3]};
-        bf16_t* hp = (bf16_t*)p.y + (size_t)c16 * p.ldy + tile * 16 + 4 * g4;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) hp[j] = f2bf(v[j]);
+        tile4_resid_finish<R32>(p, c16, tile * 16 + 4 * g4, pre, v);
     }
 }
 

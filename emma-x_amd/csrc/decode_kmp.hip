@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "decode_epilogue.h"
 
 namespace {
 
@@ -43,16 +44,6 @@ constexpr int KP_RPL = KP_ROWS * KP_PH * 4 / 64;   // 16-byte chunks per lane an
 
 // phases of weights in flight (fp8 tiles carry 64 k per KiB: twice the phases for the same bytes)
 template <int TMAX, bool FP8> struct KpLook { static constexpr int L = (TMAX >= 4 ? 1 : TMAX >= 2 ? 2 : 4) * (FP8 ? 2 : 1); };
-
-// two fp8 e4m3 pairs (the low / high half of a dword) -> two bf16, exact (as decode_km.hip)
-template <bool HI>
-__device__ __forceinline__ uint32_t kp_fp8x2(uint32_t v) {
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(v, 1.0f, HI));
-}
-__device__ __forceinline__ bf16x8_t kp_fp8x8(uint32_t lo, uint32_t hi) {
-    const u32x4_t v = {kp_fp8x2<false>(lo), kp_fp8x2<true>(lo), kp_fp8x2<false>(hi), kp_fp8x2<true>(hi)};
-    return __builtin_bit_cast(bf16x8_t, v);
-}
 
 // activation row sets in flight (registers): the eleven-phase down projection keeps two
 template <int TMAX, int NPH> struct KpRowSets { static constexpr int N = (NPH > 4 && TMAX == 1) ? KP_XD_LONG : 1; };
@@ -106,31 +97,7 @@ __global__ __launch_bounds__(KP_THREADS, 2) void emmax_decode_kmp_kernel(GemvPar
         e_on[nt] = e_tl < ntb && e_tl < TMAX && e_c < B && (!e_pairs || e_rq < 2);
 #pragma unroll
         for (int j = 0; j < 4; ++j) pre_a[nt][j] = pre_b[nt][j] = 0.f;
-        if (e_on[nt]) {
-            if (MODE == GEMV_RESID) {
-                if constexpr (R32) {
-                    const f32x4_t hv = *(const f32x4_t*)(p.h32 + (size_t)e_c * p.ldh + e_tile * 16 + 4 * e_rq);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) pre_a[nt][j] = hv[j];
-                } else {
-                    const bf16_t* hp = (const bf16_t*)p.y + (size_t)e_c * p.ldy + e_tile * 16 + 4 * e_rq;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) pre_a[nt][j] = bf2f(hp[j]);
-                }
-            } else if (MODE == GEMV_QKV) {
-                pre_pos[nt] = p.ctx_len[e_c];
-                pre_pg[nt] = p.page_table[(size_t)e_c * p.max_pages + pre_pos[nt] / p.page];
-                const int hd = p.head_dim, half = hd >> 1, tph = hd / 16;
-                const int hb = e_tile / tph, d0 = 8 * (e_tile - hb * tph) + 4 * e_rq;
-                if (hb < p.Hq + p.Hkv) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        pre_a[nt][j] = p.cos_t[(size_t)pre_pos[nt] * half + d0 + j];
-                        pre_b[nt][j] = p.sin_t[(size_t)pre_pos[nt] * half + d0 + j];
-                    }
-                }
-            }
-        }
+        if (e_on[nt]) tile4_prefetch<MODE, R32>(p, e_c, e_tile, e_rq, pre_a[nt], pre_b[nt], pre_pos[nt], pre_pg[nt]);
     }
 
     // ---- weight stream: buffer loads, the (tile, step) offset in an SGPR, the lane's 16 bytes in the VGPR offset ----
@@ -254,7 +221,7 @@ __global__ __launch_bounds__(KP_THREADS, 2) void emmax_decode_kmp_kernel(GemvPar
                     constexpr int slot0 = (ph % LOOK) * TMAX * PHS;                                                     \
                     const u32x4_t wv = w[slot0 + tl * PHS + s];                                                         \
                     if constexpr (FP8) { /* a 16 x 64 e4m3 tile: two bf16 fragments */                                  \
-                        const bf16x8_t wlo = kp_fp8x8(wv[0], wv[1]), whi = kp_fp8x8(wv[2], wv[3]);                      \
+                        const bf16x8_t wlo = fp8x8_to_bf16x8(wv[0], wv[1]), whi = fp8x8_to_bf16x8(wv[2], wv[3]);        \
                         acc[tl][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlo, xf[2 * s][0], acc[tl][0], 0, 0, 0);   \
                         acc[tl][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlo, xf[2 * s][1], acc[tl][1], 0, 0, 0);   \
                         acc[tl][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whi, xf[2 * s + 1][0], acc[tl][0], 0, 0, 0); \
@@ -336,22 +303,8 @@ __global__ __launch_bounds__(KP_THREADS, 2) void emmax_decode_kmp_kernel(GemvPar
                     if (e_pairs) u[j] *= p.wscale[q_tile * 16 + 8 + 4 * e_rq + j];
                 }
             }
-            const int row0 = q_tile * 16 + 4 * e_rq;   // natural-order matrices
-            if (MODE == GEMV_PLAIN) {
-                bf16_t* yp = (bf16_t*)p.y + (size_t)e_c * p.ldy + row0;
-    #pragma unroll
-                for (int j = 0; j < 4; ++j) yp[j] = f2bf(v[j]);
-            } else if (MODE == GEMV_RESID) {
-                if constexpr (R32)
-                    *(f32x4_t*)(p.h32 + (size_t)e_c * p.ldh + row0) = (f32x4_t){pre_a[nt][0] + v[0], pre_a[nt][1] + v[1], pre_a[nt][2] + v[2], pre_a[nt][3] + v[3]};
-                bf16_t* hp = (bf16_t*)p.y + (size_t)e_c * p.ldy + row0;
-    #pragma unroll
-                for (int j = 0; j < 4; ++j) hp[j] = f2bf(pre_a[nt][j] + v[j]);
-            } else if (MODE == GEMV_GATEUP) {
-                bf16_t* yp = (bf16_t*)p.y + (size_t)e_c * p.ldy + 8 * q_tile + 4 * e_rq;
-    #pragma unroll
-                for (int j = 0; j < 4; ++j) yp[j] = f2bf(silu(v[j]) * u[j]);
-            } else if (MODE == GEMV_QKV) {
+            if (MODE == GEMV_QKV) {
+                // (the rotation stays in each kernel's own text: decode_epilogue.h says why)
                 const int hd = p.head_dim, half = hd >> 1, tph = hd / 16;
                 const int hb = q_tile / tph, d0 = 8 * (q_tile - hb * tph) + 4 * e_rq;
                 const int pos = pre_pos[nt], pg = pre_pg[nt];
@@ -377,15 +330,8 @@ __global__ __launch_bounds__(KP_THREADS, 2) void emmax_decode_kmp_kernel(GemvPar
                         vc[d + half] = f2bf(x1);
                     }
                 }
-            } else if (MODE == GEMV_LMHEAD) {
-    #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int row = row0 + j;
-                    if (row < p.n_rows) {
-                        if (v[j] > best[nt]) { best[nt] = v[j]; besti[nt] = row; }   // rows ascend: the first index wins ties
-                        if (p.logits_out) p.logits_out[(size_t)e_c * p.n_rows + row] = v[j];
-                    }
-                }
+            } else {
+                tile4_finish<MODE, R32, false>(p, e_c, q_tile, e_rq, v, u, pre_a[nt], best[nt], besti[nt]);
             }
         }
     }
@@ -402,17 +348,8 @@ __global__ __launch_bounds__(KP_THREADS, 2) void emmax_decode_kmp_kernel(GemvPar
         __syncthreads();
         if (tid < B) {
             const int nt = tid >> 4, c = tid & 15;
-            float v0 = -INFINITY;
-            int i0 = 0x7fffffff;
-            for (int tl = 0; tl < KP_WAVES; ++tl)
-                for (int rq = 0; rq < 4; ++rq) {
-                    const int e = nt * KP_THREADS + tl * 64 + rq * 16 + c;
-                    const float x = bv[e];
-                    const int ii = bi[e];
-                    if (x > v0 || (x == v0 && ii < i0)) { v0 = x; i0 = ii; }
-                }
-            p.part_val[(size_t)bid * B + tid] = v0;
-            p.part_idx[(size_t)bid * B + tid] = i0;
+            const auto slot = [&](int k) { return nt * KP_THREADS + (k >> 2) * 64 + (k & 3) * 16 + c; };
+            lmhead_col_finish(p, B, tid, bv, bi, KP_WAVES * 4, slot, -INFINITY, 0x7fffffff);
         }
     }
 }

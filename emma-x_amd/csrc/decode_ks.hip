@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "decode_epilogue.h"
 
 #ifndef KS_W_AUX
 #define KS_W_AUX 2   // cache policy of the weight stream (lab: -DKS_W_AUX=n; 2 = nt, the product)
@@ -30,8 +31,6 @@ namespace {
 constexpr int KS_WAVES = 8;
 constexpr int KS_NT = KS_WAVES * 64;
 constexpr int PSTRIDE = EMMAX_PSTRIDE;
-
-__device__ __forceinline__ u32x4_t ks_ld_nt(const u32x4_t* p) { return __builtin_nontemporal_load(p); }
 
 // ---- transposing reduction ------------------------------------------------------------------------------------------
 // In: v[j], j < RB = this lane's partial sum of row j.  Out: the total of row ks_row_of_lane<RB>(lane) (every lane of the
@@ -205,24 +204,12 @@ __device__ __forceinline__ void ks_run_op(const GemvParams& p, u32x4_t (&wr)[KsR
     int pre_pos = 0, pre_pg = 0;
     if (epi) {
         if (MODE == GEMV_RESID) {
-            if constexpr (R32) {
-                const float* hp = p.h32 + (size_t)eb * p.ldh;
-                pre_a = hp[er0];
-                pre_b = hp[er1];
-            } else {
-                const bf16_t* hp = (const bf16_t*)p.y + (size_t)eb * p.ldy;
-                pre_a = bf2f(hp[er0]);
-                pre_b = bf2f(hp[er1]);
-            }
+            pre_a = resid_fetch(p, eb, er0, R32);
+            pre_b = resid_fetch(p, eb, er1, R32);
         } else if (MODE == GEMV_QKV) {
-            pre_pos = p.ctx_len[eb];
-            pre_pg = p.page_table[(size_t)eb * p.max_pages + pre_pos / p.page];
-            const int half = p.head_dim >> 1;
-            const int hb = epair >> p.ks_shift, d = epair - hb * half;
-            if (hb < p.Hq + p.Hkv) {
-                pre_a = p.cos_t[(size_t)pre_pos * half + d];
-                pre_b = p.sin_t[(size_t)pre_pos * half + d];
-            }
+            qkv_row_pos(p, eb, pre_pos, pre_pg);
+            const int hb = epair >> p.ks_shift;
+            qkv_rope_fetch(p, pre_pos, hb, epair - hb * (p.head_dim >> 1), pre_a, pre_b);
         }
     }
 
@@ -440,18 +427,14 @@ __device__ __forceinline__ void ks_run_op(const GemvParams& p, u32x4_t (&wr)[KsR
                 hq[er0] = pre_a + red0;
                 if (has1) hq[er1] = pre_b + red1;
             }
+            // (the pair's two mirrors come out of ONE v_cvt_pk_bf16_f32)
             const uint32_t hv = pack_bf16x2(pre_a + red0, pre_b + red1);
             bf16_t* hp = (bf16_t*)p.y + (size_t)eb * p.ldy;
             hp[er0] = (bf16_t)(hv & 0xffffu);
             if (has1) hp[er1] = (bf16_t)(hv >> 16);
         }
     } else if (MODE == GEMV_GATEUP) {
-        if constexpr (EX) {
-            if (epi) ((float*)p.y)[(size_t)eb * p.ldy + epair] = silu_precise(red0) * red1;
-        } else {
-            const float a = silu(red0) * red1;
-            if (epi) ((bf16_t*)p.y)[(size_t)eb * p.ldy + epair] = f2bf(a);
-        }
+        if (epi) swiglu_finish<EX>(p, eb, epair, red0, red1);
     } else if (MODE == GEMV_QKV && EX) {
         if (epi) {   // exact numerics: nothing is rounded to bf16 -- fp32 RoPE (every product rounded on its own, as torch does), fp32 q, fp32 cache rows
             const int hd = p.head_dim, half = hd >> 1;
@@ -501,7 +484,7 @@ __device__ __forceinline__ void ks_run_op(const GemvParams& p, u32x4_t (&wr)[KsR
             if (epi) {
                 bv = red0;
                 bi = er0;
-                if (has1 && red1 > bv) { bv = red1; bi = er1; }   // er1 > er0: the first index wins ties (torch.argmax)
+                if (has1) lmhead_take(red1, er1, bv, bi);   // (er1 > er0)
                 if (p.logits_out) {
                     p.logits_out[(size_t)eb * p.n_rows + er0] = red0;
                     if (has1) p.logits_out[(size_t)eb * p.n_rows + er1] = red1;

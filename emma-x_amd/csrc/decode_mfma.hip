@@ -15,14 +15,13 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "decode_epilogue.h"
 
 namespace {
 
-enum { MODE_QKV = 0, MODE_RESID = 1, MODE_GATEUP = 2, MODE_LMHEAD = 3, MODE_PLAIN = 4 };
 constexpr int PSTRIDE = EMMAX_PSTRIDE;
 constexpr int MFMA_MAX_B = 8;   // this kernel stages at most 8 batch rows (batch 9-16 run on decode_km.hip only)
 constexpr int GW = 8;
-__device__ __forceinline__ u32x4_t ld_nt(const u32x4_t* p) { return __builtin_nontemporal_load(p); }
 
 // row-major [N, ld] -> fragment-major tiles (N % 16 == 0, K % 32 == 0)
 __global__ __launch_bounds__(256) void emmax_repack_fm_kernel(const bf16_t* __restrict__ src, int ld, u32x4_t* __restrict__ dst, int N, int K) {
@@ -72,39 +71,6 @@ __global__ __launch_bounds__(256) void emmax_quant_fm8_kernel(const bf16_t* __re
     }
 }
 
-// 8 fp8 e4m3 (two dwords) -> 8 bf16 (exact: e4m3 fits bf16): v_cvt_scalef32_pk_bf16_fp8 with scale 1, two values per
-// instruction.  (Through v_cvt_pk_f32_fp8 + repacking it was three to four instructions per pair, and VALU work is not free
-// next to the MFMAs -- MFMA and VALU instructions of one SIMD do not overlap, tools/mfma_valu_overlap.hip -- the fp8
-// projections were bound by this conversion, not by HBM.)
-__device__ __forceinline__ bf16x8_t fp8x8_to_bf16x8(uint32_t a, uint32_t b) {
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2v;
-    const bf16x2v p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(a, 1.0f, false), p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(a, 1.0f, true);
-    const bf16x2v p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b, 1.0f, false), p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b, 1.0f, true);
-    u32x4_t r;
-    r[0] = __builtin_bit_cast(uint32_t, p0);
-    r[1] = __builtin_bit_cast(uint32_t, p1);
-    r[2] = __builtin_bit_cast(uint32_t, p2);
-    r[3] = __builtin_bit_cast(uint32_t, p3);
-    return __builtin_bit_cast(bf16x8_t, r);
-}
-
-// o-proj prologue: merge the NS split partials of head (cg >> 4) for every batch row, two rows per iteration so the loads
-// of both are in flight together; dst = LDS address of chunk c of row 0
-template <int NS>
-__device__ __forceinline__ void stage_attn_rows(const float* __restrict__ attn_part, unsigned char* dst, int pitch, int B, int Hq, int cg) {
-    const float* pp0 = attn_part + (size_t)(cg >> 4) * NS * PSTRIDE;
-    const size_t row = (size_t)Hq * NS * PSTRIDE;
-    const int d0 = (cg & 15) * 8;
-    int b = 0;
-    for (; b + 1 < B; b += 2) {
-        const u32x4_t v0 = attn_merge_chunk<NS>(pp0 + (size_t)b * row, d0);
-        const u32x4_t v1 = attn_merge_chunk<NS>(pp0 + (size_t)(b + 1) * row, d0);
-        *(u32x4_t*)(dst + (size_t)b * pitch) = v0;
-        *(u32x4_t*)(dst + (size_t)(b + 1) * pitch) = v1;
-    }
-    if (b < B) *(u32x4_t*)(dst + (size_t)b * pitch) = attn_merge_chunk<NS>(pp0 + (size_t)b * row, d0);
-}
-
 // FP8: weights are the fp8 fragment-major copy (1 KiB tile = 16 rows x 64 k), de-quantised to bf16 in registers
 // (exact), per-row scale applied to the fp32 result; activations stay bf16.  A "k-step" is then 64 elements.
 #ifdef DECODE_LAB_TRACE
@@ -116,7 +82,7 @@ __device__ unsigned long long g_dec_trace[256 * 8];   // [block][stamp]: s_memre
 template <int MODE, bool NORM, bool XATTN, bool FP8 = false>
 __global__ __launch_bounds__(GW * 64, 2) void emmax_decode_mfma_kernel(GemvParams p) {
     DEC_STAMP(0);
-    constexpr int TILES = (MODE == MODE_QKV || MODE == MODE_GATEUP) ? 2 : 1;
+    constexpr int TILES = (MODE == GEMV_QKV || MODE == GEMV_GATEUP) ? 2 : 1;
     // k-steps per ring block: 8 KiB of weights in flight per wave (64 KiB per CU, 16 MiB on the chip) is the measured optimum
     // once the ring really rolls -- 16 KiB per wave costs 1-3 us per launch, 32 KiB up to 20 us (the first burst alone is then
     // 64 MB: everything else, the activations of the prologue included, queues behind it)
@@ -185,7 +151,7 @@ __global__ __launch_bounds__(GW * 64, 2) void emmax_decode_mfma_kernel(GemvParam
 
     // tile index (16-row units) of tile tt of task t
     auto tile_of = [&](int t, int tt) {
-        if (MODE == MODE_QKV) {
+        if (MODE == GEMV_QKV) {
             const int halfb = 1 << p.qk_shift;                               // head_dim / 32: 8 tiles per head, 4 low + 4 high
             const int hb = t >> p.qk_shift, db = t & (halfb - 1);
             return hb * 2 * halfb + db + tt * halfb;
@@ -441,23 +407,12 @@ __global__ __launch_bounds__(GW * 64, 2) void emmax_decode_mfma_kernel(GemvParam
     const int ec = tid & 15;   // batch column this thread finalises (tid < 256)
     int pre_pos = 0, pre_pg = 0;
     float pf_a = 0.f, pf_b = 0.f;
-    if (MODE == MODE_QKV && tid < 256 && ec < B) {
-        pre_pos = p.ctx_len[ec];
-        pre_pg = p.page_table[(size_t)ec * p.max_pages + pre_pos / p.page];
-    }
+    if (MODE == GEMV_QKV && tid < 256 && ec < B) qkv_row_pos(p, ec, pre_pos, pre_pg);
     auto prefetch_epilogue = [&](const Seg& cs) {
         if (tid >= 256 || ec >= B || cs.gb != 0) return;   // segments that only publish partial sums have no epilogue
         const int row_in = 4 * ((tid & 63) >> 4) + (tid >> 6);
-        if (MODE == MODE_RESID) {
-            pf_a = p.h32 ? p.h32[(size_t)ec * p.ldh + cs.t * 16 + row_in] : bf2f(((const bf16_t*)p.y)[(size_t)ec * p.ldy + cs.t * 16 + row_in]);
-        } else if (MODE == MODE_QKV) {
-            const int half = p.head_dim >> 1;
-            const int hb = cs.t >> p.qk_shift, d = (cs.t & ((1 << p.qk_shift) - 1)) * 16 + row_in;
-            if (hb < p.Hq + p.Hkv) {
-                pf_a = p.cos_t[(size_t)pre_pos * half + d];
-                pf_b = p.sin_t[(size_t)pre_pos * half + d];
-            }
-        }
+        if (MODE == GEMV_RESID) pf_a = resid_fetch(p, ec, cs.t * 16 + row_in, p.h32 != nullptr);
+        else if (MODE == GEMV_QKV) qkv_rope_fetch(p, pre_pos, cs.t >> p.qk_shift, (cs.t & ((1 << p.qk_shift) - 1)) * 16 + row_in, pf_a, pf_b);
     };
     auto reduce_epilogue = [&](const Seg& cs, const float* rb) {
         const int t = cs.t;
@@ -502,16 +457,16 @@ __global__ __launch_bounds__(GW * 64, 2) void emmax_decode_mfma_kernel(GemvParam
                 for (int tt = 0; tt < TILES; ++tt) v[tt] *= p.wscale[tile_of(t, tt) * 16 + row_in];
             }
             if (finalise && c < B) {
-                if (MODE == MODE_PLAIN) {
+                if (MODE == GEMV_PLAIN) {
                     ((bf16_t*)p.y)[(size_t)c * p.ldy + t * 16 + row_in] = f2bf(v[0]);
-                } else if (MODE == MODE_RESID) {
+                } else if (MODE == GEMV_RESID) {
                     // fp32 residual stream (GemvParams::h32): the master copy + its bf16 mirror (what the NORM modes read)
                     if (p.h32) p.h32[(size_t)c * p.ldh + t * 16 + row_in] = pf_a + v[0];
                     bf16_t* hp = (bf16_t*)p.y + (size_t)c * p.ldy + t * 16 + row_in;
                     *hp = f2bf(pf_a + v[0]);
-                } else if (MODE == MODE_GATEUP) {
-                    ((bf16_t*)p.y)[(size_t)c * p.ldy + t * 16 + row_in] = f2bf(silu(v[0]) * v[TILES - 1]);
-                } else if (MODE == MODE_QKV) {
+                } else if (MODE == GEMV_GATEUP) {
+                    swiglu_finish<false>(p, c, t * 16 + row_in, v[0], v[TILES - 1]);
+                } else if (MODE == GEMV_QKV) {
                     const int hd = p.head_dim, half = hd >> 1;
                     const int hb = t >> p.qk_shift, d = (t & ((1 << p.qk_shift) - 1)) * 16 + row_in;
                     const int pos = pre_pos;
@@ -535,15 +490,8 @@ __global__ __launch_bounds__(GW * 64, 2) void emmax_decode_mfma_kernel(GemvParam
                         vc[d] = f2bf(x0);
                         vc[d + half] = f2bf(x1);
                     }
-                } else if (MODE == MODE_LMHEAD) {
-                    const int row = t * 16 + row_in;
-                    if (row < p.n_rows) {
-                        if (v[0] > best || (v[0] == best && row < besti)) {
-                            best = v[0];
-                            besti = row;
-                        }
-                        if (p.logits_out) p.logits_out[(size_t)c * p.n_rows + row] = v[0];
-                    }
+                } else if (MODE == GEMV_LMHEAD) {
+                    lmhead_row(p, c, t * 16 + row_in, v[0], best, besti);
                 }
             }
         }
@@ -632,7 +580,7 @@ __global__ __launch_bounds__(GW * 64, 2) void emmax_decode_mfma_kernel(GemvParam
     }
     DEC_STAMP(5);
 
-    if (MODE == MODE_LMHEAD) {
+    if (MODE == GEMV_LMHEAD) {
         __syncthreads();                      // the last reduction has read red[]
         float* bv = red;                      // [256]
         int* bi = (int*)(red + 256);          // [256]
@@ -641,21 +589,10 @@ __global__ __launch_bounds__(GW * 64, 2) void emmax_decode_mfma_kernel(GemvParam
             bi[tid] = besti;
         }
         __syncthreads();
-        if (tid < B) {   // the 16 (row slot) entries of batch column tid: l = g*16 + tid, r = 0..3
-            float v0 = -INFINITY;
-            int i0 = 0x7fffffff;
-            for (int g = 0; g < 4; ++g)
-                for (int r = 0; r < 4; ++r) {
-                    const int e = r * 64 + g * 16 + tid;
-                    const float v = bv[e];
-                    const int ii = bi[e];
-                    if (v > v0 || (v == v0 && ii < i0)) {
-                        v0 = v;
-                        i0 = ii;
-                    }
-                }
-            p.part_val[(size_t)blockIdx.x * B + tid] = v0;
-            p.part_idx[(size_t)blockIdx.x * B + tid] = i0;
+        // the 16 (row slot) entries of batch column tid: l = g*16 + tid, r = 0..3
+        if (tid < B) {
+            const auto slot = [&](int k) { return (k & 3) * 64 + (k >> 2) * 16 + tid; };
+            lmhead_col_finish(p, B, tid, bv, bi, 16, slot, -INFINITY, 0x7fffffff);
         }
     }
 }
@@ -682,10 +619,10 @@ static int mfma_kc(int B, int K, int tiles, int kstep) {
 
 template <int MODE, bool NORM, bool XATTN, bool FP8>
 static int launch_mfma_t(GemvParams p, int B, hipStream_t stream, int* grid_out) {
-    constexpr int TILES = (MODE == MODE_QKV || MODE == MODE_GATEUP) ? 2 : 1;
+    constexpr int TILES = (MODE == GEMV_QKV || MODE == GEMV_GATEUP) ? 2 : 1;
     if (FP8 && !p.wscale) return -1;
     if (p.K % (FP8 ? 64 : 32) || p.n_rows % (16 * TILES)) {
-        if (!(MODE == MODE_LMHEAD && p.n_rows % 16 == 0)) return -1;
+        if (!(MODE == GEMV_LMHEAD && p.n_rows % 16 == 0)) return -1;
     }
     p.batch = B;
     p.x_bar = XATTN ? 0 : emmax_tune().mfma_xbar;   // default on for the prologues that load activations ahead of the head
@@ -693,9 +630,9 @@ static int launch_mfma_t(GemvParams p, int B, hipStream_t stream, int* grid_out)
     if (NORM && p.kc != p.K) return -1;
     p.n_groups = p.n_rows / (16 * TILES);
     int grid = min(256, p.n_groups);
-    if (MODE == MODE_LMHEAD) grid = min(grid, p.max_parts);
+    if (MODE == GEMV_LMHEAD) grid = min(grid, p.max_parts);
     if (grid_out) *grid_out = grid;
-    if (MODE == MODE_QKV) {
+    if (MODE == GEMV_QKV) {
         p.qk_shift = 0;
         while ((32 << p.qk_shift) < p.head_dim) ++p.qk_shift;
         if ((32 << p.qk_shift) != p.head_dim) return -1;   // head_dim / 32 must be a power of two
@@ -718,12 +655,12 @@ static int launch_mfma_t(GemvParams p, int B, hipStream_t stream, int* grid_out)
 template <bool FP8>
 static int launch_mfma_mode(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out) {
     switch (mode) {
-        case MODE_QKV: return launch_mfma_t<MODE_QKV, true, false, FP8>(p, B, stream, grid_out);
-        case MODE_RESID:
-            return p.attn_part ? launch_mfma_t<MODE_RESID, false, true, FP8>(p, B, stream, grid_out) : launch_mfma_t<MODE_RESID, false, false, FP8>(p, B, stream, grid_out);
-        case MODE_GATEUP: return launch_mfma_t<MODE_GATEUP, true, false, FP8>(p, B, stream, grid_out);
-        case MODE_LMHEAD: return launch_mfma_t<MODE_LMHEAD, true, false, FP8>(p, B, stream, grid_out);
-        case MODE_PLAIN: return launch_mfma_t<MODE_PLAIN, false, false, FP8>(p, B, stream, grid_out);
+        case GEMV_QKV: return launch_mfma_t<GEMV_QKV, true, false, FP8>(p, B, stream, grid_out);
+        case GEMV_RESID:
+            return p.attn_part ? launch_mfma_t<GEMV_RESID, false, true, FP8>(p, B, stream, grid_out) : launch_mfma_t<GEMV_RESID, false, false, FP8>(p, B, stream, grid_out);
+        case GEMV_GATEUP: return launch_mfma_t<GEMV_GATEUP, true, false, FP8>(p, B, stream, grid_out);
+        case GEMV_LMHEAD: return launch_mfma_t<GEMV_LMHEAD, true, false, FP8>(p, B, stream, grid_out);
+        case GEMV_PLAIN: return launch_mfma_t<GEMV_PLAIN, false, false, FP8>(p, B, stream, grid_out);
         default: return -1;
     }
 }
@@ -748,8 +685,8 @@ int decode_mfma_init() {
 #define SET(M, N_, X)                                                                                                          \
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)emmax_decode_mfma_kernel<M, N_, X, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim); \
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)emmax_decode_mfma_kernel<M, N_, X, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)
-    SET(MODE_QKV, true, false); SET(MODE_RESID, false, true); SET(MODE_RESID, false, false); SET(MODE_GATEUP, true, false);
-    SET(MODE_LMHEAD, true, false); SET(MODE_PLAIN, false, false);
+    SET(GEMV_QKV, true, false); SET(GEMV_RESID, false, true); SET(GEMV_RESID, false, false); SET(GEMV_GATEUP, true, false);
+    SET(GEMV_LMHEAD, true, false); SET(GEMV_PLAIN, false, false);
 #undef SET
     done = (e == hipSuccess) ? 0 : -4;
     return done;

@@ -249,23 +249,7 @@ struct GemvParams {
     long long kv24;         // exact numerics: > 0 = the K / V caches are 24-bit (common.h: x24) -- kcache / vcache point at the bf16 plane of kv24 elements,
                             //   the 8-bit extension plane follows it; 0 = fp32 rows
 };
-// where the QKV epilogues put element block (head hk, K or V) of batch row b: the paged bf16 cache, or the staging rows of the fp8 KV cache
-__device__ __forceinline__ bf16_t* gemv_kv_row(const GemvParams& p, bool is_v, int b, int pg, int pos, int hk) {
-    if (p.kv_stage) return (bf16_t*)p.kv_stage + (((size_t)b * p.Hkv + hk) * 2 + (is_v ? 1 : 0)) * p.head_dim;
-    return (bf16_t*)(is_v ? p.vcache : p.kcache) + (((size_t)pg * p.Hkv + hk) * p.page + pos % p.page) * p.head_dim;
-}
-// exact numerics: element d of the (page, kv head, position) row of the fp32 / 24-bit paged cache
-__device__ __forceinline__ void gemv_kv_store_x(const GemvParams& p, bool is_v, int pg, int pos, int hk, int d, float v) {
-    const size_t idx = (((size_t)pg * p.Hkv + hk) * p.page + pos % p.page) * p.head_dim + d;
-    void* base = is_v ? p.vcache : p.kcache;
-    if (p.kv24 > 0) {
-        const uint32_t u = x24_bits(v);
-        ((bf16_t*)base)[idx] = (bf16_t)(u >> 16);
-        ((uint8_t*)base + (size_t)p.kv24 * 2)[idx] = (uint8_t)(u >> 8);
-    } else {
-        ((float*)base)[idx] = v;
-    }
-}
+// (where the QKV epilogues put the new K / V rows: gemv_kv_row / gemv_kv_store_x, decode_epilogue.h -- device code, this is also a host header)
 // staged_out (optional): 1 when decode.hip's own LDS-staged kernel served the call, 0 when decode_ks.hip took it
 int launch_decode_gemv(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out = nullptr, int* staged_out = nullptr);
 // decode_ks.hip: the batch 1-2 bf16 projections with K split across the waves of a block (activation slice in registers, no

@@ -16,8 +16,8 @@ int main(int argc, char** argv) {
     const int B = argc > 1 ? atoi(argv[1]) : 1;
     const bool fp8 = argc > 2 && !strcmp(argv[2], "fp8");   // the e4m3 row copy (half the bytes), batch 1-2
     struct Shape { const char* name; int mode, N, K; };
-    const Shape shapes[] = {{"gate/up (norm, SwiGLU)", MODE_GATEUP, 22016, 4096}, {"down (+residual)", MODE_RESID, 4096, 11008}, {"plain 4096 x 4096", MODE_PLAIN, 4096, 4096},
-                            {"plain 12288 x 4096", MODE_PLAIN, 12288, 4096}};
+    const Shape shapes[] = {{"gate/up (norm, SwiGLU)", GEMV_GATEUP, 22016, 4096}, {"down (+residual)", GEMV_RESID, 4096, 11008}, {"plain 4096 x 4096", GEMV_PLAIN, 4096, 4096},
+                            {"plain 12288 x 4096", GEMV_PLAIN, 12288, 4096}};
     if (decode_gemv_init() != 0) { printf("init failed\n"); return 1; }
     for (const Shape& s : shapes) {
         const size_t nw = (size_t)s.N * s.K, wb = fp8 ? 1 : 2;
@@ -37,7 +37,7 @@ int main(int argc, char** argv) {
             for (int i = 0; i < NBUF; ++i) {
                 GemvParams p;
                 memset(&p, 0, sizeof(p));
-                p.x = x; p.ldx = s.K; p.W = W[i]; p.ldw = s.K; p.K = s.K; p.y = y; p.ldy = s.mode == MODE_GATEUP ? s.N / 2 : s.N; p.n_rows = s.N;
+                p.x = x; p.ldx = s.K; p.W = W[i]; p.ldw = s.K; p.K = s.K; p.y = y; p.ldy = s.mode == GEMV_GATEUP ? s.N / 2 : s.N; p.n_rows = s.N;
                 p.norm_w = nwp; p.eps = 1e-5f;
                 if (fp8) p.wscale = (const float*)wsc;
                 if (launch_decode_gemv(s.mode, p, B, 0, &grid) != 0) { printf("launch failed\n"); return 1; }
