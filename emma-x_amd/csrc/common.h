@@ -212,53 +212,6 @@ __device__ __forceinline__ bf16x8_t fp8x8_to_bf16x8(uint32_t lo, uint32_t hi) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Activation accesses with a block-uniform `coh` switch: plain under ordinary stream ordering; agent-scope (sc1: past the
-// XCD-private L2) where a kernel reads what ANOTHER block of the same launch wrote (the in-attention split merge, decode.hip).
-// ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u32x4_t ld_act16(const u32x4_t* p, bool coh) {
-    if (!coh) return *p;
-    const unsigned long long* q = (const unsigned long long*)p;
-    const unsigned long long a = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long b = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return (u32x4_t){(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32)};
-}
-__device__ __forceinline__ void st_act16(u32x4_t* p, u32x4_t v, bool coh) {
-    if (!coh) { *p = v; return; }
-    unsigned long long* q = (unsigned long long*)p;
-    __hip_atomic_store(q, (unsigned long long)v[0] | ((unsigned long long)v[1] << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(q + 1, (unsigned long long)v[2] | ((unsigned long long)v[3] << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ bf16_t ld_act_bf16(const bf16_t* p, bool coh) {
-    return coh ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
-}
-__device__ __forceinline__ void st_act_bf16(bf16_t* p, bf16_t v, bool coh) {
-    if (coh) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else *p = v;
-}
-__device__ __forceinline__ float ld_act_f32(const float* p, bool coh) {
-    return coh ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
-}
-__device__ __forceinline__ void st_act_f32(float* p, float v, bool coh) {
-    if (coh) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else *p = v;
-}
-__device__ __forceinline__ int ld_act_i32(const int* p, bool coh) {
-    return coh ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
-}
-__device__ __forceinline__ void st_act_i32(int* p, int v, bool coh) {
-    if (coh) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else *p = v;
-}
-__device__ __forceinline__ f32x4_t ld_act_f32x4(const float* p, bool coh) {
-    if (!coh) return *(const f32x4_t*)p;
-    const u32x4_t v = ld_act16((const u32x4_t*)p, true);
-    return __builtin_bit_cast(f32x4_t, v);
-}
-
-// 16-byte write-through (agent-scope, sc1) store: acknowledged once it is past the XCD-private L2.  Compiler-visible (the data
-// registers are read before the statement ends: the trailing s_nop, cdna_hip_programming.md section 5.7 item 1).
-__device__ __forceinline__ void st_sc1_f32x4(float* p, f32x4_t v) {
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
 // Split-KV attention partials: per (row, head, split) EMMAX_PSTRIDE floats = { o[0..128) un-normalised, m, l, 2 pad }.
 // attn_merge_chunk merges the NS partials of one head for the 8 output elements d0..d0+8 and returns them as 8 bf16.
 // Branch-free with every load issued before the first use (one L2 round trip for the scalars, one for the vectors):
@@ -288,8 +241,8 @@ __device__ __forceinline__ u32x4_t attn_merge_chunk(const float* __restrict__ pp
         }
 #pragma unroll
         for (int s = 0; s < GS; ++s) {
-            // explicit fma: the two merge variants (this one and the loop below) must round identically -- the chained launch
-            // uses the loop, the plain launch this one, and their logits are compared bit for bit
+            // explicit fma: the two merge variants (this one and the loop below) must round identically -- a kernel takes this one
+            // for its first chunk and the loop for the rest, and tools/merge_test.hip compares them bit for bit
             const float wgt = (ms[s0 + s] == -INFINITY) ? 0.f : __expf(ms[s0 + s] - M);
             den = __builtin_fmaf(dn[s0 + s], wgt, den);
 #pragma unroll
@@ -311,16 +264,16 @@ __device__ __forceinline__ u32x4_t attn_merge_chunk(const float* __restrict__ pp
 }
 // generic split count, small register footprint (the dot2 GEMV keeps its 16-load weight ring live across the prologue
 // and must stay under 128 VGPRs)
-__device__ __forceinline__ u32x4_t attn_merge_chunk_loop(const float* __restrict__ pp, int d0, int nsplit, bool coh = false, float* out32 = nullptr) {
+__device__ __forceinline__ u32x4_t attn_merge_chunk_loop(const float* __restrict__ pp, int d0, int nsplit, float* out32 = nullptr) {
     float M = -INFINITY;
-    for (int s = 0; s < nsplit; ++s) M = fmaxf(M, ld_act_f32(pp + s * EMMAX_PSTRIDE + 128, coh));
+    for (int s = 0; s < nsplit; ++s) M = fmaxf(M, pp[s * EMMAX_PSTRIDE + 128]);
     float den = 0.f, a8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int s = 0; s < nsplit; ++s) {
-        const float m = ld_act_f32(pp + s * EMMAX_PSTRIDE + 128, coh);
+        const float m = pp[s * EMMAX_PSTRIDE + 128];
         const float wgt = (m == -INFINITY) ? 0.f : __expf(m - M);
-        den = __builtin_fmaf(ld_act_f32(pp + s * EMMAX_PSTRIDE + 129, coh), wgt, den);
-        const f32x4_t o0 = ld_act_f32x4(pp + s * EMMAX_PSTRIDE + d0, coh);
-        const f32x4_t o1 = ld_act_f32x4(pp + s * EMMAX_PSTRIDE + d0 + 4, coh);
+        den = __builtin_fmaf(pp[s * EMMAX_PSTRIDE + 129], wgt, den);
+        const f32x4_t o0 = *(const f32x4_t*)(pp + s * EMMAX_PSTRIDE + d0);
+        const f32x4_t o1 = *(const f32x4_t*)(pp + s * EMMAX_PSTRIDE + d0 + 4);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {   // explicit fma: see attn_merge_chunk
             a8[j] = __builtin_fmaf(o0[j], wgt, a8[j]);

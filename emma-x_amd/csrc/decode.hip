@@ -1,20 +1,22 @@
-// decode.hip -- the autoregressive decode step (HBM-bound): one token per sequence, batch B <= 8.
-// Replaces HF `LlamaDecoderLayer` at q_len == 1 + one greedy step of `GenerationMixin.generate`
+// decode.hip -- the LDS-staged dot-product GEMV of the autoregressive decode step (HBM-bound, one token per sequence) and the step's small
+// kernels.  Replaces the projections of HF `LlamaDecoderLayer` at q_len == 1 + one greedy step of `GenerationMixin.generate`
 // (cached branch of prismatic/extern/hf/modeling_prismatic.py:325-341; loop invoked at :519 and
 // prismatic/models/vlms/prismatic.py:659-663).
 //
-// Every projection is a weight-streaming GEMV: weights bf16 [N,K] row-major are read exactly once with 16-byte
-// non-temporal loads, many loads in flight per lane, straight to VGPRs (no LDS round trip for data that is not
-// shared); the B activation vectors are staged once per block in LDS (bf16) and read back with broadcast-free
-// ds_read_b128; products go through v_dot2c_f32_bf16 with fp32 accumulation; rows are reduced across the wave.
+// The staged GEMV: weights bf16 [N,K] row-major (or the e4m3 row copy of emmax_quant_rm8_kernel) are read exactly once with 16-byte
+// non-temporal loads, many loads in flight per lane, straight to VGPRs (no LDS round trip for data that is not shared); the B
+// activation vectors are staged once per block in LDS (bf16) and read back with broadcast-free ds_read_b128; products go through
+// v_dot2c_f32_bf16 with fp32 accumulation; rows are reduced across the wave.
 // Fusions (no activation round trip through HBM beyond one bf16 vector per stage):
 //   qkv    : RMSNorm prologue  -> GEMV -> RoPE (rotate-half) -> q buffer / paged K,V cache append
-//   oproj  : GEMV -> + residual (in place)
+//   oproj  : merge of the attention split partials -> GEMV -> + residual (in place)
 //   gateup : RMSNorm prologue  -> GEMV over 16-row interleaved (gate,up) -> SiLU(gate)*up
 //   down   : GEMV -> + residual (in place)
 //   lmhead : final RMSNorm prologue -> GEMV -> per-block greedy argmax (logits never reach HBM)
-// Attention: split-KV over the paged cache (16 lanes per key row, 4 keys per wave load), fp32 two-pass softmax inside
-// a split, log-sum-exp merge of the splits in a tiny combine kernel.
+// It serves the fused modes at batch 1-2 (bf16 shapes decode_ks.hip does not take, the tuning switch ks = 0, the fp8 rows) and plain rows
+// up to batch 8 (emmax_op_gemv).  The other projection families: decode_ks.hip (batch 1-2, K-split), decode_km.hip / decode_kmp.hip and
+// decode_mfma.hip (MFMA, batch >= 3 and fp8); their shared epilogues: decode_epilogue.h; the decode attention: decode_attn.hip.
+// Also here: the e4m3 row quantiser, the embedding gather, the greedy finish of a step and emmax_set_tokens_kernel.
 // All step-varying state (positions, current tokens, done flags) is read from device memory -> hipGraph-capturable.
 #include <cstdlib>
 #include <type_traits>
@@ -24,8 +26,6 @@
 #include "decode_epilogue.h"
 
 namespace {
-
-constexpr int PSTRIDE = EMMAX_PSTRIDE;   // floats per attention split partial: 128 o + m + l + 2 pad (16-byte aligned rows)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // GEMV.  Persistent blocks of 512 threads = 8 waves; block b owns a contiguous range of row GROUPS, its waves interleave
@@ -213,29 +213,25 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
         }
         advance(P);
     };
-    constexpr bool coh = false;   // activations move with plain accesses (stream ordering)
     const bool one_pass = NORM && !XATTN && !multi_phase && (K >> 3) <= NT;
     // x first pays for the qkv projection only (-0.9 us); gate/up and lm-head lose 1.5 us with it, the plain rows of the down
-    // projection gain nothing.  The chained launch waits for its producer first, so there the stream always goes out ahead.
+    // projection gain nothing.
     // The o-proj prologue (XATTN: merge of the attention split partials) also goes first: with every load of a chunk's merge
     // requested up front (branch-free, split count as a template argument -- only affordable while the weight block is not
     // occupying 64 registers) it is one round trip of ~1 us; as a loop BEHIND the weight stream it was sixteen dependent
     // round trips, ~5 of the 11 us of the launch.
-    // plain rows (down projection) that fit one round of four chunks per thread: activations first, see stage_x
-    // (round 3: off -- the four-chunk burst next to the 64-register weight head spilled 44-84 registers at the 128-VGPR cap of
-    // two blocks per CU, i.e. the wave stored its own weight head to scratch right after requesting it; the down projection this
-    // was built for runs on decode_ks.hip now, this kernel only keeps shapes with K % 64 != 0 and the fp8 rows)
-    const bool plain_first = false;
+    // (Tried and removed: plain rows staged first as one four-chunk burst per thread -- next to the 64-register weight head it
+    // spilled 44-84 registers at the 128-VGPR cap of two blocks per CU.)
     // fp8: every one-pass prologue goes first -- the first burst is most of the matrix, the refills cannot go out before x is
     // staged, and x requested behind the burst arrived 7 us into a 19 us gate/up launch (tools/gemv_lab.hip)
-    const bool head_first = !((one_pass && (MODE == GEMV_QKV || FP8)) || XATTN || plain_first);
+    const bool head_first = !((one_pass && (MODE == GEMV_QKV || FP8)) || XATTN);
     if (head_first) issue_head(false);
 
     // chunk c (8 elements) of activation row b of a NORM mode: from the fp32 residual stream when the step keeps one (GemvParams::h32;
     // rounded to bf16 here, once per read -- decode_ks.hip, the product path at these batches, keeps statistics and x g in fp32)
     auto ld_x8 = [&](int b, int c) -> u32x4_t {
         if (p.h32) return f32x8_to_bf16(ld_f32x8(p.h32 + (size_t)b * p.ldh + (size_t)c * 8));
-        return ld_act16((const u32x4_t*)((const bf16_t*)p.x + (size_t)b * p.ldx) + c, coh);
+        return *((const u32x4_t*)((const bf16_t*)p.x + (size_t)b * p.ldx) + c);
     };
     // ---- RMSNorm statistics ----
     float rstd[B];
@@ -315,28 +311,6 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
     // stage x[:, kc0 : kc0 + 8*nch] into LDS (normalised if NORM, merged from the attention partials if XATTN)
     auto stage_x = [&](int kc0, int nch, auto first_tag) {
         constexpr bool FIRST = decltype(first_tag)::value;   // the call in front of the main loop (no weight block live yet)
-        if (!XATTN && !NORM && FIRST && plain_first) {
-            // plain rows in front of the main loop (down projection: 22 KB per row): every chunk of a thread requested at once,
-            // UNCONDITIONALLY (clamped index, masked at the store), and the weight head right behind them -- the wait for the
-            // activations is then a counted one.  (Behind the head, with predicated loads, hipcc waited for vmcnt(0): phase
-            // stamps showed the prologue of a down launch ending 6 us in, when each wave's whole 16 KiB head had landed.)
-            u32x4_t v[B][4];
-#pragma unroll
-            for (int b = 0; b < B; ++b) {
-                const u32x4_t* xr = (const u32x4_t*)((const bf16_t*)p.x + (size_t)b * p.ldx + kc0);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[b][j] = ld_act16(xr + min(tid + j * NT, nch - 1), coh);
-            }
-            issue_head(true);
-#pragma unroll
-            for (int b = 0; b < B; ++b) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (tid + j * NT < nch) xs[b * XS + tid + j * NT] = v[b][j];
-                if (tid == NT - 1) xs[b * XS + nch] = (u32x4_t){0u, 0u, 0u, 0u};
-            }
-            return;
-        }
         if (!XATTN && !NORM) {
             // plain rows (down projection: 22 KB per row): four loads in flight per thread, then the LDS writes
 #pragma unroll
@@ -345,7 +319,7 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
                 for (int c0 = tid; c0 < nch; c0 += 4 * NT) {
                     u32x4_t v[4];
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = (c0 + j * NT < nch) ? ld_act16(xr + c0 + j * NT, coh) : (u32x4_t){0u, 0u, 0u, 0u};
+                    for (int j = 0; j < 4; ++j) v[j] = (c0 + j * NT < nch) ? *(xr + c0 + j * NT) : (u32x4_t){0u, 0u, 0u, 0u};
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
                         if (c0 + j * NT < nch) xs[b * XS + c0 + j * NT] = v[j];
@@ -360,7 +334,7 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
             // requested right behind it; any further chunk (K > 4096) takes the low-register loop.
             auto merge_at = [&](int c, int b, bool fast) {
                 const int cg = (kc0 >> 3) + c;
-                const float* pp = p.attn_part + (size_t)(b * p.Hq + (cg >> 4)) * p.nsplit * PSTRIDE;
+                const float* pp = p.attn_part + (size_t)(b * p.Hq + (cg >> 4)) * p.nsplit * EMMAX_PSTRIDE;
                 const int d0 = (cg & 15) * 8;
                 // 8 splits is what decode_attn_nsplit gives at batch 1-2 for every head count up to 32
                 return (fast && p.nsplit == 8) ? attn_merge_chunk<8, 4>(pp, d0) : attn_merge_chunk_loop(pp, d0, p.nsplit);
@@ -386,15 +360,7 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
         for (int b = 0; b < B; ++b) {
             const u32x4_t* xr = (const u32x4_t*)((const bf16_t*)p.x + (size_t)b * p.ldx + kc0);
             for (int c = tid; c < nch; c += NT) {
-                u32x4_t v;
-                if (XATTN) {
-                    // chunk cg = head (cg>>4), elements (cg&15)*8..+8 of the split partials
-                    const int cg = (kc0 >> 3) + c;
-                    const float* pp = p.attn_part + (size_t)(b * p.Hq + (cg >> 4)) * p.nsplit * PSTRIDE;
-                    v = attn_merge_chunk_loop(pp, (cg & 15) * 8, p.nsplit, coh);
-                } else {
-                    v = NORM ? ld_x8(b, (kc0 >> 3) + c) : ld_act16(xr + c, coh);
-                }
+                u32x4_t v = NORM ? ld_x8(b, (kc0 >> 3) + c) : xr[c];
                 if (NORM) {
                     const u32x4_t wv = *((const u32x4_t*)((const bf16_t*)p.norm_w + kc0) + c);
 #pragma unroll
@@ -461,8 +427,8 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
             if (MODE == GEMV_RESID) {
                 int r0, r1;
                 pair_rows(pg, r0, r1);
-                pre_a[i] = resid_fetch(p, eb, r0, p.h32 != nullptr, coh);
-                pre_b[i] = resid_fetch(p, eb, r1, p.h32 != nullptr, coh);
+                pre_a[i] = resid_fetch(p, eb, r0, p.h32 != nullptr);
+                pre_b[i] = resid_fetch(p, eb, r1, p.h32 != nullptr);
             } else if (MODE == GEMV_QKV) {
                 const int half = p.head_dim >> 1, hb = pg / half;
                 qkv_rope_fetch(p, pre_pos, hb, pg - hb * half, pre_a[i], pre_b[i]);
@@ -580,9 +546,13 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
         if (MODE == GEMV_PLAIN) {
 #pragma unroll
             for (int b = 0; b < B; ++b)
-                if (lane == b) {
-                    st_act_bf16((bf16_t*)p.y + (size_t)b * p.ldy + r0, f2bf(red0[b]), coh);
-                    if (2 * pg + 1 < p.n_rows) st_act_bf16((bf16_t*)p.y + (size_t)b * p.ldy + r1, f2bf(red1[b]), coh);
+                if (lane == b) {   // (here and below: a store's address is formed before its value -- the order decides hipcc's schedule)
+                    bf16_t* y0 = (bf16_t*)p.y + (size_t)b * p.ldy + r0;
+                    *y0 = f2bf(red0[b]);
+                    if (2 * pg + 1 < p.n_rows) {
+                        bf16_t* y1 = (bf16_t*)p.y + (size_t)b * p.ldy + r1;
+                        *y1 = f2bf(red1[b]);
+                    }
                 }
         } else if (MODE == GEMV_RESID) {
 #pragma unroll
@@ -594,13 +564,17 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
                         if (2 * pg + 1 < p.n_rows) hq[r1] = pre_b[i] + red1[b];
                     }
                     bf16_t* hp = (bf16_t*)p.y + (size_t)b * p.ldy;
-                    st_act_bf16(hp + r0, f2bf(pre_a[i] + red0[b]), coh);
-                    if (2 * pg + 1 < p.n_rows) st_act_bf16(hp + r1, f2bf(pre_b[i] + red1[b]), coh);
+                    bf16_t* h0 = hp + r0;
+                    *h0 = f2bf(pre_a[i] + red0[b]);
+                    if (2 * pg + 1 < p.n_rows) {
+                        bf16_t* h1 = hp + r1;
+                        *h1 = f2bf(pre_b[i] + red1[b]);
+                    }
                 }
         } else if (MODE == GEMV_GATEUP) {
 #pragma unroll
             for (int b = 0; b < B; ++b)
-                if (lane == b) swiglu_finish<false>(p, b, pg, red0[b], red1[b], coh);
+                if (lane == b) swiglu_finish<false>(p, b, pg, red0[b], red1[b]);
         } else if (MODE == GEMV_QKV) {
             const int hd = p.head_dim, half = hd >> 1;
             const int hb = pg / half, d = pg - hb * half;
@@ -615,19 +589,21 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
                         const bf16_t y0 = f2bf(x0 * cs - x1 * sn), y1 = f2bf(x1 * cs + x0 * sn);
                         if (hb < p.Hq) {
                             bf16_t* q = (bf16_t*)p.y + (size_t)b * p.ldy + hb * hd;
-                            st_act_bf16(q + d, y0, coh);
-                            st_act_bf16(q + d + half, y1, coh);
+                            q[d] = y0;
+                            *(q + d + half) = y1;
                         } else {
                             const int pgid = pre_pg;
                             bf16_t* kc = gemv_kv_row(p, false, b, pgid, pos, hb - p.Hq);
-                            st_act_bf16(kc + d, y0, coh);
-                            st_act_bf16(kc + d + half, y1, coh);
+                            kc[d] = y0;
+                            *(kc + d + half) = y1;
                         }
                     } else {
                         const int pgid = pre_pg;
                         bf16_t* vc = gemv_kv_row(p, true, b, pgid, pos, hb - p.Hq - p.Hkv);
-                        st_act_bf16(vc + d, f2bf(x0), coh);
-                        st_act_bf16(vc + d + half, f2bf(x1), coh);
+                        bf16_t* v0 = vc + d;
+                        *v0 = f2bf(x0);
+                        bf16_t* v1 = vc + d + half;
+                        *v1 = f2bf(x1);
                     }
                 }
         } else if (MODE == GEMV_LMHEAD) {
@@ -662,7 +638,7 @@ __global__ __launch_bounds__(GW * 64, (B <= 2 && F8 != 1 && F8 != 2 ? 4 : 2)) vo
         // thread b: the eight waves' candidates of batch row b, starting from wave 0's
         if (tid < B) {
             const auto slot = [&](int k) { return (k + 1) * B + tid; };
-            lmhead_col_finish(p, B, tid, &bv[0][0], &bi[0][0], GW - 1, slot, bv[0][tid], bi[0][tid], coh);
+            lmhead_col_finish(p, B, tid, &bv[0][0], &bi[0][0], GW - 1, slot, bv[0][tid], bi[0][tid]);
         }
     }
 }
@@ -677,7 +653,6 @@ __global__ __launch_bounds__(256) void emmax_decode_embed_kernel(const int32_t* 
     id = min(max(id, 0), vocab - 1);
     const u32x4_t* s = (const u32x4_t*)(E + (size_t)id * hidden);
     u32x4_t* o = (u32x4_t*)(h + (size_t)b * hidden);
-    constexpr bool coh = false;
     if (h32) {   // fp32 residual stream: the embedding row widened (exact), beside the bf16 row
         for (int c = threadIdx.x; c < hidden / 8; c += blockDim.x) {
             const f32x8_t f = bf16x8_to_f32(s[c]);
@@ -686,295 +661,7 @@ __global__ __launch_bounds__(256) void emmax_decode_embed_kernel(const int32_t* 
             *(f32x4_t*)(hp + 4) = f.hi;
         }
     }
-    for (int c = threadIdx.x; c < hidden / 8; c += blockDim.x) st_act16(o + c, s[c], coh);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Split-KV decode attention over the paged cache.  grid (NSPLIT, Hkv, B), 256 threads.
-// A 16-lane group owns one key at a time (lane = 16-byte chunk of the 128-wide row; 4 keys per wave load instruction,
-// fully coalesced) and keeps its own online-softmax state (m, l, o[8 per lane]); K and V of a whole chunk of keys are
-// requested before the first score is computed, so 2*KU 16-byte loads per lane are in flight.  The 16 group states of
-// the block are merged through shuffles + LDS, and the block writes one partial per (row, head, split):
-//   part[((b*Hq + h)*nsplit + s) * PSTRIDE] = { o[0..HD) un-normalised, m, l, pad }
-// The cross-split merge is fused into the staging prologue of the o-proj GEMV (XATTN).
-// ---------------------------------------------------------------------------------------------------------------------
-// DIRECT (one KV split per (row, head): batch >= 5 at 32 heads): nothing to merge -- the block holds the head's whole result,
-// normalises it and writes the bf16 row the o-proj reads (the arithmetic of a one-split merge), no partials, no o-proj prologue.
-// (Round 3 also measured a cross-split merge INSIDE this launch for 2-8 splits -- sc1 partials, arrival counter, last arriver
-// merges: 12.6 against 5.7 us per launch at B = 1; removed from the product source in round 4)
-// KV8 (round 5, opt-in fp8 KV cache): K / V pages hold e4m3 rows with one fp32 scale per (token, head) row -- 8 bytes per lane and key
-// instead of 16, de-quantised in registers (v_cvt_scalef32_pk_bf16_fp8 with the row's scale) right before the dot products.  The key the
-// qkv launch of THIS step produced (position L - 1) waits as bf16 in p.kv_stage: every block quantises it itself (so that this step sees
-// the values every later step will read back) and split 0 appends bytes + scale to the cache.
-// DEEP: four chunks of keys in flight per wave instead of two (always with KV8; bf16: tuning switch attn_deep)
-template <int HD, int G, bool DIRECT = false, int NW = 4, bool KV8 = false, bool DEEP = KV8>
-__global__ __launch_bounds__(NW * 64) void emmax_decode_attn_kernel(DecodeAttnParams p) {
-    // waves per block: 4 (8-wave blocks were measured no faster at batch 1-2, where 512 four-wave blocks already put 8 waves on a CU,
-    // DESIGN.md section 6); the one-split form of batch 5-8 is 256 blocks = ONE per CU: NW = 8 there (tuning switch attn_nw, round 5)
-    constexpr int NT = NW * 64;
-    static_assert(HD == 128, "decode attention maps 16 lanes x 8 elements onto one 128-wide K/V row");
-    constexpr int KU = G <= 2 ? 4 : 2;    // keys per lane group per chunk (block chunk = 16 * KU keys), two chunks in flight
-    constexpr int SP = 512;  // page ids kept in LDS = the longest page table the launcher accepts (32 K tokens at 64 per page)
-    __shared__ int s_pages[SP];
-    __shared__ float red_o[NW][G][HD];
-    __shared__ float red_ml[NW][G][2];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int kg = lane >> 4, ch = lane & 15;       // key group within the wave, 16-byte chunk within the row
-    const int split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
-    const int nsplit = gridDim.x;
-    constexpr bool coh = false;   // activations move with plain accesses (stream ordering)
-    // ONE memory round trip for everything in front of the K/V loads: the context length and the done flag (scalar loads,
-    // requested first), the row's whole page table (<= SP entries, two per thread, kept in registers until all requests are
-    // out, then written to LDS) and q.  (A loop that waited for each table load, then a dependent scalar load for the length,
-    // then another for the flag cost three extra round trips -- half of this 7 us kernel.)
-    const int ctx_now = p.ctx_len[b];
-    const int done_word = *(p.done ? p.done + b : p.ctx_len + b);   // always a load, never a branch with its own wait in front of
-    const int row_done = p.done ? done_word : 0;                  // the q / page-table requests
-    const int32_t* ptab = p.page_table + (size_t)b * p.max_pages;
-    // q (already rotated, bf16) for the G heads of this kv head: lane holds elements ch*8 .. +8
-    u32x4_t q[G];
-#pragma unroll
-    for (int gq = 0; gq < G; ++gq)
-        q[gq] = ld_act16((const u32x4_t*)((const bf16_t*)p.q + (size_t)b * p.ldq + (hk * G + gq) * HD + ch * 8), coh);
-    const int pt0 = ptab[min(tid, p.max_pages - 1)], pt1 = ptab[min(tid + NT, p.max_pages - 1)];
-    __builtin_amdgcn_sched_barrier(0);   // every request above is out before the first wait (hipcc sinks the q load below the LDS write otherwise)
-    s_pages[tid] = pt0;
-    if (NT < SP) s_pages[tid + NT] = pt1;
-    const int L = ctx_now + 1;                      // keys including the one appended by the qkv kernel of this step
-    int kps = (L + nsplit - 1) >> __builtin_ctz(nsplit);   // the split count is a power of two (launcher)
-    kps = (kps + 15) & ~15;
-    const int k0 = split * kps;
-    const int k1 = min(L, k0 + kps);
-    const int Hq = p.Hkv * G;
-    float* part = p.part + ((size_t)(b * Hq + hk * G) * nsplit + split) * PSTRIDE;
-
-    if (k0 >= L || row_done) {   // empty split, or a row that no longer decodes: no K/V traffic
-        if constexpr (DIRECT) {   // a row that no longer decodes: zeros (what the merge of an empty partial gives)
-            for (int i = tid; i < G * (HD / 8); i += NT)
-                *((u32x4_t*)((bf16_t*)p.o_out + (size_t)b * p.ldq + hk * G * HD) + i) = (u32x4_t){0u, 0u, 0u, 0u};
-            return;
-        }
-        for (int i = tid; i < G * PSTRIDE; i += NT) {
-            const int gq = i / PSTRIDE, j = i - gq * PSTRIDE;
-            st_act_f32(part + (size_t)gq * nsplit * PSTRIDE + j, (j == HD) ? -INFINITY : 0.f, coh);
-        }
-        return;
-    }
-
-    const bf16_t* kc = (const bf16_t*)p.kcache;
-    const bf16_t* vc = (const bf16_t*)p.vcache;
-    const uint8_t* kc8 = (const uint8_t*)p.kcache;
-    const uint8_t* vc8 = (const uint8_t*)p.vcache;
-    // KV8: the step's new K / V row of this kv head, requested now (one round trip with the page table), quantised below
-    u32x4_t new_k = {0u, 0u, 0u, 0u}, new_v = {0u, 0u, 0u, 0u};
-    if constexpr (KV8) {
-        const bf16_t* st = (const bf16_t*)p.kv_stage + ((size_t)b * p.Hkv + hk) * 2 * HD + ch * 8;
-        new_k = *(const u32x4_t*)st;
-        new_v = *(const u32x4_t*)(st + HD);
-    }
-
-    __syncthreads();
-    if constexpr (KV8) {
-        // one scale per row (e4m3_row_scale of the amax) over the 16 lanes of a key group (every group of every wave holds the same row)
-        auto requant = [&](u32x4_t& v, uint8_t* cache, float* scales) {
-            float am = 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) am = fmaxf(am, fmaxf(fabsf(bf_lo(v[j])), fabsf(bf_hi(v[j]))));
-            am = row16_max(am);
-            const float sc = e4m3_row_scale(am);
-            const u32x2_t q8 = quant8_e4m3(v, 1.0f / sc);
-            v = dequant8_e4m3(q8, sc);
-            if (split == 0 && tid < 16) {   // append: bytes + scale at position L - 1
-                const int pos = L - 1, pg = s_pages[pos >> p.page_shift];
-                const size_t rowi = (((size_t)pg * p.Hkv + hk) << p.page_shift) + (pos & (p.page - 1));
-                *(u32x2_t*)(cache + rowi * HD + ch * 8) = q8;
-                if (tid == 0) scales[rowi] = sc;
-            }
-        };
-        requant(new_k, (uint8_t*)p.kcache, p.kscale);
-        requant(new_v, (uint8_t*)p.vcache, p.vscale);
-    }
-
-    float m[G], l[G], o[G][8];
-#pragma unroll
-    for (int gq = 0; gq < G; ++gq) {
-        m[gq] = -INFINITY;
-        l[gq] = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[gq][j] = 0.f;
-    }
-
-    // software pipeline: two register chunk buffers; the loads of chunk i+1 are issued before the scores of chunk i are
-    // computed, so every wave has K/V requests in flight at all times (a 1/8 split of a 1K context is two chunks: both
-    // are requested up front)
-    // KV8: kv / vv carry the raw bytes in [0..1] and the row's scale in [2] until consume_chunk de-quantises them
-    auto load_chunk = [&](int kb, u32x4_t (&kv)[KU], u32x4_t (&vv)[KU], bool (&ok)[KU]) {
-#pragma unroll
-        for (int u = 0; u < KU; ++u) {
-            const int key = kb + u * (4 * NW) + wave * 4 + kg;
-            ok[u] = key < k1;
-            const int kk = ok[u] ? key : k0;
-            if constexpr (KV8) {
-                const int pg8 = s_pages[kk >> p.page_shift];
-                const size_t rowi = (((size_t)pg8 * p.Hkv + hk) << p.page_shift) + (kk & (p.page - 1));
-                const u32x2_t k8 = __builtin_nontemporal_load((const u32x2_t*)(kc8 + rowi * HD + ch * 8)),   // (non-temporal: see the bf16 path below)
-                              v8 = __builtin_nontemporal_load((const u32x2_t*)(vc8 + rowi * HD + ch * 8));
-                kv[u] = (u32x4_t){k8[0], k8[1], __float_as_uint(p.kscale[rowi]), (uint32_t)key};
-                vv[u] = (u32x4_t){v8[0], v8[1], __float_as_uint(p.vscale[rowi]), 0u};
-                continue;
-            }
-            // the page id ALWAYS comes from LDS (the launcher rejects tables longer than SP): a select between the LDS copy and
-            // the global table became a FLAT load, whose wait (vmcnt(0) lgkmcnt(0)) also drained the K/V loads in flight --
-            // every key's lookup waited for the previous key's rows
-            const int pg = s_pages[kk >> p.page_shift];
-            const size_t off = ((((size_t)pg * p.Hkv + hk) << p.page_shift) + (kk & (p.page - 1))) * HD + ch * 8;
-            // NON-TEMPORAL loads (round 5): a K / V row is read by ONE block, once per step -- as plain loads the rows were allocated in the
-            // XCD's L2 and in the MALL on their way through, displacing the lines every block of the NEXT launches re-reads (activation rows,
-            // norm weights, RoPE tables).  Measured, builds alternating on one box (profiles/r05_attn_kv_nt_ab.txt): this launch 5.63 ->
-            // 5.42 us at batch 1, 19.9 -> 18.3 at 8 rows, 69.0 -> 61.7 at 32; the whole step 2.593 -> 2.568 ms/token, 3.26 -> 3.19, 5.37 -> 5.11 ms
-            kv[u] = __builtin_nontemporal_load((const u32x4_t*)(kc + off));
-            vv[u] = __builtin_nontemporal_load((const u32x4_t*)(vc + off));
-            if (coh && kk == L - 1) {   // the row appended by the qkv kernel of THIS step (one kernel back): agent-scope re-read
-                kv[u] = ld_act16((const u32x4_t*)(kc + off), true);
-                vv[u] = ld_act16((const u32x4_t*)(vc + off), true);
-            }
-        }
-    };
-    auto consume_chunk = [&](u32x4_t (&kv)[KU], u32x4_t (&vv)[KU], const bool (&ok)[KU]) {
-        if constexpr (KV8) {   // bytes -> bf16 x scale; the key of this step comes from the staging row (its cache bytes may not have landed)
-#pragma unroll
-            for (int u = 0; u < KU; ++u) {
-                const bool is_new = (int)kv[u][3] == L - 1;
-                const u32x4_t kd = dequant8_e4m3((u32x2_t){kv[u][0], kv[u][1]}, __uint_as_float(kv[u][2]));
-                const u32x4_t vd = dequant8_e4m3((u32x2_t){vv[u][0], vv[u][1]}, __uint_as_float(vv[u][2]));
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    kv[u][j] = is_new ? new_k[j] : kd[j];
-                    vv[u][j] = is_new ? new_v[j] : vd[j];
-                }
-            }
-        }
-#pragma unroll
-        for (int gq = 0; gq < G; ++gq) {
-            float sc[KU];
-            float mc = -INFINITY;
-#pragma unroll
-            for (int u = 0; u < KU; ++u) {
-                float s = 0.f;
-                s = dot2_bf16(kv[u][0], q[gq][0], s);
-                s = dot2_bf16(kv[u][1], q[gq][1], s);
-                s = dot2_bf16(kv[u][2], q[gq][2], s);
-                s = dot2_bf16(kv[u][3], q[gq][3], s);
-                s = row16_sum(s);   // the 16 lanes of a key group are one DPP row
-                s = ok[u] ? s * p.scale : -INFINITY;
-                sc[u] = s;
-                mc = fmaxf(mc, s);
-            }
-            const float mn = fmaxf(m[gq], mc);
-            const float msafe = (mn == -INFINITY) ? 0.f : mn;
-            const float alpha = __expf(m[gq] - msafe);
-            float ls = l[gq] * alpha;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[gq][j] *= alpha;
-#pragma unroll
-            for (int u = 0; u < KU; ++u) {
-                const float pw = __expf(sc[u] - msafe);
-                ls += pw;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    o[gq][2 * j] += pw * bf_lo(vv[u][j]);
-                    o[gq][2 * j + 1] += pw * bf_hi(vv[u][j]);
-                }
-            }
-            l[gq] = ls;
-            m[gq] = mn;
-        }
-    };
-    if constexpr (DEEP) {
-        // FOUR chunks in flight: at 8 bytes per lane and key two chunks are 8 KiB per wave -- the launch was a latency chain (one chunk
-        // per ~1.1 us round trip: 18.9 us for 53 MB at batch 8); the raw bytes of four chunks take the registers two bf16 chunks did
-        constexpr int CHK = (4 * NW) * KU;
-        u32x4_t kvA[KU], vvA[KU], kvB[KU], vvB[KU], kvC[KU], vvC[KU], kvD[KU], vvD[KU];
-        bool okA[KU], okB[KU], okC[KU], okD[KU];
-        load_chunk(k0, kvA, vvA, okA);
-        if (k0 + CHK < k1) load_chunk(k0 + CHK, kvB, vvB, okB);
-        if (k0 + 2 * CHK < k1) load_chunk(k0 + 2 * CHK, kvC, vvC, okC);
-        for (int kb = k0; kb < k1; kb += 4 * CHK) {               // every condition is block-uniform
-            if (kb + 3 * CHK < k1) load_chunk(kb + 3 * CHK, kvD, vvD, okD);
-            consume_chunk(kvA, vvA, okA);
-            if (kb + 4 * CHK < k1) load_chunk(kb + 4 * CHK, kvA, vvA, okA);
-            if (kb + CHK < k1) consume_chunk(kvB, vvB, okB);
-            if (kb + 5 * CHK < k1) load_chunk(kb + 5 * CHK, kvB, vvB, okB);
-            if (kb + 2 * CHK < k1) consume_chunk(kvC, vvC, okC);
-            if (kb + 6 * CHK < k1) load_chunk(kb + 6 * CHK, kvC, vvC, okC);
-            if (kb + 3 * CHK < k1) consume_chunk(kvD, vvD, okD);
-        }
-    } else {
-        u32x4_t kvA[KU], vvA[KU], kvB[KU], vvB[KU];
-        bool okA[KU], okB[KU];
-        load_chunk(k0, kvA, vvA, okA);
-        for (int kb = k0; kb < k1; kb += 2 * (4 * NW) * KU) {
-            const bool hasB = kb + (4 * NW) * KU < k1;          // block-uniform
-            if (hasB) load_chunk(kb + (4 * NW) * KU, kvB, vvB, okB);
-            consume_chunk(kvA, vvA, okA);
-            if (kb + 2 * (4 * NW) * KU < k1) load_chunk(kb + 2 * (4 * NW) * KU, kvA, vvA, okA);
-            if (hasB) consume_chunk(kvB, vvB, okB);
-        }
-    }
-
-    // ---- merge the 4 key groups of the wave (lanes with equal ch), then the 4 waves through LDS ----
-#pragma unroll
-    for (int gq = 0; gq < G; ++gq) {
-        const float mw = rows_max(m[gq]);
-        const float msafe = (mw == -INFINITY) ? 0.f : mw;
-        const float f = __expf(m[gq] - msafe);
-        // every lane of a 16-lane key group carries the same l: after the two exchanges each lane holds the wave sum
-        const float lv = rows_sum(l[gq] * f);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float v = rows_sum(o[gq][j] * f);
-            if (kg == 0) red_o[wave][gq][ch * 8 + j] = v;
-        }
-        if (lane == 0) {
-            red_ml[wave][gq][0] = mw;
-            red_ml[wave][gq][1] = lv;
-        }
-    }
-    __syncthreads();
-    auto part_value = [&](int gq, int j) {
-        float M = red_ml[0][gq][0];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) M = fmaxf(M, red_ml[w][gq][0]);
-        const float msafe = (M == -INFINITY) ? 0.f : M;
-        float v = 0.f;
-        if (j < HD) {
-#pragma unroll
-            for (int w = 0; w < NW; ++w) v += red_o[w][gq][j] * __expf(red_ml[w][gq][0] - msafe);
-        } else if (j == HD) {
-            v = M;
-        } else if (j == HD + 1) {
-#pragma unroll
-            for (int w = 0; w < NW; ++w) v += red_ml[w][gq][1] * __expf(red_ml[w][gq][0] - msafe);
-        }
-        return v;
-    };
-    if constexpr (DIRECT) {   // this block holds the head's whole result -- normalise and write the bf16 row directly
-        for (int i = tid; i < G * (HD / 8); i += NT) {
-            const int gq = i / (HD / 8), c = i - gq * (HD / 8);
-            const float den = part_value(gq, HD + 1);
-            const float inv = den > 0.f ? 1.0f / den : 0.f;   // the arithmetic of attn_merge_chunk<1> (weight exp(m - M) = 1)
-            u32x4_t v;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = pack_bf16x2(part_value(gq, c * 8 + 2 * j) * inv, part_value(gq, c * 8 + 2 * j + 1) * inv);
-            *((u32x4_t*)((bf16_t*)p.o_out + (size_t)b * p.ldq + (hk * G + gq) * HD) + c) = v;
-        }
-        return;
-    }
-    for (int i = tid; i < G * PSTRIDE; i += NT) {
-        const int gq = i / PSTRIDE, j = i - gq * PSTRIDE;
-        st_act_f32(part + (size_t)gq * nsplit * PSTRIDE + j, part_value(gq, j), coh);
-    }
+    for (int c = threadIdx.x; c < hidden / 8; c += blockDim.x) o[c] = s[c];
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -982,14 +669,13 @@ __global__ __launch_bounds__(NW * 64) void emmax_decode_attn_kernel(DecodeAttnPa
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void emmax_decode_finish_kernel(FinishParams p) {
     const int b = blockIdx.x, tid = threadIdx.x;
-    constexpr bool coh = false;
     __shared__ float sv[256];
     __shared__ int si[256];
     float best = -INFINITY;
     int besti = 0x7fffffff;
     for (int i = tid; i < p.n_part; i += 256) {
-        const float v = ld_act_f32(p.part_val + (size_t)i * p.B + b, coh);
-        const int ii = ld_act_i32(p.part_idx + (size_t)i * p.B + b, coh);
+        const float v = *(p.part_val + (size_t)i * p.B + b);
+        const int ii = *(p.part_idx + (size_t)i * p.B + b);
         if (v > best || (v == best && ii < besti)) {
             best = v;
             besti = ii;
@@ -1081,12 +767,17 @@ static int launch_gemv_mode(GemvParams p, int B, hipStream_t stream, int* grid_o
 #undef CASEF
         return -1;
     }
-    switch (B) {
 #define CASEB(BB) case BB: return launch_gemv_t<BB, MODE, NORM, XATTN>(p, stream, grid_out)
-        CASEB(1); CASEB(2); CASEB(3); CASEB(4); CASEB(5); CASEB(6); CASEB(7); CASEB(8);
-#undef CASEB
-        default: return -1;
+    switch (B) {
+        CASEB(1); CASEB(2);
     }
+    if constexpr (MODE == GEMV_PLAIN) {   // 3-8 rows: plain rows only (emmax_op_gemv); a fused step of that size runs on the MFMA kernels
+        switch (B) {
+            CASEB(3); CASEB(4); CASEB(5); CASEB(6); CASEB(7); CASEB(8);
+        }
+    }
+#undef CASEB
+    return -1;
 }
 
 template <int MODE, bool NORM, bool XATTN = false>
@@ -1094,7 +785,8 @@ static int gemv_init_mode() {
     const int lim = 160 * 1024 - 4096;
     hipError_t e = hipSuccess;
 #define SETB(BB) if (e == hipSuccess) e = hipFuncSetAttribute((const void*)emmax_decode_gemv_kernel<BB, MODE, NORM, XATTN>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)
-    SETB(1); SETB(2); SETB(3); SETB(4); SETB(5); SETB(6); SETB(7); SETB(8);
+    SETB(1); SETB(2);
+    if constexpr (MODE == GEMV_PLAIN) { SETB(3); SETB(4); SETB(5); SETB(6); SETB(7); SETB(8); }   // (launch_gemv_mode)
 #undef SETB
 #define SETF(BB, FF) if (e == hipSuccess) e = hipFuncSetAttribute((const void*)emmax_decode_gemv_kernel<BB, MODE, NORM, XATTN, FF>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)
     SETF(1, 1); SETF(1, 2); SETF(1, 3); SETF(2, 1); SETF(2, 2); SETF(2, 3);
@@ -1149,59 +841,6 @@ int launch_decode_gemv(int mode, const GemvParams& p, int B, hipStream_t stream,
 
 int launch_decode_embed(const int32_t* cur_tok, const void* E, void* h, int B, int hidden, int vocab, hipStream_t stream, float* h32) {
     hipLaunchKernelGGL(emmax_decode_embed_kernel, dim3(B), dim3(256), 0, stream, cur_tok, (const bf16_t*)E, (bf16_t*)h, hidden, vocab, h32);
-    return hipGetLastError() == hipSuccess ? 0 : -4;
-}
-
-// splits of the KV range per (row, kv head): ~512 blocks in flight, at most 8 partials to merge
-int decode_attn_nsplit(int B, int Hkv) {
-    const int forced = emmax_tune().attn_nsplit;
-    if (forced > 0) {   // rounded down to a power of two (the kernel divides by shifting)
-        int f = forced > 16 ? 16 : forced;
-        while (f & (f - 1)) f &= f - 1;
-        return f;
-    }
-    // batch 1-2: ~512 blocks of 4 waves (8 splits at 32 heads).  Batch >= 3: one block per CU is enough and every split less
-    // halves the partials the o-proj has to merge for 8 rows -- at B = 8 (32 heads) ONE split: attention 20.5 -> 20.0 us, o-proj
-    // 12.6 -> 11.0 us, step 3.373 -> 3.297 ms (4 splits: 22.3 / 15.5 us)
-    int ns = (B >= 3 ? 256 : 512) / (B * Hkv);
-    if (ns < 1) ns = 1;
-    if (ns > 8) ns = 8;
-    while (ns & (ns - 1)) ns &= ns - 1;   // power of two: the o-proj prologue merges with a branch-free unrolled loop
-    return ns;
-}
-
-int launch_decode_attn(const DecodeAttnParams& p_in, int B, int Hq, int head_dim, int nsplit, hipStream_t stream) {
-    if (head_dim != 128) return -1;
-    DecodeAttnParams p = p_in;
-    if (p.max_pages < 1 || p.max_pages > 512 || p.page < 1 || (p.page & (p.page - 1))) return -1;   // table fits the kernel's LDS copy; page = 2^k
-    if (nsplit < 1 || (nsplit & (nsplit - 1))) return -1;   // the kernel divides the keys among the splits by shifting
-    p.page_shift = 0;
-    while ((1 << p.page_shift) < p.page) ++p.page_shift;
-    if (p.o_out && nsplit != 1) return -1;   // the direct form exists for one split only (nothing to merge)
-    if (p.kv_stage && (!p.kscale || !p.vscale)) return -1;   // fp8 KV cache: bytes + one scale per row
-    const int G = Hq / p.Hkv;
-    dim3 grid(nsplit, p.Hkv, B), block(256);
-    const int nw = emmax_tune().attn_nw;
-    const bool nw8 = nw == 8 || (nw == 0 && p.o_out && (long)p.Hkv * B <= 256);
-    // four chunks of keys in flight (bf16 cache): measured on one box (profiles/r05_attn_deep_k32_spread_ab.txt) -- B = 32 (1024 blocks, four
-    // per CU) 73.0 -> 68.5 us per launch, B = 8 / 16 (256 / 512 blocks) 20.0 -> 20.6 / 36.9 -> 37.3: on from 1024 blocks (-1 = that rule)
-    const int deep_sw = emmax_tune().attn_deep;
-    const bool deep = G <= 2 && (deep_sw > 0 || (deep_sw < 0 && (long)nsplit * p.Hkv * B >= 1024));   // (G >= 4: no registers for it)
-    switch (G) {
-#define ATTN_CASE(GG)                                                                                                   \
-    case GG:                                                                                                           \
-        if (p.kv_stage && p.o_out) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, true, 4, true>), grid, block, 0, stream, p); \
-        else if (p.kv_stage) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, false, 4, true>), grid, block, 0, stream, p); \
-        else if (p.o_out && deep) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, true, 4, false, true>), grid, block, 0, stream, p); \
-        else if (deep) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, false, 4, false, true>), grid, block, 0, stream, p); \
-        else if (p.o_out && nw8) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, true, 8>), grid, dim3(512), 0, stream, p); \
-        else if (p.o_out) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, true>), grid, block, 0, stream, p);     \
-        else hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG>), grid, block, 0, stream, p);                         \
-        break
-        ATTN_CASE(1); ATTN_CASE(2); ATTN_CASE(4); ATTN_CASE(8);
-#undef ATTN_CASE
-        default: return -1;
-    }
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

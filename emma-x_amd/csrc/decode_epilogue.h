@@ -8,7 +8,6 @@
 // scalars and references, so that a kernel keeps live exactly what it kept when the text stood in its own file (the kernels sit at the
 // edge of the register file), and none of them decides WHEN an operand is requested: the fetch helpers are called where each kernel had
 // its loads.
-// `coh` (defaulted): decode.hip's block-uniform agent-scope switch (common.h: st_act_*); absent, the stores are plain stores.
 #pragma once
 
 #include "common.h"
@@ -54,8 +53,8 @@ __device__ __forceinline__ void qkv_rope_fetch(const GemvParams& p, int pos, int
 
 // ---- residual (o-proj, down): h += W x in place.  r32: the fp32 stream p.h32 is the master copy (GemvParams::h32), the bf16 rows p.y its
 // mirror (what the NORM modes of the batch >= 3 / fp8 kernels read) ----
-__device__ __forceinline__ float resid_fetch(const GemvParams& p, int b, int row, bool r32, bool coh = false) {
-    return r32 ? p.h32[(size_t)b * p.ldh + row] : bf2f(ld_act_bf16((const bf16_t*)p.y + (size_t)b * p.ldy + row, coh));
+__device__ __forceinline__ float resid_fetch(const GemvParams& p, int b, int row, bool r32) {
+    return r32 ? p.h32[(size_t)b * p.ldh + row] : bf2f(*((const bf16_t*)p.y + (size_t)b * p.ldy + row));
 }
 // The element-level add + stores stay in each kernel: decode.hip and decode_mfma.hip multiply by the fp8 row scale right before the add,
 // and whether hipcc contracts that multiply into the add is decided per call site (one rounding or two: the fp32 stream would show it);
@@ -63,9 +62,12 @@ __device__ __forceinline__ float resid_fetch(const GemvParams& p, int b, int row
 
 // ---- SwiGLU (gate/up): element col of the activation row.  EX (exact numerics): the IEEE quotient, the product stays fp32 ----
 template <bool EX>
-__device__ __forceinline__ void swiglu_finish(const GemvParams& p, int b, int col, float g, float u, bool coh = false) {
+__device__ __forceinline__ void swiglu_finish(const GemvParams& p, int b, int col, float g, float u) {
     if constexpr (EX) ((float*)p.y)[(size_t)b * p.ldy + col] = silu_precise(g) * u;
-    else st_act_bf16((bf16_t*)p.y + (size_t)b * p.ldy + col, f2bf(silu(g) * u), coh);
+    else {   // (the address before the value: the order of the instructions decides hipcc's schedule in the callers)
+        bf16_t* y = (bf16_t*)p.y + (size_t)b * p.ldy + col;
+        *y = f2bf(silu(g) * u);
+    }
 }
 
 // ---- lm-head: greedy argmax with torch.argmax's tie rule -- take if greater; on equality the lower index ----
@@ -87,14 +89,13 @@ __device__ __forceinline__ void lmhead_row(const GemvParams& p, int b, int row, 
 // the block's best of batch column col: thread col folds the n LDS slots slot(0) .. slot(n - 1) of its column into (v0, i0) -- the caller
 // sets the start: (-inf, INT_MAX), or its first slot -- and writes the block's partial
 template <class Slot>
-__device__ __forceinline__ void lmhead_col_finish(const GemvParams& p, int B, int col, const float* bv, const int* bi, int n, Slot slot, float v0, int i0,
-                                                  bool coh = false) {
+__device__ __forceinline__ void lmhead_col_finish(const GemvParams& p, int B, int col, const float* bv, const int* bi, int n, Slot slot, float v0, int i0) {
     for (int k = 0; k < n; ++k) {
         const int e = slot(k);
         lmhead_take(bv[e], bi[e], v0, i0);
     }
-    st_act_f32(p.part_val + (size_t)blockIdx.x * B + col, v0, coh);
-    st_act_i32(p.part_idx + (size_t)blockIdx.x * B + col, i0, coh);
+    *(p.part_val + (size_t)blockIdx.x * B + col) = v0;
+    *(p.part_idx + (size_t)blockIdx.x * B + col) = i0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

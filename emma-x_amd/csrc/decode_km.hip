@@ -137,7 +137,7 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
             if constexpr (EX) {   // the merged chunk in fp32, split into its two terms: rows b and b + 8
                 for (int b = 0; b < B; ++b) {
                     float m8[8];
-                    (void)attn_merge_chunk_loop(p.attn_part + (size_t)(b * p.Hq + (c >> 4)) * p.nsplit * PSTRIDE, (c & 15) * 8, p.nsplit, false, m8);
+                    (void)attn_merge_chunk_loop(p.attn_part + (size_t)(b * p.Hq + (c >> 4)) * p.nsplit * PSTRIDE, (c & 15) * 8, p.nsplit, m8);
                     u32x4_t hi, lo;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {

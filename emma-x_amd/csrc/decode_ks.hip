@@ -250,7 +250,7 @@ __device__ __forceinline__ void ks_run_op(const GemvParams& p, u32x4_t (&wr)[KsR
                 const float* pp = p.attn_part + (size_t)(b * p.Hq + (cg >> 4)) * p.nsplit * PSTRIDE;
                 if constexpr (EX) {
                     float m8[8];
-                    (void)(p.nsplit == 8 ? attn_merge_chunk<8, 4>(pp, (cg & 15) * 8, m8) : attn_merge_chunk_loop(pp, (cg & 15) * 8, p.nsplit, false, m8));
+                    (void)(p.nsplit == 8 ? attn_merge_chunk<8, 4>(pp, (cg & 15) * 8, m8) : attn_merge_chunk_loop(pp, (cg & 15) * 8, p.nsplit, m8));
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const hl2_t t = split_hl2(cok[j] ? m8[2 * e] : 0.f, cok[j] ? m8[2 * e + 1] : 0.f);

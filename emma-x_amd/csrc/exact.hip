@@ -430,7 +430,7 @@ __global__ __launch_bounds__(256) void emmax_x_attention_kernel(AttnParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Split-KV decode attention over the fp32 paged cache: decode.hip's emmax_decode_attn_kernel (16 lanes per key row, online softmax per
+// Split-KV decode attention over the fp32 paged cache: decode_attn.hip's emmax_decode_attn_kernel (16 lanes per key row, online softmax per
 // lane group, chunks of keys software-pipelined through two register buffers, the block's partial { o[128], m, l } per (row, head, split)
 // merged by the o-proj's prologue) with fp32 q (8 elements per lane), fp32 K / V rows (two 16-byte loads per lane, key and operand) and
 // fma dot products -- the arithmetic of HF's eager attention on an fp32 cache.  grid (nsplit, Hkv, B), 256 threads.
@@ -720,7 +720,7 @@ int launch_x_attention(const AttnParams& p, int head_dim, hipStream_t stream) {
     return -1;
 }
 
-// fp32 q rows [B, ldq], fp32 K / V caches [pages][Hkv][page][128]; partials as decode.hip's kernel writes them
+// fp32 q rows [B, ldq], fp32 K / V caches [pages][Hkv][page][128]; partials as decode_attn.hip's kernel writes them
 int launch_x_decode_attn(const DecodeAttnParams& p_in, int B, int Hq, int head_dim, int nsplit, hipStream_t stream) {
     if (head_dim != 128) return -1;
     DecodeAttnParams p = p_in;

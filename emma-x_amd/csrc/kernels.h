@@ -191,7 +191,7 @@ struct EmmaxTune {
 };
 const EmmaxTune& emmax_tune();
 
-// ---- decode.hip ----
+// ---- decode.hip: the LDS-staged GEMV, the embedding gather ----
 enum { GEMV_QKV = 0, GEMV_RESID = 1, GEMV_GATEUP = 2, GEMV_LMHEAD = 3, GEMV_PLAIN = 4 };
 struct GemvParams {
     const void* x;          // bf16 [B, ldx] activations
@@ -250,7 +250,9 @@ struct GemvParams {
                             //   the 8-bit extension plane follows it; 0 = fp32 rows
 };
 // (where the QKV epilogues put the new K / V rows: gemv_kv_row / gemv_kv_store_x, decode_epilogue.h -- device code, this is also a host header)
-// staged_out (optional): 1 when decode.hip's own LDS-staged kernel served the call, 0 when decode_ks.hip took it
+// staged_out (optional): 1 when decode.hip's own LDS-staged kernel served the call, 0 when decode_ks.hip took it.
+// The staged kernel exists for the fused modes at B = 1, 2 (bf16 and fp8 rows) and for GEMV_PLAIN at B <= 8 (fp8 rows: B <= 2); any other
+// (mode, B) returns -1 -- launch_proj (step.hip) sends every batch >= EMMAX_MFMA_MIN_BATCH to the MFMA kernels.
 int launch_decode_gemv(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out = nullptr, int* staged_out = nullptr);
 // decode_ks.hip: the batch 1-2 bf16 projections with K split across the waves of a block (activation slice in registers, no
 // block-wide stage); returns -2 for a shape it does not take.  launch_decode_gemv tries it first (tuning switch `ks` = 0: never).
@@ -259,6 +261,7 @@ bool decode_ks_enabled();
 int decode_gemv_init();   // raise the dynamic-LDS limit of every GEMV instantiation (call once, outside graph capture)
 int launch_decode_embed(const int32_t* cur_tok, const void* E, void* h, int B, int hidden, int vocab, hipStream_t stream, float* h32 = nullptr);
 
+// ---- decode_attn.hip ----
 struct DecodeAttnParams {
     const void* q;          // bf16 [B, ldq] rotated queries
     const void* kcache;     // bf16 [pages][Hkv][page][hd]
@@ -283,6 +286,7 @@ int decode_attn_nsplit(int B, int Hkv);
 int launch_decode_attn(const DecodeAttnParams& p, int B, int Hq, int head_dim, int nsplit, hipStream_t stream);
 int launch_x_decode_attn(const DecodeAttnParams& p, int B, int Hq, int head_dim, int nsplit, hipStream_t stream);   // exact.hip: fp32 q, fp32 cache
 
+// ---- decode.hip: the greedy finish of a step ----
 struct FinishParams {
     const float* part_val;
     const int32_t* part_idx;

@@ -190,6 +190,8 @@ CASES = [
     # hidden 512: the fp8 qkv / gate-up / lm-head on the K-split kernels (8 and 16 staged rows of decode_km.hip, decode_kmp.hip)
     _case("H8", 3, {}, _all(KM)), _case("H8", 16, {}, _all(KM)), _case("H8", 32, {}, _all(KMP)),
     _case("GX", 1, {}, _all(KS)), _case("GX", 2, {}, _all(KS)), _case("GX", 3, {}, _all(KM)), _case("GX", 8, {}, _all(KM)),
+    # a split count other than 8: the o-proj merges the partials in a loop (attn_merge_chunk_loop) -- the staged GEMV's, decode_ks.hip's fp32 one
+    _case("G", 2, {"ks": 0, "attn_nsplit": 4}, _all(GEMV)), _case("GX", 2, {"attn_nsplit": 4}, _all(KS)),
 ]
 
 
