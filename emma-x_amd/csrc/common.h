@@ -211,6 +211,19 @@ __device__ __forceinline__ bf16x8_t fp8x8_to_bf16x8(uint32_t lo, uint32_t hi) {
     return __builtin_bit_cast(bf16x8_t, v);
 }
 
+// OCP MXFP4 weights -> bf16 in registers (exact: an e2m1 element times a power of two has one mantissa bit): v_cvt_scalef32_pk_bf16_fp4 widens
+// the two elements of byte SEL of a dword (low nibble first) and multiplies by the block scale; 8 elements = one dword.  The scale operand is the
+// block's e8m0 code in the exponent field of an fp32 (the instruction applies the exponent only, e4m3_row_scale above): byte j of a dword of
+// four codes, one shift behind the field extract.
+__device__ __forceinline__ float e8m0_scale(uint32_t codes, int j) { return __uint_as_float(((codes >> (8 * j)) & 0xffu) << 23); }
+__device__ __forceinline__ bf16x8_t mx4x8_to_bf16x8(uint32_t q, float scale) {
+    const u32x4_t v = {__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 0)),
+                       __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 1)),
+                       __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 2)),
+                       __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 3))};
+    return __builtin_bit_cast(bf16x8_t, v);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Split-KV attention partials: per (row, head, split) EMMAX_PSTRIDE floats = { o[0..128) un-normalised, m, l, 2 pad }.
 // attn_merge_chunk merges the NS partials of one head for the 8 output elements d0..d0+8 and returns them as 8 bf16.

@@ -34,6 +34,7 @@ constexpr int KM_NT = KM_WAVES * 64;
 constexpr int KM_STEPS = 16;      // bf16 k-steps (32 elements) per tile and wave: K <= 8 * 16 * 32 = 4096
 constexpr int KM_MAX_TILES = 8;   // tiles per block the LDS partial sums hold
 constexpr int PSTRIDE = EMMAX_PSTRIDE;
+enum { W_BF16 = 0, W_FP8 = 1, W_MX4 = 2 };   // weight format of a tile stream
 
 // row-major [N, ld] -> fragment-major tiles in the km row order (N % 16 == 0, K % 32 == 0)
 __global__ __launch_bounds__(256) void emmax_repack_km_kernel(const bf16_t* __restrict__ src, int ld, u32x4_t* __restrict__ dst, int N, int K,
@@ -45,6 +46,83 @@ __global__ __launch_bounds__(256) void emmax_repack_km_kernel(const bf16_t* __re
         const int kt = (int)(tile % (K / 32)), nt = (int)(tile / (K / 32));
         const int n = km_src_row(perm, head_dim, nt, lane & 15), k = kt * 32 + (lane >> 4) * 8;
         dst[c] = *(const u32x4_t*)(src + (size_t)n * ld + k);
+    }
+}
+
+// ---- MXFP4 copies (kernels.h: launch_quant_mx4) -- integer arithmetic only, so that bf16 denormals and the clamped exponent come out as the
+// format defines them whatever the float modes are.  One thread per (tile, row): 128 k = four blocks, 16 dwords of elements + one of codes.
+// |w| = S 2^q with S the 8-bit significand; x = |w| / 2^e as the fixed-point number x 2^42, compared with the midpoints of the e2m1 grid
+// (ties to the even code: <= below an even code's upper midpoint, < below an odd one's)
+__device__ __forceinline__ uint32_t mx4_code(uint32_t mag /* bf16 bits without the sign */, int e) {
+    const int E = (int)(mag >> 7);
+    const uint64_t S = E ? (0x80u | (mag & 0x7fu)) : (mag & 0x7fu);
+    const int sh = (E ? E : 1) - 127 - 7 - e + 42;   // x 2^42 = S << sh;  x < 8 (or saturates): sh <= 38
+    const uint64_t x = sh < 0 ? 0 : sh > 40 ? ~0ull : (S << sh);
+    const uint64_t q = 1ull << 40;   // 0.25
+    return x <= q ? 0u : x < 3 * q ? 1u : x <= 5 * q ? 2u : x < 7 * q ? 3u : x <= 10 * q ? 4u : x < 14 * q ? 5u : x <= 20 * q ? 6u : 7u;
+}
+// bf16 bits of +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}[code & 7] 2^e, e in [-127, 127] (denormal results included)
+__device__ __forceinline__ uint32_t mx4_value_bits(uint32_t code, int e) {
+    const uint32_t c = code & 7u, sign = (code & 8u) << 12;
+    if (!c) return 0u;   // (zeros are +0 whatever the sign nibble says)
+    const int p = e + (c == 1 ? -1 : (int)(c >> 1) - 1);   // value = (1 + man / 2) 2^p
+    const uint32_t man = c == 1 ? 0u : (c & 1u);
+    if (p >= -126) return sign | ((uint32_t)(p + 127) << 7) | (man << 6);
+    return sign | ((2u + man) << (p + 132));            // p = -127, -128: (2 + man) 2^(p - 1) in units of 2^-133
+}
+__global__ __launch_bounds__(256) void emmax_quant_mx4_kernel(const bf16_t* __restrict__ src, int ld, uint32_t* __restrict__ tiles, uint32_t* __restrict__ scales,
+                                                             int N, int K, int perm, int head_dim) {
+    const int KT = K / 128;
+    const size_t total = (size_t)N * KT;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int r = (int)(i & 15);
+        const size_t tile = i >> 4;
+        const int kt = (int)(tile % KT), nt = (int)(tile / KT);
+        const bf16_t* row = src + (size_t)km_src_row(perm, head_dim, nt, r) * ld + (size_t)kt * 128;
+        uint32_t codes = 0;
+        for (int j = 0; j < 4; ++j) {
+            u32x4_t v[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) v[g] = *(const u32x4_t*)(row + j * 32 + g * 8);
+            uint32_t amax = 0;
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int d = 0; d < 4; ++d) amax = max(amax, max(v[g][d] & 0x7fffu, (v[g][d] >> 16) & 0x7fffu));
+            // floor(log2(amax)) - 2 clamped at -127 (bf16 cannot reach the upper clamp): the exponent field less 2, zero for denormals
+            const int E = (int)(amax >> 7);
+            const int code = amax == 0 ? 127 : max(E - 2, 0);
+            const int e = code - 127;
+            codes |= (uint32_t)code << (8 * j);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {   // lane (g, r) of the tile: dword j = its 8 elements of MFMA step j
+                uint32_t q = 0;
+#pragma unroll
+                for (int d = 0; d < 4; ++d) {
+                    const uint32_t lo = v[g][d] & 0xffffu, hi = v[g][d] >> 16;
+                    q |= (mx4_code(lo & 0x7fffu, e) | ((lo >> 12) & 8u)) << (8 * d);
+                    q |= (mx4_code(hi & 0x7fffu, e) | ((hi >> 12) & 8u)) << (8 * d + 4);
+                }
+                tiles[(tile * 64 + (size_t)(g * 16 + r)) * 4 + j] = q;
+            }
+        }
+        scales[i] = codes;
+    }
+}
+__global__ __launch_bounds__(256) void emmax_dequant_mx4_kernel(const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ scales, bf16_t* __restrict__ dst,
+                                                               int ld, int N, int K, int perm, int head_dim) {
+    const int KT = K / 128;
+    const size_t total = (size_t)N * KT * 16;   // one thread per (tile, lane, dword): 8 elements
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int j = (int)(i & 3), lane = (int)((i >> 2) & 63), r = lane & 15, g = lane >> 4;
+        const size_t tile = i >> 8;
+        const int kt = (int)(tile % KT), nt = (int)(tile / KT);
+        const uint32_t q = tiles[i];
+        const int e = (int)((scales[tile * 16 + r] >> (8 * j)) & 0xffu) - 127;
+        u32x4_t o;
+#pragma unroll
+        for (int d = 0; d < 4; ++d) o[d] = mx4_value_bits(q >> (8 * d), e) | (mx4_value_bits(q >> (8 * d + 4), e) << 16);
+        *(u32x4_t*)(dst + (size_t)km_src_row(perm, head_dim, nt, r) * ld + (size_t)kt * 128 + j * 32 + g * 8) = o;
     }
 }
 
@@ -71,15 +149,25 @@ __global__ __launch_bounds__(256) void emmax_repack_km_kernel(const bf16_t* __re
 // batch column b, the lo terms in column b + 8: the eight columns a batch <= 8 leaves empty carry the second term, so the weight stream, the
 // MFMA count and the register budget are those of the plain kernel; the epilogue adds columns b and b + 8 and hands fp32 results on (fp32 q rows,
 // fp32 RoPE with torch's per-product rounding, the 24-bit / fp32 cache, the SwiGLU product in fp32) as decode_ks.hip's EX form does at batch 1-2.
-template <int MODE, bool NORM, bool XATTN, bool FP8, bool R32, int NB, bool ROLL, bool EX = false>
+// register state of the MX4 form (WF below): QD sets of a tile's QS load steps and their scale dwords; nothing in the other forms
+template <bool ON, int QD, int QS> struct Mx4Tiles {};
+template <int QD, int QS> struct Mx4Tiles<true, QD, QS> { u32x4_t w[QD][QS]; uint32_t s[QD][QS]; };
+// WF (weight format of the tiles): W_BF16; W_FP8 (above); W_MX4: OCP MXFP4 -- e2m1 elements, one e8m0 scale per 32 k of a row.  One 1 KiB tile =
+// 16 rows x 128 k: lane l holds row l & 15, dword j of its 16 bytes = the 8 k of group l >> 4 of the tile's j-th 32-wide MFMA step (element e in
+// nibble e), so ONE load feeds four MFMAs; the scales are a second stream in the same tile order, one dword of four e8m0 codes per (tile, row)
+// = 64 B per tile, fetched by the sixteen rows' lanes as one request.  v_cvt_scalef32_pk_bf16_fp4 widens two elements and applies the block
+// scale (the code shifted into an fp32 exponent); a de-quantised value is exact in bf16, so MFMA, prologues and epilogues are the bf16 form's.
+// Four tiles (16 KiB + scales) per wave in flight.
+template <int MODE, bool NORM, bool XATTN, int WF, bool R32, int NB, bool ROLL, bool EX = false>
 __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p) {
-    static_assert(!EX || (NB == 16 && !FP8 && !ROLL), "exact numerics: sixteen window rows = eight batch rows x two terms, bf16 weights");
+    constexpr bool FP8 = WF == W_FP8, MX4 = WF == W_MX4;
+    static_assert(!EX || (NB == 16 && WF == W_BF16 && !ROLL), "exact numerics: sixteen window rows = eight batch rows x two terms, bf16 weights");
     extern __shared__ __attribute__((aligned(16))) unsigned char km_smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g4 = lane >> 4, c16 = lane & 15;
     const int B = p.batch, K = p.K;
-    constexpr int KS = FP8 ? 64 : 32;             // elements per load step
-    constexpr int NSTEP = FP8 ? KM_STEPS / 2 : KM_STEPS;   // load steps per tile and wave
+    constexpr int KS = MX4 ? 128 : FP8 ? 64 : 32;   // elements per load step
+    constexpr int NSTEP = KM_STEPS * 32 / KS;     // load steps per tile and wave
     const int KT = K / KS;                        // load steps of a whole row
     const int KTW = KT / KM_WAVES;                // ... of this wave's slice (launcher: K % (8 * KS) == 0, KTW <= NSTEP)
     const int tiles_cap = p.kc;                   // launcher
@@ -107,10 +195,14 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
     if (e_on) tile4_prefetch<MODE, R32>(p, e_c, e_tile, e_rq, pre_a, pre_b, pre_pos, pre_pg);
 
     // ---- weight stream: buffer loads, the (tile, step) offset in an SGPR, the lane's 16 bytes in the VGPR offset ----
-    const unsigned w_bytes = (unsigned)((size_t)p.n_groups * 16 * (size_t)K * (FP8 ? 1 : 2));
+    const unsigned w_bytes = MX4 ? (unsigned)((size_t)p.n_groups * 8 * (size_t)K) : (unsigned)((size_t)p.n_groups * 16 * (size_t)K * (FP8 ? 1 : 2));
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (int)w_bytes, 0x00020000);
     const unsigned voff = (unsigned)lane * 16u;
     u32x4_t wa[NSTEP], wb[NSTEP];   // two tiles in flight
+    // MX4: four register sets of a tile's four load steps, and each step's scale dword (the rows' lanes: 4 bytes at 4 (lane & 15) of the tile's 64).
+    // (An empty struct in the bf16 / fp8 forms: everything that touches it sits under `if constexpr (MX4)`.)
+    constexpr int QD = 4, QS = NSTEP;
+    Mx4Tiles<MX4, QD, QS> q4;
     auto issue_one = [&](u32x4_t (&w)[NSTEP], int tl, int s) {   // step s of tile tl of the block (uniform); past the end: out of range = zeros, no traffic
         const int ok = (tl < ntb && s < KTW) ? -1 : 0;
         const unsigned so = ((unsigned)(((t_lo + tl) * KT + wave * KTW + s) * 1024) & (unsigned)ok) | (w_bytes & (unsigned)~ok);
@@ -120,6 +212,21 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
 #pragma unroll
         for (int s = 0; s < NSTEP; ++s) issue_one(w, tl, s);
     };
+    auto issue4_one = [&](int d, int tl, int s) {   // MX4: step s of tile tl of the block into set d (uniform); past the end: zeros, no traffic
+        if constexpr (MX4) {
+            const unsigned s_bytes = w_bytes / 16u;
+            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w4_scales, 0, (int)s_bytes, 0x00020000);
+            const int ok = (tl < ntb && s < KTW) ? -1 : 0;
+            const unsigned ti = (unsigned)((t_lo + tl) * KT + wave * KTW + s);
+            q4.w[d][s] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, voff, ((ti * 1024u) & (unsigned)ok) | (w_bytes & (unsigned)~ok), 2));
+            q4.s[d][s] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(srsrc, (unsigned)c16 * 4u, ((ti * 64u) & (unsigned)ok) | (s_bytes & (unsigned)~ok), 2);
+        }
+    };
+    auto issue4 = [&](int d, int tl) {
+#pragma unroll
+        for (int s = 0; s < QS; ++s) issue4_one(d, tl, s);
+    };
+    auto issue_first = [&]() { if constexpr (MX4) issue4(0, 0); else issue(wa, 0); };
 
     // ---- activations: this wave's K slice as MFMA B fragments (batch row = lane & 15, k = 8 (lane >> 4) .. + 8 of a 32-step) ----
     // Fetched ROW-shaped -- one contiguous 1 KiB request per batch row, lane l the 8 elements [8 l, 8 l + 8) of the slice -- and
@@ -130,7 +237,7 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
     const int ksl = K / KM_WAVES / 32;   // 32-element fragments in the wave's slice
     if constexpr (XATTN) {
         // o-proj: the block merges the attention split partials once (every thread one 8-element chunk per row), through LDS
-        issue(wa, 0);
+        issue_first();
         const int nch = K >> 3;
         for (int c = tid; c < nch; c += KM_NT) {
             unsigned char* dst = xlds + (size_t)c * 16;
@@ -186,7 +293,7 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
             }
             u32x4_t nwv = {0u, 0u, 0u, 0u};
             if constexpr (NORM) nwv = *((const u32x4_t*)((const bf16_t*)p.norm_w + wave * ksl * 32) + ch);
-            issue(wa, 0);
+            issue_first();
 #pragma unroll
             for (int b = 0; b < 8; ++b) {
                 float ss = 0.f;
@@ -216,7 +323,7 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
         for (int b = 0; b < NB; ++b) xr[b] = *((const u32x4_t*)((const bf16_t*)p.x + (size_t)min(b, B - 1) * p.ldx + wave * ksl * 32) + ch);
         u32x4_t nwv = {0u, 0u, 0u, 0u};
         if constexpr (NORM) nwv = *((const u32x4_t*)((const bf16_t*)p.norm_w + wave * ksl * 32) + ch);
-        issue(wa, 0);   // behind the activation requests: those are waited for by count while the first tile is in flight
+        issue_first();   // behind the activation requests: those are waited for by count while the first tile is in flight
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
             float ss = 0.f;
@@ -244,6 +351,10 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
             xf[s] = __builtin_bit_cast(bf16x8_t, v);
         }
     }
+    if constexpr (MX4) {
+#pragma unroll
+        for (int d = 1; d < QD; ++d) issue4(d, d);
+    } else
     issue(wb, 1);   // the second tile once the prologue's temporaries are dead (all of them next to two tiles would not fit 256 VGPRs)
 
     // ---- main loop: two tiles per trip (register sets a / b); a set is consumed MFMA by MFMA and refilled with the tile two ahead ----
@@ -266,9 +377,30 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
         }
         if (tl < ntb) *(f32x4_t*)(part_of(wave) + ((size_t)tl * 64 + lane) * 4) = acc;
     };
-    for (int tl = 0; tl < ntb; tl += 2) {
-        run_tile(wa, tl);
-        run_tile(wb, tl + 1);
+    // MX4: set d holds tile tl; per load step four MFMAs, byte j of the step's scale dword shifted into the exponent of the conversion's scale
+    // operand; the set's step is refilled with the tile four ahead as soon as its MFMAs have issued
+    auto run_tile4 = [&](int d, int tl) {
+        if constexpr (MX4) {
+            f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < QS; ++s) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(mx4x8_to_bf16x8(q4.w[d][s][j], e8m0_scale(q4.s[d][s], j)), xf[4 * s + j], acc, 0, 0, 0);
+                issue4_one(d, tl + QD, s);
+            }
+            if (tl < ntb) *(f32x4_t*)(part_of(wave) + ((size_t)tl * 64 + lane) * 4) = acc;
+        }
+    };
+    if constexpr (MX4) {
+        for (int tl = 0; tl < ntb; tl += QD) {
+#pragma unroll
+            for (int d = 0; d < QD; ++d) run_tile4(d, tl + d);
+        }
+    } else {
+        for (int tl = 0; tl < ntb; tl += 2) {
+            run_tile(wa, tl);
+            run_tile(wb, tl + 1);
+        }
     }
     __syncthreads();
 
@@ -401,24 +533,26 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
 // the start (22 / 12 KiB per wave), every register refilled with the next phase's step as soon as its MFMA has issued.
 // y = h + W x in place (+ the per-row scale with fp8 weights).
 // ---------------------------------------------------------------------------------------------------------------------
-template <int NB> struct KdShape {
-    static constexpr int FR = NB == 8 ? 22 : 12;      // fragments (32 elements) per phase and wave
+// (MX4 tiles: a load step is four fragments, so eight rows run two phases of 24 -- 97 KiB of windows against 89)
+template <int NB, int WF = 0> struct KdShape {
+    static constexpr int FR = NB == 8 ? (WF == W_MX4 ? 24 : 22) : 12;      // fragments (32 elements) per phase and wave
     static constexpr int NPH = NB == 8 ? 2 : 4;       // phases: K <= 8 waves x NPH x FR x 32 = 11264 / 12288
     static constexpr int XP = FR * 64 + 16;           // bytes per staged row slice
     static constexpr int CH = (FR * 4 + 63) / 64;     // 16-byte chunks per lane and row of a phase
 };
 // EX (exact numerics, batch 3-8; NB = 16): p.x holds the fp32 SwiGLU product; window rows b / b + 8 = the two bf16 terms of batch row b (see
 // emmax_decode_km_kernel); the row registers hold the fp32 chunk as two quads (r[2 b], r[2 b + 1]).
-template <bool FP8, bool R32, int NB, bool EX = false>
+template <int WF, bool R32, int NB, bool EX = false>
 __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_kmd_kernel(GemvParams p) {
-    static_assert(!EX || (NB == 16 && !FP8 && R32), "exact numerics: eight batch rows x two terms, bf16 weights, fp32 residual stream");
+    constexpr bool FP8 = WF == W_FP8, MX4 = WF == W_MX4;
+    static_assert(!EX || (NB == 16 && WF == W_BF16 && R32), "exact numerics: eight batch rows x two terms, bf16 weights, fp32 residual stream");
     extern __shared__ __attribute__((aligned(16))) unsigned char km_smem[];
-    using S = KdShape<NB>;
+    using S = KdShape<NB, WF>;
     constexpr int FR = S::FR, NPH = S::NPH, XP = S::XP, CH = S::CH;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g4 = lane >> 4, c16 = lane & 15;
     const int B = p.batch, K = p.K;
-    constexpr int KS = FP8 ? 64 : 32, FPS = FP8 ? 2 : 1;   // elements / fragments per load step
+    constexpr int FPS = MX4 ? 4 : FP8 ? 2 : 1, KS = 32 * FPS;   // fragments / elements per load step
     constexpr int NST = FR / FPS;                            // load steps per phase
     const int KT = K / KS;
     const int kq = KT / KM_WAVES, kr = KT % KM_WAVES;
@@ -496,14 +630,21 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_kmd_kernel(GemvParams p
     load_rows(1, xb);
 
     // ---- weights: phase 0 in flight now, later phases refilled register by register ----
-    const unsigned w_bytes = (unsigned)((size_t)p.n_groups * 16 * (size_t)K * (FP8 ? 1 : 2));
+    const unsigned w_bytes = MX4 ? (unsigned)((size_t)p.n_groups * 8 * (size_t)K) : (unsigned)((size_t)p.n_groups * 16 * (size_t)K * (FP8 ? 1 : 2));
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (int)w_bytes, 0x00020000);
     const unsigned voff = (unsigned)lane * 16u;
     u32x4_t w[NST];
+    // MX4: the scale dword of each load step (emmax_decode_km_kernel: 64 B per tile in the tiles' order, 4 bytes per row)
+    Mx4Tiles<MX4, 1, NST> q4;
     auto issue_w = [&](int ph, int s) {   // load step s of phase ph (past the wave's slice: out of range = zeros, no traffic)
         const int ok = (ph * NST + s < k_n) ? -1 : 0;
         const unsigned so = ((unsigned)((tile * KT + k_lo + ph * NST + s) * 1024) & (unsigned)ok) | (w_bytes & (unsigned)~ok);
         w[s] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, voff, so, 2));
+        if constexpr (MX4) {
+            const unsigned s_bytes = w_bytes / 16u;
+            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w4_scales, 0, (int)s_bytes, 0x00020000);
+            q4.s[0][s] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(srsrc, (unsigned)c16 * 4u, ((unsigned)((tile * KT + k_lo + ph * NST + s) * 64) & (unsigned)ok) | (s_bytes & (unsigned)~ok), 2);
+        }
     };
 #pragma unroll
     for (int s = 0; s < NST; ++s) issue_w(0, s);
@@ -517,7 +658,10 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_kmd_kernel(GemvParams p
         return __builtin_bit_cast(bf16x8_t, (EX ? (c16 & 7) < B : c16 < B) ? v : (u32x4_t){0u, 0u, 0u, 0u});
     };
     auto mfma_step = [&](int s) {
-        if constexpr (FP8) {
+        if constexpr (MX4) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(mx4x8_to_bf16x8(w[s][j], e8m0_scale(q4.s[0][s], j)), frag(4 * s + j), acc, 0, 0, 0);
+        } else if constexpr (FP8) {
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fp8x8_to_bf16x8(w[s][0], w[s][1]), frag(2 * s), acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fp8x8_to_bf16x8(w[s][2], w[s][3]), frag(2 * s + 1), acc, 0, 0, 0);
         } else {
@@ -566,10 +710,10 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_kmd_kernel(GemvParams p
     }
 }
 
-template <bool FP8, int NB, bool EX = false>
+template <int WF, int NB, bool EX = false>
 int kmd_launch(GemvParams p, int B, hipStream_t stream) {
-    using S = KdShape<NB>;
-    constexpr int KS = FP8 ? 64 : 32, FPS = FP8 ? 2 : 1;
+    using S = KdShape<NB, WF>;
+    constexpr int FPS = WF == W_MX4 ? 4 : WF == W_FP8 ? 2 : 1, KS = 32 * FPS;
     if (p.K % KS || p.n_rows % 16 || p.attn_part) return -2;
     p.batch = B;
     p.n_groups = p.n_rows / 16;
@@ -578,17 +722,17 @@ int kmd_launch(GemvParams p, int B, hipStream_t stream) {
     const size_t smem = (size_t)KM_WAVES * 1024 + (size_t)KM_WAVES * NB * S::XP;
     if constexpr (EX) {
         if (!p.h32 || B > 8) return -2;
-        hipLaunchKernelGGL((emmax_decode_kmd_kernel<false, true, 16, true>), dim3(p.n_groups), dim3(KM_NT), smem, stream, p);
+        hipLaunchKernelGGL((emmax_decode_kmd_kernel<W_BF16, true, 16, true>), dim3(p.n_groups), dim3(KM_NT), smem, stream, p);
     } else {
-        if (p.h32) hipLaunchKernelGGL((emmax_decode_kmd_kernel<FP8, true, NB>), dim3(p.n_groups), dim3(KM_NT), smem, stream, p);
-        else hipLaunchKernelGGL((emmax_decode_kmd_kernel<FP8, false, NB>), dim3(p.n_groups), dim3(KM_NT), smem, stream, p);
+        if (p.h32) hipLaunchKernelGGL((emmax_decode_kmd_kernel<WF, true, NB>), dim3(p.n_groups), dim3(KM_NT), smem, stream, p);
+        else hipLaunchKernelGGL((emmax_decode_kmd_kernel<WF, false, NB>), dim3(p.n_groups), dim3(KM_NT), smem, stream, p);
     }
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
-template <int MODE, bool NORM, bool XATTN, bool FP8, int NB, bool ROLL, bool EX = false>
+template <int MODE, bool NORM, bool XATTN, int WF, int NB, bool ROLL, bool EX = false>
 int km_launch_nb(GemvParams p, int B, hipStream_t stream, int* grid_out) {
-    constexpr int KS = FP8 ? 64 : 32;
+    constexpr int KS = WF == W_MX4 ? 128 : WF == W_FP8 ? 64 : 32;
     if (p.K % (KM_WAVES * KS) || p.K > KM_WAVES * KM_STEPS * 32 || p.n_rows % 16) return -2;
     if (MODE == GEMV_QKV && (p.head_dim % 16 || p.head_dim < 16)) return -2;
     p.batch = B;
@@ -606,56 +750,62 @@ int km_launch_nb(GemvParams p, int B, hipStream_t stream, int* grid_out) {
     if (grid_out) *grid_out = grid;
     if constexpr (EX) {   // exact numerics: fp32 rows in (h32 / p.x / the split partials), two terms per batch row, batch <= 8
         if (B > 8 || !p.h32) return -2;
-        hipLaunchKernelGGL((emmax_decode_km_kernel<MODE, NORM, XATTN, false, MODE == GEMV_RESID, 16, false, true>), dim3(grid), dim3(KM_NT), smem, stream, p);
+        hipLaunchKernelGGL((emmax_decode_km_kernel<MODE, NORM, XATTN, W_BF16, MODE == GEMV_RESID, 16, false, true>), dim3(grid), dim3(KM_NT), smem, stream, p);
         return hipGetLastError() == hipSuccess ? 0 : -4;
     }
     if constexpr (MODE == GEMV_RESID) {   // (NORM modes read the bf16 mirror: h32 is ignored there)
         if (p.h32) {
-            hipLaunchKernelGGL((emmax_decode_km_kernel<MODE, NORM, XATTN, FP8, true, NB, ROLL>), dim3(grid), dim3(KM_NT), smem, stream, p);
+            hipLaunchKernelGGL((emmax_decode_km_kernel<MODE, NORM, XATTN, WF, true, NB, ROLL>), dim3(grid), dim3(KM_NT), smem, stream, p);
             return hipGetLastError() == hipSuccess ? 0 : -4;
         }
     }
-    hipLaunchKernelGGL((emmax_decode_km_kernel<MODE, NORM, XATTN, FP8, false, NB, ROLL>), dim3(grid), dim3(KM_NT), smem, stream, p);
+    hipLaunchKernelGGL((emmax_decode_km_kernel<MODE, NORM, XATTN, WF, false, NB, ROLL>), dim3(grid), dim3(KM_NT), smem, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
-template <int MODE, bool NORM, bool XATTN, bool FP8>
+template <int MODE, bool NORM, bool XATTN, int WF>
 int km_launch_t(const GemvParams& p, int B, hipStream_t stream, int* grid_out) {
-    if (emmax_tune().km_roll)
-        return B <= 8 ? km_launch_nb<MODE, NORM, XATTN, FP8, 8, true>(p, B, stream, grid_out) : km_launch_nb<MODE, NORM, XATTN, FP8, 16, true>(p, B, stream, grid_out);
-    return B <= 8 ? km_launch_nb<MODE, NORM, XATTN, FP8, 8, false>(p, B, stream, grid_out) : km_launch_nb<MODE, NORM, XATTN, FP8, 16, false>(p, B, stream, grid_out);
+    if constexpr (WF == W_MX4 && XATTN) {   // split partials of 9-16 rows x K do not fit the LDS stage: those batches exist in the one-split form only
+        return B <= 8 ? km_launch_nb<MODE, NORM, XATTN, WF, 8, false>(p, B, stream, grid_out) : -2;
+    } else {
+        if constexpr (WF != W_MX4) {   // (the MX4 form always refills step by step: one instantiation per batch width)
+            if (emmax_tune().km_roll)
+                return B <= 8 ? km_launch_nb<MODE, NORM, XATTN, WF, 8, true>(p, B, stream, grid_out) : km_launch_nb<MODE, NORM, XATTN, WF, 16, true>(p, B, stream, grid_out);
+        }
+        return B <= 8 ? km_launch_nb<MODE, NORM, XATTN, WF, 8, false>(p, B, stream, grid_out) : km_launch_nb<MODE, NORM, XATTN, WF, 16, false>(p, B, stream, grid_out);
+    }
 }
 
 // exact numerics (GemvParams::exact), batch 3-8: the EX forms
 int km_launch_mode_x(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out) {
     switch (mode) {
-        case GEMV_QKV: return km_launch_nb<GEMV_QKV, true, false, false, 16, false, true>(p, B, stream, grid_out);
+        case GEMV_QKV: return km_launch_nb<GEMV_QKV, true, false, W_BF16, 16, false, true>(p, B, stream, grid_out);
         case GEMV_RESID:
             if (p.attn_part && p.K != p.Hq * 128) return -2;
-            return p.attn_part ? km_launch_nb<GEMV_RESID, false, true, false, 16, false, true>(p, B, stream, grid_out)
-                               : km_launch_nb<GEMV_RESID, false, false, false, 16, false, true>(p, B, stream, grid_out);
-        case GEMV_GATEUP: return km_launch_nb<GEMV_GATEUP, true, false, false, 16, false, true>(p, B, stream, grid_out);
-        case GEMV_LMHEAD: return km_launch_nb<GEMV_LMHEAD, true, false, false, 16, false, true>(p, B, stream, grid_out);
+            return p.attn_part ? km_launch_nb<GEMV_RESID, false, true, W_BF16, 16, false, true>(p, B, stream, grid_out)
+                               : km_launch_nb<GEMV_RESID, false, false, W_BF16, 16, false, true>(p, B, stream, grid_out);
+        case GEMV_GATEUP: return km_launch_nb<GEMV_GATEUP, true, false, W_BF16, 16, false, true>(p, B, stream, grid_out);
+        case GEMV_LMHEAD: return km_launch_nb<GEMV_LMHEAD, true, false, W_BF16, 16, false, true>(p, B, stream, grid_out);
         default: return -2;
     }
 }
 
-template <bool FP8>
+template <int WF>
 int km_launch_mode(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out) {
     switch (mode) {
-        case GEMV_QKV: return km_launch_t<GEMV_QKV, true, false, FP8>(p, B, stream, grid_out);
+        case GEMV_QKV: return km_launch_t<GEMV_QKV, true, false, WF>(p, B, stream, grid_out);
         case GEMV_RESID:
             if (p.attn_part && p.K != p.Hq * 128) return -2;
-            if constexpr (!FP8) {
+            if constexpr (WF == W_BF16) {
                 // the bf16 o-proj with the split merge stays on decode_mfma.hip (12.5 against 15.4 us at B = 8: the merge of 8 rows
                 // queues behind this kernel's 16 KiB weight heads); with fp8 weights this kernel is the faster one (10.3 against 10.8)
                 if (p.attn_part) return -2;
-                return km_launch_t<GEMV_RESID, false, false, FP8>(p, B, stream, grid_out);
+                return km_launch_t<GEMV_RESID, false, false, WF>(p, B, stream, grid_out);
             } else {
-                return p.attn_part ? km_launch_t<GEMV_RESID, false, true, FP8>(p, B, stream, grid_out) : km_launch_t<GEMV_RESID, false, false, FP8>(p, B, stream, grid_out);
+                return p.attn_part ? km_launch_t<GEMV_RESID, false, true, WF>(p, B, stream, grid_out) : km_launch_t<GEMV_RESID, false, false, WF>(p, B, stream, grid_out);
             }
-        case GEMV_GATEUP: return km_launch_t<GEMV_GATEUP, true, false, FP8>(p, B, stream, grid_out);
-        case GEMV_LMHEAD: return km_launch_t<GEMV_LMHEAD, true, false, FP8>(p, B, stream, grid_out);
-        case GEMV_PLAIN: return km_launch_t<GEMV_PLAIN, false, false, FP8>(p, B, stream, grid_out);
+        case GEMV_GATEUP: return km_launch_t<GEMV_GATEUP, true, false, WF>(p, B, stream, grid_out);
+        case GEMV_LMHEAD: return km_launch_t<GEMV_LMHEAD, true, false, WF>(p, B, stream, grid_out);
+        case GEMV_PLAIN: return km_launch_t<GEMV_PLAIN, false, false, WF>(p, B, stream, grid_out);
         default: return -2;
     }
 }
@@ -673,9 +823,15 @@ int decode_km_init() {
 #define KM_SET3(M, N_, X, F, R, NB_) KM_SET4(M, N_, X, F, R, NB_, false); KM_SET4(M, N_, X, F, R, NB_, true)
 #define KM_SET2(M, N_, X, F, R) KM_SET3(M, N_, X, F, R, 8); KM_SET3(M, N_, X, F, R, 16)
 #define KM_SET1(M, N_, X, F) KM_SET2(M, N_, X, F, false); if (M == GEMV_RESID) KM_SET2(M, N_, X, F, true)
-#define KM_SET(M, N_, X) KM_SET1(M, N_, X, false); KM_SET1(M, N_, X, true)
-    KM_SET(GEMV_QKV, true, false); KM_SET1(GEMV_RESID, false, true, true); KM_SET(GEMV_RESID, false, false); KM_SET(GEMV_GATEUP, true, false);
+#define KM_SET(M, N_, X) KM_SET1(M, N_, X, W_BF16); KM_SET1(M, N_, X, W_FP8)
+    KM_SET(GEMV_QKV, true, false); KM_SET1(GEMV_RESID, false, true, W_FP8); KM_SET(GEMV_RESID, false, false); KM_SET(GEMV_GATEUP, true, false);
     KM_SET(GEMV_LMHEAD, true, false); KM_SET(GEMV_PLAIN, false, false);
+    // the MX4 forms (no rolling variant)
+#define KM_SETQ(M, N_, X, R) KM_SET4(M, N_, X, W_MX4, R, 8, false); KM_SET4(M, N_, X, W_MX4, R, 16, false)
+    KM_SETQ(GEMV_QKV, true, false, false); KM_SETQ(GEMV_GATEUP, true, false, false); KM_SETQ(GEMV_LMHEAD, true, false, false); KM_SETQ(GEMV_PLAIN, false, false, false);
+    KM_SETQ(GEMV_RESID, false, false, false); KM_SETQ(GEMV_RESID, false, false, true);
+    KM_SET4(GEMV_RESID, false, true, W_MX4, false, 8, false); KM_SET4(GEMV_RESID, false, true, W_MX4, true, 8, false);   // (the split merge: 1-8 rows)
+#undef KM_SETQ
 #undef KM_SET
 #undef KM_SET1
 #undef KM_SET2
@@ -683,14 +839,15 @@ int decode_km_init() {
 #undef KM_SET4
 #define KD_SET(F, R, NB_) \
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)emmax_decode_kmd_kernel<F, R, NB_>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)
-    KD_SET(false, false, 8); KD_SET(true, false, 8); KD_SET(false, true, 8); KD_SET(true, true, 8);
-    KD_SET(false, false, 16); KD_SET(true, false, 16); KD_SET(false, true, 16); KD_SET(true, true, 16);
+    KD_SET(W_BF16, false, 8); KD_SET(W_FP8, false, 8); KD_SET(W_BF16, true, 8); KD_SET(W_FP8, true, 8);
+    KD_SET(W_BF16, false, 16); KD_SET(W_FP8, false, 16); KD_SET(W_BF16, true, 16); KD_SET(W_FP8, true, 16);
+    KD_SET(W_MX4, false, 8); KD_SET(W_MX4, true, 8); KD_SET(W_MX4, false, 16); KD_SET(W_MX4, true, 16);
 #undef KD_SET
 #define KX_SET(M, N_, X) \
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)emmax_decode_km_kernel<M, N_, X, false, M == GEMV_RESID, 16, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)emmax_decode_km_kernel<M, N_, X, W_BF16, M == GEMV_RESID, 16, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)
     KX_SET(GEMV_QKV, true, false); KX_SET(GEMV_RESID, false, true); KX_SET(GEMV_RESID, false, false); KX_SET(GEMV_GATEUP, true, false); KX_SET(GEMV_LMHEAD, true, false);
 #undef KX_SET
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)emmax_decode_kmd_kernel<false, true, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)emmax_decode_kmd_kernel<W_BF16, true, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
     done = (e == hipSuccess) ? 0 : -4;
     return done;
 }
@@ -707,23 +864,43 @@ int launch_repack_km(const void* src, int ld, void* dst, int N, int K, int perm,
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
+static bool mx4_shape_ok(int ld, int N, int K, int perm, int head_dim) {
+    if (N < 16 || N % 16 || K < 128 || K % 128 || ld % 8 || ld < K) return false;
+    if (perm == 1 && (head_dim < 16 || head_dim % 16 || N % head_dim)) return false;
+    if (perm == 2 && N % 32) return false;
+    return perm >= 0 && perm <= 2;
+}
+int launch_quant_mx4(const void* src, int ld, void* tiles, void* scales, int N, int K, int perm, int head_dim, hipStream_t stream) {
+    if (!mx4_shape_ok(ld, N, K, perm, head_dim)) return -1;
+    hipLaunchKernelGGL(emmax_quant_mx4_kernel, dim3(2048), dim3(256), 0, stream, (const bf16_t*)src, ld, (uint32_t*)tiles, (uint32_t*)scales, N, K, perm, head_dim);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+int launch_dequant_mx4(const void* tiles, const void* scales, void* dst, int ld, int N, int K, int perm, int head_dim, hipStream_t stream) {
+    if (!mx4_shape_ok(ld, N, K, perm, head_dim)) return -1;
+    hipLaunchKernelGGL(emmax_dequant_mx4_kernel, dim3(2048), dim3(256), 0, stream, (const uint32_t*)tiles, (const uint32_t*)scales, (bf16_t*)dst, ld, N, K, perm, head_dim);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
 // p.W: the km copy of the matrix (launch_repack_km; fp8: decode_mfma.hip's e4m3 tiles of the permuted rows + p.wscale in the same
 // row order).  -2: shape outside this kernel (K % 256, K > 4096, more than 8 tiles per block) -- the caller uses decode_mfma.hip.
 int launch_decode_km(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out) {
     if (B < 1 || B > EMMAX_MAX_DECODE_BATCH) return -2;
+    if (B > 16 && p.w4_scales) return -2;   // MXFP4 tiles: this file's kernels only (1-16 rows)
     if (B > 16) return launch_decode_kmp(mode, p, B, stream, grid_out);   // two batch tiles: decode_kmp.hip
     if (decode_km_init() != 0) return -4;
     if (p.exact) {   // exact numerics: batch <= 8 (two terms per batch row in the sixteen MFMA columns), bf16 weights
-        if (B > 8 || p.wscale) return -2;
+        if (B > 8 || p.wscale || p.w4_scales) return -2;
         // RESID launches without split partials (fp32 rows in p.x): the o-proj behind a one-split attention launch on the K-split kernel when its K fits,
         // the down projection (and any other K) on the phased kernel
-        if (mode == GEMV_RESID && !p.attn_part && (p.K % (KM_WAVES * 32) || p.K > KM_WAVES * KM_STEPS * 32)) return kmd_launch<false, 16, true>(p, B, stream);
+        if (mode == GEMV_RESID && !p.attn_part && (p.K % (KM_WAVES * 32) || p.K > KM_WAVES * KM_STEPS * 32)) return kmd_launch<W_BF16, 16, true>(p, B, stream);
         return km_launch_mode_x(mode, p, B, stream, grid_out);
     }
     if (mode == GEMV_RESID && !p.attn_part && p.K > KM_WAVES * KM_STEPS * 32) {   // the down projection: two K phases (natural row order copy)
+        if (p.w4_scales) return B <= 8 ? kmd_launch<W_MX4, 8>(p, B, stream) : kmd_launch<W_MX4, 16>(p, B, stream);   // (no other kernel reads these tiles: no switch)
         if (!emmax_tune().km_down) return -2;   // A/B partner: decode_mfma.hip
-        if (B <= 8) return p.wscale ? kmd_launch<true, 8>(p, B, stream) : kmd_launch<false, 8>(p, B, stream);
-        return p.wscale ? kmd_launch<true, 16>(p, B, stream) : kmd_launch<false, 16>(p, B, stream);
+        if (B <= 8) return p.wscale ? kmd_launch<W_FP8, 8>(p, B, stream) : kmd_launch<W_BF16, 8>(p, B, stream);
+        return p.wscale ? kmd_launch<W_FP8, 16>(p, B, stream) : kmd_launch<W_BF16, 16>(p, B, stream);
     }
-    return p.wscale ? km_launch_mode<true>(mode, p, B, stream, grid_out) : km_launch_mode<false>(mode, p, B, stream, grid_out);
+    if (p.w4_scales) return km_launch_mode<W_MX4>(mode, p, B, stream, grid_out);
+    return p.wscale ? km_launch_mode<W_FP8>(mode, p, B, stream, grid_out) : km_launch_mode<W_BF16>(mode, p, B, stream, grid_out);
 }

@@ -119,7 +119,8 @@ int emmax_slots_open(emmax_session* s, int n_slots, emmax_stream stream) {
     if (s->beam.K) return fail(EMMAX_ERR_STATE, "request slots are not served while beams are on (emmax_session_clear_beams)");
     const int max_rows = s->exact ? EMMAX_MAX_DECODE_BATCH : model_max_decode_batch(s->m);
     if (n_slots < 1 || n_slots > s->max_batch || n_slots > max_rows)
-        return fail(EMMAX_ERR_INVALID, "%d slots outside 1..min(max_batch=%d, %d)", n_slots, s->max_batch, max_rows);
+        return fail(EMMAX_ERR_INVALID, "%d slots outside 1..min(max_batch=%d, %d)%s", n_slots, s->max_batch, max_rows,
+                    (s->m->mx4 && n_slots >= 1 && n_slots <= s->max_batch) ? ": the limit of a model with MXFP4 decode weights" : "");
     if (n_slots >= EMMAX_MFMA_MIN_BATCH && !s->m->aux_built)
         return fail(EMMAX_ERR_STATE, "%d slots decode on the fragment-major weight copies: call emmax_model_build_aux first", n_slots);
     StreamScope sc(s, stream);

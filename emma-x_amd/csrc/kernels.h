@@ -248,6 +248,7 @@ struct GemvParams {
     int exact;
     long long kv24;         // exact numerics: > 0 = the K / V caches are 24-bit (common.h: x24) -- kcache / vcache point at the bf16 plane of kv24 elements,
                             //   the 8-bit extension plane follows it; 0 = fp32 rows
+    const void* w4_scales;  // decode_km.hip, non-null: W holds MXFP4 tiles (launch_quant_mx4) and this is their scale stream; null: bf16 / fp8 (wscale)
 };
 // (where the QKV epilogues put the new K / V rows: gemv_kv_row / gemv_kv_store_x, decode_epilogue.h -- device code, this is also a host header)
 // staged_out (optional): 1 when decode.hip's own LDS-staged kernel served the call, 0 when decode_ks.hip took it.
@@ -484,6 +485,13 @@ int launch_set_tokens(int32_t* cur_tok, const int32_t* toks, int B, int32_t* don
 // (gate, up) pairs inside one 16-row tile).  -2: shape outside the kernel, the caller falls back to launch_decode_mfma.
 int launch_repack_km(const void* src, int ld, void* dst, int N, int K, int perm, int head_dim, hipStream_t stream);
 int launch_decode_km(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out = nullptr);
+// MXFP4 (OCP MX v1.0) copy of a row-major bf16 matrix in the km row order (perm / head_dim as launch_repack_km): blocks of 32 consecutive k of one
+// row share the exponent e = floor(log2(amax)) - 2 clamped to [-127, 127] (code e + 127; an all-zero block: code 127), elements are w / 2^e rounded
+// to nearest even onto +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}, saturating.  tiles: N K / 2 bytes (1 KiB = 16 rows x 128 k, lane-major: emmax_decode_km_kernel),
+// scales: N K / 32 bytes (one dword of four codes per (tile, row)).  N % 16 == 0, K % 128 == 0, ld % 8 == 0.  launch_dequant_mx4 writes the values
+// the copy holds back as bf16 rows (exact), each at the source row the permutation took it from.
+int launch_quant_mx4(const void* src, int ld, void* tiles, void* scales, int N, int K, int perm, int head_dim, hipStream_t stream);
+int launch_dequant_mx4(const void* tiles, const void* scales, void* dst, int ld, int N, int K, int perm, int head_dim, hipStream_t stream);
 bool decode_km_enabled();
 int decode_km_init();   // raise the dynamic-LDS limit of every instantiation (call once, outside graph capture)
 // decode_kmp.hip: batch 17-32 (two batch tiles per weight tile, the K slice in phases), bf16 weights, same copies; launch_decode_km routes there

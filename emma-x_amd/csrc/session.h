@@ -84,6 +84,8 @@ struct ProjW {
                      // lm-head: that kernel reads the natural order -- the same pointer as fm
     bf16* r8;        // fp8 mode: the same e4m3 values as rows in the GEMV's span order (batch 1-2)
     float *sc, *km_sc;      // fp8 mode: per-row scales (null otherwise), and those of km in its row order
+    void *q4, *q4s;         // MXFP4 mode: e2m1 tiles in km's row order and their e8m0 scale stream (launch_quant_mx4); null otherwise.  rm then holds the
+                            // de-quantised values: the prefill evaluates the model the decode step streams
     int gemv_mode, f8bit;   // GEMV_QKV / GEMV_RESID / GEMV_GATEUP / GEMV_LMHEAD, and its bit of the tuning switch fp8_gemv
 };
 struct LayerW {
@@ -101,7 +103,8 @@ struct emmax_model {
     bf16 *pj1_w, *pj1_b, *pj2_w, *pj2_b, *pj3_w, *pj3_b;
     bf16 *embed, *final_norm;
     ProjW lm_head_w = {};
-    bool fp8 = false;
+    bool fp8 = false;            // decode_fp8 == 1: e4m3 decode copies
+    bool mx4 = false;            // decode_fp8 == 2: MXFP4 decode copies (decode_km.hip only: batches 1-16)
     bool ln_folded = false;      // the ViT LayerNorms are folded into the qkv / fc1 weights (tuning switch gemm_lnfuse at finalize)
     bool aux_built = false;      // the batch >= 3 copies exist (fp8 models: always, they are part of the main arena)
     bool aux_ab = false;         // ... including decode_mfma.hip's qkv / gate-up pair

@@ -19,7 +19,7 @@ static int fp8_gemv_mask(int B) {
 
 // One projection of the step (ProjW, session.h).  B <= 2: per-lane dot-product GEMV over the row-major weights (fp8 mode: over the e4m3 row
 // copy w.r8); B >= 3: MFMA over the fragment-major copy.  w.km / w.km_sc: the matrix in decode_km.hip's layout (null: that kernel does not
-// serve this projection)
+// serve this projection).  w.q4 / w.q4s (MXFP4 models): the 4-bit tiles and their scale stream -- decode_km.hip at every batch 1-16, nothing else
 // via (optional): which launcher family took the call (include/emmax.h: EMMAX_VIA_*), what emmax_op_decode_stage reports
 static int launch_proj(const ProjW& w, GemvParams& p, int B, hipStream_t st, int* grid_out, int* via = nullptr) {
     const int mode = w.gemv_mode;
@@ -39,6 +39,14 @@ static int launch_proj(const ProjW& w, GemvParams& p, int B, hipStream_t st, int
             *via = EMMAX_VIA_KM;   // (exact numerics: at most 8 rows per launch, never decode_kmp.hip)
         }
         return r == -2 ? fail(EMMAX_ERR_INVALID, "exact numerics: no two-term kernel for this projection (batch %d, K %d)", B, p.K) : r;
+    }
+    if (w.q4) {   // MXFP4 copy: decode_km.hip at every batch 1-16, no other kernel reads the tiles (the model's shapes were checked at emmax_model_create)
+        GemvParams q = p;
+        q.W = w.q4;
+        q.w4_scales = w.q4s;
+        const int r = B <= 16 ? launch_decode_km(mode, q, B, st, grid_out) : -2;
+        *via = EMMAX_VIA_KM;
+        return r == -2 ? fail(EMMAX_ERR_INVALID, "MXFP4 decode weights: no kernel for this projection (batch %d of 1-16, K %d)", B, p.K) : r;
     }
     if (B < EMMAX_MFMA_MIN_BATCH && w.sc && w.r8 && (fp8_gemv_mask(B) & w.f8bit) && decode_gemv_fp8_fits(B, p.K)) {
         p.W = w.r8;
@@ -75,6 +83,10 @@ static int launch_proj(const ProjW& w, GemvParams& p, int B, hipStream_t st, int
 // most 8 tiles per block (N <= 32768), the down projection within four phases of 12 fragments per wave (K <= 12288).
 int model_max_decode_batch(const emmax_model* m) {
     const auto& c = m->cfg;
+    // MXFP4 tiles: decode_km.hip alone (check_config, model.hip, holds the shapes to it) -- 16 rows, or 8 under the one-split rule below.  The rule reads
+    // tuning switches, so the answer can shrink after a session was created: emmax_session_bytes / create check it once, run_prefill and emmax_slots_open
+    // again (a step itself is not re-checked: flipping attn_direct / attn_nsplit between a prefill and its decode steps ends in launch_proj's refusal)
+    if (m->mx4) return (emmax_tune().attn_direct == 0 || decode_attn_nsplit(9, c.n_kv_heads) != 1) ? 8 : 16;
     const bool k_ok = m->H % 256 == 0 && m->H <= 4096 && m->q_dim % 256 == 0 && m->q_dim <= 4096;
     const bool n_ok = m->qkv_dim % 16 == 0 && m->qkv_dim <= 32768 && 2 * m->inter_p <= 32768 && m->vocab_p <= 32768 && m->H % 16 == 0 && c.head_dim % 16 == 0;
     const int kd = m->fp8 ? 64 : 32;
@@ -415,7 +427,7 @@ static int run_qkv0_with_embed(emmax_session* s, int B, hipStream_t st) {
 int run_decode_step(emmax_session* s, int B, hipStream_t st) {
     emmax_model* m = s->m;
     // batch 1-2 on bf16 weights: the embedding row is read by layer 0's qkv launch itself (K-split kernel) -- one launch fewer
-    const bool fold_embed = B < EMMAX_MFMA_MIN_BATCH && !m->fp8 && decode_ks_enabled() && m->H % 64 == 0 && m->H <= 12288 &&
+    const bool fold_embed = B < EMMAX_MFMA_MIN_BATCH && !m->fp8 && !m->mx4 && decode_ks_enabled() && m->H % 64 == 0 && m->H <= 12288 &&
                             emmax_tune().fold_embed != 0;
     if (!fold_embed) KCHK(launch_decode_embed(s->cur_tok, m->embed, s->dh, B, m->H, m->vocab, st, s->exact ? s->dh32 : h32_of(s)));
     for (int li = 0; li < m->cfg.n_layers; ++li)

@@ -43,7 +43,7 @@ class ConfigC(C.Structure):
     ]
 
 
-ABI_VERSION = 10   # EMMAX_ABI_VERSION of include/emmax.h this binding was written against
+ABI_VERSION = 11   # EMMAX_ABI_VERSION of include/emmax.h this binding was written against
 
 # name -> (restype, argtypes): exactly the entry points of include/emmax.h
 SIGNATURES = {
@@ -107,6 +107,9 @@ SIGNATURES = {
     "emmax_op_gemv": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "emmax_op_resize_bicubic_u8": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp]),
     "emmax_op_quant_fm8": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp]),
+    "emmax_op_quant_mxfp4": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "emmax_op_dequant_mxfp4": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "emmax_op_gemm_small_mxfp4": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "emmax_op_gemm_small_fp8": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "emmax_op_quant_rm8": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp]),
     "emmax_op_gemv_fp8": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),

@@ -71,6 +71,16 @@ class LlmConfig:
     max_position: int = 2048  # llm_max_length (configuration_prismatic.py:84)
 
 
+# decode_weight_dtype -> emmax_config.decode_fp8 (include/emmax.h)
+DECODE_WEIGHT_DTYPES = {"bf16": 0, "fp8": 1, "mxfp4": 2}
+
+
+def check_decode_weight_dtype(name: str) -> str:
+    if name not in DECODE_WEIGHT_DTYPES:
+        raise ValueError(f"decode_weight_dtype must be one of {sorted(DECODE_WEIGHT_DTYPES)}, got {name!r}")
+    return name
+
+
 @dataclass
 class EmmaXConfig:
     towers: List[TowerConfig]
@@ -85,7 +95,8 @@ class EmmaXConfig:
     llm_backbone_id: str = "llama2-7b-pure"
     arch_specifier: str = "no-align+fused-gelu-mlp"
     image_resize_strategy: str = "resize-naive"
-    # MI355X extension (BASELINE config 5): "fp8" streams an e4m3 per-row-scaled copy of the LLM projections in decode
+    # MI355X extension (BASELINE config 5): "fp8" streams an e4m3 per-row-scaled copy of the LLM projections in decode; "mxfp4" an OCP MXFP4
+    # copy (e2m1 elements, one e8m0 scale per 32 elements; decode batches 1-16) -- prefill and decode then both evaluate the quantised model
     decode_weight_dtype: str = "bf16"
 
     # --- derived ---

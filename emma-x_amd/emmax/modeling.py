@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from .actions import ActionTokenizer, token_ids_to_actions, unnormalize
-from .config import EmmaXConfig, default_norm_stats
+from .config import EmmaXConfig, check_decode_weight_dtype, default_norm_stats
 from .engine import EmmaxEngine
 from .policy_parser import Solver
 from .processing import BatchFeature, EmmaXImageProcessor
@@ -105,12 +105,17 @@ class EmmaXForActionPrediction:
     @classmethod
     def from_pretrained(cls, path: str, torch_dtype: torch.dtype = torch.bfloat16, attn_implementation: Optional[str] = None,
                         low_cpu_mem_usage: bool = True, trust_remote_code: bool = True, load_in_8bit: bool = False,
-                        load_in_4bit: bool = False, dtype: Optional[torch.dtype] = None, **_) -> "EmmaXForActionPrediction":
+                        load_in_4bit: bool = False, dtype: Optional[torch.dtype] = None, decode_weight_dtype: Optional[str] = None,
+                        **_) -> "EmmaXForActionPrediction":
         """HF directory (config.json + *.safetensors [+ dataset_statistics.json]) or a native Prismatic `.pt` file.
         (`dtype=` is the transformers >= 5 spelling of `torch_dtype=`; `config=` passed by the Auto classes is ignored: the
-        directory is re-read through EmmaXConfig.from_pretrained.)"""
+        directory is re-read through EmmaXConfig.from_pretrained.)  `decode_weight_dtype`: "bf16" | "fp8" | "mxfp4", the format the decode
+        step streams the LLM projections in (None: the config's, bf16)."""
         if load_in_8bit or load_in_4bit:
-            raise NotImplementedError("bitsandbytes quantised loading is outside the MI355X hot path")
+            raise NotImplementedError("bitsandbytes quantised loading (int8 / NF4 code books) is outside the MI355X hot path and no other format is "
+                                      "substituted for it; the native quantised decode weights are decode_weight_dtype=\"fp8\" or \"mxfp4\"")
+        if decode_weight_dtype is not None:
+            check_decode_weight_dtype(decode_weight_dtype)
         torch_dtype = dtype if dtype is not None else torch_dtype
         if torch_dtype not in (torch.bfloat16, None, "bfloat16", "auto"):
             raise ValueError("the MI355X path computes in bf16 (fp32 accumulate); pass torch_dtype=torch.bfloat16")
@@ -140,15 +145,20 @@ class EmmaXForActionPrediction:
             sd = load_hf_state_dict(path)
             tok_dir = path
         validate_state_dict(sd, cfg)
+        if decode_weight_dtype is not None:
+            cfg.decode_weight_dtype = decode_weight_dtype
         model = cls(cfg, sd)
         model.tokenizer = load_tokenizer(tok_dir, cfg)   # the native class owns its tokenizer (prismatic.py:630); None if no files
         return model
 
     @classmethod
     def from_synthetic(cls, config: Optional[EmmaXConfig] = None, seed: int = 0, device: str = "cuda:0", planted: bool = False,
-                       **engine_kw) -> "EmmaXForActionPrediction":
-        """Random-init weights with the real names/shapes, generated directly on `device` (no checkpoint offline)."""
+                       decode_weight_dtype: Optional[str] = None, **engine_kw) -> "EmmaXForActionPrediction":
+        """Random-init weights with the real names/shapes, generated directly on `device` (no checkpoint offline).
+        `decode_weight_dtype`: "bf16" | "fp8" | "mxfp4" (None: the config's)."""
         config = config or EmmaXConfig.emma_x_7b()
+        if decode_weight_dtype is not None:
+            config.decode_weight_dtype = check_decode_weight_dtype(decode_weight_dtype)
         if not config.norm_stats:   # synthetic weights come with synthetic (made-up) statistics; a checkpoint never does
             config.norm_stats = default_norm_stats()
         sd = synthetic_state_dict(config, seed=seed, device=device, dtype=torch.bfloat16, planted=planted)

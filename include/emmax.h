@@ -41,8 +41,9 @@ extern "C" {
  *   (emmax_session_set_processing, emmax_session_set_scores and the calls around them), the workspace grew the per-row processing state and
  *   prompt ids;  9: beam search inside the decode step (emmax_session_set_beams and the calls around it), the workspace grew the beam
  *   state and trace; the paged KV region did not grow;  10: emmax_op_decode_stage / emmax_op_decode_kv_read (one decode stage through the step's
- *   own dispatch), the workspace grew that op's per-row scratch. */
-#define EMMAX_ABI_VERSION 10
+ *   own dispatch), the workspace grew that op's per-row scratch;  11: emmax_config.decode_fp8 = 2 selects MXFP4 decode weights (the struct keeps
+ *   its layout), emmax_op_quant_mxfp4 / emmax_op_dequant_mxfp4 / emmax_op_gemm_small_mxfp4. */
+#define EMMAX_ABI_VERSION 11
 
 typedef enum emmax_status {
     EMMAX_OK = 0,
@@ -74,8 +75,12 @@ typedef struct emmax_config {
     int32_t hidden, inter, n_layers, n_heads, n_kv_heads, head_dim, vocab;
     float rms_eps, rope_theta;
     int32_t bos_id, eos_id, pad_id;
-    int32_t decode_fp8;                /* 1: the decode projections stream an fp8-e4m3 (per-row scale) weight copy, de-quantised
-                                          in registers (BASELINE config 5); 0: bf16 weights (the headline path)     */
+    int32_t decode_fp8;                /* the decode weight format.  0: bf16 weights (the headline path); 1: the decode projections stream an
+                                          fp8-e4m3 (per-row scale) weight copy, de-quantised in registers (BASELINE config 5); 2: MXFP4 (OCP MX
+                                          v1.0: e2m1 elements, one e8m0 scale per 32 elements along K; 4.25 bits per weight), widened to bf16 in
+                                          registers -- decode batches 1-16, LLM shapes with hidden and n_heads * head_dim in multiples of 1024
+                                          up to 4096 and an intermediate size % 128 == 0 in 4097..12288 (emmax_model_create refuses others); the
+                                          prefill reads the de-quantised values, so prefill and decode evaluate the same quantised model        */
 } emmax_config;
 
 const char* emmax_version(void);
@@ -118,14 +123,19 @@ int emmax_model_bind_weight(emmax_model* m, const char* hf_key, const void* ptr_
 int64_t emmax_model_arena_bytes(const emmax_model* m);
 /* rows of one decode batch / slot set this model can run: 64 (bf16 or fp8 weights) when every LLM projection is a shape the K-split
  * MFMA kernels take (K % 256 == 0 and <= 4096, N <= 32768, intermediate size % 32 (fp8: % 64) == 0 and <= 11264: LLaMA-2-7B is), else 8 (round 6;
- * round 5: 32; rounds 1-4: 8).  Exact-numerics sessions: 64 whatever the shapes (8 rows per launch, larger batches in chunks). */
+ * round 5: 32; rounds 1-4: 8).  Exact-numerics sessions: 64 whatever the shapes (8 rows per launch, larger batches in chunks).
+ * MXFP4 models (decode_fp8 = 2): 16 -- decode_km.hip is the only kernel family that reads the 4-bit tiles -- or 8 when a batch of nine rows would
+ * split the attention (the o-proj then reads split partials, which its 16-row form does not take); emmax_session_bytes / create refuse a larger
+ * max_batch for such a model, naming the format.  The one-split rule reads the tuning switches attn_direct / attn_nsplit: the limit is checked when a
+ * session is sized and created and again at every prefill and emmax_slots_open, not inside a step -- changing those switches between a prefill of
+ * 9-16 rows and its decode steps makes the step fail with EMMAX_ERR_INVALID (no other kernel reads the 4-bit tiles: there is no fall-back). */
 int emmax_model_max_decode_batch(const emmax_model* m);
 int emmax_model_finalize(emmax_model* m, void* arena_dev, int64_t arena_bytes, emmax_stream stream);
 /* bf16 models: decode batches >= 3 stream the LLM projections from MFMA-fragment-major copies that a model serving batches 1-2
  * never reads.  They live in a SECOND caller-owned arena, built on demand from the finalized main arena (no bound tensors
  * needed): 13.2 GB at 7B (main arena 15.1 GB; with the tuning switch km = 0 at build time decode_mfma.hip's qkv / gate-up pair is
  * added, +9 GB).  Until it is built, emmax_prefill / emmax_slots_open with B >= 3 return EMMAX_ERR_STATE.  fp8 models keep every
- * e4m3 copy in the main arena: aux_bytes is 0 and build_aux a no-op. */
+ * e4m3 copy in the main arena, MXFP4 models their 4-bit copy: aux_bytes is 0 and build_aux a no-op. */
 int64_t emmax_model_aux_bytes(const emmax_model* m);
 int emmax_model_build_aux(emmax_model* m, void* aux_arena_dev, int64_t aux_bytes, emmax_stream stream);
 
@@ -472,6 +482,19 @@ int emmax_op_resize_bicubic_u8(const uint8_t* src_dev, int B, int H, int W, uint
  * the K-split kernels over the same tiles (decode_km.hip 9-16: K % 512 == 0 up to 4096 or the phased form above; decode_kmp.hip 17-32:
  * K % 64 == 0, K >= 512, the widest wave share <= 1408 elements), EMMAX_ERR_INVALID outside those shapes. */
 int emmax_op_quant_fm8(const void* W_dev, int ld, void* W8_fm_out_dev, float* scales_out_dev, int N, int K, emmax_stream stream);
+/* MXFP4 copy of a bf16 weight [N, ld] as emmax_model_finalize builds it for decode_fp8 = 2, and its way back.  Blocks of 32 consecutive k of
+ * one row share the exponent e = floor(log2(amax)) - 2 clamped to [-127, 127], stored as the e8m0 code e + 127 (an all-zero block: code 127);
+ * elements are w / 2^e rounded to nearest, ties to even, onto +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}, saturating at 6.  tiles_out: N K / 2 bytes --
+ * 1 KiB tiles of 16 rows x 128 k in decode_km.hip's row order (perm / perm_hd as emmax_op_repack_km), lane l = row l & 15, dword j of its 16
+ * bytes = elements 8 (l >> 4) .. + 8 of the tile's j-th 32 k, element i in nibble i; scales_out: N K / 32 bytes, one dword of four codes per
+ * (tile, row) in the tiles' order.  N % 16 == 0, K % 128 == 0, ld % 8 == 0.  emmax_op_dequant_mxfp4 writes the values the copy holds as bf16
+ * (exact: one mantissa bit times a power of two; zeros are +0) to the rows of W_out [N, ld] the permutation took them from. */
+int emmax_op_quant_mxfp4(const void* W_dev, int ld, void* tiles_out_dev, void* scales_out_dev, int N, int K, int perm, int perm_hd, emmax_stream stream);
+int emmax_op_dequant_mxfp4(const void* tiles_dev, const void* scales_dev, void* W_out_dev, int ld, int N, int K, int perm, int perm_hd, emmax_stream stream);
+/* the plain projection over such a copy (perm 0) on the kernels the decode step runs, 1 <= B <= 16: y bf16 [B, N] = x bf16 [B, K] W^T with the tiles
+ * widened in registers.  K % 1024 == 0 and K <= 4096 (the K-split kernel; the phased kernel of the down projection is reached through
+ * emmax_op_decode_stage); N % 16 == 0, N <= 32768.  Test hook: pins what the hardware widening does on every scale code. */
+int emmax_op_gemm_small_mxfp4(const void* x_dev, const void* tiles_dev, const void* scales_dev, void* y_dev, int B, int N, int K, emmax_stream stream);
 int emmax_op_gemm_small_fp8(const void* x_dev, const void* W8_fm_dev, const float* scales_dev, void* y_dev, int B, int N, int K,
                             emmax_stream stream);
 /* Batch 3-32 decode projection on the K-split MFMA kernels (decode_km.hip up to 16 rows, decode_kmp.hip above; K > 4096: the phased kernel of the
