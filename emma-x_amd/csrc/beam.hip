@@ -11,8 +11,14 @@
 // The merge needs every row's list (a grid-wide dependency) and the copy needs the chip, not one wave, so neither pair can share a launch.
 // Every reduction has a fixed order, there are no float atomics and no atomics at all outside LDS-free code paths: two launches on the
 // same inputs agree bit for bit, eager or replayed.
+//
+// SAMPLE GROUPS (N sampled rows per prompt) fork the same way once, after the prefill, and never reorder: emmax_group_fork_kernel writes the
+// page-table rows, the rows' decode state and the copy list that emmax_beam_copy_kernel consumes; emmax_group_bcast_kernel gives the group's
+// one logit row (and prompt-history row) to its N rows.  Their steps are ordinary sampled steps: nothing here runs in them.
 #include <hip/hip_runtime.h>
 #include <math.h>
+
+#include <algorithm>
 #include <stdint.h>
 
 #include "common.h"
@@ -399,6 +405,39 @@ __global__ void emmax_beam_pages_kernel(int32_t* pt, int rows, int max_pages, in
     pt[i] = r * step * max_pages + c;
 }
 
+// ---- sample groups: N sampled rows per prompt on the prompt's pages (include/emmax.h: emmax_session_set_sample_groups) ----
+// One wave per group.  Nothing is reordered after this fork, so there are no spares: row g N + j references the complete prompt pages of
+// row g N (where the prefill wrote them) and owns every page from the partial one on, out of its own static share r * max_pages + i.
+__global__ __launch_bounds__(EMMAX_WAVE) void emmax_group_fork_kernel(GroupForkParams p) {
+    const int g = blockIdx.x, tid = threadIdx.x, N = p.N, mp = p.max_pages, r0 = g * N;
+    const int L = p.S[g], nfull = L / 64, rem = L % 64;
+    for (int e = tid; e < N * mp; e += EMMAX_WAVE) {
+        const int j = e / mp, i = e - j * mp;
+        p.page_table[(size_t)(r0 + j) * mp + i] = (i < nfull ? r0 : r0 + j) * mp + i;
+    }
+    for (int j = tid; j < N; j += EMMAX_WAVE) {
+        const int r = r0 + j;
+        p.ctx_len[r] = L; p.done[r] = 0; p.n_out[r] = 0;
+        p.max_new[r] = 0x7fffffff;   // (as emmax_prefill_state_kernel: no token budget until a generate call sets one)
+        p.stop_m[r] = 0; p.stop_after[r] = -1;
+        const bool cp = rem > 0 && j > 0 && nfull < mp;
+        p.copy_src[r] = cp ? r0 * mp + nfull : -1;
+        p.copy_dst[r] = r * mp + nfull;
+        p.copy_ntok[r] = rem;
+    }
+}
+
+// W = 16 (rows are multiples of 16 bytes at a 16-byte aligned base) or 4 bytes per column
+template <class T>
+__global__ __launch_bounds__(256) void emmax_group_bcast_kernel(char* rows, long long row_bytes, int G, int N) {
+    const long long ncol = row_bytes / (long long)sizeof(T);
+    for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < ncol; c += (long long)gridDim.x * 256)
+        for (int g = G - 1; g >= 0; --g) {   // rows written so far lie behind (g + 1) N > g: every source is read before it is overwritten
+            const T x = *(const T*)(rows + (size_t)g * row_bytes + (size_t)c * sizeof(T));
+            for (int j = N - 1; j >= (g == 0 ? 1 : 0); --j) *(T*)(rows + ((size_t)g * N + j) * row_bytes + (size_t)c * sizeof(T)) = x;
+        }
+}
+
 // the kept hypotheses, best first: thread (g, k) walks hypothesis k of group g back through the parent table
 __global__ void emmax_beam_resolve_kernel(BeamResolveParams p) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -453,6 +492,22 @@ int launch_beam_reset(int rows, int K, float* run_score, float* fin_score, int32
 int launch_beam_pages(int32_t* pt, int rows, int max_pages, int step, hipStream_t stream) {
     const int n = rows * max_pages;
     hipLaunchKernelGGL(emmax_beam_pages_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, pt, rows, max_pages, step);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+int launch_group_fork(const GroupForkParams& p, int groups, hipStream_t stream) {
+    if (groups < 1 || p.N < 2 || (long long)groups * p.N > EMMAX_MAX_DECODE_BATCH || p.max_pages < 1) return -1;
+    for (int g = 0; g < groups; ++g)
+        if (p.S[g] < 1 || p.S[g] >= p.max_pages * 64) return -1;
+    hipLaunchKernelGGL(emmax_group_fork_kernel, dim3(groups), dim3(EMMAX_WAVE), 0, stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+int launch_group_bcast(void* rows, long long row_bytes, int groups, int N, hipStream_t stream) {
+    if (!rows || groups < 1 || N < 2 || (long long)groups * N > EMMAX_MAX_DECODE_BATCH || row_bytes < 4 || (row_bytes & 3)) return -1;
+    const bool wide = (row_bytes & 15) == 0 && ((uintptr_t)rows & 15) == 0;
+    const long long ncol = row_bytes / (wide ? 16 : 4);
+    const int blocks = (int)std::min<long long>((ncol + 255) / 256, 1024);
+    if (wide) hipLaunchKernelGGL(emmax_group_bcast_kernel<u32x4_t>, dim3(blocks), dim3(256), 0, stream, (char*)rows, row_bytes, groups, N);
+    else hipLaunchKernelGGL(emmax_group_bcast_kernel<uint32_t>, dim3(blocks), dim3(256), 0, stream, (char*)rows, row_bytes, groups, N);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 int launch_beam_resolve(const BeamResolveParams& p, hipStream_t stream) {

@@ -8,6 +8,10 @@ int emmax_last_logits(emmax_session* s, float* out, emmax_stream stream) {
     if (!s || !out) return fail(EMMAX_ERR_INVALID, "null argument");
     if (!s->prefilled) return fail(EMMAX_ERR_STATE, "prefill has not run");
     if (s->beam.K) return fail(EMMAX_ERR_STATE, "emmax_last_logits is not served while beams are on (bind a logits buffer: emmax_session_set_scores)");
+    if (s->grp_N && s->dec_steps == 0) {   // no step since the group prefill: the last logits are the groups' rows as the fork handed them out
+        HIPCHK(hipMemcpyAsync(out, s->logits, (size_t)s->cur_B * s->m->vocab * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return 0;
+    }
     return run_lm_head_step(s, s->cur_B, false, out, false, (hipStream_t)stream);
 }
 
@@ -117,6 +121,7 @@ int emmax_generate(emmax_session* s, int max_new, int stop_on_eos, int32_t* out_
 int emmax_slots_open(emmax_session* s, int n_slots, emmax_stream stream) {
     if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
     if (s->beam.K) return fail(EMMAX_ERR_STATE, "request slots are not served while beams are on (emmax_session_clear_beams)");
+    if (s->grp_N) return fail(EMMAX_ERR_STATE, "request slots are not served while sample groups are on (emmax_session_clear_sample_groups)");
     const int max_rows = s->exact ? EMMAX_MAX_DECODE_BATCH : model_max_decode_batch(s->m);
     if (n_slots < 1 || n_slots > s->max_batch || n_slots > max_rows)
         return fail(EMMAX_ERR_INVALID, "%d slots outside 1..min(max_batch=%d, %d)%s", n_slots, s->max_batch, max_rows,

@@ -468,6 +468,19 @@ struct BeamResolveParams {
     float* score;
 };
 int launch_beam_resolve(const BeamResolveParams& p, hipStream_t stream);
+// ---- beam.hip: sample groups (include/emmax.h: emmax_session_set_sample_groups) ----
+// the fork of G prefilled groups into G x N rows (one wave per group): the page-table rows g N + j (the prompt's complete pages by reference
+// to row g N's, every later page the row's own), the rows' fresh decode state, and the copy list of the prompt's partial page
+// (launch_beam_copy consumes it: src = -1 where nothing is copied)
+struct GroupForkParams {
+    int N, max_pages;
+    int32_t *page_table, *ctx_len, *done, *n_out, *max_new, *stop_m, *stop_after, *copy_src, *copy_dst, *copy_ntok;
+    int S[EMMAX_MAX_DECODE_BATCH];   // the groups' prompt contexts
+};
+int launch_group_fork(const GroupForkParams& p, int groups, hipStream_t stream);
+// rows[g N + j] = rows[g] for every group g and sample j, in place (rows of row_bytes bytes, a multiple of 4): destination rows overlap
+// source rows for g >= 1, so every thread owns a column and walks the groups from the highest down
+int launch_group_bcast(void* rows, long long row_bytes, int groups, int N, hipStream_t stream);
 // the prompt ids of rows 0 .. B of a prefill (ids [B][P_max]) into dst [B][max_prompt], their lengths into dst_len
 struct HistParams {
     const int32_t* ids;

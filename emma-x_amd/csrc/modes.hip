@@ -180,6 +180,7 @@ int emmax_session_set_beams(emmax_session* s, int num_beams, double length_penal
     if (s->m->vocab > EMMAX_SAMPLE_MAX_V || s->m->vocab < 2 * num_beams)
         return fail(EMMAX_ERR_INVALID, "beams take vocabularies of %d..%d entries (%d)", 2 * num_beams, EMMAX_SAMPLE_MAX_V, s->m->vocab);
     if (s->slots_open) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while request slots are open");
+    if (s->grp_N) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while sample groups are on (emmax_session_clear_sample_groups)");
     if (s->samp.on || s->proc.on) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while sampling or logits processing is on");
     if (s->scores.on && s->scores.has_scores) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while a scores buffer is bound");
     StreamScope sc(s, stream);
@@ -221,6 +222,31 @@ int emmax_session_beam_result(emmax_session* s, int max_new, int32_t* seq_dev, i
     if (score_dev) HIPCHK(hipMemcpyAsync(score_dev, s->beam.res_score, rows * 4, hipMemcpyDeviceToDevice, st));
     return sc.leave();
 }
+
+// ---- sample groups: N sampled rows per prefilled prompt (additions to ABI 11) ----------------------------------------------
+int emmax_session_set_sample_groups(emmax_session* s, int n, emmax_stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    const int max_rows = std::min(s->max_batch, s->exact ? EMMAX_MAX_DECODE_BATCH : model_max_decode_batch(s->m));
+    if (n < 2 || n > max_rows) return fail(EMMAX_ERR_INVALID, "%d samples per group outside 2..min(max_batch=%d, the model's decode batch)=%d", n, s->max_batch, max_rows);
+    if (s->beam.K) return fail(EMMAX_ERR_STATE, "sample groups cannot be turned on while beams are on (emmax_session_clear_beams)");
+    if (s->slots_open) return fail(EMMAX_ERR_STATE, "sample groups cannot be turned on while request slots are open");
+    s->grp_N = n;
+    s->prefilled = false;   // rows of an earlier batch do not continue as groups
+    return 0;
+}
+
+int emmax_session_clear_sample_groups(emmax_session* s, emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->grp_N) return 0;
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    KCHK(launch_beam_pages(s->page_table, s->rows_total, s->max_pages, 1, sc.stream()));   // static assignment again: row b owns its own pages
+    s->grp_N = 0;
+    s->prefilled = false;
+    return sc.leave();
+}
+
+int emmax_session_sample_groups(const emmax_session* s) { return s ? s->grp_N : -1; }
 
 int emmax_session_beam_trace(emmax_session* s, int max_new, int32_t* tok_dev, int32_t* parent_dev, float* score_dev, float* lse_dev, int32_t* cand_idx_dev,
                              float* cand_acc_dev, emmax_stream stream) {

@@ -37,7 +37,7 @@ static int run_prefill_x(emmax_session* s, const int32_t* ids, int B, int P_max,
         KCHK(launch_gemm(g, st));
     }
     KCHK(launch_gather_last_rows(s->ph, s->dh + (size_t)r0 * m->H, s->cu, B, m->H, st, s->dh32 + (size_t)r0 * m->H, s->ph32));
-    if (int r = run_lm_head_step(s, B, true, nullptr, true, st, r0)) return r;
+    if (int r = s->grp_N ? run_group_fork(s, B, st) : run_lm_head_step(s, B, true, nullptr, true, st, r0)) return r;
     s->prefilled = true;
     s->beam.ready = s->beam.K != 0;
     return 0;
@@ -74,6 +74,17 @@ int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B
         KCHK(launch_beam_pages(s->page_table, B, s->max_pages, s->beam.K, st));   // row g over the pool of group g: the pages of rows g K ..
         s->beam.G = B; s->beam.forked = false; s->beam.ready = false;
     }
+    if (s->grp_N) {   // sample groups on: B prompts, one prefilled row each, forked into B x N sampled rows behind the lm-head (run_group_fork)
+        if (slot_mode) return fail(EMMAX_ERR_STATE, "request slots are not served while sample groups are on");
+        if (!s->samp.on)
+            return fail(EMMAX_ERR_STATE, "sample groups need sampling: %d greedy rows of one prompt would be identical (emmax_session_set_sampling)", s->grp_N);
+        const int rows = B * s->grp_N;
+        if (rows > s->max_batch || rows > max_rows)
+            return fail(EMMAX_ERR_INVALID, "%d groups x %d samples exceed min(max_batch=%d, %d) rows", B, s->grp_N, s->max_batch, max_rows);
+        if (rows >= EMMAX_MFMA_MIN_BATCH && !m->aux_built)
+            return fail(EMMAX_ERR_STATE, "%d sampled rows decode on the fragment-major weight copies: call emmax_model_build_aux first", rows);
+        KCHK(launch_beam_pages(s->page_table, B, s->max_pages, s->grp_N, st));   // row g over the first pages of group g's pool: those of row g N
+    }
     if (slot_mode) {
         if (!s->slots_open) return fail(EMMAX_ERR_STATE, "slot prefill before emmax_slots_open");
         if (r0 >= s->stg0) {   // staging rows
@@ -100,10 +111,11 @@ int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B
     if (total > s->max_rows) return fail(EMMAX_ERR_NOMEM, "packed prefill rows %d exceed capacity %d", total, s->max_rows);
     KCHK(launch_prefill_state(ps, s->cu, s->ctx_len + r0, s->done + r0, s->n_out + r0, s->max_new_d + r0, s->stop_m + r0, s->stop_after + r0, st));
     if (s->scores.on && !slot_mode && !s->beam.K) {   // the score buffers' rows: the first prefill after the binding's; another batch size unbinds them
+        const int rows = s->grp_N ? B * s->grp_N : B;   // (sample groups: the B x N rows the prefill forks into)
         if (s->scores.rows == 0) {
-            s->scores.rows = B;
-            KCHK(launch_set_int((int32_t*)(s->scores.words + 3), B, st));
-        } else if (s->scores.rows != B) {
+            s->scores.rows = rows;
+            KCHK(launch_set_int((int32_t*)(s->scores.words + 3), rows, st));
+        } else if (s->scores.rows != rows) {
             s->scores.on = false;
         }
     }
@@ -176,7 +188,7 @@ int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B
         KCHK(launch_gemm(g, st));
     }
     KCHK(launch_gather_last_rows(s->ph, s->dh + (size_t)r0 * m->H, s->cu, B, m->H, st, h32_of(s, r0), p32 ? s->ph32 : nullptr));
-    if (int r = run_lm_head_step(s, B, true, nullptr, true, st, r0)) return r;
+    if (int r = s->grp_N ? run_group_fork(s, B, st) : run_lm_head_step(s, B, true, nullptr, true, st, r0)) return r;
     s->prefilled = true;
     s->beam.ready = s->beam.K != 0;
     return 0;

@@ -191,6 +191,9 @@ struct emmax_session {
     Processing proc;
     Scores scores;
     Beams beam;
+    // SAMPLE GROUPS (emmax_session_set_sample_groups; step.hip: run_group_fork): N sampled rows per prefilled prompt, 0 = off.  Rows g N + j are
+    // the samples of prompt g; the fork's copy list lives in the beams' (csrc / cdst / cntok: beams and groups exclude each other)
+    int grp_N = 0;
     int32_t *part_idx2;
     int32_t *part_idx, *cur_tok, *ctx_len, *done, *n_out, *out_ids, *max_new_d /* [max_batch] */, *page_table;
     // EXACT NUMERICS (round 6; tuning switch `exact` at emmax_session_create): fp32 activations end to end.  x32a: the fp32 result of the GEMM
@@ -304,6 +307,7 @@ int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B
 int model_max_decode_batch(const emmax_model* m);
 bool beam_pages_fit(const emmax_session* s, int S, int max_new);
 int launch_beam_finish(emmax_session* s, bool is_prefill, hipStream_t st);
+int run_group_fork(emmax_session* s, int G, hipStream_t st);
 int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* logits_out, bool do_finish, hipStream_t st, int slot0 = 0);
 int run_decode_stage(emmax_session* s, int B, int li, int stage, hipStream_t st);
 int decode_oproj_form(const emmax_session* s, int B, int* nsplit);

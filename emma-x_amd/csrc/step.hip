@@ -249,6 +249,8 @@ bool beam_pages_fit(const emmax_session* s, int S, int max_new) {
     return S + max_new <= s->max_ctx && need <= (long long)K * s->max_pages;
 }
 
+static int launch_page_copies(emmax_session* s, int rows, hipStream_t st);
+
 // the tail of a step with beams on (beam.hip): per-row candidates, the groups' merge + state + page-table gather, the partial-page copies.
 // is_prefill: the first beam step, from the prefill's one logit row per group, and the fork
 int launch_beam_finish(emmax_session* s, bool is_prefill, hipStream_t st) {
@@ -275,6 +277,13 @@ int launch_beam_finish(emmax_session* s, bool is_prefill, hipStream_t st) {
     if (is_prefill)
         for (int i = 0; i < G; ++i) g.S[i] = s->S[i];
     KCHK(launch_beam_merge(g, G, st));
+    return launch_page_copies(s, rows, st);
+}
+
+// the partial-page copies of the list in beam.csrc / cdst / cntok (the beam merge or the sample groups' fork wrote it), one entry per row:
+// every layer, every plane of the cache format
+static int launch_page_copies(emmax_session* s, int rows, hipStream_t st) {
+    emmax_model* m = s->m;
     BeamCopyParams c;
     memset(&c, 0, sizeof(c));
     const long long kvr = kv_rows(s), hd = m->cfg.head_dim;
@@ -295,6 +304,49 @@ int launch_beam_finish(emmax_session* s, bool is_prefill, hipStream_t st) {
         plane(0, (int)hd * 2); plane(kvr * hd * 2, (int)hd * 2);
     }
     KCHK(launch_beam_copy(c, rows, m->cfg.n_layers, st));
+    return 0;
+}
+
+// The end of a prefill with sample groups on (include/emmax.h): the lm-head of the G prefilled rows, each group's logit row (and prompt history)
+// given to its N rows, the fork of the page table with the copies of the prompt's partial page, then token 0 of all G x N rows by the
+// sampled or processing finish a G x N batch's prefill ends in -- row g N + j draws with its own parameters.  The finish reads logit rows
+// and per-row state only, so it runs behind the fork
+int run_group_fork(emmax_session* s, int G, hipStream_t st) {
+    emmax_model* m = s->m;
+    const int N = s->grp_N, rows = G * N, V = m->vocab;
+    if (s->exact) {   // (as with beams: a group's first row must not depend on how many groups were prefilled with it)
+        for (int g = 0; g < G; ++g)
+            if (int r = run_lm_head_step(s, 1, true, s->logits + (size_t)g * V, false, st, g)) return r;
+    } else if (int r = run_lm_head_step(s, G, true, s->logits, false, st, 0)) {
+        return r;
+    }
+    KCHK(launch_group_bcast(s->logits, (long long)V * 4, G, N, st));
+    if (s->proc.on) {
+        KCHK(launch_group_bcast(s->proc.hist, (long long)s->max_prompt * 4, G, N, st));
+        KCHK(launch_group_bcast(s->proc.hist_len, 4, G, N, st));
+    }
+    GroupForkParams f;
+    memset(&f, 0, sizeof(f));
+    f.N = N; f.max_pages = s->max_pages; f.page_table = s->page_table;
+    f.ctx_len = s->ctx_len; f.done = s->done; f.n_out = s->n_out; f.max_new = s->max_new_d; f.stop_m = s->stop_m; f.stop_after = s->stop_after;
+    f.copy_src = s->beam.csrc; f.copy_dst = s->beam.cdst; f.copy_ntok = s->beam.cntok;
+    bool partial = false;
+    for (int g = 0; g < G; ++g) {
+        f.S[g] = s->S[g];
+        partial = partial || s->S[g] % PAGE != 0;
+    }
+    KCHK(launch_group_fork(f, G, st));
+    if (partial)   // (every prompt ends on a page boundary: all pages are shared by reference, nothing to copy)
+        if (int r = launch_page_copies(s, rows, st)) return r;
+    for (int g = G - 1; g >= 0; --g)
+        for (int j = N - 1; j >= 0; --j) s->S[g * N + j] = s->S[g];
+    s->cur_B = rows;
+    const int mode = finish_mode(s), chunk = s->exact ? 8 : EMMAX_KMP_ROWS;   // one finish per lm-head launch of a G x N step (run_lm_head_step)
+    for (int r0 = 0; r0 < rows; r0 += chunk) {
+        const int n = std::min(chunk, rows - r0);
+        const float* lg = s->logits + (size_t)r0 * V;
+        if (int r = (mode & 6) ? launch_proc_finish_step(s, n, true, r0, lg, st) : launch_sampled_finish_step(s, n, true, r0, lg, st)) return r;
+    }
     return 0;
 }
 

@@ -140,6 +140,9 @@ SIGNATURES = {
     "emmax_session_beams": (C.c_int, [_vp]),
     "emmax_session_beam_result": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "emmax_session_beam_trace": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "emmax_session_set_sample_groups": (C.c_int, [_vp, C.c_int, _vp]),
+    "emmax_session_clear_sample_groups": (C.c_int, [_vp, _vp]),
+    "emmax_session_sample_groups": (C.c_int, [_vp]),
     "emmax_op_decode_stage": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _c_i32p, _c_i32p, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int),
                                         C.POINTER(C.c_int), C.POINTER(C.c_int), _vp]),
     "emmax_op_decode_kv_read": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _c_i32p, C.c_int, _c_f32p, _c_f32p, _vp]),

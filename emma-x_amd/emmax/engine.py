@@ -130,6 +130,7 @@ class EmmaxEngine:
         assert bool(self.lib.emmax_session_exact(self._session)) == bool(self.exact)
         self._score_bufs = None   # a new session binds no scores
         self._beam_K = 0          # ... and has beams off
+        self._group_N = 0         # ... and sample groups off
         self.max_batch, self.max_prompt, self.max_ctx, self.stage_rows = max_batch, max_prompt, max_ctx, int(stage_rows)
 
     def ensure_stage_rows(self, n: int) -> None:
@@ -254,21 +255,22 @@ class EmmaxEngine:
         """Ragged prompts (row b = list of ids starting with BOS). Returns per-row packed lengths S_b = 256 + P_b."""
         B = len(input_ids)
         K = self._beam_K
-        self.ensure_decode_batch(B * K if K else B)   # beams on: B groups decode as B x K rows
+        N = self._group_N or 1
+        self.ensure_decode_batch(B * (K or N))   # beams / sample groups on: B groups decode as B x K / B x N rows
         ids_d, lens, P_max, _ = self._pack_prompts("prefill", input_ids, self.cfg.pad_token_id)
         lens_c = (C.c_int32 * B)(*lens)
         if patch_embeds is None:   # language-only forward
             _lib.check(self.lib.emmax_prefill_text(self._session, ids_d.data_ptr(), lens_c, B, P_max, _lib.current_stream()),
                        "emmax_prefill_text")
             self._last_S = list(lens)
-            self._last_B = B
+            self._last_B = B * N
             return self._last_S
         pe = patch_embeds.contiguous()
         assert pe.dtype == self.patch_dtype and pe.shape[0] == B
         _lib.check(self.lib.emmax_prefill(self._session, ids_d.data_ptr(), lens_c, B, P_max, pe.data_ptr(), _lib.current_stream()),
                    "emmax_prefill")
         self._last_S = [self.cfg.n_patches + n for n in lens]
-        self._last_B = B
+        self._last_B = B * N   # (sample groups: the prefill forked the B prompts into B x N rows; everything after it sees that batch)
         return self._last_S
 
     def prefill_logits(self) -> List[torch.Tensor]:
@@ -443,6 +445,22 @@ class EmmaxEngine:
         _lib.check(self.lib.emmax_session_beam_trace(self._session, T, *[tr[k].data_ptr() for k in ("tok", "parent", "score", "lse", "cand_idx", "cand_acc")],
                                                      _lib.current_stream()), "emmax_session_beam_trace")
         return tr
+
+    # ---- sample groups: N sampled rows per prompt (include/emmax.h: emmax_session_set_sample_groups) ------------------------
+    def set_sample_groups(self, n: int) -> None:
+        """Sample groups on: the next prefill takes G prompts and forks each into `n` sampled rows on the prompt's KV pages (row g n + j =
+        sample j of prompt g).  Sampling must be set for all G x n rows, and the session must hold them (ensure_capacity first)."""
+        _lib.check(self.lib.emmax_session_set_sample_groups(self._session, int(n), _lib.current_stream()), "emmax_session_set_sample_groups")
+        self._group_N = int(n)
+
+    def clear_sample_groups(self) -> None:
+        """Groups off: a prefill's rows are independent prompts again, on the static page assignment."""
+        _lib.check(self.lib.emmax_session_clear_sample_groups(self._session, _lib.current_stream()), "emmax_session_clear_sample_groups")
+        self._group_N = 0
+
+    @property
+    def sample_groups(self) -> int:
+        return max(int(self.lib.emmax_session_sample_groups(self._session)), 0)
 
     @property
     def scores_bound(self) -> bool:

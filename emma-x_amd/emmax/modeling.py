@@ -27,7 +27,7 @@ from .config import EmmaXConfig, check_decode_weight_dtype, default_norm_stats
 from .engine import EmmaxEngine
 from .policy_parser import Solver
 from .processing import BatchFeature, EmmaXImageProcessor
-from .sampling import BeamParams, LogitsProcessing, SamplingParams, draw_seed
+from .sampling import MAX_DECODE_BATCH, BeamParams, LogitsProcessing, SamplingParams, draw_seed
 from .prompting import PurePromptBuilder
 from .tokenizer_stub import StubTokenizer
 from .weights import load_hf_state_dict, remap_native_state_dict, synthetic_state_dict, validate_state_dict
@@ -248,7 +248,7 @@ class EmmaXForActionPrediction:
         return eng.vision_encode_pixels(pixel_values)
 
     def _prefill(self, rows: List[List[int]], pixel_values=None, frames_u8=None, max_new: int = 0, sampling=None, processing=None,
-                 scores=None, logits=None, beams: Optional[BeamParams] = None) -> torch.Tensor:
+                 scores=None, logits=None, beams: Optional[BeamParams] = None, num_samples: int = 1) -> torch.Tensor:
         eng = self._need_engine()
         B = len(rows)
         src = pixel_values if pixel_values is not None else frames_u8
@@ -259,17 +259,23 @@ class EmmaXForActionPrediction:
         if P > self.config.llm.max_position:
             rows = [r[: self.config.llm.max_position] for r in rows]   # tokenizer truncation at llm_max_length
             P = self.config.llm.max_position
-        K = beams.num_beams if beams is not None else 1
+        N = int(num_samples)
+        K = beams.num_beams if beams is not None else N
         if B * K > eng.max_decode_batch():
-            raise ValueError(f"{B} prompts x {K} beams exceed the {eng.max_decode_batch()} rows of a decode batch")
+            what = f"{N} samples" if N > 1 else f"{K} beams"
+            raise ValueError(f"{B} prompts x {what} exceed the {eng.max_decode_batch()} rows of a decode batch")
         eng.ensure_capacity(B * K, P, max(max_new, 1))
         patches = self._encode_images(pixel_values, frames_u8)
         if beams is None and getattr(eng, "beams", 0):
             eng.clear_beams()   # (first: sampling / processing cannot be set while beams are on)
+        if N == 1 and getattr(eng, "sample_groups", 0):
+            eng.clear_sample_groups()   # (and beams cannot be set while groups are on)
         self._set_processing(eng, B * K, processing, scores, logits, max_new)
         self._set_sampling(eng, B * K, sampling)
         if beams is not None:   # B groups prefill once each and decode as B x K rows on shared KV pages
             eng.set_beams(beams)
+        if N > 1:   # B prompts prefill once each and fork into B x N sampled rows on the prompt's KV pages
+            eng.set_sample_groups(N)
         eng.prefill(rows, patches)
         return patches
 
@@ -300,6 +306,25 @@ class EmmaXForActionPrediction:
     def _beam_kw(beams) -> Dict[str, Any]:
         """generate_ids' `beams` argument, passed only when there are beams (a greedy call is spelled exactly as before)."""
         return {} if beams is None else {"beams": beams}
+
+    @staticmethod
+    def _sample_group_args(do_sample: bool, num_beams=None, num_return_sequences=None) -> int:
+        """HF generate's (do_sample=True, num_return_sequences=N) -> N sampled rows per prompt; 1 for every other call (greedy and beam calls
+        keep their own checks in _beam_args).  N must be an integer >= 1: checked before the engine is touched."""
+        if not do_sample or (num_beams is not None and num_beams != 1) or num_return_sequences is None:
+            return 1
+        return EmmaXForActionPrediction._check_num_samples(num_return_sequences, "num_return_sequences")
+
+    @staticmethod
+    def _check_num_samples(n, name: str = "num_samples") -> int:
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError(f"{name} must be an integer >= 1, got {n!r}")
+        return int(n)
+
+    @staticmethod
+    def _sample_kw(n: int) -> Dict[str, Any]:
+        """generate_ids' `num_samples` argument, passed only when N > 1 (a plain call is spelled exactly as before)."""
+        return {} if n == 1 else {"num_samples": n}
 
     def _kw_beams(self, kwargs, processing=None) -> Optional[BeamParams]:
         """The beam arguments of a **kwargs that the reference forwards to HF generate."""
@@ -420,7 +445,7 @@ class EmmaXForActionPrediction:
     @torch.inference_mode()
     def generate_ids(self, rows: List[List[int]], pixel_values=None, frames_u8=None, max_new_tokens: int = 512,
                      stop_on_eos: bool = True, sampling=None, return_logprobs: bool = False, processing=None, scores=None, logits=None,
-                     beams: Optional[BeamParams] = None):
+                     beams: Optional[BeamParams] = None, num_samples: int = 1):
         """Decode every row: greedy, or sampled in the step with `sampling` (one SamplingParams for all rows or one per row; row b draws
         with subseq b).  `processing` (one LogitsProcessing for all rows or one per row) applies HF's repetition penalty / n-gram ban /
         min-new-tokens in the step first.  `scores` / `logits`: fp32 [max_new, B, vocab] device buffers the step fills with HF's scores /
@@ -429,7 +454,18 @@ class EmmaXForActionPrediction:
         lens int32 [B]), and with return_logprobs (sampling only) the fp32 [B,max_new] log-probabilities of the emitted tokens.
         `beams` (BeamParams; no sampling, processing or scores with it): beam search in the step.  The B rows are groups, the result has
         B x num_beams rows -- row g K + k = the k-th best hypothesis of group g -- and `logits` is [max_new, B x num_beams, vocab];
-        engine.beam_result() / beam_trace() hold the scores, beam_indices and the per-step trace."""
+        engine.beam_result() / beam_trace() hold the scores, beam_indices and the per-step trace.
+        `num_samples` = N > 1 (needs `sampling`; no beams): every row is a prompt that is prefilled once and forked into N sampled rows on its
+        KV pages.  The result has B x N rows -- row b N + j = sample j of prompt b, drawing with subseq b N + j by default -- `sampling` /
+        `processing` lists have one entry per result row (or one entry for all), and `scores` / `logits` are [max_new, B x N, vocab]."""
+        N = self._check_num_samples(num_samples)
+        if N > 1:
+            if beams is not None:
+                raise ValueError("num_samples > 1 runs without beams (beam sampling is not built)")
+            if sampling is None:
+                raise ValueError(f"num_samples={N} needs sampling: {N} greedy rows of one prompt would be identical")
+            if len(rows) * N > MAX_DECODE_BATCH:
+                raise ValueError(f"{len(rows)} prompts x {N} samples exceed the {MAX_DECODE_BATCH} rows of a decode batch")
         eng = self._need_engine()
         if beams is not None:
             if not isinstance(beams, BeamParams):
@@ -442,10 +478,10 @@ class EmmaXForActionPrediction:
             ps = processing if isinstance(processing, (list, tuple)) else [processing]
             if not all(isinstance(p, LogitsProcessing) for p in ps):
                 raise ValueError("processing must be LogitsProcessing (one, or one per row)")
-        self._check_score_buffers(scores, logits, max_new_tokens, len(rows) * (beams.num_beams if beams is not None else 1),
+        self._check_score_buffers(scores, logits, max_new_tokens, len(rows) * (beams.num_beams if beams is not None else N),
                                   self.config.llm.vocab_size)
         self._prefill(rows, pixel_values, frames_u8, max_new=max_new_tokens, sampling=sampling, processing=processing, scores=scores,
-                      logits=logits, beams=beams)
+                      logits=logits, beams=beams, **self._sample_kw(N))
         out = eng.generate(max_new_tokens, stop_on_eos, return_logprobs=return_logprobs)
         if scores is not None or logits is not None:
             eng.set_scores(None, None)   # the buffers are the caller's now: no later step or prefill writes into them
@@ -473,7 +509,9 @@ class EmmaXForActionPrediction:
                  output_scores: bool = False, output_logits: bool = False, return_dict_in_generate: bool = False, **kwargs):
         """HF-style: returns LongTensor [B, P + T] = prompt ++ generated (right-padded with pad_token_id).  do_sample=True draws every token
         in the decode step (include/emmax.h: emmax_session_set_sampling) with temperature / top_k / top_p (HF defaults 1.0 / 50 / 1.0 when
-        unset); row b draws with (seed, subseq b), seed None = draw_seed(generator).  repetition_penalty / no_repeat_ngram_size /
+        unset); row b draws with (seed, subseq b), seed None = draw_seed(generator).  With num_return_sequences=N the prompt is prefilled once
+        and decoded as N sampled rows on its KV pages: [B N, P + T], row b N + j = sample j of prompt b (scores / logits: [B N, vocab] each).
+        repetition_penalty / no_repeat_ngram_size /
         min_new_tokens / min_length are applied in the step as HF's processors (emmax_session_set_processing).  return_dict_in_generate=True
         returns an EmmaXGenerateOutput: `sequences` (the tensor), and with output_scores / output_logits a tuple of T = max(lens) fp32
         [B, vocab] device tensors each (NaN past a row's length)."""
@@ -481,18 +519,21 @@ class EmmaXForActionPrediction:
         processing = self._processing_args(rows, repetition_penalty, no_repeat_ngram_size, min_new_tokens, min_length)
         beams = self._beam_args(kwargs.get("num_beams"), kwargs.get("num_return_sequences"), kwargs.get("length_penalty"),
                                 kwargs.get("early_stopping"), do_sample, processing, bool(return_dict_in_generate and output_scores))
+        N = self._sample_group_args(do_sample, kwargs.get("num_beams"), kwargs.get("num_return_sequences"))
+        if len(rows) * N > MAX_DECODE_BATCH:
+            raise ValueError(f"{len(rows)} prompts x {N} samples exceed the {MAX_DECODE_BATCH} rows of a decode batch")
         sampling = self._sampling_args(do_sample, temperature, top_k, top_p, seed, generator)
         max_new_tokens = self._max_new(rows, max_new_tokens, kwargs.get("max_length"), None)   # (min_length is in `processing`)
         want_sc, want_lg = bool(return_dict_in_generate and output_scores), bool(return_dict_in_generate and output_logits)
         sc = lg = None
-        K = beams.num_beams if beams is not None else 1
+        K = beams.num_beams if beams is not None else N
         if want_sc or want_lg:
             eng = self._need_engine()
             shape = (max_new_tokens, len(rows) * K, self.config.llm.vocab_size)
             sc = torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device) if want_sc else None
             lg = torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device) if want_lg else None
         new_ids, lens = self.generate_ids(rows, pixel_values, frames_u8, max_new_tokens, sampling=sampling, processing=processing, scores=sc,
-                                          logits=lg, **self._beam_kw(beams))
+                                          logits=lg, **self._beam_kw(beams), **self._sample_kw(N))
         if beams is not None:   # HF's layout: [B * num_return_sequences, P + T], best first per prompt
             R = beams.num_return_sequences
             keep = [g * K + k for g in range(len(rows)) for k in range(R)]
@@ -512,9 +553,9 @@ class EmmaXForActionPrediction:
         new_ids, lens = new_ids.cpu(), lens.cpu().tolist()
         T = max(lens)
         P = max(len(r) for r in rows)
-        out = torch.full((len(rows), P + T), self.config.pad_token_id, dtype=torch.long)
-        for b, r in enumerate(rows):
-            seq = r + new_ids[b, : lens[b]].tolist()
+        out = torch.full((len(rows) * N, P + T), self.config.pad_token_id, dtype=torch.long)
+        for b in range(len(rows) * N):   # (num_return_sequences = N: row b N + j is sample j of prompt b, HF's expand_inputs_for_generation order)
+            seq = rows[b // N] + new_ids[b, : lens[b]].tolist()
             out[b, : len(seq)] = torch.tensor(seq, dtype=torch.long)
         if not return_dict_in_generate:
             return out
@@ -544,12 +585,17 @@ class EmmaXForActionPrediction:
         beams = self._kw_beams(kwargs, processing)
         sampling = self._sampling_args(bool(kwargs.get("do_sample", False)), kwargs.get("temperature"), kwargs.get("top_k"), kwargs.get("top_p"),
                                        kwargs.get("seed"), kwargs.get("generator"))
+        N = self._sample_group_args(sampling is not None, kwargs.get("num_beams"), kwargs.get("num_return_sequences"))
         new_ids, lens = self.generate_ids(rows, kwargs.get("pixel_values"), kwargs.get("frames_u8"), max_new_tokens=dim, sampling=sampling,
-                                          processing=processing, **self._beam_kw(beams))
-        full = rows[0] + new_ids[0, : int(lens[0])].cpu().tolist()
-        predicted = np.array(full[-dim:])
-        normalized = token_ids_to_actions(predicted, self.vocab_size, self.bin_centers)
-        return unnormalize(normalized, self.get_action_stats(unnorm_key))
+                                          processing=processing, **self._beam_kw(beams), **self._sample_kw(N))
+
+        def action(j):
+            full = rows[0] + new_ids[j, : int(lens[j])].cpu().tolist()
+            normalized = token_ids_to_actions(np.array(full[-dim:]), self.vocab_size, self.bin_centers)
+            return unnormalize(normalized, self.get_action_stats(unnorm_key))
+
+        # do_sample=True with num_return_sequences=N > 1: the N sampled actions of the one observation, [N, action_dim]
+        return action(0) if N == 1 else np.stack([action(j) for j in range(N)])
 
     def _solver(self, tokenizer) -> Solver:
         return Solver(ActionTokenizer(tokenizer, bins=self.config.n_action_bins), verbose=False)
@@ -633,13 +679,15 @@ class EmmaXForActionPrediction:
 
     @torch.inference_mode()
     def generate_actions_batch(self, frames_u8: torch.Tensor, prompt_rows: Sequence[Sequence[int]], max_new_tokens: int = 512,
-                               stop_on_eos: bool = True, tokenizer=None, sampling=None, processing=None, beams: Optional[BeamParams] = None):
+                               stop_on_eos: bool = True, tokenizer=None, sampling=None, processing=None, beams: Optional[BeamParams] = None,
+                               num_samples: int = 1):
         """Batched extension: returns (actions f32 [B,7], new_ids int32 [B,T], lens int32 [B]).
 
         With `tokenizer` each row goes ids -> text -> Solver exactly like the bs=1 path; without it the ids-level
-        stand-in `actions_from_ids` is used (synthetic weights / throughput runs).  `sampling` / `processing`: as generate_ids (None = off)."""
+        stand-in `actions_from_ids` is used (synthetic weights / throughput runs).  `sampling` / `processing`: as generate_ids (None = off).
+        `num_samples` = N > 1 (with `sampling`): N sampled rows per frame, all three results with B x N rows (row b N + j = sample j of frame b)."""
         new_ids, lens = self.generate_ids([list(r) for r in prompt_rows], None, frames_u8, max_new_tokens, stop_on_eos, sampling=sampling,
-                                          processing=processing, **self._beam_kw(beams))
+                                          processing=processing, **self._beam_kw(beams), **self._sample_kw(self._check_num_samples(num_samples)))
         if beams is not None:   # the best hypothesis of every prompt
             new_ids, lens = new_ids[:: beams.num_beams].contiguous(), lens[:: beams.num_beams].contiguous()
         ids_h, lens_h = new_ids.cpu(), lens.cpu().tolist()

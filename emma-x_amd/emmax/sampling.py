@@ -71,6 +71,7 @@ class LogitsProcessing:
 
 
 MAX_BEAMS = 8   # EMMAX_MAX_BEAMS (include/emmax.h)
+MAX_DECODE_BATCH = 64   # EMMAX_MAX_DECODE_BATCH: rows of a decode step on any model (a model's own limit: engine.max_decode_batch())
 
 
 @dataclass(frozen=True)

@@ -112,6 +112,8 @@ class SlotScheduler:
         engine.set_stop(list(stop_trigger), stop_after)
         if getattr(engine, "beams", 0):   # a beam generation ran on this session: slots are served with beams off
             engine.clear_beams()
+        if getattr(engine, "sample_groups", 0):   # ... or a sample-group generation: slots are served with groups off
+            engine.clear_sample_groups()
         engine.slots_open(n_slots)
 
     def submit(self, req: Request) -> None:

@@ -403,6 +403,38 @@ int emmax_session_beam_result(emmax_session* s, int max_new, int32_t* seq_dev, i
 int emmax_session_beam_trace(emmax_session* s, int max_new, int32_t* tok_dev, int32_t* parent_dev, float* score_dev, float* lse_dev,
                              int32_t* cand_idx_dev, float* cand_acc_dev, emmax_stream stream);
 
+/* ---- sample groups: N sampled rows per prompt on the prompt's KV pages (additions to ABI 11: new symbols only) ------------
+ * HF generate(do_sample = True, num_return_sequences = N).  A SAMPLE GROUP is one prompt (one frame) with N rows; a session decodes G
+ * groups as G x N rows, row g N + j = sample j of prompt g (the order of HF's expand_inputs_for_generation).  2 <= N and
+ * G x N <= min(max_batch, emmax_model_max_decode_batch): there is no cap of 8.  Sampling must be on (emmax_session_set_sampling): N greedy
+ * rows of one prompt are identical, and a prefill with groups on and sampling off returns EMMAX_ERR_STATE (HF raises there too).
+ *
+ * With groups on emmax_prefill* takes G rows (G x N must fit, else EMMAX_ERR_INVALID) and does all of this before it returns:
+ *   prefill      one row per group, written to the first pages of the group's pool (the pages of rows g N .. g N + N - 1).
+ *   lm-head      one row per group (exact numerics: one row per launch, as with beams -- a group's first row does not depend on G); the row is
+ *                then given to all N rows: the session's fp32 logit rows (what emmax_last_logits returns until the first decode step), the
+ *                prompt-history rows when processing is on, and logits[0] / scores[0] of every row when buffers are bound
+ *                (emmax_session_set_scores: buffers of [max_new][G N][vocab]).
+ *   token 0      row g N + j draws with its own (temperature, top_k, top_p, seed, subseq) at step 0: the sampled or processing finish a
+ *                G x N batch's prefill ends in, unchanged.
+ *   fork         the page-table rows of the group reference the prompt's floor(S / 64) complete pages, S = patches + prompt ids; the
+ *                partial page is copied N - 1 times into each row's own page at that index, in every layer and every plane of the cache
+ *                format; no copy is made when S % 64 == 0.  Every later page is the row's own.
+ * From then on the rows are ordinary decode rows on a non-identity page table: emmax_decode_step, emmax_generate, emmax_last_logits,
+ * emmax_set_current_tokens, the log-probabilities, the scores, the stop rule and graph replay behave as for a G x N batch, and a step
+ * launches exactly the kernels a G x N sampled batch launches.  Nothing is reordered after the fork: there are no spares and no per-step
+ * copies, private pages come out of each row's own static share, so no EMMAX_ERR_NOMEM case exists beyond a plain batch's, and
+ * emmax_session_bytes is unchanged.  Every weight format and every cache format is served (the copy goes by planes).
+ *
+ *   emmax_session_set_sample_groups    N = n for every prefill from now on.  EMMAX_ERR_INVALID outside 2 .. min(max_batch,
+ *                                      emmax_model_max_decode_batch); EMMAX_ERR_STATE while beams are on or request slots are open.
+ *   emmax_session_clear_sample_groups  groups off; the page table is the identity again and the session launches what it launched before.
+ *   emmax_session_sample_groups        N, 0 = off, -1 null session.
+ * With groups on emmax_session_set_beams and emmax_slots_open return EMMAX_ERR_STATE. */
+int emmax_session_set_sample_groups(emmax_session* s, int n, emmax_stream stream);
+int emmax_session_clear_sample_groups(emmax_session* s, emmax_stream stream);
+int emmax_session_sample_groups(const emmax_session* s);
+
 /* ---- single-kernel entry points (parity tests + micro-benchmarks) -------------------------------------------------- */
 /* C[M,N] = epilogue(A[M,K] @ W[N,K]^T): bf16 in, fp32 accumulate on MFMA.  K % 64 == 0, N % 128 == 0.
  * bias/scale: bf16 [N] or NULL; residual: bf16 [M,ldr] or NULL; act: 0 none, 1 exact-erf GELU, 2 SwiGLU over
