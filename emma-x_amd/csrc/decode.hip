@@ -738,36 +738,21 @@ static int gemv_fp8_shape(int n_rows, int K) {
 }
 
 template <int B, int MODE, bool NORM, bool XATTN = false, int F8 = 0>
-static int launch_gemv_t(const GemvParams& p, hipStream_t stream, int* grid_out) {
-    const size_t smem = (size_t)B * (p.kc * 2 + 16);
-    int grid = gemv_grid(B, smem, p.n_groups, (F8 == 1 || F8 == 2) ? 256 : p.max_grid);
-    if (MODE == GEMV_LMHEAD) grid = min(grid, p.max_parts);
-    if (grid_out) *grid_out = grid;
+static int launch_gemv_t(const GemvParams& p, const ProjGeom& g, hipStream_t stream) {
     auto kern = emmax_decode_gemv_kernel<B, MODE, NORM, XATTN, F8>;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(GW * 64), smem, stream, p);
+    hipLaunchKernelGGL(kern, dim3(g.grid), dim3(GW * 64), g.smem, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
 template <int MODE, bool NORM, bool XATTN = false>
-static int launch_gemv_mode(GemvParams p, int B, hipStream_t stream, int* grid_out) {
-    // K phase: keep B * kc * 2 bytes of activations under ~128 KiB of LDS
-    const int cap = (128 * 1024 / 2 / B) & ~511;
-    p.kc = p.K <= cap ? p.K : (cdiv(cdiv(p.K, cdiv(p.K, cap)), 512) * 512);
-    if (NORM && p.kc != p.K) return -1;
-    if (MODE == GEMV_QKV) p.n_groups = p.n_rows / 2;
-    else if (MODE == GEMV_GATEUP) p.n_groups = p.n_rows / 2;
-    else p.n_groups = (p.n_rows + 1) / 2;
-    p.n_pairs = p.n_groups;
-    if (p.wscale) {   // fp8 rows (batch 1-2, one K phase)
-        if (p.kc != p.K || p.K % 16 || B > 2) return -1;
-        const int f8 = gemv_fp8_shape(p.n_rows, p.K);
-        if (f8 == 3) p.n_groups = (p.n_pairs + 1) / 2;   // groups of two pairs
-#define CASEF(BB, FF) if (B == BB && f8 == FF) return launch_gemv_t<BB, MODE, NORM, XATTN, FF>(p, stream, grid_out)
+static int launch_gemv_mode(const GemvParams& p, int B, const ProjGeom& g, hipStream_t stream) {
+    if (g.f8) {   // fp8 rows (batch 1-2, one K phase)
+#define CASEF(BB, FF) if (B == BB && g.f8 == FF) return launch_gemv_t<BB, MODE, NORM, XATTN, FF>(p, g, stream)
         CASEF(1, 1); CASEF(1, 2); CASEF(1, 3); CASEF(2, 1); CASEF(2, 2); CASEF(2, 3);
 #undef CASEF
         return -1;
     }
-#define CASEB(BB) case BB: return launch_gemv_t<BB, MODE, NORM, XATTN>(p, stream, grid_out)
+#define CASEB(BB) case BB: return launch_gemv_t<BB, MODE, NORM, XATTN>(p, g, stream)
     switch (B) {
         CASEB(1); CASEB(2);
     }
@@ -778,6 +763,32 @@ static int launch_gemv_mode(GemvParams p, int B, hipStream_t stream, int* grid_o
     }
 #undef CASEB
     return -1;
+}
+
+// What the staged kernel takes: the fused modes at 1-2 rows (bf16 rows, or the fp8 row copy of launch_quant_rm8), GEMV_PLAIN up to 8 rows
+// (fp8 rows: 2); K in K phases that keep B * kc * 2 bytes of activations under ~128 KiB of LDS -- ONE phase for the modes with a norm
+// prologue and for fp8 rows.
+bool decode_gemv_takes(const ProjShape& s, int B, ProjGeom* out) {
+    if (s.K % 8 || !s.ld_ok || s.K <= 0) return false;
+    if (s.mode < GEMV_QKV || s.mode > GEMV_PLAIN) return false;
+    const bool fp8 = s.wfmt == PW_FP8, norm = s.mode == GEMV_QKV || s.mode == GEMV_GATEUP || s.mode == GEMV_LMHEAD;
+    if (B < 1 || B > ((s.mode == GEMV_PLAIN && !fp8) ? 8 : 2) || s.wfmt == PW_MX4) return false;
+    ProjGeom g = {};
+    const int cap = (128 * 1024 / 2 / B) & ~511;
+    g.kc = s.K <= cap ? s.K : (cdiv(cdiv(s.K, cdiv(s.K, cap)), 512) * 512);
+    if ((norm || fp8) && g.kc != s.K) return false;
+    if (fp8 && s.K % 16) return false;
+    const int n_pairs = (s.mode == GEMV_QKV || s.mode == GEMV_GATEUP) ? s.n_rows / 2 : (s.n_rows + 1) / 2;
+    g.n_groups = n_pairs;
+    if (fp8) {
+        g.f8 = gemv_fp8_shape(s.n_rows, s.K);
+        if (g.f8 == 3) g.n_groups = (n_pairs + 1) / 2;   // groups of two pairs
+    }
+    g.smem = (size_t)B * (g.kc * 2 + 16);
+    g.grid = gemv_grid(B, g.smem, g.n_groups, (g.f8 == 1 || g.f8 == 2) ? 256 : s.max_grid);
+    if (s.mode == GEMV_LMHEAD) g.grid = min(g.grid, s.max_parts);
+    if (out) *out = g;
+    return true;
 }
 
 template <int MODE, bool NORM, bool XATTN = false>
@@ -806,37 +817,36 @@ int decode_gemv_init() {
     return r;
 }
 
-// the fp8 row GEMV stages the whole activation rows in LDS (one K phase) and serves batch 1-2
-bool decode_gemv_fp8_fits(int B, int K) {
-    if (B < 1 || B > 2 || K <= 0 || K % 16) return false;
-    return K <= ((128 * 1024 / 2 / B) & ~511);
-}
-
 int launch_quant_rm8(const void* src, int ld, void* dst, float* scales, int N, int K, hipStream_t stream) {
     if (N <= 0 || K <= 0 || K % 16 || ld % 8) return -1;
     hipLaunchKernelGGL(emmax_quant_rm8_kernel, dim3(N), dim3(256), 0, stream, (const bf16_t*)src, ld, (uint8_t*)dst, scales, N, K);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
-// p.wscale set: p.W is the fp8 row copy of launch_quant_rm8 (ldw = bytes per row), batch 1-2
-int launch_decode_gemv(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out, int* staged_out) {
-    if (p.K % 8 || p.ldw % 8 || p.ldx % 8) return -1;
-    if (staged_out) *staged_out = 0;
-    if (decode_ks_enabled()) {   // batch 1-2, bf16, K % 64 == 0: the K-split kernel (decode_ks.hip)
-        const int r = launch_decode_ks(mode, p, B, stream, grid_out);
-        if (r != -2) return r;
-    }
-    if (staged_out) *staged_out = 1;
+int launch_decode_gemv_staged(int mode, const GemvParams& p_in, int B, const ProjGeom& g, hipStream_t stream, int* grid_out) {
+    GemvParams p = p_in;
+    p.kc = g.kc; p.n_groups = g.n_groups;
+    p.n_pairs = (mode == GEMV_QKV || mode == GEMV_GATEUP) ? p.n_rows / 2 : (p.n_rows + 1) / 2;
+    if (grid_out) *grid_out = g.grid;
     switch (mode) {
-        case GEMV_QKV: return launch_gemv_mode<GEMV_QKV, true>(p, B, stream, grid_out);
+        case GEMV_QKV: return launch_gemv_mode<GEMV_QKV, true>(p, B, g, stream);
         case GEMV_RESID:
-            return p.attn_part ? launch_gemv_mode<GEMV_RESID, false, true>(p, B, stream, grid_out)
-                               : launch_gemv_mode<GEMV_RESID, false>(p, B, stream, grid_out);
-        case GEMV_GATEUP: return launch_gemv_mode<GEMV_GATEUP, true>(p, B, stream, grid_out);
-        case GEMV_LMHEAD: return launch_gemv_mode<GEMV_LMHEAD, true>(p, B, stream, grid_out);
-        case GEMV_PLAIN: return launch_gemv_mode<GEMV_PLAIN, false>(p, B, stream, grid_out);
-        default: return -1;
+            return p.attn_part ? launch_gemv_mode<GEMV_RESID, false, true>(p, B, g, stream) : launch_gemv_mode<GEMV_RESID, false>(p, B, g, stream);
+        case GEMV_GATEUP: return launch_gemv_mode<GEMV_GATEUP, true>(p, B, g, stream);
+        case GEMV_LMHEAD: return launch_gemv_mode<GEMV_LMHEAD, true>(p, B, g, stream);
+        default: return launch_gemv_mode<GEMV_PLAIN, false>(p, B, g, stream);
     }
+}
+
+// p.wscale set: p.W is the fp8 row copy of launch_quant_rm8 (ldw = bytes per row), batch 1-2.  -1: neither decode_ks.hip nor the staged kernel takes it
+int launch_decode_gemv(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out, int* staged_out) {
+    const ProjShape s = proj_shape(mode, p);
+    ProjGeom g;
+    if (staged_out) *staged_out = 0;
+    if (decode_ks_enabled() && decode_ks_takes(s, B, &g)) return launch_decode_ks(mode, p, B, stream, grid_out, &g);   // batch 1-2, bf16, K % 64 == 0
+    if (!decode_gemv_takes(s, B, &g)) return -1;
+    if (staged_out) *staged_out = 1;
+    return launch_decode_gemv_staged(mode, p, B, g, stream, grid_out);
 }
 
 int launch_decode_embed(const int32_t* cur_tok, const void* E, void* h, int B, int hidden, int vocab, hipStream_t stream, float* h32) {

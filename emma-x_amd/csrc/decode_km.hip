@@ -710,107 +710,150 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_kmd_kernel(GemvParams p
     }
 }
 
+// (the launch functions below run behind decode_km_takes: every shape they meet has been accepted, the geometry is its answer)
 template <int WF, int NB, bool EX = false>
-int kmd_launch(GemvParams p, int B, hipStream_t stream) {
-    using S = KdShape<NB, WF>;
-    constexpr int FPS = WF == W_MX4 ? 4 : WF == W_FP8 ? 2 : 1, KS = 32 * FPS;
-    if (p.K % KS || p.n_rows % 16 || p.attn_part) return -2;
-    p.batch = B;
-    p.n_groups = p.n_rows / 16;
-    if (cdiv(p.K / KS, KM_WAVES) > S::NPH * (S::FR / FPS)) return -2;   // NPH phases of FR fragments per wave
-    if (p.K / KS < KM_WAVES) return -2;
-    const size_t smem = (size_t)KM_WAVES * 1024 + (size_t)KM_WAVES * NB * S::XP;
+int kmd_launch(const GemvParams& p, const ProjGeom& g, hipStream_t stream) {
     if constexpr (EX) {
-        if (!p.h32 || B > 8) return -2;
-        hipLaunchKernelGGL((emmax_decode_kmd_kernel<W_BF16, true, 16, true>), dim3(p.n_groups), dim3(KM_NT), smem, stream, p);
+        hipLaunchKernelGGL((emmax_decode_kmd_kernel<W_BF16, true, 16, true>), dim3(g.grid), dim3(KM_NT), g.smem, stream, p);
     } else {
-        if (p.h32) hipLaunchKernelGGL((emmax_decode_kmd_kernel<WF, true, NB>), dim3(p.n_groups), dim3(KM_NT), smem, stream, p);
-        else hipLaunchKernelGGL((emmax_decode_kmd_kernel<WF, false, NB>), dim3(p.n_groups), dim3(KM_NT), smem, stream, p);
+        if (p.h32) hipLaunchKernelGGL((emmax_decode_kmd_kernel<WF, true, NB>), dim3(g.grid), dim3(KM_NT), g.smem, stream, p);
+        else hipLaunchKernelGGL((emmax_decode_kmd_kernel<WF, false, NB>), dim3(g.grid), dim3(KM_NT), g.smem, stream, p);
     }
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
 template <int MODE, bool NORM, bool XATTN, int WF, int NB, bool ROLL, bool EX = false>
-int km_launch_nb(GemvParams p, int B, hipStream_t stream, int* grid_out) {
-    constexpr int KS = WF == W_MX4 ? 128 : WF == W_FP8 ? 64 : 32;
-    if (p.K % (KM_WAVES * KS) || p.K > KM_WAVES * KM_STEPS * 32 || p.n_rows % 16) return -2;
-    if (MODE == GEMV_QKV && (p.head_dim % 16 || p.head_dim < 16)) return -2;
-    p.batch = B;
-    p.n_groups = p.n_rows / 16;   // tiles
-    int grid = min(256, p.n_groups);
-    if (MODE == GEMV_LMHEAD) grid = min(grid, p.max_parts);
-    if (grid < 1) return -2;
-    p.kc = cdiv(p.n_groups, grid);
-    if (p.kc > KM_MAX_TILES) return -2;
-    if (p.kc & 1) p.kc += 1;   // the loop runs tiles in pairs
-    // one region per wave (kernel: window [NB][XPITCH] overlaid by the partial tiles) + sumsq (+ XATTN: the merged rows)
-    const size_t wreg = XATTN ? (size_t)p.kc * 1024 : std::max((size_t)NB * (KM_STEPS * 64 + 16), (size_t)p.kc * 1024);
-    const size_t smem = (size_t)KM_WAVES * wreg + KM_WAVES * 16 * 4 + (XATTN ? (size_t)(EX ? 16 : B) * p.K * 2 : 0);
-    if (smem > 150 * 1024) return -2;
-    if (grid_out) *grid_out = grid;
+int km_launch_nb(const GemvParams& p, const ProjGeom& g, hipStream_t stream) {
     if constexpr (EX) {   // exact numerics: fp32 rows in (h32 / p.x / the split partials), two terms per batch row, batch <= 8
-        if (B > 8 || !p.h32) return -2;
-        hipLaunchKernelGGL((emmax_decode_km_kernel<MODE, NORM, XATTN, W_BF16, MODE == GEMV_RESID, 16, false, true>), dim3(grid), dim3(KM_NT), smem, stream, p);
+        hipLaunchKernelGGL((emmax_decode_km_kernel<MODE, NORM, XATTN, W_BF16, MODE == GEMV_RESID, 16, false, true>), dim3(g.grid), dim3(KM_NT), g.smem, stream, p);
         return hipGetLastError() == hipSuccess ? 0 : -4;
     }
     if constexpr (MODE == GEMV_RESID) {   // (NORM modes read the bf16 mirror: h32 is ignored there)
         if (p.h32) {
-            hipLaunchKernelGGL((emmax_decode_km_kernel<MODE, NORM, XATTN, WF, true, NB, ROLL>), dim3(grid), dim3(KM_NT), smem, stream, p);
+            hipLaunchKernelGGL((emmax_decode_km_kernel<MODE, NORM, XATTN, WF, true, NB, ROLL>), dim3(g.grid), dim3(KM_NT), g.smem, stream, p);
             return hipGetLastError() == hipSuccess ? 0 : -4;
         }
     }
-    hipLaunchKernelGGL((emmax_decode_km_kernel<MODE, NORM, XATTN, WF, false, NB, ROLL>), dim3(grid), dim3(KM_NT), smem, stream, p);
+    hipLaunchKernelGGL((emmax_decode_km_kernel<MODE, NORM, XATTN, WF, false, NB, ROLL>), dim3(g.grid), dim3(KM_NT), g.smem, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 template <int MODE, bool NORM, bool XATTN, int WF>
-int km_launch_t(const GemvParams& p, int B, hipStream_t stream, int* grid_out) {
+int km_launch_t(const GemvParams& p, const ProjGeom& g, hipStream_t stream) {
     if constexpr (WF == W_MX4 && XATTN) {   // split partials of 9-16 rows x K do not fit the LDS stage: those batches exist in the one-split form only
-        return B <= 8 ? km_launch_nb<MODE, NORM, XATTN, WF, 8, false>(p, B, stream, grid_out) : -2;
+        return km_launch_nb<MODE, NORM, XATTN, WF, 8, false>(p, g, stream);
     } else {
         if constexpr (WF != W_MX4) {   // (the MX4 form always refills step by step: one instantiation per batch width)
-            if (emmax_tune().km_roll)
-                return B <= 8 ? km_launch_nb<MODE, NORM, XATTN, WF, 8, true>(p, B, stream, grid_out) : km_launch_nb<MODE, NORM, XATTN, WF, 16, true>(p, B, stream, grid_out);
+            if (g.roll)
+                return g.nb == 8 ? km_launch_nb<MODE, NORM, XATTN, WF, 8, true>(p, g, stream) : km_launch_nb<MODE, NORM, XATTN, WF, 16, true>(p, g, stream);
         }
-        return B <= 8 ? km_launch_nb<MODE, NORM, XATTN, WF, 8, false>(p, B, stream, grid_out) : km_launch_nb<MODE, NORM, XATTN, WF, 16, false>(p, B, stream, grid_out);
+        return g.nb == 8 ? km_launch_nb<MODE, NORM, XATTN, WF, 8, false>(p, g, stream) : km_launch_nb<MODE, NORM, XATTN, WF, 16, false>(p, g, stream);
     }
 }
 
 // exact numerics (GemvParams::exact), batch 3-8: the EX forms
-int km_launch_mode_x(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out) {
+int km_launch_mode_x(int mode, const GemvParams& p, const ProjGeom& g, hipStream_t stream) {
     switch (mode) {
-        case GEMV_QKV: return km_launch_nb<GEMV_QKV, true, false, W_BF16, 16, false, true>(p, B, stream, grid_out);
+        case GEMV_QKV: return km_launch_nb<GEMV_QKV, true, false, W_BF16, 16, false, true>(p, g, stream);
         case GEMV_RESID:
-            if (p.attn_part && p.K != p.Hq * 128) return -2;
-            return p.attn_part ? km_launch_nb<GEMV_RESID, false, true, W_BF16, 16, false, true>(p, B, stream, grid_out)
-                               : km_launch_nb<GEMV_RESID, false, false, W_BF16, 16, false, true>(p, B, stream, grid_out);
-        case GEMV_GATEUP: return km_launch_nb<GEMV_GATEUP, true, false, W_BF16, 16, false, true>(p, B, stream, grid_out);
-        case GEMV_LMHEAD: return km_launch_nb<GEMV_LMHEAD, true, false, W_BF16, 16, false, true>(p, B, stream, grid_out);
+            return p.attn_part ? km_launch_nb<GEMV_RESID, false, true, W_BF16, 16, false, true>(p, g, stream)
+                               : km_launch_nb<GEMV_RESID, false, false, W_BF16, 16, false, true>(p, g, stream);
+        case GEMV_GATEUP: return km_launch_nb<GEMV_GATEUP, true, false, W_BF16, 16, false, true>(p, g, stream);
+        case GEMV_LMHEAD: return km_launch_nb<GEMV_LMHEAD, true, false, W_BF16, 16, false, true>(p, g, stream);
         default: return -2;
     }
 }
 
 template <int WF>
-int km_launch_mode(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out) {
+int km_launch_mode(int mode, const GemvParams& p, const ProjGeom& g, hipStream_t stream) {
     switch (mode) {
-        case GEMV_QKV: return km_launch_t<GEMV_QKV, true, false, WF>(p, B, stream, grid_out);
+        case GEMV_QKV: return km_launch_t<GEMV_QKV, true, false, WF>(p, g, stream);
         case GEMV_RESID:
-            if (p.attn_part && p.K != p.Hq * 128) return -2;
-            if constexpr (WF == W_BF16) {
-                // the bf16 o-proj with the split merge stays on decode_mfma.hip (12.5 against 15.4 us at B = 8: the merge of 8 rows
-                // queues behind this kernel's 16 KiB weight heads); with fp8 weights this kernel is the faster one (10.3 against 10.8)
-                if (p.attn_part) return -2;
-                return km_launch_t<GEMV_RESID, false, false, WF>(p, B, stream, grid_out);
+            if constexpr (WF == W_BF16) {   // (the bf16 o-proj with the split merge stays on decode_mfma.hip: decode_km_takes)
+                return km_launch_t<GEMV_RESID, false, false, WF>(p, g, stream);
             } else {
-                return p.attn_part ? km_launch_t<GEMV_RESID, false, true, WF>(p, B, stream, grid_out) : km_launch_t<GEMV_RESID, false, false, WF>(p, B, stream, grid_out);
+                return p.attn_part ? km_launch_t<GEMV_RESID, false, true, WF>(p, g, stream) : km_launch_t<GEMV_RESID, false, false, WF>(p, g, stream);
             }
-        case GEMV_GATEUP: return km_launch_t<GEMV_GATEUP, true, false, WF>(p, B, stream, grid_out);
-        case GEMV_LMHEAD: return km_launch_t<GEMV_LMHEAD, true, false, WF>(p, B, stream, grid_out);
-        case GEMV_PLAIN: return km_launch_t<GEMV_PLAIN, false, false, WF>(p, B, stream, grid_out);
+        case GEMV_GATEUP: return km_launch_t<GEMV_GATEUP, true, false, WF>(p, g, stream);
+        case GEMV_LMHEAD: return km_launch_t<GEMV_LMHEAD, true, false, WF>(p, g, stream);
+        case GEMV_PLAIN: return km_launch_t<GEMV_PLAIN, false, false, WF>(p, g, stream);
         default: return -2;
     }
 }
 
+// the phased down kernel's shape constants by (staged rows, weight format)
+struct KdDims { int fr, nph, xp; };
+template <int NB, int WF> constexpr KdDims kd_dims() { return {KdShape<NB, WF>::FR, KdShape<NB, WF>::NPH, KdShape<NB, WF>::XP}; }
+KdDims kd_dims_of(int nb, int wf) {
+    if (nb == 8) return wf == W_MX4 ? kd_dims<8, W_MX4>() : wf == W_FP8 ? kd_dims<8, W_FP8>() : kd_dims<8, W_BF16>();
+    return wf == W_MX4 ? kd_dims<16, W_MX4>() : wf == W_FP8 ? kd_dims<16, W_FP8>() : kd_dims<16, W_BF16>();
+}
+
+// the phased down form (y = h + W x, one 16-row tile per block): K in whole load steps, at least one per wave, a wave's share within
+// NPH phases of FR fragments
+bool kmd_takes(const ProjShape& s, int B, int nb, ProjGeom* g) {
+    const int fps = s.wfmt == PW_MX4 ? 4 : s.wfmt == PW_FP8 ? 2 : 1, ks = 32 * fps;
+    const KdDims d = kd_dims_of(nb, s.wfmt);
+    if (s.K % ks || s.n_rows % 16 || s.attn_part) return false;
+    if (cdiv(s.K / ks, KM_WAVES) > d.nph * (d.fr / fps) || s.K / ks < KM_WAVES) return false;
+    if (s.exact && (!s.h32 || B > 8)) return false;
+    g->phased = 1; g->nb = nb;
+    g->n_groups = g->grid = s.n_rows / 16;
+    g->smem = (size_t)KM_WAVES * 1024 + (size_t)KM_WAVES * nb * d.xp;
+    return true;
+}
+
+// the K-split form: K in whole load steps for each of the eight waves and at most sixteen fragments per wave (K <= 4096), one block
+// per CU with at most KM_MAX_TILES tiles each, one LDS region per wave (the window [NB][XPITCH] overlaid by the partial tiles) + sumsq
+// (+ with split partials in: the merged rows)
+bool kms_takes(const ProjShape& s, int B, int nb, ProjGeom* g) {
+    const int ks = s.wfmt == PW_MX4 ? 128 : s.wfmt == PW_FP8 ? 64 : 32;
+    if (s.K % (KM_WAVES * ks) || s.K > KM_WAVES * KM_STEPS * 32 || s.n_rows % 16) return false;
+    if (s.mode == GEMV_QKV && (s.head_dim % 16 || s.head_dim < 16)) return false;
+    g->nb = nb;
+    g->n_groups = s.n_rows / 16;   // tiles
+    g->grid = min(256, g->n_groups);
+    if (s.mode == GEMV_LMHEAD) g->grid = min(g->grid, s.max_parts);
+    if (g->grid < 1) return false;
+    g->kc = cdiv(g->n_groups, g->grid);
+    if (g->kc > KM_MAX_TILES) return false;
+    if (g->kc & 1) g->kc += 1;   // the loop runs tiles in pairs
+    const size_t wreg = s.attn_part ? (size_t)g->kc * 1024 : std::max((size_t)nb * (KM_STEPS * 64 + 16), (size_t)g->kc * 1024);
+    g->smem = (size_t)KM_WAVES * wreg + KM_WAVES * 16 * 4 + (s.attn_part ? (size_t)(s.exact ? 16 : B) * s.K * 2 : 0);
+    if (g->smem > 150 * 1024) return false;
+    if (s.exact && (B > 8 || !s.h32)) return false;
+    return true;
+}
+
 }  // namespace
+
+// What this file takes (the km copy of the matrix: launch_repack_km; fp8: decode_mfma.hip's e4m3 tiles of the permuted rows; MXFP4 tiles).
+// 17-64 rows: decode_kmp.hip's answer (bf16 / fp8).  Exact numerics: 1-8 rows (two terms per batch row in the sixteen MFMA columns), bf16.
+bool decode_km_takes(const ProjShape& s, int B, ProjGeom* out) {
+    ProjGeom g = {};
+    bool ok = false;
+    const bool kfits = s.K % (KM_WAVES * 32) == 0 && s.K <= KM_WAVES * KM_STEPS * 32;
+    if (B < 1 || B > EMMAX_MAX_DECODE_BATCH || s.mode < GEMV_QKV || s.mode > GEMV_PLAIN) return false;
+    if (B > 16) return s.wfmt != PW_MX4 && decode_kmp_takes(s, B, out);   // two batch tiles: decode_kmp.hip (MXFP4 tiles: this file's kernels only)
+    if (s.attn_part && (s.mode != GEMV_RESID || s.K != s.Hq * 128)) return false;
+    if (s.exact) {
+        if (B > 8 || s.wfmt != PW_BF16 || s.mode == GEMV_PLAIN) return false;
+        // RESID launches without split partials (fp32 rows in p.x): the o-proj behind a one-split attention launch on the K-split kernel when its K fits,
+        // the down projection (and any other K) on the phased kernel
+        ok = (s.mode == GEMV_RESID && !s.attn_part && !kfits) ? kmd_takes(s, B, 16, &g) : kms_takes(s, B, 16, &g);
+    } else if (s.mode == GEMV_RESID && !s.attn_part && s.K > KM_WAVES * KM_STEPS * 32) {   // the down projection: the phased form (natural row order copy)
+        // tuning switch km_down = 0: decode_mfma.hip, the A/B partner (no other kernel reads MXFP4 tiles: no switch there)
+        ok = (s.wfmt == PW_MX4 || emmax_tune().km_down) && kmd_takes(s, B, B <= 8 ? 8 : 16, &g);
+    } else {
+        // the bf16 o-proj with the split merge stays on decode_mfma.hip (12.5 against 15.4 us at B = 8: the merge of 8 rows
+        // queues behind this kernel's 16 KiB weight heads); with fp8 weights this kernel is the faster one (10.3 against 10.8).
+        // MXFP4: split partials of 9-16 rows x K do not fit the LDS stage, those batches exist in the one-split form only
+        if (s.attn_part && (s.wfmt == PW_BF16 || (s.wfmt == PW_MX4 && B > 8))) return false;
+        g.roll = s.wfmt != PW_MX4 && emmax_tune().km_roll;   // (the MX4 form always refills step by step)
+        ok = kms_takes(s, B, B <= 8 ? 8 : 16, &g);
+    }
+    if (ok && out) *out = g;
+    return ok;
+}
 
 // raise the dynamic-LDS limit of every instantiation (call once, outside graph capture)
 int decode_km_init() {
@@ -882,25 +925,22 @@ int launch_dequant_mx4(const void* tiles, const void* scales, void* dst, int ld,
 }
 
 // p.W: the km copy of the matrix (launch_repack_km; fp8: decode_mfma.hip's e4m3 tiles of the permuted rows + p.wscale in the same
-// row order).  -2: shape outside this kernel (K % 256, K > 4096, more than 8 tiles per block) -- the caller uses decode_mfma.hip.
-int launch_decode_km(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out) {
-    if (B < 1 || B > EMMAX_MAX_DECODE_BATCH) return -2;
-    if (B > 16 && p.w4_scales) return -2;   // MXFP4 tiles: this file's kernels only (1-16 rows)
-    if (B > 16) return launch_decode_kmp(mode, p, B, stream, grid_out);   // two batch tiles: decode_kmp.hip
+// row order).  -2: decode_km_takes says no (K % 256, K > 4096, more than 8 tiles per block ...) -- the caller uses decode_mfma.hip.
+int launch_decode_km(int mode, const GemvParams& p_in, int B, hipStream_t stream, int* grid_out, const ProjGeom* geom) {
+    ProjGeom g;
+    if (geom) g = *geom;
+    else if (!decode_km_takes(proj_shape(mode, p_in), B, &g)) return -2;
+    if (B > 16) return launch_decode_kmp(mode, p_in, B, stream, grid_out, &g);   // two batch tiles: decode_kmp.hip
     if (decode_km_init() != 0) return -4;
-    if (p.exact) {   // exact numerics: batch <= 8 (two terms per batch row in the sixteen MFMA columns), bf16 weights
-        if (B > 8 || p.wscale || p.w4_scales) return -2;
-        // RESID launches without split partials (fp32 rows in p.x): the o-proj behind a one-split attention launch on the K-split kernel when its K fits,
-        // the down projection (and any other K) on the phased kernel
-        if (mode == GEMV_RESID && !p.attn_part && (p.K % (KM_WAVES * 32) || p.K > KM_WAVES * KM_STEPS * 32)) return kmd_launch<W_BF16, 16, true>(p, B, stream);
-        return km_launch_mode_x(mode, p, B, stream, grid_out);
+    GemvParams p = p_in;
+    p.batch = B; p.n_groups = g.n_groups; p.kc = g.kc;
+    if (grid_out) *grid_out = g.grid;
+    if (p.exact) return g.phased ? kmd_launch<W_BF16, 16, true>(p, g, stream) : km_launch_mode_x(mode, p, g, stream);
+    if (g.phased) {
+        if (p.w4_scales) return g.nb == 8 ? kmd_launch<W_MX4, 8>(p, g, stream) : kmd_launch<W_MX4, 16>(p, g, stream);
+        if (g.nb == 8) return p.wscale ? kmd_launch<W_FP8, 8>(p, g, stream) : kmd_launch<W_BF16, 8>(p, g, stream);
+        return p.wscale ? kmd_launch<W_FP8, 16>(p, g, stream) : kmd_launch<W_BF16, 16>(p, g, stream);
     }
-    if (mode == GEMV_RESID && !p.attn_part && p.K > KM_WAVES * KM_STEPS * 32) {   // the down projection: two K phases (natural row order copy)
-        if (p.w4_scales) return B <= 8 ? kmd_launch<W_MX4, 8>(p, B, stream) : kmd_launch<W_MX4, 16>(p, B, stream);   // (no other kernel reads these tiles: no switch)
-        if (!emmax_tune().km_down) return -2;   // A/B partner: decode_mfma.hip
-        if (B <= 8) return p.wscale ? kmd_launch<W_FP8, 8>(p, B, stream) : kmd_launch<W_BF16, 8>(p, B, stream);
-        return p.wscale ? kmd_launch<W_FP8, 16>(p, B, stream) : kmd_launch<W_BF16, 16>(p, B, stream);
-    }
-    if (p.w4_scales) return km_launch_mode<W_MX4>(mode, p, B, stream, grid_out);
-    return p.wscale ? km_launch_mode<W_FP8>(mode, p, B, stream, grid_out) : km_launch_mode<W_BF16>(mode, p, B, stream, grid_out);
+    if (p.w4_scales) return km_launch_mode<W_MX4>(mode, p, g, stream);
+    return p.wscale ? km_launch_mode<W_FP8>(mode, p, g, stream) : km_launch_mode<W_BF16>(mode, p, g, stream);
 }

@@ -389,8 +389,9 @@ int kp_launch_tm(const GemvParams& p, int grid, bool r32, bool init_only, hipStr
     return kp_launch_tf<MODE, NORM, TMAX, NPH, false, NH>(p, grid, r32, init_only, stream);
 }
 
+// g: the geometry decode_kmp_takes returned (TMAX tiles per block, NPH phases, NH halves); init_only: every instantiation's LDS limit
 template <int MODE, bool NORM>
-int kp_launch_t(GemvParams p, int B, hipStream_t stream, int* grid_out, bool init_only) {
+int kp_launch_t(const GemvParams& p, const ProjGeom& g, hipStream_t stream, bool init_only) {
     if (init_only) {
         int r = kp_launch_tm<MODE, NORM, 1>(p, 0, false, true, stream);
         if (!r) r = kp_launch_tm<MODE, NORM, 3>(p, 0, false, true, stream);
@@ -404,58 +405,68 @@ int kp_launch_t(GemvParams p, int B, hipStream_t stream, int* grid_out, bool ini
         if constexpr (MODE == GEMV_GATEUP) { if (!r) r = kp_launch_tm<MODE, NORM, 6, 8, 2>(p, 0, false, true, stream); }
         return r;
     }
-    if (B > 32) {
-        // 33-64 rows (NH = 2): qkv (3 tiles per block), the o-proj (1), gate/up (6) with K within eight phases of a four-way split; the down projection and
-        // the lm-head run as two launches of <= 32 rows (model.hip)
-        const int ks2 = p.wscale ? 64 : 32;
-        if (p.K % ks2 || p.K / ks2 < 4 || cdiv(p.K / ks2, 4) * ks2 > 8 * KP_PH * 32 || p.n_rows % 16 || p.attn_part) return -2;
-        if (MODE == GEMV_QKV && (p.head_dim % 16 || p.head_dim < 16)) return -2;
-        p.batch = B;
-        p.n_groups = p.n_rows / 16;
-        const int grid2 = p.n_groups < 256 ? p.n_groups : 256;
-        const int tpb2 = cdiv(p.n_groups, grid2);
-        if (grid_out) *grid_out = grid2;
-        const bool r32b = MODE == GEMV_RESID && p.h32 != nullptr;
-        if constexpr (MODE == GEMV_QKV) { if (tpb2 <= 3) return kp_launch_tm<MODE, NORM, 3, 8, 2>(p, grid2, r32b, false, stream); }
-        if constexpr (MODE == GEMV_RESID) { if (tpb2 <= 1) return kp_launch_tm<MODE, NORM, 1, 8, 2>(p, grid2, r32b, false, stream); }
-        if constexpr (MODE == GEMV_GATEUP) { if (tpb2 <= 6) return kp_launch_tm<MODE, NORM, 6, 8, 2>(p, grid2, r32b, false, stream); }
-        return -2;
-    }
-    // K in whole load steps (32 elements; 64 with fp8 tiles), at least one per wave, a wave's share within eleven phases
-    const int ks_el = p.wscale ? 64 : 32;
-    if (p.K % ks_el || p.K / ks_el < KP_WAVES || cdiv(p.K / ks_el, KP_WAVES) * ks_el > 11 * KP_PH * 32 || p.n_rows % 16 || p.attn_part) return -2;
-    if (MODE == GEMV_QKV && (p.head_dim % 16 || p.head_dim < 16)) return -2;
-    p.batch = B;
-    p.n_groups = p.n_rows / 16;   // tiles
-    // one block per CU while that leaves at most 6 tiles per block; beyond (lm-head: 2008 tiles) more blocks of 6
-    const int grid = cdiv(p.n_groups, 256) <= 6 ? (p.n_groups < 256 ? p.n_groups : 256) : cdiv(p.n_groups, 6);
-    if (grid < 1 || (MODE == GEMV_LMHEAD && grid > p.max_parts)) return -2;
-    if (grid_out) *grid_out = grid;
-    const int tpb = cdiv(p.n_groups, grid);
     const bool r32 = MODE == GEMV_RESID && p.h32 != nullptr;
-    if (cdiv(p.K / ks_el, KP_WAVES) * ks_el > 4 * KP_PH * 32) {   // the down projection: eleven phases, one tile per block
-        if constexpr (MODE == GEMV_RESID || MODE == GEMV_PLAIN) {
-            if (tpb <= 1) return kp_launch_tm<MODE, NORM, 1, 11>(p, grid, r32, false, stream);
-        }
+    if (g.nh == 2) {
+        if constexpr (MODE == GEMV_QKV) return kp_launch_tm<MODE, NORM, 3, 8, 2>(p, g.grid, r32, false, stream);
+        if constexpr (MODE == GEMV_RESID) return kp_launch_tm<MODE, NORM, 1, 8, 2>(p, g.grid, r32, false, stream);
+        if constexpr (MODE == GEMV_GATEUP) return kp_launch_tm<MODE, NORM, 6, 8, 2>(p, g.grid, r32, false, stream);
         return -2;
     }
-    if (tpb <= 1) return kp_launch_tm<MODE, NORM, 1>(p, grid, r32, false, stream);
-    if (tpb <= 3) return kp_launch_tm<MODE, NORM, 3>(p, grid, r32, false, stream);
-    return kp_launch_tm<MODE, NORM, 6>(p, grid, r32, false, stream);
+    if (g.nph == 11) {   // the down projection: eleven phases, one tile per block
+        if constexpr (MODE == GEMV_RESID || MODE == GEMV_PLAIN) return kp_launch_tm<MODE, NORM, 1, 11>(p, g.grid, r32, false, stream);
+        return -2;
+    }
+    if (g.tmax == 1) return kp_launch_tm<MODE, NORM, 1>(p, g.grid, r32, false, stream);
+    if (g.tmax == 3) return kp_launch_tm<MODE, NORM, 3>(p, g.grid, r32, false, stream);
+    return kp_launch_tm<MODE, NORM, 6>(p, g.grid, r32, false, stream);
 }
 
-int kp_dispatch(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out, bool init_only) {
+int kp_dispatch(int mode, const GemvParams& p, const ProjGeom& g, hipStream_t stream, bool init_only) {
     switch (mode) {
-        case GEMV_QKV: return kp_launch_t<GEMV_QKV, true>(p, B, stream, grid_out, init_only);
-        case GEMV_RESID: return kp_launch_t<GEMV_RESID, false>(p, B, stream, grid_out, init_only);
-        case GEMV_GATEUP: return kp_launch_t<GEMV_GATEUP, true>(p, B, stream, grid_out, init_only);
-        case GEMV_LMHEAD: return kp_launch_t<GEMV_LMHEAD, true>(p, B, stream, grid_out, init_only);
-        case GEMV_PLAIN: return kp_launch_t<GEMV_PLAIN, false>(p, B, stream, grid_out, init_only);
+        case GEMV_QKV: return kp_launch_t<GEMV_QKV, true>(p, g, stream, init_only);
+        case GEMV_RESID: return kp_launch_t<GEMV_RESID, false>(p, g, stream, init_only);
+        case GEMV_GATEUP: return kp_launch_t<GEMV_GATEUP, true>(p, g, stream, init_only);
+        case GEMV_LMHEAD: return kp_launch_t<GEMV_LMHEAD, true>(p, g, stream, init_only);
+        case GEMV_PLAIN: return kp_launch_t<GEMV_PLAIN, false>(p, g, stream, init_only);
         default: return -2;
     }
 }
 
 }  // namespace
+
+// What this file takes: 17-64 rows, bf16 or fp8 tiles of the km copy, no split partials.  17-32 rows: K in whole load steps (32 elements; 64
+// with fp8 tiles), at least one per wave, a wave's share within four phases (up to 6 tiles per block) or eleven (the down projection: one
+// tile per block).  33-64 rows (two halves of four waves): qkv (3 tiles per block), the o-proj (1), gate/up (6) with K within eight phases of
+// a four-way split; the down projection and the lm-head run as two launches of <= 32 rows (step.hip: stage_chunk)
+bool decode_kmp_takes(const ProjShape& s, int B, ProjGeom* out) {
+    if (B < 17 || B > 64 || s.mode < GEMV_QKV || s.mode > GEMV_PLAIN || s.wfmt == PW_MX4) return false;
+    const int ks = s.wfmt == PW_FP8 ? 64 : 32, kw = B > 32 ? 4 : KP_WAVES, max_ph = B > 32 ? 8 : 11;
+    if (s.K % ks || s.K / ks < kw || cdiv(s.K / ks, kw) * ks > max_ph * KP_PH * 32 || s.n_rows % 16 || s.attn_part) return false;
+    if (s.mode == GEMV_QKV && (s.head_dim % 16 || s.head_dim < 16)) return false;
+    ProjGeom g = {};
+    g.n_groups = s.n_rows / 16;   // tiles
+    if (B > 32) {
+        g.grid = min(g.n_groups, 256);
+        g.tmax = s.mode == GEMV_QKV ? 3 : s.mode == GEMV_RESID ? 1 : s.mode == GEMV_GATEUP ? 6 : 0;
+        g.nph = 8; g.nh = 2;
+        if (g.grid < 1 || cdiv(g.n_groups, g.grid) > g.tmax) return false;
+    } else {
+        // one block per CU while that leaves at most 6 tiles per block; beyond (lm-head: 2008 tiles) more blocks of 6
+        g.grid = cdiv(g.n_groups, 256) <= 6 ? min(g.n_groups, 256) : cdiv(g.n_groups, 6);
+        if (g.grid < 1 || (s.mode == GEMV_LMHEAD && g.grid > s.max_parts)) return false;
+        const int tpb = cdiv(g.n_groups, g.grid);
+        g.nh = 1;
+        if (cdiv(s.K / ks, KP_WAVES) * ks > 4 * KP_PH * 32) {   // the down projection: eleven phases, one tile per block
+            if ((s.mode != GEMV_RESID && s.mode != GEMV_PLAIN) || tpb > 1) return false;
+            g.tmax = 1; g.nph = 11;
+        } else {
+            g.tmax = tpb <= 1 ? 1 : tpb <= 3 ? 3 : 6; g.nph = 4;
+        }
+    }
+    g.smem = g.tmax == 1 ? kp_smem_bytes<1>() : g.tmax == 3 ? kp_smem_bytes<3>() : kp_smem_bytes<6>();
+    if (out) *out = g;
+    return true;
+}
 
 // raise the dynamic-LDS limit of every instantiation (call once, outside graph capture)
 int decode_kmp_init() {
@@ -463,15 +474,20 @@ int decode_kmp_init() {
     if (done == 0) return 0;
     GemvParams p = {};
     int r = 0;
-    for (int mode = GEMV_QKV; mode <= GEMV_PLAIN && r == 0; ++mode) r = kp_dispatch(mode, p, 32, nullptr, nullptr, true);
+    for (int mode = GEMV_QKV; mode <= GEMV_PLAIN && r == 0; ++mode) r = kp_dispatch(mode, p, ProjGeom{}, nullptr, true);
     done = r == 0 ? 0 : -4;
     return done;
 }
 
 // p.W: the km copy of the matrix (launch_repack_km; fp8: decode_mfma.hip's e4m3 tiles of the permuted rows + p.wscale in the same row
-// order).  -2: shape outside this kernel (K not in whole load steps, a wave's share beyond eleven phases, the o-proj's split merge)
-int launch_decode_kmp(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out) {
-    if (B < 17 || B > 64) return -2;
+// order).  -2: decode_kmp_takes says no (K not in whole load steps, a wave's share beyond eleven phases, the o-proj's split merge)
+int launch_decode_kmp(int mode, const GemvParams& p_in, int B, hipStream_t stream, int* grid_out, const ProjGeom* geom) {
+    ProjGeom g;
+    if (geom) g = *geom;
+    else if (!decode_kmp_takes(proj_shape(mode, p_in), B, &g)) return -2;
     if (decode_kmp_init() != 0) return -4;
-    return kp_dispatch(mode, p, B, stream, grid_out, false);
+    GemvParams p = p_in;
+    p.batch = B; p.n_groups = g.n_groups;
+    if (grid_out) *grid_out = g.grid;
+    return kp_dispatch(mode, p, g, stream, false);
 }

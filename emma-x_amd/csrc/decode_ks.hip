@@ -519,63 +519,36 @@ __global__ __launch_bounds__(KS_NT, 4) void emmax_decode_ks_kernel(GemvParams p)
 }
 
 template <int B, int MODE, bool NORM, int XS, int CPL, bool R32, bool EX = false>
-int ks_launch_r(GemvParams p, hipStream_t stream, int* grid_out) {
-    constexpr int RB = KsShape<B, CPL>::RB;
-    int grid = min(512, p.n_groups);
-    if (p.max_grid > 0) grid = min(grid, p.max_grid);
-    if (MODE == GEMV_LMHEAD) grid = min(grid, p.max_parts);
-    if (grid < 1) return -2;
-    const int pairs_max = cdiv(p.n_groups, grid);
-    if (pairs_max > 64) return -2;   // the epilogue maps one lane to a pair
-    p.kc = cdiv(2 * pairs_max, RB) * RB;
-    const size_t smem = (size_t)(KS_WAVES * B * p.kc + KS_WAVES * B) * sizeof(float);
-    if (grid_out) *grid_out = grid;
-    hipLaunchKernelGGL((emmax_decode_ks_kernel<B, MODE, NORM, XS, CPL, R32, EX>), dim3(grid), dim3(KS_NT), smem, stream, p);
+int ks_launch_r(const GemvParams& p, const ProjGeom& g, hipStream_t stream) {
+    hipLaunchKernelGGL((emmax_decode_ks_kernel<B, MODE, NORM, XS, CPL, R32, EX>), dim3(g.grid), dim3(KS_NT), g.smem, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 // the fp32 residual stream concerns the modes that read (NORM) or update (RESID) the hidden rows; the embedding gather exists for qkv only
+// (decode_ks_takes has refused every other combination: the -2 below are the branches no instantiation exists for)
 template <int B, int MODE, bool NORM, bool XATTN, int CPL>
-int ks_launch_t(const GemvParams& p, hipStream_t stream, int* grid_out) {
+int ks_launch_t(const GemvParams& p, const ProjGeom& g, hipStream_t stream) {
     constexpr bool touches_h = NORM || MODE == GEMV_RESID;
     if (p.exact) {   // exact numerics: the projections of a decode step only, always on the fp32 stream
         if constexpr (MODE == GEMV_PLAIN) return -2;
         else {
-            if (!p.h32) return -2;
             if constexpr (MODE == GEMV_QKV) {
-                if (p.x_tok) return ks_launch_r<B, MODE, NORM, XS_EMBED, CPL, true, true>(p, stream, grid_out);
+                if (p.x_tok) return ks_launch_r<B, MODE, NORM, XS_EMBED, CPL, true, true>(p, g, stream);
             }
-            if (p.x_tok) return -2;
-            return ks_launch_r<B, MODE, NORM, XATTN ? XS_ATTN : XS_GLOBAL, CPL, true, true>(p, stream, grid_out);
+            return ks_launch_r<B, MODE, NORM, XATTN ? XS_ATTN : XS_GLOBAL, CPL, true, true>(p, g, stream);
         }
     }
     if constexpr (MODE == GEMV_QKV) {
-        if (p.x_tok) return p.h32 ? ks_launch_r<B, MODE, NORM, XS_EMBED, CPL, true>(p, stream, grid_out) : ks_launch_r<B, MODE, NORM, XS_EMBED, CPL, false>(p, stream, grid_out);
-    } else if (p.x_tok) return -2;
-    if constexpr (touches_h) {
-        if (p.h32) return ks_launch_r<B, MODE, NORM, XATTN ? XS_ATTN : XS_GLOBAL, CPL, true>(p, stream, grid_out);
-    } else if (p.h32) return -2;
-    return ks_launch_r<B, MODE, NORM, XATTN ? XS_ATTN : XS_GLOBAL, CPL, false>(p, stream, grid_out);
-}
-
-// pairs / shift of a mode
-template <int MODE>
-int ks_prepare(GemvParams& p) {
-    if (MODE == GEMV_QKV || MODE == GEMV_GATEUP) p.n_groups = p.n_rows / 2;
-    else p.n_groups = (p.n_rows + 1) / 2;
-    p.n_pairs = p.n_groups;
-    if (MODE == GEMV_QKV) {
-        p.ks_shift = 0;
-        while ((2 << p.ks_shift) < p.head_dim) ++p.ks_shift;
-        if ((2 << p.ks_shift) != p.head_dim) return -2;
+        if (p.x_tok) return p.h32 ? ks_launch_r<B, MODE, NORM, XS_EMBED, CPL, true>(p, g, stream) : ks_launch_r<B, MODE, NORM, XS_EMBED, CPL, false>(p, g, stream);
     }
-    return 0;
+    if constexpr (touches_h) {
+        if (p.h32) return ks_launch_r<B, MODE, NORM, XATTN ? XS_ATTN : XS_GLOBAL, CPL, true>(p, g, stream);
+    }
+    return ks_launch_r<B, MODE, NORM, XATTN ? XS_ATTN : XS_GLOBAL, CPL, false>(p, g, stream);
 }
 
 template <int MODE, bool NORM, bool XATTN>
-int ks_launch_mode(GemvParams p, int B, hipStream_t stream, int* grid_out) {
-    if (ks_prepare<MODE>(p)) return -2;
-    const int cpl = cdiv(p.K >> 6, 64);
-#define KS_CASE(BB, CC) if (B == BB && cpl == CC) return ks_launch_t<BB, MODE, NORM, XATTN, CC>(p, stream, grid_out)
+int ks_launch_mode(const GemvParams& p, int B, const ProjGeom& g, hipStream_t stream) {
+#define KS_CASE(BB, CC) if (B == BB && g.cpl == CC) return ks_launch_t<BB, MODE, NORM, XATTN, CC>(p, g, stream)
     KS_CASE(1, 1); KS_CASE(1, 2); KS_CASE(1, 3); KS_CASE(2, 1); KS_CASE(2, 2); KS_CASE(2, 3);
 #undef KS_CASE
     return -2;
@@ -586,30 +559,63 @@ int ks_launch_mode(GemvParams p, int B, hipStream_t stream, int* grid_out) {
 // tuning switch `ks` = 0 keeps the batch 1-2 bf16 projections on decode.hip's LDS-staged GEMV (the A/B partner)
 bool decode_ks_enabled() { return emmax_tune().ks != 0; }
 
-// -2: shape outside this kernel (the caller falls back to launch_decode_gemv's LDS-staged kernel); bf16 weights, batch 1-2,
-// plain stream ordering, K a multiple of 64 and at most 12288 (three 16-byte chunks per lane)
-int launch_decode_ks(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out) {
-    if (B < 1 || B > 2 || p.wscale) return -2;
-    if (p.K % 64 || p.K > 64 * 64 * 3 || p.ldw % 8 || p.ldx % 8 || p.K < 64) return -2;
+// What this file takes: bf16 weights, batch 1-2, K a multiple of 64 and at most 12288 (three 16-byte chunks per lane), at most 64 row
+// pairs per block (the epilogue maps one lane to a pair).  Geometry: 2 blocks per CU, block b owns a contiguous range of row PAIRS;
+// dynamic LDS float part[8 waves][B][rows_cap] + float sumsq[8][B].
+bool decode_ks_takes(const ProjShape& s, int B, ProjGeom* out) {
+    if (B < 1 || B > 2 || s.wfmt != PW_BF16) return false;
+    if (s.K % 64 || s.K > 64 * 64 * 3 || !s.ld_ok || s.K < 64) return false;
+    if (s.mode < GEMV_QKV || s.mode > GEMV_PLAIN) return false;
+    ProjGeom g = {};
+    int max_grid = s.max_grid;
+    if (s.mode == GEMV_RESID && s.attn_part) {
+        if (s.K != s.Hq * 128) return false;   // the merge maps 16 chunks to a 128-wide head
+        // The o-proj with the split merge in its prologue: every WAVE merges the chunks of its own four heads (24 loads in
+        // flight per lane, no LDS stage, no barrier).  With 512 blocks that is twice the L2 reads of decode.hip's 256-block
+        // LDS-staged merge and slower (12.2 against 10.1 us at B = 1, 7B); with ONE block per CU it is the faster one
+        // (9.3 us: step 2.624 -> 2.594 ms/token).  Tuning switches ks_oproj = 0: decode.hip's kernel; ks_oproj_grid.
+        if (!emmax_tune().ks_oproj) return false;
+        max_grid = emmax_tune().ks_oproj_grid;
+    }
+    // the fp32 residual stream concerns the modes that read or update the hidden rows; the embedding gather exists for qkv only; exact
+    // numerics: the projections of a decode step only, always on the fp32 stream
+    if (s.x_tok && s.mode != GEMV_QKV) return false;
+    if (s.exact ? (s.mode == GEMV_PLAIN || !s.h32) : (s.mode == GEMV_PLAIN && s.h32)) return false;
+    g.n_groups = (s.mode == GEMV_QKV || s.mode == GEMV_GATEUP) ? s.n_rows / 2 : (s.n_rows + 1) / 2;   // pairs
+    if (s.mode == GEMV_QKV) {
+        while ((2 << g.shift) < s.head_dim) ++g.shift;
+        if ((2 << g.shift) != s.head_dim) return false;
+    }
+    g.cpl = cdiv(s.K >> 6, 64);
+    const int rb = B == 1 ? (g.cpl == 1 ? KsShape<1, 1>::RB : g.cpl == 2 ? KsShape<1, 2>::RB : KsShape<1, 3>::RB)
+                          : (g.cpl == 1 ? KsShape<2, 1>::RB : g.cpl == 2 ? KsShape<2, 2>::RB : KsShape<2, 3>::RB);
+    g.grid = min(512, g.n_groups);
+    if (max_grid > 0) g.grid = min(g.grid, max_grid);
+    if (s.mode == GEMV_LMHEAD) g.grid = min(g.grid, s.max_parts);
+    if (g.grid < 1) return false;
+    const int pairs_max = cdiv(g.n_groups, g.grid);
+    if (pairs_max > 64) return false;   // the epilogue maps one lane to a pair
+    g.kc = cdiv(2 * pairs_max, rb) * rb;
+    g.smem = (size_t)(KS_WAVES * B * g.kc + KS_WAVES * B) * sizeof(float);
+    if (out) *out = g;
+    return true;
+}
+
+// -2: decode_ks_takes says no (the caller falls back to launch_decode_gemv's LDS-staged kernel); plain stream ordering
+int launch_decode_ks(int mode, const GemvParams& p_in, int B, hipStream_t stream, int* grid_out, const ProjGeom* geom) {
+    ProjGeom g;
+    if (geom) g = *geom;
+    else if (!decode_ks_takes(proj_shape(mode, p_in), B, &g)) return -2;
+    GemvParams p = p_in;
+    p.n_groups = p.n_pairs = g.n_groups; p.ks_shift = g.shift; p.kc = g.kc;
+    if (grid_out) *grid_out = g.grid;
     switch (mode) {
-        case GEMV_QKV: return ks_launch_mode<GEMV_QKV, true, false>(p, B, stream, grid_out);
+        case GEMV_QKV: return ks_launch_mode<GEMV_QKV, true, false>(p, B, g, stream);
         case GEMV_RESID:
-            if (p.attn_part && (p.K != p.Hq * 128)) return -2;   // the merge maps 16 chunks to a 128-wide head
-            // The o-proj with the split merge in its prologue: every WAVE merges the chunks of its own four heads (24 loads in
-            // flight per lane, no LDS stage, no barrier).  With 512 blocks that is twice the L2 reads of decode.hip's 256-block
-            // LDS-staged merge and slower (12.2 against 10.1 us at B = 1, 7B); with ONE block per CU it is the faster one
-            // (9.3 us: step 2.624 -> 2.594 ms/token).  Tuning switches ks_oproj = 0: decode.hip's kernel; ks_oproj_grid.
-            if (p.attn_part) {
-                if (!emmax_tune().ks_oproj) return -2;
-                GemvParams q = p;
-                q.max_grid = emmax_tune().ks_oproj_grid;
-                return ks_launch_mode<GEMV_RESID, false, true>(q, B, stream, grid_out);
-            }
-            return ks_launch_mode<GEMV_RESID, false, false>(p, B, stream, grid_out);
-        case GEMV_GATEUP: return ks_launch_mode<GEMV_GATEUP, true, false>(p, B, stream, grid_out);
-        case GEMV_LMHEAD: return ks_launch_mode<GEMV_LMHEAD, true, false>(p, B, stream, grid_out);
-        case GEMV_PLAIN: return ks_launch_mode<GEMV_PLAIN, false, false>(p, B, stream, grid_out);
-        default: return -2;
+            return p.attn_part ? ks_launch_mode<GEMV_RESID, false, true>(p, B, g, stream) : ks_launch_mode<GEMV_RESID, false, false>(p, B, g, stream);
+        case GEMV_GATEUP: return ks_launch_mode<GEMV_GATEUP, true, false>(p, B, g, stream);
+        case GEMV_LMHEAD: return ks_launch_mode<GEMV_LMHEAD, true, false>(p, B, g, stream);
+        default: return ks_launch_mode<GEMV_PLAIN, false, false>(p, B, g, stream);
     }
 }
 

@@ -617,26 +617,36 @@ static int mfma_kc(int B, int K, int tiles, int kstep) {
     return cdiv(cdiv(K, nph), kstep) * kstep;
 }
 
-template <int MODE, bool NORM, bool XATTN, bool FP8>
-static int launch_mfma_t(GemvParams p, int B, hipStream_t stream, int* grid_out) {
-    constexpr int TILES = (MODE == GEMV_QKV || MODE == GEMV_GATEUP) ? 2 : 1;
-    if (FP8 && !p.wscale) return -1;
-    if (p.K % (FP8 ? 64 : 32) || p.n_rows % (16 * TILES)) {
-        if (!(MODE == GEMV_LMHEAD && p.n_rows % 16 == 0)) return -1;
+// What this file takes: 1-8 rows of the fragment-major copy (bf16, or e4m3 tiles + per-row scales); K in whole k-steps (32 elements; fp8: 64),
+// rows in whole tiles (qkv / gate-up: pairs of tiles); the modes with a norm prologue in ONE K phase; head_dim / 32 a power of two (qkv)
+bool decode_mfma_takes(const ProjShape& s, int B, ProjGeom* out) {
+    if (B < 1 || B > MFMA_MAX_B || s.mode < GEMV_QKV || s.mode > GEMV_PLAIN || s.wfmt == PW_MX4) return false;
+    const bool fp8 = s.wfmt == PW_FP8, norm = s.mode == GEMV_QKV || s.mode == GEMV_GATEUP || s.mode == GEMV_LMHEAD;
+    const int tiles = (s.mode == GEMV_QKV || s.mode == GEMV_GATEUP) ? 2 : 1, kstep = fp8 ? 64 : 32;
+    if (s.K % kstep || s.n_rows % (16 * tiles)) {
+        if (!(s.mode == GEMV_LMHEAD && s.n_rows % 16 == 0)) return false;
     }
+    ProjGeom g = {};
+    g.kc = mfma_kc(B, s.K, tiles, kstep);
+    if (norm && g.kc != s.K) return false;
+    g.n_groups = s.n_rows / (16 * tiles);
+    g.grid = min(256, g.n_groups);
+    if (s.mode == GEMV_LMHEAD) g.grid = min(g.grid, s.max_parts);
+    if (s.mode == GEMV_QKV) {
+        while ((32 << g.shift) < s.head_dim) ++g.shift;
+        if ((32 << g.shift) != s.head_dim) return false;   // head_dim / 32 must be a power of two
+    }
+    g.smem = mfma_smem(B, g.kc, tiles);
+    if (out) *out = g;
+    return true;
+}
+
+template <int MODE, bool NORM, bool XATTN, bool FP8>
+static int launch_mfma_t(GemvParams p, int B, const ProjGeom& g, hipStream_t stream) {
     p.batch = B;
     p.x_bar = XATTN ? 0 : emmax_tune().mfma_xbar;   // default on for the prologues that load activations ahead of the head
-    p.kc = mfma_kc(B, p.K, TILES, FP8 ? 64 : 32);
-    if (NORM && p.kc != p.K) return -1;
-    p.n_groups = p.n_rows / (16 * TILES);
-    int grid = min(256, p.n_groups);
-    if (MODE == GEMV_LMHEAD) grid = min(grid, p.max_parts);
-    if (grid_out) *grid_out = grid;
-    if (MODE == GEMV_QKV) {
-        p.qk_shift = 0;
-        while ((32 << p.qk_shift) < p.head_dim) ++p.qk_shift;
-        if ((32 << p.qk_shift) != p.head_dim) return -1;   // head_dim / 32 must be a power of two
-    }
+    p.kc = g.kc; p.n_groups = g.n_groups; p.qk_shift = g.shift;
+    const int grid = g.grid;
     {   // work split (see the kernel): stream-K when it applies, whole tasks otherwise
         const int KT = p.K / (FP8 ? 64 : 32);
         const bool sk = p.sk_ws != nullptr && p.kc == p.K && KT % GW == 0 && KT / GW >= 2 && p.n_groups >= grid &&
@@ -647,27 +657,29 @@ static int launch_mfma_t(GemvParams p, int B, hipStream_t stream, int* grid_out)
         p.sk_r = total % grid;
         p.sk_magic = sk ? (unsigned)(((1ull << 32) + (unsigned)p.sk_kt8 - 1) / (unsigned)p.sk_kt8) : 0u;
     }
-    const size_t smem = mfma_smem(B, p.kc, TILES);
-    hipLaunchKernelGGL((emmax_decode_mfma_kernel<MODE, NORM, XATTN, FP8>), dim3(grid), dim3(GW * 64), smem, stream, p);
+    hipLaunchKernelGGL((emmax_decode_mfma_kernel<MODE, NORM, XATTN, FP8>), dim3(grid), dim3(GW * 64), g.smem, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
 template <bool FP8>
-static int launch_mfma_mode(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out) {
+static int launch_mfma_mode(int mode, const GemvParams& p, int B, const ProjGeom& g, hipStream_t stream) {
     switch (mode) {
-        case GEMV_QKV: return launch_mfma_t<GEMV_QKV, true, false, FP8>(p, B, stream, grid_out);
+        case GEMV_QKV: return launch_mfma_t<GEMV_QKV, true, false, FP8>(p, B, g, stream);
         case GEMV_RESID:
-            return p.attn_part ? launch_mfma_t<GEMV_RESID, false, true, FP8>(p, B, stream, grid_out) : launch_mfma_t<GEMV_RESID, false, false, FP8>(p, B, stream, grid_out);
-        case GEMV_GATEUP: return launch_mfma_t<GEMV_GATEUP, true, false, FP8>(p, B, stream, grid_out);
-        case GEMV_LMHEAD: return launch_mfma_t<GEMV_LMHEAD, true, false, FP8>(p, B, stream, grid_out);
-        case GEMV_PLAIN: return launch_mfma_t<GEMV_PLAIN, false, false, FP8>(p, B, stream, grid_out);
-        default: return -1;
+            return p.attn_part ? launch_mfma_t<GEMV_RESID, false, true, FP8>(p, B, g, stream) : launch_mfma_t<GEMV_RESID, false, false, FP8>(p, B, g, stream);
+        case GEMV_GATEUP: return launch_mfma_t<GEMV_GATEUP, true, false, FP8>(p, B, g, stream);
+        case GEMV_LMHEAD: return launch_mfma_t<GEMV_LMHEAD, true, false, FP8>(p, B, g, stream);
+        default: return launch_mfma_t<GEMV_PLAIN, false, false, FP8>(p, B, g, stream);
     }
 }
 
-int launch_decode_mfma(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out) {
-    if (B < 1 || B > MFMA_MAX_B) return -1;
-    return p.wscale ? launch_mfma_mode<true>(mode, p, B, stream, grid_out) : launch_mfma_mode<false>(mode, p, B, stream, grid_out);
+// -1: decode_mfma_takes says no
+int launch_decode_mfma(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out, const ProjGeom* geom) {
+    ProjGeom g;
+    if (geom) g = *geom;
+    else if (!decode_mfma_takes(proj_shape(mode, p), B, &g)) return -1;
+    if (grid_out) *grid_out = g.grid;
+    return p.wscale ? launch_mfma_mode<true>(mode, p, B, g, stream) : launch_mfma_mode<false>(mode, p, B, g, stream);
 }
 
 int launch_quant_fm8(const void* src, int ld, void* dst, float* scales, int N, int K, hipStream_t stream, int perm, int head_dim) {

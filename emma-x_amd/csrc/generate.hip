@@ -122,7 +122,7 @@ int emmax_slots_open(emmax_session* s, int n_slots, emmax_stream stream) {
     if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
     if (s->beam.K) return fail(EMMAX_ERR_STATE, "request slots are not served while beams are on (emmax_session_clear_beams)");
     if (s->grp_N) return fail(EMMAX_ERR_STATE, "request slots are not served while sample groups are on (emmax_session_clear_sample_groups)");
-    const int max_rows = s->exact ? EMMAX_MAX_DECODE_BATCH : model_max_decode_batch(s->m);
+    const int max_rows = session_max_rows(s);
     if (n_slots < 1 || n_slots > s->max_batch || n_slots > max_rows)
         return fail(EMMAX_ERR_INVALID, "%d slots outside 1..min(max_batch=%d, %d)%s", n_slots, s->max_batch, max_rows,
                     (s->m->mx4 && n_slots >= 1 && n_slots <= s->max_batch) ? ": the limit of a model with MXFP4 decode weights" : "");

@@ -251,13 +251,49 @@ struct GemvParams {
     const void* w4_scales;  // decode_km.hip, non-null: W holds MXFP4 tiles (launch_quant_mx4) and this is their scale stream; null: bf16 / fp8 (wscale)
 };
 // (where the QKV epilogues put the new K / V rows: gemv_kv_row / gemv_kv_store_x, decode_epilogue.h -- device code, this is also a host header)
+
+// ---- who decides what a launcher takes ----
+// ProjShape: what the five decode projection families read of a launch to decide whether they take it -- no pointers, so the planner
+// (step.hip: proj_route, model_max_decode_batch) asks before any arena or session exists.  Every family has ONE pure check,
+// <family>_takes(shape, B, geometry out): no HIP call, no stream; it reads emmax_tune() where the launcher did (km_down, km_roll, ks_oproj).
+// The launcher derives the shape, asks its own check and launches from the geometry it returned (or from the one its caller already
+// got from the same check: the `geom` argument of the launchers): a launcher has no shape-based refusal its check does not report.
+enum { PW_BF16 = 0, PW_FP8 = 1, PW_MX4 = 2 };   // weight format (fp8: the row copy for the staged GEMV, the e4m3 tiles for the MFMA families)
+struct ProjShape {
+    int mode, K, n_rows, head_dim, Hq;
+    int wfmt;
+    bool exact, h32, attn_part, x_tok;   // exact numerics; the fp32 stream is present; split partials in (nsplit of them); the folded embedding gather
+    int nsplit, max_parts, max_grid;
+    bool ld_ok;                          // ldw and ldx are multiples of 8
+};
+static inline ProjShape proj_shape(int mode, const GemvParams& p) {
+    return {mode, p.K, p.n_rows, p.head_dim, p.Hq, p.w4_scales ? PW_MX4 : p.wscale ? PW_FP8 : PW_BF16, p.exact != 0, p.h32 != nullptr,
+            p.attn_part != nullptr, p.x_tok != nullptr, p.nsplit, p.max_parts, p.max_grid, p.ldw % 8 == 0 && p.ldx % 8 == 0};
+}
+// the launch geometry a check hands its launcher (fields a family does not use stay 0)
+struct ProjGeom {
+    int grid, n_groups;     // blocks; row groups / tiles of the matrix (GemvParams::n_groups)
+    int kc;                 // GemvParams::kc as the kernel reads it: LDS rows (ks), K phase length (gemv, mfma), tiles per block (km)
+    size_t smem;            // dynamic LDS bytes
+    int shift;              // ks: ks_shift, mfma: qk_shift
+    int cpl, f8;            // ks: 16-byte chunks per lane; staged GEMV: block shape of the fp8 rows (0: bf16)
+    int nb, phased, roll;   // km: staged rows (8 / 16), the phased down form, the rolling refill (exact numerics: GemvParams::exact)
+    int tmax, nph, nh;      // kmp: tiles per block, phases, halves
+};
+bool decode_ks_takes(const ProjShape& s, int B, ProjGeom* g = nullptr);     // decode_ks.hip
+bool decode_gemv_takes(const ProjShape& s, int B, ProjGeom* g = nullptr);   // decode.hip's own staged kernel (fp8: the row GEMV)
+bool decode_km_takes(const ProjShape& s, int B, ProjGeom* g = nullptr);     // decode_km.hip; 17-64 rows: decode_kmp.hip's answer
+bool decode_kmp_takes(const ProjShape& s, int B, ProjGeom* g = nullptr);    // decode_kmp.hip
+bool decode_mfma_takes(const ProjShape& s, int B, ProjGeom* g = nullptr);   // decode_mfma.hip
 // staged_out (optional): 1 when decode.hip's own LDS-staged kernel served the call, 0 when decode_ks.hip took it.
 // The staged kernel exists for the fused modes at B = 1, 2 (bf16 and fp8 rows) and for GEMV_PLAIN at B <= 8 (fp8 rows: B <= 2); any other
 // (mode, B) returns -1 -- launch_proj (step.hip) sends every batch >= EMMAX_MFMA_MIN_BATCH to the MFMA kernels.
 int launch_decode_gemv(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out = nullptr, int* staged_out = nullptr);
+// ... its own staged kernel alone, from a geometry decode_gemv_takes returned (launch_proj: the route has asked already)
+int launch_decode_gemv_staged(int mode, const GemvParams& p, int B, const ProjGeom& g, hipStream_t stream, int* grid_out = nullptr);
 // decode_ks.hip: the batch 1-2 bf16 projections with K split across the waves of a block (activation slice in registers, no
 // block-wide stage); returns -2 for a shape it does not take.  launch_decode_gemv tries it first (tuning switch `ks` = 0: never).
-int launch_decode_ks(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out = nullptr);
+int launch_decode_ks(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out = nullptr, const ProjGeom* geom = nullptr);
 bool decode_ks_enabled();
 int decode_gemv_init();   // raise the dynamic-LDS limit of every GEMV instantiation (call once, outside graph capture)
 int launch_decode_embed(const int32_t* cur_tok, const void* E, void* h, int B, int hidden, int vocab, hipStream_t stream, float* h32 = nullptr);
@@ -497,7 +533,7 @@ int launch_set_tokens(int32_t* cur_tok, const int32_t* toks, int B, int32_t* don
 // p.W = the km copy (launch_repack_km: fragment-major tiles; perm 1 / 2 = the row orders that put the qkv RoPE pairs / the
 // (gate, up) pairs inside one 16-row tile).  -2: shape outside the kernel, the caller falls back to launch_decode_mfma.
 int launch_repack_km(const void* src, int ld, void* dst, int N, int K, int perm, int head_dim, hipStream_t stream);
-int launch_decode_km(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out = nullptr);
+int launch_decode_km(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out = nullptr, const ProjGeom* geom = nullptr);
 // MXFP4 (OCP MX v1.0) copy of a row-major bf16 matrix in the km row order (perm / head_dim as launch_repack_km): blocks of 32 consecutive k of one
 // row share the exponent e = floor(log2(amax)) - 2 clamped to [-127, 127] (code e + 127; an all-zero block: code 127), elements are w / 2^e rounded
 // to nearest even onto +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}, saturating.  tiles: N K / 2 bytes (1 KiB = 16 rows x 128 k, lane-major: emmax_decode_km_kernel),
@@ -508,14 +544,13 @@ int launch_dequant_mx4(const void* tiles, const void* scales, void* dst, int ld,
 bool decode_km_enabled();
 int decode_km_init();   // raise the dynamic-LDS limit of every instantiation (call once, outside graph capture)
 // decode_kmp.hip: batch 17-32 (two batch tiles per weight tile, the K slice in phases), bf16 weights, same copies; launch_decode_km routes there
-int launch_decode_kmp(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out = nullptr);
+int launch_decode_kmp(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out = nullptr, const ProjGeom* geom = nullptr);
 int decode_kmp_init();
 
 // ---- decode_mfma.hip: small-batch (B >= 3) projections on MFMA over the fragment-major weight copy ----
 int launch_repack_fm(const void* src, int ld, void* dst, int N, int K, hipStream_t stream);
 int launch_quant_fm8(const void* src, int ld, void* dst, float* scales, int N, int K, hipStream_t stream, int perm = 0, int head_dim = 0);   // fp8 e4m3 + per-row scale
-bool decode_gemv_fp8_fits(int B, int K);   // the fp8 row GEMV takes this (batch, K); else the MFMA kernel serves it
 int launch_quant_rm8(const void* src, int ld, void* dst, float* scales, int N, int K, hipStream_t stream);   // same values, rows in the GEMV's span order
-int launch_decode_mfma(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out = nullptr);   // p.W = fragment-major copy
+int launch_decode_mfma(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out = nullptr, const ProjGeom* geom = nullptr);   // p.W = fragment-major copy
 int decode_mfma_init();
 #define EMMAX_MFMA_MIN_BATCH 3

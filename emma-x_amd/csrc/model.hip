@@ -72,7 +72,8 @@ const EmmaxTune& emmax_tune() {
 // does (emmax/__init__.py sets the same variable at import).  VERDICT r05 next #6.
 __attribute__((constructor)) static void emmax_export_runtime_switches() { setenv("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0", 0); }
 
-static int check_config(const emmax_config& c) {
+// format_rules = false: everything but the MXFP4 shape rules (emmax_config_max_decode_batch asks the planner instead)
+static int check_config(const emmax_config& c, bool format_rules = true) {
     for (int t = 0; t < 2; ++t) {
         const auto& w = c.tower[t];
         if (w.embed_dim <= 0 || w.num_heads <= 0 || w.embed_dim % w.num_heads) return fail(EMMAX_ERR_INVALID, "tower %d: bad embed_dim/num_heads", t);
@@ -93,11 +94,13 @@ static int check_config(const emmax_config& c) {
     if (c.vocab % 8) return fail(EMMAX_ERR_INVALID, "vocab must be a multiple of 8");
     if (c.decode_fp8 < 0 || c.decode_fp8 > 2) return fail(EMMAX_ERR_INVALID, "decode_fp8 %d: 0 (bf16), 1 (fp8-e4m3) or 2 (MXFP4)", c.decode_fp8);
     if (c.decode_fp8 == 1 && (c.hidden % 64 || (c.n_heads * c.head_dim) % 64)) return fail(EMMAX_ERR_INVALID, "fp8 decode needs K % 64 == 0");
-    if (c.decode_fp8 == 2) {
+    if (c.decode_fp8 == 2 && format_rules) {
         // MXFP4 tiles are read by decode_km.hip alone, at every batch: the model must be a shape that file takes.  qkv / o-proj / gate-up / lm-head:
         // eight waves x whole load steps of 128 elements, at most sixteen fragments per wave -- K % 1024 == 0 and K <= 4096, at most 8 tiles
         // for each of 256 blocks (N <= 32768); the down projection on the phased kernel: whole load steps (K % 128 == 0), K above 4096 and
-        // within the phases (two of six steps at 1-8 rows, four of three at 9-16: ceil(K / 128 / 8) <= 12, K <= 12288)
+        // within the phases (two of six steps at 1-8 rows, four of three at 9-16: ceil(K / 128 / 8) <= 12, K <= 12288).  This runs before a model
+        // exists, so it is text; emmax_config_max_decode_batch asks the planner about the same config, and tests/test_decode_plan.py holds the
+        // two together (accepted exactly when the planner serves 8 rows)
         const int q_dim = c.n_heads * c.head_dim, qkv_dim = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim;
         if (c.hidden % 1024 || c.hidden > 4096 || q_dim % 1024 || q_dim > 4096)
             return fail(EMMAX_ERR_INVALID, "MXFP4 decode weights need hidden (%d) and n_heads * head_dim (%d) in multiples of 1024 up to 4096", c.hidden, q_dim);
@@ -413,6 +416,15 @@ int emmax_model_finalize(emmax_model* m, void* arena, int64_t arena_bytes, emmax
 }
 
 int emmax_model_max_decode_batch(const emmax_model* m) { return m ? model_max_decode_batch(m) : -1; }
+int emmax_model_max_decode_batch_exact(const emmax_model* m) { return m ? model_max_decode_batch(m, true) : -1; }
+int emmax_config_max_decode_batch(const emmax_config* cfg, int exact) {
+    if (!cfg) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (int r = check_config(*cfg, false)) return r;
+    emmax_model tmp;
+    tmp.cfg = *cfg;
+    derive(&tmp);
+    return model_max_decode_batch(&tmp, exact != 0);
+}
 
 int64_t emmax_model_aux_bytes(const emmax_model* m) {
     if (!m) return -1;

@@ -172,7 +172,7 @@ int emmax_session_set_scores(emmax_session* s, float* scores_dev, float* logits_
 // ---- beam search in the decode step (ABI 9) ---------------------------------------------------------------------------
 int emmax_session_set_beams(emmax_session* s, int num_beams, double length_penalty, int early_stopping, emmax_stream stream) {
     if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
-    const int max_rows = s->exact ? EMMAX_MAX_DECODE_BATCH : model_max_decode_batch(s->m);
+    const int max_rows = session_max_rows(s);
     if (num_beams < 2 || num_beams > EMMAX_MAX_BEAMS || num_beams > s->max_batch || num_beams > max_rows)
         return fail(EMMAX_ERR_INVALID, "num_beams %d outside 2..min(%d, max_batch=%d, %d)", num_beams, EMMAX_MAX_BEAMS, s->max_batch, max_rows);
     if (!std::isfinite(length_penalty)) return fail(EMMAX_ERR_INVALID, "length_penalty must be finite");
@@ -226,7 +226,7 @@ int emmax_session_beam_result(emmax_session* s, int max_new, int32_t* seq_dev, i
 // ---- sample groups: N sampled rows per prefilled prompt (additions to ABI 11) ----------------------------------------------
 int emmax_session_set_sample_groups(emmax_session* s, int n, emmax_stream) {
     if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
-    const int max_rows = std::min(s->max_batch, s->exact ? EMMAX_MAX_DECODE_BATCH : model_max_decode_batch(s->m));
+    const int max_rows = std::min(s->max_batch, session_max_rows(s));
     if (n < 2 || n > max_rows) return fail(EMMAX_ERR_INVALID, "%d samples per group outside 2..min(max_batch=%d, the model's decode batch)=%d", n, s->max_batch, max_rows);
     if (s->beam.K) return fail(EMMAX_ERR_STATE, "sample groups cannot be turned on while beams are on (emmax_session_clear_beams)");
     if (s->slots_open) return fail(EMMAX_ERR_STATE, "sample groups cannot be turned on while request slots are open");

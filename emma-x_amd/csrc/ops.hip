@@ -296,7 +296,7 @@ static int decode_stage_run(emmax_session* s, int layer, int stage, int B, const
         if (r == 0 && y_out) HIPCHK(hipMemcpyAsync(y_out, s->exact ? (void*)s->dq32 : (void*)s->dq, (size_t)B * m->q_dim * x4, hipMemcpyDeviceToDevice, st));
     } else if (stage == STAGE_OPROJ) {
         int ns = 1;
-        const int form = decode_oproj_form(s, B, &ns);
+        const int form = decode_oproj_form(s->m, s->exact, B, &ns);
         if (form == 1) HIPCHK(hipMemcpyAsync(s->part, x_in, (size_t)B * m->cfg.n_heads * ns * EMMAX_PSTRIDE * 4, hipMemcpyDeviceToDevice, st));
         else if (form == 2) HIPCHK(hipMemcpyAsync(s->dq32, x_in, (size_t)B * m->q_dim * 4, hipMemcpyDeviceToDevice, st));
         else HIPCHK(hipMemcpyAsync(s->datt, x_in, (size_t)B * m->q_dim * 2, hipMemcpyDeviceToDevice, st));
@@ -330,13 +330,15 @@ int emmax_op_decode_stage(emmax_session* s, int layer, int stage, int B, const v
     if (stage != STAGE_LMHEAD && (layer < 0 || layer >= m->cfg.n_layers))
         return fail(EMMAX_ERR_INVALID, "emmax_op_decode_stage: layer %d outside 0..%d", layer, m->cfg.n_layers - 1);
     int ns = 1;
-    const int form = decode_oproj_form(s, B, &ns);
+    const int form = decode_oproj_form(s->m, s->exact, B, &ns);
     if (oproj_form_out) *oproj_form_out = form;
     if (nsplit_out) *nsplit_out = ns;
     if (via_out) *via_out = EMMAX_VIA_NONE;
     if (stage == STAGE_OPROJ && !x_in && !h_in && !h32_in) return 0;   // the query form: which input the o-proj of B rows reads, nothing launched
     if (s->samp.on || s->proc.on || s->scores.on || s->beam.K || s->slots_open)
         return fail(EMMAX_ERR_STATE, "emmax_op_decode_stage: the session must be greedy (no sampling, processing, scores, beams or open slots)");
+    if (!decode_batch_served(m, B, s->exact))   // (a prefill is held to it by the limit; this op is the one way past that)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_decode_stage: steps of %d rows are served with one-split attention and an intermediate size above 4096 only (emmax_model_max_decode_batch)", B);
     if (B >= EMMAX_MFMA_MIN_BATCH && !m->aux_built)
         return fail(EMMAX_ERR_STATE, "%d rows decode on the fragment-major weight copies: call emmax_model_build_aux first", B);
     if (!h_in || (!h32_in && (s->exact || emmax_tune().resid32))) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_stage: the hidden rows (bf16 and the fp32 stream) are required");
@@ -358,6 +360,18 @@ int emmax_op_decode_stage(emmax_session* s, int layer, int stage, int B, const v
         }
     }
     return decode_stage_run(s, layer, stage, B, h_in, h32_in, ctx_len_host, page_table_host, x_in, h_out, h32_out, y_out, tok_out, via_out, (hipStream_t)stream);
+}
+
+int emmax_op_decode_route(const emmax_model* m, int stage, int B, int exact, int* via_out) {
+    if (!m) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_route: null model");
+    if (stage != STAGE_QKV && stage != STAGE_OPROJ && stage != STAGE_GATEUP && stage != STAGE_DOWN && stage != STAGE_LMHEAD)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_decode_route: stage %d is not a projection stage (0 qkv, 2 o-proj, 3 gate/up, 4 down, 5 lm-head)", stage);
+    if (B < 1 || B > EMMAX_MAX_DECODE_BATCH) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_route: B %d outside 1..%d", B, EMMAX_MAX_DECODE_BATCH);
+    const int via = decode_stage_route(m, stage, B, exact != 0);
+    if (via_out) *via_out = via > 0 ? via : EMMAX_VIA_NONE;
+    if (via > 0) return 0;
+    return fail(EMMAX_ERR_INVALID, "emmax_op_decode_route: no launcher family takes the %s projection of this model at batch %d%s%s", decode_stage_name(stage), B,
+                exact ? " in exact numerics" : "", via < 0 ? " (decode_km.hip refuses it and decode_mfma.hip's copy is only built with the tuning switch km = 0)" : "");
 }
 
 int emmax_op_decode_kv_read(emmax_session* s, int layer, int row, int p0, int n, const int32_t* page_row_host, int from_stage, float* k_out_host,
@@ -461,7 +475,7 @@ int emmax_op_gemm_small_mxfp4(const void* x, const void* tiles, const void* scal
     p.w4_scales = scales;
     if (B < 1 || B > 16) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_small_mxfp4: batch %d outside 1..16", B);
     // (the K-split kernel only: the phased kernel of the down projection is reached through emmax_op_decode_stage)
-    const int r = K > 4096 ? -2 : launch_decode_km(GEMV_PLAIN, p, B, (hipStream_t)st);
+    const int r = launch_decode_km(GEMV_PLAIN, p, B, (hipStream_t)st);
     if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_gemm_small_mxfp4: unsupported shape (N %% 16 and N <= 32768; K %% 1024 and K <= 4096)");
     return 0;
 }

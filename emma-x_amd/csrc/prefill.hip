@@ -50,7 +50,7 @@ int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B
     const auto& c = m->cfg;
     if (!m->finalized) return fail(EMMAX_ERR_STATE, "model not finalized");
     // (an exact session was checked against the shapes its two-term kernels take when it was created, and chunks larger batches: check_exact)
-    const int max_rows = s->exact ? EMMAX_MAX_DECODE_BATCH : model_max_decode_batch(m);
+    const int max_rows = session_max_rows(s);
     if (B <= 0 || B > s->max_batch || B > max_rows)
         return fail(EMMAX_ERR_INVALID, "prefill batch %d outside 1..min(max_batch=%d, %d) (%s)", B, s->max_batch, max_rows,
                     (m->mx4 && B >= 1 && B <= s->max_batch)   // (the model's limit binds: it can move after the session was created, with the attention switches)

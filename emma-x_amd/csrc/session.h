@@ -34,6 +34,7 @@ int fail(int code, const char* fmt, ...);
 
 static inline int pad_to(int x, int m) { return (x + m - 1) / m * m; }
 static const int PAGE = 64;   // KV page: 64 tokens x head_dim bf16 per kv head
+static const int EMMAX_LM_BLOCKS = 512;   // persistent lm-head grid: one argmax partial per block (the capacity of a session's partial buffers)
 
 typedef uint16_t bf16;
 
@@ -304,13 +305,18 @@ GemmParams gpx(emmax_session* s, const void* A_hl, int Kp, const void* W, int ld
 // prefill.hip
 int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B, int P_max, const void* patches, hipStream_t st, int slot0 = -1);
 // step.hip
-int model_max_decode_batch(const emmax_model* m);
+int model_max_decode_batch(const emmax_model* m, bool exact = false, int* first_stage = nullptr, int* first_B = nullptr);   // the planner: the largest batch every stage has a route for
+int session_max_rows(const emmax_session* s);                      // ... of the session's model and numerics
+int decode_stage_route(const emmax_model* m, int stage, int B, bool exact);   // EMMAX_VIA_* of the stage's last launch, <= 0: no route
+bool decode_batch_served(const emmax_model* m, int B, bool exact);             // the serving policy above 8 rows (step.hip)
+const char* decode_stage_name(int stage);
+int stage_chunk(int stage, bool exact);                            // rows per launch of a stage (exact numerics: 8; down / lm-head: EMMAX_KMP_ROWS)
 bool beam_pages_fit(const emmax_session* s, int S, int max_new);
 int launch_beam_finish(emmax_session* s, bool is_prefill, hipStream_t st);
 int run_group_fork(emmax_session* s, int G, hipStream_t st);
 int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* logits_out, bool do_finish, hipStream_t st, int slot0 = 0);
 int run_decode_stage(emmax_session* s, int B, int li, int stage, hipStream_t st);
-int decode_oproj_form(const emmax_session* s, int B, int* nsplit);
+int decode_oproj_form(const emmax_model* m, bool exact, int B, int* nsplit);
 int run_decode_step(emmax_session* s, int B, hipStream_t st);
 int ensure_graph(emmax_session* s, int B, hipStream_t st);
 int launch_graph_step(emmax_session* s, int B, hipStream_t st);

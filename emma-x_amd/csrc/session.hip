@@ -57,7 +57,7 @@ static void plan_session(emmax_session* s, Bump& b) {
     s->datt = (bf16*)b.bytes((int64_t)Bd * m->q_dim * 2);
     s->dact = (bf16*)b.bytes((int64_t)Bd * m->inter_p * 2);
     s->part = (float*)b.bytes((int64_t)Bd * m->cfg.n_heads * 16 * 132 * 4);
-    s->n_lm_blocks = 512;   // persistent lm-head grid: one argmax partial per block
+    s->n_lm_blocks = EMMAX_LM_BLOCKS;
     s->part_val = (float*)b.bytes((int64_t)s->n_lm_blocks * Bd * 4);
     s->part_idx = (int32_t*)b.bytes((int64_t)s->n_lm_blocks * Bd * 4);
     s->part_val2 = (float*)b.bytes((int64_t)s->n_lm_blocks * Bd * 4);
@@ -173,18 +173,13 @@ static int check_exact(const emmax_model* m, int max_batch, int stage_rows) {
     if (m->finalized && m->ln_folded)
         return fail(EMMAX_ERR_STATE, "exact numerics needs the ViT LayerNorms unfolded: set the tuning switch exact = 1 BEFORE emmax_model_finalize");
     // batch 1-2: decode_ks.hip's two-term dot products; batch 3-8: decode_km.hip's EX kernels (the two terms of a row in the MFMA's sixteen batch
-    // columns), which need the shapes that file takes: K a multiple of 256 and <= 4096 for qkv / o-proj / gate-up / lm-head, at most 8 tiles per block,
-    // the down projection within four phases of 12 fragments per wave
-    // (batches above 8 rows run their projections in chunks of 8: run_decode_stage_x_chunks)
+    // columns); batches above 8 rows run their projections in chunks of 8 (stage_chunk).  What shapes those take is their checks' to say: the
+    // exact planner must serve min(max_batch, 8) rows
     if (max_batch > EMMAX_MAX_DECODE_BATCH) return fail(EMMAX_ERR_INVALID, "exact numerics serves batches of 1-%d rows; max_batch %d", EMMAX_MAX_DECODE_BATCH, max_batch);
-    if (max_batch > 2) {
-        const bool k_ok = m->H % 256 == 0 && m->H <= 4096 && m->q_dim % 256 == 0 && m->q_dim <= 4096 && m->q_dim == m->cfg.n_heads * 128;
-        const bool n_ok = m->qkv_dim % 16 == 0 && m->qkv_dim <= 32768 && 2 * m->inter_p <= 32768 && m->vocab_p <= 32768 && m->H % 16 == 0 && m->cfg.head_dim % 16 == 0;
-        const bool d_ok = m->inter_p % 32 == 0 && m->inter_p / 32 >= 8 && (m->inter_p / 32 + 7) / 8 <= 48;
-        if (!(k_ok && n_ok && d_ok && decode_km_enabled()))
-            return fail(EMMAX_ERR_INVALID, "exact numerics at batch >= 3 needs the shapes decode_km.hip takes (hidden / q widths in multiples of 256 up to 4096, head_dim 128); max_batch %d", max_batch);
-    }
-    if (m->H % 64 || m->q_dim % 64) return fail(EMMAX_ERR_INVALID, "exact numerics needs hidden and q widths in multiples of 64");
+    int stage = 0, B = 0;
+    if (model_max_decode_batch(m, true, &stage, &B) < std::min(max_batch, 8))
+        return fail(EMMAX_ERR_INVALID, "exact numerics: no two-term kernel takes the %s projection of this model at batch %d (decode_ks.hip at 1-2 rows: widths in multiples of 64; decode_km.hip at 3-8: hidden / q widths in multiples of 256 up to 4096, tuning switch km); max_batch %d",
+                    decode_stage_name(stage), B, max_batch);
     return 0;
 }
 

@@ -17,105 +17,175 @@ static int fp8_gemv_mask(int B) {
     return B == 1 ? (F8_OPROJ | F8_LMHEAD) : F8_OPROJ;
 }
 
-// One projection of the step (ProjW, session.h).  B <= 2: per-lane dot-product GEMV over the row-major weights (fp8 mode: over the e4m3 row
-// copy w.r8); B >= 3: MFMA over the fragment-major copy.  w.km / w.km_sc: the matrix in decode_km.hip's layout (null: that kernel does not
-// serve this projection).  w.q4 / w.q4s (MXFP4 models): the 4-bit tiles and their scale stream -- decode_km.hip at every batch 1-16, nothing else
+// Which copies of a projection's matrix exist -- flags, not pointers: the planner asks before any arena exists.  copies_of: what a
+// ProjW holds now (launch_proj); copies_planned: what the model has or, before emmax_model_build_aux, will have.
+struct ProjCopies { bool rm, r8, sc, km, fm, q4; int f8bit; };
+static ProjCopies copies_of(const ProjW& w) { return {w.rm != nullptr, w.r8 != nullptr, w.sc != nullptr, w.km != nullptr, w.fm != nullptr, w.q4 != nullptr, w.f8bit}; }
+static ProjCopies copies_planned(const emmax_model* m, int stage) {
+    // decode_mfma.hip's qkv / gate-up pair: fp8 models always, bf16 models when the aux arena was (or would now be) built with the tuning switch km = 0
+    const bool pair = stage == STAGE_QKV || stage == STAGE_GATEUP;
+    const bool fm = m->fp8 || (!m->mx4 && (!pair || (m->aux_built ? m->aux_ab : emmax_tune().km == 0)));
+    const int bit = stage == STAGE_QKV ? F8_QKV : stage == STAGE_OPROJ ? F8_OPROJ : stage == STAGE_GATEUP ? F8_GATEUP : stage == STAGE_DOWN ? F8_DOWN : F8_LMHEAD;
+    return {true, m->fp8, m->fp8, !m->mx4, fm, m->mx4, bit};
+}
+
+// Which launcher family takes a projection at B rows (EMMAX_VIA_*), EMMAX_VIA_NONE when none does, ROUTE_NO_FM when only decode_mfma.hip's copy
+// (not built) could have.  The order of preference: exact numerics -- the two-term forms or nothing (decode_ks.hip at batch 1-2,
+// decode_km.hip's EX kernels at 3-8); MXFP4 tiles -- decode_km.hip at every batch 1-16, no other kernel reads them; the fp8 row GEMV at batch
+// 1-2 under the fp8_gemv mask; batch >= 3 and fp8: the K-split MFMA kernels (decode_km.hip, 17-64 rows decode_kmp.hip), else decode_mfma.hip;
+// else (batch 1-2, bf16) decode_ks.hip, else decode.hip's staged GEMV.  Pure: every question goes to a family's own check, and *g is the
+// geometry the chosen family's check returned -- its launcher runs from it without asking again.
+enum { ROUTE_NO_FM = -1 };
+static int proj_route(const ProjCopies& c, ProjShape s, int B, ProjGeom* g) {
+    if (s.exact) {
+        s.wfmt = PW_BF16;
+        if (c.sc || c.q4) return EMMAX_VIA_NONE;   // (bf16 weights only: check_exact)
+        if (B < EMMAX_MFMA_MIN_BATCH) return decode_ks_takes(s, B, g) ? EMMAX_VIA_KS : EMMAX_VIA_NONE;
+        // (at most 8 rows per launch, never decode_kmp.hip; tuning switch km = 0 names decode_mfma.hip, which has no two-term form: nothing)
+        return c.km && decode_km_enabled() && decode_km_takes(s, B, g) ? EMMAX_VIA_KM : EMMAX_VIA_NONE;
+    }
+    if (c.q4) {
+        s.wfmt = PW_MX4;
+        // the MXFP4 down projection runs on the phased kernel only: the K-split form would take K <= 4096, but the format's error lines were
+        // measured on the phased kernel alone (policy, not a kernel limit -- the same line emmax_model_create draws)
+        if (c.f8bit == F8_DOWN && s.K <= 4096) return EMMAX_VIA_NONE;
+        return B <= 16 && decode_km_takes(s, B, g) ? EMMAX_VIA_KM : EMMAX_VIA_NONE;
+    }
+    s.wfmt = c.sc ? PW_FP8 : PW_BF16;
+    if (B < EMMAX_MFMA_MIN_BATCH && c.sc && c.r8 && (fp8_gemv_mask(B) & c.f8bit) && decode_gemv_takes(s, B, g)) return EMMAX_VIA_GEMV_FP8;
+    if (B >= EMMAX_MFMA_MIN_BATCH || c.sc) {
+        if (c.km && decode_km_enabled() && decode_km_takes(s, B, g)) return B > 16 ? EMMAX_VIA_KMP : EMMAX_VIA_KM;   // (decode_km.hip hands 17-64 rows to decode_kmp.hip)
+        if (!c.fm) return ROUTE_NO_FM;
+        return decode_mfma_takes(s, B, g) ? EMMAX_VIA_MFMA : EMMAX_VIA_NONE;
+    }
+    if (decode_ks_enabled() && decode_ks_takes(s, B, g)) return EMMAX_VIA_KS;
+    return decode_gemv_takes(s, B, g) ? EMMAX_VIA_GEMV : EMMAX_VIA_NONE;
+}
+
+// One projection of the step (ProjW, session.h): route once, point p at the chosen family's copy of the matrix, launch from the route's geometry.
 // via (optional): which launcher family took the call (include/emmax.h: EMMAX_VIA_*), what emmax_op_decode_stage reports
 static int launch_proj(const ProjW& w, GemvParams& p, int B, hipStream_t st, int* grid_out, int* via = nullptr) {
     const int mode = w.gemv_mode;
-    int via_tmp = 0;
-    if (!via) via = &via_tmp;
-    *via = EMMAX_VIA_NONE;
-    if (p.exact) {   // exact numerics: the two-term forms or nothing -- decode_ks.hip at batch 1-2, decode_km.hip's EX kernels at batch 3-8
-        int r = -2;
-        if (!w.sc && B < EMMAX_MFMA_MIN_BATCH) {
+    ProjGeom g;
+    const int route = proj_route(copies_of(w), proj_shape(mode, p), B, &g);
+    if (via) *via = route > 0 ? route : EMMAX_VIA_NONE;
+    switch (route) {
+        case EMMAX_VIA_KS:
             p.W = w.rm;
-            r = launch_decode_ks(mode, p, B, st, grid_out);
-            *via = EMMAX_VIA_KS;
-        } else if (!w.sc && w.km) {
-            GemvParams q = p;
-            q.W = w.km;
-            r = launch_decode_km(mode, q, B, st, grid_out);
-            *via = EMMAX_VIA_KM;   // (exact numerics: at most 8 rows per launch, never decode_kmp.hip)
-        }
-        return r == -2 ? fail(EMMAX_ERR_INVALID, "exact numerics: no two-term kernel for this projection (batch %d, K %d)", B, p.K) : r;
+            return launch_decode_ks(mode, p, B, st, grid_out, &g);
+        case EMMAX_VIA_GEMV:
+            p.W = w.rm;
+            return launch_decode_gemv_staged(mode, p, B, g, st, grid_out);
+        case EMMAX_VIA_GEMV_FP8:
+            p.W = w.r8; p.wscale = w.sc;
+            p.ldw = p.K;   // bytes per row
+            return launch_decode_gemv_staged(mode, p, B, g, st, grid_out);
+        case EMMAX_VIA_KM:
+        case EMMAX_VIA_KMP:
+            if (w.q4) { p.W = w.q4; p.w4_scales = w.q4s; }
+            else { p.W = w.km; p.wscale = w.sc ? w.km_sc : nullptr; }
+            return launch_decode_km(mode, p, B, st, grid_out, &g);
+        case EMMAX_VIA_MFMA:
+            p.W = w.fm; p.wscale = w.sc;
+            return launch_decode_mfma(mode, p, B, st, grid_out, &g);
+        case ROUTE_NO_FM:
+            return fail(EMMAX_ERR_STATE, "decode_mfma.hip's copy of this matrix was not built (tuning switch km was 1 at emmax_model_build_aux)");
+        default: break;
     }
-    if (w.q4) {   // MXFP4 copy: decode_km.hip at every batch 1-16, no other kernel reads the tiles (the model's shapes were checked at emmax_model_create)
-        GemvParams q = p;
-        q.W = w.q4;
-        q.w4_scales = w.q4s;
-        const int r = B <= 16 ? launch_decode_km(mode, q, B, st, grid_out) : -2;
-        *via = EMMAX_VIA_KM;
-        return r == -2 ? fail(EMMAX_ERR_INVALID, "MXFP4 decode weights: no kernel for this projection (batch %d of 1-16, K %d)", B, p.K) : r;
-    }
-    if (B < EMMAX_MFMA_MIN_BATCH && w.sc && w.r8 && (fp8_gemv_mask(B) & w.f8bit) && decode_gemv_fp8_fits(B, p.K)) {
-        p.W = w.r8;
-        p.wscale = w.sc;
-        p.ldw = p.K;   // bytes per row
-        *via = EMMAX_VIA_GEMV_FP8;
-        return launch_decode_gemv(mode, p, B, st, grid_out);
-    }
-    if (B >= EMMAX_MFMA_MIN_BATCH || w.sc) {
-        // K-split MFMA kernel (decode_km.hip): batch >= 3, and with fp8 weights every batch the row GEMV above did not take
-        if ((B >= EMMAX_MFMA_MIN_BATCH || w.sc) && w.km && decode_km_enabled()) {
-            GemvParams q = p;
-            q.W = w.km;
-            q.wscale = w.sc ? w.km_sc : nullptr;
-            const int r = launch_decode_km(mode, q, B, st, grid_out);
-            *via = B > 16 ? EMMAX_VIA_KMP : EMMAX_VIA_KM;   // (launch_decode_km hands 17-64 rows to decode_kmp.hip)
-            if (r != -2) return r;
-        }
-        if (!w.fm) return fail(EMMAX_ERR_STATE, "decode_mfma.hip's copy of this matrix was not built (tuning switch km was 1 at emmax_model_build_aux)");
-        p.W = w.fm;
-        p.wscale = w.sc;
-        *via = EMMAX_VIA_MFMA;
-        return launch_decode_mfma(mode, p, B, st, grid_out);
-    }
-    p.W = w.rm;
-    int staged = 0;
-    const int r = launch_decode_gemv(mode, p, B, st, grid_out, &staged);
-    *via = staged ? EMMAX_VIA_GEMV : EMMAX_VIA_KS;
-    return r;
+    if (p.exact) return fail(EMMAX_ERR_INVALID, "exact numerics: no two-term kernel for this projection (batch %d, K %d)", B, p.K);
+    if (w.q4) return fail(EMMAX_ERR_INVALID, "MXFP4 decode weights: no kernel for this projection (batch %d of 1-16, K %d)", B, p.K);
+    return -1;   // no family takes this shape at this batch
 }
 
-// Decode batches of 9-16 rows exist on decode_km.hip only (decode_mfma.hip, the fallback for other shapes, stages eight rows): the
-// model's projections must be shapes that kernel takes -- K a multiple of 256 and <= 4096 for qkv / o-proj / gate-up / lm-head, at
-// most 8 tiles per block (N <= 32768), the down projection within four phases of 12 fragments per wave (K <= 12288).
-int model_max_decode_batch(const emmax_model* m) {
-    const auto& c = m->cfg;
-    // MXFP4 tiles: decode_km.hip alone (check_config, model.hip, holds the shapes to it) -- 16 rows, or 8 under the one-split rule below.  The rule reads
-    // tuning switches, so the answer can shrink after a session was created: emmax_session_bytes / create check it once, run_prefill and emmax_slots_open
-    // again (a step itself is not re-checked: flipping attn_direct / attn_nsplit between a prefill and its decode steps ends in launch_proj's refusal)
-    if (m->mx4) return (emmax_tune().attn_direct == 0 || decode_attn_nsplit(9, c.n_kv_heads) != 1) ? 8 : 16;
-    const bool k_ok = m->H % 256 == 0 && m->H <= 4096 && m->q_dim % 256 == 0 && m->q_dim <= 4096;
-    const bool n_ok = m->qkv_dim % 16 == 0 && m->qkv_dim <= 32768 && 2 * m->inter_p <= 32768 && m->vocab_p <= 32768 && m->H % 16 == 0 && c.head_dim % 16 == 0;
-    const int kd = m->fp8 ? 64 : 32;
-    const bool d_ok = m->inter_p % kd == 0 && m->inter_p / kd >= 8 && (m->inter_p / kd + 7) / 8 <= (m->fp8 ? 24 : 48) && m->inter_p > 4096;
-    if (!(k_ok && n_ok && d_ok && decode_km_enabled() && emmax_tune().km_down)) return 8;
-    // 17-32 rows: decode_kmp.hip -- the down projection within eleven phases of 128 elements per wave (K in whole load steps of 32
-    // elements, 64 with fp8 tiles; the widest wave share <= 1408 elements: K <= 11264), one tile per block there (H <= 4096)
-    const bool p_ok = ((m->inter_p / kd + 7) / 8) * kd <= 11 * 128 && m->H <= 4096 && m->H / 16 <= 256;
-    // batches of 9-32 rows exist in the ONE-split direct attention form only: with split partials (tuning switches attn_direct = 0 or a
-    // forced attn_nsplit > 1) the o-proj would carry p.attn_part, which the bf16 decode_km / decode_kmp kernels do not take
-    if (emmax_tune().attn_direct == 0 || decode_attn_nsplit(9, c.n_kv_heads) != 1) return 8;
-    return p_ok ? EMMAX_MAX_DECODE_BATCH : 16;
+// How a stage's rows are split into launches: exact numerics -- chunks of 8 for every projection stage and the lm-head (the two-term MFMA kernels
+// hold 8 rows: decode_km.hip EX, the two terms of a row in the sixteen batch columns; each chunk streams the weights again, so the conformance mode
+// covers every batch the default path serves at ceil(B / 8) times its weight traffic); otherwise the down projection and the lm-head in chunks of
+// EMMAX_KMP_ROWS (33-64 rows: K = 11008 does not fit the eight phases of a four-way split; the argmax partials are laid out per launch); every
+// other stage whole.  (The attention launch takes any batch.)
+int stage_chunk(int stage, bool exact) {
+    return exact ? 8 : (stage == STAGE_DOWN || stage == STAGE_LMHEAD) ? EMMAX_KMP_ROWS : EMMAX_MAX_DECODE_BATCH;
 }
 
 // one KV split per (row, head) (batch >= 5 at 32 heads): nothing to merge -- the attention launch normalises and writes the bf16 row
 // itself and the o-proj is a plain projection; otherwise the o-proj prologue merges the split partials.
-static bool attn_direct_on(const emmax_session* s, int B) {
+static bool attn_direct_on(const emmax_model* m, bool exact, int B) {
     // exact numerics: the fp32 row in place over the q rows, at batch >= 3 (decode_km.hip's EX o-proj takes fp32 rows; decode_ks.hip's merges the partials)
-    if (s->exact && B < EMMAX_MFMA_MIN_BATCH) return false;
-    return decode_attn_nsplit(B, s->m->cfg.n_kv_heads) == 1 && emmax_tune().attn_direct != 0;
+    if (exact && B < EMMAX_MFMA_MIN_BATCH) return false;
+    return decode_attn_nsplit(B, m->cfg.n_kv_heads) == 1 && emmax_tune().attn_direct != 0;
 }
+static bool attn_direct_on(const emmax_session* s, int B) { return attn_direct_on(s->m, s->exact, B); }
 
 // what the o-proj of a B-row step reads (emmax_op_decode_stage feeds it): 0 = the bf16 attention rows, 1 = split partials (*nsplit of them per
 // (row, head)), 2 = exact numerics, the fp32 rows the one-split attention launch left over the q rows
-int decode_oproj_form(const emmax_session* s, int B, int* nsplit) {
-    const bool direct = attn_direct_on(s, B);
-    if (nsplit) *nsplit = direct ? 1 : decode_attn_nsplit(B, s->m->cfg.n_kv_heads);
-    return !direct ? 1 : (s->exact ? 2 : 0);
+int decode_oproj_form(const emmax_model* m, bool exact, int B, int* nsplit) {
+    const bool direct = attn_direct_on(m, exact, B);
+    if (nsplit) *nsplit = direct ? 1 : decode_attn_nsplit(B, m->cfg.n_kv_heads);
+    return !direct ? 1 : (exact ? 2 : 0);
 }
+
+// The shape of a stage's projection in a B-row step, from the model's dimensions alone (what stage_params / lmhead_params put into GemvParams)
+static ProjShape stage_shape(const emmax_model* m, int stage, int B, bool exact) {
+    ProjShape s = {};
+    s.exact = exact; s.h32 = exact || emmax_tune().resid32 != 0; s.ld_ok = true;   // (every K is a multiple of 64: check_config, derive)
+    switch (stage) {
+        case STAGE_QKV: s.mode = GEMV_QKV; s.K = m->H; s.n_rows = m->qkv_dim; s.head_dim = m->cfg.head_dim; s.Hq = m->cfg.n_heads; break;
+        case STAGE_OPROJ:
+            s.mode = GEMV_RESID; s.K = m->q_dim; s.n_rows = m->H;
+            if (decode_oproj_form(m, exact, B, &s.nsplit) == 1) { s.attn_part = true; s.Hq = m->cfg.n_heads; }
+            break;
+        case STAGE_GATEUP: s.mode = GEMV_GATEUP; s.K = m->H; s.n_rows = 2 * m->inter_p; break;
+        case STAGE_DOWN: s.mode = GEMV_RESID; s.K = m->inter_p; s.n_rows = m->H; break;
+        default: s.mode = GEMV_LMHEAD; s.K = m->H; s.n_rows = m->vocab; s.max_parts = EMMAX_LM_BLOCKS;
+    }
+    return s;
+}
+
+// Steps of more than 8 rows are served in the forms they were built and measured in, whatever else the launchers would take: the ONE-split
+// direct attention form (judged at nine rows, as ever: with split partials the bf16 and MXFP4 o-proj have no kernel there, and decode_km.hip's
+// fp8 one, which has, is not run at those batches anywhere) and an intermediate size above 4096 (the phased down kernels; a shorter K would go
+// through the K-split form, which no test runs as a down projection at 9-64 rows).  Policy, not a kernel limit: widening it is a change of its
+// own with GPU coverage at the shapes it opens.  Exact numerics runs 8 rows per launch and is not concerned.
+bool decode_batch_served(const emmax_model* m, int B, bool exact) {
+    if (exact || B <= 8) return true;
+    return emmax_tune().attn_direct != 0 && decode_attn_nsplit(9, m->cfg.n_kv_heads) == 1 && m->inter_p > 4096;
+}
+
+// The family that takes the LAST launch of a stage of a B-row step (what emmax_op_decode_stage reports), or EMMAX_VIA_NONE / ROUTE_NO_FM when one
+// of the stage's launches has no route or the step is not served at B rows (decode_batch_served).  Host only.
+int decode_stage_route(const emmax_model* m, int stage, int B, bool exact) {
+    if (!decode_batch_served(m, B, exact)) return EMMAX_VIA_NONE;
+    const ProjShape s = stage_shape(m, stage, B, exact);
+    const ProjCopies c = copies_planned(m, stage);
+    const int chunk = stage_chunk(stage, exact);
+    int via = EMMAX_VIA_NONE, n_prev = 0;
+    for (int r = 0; r < B && via >= 0; r += chunk) {
+        const int n = std::min(chunk, B - r);
+        ProjGeom g;
+        if (n != n_prev && (via = proj_route(c, s, n, &g)) == EMMAX_VIA_NONE) break;   // (n == n_prev: the same launch again)
+        n_prev = n;
+    }
+    return via;
+}
+
+static const int kProjStages[] = {STAGE_QKV, STAGE_OPROJ, STAGE_GATEUP, STAGE_DOWN, STAGE_LMHEAD};
+const char* decode_stage_name(int stage) {
+    return stage == STAGE_QKV ? "qkv" : stage == STAGE_OPROJ ? "o-proj" : stage == STAGE_GATEUP ? "gate/up" : stage == STAGE_DOWN ? "down" : "lm-head";
+}
+
+// The largest B <= EMMAX_MAX_DECODE_BATCH such that every launch of every stage of every step of 1 .. B rows has a route.  It reads tuning
+// switches (km, km_down, attn_direct, attn_nsplit ...), so the answer can shrink after a session was created: emmax_session_bytes / create
+// check it once, run_prefill and emmax_slots_open again.  first_stage / first_B (optional): the first (stage, batch) without a route
+int model_max_decode_batch(const emmax_model* m, bool exact, int* first_stage, int* first_B) {
+    for (int B = 1; B <= EMMAX_MAX_DECODE_BATCH; ++B)
+        for (int stage : kProjStages)
+            if (decode_stage_route(m, stage, B, exact) <= 0) {
+                if (first_stage) *first_stage = stage;
+                if (first_B) *first_B = B;
+                return B - 1;
+            }
+    return EMMAX_MAX_DECODE_BATCH;
+}
+int session_max_rows(const emmax_session* s) { return model_max_decode_batch(s->m, s->exact); }
 
 // GemvParams of a projection stage of decoder layer `li` (qkv / o-proj / gate-up / down), as every launcher takes them
 static void stage_params(emmax_session* s, int B, int li, int stage, GemvParams& p) {
@@ -341,7 +411,7 @@ int run_group_fork(emmax_session* s, int G, hipStream_t st) {
     for (int g = G - 1; g >= 0; --g)
         for (int j = N - 1; j >= 0; --j) s->S[g * N + j] = s->S[g];
     s->cur_B = rows;
-    const int mode = finish_mode(s), chunk = s->exact ? 8 : EMMAX_KMP_ROWS;   // one finish per lm-head launch of a G x N step (run_lm_head_step)
+    const int mode = finish_mode(s), chunk = stage_chunk(STAGE_LMHEAD, s->exact);   // one finish per lm-head launch of a G x N step (run_lm_head_step)
     for (int r0 = 0; r0 < rows; r0 += chunk) {
         const int n = std::min(chunk, rows - r0);
         const float* lg = s->logits + (size_t)r0 * V;
@@ -366,10 +436,11 @@ int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* logits_out
         if (r || is_prefill) return r;
         return launch_beam_finish(s, false, st);
     }
-    const int chunk = s->exact ? 8 : EMMAX_KMP_ROWS;   // (exact numerics: the two-term MFMA kernels hold 8 rows)
-    if (B > chunk) {   // 33-64 rows: launches of <= 32 rows (each with its own finish: the argmax partials are laid out per launch)
-        if (int r = run_lm_head_step(s, chunk, is_prefill, logits_out, do_finish, st, slot0)) return r;
-        return run_lm_head_step(s, B - chunk, is_prefill, logits_out ? logits_out + (size_t)chunk * m->vocab : nullptr, do_finish, st, slot0 + chunk);
+    const int chunk = stage_chunk(STAGE_LMHEAD, s->exact);
+    if (B > chunk) {   // one launch per chunk, each with its own finish: the argmax partials are laid out per launch
+        for (int r0 = 0; r0 < B; r0 += chunk)
+            if (int r = run_lm_head_step(s, std::min(chunk, B - r0), is_prefill, logits_out ? logits_out + (size_t)r0 * m->vocab : nullptr, do_finish, st, slot0 + r0)) return r;
+        return 0;
     }
     // sampling, processing or scores on: a step's lm-head also writes the fp32 logit rows of its B rows, and the sampled or processing finish
     // reads them
@@ -386,39 +457,28 @@ int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* logits_out
     return 0;
 }
 
-// one stage of decoder layer `li` (the unit the profiler times); the step is stages 0..4 of every layer + lm head
-// exact numerics, batches above 8 rows: the two-term MFMA kernels hold 8 rows (decode_km.hip EX: the two terms of a row in the sixteen batch columns), so a
-// projection stage runs in chunks of 8 rows -- each chunk streams the weights again: the conformance mode covers every batch the default path serves, at
-// ceil(B / 8) times its weight traffic.  (The attention launch takes any batch; the lm-head chunks in run_lm_head_step.)
-#define EMMAX_EXACT_ROWS 8
-static int run_decode_stage_x_chunks(emmax_session* s, int B, int li, int stage, hipStream_t st) {
-    GemvParams p0;
-    stage_params(s, B, li, stage, p0);
-    for (int r = 0; r < B; r += EMMAX_EXACT_ROWS) {
-        GemvParams p = p0;
-        const int n = std::min(EMMAX_EXACT_ROWS, B - r);
-        int grid = 0;
-        if (p.h32) p.h32 += (size_t)r * p.ldh;
-        switch (stage) {   // the chunk's rows of the stage's operands
-            case STAGE_QKV:
-                p.y = (float*)p.y + (size_t)r * p.ldy;
-                p.ctx_len += r; p.page_table += (size_t)r * p.max_pages;
-                break;
-            case STAGE_OPROJ:
-                if (p.attn_part) p.attn_part += (size_t)r * p.Hq * p.nsplit * EMMAX_PSTRIDE;
-                else p.x = (const float*)p.x + (size_t)r * p.ldx;
-                p.y = (bf16*)p.y + (size_t)r * p.ldy;
-                break;
-            case STAGE_GATEUP: p.y = (float*)p.y + (size_t)r * p.ldy; break;
-            default:   // STAGE_DOWN
-                p.x = (const float*)p.x + (size_t)r * p.ldx;
-                p.y = (bf16*)p.y + (size_t)r * p.ldy;
-        }
-        KCHK(launch_proj(s->m->layers[li].proj[stage], p, n, st, &grid, &s->last_via));
+// rows r .. of a projection stage's operands (stage_chunk: which stages run in more than one launch)
+static void offset_rows(GemvParams& p, int stage, int r, bool exact) {
+    const size_t eb = exact ? 4 : 2;   // bytes of an activation element the stages hand on (exact numerics: fp32)
+    if (p.h32) p.h32 += (size_t)r * p.ldh;
+    switch (stage) {
+        case STAGE_QKV:   // (qkv and gate/up run in chunks in exact numerics only, where the rows are read from the fp32 stream)
+            p.y = (char*)p.y + (size_t)r * p.ldy * eb;
+            p.ctx_len += r; p.page_table += (size_t)r * p.max_pages;
+            break;
+        case STAGE_OPROJ:
+            if (p.attn_part) p.attn_part += (size_t)r * p.Hq * p.nsplit * EMMAX_PSTRIDE;
+            else p.x = (const char*)p.x + (size_t)r * p.ldx * eb;
+            p.y = (bf16*)p.y + (size_t)r * p.ldy;
+            break;
+        case STAGE_GATEUP: p.y = (char*)p.y + (size_t)r * p.ldy * eb; break;
+        default:   // STAGE_DOWN
+            p.x = (const char*)p.x + (size_t)r * p.ldx * eb;
+            p.y = (bf16*)p.y + (size_t)r * p.ldy;
     }
-    return 0;
 }
 
+// one stage of decoder layer `li` (the unit the profiler times); the step is stages 0..4 of every layer + lm head
 int run_decode_stage(emmax_session* s, int B, int li, int stage, hipStream_t st) {
     emmax_model* m = s->m;
     const auto& c = m->cfg;
@@ -441,34 +501,28 @@ int run_decode_stage(emmax_session* s, int B, int li, int stage, hipStream_t st)
         return 0;
     }
     if (stage < STAGE_QKV || stage > STAGE_DOWN) return fail(EMMAX_ERR_INVALID, "unknown decode stage %d", stage);
-    if (s->exact && B > EMMAX_EXACT_ROWS) return run_decode_stage_x_chunks(s, B, li, stage, st);
-    // (o-proj at batch >= 3: the K-split MFMA kernel takes it with fp8 weights only, see decode_km.hip)
     const ProjW& w = m->layers[li].proj[stage];
-    GemvParams p;
-    int grid = 0;
-    stage_params(s, B, li, stage, p);
-    if (stage == STAGE_DOWN && B > EMMAX_KMP_ROWS) {   // 33-64 rows: K = 11008 does not fit the eight phases of a four-way split -- two launches of <= 32 rows
-        GemvParams q = p;
-        KCHK(launch_proj(w, q, EMMAX_KMP_ROWS, st, &grid, &s->last_via));
-        q = p;
-        q.x = (const bf16*)q.x + (size_t)EMMAX_KMP_ROWS * q.ldx;
-        q.y = (bf16*)q.y + (size_t)EMMAX_KMP_ROWS * q.ldy;
-        if (q.h32) q.h32 += (size_t)EMMAX_KMP_ROWS * q.ldh;
-        KCHK(launch_proj(w, q, B - EMMAX_KMP_ROWS, st, &grid, &s->last_via));
-        return 0;
+    GemvParams p0;
+    stage_params(s, B, li, stage, p0);
+    const int chunk = stage_chunk(stage, s->exact);
+    for (int r = 0; r < B; r += chunk) {
+        GemvParams p = p0;
+        int grid = 0;
+        offset_rows(p, stage, r, s->exact);
+        KCHK(launch_proj(w, p, std::min(chunk, B - r), st, &grid, &s->last_via));
     }
-    KCHK(launch_proj(w, p, B, st, &grid, &s->last_via));
     return 0;
 }
 
-// layer 0's qkv with the embedding gather folded in (K-split kernel; anything else: embed launch + the plain stage)
+// layer 0's qkv with the embedding gather folded in: decode_ks.hip's check is asked with the launch's own parameters (x_tok set); where it
+// says no, the embed launch and the plain stage
 static int run_qkv0_with_embed(emmax_session* s, int B, hipStream_t st) {
     emmax_model* m = s->m;
     GemvParams p;
     stage_params(s, B, 0, STAGE_QKV, p);
     p.W = m->layers[0].proj[STAGE_QKV].rm;
     p.x = m->embed; p.x_tok = s->cur_tok; p.x_copy = s->dh; p.x_vocab = m->vocab;
-    int r = launch_decode_ks(GEMV_QKV, p, B, st, nullptr);
+    const int r = launch_decode_ks(GEMV_QKV, p, B, st, nullptr);
     if (r == -2) {
         KCHK(launch_decode_embed(s->cur_tok, m->embed, s->dh, B, m->H, m->vocab, st, s->exact ? s->dh32 : h32_of(s)));
         return run_decode_stage(s, B, 0, STAGE_QKV, st);
@@ -478,9 +532,8 @@ static int run_qkv0_with_embed(emmax_session* s, int B, hipStream_t st) {
 
 int run_decode_step(emmax_session* s, int B, hipStream_t st) {
     emmax_model* m = s->m;
-    // batch 1-2 on bf16 weights: the embedding row is read by layer 0's qkv launch itself (K-split kernel) -- one launch fewer
-    const bool fold_embed = B < EMMAX_MFMA_MIN_BATCH && !m->fp8 && !m->mx4 && decode_ks_enabled() && m->H % 64 == 0 && m->H <= 12288 &&
-                            emmax_tune().fold_embed != 0;
+    // batch 1-2 on bf16 weights: the embedding row is read by layer 0's qkv launch itself (decode_ks.hip, when it takes the launch) -- one launch fewer
+    const bool fold_embed = B < EMMAX_MFMA_MIN_BATCH && !m->fp8 && !m->mx4 && decode_ks_enabled() && emmax_tune().fold_embed != 0;
     if (!fold_embed) KCHK(launch_decode_embed(s->cur_tok, m->embed, s->dh, B, m->H, m->vocab, st, s->exact ? s->dh32 : h32_of(s)));
     for (int li = 0; li < m->cfg.n_layers; ++li)
         for (int stage = STAGE_QKV; stage <= STAGE_DOWN; ++stage) {

@@ -58,6 +58,8 @@ SIGNATURES = {
     "emmax_model_bind_weight": (C.c_int, [_vp, C.c_char_p, _vp, C.c_int, _c_i64p, C.c_int]),
     "emmax_model_arena_bytes": (C.c_int64, [_vp]),
     "emmax_model_max_decode_batch": (C.c_int, [_vp]),
+    "emmax_model_max_decode_batch_exact": (C.c_int, [_vp]),
+    "emmax_config_max_decode_batch": (C.c_int, [C.POINTER(ConfigC), C.c_int]),
     "emmax_model_finalize": (C.c_int, [_vp, _vp, C.c_int64, _vp]),
     "emmax_model_aux_bytes": (C.c_int64, [_vp]),
     "emmax_model_build_aux": (C.c_int, [_vp, _vp, C.c_int64, _vp]),
@@ -145,6 +147,7 @@ SIGNATURES = {
     "emmax_session_sample_groups": (C.c_int, [_vp]),
     "emmax_op_decode_stage": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _c_i32p, _c_i32p, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int),
                                         C.POINTER(C.c_int), C.POINTER(C.c_int), _vp]),
+    "emmax_op_decode_route": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "emmax_op_decode_kv_read": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _c_i32p, C.c_int, _c_f32p, _c_f32p, _vp]),
 }
 

@@ -160,9 +160,10 @@ class EmmaxEngine:
 
     def max_decode_batch(self) -> int:
         """Rows of one decode batch this model can run (64 for LLaMA-2-7B shapes, 8 for shapes outside the K-split kernels; MXFP4 weights: 16, or 8
-        when nine rows would split the attention)."""
-        if self.exact:      # the two-term kernels take 8 rows per launch and larger batches run in chunks of 8, whatever the default kernels' shape limits
-            return 64
+        when nine rows would split the attention).  Exact numerics: the two-term kernels take 8 rows per launch and larger batches run in chunks
+        of 8 -- 64 on the shapes those kernels take, 2 where only the batch 1-2 kernel does."""
+        if self.exact:
+            return int(self.lib.emmax_model_max_decode_batch_exact(self._model))
         return int(self.lib.emmax_model_max_decode_batch(self._model))
 
     def weight_bytes(self) -> int:

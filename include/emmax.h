@@ -121,15 +121,22 @@ void emmax_model_destroy(emmax_model* m);
 int emmax_model_bind_weight(emmax_model* m, const char* hf_key, const void* ptr_dev, int dtype,
                             const int64_t* shape, int ndim);
 int64_t emmax_model_arena_bytes(const emmax_model* m);
-/* rows of one decode batch / slot set this model can run: 64 (bf16 or fp8 weights) when every LLM projection is a shape the K-split
- * MFMA kernels take (K % 256 == 0 and <= 4096, N <= 32768, intermediate size % 32 (fp8: % 64) == 0 and <= 11264: LLaMA-2-7B is), else 8 (round 6;
- * round 5: 32; rounds 1-4: 8).  Exact-numerics sessions: 64 whatever the shapes (8 rows per launch, larger batches in chunks).
+/* rows of one decode batch / slot set this model can run: the largest B <= 64 such that every projection launch of every step of 1 .. B
+ * rows is taken by a launcher family -- asked of the launchers' own shape checks (emmax_op_decode_route answers the same question per stage),
+ * under the tuning switches as they are now.  64 (bf16 or fp8 weights) when every LLM projection is a shape the K-split MFMA kernels take
+ * (K % 256 (fp8: % 512) == 0 and <= 4096, N <= 32768, intermediate size % 32 (fp8: % 64) == 0 and <= 11264: LLaMA-2-7B is), else usually 8.
+ * emmax_model_max_decode_batch_exact: the same for exact-numerics sessions (8 rows per launch, larger batches in chunks of 8): 64 on the
+ * shapes decode_km.hip's two-term kernels take, 2 where only decode_ks.hip's do, 0 on fp8 / MXFP4 weights.
  * MXFP4 models (decode_fp8 = 2): 16 -- decode_km.hip is the only kernel family that reads the 4-bit tiles -- or 8 when a batch of nine rows would
  * split the attention (the o-proj then reads split partials, which its 16-row form does not take); emmax_session_bytes / create refuse a larger
  * max_batch for such a model, naming the format.  The one-split rule reads the tuning switches attn_direct / attn_nsplit: the limit is checked when a
  * session is sized and created and again at every prefill and emmax_slots_open, not inside a step -- changing those switches between a prefill of
  * 9-16 rows and its decode steps makes the step fail with EMMAX_ERR_INVALID (no other kernel reads the 4-bit tiles: there is no fall-back). */
 int emmax_model_max_decode_batch(const emmax_model* m);
+int emmax_model_max_decode_batch_exact(const emmax_model* m);
+/* the same planner on a config, before (or without) a model: negative status when the config fails the checks that do not concern the decode
+ * weight format.  An MXFP4 config is accepted by emmax_model_create exactly when this answers >= 8. */
+int emmax_config_max_decode_batch(const emmax_config* cfg, int exact);
 int emmax_model_finalize(emmax_model* m, void* arena_dev, int64_t arena_bytes, emmax_stream stream);
 /* bf16 models: decode batches >= 3 stream the LLM projections from MFMA-fragment-major copies that a model serving batches 1-2
  * never reads.  They live in a SECOND caller-owned arena, built on demand from the finalized main arena (no bound tensors
@@ -568,6 +575,9 @@ int emmax_op_gemm_small(const void* x_dev, const void* W_fm_dev, void* y_dev, in
  *   tok_out_dev             lm-head: int32 [B], the token the greedy finish picks per row -- run against per-row state of the op's own, not
  *                           the session's generation state
  *   via_out                 the launcher family that served the LAST launch of the stage (EMMAX_VIA_*)
+ * emmax_op_decode_route answers on the HOST, launching nothing and needing no device, which family emmax_op_decode_stage would report for
+ * (stage, B rows) of a model -- created is enough -- under the current tuning switches (exact != 0: for an exact-numerics session), from the
+ * copies the model has or emmax_model_build_aux would build now; EMMAX_ERR_INVALID with the refusal when a launch of the stage has no taker.
  * emmax_op_decode_kv_read decodes the K and V rows of (layer, row, positions p0 .. p0 + n - 1) of the paged cache to fp32 on the HOST:
  * k_out_host / v_out_host float [n][Hkv][head_dim], whatever the cache format (bf16, e4m3 + scale, 24-bit, fp32).  page_row_host: int32
  * [max_pages], the row's page-table row to look positions up in (NULL: the session's).  from_stage = 1 (fp8 KV cache only): the row's entry
@@ -576,6 +586,7 @@ enum { EMMAX_VIA_NONE = 0, EMMAX_VIA_KS = 1, EMMAX_VIA_GEMV = 2, EMMAX_VIA_GEMV_
 int emmax_op_decode_stage(emmax_session* s, int layer, int stage, int B, const void* h_in_dev, const float* h32_in_dev, const int32_t* ctx_len_host,
                           const int32_t* page_table_host, const void* x_in_dev, void* h_out_dev, float* h32_out_dev, void* y_out_dev,
                           int32_t* tok_out_dev, int* via_out, int* oproj_form_out, int* nsplit_out, emmax_stream stream);
+int emmax_op_decode_route(const emmax_model* m, int stage, int B, int exact, int* via_out);
 int emmax_op_decode_kv_read(emmax_session* s, int layer, int row, int p0, int n, const int32_t* page_row_host, int from_stage, float* k_out_host,
                             float* v_out_host, emmax_stream stream);
 

@@ -24,6 +24,7 @@ The roundings (emma-x_amd/csrc/decode*.hip), most-rounded form of each stage:
 
 import math
 
+import pytest
 import torch
 
 # ---- dimensions (ISSUE: the smallest at which every kernel family is reached) ------------------------------------------------------------
@@ -34,6 +35,52 @@ PAGE = 64
 PSTRIDE = 132
 INTER_P = (INTER + 63) // 64 * 64   # the activation rows' pitch: the intermediate size padded to 64
 MODELS = {"G": (4, 2, HIDDEN), "W": (32, 32, HIDDEN), "H": (32, 32, 512)}   # name -> (query heads, kv heads, hidden); H: fp8 tiles on the K-split kernels need K % 512
+
+# ---- stages and launcher families (include/emmax.h: the stage numbers of emmax_op_decode_stage, EMMAX_VIA_*) ----------------------------------
+QKV, OPROJ, GATEUP, DOWN, LMHEAD = 0, 2, 3, 4, 5
+KS, GEMV, GEMV_FP8, KM, KMP, MFMA = 1, 2, 3, 4, 5, 6
+REFUSED = -1
+VIA_NAME = {0: "none", KS: "ks", GEMV: "gemv", GEMV_FP8: "gemv_fp8", KM: "km", KMP: "kmp", MFMA: "mfma", REFUSED: "refused"}
+
+
+
+# ---- the routing table (ISSUE): (engine, rows, switches, expected launcher per stage) -------------------------------------------------------
+def _all(v):
+    return {QKV: v, OPROJ: v, GATEUP: v, DOWN: v, LMHEAD: v}
+
+
+def _case(eng, B, sw, via):
+    name = f"{eng}-B{B}" + "".join(f"-{k}{v}" for k, v in sw.items())
+    return pytest.param(eng, B, sw, via, id=name)
+
+
+KM_SPLIT = {QKV: KM, OPROJ: MFMA, GATEUP: KM, DOWN: KM, LMHEAD: KM}       # the bf16 o-proj with split partials stays on decode_mfma.hip
+F8_SMALL_K = {QKV: MFMA, OPROJ: KM, GATEUP: MFMA, DOWN: KM, LMHEAD: MFMA}  # fp8 tiles at K = 256: decode_km.hip refuses (K % 512), decode_mfma.hip serves
+CASES = [
+    _case("G", 1, {}, _all(KS)), _case("G", 2, {}, _all(KS)), _case("G", 1, {"resid32": 0}, _all(KS)),
+    _case("G", 1, {"ks": 0}, _all(GEMV)), _case("G", 2, {"ks": 0}, _all(GEMV)), _case("G", 1, {"ks": 0, "resid32": 0}, _all(GEMV)),
+    _case("G", 3, {}, KM_SPLIT), _case("G", 8, {}, KM_SPLIT), _case("G", 3, {"km": 0}, _all(MFMA)), _case("G", 8, {"km": 0}, _all(MFMA)),
+    _case("W", 5, {}, _all(KM)), _case("W", 9, {}, _all(KM)), _case("W", 16, {}, _all(KM)),
+    _case("W", 17, {}, _all(KMP)), _case("W", 32, {}, _all(KMP)),
+    # 33 rows: down / lm-head run as 32 + 1 rows, and the one-row launch is a batch-1 launch (decode_ks.hip); 64 rows: 32 + 32
+    _case("W", 33, {}, {QKV: KMP, OPROJ: KMP, GATEUP: KMP, DOWN: KS, LMHEAD: KS}), _case("W", 64, {}, _all(KMP)),
+    # fp8 weights, 1-2 rows: the default mask puts the o-proj (and at one row the lm-head) on the row GEMV
+    _case("G8", 1, {}, {QKV: MFMA, OPROJ: GEMV_FP8, GATEUP: MFMA, DOWN: KM, LMHEAD: GEMV_FP8}),
+    _case("G8", 2, {}, {QKV: MFMA, OPROJ: GEMV_FP8, GATEUP: MFMA, DOWN: KM, LMHEAD: MFMA}),
+    _case("G8", 1, {"fp8_gemv": 0}, F8_SMALL_K), _case("G8", 2, {"fp8_gemv": 0}, F8_SMALL_K),
+    _case("G8", 1, {"fp8_gemv": 31}, _all(GEMV_FP8)), _case("G8", 2, {"fp8_gemv": 31}, _all(GEMV_FP8)),
+    _case("G8", 3, {}, F8_SMALL_K), _case("G8", 8, {}, F8_SMALL_K),
+    _case("W8", 8, {}, F8_SMALL_K),
+    _case("W8", 16, {}, {QKV: REFUSED, OPROJ: KM, GATEUP: REFUSED, DOWN: KM, LMHEAD: REFUSED}),
+    _case("W8", 32, {}, {QKV: REFUSED, OPROJ: KMP, GATEUP: REFUSED, DOWN: KMP, LMHEAD: REFUSED}),
+    _case("W8", 64, {}, {QKV: KMP, OPROJ: KMP, GATEUP: KMP, DOWN: KMP, LMHEAD: REFUSED}),
+    # hidden 512: the fp8 qkv / gate-up / lm-head on the K-split kernels (8 and 16 staged rows of decode_km.hip, decode_kmp.hip)
+    _case("H8", 3, {}, _all(KM)), _case("H8", 16, {}, _all(KM)), _case("H8", 32, {}, _all(KMP)),
+    _case("GX", 1, {}, _all(KS)), _case("GX", 2, {}, _all(KS)), _case("GX", 3, {}, _all(KM)), _case("GX", 8, {}, _all(KM)),
+    # a split count other than 8: the o-proj merges the partials in a loop (attn_merge_chunk_loop) -- the staged GEMV's, decode_ks.hip's fp32 one
+    _case("G", 2, {"ks": 0, "attn_nsplit": 4}, _all(GEMV)), _case("GX", 2, {"attn_nsplit": 4}, _all(KS)),
+]
+
 
 # ---- tolerances ------------------------------------------------------------------------------------------------------------------------
 # assert_elementwise(got, ref, rtol, atol_frac): |err| <= atol_frac * rms(ref) + rtol * |ref|; relerr: max|err| / max|ref|.  The project's

@@ -36,11 +36,7 @@ from test_ops_gpu import assert_elementwise, relerr
 
 pytestmark = pytest.mark.gpu
 
-QKV, OPROJ, GATEUP, DOWN, LMHEAD = 0, 2, 3, 4, 5
-KS, GEMV, GEMV_FP8, KM, KMP, MFMA = 1, 2, 3, 4, 5, 6
-REFUSED = -1
-VIA_NAME = {0: "none", KS: "ks", GEMV: "gemv", GEMV_FP8: "gemv_fp8", KM: "km", KMP: "kmp", MFMA: "mfma", REFUSED: "refused"}
-
+from decode_stage_ref import CASES, DOWN, GATEUP, GEMV, GEMV_FP8, KM, KMP, KS, LMHEAD, MFMA, OPROJ, QKV, REFUSED, VIA_NAME
 
 # ---- engines ---------------------------------------------------------------------------------------------------------------------------
 class Eng:
@@ -102,13 +98,21 @@ class Eng:
             flat = pages.reshape(-1).tolist()
             pt_c = (C.c_int32 * len(flat))(*flat)
         via = C.c_int(0)
+        want = self.route(stage, B)   # the host-only route query: the same family, or the same refusal, as what really launches below
         rc = self.lib.emmax_op_decode_stage(self.eng._session, layer, stage, B, h_d.data_ptr(), h32_d.data_ptr(), ctx_c, pt_c, self.L.ptr(x_d),
                                             h_out.data_ptr(), h32_out.data_ptr(), self.L.ptr(y), self.L.ptr(tok), C.byref(via), None, None,
                                             self.L.current_stream())
         self.last_via = via.value
+        self.last_route = want
+        assert rc != 0 or via.value == want, f"stage {stage}, B {B}: ran on {VIA_NAME[via.value]}, the route says {VIA_NAME[want]}"
         self.L.check(rc, f"emmax_op_decode_stage(stage {stage}, B {B})")
         torch.cuda.synchronize()
         return {"h": h_out.cpu(), "h32": h32_out.cpu(), "y": None if y is None else y.cpu(), "tok": None if tok is None else tok.cpu(), "via": via.value}
+
+    def route(self, stage, B):
+        via = C.c_int(0)
+        rc = self.lib.emmax_op_decode_route(self.eng._model, stage, B, int(self.exact), C.byref(via))
+        return via.value if rc == 0 else REFUSED
 
     def kv_read(self, layer, row, p0, n, page_row=None, from_stage=False):
         nn = 1 if from_stage else n
@@ -157,44 +161,6 @@ def engines(device):
         e.eng.close()
 
 
-# ---- the routing table (ISSUE): (engine, rows, switches, expected launcher per stage) -------------------------------------------------------
-def _all(v):
-    return {QKV: v, OPROJ: v, GATEUP: v, DOWN: v, LMHEAD: v}
-
-
-def _case(eng, B, sw, via):
-    name = f"{eng}-B{B}" + "".join(f"-{k}{v}" for k, v in sw.items())
-    return pytest.param(eng, B, sw, via, id=name)
-
-
-KM_SPLIT = {QKV: KM, OPROJ: MFMA, GATEUP: KM, DOWN: KM, LMHEAD: KM}       # the bf16 o-proj with split partials stays on decode_mfma.hip
-F8_SMALL_K = {QKV: MFMA, OPROJ: KM, GATEUP: MFMA, DOWN: KM, LMHEAD: MFMA}  # fp8 tiles at K = 256: decode_km.hip refuses (K % 512), decode_mfma.hip serves
-CASES = [
-    _case("G", 1, {}, _all(KS)), _case("G", 2, {}, _all(KS)), _case("G", 1, {"resid32": 0}, _all(KS)),
-    _case("G", 1, {"ks": 0}, _all(GEMV)), _case("G", 2, {"ks": 0}, _all(GEMV)), _case("G", 1, {"ks": 0, "resid32": 0}, _all(GEMV)),
-    _case("G", 3, {}, KM_SPLIT), _case("G", 8, {}, KM_SPLIT), _case("G", 3, {"km": 0}, _all(MFMA)), _case("G", 8, {"km": 0}, _all(MFMA)),
-    _case("W", 5, {}, _all(KM)), _case("W", 9, {}, _all(KM)), _case("W", 16, {}, _all(KM)),
-    _case("W", 17, {}, _all(KMP)), _case("W", 32, {}, _all(KMP)),
-    # 33 rows: down / lm-head run as 32 + 1 rows, and the one-row launch is a batch-1 launch (decode_ks.hip); 64 rows: 32 + 32
-    _case("W", 33, {}, {QKV: KMP, OPROJ: KMP, GATEUP: KMP, DOWN: KS, LMHEAD: KS}), _case("W", 64, {}, _all(KMP)),
-    # fp8 weights, 1-2 rows: the default mask puts the o-proj (and at one row the lm-head) on the row GEMV
-    _case("G8", 1, {}, {QKV: MFMA, OPROJ: GEMV_FP8, GATEUP: MFMA, DOWN: KM, LMHEAD: GEMV_FP8}),
-    _case("G8", 2, {}, {QKV: MFMA, OPROJ: GEMV_FP8, GATEUP: MFMA, DOWN: KM, LMHEAD: MFMA}),
-    _case("G8", 1, {"fp8_gemv": 0}, F8_SMALL_K), _case("G8", 2, {"fp8_gemv": 0}, F8_SMALL_K),
-    _case("G8", 1, {"fp8_gemv": 31}, _all(GEMV_FP8)), _case("G8", 2, {"fp8_gemv": 31}, _all(GEMV_FP8)),
-    _case("G8", 3, {}, F8_SMALL_K), _case("G8", 8, {}, F8_SMALL_K),
-    _case("W8", 8, {}, F8_SMALL_K),
-    _case("W8", 16, {}, {QKV: REFUSED, OPROJ: KM, GATEUP: REFUSED, DOWN: KM, LMHEAD: REFUSED}),
-    _case("W8", 32, {}, {QKV: REFUSED, OPROJ: KMP, GATEUP: REFUSED, DOWN: KMP, LMHEAD: REFUSED}),
-    _case("W8", 64, {}, {QKV: KMP, OPROJ: KMP, GATEUP: KMP, DOWN: KMP, LMHEAD: REFUSED}),
-    # hidden 512: the fp8 qkv / gate-up / lm-head on the K-split kernels (8 and 16 staged rows of decode_km.hip, decode_kmp.hip)
-    _case("H8", 3, {}, _all(KM)), _case("H8", 16, {}, _all(KM)), _case("H8", 32, {}, _all(KMP)),
-    _case("GX", 1, {}, _all(KS)), _case("GX", 2, {}, _all(KS)), _case("GX", 3, {}, _all(KM)), _case("GX", 8, {}, _all(KM)),
-    # a split count other than 8: the o-proj merges the partials in a loop (attn_merge_chunk_loop) -- the staged GEMV's, decode_ks.hip's fp32 one
-    _case("G", 2, {"ks": 0, "attn_nsplit": 4}, _all(GEMV)), _case("GX", 2, {"attn_nsplit": 4}, _all(KS)),
-]
-
-
 def operand_form(e, via, resid32):
     """which documented rounding form the launcher's norm prologue has (decode_stage_ref.py)"""
     if e.exact:
@@ -229,6 +195,7 @@ def expect_refusal(e, fn):
         fn()
     msg = str(ei.value)
     assert "launch_proj" in msg and "failed (-1)" in msg, msg   # decode_mfma.hip stages at most 8 rows: nothing is left to serve the shape
+    assert e.last_route == REFUSED, f"the launch was refused, the route says {VIA_NAME[e.last_route]}"
 
 
 # ---- QKV: norm prologue, RoPE, the K / V append ---------------------------------------------------------------------------------------------
