@@ -1205,6 +1205,8 @@ static int hybrid_cols_plan(const GemmParams& p, int* n1_out, double* cost_out) 
     return ks;
 }
 
+bool gemm_splitk_fuses_norm(const GemmParams& p) { return splitk_norm_ok(p); }
+
 bool gemm_fuses_norm(const GemmParams& p) {
     if (p.M <= 0 || emmax_tune().gemm_big >= 0 || emmax_tune().gemm_splitk == 0 || emmax_tune().gemm_normfuse == 0) return false;
     return splitk_norm_ok(p) && splitk_plan(p) != 0;

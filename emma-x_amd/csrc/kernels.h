@@ -57,6 +57,7 @@ int gemm_big_tiles(const GemmParams& p);
 int gemm_plan_describe(const GemmParams& p, char* buf, int len);              // the plan launch_gemm would run, as text (host only); returns its kind or -1
 bool gemm_fuses_norm(const GemmParams& p);                                    // launch_gemm(p) will apply p.norm_* (see GemmParams)
 int launch_gemm_splitk(const GemmParams& p, int ksplit, hipStream_t stream, int big = 0);  // ksplit K slices per tile (128x128; big: 256x256) + reduce / epilogue pass (needs p.ws)
+bool gemm_splitk_fuses_norm(const GemmParams& p);                             // launch_gemm_splitk(p, ...) can apply p.norm_* (explicit slices: tools, tests)
 
 // ---- norm.hip ----
 int launch_layernorm(const void* x, void* y, const void* w, const void* b, int rows, int D, int ldx, int ldy, float eps,

@@ -534,5 +534,102 @@ int emmax_op_gemm_small(const void* x, const void* W_fm, void* y, int B, int N, 
     return 0;
 }
 
+// ---- the prefill's stage kernels one by one (ABI 12; tests/test_prefill_stages_gpu.py): pure ops, no session, no device allocation ----------
+int emmax_op_gemm_stream(const void* A, int lda, const void* W, int ldw, float* C32, int ldc, const float* residual32, int ldr, int M, int N, int K,
+                         const void* bias, int act, const void* scale, int n_store, int ksplit, void* ws, int64_t ws_bytes, const void* norm_w,
+                         void* norm_out, int ld_norm, float eps, emmax_stream stream) {
+    if (!A || !W || !C32) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_stream: null argument");
+    if (M < 1 || N < 1 || K < 1 || K % 64 || N % 128 || lda % 8 || ldw % 8 || lda < K || ldw < K)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_stream: M %d, N %d (%% 128), K %d (%% 64), lda %d / ldw %d (%% 8, >= K)", M, N, K, lda, ldw);
+    if (act != 0 && act != 1) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_stream: act %d (0 none, 1 GELU; SwiGLU has no fp32 stream form)", act);
+    if (n_store < 1 || n_store > N || ldc < n_store) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_stream: n_store %d outside 1..N or ldc %d < n_store", n_store, ldc);
+    if (residual32 && ldr < n_store) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_stream: ldr %d < n_store %d", ldr, n_store);
+    if (((uintptr_t)C32 | (uintptr_t)residual32 | (uintptr_t)A | (uintptr_t)W) & 15)   // (the epilogues read and write 16 bytes wherever ld %% 4 == 0)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_stream: A, W and the fp32 rows must be 16-byte aligned");
+    if (ksplit != 0 && (ksplit < 2 || ksplit > K / 64)) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_stream: ksplit %d (0 = the launch plan, else 2..K / 64 = %d)", ksplit, K / 64);
+    if (ws && (ws_bytes < 0 || ((uintptr_t)ws & 15))) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_stream: the workspace must be 16-byte aligned");
+    if (ksplit >= 2 && (!ws || (long long)ksplit * M * N * 4 > ws_bytes))
+        return fail(EMMAX_ERR_NOMEM, "emmax_op_gemm_stream: %d slices need a workspace of %lld bytes (%lld given)", ksplit, (long long)ksplit * M * N * 4, (long long)(ws ? ws_bytes : 0));
+    if ((norm_w == nullptr) != (norm_out == nullptr)) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_stream: norm_w and norm_out go together");
+    GemmParams p = gp(A, lda, W, ldw, C32, ldc, M, N, K);
+    p.bias = bias; p.act = act; p.scale = scale; p.out_f32 = 1; p.res_f32 = 1; p.N_store = n_store;
+    p.residual = residual32 ? residual32 : C32;   // (null: the stream is its own residual -- the prefill's aliased form)
+    p.ldr = residual32 ? ldr : ldc;
+    if (ws) { p.ws = (float*)ws; p.ws_bytes = ws_bytes; }
+    if (norm_out) {
+        p.norm_w = norm_w; p.norm_out = norm_out; p.ld_norm = ld_norm; p.norm_eps = eps;
+        // the norm is never skipped: a path that cannot apply it in its reduce pass refuses the call
+        if (ld_norm < N) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_stream: ld_norm %d < N %d", ld_norm, N);
+        if (ksplit == 0 ? !gemm_fuses_norm(p) : !gemm_splitk_fuses_norm(p))
+            return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_stream: this path does not fuse the RMSNorm (act 0, N = 4096 whole rows, 16-byte aligned rows of ld %% 8, %s)",
+                        ksplit == 0 ? "and a launch plan that splits K with the given workspace" : "explicit slices");
+    }
+    const int r = ksplit == 0 ? launch_gemm(p, (hipStream_t)stream) : launch_gemm_splitk(p, ksplit, (hipStream_t)stream, emmax_tune().gemm_sk_big > 0 ? 1 : 0);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_gemm_stream: unsupported shape or launch failure");
+    return 0;
+}
+int emmax_op_rmsnorm_f32(const float* x, int ldx, void* y, int ldy, const void* w, int rows, int D, float eps, emmax_stream stream) {
+    if (!x || !y || !w) return fail(EMMAX_ERR_INVALID, "emmax_op_rmsnorm_f32: null argument");
+    if (rows < 1 || D < 8 || ldx < D || ldy < D || (((uintptr_t)x | (uintptr_t)y | (uintptr_t)w) & 15))
+        return fail(EMMAX_ERR_INVALID, "emmax_op_rmsnorm_f32: rows %d, D %d, ldx %d / ldy %d (>= D), 16-byte aligned pointers", rows, D, ldx, ldy);
+    const int r = launch_rmsnorm_f32(x, y, w, rows, D, ldx, ldy, eps, (hipStream_t)stream);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_rmsnorm_f32: unsupported shape (D %% 8, D <= 8192, ldx %% 4, ldy %% 8)");
+    return 0;
+}
+int emmax_op_rope_kv_write(void* qkv, int ld, int q_off, int k_off, int v_off, const int32_t* cu, int B, int total_rows, const float* cos_t, const float* sin_t,
+                           void* kcache, void* vcache, const int32_t* page_table, int max_pages, int Hq, int Hkv, int head_dim, int page, emmax_stream stream) {
+    if (!qkv || !cu || !cos_t || !sin_t || !page_table) return fail(EMMAX_ERR_INVALID, "emmax_op_rope_kv_write: null argument");
+    if ((kcache == nullptr) != (vcache == nullptr)) return fail(EMMAX_ERR_INVALID, "emmax_op_rope_kv_write: kcache and vcache go together (both null: rotate only)");
+    if (B < 1 || B > EMMAX_MAX_DECODE_BATCH || total_rows < 1 || Hq < 1 || Hkv < 1 || page < 1 || max_pages < 1)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_rope_kv_write: B %d (1..%d), total_rows %d, heads %d / %d, page %d, max_pages %d", B, EMMAX_MAX_DECODE_BATCH, total_rows, Hq, Hkv, page, max_pages);
+    // V moves in 16-byte pieces in both kernels: rows, offsets and heads in multiples of 8 elements
+    if (head_dim < 8 || head_dim % 8 || (ld | q_off | k_off | v_off) % 8 || q_off < 0 || k_off < 0 || v_off < 0 || q_off + Hq * head_dim > ld || k_off + Hkv * head_dim > ld ||
+        v_off + Hkv * head_dim > ld)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_rope_kv_write: head_dim %d, ld %d and the offsets %d / %d / %d in multiples of 8, the heads inside a row", head_dim, ld, q_off, k_off, v_off);
+    if ((((uintptr_t)qkv | (uintptr_t)kcache | (uintptr_t)vcache) & 15) || (((uintptr_t)cos_t | (uintptr_t)sin_t | (uintptr_t)cu | (uintptr_t)page_table) & 3))
+        return fail(EMMAX_ERR_INVALID, "emmax_op_rope_kv_write: qkv and the caches must be 16-byte aligned, the tables 4-byte aligned");
+    const int r = launch_rope_kv_write(qkv, ld, q_off, k_off, v_off, cu, B, total_rows, cos_t, sin_t, kcache, vcache, page_table, max_pages, Hq, Hkv, head_dim, page,
+                                       (hipStream_t)stream);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_rope_kv_write: launch failure");
+    return 0;
+}
+int emmax_op_kv_quant_rows(void* qkv, int ld, int k_off, int v_off, const int32_t* cu, int B, int total_rows, void* k8, void* v8, float* kscale, float* vscale,
+                           const int32_t* page_table, int max_pages, int Hkv, int head_dim, int page, emmax_stream stream) {
+    if (!qkv || !cu || !k8 || !v8 || !kscale || !vscale || !page_table) return fail(EMMAX_ERR_INVALID, "emmax_op_kv_quant_rows: null argument");
+    if (head_dim != 128) return fail(EMMAX_ERR_INVALID, "emmax_op_kv_quant_rows: head_dim %d (the fp8 KV cache holds rows of 128)", head_dim);
+    if (B < 1 || B > EMMAX_MAX_DECODE_BATCH || total_rows < 1 || Hkv < 1 || page < 1 || max_pages < 1)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_kv_quant_rows: B %d (1..%d), total_rows %d, Hkv %d, page %d, max_pages %d", B, EMMAX_MAX_DECODE_BATCH, total_rows, Hkv, page, max_pages);
+    if ((ld | k_off | v_off) % 8 || k_off < 0 || v_off < 0 || k_off + Hkv * 128 > ld || v_off + Hkv * 128 > ld)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_kv_quant_rows: ld %d and the offsets %d / %d in multiples of 8, the heads inside a row", ld, k_off, v_off);
+    if (((uintptr_t)qkv & 15) || (((uintptr_t)k8 | (uintptr_t)v8) & 7) || (((uintptr_t)kscale | (uintptr_t)vscale | (uintptr_t)cu | (uintptr_t)page_table) & 3))
+        return fail(EMMAX_ERR_INVALID, "emmax_op_kv_quant_rows: qkv must be 16-byte aligned, the e4m3 pages 8-byte, scales and tables 4-byte");
+    const int r = launch_kv_quant_rows(qkv, ld, k_off, v_off, cu, B, total_rows, k8, v8, kscale, vscale, page_table, max_pages, Hkv, head_dim, page, (hipStream_t)stream);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_kv_quant_rows: launch failure");
+    return 0;
+}
+int emmax_op_embed_splice(const int32_t* ids, int P_max, const int32_t* cu, const void* E, const void* patches, void* h, float* h32, int B, int max_seqlen,
+                          int n_patches, int hidden, int vocab, emmax_stream stream) {
+    if (!ids || !cu || !E || !h) return fail(EMMAX_ERR_INVALID, "emmax_op_embed_splice: null argument");
+    if (n_patches < 0 || (n_patches > 0 && !patches)) return fail(EMMAX_ERR_INVALID, "emmax_op_embed_splice: n_patches %d needs the patch rows (0: text only)", n_patches);
+    if (B < 1 || B > EMMAX_MAX_DECODE_BATCH || P_max < 1 || max_seqlen < 1 || max_seqlen > n_patches + P_max || vocab < 1 || hidden < 8 || hidden % 8)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_embed_splice: B %d (1..%d), P_max %d, max_seqlen %d (1..n_patches + P_max), vocab %d, hidden %d (%% 8)", B, EMMAX_MAX_DECODE_BATCH, P_max,
+                    max_seqlen, vocab, hidden);
+    if ((((uintptr_t)E | (uintptr_t)patches | (uintptr_t)h | (uintptr_t)h32) & 15) || (((uintptr_t)ids | (uintptr_t)cu) & 3))
+        return fail(EMMAX_ERR_INVALID, "emmax_op_embed_splice: rows must be 16-byte aligned, ids and cu 4-byte aligned");
+    const int r = launch_embed_splice(ids, P_max, cu, E, patches, h, B, max_seqlen, n_patches, hidden, vocab, (hipStream_t)stream, h32);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_embed_splice: launch failure");
+    return 0;
+}
+int emmax_op_gather_last_rows(const void* in, const float* in32, void* out, float* out32, const int32_t* cu, int B, int D, emmax_stream stream) {
+    if ((!in && !in32) || !out || !cu) return fail(EMMAX_ERR_INVALID, "emmax_op_gather_last_rows: null argument (source rows as bf16 or as fp32, bf16 out, cu)");
+    if (in && in32) return fail(EMMAX_ERR_INVALID, "emmax_op_gather_last_rows: one source, bf16 or fp32");
+    if (B < 1 || B > EMMAX_MAX_DECODE_BATCH || D < 8 || D % 8) return fail(EMMAX_ERR_INVALID, "emmax_op_gather_last_rows: B %d (1..%d), D %d (%% 8)", B, EMMAX_MAX_DECODE_BATCH, D);
+    if ((((uintptr_t)in | (uintptr_t)in32 | (uintptr_t)out | (uintptr_t)out32) & 15) || ((uintptr_t)cu & 3))
+        return fail(EMMAX_ERR_INVALID, "emmax_op_gather_last_rows: rows must be 16-byte aligned, cu 4-byte aligned");
+    const int r = launch_gather_last_rows(in, out, cu, B, D, (hipStream_t)stream, out32, in32);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_gather_last_rows: launch failure");
+    return 0;
+}
+
 
 }  // extern "C"

@@ -43,7 +43,7 @@ class ConfigC(C.Structure):
     ]
 
 
-ABI_VERSION = 11   # EMMAX_ABI_VERSION of include/emmax.h this binding was written against
+ABI_VERSION = 12   # EMMAX_ABI_VERSION of include/emmax.h this binding was written against
 
 # name -> (restype, argtypes): exactly the entry points of include/emmax.h
 SIGNATURES = {
@@ -149,6 +149,14 @@ SIGNATURES = {
                                         C.POINTER(C.c_int), C.POINTER(C.c_int), _vp]),
     "emmax_op_decode_route": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "emmax_op_decode_kv_read": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _c_i32p, C.c_int, _c_f32p, _c_f32p, _vp]),
+    "emmax_op_gemm_stream": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int64,
+                                       _vp, _vp, C.c_int, C.c_float, _vp]),
+    "emmax_op_rmsnorm_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_float, _vp]),
+    "emmax_op_rope_kv_write": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, _vp]),
+    "emmax_op_kv_quant_rows": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "emmax_op_embed_splice": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "emmax_op_gather_last_rows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

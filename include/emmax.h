@@ -42,8 +42,9 @@ extern "C" {
  *   prompt ids;  9: beam search inside the decode step (emmax_session_set_beams and the calls around it), the workspace grew the beam
  *   state and trace; the paged KV region did not grow;  10: emmax_op_decode_stage / emmax_op_decode_kv_read (one decode stage through the step's
  *   own dispatch), the workspace grew that op's per-row scratch;  11: emmax_config.decode_fp8 = 2 selects MXFP4 decode weights (the struct keeps
- *   its layout), emmax_op_quant_mxfp4 / emmax_op_dequant_mxfp4 / emmax_op_gemm_small_mxfp4. */
-#define EMMAX_ABI_VERSION 11
+ *   its layout), emmax_op_quant_mxfp4 / emmax_op_dequant_mxfp4 / emmax_op_gemm_small_mxfp4;  12: the prefill's stage kernels one by one (emmax_op_gemm_stream, emmax_op_rmsnorm_f32,
+ *   emmax_op_rope_kv_write, emmax_op_kv_quant_rows, emmax_op_embed_splice, emmax_op_gather_last_rows): new symbols only. */
+#define EMMAX_ABI_VERSION 12
 
 typedef enum emmax_status {
     EMMAX_OK = 0,
@@ -589,6 +590,51 @@ int emmax_op_decode_stage(emmax_session* s, int layer, int stage, int B, const v
 int emmax_op_decode_route(const emmax_model* m, int stage, int B, int exact, int* via_out);
 int emmax_op_decode_kv_read(emmax_session* s, int layer, int row, int p0, int n, const int32_t* page_row_host, int from_stage, float* k_out_host,
                             float* v_out_host, emmax_stream stream);
+
+/* ---- the prefill's stage kernels one by one (ABI 12; tests/test_prefill_stages_gpu.py) -----------------------------------------------------------
+ * Thin wrappers over the launchers the LLM prefill runs between its GEMMs and its attention: pure ops -- no session, no device allocation.
+ * Every argument check returns EMMAX_ERR_INVALID (a split-K workspace that is too small: EMMAX_ERR_NOMEM) with a message.
+ *   emmax_op_gemm_stream       the projection onto the fp32 residual stream (tuning switch resid32): C32[M, ldc] = residual32 + scale .* act(A W^T +
+ *                              bias) (act 0 none, 1 exact-erf GELU), A bf16 [M, lda], W bf16 [N, ldw], fp32 accumulate, fp32 residual in, fp32 rows out -- nothing of the stream passes
+ *                              through bf16.  residual32 = NULL: the stream is its own residual, C32 += ..., the aliased form the prefill runs (ldr
+ *                              ignored); else a separate fp32 [M, ldr].  Columns >= n_store are not written (1 <= n_store <= N,
+ *                              ldc >= n_store).  ksplit = 0: the launch plan a session stage runs with this workspace (emmax_gemm_plan with
+ *                              has_residual = 2 prints it); ksplit >= 2: that many K slices + the reduce pass, on the tile geometry the tuning switch
+ *                              gemm_sk_big names, as emmax_op_gemm_splitk.  norm_w / norm_out (both or neither): norm_out bf16 [M, ld_norm] =
+ *                              RMSNorm of the result rows (norm_w bf16 [N], eps), applied by the split-K reduce pass.  A path that cannot apply it
+ *                              there (act 1, N != 4096, n_store < N, a launch plan that does not split K) REFUSES the call: the norm is never skipped.
+ *                              K % 64 == 0, N % 128 == 0, lda / ldw % 8 == 0, 16-byte aligned pointers.
+ *   emmax_op_rmsnorm_f32       HF LlamaRMSNorm on fp32 rows x [rows, ldx]: statistics and normalise in fp32, round to bf16, multiply by w bf16 [D], round;
+ *                              y bf16 [rows, ldy].  D % 8 == 0, D <= 8192, ldx % 4 == 0, ldy % 8 == 0.
+ *   emmax_op_rope_kv_write     RoPE (rotate-half pairs d, d + head_dim / 2) in place on the q and k heads of every packed row of qkv bf16 [total_rows, ld]
+ *                              (token t of sequence b = row cu[b] + t, position t) from fp32 tables cos_t / sin_t [position][head_dim / 2], and the
+ *                              append of the rotated K and the V rows to kcache / vcache bf16 [pages][Hkv][page][head_dim] at page
+ *                              page_table[b][t / page], slot t % page.  kcache = vcache = NULL: rotate only (the fp8 KV cache: emmax_op_kv_quant_rows
+ *                              appends).  head_dim, ld and the offsets in multiples of 8; the 16-byte kernel runs when head_dim % 16 == 0 and the
+ *                              tables are 16-byte aligned, else the element-wise one -- bit-identical.  1 <= B <= 64.
+ *   emmax_op_kv_quant_rows     the fp8 KV append of the prefill: the K (already rotated) and V rows of every packed token as e4m3 bytes k8 / v8
+ *                              [pages][Hkv][page][128] with one power-of-two fp32 scale per row (the smallest with amax / scale <= 448; an all-zero
+ *                              row: 1), kscale / vscale fp32 [pages][Hkv][page]; the rows are written back into qkv as bf16 of e4m3 x scale.
+ *                              head_dim 128 only.
+ *   emmax_op_embed_splice      h bf16 [sum_b S_b, hidden], row cu[b] + s = s == 0 ? E[ids[b][0]] : s <= n_patches ? patches[b][s - 1] :
+ *                              E[ids[b][s - n_patches]], ids int32 [B, P_max] clamped to 0 .. vocab - 1, S_b = cu[b + 1] - cu[b] <= max_seqlen;
+ *                              n_patches = 0 (patches may be NULL): text only.  h32 != NULL: the same rows widened to fp32.  hidden % 8 == 0.
+ *   emmax_op_gather_last_rows  out bf16 [B, D] = the last row of every packed sequence, row cu[b + 1] - 1 of in bf16 [.., D] or, when in32 is given
+ *                              instead, of in32 fp32 [.., D] rounded to nearest even; out32 != NULL: the rows also as fp32 (widened, or copied from
+ *                              in32).  D % 8 == 0. */
+int emmax_op_gemm_stream(const void* A_dev, int lda, const void* W_dev, int ldw, float* C32_dev, int ldc, const float* residual32_dev, int ldr, int M, int N,
+                         int K, const void* bias_dev, int act, const void* scale_dev, int n_store, int ksplit, void* ws_dev, int64_t ws_bytes,
+                         const void* norm_w_dev, void* norm_out_dev, int ld_norm, float eps, emmax_stream stream);
+int emmax_op_rmsnorm_f32(const float* x_dev, int ldx, void* y_dev, int ldy, const void* w_dev, int rows, int D, float eps, emmax_stream stream);
+int emmax_op_rope_kv_write(void* qkv_dev, int ld, int q_off, int k_off, int v_off, const int32_t* cu_seqlens_dev, int B, int total_rows, const float* cos_dev,
+                           const float* sin_dev, void* kcache_dev, void* vcache_dev, const int32_t* page_table_dev, int max_pages, int Hq, int Hkv, int head_dim,
+                           int page, emmax_stream stream);
+int emmax_op_kv_quant_rows(void* qkv_dev, int ld, int k_off, int v_off, const int32_t* cu_seqlens_dev, int B, int total_rows, void* k8_dev, void* v8_dev,
+                           float* kscale_dev, float* vscale_dev, const int32_t* page_table_dev, int max_pages, int Hkv, int head_dim, int page, emmax_stream stream);
+int emmax_op_embed_splice(const int32_t* ids_dev, int P_max, const int32_t* cu_seqlens_dev, const void* embed_dev, const void* patches_dev, void* h_dev,
+                          float* h32_dev, int B, int max_seqlen, int n_patches, int hidden, int vocab, emmax_stream stream);
+int emmax_op_gather_last_rows(const void* in_dev, const float* in32_dev, void* out_dev, float* out32_dev, const int32_t* cu_seqlens_dev, int B, int D,
+                              emmax_stream stream);
 
 /* ---- exact numerics (tuning switch exact), kernel by kernel: fp32 operands in, fp32 results out (tests/test_exact_gpu.py).
  * hl_ws: device scratch for the two-term bf16 image of the activation operand, 4 bytes per (padded) element.

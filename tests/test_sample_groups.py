@@ -208,7 +208,7 @@ def test_new_symbols_are_declared_bound_documented_and_exported():
         assert re.search(r"\bint %s\s*\(" % name, header), name
         assert name in _lib.SIGNATURES and hasattr(so, name), name
         assert re.search(r"^\|[^|]*`%s`" % name, table, re.M), f"{name} is missing from the INTEGRATION.md table"
-    assert re.search(r"#define EMMAX_ABI_VERSION 11\b", header) and _lib.ABI_VERSION == 11   # additions only
+    assert re.search(r"#define EMMAX_ABI_VERSION 12\b", header) and _lib.ABI_VERSION == 12   # (additions to ABI 11; 12: the prefill stage ops)
     assert so.emmax_session_sample_groups(None) == -1
     assert so.emmax_session_set_sample_groups(None, 2, None) != 0 and so.emmax_session_clear_sample_groups(None, None) != 0   # null session
 
