@@ -301,6 +301,7 @@ __global__ __launch_bounds__(EMMAX_WAVE) void emmax_beam_merge_kernel(BeamMergeP
         const int P0 = r0 * mp, nfull = L / 64, rem = L % 64;
         for (int i = tid; i < nfull && i < mp; i += EMMAX_WAVE)
             for (int j = 0; j < K; ++j) pt[(size_t)j * mp + i] = P0 + i;
+        if (tid == 0) p.grp_shared[g] = min(nfull, mp);   // the reorders below gather whole table rows: these entries stay equal in the group
         if (tid == 0 && nfull < mp) {
             int next = P0 + (L + 63) / 64;
             for (int j = 0; j < K; ++j) {
@@ -415,6 +416,7 @@ __global__ __launch_bounds__(EMMAX_WAVE) void emmax_group_fork_kernel(GroupForkP
         const int j = e / mp, i = e - j * mp;
         p.page_table[(size_t)(r0 + j) * mp + i] = (i < nfull ? r0 : r0 + j) * mp + i;
     }
+    if (tid == 0) p.grp_shared[g] = min(nfull, mp);
     for (int j = tid; j < N; j += EMMAX_WAVE) {
         const int r = r0 + j;
         p.ctx_len[r] = L; p.done[r] = 0; p.n_out[r] = 0;

@@ -26,8 +26,21 @@ constexpr int PSTRIDE = EMMAX_PSTRIDE;   // floats per attention split partial: 
 // qkv launch of THIS step produced (position L - 1) waits as bf16 in p.kv_stage: every block quantises it itself (so that this step sees
 // the values every later step will read back) and split 0 appends bytes + scale to the cache.
 // DEEP: four chunks of keys in flight per wave instead of two (always with KV8; bf16: tuning switch attn_deep)
-template <int HD, int G, bool DIRECT = false, int NW = 4, bool KV8 = false, bool DEEP = KV8>
+// GRP (grouped steps: N rows per prompt on the prompt's pages, launch_group_attn): the rows of group g = b / N hold the same page ids in their
+// first p.grp_shared[g] table entries, sh = grp_shared[g] * page keys that N blocks per kv head would each stream for themselves.  Two launches,
+// the kernel boundary between them the only hand-off (no counters, no last-arriver block, no fences):
+//   GRP_SPAN  grid (splits, Hkv, groups x query chunks): a block reads each K / V row of its slice of [0, sh) ONCE and scores it against up to G
+//             (row, q head) pairs of the group -- query j of the group is row g N + j / gqa, head hk gqa + j % gqa: the G-queries-per-key loop
+//             of GQA with the rows of a group in the role of the heads of a kv group.  Queries past N gqa and those of finished rows are
+//             computed and never stored.  One partial per (row, head, split) in p.part, the empty partial for an empty slice.  Every key is an
+//             old one: the fp8-cache form de-quantises with the row scale, no staging row.
+//   GRP_TAIL  the DIRECT form over the row's own keys [sh, L): before it normalises, the block folds in the row's p.grp_nsplit shared partials
+//             (attn_merge_chunk's arithmetic).  The range holds at least the key this step appended.
+enum { GRP_OFF = 0, GRP_TAIL = 1, GRP_SPAN = 2 };
+template <int HD, int G, bool DIRECT = false, int NW = 4, bool KV8 = false, bool DEEP = KV8, int GRP = GRP_OFF>
 __global__ __launch_bounds__(NW * 64) void emmax_decode_attn_kernel(DecodeAttnParams p) {
+    static_assert(GRP != GRP_TAIL || DIRECT, "the tail form finishes the row");
+    static_assert(GRP != GRP_SPAN || !DIRECT, "the shared span hands partials on");
     // waves per block: 4 (8-wave blocks were measured no faster at batch 1-2, where 512 four-wave blocks already put 8 waves on a CU,
     // DESIGN.md section 6); the one-split form of batch 5-8 is 256 blocks = ONE per CU: NW = 8 there (tuning switch attn_nw, round 5)
     constexpr int NT = NW * 64;
@@ -40,8 +53,20 @@ __global__ __launch_bounds__(NW * 64) void emmax_decode_attn_kernel(DecodeAttnPa
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int kg = lane >> 4, ch = lane & 15;       // key group within the wave, 16-byte chunk within the row
-    const int split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
+    const int split = blockIdx.x, hk = blockIdx.y;
+    int b = blockIdx.z;
     const int nsplit = gridDim.x;
+    // SPAN: blockIdx.z = group x query chunk; b becomes the group's first row (its table row holds the shared pages), j0 the chunk's first query
+    int gqa = 1, nq = 0, j0 = 0;
+    if constexpr (GRP == GRP_SPAN) {
+        gqa = p.grp_Hq / p.Hkv;
+        nq = p.grp_N * gqa;
+        const int nchunk = (nq + G - 1) / G, g = b / nchunk;
+        j0 = (b - g * nchunk) * G;
+        b = g * p.grp_N;
+    }
+    int sh_pages = 0;   // (clamped: whatever the array holds, no key index leaves the page table)
+    if constexpr (GRP != GRP_OFF) sh_pages = min(max(p.grp_shared[b / p.grp_N], 0), p.max_pages);
     // ONE memory round trip for everything in front of the K/V loads: the context length and the done flag (scalar loads,
     // requested first), the row's whole page table (<= SP entries, two per thread, kept in registers until all requests are
     // out, then written to LDS) and q.  (A loop that waited for each table load, then a dependent scalar load for the length,
@@ -52,22 +77,45 @@ __global__ __launch_bounds__(NW * 64) void emmax_decode_attn_kernel(DecodeAttnPa
     const int32_t* ptab = p.page_table + (size_t)b * p.max_pages;
     // q (already rotated, bf16) for the G heads of this kv head: lane holds elements ch*8 .. +8
     u32x4_t q[G];
+    int qhead[G];      // SPAN: (row, head) index row * Hq + head of query gq, and whether its partial is stored
+    bool qlive[G];
 #pragma unroll
-    for (int gq = 0; gq < G; ++gq)
+    for (int gq = 0; gq < G; ++gq) {
+        if constexpr (GRP == GRP_SPAN) {
+            const int j = min(j0 + gq, nq - 1), row = b + j / gqa, head = hk * gqa + j % gqa;
+            qhead[gq] = row * p.grp_Hq + head;
+            qlive[gq] = j0 + gq < nq && !(p.done && p.done[row] != 0);
+            q[gq] = *(const u32x4_t*)((const bf16_t*)p.q + (size_t)row * p.ldq + head * HD + ch * 8);
+            continue;
+        }
         q[gq] = *(const u32x4_t*)((const bf16_t*)p.q + (size_t)b * p.ldq + (hk * G + gq) * HD + ch * 8);
+    }
     const int pt0 = ptab[min(tid, p.max_pages - 1)], pt1 = ptab[min(tid + NT, p.max_pages - 1)];
     __builtin_amdgcn_sched_barrier(0);   // every request above is out before the first wait (hipcc sinks the q load below the LDS write otherwise)
     s_pages[tid] = pt0;
     if (NT < SP) s_pages[tid + NT] = pt1;
-    const int L = ctx_now + 1;                      // keys including the one appended by the qkv kernel of this step
+    const int sh = sh_pages << p.page_shift;
+    const int L = GRP == GRP_SPAN ? sh : ctx_now + 1;   // keys including the one appended by the qkv kernel of this step (SPAN: the shared ones)
     int kps = (L + nsplit - 1) >> __builtin_ctz(nsplit);   // the split count is a power of two (launcher)
     kps = (kps + 15) & ~15;
-    const int k0 = split * kps;
+    const int k0 = (GRP == GRP_TAIL ? sh : 0) + split * kps;   // (TAIL: one split, [sh, L))
     const int k1 = min(L, k0 + kps);
     const int Hq = p.Hkv * G;
     float* part = p.part + ((size_t)(b * Hq + hk * G) * nsplit + split) * PSTRIDE;
 
-    if (k0 >= L || row_done) {   // empty split, or a row that no longer decodes: no K/V traffic
+    if constexpr (GRP == GRP_SPAN) {
+        bool any = false;
+#pragma unroll
+        for (int gq = 0; gq < G; ++gq) any = any || qlive[gq];
+        if (!any) return;   // every row of the chunk has finished: the tail launch writes their zeros and reads no partial
+        if (k0 >= L) {      // empty slice (or no shared page at all): the empty partial
+#pragma unroll
+            for (int gq = 0; gq < G; ++gq)
+                if (qlive[gq])
+                    for (int j = tid; j < PSTRIDE; j += NT) p.part[((size_t)qhead[gq] * nsplit + split) * PSTRIDE + j] = (j == HD) ? -INFINITY : 0.f;
+            return;
+        }
+    } else if (k0 >= L || row_done) {   // empty split, or a row that no longer decodes: no K/V traffic
         if constexpr (DIRECT) {   // a row that no longer decodes: zeros (what the merge of an empty partial gives)
             for (int i = tid; i < G * (HD / 8); i += NT)
                 *((u32x4_t*)((bf16_t*)p.o_out + (size_t)b * p.ldq + hk * G * HD) + i) = (u32x4_t){0u, 0u, 0u, 0u};
@@ -87,14 +135,14 @@ __global__ __launch_bounds__(NW * 64) void emmax_decode_attn_kernel(DecodeAttnPa
     const uint8_t* vc8 = (const uint8_t*)p.vcache;
     // KV8: the step's new K / V row of this kv head, requested now (one round trip with the page table), quantised below
     u32x4_t new_k = {0u, 0u, 0u, 0u}, new_v = {0u, 0u, 0u, 0u};
-    if constexpr (KV8) {
+    if constexpr (KV8 && GRP != GRP_SPAN) {
         const bf16_t* st = (const bf16_t*)p.kv_stage + ((size_t)b * p.Hkv + hk) * 2 * HD + ch * 8;
         new_k = *(const u32x4_t*)st;
         new_v = *(const u32x4_t*)(st + HD);
     }
 
     __syncthreads();
-    if constexpr (KV8) {
+    if constexpr (KV8 && GRP != GRP_SPAN) {
         // one scale per row (e4m3_row_scale of the amax) over the 16 lanes of a key group (every group of every wave holds the same row)
         auto requant = [&](u32x4_t& v, uint8_t* cache, float* scales) {
             float am = 0.f;
@@ -139,7 +187,9 @@ __global__ __launch_bounds__(NW * 64) void emmax_decode_attn_kernel(DecodeAttnPa
                 const size_t rowi = (((size_t)pg8 * p.Hkv + hk) << p.page_shift) + (kk & (p.page - 1));
                 const u32x2_t k8 = __builtin_nontemporal_load((const u32x2_t*)(kc8 + rowi * HD + ch * 8)),   // (non-temporal: see the bf16 path below)
                               v8 = __builtin_nontemporal_load((const u32x2_t*)(vc8 + rowi * HD + ch * 8));
-                kv[u] = (u32x4_t){k8[0], k8[1], __float_as_uint(p.kscale[rowi]), (uint32_t)key};
+                // (GRP: the position the lane READ -- a masked lane re-reads key k0, and a tail that is the new key alone starts on the row
+                // the cache does not hold yet: bytes and scale there are anything, and 0 x NaN is not 0)
+                kv[u] = (u32x4_t){k8[0], k8[1], __float_as_uint(p.kscale[rowi]), (uint32_t)(GRP != GRP_OFF ? kk : key)};
                 vv[u] = (u32x4_t){v8[0], v8[1], __float_as_uint(p.vscale[rowi]), 0u};
                 continue;
             }
@@ -160,7 +210,7 @@ __global__ __launch_bounds__(NW * 64) void emmax_decode_attn_kernel(DecodeAttnPa
         if constexpr (KV8) {   // bytes -> bf16 x scale; the key of this step comes from the staging row (its cache bytes may not have landed)
 #pragma unroll
             for (int u = 0; u < KU; ++u) {
-                const bool is_new = (int)kv[u][3] == L - 1;
+                const bool is_new = GRP != GRP_SPAN && (int)kv[u][3] == L - 1;
                 const u32x4_t kd = dequant8_e4m3((u32x2_t){kv[u][0], kv[u][1]}, __uint_as_float(kv[u][2]));
                 const u32x4_t vd = dequant8_e4m3((u32x2_t){vv[u][0], vv[u][1]}, __uint_as_float(vv[u][2]));
 #pragma unroll
@@ -277,6 +327,34 @@ __global__ __launch_bounds__(NW * 64) void emmax_decode_attn_kernel(DecodeAttnPa
     if constexpr (DIRECT) {   // this block holds the head's whole result -- normalise and write the bf16 row directly
         for (int i = tid; i < G * (HD / 8); i += NT) {
             const int gq = i / (HD / 8), c = i - gq * (HD / 8);
+            if constexpr (GRP == GRP_TAIL) {   // the row's shared partials and this block's own: attn_merge_chunk_loop's arithmetic
+                const float* sp = p.part + (size_t)(b * Hq + hk * G + gq) * p.grp_nsplit * PSTRIDE;
+                const float mt = part_value(gq, HD);
+                float M = mt;
+                for (int s = 0; s < p.grp_nsplit; ++s) M = fmaxf(M, sp[s * PSTRIDE + HD]);
+                const float wt = (mt == -INFINITY) ? 0.f : __expf(mt - M);
+                float den = part_value(gq, HD + 1) * wt, a8[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) a8[j] = part_value(gq, c * 8 + j) * wt;
+                for (int s = 0; s < p.grp_nsplit; ++s) {
+                    const float ms = sp[s * PSTRIDE + HD];
+                    const float wgt = (ms == -INFINITY) ? 0.f : __expf(ms - M);
+                    den = __builtin_fmaf(sp[s * PSTRIDE + HD + 1], wgt, den);
+                    const f32x4_t o0 = *(const f32x4_t*)(sp + s * PSTRIDE + c * 8);
+                    const f32x4_t o1 = *(const f32x4_t*)(sp + s * PSTRIDE + c * 8 + 4);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        a8[j] = __builtin_fmaf(o0[j], wgt, a8[j]);
+                        a8[4 + j] = __builtin_fmaf(o1[j], wgt, a8[4 + j]);
+                    }
+                }
+                const float inv = den > 0.f ? 1.0f / den : 0.f;
+                u32x4_t v;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = pack_bf16x2(a8[2 * j] * inv, a8[2 * j + 1] * inv);
+                *((u32x4_t*)((bf16_t*)p.o_out + (size_t)b * p.ldq + (hk * G + gq) * HD) + c) = v;
+                continue;
+            }
             const float den = part_value(gq, HD + 1);
             const float inv = den > 0.f ? 1.0f / den : 0.f;   // the arithmetic of attn_merge_chunk<1> (weight exp(m - M) = 1)
             u32x4_t v;
@@ -284,6 +362,13 @@ __global__ __launch_bounds__(NW * 64) void emmax_decode_attn_kernel(DecodeAttnPa
             for (int j = 0; j < 4; ++j) v[j] = pack_bf16x2(part_value(gq, c * 8 + 2 * j) * inv, part_value(gq, c * 8 + 2 * j + 1) * inv);
             *((u32x4_t*)((bf16_t*)p.o_out + (size_t)b * p.ldq + (hk * G + gq) * HD) + c) = v;
         }
+        return;
+    }
+    if constexpr (GRP == GRP_SPAN) {
+#pragma unroll
+        for (int gq = 0; gq < G; ++gq)
+            if (qlive[gq])
+                for (int j = tid; j < PSTRIDE; j += NT) p.part[((size_t)qhead[gq] * nsplit + split) * PSTRIDE + j] = part_value(gq, j);
         return;
     }
     for (int i = tid; i < G * PSTRIDE; i += NT) {
@@ -343,6 +428,58 @@ int launch_decode_attn(const DecodeAttnParams& p_in, int B, int Hq, int head_dim
         break
         ATTN_CASE(1); ATTN_CASE(2); ATTN_CASE(4); ATTN_CASE(8);
 #undef ATTN_CASE
+        default: return -1;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// ---- grouped steps: the shared span once per group, then the rows' tails (the kernel's GRP forms) ----
+// queries per span block: the narrowest instantiated width that holds the group's N x gqa (row, q head) pairs, else chunks of 8
+static int group_attn_width(int nq) { return nq <= 2 ? 2 : nq <= 4 ? 4 : 8; }
+bool group_attn_takes(int B, int N, int Hq, int Hkv) {
+    if (N < 2 || B < N || B > EMMAX_MAX_DECODE_BATCH || B % N || Hkv < 1 || Hq % Hkv) return false;
+    const int gqa = Hq / Hkv;
+    return gqa == 1 || gqa == 2 || gqa == 4 || gqa == 8;
+}
+// splits of the shared span: about one block per CU, as decode_attn_nsplit argues for batch >= 3 (one group of 8 rows at 32 heads: 8 splits, eight
+// groups: one); at most EMMAX_GROUP_ATTN_MAX_SPLITS partials for the tail to fold in
+int group_attn_nsplit(int B, int N, int Hq, int Hkv) {
+    const int nq = N * (Hq / Hkv), w = group_attn_width(nq), blocks = Hkv * (B / N) * ((nq + w - 1) / w);
+    int ns = 1;   // the smallest power of two (the kernel divides the keys among the splits by shifting) that leaves no CU without a block:
+    while (ns * blocks < 256 && ns < EMMAX_GROUP_ATTN_MAX_SPLITS) ns *= 2;   // rounding DOWN left 160 blocks at five groups of 8 -- 5.93 -> 6.11 ms per step
+    return ns;
+}
+
+int launch_group_attn(const DecodeAttnParams& p_in, int B, int N, int Hq, int head_dim, hipStream_t stream) {
+    if (head_dim != 128 || !group_attn_takes(B, N, Hq, p_in.Hkv)) return -1;
+    DecodeAttnParams p = p_in;
+    if (p.max_pages < 1 || p.max_pages > 512 || p.page < 1 || (p.page & (p.page - 1))) return -1;   // as launch_decode_attn
+    if (!p.o_out || !p.part || !p.grp_shared) return -1;
+    if (p.kv_stage && (!p.kscale || !p.vscale)) return -1;
+    p.page_shift = 0;
+    while ((1 << p.page_shift) < p.page) ++p.page_shift;
+    const int G = Hq / p.Hkv, nq = N * G, w = group_attn_width(nq);
+    p.grp_N = N; p.grp_Hq = Hq; p.grp_nsplit = group_attn_nsplit(B, N, Hq, p.Hkv);
+    const dim3 span(p.grp_nsplit, p.Hkv, (B / N) * ((nq + w - 1) / w)), tail(1, p.Hkv, B), block(256);
+    switch (w) {
+#define SPAN_CASE(W)                                                                                                                   \
+    case W:                                                                                                                            \
+        if (p.kv_stage) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, W, false, 4, true, true, GRP_SPAN>), span, block, 0, stream, p); \
+        else hipLaunchKernelGGL((emmax_decode_attn_kernel<128, W, false, 4, false, false, GRP_SPAN>), span, block, 0, stream, p);      \
+        break
+        SPAN_CASE(2); SPAN_CASE(4); SPAN_CASE(8);
+#undef SPAN_CASE
+        default: return -1;
+    }
+    if (hipGetLastError() != hipSuccess) return -4;
+    switch (G) {
+#define TAIL_CASE(GG)                                                                                                                  \
+    case GG:                                                                                                                           \
+        if (p.kv_stage) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, true, 4, true, true, GRP_TAIL>), tail, block, 0, stream, p); \
+        else hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, true, 4, false, false, GRP_TAIL>), tail, block, 0, stream, p);      \
+        break
+        TAIL_CASE(1); TAIL_CASE(2); TAIL_CASE(4); TAIL_CASE(8);
+#undef TAIL_CASE
         default: return -1;
     }
     return hipGetLastError() == hipSuccess ? 0 : -4;

@@ -169,6 +169,9 @@ struct EmmaxTune {
     int attn_nw;         // waves per decode-attention block: 0 = by shape (4; 8 for the one-split form when that leaves <= 256 blocks), 4 / 8 forced
     int streamk;         // 1: stream-K work split in decode_mfma.hip; 0: whole tasks per block
     int fp8_gemv;        // -1: default routing of the batch 1-2 fp8 projections; >= 0: bit mask (1 qkv, 2 o-proj, 4 gate/up, 8 down, 16 lm-head) on the row GEMV
+    int attn_group;      // decode attention of a grouped step (sample groups, beams): the shared prompt pages read once per group and the rows' own tails by a second
+                         //   launch -- -1 = at the shapes where that was measured faster (sample groups of 4-16 rows at 32 / 48 / 64 rows; step.hip: attn_group_rows), 1 = wherever the kernels
+                         //   take the step, 0 = never: one launch, every row streams its whole context
     int attn_nsplit;     // 0: KV splits of the decode attention chosen from (B, kv heads); > 0: forced (rounded down to 2^k, <= 16)
     int attn_direct;     // 1: with one KV split the attention launch writes the normalised bf16 row itself
     int fold_embed;      // 1: layer 0's qkv launch gathers the embedding row itself (batch 1-2, bf16)
@@ -319,9 +322,20 @@ struct DecodeAttnParams {
     int page_shift;         // log2(page), set by the launcher
     float scale;
     long long kv24;         // exact numerics (launch_x_decode_attn): > 0 = 24-bit caches (GemvParams::kv24), 0 = fp32 rows
+    // grouped form (launch_group_attn): rows g N .. g N + N - 1 hold the same page ids in their first grp_shared[g] table entries.  A DEVICE
+    // array: a captured step is replayed for later prompts of other lengths
+    const int32_t* grp_shared;
+    int grp_N, grp_nsplit, grp_Hq;   // rows per group; splits of the shared span; q heads (set by the launcher)
 };
 int decode_attn_nsplit(int B, int Hkv);
 int launch_decode_attn(const DecodeAttnParams& p, int B, int Hq, int head_dim, int nsplit, hipStream_t stream);
+// The attention of a step whose B rows are B / N groups on shared prompt pages, in two launches: the span [0, grp_shared[g] * page) once per
+// group into split partials (p.part: group_attn_nsplit() per (row, head)), then one block per (row, kv head) over the row's own tail, which
+// folds the partials in and writes the bf16 row (p.o_out).  bf16 and fp8 cache; -1 for a shape it does not take (group_attn_takes)
+enum { EMMAX_GROUP_ATTN_MAX_SPLITS = 8 };
+bool group_attn_takes(int B, int N, int Hq, int Hkv);
+int group_attn_nsplit(int B, int N, int Hq, int Hkv);
+int launch_group_attn(const DecodeAttnParams& p, int B, int N, int Hq, int head_dim, hipStream_t stream);
 int launch_x_decode_attn(const DecodeAttnParams& p, int B, int Hq, int head_dim, int nsplit, hipStream_t stream);   // exact.hip: fp32 q, fp32 cache
 
 // ---- decode.hip: the greedy finish of a step ----
@@ -477,6 +491,7 @@ struct BeamMergeParams {
     int32_t *cur_tok, *ctx_len, *done, *n_out;
     const int32_t* max_new_p;
     int32_t *page_table, *spare, *copy_src, *copy_dst, *copy_ntok;
+    int32_t* grp_shared;        // [groups], prefill form: the complete prompt pages every beam of the group references (DecodeAttnParams::grp_shared)
     int32_t *tr_tok, *tr_par;   // [max_out][tr_ld]
     float *tr_score, *tr_lse;
     int32_t* tc_idx;            // [max_out][2 tr_ld]
@@ -512,6 +527,7 @@ int launch_beam_resolve(const BeamResolveParams& p, hipStream_t stream);
 struct GroupForkParams {
     int N, max_pages;
     int32_t *page_table, *ctx_len, *done, *n_out, *max_new, *stop_m, *stop_after, *copy_src, *copy_dst, *copy_ntok;
+    int32_t* grp_shared;             // [groups]: the complete prompt pages the group's rows share (DecodeAttnParams::grp_shared)
     int S[EMMAX_MAX_DECODE_BATCH];   // the groups' prompt contexts
 };
 int launch_group_fork(const GroupForkParams& p, int groups, hipStream_t stream);

@@ -45,7 +45,7 @@ const TuneEntry kTune[] = {
     {"gemm_lnfuse", &EmmaxTune::gemm_lnfuse, 1}, {"attn_resident", &EmmaxTune::attn_resident, -1},
     {"gemm_hybrid", &EmmaxTune::gemm_hybrid, 1}, {"gemm_normfuse", &EmmaxTune::gemm_normfuse, 1},
     {"resid32", &EmmaxTune::resid32, 1},       {"kv_fp8", &EmmaxTune::kv_fp8, 0},
-    {"exact", &EmmaxTune::exact, 0},
+    {"exact", &EmmaxTune::exact, 0},           {"attn_group", &EmmaxTune::attn_group, -1},
 };
 EmmaxTune g_tune;
 std::once_flag g_tune_once;

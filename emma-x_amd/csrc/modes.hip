@@ -248,6 +248,8 @@ int emmax_session_clear_sample_groups(emmax_session* s, emmax_stream stream) {
 
 int emmax_session_sample_groups(const emmax_session* s) { return s ? s->grp_N : -1; }
 
+int emmax_session_attn_grouped(const emmax_session* s, int B) { return !s ? -1 : (B >= 1 && attn_group_rows(s, B)) ? 1 : 0; }
+
 int emmax_session_beam_trace(emmax_session* s, int max_new, int32_t* tok_dev, int32_t* parent_dev, float* score_dev, float* lse_dev, int32_t* cand_idx_dev,
                              float* cand_acc_dev, emmax_stream stream) {
     if (!s) return fail(EMMAX_ERR_INVALID, "null argument");

@@ -177,6 +177,50 @@ int emmax_op_decode_attention_kv8(const void* q, void* kcache8, void* vcache8, f
     if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_decode_attention_kv8: unsupported (GQA group in {1,2,4,8}, page = 2^k, max_pages <= 512, nsplit = 2^k)");
     return 0;
 }
+// the grouped form (decode_attn.hip: launch_group_attn) as a pure op: the shapes and the groups' shared page counts are checked on the host
+// BEFORE anything is launched (the counts are read back: the call synchronises the stream and cannot be captured)
+static int op_group_attention(const char* who, DecodeAttnParams& a, int B, int Hq, int N, const int32_t* shared_pages, hipStream_t st) {
+    if (!a.q || !a.kcache || !a.vcache || !a.page_table || !a.ctx_len || !a.o_out || !a.part || !shared_pages) return fail(EMMAX_ERR_INVALID, "%s: null argument", who);
+    if (N < 2 || B < 1 || B % N) return fail(EMMAX_ERR_INVALID, "%s: %d rows are not whole groups of N = %d >= 2 rows", who, B, N);
+    if (!group_attn_takes(B, N, Hq, a.Hkv) || a.max_pages < 1 || a.max_pages > 512 || a.page < 1 || (a.page & (a.page - 1)))
+        return fail(EMMAX_ERR_INVALID, "%s: unsupported (B <= %d, GQA group in {1,2,4,8}, page = 2^k, max_pages <= 512)", who, EMMAX_MAX_DECODE_BATCH);
+    int32_t sh[EMMAX_MAX_DECODE_BATCH], ctx[EMMAX_MAX_DECODE_BATCH];
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(sh, shared_pages, (size_t)(B / N) * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ctx, a.ctx_len, (size_t)B * 4, hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; ++b) {
+        const int g = b / N;
+        if (sh[g] < 0 || sh[g] > a.max_pages) return fail(EMMAX_ERR_INVALID, "%s: group %d shares %d pages of a table of %d", who, g, sh[g], a.max_pages);
+        // (a span past a row's context would leave the row's tail empty: it would write zeros and drop the partials)
+        if ((long long)sh[g] * a.page > ctx[b]) return fail(EMMAX_ERR_INVALID, "%s: group %d shares %d pages, row %d holds %d keys", who, g, sh[g], b, ctx[b]);
+    }
+    a.grp_shared = shared_pages;
+    const int r = launch_group_attn(a, B, N, Hq, 128, st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "%s: launch failed (%d)", who, r);
+    return 0;
+}
+int emmax_op_decode_attention_group(const void* q, const void* kcache, const void* vcache, const int32_t* page_table, const int32_t* ctx_len,
+                                    const int32_t* done, void* o_out, int B, int Hq, int Hkv, int page, int max_pages, float scale, int N,
+                                    const int32_t* shared_pages, float* part_ws, emmax_stream st) {
+    if (Hkv < 1 || Hq % Hkv) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_attention_group: bad heads");
+    DecodeAttnParams a;
+    memset(&a, 0, sizeof(a));
+    a.q = q; a.ldq = Hq * 128; a.kcache = kcache; a.vcache = vcache; a.page_table = page_table; a.ctx_len = ctx_len; a.done = done;
+    a.part = part_ws; a.Hkv = Hkv; a.page = page; a.max_pages = max_pages; a.scale = scale; a.o_out = o_out;
+    return op_group_attention("emmax_op_decode_attention_group", a, B, Hq, N, shared_pages, (hipStream_t)st);
+}
+int emmax_op_decode_attention_group_kv8(const void* q, void* kcache8, void* vcache8, float* kscale, float* vscale, const void* kv_stage,
+                                        const int32_t* page_table, const int32_t* ctx_len, const int32_t* done, float* part_ws, void* o_out, int B,
+                                        int Hq, int Hkv, int page, int max_pages, int N, const int32_t* shared_pages, float scale, emmax_stream st) {
+    if (Hkv < 1 || Hq % Hkv) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_attention_group_kv8: bad heads");
+    if (!kscale || !vscale || !kv_stage) return fail(EMMAX_ERR_INVALID, "emmax_op_decode_attention_group_kv8: null argument");
+    DecodeAttnParams a;
+    memset(&a, 0, sizeof(a));
+    a.q = q; a.ldq = Hq * 128; a.kcache = kcache8; a.vcache = vcache8; a.kscale = kscale; a.vscale = vscale; a.kv_stage = kv_stage;
+    a.page_table = page_table; a.ctx_len = ctx_len; a.done = done; a.part = part_ws; a.o_out = o_out;
+    a.Hkv = Hkv; a.page = page; a.max_pages = max_pages; a.scale = scale;
+    return op_group_attention("emmax_op_decode_attention_group_kv8", a, B, Hq, N, shared_pages, (hipStream_t)st);
+}
 // ---- exact numerics: single-kernel entry points (fp32 in, fp32 out; hl_ws: caller scratch for the two-term image of the operand) ----
 int emmax_op_x_gemm(const float* A32, int lda, const void* W, int ldw, float* C32, int ldc, int M, int N, int K, const void* bias, int act,
                     const float* residual32, int ldr, void* hl_ws, void* ws, int64_t ws_bytes, emmax_stream stream) {

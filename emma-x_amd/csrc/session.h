@@ -195,6 +195,9 @@ struct emmax_session {
     // SAMPLE GROUPS (emmax_session_set_sample_groups; step.hip: run_group_fork): N sampled rows per prefilled prompt, 0 = off.  Rows g N + j are
     // the samples of prompt g; the fork's copy list lives in the beams' (csrc / cdst / cntok: beams and groups exclude each other)
     int grp_N = 0;
+    // complete prompt pages the rows of group g share, int32 [groups]: written by the fork (sample groups: run_group_fork; beams: the prefill
+    // form of the beam merge), read by the grouped decode attention (step.hip: attn_group_rows)
+    int32_t* grp_shared = nullptr;
     int32_t *part_idx2;
     int32_t *part_idx, *cur_tok, *ctx_len, *done, *n_out, *out_ids, *max_new_d /* [max_batch] */, *page_table;
     // EXACT NUMERICS (round 6; tuning switch `exact` at emmax_session_create): fp32 activations end to end.  x32a: the fp32 result of the GEMM
@@ -240,6 +243,7 @@ struct emmax_session {
     int32_t *op_state = nullptr, *op_out = nullptr;
     hipEvent_t ev = nullptr;
     int graph_epoch = -1;      // emmax_tune().epoch the graph was captured under (a changed switch re-captures)
+    int graph_grp = 0;    // attn_group_rows() the step was captured under (rows per group of the grouped attention route, 0 = today's launch)
     int graph_mode = 0;   // finish_mode() the step was captured under (the parameters and score buffers are device words: a change re-captures nothing)
     hipStream_t own_stream = nullptr;   // where a call made on the (uncapturable) legacy stream runs: StreamScope
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
@@ -317,6 +321,7 @@ int run_group_fork(emmax_session* s, int G, hipStream_t st);
 int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* logits_out, bool do_finish, hipStream_t st, int slot0 = 0);
 int run_decode_stage(emmax_session* s, int B, int li, int stage, hipStream_t st);
 int decode_oproj_form(const emmax_model* m, bool exact, int B, int* nsplit);
+int attn_group_rows(const emmax_session* s, int B);                // rows per group when a B-row step takes the grouped attention route, else 0
 int run_decode_step(emmax_session* s, int B, hipStream_t st);
 int ensure_graph(emmax_session* s, int B, hipStream_t st);
 int launch_graph_step(emmax_session* s, int B, hipStream_t st);

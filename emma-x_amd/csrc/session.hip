@@ -108,6 +108,7 @@ static void plan_session(emmax_session* s, Bump& b) {
         s->beam.csrc = (int32_t*)b.bytes(Rb * 4);
         s->beam.cdst = (int32_t*)b.bytes(Rb * 4);
         s->beam.cntok = (int32_t*)b.bytes(Rb * 4);
+        s->grp_shared = (int32_t*)b.bytes(Rb * 4);
         s->beam.pw = (float*)b.bytes((T + 1) * 4);
         s->beam.tr_tok = (int32_t*)b.bytes(T * Rb * 4);
         s->beam.tr_par = (int32_t*)b.bytes(T * Rb * 4);

@@ -115,6 +115,26 @@ static bool attn_direct_on(const emmax_model* m, bool exact, int B) {
 }
 static bool attn_direct_on(const emmax_session* s, int B) { return attn_direct_on(s->m, s->exact, B); }
 
+// THE route rule of the grouped attention (decode_attn.hip: launch_group_attn): rows per group when a B-row step of the session, as configured
+// now, reads each group's shared prompt pages once, else 0 = the launch of a plain batch.  Groups on (sample groups, or beams behind their
+// fork), default numerics, a step whose attention is the one-split direct form, B whole groups of a width the launcher takes, and the tuning
+// switch attn_group: 0 never, 1 wherever all of that holds, -1 (default) only at the batches where the two launches were MEASURED faster than
+// the one (profiles/group_attn_bench.txt; ms per step at context 768, 32 layers, one launch -> two, spread <= 0.02):
+//    8 rows 3.093 -> 3.340   16 rows 3.379 -> 3.557   24 rows 3.794 -> 3.959   40 rows 5.911 -> 6.004      slower: out of the rule
+//   32 rows 4.124 -> 4.101 (4 x 8), 4.102 -> 4.066 (2 x 16), 4.230 -> 4.187 (8 x 4)   48 rows 6.232 -> 6.117   64 rows 6.965 -> 6.498 (8 x 8),
+//   6.922 -> 6.457 (4 x 16), 7.144 -> 6.513 (16 x 4)                                                       faster: in
+// (up to 24 rows the caches serve the rows' repeated reads and the second launch boundary costs more than the bytes; 40 rows = 160 span
+// blocks x 2 splits on 256 CUs, a round and a quarter.)  The default rule is those measured shapes and no other: SAMPLE groups of 4 .. 16 rows
+// at 32, 48 or 64 rows.  Beams were measured as one K = 8 group only (3.249 -> 3.505, slower) and N = 2 / 3 not at all: they take the route
+// under attn_group = 1 alone until someone measures them.  run_decode_stage, ensure_graph and emmax_session_attn_grouped all ask here.
+int attn_group_rows(const emmax_session* s, int B) {
+    const int N = s->grp_N > 0 ? s->grp_N : (s->beam.K >= 2 && s->beam.forked) ? s->beam.K : 0;
+    const int sw = emmax_tune().attn_group;
+    if (N < 2 || s->exact || sw == 0 || !attn_direct_on(s, B)) return 0;
+    if (sw < 0 && !(s->grp_N >= 4 && s->grp_N <= 16 && (B == 32 || B == 48 || B == 64))) return 0;
+    return group_attn_takes(B, N, s->m->cfg.n_heads, s->m->cfg.n_kv_heads) ? N : 0;
+}
+
 // what the o-proj of a B-row step reads (emmax_op_decode_stage feeds it): 0 = the bf16 attention rows, 1 = split partials (*nsplit of them per
 // (row, head)), 2 = exact numerics, the fp32 rows the one-split attention launch left over the q rows
 int decode_oproj_form(const emmax_model* m, bool exact, int B, int* nsplit) {
@@ -342,6 +362,7 @@ int launch_beam_finish(emmax_session* s, bool is_prefill, hipStream_t st) {
     g.fin_tok = s->beam.fin_tok; g.grp_state = s->beam.grp;
     g.cur_tok = s->cur_tok; g.ctx_len = s->ctx_len; g.done = s->done; g.n_out = s->n_out; g.max_new_p = s->max_new_d;
     g.page_table = s->page_table; g.spare = s->beam.spare; g.copy_src = s->beam.csrc; g.copy_dst = s->beam.cdst; g.copy_ntok = s->beam.cntok;
+    g.grp_shared = s->grp_shared;
     g.tr_tok = s->beam.tr_tok; g.tr_par = s->beam.tr_par; g.tr_score = s->beam.tr_score; g.tr_lse = s->beam.tr_lse; g.tc_idx = s->beam.tc_idx;
     g.tc_acc = s->beam.tc_acc;
     if (is_prefill)
@@ -399,7 +420,7 @@ int run_group_fork(emmax_session* s, int G, hipStream_t st) {
     memset(&f, 0, sizeof(f));
     f.N = N; f.max_pages = s->max_pages; f.page_table = s->page_table;
     f.ctx_len = s->ctx_len; f.done = s->done; f.n_out = s->n_out; f.max_new = s->max_new_d; f.stop_m = s->stop_m; f.stop_after = s->stop_after;
-    f.copy_src = s->beam.csrc; f.copy_dst = s->beam.cdst; f.copy_ntok = s->beam.cntok;
+    f.copy_src = s->beam.csrc; f.copy_dst = s->beam.cdst; f.copy_ntok = s->beam.cntok; f.grp_shared = s->grp_shared;
     bool partial = false;
     for (int g = 0; g < G; ++g) {
         f.S[g] = s->S[g];
@@ -497,6 +518,11 @@ int run_decode_stage(emmax_session* s, int B, int li, int stage, hipStream_t st)
             KCHK(launch_x_decode_attn(a, B, c.n_heads, c.head_dim, ns, st));
             return 0;
         }
+        if (const int N = attn_group_rows(s, B)) {   // the shared prompt pages once per group, then the rows' tails
+            a.grp_shared = s->grp_shared;
+            KCHK(launch_group_attn(a, B, N, c.n_heads, c.head_dim, st));
+            return 0;
+        }
         KCHK(launch_decode_attn(a, B, c.n_heads, c.head_dim, ns, st));
         return 0;
     }
@@ -567,7 +593,8 @@ int ensure_graph(emmax_session* s, int B, hipStream_t st) {
     // cannot be kept free).
     s->last_step_graph = 0;   // set again by launch_graph_step when a replay really runs
     if (!emmax_tune().graph) return 1;   // eager step: a captured graph stays valid for the next caller that wants replay
-    if (s->graph_exec && s->graph_B == B && s->graph_stream_cap == st && s->graph_epoch == emmax_tune().epoch && s->graph_mode == finish_mode(s))
+    if (s->graph_exec && s->graph_B == B && s->graph_stream_cap == st && s->graph_epoch == emmax_tune().epoch && s->graph_mode == finish_mode(s) &&
+        s->graph_grp == attn_group_rows(s, B))
         return 0;
     drop_graph(s);
     if (s->graph_failed) return 1;
@@ -587,7 +614,7 @@ int ensure_graph(emmax_session* s, int B, hipStream_t st) {
         return graph_fail(s, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
     }
     s->graph = g; s->graph_exec = ge; s->graph_B = B; s->graph_stream_cap = st; s->graph_epoch = emmax_tune().epoch;
-    s->graph_mode = finish_mode(s);
+    s->graph_mode = finish_mode(s); s->graph_grp = attn_group_rows(s, B);
     return 0;
 }
 

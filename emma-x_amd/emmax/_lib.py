@@ -106,6 +106,9 @@ SIGNATURES = {
     "emmax_op_decode_attention_direct": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _vp]),
     "emmax_op_decode_attention_kv8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.c_float, _vp]),
+    "emmax_op_decode_attention_group": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _vp, _vp, _vp]),
+    "emmax_op_decode_attention_group_kv8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                      _vp, C.c_float, _vp]),
     "emmax_op_gemv": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "emmax_op_resize_bicubic_u8": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp]),
     "emmax_op_quant_fm8": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp]),
@@ -145,6 +148,7 @@ SIGNATURES = {
     "emmax_session_set_sample_groups": (C.c_int, [_vp, C.c_int, _vp]),
     "emmax_session_clear_sample_groups": (C.c_int, [_vp, _vp]),
     "emmax_session_sample_groups": (C.c_int, [_vp]),
+    "emmax_session_attn_grouped": (C.c_int, [_vp, C.c_int]),
     "emmax_op_decode_stage": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _c_i32p, _c_i32p, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int),
                                         C.POINTER(C.c_int), C.POINTER(C.c_int), _vp]),
     "emmax_op_decode_route": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),

@@ -463,6 +463,11 @@ class EmmaxEngine:
     def sample_groups(self) -> int:
         return max(int(self.lib.emmax_session_sample_groups(self._session)), 0)
 
+    def attn_grouped(self, rows: int) -> bool:
+        """Whether a decode step of `rows` rows, as the session is configured now, reads each group's shared prompt pages once
+        (sample groups or forked beams; emmax_session_attn_grouped)."""
+        return int(self.lib.emmax_session_attn_grouped(self._session, int(rows))) == 1
+
     @property
     def scores_bound(self) -> bool:
         return self._score_bufs is not None

@@ -95,7 +95,7 @@ int emmax_config_size(void);
  * environment variable EMMAX_<NAME> for each of them ONCE, the first time any value is needed; afterwards only emmax_tuning_set
  * changes them (no launcher reads the environment).  Every default is the product path; the other values are the A/B partners
  * DESIGN.md quotes.  Names: graph (1 = hipGraph replay of the decode step, BASELINE configs[4]), ks, ks_oproj, ks_oproj_grid, km,
- * km_down, km_roll, streamk, fp8_gemv, attn_nsplit, attn_direct, attn_nw, attn_deep, attn_ksplit, attn_lazy, vis_streams, fold_embed, mfma_xbar, gemm_big (2 = the 128 x 256 x 32 lab tile), gemm_splitk, gemm_sk_big,
+ * km_down, km_roll, streamk, fp8_gemv, attn_nsplit, attn_direct, attn_nw, attn_deep, attn_group (-1 = the grouped decode attention at the batches it was measured faster at, 1 = wherever it applies, 0 = never), attn_ksplit, attn_lazy, vis_streams, fold_embed, mfma_xbar, gemm_big (2 = the 128 x 256 x 32 lab tile), gemm_splitk, gemm_sk_big,
  * gemm_hybrid, gemm_normfuse, gemm_deep, gemm_lnfuse, attn_resident, resid32 (1 = fp32 residual stream in prefill and decode, 2 = decode only,
  * 0 = bf16 rows), kv_fp8 (1 = sessions created from now on keep an e4m3 KV cache).
  * Three switches are read when an object is BUILT and frozen in it: gemm_lnfuse at emmax_model_finalize (the LayerNorm fold rewrites the ViT
@@ -430,9 +430,9 @@ int emmax_session_beam_trace(emmax_session* s, int max_new, int32_t* tok_dev, in
  *                format; no copy is made when S % 64 == 0.  Every later page is the row's own.
  * From then on the rows are ordinary decode rows on a non-identity page table: emmax_decode_step, emmax_generate, emmax_last_logits,
  * emmax_set_current_tokens, the log-probabilities, the scores, the stop rule and graph replay behave as for a G x N batch, and a step
- * launches exactly the kernels a G x N sampled batch launches.  Nothing is reordered after the fork: there are no spares and no per-step
+ * launches the kernels a G x N sampled batch launches (but for the attention where emmax_session_attn_grouped says so: below).  Nothing is reordered after the fork: there are no spares and no per-step
  * copies, private pages come out of each row's own static share, so no EMMAX_ERR_NOMEM case exists beyond a plain batch's, and
- * emmax_session_bytes is unchanged.  Every weight format and every cache format is served (the copy goes by planes).
+ * emmax_session_bytes grows by one int32 per decode row (the groups' shared page counts).  Every weight format and every cache format is served (the copy goes by planes).
  *
  *   emmax_session_set_sample_groups    N = n for every prefill from now on.  EMMAX_ERR_INVALID outside 2 .. min(max_batch,
  *                                      emmax_model_max_decode_batch); EMMAX_ERR_STATE while beams are on or request slots are open.
@@ -442,6 +442,16 @@ int emmax_session_beam_trace(emmax_session* s, int max_new, int32_t* tok_dev, in
 int emmax_session_set_sample_groups(emmax_session* s, int n, emmax_stream stream);
 int emmax_session_clear_sample_groups(emmax_session* s, emmax_stream stream);
 int emmax_session_sample_groups(const emmax_session* s);
+/* GROUPED DECODE ATTENTION (new symbols, same ABI).  The rows of a sample group, and the beams of a forked beam group, all reference the
+ * prompt's floor(S / 64) complete pages.  Where the route rule holds, a step's attention reads those pages ONCE per group (split partials
+ * per (row, head)) and a second launch reads each row's own tail, folds the partials in and writes the row the o-proj reads.  The rule:
+ * groups on (sample groups, or beams behind their fork), default numerics, a step whose attention is the one-split direct form (5 rows
+ * and more at 32 kv heads), and the tuning switch attn_group: 1 = at every such step, -1 (the default) = only at the batches where the
+ * two launches were measured faster than the one (sample groups of 4-16 rows at 32, 48 or 64 rows), 0 = never.  Every other step launches what
+ * it launched before.  The page counts
+ * live in device memory, written by the fork: a captured step replays for later prompts of other lengths.
+ *   emmax_session_attn_grouped   1 if a B-row step of the session, as configured now, takes that route, 0 if not, -1 null session. */
+int emmax_session_attn_grouped(const emmax_session* s, int B);
 
 /* ---- single-kernel entry points (parity tests + micro-benchmarks) -------------------------------------------------- */
 /* C[M,N] = epilogue(A[M,K] @ W[N,K]^T): bf16 in, fp32 accumulate on MFMA.  K % 64 == 0, N % 128 == 0.
@@ -506,6 +516,21 @@ int emmax_op_decode_attention_kv8(const void* q_dev, void* kcache8_dev, void* vc
                                   const void* kv_stage_dev, const int32_t* page_table_dev, const int32_t* ctx_len_dev, const int32_t* done_dev,
                                   float* partials_out_dev, void* o_out_dev, int B, int Hq, int Hkv, int page, int max_pages, int nsplit,
                                   float scale, emmax_stream stream);
+/* The grouped form of the one-split attention (emmax_session_attn_grouped), as a pure op: the B rows are B / N groups of N, and the CALLER
+ * GUARANTEES that rows g N .. g N + N - 1 hold identical page-table entries for their first shared_pages_dev[g] pages, all of them complete
+ * (shared_pages[g] * page <= ctx_len of every row of the group).  Launch 1 reads keys [0, shared_pages[g] * page) once per group, launch 2
+ * the keys from there to ctx_len[b] per row; the result is o_out_dev bf16 [B, Hq*128] (rows flagged done: zeros), to the tolerance of
+ * emmax_op_decode_attention_direct.  part_ws_dev: f32 scratch of B * Hq * 8 * 132 elements.  shared_pages_dev: int32 [B / N], read back and
+ * checked, with ctx_len_dev, before anything is launched (the call synchronises the stream).  EMMAX_ERR_INVALID: N < 2, B % N != 0, a
+ * count outside 0 .. max_pages or beyond the context of a row of its group, or a shape the kernels do not take (as the direct form).  _kv8: the same over the fp8 cache, the step's key waiting in
+ * kv_stage as for emmax_op_decode_attention_kv8. */
+int emmax_op_decode_attention_group(const void* q_dev, const void* kcache_dev, const void* vcache_dev, const int32_t* page_table_dev,
+                                    const int32_t* ctx_len_dev, const int32_t* done_dev, void* o_out_dev, int B, int Hq, int Hkv, int page,
+                                    int max_pages, float scale, int N, const int32_t* shared_pages_dev, float* part_ws_dev, emmax_stream stream);
+int emmax_op_decode_attention_group_kv8(const void* q_dev, void* kcache8_dev, void* vcache8_dev, float* kscale_dev, float* vscale_dev,
+                                        const void* kv_stage_dev, const int32_t* page_table_dev, const int32_t* ctx_len_dev,
+                                        const int32_t* done_dev, float* part_ws_dev, void* o_out_dev, int B, int Hq, int Hkv, int page,
+                                        int max_pages, int N, const int32_t* shared_pages_dev, float scale, emmax_stream stream);
 /* Decode-path weight-streaming GEMV: y[b,n] = sum_k x[b,k] W[n,k]  (bf16 in, fp32 accumulate, bf16 out), B <= 8. */
 int emmax_op_gemv(const void* x_dev, const void* W_dev, void* y_dev, int B, int N, int K, emmax_stream stream);
 

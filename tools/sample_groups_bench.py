@@ -12,7 +12,15 @@ the first token, and that the group's rows read the prompt's pages at the same a
   actions_ms      generate_actions_batch end to end: frames + prompts -> actions
 The two variants are measured INTERLEAVED, --rounds times on one box; each figure is the median over the rounds, and `spread` is max - min
 over the rounds of the same variant -- the noise a difference between the variants has to clear.  EOS is disabled (as in bench.py).
-Prints one JSON line per N."""
+Prints one JSON line per N.
+
+--attn-ab POINTS: the grouped decode attention (tuning switch attn_group; include/emmax.h: emmax_session_attn_grouped) against the launch of a
+plain batch, on the same build: attn_group = 0 / 1 ALTERNATE in this process on this box, --rounds times after a warm-up round; each figure is
+the median over the rounds and `spread` is max - min.  attn_group = 0 launches the attention the build before the route launched (the
+route function returns 0 and the step takes the old branch).  POINTS: "GxN" = G prompts of context 256 + --prompt-tokens with N samples
+each (1x8, 2x8, 8x8 = 64 rows), "beamK" = one group of K beams.  Per point and switch value: ms_per_step as above, and attn_us = one
+attention stage (both launches of the grouped route) timed by emmax_profile_decode_stage on the forked session (sample groups only: beams
+fork inside generate).  One JSON line per point."""
 import argparse
 import json
 import os
@@ -37,12 +45,15 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--tiny", action="store_true")
     ap.add_argument("--variants", default="group,expanded", help="one of them alone: a run to put under `rocprofv3 --kernel-trace --stats`")
+    ap.add_argument("--attn-ab", default="", help='operating points of the attn_group A/B, e.g. "1x8,2x8,8x8,beam8" (replaces the group / expanded run)')
     args = ap.parse_args()
     dev = "cuda:0"
     ns = [int(n) for n in args.samples.split(",")]
     cfg = EmmaXConfig.tiny() if args.tiny else EmmaXConfig.emma_x_7b()
     cfg.eos_token_id = -1
     P, T = args.prompt_tokens, args.new_tokens
+    if args.attn_ab:
+        return attn_ab(args, cfg, dev)
     model = EmmaXForActionPrediction.from_synthetic(cfg, seed=0, device=dev, max_batch=max(ns), max_prompt=P, max_ctx=cfg.n_patches + P + T + 1)
     eng = model.engine
     rng = np.random.default_rng(1234)
@@ -88,6 +99,58 @@ def main():
         print(json.dumps(rec), flush=True)
     eng.clear_sample_groups()
     eng.clear_sampling()
+
+
+def attn_ab(args, cfg, dev):
+    from emmax import _lib
+    from emmax.sampling import BeamParams
+
+    P, T = args.prompt_tokens, args.new_tokens
+    points = []
+    for name in args.attn_ab.split(","):
+        points.append((name, 1, int(name[4:]), True) if name.startswith("beam") else (name, int(name.split("x")[0]), int(name.split("x")[1]), False))
+    rows_max = max(g * n for _, g, n, _ in points)
+    model = EmmaXForActionPrediction.from_synthetic(cfg, seed=0, device=dev, max_batch=rows_max, max_prompt=P, max_ctx=cfg.n_patches + P + T + 1)
+    eng = model.engine
+    rng = np.random.default_rng(1234)
+    samp = SamplingParams(1.0, 50, 1.0, seed=1)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0)
+
+    for name, G, N, beam in points:
+        frames = torch.from_numpy(rng.integers(0, 256, size=(G, 224, 224, 3), dtype=np.uint8)).to(dev)
+        prompts = [[1] + [int(x) for x in rng.integers(3, 31744, size=P - 1)] for _ in range(G)]
+        kw = dict(beams=BeamParams(N, 1.0, False, N)) if beam else dict(sampling=samp, num_samples=N)
+        figs = {sw: {"ms_per_step": [], "attn_us": []} for sw in (0, 1)}
+        for rnd in range(args.rounds + 1):   # (round 0 warms up)
+            for sw in (0, 1):
+                with _lib.tuning(attn_group=sw):
+                    us = float("nan")
+                    if not beam:   # (beams fork inside generate and are done behind it: rows flagged done read nothing -- not covered)
+                        model._prefill(prompts, frames_u8=frames, max_new=T, **kw)
+                        us = eng.profile_decode_stage(1, 5)   # the forked rows at the prompt's context; leaves garbage rows: prefill again
+                    model._prefill(prompts, frames_u8=frames, max_new=T, **kw)
+                    out = []
+                    step = timed(lambda: out.append(eng.generate(T, stop_on_eos=False))) / (T - 1)
+                    assert out[0][0].shape[0] == G * N and (sw or not eng.attn_grouped(G * N))
+                    if sw and not eng.attn_grouped(G * N):
+                        raise SystemExit(f"{name}: a step of {G * N} rows does not take the grouped route (fewer than 5 rows at 32 heads?): nothing to compare")
+                if rnd:
+                    figs[sw]["ms_per_step"].append(step)
+                    figs[sw]["attn_us"].append(us)
+        rec = {"point": name, "groups": G, "rows_per_group": N, "context": cfg.n_patches + P, "new_tokens": T, "layers": cfg.llm.num_layers, "rounds": args.rounds}
+        for sw in (0, 1):
+            for k, xs in figs[sw].items():
+                rec[f"attn_group{sw}_{k}"] = round(float(np.median(xs)), 4)
+                rec[f"attn_group{sw}_{k}_spread"] = round(float(max(xs) - min(xs)), 4)
+        print(json.dumps(rec), flush=True)
+        (eng.clear_beams() if beam else eng.clear_sample_groups())
+    eng.clear_sampling() if eng.sampling else None
 
 
 if __name__ == "__main__":
