@@ -2,6 +2,21 @@
 // logits, and slot serving (continuous batching: open, prefill into slots or staging rows, commit, step, state, output, release).
 #include "session.h"
 
+int slots_restore_pages(emmax_session* s, hipStream_t st) {
+    if (s->sg_followers) KCHK(launch_slots_unhide(s->page_table, s->hidden, s->rows_total * s->max_pages, st));
+    s->sg_followers = 0;
+    std::fill(s->sg_gid.begin(), s->sg_gid.end(), -1);
+    std::fill(s->sg_own.begin(), s->sg_own.end(), 0);
+    return 0;
+}
+
+// a slot that a prefill or a commit is about to fill must not be a member of a live group: its table row names pages it does not own
+static int check_not_in_group(const emmax_session* s, int slot, const char* what) {
+    if (s->sg_gid[slot] >= 0)
+        return fail(EMMAX_ERR_STATE, "%s: slot %d still belongs to a sample group (emmax_slot_release it first)", what, slot);
+    return 0;
+}
+
 extern "C" {
 
 int emmax_last_logits(emmax_session* s, float* out, emmax_stream stream) {
@@ -130,9 +145,12 @@ int emmax_slots_open(emmax_session* s, int n_slots, emmax_stream stream) {
         return fail(EMMAX_ERR_STATE, "%d slots decode on the fragment-major weight copies: call emmax_model_build_aux first", n_slots);
     StreamScope sc(s, stream);
     if (sc.error()) return sc.error();
+    if (int r = slots_restore_pages(s, sc.stream())) return r;   // a group still outstanding from the last serve
     KCHK(launch_slots_idle(n_slots, s->cur_tok, s->ctx_len, s->done, s->n_out, s->m->cfg.pad_id, sc.stream()));
     s->cur_B = n_slots;
     s->S.assign(s->rows_total, 0);
+    std::fill(s->slot_fresh.begin(), s->slot_fresh.end(), 0);
+    std::fill(s->slot_stg_idx.begin(), s->slot_stg_idx.end(), -1);
     s->slots_open = true;
     s->scores.on = false;   // no scores in slot serving (the bound buffers were a generate call's)
     s->prefilled = true;   // decode steps are legal: idle slots are rows that are already done
@@ -144,10 +162,13 @@ int emmax_slot_prefill(emmax_session* s, int slot, const int32_t* ids, int len, 
     if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slot_prefill before emmax_slots_open");
     if (slot < 0 || slot >= s->cur_B) return fail(EMMAX_ERR_INVALID, "slot %d outside 0..%d", slot, s->cur_B - 1);
     if (max_new < 1 || max_new > s->max_out) return fail(EMMAX_ERR_INVALID, "max_new_tokens %d outside 1..%d", max_new, s->max_out);
+    if (int r = check_not_in_group(s, slot, "emmax_slot_prefill")) return r;
     StreamScope sc(s, stream);
     if (sc.error()) return sc.error();
+    s->slot_fresh[slot] = 0; s->slot_stg_idx[slot] = -1;
     if (int r = run_prefill(s, ids, &len, 1, len, patches, sc.stream(), slot)) return r;
     KCHK(launch_set_ints(s->max_new_d + slot, 1, max_new, sc.stream()));
+    s->slot_fresh[slot] = s->samp.on ? 1 : 0;   // (sampling on: the prefill left the prompt's logit row in the slot's own)
     return sc.leave();
 }
 
@@ -159,10 +180,14 @@ int emmax_slots_prefill(emmax_session* s, int slot0, int n, const int32_t* ids, 
     for (int i = 0; i < n; ++i)
         if (max_new_host[i] < 1 || max_new_host[i] > s->max_out)
             return fail(EMMAX_ERR_INVALID, "slot %d: max_new_tokens %d outside 1..%d", slot0 + i, max_new_host[i], s->max_out);
+    for (int i = 0; i < n; ++i)
+        if (int r = check_not_in_group(s, slot0 + i, "emmax_slots_prefill")) return r;
     StreamScope sc(s, stream);
     if (sc.error()) return sc.error();
+    for (int i = 0; i < n; ++i) { s->slot_fresh[slot0 + i] = 0; s->slot_stg_idx[slot0 + i] = -1; }
     if (int r = run_prefill(s, ids, lens_host, n, P_max, patches, sc.stream(), slot0)) return r;   // one packed pass over the n requests (ragged lengths)
     for (int i = 0; i < n; ++i) KCHK(launch_set_ints(s->max_new_d + slot0 + i, 1, max_new_host[i], sc.stream()));
+    for (int i = 0; i < n; ++i) s->slot_fresh[slot0 + i] = s->samp.on ? 1 : 0;
     return sc.leave();
 }
 
@@ -179,6 +204,8 @@ int emmax_slots_prefill_staged(emmax_session* s, int n, const int32_t* ids, int 
         if (max_new_host[i] < 1 || max_new_host[i] > s->max_out)
             return fail(EMMAX_ERR_INVALID, "staged request %d: max_new_tokens %d outside 1..%d", i, max_new_host[i], s->max_out);
     hipStream_t st = (hipStream_t)stream;
+    s->stg_epoch += 1;   // the staging rows' logit rows are this batch's from here on
+    s->stg_logits = s->samp.on;
     if (int r = run_prefill(s, ids, lens_host, n, P_max, patches, st, s->stg0)) return r;
     for (int i = 0; i < n; ++i) KCHK(launch_set_ints(s->max_new_d + s->stg0 + i, 1, max_new_host[i], st));
     return 0;
@@ -195,6 +222,7 @@ int emmax_slots_commit(emmax_session* s, const int32_t* staged_idx_host, const i
         if (staged_idx_host[i] < 0 || staged_idx_host[i] >= s->n_stg) return fail(EMMAX_ERR_INVALID, "staged request %d outside 0..%d", staged_idx_host[i], s->n_stg - 1);
         for (int j = 0; j < i; ++j)
             if (slots_host[j] == slots_host[i] || staged_idx_host[j] == staged_idx_host[i]) return fail(EMMAX_ERR_INVALID, "slot / staged request named twice");
+        if (int r = check_not_in_group(s, slots_host[i], "emmax_slots_commit")) return r;
         c.slot[i] = slots_host[i];
         c.src[i] = s->stg0 + staged_idx_host[i];
     }
@@ -212,7 +240,12 @@ int emmax_slots_commit(emmax_session* s, const int32_t* staged_idx_host, const i
     StreamScope sc(s, stream);
     if (sc.error()) return sc.error();
     KCHK(launch_slots_commit(c, sc.stream()));
-    for (int i = 0; i < n; ++i) s->S[slots_host[i]] = s->S[s->stg0 + staged_idx_host[i]];
+    for (int i = 0; i < n; ++i) {
+        const int slot = slots_host[i];
+        s->S[slot] = s->S[s->stg0 + staged_idx_host[i]];
+        s->slot_fresh[slot] = 0;   // (a commit does not move logit rows: the request's stays in its staging row)
+        s->slot_stg_idx[slot] = staged_idx_host[i]; s->slot_stg_epoch[slot] = s->stg_epoch;
+    }
     return sc.leave();
 }
 
@@ -225,6 +258,7 @@ int emmax_slots_step(emmax_session* s, int n_steps, emmax_stream stream) {
     const hipStream_t st = sc.stream();
     const int B = s->cur_B;
     const bool use_graph = ensure_graph(s, B, st) == 0;
+    std::fill(s->slot_fresh.begin(), s->slot_fresh.end(), 0);   // a sampled step overwrites every slot's logit row
     for (int i = 0; i < n_steps; ++i) {
         if (int r = use_graph ? launch_graph_step(s, B, st) : run_decode_step(s, B, st)) return r;
     }
@@ -259,6 +293,83 @@ int emmax_slot_release(emmax_session* s, int slot, emmax_stream stream) {
     if (sc.error()) return sc.error();
     KCHK(launch_slots_idle(1, s->cur_tok + slot, s->ctx_len + slot, s->done + slot, s->n_out + slot, s->m->cfg.pad_id, sc.stream()));
     s->S[slot] = 0;
+    s->slot_fresh[slot] = 0; s->slot_stg_idx[slot] = -1;
+    if (s->sg_gid[slot] >= 0) {   // a member of a group: a follower takes its hidden pages back; the owner takes its heir's and the heir owns the shared ones
+        const int gid = s->sg_gid[slot], nfull = s->sg_nfull[slot], mp = s->max_pages;
+        int from = slot;
+        if (s->sg_own[slot]) {
+            from = -1;
+            for (int h = 0; h < s->cur_B && from < 0; ++h)
+                if (h != slot && s->sg_gid[h] == gid) from = h;   // the heir: the lowest-numbered live follower
+            if (from >= 0) s->sg_own[from] = 1;
+        }
+        if (from >= 0) {
+            if (nfull > 0) KCHK(launch_slots_unhide(s->page_table + (size_t)slot * mp, s->hidden + (size_t)from * mp, nfull, sc.stream()));
+            s->sg_followers -= 1;
+        }
+        s->sg_gid[slot] = -1; s->sg_own[slot] = 0;
+    }
+    return sc.leave();
+}
+
+int emmax_slots_fork(emmax_session* s, int src_slot, int staged_idx, const int32_t* dst_slots_host, int n, const float* temperature_host,
+                     const int32_t* top_k_host, const float* top_p_host, const uint64_t* seed_host, const uint32_t* subseq_host, emmax_stream stream) {
+    if (!s || !dst_slots_host || !temperature_host || !top_k_host || !top_p_host || !seed_host || !subseq_host) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slots_fork before emmax_slots_open");
+    if (n < 1) return fail(EMMAX_ERR_INVALID, "%d followers < 1", n);
+    if (!s->samp.on)
+        return fail(EMMAX_ERR_STATE, "a fork needs sampling: %d greedy rows of one prompt would be identical (emmax_session_set_sampling)", n + 1);
+    if (src_slot < 0 || src_slot >= s->cur_B) return fail(EMMAX_ERR_INVALID, "source slot %d outside 0..%d", src_slot, s->cur_B - 1);
+    if (staged_idx < -1 || staged_idx >= s->n_stg) return fail(EMMAX_ERR_INVALID, "staged request %d outside -1..%d", staged_idx, s->n_stg - 1);
+    for (int i = 0; i < n; ++i) {
+        const int d = dst_slots_host[i];
+        if (d < 0 || d >= s->cur_B) return fail(EMMAX_ERR_INVALID, "destination slot %d outside 0..%d", d, s->cur_B - 1);
+        if (d == src_slot) return fail(EMMAX_ERR_INVALID, "destination slot %d is the source", d);
+        for (int j = 0; j < i; ++j)
+            if (dst_slots_host[j] == d) return fail(EMMAX_ERR_INVALID, "destination slot %d named twice", d);
+        if (s->S[d] != 0 || s->sg_gid[d] >= 0) return fail(EMMAX_ERR_INVALID, "destination slot %d is not idle (emmax_slot_release it first)", d);
+    }
+    if (int r = check_sampling_values(s, dst_slots_host, n, temperature_host, top_k_host, top_p_host)) return r;
+    if (s->S[src_slot] == 0) return fail(EMMAX_ERR_STATE, "source slot %d holds no request", src_slot);
+    if (s->sg_gid[src_slot] >= 0) return fail(EMMAX_ERR_STATE, "source slot %d already belongs to a sample group", src_slot);
+    int logit_row = src_slot;
+    if (staged_idx < 0) {
+        if (s->slot_stg_idx[src_slot] >= 0)
+            return fail(EMMAX_ERR_STATE, "source slot %d was committed from staged request %d: its logit row is that staging row's (pass staged_idx)", src_slot,
+                        s->slot_stg_idx[src_slot]);
+        if (!s->slot_fresh[src_slot])
+            return fail(EMMAX_ERR_STATE, "source slot %d: a decode step ran since its prefill (or it was prefilled with sampling off), the prompt's logit row is gone",
+                        src_slot);
+    } else {
+        if (s->slot_stg_idx[src_slot] != staged_idx || s->slot_stg_epoch[src_slot] != s->stg_epoch)
+            return fail(EMMAX_ERR_STATE, "staged request %d of source slot %d is not of the current staged batch: an older batch's logit row is gone", staged_idx,
+                        src_slot);
+        if (!s->stg_logits) return fail(EMMAX_ERR_STATE, "the staged batch was prefilled with sampling off: it left no logit rows");
+        logit_row = s->stg0 + staged_idx;
+    }
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    if (int r = upload_fork_sampling(s, n, temperature_host, top_k_host, top_p_host, seed_host, subseq_host, sc.stream())) return r;
+    if (int r = run_slots_fork(s, src_slot, logit_row, dst_slots_host, n, sc.stream())) return r;
+    const int gid = s->sg_next++;
+    s->sg_gid[src_slot] = gid; s->sg_own[src_slot] = 1; s->sg_nfull[src_slot] = s->S[src_slot] / PAGE;
+    for (int i = 0; i < n; ++i) {
+        const int d = dst_slots_host[i];
+        s->S[d] = s->S[src_slot];
+        s->sg_gid[d] = gid; s->sg_own[d] = 0; s->sg_nfull[d] = s->S[src_slot] / PAGE;
+        s->slot_fresh[d] = 0; s->slot_stg_idx[d] = -1;
+    }
+    s->sg_followers += n;
+    return sc.leave();
+}
+
+int emmax_slots_page_state(emmax_session* s, int32_t* table_out_dev, int32_t* hidden_out_dev, emmax_stream stream) {
+    if (!s || !table_out_dev || !hidden_out_dev) return fail(EMMAX_ERR_INVALID, "null argument");
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    const size_t bytes = (size_t)s->rows_total * s->max_pages * 4;
+    HIPCHK(hipMemcpyAsync(table_out_dev, s->page_table, bytes, hipMemcpyDeviceToDevice, sc.stream()));
+    HIPCHK(hipMemcpyAsync(hidden_out_dev, s->hidden, bytes, hipMemcpyDeviceToDevice, sc.stream()));
     return sc.leave();
 }
 

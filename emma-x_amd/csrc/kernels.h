@@ -134,6 +134,31 @@ struct CommitParams {
     int max_prompt;
 };
 int launch_slots_commit(const CommitParams& c, hipStream_t stream);
+// emmax_slots_fork: the freshly prefilled slot `src` forked into the n idle slots dst[] (one block per follower).  Follower f hides its own
+// first nfull pages (hidden[f][i] = table[f][i]) and references the source's (table[f][i] = table[src][i]: the slot table is a permutation,
+// nothing here assumes the identity); from the prompt's partial page on it keeps its own pages, and entry j of the copy list names that
+// page's copy (launch_beam_copy consumes it: src = -1 where the prompt ends on a page boundary).  Fresh decode state as
+// emmax_group_fork_kernel leaves it, the source's token budget, the uploaded sampling parameters in_*[j], and with processing on the
+// source's processors and prompt ids
+struct SlotForkParams {
+    int n, rows, src, S, max_pages, max_prompt;
+    int dst[EMMAX_MAX_DECODE_BATCH];
+    int32_t *page_table, *hidden, *ctx_len, *done, *n_out, *max_new, *stop_m, *stop_after, *copy_src, *copy_dst, *copy_ntok;
+    const float *in_t, *in_p;
+    const int32_t* in_k;
+    const uint64_t* in_seed;
+    const uint32_t* in_sub;
+    float *temperature, *top_p;
+    int32_t* top_k;
+    uint64_t* seed;
+    uint32_t* subseq;
+    float* penalty;   // processing on (else all null)
+    int32_t *ngram, *min_new, *hist, *hist_len;
+};
+int launch_slots_fork(const SlotForkParams& p, hipStream_t stream);
+// table[i] = hidden[i], hidden[i] = -1 wherever hidden[i] >= 0, i < n: a released follower takes its own pages back (its two rows), an
+// owner's slot takes its heir's (the owner's table row, the heir's hidden row), and every row at once when slot serving ends
+int launch_slots_unhide(int32_t* table, int32_t* hidden, int n, hipStream_t stream);
 int launch_set_int(int32_t* p, int32_t v, hipStream_t stream);
 int launch_set_ints(int32_t* p, int n, int32_t v, hipStream_t stream);
 int launch_slots_idle(int n, int32_t* cur_tok, int32_t* ctx_len, int32_t* done, int32_t* n_out, int32_t pad_id, hipStream_t stream);

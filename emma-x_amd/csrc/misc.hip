@@ -347,6 +347,42 @@ __global__ __launch_bounds__(256) void emmax_slots_commit_kernel(CommitParams c)
     }
 }
 
+// one block per follower (kernels.h: SlotForkParams)
+__global__ __launch_bounds__(256) void emmax_slots_fork_kernel(SlotForkParams p) {
+    const int j = blockIdx.x, f = p.dst[j], src = p.src, tid = threadIdx.x, mp = p.max_pages;
+    const int nfull = p.S / 64, rem = p.S % 64;
+    int32_t* mine = p.page_table + (size_t)f * mp;
+    const int32_t* theirs = p.page_table + (size_t)src * mp;
+    for (int i = tid; i < nfull && i < mp; i += 256) {
+        p.hidden[(size_t)f * mp + i] = mine[i];
+        mine[i] = theirs[i];
+    }
+    if (p.penalty)
+        for (int k = tid; k < p.max_prompt; k += 256) p.hist[(size_t)f * p.max_prompt + k] = p.hist[(size_t)src * p.max_prompt + k];
+    if (tid == 0) {
+        p.ctx_len[f] = p.S; p.done[f] = 0; p.n_out[f] = 0; p.max_new[f] = p.max_new[src];
+        p.stop_m[f] = 0; p.stop_after[f] = -1;
+        p.temperature[f] = p.in_t[j]; p.top_k[f] = p.in_k[j]; p.top_p[f] = p.in_p[j]; p.seed[f] = p.in_seed[j]; p.subseq[f] = p.in_sub[j];
+        if (p.penalty) {
+            p.penalty[f] = p.penalty[src]; p.ngram[f] = p.ngram[src]; p.min_new[f] = p.min_new[src]; p.hist_len[f] = p.hist_len[src];
+        }
+        const bool cp = rem > 0 && nfull < mp;   // (page nfull is past the shared ones: both rows still hold their own entry there)
+        p.copy_src[j] = cp ? theirs[nfull] : -1;
+        p.copy_dst[j] = cp ? mine[nfull] : -1;
+        p.copy_ntok[j] = rem;
+    }
+}
+
+__global__ void emmax_slots_unhide_kernel(int32_t* table, int32_t* hidden, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t h = hidden[i];
+    if (h >= 0) {
+        table[i] = h;
+        hidden[i] = -1;
+    }
+}
+
 __global__ __launch_bounds__(256) void emmax_hist_fill_kernel(HistParams h) {
     const int b = blockIdx.x, n = h.len[b];
     for (int k = threadIdx.x; k < n; k += 256) h.dst[(size_t)b * h.max_prompt + k] = h.ids[(size_t)b * h.P_max + k];
@@ -366,6 +402,20 @@ int launch_hist_fill(const HistParams& h, hipStream_t stream) {
 int launch_slots_commit(const CommitParams& c, hipStream_t stream) {
     if (c.n < 1 || c.n > EMMAX_MAX_DECODE_BATCH) return -1;
     hipLaunchKernelGGL(emmax_slots_commit_kernel, dim3(c.n), dim3(256), 0, stream, c);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+int launch_slots_fork(const SlotForkParams& p, hipStream_t stream) {
+    if (p.n < 1 || p.n > EMMAX_MAX_DECODE_BATCH || p.rows < 1 || p.src < 0 || p.src >= p.rows || p.max_pages < 1 || p.S < 1 || p.S >= p.max_pages * 64) return -1;
+    for (int j = 0; j < p.n; ++j)
+        if (p.dst[j] < 0 || p.dst[j] >= p.rows || p.dst[j] == p.src) return -1;
+    hipLaunchKernelGGL(emmax_slots_fork_kernel, dim3(p.n), dim3(256), 0, stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+int launch_slots_unhide(int32_t* table, int32_t* hidden, int n, hipStream_t stream) {
+    if (!table || !hidden || n < 1) return -1;
+    hipLaunchKernelGGL(emmax_slots_unhide_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, table, hidden, n);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

@@ -39,18 +39,30 @@ static int check_rows(const emmax_session* s, int row0, int n, bool staged) {
 }
 
 // ---- sampling in the decode step (ABI 7) ------------------------------------------------------------------------------
+int check_sampling_values(const emmax_session* s, const int32_t* rows, int n, const float* T, const int32_t* top_k, const float* top_p) {
+    if (s->m->vocab > EMMAX_SAMPLE_MAX_V) return fail(EMMAX_ERR_INVALID, "sampling takes vocabularies of up to %d entries (%d)", EMMAX_SAMPLE_MAX_V, s->m->vocab);
+    for (int i = 0; i < n; ++i) {
+        if (!std::isfinite(T[i]) || T[i] < 0.f) return fail(EMMAX_ERR_INVALID, "row %d: temperature %g (finite and >= 0)", rows[i], (double)T[i]);
+        if (top_k[i] < 0) return fail(EMMAX_ERR_INVALID, "row %d: top_k %d (>= 0)", rows[i], top_k[i]);
+        if (!(top_p[i] > 0.f && top_p[i] <= 1.f)) return fail(EMMAX_ERR_INVALID, "row %d: top_p %g (0 < top_p <= 1)", rows[i], (double)top_p[i]);
+    }
+    return 0;
+}
+
+int upload_fork_sampling(emmax_session* s, int n, const float* T, const int32_t* top_k, const float* top_p, const uint64_t* seed, const uint32_t* subseq,
+                         hipStream_t st) {
+    return upload_rows(s, 0, n, st, {{s->fork_t, T, 4}, {s->fork_k, top_k, 4}, {s->fork_p, top_p, 4}, {s->fork_sub, subseq, 4}, {s->fork_seed, seed, 8}});
+}
+
 static int set_sampling_rows(emmax_session* s, int row0, int n, bool staged, const float* T, const int32_t* top_k, const float* top_p, const uint64_t* seed,
                              const uint32_t* subseq, emmax_stream stream) {
     if (!s || !T || !top_k || !top_p || !seed || !subseq) return fail(EMMAX_ERR_INVALID, "null argument");
     if (int r = check_rows(s, row0, n, staged)) return r;
     if (!staged && s->beam.K) return fail(EMMAX_ERR_STATE, "sampling is not available while beams are on");
     const int r0 = staged ? s->stg0 : row0;
-    if (s->m->vocab > EMMAX_SAMPLE_MAX_V) return fail(EMMAX_ERR_INVALID, "sampling takes vocabularies of up to %d entries (%d)", EMMAX_SAMPLE_MAX_V, s->m->vocab);
-    for (int i = 0; i < n; ++i) {
-        if (!std::isfinite(T[i]) || T[i] < 0.f) return fail(EMMAX_ERR_INVALID, "row %d: temperature %g (finite and >= 0)", r0 + i, (double)T[i]);
-        if (top_k[i] < 0) return fail(EMMAX_ERR_INVALID, "row %d: top_k %d (>= 0)", r0 + i, top_k[i]);
-        if (!(top_p[i] > 0.f && top_p[i] <= 1.f)) return fail(EMMAX_ERR_INVALID, "row %d: top_p %g (0 < top_p <= 1)", r0 + i, (double)top_p[i]);
-    }
+    std::vector<int32_t> rows(n);
+    for (int i = 0; i < n; ++i) rows[i] = r0 + i;
+    if (int r = check_sampling_values(s, rows.data(), n, T, top_k, top_p)) return r;
     StreamScope sc(s, stream);
     if (sc.error()) return sc.error();
     if (int r = upload_rows(s, r0, n, sc.stream(), {{s->samp.t, T, 4}, {s->samp.k, top_k, 4}, {s->samp.p, top_p, 4}, {s->samp.sub, subseq, 4}, {s->samp.seed, seed, 8}})) return r;
@@ -185,6 +197,7 @@ int emmax_session_set_beams(emmax_session* s, int num_beams, double length_penal
     if (s->scores.on && s->scores.has_scores) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while a scores buffer is bound");
     StreamScope sc(s, stream);
     if (sc.error()) return sc.error();
+    if (int r = slots_restore_pages(s, sc.stream())) return r;
     std::vector<float> pw((size_t)s->max_out + 1);
     for (size_t n = 0; n < pw.size(); ++n) pw[n] = (float)pow((double)n, length_penalty);
     HIPCHK(hipStreamSynchronize(sc.stream()));
@@ -224,12 +237,18 @@ int emmax_session_beam_result(emmax_session* s, int max_new, int32_t* seq_dev, i
 }
 
 // ---- sample groups: N sampled rows per prefilled prompt (additions to ABI 11) ----------------------------------------------
-int emmax_session_set_sample_groups(emmax_session* s, int n, emmax_stream) {
+int emmax_session_set_sample_groups(emmax_session* s, int n, emmax_stream stream) {
     if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
     const int max_rows = std::min(s->max_batch, session_max_rows(s));
     if (n < 2 || n > max_rows) return fail(EMMAX_ERR_INVALID, "%d samples per group outside 2..min(max_batch=%d, the model's decode batch)=%d", n, s->max_batch, max_rows);
     if (s->beam.K) return fail(EMMAX_ERR_STATE, "sample groups cannot be turned on while beams are on (emmax_session_clear_beams)");
     if (s->slots_open) return fail(EMMAX_ERR_STATE, "sample groups cannot be turned on while request slots are open");
+    if (s->sg_followers) {
+        StreamScope sc(s, stream);
+        if (sc.error()) return sc.error();
+        if (int r = slots_restore_pages(s, sc.stream())) return r;
+        if (int r = sc.leave()) return r;
+    }
     s->grp_N = n;
     s->prefilled = false;   // rows of an earlier batch do not continue as groups
     return 0;

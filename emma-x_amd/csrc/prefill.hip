@@ -61,6 +61,8 @@ int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B
     const int np = patches ? m->tw[0].n_patches : 0;
     const bool slot_mode = slot0 >= 0;
     const int r0 = slot_mode ? slot0 : 0;
+    if (!slot_mode)   // a plain prefill ends slot serving: the pages that followers of a group hide go back into their rows first
+        if (int r = slots_restore_pages(s, st)) return r;
     if (s->beam.K) {   // beams on: B groups, one prefilled row each, forked into B x K rows by emmax_generate
         if (slot_mode) return fail(EMMAX_ERR_STATE, "request slots are not served while beams are on");
         const int rows = B * s->beam.K;

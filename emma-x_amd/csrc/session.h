@@ -198,6 +198,21 @@ struct emmax_session {
     // complete prompt pages the rows of group g share, int32 [groups]: written by the fork (sample groups: run_group_fork; beams: the prefill
     // form of the beam merge), read by the grouped decode attention (step.hip: attn_group_rows)
     int32_t* grp_shared = nullptr;
+    // GROUPS IN SLOT SERVING (emmax_slots_fork; generate.hip): a prefilled slot forked into idle slots that read its complete prompt pages.
+    // hidden: the pages a follower's table row does not name while it names the owner's, int32 [rows_total][max_pages], -1 = none -- table
+    // entries that are a row's own plus hidden entries are a permutation of all page ids at every moment.  fork_*: the upload columns of a
+    // fork's sampling parameters (one entry per follower; the fork kernel hands them to the followers' rows)
+    int32_t* hidden = nullptr;
+    float *fork_t = nullptr, *fork_p = nullptr;
+    int32_t* fork_k = nullptr;
+    uint64_t* fork_seed = nullptr;
+    uint32_t* fork_sub = nullptr;
+    // ... host side, per slot: the group it belongs to (-1: none), whether it owns the group's shared pages, how many those are; whether its
+    // own logit row is still its prompt's (prefilled in place with sampling on, no step since), and the staged request it was committed from
+    std::vector<int> sg_gid, sg_own, sg_nfull, slot_fresh, slot_stg_idx, slot_stg_epoch;
+    int sg_next = 0, sg_followers = 0 /* rows that hide pages now */;
+    int stg_epoch = 0;          // staged batches so far: a staging row's logit row is its request's until the next emmax_slots_prefill_staged
+    bool stg_logits = false;    // ... and was written at all (sampling was on at that staged prefill)
     int32_t *part_idx2;
     int32_t *part_idx, *cur_tok, *ctx_len, *done, *n_out, *out_ids, *max_new_d /* [max_batch] */, *page_table;
     // EXACT NUMERICS (round 6; tuning switch `exact` at emmax_session_create): fp32 activations end to end.  x32a: the fp32 result of the GEMM
@@ -302,6 +317,13 @@ private:
     int err_;
 };
 
+// modes.hip: the checks of emmax_session_set_sampling on n host values (rows: the row each is for, named in the message), and the upload
+// of a fork's parameters into the session's fork_* columns
+int check_sampling_values(const emmax_session* s, const int32_t* rows, int n, const float* T, const int32_t* top_k, const float* top_p);
+int upload_fork_sampling(emmax_session* s, int n, const float* T, const int32_t* top_k, const float* top_p, const uint64_t* seed, const uint32_t* subseq,
+                         hipStream_t st);
+// generate.hip: every hidden page back into its row's table (a permutation again), no slot in a group; what ends or restarts slot serving calls it
+int slots_restore_pages(emmax_session* s, hipStream_t st);
 // vision.hip: GEMM parameters -- plain; of a session stage (with the session's split-K scratch); of an exact-numerics stage (HL rows in, fp32 out)
 GemmParams gp(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K);
 GemmParams gps(emmax_session* s, const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K);
@@ -318,6 +340,7 @@ int stage_chunk(int stage, bool exact);                            // rows per l
 bool beam_pages_fit(const emmax_session* s, int S, int max_new);
 int launch_beam_finish(emmax_session* s, bool is_prefill, hipStream_t st);
 int run_group_fork(emmax_session* s, int G, hipStream_t st);
+int run_slots_fork(emmax_session* s, int src, int logit_row, const int32_t* dst, int n, hipStream_t st);   // the device side of emmax_slots_fork
 int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* logits_out, bool do_finish, hipStream_t st, int slot0 = 0);
 int run_decode_stage(emmax_session* s, int B, int li, int stage, hipStream_t st);
 int decode_oproj_form(const emmax_model* m, bool exact, int B, int* nsplit);

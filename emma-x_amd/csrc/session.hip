@@ -120,6 +120,15 @@ static void plan_session(emmax_session* s, Bump& b) {
         s->beam.res_len = (int32_t*)b.bytes(Rb * 4);
         s->beam.res_score = (float*)b.bytes(Rb * 4);
     }
+    {   // groups in slot serving: the hidden-page rows, and a fork's parameter upload (followers are decode rows)
+        const int64_t Rb = std::min(Bd, EMMAX_MAX_DECODE_BATCH);
+        s->hidden = (int32_t*)b.bytes((int64_t)Br * s->max_pages * 4);
+        s->fork_t = (float*)b.bytes(Rb * 4);
+        s->fork_p = (float*)b.bytes(Rb * 4);
+        s->fork_k = (int32_t*)b.bytes(Rb * 4);
+        s->fork_seed = (uint64_t*)b.bytes(Rb * 8);
+        s->fork_sub = (uint32_t*)b.bytes(Rb * 4);
+    }
     s->op_rows = std::min(Bd, EMMAX_MAX_DECODE_BATCH);
     s->op_state = (int32_t*)b.bytes((int64_t)s->op_rows * 8 * 4);
     s->op_out = (int32_t*)b.bytes((int64_t)s->op_rows * s->max_out * 4);
@@ -236,12 +245,15 @@ int emmax_session_create_ex(emmax_model* m, int max_batch, int max_prompt, int m
     s->exact = emmax_tune().exact != 0;
     Bump b{(char*)ws};
     plan_session(s, b);
+    s->sg_gid.assign(s->rows_total, -1); s->sg_own.assign(s->rows_total, 0); s->sg_nfull.assign(s->rows_total, 0);
+    s->slot_fresh.assign(s->rows_total, 0); s->slot_stg_idx.assign(s->rows_total, -1); s->slot_stg_epoch.assign(s->rows_total, -1);
     s->kv = (bf16*)kv;
     s->kv8 = !s->exact && emmax_tune().kv_fp8 != 0;
     s->kv_fmt = kv_format_now();
     s->kv_layer_stride = kv_layer_bytes(m, s->rows_total, s->max_pages, s->kv_fmt);
     s->kv24 = s->kv_fmt == KV_X24 ? (long long)kv_rows_per_layer(m, s->rows_total, s->max_pages) * m->cfg.head_dim : 0;
     HIPCHK(hipMemset(ws, 0, need_ws));   // padding columns of every activation buffer stay zero forever
+    HIPCHK(hipMemset(s->hidden, 0xff, (size_t)s->rows_total * s->max_pages * 4));   // no row hides a page
     HIPCHK(hipMemset(kv, 0, need_kv));
     HIPCHK(hipDeviceSynchronize());
     if (decode_gemv_init() != 0) return fail(EMMAX_ERR_HIP, "could not raise the dynamic LDS limit of the GEMV kernels");

@@ -441,6 +441,29 @@ int run_group_fork(emmax_session* s, int G, hipStream_t st) {
     return 0;
 }
 
+// The device side of emmax_slots_fork (include/emmax.h): the fork of slot `src` into the n idle slots dst[] -- page-table rows, hidden pages,
+// per-row state and parameters in one launch, the copies of the prompt's partial page, then token 0 of every follower by the finish a one-row
+// prefill ends in, reading the prompt's logit row where the source's prefill left it (row `logit_row`: the finishes take it as const)
+int run_slots_fork(emmax_session* s, int src, int logit_row, const int32_t* dst, int n, hipStream_t st) {
+    SlotForkParams f;
+    memset(&f, 0, sizeof(f));
+    f.n = n; f.rows = s->cur_B; f.src = src; f.S = s->S[src]; f.max_pages = s->max_pages; f.max_prompt = s->max_prompt;
+    for (int j = 0; j < n; ++j) f.dst[j] = dst[j];
+    f.page_table = s->page_table; f.hidden = s->hidden;
+    f.ctx_len = s->ctx_len; f.done = s->done; f.n_out = s->n_out; f.max_new = s->max_new_d; f.stop_m = s->stop_m; f.stop_after = s->stop_after;
+    f.copy_src = s->beam.csrc; f.copy_dst = s->beam.cdst; f.copy_ntok = s->beam.cntok;
+    f.in_t = s->fork_t; f.in_p = s->fork_p; f.in_k = s->fork_k; f.in_seed = s->fork_seed; f.in_sub = s->fork_sub;
+    f.temperature = s->samp.t; f.top_p = s->samp.p; f.top_k = s->samp.k; f.seed = s->samp.seed; f.subseq = s->samp.sub;
+    if (s->proc.on) { f.penalty = s->proc.pen; f.ngram = s->proc.ng; f.min_new = s->proc.mn; f.hist = s->proc.hist; f.hist_len = s->proc.hist_len; }
+    KCHK(launch_slots_fork(f, st));
+    if (f.S % PAGE != 0)   // (else the prompt ends on a page boundary: every page is shared by reference, nothing to copy)
+        if (int r = launch_page_copies(s, n, st)) return r;
+    const float* lg = s->logits + (size_t)logit_row * s->m->vocab;
+    for (int j = 0; j < n; ++j)
+        if (int r = s->proc.on ? launch_proc_finish_step(s, 1, true, dst[j], lg, st) : launch_sampled_finish_step(s, 1, true, dst[j], lg, st)) return r;
+    return 0;
+}
+
 // slot0: first row of the B rows this call covers (slot prefill: one row in the middle of a live batch)
 int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* logits_out, bool do_finish, hipStream_t st, int slot0) {
     emmax_model* m = s->m;

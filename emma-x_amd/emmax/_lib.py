@@ -91,6 +91,8 @@ SIGNATURES = {
     "emmax_slots_state": (C.c_int, [_vp, _vp, _vp, _vp]),
     "emmax_slot_output": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp]),
     "emmax_slot_release": (C.c_int, [_vp, C.c_int, _vp]),
+    "emmax_slots_fork": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "emmax_slots_page_state": (C.c_int, [_vp, _vp, _vp, _vp]),
     "emmax_op_gemm": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp,
                                 C.c_int, C.c_int, _vp]),
     "emmax_op_gemm_splitk": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp,

@@ -561,6 +561,30 @@ class EmmaxEngine:
         if staged.committed >= staged.n:
             staged.keep = None
 
+    # ---- sample groups as request slots (include/emmax.h: emmax_slots_fork) ---------------------------------------------------
+    def slots_fork(self, src_slot: int, dst_slots: Sequence[int], params, seeds, subseqs, staged: Optional[int] = None) -> None:
+        """Fork the freshly prefilled `src_slot` into the idle `dst_slots` on the current (decode) stream: they read its complete prompt
+        pages and each draws its own token 0 from the prompt's logit row with its (params, seed, subseq).  `staged`: the index of the
+        staged request the source was committed from (slots_commit), None for a source prefilled in place."""
+        k, T, tk, tp, sd, sb = self._sampling_arrays(params, seeds, subseqs, len(dst_slots))
+        if k != len(dst_slots):
+            raise ValueError("slots_fork: one set of sampling parameters per destination slot")
+        dst = (C.c_int32 * max(1, k))(*[int(v) for v in dst_slots])
+        _lib.check(self.lib.emmax_slots_fork(self._session, int(src_slot), -1 if staged is None else int(staged), dst, k, T, tk, tp, sd, sb,
+                                             _lib.current_stream()), "emmax_slots_fork")
+        if staged is not None:   # the fork read the staging row's logits: the next staged prefill waits for it as it waits for the commit
+            self._commit_event = torch.cuda.Event()
+            self._commit_event.record(torch.cuda.current_stream())
+
+    def slots_page_state(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(page table, hidden pages) of every row, staging rows included: int32 [rows, max_pages] on the host; hidden is -1 where a row
+        hides no page (tests: emmax_slots_page_state)."""
+        rows, pages = self.max_batch + self.stage_rows, (self.max_ctx + 63) // 64   # (session.h: PAGE = 64 tokens)
+        out = torch.empty(2, rows, pages, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.emmax_slots_page_state(self._session, out[0].data_ptr(), out[1].data_ptr(), _lib.current_stream()), "emmax_slots_page_state")
+        host = out.cpu()
+        return host[0], host[1]
+
     def slots_step(self, n_steps: int) -> None:
         _lib.check(self.lib.emmax_slots_step(self._session, int(n_steps), _lib.current_stream()), "emmax_slots_step")
 

@@ -30,6 +30,8 @@ class Request:
     sampling: Any = None   # emmax.sampling.SamplingParams: drawn in the decode step with the request's seed (None: draw_seed()) and subseq 0; None = greedy
     processing: Any = None   # emmax.sampling.LogitsProcessing: HF's repetition penalty / n-gram ban / min-new-tokens in the decode step; None = off
     beams: Any = None        # beam groups are not served as slots: a request with emmax.sampling.BeamParams is refused at submit
+    num_samples: int = 1     # > 1: a sample group -- one prefill, forked into num_samples slots that read the prompt's KV pages; sample j draws
+                             # with (the request's seed, subseq j), so sample 0 is what the request returns with num_samples = 1.  Needs sampling
 
 
 @dataclass
@@ -41,6 +43,7 @@ class Result:
     t_admit: float
     t_done: float
     logprobs: Optional[List[float]] = None   # sampled requests: the log-probability of every emitted token
+    sample: int = 0   # which sample of its request this is (Request.num_samples > 1: one Result per sample)
 
     @property
     def latency_s(self) -> float:
@@ -52,6 +55,7 @@ class _Active:
     req: Request
     t_submit: float
     t_admit: float
+    sample: int = 0
 
 
 MAX_SLOTS = 64   # EMMAX_MAX_DECODE_BATCH (emma-x_amd/csrc/kernels.h): rows of a decode step
@@ -61,7 +65,7 @@ class SlotScheduler:
     """Greedy slot scheduler.
 
     engine   object with slots_open / slot_prefill / slots_step / slots_state / slot_output / slot_release / set_stop
-             (emmax.engine.EmmaxEngine, or a fake in the CPU tests)
+             (emmax.engine.EmmaxEngine, or a fake in the CPU tests); slots_fork as well once a request asks for num_samples > 1
     encode   frames (list) -> patch embeddings, one [n_patches, hidden] bf16 tensor per frame; called once per admission
              round with every frame admitted in that round, so the ViT runs batched
     n_slots  decode batch (<= 64; the engine's max_decode_batch())
@@ -122,6 +126,13 @@ class SlotScheduler:
         if getattr(req, "beams", None) is not None:
             raise NotImplementedError("beam search is not served as request slots: a beam group is num_beams rows that reorder together -- "
                                       "use model.generate(num_beams=...) / generate_ids(beams=...)")
+        n = getattr(req, "num_samples", 1)
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"num_samples must be an integer >= 1, got {n!r}")
+        if n > self.n_slots:
+            raise ValueError(f"num_samples {n} exceeds the scheduler's {self.n_slots} slots: a group's samples are admitted together")
+        if n > 1 and (req.sampling is None or float(req.sampling.temperature) == 0.0):
+            raise ValueError(f"num_samples {n} needs sampling: {n} greedy samples of one prompt would be identical (set Request.sampling with a temperature > 0)")
         self.queue.append((req, self.clock()))
 
     def _sampling_rows(self, reqs):
@@ -161,20 +172,44 @@ class SlotScheduler:
         else:
             self.engine.set_sampling(params, seeds, subs, row0=row0)
 
+    @staticmethod
+    def _demand(req) -> int:
+        return getattr(req, "num_samples", 1)
+
+    def _fit(self, reqs, free: List[int]) -> List[List[int]]:
+        """Strict FIFO: the slots of the requests of `reqs` that fit the `free` slots, in order -- request k takes the next num_samples
+        free slots (a group needs all its slots at once; nothing overtakes a head that does not fit)."""
+        mine, used = [], 0
+        for r in reqs:
+            if used + self._demand(r) > len(free):
+                break
+            mine.append(free[used:used + self._demand(r)])
+            used += self._demand(r)
+        return mine
+
+    def _fork(self, req, slots, t_sub, t_adm, staged=None) -> None:
+        """The samples 1.. of a group whose sample 0 was just prefilled into (or committed to) slots[0]: one fork into slots[1:]."""
+        p = req.sampling   # (its seed is set: _set_sampling ran before the prefill)
+        n = len(slots) - 1
+        self.engine.slots_fork(slots[0], slots[1:], [p] * n, [p.seed] * n, list(range(1, n + 1)), staged=staged)
+        for j, slot in enumerate(slots[1:], start=1):
+            self.active[slot] = _Active(req, t_sub, t_adm, j)
+
     def _admit(self) -> int:
         free = [s for s in range(self.n_slots) if s not in self.active]
-        take = min(len(free), len(self.queue))
+        mine = self._fit((r for r, _ in self.queue), free)   # sample 0 is prefilled into a request's first slot, the others are forked from it
+        take = len(mine)
         if take == 0:
             return 0
         batch = [self.queue.popleft() for _ in range(take)]
         embeds = self._encode_for(batch)
         # runs of CONSECUTIVE free slots are prefilled in one packed pass (eight one-row prefills cost ~1.6x one eight-row pass);
         # engines without `slots_prefill` (test doubles) get the requests one by one
-        slots = free[:take]
+        slots = [m[0] for m in mine]
         i = 0
         while i < take:
             j = i + 1
-            while j < take and slots[j] == slots[j - 1] + 1:
+            while j < take and slots[j] == slots[j - 1] + 1 and len(mine[i]) == 1 and len(mine[j]) == 1:
                 j += 1
             if j - i > 1 and hasattr(self.engine, "slots_prefill"):
                 self._set_processing([batch[k][0] for k in range(i, j)], row0=slots[i])
@@ -186,6 +221,8 @@ class SlotScheduler:
                     self._set_processing([batch[k][0]], row0=slots[k])
                     self._set_sampling([batch[k][0]], row0=slots[k])
                     self.engine.slot_prefill(slots[k], list(batch[k][0].prompt_ids), embeds[k], batch[k][0].max_new_tokens)
+                    if len(mine[k]) > 1:   # before any decode step: the fork draws from the logit row this prefill left
+                        self._fork(batch[k][0], mine[k], batch[k][1], self.clock())
             t_adm = self.clock()
             for k in range(i, j):
                 self.active[slots[k]] = _Active(batch[k][0], batch[k][1], t_adm)
@@ -235,22 +272,28 @@ class SlotScheduler:
         if self._pending is None:
             return 0
         staged, batch, k0 = self._pending
-        slots = [s for s in range(self.n_slots) if s not in self.active][: len(batch) - k0]
-        if not slots:
+        free = [s for s in range(self.n_slots) if s not in self.active]
+        # the longest in-order prefix of what is still staged whose slots are free now (a group is one staged row and num_samples slots)
+        mine = self._fit((r for r, _ in batch[k0:]), free)
+        take = len(mine)
+        if take == 0:
             return 0
+        slots = [m[0] for m in mine]
         if not staged.ready():
             if not wait:
                 return 0
             staged.wait()
-        self.engine.slots_commit(staged, slots, list(range(k0, k0 + len(slots))))
+        self.engine.slots_commit(staged, slots, list(range(k0, k0 + take)))
         t_adm = self.clock()
-        for slot, (req, t_sub) in zip(slots, batch[k0:k0 + len(slots)]):
-            self.active[slot] = _Active(req, t_sub, t_adm)
-        self._pending[2] = k0 + len(slots)
+        for k, (m, (req, t_sub)) in enumerate(zip(mine, batch[k0:k0 + take])):
+            self.active[m[0]] = _Active(req, t_sub, t_adm)
+            if len(m) > 1:   # (the staging row keeps the prompt's logit row until the next staged prefill, which _start_admission issues later)
+                self._fork(req, m, t_sub, t_adm, staged=k0 + k)
+        self._pending[2] = k0 + take
         if self._pending[2] >= len(batch):
             self._pending = None
         self.overlapped_admissions += 1
-        return len(slots)
+        return sum(len(m) for m in mine)
 
     def _retire(self) -> int:
         done, n_out = self.engine.slots_state()
@@ -262,7 +305,7 @@ class SlotScheduler:
                 ids = self.engine.slot_output(slot, int(n_out[slot]))
                 lps = self.engine.slot_logprobs(slot, int(n_out[slot])) if a.req.sampling is not None else None
                 self.engine.slot_release(slot)
-                self.results.append(Result(a.req.rid, ids, slot, a.t_submit, a.t_admit, self.clock(), lps))
+                self.results.append(Result(a.req.rid, ids, slot, a.t_submit, a.t_admit, self.clock(), lps, a.sample))
                 n += 1
         return n
 

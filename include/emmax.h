@@ -453,6 +453,39 @@ int emmax_session_sample_groups(const emmax_session* s);
  *   emmax_session_attn_grouped   1 if a B-row step of the session, as configured now, takes that route, 0 if not, -1 null session. */
 int emmax_session_attn_grouped(const emmax_session* s, int B);
 
+/* ---- sample groups as request slots: one prefill, N sampled slots (new symbols, same ABI) ------------------------------------
+ * Slot serving with sampling on (emmax_session_set_sample_groups stays off: the two refusals above are unchanged).  A freshly prefilled
+ * slot is FORKED into idle slots between two decode steps, on the decode stream: the followers read the source's floor(S / 64) complete
+ * prompt pages through their page-table rows, get a copy of the prompt's partial page (none when S % 64 == 0) and own every later page;
+ * each draws its token 0 from the prompt's logit row with the parameters passed here -- the finish of a one-row prefill, so follower j's
+ * first token and log-probability are emmax_op_sample of that row with (seed, subseq, step 0).  No logits are copied and no other K/V moves.
+ *   source       holds a request whose token 0 is in place, prefilled with sampling on: in place (emmax_slot_prefill / emmax_slots_prefill;
+ *                staged_idx = -1) with no decode step since, or committed from request staged_idx of the CURRENT staged batch (the logit
+ *                row read is that staging row's, which emmax_slots_commit does not move and the next emmax_slots_prefill_staged
+ *                overwrites).
+ *   followers    n >= 1 idle slots (released, or never filled), none named twice, none the source.  Each gets ctx_len = S, the source's token
+ *                budget, a fresh stop-rule state, the source's processors and prompt ids when processing is on, and the sampling
+ *                parameters of the host arrays (n values each, checked as emmax_session_set_sampling checks them).
+ *   pages        the slot page table is a permutation (commits swap rows).  A follower's own first floor(S / 64) pages wait in its row of the
+ *                session's HIDDEN pages; at every moment the entries a row owns (its table row, but for a follower's shared entries) plus
+ *                the hidden entries are a permutation of all page ids, and no slot outside a group references the group's pages.
+ *   release      emmax_slot_release as before, one slot at a time.  A follower takes its hidden pages back.  The owner of the shared pages
+ *                (the source, later its heirs) takes the hidden pages of the lowest-numbered live follower, which owns the shared pages
+ *                from then on and hides nothing; the other followers are untouched.  The last member leaves nothing hidden.
+ *                emmax_slots_open, a plain emmax_prefill*, emmax_session_set_beams and emmax_session_set_sample_groups first give
+ *                every hidden page back.
+ * EMMAX_ERR_STATE (nothing launched): slots not open; sampling off (N greedy rows of one prompt are identical); a decode step ran since
+ * an in-place source's prefill; staged_idx is not the request of the current staged batch the source was committed from; the source
+ * already belongs to a group; and emmax_slot_prefill / emmax_slots_prefill / emmax_slots_commit into a slot that still belongs to a group.
+ * EMMAX_ERR_INVALID: null pointers, n < 1, a slot out of range, a follower named twice / equal to the source / not idle, bad sampling values.
+ * Not here: the grouped decode attention (groups in slots are ragged and change at every poll; the one-launch attention reads the shared
+ * pages through the table), scores, beams as slots.  emmax_session_bytes grows by one int32 per row and page (the hidden pages).
+ *   emmax_slots_page_state   test read-back: the page table and the hidden pages, device int32 [max_batch + stage rows][max pages] each
+ *                            (hidden: -1 where a row hides no page). */
+int emmax_slots_fork(emmax_session* s, int src_slot, int staged_idx, const int32_t* dst_slots_host, int n, const float* temperature_host,
+                     const int32_t* top_k_host, const float* top_p_host, const uint64_t* seed_host, const uint32_t* subseq_host, emmax_stream stream);
+int emmax_slots_page_state(emmax_session* s, int32_t* table_out_dev, int32_t* hidden_out_dev, emmax_stream stream);
+
 /* ---- single-kernel entry points (parity tests + micro-benchmarks) -------------------------------------------------- */
 /* C[M,N] = epilogue(A[M,K] @ W[N,K]^T): bf16 in, fp32 accumulate on MFMA.  K % 64 == 0, N % 128 == 0.
  * bias/scale: bf16 [N] or NULL; residual: bf16 [M,ldr] or NULL; act: 0 none, 1 exact-erf GELU, 2 SwiGLU over
