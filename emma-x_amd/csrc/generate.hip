@@ -237,6 +237,8 @@ int emmax_slots_commit(emmax_session* s, const int32_t* staged_idx_host, const i
         c.penalty = s->proc.pen; c.ngram = s->proc.ng; c.min_new = s->proc.mn; c.hist = s->proc.hist; c.hist_len = s->proc.hist_len;
         c.max_prompt = s->max_prompt;
     }
+    if (s->warp.on) { c.warp[0] = s->warp.minp; c.warp[1] = s->warp.typ; c.warp[2] = s->warp.eps; c.warp[3] = s->warp.eta; }
+    if (s->rules.on) c.rule_en = s->rules.en;
     StreamScope sc(s, stream);
     if (sc.error()) return sc.error();
     KCHK(launch_slots_commit(c, sc.stream()));

@@ -132,6 +132,9 @@ struct CommitParams {
     float* penalty;
     int32_t *ngram, *min_new, *hist, *hist_len;
     int max_prompt;
+    // warpers / token rules on (else null): the rows' four warper values and their rule enable word move too
+    float* warp[4];
+    uint32_t* rule_en;
 };
 int launch_slots_commit(const CommitParams& c, hipStream_t stream);
 // emmax_slots_fork: the freshly prefilled slot `src` forked into the n idle slots dst[] (one block per follower).  Follower f hides its own
@@ -154,6 +157,8 @@ struct SlotForkParams {
     uint32_t* subseq;
     float* penalty;   // processing on (else all null)
     int32_t *ngram, *min_new, *hist, *hist_len;
+    float* warp[4];   // warpers / token rules on (else null): a follower takes the source's
+    uint32_t* rule_en;
 };
 int launch_slots_fork(const SlotForkParams& p, hipStream_t stream);
 // table[i] = hidden[i], hidden[i] = -1 wherever hidden[i] >= 0, i < n: a released follower takes its own pages back (its two rows), an
@@ -483,6 +488,31 @@ struct ProcFinishParams : SampleFinishParams {
     const uint64_t* score_words;   // null: no scores.  Else device words {scores f32*, logits f32*, max_new, rows}: buffers [max_new][rows][V]
 };
 int launch_proc_finish(const ProcFinishParams& p, hipStream_t stream);
+// the EXT form of that finish (include/emmax.h: emmax_session_set_warpers / emmax_session_set_token_rules; emmax_op_sample_ext): the token
+// rules join the processors (biases before the repetition penalty, bans with the n-gram ban) and min_p / typical_p / epsilon_cutoff /
+// eta_cutoff follow top-k and top-p.  Its own instantiation of the kernel body: a session that uses none of them never launches it
+#define EMMAX_MAX_RULES 512         // rules of a table
+#define EMMAX_MAX_RULE_IDS 16       // ids of one rule
+#define EMMAX_MAX_RULE_TOTAL 8192   // ids of all rules
+struct RuleTable {
+    const int32_t* n;           // device word: the rule count (a session's table changes without a re-capture); null: n_host
+    int n_host;
+    const int32_t* off;         // [n + 1] offsets into ids; null: no rules
+    const int32_t* ids;
+    const int32_t* flags;       // [n] bits 0-1 kind (0 sequence_bias, 1 bad_words, 2 suppress, 3 begin_suppress), bit 2 begin-only
+    const float* bias;          // [n] (bias rules)
+};
+struct ExtFinishParams : ProcFinishParams {
+    const float *min_p, *typical_p, *eps_cut, *eta_cut;   // [B] each, 0 = off; all null: no warpers
+    RuleTable rt;
+    const uint32_t* rule_en;    // [B] bit k: the rules of kind k apply to the row
+    // the op form (emmax_op_sample_ext): tok_out non-null -- no row state is read or written (f.is_prefill = 1, f.max_out = 0: the history is
+    // hist alone, f.n_out the rows' generation index), the results go here
+    int32_t* tok_out;           // [B]
+    float* logprob_out;         // [B]
+    float* scores_out;          // [B][V] or null
+};
+int launch_ext_finish(const ExtFinishParams& p, hipStream_t stream);
 // ---- beam.hip: beam search in the decode step (include/emmax.h, ABI 9) ----
 #ifndef EMMAX_MAX_BEAMS
 #define EMMAX_MAX_BEAMS 8

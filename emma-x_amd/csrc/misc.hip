@@ -343,6 +343,9 @@ __global__ __launch_bounds__(256) void emmax_slots_commit_kernel(CommitParams c)
             c.penalty[dst] = c.penalty[src]; c.ngram[dst] = c.ngram[src]; c.min_new[dst] = c.min_new[src];
             c.hist_len[dst] = c.hist_len[src];
         }
+        if (c.warp[0])
+            for (int k = 0; k < 4; ++k) c.warp[k][dst] = c.warp[k][src];
+        if (c.rule_en) c.rule_en[dst] = c.rule_en[src];
         c.done[src] = 1; c.ctx_len[src] = 0;
     }
 }
@@ -366,6 +369,9 @@ __global__ __launch_bounds__(256) void emmax_slots_fork_kernel(SlotForkParams p)
         if (p.penalty) {
             p.penalty[f] = p.penalty[src]; p.ngram[f] = p.ngram[src]; p.min_new[f] = p.min_new[src]; p.hist_len[f] = p.hist_len[src];
         }
+        if (p.warp[0])
+            for (int k = 0; k < 4; ++k) p.warp[k][f] = p.warp[k][src];
+        if (p.rule_en) p.rule_en[f] = p.rule_en[src];
         const bool cp = rem > 0 && nfull < mp;   // (page nfull is past the shared ones: both rows still hold their own entry there)
         p.copy_src[j] = cp ? theirs[nfull] : -1;
         p.copy_dst[j] = cp ? mine[nfull] : -1;

@@ -86,10 +86,135 @@ static int set_processing_rows(emmax_session* s, int row0, int n, bool staged, c
     if (sc.error()) return sc.error();
     if (int r = upload_rows(s, r0, n, sc.stream(), {{s->proc.pen, pen, 4}, {s->proc.ng, ng, 4}, {s->proc.mn, mn, 4}})) return r;
     s->proc.on = true;
+    if (!staged) s->rules.implied_proc = false;   // the caller's own processing now: clearing the token rules leaves it on
+    return sc.leave();
+}
+
+// ---- the further warpers and the token rules (new symbols, same ABI) -------------------------------------------------------------
+int check_warper_values(int row0, int n, const float* minp, const float* typ, const float* eps, const float* eta) {
+    for (int i = 0; i < n; ++i) {
+        if (!(minp[i] >= 0.f && minp[i] <= 1.f)) return fail(EMMAX_ERR_INVALID, "row %d: min_p %g (0 = off, else 0 < min_p <= 1)", row0 + i, (double)minp[i]);
+        if (!(typ[i] >= 0.f && typ[i] <= 1.f)) return fail(EMMAX_ERR_INVALID, "row %d: typical_p %g (0 or 1 = off, else 0 < typical_p < 1)", row0 + i, (double)typ[i]);
+        if (!(eps[i] >= 0.f && eps[i] < 1.f)) return fail(EMMAX_ERR_INVALID, "row %d: epsilon_cutoff %g (0 = off, else 0 < epsilon_cutoff < 1)", row0 + i, (double)eps[i]);
+        if (!(eta[i] >= 0.f && eta[i] < 1.f)) return fail(EMMAX_ERR_INVALID, "row %d: eta_cutoff %g (0 = off, else 0 < eta_cutoff < 1)", row0 + i, (double)eta[i]);
+    }
+    return 0;
+}
+
+static int set_warper_rows(emmax_session* s, int row0, int n, bool staged, const float* minp, const float* typ, const float* eps, const float* eta, emmax_stream stream) {
+    if (!s || !minp || !typ || !eps || !eta) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (int r = check_rows(s, row0, n, staged)) return r;
+    if (!staged && s->beam.K) return fail(EMMAX_ERR_STATE, "warpers are not available while beams are on");
+    if (s->m->vocab > EMMAX_SAMPLE_MAX_V) return fail(EMMAX_ERR_INVALID, "warpers take vocabularies of up to %d entries (%d)", EMMAX_SAMPLE_MAX_V, s->m->vocab);
+    const int r0 = staged ? s->stg0 : row0;
+    if (int r = check_warper_values(r0, n, minp, typ, eps, eta)) return r;
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    if (int r = upload_rows(s, r0, n, sc.stream(), {{s->warp.minp, minp, 4}, {s->warp.typ, typ, 4}, {s->warp.eps, eps, 4}, {s->warp.eta, eta, 4}})) return r;
+    s->warp.on = true;
+    return sc.leave();
+}
+
+// a rule table as the host hands it over: n rules, rule r = ids[off[r] .. off[r + 1]), within the caps, flags and biases in range
+int check_rule_table(int n, const int32_t* off, const int32_t* ids, const int32_t* flags, const float* bias) {
+    if (n < 1 || n > EMMAX_MAX_RULES) return fail(EMMAX_ERR_INVALID, "%d token rules outside 1..%d", n, EMMAX_MAX_RULES);
+    if (!off || !ids || !flags || !bias) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (off[0] != 0 || off[n] > EMMAX_MAX_RULE_TOTAL) return fail(EMMAX_ERR_INVALID, "token rules: offsets start at %d and end at %d (0 .. at most %d ids)", off[0], off[n], EMMAX_MAX_RULE_TOTAL);
+    for (int r = 0; r < n; ++r) {
+        const int len = off[r + 1] - off[r];
+        if (len < 1 || len > EMMAX_MAX_RULE_IDS) return fail(EMMAX_ERR_INVALID, "token rule %d: %d ids outside 1..%d", r, len, EMMAX_MAX_RULE_IDS);
+        if (flags[r] < 0 || flags[r] > 7) return fail(EMMAX_ERR_INVALID, "token rule %d: flags %d outside 0..7", r, flags[r]);
+        if ((flags[r] & 3) == 0 && std::isnan(bias[r])) return fail(EMMAX_ERR_INVALID, "token rule %d: bias is NaN", r);
+        for (int k = off[r]; k < off[r + 1]; ++k)
+            if (ids[k] < 0) return fail(EMMAX_ERR_INVALID, "token rule %d: negative id %d", r, ids[k]);
+    }
+    return 0;
+}
+
+static int set_rule_enable_rows(emmax_session* s, int row0, int n, bool staged, const uint32_t* en, emmax_stream stream) {
+    if (!s || !en) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (int r = check_rows(s, row0, n, staged)) return r;
+    if (!s->rules.on) return fail(EMMAX_ERR_STATE, "no token rules are set (emmax_session_set_token_rules)");
+    const int r0 = staged ? s->stg0 : row0;
+    for (int i = 0; i < n; ++i)
+        if (en[i] > 15u) return fail(EMMAX_ERR_INVALID, "row %d: rule enable word %u outside 0..15", r0 + i, en[i]);
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    if (int r = upload_rows(s, r0, n, sc.stream(), {{s->rules.en, en, 4}})) return r;
     return sc.leave();
 }
 
 extern "C" {
+
+int emmax_session_set_warpers(emmax_session* s, int row0, int n, const float* min_p_host, const float* typical_p_host, const float* epsilon_cutoff_host,
+                              const float* eta_cutoff_host, emmax_stream stream) {
+    return set_warper_rows(s, row0, n, false, min_p_host, typical_p_host, epsilon_cutoff_host, eta_cutoff_host, stream);
+}
+
+int emmax_slots_set_warpers_staged(emmax_session* s, int n, const float* min_p_host, const float* typical_p_host, const float* epsilon_cutoff_host,
+                                   const float* eta_cutoff_host, emmax_stream stream) {
+    return set_warper_rows(s, 0, n, true, min_p_host, typical_p_host, epsilon_cutoff_host, eta_cutoff_host, stream);
+}
+
+int emmax_session_clear_warpers(emmax_session* s, emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->warp.on) return 0;
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    for (float* w : {s->warp.minp, s->warp.typ, s->warp.eps, s->warp.eta}) HIPCHK(hipMemsetAsync(w, 0, (size_t)s->rows_total * 4, sc.stream()));
+    s->warp.on = false;
+    return sc.leave();
+}
+
+int emmax_session_warpers(const emmax_session* s) { return s ? (s->warp.on ? 1 : 0) : -1; }
+
+int emmax_session_set_token_rules(emmax_session* s, int n_rules, const int32_t* offsets_host, const int32_t* ids_host, const int32_t* flags_host,
+                                  const float* bias_host, emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (int r = check_rule_table(n_rules, offsets_host, ids_host, flags_host, bias_host)) return r;
+    if (s->beam.K) return fail(EMMAX_ERR_STATE, "token rules are not available while beams are on");
+    if (s->m->vocab > EMMAX_SAMPLE_MAX_V) return fail(EMMAX_ERR_INVALID, "token rules take vocabularies of up to %d entries (%d)", EMMAX_SAMPLE_MAX_V, s->m->vocab);
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    HIPCHK(hipStreamSynchronize(sc.stream()));   // no step reads the table while it changes
+    const int32_t n = n_rules;
+    HIPCHK(hipMemcpy(s->rules.off, offsets_host, (size_t)(n_rules + 1) * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->rules.ids, ids_host, (size_t)offsets_host[n_rules] * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->rules.flags, flags_host, (size_t)n_rules * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->rules.bias, bias_host, (size_t)n_rules * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->rules.n, &n, 4, hipMemcpyHostToDevice));
+    if (!s->rules.on) {   // every row starts with every kind enabled; the rules read the history: processing on, neutral where it was off
+        std::vector<uint32_t> all((size_t)s->rows_total, 15u);
+        HIPCHK(hipMemcpy(s->rules.en, all.data(), all.size() * 4, hipMemcpyHostToDevice));
+        if (!s->proc.on) {
+            std::vector<float> one((size_t)s->rows_total, 1.f);
+            HIPCHK(hipMemcpy(s->proc.pen, one.data(), one.size() * 4, hipMemcpyHostToDevice));
+            HIPCHK(hipMemset(s->proc.ng, 0, (size_t)s->rows_total * 4));
+            HIPCHK(hipMemset(s->proc.mn, 0, (size_t)s->rows_total * 4));
+            s->proc.on = true;
+            s->rules.implied_proc = true;
+        }
+    }
+    s->rules.on = true;
+    return sc.leave();
+}
+
+int emmax_session_set_rule_enables(emmax_session* s, int row0, int n, const uint32_t* enable_host, emmax_stream stream) {
+    return set_rule_enable_rows(s, row0, n, false, enable_host, stream);
+}
+
+int emmax_slots_set_rule_enables_staged(emmax_session* s, int n, const uint32_t* enable_host, emmax_stream stream) {
+    return set_rule_enable_rows(s, 0, n, true, enable_host, stream);
+}
+
+int emmax_session_clear_token_rules(emmax_session* s, emmax_stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (s->rules.on && s->rules.implied_proc) s->proc.on = false;
+    s->rules.on = s->rules.implied_proc = false;
+    return 0;
+}
+
+int emmax_session_token_rules(const emmax_session* s) { return s ? (s->rules.on ? 1 : 0) : -1; }
 
 int emmax_session_set_stop(emmax_session* s, const int32_t* trigger_ids, int n_trigger, int n_after, emmax_stream stream) {
     if (!s || (n_trigger > 0 && !trigger_ids)) return fail(EMMAX_ERR_INVALID, "null argument");
@@ -112,10 +237,10 @@ int emmax_slots_set_sampling_staged(emmax_session* s, int n, const float* temper
     return set_sampling_rows(s, 0, n, true, temperature_host, top_k_host, top_p_host, seed_host, subseq_host, stream);
 }
 
-int emmax_session_clear_sampling(emmax_session* s, emmax_stream) {
+int emmax_session_clear_sampling(emmax_session* s, emmax_stream stream) {
     if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
     s->samp.on = false;
-    return 0;
+    return emmax_session_clear_warpers(s, stream);   // the warpers belong to the draw
 }
 
 int emmax_session_sampling(const emmax_session* s) { return s ? (s->samp.on ? 1 : 0) : -1; }
@@ -156,6 +281,7 @@ int emmax_slots_set_processing_staged(emmax_session* s, int n, const float* pena
 int emmax_session_clear_processing(emmax_session* s, emmax_stream) {
     if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
     s->proc.on = false;
+    s->rules.on = s->rules.implied_proc = false;   // the token rules are processors (the table stays on the device; set it again to use it)
     return 0;
 }
 
@@ -193,7 +319,7 @@ int emmax_session_set_beams(emmax_session* s, int num_beams, double length_penal
         return fail(EMMAX_ERR_INVALID, "beams take vocabularies of %d..%d entries (%d)", 2 * num_beams, EMMAX_SAMPLE_MAX_V, s->m->vocab);
     if (s->slots_open) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while request slots are open");
     if (s->grp_N) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while sample groups are on (emmax_session_clear_sample_groups)");
-    if (s->samp.on || s->proc.on) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while sampling or logits processing is on");
+    if (s->samp.on || s->proc.on || s->warp.on || s->rules.on) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while sampling or logits processing is on");
     if (s->scores.on && s->scores.has_scores) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while a scores buffer is bound");
     StreamScope sc(s, stream);
     if (sc.error()) return sc.error();

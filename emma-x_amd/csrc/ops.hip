@@ -63,6 +63,32 @@ int emmax_op_sample(const float* logits, int ld, int B, int V, const float* temp
     KCHK(launch_sample(p, B, (hipStream_t)stream));
     return 0;
 }
+int emmax_op_sample_ext(const float* logits, int ld, int B, int V, const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seed,
+                        const uint32_t* subseq, const int32_t* n_out, const float* min_p, const float* typical_p, const float* epsilon_cutoff,
+                        const float* eta_cutoff, const float* penalty, const int32_t* ngram, const int32_t* min_new, const int32_t* hist, const int32_t* hist_len,
+                        int max_hist, int n_rules, const int32_t* rule_off, const int32_t* rule_ids, const int32_t* rule_flags, const float* rule_bias,
+                        const uint32_t* rule_enable, int eos_id, int pad_id, int32_t* tok_out, float* logprob_out, float* scores_out, emmax_stream stream) {
+    if (!logits || !temperature || !top_k || !top_p || !seed || !subseq || !n_out || !tok_out || !logprob_out) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (B < 1 || V < 1 || V > EMMAX_SAMPLE_MAX_V || ld < V)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_sample_ext: B %d (>= 1), V %d (1..%d), ld %d (>= V)", B, V, EMMAX_SAMPLE_MAX_V, ld);
+    const bool warp = min_p || typical_p || epsilon_cutoff || eta_cutoff, proc = penalty || ngram || min_new || hist || hist_len;
+    if (warp && (!min_p || !typical_p || !epsilon_cutoff || !eta_cutoff)) return fail(EMMAX_ERR_INVALID, "emmax_op_sample_ext: the four warper arrays come together");
+    if (proc && (!penalty || !ngram || !min_new || !hist || !hist_len || max_hist < 1))
+        return fail(EMMAX_ERR_INVALID, "emmax_op_sample_ext: the processor arrays and the histories come together (max_hist >= 1)");
+    if (n_rules < 0 || n_rules > EMMAX_MAX_RULES) return fail(EMMAX_ERR_INVALID, "%d token rules outside 0..%d", n_rules, EMMAX_MAX_RULES);
+    if (n_rules > 0 && (!proc || !rule_off || !rule_ids || !rule_flags || !rule_bias || !rule_enable))
+        return fail(EMMAX_ERR_INVALID, "emmax_op_sample_ext: token rules need the table's five arrays and the processor arrays (the histories)");
+    ExtFinishParams p;
+    memset(&p, 0, sizeof(p));
+    p.f.B = B; p.f.n_out = (int32_t*)n_out; p.f.is_prefill = 1; p.f.max_out = 0; p.f.eos_id = eos_id; p.f.pad_id = pad_id;
+    p.logits = logits; p.ld = ld; p.V = V; p.temperature = temperature; p.top_k = top_k; p.top_p = top_p; p.seed = seed; p.subseq = subseq;
+    p.min_p = min_p; p.typical_p = typical_p; p.eps_cut = epsilon_cutoff; p.eta_cut = eta_cutoff;
+    p.penalty = penalty; p.ngram = ngram; p.min_new = min_new; p.hist = hist; p.hist_len = hist_len; p.max_prompt = max_hist;
+    if (n_rules > 0) { p.rt.n_host = n_rules; p.rt.off = rule_off; p.rt.ids = rule_ids; p.rt.flags = rule_flags; p.rt.bias = rule_bias; p.rule_en = rule_enable; }
+    p.tok_out = tok_out; p.logprob_out = logprob_out; p.scores_out = scores_out;
+    KCHK(launch_ext_finish(p, (hipStream_t)stream));
+    return 0;
+}
 int emmax_op_gemm(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K, const void* bias, int act,
                   const void* scale, const void* residual, int ldr, int out_f32, emmax_stream st) {
     GemmParams p = gp(A, lda, W, ldw, C, ldc, M, N, K);
@@ -379,7 +405,7 @@ int emmax_op_decode_stage(emmax_session* s, int layer, int stage, int B, const v
     if (nsplit_out) *nsplit_out = ns;
     if (via_out) *via_out = EMMAX_VIA_NONE;
     if (stage == STAGE_OPROJ && !x_in && !h_in && !h32_in) return 0;   // the query form: which input the o-proj of B rows reads, nothing launched
-    if (s->samp.on || s->proc.on || s->scores.on || s->beam.K || s->slots_open)
+    if (s->samp.on || s->proc.on || s->warp.on || s->rules.on || s->scores.on || s->beam.K || s->slots_open)
         return fail(EMMAX_ERR_STATE, "emmax_op_decode_stage: the session must be greedy (no sampling, processing, scores, beams or open slots)");
     if (!decode_batch_served(m, B, s->exact))   // (a prefill is held to it by the limit; this op is the one way past that)
         return fail(EMMAX_ERR_INVALID, "emmax_op_decode_stage: steps of %d rows are served with one-split attention and an intermediate size above 4096 only (emmax_model_max_decode_batch)", B);

@@ -196,10 +196,193 @@ __device__ __forceinline__ float row_temperature(const ProcFinishParams& p, int 
 // id j of row b's history: the prompt ids, then the ids the row has emitted
 __device__ __forceinline__ int hist_id(const int32_t* prompt, int plen, const int32_t* out, int j) { return j < plen ? prompt[j] : out[j - plen]; }
 
+// ---- the EXT forms (include/emmax.h: emmax_op_sample_ext; kernels.h: ExtFinishParams) -----------------------------------------------
+// entry j of a lane (register z[j]) is id 4 ((j / 4) ST + tid) + j % 4
+__device__ __forceinline__ int entry_id(int j, int tid) { return ((j >> 2) * ST + tid) * 4 + (j & 3); }
+
+// The radix walk of radix_threshold over any per-entry (active, key, mass): returns the threshold key t such that the active entries with
+// key >= t are exactly those whose mass strictly above them is below `target` (or zero).  A copy of that walk rather than its generalisation:
+// the existing instantiations are to keep their code object byte for byte
+template <class F>
+__device__ uint32_t radix_walk(F entry, double target, SampleShared& sh, int tid, int lane, int wave) {
+    uint32_t prefix = 0, mask = 0;
+    unsigned long long above = 0;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        for (int j = lane; j < 256; j += EMMAX_WAVE) sh.hist[wave][j] = 0;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < SG * 4; ++j) {
+            uint32_t key;
+            unsigned long long m;
+            if (entry(j, key, m) && (key & mask) == prefix) atomicAdd(&sh.hist[wave][(key >> shift) & 255u], m);
+        }
+        __syncthreads();
+        if (tid < 256) {
+            unsigned long long s = 0;
+#pragma unroll
+            for (int v = 0; v < SWV; ++v) s += sh.hist[v][tid];
+            sh.tot[tid] = s;
+        }
+        __syncthreads();
+        if (wave == 0) {   // lane l holds bins 4l .. 4l + 3; S(d) = mass in the bins above d
+            const unsigned long long c0 = sh.tot[4 * lane], c1 = sh.tot[4 * lane + 1], c2 = sh.tot[4 * lane + 2], c3 = sh.tot[4 * lane + 3];
+            const unsigned long long mine = c0 + c1 + c2 + c3;
+            unsigned long long incl = mine;
+#pragma unroll
+            for (int o = 1; o < EMMAX_WAVE; o <<= 1) {
+                const unsigned long long t = __shfl_down(incl, o);
+                if (lane + o < EMMAX_WAVE) incl += t;
+            }
+            const unsigned long long up = above + (incl - mine);
+            const unsigned long long s3 = up, s2 = up + c3, s1 = s2 + c2, s0 = s1 + c1;
+            auto ok = [&](unsigned long long s) { return s == 0 || (double)s < target; };
+            const int dl = ok(s0) ? 0 : ok(s1) ? 1 : ok(s2) ? 2 : ok(s3) ? 3 : -1;
+            const unsigned long long sd = dl == 0 ? s0 : dl == 1 ? s1 : dl == 2 ? s2 : s3;
+            const unsigned long long bal = __ballot(dl >= 0);
+            const int L = __ffsll((long long)bal) - 1;
+            if (lane == L) {
+                sh.sel_d = 4 * lane + dl;
+                sh.sel_a = sd;
+            }
+        }
+        __syncthreads();
+        prefix |= (uint32_t)sh.sel_d << shift;
+        mask |= 255u << shift;
+        above = sh.sel_a;
+        __syncthreads();
+    }
+    return prefix;
+}
+
+// The warpers behind top-k / top-p (include/emmax.h), in HF's order, on the kept set `km` (bit j: entry j of this lane is kept) of the row
+// z = l / T: min_p, typical_p, epsilon_cutoff, eta_cutoff.  Integer masses W = mass_of(z, zmax); every sum has a fixed order.
+__device__ void warp_row(const ExtFinishParams& p, int b, int tid, const float (&z)[SG * 4], float zmax, uint32_t& km, SampleShared& sh,
+                         int lane, int wave) {
+    const float mp = p.min_p[b], ty = p.typical_p[b], ep = p.eps_cut[b], et = p.eta_cut[b];
+    auto kept_mass = [&]() {
+        unsigned long long t = 0;
+#pragma unroll
+        for (int j = 0; j < SG * 4; ++j)
+            if ((km >> j) & 1u) t += mass_of(z[j], zmax);
+        return block_sum_u64(t, sh, lane, wave);
+    };
+    // H = -sum p_i lp_i over the kept set: p_i = fp32(W_i) / fp32(S), lp_i = (z_i - zmax) - lnZ; lane entries in register order, then block_sum
+    auto entropy = [&](float invS, float lnZ) {
+        float e = 0.f;
+#pragma unroll
+        for (int j = 0; j < SG * 4; ++j)
+            if ((km >> j) & 1u) {
+                const float pj = __fmul_rn((float)mass_of(z[j], zmax), invS);
+                e = __fadd_rn(e, __fmul_rn(pj, (z[j] - zmax) - lnZ));
+            }
+        return -block_sum(e, sh, lane, wave);
+    };
+    if (mp > 0.f) {   // W_i >= floor(min_p 2^32): the maximum's mass is 2^32
+        const unsigned long long M = (unsigned long long)(mp * 4294967296.0f);
+#pragma unroll
+        for (int j = 0; j < SG * 4; ++j)
+            if (((km >> j) & 1u) && mass_of(z[j], zmax) < M) km &= ~(1u << j);
+    }
+    if (ty > 0.f && ty < 1.f) {
+        const unsigned long long S = kept_mass();
+        if (S > 0) {
+            const float lnZ = logf((float)S * 0x1p-32f), invS = 1.f / (float)S;
+            const float H = entropy(invS, lnZ);
+            // ascending distance |(-lp_i) - H|: the walk runs on the complemented key
+            auto entry = [&](int j, uint32_t& key, unsigned long long& m) {
+                key = ~fkey(fabsf(-((z[j] - zmax) - lnZ) - H));
+                m = mass_of(z[j], zmax);
+                return ((km >> j) & 1u) != 0;
+            };
+            const uint32_t t = radix_walk(entry, (double)ty * (double)S, sh, tid, lane, wave);
+#pragma unroll
+            for (int j = 0; j < SG * 4; ++j)
+                if (((km >> j) & 1u) && ~fkey(fabsf(-((z[j] - zmax) - lnZ) - H)) < t) km &= ~(1u << j);
+        }
+    }
+    const bool eps_on = ep > 0.f && ep < 1.f, eta_on = et > 0.f && et < 1.f;
+    if (eps_on || eta_on) {
+        float cm = -INFINITY;   // the largest kept z (typical_p may have dropped the row's maximum): it always stays
+#pragma unroll
+        for (int j = 0; j < SG * 4; ++j)
+            if ((km >> j) & 1u) cm = fmaxf(cm, z[j]);
+        cm = block_max(cm, sh, lane, wave);
+        for (int pass = 0; pass < 2; ++pass) {
+            if (!(pass == 0 ? eps_on : eta_on)) continue;
+            const unsigned long long S = kept_mass();
+            if (S == 0) break;
+            float cut = ep;
+            if (pass == 1) {
+                const float H = entropy(1.f / (float)S, logf((float)S * 0x1p-32f));
+                cut = fminf(et, __fmul_rn(sqrtf(et), expf(-H)));
+            }
+            const double line = (double)cut * (double)S;   // keep W_i >= fp64(cut) fp64(S), one rounding
+#pragma unroll
+            for (int j = 0; j < SG * 4; ++j)
+                if (((km >> j) & 1u) && (double)mass_of(z[j], zmax) < line && z[j] < cm) km &= ~(1u << j);
+        }
+    }
+}
+
+// The token rules of an EXT processing finish against the tail of the row's history (include/emmax.h): rule r = ids off[r] .. off[r + 1],
+// flags (bits 0-1 kind: 0 sequence_bias, 1 bad_words, 2 suppress, 3 begin_suppress; bit 2: fires at n_out == 0 only), enabled by bit `kind`
+// of the row's enable word.  A rule of n ids fires when n == 1, or n <= L and the history ends with its first n - 1 ids.  Bans go into the
+// ban bitmap; a bias rule leaves its last id in lid[r] (-1: did not fire)
+__device__ void match_rules(const ExtFinishParams& p, int b, int tid, int V, int n_out, const int32_t* prompt, int plen, const int32_t* out, int L,
+                            int R, uint32_t* ban, int* lid) {
+    const uint32_t en = p.rule_en[b];
+    for (int r = tid; r < EMMAX_MAX_RULES; r += ST) {
+        int hit = -1;
+        if (r < R) {
+            const int o = p.rt.off[r], n = p.rt.off[r + 1] - o, fl = p.rt.flags[r];
+            if (o >= 0 && n >= 1 && n <= EMMAX_MAX_RULE_IDS && o + n <= EMMAX_MAX_RULE_TOTAL && ((en >> (fl & 3)) & 1u) && (!(fl & 4) || n_out == 0) &&
+                (n == 1 || n <= L)) {
+                bool same = true;
+                for (int k = 0; k < n - 1 && same; ++k) same = hist_id(prompt, plen, out, L - (n - 1) + k) == p.rt.ids[o + k];
+                const int id = p.rt.ids[o + n - 1];
+                if (same && id >= 0 && id < V) {
+                    if (fl & 3) atomicOr(&ban[id >> 5], 1u << (id & 31));
+                    else hit = id;
+                }
+            }
+        }
+        lid[r] = hit;
+    }
+}
+
+// The biases of the fired sequence_bias rules, added to the row held in z: per id the biases are summed in rule order from 0 (fp32), by the
+// first fired rule of that id, and the sum is added once (HF: scores + bias) by the lane that holds the id
+__device__ void apply_bias(const ExtFinishParams& p, int tid, int R, float (&z)[SG * 4], const int* lid, int* own, float* bsum) {
+    for (int r = tid; r < EMMAX_MAX_RULES; r += ST) {
+        const int id = r < R ? lid[r] : -1;
+        bool first = id >= 0;
+        for (int j = 0; j < r && first; ++j) first = lid[j] != id;
+        float acc = 0.f;
+        if (first)
+            for (int j = r; j < R; ++j)
+                if (lid[j] == id) acc += p.rt.bias[j];
+        own[r] = first ? id : -1;
+        bsum[r] = acc;
+    }
+    __syncthreads();
+    for (int r = 0; r < R; ++r) {
+        const int id = own[r];
+        if (id >= 0 && ((id >> 2) & (ST - 1)) == tid) {
+            const int jj = ((id >> 2) / ST) * 4 + (id & 3);
+            const float a = bsum[r];
+#pragma unroll
+            for (int j = 0; j < SG * 4; ++j)
+                if (j == jj) z[j] += a;
+        }
+    }
+}
+
 // The logits processors of a processing finish (include/emmax.h), in HF's order, on the row held in z (entry i = 4 (g * ST + tid) + c):
 // repetition penalty over the distinct ids of the history, n-gram ban, EOS ban while n_out < min_new.  The presence and ban bitmaps are
 // LDS words set with integer atomicOr only, so the processed row does not depend on the order work arrives in.
-__device__ void process_row(const ProcFinishParams& p, int b, int tid, int V, int n_out, float (&z)[SG * 4], uint32_t* pres, uint32_t* ban) {
+template <class P>
+__device__ void process_row(const P& p, int b, int tid, int V, int n_out, float (&z)[SG * 4], uint32_t* pres, uint32_t* ban) {
+    constexpr bool EXT = std::is_same<P, ExtFinishParams>::value;
     const float pen = p.penalty[b];
     const int ng = p.ngram[b], mn = p.min_new[b];
     const int plen = min(max(p.hist_len[b], 0), p.max_prompt);
@@ -209,6 +392,17 @@ __device__ void process_row(const ProcFinishParams& p, int b, int tid, int V, in
     const int W = (V + 31) / 32;
     for (int w = tid; w < W; w += ST) { pres[w] = 0u; ban[w] = 0u; }
     __syncthreads();
+    [[maybe_unused]] int R = 0;
+    if constexpr (EXT) {
+        if (p.rt.off) {
+            __shared__ int lid[EMMAX_MAX_RULES], own[EMMAX_MAX_RULES];
+            __shared__ float bsum[EMMAX_MAX_RULES];
+            R = min(max(p.rt.n ? *p.rt.n : p.rt.n_host, 0), EMMAX_MAX_RULES);
+            match_rules(p, b, tid, V, n_out, prompt, plen, out, L, R, ban, lid);
+            __syncthreads();
+            apply_bias(p, tid, R, z, lid, own, bsum);
+        }
+    }
     if (pen != 1.f)
         for (int j = tid; j < L; j += ST) {
             const int id = hist_id(prompt, plen, out, j);
@@ -260,7 +454,8 @@ __device__ __forceinline__ void store_row(float* dst, const float (&z)[SG * 4], 
 // than a shared device function: inlining the draw into two kernels raised the spills of this one from 75 to 88 VGPRs.)
 template <class P>
 __global__ __launch_bounds__(ST) void emmax_sample_kernel(P p) {
-    constexpr bool PROC = std::is_same<P, ProcFinishParams>::value;
+    constexpr bool EXT = std::is_same<P, ExtFinishParams>::value;   // the processing finish with the token rules and the further warpers
+    constexpr bool PROC = std::is_same<P, ProcFinishParams>::value || EXT;
     constexpr bool FIN = std::is_same<P, SampleFinishParams>::value || PROC;
     __shared__ SampleShared sh;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (EMMAX_WAVE - 1), wave = tid / EMMAX_WAVE;
@@ -314,6 +509,7 @@ __global__ __launch_bounds__(ST) void emmax_sample_kernel(P p) {
     float bv = -INFINITY;
     int bi = 0x7fffffff;
     uint32_t kept = 0;   // (processing finish, T > 0) the kept set: key(z) >= kept
+    [[maybe_unused]] uint32_t km = 0;   // (EXT, T > 0) the kept set: bit j = entry z[j]
     if (dead) {
     } else if (!(T > 0.f)) {   // greedy: argmax, lowest id on ties
 #pragma unroll
@@ -346,6 +542,25 @@ __global__ __launch_bounds__(ST) void emmax_sample_kernel(P p) {
         kept = thr;
         // Gumbel-max over the kept entries; Philox only for groups with a kept entry
         const uint32_t k0 = (uint32_t)p.seed[b], k1 = (uint32_t)(p.seed[b] >> 32), sub = p.subseq[b];
+        if constexpr (EXT) {   // the same draw over the kept bits the warpers leave (-inf and NaN entries are never kept)
+#pragma unroll
+            for (int j = 0; j < SG * 4; ++j)
+                if (entry_id(j, tid) < V && fkey(z[j]) >= thr && z[j] > -INFINITY) km |= 1u << j;
+            if (p.min_p) warp_row(p, b, tid, z, zmax, km, sh, lane, wave);
+#pragma unroll
+            for (int g = 0; g < SG; ++g) {
+                if (!((km >> (g * 4)) & 15u)) continue;
+                const int q = g * ST + tid;
+                uint32_t x[4] = {(uint32_t)q, (uint32_t)step, sub, 0u};
+                philox4x32_10(x, k0, k1);
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if ((km >> (g * 4 + c)) & 1u) {
+                        const float s = z[g * 4 + c] + gumbel_of(x[c]);
+                        if (better(s, 4 * q + c, bv, bi)) { bv = s; bi = 4 * q + c; }
+                    }
+            }
+        } else
 #pragma unroll
         for (int g = 0; g < SG; ++g) {
             const int q = g * ST + tid;
@@ -376,7 +591,7 @@ __global__ __launch_bounds__(ST) void emmax_sample_kernel(P p) {
                 if (sc) {
                     if (T > 0.f && !dead)
 #pragma unroll
-                        for (int j = 0; j < SG * 4; ++j) z[j] = fkey(z[j]) >= kept ? z[j] : -INFINITY;
+                        for (int j = 0; j < SG * 4; ++j) z[j] = (EXT ? ((km >> j) & 1u) != 0 : fkey(z[j]) >= kept) ? z[j] : -INFINITY;
                     store_row(sc + off, z, tid, V);
                 }
                 if (lg)
@@ -384,12 +599,27 @@ __global__ __launch_bounds__(ST) void emmax_sample_kernel(P p) {
             }
         }
     }
+    if constexpr (EXT) {
+        if (p.scores_out) {   // (the op form) the row's scores, as the scores store above
+            if (T > 0.f && !dead)
+#pragma unroll
+                for (int j = 0; j < SG * 4; ++j) z[j] = ((km >> j) & 1u) ? z[j] : -INFINITY;
+            store_row(p.scores_out + (size_t)b * V, z, tid, V);
+        }
+    }
     if (tid == 0) {
         // (an all-NaN row keeps no entry: the token is -1, its log-probability NaN.  In a step -1 never reaches cur_tok, whose row the next
         // step's embedding gather reads: the row emits pad and is done)
         const bool ok = tok >= 0 && tok < V;
         const float lp = ok ? row[tok] - lse : __int_as_float(0x7fc00000);
-        if constexpr (FIN) {
+        if constexpr (EXT) {
+            if (p.tok_out) {   // the op form: no row state
+                p.tok_out[b] = ok ? tok : dead ? p.f.pad_id : -1;
+                p.logprob_out[b] = lp;
+            } else {
+                emmax_finish_row(p.f, b, ok ? tok : p.f.pad_id, p.logprob + (size_t)b * p.f.max_out, lp, !ok);
+            }
+        } else if constexpr (FIN) {
             emmax_finish_row(p.f, b, ok ? tok : p.f.pad_id, p.logprob + (size_t)b * p.f.max_out, lp, !ok);
         } else {
             p.tok_out[b] = ok ? tok : -1;
@@ -416,5 +646,15 @@ int launch_proc_finish(const ProcFinishParams& p, hipStream_t stream) {
 int launch_sample_finish(const SampleFinishParams& p, hipStream_t stream) {
     if (p.f.B < 1 || p.V < 1 || p.V > EMMAX_SAMPLE_MAX_V || p.ld < p.V) return -1;
     hipLaunchKernelGGL(emmax_sample_kernel<SampleFinishParams>, dim3(p.f.B), dim3(ST), 0, stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+int launch_ext_finish(const ExtFinishParams& p, hipStream_t stream) {
+    if (p.f.B < 1 || p.V < 1 || p.V > EMMAX_SAMPLE_MAX_V || p.ld < p.V) return -1;
+    if (p.penalty && (!p.ngram || !p.min_new || !p.hist || !p.hist_len || p.max_prompt < 1)) return -1;
+    if (p.rt.off && (!p.penalty || !p.rt.ids || !p.rt.flags || !p.rt.bias || !p.rule_en || (!p.rt.n && (p.rt.n_host < 0 || p.rt.n_host > EMMAX_MAX_RULES)))) return -1;
+    if (p.min_p && (!p.typical_p || !p.eps_cut || !p.eta_cut)) return -1;
+    if (p.tok_out && (!p.logprob_out || !p.f.is_prefill || p.f.max_out != 0)) return -1;
+    hipLaunchKernelGGL(emmax_sample_kernel<ExtFinishParams>, dim3(p.f.B), dim3(ST), 0, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }

@@ -138,6 +138,20 @@ struct Processing {
     float* pen;
     int32_t *ng, *mn, *hist /* [rows_total][max_prompt] */, *hist_len;
 };
+// WARPERS (emmax_session_set_warpers): per-row min_p / typical_p / epsilon_cutoff / eta_cutoff of every row, staging rows included (0 = off;
+// the workspace starts zeroed).  TOKEN RULES (emmax_session_set_token_rules): the session's one rule table behind a device count word, and
+// a per-row enable word.  Either on: a step ends in the EXT finish (sample.hip).  Both off: none of it is touched
+struct Warpers {
+    bool on = false;
+    float *minp, *typ, *eps, *eta;
+};
+struct TokenRules {
+    bool on = false;
+    bool implied_proc = false;   // the rules turned processing on with neutral values (they read the history): clearing them turns it off again
+    int32_t *n /* [1] */, *off /* [EMMAX_MAX_RULES + 1] */, *ids /* [EMMAX_MAX_RULE_TOTAL] */, *flags;
+    float* bias;
+    uint32_t* en;                // [rows_total]
+};
 // SCORES (emmax_session_set_scores): device words {scores, logits, max_new, rows} the processing finish stores through.  Processing or scores
 // on: the step runs on the logit rows and ends in the processing finish.  Both off: none of it is touched
 struct Scores {
@@ -190,6 +204,8 @@ struct emmax_session {
     float* logits;              // f32 [rows_total][vocab]
     Sampling samp;
     Processing proc;
+    Warpers warp;
+    TokenRules rules;
     Scores scores;
     Beams beam;
     // SAMPLE GROUPS (emmax_session_set_sample_groups; step.hip: run_group_fork): N sampled rows per prefilled prompt, 0 = off.  Rows g N + j are

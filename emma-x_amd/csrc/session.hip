@@ -75,6 +75,16 @@ static void plan_session(emmax_session* s, Bump& b) {
     s->proc.hist = (int32_t*)b.bytes((int64_t)Br * s->max_prompt * 4);
     s->proc.hist_len = (int32_t*)b.bytes(Br * 4);
     s->scores.words = (uint64_t*)b.bytes(4 * 8);
+    s->warp.minp = (float*)b.bytes(Br * 4);
+    s->warp.typ = (float*)b.bytes(Br * 4);
+    s->warp.eps = (float*)b.bytes(Br * 4);
+    s->warp.eta = (float*)b.bytes(Br * 4);
+    s->rules.n = (int32_t*)b.bytes(4);
+    s->rules.off = (int32_t*)b.bytes((EMMAX_MAX_RULES + 1) * 4);
+    s->rules.ids = (int32_t*)b.bytes(EMMAX_MAX_RULE_TOTAL * 4);
+    s->rules.flags = (int32_t*)b.bytes(EMMAX_MAX_RULES * 4);
+    s->rules.bias = (float*)b.bytes(EMMAX_MAX_RULES * 4);
+    s->rules.en = (uint32_t*)b.bytes(Br * 4);
     s->cur_tok = (int32_t*)b.bytes(Br * 4);
     s->ctx_len = (int32_t*)b.bytes(Br * 4);
     s->done = (int32_t*)b.bytes(Br * 4);

@@ -261,9 +261,12 @@ static void lmhead_params(emmax_session* s, int slot0, float* logits_out, GemvPa
 // how a step ends (the captured graph is keyed on it: the finish's parameters differ in each): bit 0 sampling, bit 1 processing, bit 2
 // scores.  0: the greedy finish (lm-head argmax partials); 1: the sampled finish; bit 1 or 2 set: the processing finish
 // beams on: bit 3, stop_on_eos in bit 4, K and the early-stopping mode above (the beam finish holds them by value)
+// warpers or token rules on (bits 13, 14): the EXT finish
+enum { FINISH_WARP = 1 << 13, FINISH_RULES = 1 << 14, FINISH_EXT = FINISH_WARP | FINISH_RULES, FINISH_ROWS = 6 | FINISH_EXT /* runs on the logit rows */ };
 static int finish_mode(const emmax_session* s) {
     return (s->samp.on ? 1 : 0) | (s->proc.on ? 2 : 0) | (s->scores.on ? 4 : 0) |
-           (s->beam.K ? (8 | (s->beam.eos >= 0 ? 16 : 0) | (s->beam.K << 5) | (s->beam.es << 10) | (s->beam.lp_pos << 12)) : 0);
+           (s->beam.K ? (8 | (s->beam.eos >= 0 ? 16 : 0) | (s->beam.K << 5) | (s->beam.es << 10) | (s->beam.lp_pos << 12)) : 0) |
+           (s->warp.on ? FINISH_WARP : 0) | (s->rules.on ? FINISH_RULES : 0);
 }
 
 // the per-row state of rows slot0 .. slot0 + B that a finish updates
@@ -313,7 +316,7 @@ static int launch_sampled_finish_step(emmax_session* s, int B, bool is_prefill, 
 
 // finish of a step with logits processing or scores on: the processors, then the draw (sampling on) or the argmax, then the scores store
 static int launch_proc_finish_step(emmax_session* s, int B, bool is_prefill, int slot0, const float* logits, hipStream_t st) {
-    ProcFinishParams p;
+    ExtFinishParams p;   // (warpers and token rules off: launched as its ProcFinishParams base)
     memset(&p, 0, sizeof(p));
     finish_rows(s, B, is_prefill, slot0, p.f);
     p.logits = logits; p.ld = s->m->vocab; p.V = s->m->vocab;
@@ -325,7 +328,16 @@ static int launch_proc_finish_step(emmax_session* s, int B, bool is_prefill, int
         p.hist = s->proc.hist + (size_t)slot0 * s->max_prompt; p.hist_len = s->proc.hist_len + slot0; p.max_prompt = s->max_prompt;
     }
     if (s->scores.on) p.score_words = s->scores.words;
-    KCHK(launch_proc_finish(p, st));
+    if (!s->warp.on && !s->rules.on) {
+        KCHK(launch_proc_finish(p, st));
+        return 0;
+    }
+    if (s->warp.on) { p.min_p = s->warp.minp + slot0; p.typical_p = s->warp.typ + slot0; p.eps_cut = s->warp.eps + slot0; p.eta_cut = s->warp.eta + slot0; }
+    if (s->rules.on) {
+        p.rt.n = s->rules.n; p.rt.off = s->rules.off; p.rt.ids = s->rules.ids; p.rt.flags = s->rules.flags; p.rt.bias = s->rules.bias;
+        p.rule_en = s->rules.en + slot0;
+    }
+    KCHK(launch_ext_finish(p, st));
     return 0;
 }
 
@@ -436,7 +448,7 @@ int run_group_fork(emmax_session* s, int G, hipStream_t st) {
     for (int r0 = 0; r0 < rows; r0 += chunk) {
         const int n = std::min(chunk, rows - r0);
         const float* lg = s->logits + (size_t)r0 * V;
-        if (int r = (mode & 6) ? launch_proc_finish_step(s, n, true, r0, lg, st) : launch_sampled_finish_step(s, n, true, r0, lg, st)) return r;
+        if (int r = (mode & FINISH_ROWS) ? launch_proc_finish_step(s, n, true, r0, lg, st) : launch_sampled_finish_step(s, n, true, r0, lg, st)) return r;
     }
     return 0;
 }
@@ -455,12 +467,14 @@ int run_slots_fork(emmax_session* s, int src, int logit_row, const int32_t* dst,
     f.in_t = s->fork_t; f.in_p = s->fork_p; f.in_k = s->fork_k; f.in_seed = s->fork_seed; f.in_sub = s->fork_sub;
     f.temperature = s->samp.t; f.top_p = s->samp.p; f.top_k = s->samp.k; f.seed = s->samp.seed; f.subseq = s->samp.sub;
     if (s->proc.on) { f.penalty = s->proc.pen; f.ngram = s->proc.ng; f.min_new = s->proc.mn; f.hist = s->proc.hist; f.hist_len = s->proc.hist_len; }
+    if (s->warp.on) { f.warp[0] = s->warp.minp; f.warp[1] = s->warp.typ; f.warp[2] = s->warp.eps; f.warp[3] = s->warp.eta; }
+    if (s->rules.on) f.rule_en = s->rules.en;
     KCHK(launch_slots_fork(f, st));
     if (f.S % PAGE != 0)   // (else the prompt ends on a page boundary: every page is shared by reference, nothing to copy)
         if (int r = launch_page_copies(s, n, st)) return r;
     const float* lg = s->logits + (size_t)logit_row * s->m->vocab;
     for (int j = 0; j < n; ++j)
-        if (int r = s->proc.on ? launch_proc_finish_step(s, 1, true, dst[j], lg, st) : launch_sampled_finish_step(s, 1, true, dst[j], lg, st)) return r;
+        if (int r = (finish_mode(s) & FINISH_ROWS) ? launch_proc_finish_step(s, 1, true, dst[j], lg, st) : launch_sampled_finish_step(s, 1, true, dst[j], lg, st)) return r;
     return 0;
 }
 
@@ -495,7 +509,7 @@ int run_lm_head_step(emmax_session* s, int B, bool is_prefill, float* logits_out
     lmhead_params(s, slot0, logits_out, p);
     int lm_grid = 0;
     KCHK(launch_proj(m->lm_head_w, p, B, st, &lm_grid, &s->last_via));
-    if (mode & 6) return launch_proc_finish_step(s, B, is_prefill, slot0, logits_out, st);
+    if (mode & FINISH_ROWS) return launch_proc_finish_step(s, B, is_prefill, slot0, logits_out, st);
     if (sampled) return launch_sampled_finish_step(s, B, is_prefill, slot0, logits_out, st);
     if (do_finish) return launch_finish_step(s, B, is_prefill, lm_grid, slot0, st);
     return 0;

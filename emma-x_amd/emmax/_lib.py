@@ -142,6 +142,17 @@ SIGNATURES = {
     "emmax_session_clear_processing": (C.c_int, [_vp, _vp]),
     "emmax_session_processing": (C.c_int, [_vp]),
     "emmax_session_set_scores": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
+    "emmax_session_set_warpers": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "emmax_slots_set_warpers_staged": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "emmax_session_clear_warpers": (C.c_int, [_vp, _vp]),
+    "emmax_session_warpers": (C.c_int, [_vp]),
+    "emmax_session_set_token_rules": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "emmax_session_set_rule_enables": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    "emmax_slots_set_rule_enables_staged": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "emmax_session_clear_token_rules": (C.c_int, [_vp, _vp]),
+    "emmax_session_token_rules": (C.c_int, [_vp]),
+    "emmax_op_sample_ext": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int,
+                                      _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "emmax_session_set_beams": (C.c_int, [_vp, C.c_int, C.c_double, C.c_int, _vp]),
     "emmax_session_clear_beams": (C.c_int, [_vp, _vp]),
     "emmax_session_beams": (C.c_int, [_vp]),

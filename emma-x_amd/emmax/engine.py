@@ -384,6 +384,73 @@ class EmmaxEngine:
     def processing(self) -> bool:
         return self.lib.emmax_session_processing(self._session) == 1
 
+    # ---- the further warpers and the token rules (include/emmax.h: emmax_session_set_warpers / emmax_session_set_token_rules) ----------
+    @staticmethod
+    def _warper_arrays(params, n: Optional[int] = None):
+        """Host arrays (min_p, typical_p, epsilon_cutoff, eta_cutoff; 0 = off) of len(params) rows: one SamplingParams for all rows needs `n`."""
+        from .sampling import SamplingParams, _per_row
+
+        ps = _per_row(params, n if n is not None else (len(params) if isinstance(params, (list, tuple)) else 1), "params")
+        if not all(isinstance(p, SamplingParams) for p in ps):
+            raise ValueError("set_warpers: params must be SamplingParams")
+        k = len(ps)
+        return (k,) + tuple((C.c_float * k)(*[p.warpers[j] for p in ps]) for j in range(4))
+
+    def set_warpers(self, params, row0: int = 0, n: Optional[int] = None) -> None:
+        """min_p / typical_p / epsilon_cutoff / eta_cutoff of rows row0.. from their SamplingParams (turns the warpers on: the step ends in
+        the EXT finish).  set_sampling leaves them alone; clear_sampling and clear_warpers turn them off."""
+        k, mp, ty, ep, et = self._warper_arrays(params, n)
+        _lib.check(self.lib.emmax_session_set_warpers(self._session, int(row0), k, mp, ty, ep, et, _lib.current_stream()), "emmax_session_set_warpers")
+
+    def set_warpers_staged(self, params, n: Optional[int] = None) -> None:
+        """set_warpers for the requests of the next slots_prefill_staged."""
+        k, mp, ty, ep, et = self._warper_arrays(params, n)
+        _lib.check(self.lib.emmax_slots_set_warpers_staged(self._session, k, mp, ty, ep, et, _lib.current_stream()), "emmax_slots_set_warpers_staged")
+
+    def clear_warpers(self) -> None:
+        _lib.check(self.lib.emmax_session_clear_warpers(self._session, _lib.current_stream()), "emmax_session_clear_warpers")
+
+    @property
+    def warpers(self) -> bool:
+        return self.lib.emmax_session_warpers(self._session) == 1
+
+    def set_token_rules(self, params, row0: int = 0, n: Optional[int] = None, enables: bool = True) -> None:
+        """The session's rule table (sequence_bias / bad_words_ids / suppress_tokens / begin_suppress_tokens) from the LogitsProcessing of rows
+        row0.. (one per row, or one for `n` rows), and those rows' enable words.  The rows that name a kind name the same rules.  Turns
+        processing on with neutral values where it was off (the rules read the history); params without rules clear the table.
+        enables=False: the table alone (a serve sets each request's word at its admission)."""
+        from .sampling import _per_row, rule_table
+
+        ps = _per_row(params, n if n is not None else (len(params) if isinstance(params, (list, tuple)) else 1), "processing")
+        t = rule_table(ps)
+        if t is None:
+            return self.clear_token_rules()
+        off, ids, flags, bias, en = t
+        R = len(flags)
+        _lib.check(self.lib.emmax_session_set_token_rules(self._session, R, (C.c_int32 * (R + 1))(*off), (C.c_int32 * len(ids))(*ids), (C.c_int32 * R)(*flags),
+                                                          (C.c_float * R)(*bias), _lib.current_stream()), "emmax_session_set_token_rules")
+        if enables:
+            self.set_rule_enables(en, row0)
+
+    def set_rule_enables(self, words, row0: int = 0) -> None:
+        """Rows row0..: which kinds of the session's rules apply (bit 0 sequence_bias, 1 bad_words_ids, 2 suppress_tokens, 3 begin_suppress_tokens)."""
+        k = len(words)
+        _lib.check(self.lib.emmax_session_set_rule_enables(self._session, int(row0), k, (C.c_uint32 * k)(*[int(w) for w in words]), _lib.current_stream()),
+                   "emmax_session_set_rule_enables")
+
+    def set_rule_enables_staged(self, words) -> None:
+        """set_rule_enables for the requests of the next slots_prefill_staged."""
+        k = len(words)
+        _lib.check(self.lib.emmax_slots_set_rule_enables_staged(self._session, k, (C.c_uint32 * k)(*[int(w) for w in words]), _lib.current_stream()),
+                   "emmax_slots_set_rule_enables_staged")
+
+    def clear_token_rules(self) -> None:
+        _lib.check(self.lib.emmax_session_clear_token_rules(self._session, _lib.current_stream()), "emmax_session_clear_token_rules")
+
+    @property
+    def token_rules(self) -> bool:
+        return self.lib.emmax_session_token_rules(self._session) == 1
+
     def set_scores(self, scores: Optional[torch.Tensor], logits: Optional[torch.Tensor], max_new: int = 0, rows: int = 0) -> None:
         """Bind fp32 [max_new, rows, vocab] device buffers that the decode step fills with HF's `scores` (processed rows) / `logits` (raw
         rows) at each emitted token's index; `rows` must be the batch of the next prefill (the step stores row b of that batch at [t, b]).

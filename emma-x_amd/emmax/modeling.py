@@ -14,6 +14,7 @@ reference's bs=1 result for that row.
 
 from __future__ import annotations
 
+import dataclasses
 import json
 import os
 from dataclasses import dataclass
@@ -27,7 +28,7 @@ from .config import EmmaXConfig, check_decode_weight_dtype, default_norm_stats
 from .engine import EmmaxEngine
 from .policy_parser import Solver
 from .processing import BatchFeature, EmmaXImageProcessor
-from .sampling import MAX_DECODE_BATCH, BeamParams, LogitsProcessing, SamplingParams, draw_seed
+from .sampling import MAX_DECODE_BATCH, BeamParams, LogitsProcessing, SamplingParams, draw_seed, fold_bad_words
 from .prompting import PurePromptBuilder
 from .tokenizer_stub import StubTokenizer
 from .weights import load_hf_state_dict, remap_native_state_dict, synthetic_state_dict, validate_state_dict
@@ -341,6 +342,11 @@ class EmmaXForActionPrediction:
             eng.set_processing(processing, n=B)
         elif getattr(eng, "processing", False):
             eng.clear_processing()
+        ps = processing if isinstance(processing, (list, tuple)) else [processing]
+        if processing is not None and any(p.rule_enable for p in ps):   # the session's rule table and the rows' enable words
+            eng.set_token_rules(processing, n=B)
+        elif getattr(eng, "token_rules", False):
+            eng.clear_token_rules()
         if scores is not None or logits is not None:
             eng.set_scores(scores, logits, max_new, rows=B)
         elif getattr(eng, "scores_bound", False):
@@ -358,19 +364,22 @@ class EmmaXForActionPrediction:
                 raise ValueError(f"{name} must be a contiguous fp32 [max_new_tokens={max_new}, B={B}, vocab={V}] tensor, got {got}")
 
     @staticmethod
-    def _processing_args(rows, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None,
-                         min_length=None) -> Optional[LogitsProcessing]:
+    def _processing_args(rows, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None, min_length=None, sequence_bias=None,
+                         bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, eos_token_id=None) -> Optional[LogitsProcessing]:
         """HF generate's processor arguments -> the LogitsProcessing every row gets (None: HF would add no processor).  min_length L (a
         total, prompt included) becomes min_new_tokens max(min_new_tokens, L - P_max), P_max the longest prompt, as HF counts it on a
-        padded batch."""
+        padded batch.  sequence_bias / bad_words_ids / suppress_tokens / begin_suppress_tokens are checked as HF's processors check them
+        (a bad word that is the lone EOS id is dropped, as HF drops it)."""
         proc = LogitsProcessing(repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty,
                                 no_repeat_ngram_size=0 if no_repeat_ngram_size is None else no_repeat_ngram_size,
-                                min_new_tokens=0 if min_new_tokens is None else min_new_tokens)   # (validates)
+                                min_new_tokens=0 if min_new_tokens is None else min_new_tokens, sequence_bias=sequence_bias,
+                                bad_words_ids=fold_bad_words(bad_words_ids, eos_token_id), suppress_tokens=suppress_tokens,
+                                begin_suppress_tokens=begin_suppress_tokens)   # (validates)
         if min_length is not None:
             if isinstance(min_length, bool) or not isinstance(min_length, (int, np.integer)) or min_length < 0:
                 raise ValueError(f"min_length must be an integer >= 0, got {min_length}")
             m = max(int(proc.min_new_tokens), int(min_length) - max(len(r) for r in rows))
-            proc = LogitsProcessing(proc.repetition_penalty, proc.no_repeat_ngram_size, m)
+            proc = dataclasses.replace(proc, min_new_tokens=m)
         return None if proc.neutral else proc
 
     @staticmethod
@@ -381,20 +390,28 @@ class EmmaXForActionPrediction:
             eng.set_sampling(sampling, n=B)
         elif getattr(eng, "sampling", False):
             eng.clear_sampling()
+        ps = sampling if isinstance(sampling, (list, tuple)) else [sampling]
+        if sampling is not None and any(p.has_warpers for p in ps):   # min_p / typical_p / epsilon_cutoff / eta_cutoff of the rows
+            eng.set_warpers(sampling, n=B)
+        elif getattr(eng, "warpers", False):
+            eng.clear_warpers()
 
     @staticmethod
-    def _sampling_args(do_sample: bool, temperature=None, top_k=None, top_p=None, seed=None, generator=None) -> Optional[SamplingParams]:
+    def _sampling_args(do_sample: bool, temperature=None, top_k=None, top_p=None, seed=None, generator=None, min_p=None, typical_p=None,
+                       epsilon_cutoff=None, eta_cutoff=None) -> Optional[SamplingParams]:
         """HF generate's sampling arguments -> the SamplingParams every row draws with (None: greedy).  Unset values take the HF defaults
-        (temperature 1.0, top_k 50, top_p 1.0; top_k 0 = off); seed None = draw_seed(generator), so torch.manual_seed fixes a call.  Greedy
-        calls consume no torch RNG."""
+        (temperature 1.0, top_k 50, top_p 1.0; top_k 0 = off; min_p / typical_p / epsilon_cutoff / eta_cutoff off); seed None =
+        draw_seed(generator), so torch.manual_seed fixes a call.  Greedy calls consume no torch RNG and ignore the warpers, as HF does."""
         if not do_sample:
             return None
         t = 1.0 if temperature is None else float(temperature)
         if not t > 0.0:
             raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float when do_sample=True")
-        p = SamplingParams(temperature=t, top_k=50 if top_k is None else top_k, top_p=1.0 if top_p is None else top_p,
-                           seed=seed)   # (validates top_k / top_p / seed)
-        return p if seed is not None else SamplingParams(p.temperature, p.top_k, p.top_p, draw_seed(generator))
+        p = SamplingParams(temperature=t, top_k=50 if top_k is None else top_k, top_p=1.0 if top_p is None else top_p, seed=seed,
+                           min_p=0.0 if min_p is None else min_p, typical_p=1.0 if typical_p is None else typical_p,
+                           epsilon_cutoff=0.0 if epsilon_cutoff is None else epsilon_cutoff,
+                           eta_cutoff=0.0 if eta_cutoff is None else eta_cutoff)   # (validates)
+        return p if seed is not None else dataclasses.replace(p, seed=draw_seed(generator))
 
     def forward(self, input_ids=None, attention_mask=None, pixel_values=None, labels=None, inputs_embeds=None,
                 past_key_values=None, use_cache=None, output_attentions=None, output_hidden_states=None,
@@ -516,13 +533,13 @@ class EmmaXForActionPrediction:
         returns an EmmaXGenerateOutput: `sequences` (the tensor), and with output_scores / output_logits a tuple of T = max(lens) fp32
         [B, vocab] device tensors each (NaN past a row's length)."""
         rows = self._rows(input_ids, attention_mask)
-        processing = self._processing_args(rows, repetition_penalty, no_repeat_ngram_size, min_new_tokens, min_length)
+        processing = self._processing_args(rows, repetition_penalty, no_repeat_ngram_size, min_new_tokens, min_length, **self._kw_rules(kwargs))
         beams = self._beam_args(kwargs.get("num_beams"), kwargs.get("num_return_sequences"), kwargs.get("length_penalty"),
                                 kwargs.get("early_stopping"), do_sample, processing, bool(return_dict_in_generate and output_scores))
         N = self._sample_group_args(do_sample, kwargs.get("num_beams"), kwargs.get("num_return_sequences"))
         if len(rows) * N > MAX_DECODE_BATCH:
             raise ValueError(f"{len(rows)} prompts x {N} samples exceed the {MAX_DECODE_BATCH} rows of a decode batch")
-        sampling = self._sampling_args(do_sample, temperature, top_k, top_p, seed, generator)
+        sampling = self._sampling_args(do_sample, temperature, top_k, top_p, seed, generator, **self._kw_warpers(kwargs))
         max_new_tokens = self._max_new(rows, max_new_tokens, kwargs.get("max_length"), None)   # (min_length is in `processing`)
         want_sc, want_lg = bool(return_dict_in_generate and output_scores), bool(return_dict_in_generate and output_logits)
         sc = lg = None
@@ -565,7 +582,18 @@ class EmmaXForActionPrediction:
     def _kw_processing(self, rows, kwargs) -> Optional[LogitsProcessing]:
         """The processor arguments of a **kwargs that the reference forwards to HF generate."""
         return self._processing_args(rows, kwargs.get("repetition_penalty"), kwargs.get("no_repeat_ngram_size"), kwargs.get("min_new_tokens"),
-                                     kwargs.get("min_length"))
+                                     kwargs.get("min_length"), **self._kw_rules(kwargs))
+
+    def _kw_rules(self, kwargs) -> Dict[str, Any]:
+        """The token-rule arguments of a **kwargs (HF generate's names), with the EOS id HF filters bad words by."""
+        return {"sequence_bias": kwargs.get("sequence_bias"), "bad_words_ids": kwargs.get("bad_words_ids"),
+                "suppress_tokens": kwargs.get("suppress_tokens"), "begin_suppress_tokens": kwargs.get("begin_suppress_tokens"),
+                "eos_token_id": self.config.eos_token_id}
+
+    @staticmethod
+    def _kw_warpers(kwargs) -> Dict[str, Any]:
+        """The warper arguments of a **kwargs (HF generate's names)."""
+        return {k: kwargs.get(k) for k in ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")}
 
     # ------------------------------------------------------------------------------------------------------------------
     # action APIs
@@ -584,7 +612,7 @@ class EmmaXForActionPrediction:
         processing = self._kw_processing(rows, kwargs)
         beams = self._kw_beams(kwargs, processing)
         sampling = self._sampling_args(bool(kwargs.get("do_sample", False)), kwargs.get("temperature"), kwargs.get("top_k"), kwargs.get("top_p"),
-                                       kwargs.get("seed"), kwargs.get("generator"))
+                                       kwargs.get("seed"), kwargs.get("generator"), **self._kw_warpers(kwargs))
         N = self._sample_group_args(sampling is not None, kwargs.get("num_beams"), kwargs.get("num_return_sequences"))
         new_ids, lens = self.generate_ids(rows, kwargs.get("pixel_values"), kwargs.get("frames_u8"), max_new_tokens=dim, sampling=sampling,
                                           processing=processing, **self._beam_kw(beams), **self._sample_kw(N))

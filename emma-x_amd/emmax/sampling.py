@@ -14,6 +14,7 @@ import math
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple, Union
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -28,6 +29,11 @@ class SamplingParams:
     top_k: int = 50            # 0 = off
     top_p: float = 1.0         # (0, 1]; 1 = off
     seed: Optional[int] = None   # 64-bit; None = drawn from torch's default CPU generator (draw_seed)
+    # the further warpers (include/emmax.h: emmax_session_set_warpers), in HF's order behind top_p; the defaults are off
+    min_p: float = 0.0           # [0, 1]; 0 = off
+    typical_p: float = 1.0       # (0, 1]; 1 = off
+    epsilon_cutoff: float = 0.0  # [0, 1); 0 = off
+    eta_cutoff: float = 0.0      # [0, 1); 0 = off
 
     def __post_init__(self):
         t = float(self.temperature)
@@ -40,9 +46,91 @@ class SamplingParams:
             raise ValueError(f"top_p must lie in (0, 1], got {self.top_p}")
         if self.seed is not None and not (0 <= int(self.seed) <= _U64):
             raise ValueError(f"seed must be a 64-bit unsigned integer, got {self.seed}")
+        if not (0.0 <= float(self.min_p) <= 1.0):
+            raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {self.min_p}")
+        if not (0.0 < float(self.typical_p) <= 1.0):
+            raise ValueError(f"`typical_p` has to be a float > 0 and < 1 (1 = off), but is {self.typical_p}")
+        if not (0.0 <= float(self.epsilon_cutoff) < 1.0):
+            raise ValueError(f"`epsilon_cutoff` has to be a float > 0 and < 1 (0 = off), but is {self.epsilon_cutoff}")
+        if not (0.0 <= float(self.eta_cutoff) < 1.0):
+            raise ValueError(f"`eta_cutoff` has to be a float > 0 and < 1 (0 = off), but is {self.eta_cutoff}")
+
+    @property
+    def warpers(self) -> Tuple[float, float, float, float]:
+        """(min_p, typical_p, epsilon_cutoff, eta_cutoff) as the device takes them: 0 = off."""
+        t = float(self.typical_p)
+        return float(self.min_p), 0.0 if t == 1.0 else t, float(self.epsilon_cutoff), float(self.eta_cutoff)
+
+    @property
+    def has_warpers(self) -> bool:
+        return any(w != 0.0 for w in self.warpers)
 
 
 MAX_NGRAM = 32   # EMMAX_MAX_NGRAM (emma-x_amd/csrc/kernels.h): the largest no_repeat_ngram_size
+MAX_RULES, MAX_RULE_IDS, MAX_RULE_TOTAL = 512, 16, 8192   # EMMAX_MAX_RULES / _RULE_IDS / _RULE_TOTAL: the caps of a session's token-rule table
+RULE_BIAS, RULE_BAD_WORDS, RULE_SUPPRESS, RULE_BEGIN_SUPPRESS = 0, 1, 2, 3   # rule kinds = bits of a row's enable word
+
+
+def _is_id(t) -> bool:
+    return isinstance(t, (int, np.integer)) and not isinstance(t, bool) and t >= 0
+
+
+def fold_sequence_bias(sequence_bias) -> Optional[tuple]:
+    """HF's `sequence_bias` ({tuple(ids): float} or [[ids, float], ...]) -> ((ids, bias), ...), with SequenceBiasLogitsProcessor's errors."""
+    if sequence_bias is None:
+        return None
+    sb = sequence_bias
+    if isinstance(sb, tuple) and all(isinstance(e, tuple) and len(e) == 2 and isinstance(e[0], tuple) for e in sb) and len(sb) > 0:
+        sb = {e[0]: e[1] for e in sb}   # (already folded)
+    if not isinstance(sb, (dict, list)) or len(sb) == 0:
+        raise ValueError(f"`sequence_bias` has to be a non-empty dictionary, or non-empty list of lists but is {sequence_bias}.")
+    if isinstance(sb, list):
+        if any(not isinstance(e, (list, tuple)) or len(e) != 2 or not isinstance(e[0], list) or len(e[0]) == 0 or not all(_is_id(t) for t in e[0])
+               or not isinstance(e[1], float) for e in sb):
+            raise ValueError(f"Each element in `sequence_bias` has to be a non-empty list of lists of positive integers and float, but is {sequence_bias}.")
+        sb = {tuple(e[0]): e[1] for e in sb}
+    if any(not isinstance(k, tuple) for k in sb):
+        raise ValueError(f"`sequence_bias` has to be a dict with tuples as keys, but is {sequence_bias}.")
+    if any(len(k) == 0 or not all(_is_id(t) for t in k) for k in sb):
+        raise ValueError(f"Each key in `sequence_bias` has to be a non-empty tuple of positive integers, but is {sequence_bias}.")
+    if any(not isinstance(b, float) for b in sb.values()):
+        raise ValueError(f"`sequence_bias` has to be a dict with floats as values, but is {sequence_bias}.")
+    if any(math.isnan(b) for b in sb.values()):
+        raise ValueError(f"`sequence_bias` values must not be NaN, but is {sequence_bias}.")
+    return tuple((tuple(int(t) for t in k), float(b)) for k, b in sb.items())
+
+
+def fold_bad_words(bad_words_ids, eos_token_id=None) -> Optional[tuple]:
+    """HF's `bad_words_ids` -> (ids, ...), with NoBadWordsLogitsProcessor's errors; a lone EOS id is dropped as HF drops it."""
+    if bad_words_ids is None:
+        return None
+    bw = [list(w) if isinstance(w, tuple) else w for w in bad_words_ids] if isinstance(bad_words_ids, tuple) else bad_words_ids
+    if not isinstance(bw, list) or len(bw) == 0:
+        raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bad_words_ids}.")
+    if any(not isinstance(w, list) for w in bw):
+        raise ValueError(f"`bad_words_ids` has to be a list of lists, but is {bad_words_ids}.")
+    if any(not all(_is_id(t) for t in w) for w in bw):
+        raise ValueError(f"Each list in `bad_words_ids` has to be a list of positive integers, but is {bad_words_ids}.")
+    if any(len(w) == 0 for w in bw):
+        raise ValueError(f"Each list in `bad_words_ids` has to be a non-empty list of positive integers, but is {bad_words_ids}.")
+    eos = [] if eos_token_id is None else [int(e) for e in (eos_token_id if isinstance(eos_token_id, (list, tuple)) else [eos_token_id])]
+    out, seen = [], set()
+    for w in bw:
+        t = tuple(int(x) for x in w)
+        if (len(t) == 1 and t[0] in eos) or t in seen:
+            continue
+        seen.add(t)
+        out.append(t)
+    return tuple(out) if out else None
+
+
+def fold_suppress(tokens, name: str) -> Optional[tuple]:
+    """HF's `suppress_tokens` / `begin_suppress_tokens` -> (id, ...)."""
+    if tokens is None:
+        return None
+    if not isinstance(tokens, (list, tuple)) or len(tokens) == 0 or not all(_is_id(t) for t in tokens):
+        raise ValueError(f"`{name}` has to be a non-empty list of non-negative integers, but is {tokens}.")
+    return tuple(dict.fromkeys(int(t) for t in tokens))
 
 
 @dataclass(frozen=True)
@@ -52,8 +140,22 @@ class LogitsProcessing:
     repetition_penalty: float = 1.0   # finite, > 0; 1 = off
     no_repeat_ngram_size: int = 0     # 0 = off, <= MAX_NGRAM
     min_new_tokens: int = 0           # EOS is banned while fewer tokens were emitted
+    # the token rules (include/emmax.h: emmax_session_set_token_rules), folded to tuples (fold_*; HF's spellings are accepted and checked
+    # as HF checks them); None = off.  A session holds one table: the rows that name a kind name the same rules
+    sequence_bias: Optional[tuple] = None           # ((ids, bias), ...): bias added to ids[-1] when the history ends with ids[:-1]
+    bad_words_ids: Optional[tuple] = None           # (ids, ...): the same match with -inf
+    suppress_tokens: Optional[tuple] = None         # (id, ...): -inf at every step
+    begin_suppress_tokens: Optional[tuple] = None   # (id, ...): -inf for the first generated token only
 
     def __post_init__(self):
+        object.__setattr__(self, "sequence_bias", fold_sequence_bias(self.sequence_bias))
+        object.__setattr__(self, "bad_words_ids", fold_bad_words(self.bad_words_ids))
+        object.__setattr__(self, "suppress_tokens", fold_suppress(self.suppress_tokens, "suppress_tokens"))
+        object.__setattr__(self, "begin_suppress_tokens", fold_suppress(self.begin_suppress_tokens, "begin_suppress_tokens"))
+        rules = self.rules
+        if len(rules) > MAX_RULES or any(len(ids) > MAX_RULE_IDS for _, ids, _ in rules) or sum(len(ids) for _, ids, _ in rules) > MAX_RULE_TOTAL:
+            raise ValueError(f"token rules: at most {MAX_RULES} rules of at most {MAX_RULE_IDS} ids, {MAX_RULE_TOTAL} ids in all "
+                             f"(got {len(rules)} rules, {sum(len(ids) for _, ids, _ in rules)} ids)")
         p = float(self.repetition_penalty)
         if not math.isfinite(p) or not p > 0.0:
             raise ValueError(f"repetition_penalty must be a finite float > 0, got {self.repetition_penalty}")
@@ -67,7 +169,45 @@ class LogitsProcessing:
     @property
     def neutral(self) -> bool:
         """No processor would change a row (HF adds none for these values)."""
-        return float(self.repetition_penalty) == 1.0 and int(self.no_repeat_ngram_size) == 0 and int(self.min_new_tokens) == 0
+        return float(self.repetition_penalty) == 1.0 and int(self.no_repeat_ngram_size) == 0 and int(self.min_new_tokens) == 0 and not self.rules
+
+    @property
+    def rules(self) -> list:
+        """The rows of the device table, [(kind, ids, bias)]: sequence_bias with its 1-id rules first (HF adds those first), then
+        bad_words_ids, suppress_tokens, begin_suppress_tokens."""
+        sb = list(self.sequence_bias or ())
+        out = [(RULE_BIAS, ids, b) for ids, b in sb if len(ids) == 1] + [(RULE_BIAS, ids, b) for ids, b in sb if len(ids) > 1]
+        out += [(RULE_BAD_WORDS, ids, 0.0) for ids in self.bad_words_ids or ()]
+        out += [(RULE_SUPPRESS, (t,), 0.0) for t in self.suppress_tokens or ()]
+        out += [(RULE_BEGIN_SUPPRESS, (t,), 0.0) for t in self.begin_suppress_tokens or ()]
+        return out
+
+    @property
+    def rule_enable(self) -> int:
+        """The row's enable word: bit k set iff the row names rules of kind k."""
+        return sum(1 << k for k, f in enumerate((self.sequence_bias, self.bad_words_ids, self.suppress_tokens, self.begin_suppress_tokens)) if f)
+
+
+def rule_table(params: Sequence[LogitsProcessing]):
+    """The one table of a session whose rows have `params`, and each row's enable word: (offsets, ids, flags, bias, enables), or None when
+    no row names a rule.  The rows that name a kind must name the same rules (a session holds one table)."""
+    fields = ("sequence_bias", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens")
+    chosen = {}
+    for p in params:
+        for f in fields:
+            v = getattr(p, f)
+            if v and chosen.setdefault(f, v) != v:
+                raise ValueError(f"rows of one session name different `{f}`: a session holds one rule table (rows opt in or out of it)")
+    if not chosen:
+        return None
+    rules = LogitsProcessing(**chosen).rules
+    off, ids, flags, bias = [0], [], [], []
+    for kind, r, b in rules:
+        ids += list(r)
+        off.append(len(ids))
+        flags.append(kind | (4 if kind == RULE_BEGIN_SUPPRESS else 0))
+        bias.append(float(b))
+    return off, ids, flags, bias, [p.rule_enable for p in params]
 
 
 MAX_BEAMS = 8   # EMMAX_MAX_BEAMS (include/emmax.h)

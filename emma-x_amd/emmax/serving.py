@@ -14,6 +14,7 @@ The scheduler is host logic only (testable without a GPU against a fake engine);
 """
 from __future__ import annotations
 
+import dataclasses
 import time
 from dataclasses import dataclass, field
 from typing import Any, Callable, Deque, Dict, List, Optional, Sequence
@@ -109,6 +110,8 @@ class SlotScheduler:
         self.overlapped_admissions = 0
         self._sampling = False                       # some request of the current run samples (run)
         self._processing = False                     # some request of the current run has logits processing (run)
+        self._warpers = False                        # ... min_p / typical_p / epsilon_cutoff / eta_cutoff (run)
+        self._rules = False                          # ... token rules (run)
         # a staged batch is at most max(stage_batch, free slots) <= n_slots requests: the session needs that many staging rows
         # (they cost KV pages, so a session only has them when a scheduler asks: engine.ensure_stage_rows re-creates it if needed)
         if self.overlap and hasattr(engine, "ensure_stage_rows"):
@@ -143,7 +146,7 @@ class SlotScheduler:
         for r in reqs:
             p = r.sampling if r.sampling is not None else SamplingParams(temperature=0.0, top_k=0, top_p=1.0, seed=0)
             if p.seed is None:
-                p = SamplingParams(p.temperature, p.top_k, p.top_p, draw_seed())
+                p = dataclasses.replace(p, seed=draw_seed())
                 r.sampling = p   # the seed the request was served with
             params.append(p)
             seeds.append(p.seed)
@@ -161,6 +164,12 @@ class SlotScheduler:
             self.engine.set_processing_staged(params)
         else:
             self.engine.set_processing(params, row0=row0)
+        if self._rules:   # which kinds of the run's rule table each request takes
+            words = [p.rule_enable for p in params]
+            if staged:
+                self.engine.set_rule_enables_staged(words)
+            else:
+                self.engine.set_rule_enables(words, row0=row0)
 
     def _set_sampling(self, reqs, row0: int = 0, staged: bool = False) -> None:
         """A serve where some request samples: every prefill is preceded by its rows' parameters.  Greedy-only serves call nothing here."""
@@ -171,6 +180,11 @@ class SlotScheduler:
             self.engine.set_sampling_staged(params, seeds, subs)
         else:
             self.engine.set_sampling(params, seeds, subs, row0=row0)
+        if self._warpers:   # min_p / typical_p / epsilon_cutoff / eta_cutoff per request (off for the requests without them)
+            if staged:
+                self.engine.set_warpers_staged(params)
+            else:
+                self.engine.set_warpers(params, row0=row0)
 
     @staticmethod
     def _demand(req) -> int:
@@ -314,7 +328,13 @@ class SlotScheduler:
         samples, the session samples for the whole run (greedy requests at temperature 0: their greedy ids) and is greedy again after it.  Logits processing likewise (requests without it get neutral processors)."""
         self._sampling = any(r.sampling is not None for r, _ in self.queue)
         self._processing = any(getattr(r, "processing", None) is not None for r, _ in self.queue)
+        self._warpers = any(r.sampling is not None and getattr(r.sampling, "has_warpers", False) for r, _ in self.queue)
+        with_rules = [r.processing for r, _ in self.queue if getattr(r, "processing", None) is not None and getattr(r.processing, "rule_enable", 0)]
+        self._rules = bool(with_rules)
         try:
+            if self._rules:   # one rule table for the run (the requests that name a kind name the same rules); every row starts opted out
+                self.engine.set_token_rules(with_rules, enables=False)
+                self.engine.set_rule_enables([0] * self.n_slots)
             return self._run()
         finally:
             if self._processing:

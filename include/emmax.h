@@ -343,6 +343,79 @@ int emmax_session_clear_processing(emmax_session* s, emmax_stream stream);
 int emmax_session_processing(const emmax_session* s);
 int emmax_session_set_scores(emmax_session* s, float* scores_dev, float* logits_dev, int max_new, emmax_stream stream);
 
+/* ---- the further warpers and the token rules inside the decode step (new symbols, same ABI) --------------------------------------------
+ * The rest of that family of transformers 5.15 (generation/logits_process.py; order of _get_logits_processor), per row.  They run in the
+ * EXT form of the processing finish: its own instantiation of the kernel, launched only while warpers or token rules are set -- a
+ * session that sets neither launches exactly what it launched before.  Same launch count; the step graph is keyed on the two being on or
+ * off; values, the rule table and the enable words are device words behind stable pointers: changing them re-captures nothing.
+ *
+ * WARPERS, after temperature, top_k and top_p, in this order, on sampled rows (temperature 0 ignores them as it ignores top_k / top_p).
+ * K = the set kept so far, W_i = floor(exp(z_i - max z) 2^32) the integer masses of ABI 6 (max z = the processed row's maximum over T:
+ * W = 2^32 there), S = sum_{i in K} W_i as a 64-bit integer, recomputed before each warper.  -inf and NaN entries are never in K.
+ *   min_p m in (0, 1]      keep i iff W_i >= floor(fp32(m) 2^32) (an integer comparison; the maxima always stay).  0 = off.
+ *   typical_p t in (0, 1)  lnZ = logf(fp32(S) 2^-32), lp_i = (z_i - max z) - lnZ, p_i = fp32(W_i) * (1 / fp32(S)), all fp32;
+ *                          H = -sum_{i in K} p_i lp_i, one fp32 reduction in the order of the row's log-sum-exp (a lane's entries in register
+ *                          order with separately rounded products and sums, xor butterfly 32..1, the 16 waves in order);
+ *                          d_i = |(-lp_i) - H| (fp32).  Keep i iff sum_{j in K, d_j < d_i} W_j < fp64(fp32(t)) fp64(S) (one rounding), or that
+ *                          sum is 0: the shortest prefix in ascending d whose mass reaches t S, ties kept -- one more radix walk, over the
+ *                          order-preserving key of d.  As in HF the row's maximum may go.  0 or 1 = off.
+ *   epsilon_cutoff e in (0, 1)  keep i iff fp64(W_i) >= fp64(fp32(e)) fp64(S) (one rounding), or z_i = the largest kept z.  0 = off.
+ *   eta_cutoff e in (0, 1)      the same with e' = fminf(e, sqrtf(e) * expf(-H)) (fp32, H as above over the set kept so far).  0 = off.
+ * scores[t][b] keeps its meaning (z on the final kept set, -inf elsewhere), log-probabilities theirs (raw logits, T = 1, unfiltered).  No
+ * float atomics; the same inputs give the same bits; the kept set does not depend on the row's place in the batch or on B.
+ *
+ * TOKEN RULES, processors on the row's history H (ABI 8's: prompt ids, then emitted ids; L ids).  One table per session: n rules, rule r =
+ * ids[off[r] .. off[r + 1]) = (s_1 .. s_m), flags[r] (bits 0-1 the kind: 0 sequence_bias, 1 bad_words_ids, 2 suppress_tokens, 3
+ * begin_suppress_tokens; bit 2: the rule fires for the first generated token only, n_out == 0), bias[r] (kind 0).  Caps: 512 rules
+ * (EMMAX_MAX_RULES), 16 ids per rule, 8192 ids in all.  A rule applies to a row iff bit `kind` of the row's enable word is set.  It FIRES
+ * iff m == 1, or m <= L (HF skips a sequence longer than the context) and H ends with s_1 .. s_{m-1}; its target is s_m (ignored when >= V).
+ *   kind 0   first of all processors: x[s_m] += B, B = the fp32 sum, from 0 in rule order, of the biases of the fired rules with that target
+ *            (HF builds the bias row, then adds it once; list 1-id rules first to reproduce HF's bits).
+ *   kinds 1-3  x[s_m] = -inf, with the n-gram ban (after the repetition penalty).
+ * A row with no finite entry left emits pad_id and is done.  The rules need the history: setting a table turns processing on with neutral
+ * values (penalty 1, ngram 0, min_new 0) where it was off, and clearing the table turns that off again.
+ *   emmax_session_set_warpers            rows row0 .. row0 + n - 1, host arrays of n values (0 = off), checked here: 0 <= min_p <= 1,
+ *                                        0 <= typical_p <= 1, 0 <= epsilon_cutoff < 1, 0 <= eta_cutoff < 1 -- else EMMAX_ERR_INVALID and nothing
+ *                                        changes.  Turns the warpers on.  emmax_session_set_sampling leaves them as they were;
+ *                                        emmax_session_clear_sampling and emmax_session_clear_warpers zero every row's and turn them off.
+ *   emmax_slots_set_warpers_staged       the same for the n requests of the next emmax_slots_prefill_staged.
+ *   emmax_session_set_token_rules        the table (host arrays), checked here: counts within the caps, offsets rising from 0, ids >= 0, flags
+ *                                        0..7, no NaN bias -- else EMMAX_ERR_INVALID and nothing changes.  Synchronises the stream.  The first
+ *                                        table enables every kind on every row.  emmax_session_set_processing leaves table and words alone;
+ *                                        emmax_session_clear_processing and emmax_session_clear_token_rules turn the rules off.
+ *   emmax_session_set_rule_enables       rows row0 .. row0 + n - 1: enable words 0..15.  EMMAX_ERR_STATE before a table is set.
+ *   emmax_slots_set_rule_enables_staged  the same for the n requests of the next emmax_slots_prefill_staged.
+ *   emmax_slots_commit / emmax_slots_fork move a request's warper values and enable word with the rest of its state (a fork's followers
+ *                                        take the source's).
+ *   emmax_session_warpers / emmax_session_token_rules   1 on, 0 off, -1 null session.
+ * Beams: the setters return EMMAX_ERR_STATE while beams are on, and emmax_session_set_beams while either is on.
+ *
+ * emmax_op_sample_ext is that finish on its own: emmax_op_sample's rows and sampling arrays (n_out_dev = the Philox step = the generation
+ * index the rules and min_new see), the four warper arrays (all or none; NULL = off), the processor arrays of ABI 8 with the rows' complete
+ * histories hist_dev [B][max_hist] + hist_len_dev (all or none), a rule table in device memory (n_rules = 0: none; needs the histories) with
+ * the rows' enable words.  Out: the token (pad_id for a row with no finite entry left after processing, -1 for an all-NaN row without
+ * processing), the log-probability of ABI 6 and, when scores_out_dev is not NULL, the row's HF scores [B][V].  Array values are the caller's to
+ * check. */
+int emmax_session_set_warpers(emmax_session* s, int row0, int n, const float* min_p_host, const float* typical_p_host, const float* epsilon_cutoff_host,
+                              const float* eta_cutoff_host, emmax_stream stream);
+int emmax_slots_set_warpers_staged(emmax_session* s, int n, const float* min_p_host, const float* typical_p_host, const float* epsilon_cutoff_host,
+                                   const float* eta_cutoff_host, emmax_stream stream);
+int emmax_session_clear_warpers(emmax_session* s, emmax_stream stream);
+int emmax_session_warpers(const emmax_session* s);
+int emmax_session_set_token_rules(emmax_session* s, int n_rules, const int32_t* offsets_host, const int32_t* ids_host, const int32_t* flags_host,
+                                  const float* bias_host, emmax_stream stream);
+int emmax_session_set_rule_enables(emmax_session* s, int row0, int n, const uint32_t* enable_host, emmax_stream stream);
+int emmax_slots_set_rule_enables_staged(emmax_session* s, int n, const uint32_t* enable_host, emmax_stream stream);
+int emmax_session_clear_token_rules(emmax_session* s, emmax_stream stream);
+int emmax_session_token_rules(const emmax_session* s);
+int emmax_op_sample_ext(const float* logits_dev, int ld, int B, int V, const float* temperature_dev, const int32_t* top_k_dev, const float* top_p_dev,
+                        const uint64_t* seed_dev, const uint32_t* subseq_dev, const int32_t* n_out_dev, const float* min_p_dev, const float* typical_p_dev,
+                        const float* epsilon_cutoff_dev, const float* eta_cutoff_dev, const float* penalty_dev, const int32_t* ngram_dev,
+                        const int32_t* min_new_dev, const int32_t* hist_dev, const int32_t* hist_len_dev, int max_hist, int n_rules,
+                        const int32_t* rule_off_dev, const int32_t* rule_ids_dev, const int32_t* rule_flags_dev, const float* rule_bias_dev,
+                        const uint32_t* rule_enable_dev, int eos_id, int pad_id, int32_t* tok_out_dev, float* logprob_out_dev, float* scores_out_dev,
+                        emmax_stream stream);
+
 /* ---- beam search inside the decode step (ABI 9) ----------------------------------------------------------------------
  * The semantics of transformers 5.15's GenerationMixin._beam_search (_get_top_k_continuations, _get_running_beams_for_next_iteration,
  * _update_finished_beams, _check_early_stop_heuristic, _beam_search_has_unfinished_sequences) for do_sample = False, one EOS id and no

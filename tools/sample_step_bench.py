@@ -8,6 +8,8 @@ greedy step, at the shapes of the headline bench (Emma-X-7B synthetic weights, 5
   pgreedy  repetition penalty 1.1 and no_repeat_ngram_size 3, greedy (the processing finish)
   phf      the same with the HF-default draw
   pscores  pgreedy with output_scores: the processed rows stored at every step ([new tokens, B, vocab] fp32)
+  minp / typ / eps / eta   hf with min_p 0.05 / typical_p 0.9 / epsilon_cutoff 3e-4 / eta_cutoff 1e-3 (the EXT finish)
+  warp4    hf with all four;  rules256   hf with a table of 256 rules (the 256 action ids suppressed)
 
 --beams K1,K2,..  (ABI 9) instead: one K-beam group (`generate(num_beams=K)`: G = 1, K rows on shared KV pages) against K independent greedy
 rows of the same prompt -- ms per step, time to the first token (prefill + first step: the beam group prefills ONE row) and end-to-end
@@ -36,6 +38,13 @@ PROC = LogitsProcessing(1.1, 3, 0)
 MODES = {"greedy": (None, None, False), "t0": (SamplingParams(0.0, 0, 1.0, seed=1), None, False), "hf": (HF, None, False),
          "topp": (SamplingParams(1.0, 0, 0.9, seed=1), None, False), "pgreedy": (None, PROC, False), "phf": (HF, PROC, False),
          "pscores": (None, PROC, True)}
+if "min_p" in SamplingParams.__dataclass_fields__:
+    import dataclasses
+
+    MODES.update({"minp": (dataclasses.replace(HF, min_p=0.05), None, False), "typ": (dataclasses.replace(HF, typical_p=0.9), None, False),
+                  "eps": (dataclasses.replace(HF, epsilon_cutoff=3e-4), None, False), "eta": (dataclasses.replace(HF, eta_cutoff=1e-3), None, False),
+                  "warp4": (dataclasses.replace(HF, min_p=0.05, typical_p=0.9, epsilon_cutoff=3e-4, eta_cutoff=1e-3), None, False),
+                  "rules256": (HF, LogitsProcessing(suppress_tokens=list(range(31744, 32000))), False)})
 
 
 def main():
