@@ -827,13 +827,13 @@ bool kms_takes(const ProjShape& s, int B, int nb, ProjGeom* g) {
 }  // namespace
 
 // What this file takes (the km copy of the matrix: launch_repack_km; fp8: decode_mfma.hip's e4m3 tiles of the permuted rows; MXFP4 tiles).
-// 17-64 rows: decode_kmp.hip's answer (bf16 / fp8).  Exact numerics: 1-8 rows (two terms per batch row in the sixteen MFMA columns), bf16.
+// 17-64 rows: decode_kmp.hip's answer (bf16 / fp8; MXFP4 under ProjShape::mx4_wide).  Exact numerics: 1-8 rows (two terms per batch row in the sixteen MFMA columns), bf16.
 bool decode_km_takes(const ProjShape& s, int B, ProjGeom* out) {
     ProjGeom g = {};
     bool ok = false;
     const bool kfits = s.K % (KM_WAVES * 32) == 0 && s.K <= KM_WAVES * KM_STEPS * 32;
     if (B < 1 || B > EMMAX_MAX_DECODE_BATCH || s.mode < GEMV_QKV || s.mode > GEMV_PLAIN) return false;
-    if (B > 16) return s.wfmt != PW_MX4 && decode_kmp_takes(s, B, out);   // two batch tiles: decode_kmp.hip (MXFP4 tiles: this file's kernels only)
+    if (B > 16) return decode_kmp_takes(s, B, out);   // two batch tiles: decode_kmp.hip (MXFP4 tiles: only when the shape says wide, else this file's kernels only)
     if (s.attn_part && (s.mode != GEMV_RESID || s.K != s.Hq * 128)) return false;
     if (s.exact) {
         if (B > 8 || s.wfmt != PW_BF16 || s.mode == GEMV_PLAIN) return false;

@@ -15,7 +15,8 @@
 // and a scale per row: a load step is then two fragments, converted to bf16 in registers, and the lookahead counts twice the phases
 // for the same bytes in flight), same fused prologues / epilogues, same arithmetic (y = rstd * W (x .* g), the eight K-slice partial
 // tiles meet in LDS at the end of the block).  The K slices of the waves are whole load steps and may differ by one (the fp8 down
-// projection: 172 steps over 8 waves).
+// projection: 172 steps over 8 waves).  MXFP4 tiles (decode_km.hip's, 16 rows x 128 k and a scale dword per row): a load step is one whole phase,
+// four fragments widened in registers (WF below; served for models that froze the tuning switch mx4_wide).
 #include <cstdlib>
 #include <type_traits>
 
@@ -42,8 +43,19 @@ constexpr int KP_RPL = KP_ROWS * KP_PH * 4 / 64;   // 16-byte chunks per lane an
 #define KP_HALF_SYNC 1
 #endif
 
-// phases of weights in flight (fp8 tiles carry 64 k per KiB: twice the phases for the same bytes)
-template <int TMAX, bool FP8> struct KpLook { static constexpr int L = (TMAX >= 4 ? 1 : TMAX >= 2 ? 2 : 4) * (FP8 ? 2 : 1); };
+enum { W_BF16 = 0, W_FP8 = 1, W_MX4 = 2 };   // weight format of a tile stream (decode_km.hip's)
+
+// phases of weights in flight (fp8 tiles carry 64 k per KiB: twice the phases for the same bytes).  MXFP4 tiles carry 128 k: a phase is ONE KiB per
+// tile, and every ring register has a scale dword beside it -- 18 KiB per wave (six tiles x 3 phases, three x 6) where the bf16 form holds 24: with
+// 24 KiB + 24 scale dwords the six-tile qkv and gate/up forms spilled; one tile: 16; never more than the kernel has phases -- the whole slice of
+// a wave is then requested up front and nothing is refilled
+template <int TMAX, int WF, int NPH> struct KpLook {
+    static constexpr int BASE = WF == W_MX4 ? (TMAX >= 4 ? 3 : TMAX >= 2 ? 6 : 16) : (TMAX >= 4 ? 1 : TMAX >= 2 ? 2 : 4) * (WF == W_FP8 ? 2 : 1);
+    static constexpr int L = (WF == W_MX4 && BASE > NPH) ? NPH : BASE;
+};
+// the MX4 form's scale dwords, one beside each register of the weight ring (nothing in the other forms)
+template <bool ON, int N> struct KpScales {};
+template <int N> struct KpScales<true, N> { uint32_t s[N]; };
 
 // activation row sets in flight (registers): the eleven-phase down projection keeps two
 template <int TMAX, int NPH> struct KpRowSets { static constexpr int N = (NPH > 4 && TMAX == 1) ? KP_XD_LONG : 1; };
@@ -51,14 +63,18 @@ template <int TMAX, int NPH> struct KpRowSets { static constexpr int N = (NPH > 
 // NH = 2 (round 6, batches of 33-64 rows): the block's eight waves are two HALVES of four -- half h stages rows 32 h .. 32 h + 31 and owns their two batch
 // tiles, its four waves split K four ways (twice the phases per wave); both halves stream the block's weight tiles (the second request is an L2 hit: HBM
 // reads them once), so the registers of a wave are those of the 32-row kernel.  Epilogue slots (tile, half) are dealt to the eight waves in passes.
-template <int MODE, bool NORM, bool R32, int TMAX, int NPH, bool FP8, int NH = 1>
+// WF (weight format of the tiles): W_BF16, W_FP8, or W_MX4 -- decode_km.hip's MXFP4 tiles (launch_quant_mx4): 16 rows x 128 k per KiB, lane l = row l & 15,
+// dword j of its 16 bytes = the 8 k of group l >> 4 of the tile's j-th 32-wide step; the scale stream one dword of four e8m0 codes per (tile, row).  A
+// load step is then exactly one phase: one tile register and its scale dword per (phase, tile), four conversions (exact in bf16) and eight MFMAs per KiB.
+template <int MODE, bool NORM, bool R32, int TMAX, int NPH, int WF, int NH = 1>
 __global__ __launch_bounds__(KP_THREADS, 2) void emmax_decode_kmp_kernel(GemvParams p) {
+    constexpr bool FP8 = WF == W_FP8, MX4 = WF == W_MX4;
     static_assert(NH == 1 || (NH == 2 && MODE != GEMV_LMHEAD), "halves: 1 or 2; the lm-head of 33-64 rows runs as two launches");
     constexpr int KW = KP_WAVES / NH;          // K slices = waves of a half
     constexpr int KP_NPH = NPH;
     extern __shared__ __attribute__((aligned(16))) unsigned char kp_smem[];
-    constexpr int LOOK = KpLook<TMAX, FP8>::L;
-    constexpr int KS = FP8 ? 64 : 32;                  // elements per load step (one 1 KiB tile)
+    constexpr int LOOK = KpLook<TMAX, WF, NPH>::L;
+    constexpr int KS = MX4 ? 128 : FP8 ? 64 : 32;      // elements per load step (one 1 KiB tile)
     constexpr int PHS = KP_PH * 32 / KS;               // load steps per phase
     constexpr int RING = TMAX * PHS * LOOK;            // weight registers (16-byte loads of 1 KiB tiles) of a wave
     constexpr int WREG = TMAX * 2048 > KP_ROWS * KP_XP ? TMAX * 2048 : KP_ROWS * KP_XP;   // a wave's LDS region: window, later its partial tiles
@@ -101,10 +117,11 @@ __global__ __launch_bounds__(KP_THREADS, 2) void emmax_decode_kmp_kernel(GemvPar
     }
 
     // ---- weight stream: buffer loads, the (tile, step) offset in an SGPR, the lane's 16 bytes in the VGPR offset ----
-    const unsigned w_bytes = (unsigned)((size_t)p.n_groups * 16 * (size_t)K * (FP8 ? 1 : 2));
+    const unsigned w_bytes = MX4 ? (unsigned)((size_t)p.n_groups * 8 * (size_t)K) : (unsigned)((size_t)p.n_groups * 16 * (size_t)K * (FP8 ? 1 : 2));
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (int)w_bytes, 0x00020000);
     const unsigned voff = (unsigned)lane * 16u;
     u32x4_t w[RING];
+    KpScales<MX4, RING> q4;   // MX4: the scale dword of each ring register (the rows' lanes: 4 bytes at 4 (lane & 15) of the tile's 64)
     // unit (ph, tl, s) lives in register ((ph % LOOK) * TMAX + tl) * PHS + s; past the block's tiles / the slice: out of range = zeros, no traffic
     // (measured and removed, profiles/r06_kmp_rot_ab.txt: blocks walking their phases in ROTATED order -- so that the CUs of an XCD would not ask L2 for the same
     // row chunks at the same time -- is slower, qkv 23.0 -> 26.8 us, gate/up 33.6 -> 36.3 at 32 rows: the simultaneous requests for the same rows are what L2 merges)
@@ -115,6 +132,12 @@ __global__ __launch_bounds__(KP_THREADS, 2) void emmax_decode_kmp_kernel(GemvPar
         // aux 2 = nt (streamed once); NH = 2: the other half of the block requests the same tile -- default policy, so that the second request hits L2
         // (with nt both went to HBM: gate/up at 64 rows 61.8 us = twice the 32-row launch)
         w[((ph % LOOK) * TMAX + tl) * PHS + s] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, voff, so, NH == 2 ? KP_AUX2 : 2));
+        if constexpr (MX4) {   // the tile's scale dwords, masked the same way: 64 B per tile in the tiles' order
+            const unsigned s_bytes = w_bytes / 16u;
+            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w4_scales, 0, (int)s_bytes, 0x00020000);
+            const unsigned ss = ((unsigned)(((t_lo + tl) * KT + k_lo + ks) * 64) & (unsigned)ok) | (s_bytes & (unsigned)~ok);
+            q4.s[((ph % LOOK) * TMAX + tl) * PHS + s] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(srsrc, (unsigned)c16 * 4u, ss, NH == 2 ? KP_AUX2 : 2);
+        }
     };
 
     // ---- activations of a phase: lane l holds chunk l & 15 (8 elements) of rows (l >> 4) + 4 j of the phase's 128-element slice ----
@@ -199,7 +222,7 @@ __global__ __launch_bounds__(KP_THREADS, 2) void emmax_decode_kmp_kernel(GemvPar
            so that the second request finds the line in flight or present in L2 instead of reading HBM again (PMC: gate/up  \
            347 -> 201 MB per launch, 55 -> 44 us; qkv 183 -> 107 MB, 37 -> 35 us).  Not for the one-tile o-proj (14.8 -> 16.0 us) \
            nor with fp8 tiles (half the bytes: the launch is bound by the L2 -> CU path either way, the barrier only costs) */ \
-        if constexpr (NH == 2 && KP_HALF_SYNC && !FP8 && TMAX >= 3) __syncthreads();                                    \
+        if constexpr (NH == 2 && KP_HALF_SYNC && WF == W_BF16 && TMAX >= 3) __syncthreads();                           \
         /* the phase's fragments: batch tile nt, k-step s: row 16 nt + c16, chunk 4 s + g4 (wave-private window: only this  \
            wave's own LDS writes have to have landed, no barrier) */                                                    \
         bf16x8_t xf[KP_PH][2];                                                                                          \
@@ -220,7 +243,14 @@ __global__ __launch_bounds__(KP_THREADS, 2) void emmax_decode_kmp_kernel(GemvPar
                 _Pragma("unroll") for (int s = 0; s < PHS; ++s) {                                                       \
                     constexpr int slot0 = (ph % LOOK) * TMAX * PHS;                                                     \
                     const u32x4_t wv = w[slot0 + tl * PHS + s];                                                         \
-                    if constexpr (FP8) { /* a 16 x 64 e4m3 tile: two bf16 fragments */                                  \
+                    if constexpr (MX4) { /* a 16 x 128 MXFP4 tile = the phase: four bf16 fragments, scale code j each */ \
+                        const uint32_t sc = q4.s[slot0 + tl * PHS + s];                                                 \
+                        _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                 \
+                            const bf16x8_t wq = mx4x8_to_bf16x8(wv[j], e8m0_scale(sc, j));                              \
+                            acc[tl][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wq, xf[j][0], acc[tl][0], 0, 0, 0);    \
+                            acc[tl][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wq, xf[j][1], acc[tl][1], 0, 0, 0);    \
+                        }                                                                                               \
+                    } else if constexpr (FP8) { /* a 16 x 64 e4m3 tile: two bf16 fragments */                           \
                         const bf16x8_t wlo = fp8x8_to_bf16x8(wv[0], wv[1]), whi = fp8x8_to_bf16x8(wv[2], wv[3]);        \
                         acc[tl][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlo, xf[2 * s][0], acc[tl][0], 0, 0, 0);   \
                         acc[tl][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlo, xf[2 * s][1], acc[tl][1], 0, 0, 0);   \
@@ -231,7 +261,8 @@ __global__ __launch_bounds__(KP_THREADS, 2) void emmax_decode_kmp_kernel(GemvPar
                         acc[tl][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xf[s][0], acc[tl][0], 0, 0, 0);        \
                         acc[tl][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xf[s][1], acc[tl][1], 0, 0, 0);        \
                     }                                                                                                   \
-                    issue_w(ph + LOOK, tl, s); /* the register's unit LOOK phases ahead */                              \
+                    /* the register's unit LOOK phases ahead (MX4: not past the last phase -- nothing to refill) */     \
+                    if constexpr (!MX4 || ph + LOOK < KP_NPH) issue_w(ph + LOOK, tl, s);                                \
                 }                                                                                                       \
             }                                                                                                           \
         }                                                                                                               \
@@ -358,9 +389,9 @@ template <int TMAX> constexpr size_t kp_smem_bytes() {
     return (size_t)KP_WAVES * (TMAX * 2048 > KP_ROWS * KP_XP ? TMAX * 2048 : KP_ROWS * KP_XP) + KP_WAVES * 32 * 4;
 }
 
-template <int MODE, bool NORM, bool R32, int TMAX, int NPH, bool FP8, int NH = 1>
+template <int MODE, bool NORM, bool R32, int TMAX, int NPH, int WF, int NH = 1>
 int kp_launch_r(const GemvParams& p, int grid, hipStream_t stream) {
-    auto kern = emmax_decode_kmp_kernel<MODE, NORM, R32, TMAX, NPH, FP8, NH>;
+    auto kern = emmax_decode_kmp_kernel<MODE, NORM, R32, TMAX, NPH, WF, NH>;
     static bool attr_done = false;   // per instantiation (first call: outside graph capture -- decode_kmp_init)
     if (!attr_done) {
         if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kp_smem_bytes<TMAX>()) != hipSuccess) return -4;
@@ -370,23 +401,32 @@ int kp_launch_r(const GemvParams& p, int grid, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
-template <int MODE, bool NORM, int TMAX, int NPH, bool FP8, int NH = 1>
+template <int MODE, bool NORM, int TMAX, int NPH, int WF, int NH = 1>
 int kp_launch_tf(const GemvParams& p, int grid, bool r32, bool init_only, hipStream_t stream) {
     if constexpr (MODE == GEMV_RESID) {   // (NORM modes read the bf16 mirror of the fp32 residual stream, as in decode_km.hip)
         if (init_only || r32) {
-            const int r = kp_launch_r<MODE, NORM, true, TMAX, NPH, FP8, NH>(p, init_only ? 0 : grid, stream);
+            const int r = kp_launch_r<MODE, NORM, true, TMAX, NPH, WF, NH>(p, init_only ? 0 : grid, stream);
             if (r || !init_only) return r;
         }
     }
-    return kp_launch_r<MODE, NORM, false, TMAX, NPH, FP8, NH>(p, init_only ? 0 : grid, stream);
+    return kp_launch_r<MODE, NORM, false, TMAX, NPH, WF, NH>(p, init_only ? 0 : grid, stream);
 }
 template <int MODE, bool NORM, int TMAX, int NPH = 4, int NH = 1>
 int kp_launch_tm(const GemvParams& p, int grid, bool r32, bool init_only, hipStream_t stream) {
+    // (no MX4 form of the six-tile qkv of 17-32 rows: an MXFP4 model has at most 32 heads x 128 = 768 qkv tiles, three per block -- decode_kmp_takes refuses it)
+    if constexpr (!(MODE == GEMV_QKV && TMAX == 6 && NH == 1)) {
+        if (init_only || p.w4_scales) {
+            const int r = kp_launch_tf<MODE, NORM, TMAX, NPH, W_MX4, NH>(p, grid, r32, init_only, stream);
+            if (r || !init_only) return r;
+        }
+    } else if (!init_only && p.w4_scales) {
+        return -2;
+    }
     if (init_only || p.wscale) {
-        const int r = kp_launch_tf<MODE, NORM, TMAX, NPH, true, NH>(p, grid, r32, init_only, stream);
+        const int r = kp_launch_tf<MODE, NORM, TMAX, NPH, W_FP8, NH>(p, grid, r32, init_only, stream);
         if (r || !init_only) return r;
     }
-    return kp_launch_tf<MODE, NORM, TMAX, NPH, false, NH>(p, grid, r32, init_only, stream);
+    return kp_launch_tf<MODE, NORM, TMAX, NPH, W_BF16, NH>(p, grid, r32, init_only, stream);
 }
 
 // g: the geometry decode_kmp_takes returned (TMAX tiles per block, NPH phases, NH halves); init_only: every instantiation's LDS limit
@@ -434,13 +474,14 @@ int kp_dispatch(int mode, const GemvParams& p, const ProjGeom& g, hipStream_t st
 
 }  // namespace
 
-// What this file takes: 17-64 rows, bf16 or fp8 tiles of the km copy, no split partials.  17-32 rows: K in whole load steps (32 elements; 64
-// with fp8 tiles), at least one per wave, a wave's share within four phases (up to 6 tiles per block) or eleven (the down projection: one
+// What this file takes: 17-64 rows, bf16 or fp8 tiles of the km copy, or MXFP4 tiles when the shape says wide (ProjShape::mx4_wide: the model froze the
+// tuning switch mx4_wide at emmax_model_create), no split partials.  17-32 rows: K in whole load steps (32 elements; 64
+// with fp8 tiles, 128 with MXFP4 tiles), at least one per wave, a wave's share within four phases (up to 6 tiles per block) or eleven (the down projection: one
 // tile per block).  33-64 rows (two halves of four waves): qkv (3 tiles per block), the o-proj (1), gate/up (6) with K within eight phases of
 // a four-way split; the down projection and the lm-head run as two launches of <= 32 rows (step.hip: stage_chunk)
 bool decode_kmp_takes(const ProjShape& s, int B, ProjGeom* out) {
-    if (B < 17 || B > 64 || s.mode < GEMV_QKV || s.mode > GEMV_PLAIN || s.wfmt == PW_MX4) return false;
-    const int ks = s.wfmt == PW_FP8 ? 64 : 32, kw = B > 32 ? 4 : KP_WAVES, max_ph = B > 32 ? 8 : 11;
+    if (B < 17 || B > 64 || s.mode < GEMV_QKV || s.mode > GEMV_PLAIN || (s.wfmt == PW_MX4 && !s.mx4_wide)) return false;
+    const int ks = s.wfmt == PW_MX4 ? 128 : s.wfmt == PW_FP8 ? 64 : 32, kw = B > 32 ? 4 : KP_WAVES, max_ph = B > 32 ? 8 : 11;
     if (s.K % ks || s.K / ks < kw || cdiv(s.K / ks, kw) * ks > max_ph * KP_PH * 32 || s.n_rows % 16 || s.attn_part) return false;
     if (s.mode == GEMV_QKV && (s.head_dim % 16 || s.head_dim < 16)) return false;
     ProjGeom g = {};
@@ -461,6 +502,7 @@ bool decode_kmp_takes(const ProjShape& s, int B, ProjGeom* out) {
             g.tmax = 1; g.nph = 11;
         } else {
             g.tmax = tpb <= 1 ? 1 : tpb <= 3 ? 3 : 6; g.nph = 4;
+            if (s.wfmt == PW_MX4 && s.mode == GEMV_QKV && g.tmax == 6) return false;   // (no such instantiation: kp_launch_tm)
         }
     }
     g.smem = g.tmax == 1 ? kp_smem_bytes<1>() : g.tmax == 3 ? kp_smem_bytes<3>() : kp_smem_bytes<6>();
@@ -480,11 +522,15 @@ int decode_kmp_init() {
 }
 
 // p.W: the km copy of the matrix (launch_repack_km; fp8: decode_mfma.hip's e4m3 tiles of the permuted rows + p.wscale in the same row
-// order).  -2: decode_kmp_takes says no (K not in whole load steps, a wave's share beyond eleven phases, the o-proj's split merge)
+// order; MXFP4: launch_quant_mx4's tiles + p.w4_scales -- without a geometry from the caller the shape is taken as wide).  -2: decode_kmp_takes says no (K not in whole load steps, a wave's share beyond eleven phases, the o-proj's split merge)
 int launch_decode_kmp(int mode, const GemvParams& p_in, int B, hipStream_t stream, int* grid_out, const ProjGeom* geom) {
     ProjGeom g;
     if (geom) g = *geom;
-    else if (!decode_kmp_takes(proj_shape(mode, p_in), B, &g)) return -2;
+    else {
+        ProjShape s = proj_shape(mode, p_in);
+        s.mx4_wide = s.wfmt == PW_MX4;
+        if (!decode_kmp_takes(s, B, &g)) return -2;
+    }
     if (decode_kmp_init() != 0) return -4;
     GemvParams p = p_in;
     p.batch = B; p.n_groups = g.n_groups;

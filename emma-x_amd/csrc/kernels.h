@@ -217,6 +217,7 @@ struct EmmaxTune {
     int attn_resident;   // -1: resident ViT attention kernel where measured faster; 0: never; 2: whenever it fits (tests)
     int kv_fp8;          // 1: sessions created from now on keep the paged KV cache as e4m3 rows + one fp32 scale per (token, head) row (opt-in: half the attention bytes of a decode step, its own error line in the tests); 0: bf16
     int resid32;         // 1: prefill and decode step keep the residual stream in fp32 (GemmParams::res_f32, GemvParams::h32); 2: the decode step only; 0: bf16 rows (rounds 1-4)
+    int mx4_wide;        // 1: MXFP4 models CREATED from now on serve 17-64 rows on decode_kmp.hip's MX4 form (read at emmax_model_create and frozen in the model: emmax_model_mxfp4_wide); 0: 1-16 rows (default)
     int exact;           // 1: EXACT NUMERICS (round 6) -- models finalized and sessions created from now on carry fp32 activations end to end, every bf16
                          //    MFMA / dot2 activation operand as two bf16 terms (hi + lo), fp32 attention (fp32 MFMA) over an fp32 KV cache: the
                          //    reference's fp32 CPU arithmetic to ~1e-5 of max|logit| instead of 2.4e-2.  Batch 1-2 sessions on bf16 weights; the model
@@ -299,6 +300,7 @@ struct ProjShape {
     bool exact, h32, attn_part, x_tok;   // exact numerics; the fp32 stream is present; split partials in (nsplit of them); the folded embedding gather
     int nsplit, max_parts, max_grid;
     bool ld_ok;                          // ldw and ldx are multiples of 8
+    bool mx4_wide;                       // MXFP4 tiles at 17-64 rows: decode_kmp.hip's MX4 form may take them (the model froze the tuning switch mx4_wide; proj_shape leaves it false)
 };
 static inline ProjShape proj_shape(int mode, const GemvParams& p) {
     return {mode, p.K, p.n_rows, p.head_dim, p.Hq, p.w4_scales ? PW_MX4 : p.wscale ? PW_FP8 : PW_BF16, p.exact != 0, p.h32 != nullptr,

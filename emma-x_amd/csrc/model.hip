@@ -46,6 +46,7 @@ const TuneEntry kTune[] = {
     {"gemm_hybrid", &EmmaxTune::gemm_hybrid, 1}, {"gemm_normfuse", &EmmaxTune::gemm_normfuse, 1},
     {"resid32", &EmmaxTune::resid32, 1},       {"kv_fp8", &EmmaxTune::kv_fp8, 0},
     {"exact", &EmmaxTune::exact, 0},           {"attn_group", &EmmaxTune::attn_group, -1},
+    {"mx4_wide", &EmmaxTune::mx4_wide, 0},
 };
 EmmaxTune g_tune;
 std::once_flag g_tune_once;
@@ -159,6 +160,12 @@ static void derive(emmax_model* m) {
     m->lm_head_w.gemv_mode = GEMV_LMHEAD; m->lm_head_w.f8bit = F8_LMHEAD;
     m->fp8 = c.decode_fp8 == 1;
     m->mx4 = c.decode_fp8 == 2;
+    // the tuning switch mx4_wide is read HERE, once (emmax_model_create; emmax_config_max_decode_batch's model of the moment), and frozen: planner,
+    // session checks and launch_proj ask the model, never the live switch
+    m->mx4_wide = m->mx4 && emmax_tune().mx4_wide != 0;
+    for (auto& L : m->layers)
+        for (const ProjDim& d : layer_projs(m)) L.proj[d.stage].q4w = m->mx4_wide;
+    m->lm_head_w.q4w = m->mx4_wide;
 }
 
 static void plan_arena(emmax_model* m, Bump& b) {
@@ -417,6 +424,7 @@ int emmax_model_finalize(emmax_model* m, void* arena, int64_t arena_bytes, emmax
 
 int emmax_model_max_decode_batch(const emmax_model* m) { return m ? model_max_decode_batch(m) : -1; }
 int emmax_model_max_decode_batch_exact(const emmax_model* m) { return m ? model_max_decode_batch(m, true) : -1; }
+int emmax_model_mxfp4_wide(const emmax_model* m) { return m ? (m->mx4_wide ? 1 : 0) : -1; }
 int emmax_config_max_decode_batch(const emmax_config* cfg, int exact) {
     if (!cfg) return fail(EMMAX_ERR_INVALID, "null argument");
     if (int r = check_config(*cfg, false)) return r;

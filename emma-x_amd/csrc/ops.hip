@@ -549,6 +549,20 @@ int emmax_op_gemm_small_mxfp4(const void* x, const void* tiles, const void* scal
     if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_gemm_small_mxfp4: unsupported shape (N %% 16 and N <= 32768; K %% 1024 and K <= 4096)");
     return 0;
 }
+int emmax_op_gemm_wide_mxfp4(const void* x, const void* tiles, const void* scales, void* y, int B, int N, int K, emmax_stream st) {
+    if (!x || !tiles || !scales || !y) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_wide_mxfp4: null argument");
+    if (B < 17 || B > EMMAX_KMP_ROWS) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_wide_mxfp4: batch %d outside 17..%d", B, EMMAX_KMP_ROWS);
+    GemvParams p = plain_gemv(x, tiles, y, N, K);
+    p.w4_scales = scales;
+    // decode_kmp.hip's MX4 form as a pure op: the shape is wide by definition here (no model, no switch); its own check decides the rest
+    ProjShape s = proj_shape(GEMV_PLAIN, p);
+    s.mx4_wide = true;
+    ProjGeom g;
+    const bool ok = N >= 16 && N <= 32768 && K >= 128 && decode_kmp_takes(s, B, &g);
+    const int r = ok ? launch_decode_kmp(GEMV_PLAIN, p, B, (hipStream_t)st, nullptr, &g) : -2;
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_gemm_wide_mxfp4: unsupported shape (N %% 16 and N <= 32768; K %% 128 and K >= 1024; K <= 4096, or K <= 11264 with N <= 4096)");
+    return 0;
+}
 int emmax_op_gemv_fp8(const void* x, const void* W8, const float* scales, void* y, int B, int N, int K, emmax_stream st) {
     if (B < 1 || B > 2) return fail(EMMAX_ERR_INVALID, "emmax_op_gemv_fp8: batch must be 1..2");
     if (!scales) return fail(EMMAX_ERR_INVALID, "emmax_op_gemv_fp8: scales required");

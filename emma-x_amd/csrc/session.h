@@ -88,6 +88,7 @@ struct ProjW {
     void *q4, *q4s;         // MXFP4 mode: e2m1 tiles in km's row order and their e8m0 scale stream (launch_quant_mx4); null otherwise.  rm then holds the
                             // de-quantised values: the prefill evaluates the model the decode step streams
     int gemv_mode, f8bit;   // GEMV_QKV / GEMV_RESID / GEMV_GATEUP / GEMV_LMHEAD, and its bit of the tuning switch fp8_gemv
+    bool q4w;               // MXFP4 mode: the model's mx4_wide (the tiles are served at 17-64 rows too)
 };
 struct LayerW {
     bf16 *ln1, *ln2;
@@ -105,7 +106,8 @@ struct emmax_model {
     bf16 *embed, *final_norm;
     ProjW lm_head_w = {};
     bool fp8 = false;            // decode_fp8 == 1: e4m3 decode copies
-    bool mx4 = false;            // decode_fp8 == 2: MXFP4 decode copies (decode_km.hip only: batches 1-16)
+    bool mx4 = false;            // decode_fp8 == 2: MXFP4 decode copies (decode_km.hip: batches 1-16)
+    bool mx4_wide = false;       // ... and 17-64 rows on decode_kmp.hip's MX4 form: the tuning switch mx4_wide as it stood at emmax_model_create, frozen
     bool ln_folded = false;      // the ViT LayerNorms are folded into the qkv / fc1 weights (tuning switch gemm_lnfuse at finalize)
     bool aux_built = false;      // the batch >= 3 copies exist (fp8 models: always, they are part of the main arena)
     bool aux_ab = false;         // ... including decode_mfma.hip's qkv / gate-up pair

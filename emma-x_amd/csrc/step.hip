@@ -19,19 +19,20 @@ static int fp8_gemv_mask(int B) {
 
 // Which copies of a projection's matrix exist -- flags, not pointers: the planner asks before any arena exists.  copies_of: what a
 // ProjW holds now (launch_proj); copies_planned: what the model has or, before emmax_model_build_aux, will have.
-struct ProjCopies { bool rm, r8, sc, km, fm, q4; int f8bit; };
-static ProjCopies copies_of(const ProjW& w) { return {w.rm != nullptr, w.r8 != nullptr, w.sc != nullptr, w.km != nullptr, w.fm != nullptr, w.q4 != nullptr, w.f8bit}; }
+// q4w: the MXFP4 tiles are served at 17-64 rows too (decode_kmp.hip's MX4 form): the model was created under the tuning switch mx4_wide
+struct ProjCopies { bool rm, r8, sc, km, fm, q4; int f8bit; bool q4w; };
+static ProjCopies copies_of(const ProjW& w) { return {w.rm != nullptr, w.r8 != nullptr, w.sc != nullptr, w.km != nullptr, w.fm != nullptr, w.q4 != nullptr, w.f8bit, w.q4 != nullptr && w.q4w}; }
 static ProjCopies copies_planned(const emmax_model* m, int stage) {
     // decode_mfma.hip's qkv / gate-up pair: fp8 models always, bf16 models when the aux arena was (or would now be) built with the tuning switch km = 0
     const bool pair = stage == STAGE_QKV || stage == STAGE_GATEUP;
     const bool fm = m->fp8 || (!m->mx4 && (!pair || (m->aux_built ? m->aux_ab : emmax_tune().km == 0)));
     const int bit = stage == STAGE_QKV ? F8_QKV : stage == STAGE_OPROJ ? F8_OPROJ : stage == STAGE_GATEUP ? F8_GATEUP : stage == STAGE_DOWN ? F8_DOWN : F8_LMHEAD;
-    return {true, m->fp8, m->fp8, !m->mx4, fm, m->mx4, bit};
+    return {true, m->fp8, m->fp8, !m->mx4, fm, m->mx4, bit, m->mx4 && m->mx4_wide};
 }
 
 // Which launcher family takes a projection at B rows (EMMAX_VIA_*), EMMAX_VIA_NONE when none does, ROUTE_NO_FM when only decode_mfma.hip's copy
 // (not built) could have.  The order of preference: exact numerics -- the two-term forms or nothing (decode_ks.hip at batch 1-2,
-// decode_km.hip's EX kernels at 3-8); MXFP4 tiles -- decode_km.hip at every batch 1-16, no other kernel reads them; the fp8 row GEMV at batch
+// decode_km.hip's EX kernels at 3-8); MXFP4 tiles -- decode_km.hip at every batch 1-16, decode_kmp.hip's MX4 form at 17-64 when the model froze mx4_wide, no other kernel reads them; the fp8 row GEMV at batch
 // 1-2 under the fp8_gemv mask; batch >= 3 and fp8: the K-split MFMA kernels (decode_km.hip, 17-64 rows decode_kmp.hip), else decode_mfma.hip;
 // else (batch 1-2, bf16) decode_ks.hip, else decode.hip's staged GEMV.  Pure: every question goes to a family's own check, and *g is the
 // geometry the chosen family's check returned -- its launcher runs from it without asking again.
@@ -49,7 +50,10 @@ static int proj_route(const ProjCopies& c, ProjShape s, int B, ProjGeom* g) {
         // the MXFP4 down projection runs on the phased kernel only: the K-split form would take K <= 4096, but the format's error lines were
         // measured on the phased kernel alone (policy, not a kernel limit -- the same line emmax_model_create draws)
         if (c.f8bit == F8_DOWN && s.K <= 4096) return EMMAX_VIA_NONE;
-        return B <= 16 && decode_km_takes(s, B, g) ? EMMAX_VIA_KM : EMMAX_VIA_NONE;
+        // 17-64 rows: decode_kmp.hip's MX4 form, for a model that froze the tuning switch mx4_wide (decode_km_takes hands them on under the shape's flag)
+        s.mx4_wide = c.q4w;
+        if (!decode_km_takes(s, B, g)) return EMMAX_VIA_NONE;
+        return B > 16 ? EMMAX_VIA_KMP : EMMAX_VIA_KM;
     }
     s.wfmt = c.sc ? PW_FP8 : PW_BF16;
     if (B < EMMAX_MFMA_MIN_BATCH && c.sc && c.r8 && (fp8_gemv_mask(B) & c.f8bit) && decode_gemv_takes(s, B, g)) return EMMAX_VIA_GEMV_FP8;
@@ -93,7 +97,7 @@ static int launch_proj(const ProjW& w, GemvParams& p, int B, hipStream_t st, int
         default: break;
     }
     if (p.exact) return fail(EMMAX_ERR_INVALID, "exact numerics: no two-term kernel for this projection (batch %d, K %d)", B, p.K);
-    if (w.q4) return fail(EMMAX_ERR_INVALID, "MXFP4 decode weights: no kernel for this projection (batch %d of 1-16, K %d)", B, p.K);
+    if (w.q4) return fail(EMMAX_ERR_INVALID, "MXFP4 decode weights: no kernel for this projection (batch %d of 1-%d, K %d)", B, w.q4w ? EMMAX_MAX_DECODE_BATCH : 16, p.K);
     return -1;   // no family takes this shape at this batch
 }
 

@@ -59,6 +59,7 @@ SIGNATURES = {
     "emmax_model_arena_bytes": (C.c_int64, [_vp]),
     "emmax_model_max_decode_batch": (C.c_int, [_vp]),
     "emmax_model_max_decode_batch_exact": (C.c_int, [_vp]),
+    "emmax_model_mxfp4_wide": (C.c_int, [_vp]),
     "emmax_config_max_decode_batch": (C.c_int, [C.POINTER(ConfigC), C.c_int]),
     "emmax_model_finalize": (C.c_int, [_vp, _vp, C.c_int64, _vp]),
     "emmax_model_aux_bytes": (C.c_int64, [_vp]),
@@ -117,6 +118,7 @@ SIGNATURES = {
     "emmax_op_quant_mxfp4": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "emmax_op_dequant_mxfp4": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "emmax_op_gemm_small_mxfp4": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "emmax_op_gemm_wide_mxfp4": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "emmax_op_gemm_small_fp8": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "emmax_op_quant_rm8": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp]),
     "emmax_op_gemv_fp8": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),

@@ -62,7 +62,9 @@ class EmmaxEngine:
 
     def __init__(self, cfg: EmmaXConfig, state_dict: Dict[str, torch.Tensor], device: str = "cuda:0",
                  max_batch: int = 1, max_prompt: int = 512, max_ctx: Optional[int] = None, free_state_dict: bool = False,
-                 exact: Optional[bool] = None):
+                 exact: Optional[bool] = None, mxfp4_wide: Optional[bool] = None):
+        if mxfp4_wide and cfg.decode_weight_dtype != "mxfp4":   # (before anything touches the device)
+            raise ValueError(f"mxfp4_wide serves MXFP4 decode weights at 17-64 rows: this config has decode_weight_dtype={cfg.decode_weight_dtype!r}")
         self.lib = _lib.load()
         # EXACT NUMERICS (include/emmax.h, tuning switch `exact`): the fp32 CPU arithmetic of the reference instead of bf16 operands.  Frozen into
         # the model at finalize (ViT LayerNorms unfolded) and into every session of this engine; None = what the library's switch says (EMMAX_EXACT)
@@ -77,7 +79,11 @@ class EmmaxEngine:
         self._model = C.c_void_p()
         self._session = C.c_void_p()
         cc = _config_c(cfg)
-        _lib.check(self.lib.emmax_model_create(C.byref(cc), C.byref(self._model)), "emmax_model_create")
+        # MXFP4 at 17-64 rows (include/emmax.h, tuning switch `mx4_wide`): read once, at emmax_model_create, and frozen into the model; None = what
+        # the library's switch says (EMMAX_MX4_WIDE)
+        with _lib.tuning(**({} if mxfp4_wide is None else {"mx4_wide": int(bool(mxfp4_wide))})):
+            _lib.check(self.lib.emmax_model_create(C.byref(cc), C.byref(self._model)), "emmax_model_create")
+        self.mxfp4_wide = bool(self.lib.emmax_model_mxfp4_wide(self._model) == 1)   # what the model froze
         # ---- bind (bf16, on device) and finalize into the arena ----
         keep: List[torch.Tensor] = []
         for key, shape, _ in param_shapes(cfg):
@@ -160,7 +166,7 @@ class EmmaxEngine:
 
     def max_decode_batch(self) -> int:
         """Rows of one decode batch this model can run (64 for LLaMA-2-7B shapes, 8 for shapes outside the K-split kernels; MXFP4 weights: 16, or 8
-        when nine rows would split the attention).  Exact numerics: the two-term kernels take 8 rows per launch and larger batches run in chunks
+        when nine rows would split the attention; created with mxfp4_wide: up to 64).  Exact numerics: the two-term kernels take 8 rows per launch and larger batches run in chunks
         of 8 -- 64 on the shapes those kernels take, 2 where only the batch 1-2 kernel does."""
         if self.exact:
             return int(self.lib.emmax_model_max_decode_batch_exact(self._model))

@@ -160,6 +160,8 @@ class EmmaXForActionPrediction:
         config = config or EmmaXConfig.emma_x_7b()
         if decode_weight_dtype is not None:
             config.decode_weight_dtype = check_decode_weight_dtype(decode_weight_dtype)
+        if engine_kw.get("mxfp4_wide") and config.decode_weight_dtype != "mxfp4":   # (before the weights are generated on the device)
+            raise ValueError(f"mxfp4_wide serves MXFP4 decode weights at 17-64 rows: this config has decode_weight_dtype={config.decode_weight_dtype!r}")
         if not config.norm_stats:   # synthetic weights come with synthetic (made-up) statistics; a checkpoint never does
             config.norm_stats = default_norm_stats()
         sd = synthetic_state_dict(config, seed=seed, device=device, dtype=torch.bfloat16, planted=planted)
@@ -168,9 +170,13 @@ class EmmaXForActionPrediction:
         return m.to(device, **engine_kw)
 
     def to(self, device: Union[str, torch.device], max_batch: int = 1, max_prompt: int = 512,
-           max_ctx: Optional[int] = None, exact: Optional[bool] = None) -> "EmmaXForActionPrediction":
+           max_ctx: Optional[int] = None, exact: Optional[bool] = None, mxfp4_wide: Optional[bool] = None) -> "EmmaXForActionPrediction":
         """`exact=True`: exact numerics -- the reference's fp32 CPU arithmetic (prismatic.py:659-663 on CPU) instead of bf16 operands
-        (include/emmax.h, tuning switch `exact`; 8 rows per launch, larger batches in chunks; None = the library's switch, EMMAX_EXACT)."""
+        (include/emmax.h, tuning switch `exact`; 8 rows per launch, larger batches in chunks; None = the library's switch, EMMAX_EXACT).
+        `mxfp4_wide=True`: MXFP4 decode weights serve 17-64 rows too (tuning switch `mx4_wide`, frozen into the model when it is created; opt-in;
+        None = the library's switch, EMMAX_MX4_WIDE); a ValueError on any other decode_weight_dtype."""
+        if mxfp4_wide and self.config.decode_weight_dtype != "mxfp4":
+            raise ValueError(f"mxfp4_wide serves MXFP4 decode weights at 17-64 rows: this config has decode_weight_dtype={self.config.decode_weight_dtype!r}")
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("EmmaXForActionPrediction runs on MI355X (cuda:N) only; there is no CPU execution path")
@@ -178,7 +184,7 @@ class EmmaXForActionPrediction:
             if self._state_dict is None:
                 raise RuntimeError("no weights to load")
             self.engine = EmmaxEngine(self.config, self._state_dict, device=str(device), max_batch=max_batch,
-                                      max_prompt=max_prompt, max_ctx=max_ctx, free_state_dict=True, exact=exact)
+                                      max_prompt=max_prompt, max_ctx=max_ctx, free_state_dict=True, exact=exact, mxfp4_wide=mxfp4_wide)
             self._state_dict = None
         elif device != self.device:
             raise RuntimeError("moving an already-materialised engine between devices is not supported")

@@ -43,7 +43,8 @@ extern "C" {
  *   state and trace; the paged KV region did not grow;  10: emmax_op_decode_stage / emmax_op_decode_kv_read (one decode stage through the step's
  *   own dispatch), the workspace grew that op's per-row scratch;  11: emmax_config.decode_fp8 = 2 selects MXFP4 decode weights (the struct keeps
  *   its layout), emmax_op_quant_mxfp4 / emmax_op_dequant_mxfp4 / emmax_op_gemm_small_mxfp4;  12: the prefill's stage kernels one by one (emmax_op_gemm_stream, emmax_op_rmsnorm_f32,
- *   emmax_op_rope_kv_write, emmax_op_kv_quant_rows, emmax_op_embed_splice, emmax_op_gather_last_rows): new symbols only. */
+ *   emmax_op_rope_kv_write, emmax_op_kv_quant_rows, emmax_op_embed_splice, emmax_op_gather_last_rows): new symbols only; still 12: MXFP4 at 17-64 rows
+ *   (tuning switch mx4_wide, emmax_model_mxfp4_wide, emmax_op_gemm_wide_mxfp4): new symbols only. */
 #define EMMAX_ABI_VERSION 12
 
 typedef enum emmax_status {
@@ -79,7 +80,7 @@ typedef struct emmax_config {
     int32_t decode_fp8;                /* the decode weight format.  0: bf16 weights (the headline path); 1: the decode projections stream an
                                           fp8-e4m3 (per-row scale) weight copy, de-quantised in registers (BASELINE config 5); 2: MXFP4 (OCP MX
                                           v1.0: e2m1 elements, one e8m0 scale per 32 elements along K; 4.25 bits per weight), widened to bf16 in
-                                          registers -- decode batches 1-16, LLM shapes with hidden and n_heads * head_dim in multiples of 1024
+                                          registers -- decode batches 1-16 (17-64 too for a model created under the tuning switch mx4_wide), LLM shapes with hidden and n_heads * head_dim in multiples of 1024
                                           up to 4096 and an intermediate size % 128 == 0 in 4097..12288 (emmax_model_create refuses others); the
                                           prefill reads the de-quantised values, so prefill and decode evaluate the same quantised model        */
 } emmax_config;
@@ -97,10 +98,12 @@ int emmax_config_size(void);
  * DESIGN.md quotes.  Names: graph (1 = hipGraph replay of the decode step, BASELINE configs[4]), ks, ks_oproj, ks_oproj_grid, km,
  * km_down, km_roll, streamk, fp8_gemv, attn_nsplit, attn_direct, attn_nw, attn_deep, attn_group (-1 = the grouped decode attention at the batches it was measured faster at, 1 = wherever it applies, 0 = never), attn_ksplit, attn_lazy, vis_streams, fold_embed, mfma_xbar, gemm_big (2 = the 128 x 256 x 32 lab tile), gemm_splitk, gemm_sk_big,
  * gemm_hybrid, gemm_normfuse, gemm_deep, gemm_lnfuse, attn_resident, resid32 (1 = fp32 residual stream in prefill and decode, 2 = decode only,
- * 0 = bf16 rows), kv_fp8 (1 = sessions created from now on keep an e4m3 KV cache).
- * Three switches are read when an object is BUILT and frozen in it: gemm_lnfuse at emmax_model_finalize (the LayerNorm fold rewrites the ViT
+ * 0 = bf16 rows), kv_fp8 (1 = sessions created from now on keep an e4m3 KV cache), mx4_wide (1 = MXFP4 models created from now on serve decode
+ * batches of 17-64 rows too; 0, the default: 1-16).
+ * Four switches are read when an object is BUILT and frozen in it: gemm_lnfuse at emmax_model_finalize (the LayerNorm fold rewrites the ViT
  * qkv / fc1 weights in place: setting it afterwards does not change a finalized model), km at emmax_model_build_aux (which copies exist),
- * kv_fp8 at emmax_session_create (the cache format).
+ * kv_fp8 at emmax_session_create (the cache format), mx4_wide at emmax_model_create (emmax_model_mxfp4_wide; emmax_config_max_decode_batch has
+ * no model and reads it as it stands at the call).
  * exact (round 6; 0 = off, the default): EXACT NUMERICS -- the reference's fp32 CPU arithmetic (prismatic/models/vlms/prismatic.py:659-663 under
  * BASELINE configs[0]) instead of bf16 operands: fp32 activations end to end, every activation operand of a bf16 MFMA / dot2 as TWO bf16 terms
  * hi + lo (the checkpoint's weights are exact bf16), attention on the fp32 MFMA over an fp32 KV cache.  Read at emmax_model_finalize (the ViT
@@ -130,11 +133,16 @@ int64_t emmax_model_arena_bytes(const emmax_model* m);
  * shapes decode_km.hip's two-term kernels take, 2 where only decode_ks.hip's do, 0 on fp8 / MXFP4 weights.
  * MXFP4 models (decode_fp8 = 2): 16 -- decode_km.hip is the only kernel family that reads the 4-bit tiles -- or 8 when a batch of nine rows would
  * split the attention (the o-proj then reads split partials, which its 16-row form does not take); emmax_session_bytes / create refuse a larger
- * max_batch for such a model, naming the format.  The one-split rule reads the tuning switches attn_direct / attn_nsplit: the limit is checked when a
+ * max_batch for such a model, naming the format (a model created under the tuning switch mx4_wide: emmax_model_mxfp4_wide below).  The one-split rule reads the tuning switches attn_direct / attn_nsplit: the limit is checked when a
  * session is sized and created and again at every prefill and emmax_slots_open, not inside a step -- changing those switches between a prefill of
  * 9-16 rows and its decode steps makes the step fail with EMMAX_ERR_INVALID (no other kernel reads the 4-bit tiles: there is no fall-back). */
 int emmax_model_max_decode_batch(const emmax_model* m);
 int emmax_model_max_decode_batch_exact(const emmax_model* m);
+/* 1: the model was created under the tuning switch mx4_wide = 1 on MXFP4 weights -- decode_kmp.hip's MXFP4 form serves it at 17-64 rows, and
+ * emmax_model_max_decode_batch answers up to 64 (LLaMA-2-7B shapes: 64; 2 kv heads: still 8; an intermediate size above 11264: still 16, its
+ * down projection has no 17-row route); 0: any other model (MXFP4: the limits above); -1: null.  Frozen at emmax_model_create: the planner, the
+ * session checks, every prefill and emmax_slots_open ask the model, whatever the switch says later. */
+int emmax_model_mxfp4_wide(const emmax_model* m);
 /* the same planner on a config, before (or without) a model: negative status when the config fails the checks that do not concern the decode
  * weight format.  An MXFP4 config is accepted by emmax_model_create exactly when this answers >= 8. */
 int emmax_config_max_decode_batch(const emmax_config* cfg, int exact);
@@ -666,6 +674,10 @@ int emmax_op_dequant_mxfp4(const void* tiles_dev, const void* scales_dev, void* 
  * widened in registers.  K % 1024 == 0 and K <= 4096 (the K-split kernel; the phased kernel of the down projection is reached through
  * emmax_op_decode_stage); N % 16 == 0, N <= 32768.  Test hook: pins what the hardware widening does on every scale code. */
 int emmax_op_gemm_small_mxfp4(const void* x_dev, const void* tiles_dev, const void* scales_dev, void* y_dev, int B, int N, int K, emmax_stream stream);
+/* its sibling for 17 <= B <= 32: decode_kmp.hip's MXFP4 form (what a model created under the tuning switch mx4_wide runs at 17-64 rows), plain
+ * epilogue.  N % 16 == 0, N <= 32768; K % 128 == 0 and at least 1024 (one load step of 128 k for each of eight waves); K <= 4096 (four phases of
+ * 128 k per wave), or K <= 11264 with N <= 4096 (the eleven-phase form of the down projection: one tile per block).  Needs no model and no switch. */
+int emmax_op_gemm_wide_mxfp4(const void* x_dev, const void* tiles_dev, const void* scales_dev, void* y_dev, int B, int N, int K, emmax_stream stream);
 int emmax_op_gemm_small_fp8(const void* x_dev, const void* W8_fm_dev, const float* scales_dev, void* y_dev, int B, int N, int K,
                             emmax_stream stream);
 /* Batch 3-32 decode projection on the K-split MFMA kernels (decode_km.hip up to 16 rows, decode_kmp.hip above; K > 4096: the phased kernel of the

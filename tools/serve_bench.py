@@ -142,10 +142,13 @@ def main():
     ap.add_argument("--samples", type=str, default="", help="N (or N1,N2,...): every request is a sample group of N (Request.num_samples)")
     ap.add_argument("--unforked", action="store_true", help="with --samples: the same work as N independent requests per frame (the baseline)")
     ap.add_argument("--alternate", type=int, default=0, help="with --samples: run forked and unforked this many times in turn")
+    ap.add_argument("--weights", default="", help="decode_weight_dtype (bf16 / fp8 / mxfp4; default: the config's); mxfp4 with more than 16 slots is created wide")
     args = ap.parse_args()
     cfg = EmmaXConfig.tiny() if args.tiny else EmmaXConfig.emma_x_7b()
     dev = "cuda:0"
-    model = EmmaXForActionPrediction.from_synthetic(cfg, seed=5, device=dev, planted=True, max_batch=args.slots, max_prompt=64, max_ctx=1024)
+    wide = {"mxfp4_wide": True} if args.weights == "mxfp4" and args.slots > 16 else {}
+    model = EmmaXForActionPrediction.from_synthetic(cfg, seed=5, device=dev, planted=True, decode_weight_dtype=args.weights or None, max_batch=args.slots,
+                                                    max_prompt=64, max_ctx=1024, **wide)
     eng = model.engine
     if args.samples:
         for n in [int(v) for v in args.samples.split(",")]:
@@ -225,7 +228,7 @@ def main():
     lc = [res_cont[i].latency_s for i in range(N)]
     le = [res_early[i].latency_s for i in range(N)]
     out = {
-        "model": "tiny" if args.tiny else "Emma-X-7B shapes (planted synthetic weights)", "requests": N, "slots": args.slots, "poll_every": args.poll,
+        "model": "tiny" if args.tiny else "Emma-X-7B shapes (planted synthetic weights)", "weights": cfg.decode_weight_dtype, "requests": N, "slots": args.slots, "poll_every": args.poll,
         "new_tokens_to_eos": {"min": min(len(w) for w in want), "mean": float(np.mean([len(w) for w in want])), "max": max(len(w) for w in want)},
         "requests_following_the_planted_chain": n_chain,
         "static": {"seconds": round(t_static, 3), "actions_per_s": round(N / t_static, 3), "latency_p50_s": round(pct(lat_static, 50), 3),

@@ -1,5 +1,6 @@
 """Decode step time and per-launch projection times of the three decode weight formats (bf16, fp8-e4m3, MXFP4) on ONE box, back to back
-(not the headline bench): the synthetic 7B model, 512-token prompts over one frame each (context 768), batches 1 / 8 / 16.  The three models are
+(not the headline bench): the synthetic 7B model, 512-token prompts over one frame each (context 768), batches 1 / 8 / 16 by default (`--batches 16,32,64`: the MXFP4 model is then created wide -- mxfp4_wide=True, decode_kmp.hip's MX4
+form at 17-64 rows -- which leaves its 1-16-row kernels as they are).  The three models are
 built once and kept; every (format, batch) point is measured `--rounds` times with the formats alternating inside a round, so that a drift of
 the box shows up as spread between rounds and not as a difference between formats.
 
@@ -43,12 +44,13 @@ def main():
     models, info = {}, {}
     for f in formats:
         t0 = time.perf_counter()
+        wide = {"mxfp4_wide": True} if f == "mxfp4" and bmax > 16 else {}   # (opt-in: a narrow MXFP4 model stops at 16 rows)
         m = EmmaXForActionPrediction.from_synthetic(EmmaXConfig.emma_x_7b(), seed=0, device="cuda:0", decode_weight_dtype=f, max_batch=bmax,
-                                                    max_prompt=512, max_ctx=256 + 512 + args.steps + 64)
+                                                    max_prompt=512, max_ctx=256 + 512 + args.steps + 64, **wide)
         m.engine.ensure_decode_batch(bmax)
         torch.cuda.synchronize()
         models[f] = m
-        info[f] = {"weight_bytes": m.engine.weight_bytes(), "max_decode_batch": m.engine.max_decode_batch(), "build_s": round(time.perf_counter() - t0, 1)}
+        info[f] = {"weight_bytes": m.engine.weight_bytes(), "max_decode_batch": m.engine.max_decode_batch(), "mxfp4_wide": bool(m.engine.mxfp4_wide), "build_s": round(time.perf_counter() - t0, 1)}
         print(f"# {f}: {json.dumps(info[f])}", flush=True)
     rows = []
     for B in batches:
