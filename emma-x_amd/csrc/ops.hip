@@ -715,5 +715,72 @@ int emmax_op_gather_last_rows(const void* in, const float* in32, void* out, floa
     return 0;
 }
 
+// ---- the vision encode's glue kernels one by one (tests/test_vision_stages_gpu.py): pure ops, no session, no device allocation ----------------
+// The launchers check almost nothing: each op refuses here what its kernel cannot do, and then nothing is launched.
+int emmax_op_patch_gather(const void* src, void* out, int B, int img, int patch, int kpad, int chan0, const float* mean_host, const float* std_host,
+                          int from_u8, int hl, emmax_stream stream) {
+    if (!src || !out || !mean_host || !std_host) return fail(EMMAX_ERR_INVALID, "emmax_op_patch_gather: null argument");
+    if (B < 1 || img < 1 || patch < 1 || img % patch) return fail(EMMAX_ERR_INVALID, "emmax_op_patch_gather: B %d, img %d, patch %d (img %% patch == 0)", B, img, patch);
+    if (kpad < 3 * patch * patch) return fail(EMMAX_ERR_INVALID, "emmax_op_patch_gather: kpad %d below 3 patch^2 = %d", kpad, 3 * patch * patch);
+    if (hl && kpad % 64) return fail(EMMAX_ERR_INVALID, "emmax_op_patch_gather: the HL form holds 64 hi and 64 lo per 64 elements: kpad %d %% 64", kpad);
+    if (!from_u8 && chan0 != 0 && chan0 != 3) return fail(EMMAX_ERR_INVALID, "emmax_op_patch_gather: chan0 %d (a tower's three of six pixel channels: 0 or 3)", chan0);
+    if (((uintptr_t)out & 1) || (!from_u8 && ((uintptr_t)src & 1))) return fail(EMMAX_ERR_INVALID, "emmax_op_patch_gather: bf16 rows must be 2-byte aligned");
+    const int r = hl ? launch_x_patch_gather(from_u8 != 0, src, out, B, img, patch, kpad, chan0, mean_host, std_host, (hipStream_t)stream)
+                     : launch_patch_gather(from_u8 != 0, src, out, B, img, patch, kpad, chan0, mean_host, std_host, (hipStream_t)stream);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_patch_gather: launch failure");
+    return 0;
+}
+int emmax_op_assemble_tokens(const void* pe, const void* pos, const void* cls, const void* reg, void* tokens, int B, int n_patches, int has_cls, int n_reg,
+                             int D, int ld, int f32, emmax_stream stream) {
+    if (!pe || !pos || !tokens) return fail(EMMAX_ERR_INVALID, "emmax_op_assemble_tokens: null argument");
+    if (has_cls != 0 && has_cls != 1) return fail(EMMAX_ERR_INVALID, "emmax_op_assemble_tokens: has_cls %d (0 or 1)", has_cls);
+    if ((has_cls && !cls) || (n_reg > 0 && !reg)) return fail(EMMAX_ERR_INVALID, "emmax_op_assemble_tokens: the cls row / the %d register rows are required", n_reg);
+    if (B < 1 || n_patches < 1 || n_reg < 0 || D < 1 || ld < D) return fail(EMMAX_ERR_INVALID, "emmax_op_assemble_tokens: B %d, n_patches %d, n_reg %d, D %d, ld %d (>= D)", B, n_patches, n_reg, D, ld);
+    if (((uintptr_t)pe | (uintptr_t)tokens) & (f32 ? 3 : 1)) return fail(EMMAX_ERR_INVALID, "emmax_op_assemble_tokens: misaligned rows");
+    const int r = f32 ? launch_x_assemble_tokens((const float*)pe, pos, cls, reg, (float*)tokens, B, n_patches, has_cls + n_reg, has_cls, D, ld, (hipStream_t)stream)
+                      : launch_assemble_tokens(pe, pos, cls, reg, tokens, B, n_patches, has_cls + n_reg, has_cls, D, ld, (hipStream_t)stream);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_assemble_tokens: launch failure");
+    return 0;
+}
+int emmax_op_copy_rows(const void* in, int ld_in, void* out, int B, int rows_in, int r_off, int rows_out, int D, int ld_out, int col_off, emmax_stream stream) {
+    if (!in || !out) return fail(EMMAX_ERR_INVALID, "emmax_op_copy_rows: null argument");
+    if (B < 1 || rows_in < 1 || rows_out < 1 || r_off < 0 || r_off + rows_out > rows_in)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_copy_rows: B %d, rows %d..%d of %d", B, r_off, r_off + rows_out - 1, rows_in);
+    if (D < 8 || (D | ld_in | ld_out | col_off) % 8 || col_off < 0 || ld_in < D || col_off + D > ld_out)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_copy_rows: D %d, ld_in %d, ld_out %d, col_off %d in multiples of 8 (16-byte moves), D <= ld_in, col_off + D <= ld_out", D, ld_in,
+                    ld_out, col_off);
+    if (((uintptr_t)in | (uintptr_t)out) & 15) return fail(EMMAX_ERR_INVALID, "emmax_op_copy_rows: rows must be 16-byte aligned");
+    const int r = launch_copy_rows(in, ld_in, out, B, rows_in, r_off, rows_out, D, ld_out, col_off, (hipStream_t)stream);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_copy_rows: launch failure");
+    return 0;
+}
+int emmax_op_row_stats(const void* x, int ldx, float* stats, int rows, int D, float eps, emmax_stream stream) {
+    if (!x || !stats) return fail(EMMAX_ERR_INVALID, "emmax_op_row_stats: null argument");
+    if (rows < 1 || D < 8 || D % 8 || D > 8192 || ldx % 8 || ldx < D)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_row_stats: rows %d, D %d (%% 8, <= 8192), ldx %d (%% 8, >= D)", rows, D, ldx);
+    if (((uintptr_t)x & 15) || ((uintptr_t)stats & 7)) return fail(EMMAX_ERR_INVALID, "emmax_op_row_stats: x must be 16-byte aligned, the (mean, rstd) pairs 8-byte");
+    const int r = launch_row_stats(x, stats, rows, D, ldx, eps, (hipStream_t)stream);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_row_stats: launch failure");
+    return 0;
+}
+int emmax_op_ln_fold(void* W, int ldw, int N, int K, const void* gamma, const void* beta, const void* bias, float* ln_s, float* ln_c, emmax_stream stream) {
+    if (!W || !gamma || !ln_s || !ln_c) return fail(EMMAX_ERR_INVALID, "emmax_op_ln_fold: null argument (beta and bias may be null)");
+    if (N < 1 || K < 1 || ldw < K) return fail(EMMAX_ERR_INVALID, "emmax_op_ln_fold: N %d, K %d, ldw %d (>= K)", N, K, ldw);
+    if (((uintptr_t)W | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)bias) & 1 || (((uintptr_t)ln_s | (uintptr_t)ln_c) & 3))
+        return fail(EMMAX_ERR_INVALID, "emmax_op_ln_fold: misaligned argument");
+    const int r = launch_ln_fold(W, ldw, N, K, gamma, beta, bias, ln_s, ln_c, (hipStream_t)stream);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_ln_fold: launch failure");
+    return 0;
+}
+int emmax_op_x_to_bf16(const float* x, int ldx, void* y, int ldy, int rows, int D, emmax_stream stream) {
+    if (!x || !y) return fail(EMMAX_ERR_INVALID, "emmax_op_x_to_bf16: null argument");
+    if (rows < 1 || D < 8 || (D | ldx | ldy) % 8 || ldx < D || ldy < D)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_x_to_bf16: rows %d, D %d, ldx %d, ldy %d in multiples of 8, pitches >= D", rows, D, ldx, ldy);
+    if (((uintptr_t)x | (uintptr_t)y) & 15) return fail(EMMAX_ERR_INVALID, "emmax_op_x_to_bf16: rows must be 16-byte aligned");
+    const int r = launch_x_to_bf16(x, ldx, y, ldy, rows, D, (hipStream_t)stream);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_x_to_bf16: launch failure");
+    return 0;
+}
+
 
 }  // extern "C"

@@ -262,7 +262,12 @@ int emmax_session_create_ex(emmax_model* m, int max_batch, int max_prompt, int m
     s->kv_fmt = kv_format_now();
     s->kv_layer_stride = kv_layer_bytes(m, s->rows_total, s->max_pages, s->kv_fmt);
     s->kv24 = s->kv_fmt == KV_X24 ? (long long)kv_rows_per_layer(m, s->rows_total, s->max_pages) * m->cfg.head_dim : 0;
-    HIPCHK(hipMemset(ws, 0, need_ws));   // padding columns of every activation buffer stay zero forever
+    // Every activation buffer starts as zeros, so its padding columns start finite.  They do NOT stay zero: the towers share scratch set 0 at each
+    // tower's own pitch, and the bf16 token assembly writes the real columns only, so a padded tower (the tiny SigLIP: D 144 in rows of 256) reads
+    // the other tower's leftovers in its padding columns.  What keeps that harmless is that the padded COLUMNS OF THE WEIGHTS are zero
+    // (model.hip) and every leftover is a finite value the encode wrote: 0 x finite = 0 in every GEMM, and the norms and the attention read
+    // the real columns only (tests/test_vision_stages_gpu.py: the shared-scratch case pins it bit for bit).
+    HIPCHK(hipMemset(ws, 0, need_ws));
     HIPCHK(hipMemset(s->hidden, 0xff, (size_t)s->rows_total * s->max_pages * 4));   // no row hides a page
     HIPCHK(hipMemset(kv, 0, need_kv));
     HIPCHK(hipDeviceSynchronize());

@@ -176,7 +176,18 @@ SIGNATURES = {
     "emmax_op_kv_quant_rows": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "emmax_op_embed_splice": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "emmax_op_gather_last_rows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
+    "emmax_op_patch_gather": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, _vp]),
+    "emmax_op_assemble_tokens": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "emmax_op_copy_rows": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "emmax_op_row_stats": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_float, _vp]),
+    "emmax_op_ln_fold": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "emmax_op_x_to_bf16": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "emmax_op_vision_stage": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
 }
+
+# stages of emmax_op_vision_stage (include/emmax.h: EMMAX_VSTAGE_*)
+(VSTAGE_EMBED, VSTAGE_QKV, VSTAGE_ATTN, VSTAGE_PROJ, VSTAGE_FC1, VSTAGE_FC2, VSTAGE_FEATURES, VSTAGE_PJ1, VSTAGE_PJ2, VSTAGE_PJ3,
+ VSTAGE_EMBED_PIXELS) = range(11)
 
 _lib: Optional[C.CDLL] = None
 

@@ -779,6 +779,55 @@ int emmax_op_embed_splice(const int32_t* ids_dev, int P_max, const int32_t* cu_s
 int emmax_op_gather_last_rows(const void* in_dev, const float* in32_dev, void* out_dev, float* out32_dev, const int32_t* cu_seqlens_dev, int B, int D,
                               emmax_stream stream);
 
+/* ---- the vision encode's glue kernels and stages one by one (still ABI 12: new symbols only; tests/test_vision_stages_gpu.py) ----------------------
+ * The glue kernels as pure ops -- no session, no device allocation.  Each refuses with EMMAX_ERR_INVALID what its kernel cannot do, and launches
+ * nothing then.
+ *   emmax_op_patch_gather     the processor's normalisation fused with timm PatchEmbed's im2col: out row (b, py, px) = the patch's 3 patch^2 values in
+ *                             conv-weight order k = c patch^2 + dy patch + dx, zeros from 3 patch^2 to kpad.  from_u8 = 1: src uint8 [B, img, img, 3],
+ *                             value = ((float)u / 255 - mean[c]) / std[c] in fp32 (mean_host / std_host: float[3] on the HOST; chan0 ignored);
+ *                             from_u8 = 0: src bf16 pixel_values [B, 6, img, img], channels chan0 .. chan0 + 2 (chan0 0 or 3; mean / std unused but
+ *                             required).  hl = 0: out bf16 [B (img / patch)^2, kpad], one rounding.  hl = 1 (exact numerics): out bf16
+ *                             [.., 2 kpad], per 64 elements 64 hi = bf16(v) then 64 lo = bf16(v - hi); kpad % 64 == 0.  img % patch == 0,
+ *                             kpad >= 3 patch^2.
+ *   emmax_op_assemble_tokens  timm _pos_embed: tokens row (b, 0) = cls (has_cls = 1), rows (b, has_cls .. has_cls + n_reg - 1) = reg rows in order,
+ *                             row (b, has_cls + n_reg + p) = pe[b, p] + pos[p]; pos / cls / reg bf16 with rows of D, pe and tokens rows of pitch ld.
+ *                             f32 = 0: pe and tokens bf16, one fp32 add and one rounding; columns D .. ld of tokens are NOT written.  f32 = 1 (exact
+ *                             numerics): pe and tokens fp32, and columns D .. ld are written as ZEROS.  ld >= D.
+ *   emmax_op_copy_rows        out[(b rows_out + r) ld_out + col_off + d] = in[(b rows_in + r_off + r) ld_in + d], d < D, bf16, 16 bytes at a time:
+ *                             D, ld_in, ld_out, col_off in multiples of 8; r_off + rows_out <= rows_in; col_off + D <= ld_out.
+ *   emmax_op_row_stats        stats f32 [rows][2] = (mean, rsqrt(var + eps)) of x bf16 [rows, ldx] over D columns, variance about the mean, fp32.
+ *                             D % 8 == 0, D <= 8192, ldx % 8 == 0, ldx >= D.
+ *   emmax_op_ln_fold          LayerNorm folded into the weight behind it, IN PLACE: W[n, k] = bf16(W[n, k] gamma[k]) for k < K (columns K .. ldw
+ *                             untouched), ln_s[n] = sum_k W'[n, k], ln_c[n] = sum_k W[n, k] beta[k] + bias[n] (beta / bias may be NULL: 0).
+ *   emmax_op_x_to_bf16        y bf16 [rows, ldy] = x fp32 [rows, ldx] rounded to nearest even, D columns.  D, ldx, ldy in multiples of 8.
+ * emmax_op_vision_stage runs ONE stage of the bf16 vision encode of a created session through the encode's own stage functions, as
+ * emmax_op_decode_stage does for the decode step.  The caller hands packed bf16 rows at the REAL width; they are copied into the session's
+ * padded scratch (whose padding columns keep what they hold), the stage runs, the result is copied out.  Stages (in -> out; N tokens and D columns
+ * of the tower, M its MLP width, np patches, V = D0 + D1 the feature width, P1 and H the projector's):
+ *   EMBED         frames uint8 [B, img, img, 3] -> token rows [B N, D]: gather, patch GEMM + bias, assemble (EMBED_PIXELS: pixel_values bf16 [B, 6, img, img])
+ *   QKV           tokens [B N, D] -> [B N, 3 D]: LayerNorm then GEMM + bias, or row statistics + the folded GEMM (as the model was finalized)
+ *   ATTN          qkv [B N, 3 D] -> [B N, D]
+ *   PROJ          attention rows [B N, D], tok_in tokens [B N, D] -> tokens + ls1 .* (x W^T + proj_b)
+ *   FC1           tokens -> [B N, M]: LayerNorm (or its folded form), GEMM + bias, GELU
+ *   FC2           MLP rows [B N, M], tok_in tokens -> tokens + ls2 .* (x W^T + fc2_b)
+ *   FEATURES      tokens [B N, D] -> the feature rows [B np, V] with the tower's patch rows at its columns; tok_in (optional): the feature rows before
+ *   PJ1 PJ2 PJ3   [B np, V] -> [B np, P1] -> [B np, H] -> [B np, H] (tower / block ignored)
+ * It refuses an exact-numerics session, a bad tower, block or stage, and B outside 1 .. max_batch.  The session's last vision result is dropped. */
+enum { EMMAX_VSTAGE_EMBED = 0, EMMAX_VSTAGE_QKV = 1, EMMAX_VSTAGE_ATTN = 2, EMMAX_VSTAGE_PROJ = 3, EMMAX_VSTAGE_FC1 = 4, EMMAX_VSTAGE_FC2 = 5,
+       EMMAX_VSTAGE_FEATURES = 6, EMMAX_VSTAGE_PJ1 = 7, EMMAX_VSTAGE_PJ2 = 8, EMMAX_VSTAGE_PJ3 = 9, EMMAX_VSTAGE_EMBED_PIXELS = 10 };
+int emmax_op_patch_gather(const void* src_dev, void* out_dev, int B, int img, int patch, int kpad, int chan0, const float* mean_host, const float* std_host,
+                          int from_u8, int hl, emmax_stream stream);
+int emmax_op_assemble_tokens(const void* pe_dev, const void* pos_dev, const void* cls_dev, const void* reg_dev, void* tokens_dev, int B, int n_patches,
+                             int has_cls, int n_reg, int D, int ld, int f32, emmax_stream stream);
+int emmax_op_copy_rows(const void* in_dev, int ld_in, void* out_dev, int B, int rows_in, int r_off, int rows_out, int D, int ld_out, int col_off,
+                       emmax_stream stream);
+int emmax_op_row_stats(const void* x_dev, int ldx, float* stats_dev, int rows, int D, float eps, emmax_stream stream);
+int emmax_op_ln_fold(void* W_dev, int ldw, int N, int K, const void* gamma_dev, const void* beta_dev, const void* bias_dev, float* ln_s_dev, float* ln_c_dev,
+                     emmax_stream stream);
+int emmax_op_x_to_bf16(const float* x_dev, int ldx, void* y_dev, int ldy, int rows, int D, emmax_stream stream);
+int emmax_op_vision_stage(emmax_session* s, int tower, int block, int stage, int B, const void* in_dev, const void* tok_in_dev, void* out_dev,
+                          emmax_stream stream);
+
 /* ---- exact numerics (tuning switch exact), kernel by kernel: fp32 operands in, fp32 results out (tests/test_exact_gpu.py).
  * hl_ws: device scratch for the two-term bf16 image of the activation operand, 4 bytes per (padded) element.
  *   emmax_op_x_gemm       C32[M, N] = act(A32[M, K] W[N, K]^T + bias) (+ residual32): A split into hi + lo, both through the bf16 MFMAs

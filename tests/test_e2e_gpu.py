@@ -83,7 +83,9 @@ def test_vision_features_and_projector(device, tiny_random):
     assert rel(got_proj, ref_proj) < FEAT_TOL
     # pixel_values entry point (PrismaticProcessor layout) must agree with the fused uint8 path
     got2 = model.engine.vision_encode_pixels(pix.to(torch.bfloat16))
-    assert rel(got2, got_proj.float().cpu()) < 1e-6 or rel(got2, ref_proj) < FEAT_TOL
+    # (exactly: the pixel path reads bf16(preprocess(u)) and the uint8 path rounds the same fp32 values once, so the two gathers are bit-identical
+    # -- tests/test_vision_stages_gpu.py holds the gather op to that -- and everything behind them is the same code)
+    assert rel(got2, got_proj.float().cpu()) < 1e-6
 
 
 def test_vision_towers_on_two_streams_equal_one_stream(device, tiny_random):
