@@ -242,6 +242,16 @@ int emmax_slots_commit(emmax_session* s, const int32_t* staged_idx_host, const i
     StreamScope sc(s, stream);
     if (sc.error()) return sc.error();
     KCHK(launch_slots_commit(c, sc.stream()));
+    for (int i = 0; i < n && s->toplp.on; ++i) {   // the request's written entries move with it: a staged request has entry 0 only
+        const TopLogprobs& t = s->toplp;
+        const size_t src = (size_t)c.src[i] * t.max_new, dst = (size_t)c.slot[i] * t.max_new;
+        if (t.n_top) {
+            HIPCHK(hipMemcpyAsync(t.ids_out + dst * t.n_top, t.ids_out + src * t.n_top, (size_t)t.n_top * 4, hipMemcpyDeviceToDevice, sc.stream()));
+            HIPCHK(hipMemcpyAsync(t.lp_out + dst * t.n_top, t.lp_out + src * t.n_top, (size_t)t.n_top * 4, hipMemcpyDeviceToDevice, sc.stream()));
+        }
+        if (t.n_watch)
+            HIPCHK(hipMemcpyAsync(t.watch_out + dst * t.n_watch, t.watch_out + src * t.n_watch, (size_t)t.n_watch * 4, hipMemcpyDeviceToDevice, sc.stream()));
+    }
     for (int i = 0; i < n; ++i) {
         const int slot = slots_host[i];
         s->S[slot] = s->S[s->stg0 + staged_idx_host[i]];

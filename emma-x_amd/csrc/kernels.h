@@ -515,6 +515,30 @@ struct ExtFinishParams : ProcFinishParams {
     float* scores_out;          // [B][V] or null
 };
 int launch_ext_finish(const ExtFinishParams& p, hipStream_t stream);
+// top-N and watched-token log-probabilities of rows of fp32 logits (include/emmax.h: emmax_op_top_logprobs / emmax_session_set_top_logprobs):
+// one 1024-thread block per row, over the RAW row -- lse as emmax_sample_kernel computes it, the first n_top non-NaN entries by (value
+// descending, id ascending) as (id, l - lse), and l[watch_ids[w]] - lse.
+//   the op form (words null):   row b's results at top_ids / top_lp [b][n_top] and watch_lp [b][n_watch];
+//   the step form (words set):  device words {top_ids, top_lp, watch_lp, n_top, n_watch, max_new}; block b is session row row0 + b and writes
+//                               entry [row0 + b][t], t = n_out[b], of buffers [rows][max_new][n] -- unless the row emits nothing (not a prefill
+//                               and done or out of budget) or t >= max_new.  It runs BEFORE the finish that advances n_out / done.
+#ifndef EMMAX_MAX_TOP_LOGPROBS
+#define EMMAX_MAX_TOP_LOGPROBS 20
+#define EMMAX_MAX_WATCH_IDS 256
+#endif
+enum { TOPLP_W_IDS = 0, TOPLP_W_LP = 1, TOPLP_W_WATCH = 2, TOPLP_W_NTOP = 3, TOPLP_W_NWATCH = 4, TOPLP_W_MAXNEW = 5, TOPLP_WORDS = 6 };
+struct TopLogprobParams {
+    const float* logits;        // f32 [B, ld]
+    int ld, V;
+    int n_top, n_watch;         // (op form) 0 = that part is off
+    int32_t* top_ids;
+    float *top_lp, *watch_lp;
+    const int32_t* watch_ids;   // device [n_watch], each in [0, V)
+    const uint64_t* words;      // the step form, else null
+    int row0, is_prefill;
+    const int32_t *n_out, *done, *max_new_p;   // (step form) the rows' state, already offset to row0
+};
+int launch_top_logprobs(const TopLogprobParams& p, int B, hipStream_t stream);
 // ---- beam.hip: beam search in the decode step (include/emmax.h, ABI 9) ----
 #ifndef EMMAX_MAX_BEAMS
 #define EMMAX_MAX_BEAMS 8

@@ -210,6 +210,7 @@ int emmax_slots_set_rule_enables_staged(emmax_session* s, int n, const uint32_t*
 int emmax_session_clear_token_rules(emmax_session* s, emmax_stream) {
     if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
     if (s->rules.on && s->rules.implied_proc) s->proc.on = false;
+    if (!s->samp.on && !s->proc.on) (void)emmax_session_clear_top_logprobs(s, nullptr);
     s->rules.on = s->rules.implied_proc = false;
     return 0;
 }
@@ -240,6 +241,7 @@ int emmax_slots_set_sampling_staged(emmax_session* s, int n, const float* temper
 int emmax_session_clear_sampling(emmax_session* s, emmax_stream stream) {
     if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
     s->samp.on = false;
+    if (!s->proc.on) (void)emmax_session_clear_top_logprobs(s, stream);   // no logit rows are written any more
     return emmax_session_clear_warpers(s, stream);   // the warpers belong to the draw
 }
 
@@ -282,6 +284,7 @@ int emmax_session_clear_processing(emmax_session* s, emmax_stream) {
     if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
     s->proc.on = false;
     s->rules.on = s->rules.implied_proc = false;   // the token rules are processors (the table stays on the device; set it again to use it)
+    if (!s->samp.on) (void)emmax_session_clear_top_logprobs(s, nullptr);   // no logit rows are written any more
     return 0;
 }
 
@@ -307,6 +310,43 @@ int emmax_session_set_scores(emmax_session* s, float* scores_dev, float* logits_
     return sc.leave();
 }
 
+// ---- top-N and watched-token log-probabilities in the decode step (new symbols, same ABI) -------------------------------------
+int emmax_session_set_top_logprobs(emmax_session* s, int n_top, int32_t* top_ids_dev, float* top_lp_dev, int n_watch, const int32_t* watch_ids_host,
+                                   float* watch_lp_dev, int max_new, emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    const int V = s->m->vocab;
+    if (n_top < 0 || n_top > EMMAX_MAX_TOP_LOGPROBS || n_top > V)
+        return fail(EMMAX_ERR_INVALID, "n_top %d outside 0..min(%d, the vocabulary's %d)", n_top, EMMAX_MAX_TOP_LOGPROBS, V);
+    if (n_watch < 0 || n_watch > EMMAX_MAX_WATCH_IDS) return fail(EMMAX_ERR_INVALID, "n_watch %d outside 0..%d", n_watch, EMMAX_MAX_WATCH_IDS);
+    if (n_top == 0 && n_watch == 0) return fail(EMMAX_ERR_INVALID, "neither top log-probabilities nor watched ids asked for (emmax_session_clear_top_logprobs unbinds)");
+    if ((n_top > 0 && (!top_ids_dev || !top_lp_dev)) || (n_watch > 0 && (!watch_ids_host || !watch_lp_dev))) return fail(EMMAX_ERR_INVALID, "null argument");
+    for (int w = 0; w < n_watch; ++w)
+        if (watch_ids_host[w] < 0 || watch_ids_host[w] >= V) return fail(EMMAX_ERR_INVALID, "watch id %d (entry %d) outside 0..%d", watch_ids_host[w], w, V - 1);
+    if (max_new < 1 || max_new > s->max_out) return fail(EMMAX_ERR_INVALID, "max_new_tokens %d outside 1..%d", max_new, s->max_out);
+    if (V > EMMAX_SAMPLE_MAX_V) return fail(EMMAX_ERR_INVALID, "top log-probabilities take vocabularies of up to %d entries (%d)", EMMAX_SAMPLE_MAX_V, V);
+    if (s->beam.K) return fail(EMMAX_ERR_STATE, "top log-probabilities are not available while beams are on");
+    if (!s->samp.on && !s->proc.on)
+        return fail(EMMAX_ERR_STATE, "top log-probabilities read the session's logit rows: turn sampling (temperature 0 for greedy rows) or logits processing on first");
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    uint64_t words[TOPLP_WORDS] = {};
+    words[TOPLP_W_IDS] = (uint64_t)(uintptr_t)top_ids_dev; words[TOPLP_W_LP] = (uint64_t)(uintptr_t)top_lp_dev; words[TOPLP_W_WATCH] = (uint64_t)(uintptr_t)watch_lp_dev;
+    words[TOPLP_W_NTOP] = (uint64_t)n_top; words[TOPLP_W_NWATCH] = (uint64_t)n_watch; words[TOPLP_W_MAXNEW] = (uint64_t)max_new;
+    if (int r = upload_rows(s, 0, 1, sc.stream(), {{s->toplp.words, words, (int)sizeof(words)}, {s->toplp.watch_ids, watch_ids_host, n_watch * 4}})) return r;
+    s->toplp.on = true;
+    s->toplp.n_top = n_top; s->toplp.n_watch = n_watch; s->toplp.max_new = max_new;
+    s->toplp.ids_out = top_ids_dev; s->toplp.lp_out = top_lp_dev; s->toplp.watch_out = watch_lp_dev;
+    return sc.leave();
+}
+
+int emmax_session_clear_top_logprobs(emmax_session* s, emmax_stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    s->toplp = TopLogprobs{false, 0, 0, 0, nullptr, nullptr, nullptr, s->toplp.words, s->toplp.watch_ids};
+    return 0;
+}
+
+int emmax_session_top_logprobs(const emmax_session* s) { return s ? (s->toplp.on ? 1 : 0) : -1; }
+
 // ---- beam search in the decode step (ABI 9) ---------------------------------------------------------------------------
 int emmax_session_set_beams(emmax_session* s, int num_beams, double length_penalty, int early_stopping, emmax_stream stream) {
     if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
@@ -321,6 +361,7 @@ int emmax_session_set_beams(emmax_session* s, int num_beams, double length_penal
     if (s->grp_N) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while sample groups are on (emmax_session_clear_sample_groups)");
     if (s->samp.on || s->proc.on || s->warp.on || s->rules.on) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while sampling or logits processing is on");
     if (s->scores.on && s->scores.has_scores) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while a scores buffer is bound");
+    if (s->toplp.on) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while top log-probabilities are bound (emmax_session_clear_top_logprobs)");
     StreamScope sc(s, stream);
     if (sc.error()) return sc.error();
     if (int r = slots_restore_pages(s, sc.stream())) return r;

@@ -63,6 +63,22 @@ int emmax_op_sample(const float* logits, int ld, int B, int V, const float* temp
     KCHK(launch_sample(p, B, (hipStream_t)stream));
     return 0;
 }
+int emmax_op_top_logprobs(const float* logits, int ld, int B, int V, int n_top, int32_t* top_ids_out, float* top_lp_out, int n_watch,
+                          const int32_t* watch_ids, float* watch_lp_out, emmax_stream stream) {
+    if (!logits) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (B < 1 || V < 1 || V > EMMAX_SAMPLE_MAX_V || ld < V)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_top_logprobs: B %d (>= 1), V %d (1..%d), ld %d (>= V)", B, V, EMMAX_SAMPLE_MAX_V, ld);
+    if (n_top < 0 || n_top > EMMAX_MAX_TOP_LOGPROBS || n_top > V)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_top_logprobs: n_top %d outside 0..min(%d, V = %d)", n_top, EMMAX_MAX_TOP_LOGPROBS, V);
+    if (n_watch < 0 || n_watch > EMMAX_MAX_WATCH_IDS) return fail(EMMAX_ERR_INVALID, "emmax_op_top_logprobs: n_watch %d outside 0..%d", n_watch, EMMAX_MAX_WATCH_IDS);
+    if ((n_top > 0 && (!top_ids_out || !top_lp_out)) || (n_watch > 0 && (!watch_ids || !watch_lp_out))) return fail(EMMAX_ERR_INVALID, "null argument");
+    TopLogprobParams p;
+    memset(&p, 0, sizeof(p));
+    p.logits = logits; p.ld = ld; p.V = V; p.n_top = n_top; p.top_ids = top_ids_out; p.top_lp = top_lp_out;
+    p.n_watch = n_watch; p.watch_ids = watch_ids; p.watch_lp = watch_lp_out;
+    KCHK(launch_top_logprobs(p, B, (hipStream_t)stream));
+    return 0;
+}
 int emmax_op_sample_ext(const float* logits, int ld, int B, int V, const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seed,
                         const uint32_t* subseq, const int32_t* n_out, const float* min_p, const float* typical_p, const float* epsilon_cutoff,
                         const float* eta_cutoff, const float* penalty, const int32_t* ngram, const int32_t* min_new, const int32_t* hist, const int32_t* hist_len,

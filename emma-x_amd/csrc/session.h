@@ -161,6 +161,17 @@ struct Scores {
     int rows = 0;   // rows of the bound score buffers: the batch of the first prefill after the binding (0: none yet)
     uint64_t* words;
 };
+// TOP-N / WATCHED-TOKEN LOG-PROBABILITIES (emmax_session_set_top_logprobs; sample.hip: emmax_top_logprobs_kernel): device words {top_ids,
+// top_lp, watch_lp, n_top, n_watch, max_new} naming the caller's buffers, and the session's copy of the watch list.  The host keeps the same
+// values for the copies a commit makes.  Off: none of it is touched and a step launches what it launches without
+struct TopLogprobs {
+    bool on = false;
+    int n_top = 0, n_watch = 0, max_new = 0;
+    int32_t* ids_out = nullptr;
+    float *lp_out = nullptr, *watch_out = nullptr;
+    uint64_t* words;      // [TOPLP_WORDS]
+    int32_t* watch_ids;   // [EMMAX_MAX_WATCH_IDS]
+};
 // BEAM SEARCH (emmax_session_set_beams; beam.hip): K beams per group, 0 = off.  Rows g K + k are the running beams of group g; the per-row
 // candidate lists of a step, HF's running / finished state, the groups' words, the page bookkeeping (spare page and copy list per row), the
 // trace [max_out][max_batch] and the resolved result.  Beams off: none of it is touched
@@ -209,6 +220,7 @@ struct emmax_session {
     Warpers warp;
     TokenRules rules;
     Scores scores;
+    TopLogprobs toplp;
     Beams beam;
     // SAMPLE GROUPS (emmax_session_set_sample_groups; step.hip: run_group_fork): N sampled rows per prefilled prompt, 0 = off.  Rows g N + j are
     // the samples of prompt g; the fork's copy list lives in the beams' (csrc / cdst / cntok: beams and groups exclude each other)

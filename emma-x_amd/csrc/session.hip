@@ -157,6 +157,9 @@ static void plan_session(emmax_session* s, Bump& b) {
         s->dq32 = (float*)b.bytes((int64_t)Bd * m->q_dim * 4);
         s->dact32 = (float*)b.bytes((int64_t)Bd * m->inter_p * 4);
     }
+    // top-N / watched log-probabilities: the words that name the caller's buffers and the watch list (last in the plan: every other offset stays)
+    s->toplp.words = (uint64_t*)b.bytes(TOPLP_WORDS * 8);
+    s->toplp.watch_ids = (int32_t*)b.bytes(EMMAX_MAX_WATCH_IDS * 4);
 }
 
 static int kv_format_now() { return emmax_tune().exact >= 2 ? KV_F32 : emmax_tune().exact == 1 ? KV_X24 : (emmax_tune().kv_fp8 ? KV_FP8 : KV_BF16); }

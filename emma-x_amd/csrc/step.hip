@@ -265,12 +265,12 @@ static void lmhead_params(emmax_session* s, int slot0, float* logits_out, GemvPa
 // how a step ends (the captured graph is keyed on it: the finish's parameters differ in each): bit 0 sampling, bit 1 processing, bit 2
 // scores.  0: the greedy finish (lm-head argmax partials); 1: the sampled finish; bit 1 or 2 set: the processing finish
 // beams on: bit 3, stop_on_eos in bit 4, K and the early-stopping mode above (the beam finish holds them by value)
-// warpers or token rules on (bits 13, 14): the EXT finish
-enum { FINISH_WARP = 1 << 13, FINISH_RULES = 1 << 14, FINISH_EXT = FINISH_WARP | FINISH_RULES, FINISH_ROWS = 6 | FINISH_EXT /* runs on the logit rows */ };
+// warpers or token rules on (bits 13, 14): the EXT finish; top-N / watched log-probabilities bound (bit 15): their launch ahead of the finish
+enum { FINISH_TOPLP = 1 << 15, FINISH_WARP = 1 << 13, FINISH_RULES = 1 << 14, FINISH_EXT = FINISH_WARP | FINISH_RULES, FINISH_ROWS = 6 | FINISH_EXT /* runs on the logit rows */ };
 static int finish_mode(const emmax_session* s) {
     return (s->samp.on ? 1 : 0) | (s->proc.on ? 2 : 0) | (s->scores.on ? 4 : 0) |
            (s->beam.K ? (8 | (s->beam.eos >= 0 ? 16 : 0) | (s->beam.K << 5) | (s->beam.es << 10) | (s->beam.lp_pos << 12)) : 0) |
-           (s->warp.on ? FINISH_WARP : 0) | (s->rules.on ? FINISH_RULES : 0);
+           (s->warp.on ? FINISH_WARP : 0) | (s->rules.on ? FINISH_RULES : 0) | (s->toplp.on ? FINISH_TOPLP : 0);
 }
 
 // the per-row state of rows slot0 .. slot0 + B that a finish updates
@@ -305,9 +305,23 @@ static void sampling_rows(emmax_session* s, int slot0, P& p) {
     p.seed = s->samp.seed + slot0; p.subseq = s->samp.sub + slot0;
 }
 
+// top-N / watched log-probabilities bound: the rows' entries at their generation index, from the raw logit rows the lm-head just wrote.  Its own
+// launch AHEAD of the finish: it reads n_out and done as the step found them (the finish advances both)
+static int launch_top_logprobs_step(emmax_session* s, int B, bool is_prefill, int slot0, const float* logits, hipStream_t st) {
+    if (!s->toplp.on) return 0;
+    TopLogprobParams p;
+    memset(&p, 0, sizeof(p));
+    p.logits = logits; p.ld = s->m->vocab; p.V = s->m->vocab;
+    p.words = s->toplp.words; p.watch_ids = s->toplp.watch_ids; p.row0 = slot0; p.is_prefill = is_prefill ? 1 : 0;
+    p.n_out = s->n_out + slot0; p.done = s->done + slot0; p.max_new_p = s->max_new_d + slot0;
+    KCHK(launch_top_logprobs(p, B, st));
+    return 0;
+}
+
 // finish of a SAMPLED step over rows slot0 .. slot0 + B: each row's draw from its complete fp32 logit row (the lm-head launch just before
 // wrote them, on the same stream), then the same bookkeeping
 static int launch_sampled_finish_step(emmax_session* s, int B, bool is_prefill, int slot0, const float* logits, hipStream_t st) {
+    if (int r = launch_top_logprobs_step(s, B, is_prefill, slot0, logits, st)) return r;
     SampleFinishParams p;
     memset(&p, 0, sizeof(p));
     finish_rows(s, B, is_prefill, slot0, p.f);
@@ -320,6 +334,7 @@ static int launch_sampled_finish_step(emmax_session* s, int B, bool is_prefill, 
 
 // finish of a step with logits processing or scores on: the processors, then the draw (sampling on) or the argmax, then the scores store
 static int launch_proc_finish_step(emmax_session* s, int B, bool is_prefill, int slot0, const float* logits, hipStream_t st) {
+    if (int r = launch_top_logprobs_step(s, B, is_prefill, slot0, logits, st)) return r;
     ExtFinishParams p;   // (warpers and token rules off: launched as its ProcFinishParams base)
     memset(&p, 0, sizeof(p));
     finish_rows(s, B, is_prefill, slot0, p.f);

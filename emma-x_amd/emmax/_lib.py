@@ -155,6 +155,10 @@ SIGNATURES = {
     "emmax_session_token_rules": (C.c_int, [_vp]),
     "emmax_op_sample_ext": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int,
                                       _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "emmax_op_top_logprobs": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "emmax_session_set_top_logprobs": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp]),
+    "emmax_session_clear_top_logprobs": (C.c_int, [_vp, _vp]),
+    "emmax_session_top_logprobs": (C.c_int, [_vp]),
     "emmax_session_set_beams": (C.c_int, [_vp, C.c_int, C.c_double, C.c_int, _vp]),
     "emmax_session_clear_beams": (C.c_int, [_vp, _vp]),
     "emmax_session_beams": (C.c_int, [_vp]),

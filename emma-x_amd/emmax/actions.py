@@ -51,6 +51,11 @@ def token_ids_to_actions(ids: np.ndarray, vocab_size: int, centers: np.ndarray) 
     return centers[idx]
 
 
+def action_bin_token_ids(vocab_size: int, n_bins: int = 256) -> List[int]:
+    """The token id of every action bin, in bin order: bin k is id vocab_size - 1 - k (the inverse of token_ids_to_actions' index)."""
+    return [int(vocab_size) - 1 - k for k in range(int(n_bins))]
+
+
 def unnormalize(normalized: np.ndarray, stats: Dict[str, Any], lo_key: str = "q01", hi_key: str = "q99") -> np.ndarray:
     """Map [-1,1] back to the dataset range on masked dimensions (gripper dimension passes through)."""
     lo, hi = np.array(stats[lo_key]), np.array(stats[hi_key])

@@ -135,6 +135,7 @@ class EmmaxEngine:
                        "emmax_session_create_ex")
         assert bool(self.lib.emmax_session_exact(self._session)) == bool(self.exact)
         self._score_bufs = None   # a new session binds no scores
+        self._top_bufs = None     # ... and no top / watched log-probability buffers
         self._beam_K = 0          # ... and has beams off
         self._group_N = 0         # ... and sample groups off
         self.max_batch, self.max_prompt, self.max_ctx, self.stage_rows = max_batch, max_prompt, max_ctx, int(stage_rows)
@@ -351,6 +352,7 @@ class EmmaxEngine:
     def clear_sampling(self) -> None:
         """Greedy again: the session launches exactly the kernels of one that never sampled."""
         _lib.check(self.lib.emmax_session_clear_sampling(self._session, _lib.current_stream()), "emmax_session_clear_sampling")
+        self._drop_unbound_top()
 
     @property
     def sampling(self) -> bool:
@@ -385,6 +387,7 @@ class EmmaxEngine:
     def clear_processing(self) -> None:
         """Processing off: with scores unbound and sampling off the session launches exactly what a greedy session launches."""
         _lib.check(self.lib.emmax_session_clear_processing(self._session, _lib.current_stream()), "emmax_session_clear_processing")
+        self._drop_unbound_top()
 
     @property
     def processing(self) -> bool:
@@ -452,6 +455,7 @@ class EmmaxEngine:
 
     def clear_token_rules(self) -> None:
         _lib.check(self.lib.emmax_session_clear_token_rules(self._session, _lib.current_stream()), "emmax_session_clear_token_rules")
+        self._drop_unbound_top()
 
     @property
     def token_rules(self) -> bool:
@@ -477,6 +481,52 @@ class EmmaxEngine:
                                                      logits.data_ptr() if logits is not None else None, int(max_new), _lib.current_stream()),
                    "emmax_session_set_scores")
         self._score_bufs = (scores, logits)
+
+    # ---- top-N and watched-token log-probabilities in the decode step (include/emmax.h: emmax_session_set_top_logprobs) ------
+    def set_top_logprobs(self, n_top: int, watch_ids: Optional[Sequence[int]] = None, max_new: int = 1):
+        """Bind buffers that every emitted token's top-`n_top` (id, log-probability) pairs and the log-probabilities of `watch_ids` are written
+        into, at [row, t]: top_ids int32 / top_logprobs fp32 [rows, max_new, n_top] and watch_logprobs fp32 [rows, max_new, W], rows =
+        max_batch + stage_rows (row = decode row or slot; staging row k = max_batch + k), filled with -1 / NaN: entries no token was emitted
+        for keep that.  Needs sampling or processing on (greedy rows: temperature 0) and no beams.  Returns the three tensors; the engine
+        keeps them alive while they are bound."""
+        from .sampling import check_top_logprobs
+
+        n, ids = check_top_logprobs(n_top, watch_ids, self.cfg.llm.vocab_size, "set_top_logprobs")
+        W, T, R = len(ids), int(max_new), self.max_batch + self.stage_rows
+        if n == 0 and W == 0:
+            raise ValueError("set_top_logprobs: neither top_logprobs nor watch_ids asked for (clear_top_logprobs unbinds)")
+        if T < 1:
+            raise ValueError(f"set_top_logprobs: max_new ({max_new}) must be >= 1")
+        bufs = (torch.full((R, T, n), -1, dtype=torch.int32, device=self.device), torch.full((R, T, n), float("nan"), dtype=torch.float32, device=self.device),
+                torch.full((R, T, W), float("nan"), dtype=torch.float32, device=self.device))
+        wi = (C.c_int32 * max(1, W))(*ids)
+        _lib.check(self.lib.emmax_session_set_top_logprobs(self._session, n, bufs[0].data_ptr() if n else None, bufs[1].data_ptr() if n else None, W,
+                                                           wi if W else None, bufs[2].data_ptr() if W else None, T, _lib.current_stream()),
+                   "emmax_session_set_top_logprobs")
+        self._top_bufs = bufs
+        return bufs
+
+    def _drop_unbound_top(self) -> None:
+        """(the library unbinds when the logit rows are turned off: the buffers are the caller's again)"""
+        if self._top_bufs is not None and not self.top_logprobs_bound:
+            self._top_bufs = None
+
+    def clear_top_logprobs(self) -> None:
+        """Unbind: the session launches what it launched before, and the buffers are the caller's."""
+        _lib.check(self.lib.emmax_session_clear_top_logprobs(self._session, _lib.current_stream()), "emmax_session_clear_top_logprobs")
+        self._top_bufs = None
+
+    def slot_top_logprobs(self, slot: int, n: int):
+        """The first n entries of row / slot `slot` of the bound buffers, on the host: (top ids [n][N], top log-probabilities [n][N],
+        watched log-probabilities [n][W]) as nested lists."""
+        if self._top_bufs is None:
+            raise _lib.EmmaxError("slot_top_logprobs: no buffers are bound (set_top_logprobs)")
+        torch.cuda.current_stream().synchronize()
+        return tuple(t[int(slot), : int(n)].cpu().tolist() for t in self._top_bufs)
+
+    @property
+    def top_logprobs_bound(self) -> bool:
+        return self.lib.emmax_session_top_logprobs(self._session) == 1
 
     # ---- beam search inside the decode step (include/emmax.h, ABI 9) ------------------------------------------------------
     def set_beams(self, params) -> None:

@@ -23,12 +23,12 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from .actions import ActionTokenizer, token_ids_to_actions, unnormalize
+from .actions import ActionTokenizer, action_bin_token_ids, token_ids_to_actions, unnormalize
 from .config import EmmaXConfig, check_decode_weight_dtype, default_norm_stats
 from .engine import EmmaxEngine
 from .policy_parser import Solver
 from .processing import BatchFeature, EmmaXImageProcessor
-from .sampling import MAX_DECODE_BATCH, BeamParams, LogitsProcessing, SamplingParams, draw_seed, fold_bad_words
+from .sampling import MAX_DECODE_BATCH, BeamParams, LogitsProcessing, SamplingParams, check_top_logprobs, draw_seed, fold_bad_words
 from .prompting import PurePromptBuilder
 from .tokenizer_stub import StubTokenizer
 from .weights import load_hf_state_dict, remap_native_state_dict, synthetic_state_dict, validate_state_dict
@@ -70,9 +70,27 @@ class EmmaXGenerateOutput:
     # [B * num_beams, vocab]: the rows the running beams read at each step
     sequences_scores: Optional[torch.Tensor] = None
     beam_indices: Optional[torch.Tensor] = None
+    # top_logprobs=N / watch_ids=[...]: per generated position the N most likely ids and their log-probabilities, int32 / fp32 [B, T, N], and
+    # the log-probabilities of the watched ids, fp32 [B, T, W] -- log_softmax of the RAW logits; past a row's length ids are -1, values NaN
+    top_token_ids: Optional[torch.Tensor] = None
+    top_logprobs: Optional[torch.Tensor] = None
+    watch_logprobs: Optional[torch.Tensor] = None
 
     def __getitem__(self, key: str):
         return getattr(self, key)
+
+
+@dataclass
+class TopLogprobsOutput:
+    """The trailing object of generate_ids(..., top_logprobs=N, watch_ids=[...]): device tensors over the B result rows.  top_ids int32 /
+    top_logprobs fp32 [B, max_new, N]: per emitted token the N most likely ids, best first (equal values by the lower id), and their
+    log-probabilities; watch_logprobs fp32 [B, max_new, W]: those of the watched ids; logprobs fp32 [B, max_new]: the emitted tokens' own.
+    All are log_softmax of the RAW logits (T = 1, unprocessed, unfiltered).  Entries past a row's length: ids -1, top / watched values
+    NaN, logprobs 0."""
+    top_ids: torch.Tensor
+    top_logprobs: torch.Tensor
+    watch_logprobs: torch.Tensor
+    logprobs: torch.Tensor
 
 
 class KVHandle:
@@ -255,7 +273,7 @@ class EmmaXForActionPrediction:
         return eng.vision_encode_pixels(pixel_values)
 
     def _prefill(self, rows: List[List[int]], pixel_values=None, frames_u8=None, max_new: int = 0, sampling=None, processing=None,
-                 scores=None, logits=None, beams: Optional[BeamParams] = None, num_samples: int = 1) -> torch.Tensor:
+                 scores=None, logits=None, beams: Optional[BeamParams] = None, num_samples: int = 1, top=None) -> torch.Tensor:
         eng = self._need_engine()
         B = len(rows)
         src = pixel_values if pixel_values is not None else frames_u8
@@ -279,6 +297,10 @@ class EmmaXForActionPrediction:
             eng.clear_sample_groups()   # (and beams cannot be set while groups are on)
         self._set_processing(eng, B * K, processing, scores, logits, max_new)
         self._set_sampling(eng, B * K, sampling)
+        if top is not None:   # (n_top, watch ids): bound behind sampling -- the launch reads the logit rows a sampled step writes
+            eng.set_top_logprobs(top[0], top[1], max(max_new, 1))
+        elif getattr(eng, "top_logprobs_bound", False):
+            eng.clear_top_logprobs()
         if beams is not None:   # B groups prefill once each and decode as B x K rows on shared KV pages
             eng.set_beams(beams)
         if N > 1:   # B prompts prefill once each and fork into B x N sampled rows on the prompt's KV pages
@@ -468,7 +490,7 @@ class EmmaXForActionPrediction:
     @torch.inference_mode()
     def generate_ids(self, rows: List[List[int]], pixel_values=None, frames_u8=None, max_new_tokens: int = 512,
                      stop_on_eos: bool = True, sampling=None, return_logprobs: bool = False, processing=None, scores=None, logits=None,
-                     beams: Optional[BeamParams] = None, num_samples: int = 1):
+                     beams: Optional[BeamParams] = None, num_samples: int = 1, top_logprobs: int = 0, watch_ids: Optional[Sequence[int]] = None):
         """Decode every row: greedy, or sampled in the step with `sampling` (one SamplingParams for all rows or one per row; row b draws
         with subseq b).  `processing` (one LogitsProcessing for all rows or one per row) applies HF's repetition penalty / n-gram ban /
         min-new-tokens in the step first.  `scores` / `logits`: fp32 [max_new, B, vocab] device buffers the step fills with HF's scores /
@@ -480,7 +502,15 @@ class EmmaXForActionPrediction:
         engine.beam_result() / beam_trace() hold the scores, beam_indices and the per-step trace.
         `num_samples` = N > 1 (needs `sampling`; no beams): every row is a prompt that is prefilled once and forked into N sampled rows on its
         KV pages.  The result has B x N rows -- row b N + j = sample j of prompt b, drawing with subseq b N + j by default -- `sampling` /
-        `processing` lists have one entry per result row (or one entry for all), and `scores` / `logits` are [max_new, B x N, vocab]."""
+        `processing` lists have one entry per result row (or one entry for all), and `scores` / `logits` are [max_new, B x N, vocab].
+        `top_logprobs` = n (1..20) and / or `watch_ids` (up to 256 ids): the return gains one trailing TopLogprobsOutput -- per emitted token the
+        n most likely ids with their log-probabilities and the log-probabilities of the watched ids, over the RAW logits, and the emitted
+        tokens' own.  A greedy call samples at temperature 0 underneath (the greedy ids) and is greedy again afterwards.  Works with
+        num_samples (B x N rows); not with beams."""
+        n_top, watch = check_top_logprobs(top_logprobs, watch_ids, self.config.llm.vocab_size, "generate_ids")
+        want_top = n_top > 0 or len(watch) > 0
+        if want_top and beams is not None:
+            raise NotImplementedError("top_logprobs / watch_ids with num_beams > 1 are outside the hot path (output_logits is served)")
         N = self._check_num_samples(num_samples)
         if N > 1:
             if beams is not None:
@@ -495,7 +525,7 @@ class EmmaXForActionPrediction:
                 raise ValueError("beams must be BeamParams")
             if sampling is not None or processing is not None or scores is not None:
                 raise ValueError("beams run without sampling, logits processing and scores")
-        if return_logprobs and sampling is None:
+        if return_logprobs and sampling is None and not want_top:
             raise ValueError("return_logprobs needs sampling (log-probabilities are kept by the sampled step only)")
         if processing is not None:
             ps = processing if isinstance(processing, (list, tuple)) else [processing]
@@ -503,12 +533,26 @@ class EmmaXForActionPrediction:
                 raise ValueError("processing must be LogitsProcessing (one, or one per row)")
         self._check_score_buffers(scores, logits, max_new_tokens, len(rows) * (beams.num_beams if beams is not None else N),
                                   self.config.llm.vocab_size)
-        self._prefill(rows, pixel_values, frames_u8, max_new=max_new_tokens, sampling=sampling, processing=processing, scores=scores,
-                      logits=logits, beams=beams, **self._sample_kw(N))
-        out = eng.generate(max_new_tokens, stop_on_eos, return_logprobs=return_logprobs)
+        if not want_top:
+            self._prefill(rows, pixel_values, frames_u8, max_new=max_new_tokens, sampling=sampling, processing=processing, scores=scores,
+                          logits=logits, beams=beams, **self._sample_kw(N))
+            out = eng.generate(max_new_tokens, stop_on_eos, return_logprobs=return_logprobs)
+            if scores is not None or logits is not None:
+                eng.set_scores(None, None)   # the buffers are the caller's now: no later step or prefill writes into them
+            return out
+        # a greedy caller: temperature-0 sampling underneath (the argmax of the same fp32 rows), so that the logit rows are written
+        self._prefill(rows, pixel_values, frames_u8, max_new=max_new_tokens, sampling=sampling if sampling is not None else SamplingParams(0.0, 0, 1.0, seed=0),
+                      processing=processing, scores=scores, logits=logits, top=(n_top, watch), **self._sample_kw(N))
+        ids, lens, lp = eng.generate(max_new_tokens, stop_on_eos, return_logprobs=True)
+        B = ids.shape[0]
+        ti, tl, wl = (t[:B] for t in eng._top_bufs)
+        eng.clear_top_logprobs()   # the state of before: the buffers are the caller's, and a greedy session is greedy again
         if scores is not None or logits is not None:
-            eng.set_scores(None, None)   # the buffers are the caller's now: no later step or prefill writes into them
-        return out
+            eng.set_scores(None, None)
+        if sampling is None:
+            eng.clear_sampling()
+        top = TopLogprobsOutput(top_ids=ti, top_logprobs=tl, watch_logprobs=wl, logprobs=lp)
+        return (ids, lens, lp, top) if return_logprobs else (ids, lens, top)
 
     def _max_new(self, rows, max_new_tokens, max_length, min_length, had_max_new: bool = True) -> int:
         """HF length semantics: `max_length` counts the PROMPT too (as HF counts it: the text ids, not the patch rows) and only
@@ -529,7 +573,8 @@ class EmmaXForActionPrediction:
                  min_length: int = 1, temperature: Optional[float] = None, frames_u8=None, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, seed: Optional[int] = None, generator: Optional[torch.Generator] = None,
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
-                 output_scores: bool = False, output_logits: bool = False, return_dict_in_generate: bool = False, **kwargs):
+                 output_scores: bool = False, output_logits: bool = False, return_dict_in_generate: bool = False, top_logprobs: int = 0,
+                 watch_ids: Optional[Sequence[int]] = None, **kwargs):
         """HF-style: returns LongTensor [B, P + T] = prompt ++ generated (right-padded with pad_token_id).  do_sample=True draws every token
         in the decode step (include/emmax.h: emmax_session_set_sampling) with temperature / top_k / top_p (HF defaults 1.0 / 50 / 1.0 when
         unset); row b draws with (seed, subseq b), seed None = draw_seed(generator).  With num_return_sequences=N the prompt is prefilled once
@@ -537,11 +582,18 @@ class EmmaXForActionPrediction:
         repetition_penalty / no_repeat_ngram_size /
         min_new_tokens / min_length are applied in the step as HF's processors (emmax_session_set_processing).  return_dict_in_generate=True
         returns an EmmaXGenerateOutput: `sequences` (the tensor), and with output_scores / output_logits a tuple of T = max(lens) fp32
-        [B, vocab] device tensors each (NaN past a row's length)."""
+        [B, vocab] device tensors each (NaN past a row's length).  top_logprobs=N / watch_ids=[...] (with return_dict_in_generate; not with
+        num_beams > 1): `top_token_ids` / `top_logprobs` [B, T, N] and `watch_logprobs` [B, T, W] of the output, over the RAW logits."""
+        n_top, watch = check_top_logprobs(top_logprobs, watch_ids, self.config.llm.vocab_size, "generate")
+        want_top = n_top > 0 or len(watch) > 0
+        if want_top and not return_dict_in_generate:
+            raise ValueError("top_logprobs / watch_ids are returned in the generate output: pass return_dict_in_generate=True")
         rows = self._rows(input_ids, attention_mask)
         processing = self._processing_args(rows, repetition_penalty, no_repeat_ngram_size, min_new_tokens, min_length, **self._kw_rules(kwargs))
         beams = self._beam_args(kwargs.get("num_beams"), kwargs.get("num_return_sequences"), kwargs.get("length_penalty"),
                                 kwargs.get("early_stopping"), do_sample, processing, bool(return_dict_in_generate and output_scores))
+        if want_top and beams is not None:
+            raise NotImplementedError("top_logprobs / watch_ids with num_beams > 1 are outside the hot path (output_logits is served)")
         N = self._sample_group_args(do_sample, kwargs.get("num_beams"), kwargs.get("num_return_sequences"))
         if len(rows) * N > MAX_DECODE_BATCH:
             raise ValueError(f"{len(rows)} prompts x {N} samples exceed the {MAX_DECODE_BATCH} rows of a decode batch")
@@ -555,8 +607,9 @@ class EmmaXForActionPrediction:
             shape = (max_new_tokens, len(rows) * K, self.config.llm.vocab_size)
             sc = torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device) if want_sc else None
             lg = torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device) if want_lg else None
-        new_ids, lens = self.generate_ids(rows, pixel_values, frames_u8, max_new_tokens, sampling=sampling, processing=processing, scores=sc,
-                                          logits=lg, **self._beam_kw(beams), **self._sample_kw(N))
+        res = self.generate_ids(rows, pixel_values, frames_u8, max_new_tokens, sampling=sampling, processing=processing, scores=sc,
+                                logits=lg, **self._beam_kw(beams), **self._sample_kw(N), **self._top_kw(n_top, watch))
+        new_ids, lens = res[0], res[1]
         if beams is not None:   # HF's layout: [B * num_return_sequences, P + T], best first per prompt
             R = beams.num_return_sequences
             keep = [g * K + k for g in range(len(rows)) for k in range(R)]
@@ -582,8 +635,16 @@ class EmmaXForActionPrediction:
             out[b, : len(seq)] = torch.tensor(seq, dtype=torch.long)
         if not return_dict_in_generate:
             return out
+        top = res[2] if want_top else None
         return EmmaXGenerateOutput(sequences=out, scores=tuple(sc[t] for t in range(T)) if want_sc else None,
-                                   logits=tuple(lg[t] for t in range(T)) if want_lg else None)
+                                   logits=tuple(lg[t] for t in range(T)) if want_lg else None,
+                                   top_token_ids=top.top_ids[:, :T] if n_top else None, top_logprobs=top.top_logprobs[:, :T] if n_top else None,
+                                   watch_logprobs=top.watch_logprobs[:, :T] if watch else None)
+
+    @staticmethod
+    def _top_kw(n_top: int, watch) -> Dict[str, Any]:
+        """generate_ids' `top_logprobs` / `watch_ids` arguments, passed only when asked for (a plain call is spelled exactly as before)."""
+        return {} if not n_top and not watch else {"top_logprobs": n_top, "watch_ids": list(watch) if watch else None}
 
     def _kw_processing(self, rows, kwargs) -> Optional[LogitsProcessing]:
         """The processor arguments of a **kwargs that the reference forwards to HF generate."""
@@ -605,8 +666,11 @@ class EmmaXForActionPrediction:
     # action APIs
     # ------------------------------------------------------------------------------------------------------------------
     @torch.inference_mode()
-    def predict_action(self, input_ids=None, unnorm_key: Optional[str] = None, **kwargs) -> np.ndarray:
-        """modeling_prismatic.py:506-537: append 29871 if missing, generate `action_dim` tokens, de-tokenise, un-normalise."""
+    def predict_action(self, input_ids=None, unnorm_key: Optional[str] = None, return_bin_logprobs: bool = False, **kwargs) -> np.ndarray:
+        """modeling_prismatic.py:506-537: append 29871 if missing, generate `action_dim` tokens, de-tokenise, un-normalise.
+        return_bin_logprobs=True returns (action, fp32 [action_dim, n_action_bins]): at each action token the log-probabilities of the action-bin
+        ids, renormalised over the bins, column k = bin k (actions.py: id vocab_size - 1 - k); [N, action_dim, n_action_bins] for a sample
+        group.  Not with num_beams > 1."""
         rows = self._rows(input_ids, kwargs.pop("attention_mask", None))
         if len(rows) != 1:
             raise ValueError("Generation with batch size > 1 is not currently supported!")   # reference contract
@@ -620,8 +684,12 @@ class EmmaXForActionPrediction:
         sampling = self._sampling_args(bool(kwargs.get("do_sample", False)), kwargs.get("temperature"), kwargs.get("top_k"), kwargs.get("top_p"),
                                        kwargs.get("seed"), kwargs.get("generator"), **self._kw_warpers(kwargs))
         N = self._sample_group_args(sampling is not None, kwargs.get("num_beams"), kwargs.get("num_return_sequences"))
-        new_ids, lens = self.generate_ids(rows, kwargs.get("pixel_values"), kwargs.get("frames_u8"), max_new_tokens=dim, sampling=sampling,
-                                          processing=processing, **self._beam_kw(beams), **self._sample_kw(N))
+        bin_ids = action_bin_token_ids(self.vocab_size, self.config.n_action_bins) if return_bin_logprobs else []
+        if return_bin_logprobs and beams is not None:
+            raise NotImplementedError("return_bin_logprobs with num_beams > 1 is outside the hot path")
+        res = self.generate_ids(rows, kwargs.get("pixel_values"), kwargs.get("frames_u8"), max_new_tokens=dim, sampling=sampling,
+                                processing=processing, **self._beam_kw(beams), **self._sample_kw(N), **self._top_kw(0, bin_ids))
+        new_ids, lens = res[0], res[1]
 
         def action(j):
             full = rows[0] + new_ids[j, : int(lens[j])].cpu().tolist()
@@ -629,7 +697,86 @@ class EmmaXForActionPrediction:
             return unnormalize(normalized, self.get_action_stats(unnorm_key))
 
         # do_sample=True with num_return_sequences=N > 1: the N sampled actions of the one observation, [N, action_dim]
-        return action(0) if N == 1 else np.stack([action(j) for j in range(N)])
+        acts = action(0) if N == 1 else np.stack([action(j) for j in range(N)])
+        if not return_bin_logprobs:
+            return acts
+        lp = self.renormalize_logprobs(res[2].watch_logprobs[:, :dim].cpu().numpy())   # [N, dim, n_action_bins]
+        return acts, (lp[0] if N == 1 else lp)
+
+    @staticmethod
+    def renormalize_logprobs(lp: np.ndarray) -> np.ndarray:
+        """log-probabilities of a subset of the vocabulary -> fp32 log-probabilities over that subset alone (last axis; float64 inside)"""
+        x = np.asarray(lp, dtype=np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            m = np.max(x, axis=-1, keepdims=True)
+            return (x - (m + np.log(np.sum(np.exp(x - m), axis=-1, keepdims=True)))).astype(np.float32)
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # generate_batch (prismatic/models/vlms/prismatic.py:524-595)
+    # ------------------------------------------------------------------------------------------------------------------
+    TRIGGER_STRINGS = ["True", "False", "Yes", "No"] + [chr(ord("A") + i) for i in range(26)]
+
+    def string2idx(self, tokenizer=None) -> Dict[str, List[int]]:
+        """The reference's trigger strings ("True", "False", "Yes", "No", "A" .. "Z") -> their token ids without special tokens
+        (prismatic.py:83-87).  The reference asserts one token each when the model is built; here the rule is enforced on the strings a call
+        asks for (generate_batch), since the offline stand-in tokenizer spells every string as several tokens."""
+        tok = tokenizer if tokenizer is not None else self.tokenizer
+        if tok is None:
+            raise ValueError("no tokenizer attached: the checkpoint directory holds no tokenizer files; set model.tokenizer")
+        return {s: [int(i) for i in tok.encode(s, add_special_tokens=False)] for s in self.TRIGGER_STRINGS}
+
+    @staticmethod
+    def string_probabilities(watch_logprobs_first: np.ndarray) -> List[float]:
+        """softmax(first position)[ids] / their sum, from the watched log-probabilities of that position (the lse cancels)"""
+        x = np.asarray(watch_logprobs_first, dtype=np.float64)
+        p = np.exp(x - np.max(x))
+        return (p / p.sum()).tolist()
+
+    @torch.inference_mode()
+    def generate_batch(self, pixel_values, texts: List[str], return_string_probabilities: Optional[List[str]] = None, **kwargs):
+        """The reference's PrismaticVLM.generate_batch: `pixel_values` is one image ([C, H, W] tensor or {"dino", "siglip"} dict of them) shared by
+        every text, or a batch with one image per text; **kwargs go to generate.  Returns the generated texts -- or, with
+        return_string_probabilities=[...] (trigger strings of string2idx, one token each), per text the probabilities the FIRST generated
+        position gives those strings' tokens, divided by their sum.  The texts run as one batch: each row equals its batch-1 result."""
+        tok = kwargs.pop("tokenizer", None)
+        tok = tok if tok is not None else self.tokenizer
+        if tok is None:
+            raise ValueError("no tokenizer attached: the checkpoint directory holds no tokenizer files; set model.tokenizer")
+        if isinstance(texts, str) or len(texts) < 1:
+            raise ValueError("generate_batch: `texts` is a non-empty list of strings")
+        watch: List[int] = []
+        if return_string_probabilities is not None:
+            table = self.string2idx(tok)
+            for st in return_string_probabilities:
+                if st not in table:
+                    raise ValueError(f'String "{st}" is not one of the trigger strings {self.TRIGGER_STRINGS}')
+                if len(table[st]) != 1:
+                    raise ValueError(f'String "{st}" is tokenized as more than one token!')
+                watch.append(table[st][0])
+            if not watch:
+                raise ValueError("generate_batch: return_string_probabilities names no string")
+        n = len(texts)
+
+        def batch(t):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"Unsupported `pixel_values` type = {type(t)}")
+            if t.ndim == 3:
+                return t[None].expand(n, *t.shape)
+            if t.ndim != 4 or t.shape[0] != n:
+                raise ValueError(f"generate_batch: one image for all texts or one per text, got {tuple(t.shape)} for {n} texts")
+            return t
+
+        if isinstance(pixel_values, dict):
+            pv = {k: batch(v) for k, v in pixel_values.items()}
+        else:
+            pv = batch(pixel_values)
+        rows = [self._rows(tok(t, truncation=True, return_tensors="pt").input_ids)[0] for t in texts]
+        if watch:
+            out = self.generate(rows, pv, return_dict_in_generate=True, watch_ids=watch, **kwargs)
+            first = out.watch_logprobs[:, 0].cpu().numpy()
+            return [self.string_probabilities(first[b]) for b in range(n)]
+        seqs = self.generate(rows, pv, **kwargs)
+        return [tok.decode(seqs[b, len(rows[b]):].tolist(), skip_special_tokens=True).strip() for b in range(n)]
 
     def _solver(self, tokenizer) -> Solver:
         return Solver(ActionTokenizer(tokenizer, bins=self.config.n_action_bins), verbose=False)

@@ -291,3 +291,52 @@ def sample_logits(logits: torch.Tensor, params: Union[SamplingParams, Sequence[S
     _lib.check(lib.emmax_op_sample(logits.data_ptr(), ld, B, V, temp.data_ptr(), top_k.data_ptr(), top_p.data_ptr(), seed_t.data_ptr(),
                                    sub_t.data_ptr(), step_t.data_ptr(), tok.data_ptr(), lp.data_ptr(), _lib.current_stream()), "emmax_op_sample")
     return tok, lp
+
+
+MAX_TOP_LOGPROBS = 20   # include/emmax.h: EMMAX_MAX_TOP_LOGPROBS
+MAX_WATCH_IDS = 256     # include/emmax.h: EMMAX_MAX_WATCH_IDS (the model's n_action_bins)
+
+
+def check_top_logprobs(n, watch_ids, vocab: Optional[int] = None, who: str = "top_logprobs") -> Tuple[int, list]:
+    """(N, watch list) as the library takes them, checked on the host: 0 <= N <= MAX_TOP_LOGPROBS (and <= vocab), at most MAX_WATCH_IDS ids,
+    each an integer in [0, vocab); None is no watch list.  Duplicates are allowed."""
+    if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= MAX_TOP_LOGPROBS:
+        raise ValueError(f"{who}: top_logprobs must be an integer in 0..{MAX_TOP_LOGPROBS}, got {n!r}")
+    if vocab is not None and n > vocab:
+        raise ValueError(f"{who}: top_logprobs {n} exceeds the {vocab} entries of a row")
+    ids = [] if watch_ids is None else list(watch_ids)
+    if len(ids) > MAX_WATCH_IDS:
+        raise ValueError(f"{who}: {len(ids)} watch ids (at most {MAX_WATCH_IDS})")
+    for i in ids:
+        if isinstance(i, bool) or not isinstance(i, int) or i < 0 or (vocab is not None and i >= vocab):
+            raise ValueError(f"{who}: watch id {i!r} is not an integer in 0..{'' if vocab is None else vocab - 1}")
+    return n, ids
+
+
+def top_logprobs(logits: torch.Tensor, n: int, watch_ids: Optional[Sequence[int]] = None):
+    """Top-n and watched-token log-probabilities of every row of `logits` (fp32 [B, V] on the device, V <= 32768) on the current stream
+    (include/emmax.h: emmax_op_top_logprobs).  Returns (top_ids int32 [B, n], top_logprobs fp32 [B, n], watch_logprobs fp32 [B, W]) on the
+    device: the n entries that are not NaN with the largest values, best first, equal values by the lower id, as (id, log_softmax(row)[id]);
+    places past the entries that are not NaN hold (-1, -inf); and log_softmax(row)[watch_ids]."""
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.device.type != "cuda":
+        raise ValueError("top_logprobs: logits must be a 2-D float32 tensor on a HIP device")
+    B, V = logits.shape
+    if B < 1 or not 1 <= V <= MAX_VOCAB:
+        raise ValueError(f"top_logprobs: {B} rows of {V} entries (1..{MAX_VOCAB})")
+    n, ids = check_top_logprobs(n, watch_ids, V)
+    if logits.stride(1) != 1 or (B > 1 and logits.stride(0) < V):
+        logits = logits.contiguous()
+    ld = logits.stride(0) if B > 1 else V
+    dev = logits.device
+    W = len(ids)
+    top_ids = torch.empty(B, n, dtype=torch.int32, device=dev)
+    top_lp = torch.empty(B, n, dtype=torch.float32, device=dev)
+    watch_lp = torch.empty(B, W, dtype=torch.float32, device=dev)
+    if n == 0 and W == 0:
+        return top_ids, top_lp, watch_lp
+    ids_t = torch.tensor(ids, dtype=torch.int32).to(dev) if W else None
+    lib = _lib.load()
+    _lib.check(lib.emmax_op_top_logprobs(logits.data_ptr(), ld, B, V, n, top_ids.data_ptr() if n else None, top_lp.data_ptr() if n else None, W,
+                                         ids_t.data_ptr() if W else None, watch_lp.data_ptr() if W else None, _lib.current_stream()),
+               "emmax_op_top_logprobs")
+    return top_ids, top_lp, watch_lp

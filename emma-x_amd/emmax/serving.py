@@ -33,6 +33,9 @@ class Request:
     beams: Any = None        # beam groups are not served as slots: a request with emmax.sampling.BeamParams is refused at submit
     num_samples: int = 1     # > 1: a sample group -- one prefill, forked into num_samples slots that read the prompt's KV pages; sample j draws
                              # with (the request's seed, subseq j), so sample 0 is what the request returns with num_samples = 1.  Needs sampling
+    top_logprobs: int = 0    # N in 1..20: every emitted token comes with the N most likely ids and their log-probabilities (RAW logits); 0 = off
+    watch_ids: Optional[Sequence[int]] = None   # ... and with the log-probabilities of these ids (up to 256).  One list per run: the requests
+                                                # that name a list name the same one
 
 
 @dataclass
@@ -45,6 +48,8 @@ class Result:
     t_done: float
     logprobs: Optional[List[float]] = None   # sampled requests: the log-probability of every emitted token
     sample: int = 0   # which sample of its request this is (Request.num_samples > 1: one Result per sample)
+    top_logprobs: Optional[List[List[tuple]]] = None   # Request.top_logprobs = N: per emitted token its N (id, logprob) pairs, best first
+    watch_logprobs: Optional[List[List[float]]] = None   # Request.watch_ids: per emitted token the log-probabilities of those ids
 
     @property
     def latency_s(self) -> float:
@@ -67,6 +72,7 @@ class SlotScheduler:
 
     engine   object with slots_open / slot_prefill / slots_step / slots_state / slot_output / slot_release / set_stop
              (emmax.engine.EmmaxEngine, or a fake in the CPU tests); slots_fork as well once a request asks for num_samples > 1
+             and set_top_logprobs / slot_top_logprobs / clear_top_logprobs once one asks for top_logprobs or watch_ids
     encode   frames (list) -> patch embeddings, one [n_patches, hidden] bf16 tensor per frame; called once per admission
              round with every frame admitted in that round, so the ViT runs batched
     n_slots  decode batch (<= 64; the engine's max_decode_batch())
@@ -112,6 +118,7 @@ class SlotScheduler:
         self._processing = False                     # some request of the current run has logits processing (run)
         self._warpers = False                        # ... min_p / typical_p / epsilon_cutoff / eta_cutoff (run)
         self._rules = False                          # ... token rules (run)
+        self._top = None                             # (N, watch list) bound for the current run, None when no request asks (run)
         # a staged batch is at most max(stage_batch, free slots) <= n_slots requests: the session needs that many staging rows
         # (they cost KV pages, so a session only has them when a scheduler asks: engine.ensure_stage_rows re-creates it if needed)
         if self.overlap and hasattr(engine, "ensure_stage_rows"):
@@ -136,6 +143,10 @@ class SlotScheduler:
             raise ValueError(f"num_samples {n} exceeds the scheduler's {self.n_slots} slots: a group's samples are admitted together")
         if n > 1 and (req.sampling is None or float(req.sampling.temperature) == 0.0):
             raise ValueError(f"num_samples {n} needs sampling: {n} greedy samples of one prompt would be identical (set Request.sampling with a temperature > 0)")
+        if getattr(req, "top_logprobs", 0) or getattr(req, "watch_ids", None) is not None:
+            from .sampling import check_top_logprobs
+
+            check_top_logprobs(req.top_logprobs, req.watch_ids, None, "Request")
         self.queue.append((req, self.clock()))
 
     def _sampling_rows(self, reqs):
@@ -318,8 +329,16 @@ class SlotScheduler:
                 a = self.active.pop(slot)
                 ids = self.engine.slot_output(slot, int(n_out[slot]))
                 lps = self.engine.slot_logprobs(slot, int(n_out[slot])) if a.req.sampling is not None else None
+                top = watch = None
+                n_top, ask_watch = getattr(a.req, "top_logprobs", 0), getattr(a.req, "watch_ids", None) is not None
+                if self._top is not None and (n_top or ask_watch):   # the run's binding holds max N pairs per token: this request's first N
+                    t_ids, t_lps, w_lps = self.engine.slot_top_logprobs(slot, int(n_out[slot]))
+                    if n_top:
+                        top = [[(int(i), float(v)) for i, v in zip(ri[:n_top], rv[:n_top])] for ri, rv in zip(t_ids, t_lps)]
+                    if ask_watch:
+                        watch = [[float(v) for v in row] for row in w_lps]
                 self.engine.slot_release(slot)
-                self.results.append(Result(a.req.rid, ids, slot, a.t_submit, a.t_admit, self.clock(), lps, a.sample))
+                self.results.append(Result(a.req.rid, ids, slot, a.t_submit, a.t_admit, self.clock(), lps, a.sample, top, watch))
                 n += 1
         return n
 
@@ -331,16 +350,43 @@ class SlotScheduler:
         self._warpers = any(r.sampling is not None and getattr(r.sampling, "has_warpers", False) for r, _ in self.queue)
         with_rules = [r.processing for r, _ in self.queue if getattr(r, "processing", None) is not None and getattr(r.processing, "rule_enable", 0)]
         self._rules = bool(with_rules)
+        self._top = self._top_of_run()
+        if self._top is not None:
+            self._sampling = True   # the binding reads the logit rows a sampling session writes: greedy requests at temperature 0
         try:
+            if self._top is not None:   # bound once for the run, behind sampling on every slot (each admission sets its rows' own again)
+                from .sampling import SamplingParams
+
+                greedy = SamplingParams(temperature=0.0, top_k=0, top_p=1.0, seed=0)
+                self.engine.set_sampling([greedy] * self.n_slots, [0] * self.n_slots, [0] * self.n_slots, row0=0)
+                self.engine.set_top_logprobs(self._top[0], self._top[1], max(int(r.max_new_tokens) for r, _ in self.queue))
             if self._rules:   # one rule table for the run (the requests that name a kind name the same rules); every row starts opted out
                 self.engine.set_token_rules(with_rules, enables=False)
                 self.engine.set_rule_enables([0] * self.n_slots)
             return self._run()
         finally:
+            if self._top is not None:
+                self.engine.clear_top_logprobs()
+                self._top = None
             if self._processing:
                 self.engine.clear_processing()
             if self._sampling:
                 self.engine.clear_sampling()
+
+    def _top_of_run(self):
+        """(N, watch list) the run binds: N = the largest top_logprobs a queued request asks for (each Result is trimmed to its own), and the
+        one watch list the requests name -- two different lists are a ValueError, as two rule tables are.  None: no request asks, and the
+        run calls no engine method it did not call before."""
+        n, watch = 0, None
+        for r, _ in self.queue:
+            n = max(n, int(getattr(r, "top_logprobs", 0) or 0))
+            w = getattr(r, "watch_ids", None)
+            if w is not None:
+                w = [int(i) for i in w]
+                if watch is not None and w != watch:
+                    raise ValueError(f"request {r.rid!r} names a watch list that differs from another request's: a run serves one list")
+                watch = w
+        return None if n == 0 and not watch else (n, watch or [])
 
     def _run(self) -> List[Result]:
         if self.overlap:

@@ -44,7 +44,9 @@ extern "C" {
  *   own dispatch), the workspace grew that op's per-row scratch;  11: emmax_config.decode_fp8 = 2 selects MXFP4 decode weights (the struct keeps
  *   its layout), emmax_op_quant_mxfp4 / emmax_op_dequant_mxfp4 / emmax_op_gemm_small_mxfp4;  12: the prefill's stage kernels one by one (emmax_op_gemm_stream, emmax_op_rmsnorm_f32,
  *   emmax_op_rope_kv_write, emmax_op_kv_quant_rows, emmax_op_embed_splice, emmax_op_gather_last_rows): new symbols only; still 12: MXFP4 at 17-64 rows
- *   (tuning switch mx4_wide, emmax_model_mxfp4_wide, emmax_op_gemm_wide_mxfp4): new symbols only. */
+ *   (tuning switch mx4_wide, emmax_model_mxfp4_wide, emmax_op_gemm_wide_mxfp4): new symbols only; still 12: top-N and watched-token
+ *   log-probabilities (emmax_op_top_logprobs, emmax_session_set_top_logprobs and the calls around it): new symbols only, the workspace grew
+ *   their six device words and the watch list (1.3 KB). */
 #define EMMAX_ABI_VERSION 12
 
 typedef enum emmax_status {
@@ -849,6 +851,48 @@ int emmax_op_x_join(const void* hl_dev, float* out32_dev, int rows, int D, emmax
 int emmax_op_x_decode_attention(const float* q32_dev, const void* kcache_dev, const void* vcache_dev, int64_t kv24_elems, const int32_t* page_table_dev,
                                 const int32_t* ctx_len_dev, const int32_t* done_dev, float* part_out_dev, int B, int Hq, int Hkv, int page, int max_pages,
                                 int nsplit, float scale, emmax_stream stream);
+
+/* ---- top-N and watched-token log-probabilities (new symbols, same ABI) ---------------------------------------------------------
+ * A short, fixed-size slice of the distribution a row's token was drawn from, over the RAW fp32 lm-head row l of V entries (T = 1,
+ * unprocessed, unfiltered: the meaning of the chosen token's log-probability, ABI 6 / 7):
+ *   lse        m + logf(sum expf(l_i - m)), m = max l, in the sampling kernel's fixed order: the bits of emmax_op_sample's.
+ *   top N      1 <= N <= EMMAX_MAX_TOP_LOGPROBS, N <= V.  The entries that are not NaN, ordered by l_i descending, equal fp32 values (+0 = -0)
+ *              by the lower id; the first N as (id, fp32(l_i - lse)).  -inf entries are ordinary candidates with log-probability -inf.  Fewer
+ *              than N entries that are not NaN: the remaining places are (-1, -inf).  A row that holds a NaN has lse = NaN, and so every
+ *              entry's log-probability; the ids are still the order above.
+ *   watched    one list of 0 <= W <= EMMAX_MAX_WATCH_IDS ids in [0, V) (256 = the model's n_action_bins: the whole action-bin range fits),
+ *              duplicates allowed: watch_lp[w] = fp32(l[id_w] - lse).
+ * The emitted token's entry, where it is among them, has exactly the bits of emmax_session_logprobs.  No float atomics: the same inputs give
+ * the same bits, whatever the row's place in the batch or B.
+ *   emmax_op_top_logprobs           the kernel on its own over rows logits_dev [B][ld] (as emmax_op_sample): top_ids_out / top_lp_out [B][n_top],
+ *                                   watch_lp_out [B][n_watch], watch_ids_dev [n_watch] (device; its values are the caller's to check).  Either
+ *                                   part may be off (n_top = 0 / n_watch = 0: its pointers are not read).  EMMAX_ERR_INVALID for a null pointer
+ *                                   of a part that is on, n_top or n_watch outside the caps, n_top > V, V outside 1..32768 or ld < V.
+ *   emmax_session_set_top_logprobs  binds caller-owned device buffers top_ids_dev int32 / top_lp_dev fp32 [R][max_new][n_top] and watch_lp_dev
+ *                                   fp32 [R][max_new][n_watch], R = max_batch + emmax_session_stage_rows (row index = the decode row or slot;
+ *                                   staging row k is row max_batch + k); the library allocates nothing.  From then on every lm-head that emits
+ *                                   a token -- prefills, decode steps eager and replayed, emmax_generate, emmax_slots_step -- is followed by
+ *                                   one launch that writes entry [row][t] of each row that emits a token at generation index t (0: the token
+ *                                   a prefill emits).  A row that is done, idle or out of budget writes nothing, nor does t >= max_new: such
+ *                                   entries keep what the caller put there.  The step graph is keyed on bound / not bound; the buffers, N, W,
+ *                                   max_new and the watch list are device words (a change re-captures nothing; the call synchronises the
+ *                                   stream).  watch_ids_host is checked against the model's vocabulary.  EMMAX_ERR_INVALID: a cap, a null
+ *                                   pointer of a part that is on, both parts off, a watch id outside [0, V), max_new outside 1..max_ctx.
+ *                                   EMMAX_ERR_STATE: beams on, or the session does not write its logit rows (neither sampling nor logits
+ *                                   processing on; greedy rows sample at temperature 0).  The binding survives emmax_slots_open and prefills
+ *                                   of any batch size; emmax_session_clear_sampling / emmax_session_clear_processing / emmax_session_clear_
+ *                                   token_rules unbind when they turn the logit rows off, and emmax_session_set_beams is EMMAX_ERR_STATE
+ *                                   while bound.  emmax_slots_commit copies a staged request's entry 0 to its slot; emmax_slots_fork and
+ *                                   sample groups give every follower the entry 0 of the prompt's one logit row.
+ *   emmax_session_clear_top_logprobs  unbinds: the session launches what it launched before.  emmax_session_top_logprobs: 1 / 0 / -1 (null). */
+#define EMMAX_MAX_TOP_LOGPROBS 20
+#define EMMAX_MAX_WATCH_IDS 256
+int emmax_op_top_logprobs(const float* logits_dev, int ld, int B, int V, int n_top, int32_t* top_ids_out_dev, float* top_lp_out_dev, int n_watch,
+                          const int32_t* watch_ids_dev, float* watch_lp_out_dev, emmax_stream stream);
+int emmax_session_set_top_logprobs(emmax_session* s, int n_top, int32_t* top_ids_dev, float* top_lp_dev, int n_watch, const int32_t* watch_ids_host,
+                                   float* watch_lp_dev, int max_new, emmax_stream stream);
+int emmax_session_clear_top_logprobs(emmax_session* s, emmax_stream stream);
+int emmax_session_top_logprobs(const emmax_session* s);
 
 #ifdef __cplusplus
 }
