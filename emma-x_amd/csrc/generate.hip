@@ -239,6 +239,7 @@ int emmax_slots_commit(emmax_session* s, const int32_t* staged_idx_host, const i
     }
     if (s->warp.on) { c.warp[0] = s->warp.minp; c.warp[1] = s->warp.typ; c.warp[2] = s->warp.eps; c.warp[3] = s->warp.eta; }
     if (s->rules.on) c.rule_en = s->rules.en;
+    if (s->aut.on) { c.aut_start = s->aut.start; c.aut_state = s->aut.state; }
     StreamScope sc(s, stream);
     if (sc.error()) return sc.error();
     KCHK(launch_slots_commit(c, sc.stream()));

@@ -135,6 +135,7 @@ struct CommitParams {
     // warpers / token rules on (else null): the rows' four warper values and their rule enable word move too
     float* warp[4];
     uint32_t* rule_en;
+    int32_t *aut_start, *aut_state;   // an automaton is set (else null): the rows' start and state move too
 };
 int launch_slots_commit(const CommitParams& c, hipStream_t stream);
 // emmax_slots_fork: the freshly prefilled slot `src` forked into the n idle slots dst[] (one block per follower).  Follower f hides its own
@@ -159,6 +160,7 @@ struct SlotForkParams {
     int32_t *ngram, *min_new, *hist, *hist_len;
     float* warp[4];   // warpers / token rules on (else null): a follower takes the source's
     uint32_t* rule_en;
+    int32_t *aut_start, *aut_state;   // an automaton is set (else null): a follower enters at the source's start state
 };
 int launch_slots_fork(const SlotForkParams& p, hipStream_t stream);
 // table[i] = hidden[i], hidden[i] = -1 wherever hidden[i] >= 0, i < n: a released follower takes its own pages back (its two rows), an
@@ -515,6 +517,21 @@ struct ExtFinishParams : ProcFinishParams {
     float* scores_out;          // [B][V] or null
 };
 int launch_ext_finish(const ExtFinishParams& p, hipStream_t stream);
+// the CONSTRAINED form of the EXT finish (include/emmax.h: emmax_session_set_automaton; emmax_op_sample_constrained): a token automaton over
+// token classes joins the bans.  A row in state s >= 0 keeps the ids whose class bit is set in allow[s] (every other id becomes -inf with the
+// n-gram ban), and the one thread that ends the row moves it to next[s][cls[tok]] (-1: the row is done after this token).  A state outside
+// 0 .. n_states allows nothing.  Its own instantiation again: a session without an automaton never launches it
+#define EMMAX_MAX_AUT_STATES 1024
+#define EMMAX_MAX_AUT_CLASSES 256
+struct ConFinishParams : ExtFinishParams {
+    const uint8_t* cls;         // [V] class of every id (read as dwords where four ids of a lane's group lie below V)
+    const uint32_t* allow;      // [n_states][8] bit c: class c is allowed
+    const int16_t* next;        // [n_states][next_ld]
+    int n_states, next_ld;
+    int32_t* state;             // [B] in / out; -1: the row is unconstrained
+    int32_t* state_out;         // (the op form) [B] the state after the token, state is read only; null: state is updated in place
+};
+int launch_con_finish(const ConFinishParams& p, hipStream_t stream);
 // top-N and watched-token log-probabilities of rows of fp32 logits (include/emmax.h: emmax_op_top_logprobs / emmax_session_set_top_logprobs):
 // one 1024-thread block per row, over the RAW row -- lse as emmax_sample_kernel computes it, the first n_top non-NaN entries by (value
 // descending, id ascending) as (id, l - lse), and l[watch_ids[w]] - lse.

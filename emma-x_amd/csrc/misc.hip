@@ -346,6 +346,7 @@ __global__ __launch_bounds__(256) void emmax_slots_commit_kernel(CommitParams c)
         if (c.warp[0])
             for (int k = 0; k < 4; ++k) c.warp[k][dst] = c.warp[k][src];
         if (c.rule_en) c.rule_en[dst] = c.rule_en[src];
+        if (c.aut_start) { c.aut_start[dst] = c.aut_start[src]; c.aut_state[dst] = c.aut_state[src]; }
         c.done[src] = 1; c.ctx_len[src] = 0;
     }
 }
@@ -372,6 +373,7 @@ __global__ __launch_bounds__(256) void emmax_slots_fork_kernel(SlotForkParams p)
         if (p.warp[0])
             for (int k = 0; k < 4; ++k) p.warp[k][f] = p.warp[k][src];
         if (p.rule_en) p.rule_en[f] = p.rule_en[src];
+        if (p.aut_start) { p.aut_start[f] = p.aut_start[src]; p.aut_state[f] = p.aut_start[src]; }
         const bool cp = rem > 0 && nfull < mp;   // (page nfull is past the shared ones: both rows still hold their own entry there)
         p.copy_src[j] = cp ? theirs[nfull] : -1;
         p.copy_dst[j] = cp ? mine[nfull] : -1;

@@ -86,7 +86,7 @@ static int set_processing_rows(emmax_session* s, int row0, int n, bool staged, c
     if (sc.error()) return sc.error();
     if (int r = upload_rows(s, r0, n, sc.stream(), {{s->proc.pen, pen, 4}, {s->proc.ng, ng, 4}, {s->proc.mn, mn, 4}})) return r;
     s->proc.on = true;
-    if (!staged) s->rules.implied_proc = false;   // the caller's own processing now: clearing the token rules leaves it on
+    if (!staged) s->rules.implied_proc = s->aut.implied_proc = false;   // the caller's own processing now: clearing the token rules or the automaton leaves it on
     return sc.leave();
 }
 
@@ -209,13 +209,110 @@ int emmax_slots_set_rule_enables_staged(emmax_session* s, int n, const uint32_t*
 
 int emmax_session_clear_token_rules(emmax_session* s, emmax_stream) {
     if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (s->rules.on && s->rules.implied_proc) s->proc.on = false;
+    if (s->rules.on && s->rules.implied_proc) {
+        if (s->aut.on) s->aut.implied_proc = true;   // the automaton still needs the neutral processing: it is its to turn off now
+        else s->proc.on = false;
+    }
     if (!s->samp.on && !s->proc.on) (void)emmax_session_clear_top_logprobs(s, nullptr);
     s->rules.on = s->rules.implied_proc = false;
     return 0;
 }
 
 int emmax_session_token_rules(const emmax_session* s) { return s ? (s->rules.on ? 1 : 0) : -1; }
+
+// ---- the token automaton (new symbols, same ABI) --------------------------------------------------------------------------------
+static int set_automaton_start_rows(emmax_session* s, int row0, int n, bool staged, const int32_t* start, emmax_stream stream) {
+    if (!s || !start) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (int r = check_rows(s, row0, n, staged)) return r;
+    if (!s->aut.on) return fail(EMMAX_ERR_STATE, "no token automaton is set (emmax_session_set_automaton)");
+    const int r0 = staged ? s->stg0 : row0;
+    for (int i = 0; i < n; ++i)
+        if (start[i] < -1 || start[i] >= s->aut.n_states) return fail(EMMAX_ERR_INVALID, "row %d: start state %d outside -1..%d", r0 + i, start[i], s->aut.n_states - 1);
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    if (int r = upload_rows(s, r0, n, sc.stream(), {{s->aut.start, start, 4}})) return r;
+    return sc.leave();
+}
+
+int emmax_session_set_automaton(emmax_session* s, int n_states, int n_classes, const uint8_t* cls_host, const uint32_t* allow_host, const int16_t* next_host,
+                                emmax_stream stream) {
+    if (!s || !cls_host || !allow_host || !next_host) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (n_states < 1 || n_states > EMMAX_MAX_AUT_STATES) return fail(EMMAX_ERR_INVALID, "%d automaton states outside 1..%d", n_states, EMMAX_MAX_AUT_STATES);
+    if (n_classes < 1 || n_classes > EMMAX_MAX_AUT_CLASSES) return fail(EMMAX_ERR_INVALID, "%d token classes outside 1..%d", n_classes, EMMAX_MAX_AUT_CLASSES);
+    const int V = s->m->vocab;
+    if (V > EMMAX_SAMPLE_MAX_V) return fail(EMMAX_ERR_INVALID, "a token automaton takes vocabularies of up to %d entries (%d)", EMMAX_SAMPLE_MAX_V, V);
+    for (int i = 0; i < V; ++i)
+        if (cls_host[i] >= n_classes) return fail(EMMAX_ERR_INVALID, "token %d: class %d outside 0..%d", i, (int)cls_host[i], n_classes - 1);
+    for (int st = 0; st < n_states; ++st)
+        for (int c = 0; c < n_classes; ++c) {
+            const int v = next_host[(size_t)st * n_classes + c];
+            if (v < -1 || v >= n_states) return fail(EMMAX_ERR_INVALID, "state %d, class %d: next state %d outside -1..%d", st, c, v, n_states - 1);
+        }
+    if (s->beam.K) return fail(EMMAX_ERR_STATE, "a token automaton is not available while beams are on");
+    // the device layout: full-size tables, rows of next at EMMAX_MAX_AUT_CLASSES; what the table does not have allows nothing and ends the row
+    std::vector<uint8_t> cls((size_t)EMMAX_SAMPLE_MAX_V, 0);
+    std::vector<uint32_t> allow((size_t)EMMAX_MAX_AUT_STATES * 8, 0u);
+    std::vector<int16_t> next((size_t)EMMAX_MAX_AUT_STATES * EMMAX_MAX_AUT_CLASSES, (int16_t)-1);
+    memcpy(cls.data(), cls_host, (size_t)V);
+    for (int st = 0; st < n_states; ++st) {
+        for (int c = 0; c < n_classes; ++c) {
+            if ((allow_host[(size_t)st * 8 + (c >> 5)] >> (c & 31)) & 1u) allow[(size_t)st * 8 + (c >> 5)] |= 1u << (c & 31);
+            next[(size_t)st * EMMAX_MAX_AUT_CLASSES + c] = next_host[(size_t)st * n_classes + c];
+        }
+    }
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    HIPCHK(hipStreamSynchronize(sc.stream()));   // no step reads the table while it changes
+    HIPCHK(hipMemcpy(s->aut.cls, cls.data(), cls.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->aut.allow, allow.data(), allow.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->aut.next, next.data(), next.size() * 2, hipMemcpyHostToDevice));
+    if (!s->aut.on) {   // every row starts unconstrained; the mask is a processor: processing on, neutral where it was off
+        HIPCHK(hipMemset(s->aut.start, 0xff, (size_t)s->rows_total * 4));
+        HIPCHK(hipMemset(s->aut.state, 0xff, (size_t)s->rows_total * 4));
+        if (!s->proc.on) {
+            std::vector<float> one((size_t)s->rows_total, 1.f);
+            HIPCHK(hipMemcpy(s->proc.pen, one.data(), one.size() * 4, hipMemcpyHostToDevice));
+            HIPCHK(hipMemset(s->proc.ng, 0, (size_t)s->rows_total * 4));
+            HIPCHK(hipMemset(s->proc.mn, 0, (size_t)s->rows_total * 4));
+            s->proc.on = true;
+            s->aut.implied_proc = true;
+        }
+    }
+    s->aut.on = true;
+    s->aut.n_states = n_states; s->aut.n_classes = n_classes;
+    return sc.leave();
+}
+
+int emmax_session_set_automaton_starts(emmax_session* s, int row0, int n, const int32_t* start_host, emmax_stream stream) {
+    return set_automaton_start_rows(s, row0, n, false, start_host, stream);
+}
+
+int emmax_slots_set_automaton_starts_staged(emmax_session* s, int n, const int32_t* start_host, emmax_stream stream) {
+    return set_automaton_start_rows(s, 0, n, true, start_host, stream);
+}
+
+int emmax_session_clear_automaton(emmax_session* s, emmax_stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (s->aut.on && s->aut.implied_proc) {
+        if (s->rules.on) s->rules.implied_proc = true;   // the token rules still need the neutral processing: it is theirs to turn off now
+        else s->proc.on = false;
+    }
+    if (!s->samp.on && !s->proc.on) (void)emmax_session_clear_top_logprobs(s, nullptr);
+    s->aut.on = s->aut.implied_proc = false;
+    return 0;
+}
+
+int emmax_session_automaton(const emmax_session* s) { return s ? (s->aut.on ? 1 : 0) : -1; }
+
+int emmax_session_automaton_state(emmax_session* s, int row0, int n, int32_t* state_out_dev, emmax_stream stream) {
+    if (!s || !state_out_dev) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->aut.on) return fail(EMMAX_ERR_STATE, "no token automaton is set (emmax_session_set_automaton)");
+    if (n < 1 || row0 < 0 || row0 + n > s->rows_total) return fail(EMMAX_ERR_INVALID, "rows %d..%d outside 0..%d", row0, row0 + n - 1, s->rows_total - 1);
+    StreamScope sc(s, stream);
+    if (sc.error()) return sc.error();
+    HIPCHK(hipMemcpyAsync(state_out_dev, s->aut.state + row0, (size_t)n * 4, hipMemcpyDeviceToDevice, sc.stream()));
+    return sc.leave();
+}
 
 int emmax_session_set_stop(emmax_session* s, const int32_t* trigger_ids, int n_trigger, int n_after, emmax_stream stream) {
     if (!s || (n_trigger > 0 && !trigger_ids)) return fail(EMMAX_ERR_INVALID, "null argument");
@@ -284,6 +381,7 @@ int emmax_session_clear_processing(emmax_session* s, emmax_stream) {
     if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
     s->proc.on = false;
     s->rules.on = s->rules.implied_proc = false;   // the token rules are processors (the table stays on the device; set it again to use it)
+    s->aut.on = s->aut.implied_proc = false;       // ... and so is the automaton's mask
     if (!s->samp.on) (void)emmax_session_clear_top_logprobs(s, nullptr);   // no logit rows are written any more
     return 0;
 }
@@ -359,6 +457,7 @@ int emmax_session_set_beams(emmax_session* s, int num_beams, double length_penal
         return fail(EMMAX_ERR_INVALID, "beams take vocabularies of %d..%d entries (%d)", 2 * num_beams, EMMAX_SAMPLE_MAX_V, s->m->vocab);
     if (s->slots_open) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while request slots are open");
     if (s->grp_N) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while sample groups are on (emmax_session_clear_sample_groups)");
+    if (s->aut.on) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while a token automaton is set (emmax_session_clear_automaton)");
     if (s->samp.on || s->proc.on || s->warp.on || s->rules.on) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while sampling or logits processing is on");
     if (s->scores.on && s->scores.has_scores) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while a scores buffer is bound");
     if (s->toplp.on) return fail(EMMAX_ERR_STATE, "beams cannot be turned on while top log-probabilities are bound (emmax_session_clear_top_logprobs)");

@@ -105,6 +105,38 @@ int emmax_op_sample_ext(const float* logits, int ld, int B, int V, const float* 
     KCHK(launch_ext_finish(p, (hipStream_t)stream));
     return 0;
 }
+int emmax_op_sample_constrained(const float* logits, int ld, int B, int V, const float* temperature, const int32_t* top_k, const float* top_p,
+                                const uint64_t* seed, const uint32_t* subseq, const int32_t* n_out, const float* min_p, const float* typical_p,
+                                const float* epsilon_cutoff, const float* eta_cutoff, const float* penalty, const int32_t* ngram, const int32_t* min_new,
+                                const int32_t* hist, const int32_t* hist_len, int max_hist, int n_rules, const int32_t* rule_off, const int32_t* rule_ids,
+                                const int32_t* rule_flags, const float* rule_bias, const uint32_t* rule_enable, int eos_id, int pad_id, int n_states,
+                                int n_classes, const uint8_t* cls, const uint32_t* allow, const int16_t* next, const int32_t* state, int32_t* tok_out,
+                                float* logprob_out, int32_t* state_out, float* scores_out, emmax_stream stream) {
+    if (!logits || !temperature || !top_k || !top_p || !seed || !subseq || !n_out || !tok_out || !logprob_out) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!cls || !allow || !next || !state || !state_out) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (B < 1 || V < 1 || V > EMMAX_SAMPLE_MAX_V || ld < V)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_sample_constrained: B %d (>= 1), V %d (1..%d), ld %d (>= V)", B, V, EMMAX_SAMPLE_MAX_V, ld);
+    if (n_states < 1 || n_states > EMMAX_MAX_AUT_STATES || n_classes < 1 || n_classes > EMMAX_MAX_AUT_CLASSES)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_sample_constrained: %d states (1..%d), %d classes (1..%d)", n_states, EMMAX_MAX_AUT_STATES, n_classes, EMMAX_MAX_AUT_CLASSES);
+    const bool warp = min_p || typical_p || epsilon_cutoff || eta_cutoff;
+    if (warp && (!min_p || !typical_p || !epsilon_cutoff || !eta_cutoff)) return fail(EMMAX_ERR_INVALID, "emmax_op_sample_constrained: the four warper arrays come together");
+    if (!penalty || !ngram || !min_new || !hist || !hist_len || max_hist < 1)
+        return fail(EMMAX_ERR_INVALID, "emmax_op_sample_constrained: the mask is a processor: it needs the processor arrays and the histories (max_hist >= 1)");
+    if (n_rules < 0 || n_rules > EMMAX_MAX_RULES) return fail(EMMAX_ERR_INVALID, "%d token rules outside 0..%d", n_rules, EMMAX_MAX_RULES);
+    if (n_rules > 0 && (!rule_off || !rule_ids || !rule_flags || !rule_bias || !rule_enable))
+        return fail(EMMAX_ERR_INVALID, "emmax_op_sample_constrained: token rules need the table's five arrays");
+    ConFinishParams p;
+    memset(&p, 0, sizeof(p));
+    p.f.B = B; p.f.n_out = (int32_t*)n_out; p.f.is_prefill = 1; p.f.max_out = 0; p.f.eos_id = eos_id; p.f.pad_id = pad_id;
+    p.logits = logits; p.ld = ld; p.V = V; p.temperature = temperature; p.top_k = top_k; p.top_p = top_p; p.seed = seed; p.subseq = subseq;
+    p.min_p = min_p; p.typical_p = typical_p; p.eps_cut = epsilon_cutoff; p.eta_cut = eta_cutoff;
+    p.penalty = penalty; p.ngram = ngram; p.min_new = min_new; p.hist = hist; p.hist_len = hist_len; p.max_prompt = max_hist;
+    if (n_rules > 0) { p.rt.n_host = n_rules; p.rt.off = rule_off; p.rt.ids = rule_ids; p.rt.flags = rule_flags; p.rt.bias = rule_bias; p.rule_en = rule_enable; }
+    p.tok_out = tok_out; p.logprob_out = logprob_out; p.scores_out = scores_out;
+    p.cls = cls; p.allow = allow; p.next = next; p.n_states = n_states; p.next_ld = n_classes; p.state = (int32_t*)state; p.state_out = state_out;
+    KCHK(launch_con_finish(p, (hipStream_t)stream));
+    return 0;
+}
 int emmax_op_gemm(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K, const void* bias, int act,
                   const void* scale, const void* residual, int ldr, int out_f32, emmax_stream st) {
     GemmParams p = gp(A, lda, W, ldw, C, ldc, M, N, K);

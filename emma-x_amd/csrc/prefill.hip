@@ -112,6 +112,10 @@ int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B
     }
     if (total > s->max_rows) return fail(EMMAX_ERR_NOMEM, "packed prefill rows %d exceed capacity %d", total, s->max_rows);
     KCHK(launch_prefill_state(ps, s->cu, s->ctx_len + r0, s->done + r0, s->n_out + r0, s->max_new_d + r0, s->stop_m + r0, s->stop_after + r0, st));
+    if (s->aut.on) {   // the rows enter the automaton at their start states (sample groups: the B x N rows the prefill forks into)
+        const int rows = s->grp_N && !slot_mode ? B * s->grp_N : B;
+        HIPCHK(hipMemcpyAsync(s->aut.state + r0, s->aut.start + r0, (size_t)rows * 4, hipMemcpyDeviceToDevice, st));
+    }
     if (s->scores.on && !slot_mode && !s->beam.K) {   // the score buffers' rows: the first prefill after the binding's; another batch size unbinds them
         const int rows = s->grp_N ? B * s->grp_N : B;   // (sample groups: the B x N rows the prefill forks into)
         if (s->scores.rows == 0) {

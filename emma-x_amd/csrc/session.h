@@ -154,6 +154,20 @@ struct TokenRules {
     float* bias;
     uint32_t* en;                // [rows_total]
 };
+// TOKEN AUTOMATON (emmax_session_set_automaton): the session's one automaton over token classes -- cls [EMMAX_SAMPLE_MAX_V] (the tail stays
+// zero: a lane reads four class bytes as a dword), allow [EMMAX_MAX_AUT_STATES][8], next [EMMAX_MAX_AUT_STATES][EMMAX_MAX_AUT_CLASSES] -- at full
+// size behind stable pointers, so that another table re-captures nothing; per row, staging rows included, the start state (-1: unconstrained)
+// and the state, which every prefill that restarts the row sets to its start.  On: a step ends in the CON finish (sample_con.hip).  Off: none of it
+// is touched
+struct Automaton {
+    bool on = false;
+    bool implied_proc = false;   // the automaton turned processing on with neutral values: clearing it turns it off again
+    int n_states = 0, n_classes = 0;
+    uint8_t* cls;
+    uint32_t* allow;
+    int16_t* next;
+    int32_t *start, *state;      // [rows_total]
+};
 // SCORES (emmax_session_set_scores): device words {scores, logits, max_new, rows} the processing finish stores through.  Processing or scores
 // on: the step runs on the logit rows and ends in the processing finish.  Both off: none of it is touched
 struct Scores {
@@ -219,6 +233,7 @@ struct emmax_session {
     Processing proc;
     Warpers warp;
     TokenRules rules;
+    Automaton aut;
     Scores scores;
     TopLogprobs toplp;
     Beams beam;

@@ -160,6 +160,12 @@ static void plan_session(emmax_session* s, Bump& b) {
     // top-N / watched log-probabilities: the words that name the caller's buffers and the watch list (last in the plan: every other offset stays)
     s->toplp.words = (uint64_t*)b.bytes(TOPLP_WORDS * 8);
     s->toplp.watch_ids = (int32_t*)b.bytes(EMMAX_MAX_WATCH_IDS * 4);
+    // the token automaton (behind them for the same reason)
+    s->aut.cls = (uint8_t*)b.bytes(EMMAX_SAMPLE_MAX_V);
+    s->aut.allow = (uint32_t*)b.bytes((int64_t)EMMAX_MAX_AUT_STATES * 8 * 4);
+    s->aut.next = (int16_t*)b.bytes((int64_t)EMMAX_MAX_AUT_STATES * EMMAX_MAX_AUT_CLASSES * 2);
+    s->aut.start = (int32_t*)b.bytes(Br * 4);
+    s->aut.state = (int32_t*)b.bytes(Br * 4);
 }
 
 static int kv_format_now() { return emmax_tune().exact >= 2 ? KV_F32 : emmax_tune().exact == 1 ? KV_X24 : (emmax_tune().kv_fp8 ? KV_FP8 : KV_BF16); }

@@ -266,11 +266,14 @@ static void lmhead_params(emmax_session* s, int slot0, float* logits_out, GemvPa
 // scores.  0: the greedy finish (lm-head argmax partials); 1: the sampled finish; bit 1 or 2 set: the processing finish
 // beams on: bit 3, stop_on_eos in bit 4, K and the early-stopping mode above (the beam finish holds them by value)
 // warpers or token rules on (bits 13, 14): the EXT finish; top-N / watched log-probabilities bound (bit 15): their launch ahead of the finish
-enum { FINISH_TOPLP = 1 << 15, FINISH_WARP = 1 << 13, FINISH_RULES = 1 << 14, FINISH_EXT = FINISH_WARP | FINISH_RULES, FINISH_ROWS = 6 | FINISH_EXT /* runs on the logit rows */ };
+// a token automaton set (bit 16): the CON finish
+enum { FINISH_TOPLP = 1 << 15, FINISH_WARP = 1 << 13, FINISH_RULES = 1 << 14, FINISH_AUT = 1 << 16, FINISH_EXT = FINISH_WARP | FINISH_RULES | FINISH_AUT,
+       FINISH_ROWS = 6 | FINISH_EXT /* runs on the logit rows */ };
 static int finish_mode(const emmax_session* s) {
     return (s->samp.on ? 1 : 0) | (s->proc.on ? 2 : 0) | (s->scores.on ? 4 : 0) |
            (s->beam.K ? (8 | (s->beam.eos >= 0 ? 16 : 0) | (s->beam.K << 5) | (s->beam.es << 10) | (s->beam.lp_pos << 12)) : 0) |
-           (s->warp.on ? FINISH_WARP : 0) | (s->rules.on ? FINISH_RULES : 0) | (s->toplp.on ? FINISH_TOPLP : 0);
+           (s->warp.on ? FINISH_WARP : 0) | (s->rules.on ? FINISH_RULES : 0) | (s->toplp.on ? FINISH_TOPLP : 0) |
+           (s->aut.on ? FINISH_AUT : 0);
 }
 
 // the per-row state of rows slot0 .. slot0 + B that a finish updates
@@ -335,7 +338,7 @@ static int launch_sampled_finish_step(emmax_session* s, int B, bool is_prefill, 
 // finish of a step with logits processing or scores on: the processors, then the draw (sampling on) or the argmax, then the scores store
 static int launch_proc_finish_step(emmax_session* s, int B, bool is_prefill, int slot0, const float* logits, hipStream_t st) {
     if (int r = launch_top_logprobs_step(s, B, is_prefill, slot0, logits, st)) return r;
-    ExtFinishParams p;   // (warpers and token rules off: launched as its ProcFinishParams base)
+    ConFinishParams p;   // (no automaton: launched as its ExtFinishParams base; warpers and token rules off too: as its ProcFinishParams base)
     memset(&p, 0, sizeof(p));
     finish_rows(s, B, is_prefill, slot0, p.f);
     p.logits = logits; p.ld = s->m->vocab; p.V = s->m->vocab;
@@ -347,7 +350,7 @@ static int launch_proc_finish_step(emmax_session* s, int B, bool is_prefill, int
         p.hist = s->proc.hist + (size_t)slot0 * s->max_prompt; p.hist_len = s->proc.hist_len + slot0; p.max_prompt = s->max_prompt;
     }
     if (s->scores.on) p.score_words = s->scores.words;
-    if (!s->warp.on && !s->rules.on) {
+    if (!s->warp.on && !s->rules.on && !s->aut.on) {
         KCHK(launch_proc_finish(p, st));
         return 0;
     }
@@ -355,6 +358,12 @@ static int launch_proc_finish_step(emmax_session* s, int B, bool is_prefill, int
     if (s->rules.on) {
         p.rt.n = s->rules.n; p.rt.off = s->rules.off; p.rt.ids = s->rules.ids; p.rt.flags = s->rules.flags; p.rt.bias = s->rules.bias;
         p.rule_en = s->rules.en + slot0;
+    }
+    if (s->aut.on) {
+        p.cls = s->aut.cls; p.allow = s->aut.allow; p.next = s->aut.next; p.n_states = EMMAX_MAX_AUT_STATES; p.next_ld = EMMAX_MAX_AUT_CLASSES;
+        p.state = s->aut.state + slot0;
+        KCHK(launch_con_finish(p, st));
+        return 0;
     }
     KCHK(launch_ext_finish(p, st));
     return 0;
@@ -488,6 +497,7 @@ int run_slots_fork(emmax_session* s, int src, int logit_row, const int32_t* dst,
     if (s->proc.on) { f.penalty = s->proc.pen; f.ngram = s->proc.ng; f.min_new = s->proc.mn; f.hist = s->proc.hist; f.hist_len = s->proc.hist_len; }
     if (s->warp.on) { f.warp[0] = s->warp.minp; f.warp[1] = s->warp.typ; f.warp[2] = s->warp.eps; f.warp[3] = s->warp.eta; }
     if (s->rules.on) f.rule_en = s->rules.en;
+    if (s->aut.on) { f.aut_start = s->aut.start; f.aut_state = s->aut.state; }
     KCHK(launch_slots_fork(f, st));
     if (f.S % PAGE != 0)   // (else the prompt ends on a page boundary: every page is shared by reference, nothing to copy)
         if (int r = launch_page_copies(s, n, st)) return r;

@@ -155,6 +155,14 @@ SIGNATURES = {
     "emmax_session_token_rules": (C.c_int, [_vp]),
     "emmax_op_sample_ext": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int,
                                       _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "emmax_session_set_automaton": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "emmax_session_set_automaton_starts": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    "emmax_slots_set_automaton_starts_staged": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "emmax_session_clear_automaton": (C.c_int, [_vp, _vp]),
+    "emmax_session_automaton": (C.c_int, [_vp]),
+    "emmax_session_automaton_state": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    "emmax_op_sample_constrained": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                                              C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "emmax_op_top_logprobs": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "emmax_session_set_top_logprobs": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp]),
     "emmax_session_clear_top_logprobs": (C.c_int, [_vp, _vp]),

@@ -461,6 +461,48 @@ class EmmaxEngine:
     def token_rules(self) -> bool:
         return self.lib.emmax_session_token_rules(self._session) == 1
 
+    # ---- constrained decoding: a token automaton in the decode step (include/emmax.h: emmax_session_set_automaton) ----------------
+    def set_automaton(self, automaton) -> None:
+        """The session's token automaton (constraints.TokenAutomaton; turns processing on with neutral values where it was off).  The first
+        one leaves every row unconstrained: set_automaton_starts says which rows enter it, and where.  Another table re-captures nothing."""
+        a = automaton
+        if getattr(self, "_automaton_set", None) is a and self.automaton:   # this very object is on the device and still on: nothing to upload
+            return                                                            # (a set automaton's tables are not to be changed in place)
+        if a.vocab != self.cfg.llm.vocab_size:
+            raise ValueError(f"set_automaton: the automaton is over {a.vocab} ids, the model's vocabulary has {self.cfg.llm.vocab_size}")
+        cls, allow, nxt = a.tables()
+        _lib.check(self.lib.emmax_session_set_automaton(self._session, a.n_states, a.n_classes, cls.ctypes.data, allow.ctypes.data, nxt.ctypes.data,
+                                                        _lib.current_stream()), "emmax_session_set_automaton")
+        self._automaton_set = a
+
+    def set_automaton_starts(self, starts: Sequence[int], row0: int = 0) -> None:
+        """Rows row0..: the state each enters the automaton at with its next prefill (-1: unconstrained)."""
+        k = len(starts)
+        _lib.check(self.lib.emmax_session_set_automaton_starts(self._session, int(row0), k, (C.c_int32 * k)(*[int(v) for v in starts]), _lib.current_stream()),
+                   "emmax_session_set_automaton_starts")
+
+    def set_automaton_starts_staged(self, starts: Sequence[int]) -> None:
+        """set_automaton_starts for the requests of the next slots_prefill_staged."""
+        k = len(starts)
+        _lib.check(self.lib.emmax_slots_set_automaton_starts_staged(self._session, k, (C.c_int32 * k)(*[int(v) for v in starts]), _lib.current_stream()),
+                   "emmax_slots_set_automaton_starts_staged")
+
+    def clear_automaton(self) -> None:
+        _lib.check(self.lib.emmax_session_clear_automaton(self._session, _lib.current_stream()), "emmax_session_clear_automaton")
+        self._automaton_set = None
+        self._drop_unbound_top()
+
+    @property
+    def automaton(self) -> bool:
+        return self.lib.emmax_session_automaton(self._session) == 1
+
+    def automaton_state(self, row0: int = 0, n: int = 1) -> List[int]:
+        """The automaton states of rows row0 .. row0 + n - 1 (staging row k = max_batch + k); synchronises with the device."""
+        out = torch.empty(int(n), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.emmax_session_automaton_state(self._session, int(row0), int(n), out.data_ptr(), _lib.current_stream()),
+                   "emmax_session_automaton_state")
+        return out.cpu().tolist()
+
     def set_scores(self, scores: Optional[torch.Tensor], logits: Optional[torch.Tensor], max_new: int = 0, rows: int = 0) -> None:
         """Bind fp32 [max_new, rows, vocab] device buffers that the decode step fills with HF's `scores` (processed rows) / `logits` (raw
         rows) at each emitted token's index; `rows` must be the batch of the next prefill (the step stores row b of that batch at [t, b]).

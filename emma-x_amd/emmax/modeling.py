@@ -273,7 +273,8 @@ class EmmaXForActionPrediction:
         return eng.vision_encode_pixels(pixel_values)
 
     def _prefill(self, rows: List[List[int]], pixel_values=None, frames_u8=None, max_new: int = 0, sampling=None, processing=None,
-                 scores=None, logits=None, beams: Optional[BeamParams] = None, num_samples: int = 1, top=None) -> torch.Tensor:
+                 scores=None, logits=None, beams: Optional[BeamParams] = None, num_samples: int = 1, top=None, constraint=None,
+                 constraint_start=None) -> torch.Tensor:
         eng = self._need_engine()
         B = len(rows)
         src = pixel_values if pixel_values is not None else frames_u8
@@ -295,12 +296,20 @@ class EmmaXForActionPrediction:
             eng.clear_beams()   # (first: sampling / processing cannot be set while beams are on)
         if N == 1 and getattr(eng, "sample_groups", 0):
             eng.clear_sample_groups()   # (and beams cannot be set while groups are on)
-        self._set_processing(eng, B * K, processing, scores, logits, max_new)
+        # the call's automaton is the one the session holds: processing, which that automaton may have turned on with neutral values, is set
+        # to neutral values instead of cleared (clearing it turns the automaton off, and the tables would be uploaded again for every call)
+        keep = constraint is not None and processing is None and getattr(eng, "_automaton_set", None) is constraint and getattr(eng, "automaton", False)
+        self._set_processing(eng, B * K, LogitsProcessing() if keep else processing, scores, logits, max_new)
         self._set_sampling(eng, B * K, sampling)
         if top is not None:   # (n_top, watch ids): bound behind sampling -- the launch reads the logit rows a sampled step writes
             eng.set_top_logprobs(top[0], top[1], max(max_new, 1))
         elif getattr(eng, "top_logprobs_bound", False):
             eng.clear_top_logprobs()
+        if constraint is not None:   # behind processing: clearing that clears the automaton, and setting one turns neutral processing on
+            eng.set_automaton(constraint)
+            eng.set_automaton_starts(constraint.starts(constraint_start, B * K))
+        elif getattr(eng, "automaton", False):
+            eng.clear_automaton()
         if beams is not None:   # B groups prefill once each and decode as B x K rows on shared KV pages
             eng.set_beams(beams)
         if N > 1:   # B prompts prefill once each and fork into B x N sampled rows on the prompt's KV pages
@@ -490,7 +499,8 @@ class EmmaXForActionPrediction:
     @torch.inference_mode()
     def generate_ids(self, rows: List[List[int]], pixel_values=None, frames_u8=None, max_new_tokens: int = 512,
                      stop_on_eos: bool = True, sampling=None, return_logprobs: bool = False, processing=None, scores=None, logits=None,
-                     beams: Optional[BeamParams] = None, num_samples: int = 1, top_logprobs: int = 0, watch_ids: Optional[Sequence[int]] = None):
+                     beams: Optional[BeamParams] = None, num_samples: int = 1, top_logprobs: int = 0, watch_ids: Optional[Sequence[int]] = None,
+                     constraint=None, constraint_start=None):
         """Decode every row: greedy, or sampled in the step with `sampling` (one SamplingParams for all rows or one per row; row b draws
         with subseq b).  `processing` (one LogitsProcessing for all rows or one per row) applies HF's repetition penalty / n-gram ban /
         min-new-tokens in the step first.  `scores` / `logits`: fp32 [max_new, B, vocab] device buffers the step fills with HF's scores /
@@ -506,7 +516,13 @@ class EmmaXForActionPrediction:
         `top_logprobs` = n (1..20) and / or `watch_ids` (up to 256 ids): the return gains one trailing TopLogprobsOutput -- per emitted token the
         n most likely ids with their log-probabilities and the log-probabilities of the watched ids, over the RAW logits, and the emitted
         tokens' own.  A greedy call samples at temperature 0 underneath (the greedy ids) and is greedy again afterwards.  Works with
-        num_samples (B x N rows); not with beams."""
+        num_samples (B x N rows); not with beams.
+        `constraint` (constraints.TokenAutomaton): constrained decoding in the step -- a row in automaton state s can only emit the ids that
+        state allows (HF's prefix_allowed_tokens_fn, compiled).  `constraint_start`: None = every row enters at the automaton's entry "start"
+        (state 0 without one), a name / state = every row there, a list = one per result row (None in it: that row is unconstrained).  Works
+        greedy, sampled and with num_samples; not with beams.  Scores are -inf at the ids the automaton forbids; log-probabilities stay raw."""
+        cst = self._check_constraint(constraint, constraint_start, beams.num_beams if beams is not None else 1,
+                                     len(rows) * self._check_num_samples(num_samples))
         n_top, watch = check_top_logprobs(top_logprobs, watch_ids, self.config.llm.vocab_size, "generate_ids")
         want_top = n_top > 0 or len(watch) > 0
         if want_top and beams is not None:
@@ -535,14 +551,14 @@ class EmmaXForActionPrediction:
                                   self.config.llm.vocab_size)
         if not want_top:
             self._prefill(rows, pixel_values, frames_u8, max_new=max_new_tokens, sampling=sampling, processing=processing, scores=scores,
-                          logits=logits, beams=beams, **self._sample_kw(N))
+                          logits=logits, beams=beams, **self._sample_kw(N), **cst)
             out = eng.generate(max_new_tokens, stop_on_eos, return_logprobs=return_logprobs)
             if scores is not None or logits is not None:
                 eng.set_scores(None, None)   # the buffers are the caller's now: no later step or prefill writes into them
             return out
         # a greedy caller: temperature-0 sampling underneath (the argmax of the same fp32 rows), so that the logit rows are written
         self._prefill(rows, pixel_values, frames_u8, max_new=max_new_tokens, sampling=sampling if sampling is not None else SamplingParams(0.0, 0, 1.0, seed=0),
-                      processing=processing, scores=scores, logits=logits, top=(n_top, watch), **self._sample_kw(N))
+                      processing=processing, scores=scores, logits=logits, top=(n_top, watch), **self._sample_kw(N), **cst)
         ids, lens, lp = eng.generate(max_new_tokens, stop_on_eos, return_logprobs=True)
         B = ids.shape[0]
         ti, tl, wl = (t[:B] for t in eng._top_bufs)
@@ -553,6 +569,47 @@ class EmmaXForActionPrediction:
             eng.clear_sampling()
         top = TopLogprobsOutput(top_ids=ti, top_logprobs=tl, watch_logprobs=wl, logprobs=lp)
         return (ids, lens, lp, top) if return_logprobs else (ids, lens, top)
+
+    def _check_constraint(self, constraint, constraint_start, num_beams: int, n_rows: int) -> Dict[str, Any]:
+        """`constraint` / `constraint_start` of a call, checked before the engine is touched -> _prefill's keywords ({}: no constraint)."""
+        from .constraints import TokenAutomaton
+
+        if constraint is None:
+            if constraint_start is not None:
+                raise ValueError("constraint_start needs constraint= (a constraints.TokenAutomaton)")
+            return {}
+        if not isinstance(constraint, TokenAutomaton):
+            raise ValueError("constraint must be a constraints.TokenAutomaton (constraints.build / action_bins / policy_line make one)")
+        if num_beams > 1:
+            raise NotImplementedError("constraint= with num_beams > 1 is outside the hot path (the automaton runs in the greedy and sampled finish)")
+        if constraint.vocab != self.config.llm.vocab_size:
+            raise ValueError(f"the constraint is over {constraint.vocab} ids, the model's vocabulary has {self.config.llm.vocab_size}")
+        constraint.starts(constraint_start, n_rows)   # (validates)
+        return {"constraint": constraint, "constraint_start": constraint_start}
+
+    def _bin_automaton(self, dim: int):
+        """constraints.action_bins for `dim` action tokens of this model, built once per (vocabulary, bins, dim, tokenizer vocabulary): the
+        same object every call, so the session keeps its tables."""
+        from .constraints import action_bins
+
+        key = (self.config.llm.vocab_size, self.config.n_action_bins, int(dim), self.vocab_size)
+        cache = self.__dict__.setdefault("_bin_automata", {})
+        if key not in cache:
+            cache[key] = action_bins(key[0], key[1], key[2], token_vocab=key[3])
+        return cache[key]
+
+    def _kw_constraint(self, kwargs) -> Dict[str, Any]:
+        """The constraint arguments of a **kwargs, passed on only when given; prefix_allowed_tokens_fn (a Python callback per row per step cannot
+        run inside the step) points at them."""
+        if kwargs.get("prefix_allowed_tokens_fn") is not None:
+            raise NotImplementedError("prefix_allowed_tokens_fn is a Python callback per row and step and cannot run in the decode step: compile the "
+                                      "constraint into a constraints.TokenAutomaton and pass constraint= (and constraint_start=)")
+        if kwargs.get("constraint") is None and kwargs.get("constraint_start") is None:
+            return {}
+        nb = kwargs.get("num_beams")
+        if kwargs.get("constraint") is not None and nb is not None and nb != 1:
+            raise NotImplementedError("constraint= with num_beams > 1 is outside the hot path (the automaton runs in the greedy and sampled finish)")
+        return {"constraint": kwargs.get("constraint"), "constraint_start": kwargs.get("constraint_start")}
 
     def _max_new(self, rows, max_new_tokens, max_length, min_length, had_max_new: bool = True) -> int:
         """HF length semantics: `max_length` counts the PROMPT too (as HF counts it: the text ids, not the patch rows) and only
@@ -582,12 +639,14 @@ class EmmaXForActionPrediction:
         repetition_penalty / no_repeat_ngram_size /
         min_new_tokens / min_length are applied in the step as HF's processors (emmax_session_set_processing).  return_dict_in_generate=True
         returns an EmmaXGenerateOutput: `sequences` (the tensor), and with output_scores / output_logits a tuple of T = max(lens) fp32
-        [B, vocab] device tensors each (NaN past a row's length).  top_logprobs=N / watch_ids=[...] (with return_dict_in_generate; not with
+        [B, vocab] device tensors each (NaN past a row's length).  constraint= (a constraints.TokenAutomaton) and constraint_start= constrain the
+        rows in the step as generate_ids describes (sample groups are served; num_beams > 1 and prefix_allowed_tokens_fn= raise).  top_logprobs=N / watch_ids=[...] (with return_dict_in_generate; not with
         num_beams > 1): `top_token_ids` / `top_logprobs` [B, T, N] and `watch_logprobs` [B, T, W] of the output, over the RAW logits."""
         n_top, watch = check_top_logprobs(top_logprobs, watch_ids, self.config.llm.vocab_size, "generate")
         want_top = n_top > 0 or len(watch) > 0
         if want_top and not return_dict_in_generate:
             raise ValueError("top_logprobs / watch_ids are returned in the generate output: pass return_dict_in_generate=True")
+        cst = self._kw_constraint(kwargs)   # (before the engine is touched: num_beams > 1 and prefix_allowed_tokens_fn raise here)
         rows = self._rows(input_ids, attention_mask)
         processing = self._processing_args(rows, repetition_penalty, no_repeat_ngram_size, min_new_tokens, min_length, **self._kw_rules(kwargs))
         beams = self._beam_args(kwargs.get("num_beams"), kwargs.get("num_return_sequences"), kwargs.get("length_penalty"),
@@ -608,7 +667,7 @@ class EmmaXForActionPrediction:
             sc = torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device) if want_sc else None
             lg = torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device) if want_lg else None
         res = self.generate_ids(rows, pixel_values, frames_u8, max_new_tokens, sampling=sampling, processing=processing, scores=sc,
-                                logits=lg, **self._beam_kw(beams), **self._sample_kw(N), **self._top_kw(n_top, watch))
+                                logits=lg, **self._beam_kw(beams), **self._sample_kw(N), **self._top_kw(n_top, watch), **cst)
         new_ids, lens = res[0], res[1]
         if beams is not None:   # HF's layout: [B * num_return_sequences, P + T], best first per prompt
             R = beams.num_return_sequences
@@ -666,11 +725,15 @@ class EmmaXForActionPrediction:
     # action APIs
     # ------------------------------------------------------------------------------------------------------------------
     @torch.inference_mode()
-    def predict_action(self, input_ids=None, unnorm_key: Optional[str] = None, return_bin_logprobs: bool = False, **kwargs) -> np.ndarray:
+    def predict_action(self, input_ids=None, unnorm_key: Optional[str] = None, return_bin_logprobs: bool = False, constrain_to_bins: bool = False,
+                       **kwargs) -> np.ndarray:
         """modeling_prismatic.py:506-537: append 29871 if missing, generate `action_dim` tokens, de-tokenise, un-normalise.
         return_bin_logprobs=True returns (action, fp32 [action_dim, n_action_bins]): at each action token the log-probabilities of the action-bin
         ids, renormalised over the bins, column k = bin k (actions.py: id vocab_size - 1 - k); [N, action_dim, n_action_bins] for a sample
-        group.  Not with num_beams > 1."""
+        group.  Not with num_beams > 1.
+        constrain_to_bins=True: every one of the `action_dim` tokens is an action-bin id (constraints.action_bins in the decode step; a token
+        outside the bins would be mapped to a wrong bin unnoticed).  Also with return_bin_logprobs and num_return_sequences=N; not with
+        num_beams > 1."""
         rows = self._rows(input_ids, kwargs.pop("attention_mask", None))
         if len(rows) != 1:
             raise ValueError("Generation with batch size > 1 is not currently supported!")   # reference contract
@@ -687,8 +750,15 @@ class EmmaXForActionPrediction:
         bin_ids = action_bin_token_ids(self.vocab_size, self.config.n_action_bins) if return_bin_logprobs else []
         if return_bin_logprobs and beams is not None:
             raise NotImplementedError("return_bin_logprobs with num_beams > 1 is outside the hot path")
+        cst = self._kw_constraint(kwargs)
+        if constrain_to_bins:
+            if beams is not None:
+                raise NotImplementedError("constrain_to_bins with num_beams > 1 is outside the hot path")
+            if cst:
+                raise ValueError("constrain_to_bins builds its own constraint: pass one of constrain_to_bins= and constraint=")
+            cst = {"constraint": self._bin_automaton(dim)}
         res = self.generate_ids(rows, kwargs.get("pixel_values"), kwargs.get("frames_u8"), max_new_tokens=dim, sampling=sampling,
-                                processing=processing, **self._beam_kw(beams), **self._sample_kw(N), **self._top_kw(0, bin_ids))
+                                processing=processing, **self._beam_kw(beams), **self._sample_kw(N), **self._top_kw(0, bin_ids), **cst)
         new_ids, lens = res[0], res[1]
 
         def action(j):
@@ -825,7 +895,7 @@ class EmmaXForActionPrediction:
             beams = self._kw_beams(kwargs, processing)   # num_beams > 1: the best hypothesis (row 0 of the group) is decoded
             max_new = self._max_new(rows, kwargs.get("max_new_tokens", None if "max_length" in kwargs else 512), kwargs.get("max_length"), None)
             new_ids, lens = self.generate_ids(rows, inputs.get("pixel_values"), inputs.get("frames_u8"), max_new_tokens=max_new,
-                                              processing=processing, **self._beam_kw(beams))
+                                              processing=processing, **self._beam_kw(beams), **self._kw_constraint(kwargs))
             actions, text = self._postprocess(new_ids[0, : int(lens[0])].cpu().tolist(), tokenizer, "act")
             return actions[0], text
         # native form
@@ -855,7 +925,7 @@ class EmmaXForActionPrediction:
         max_new = self._max_new(rows, kwargs.get("max_new_tokens"), kwargs.get("max_length"), None)
         feat = self.image_transform(vals["image"])
         new_ids, lens = self.generate_ids(rows, feat["pixel_values"], feat.get("frames_u8"), max_new_tokens=max_new, processing=processing,
-                                          **self._beam_kw(beams))
+                                          **self._beam_kw(beams), **self._kw_constraint(kwargs))
         return self._postprocess(new_ids[0, : int(lens[0])].cpu().tolist(), tokenizer, vals["type"])
 
     @torch.inference_mode()

@@ -36,6 +36,8 @@ class Request:
     top_logprobs: int = 0    # N in 1..20: every emitted token comes with the N most likely ids and their log-probabilities (RAW logits); 0 = off
     watch_ids: Optional[Sequence[int]] = None   # ... and with the log-probabilities of these ids (up to 256).  One list per run: the requests
                                                 # that name a list name the same one
+    constraint_start: Any = None   # a state or entry name of the scheduler's automaton (SlotScheduler(automaton=...)): the request is decoded
+                                   # under that constraint from there; None = unconstrained.  A sample group's samples all enter there
 
 
 @dataclass
@@ -72,7 +74,8 @@ class SlotScheduler:
 
     engine   object with slots_open / slot_prefill / slots_step / slots_state / slot_output / slot_release / set_stop
              (emmax.engine.EmmaxEngine, or a fake in the CPU tests); slots_fork as well once a request asks for num_samples > 1
-             and set_top_logprobs / slot_top_logprobs / clear_top_logprobs once one asks for top_logprobs or watch_ids
+             and set_top_logprobs / slot_top_logprobs / clear_top_logprobs once one asks for top_logprobs or watch_ids, and set_automaton /
+             set_automaton_starts(_staged) / clear_automaton once one names a constraint_start
     encode   frames (list) -> patch embeddings, one [n_patches, hidden] bf16 tensor per frame; called once per admission
              round with every frame admitted in that round, so the ViT runs batched
     n_slots  decode batch (<= 64; the engine's max_decode_batch())
@@ -81,11 +84,13 @@ class SlotScheduler:
     encode_ahead frames encoded per `encode` call: the frames being admitted plus the next ones in the queue, so the ViT
                  always runs at a useful batch (a lone frame costs ~6 ms, eight cost ~8 ms); their patch embeddings wait in
                  `self._embeds` (16 MB for eight 7B-shape frames) until their request is admitted
+    automaton    a constraints.TokenAutomaton: the one automaton the run's requests may enter (Request.constraint_start says where; requests
+                 without one are unconstrained).  It is set on the session for the runs in which some request names a start
     """
 
     def __init__(self, engine, encode: Callable[[List[Any]], List[Any]], n_slots: int = 8, poll_every: int = 4,
                  stop_trigger: Sequence[int] = (), stop_after: int = 0, clock: Callable[[], float] = time.perf_counter,
-                 encode_ahead: int = 0, overlap: Optional[bool] = None, stage_batch: Optional[int] = None) -> None:
+                 encode_ahead: int = 0, overlap: Optional[bool] = None, stage_batch: Optional[int] = None, automaton=None) -> None:
         if not 1 <= n_slots <= MAX_SLOTS:
             raise ValueError(f"n_slots {n_slots} outside 1..{MAX_SLOTS}")
         if poll_every < 1:
@@ -119,6 +124,8 @@ class SlotScheduler:
         self._warpers = False                        # ... min_p / typical_p / epsilon_cutoff / eta_cutoff (run)
         self._rules = False                          # ... token rules (run)
         self._top = None                             # (N, watch list) bound for the current run, None when no request asks (run)
+        self.automaton = automaton
+        self._constrained = False                    # some request of the current run names a constraint_start (run)
         # a staged batch is at most max(stage_batch, free slots) <= n_slots requests: the session needs that many staging rows
         # (they cost KV pages, so a session only has them when a scheduler asks: engine.ensure_stage_rows re-creates it if needed)
         if self.overlap and hasattr(engine, "ensure_stage_rows"):
@@ -147,6 +154,10 @@ class SlotScheduler:
             from .sampling import check_top_logprobs
 
             check_top_logprobs(req.top_logprobs, req.watch_ids, None, "Request")
+        if getattr(req, "constraint_start", None) is not None:
+            if self.automaton is None:
+                raise ValueError(f"request {req.rid!r} names a constraint_start, but the scheduler has no automaton (SlotScheduler(automaton=...))")
+            self.automaton.start_state(req.constraint_start)   # (validates: a ValueError names the entries)
         self.queue.append((req, self.clock()))
 
     def _sampling_rows(self, reqs):
@@ -181,6 +192,17 @@ class SlotScheduler:
                 self.engine.set_rule_enables_staged(words)
             else:
                 self.engine.set_rule_enables(words, row0=row0)
+
+    def _set_constraint(self, reqs, row0: int = 0, staged: bool = False) -> None:
+        """A serve where some request is constrained: every prefill is preceded by its rows' start states (-1 for the unconstrained ones).
+        Other serves call nothing here."""
+        if not self._constrained:
+            return
+        starts = [self.automaton.start_state(getattr(r, "constraint_start", None)) for r in reqs]
+        if staged:
+            self.engine.set_automaton_starts_staged(starts)
+        else:
+            self.engine.set_automaton_starts(starts, row0=row0)
 
     def _set_sampling(self, reqs, row0: int = 0, staged: bool = False) -> None:
         """A serve where some request samples: every prefill is preceded by its rows' parameters.  Greedy-only serves call nothing here."""
@@ -238,12 +260,14 @@ class SlotScheduler:
                 j += 1
             if j - i > 1 and hasattr(self.engine, "slots_prefill"):
                 self._set_processing([batch[k][0] for k in range(i, j)], row0=slots[i])
+                self._set_constraint([batch[k][0] for k in range(i, j)], row0=slots[i])
                 self._set_sampling([batch[k][0] for k in range(i, j)], row0=slots[i])
                 self.engine.slots_prefill(slots[i], [list(batch[k][0].prompt_ids) for k in range(i, j)], embeds[i:j] if embeds[i] is not None else None,
                                           [batch[k][0].max_new_tokens for k in range(i, j)])
             else:
                 for k in range(i, j):
                     self._set_processing([batch[k][0]], row0=slots[k])
+                    self._set_constraint([batch[k][0]], row0=slots[k])
                     self._set_sampling([batch[k][0]], row0=slots[k])
                     self.engine.slot_prefill(slots[k], list(batch[k][0].prompt_ids), embeds[k], batch[k][0].max_new_tokens)
                     if len(mine[k]) > 1:   # before any decode step: the fork draws from the logit row this prefill left
@@ -278,6 +302,7 @@ class SlotScheduler:
             with self.engine.admission():
                 embeds = self._encode_for(batch)
                 self._set_processing([r for r, _ in batch], staged=True)
+                self._set_constraint([r for r, _ in batch], staged=True)
                 self._set_sampling([r for r, _ in batch], staged=True)
                 staged = self.engine.slots_prefill_staged([list(r.prompt_ids) for r, _ in batch], embeds if embeds[0] is not None else None,
                                                           [r.max_new_tokens for r, _ in batch])
@@ -350,6 +375,7 @@ class SlotScheduler:
         self._warpers = any(r.sampling is not None and getattr(r.sampling, "has_warpers", False) for r, _ in self.queue)
         with_rules = [r.processing for r, _ in self.queue if getattr(r, "processing", None) is not None and getattr(r.processing, "rule_enable", 0)]
         self._rules = bool(with_rules)
+        self._constrained = any(getattr(r, "constraint_start", None) is not None for r, _ in self.queue)
         self._top = self._top_of_run()
         if self._top is not None:
             self._sampling = True   # the binding reads the logit rows a sampling session writes: greedy requests at temperature 0
@@ -363,8 +389,14 @@ class SlotScheduler:
             if self._rules:   # one rule table for the run (the requests that name a kind name the same rules); every row starts opted out
                 self.engine.set_token_rules(with_rules, enables=False)
                 self.engine.set_rule_enables([0] * self.n_slots)
+            if self._constrained:   # one automaton for the run; every row starts unconstrained, each admission sets its rows' starts
+                self.engine.set_automaton(self.automaton)
+                self.engine.set_automaton_starts([-1] * self.n_slots)
             return self._run()
         finally:
+            if self._constrained:
+                self.engine.clear_automaton()
+                self._constrained = False
             if self._top is not None:
                 self.engine.clear_top_logprobs()
                 self._top = None

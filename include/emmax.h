@@ -426,6 +426,59 @@ int emmax_op_sample_ext(const float* logits_dev, int ld, int B, int V, const flo
                         const uint32_t* rule_enable_dev, int eos_id, int pad_id, int32_t* tok_out_dev, float* logprob_out_dev, float* scores_out_dev,
                         emmax_stream stream);
 
+/* ---- constrained decoding: a token automaton in the decode step (new symbols, same ABI) ---------------------------------
+ * HF's prefix_allowed_tokens_fn (PrefixConstrainedLogitsProcessor) as a compiled automaton over TOKEN CLASSES, so that it runs inside a
+ * captured step.  One automaton per session, device words behind stable pointers (another table re-captures nothing):
+ *   cls[V]       uint8   the class of every token id; C classes, C <= 256 (EMMAX_MAX_AUT_CLASSES)
+ *   allow[S][8]  uint32  bit c of allow[s] (word c / 32, bit c % 32): class c is allowed in state s; S states, S <= 1024 (EMMAX_MAX_AUT_STATES)
+ *   next[S][C]   int16   the state after a token of class c in state s; -1: the row is DONE AFTER THIS TOKEN, whatever the token is
+ * and per row (decode rows and staging rows) start[b] (int32, -1: the row is unconstrained for its whole life) and state[b], which every
+ * prefill that restarts the row sets to start[b] -- where the stop rule's matcher is reset.
+ * A row that emits a token in state s >= 0: every id i whose bit cls[i] of allow[s] is clear becomes -inf together with the other bans
+ * (after the sequence biases and the repetition penalty; every later processor only bans, so their order does not matter: HF's result).  The
+ * warpers and the draw, or the argmax, are unchanged.  Then state[b] = next[s][cls[tok]] for the token emitted; -1 marks the row done as an
+ * EOS does (and stays in state[b]).  A row that was done, is idle or is out of budget does not move.  A state that allows nothing leaves no
+ * finite entry: the row emits pad_id and is done (its state stays).  EOS is a token like any other: the automaton says where it may appear.
+ * Log-probabilities and top-N / watched log-probabilities are of the RAW row; scores[t][b] is the processed row (-inf at the disallowed
+ * ids); logits[t][b] is raw.  No float atomics; the same inputs give the same bits; the kept set and the token do not depend on the row's
+ * place in the batch or on B.  The mask is a processor on whole fp32 logit rows: setting an automaton turns processing on with neutral
+ * values where it was off, and clearing it turns that off again.  A session without an automaton launches what it launched before: the
+ * constrained finish is an instantiation of its own (finish mode bit 16).
+ *   emmax_session_set_automaton              the tables (host arrays: cls[V], allow[S][8], next[S][C]), checked here: 1 <= S <= 1024,
+ *                                            1 <= C <= 256, every cls < C, every next in [-1, S) -- else EMMAX_ERR_INVALID and nothing
+ *                                            changes.  Synchronises the stream.  The first table leaves every row at start = -1; a later
+ *                                            one keeps the rows' starts (a state the new table does not have allows nothing).
+ *   emmax_session_set_automaton_starts       rows row0 .. row0 + n - 1: start states in [-1, S).  EMMAX_ERR_STATE before a table is set.  Set
+ *                                            them before the prefill whose first token they govern.
+ *   emmax_slots_set_automaton_starts_staged  the same for the n requests of the next emmax_slots_prefill_staged.
+ *   emmax_session_clear_automaton            off (emmax_session_clear_processing turns it off too).
+ *   emmax_session_automaton                  1 on, 0 off, -1 null session.
+ *   emmax_session_automaton_state            rows row0 .. row0 + n - 1 of state[] (staging rows behind the decode rows) to a device array.
+ *   emmax_slots_commit / emmax_slots_fork    move start and state with the rest of a request's state; a fork's followers enter at the
+ *                                            source's start, as if the prompt had been prefilled for each of them alone.
+ *   emmax_set_current_tokens                 stays EMMAX_ERR_STATE (processing is on).
+ * Beams: the setter returns EMMAX_ERR_STATE while beams are on, and emmax_session_set_beams while an automaton is set.
+ *
+ * emmax_op_sample_constrained is that finish on its own: the arguments of emmax_op_sample_ext (the processor arrays and histories are
+ * required: the mask is a processor), the three tables in device memory (next at a pitch of n_classes) and state_dev[B] (-1: unconstrained;
+ * a state outside 0 .. n_states - 1 allows nothing).  Out: token, raw log-probability, state_out_dev[B] = the state after the token (the
+ * row's state where it emitted pad_id) and, when scores_out_dev is not NULL, the scores. */
+int emmax_session_set_automaton(emmax_session* s, int n_states, int n_classes, const uint8_t* cls_host, const uint32_t* allow_host, const int16_t* next_host,
+                                emmax_stream stream);
+int emmax_session_set_automaton_starts(emmax_session* s, int row0, int n, const int32_t* start_host, emmax_stream stream);
+int emmax_slots_set_automaton_starts_staged(emmax_session* s, int n, const int32_t* start_host, emmax_stream stream);
+int emmax_session_clear_automaton(emmax_session* s, emmax_stream stream);
+int emmax_session_automaton(const emmax_session* s);
+int emmax_session_automaton_state(emmax_session* s, int row0, int n, int32_t* state_out_dev, emmax_stream stream);
+int emmax_op_sample_constrained(const float* logits_dev, int ld, int B, int V, const float* temperature_dev, const int32_t* top_k_dev, const float* top_p_dev,
+                                const uint64_t* seed_dev, const uint32_t* subseq_dev, const int32_t* n_out_dev, const float* min_p_dev,
+                                const float* typical_p_dev, const float* epsilon_cutoff_dev, const float* eta_cutoff_dev, const float* penalty_dev,
+                                const int32_t* ngram_dev, const int32_t* min_new_dev, const int32_t* hist_dev, const int32_t* hist_len_dev, int max_hist,
+                                int n_rules, const int32_t* rule_off_dev, const int32_t* rule_ids_dev, const int32_t* rule_flags_dev,
+                                const float* rule_bias_dev, const uint32_t* rule_enable_dev, int eos_id, int pad_id, int n_states, int n_classes,
+                                const uint8_t* cls_dev, const uint32_t* allow_dev, const int16_t* next_dev, const int32_t* state_dev, int32_t* tok_out_dev,
+                                float* logprob_out_dev, int32_t* state_out_dev, float* scores_out_dev, emmax_stream stream);
+
 /* ---- beam search inside the decode step (ABI 9) ----------------------------------------------------------------------
  * The semantics of transformers 5.15's GenerationMixin._beam_search (_get_top_k_continuations, _get_running_beams_for_next_iteration,
  * _update_finished_beams, _check_early_stop_heuristic, _beam_search_has_unfinished_sequences) for do_sample = False, one EOS id and no
