@@ -187,9 +187,11 @@ __global__ __launch_bounds__(NW * 64) void emmax_decode_attn_kernel(DecodeAttnPa
                 const size_t rowi = (((size_t)pg8 * p.Hkv + hk) << p.page_shift) + (kk & (p.page - 1));
                 const u32x2_t k8 = __builtin_nontemporal_load((const u32x2_t*)(kc8 + rowi * HD + ch * 8)),   // (non-temporal: see the bf16 path below)
                               v8 = __builtin_nontemporal_load((const u32x2_t*)(vc8 + rowi * HD + ch * 8));
-                // (GRP: the position the lane READ -- a masked lane re-reads key k0, and a tail that is the new key alone starts on the row
-                // the cache does not hold yet: bytes and scale there are anything, and 0 x NaN is not 0)
-                kv[u] = (u32x4_t){k8[0], k8[1], __float_as_uint(p.kscale[rowi]), (uint32_t)(GRP != GRP_OFF ? kk : key)};
+                // (the position the lane READ, in every form -- a masked lane re-reads key k0, and a split or tail that is the new key alone
+                // starts on the row the cache does not hold yet: bytes and scale there are anything, and 0 x NaN is not 0.  With the position
+                // read, is_new below hands such a lane the staging row.  The plain form carried `key` until tests/test_decode_attn_forms_gpu.py
+                // poisoned the cache past the context: ctx a multiple of the split's key count, ctx = 0 with one split)
+                kv[u] = (u32x4_t){k8[0], k8[1], __float_as_uint(p.kscale[rowi]), (uint32_t)kk};
                 vv[u] = (u32x4_t){v8[0], v8[1], __float_as_uint(p.vscale[rowi]), 0u};
                 continue;
             }
@@ -398,32 +400,44 @@ int decode_attn_nsplit(int B, int Hkv) {
     return ns;
 }
 
-int launch_decode_attn(const DecodeAttnParams& p_in, int B, int Hq, int head_dim, int nsplit, hipStream_t stream) {
-    if (head_dim != 128) return -1;
-    DecodeAttnParams p = p_in;
-    if (p.max_pages < 1 || p.max_pages > 512 || p.page < 1 || (p.page & (p.page - 1))) return -1;   // table fits the kernel's LDS copy; page = 2^k
-    if (nsplit < 1 || (nsplit & (nsplit - 1))) return -1;   // the kernel divides the keys among the splits by shifting
-    p.page_shift = 0;
-    while ((1 << p.page_shift) < p.page) ++p.page_shift;
-    if (p.o_out && nsplit != 1) return -1;   // the direct form exists for one split only (nothing to merge)
-    if (p.kv_stage && (!p.kscale || !p.vscale)) return -1;   // fp8 KV cache: bytes + one scale per row
+// THE instantiation choice of launch_decode_attn, on the host and from the shapes, the operands that exist and the tuning switches alone
+bool decode_attn_form(const DecodeAttnParams& p, int B, int Hq, int nsplit, DecodeAttnForm* f) {
+    if (B < 1 || p.Hkv < 1 || Hq < 1 || Hq % p.Hkv) return false;
+    if (p.max_pages < 1 || p.max_pages > 512 || p.page < 1 || (p.page & (p.page - 1))) return false;   // table fits the kernel's LDS copy; page = 2^k
+    if (nsplit < 1 || (nsplit & (nsplit - 1))) return false;   // the kernel divides the keys among the splits by shifting
+    if (p.o_out && nsplit != 1) return false;   // the direct form exists for one split only (nothing to merge)
+    if (p.kv_stage && (!p.kscale || !p.vscale)) return false;   // fp8 KV cache: bytes + one scale per row
     const int G = Hq / p.Hkv;
-    dim3 grid(nsplit, p.Hkv, B), block(256);
+    if (G != 1 && G != 2 && G != 4 && G != 8) return false;
     const int nw = emmax_tune().attn_nw;
     const bool nw8 = nw == 8 || (nw == 0 && p.o_out && (long)p.Hkv * B <= 256);
     // four chunks of keys in flight (bf16 cache): measured on one box (profiles/r05_attn_deep_k32_spread_ab.txt) -- B = 32 (1024 blocks, four
     // per CU) 73.0 -> 68.5 us per launch, B = 8 / 16 (256 / 512 blocks) 20.0 -> 20.6 / 36.9 -> 37.3: on from 1024 blocks (-1 = that rule)
     const int deep_sw = emmax_tune().attn_deep;
     const bool deep = G <= 2 && (deep_sw > 0 || (deep_sw < 0 && (long)nsplit * p.Hkv * B >= 1024));   // (G >= 4: no registers for it)
-    switch (G) {
+    f->G = G; f->nsplit = nsplit; f->direct = p.o_out ? 1 : 0; f->kv8 = p.kv_stage ? 1 : 0;
+    f->deep = (f->kv8 || deep) ? 1 : 0;                        // (the fp8-cache form always has four chunks in flight, at every G)
+    f->nw = (!f->kv8 && !deep && f->direct && nw8) ? 8 : 4;    // (eight waves: the bf16 direct form alone, and never with four chunks)
+    return true;
+}
+
+int launch_decode_attn(const DecodeAttnParams& p_in, int B, int Hq, int head_dim, int nsplit, hipStream_t stream) {
+    if (head_dim != 128) return -1;
+    DecodeAttnParams p = p_in;
+    DecodeAttnForm f;
+    if (!decode_attn_form(p, B, Hq, nsplit, &f)) return -1;
+    p.page_shift = 0;
+    while ((1 << p.page_shift) < p.page) ++p.page_shift;
+    dim3 grid(f.nsplit, p.Hkv, B), block(f.nw * 64);
+    switch (f.G) {
 #define ATTN_CASE(GG)                                                                                                   \
     case GG:                                                                                                           \
-        if (p.kv_stage && p.o_out) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, true, 4, true>), grid, block, 0, stream, p); \
-        else if (p.kv_stage) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, false, 4, true>), grid, block, 0, stream, p); \
-        else if (p.o_out && deep) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, true, 4, false, true>), grid, block, 0, stream, p); \
-        else if (deep) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, false, 4, false, true>), grid, block, 0, stream, p); \
-        else if (p.o_out && nw8) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, true, 8>), grid, dim3(512), 0, stream, p); \
-        else if (p.o_out) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, true>), grid, block, 0, stream, p);     \
+        if (f.kv8 && f.direct) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, true, 4, true>), grid, block, 0, stream, p); \
+        else if (f.kv8) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, false, 4, true>), grid, block, 0, stream, p); \
+        else if (f.direct && f.deep) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, true, 4, false, true>), grid, block, 0, stream, p); \
+        else if (f.deep) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, false, 4, false, true>), grid, block, 0, stream, p); \
+        else if (f.direct && f.nw == 8) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, true, 8>), grid, block, 0, stream, p); \
+        else if (f.direct) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, true>), grid, block, 0, stream, p);     \
         else hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG>), grid, block, 0, stream, p);                         \
         break
         ATTN_CASE(1); ATTN_CASE(2); ATTN_CASE(4); ATTN_CASE(8);
@@ -450,21 +464,28 @@ int group_attn_nsplit(int B, int N, int Hq, int Hkv) {
     return ns;
 }
 
+bool group_attn_form(const DecodeAttnParams& p, int B, int N, int Hq, GroupAttnForm* f) {
+    if (!group_attn_takes(B, N, Hq, p.Hkv)) return false;
+    if (p.max_pages < 1 || p.max_pages > 512 || p.page < 1 || (p.page & (p.page - 1))) return false;   // as launch_decode_attn
+    if (p.kv_stage && (!p.kscale || !p.vscale)) return false;
+    const int G = Hq / p.Hkv, nq = N * G, w = group_attn_width(nq);
+    f->width = w; f->nsplit = group_attn_nsplit(B, N, Hq, p.Hkv); f->chunks = (nq + w - 1) / w; f->G = G; f->kv8 = p.kv_stage ? 1 : 0;
+    return true;
+}
+
 int launch_group_attn(const DecodeAttnParams& p_in, int B, int N, int Hq, int head_dim, hipStream_t stream) {
-    if (head_dim != 128 || !group_attn_takes(B, N, Hq, p_in.Hkv)) return -1;
+    GroupAttnForm f;
+    if (head_dim != 128 || !group_attn_form(p_in, B, N, Hq, &f)) return -1;
     DecodeAttnParams p = p_in;
-    if (p.max_pages < 1 || p.max_pages > 512 || p.page < 1 || (p.page & (p.page - 1))) return -1;   // as launch_decode_attn
     if (!p.o_out || !p.part || !p.grp_shared) return -1;
-    if (p.kv_stage && (!p.kscale || !p.vscale)) return -1;
     p.page_shift = 0;
     while ((1 << p.page_shift) < p.page) ++p.page_shift;
-    const int G = Hq / p.Hkv, nq = N * G, w = group_attn_width(nq);
-    p.grp_N = N; p.grp_Hq = Hq; p.grp_nsplit = group_attn_nsplit(B, N, Hq, p.Hkv);
-    const dim3 span(p.grp_nsplit, p.Hkv, (B / N) * ((nq + w - 1) / w)), tail(1, p.Hkv, B), block(256);
-    switch (w) {
+    p.grp_N = N; p.grp_Hq = Hq; p.grp_nsplit = f.nsplit;
+    const dim3 span(f.nsplit, p.Hkv, (B / N) * f.chunks), tail(1, p.Hkv, B), block(256);
+    switch (f.width) {
 #define SPAN_CASE(W)                                                                                                                   \
     case W:                                                                                                                            \
-        if (p.kv_stage) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, W, false, 4, true, true, GRP_SPAN>), span, block, 0, stream, p); \
+        if (f.kv8) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, W, false, 4, true, true, GRP_SPAN>), span, block, 0, stream, p); \
         else hipLaunchKernelGGL((emmax_decode_attn_kernel<128, W, false, 4, false, false, GRP_SPAN>), span, block, 0, stream, p);      \
         break
         SPAN_CASE(2); SPAN_CASE(4); SPAN_CASE(8);
@@ -472,10 +493,10 @@ int launch_group_attn(const DecodeAttnParams& p_in, int B, int N, int Hq, int he
         default: return -1;
     }
     if (hipGetLastError() != hipSuccess) return -4;
-    switch (G) {
+    switch (f.G) {
 #define TAIL_CASE(GG)                                                                                                                  \
     case GG:                                                                                                                           \
-        if (p.kv_stage) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, true, 4, true, true, GRP_TAIL>), tail, block, 0, stream, p); \
+        if (f.kv8) hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, true, 4, true, true, GRP_TAIL>), tail, block, 0, stream, p); \
         else hipLaunchKernelGGL((emmax_decode_attn_kernel<128, GG, true, 4, false, false, GRP_TAIL>), tail, block, 0, stream, p);      \
         break
         TAIL_CASE(1); TAIL_CASE(2); TAIL_CASE(4); TAIL_CASE(8);

@@ -362,6 +362,11 @@ struct DecodeAttnParams {
     int grp_N, grp_nsplit, grp_Hq;   // rows per group; splits of the shared span; q heads (set by the launcher)
 };
 int decode_attn_nsplit(int B, int Hkv);
+// the instantiation launch_decode_attn takes (it dispatches on this struct; emmax_decode_attn_plan prints it): template arguments G, NW, DIRECT,
+// KV8, DEEP and the grid's split count.  false = a shape the launcher refuses.  Host only: looks at which operands exist, never through them
+struct DecodeAttnForm { int G, nw, direct, kv8, deep, nsplit; };
+bool decode_attn_form(const DecodeAttnParams& p, int B, int Hq, int nsplit, DecodeAttnForm* f);
+bool attn_direct_rule(int B, int Hkv, bool exact);   // step.hip: the one-split direct form in a B-row step (attn_direct_on without a model)
 int launch_decode_attn(const DecodeAttnParams& p, int B, int Hq, int head_dim, int nsplit, hipStream_t stream);
 // The attention of a step whose B rows are B / N groups on shared prompt pages, in two launches: the span [0, grp_shared[g] * page) once per
 // group into split partials (p.part: group_attn_nsplit() per (row, head)), then one block per (row, kv head) over the row's own tail, which
@@ -369,6 +374,9 @@ int launch_decode_attn(const DecodeAttnParams& p, int B, int Hq, int head_dim, i
 enum { EMMAX_GROUP_ATTN_MAX_SPLITS = 8 };
 bool group_attn_takes(int B, int N, int Hq, int Hkv);
 int group_attn_nsplit(int B, int N, int Hq, int Hkv);
+// the two launches of launch_group_attn (it dispatches on this struct): queries per span block, span splits, query chunks per (group, kv head), tail G
+struct GroupAttnForm { int width, nsplit, chunks, G, kv8; };
+bool group_attn_form(const DecodeAttnParams& p, int B, int N, int Hq, GroupAttnForm* f);
 int launch_group_attn(const DecodeAttnParams& p, int B, int N, int Hq, int head_dim, hipStream_t stream);
 int launch_x_decode_attn(const DecodeAttnParams& p, int B, int Hq, int head_dim, int nsplit, hipStream_t stream);   // exact.hip: fp32 q, fp32 cache
 

@@ -251,6 +251,47 @@ int emmax_op_decode_attention_kv8(const void* q, void* kcache8, void* vcache8, f
     if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_decode_attention_kv8: unsupported (GQA group in {1,2,4,8}, page = 2^k, max_pages <= 512, nsplit = 2^k)");
     return 0;
 }
+// ---- the forms of the decode attention, host only (decode_attn.hip: decode_attn_form / group_attn_form -- what the launchers dispatch on) ----
+static void attn_plan_operands(DecodeAttnParams& a, int Hq, int Hkv, int direct, int kv8) {
+    void* const any = (void*)(uintptr_t)256;   // the form looks at which operands exist -- never through a pointer
+    memset(&a, 0, sizeof(a));
+    a.q = any; a.ldq = Hq * 128; a.kcache = any; a.vcache = any; a.page_table = (const int32_t*)any; a.ctx_len = (const int32_t*)any;
+    a.part = (float*)any; a.Hkv = Hkv; a.page = 64; a.max_pages = 1;
+    if (direct) a.o_out = any;
+    if (kv8) { a.kv_stage = any; a.kscale = (float*)any; a.vscale = (float*)any; }
+}
+int emmax_decode_attn_plan(int B, int Hq, int Hkv, int nsplit, int direct, int kv8, int* G_out, int* nw_out, int* direct_out, int* deep_out,
+                           int* nsplit_out) {
+    if (B < 1 || B > EMMAX_MAX_DECODE_BATCH || Hkv < 1 || Hq < 1 || Hq % Hkv) return fail(EMMAX_ERR_INVALID, "emmax_decode_attn_plan: bad B / heads");
+    const bool step = nsplit == 0 && direct == -1;   // what a B-row step launches: decode_attn_nsplit + the one-split rule (step.hip: run_decode_stage)
+    if (!step && (nsplit < 1 || nsplit > 16 || (direct != 0 && direct != 1)))
+        return fail(EMMAX_ERR_INVALID, "emmax_decode_attn_plan: nsplit 1..16 with direct 0 / 1, or nsplit 0 with direct -1 (a step's own choice)");
+    if (step) { nsplit = decode_attn_nsplit(B, Hkv); direct = attn_direct_rule(B, Hkv, false) ? 1 : 0; }
+    DecodeAttnParams a;
+    attn_plan_operands(a, Hq, Hkv, direct, kv8);
+    DecodeAttnForm f;
+    if (!decode_attn_form(a, B, Hq, nsplit, &f))
+        return fail(EMMAX_ERR_INVALID, "emmax_decode_attn_plan: unsupported (GQA group in {1,2,4,8}, nsplit = 2^k, one split for the direct form)");
+    if (G_out) *G_out = f.G;
+    if (nw_out) *nw_out = f.nw;
+    if (direct_out) *direct_out = f.direct;
+    if (deep_out) *deep_out = f.deep;
+    if (nsplit_out) *nsplit_out = f.nsplit;
+    return 0;
+}
+int emmax_group_attn_plan(int B, int N, int Hq, int Hkv, int kv8, int* span_width_out, int* span_nsplit_out, int* span_chunks_out, int* tail_G_out) {
+    if (Hkv < 1 || Hq < 1 || Hq % Hkv) return fail(EMMAX_ERR_INVALID, "emmax_group_attn_plan: bad heads");
+    DecodeAttnParams a;
+    attn_plan_operands(a, Hq, Hkv, 1, kv8);
+    GroupAttnForm f;
+    if (!group_attn_form(a, B, N, Hq, &f))
+        return fail(EMMAX_ERR_INVALID, "emmax_group_attn_plan: unsupported (whole groups of N >= 2 rows, B <= %d, GQA group in {1,2,4,8})", EMMAX_MAX_DECODE_BATCH);
+    if (span_width_out) *span_width_out = f.width;
+    if (span_nsplit_out) *span_nsplit_out = f.nsplit;
+    if (span_chunks_out) *span_chunks_out = f.chunks;
+    if (tail_G_out) *tail_G_out = f.G;
+    return 0;
+}
 // the grouped form (decode_attn.hip: launch_group_attn) as a pure op: the shapes and the groups' shared page counts are checked on the host
 // BEFORE anything is launched (the counts are read back: the call synchronises the stream and cannot be captured)
 static int op_group_attention(const char* who, DecodeAttnParams& a, int B, int Hq, int N, const int32_t* shared_pages, hipStream_t st) {
@@ -351,6 +392,19 @@ int emmax_op_x_decode_attention(const float* q32, const void* kcache32, const vo
     a.part = part_out; a.Hkv = Hkv; a.page = page; a.max_pages = max_pages; a.scale = scale; a.kv24 = kv24_elems;
     int r = launch_x_decode_attn(a, B, Hq, 128, nsplit, (hipStream_t)st);
     if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_x_decode_attention: unsupported (GQA group in {1,2,4,8}, page = 2^k, max_pages <= 512, nsplit = 2^k)");
+    return 0;
+}
+int emmax_op_x_decode_attention_direct(float* q32, const void* kcache32, const void* vcache32, int64_t kv24_elems, const int32_t* page_table,
+                                       const int32_t* ctx_len, const int32_t* done, int B, int Hq, int Hkv, int page, int max_pages, float scale,
+                                       emmax_stream st) {
+    if (!q32 || !kcache32 || !vcache32 || !page_table || !ctx_len) return fail(EMMAX_ERR_INVALID, "emmax_op_x_decode_attention_direct: null argument");
+    if (B < 1 || B > EMMAX_MAX_DECODE_BATCH || Hkv < 1 || Hq % Hkv) return fail(EMMAX_ERR_INVALID, "emmax_op_x_decode_attention_direct: bad B / heads");
+    DecodeAttnParams a;
+    memset(&a, 0, sizeof(a));
+    a.q = q32; a.ldq = Hq * 128; a.kcache = kcache32; a.vcache = vcache32; a.page_table = page_table; a.ctx_len = ctx_len; a.done = done;
+    a.o_out = q32; a.Hkv = Hkv; a.page = page; a.max_pages = max_pages; a.scale = scale; a.kv24 = kv24_elems;   // in place, as run_decode_stage launches it
+    int r = launch_x_decode_attn(a, B, Hq, 128, 1, (hipStream_t)st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_x_decode_attention_direct: unsupported (GQA group in {1,2,4,8}, page = 2^k, max_pages <= 512)");
     return 0;
 }
 // ---- one decode stage through the product's own dispatch (tests/test_decode_stages_gpu.py) ----------------------------

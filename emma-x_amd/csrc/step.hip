@@ -112,11 +112,12 @@ int stage_chunk(int stage, bool exact) {
 
 // one KV split per (row, head) (batch >= 5 at 32 heads): nothing to merge -- the attention launch normalises and writes the bf16 row
 // itself and the o-proj is a plain projection; otherwise the o-proj prologue merges the split partials.
-static bool attn_direct_on(const emmax_model* m, bool exact, int B) {
+bool attn_direct_rule(int B, int Hkv, bool exact) {
     // exact numerics: the fp32 row in place over the q rows, at batch >= 3 (decode_km.hip's EX o-proj takes fp32 rows; decode_ks.hip's merges the partials)
     if (exact && B < EMMAX_MFMA_MIN_BATCH) return false;
-    return decode_attn_nsplit(B, m->cfg.n_kv_heads) == 1 && emmax_tune().attn_direct != 0;
+    return decode_attn_nsplit(B, Hkv) == 1 && emmax_tune().attn_direct != 0;
 }
+static bool attn_direct_on(const emmax_model* m, bool exact, int B) { return attn_direct_rule(B, m->cfg.n_kv_heads, exact); }
 static bool attn_direct_on(const emmax_session* s, int B) { return attn_direct_on(s->m, s->exact, B); }
 
 // THE route rule of the grouped attention (decode_attn.hip: launch_group_attn): rows per group when a B-row step of the session, as configured

@@ -700,6 +700,18 @@ int emmax_op_decode_attention_group_kv8(const void* q_dev, void* kcache8_dev, vo
                                         const void* kv_stage_dev, const int32_t* page_table_dev, const int32_t* ctx_len_dev,
                                         const int32_t* done_dev, float* part_ws_dev, void* o_out_dev, int B, int Hq, int Hkv, int page,
                                         int max_pages, int N, const int32_t* shared_pages_dev, float scale, emmax_stream stream);
+/* Which form of the decode attention a launch takes -- HOST ONLY, launches nothing and needs no device; the launchers dispatch on the very
+ * structs these calls fill (decode_attn.hip: decode_attn_form, group_attn_form), so the answer cannot differ from the launch.
+ * emmax_decode_attn_plan: B rows, Hq / Hkv heads, kv8 = the fp8 cache.  nsplit > 0 and direct in {0, 1}: what emmax_op_decode_attention (direct
+ * 0) / _direct (1; one split only) / _kv8 launch for these arguments under the tuning switches attn_nw / attn_deep.  nsplit = 0, direct = -1:
+ * what a B-row step of a default-numerics session with these heads launches (splits by shape or attn_nsplit; direct with one split unless
+ * attn_direct = 0).  Outputs (any may be NULL): the GQA group G of the instantiation, waves per block (4 / 8), direct 0 / 1, deep = four chunks of
+ * keys in flight instead of two (0 / 1), the split count.  emmax_group_attn_plan: the two launches of emmax_op_decode_attention_group(_kv8) for B
+ * rows in groups of N: queries per span block (2 / 4 / 8), splits of the span, query chunks per (group, kv head), the tail's G.
+ * EMMAX_ERR_INVALID: a shape the launchers refuse. */
+int emmax_decode_attn_plan(int B, int Hq, int Hkv, int nsplit, int direct, int kv8, int* G_out, int* nw_out, int* direct_out, int* deep_out,
+                           int* nsplit_out);
+int emmax_group_attn_plan(int B, int N, int Hq, int Hkv, int kv8, int* span_width_out, int* span_nsplit_out, int* span_chunks_out, int* tail_G_out);
 /* Decode-path weight-streaming GEMV: y[b,n] = sum_k x[b,k] W[n,k]  (bf16 in, fp32 accumulate, bf16 out), B <= 8. */
 int emmax_op_gemv(const void* x_dev, const void* W_dev, void* y_dev, int B, int N, int K, emmax_stream stream);
 
@@ -893,7 +905,9 @@ int emmax_op_vision_stage(emmax_session* s, int tower, int block, int stage, int
  *                         head_dim)); emmax_op_x_join widens HL rows to fp32 (timm Attention / HF SDPA: modeling_prismatic.py:114-123,404-415)
  *   emmax_op_x_decode_attention  emmax_op_decode_attention over fp32 q rows and the exact-numerics paged cache (same partial layout): kv24_elems = 0:
  *                         fp32 rows [pages][Hkv][page][128] (tuning switch exact = 2); > 0: the 24-bit cache of exact = 1 -- per operand a bf16 plane of
- *                         kv24_elems elements (the top 16 bits of the fp32 value rounded to 24 bits) followed by an 8-bit extension plane */
+ *                         kv24_elems elements (the top 16 bits of the fp32 value rounded to 24 bits) followed by an 8-bit extension plane
+ *   emmax_op_x_decode_attention_direct  its ONE-split form, as exact sessions launch it at 3 - 8 rows: the block normalises the head's result and
+ *                         writes the fp32 row IN PLACE over the head's 128 q values in q32_dev [B, Hq * 128] (rows flagged done: zeros); no partials */
 int emmax_op_x_gemm(const float* A32_dev, int lda, const void* W_dev, int ldw, float* C32_dev, int ldc, int M, int N, int K, const void* bias_dev, int act,
                     const float* residual32_dev, int ldr, void* hl_ws_dev, void* ws_dev, int64_t ws_bytes, emmax_stream stream);
 int emmax_op_x_rownorm(int mode, const float* x_dev, float* y32_dev, const void* w_dev, const void* b_dev, int rows, int D, float eps, void* hl_ws_dev,
@@ -904,6 +918,9 @@ int emmax_op_x_join(const void* hl_dev, float* out32_dev, int rows, int D, emmax
 int emmax_op_x_decode_attention(const float* q32_dev, const void* kcache_dev, const void* vcache_dev, int64_t kv24_elems, const int32_t* page_table_dev,
                                 const int32_t* ctx_len_dev, const int32_t* done_dev, float* part_out_dev, int B, int Hq, int Hkv, int page, int max_pages,
                                 int nsplit, float scale, emmax_stream stream);
+int emmax_op_x_decode_attention_direct(float* q32_dev, const void* kcache_dev, const void* vcache_dev, int64_t kv24_elems, const int32_t* page_table_dev,
+                                       const int32_t* ctx_len_dev, const int32_t* done_dev, int B, int Hq, int Hkv, int page, int max_pages, float scale,
+                                       emmax_stream stream);
 
 /* ---- top-N and watched-token log-probabilities (new symbols, same ABI) ---------------------------------------------------------
  * A short, fixed-size slice of the distribution a row's token was drawn from, over the RAW fp32 lm-head row l of V entries (T = 1,

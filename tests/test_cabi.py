@@ -174,6 +174,29 @@ def test_null_arguments_are_errors(lib):
     assert so.emmax_model_create(None, None) == -1
     assert so.emmax_decode_step(None, None) == -1
     assert so.emmax_generate(None, 4, 1, None, None, None) == -1
+    # the exact-numerics in-place attention row: refused on the host before anything is launched
+    assert so.emmax_op_x_decode_attention_direct(None, None, None, 0, None, None, None, 1, 2, 2, 64, 1, 1.0, None) == -1
+    assert b"emmax_op_x_decode_attention_direct: null argument" in so.emmax_last_error()
+
+
+def test_decode_attention_plans_of_the_benchmark_steps(lib):
+    """emmax_decode_attn_plan / emmax_group_attn_plan (host only; tests/test_decode_attn_plan.py holds the full tables): the 32-head model's steps --
+    eight splits at batch 1, the one-split direct form at 8 rows, four chunks of keys in flight from 32; on the fp8 cache always; a 64-row step
+    in eight groups of 8 is one split of the shared span at width 8."""
+    import ctypes as C
+
+    _, so = lib
+    o = [C.c_int() for _ in range(5)]
+
+    def plan(B, kv8=0):
+        assert so.emmax_decode_attn_plan(B, 32, 32, 0, -1, kv8, *[C.byref(x) for x in o]) == 0
+        return tuple(x.value for x in o)   # (G, waves, direct, deep, splits)
+
+    assert plan(1) == (1, 4, 0, 0, 8) and plan(8) == (1, 4, 1, 0, 1) and plan(32) == (1, 4, 1, 1, 1) and plan(8, 1) == (1, 4, 1, 1, 1)
+    g = [C.c_int() for _ in range(4)]
+    assert so.emmax_group_attn_plan(64, 8, 32, 32, 0, *[C.byref(x) for x in g]) == 0 and tuple(x.value for x in g) == (8, 1, 1, 1)
+    assert so.emmax_decode_attn_plan(1, 32, 5, 0, -1, 0, None, None, None, None, None) == -1 and b"emmax_decode_attn_plan" in so.emmax_last_error()
+    assert so.emmax_group_attn_plan(7, 2, 32, 32, 0, None, None, None, None) == -1 and b"emmax_group_attn_plan" in so.emmax_last_error()
 
 
 def test_gemm_launch_plans_of_the_hot_path(lib):
