@@ -380,6 +380,40 @@ bool group_attn_form(const DecodeAttnParams& p, int B, int N, int Hq, GroupAttnF
 int launch_group_attn(const DecodeAttnParams& p, int B, int N, int Hq, int head_dim, hipStream_t stream);
 int launch_x_decode_attn(const DecodeAttnParams& p, int B, int Hq, int head_dim, int nsplit, hipStream_t stream);   // exact.hip: fp32 q, fp32 cache
 
+// ---- extend_attn.hip: n new tokens per sequence on top of a cached context ----
+// packed row i of sequence b (rows cu[b] .. cu[b + 1]) sits at position base[b] + i; cu and base are device arrays
+struct ExtendAttnParams {
+    const void* q;          // bf16 packed rows [total, ldq], head h of a row at q_off + h * 128 (already rotated)
+    void* out;              // bf16 [total, ld_out]
+    const void* kcache;     // bf16 [pages][Hkv][64][128], or e4m3 bytes with kscale / vscale fp32 [pages][Hkv][64]
+    const void* vcache;
+    const float* kscale;
+    const float* vscale;
+    const int32_t* page_table;   // [B][max_pages]
+    const int32_t* cu;           // [B + 1]
+    const int32_t* base;         // [B]: the sequences' cached lengths BEFORE the append
+    float* part;                 // split form: f32 [total][Hq][nsplit][132] = { o[128] un-normalised, m, l, pad }
+    int ldq, q_off, ld_out, B, Hq, Hkv, max_pages;
+    float scale;
+};
+// what launch_extend_attn dispatches on (emmax_extend_attn_plan prints it): GQA group, tokens per block (128 / G), query tiles per sequence, key
+// splits, the split form (partials + merge pass) or the direct one, the e4m3 cache
+struct ExtendAttnPlan { int G, qt, nqt, nsplit, split, kv8; };
+// max_n / max_L: upper bounds of the new rows / of base + n of any sequence; nsplit 0 = the planner's choice.  false: a shape the launcher refuses
+bool extend_attn_plan(int B, int max_n, int max_L, int Hq, int Hkv, int nsplit, int kv8, ExtendAttnPlan* f);
+int launch_extend_attn(const ExtendAttnParams& p, const ExtendAttnPlan& f, int total_rows, hipStream_t stream);   // page = 64, head_dim = 128
+// launch_rope_kv_write / launch_kv_quant_rows at position base[b] + i (the quantising pass leaves the qkv rows as they are); max_pos: rows of cos / sin
+int launch_rope_kv_write_at(void* qkv, int ld, int q_off, int k_off, int v_off, const int32_t* cu, const int32_t* base, int B, int total_rows,
+                            const float* cos_t, const float* sin_t, void* kcache, void* vcache, const int32_t* page_table, int max_pages, int Hq,
+                            int Hkv, int hd, int page, int max_pos, hipStream_t stream);
+// the rows' state when they grow by st.S[b] tokens: base[b] = ctx_len[b], cu = the packed offsets of the new rows, ctx_len += S; the rest as launch_prefill_state.
+// aut_state / aut_start (both or neither): a row outside the automaton (state -1) enters at its start state, the others keep their state
+int launch_extend_state(const PrefillState& st, int32_t* cu, int32_t* base, int32_t* ctx_len, int32_t* done, int32_t* n_out, int32_t* max_new, int32_t* stop_m,
+                        int32_t* stop_after, int32_t* aut_state, const int32_t* aut_start, hipStream_t stream);
+int launch_kv_quant_rows_at(const void* qkv, int ld, int k_off, int v_off, const int32_t* cu, const int32_t* base, int B, int total_rows, void* k8,
+                            void* v8, float* kscale, float* vscale, const int32_t* page_table, int max_pages, int Hkv, int hd, int page,
+                            hipStream_t stream);
+
 // ---- decode.hip: the greedy finish of a step ----
 struct FinishParams {
     const float* part_val;

@@ -292,6 +292,99 @@ int emmax_group_attn_plan(int B, int N, int Hq, int Hkv, int kv8, int* span_widt
     if (tail_G_out) *tail_G_out = f.G;
     return 0;
 }
+// ---- extend_attn.hip as pure ops: n new rows per sequence over the paged cache.  cu and base are read back and checked on the host BEFORE
+// anything is launched (the call synchronises the stream and cannot be captured) ----
+int emmax_extend_attn_plan(int B, int max_n, int max_L, int Hq, int Hkv, int nsplit, int kv8, int* G_out, int* tokens_per_block_out, int* query_tiles_out,
+                           int* nsplit_out, int* split_form_out) {
+    ExtendAttnPlan f;
+    if (B > EMMAX_MAX_DECODE_BATCH || !extend_attn_plan(B, max_n, max_L, Hq, Hkv, nsplit, kv8, &f))
+        return fail(EMMAX_ERR_INVALID, "emmax_extend_attn_plan: unsupported (B 1..%d, 1 <= max_n <= max_L, GQA group in {1,2,4,8}, nsplit 0..16)", EMMAX_MAX_DECODE_BATCH);
+    if (G_out) *G_out = f.G;
+    if (tokens_per_block_out) *tokens_per_block_out = f.qt;
+    if (query_tiles_out) *query_tiles_out = f.nqt;
+    if (nsplit_out) *nsplit_out = f.nsplit;
+    if (split_form_out) *split_form_out = f.split;
+    return 0;
+}
+// cu / base of an extension op on the host: 0 = cu[0] < cu[1] < .. = total_rows, 0 <= base[b], base[b] + n[b] <= limit
+static int extend_op_lengths(const char* who, const int32_t* cu, const int32_t* base, int B, int total_rows, long limit, int* max_n, int* max_L, hipStream_t st) {
+    if (B < 1 || B > EMMAX_MAX_DECODE_BATCH || total_rows < B) return fail(EMMAX_ERR_INVALID, "%s: B %d (1..%d), total_rows %d (>= B)", who, B, EMMAX_MAX_DECODE_BATCH, total_rows);
+    int32_t h_cu[EMMAX_MAX_DECODE_BATCH + 1], h_base[EMMAX_MAX_DECODE_BATCH];
+    HIPCHK(hipMemcpyAsync(h_cu, cu, (size_t)(B + 1) * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_base, base, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (h_cu[0] != 0 || h_cu[B] != total_rows) return fail(EMMAX_ERR_INVALID, "%s: cu_seqlens runs %d..%d, not 0..total_rows = %d", who, h_cu[0], h_cu[B], total_rows);
+    *max_n = 0; *max_L = 0;
+    for (int b = 0; b < B; ++b) {
+        const int n = h_cu[b + 1] - h_cu[b];
+        if (n < 1) return fail(EMMAX_ERR_INVALID, "%s: sequence %d has %d new rows (>= 1)", who, b, n);
+        if (h_base[b] < 0 || (long)h_base[b] + n > limit)
+            return fail(EMMAX_ERR_INVALID, "%s: sequence %d: base %d + %d new rows outside 0..%ld (the page table / the RoPE tables)", who, b, h_base[b], n, limit);
+        *max_n = std::max(*max_n, n);
+        *max_L = std::max(*max_L, h_base[b] + n);
+    }
+    return 0;
+}
+static int op_extend_attention(const char* who, ExtendAttnParams& a, int total_rows, int page, int nsplit, int kv8, long long ws_floats, int* nsplit_out,
+                               hipStream_t st) {
+    if (!a.q || !a.out || !a.kcache || !a.vcache || !a.page_table || !a.cu || !a.base) return fail(EMMAX_ERR_INVALID, "%s: null argument", who);
+    if (page != 64) return fail(EMMAX_ERR_INVALID, "%s: page %d (one K / V tile is one page of 64 keys)", who, page);
+    if (a.Hkv < 1 || a.Hq < 1 || a.Hq % a.Hkv || a.max_pages < 1) return fail(EMMAX_ERR_INVALID, "%s: heads %d / %d, max_pages %d", who, a.Hq, a.Hkv, a.max_pages);
+    if (a.ldq % 8 || a.q_off % 8 || a.ld_out % 8 || a.q_off < 0 || a.q_off + a.Hq * 128 > a.ldq || a.ld_out < a.Hq * 128)
+        return fail(EMMAX_ERR_INVALID, "%s: ldq %d, q_off %d, ld_out %d in multiples of 8, the %d heads of 128 inside a row", who, a.ldq, a.q_off, a.ld_out, a.Hq);
+    if ((((uintptr_t)a.q | (uintptr_t)a.out | (uintptr_t)a.part) & 15) || (((uintptr_t)a.kcache | (uintptr_t)a.vcache) & (kv8 ? 7 : 15)) ||
+        (((uintptr_t)a.kscale | (uintptr_t)a.vscale | (uintptr_t)a.cu | (uintptr_t)a.base | (uintptr_t)a.page_table) & 3))
+        return fail(EMMAX_ERR_INVALID, "%s: q, out, the workspace and bf16 pages 16-byte aligned, e4m3 pages 8-byte, scales and tables 4-byte", who);
+    int max_n = 0, max_L = 0;
+    if (int r = extend_op_lengths(who, a.cu, a.base, a.B, total_rows, (long)a.max_pages * page, &max_n, &max_L, st)) return r;
+    ExtendAttnPlan f;
+    if (!extend_attn_plan(a.B, max_n, max_L, a.Hq, a.Hkv, nsplit, kv8, &f)) return fail(EMMAX_ERR_INVALID, "%s: unsupported (GQA group in {1,2,4,8}, nsplit 0..16)", who);
+    if (nsplit_out) *nsplit_out = f.nsplit;
+    if (f.split && (!a.part || ws_floats < (long long)total_rows * a.Hq * f.nsplit * EMMAX_PSTRIDE))
+        return fail(EMMAX_ERR_INVALID, "%s: %d splits need a workspace of total_rows x Hq x nsplit x %d = %lld floats (given %lld)", who, f.nsplit, EMMAX_PSTRIDE,
+                    (long long)total_rows * a.Hq * f.nsplit * EMMAX_PSTRIDE, ws_floats);
+    const int r = launch_extend_attn(a, f, total_rows, st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "%s: launch failure", who);
+    return 0;
+}
+int emmax_op_extend_attention(const void* q, int ldq, int q_off, const void* kcache, const void* vcache, const int32_t* page_table, const int32_t* cu,
+                              const int32_t* base, int B, int total_rows, int Hq, int Hkv, int page, int max_pages, int nsplit, float scale, void* out, int ld_out,
+                              float* ws, long long ws_floats, int* nsplit_out, emmax_stream st) {
+    ExtendAttnParams a;
+    memset(&a, 0, sizeof(a));
+    a.q = q; a.ldq = ldq; a.q_off = q_off; a.out = out; a.ld_out = ld_out; a.kcache = kcache; a.vcache = vcache; a.page_table = page_table; a.cu = cu; a.base = base;
+    a.part = ws; a.B = B; a.Hq = Hq; a.Hkv = Hkv; a.max_pages = max_pages; a.scale = scale;
+    return op_extend_attention("emmax_op_extend_attention", a, total_rows, page, nsplit, 0, ws_floats, nsplit_out, (hipStream_t)st);
+}
+int emmax_op_extend_attention_kv8(const void* q, int ldq, int q_off, const void* kcache8, const void* vcache8, const float* kscale, const float* vscale,
+                                  const int32_t* page_table, const int32_t* cu, const int32_t* base, int B, int total_rows, int Hq, int Hkv, int page, int max_pages,
+                                  int nsplit, float scale, void* out, int ld_out, float* ws, long long ws_floats, int* nsplit_out, emmax_stream st) {
+    if (!kscale || !vscale) return fail(EMMAX_ERR_INVALID, "emmax_op_extend_attention_kv8: null argument");
+    ExtendAttnParams a;
+    memset(&a, 0, sizeof(a));
+    a.q = q; a.ldq = ldq; a.q_off = q_off; a.out = out; a.ld_out = ld_out; a.kcache = kcache8; a.vcache = vcache8; a.kscale = kscale; a.vscale = vscale;
+    a.page_table = page_table; a.cu = cu; a.base = base; a.part = ws; a.B = B; a.Hq = Hq; a.Hkv = Hkv; a.max_pages = max_pages; a.scale = scale;
+    return op_extend_attention("emmax_op_extend_attention_kv8", a, total_rows, page, nsplit, 1, ws_floats, nsplit_out, (hipStream_t)st);
+}
+int emmax_op_rope_kv_write_at(void* qkv, int ld, int q_off, int k_off, int v_off, const int32_t* cu, const int32_t* base, int B, int total_rows, const float* cos_t,
+                              const float* sin_t, int max_pos, void* kcache, void* vcache, const int32_t* page_table, int max_pages, int Hq, int Hkv, int head_dim,
+                              int page, emmax_stream stream) {
+    const char* who = "emmax_op_rope_kv_write_at";
+    if (!qkv || !cu || !base || !cos_t || !sin_t || !page_table) return fail(EMMAX_ERR_INVALID, "%s: null argument", who);
+    if ((kcache == nullptr) != (vcache == nullptr)) return fail(EMMAX_ERR_INVALID, "%s: kcache and vcache go together (both null: rotate only)", who);
+    if (Hq < 1 || Hkv < 1 || page < 1 || max_pages < 1 || max_pos < 1) return fail(EMMAX_ERR_INVALID, "%s: heads %d / %d, page %d, max_pages %d, max_pos %d", who, Hq, Hkv, page, max_pages, max_pos);
+    if (head_dim < 16 || head_dim % 16 || (ld | q_off | k_off | v_off) % 8 || q_off < 0 || k_off < 0 || v_off < 0 || q_off + Hq * head_dim > ld || k_off + Hkv * head_dim > ld ||
+        v_off + Hkv * head_dim > ld)
+        return fail(EMMAX_ERR_INVALID, "%s: head_dim %d in multiples of 16, ld %d and the offsets %d / %d / %d in multiples of 8, the heads inside a row", who, head_dim, ld, q_off, k_off, v_off);
+    if ((((uintptr_t)qkv | (uintptr_t)kcache | (uintptr_t)vcache | (uintptr_t)cos_t | (uintptr_t)sin_t) & 15) || (((uintptr_t)cu | (uintptr_t)base | (uintptr_t)page_table) & 3))
+        return fail(EMMAX_ERR_INVALID, "%s: qkv, the caches and the RoPE tables must be 16-byte aligned, the index arrays 4-byte aligned", who);
+    int max_n = 0, max_L = 0;
+    if (int r = extend_op_lengths(who, cu, base, B, total_rows, std::min((long)max_pages * page, (long)max_pos), &max_n, &max_L, (hipStream_t)stream)) return r;
+    const int r = launch_rope_kv_write_at(qkv, ld, q_off, k_off, v_off, cu, base, B, total_rows, cos_t, sin_t, kcache, vcache, page_table, max_pages, Hq, Hkv, head_dim, page,
+                                          max_pos, (hipStream_t)stream);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "%s: launch failure", who);
+    return 0;
+}
 // the grouped form (decode_attn.hip: launch_group_attn) as a pure op: the shapes and the groups' shared page counts are checked on the host
 // BEFORE anything is launched (the counts are read back: the call synchronises the stream and cannot be captured)
 static int op_group_attention(const char* who, DecodeAttnParams& a, int B, int Hq, int N, const int32_t* shared_pages, hipStream_t st) {

@@ -43,6 +43,87 @@ static int run_prefill_x(emmax_session* s, const int32_t* ids, int B, int P_max,
     return 0;
 }
 
+// The decoder layers over the packed rows in s->ph / s->ph32 (embedded by the caller) and the gather of every sequence's last row into the decode
+// rows r0 ..: shared by the prefill (ext == nullptr: rows at positions 0 .., causal attention inside the qkv buffer) and by the extension of a cached
+// context (extend.hip: ext = the extension attention's plan)
+int run_prefill_layers(emmax_session* s, int B, int total, int maxS, int r0, const ExtendAttnPlan* ext, hipStream_t st) {
+    emmax_model* m = s->m;
+    const auto& c = m->cfg;
+    const bool p32 = s->p32;
+    auto input_norm = [&](const void* w) {
+        return p32 ? launch_rmsnorm_f32(s->ph32, s->pxn, w, total, m->H, m->H, m->H, c.rms_eps, st)
+                   : launch_rmsnorm(s->ph, s->pxn, w, total, m->H, m->H, m->H, c.rms_eps, st);
+    };
+    auto into_stream = [&](GemmParams& g) {   // C = residual stream += A W^T
+        if (p32) { g.C = s->ph32; g.out_f32 = 1; g.residual = s->ph32; g.res_f32 = 1; }
+        else { g.residual = s->ph; }
+        g.ldr = m->H;
+    };
+    // the RMSNorm behind a projection whose partial tiles meet in a split-K reduce pass (one-frame prefill: o-proj, down) is applied
+    // by that pass (gemm_fuses_norm); otherwise it is its own launch
+    auto with_norm = [&](GemmParams& g, const void* w) {
+        g.norm_w = w; g.norm_out = s->pxn; g.ld_norm = m->H; g.norm_eps = c.rms_eps;
+        if (gemm_fuses_norm(g)) return true;
+        g.norm_w = nullptr; g.norm_out = nullptr;
+        return false;
+    };
+    bool normed = false;   // s->pxn already holds ln1 of the current layer
+    for (int li = 0; li < c.n_layers; ++li) {
+        const LayerW& L = m->layers[li];
+        if (!normed) KCHK(input_norm(L.ln1));
+        GemmParams g = gps(s, s->pxn, m->H, L.proj[STAGE_QKV].rm, m->H, s->pqkv, m->qkv_dim, total, m->qkv_dim, m->H);
+        KCHK(launch_gemm(g, st));
+        const int32_t* ptab = s->page_table + (size_t)r0 * s->max_pages;
+        if (ext) {
+            // the rows sit at position ext_base[b] + i: RoPE, the K / V append and the attention take that offset from the device, and the attention
+            // reads keys and values from the paged cache alone -- the cached prefix and the rows just appended (extend_attn.hip)
+            KCHK(launch_rope_kv_write_at(s->pqkv, m->qkv_dim, 0, m->q_dim, m->q_dim + m->kv_dim, s->cu, s->ext_base, B, total, s->cos_t, s->sin_t,
+                                         s->kv8 ? nullptr : kcache_of(s, li), s->kv8 ? nullptr : vcache_of(s, li), ptab, s->max_pages, c.n_heads, c.n_kv_heads,
+                                         c.head_dim, PAGE, s->max_ctx, st));
+            if (s->kv8)
+                KCHK(launch_kv_quant_rows_at(s->pqkv, m->qkv_dim, m->q_dim, m->q_dim + m->kv_dim, s->cu, s->ext_base, B, total, kcache_of(s, li), vcache_of(s, li),
+                                             kscale_of(s, li), vscale_of(s, li), ptab, s->max_pages, c.n_kv_heads, c.head_dim, PAGE, st));
+            ExtendAttnParams a;
+            memset(&a, 0, sizeof(a));
+            a.q = s->pqkv; a.ldq = m->qkv_dim; a.q_off = 0; a.out = s->patt; a.ld_out = m->q_dim;
+            a.kcache = kcache_of(s, li); a.vcache = vcache_of(s, li);
+            if (s->kv8) { a.kscale = kscale_of(s, li); a.vscale = vscale_of(s, li); }
+            a.page_table = ptab; a.cu = s->cu; a.base = s->ext_base; a.part = s->splitk_ws;   // (the split-K scratch is idle between two GEMMs)
+            a.B = B; a.Hq = c.n_heads; a.Hkv = c.n_kv_heads; a.max_pages = s->max_pages; a.scale = 1.0f / sqrtf((float)c.head_dim);
+            KCHK(launch_extend_attn(a, *ext, total, st));
+        } else {
+            // (fp8 KV cache: the pass rotates q / k in place only, the quantising pass appends K and V as e4m3 rows + scales)
+            KCHK(launch_rope_kv_write(s->pqkv, m->qkv_dim, 0, m->q_dim, m->q_dim + m->kv_dim, s->cu, B, total, s->cos_t, s->sin_t,
+                                      s->kv8 ? nullptr : kcache_of(s, li), s->kv8 ? nullptr : vcache_of(s, li), s->page_table + (size_t)r0 * s->max_pages,
+                                      s->max_pages, c.n_heads, c.n_kv_heads, c.head_dim, PAGE, st));
+            if (s->kv8)
+                KCHK(launch_kv_quant_rows(s->pqkv, m->qkv_dim, m->q_dim, m->q_dim + m->kv_dim, s->cu, B, total, kcache_of(s, li), vcache_of(s, li),
+                                          kscale_of(s, li), vscale_of(s, li), s->page_table + (size_t)r0 * s->max_pages, s->max_pages, c.n_kv_heads,
+                                          c.head_dim, PAGE, st));
+            AttnParams a;
+            a.qkv = s->pqkv; a.out = s->patt; a.cu_seqlens = s->cu;
+            a.ld_qkv = m->qkv_dim; a.q_off = 0; a.k_off = m->q_dim; a.v_off = m->q_dim + m->kv_dim; a.ld_out = m->q_dim;
+            a.B = B; a.max_seqlen = maxS; a.Hq = c.n_heads; a.Hkv = c.n_kv_heads;
+            a.scale = 1.0f / sqrtf((float)c.head_dim); a.causal = 1;
+            KCHK(launch_attention(a, c.head_dim, st));
+        }
+        g = gps(s, s->patt, m->q_dim, L.proj[STAGE_OPROJ].rm, m->q_dim, s->ph, m->H, total, m->H, m->q_dim);
+        into_stream(g);
+        normed = with_norm(g, L.ln2);
+        KCHK(launch_gemm(g, st));
+        if (!normed) KCHK(input_norm(L.ln2));
+        g = gps(s, s->pxn, m->H, L.proj[STAGE_GATEUP].rm, m->H, s->pact, m->inter_p, total, 2 * m->inter_p, m->H);
+        g.act = 2;
+        KCHK(launch_gemm(g, st));
+        g = gps(s, s->pact, m->inter_p, L.proj[STAGE_DOWN].rm, m->inter_p, s->ph, m->H, total, m->H, m->inter_p);
+        into_stream(g);
+        normed = li + 1 < c.n_layers && with_norm(g, m->layers[li + 1].ln1);
+        KCHK(launch_gemm(g, st));
+    }
+    KCHK(launch_gather_last_rows(s->ph, s->dh + (size_t)r0 * m->H, s->cu, B, m->H, st, h32_of(s, r0), p32 ? s->ph32 : nullptr));
+    return 0;
+}
+
 // patches == nullptr: language-only forward (no patch rows are spliced in; modeling_prismatic.py:343-359)
 // slot0 >= 0: slot serving -- the B (= 1) rows land in rows slot0.. of the live decode batch, whose other rows are untouched
 int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B, int P_max, const void* patches, hipStream_t st, int slot0) {
@@ -143,57 +224,7 @@ int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B
     const bool p32 = emmax_tune().resid32 == 1;
     s->p32 = p32;
     KCHK(launch_embed_splice(ids, P_max, s->cu, m->embed, patches, s->ph, B, maxS, np, m->H, m->vocab, st, p32 ? s->ph32 : nullptr));
-    auto input_norm = [&](const void* w) {
-        return p32 ? launch_rmsnorm_f32(s->ph32, s->pxn, w, total, m->H, m->H, m->H, c.rms_eps, st)
-                   : launch_rmsnorm(s->ph, s->pxn, w, total, m->H, m->H, m->H, c.rms_eps, st);
-    };
-    auto into_stream = [&](GemmParams& g) {   // C = residual stream += A W^T
-        if (p32) { g.C = s->ph32; g.out_f32 = 1; g.residual = s->ph32; g.res_f32 = 1; }
-        else { g.residual = s->ph; }
-        g.ldr = m->H;
-    };
-    // the RMSNorm behind a projection whose partial tiles meet in a split-K reduce pass (one-frame prefill: o-proj, down) is applied
-    // by that pass (gemm_fuses_norm); otherwise it is its own launch
-    auto with_norm = [&](GemmParams& g, const void* w) {
-        g.norm_w = w; g.norm_out = s->pxn; g.ld_norm = m->H; g.norm_eps = c.rms_eps;
-        if (gemm_fuses_norm(g)) return true;
-        g.norm_w = nullptr; g.norm_out = nullptr;
-        return false;
-    };
-    bool normed = false;   // s->pxn already holds ln1 of the current layer
-    for (int li = 0; li < c.n_layers; ++li) {
-        const LayerW& L = m->layers[li];
-        if (!normed) KCHK(input_norm(L.ln1));
-        GemmParams g = gps(s, s->pxn, m->H, L.proj[STAGE_QKV].rm, m->H, s->pqkv, m->qkv_dim, total, m->qkv_dim, m->H);
-        KCHK(launch_gemm(g, st));
-        // (fp8 KV cache: the pass rotates q / k in place only, the quantising pass appends K and V as e4m3 rows + scales)
-        KCHK(launch_rope_kv_write(s->pqkv, m->qkv_dim, 0, m->q_dim, m->q_dim + m->kv_dim, s->cu, B, total, s->cos_t, s->sin_t,
-                                  s->kv8 ? nullptr : kcache_of(s, li), s->kv8 ? nullptr : vcache_of(s, li), s->page_table + (size_t)r0 * s->max_pages,
-                                  s->max_pages, c.n_heads, c.n_kv_heads, c.head_dim, PAGE, st));
-        if (s->kv8)
-            KCHK(launch_kv_quant_rows(s->pqkv, m->qkv_dim, m->q_dim, m->q_dim + m->kv_dim, s->cu, B, total, kcache_of(s, li), vcache_of(s, li),
-                                      kscale_of(s, li), vscale_of(s, li), s->page_table + (size_t)r0 * s->max_pages, s->max_pages, c.n_kv_heads,
-                                      c.head_dim, PAGE, st));
-        AttnParams a;
-        a.qkv = s->pqkv; a.out = s->patt; a.cu_seqlens = s->cu;
-        a.ld_qkv = m->qkv_dim; a.q_off = 0; a.k_off = m->q_dim; a.v_off = m->q_dim + m->kv_dim; a.ld_out = m->q_dim;
-        a.B = B; a.max_seqlen = maxS; a.Hq = c.n_heads; a.Hkv = c.n_kv_heads;
-        a.scale = 1.0f / sqrtf((float)c.head_dim); a.causal = 1;
-        KCHK(launch_attention(a, c.head_dim, st));
-        g = gps(s, s->patt, m->q_dim, L.proj[STAGE_OPROJ].rm, m->q_dim, s->ph, m->H, total, m->H, m->q_dim);
-        into_stream(g);
-        normed = with_norm(g, L.ln2);
-        KCHK(launch_gemm(g, st));
-        if (!normed) KCHK(input_norm(L.ln2));
-        g = gps(s, s->pxn, m->H, L.proj[STAGE_GATEUP].rm, m->H, s->pact, m->inter_p, total, 2 * m->inter_p, m->H);
-        g.act = 2;
-        KCHK(launch_gemm(g, st));
-        g = gps(s, s->pact, m->inter_p, L.proj[STAGE_DOWN].rm, m->inter_p, s->ph, m->H, total, m->H, m->inter_p);
-        into_stream(g);
-        normed = li + 1 < c.n_layers && with_norm(g, m->layers[li + 1].ln1);
-        KCHK(launch_gemm(g, st));
-    }
-    KCHK(launch_gather_last_rows(s->ph, s->dh + (size_t)r0 * m->H, s->cu, B, m->H, st, h32_of(s, r0), p32 ? s->ph32 : nullptr));
+    if (int r = run_prefill_layers(s, B, total, maxS, r0, nullptr, st)) return r;
     if (int r = s->grp_N ? run_group_fork(s, B, st) : run_lm_head_step(s, B, true, nullptr, true, st, r0)) return r;
     s->prefilled = true;
     s->beam.ready = s->beam.K != 0;

@@ -301,6 +301,7 @@ struct emmax_session {
     // n_out, max_new, stop_m, stop_after, -) and an output row each -- so that a single stage never touches the session's generation state
     int op_rows = 0;
     int32_t *op_state = nullptr, *op_out = nullptr;
+    int32_t* ext_base = nullptr;   // emmax_extend / emmax_slot_extend (extend.hip): the extended rows' cached lengths before the call, int32 [max_batch]
     hipEvent_t ev = nullptr;
     int graph_epoch = -1;      // emmax_tune().epoch the graph was captured under (a changed switch re-captures)
     int graph_grp = 0;    // attn_group_rows() the step was captured under (rows per group of the grouped attention route, 0 = today's launch)
@@ -375,6 +376,10 @@ GemmParams gps(emmax_session* s, const void* A, int lda, const void* W, int ldw,
 GemmParams gpx(emmax_session* s, const void* A_hl, int Kp, const void* W, int ldw, float* C, int ldc, int M, int N);
 // prefill.hip
 int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B, int P_max, const void* patches, hipStream_t st, int slot0 = -1);
+// the decoder layers over the packed rows + the gather of the last rows; ext != nullptr: the rows extend a cached context (extend_attn.hip)
+int run_prefill_layers(emmax_session* s, int B, int total, int maxS, int r0, const ExtendAttnPlan* ext, hipStream_t st);
+// extend.hip: lens[b] more tokens on top of the cached context of rows r0 .. r0 + B (slot: a request slot, between two steps)
+int run_extend(emmax_session* s, int r0, int B, const int32_t* ids, const int32_t* lens, int P_max, int max_new, bool slot, hipStream_t st);
 // step.hip
 int model_max_decode_batch(const emmax_model* m, bool exact = false, int* first_stage = nullptr, int* first_B = nullptr);   // the planner: the largest batch every stage has a route for
 int session_max_rows(const emmax_session* s);                      // ... of the session's model and numerics

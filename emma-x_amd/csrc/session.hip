@@ -142,6 +142,7 @@ static void plan_session(emmax_session* s, Bump& b) {
     s->op_rows = std::min(Bd, EMMAX_MAX_DECODE_BATCH);
     s->op_state = (int32_t*)b.bytes((int64_t)s->op_rows * 8 * 4);
     s->op_out = (int32_t*)b.bytes((int64_t)s->op_rows * s->max_out * 4);
+    s->ext_base = (int32_t*)b.bytes((int64_t)Bd * 4);
     if (s->exact) {
         const int64_t npr = (int64_t)Bv * np;
         auto mx = [](int64_t a, int64_t b2) { return a > b2 ? a : b2; };

@@ -114,6 +114,16 @@ SIGNATURES = {
                                                       _vp, C.c_float, _vp]),
     "emmax_decode_attn_plan": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int)] * 5),
     "emmax_group_attn_plan": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int)] * 4),
+    "emmax_extend": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _c_i32p, C.c_int, C.c_int, _vp]),
+    "emmax_slot_extend": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp]),
+    "emmax_session_context": (C.c_int, [_vp, C.c_int, C.c_int, _c_i32p, _vp]),
+    "emmax_op_extend_attention": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp] + [C.c_int] * 7 + [C.c_float, _vp, C.c_int, _vp, C.c_longlong,
+                                            C.POINTER(C.c_int), _vp]),
+    "emmax_op_extend_attention_kv8": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp] + [C.c_int] * 7 + [C.c_float, _vp, C.c_int, _vp,
+                                                C.c_longlong, C.POINTER(C.c_int), _vp]),
+    "emmax_op_rope_kv_write_at": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp] + [C.c_int] * 5
+                                  + [_vp]),
+    "emmax_extend_attn_plan": (C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_int)] * 5),
     "emmax_op_gemv": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "emmax_op_resize_bicubic_u8": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp]),
     "emmax_op_quant_fm8": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp]),

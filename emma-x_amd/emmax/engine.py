@@ -138,6 +138,7 @@ class EmmaxEngine:
         self._top_bufs = None     # ... and no top / watched log-probability buffers
         self._beam_K = 0          # ... and has beams off
         self._group_N = 0         # ... and sample groups off
+        self.session_epoch = getattr(self, "session_epoch", 0) + 1   # which session a KV handle names (modeling.KVHandle)
         self.max_batch, self.max_prompt, self.max_ctx, self.stage_rows = max_batch, max_prompt, max_ctx, int(stage_rows)
 
     def ensure_stage_rows(self, n: int) -> None:
@@ -316,6 +317,50 @@ class EmmaxEngine:
         lp = torch.empty(B, max_new_tokens, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.emmax_session_logprobs(self._session, max_new_tokens, lp.data_ptr(), _lib.current_stream()), "emmax_session_logprobs")
         return out, lens, lp
+
+    # ---- extending a cached context (include/emmax.h: emmax_extend) ----------------------------------------------------------
+    def _check_extension_fits(self, who: str, n_rows: int, longest: int) -> None:
+        """A continuation must never re-create the session (that would drop the very cache it extends): what ensure_capacity would grow is an error."""
+        if n_rows > self.max_batch or longest * n_rows > self.max_batch * (self.cfg.n_patches + self.max_prompt):
+            raise _lib.EmmaxError(
+                f"{who}: {n_rows} rows of up to {longest} new ids exceed the session's prefill capacity (max_batch {self.max_batch} x "
+                f"(n_patches + max_prompt {self.max_prompt}) packed rows); a continuation cannot re-create the session -- create it larger "
+                f"(max_prompt / cache_reserve / max_ctx) before the first prefill")
+
+    def extend(self, rows: Sequence[Sequence[int]], row0: int = 0, max_new_tokens: int = 0) -> List[int]:
+        """Append the ids rows[b] (>= 1 each) to the cached context of live rows row0 .. row0 + len(rows) - 1 -- after a prefill and any number of
+        decode steps -- in one pass over the new rows alone.  A row's pending token (picked, not yet cached) is dropped: pass it as the first id
+        to keep it.  Afterwards the rows are as a prefill leaves them (first token of the continuation picked; `generate` continues), and
+        prefill_logits() returns the new rows' logits.  max_new_tokens: what will be generated next, for the capacity check (a context beyond
+        max_ctx is refused: it is fixed when the session is created).  Returns the rows' new cached lengths."""
+        rows = [list(r) for r in rows]
+        B = len(rows)
+        self._check_extension_fits("extend", B, max(len(r) for r in rows))
+        ids_d, lens, P_max, _ = self._pack_prompts("extend", rows, self.cfg.pad_token_id)
+        lens_c = (C.c_int32 * B)(*lens)
+        _lib.check(self.lib.emmax_extend(self._session, int(row0), B, ids_d.data_ptr(), lens_c, P_max, int(max_new_tokens), _lib.current_stream()),
+                   "emmax_extend")
+        torch.cuda.current_stream().synchronize()   # `ids_d` must outlive the pass
+        self._last_S = list(lens)   # what prefill_logits splits by: the new rows
+        return self.context_lengths(int(row0), B)
+
+    def slot_extend(self, slot: int, ids: Sequence[int], max_new_tokens: int) -> None:
+        """A follow-up on the context a FINISHED request left in `slot` (done, not released): its ids are appended in one pass, the first token
+        of the answer is in place afterwards and the slot decodes again with the new budget.  The other slots are untouched."""
+        ids = list(ids)
+        self._check_extension_fits("slot_extend", 1, len(ids))
+        ids_d = torch.as_tensor(ids, dtype=torch.int32).to(self.device)
+        _lib.check(self.lib.emmax_slot_extend(self._session, int(slot), ids_d.data_ptr(), len(ids), int(max_new_tokens), _lib.current_stream()),
+                   "emmax_slot_extend")
+        torch.cuda.current_stream().synchronize()   # `ids_d` must outlive the pass
+        self._last_S = [len(ids)]   # what prefill_logits splits by: the slot's new rows
+
+    def context_lengths(self, row0: int = 0, n: Optional[int] = None) -> List[int]:
+        """The cached lengths of rows row0 .. row0 + n - 1 (default: the live batch), read back from the device."""
+        n = self._last_B if n is None else int(n)
+        out = (C.c_int32 * n)()
+        _lib.check(self.lib.emmax_session_context(self._session, int(row0), n, out, _lib.current_stream()), "emmax_session_context")
+        return list(out)
 
     # ---- sampling inside the decode step (include/emmax.h, ABI 7) -------------------------------------------------------
     @staticmethod

@@ -75,6 +75,8 @@ class EmmaXGenerateOutput:
     top_token_ids: Optional[torch.Tensor] = None
     top_logprobs: Optional[torch.Tensor] = None
     watch_logprobs: Optional[torch.Tensor] = None
+    # what the call left cached (a KVHandle; its lengths are read back from the session): generate(..., past_key_values=it) continues from there
+    past_key_values: Optional[Any] = None
 
     def __getitem__(self, key: str):
         return getattr(self, key)
@@ -94,10 +96,13 @@ class TopLogprobsOutput:
 
 
 class KVHandle:
-    """Opaque stand-in for HF `past_key_values`: the cache lives in the engine's paged KV memory."""
+    """Opaque stand-in for HF `past_key_values`: the cache lives in the engine's paged KV memory.  lengths: the rows' cached lengths (patch rows
+    included: n_patches of them per row, 0 behind a language-only forward); session: which session of the engine holds them -- a handle of a
+    session that was re-created since names nothing."""
 
-    def __init__(self, engine: EmmaxEngine, lengths: List[int]):
-        self.engine, self.lengths = engine, list(lengths)
+    def __init__(self, engine: EmmaxEngine, lengths: List[int], n_patches: int = 0):
+        self.engine, self.lengths, self.n_patches = engine, list(lengths), int(n_patches)
+        self.session = getattr(engine, "session_epoch", 0)
 
 
 class EmmaXForActionPrediction:
@@ -317,6 +322,57 @@ class EmmaXForActionPrediction:
         eng.prefill(rows, patches)
         return patches
 
+    def _check_handle(self, handle, n_rows: int, who: str) -> None:
+        eng = self._need_engine()
+        if not isinstance(handle, KVHandle) or handle.engine is not eng:
+            raise ValueError(f"{who}: past_key_values / continue_from must be the KVHandle an earlier call of this model returned")
+        if handle.session != getattr(eng, "session_epoch", 0):
+            raise ValueError(f"{who}: the handle's session was re-created since (a later call needed more rows, a longer prompt or more context than "
+                             "the session had: create the model with max_batch / max_prompt / max_ctx, or raise cache_reserve, for the whole dialogue)")
+        if n_rows != len(handle.lengths) or n_rows != getattr(eng, "_last_B", -1):
+            raise ValueError(f"{who}: {n_rows} rows continue a cache of {len(handle.lengths)} rows: a continuation keeps the batch")
+
+    def _continue(self, handle, rows: List[List[int]], max_new: int = 0, sampling=None, processing=None, scores=None, logits=None, top=None,
+                  constraint=None, constraint_start=None) -> None:
+        """_prefill for rows that continue a cached context: no vision, no prefill -- the new ids are appended to what the handle's rows hold
+        (engine.extend).  The session is never re-created here."""
+        eng = self._need_engine()
+        B = len(rows)
+        self._check_handle(handle, B, "continue_from")
+        if any(len(r) < 1 for r in rows):
+            raise ValueError("every continued row needs at least one new id (the row's last emitted token, if nothing else)")
+        if getattr(eng, "beams", 0) or getattr(eng, "sample_groups", 0):
+            raise NotImplementedError("a cache left by beam search or sample groups is not continued (outside the hot path)")
+        if processing is not None:
+            ps = processing if isinstance(processing, (list, tuple)) else [processing]
+            if any(p.repetition_penalty != 1.0 or p.no_repeat_ngram_size > 0 or p.min_new_tokens > 0 for p in ps):
+                raise NotImplementedError("repetition_penalty / no_repeat_ngram_size / min_new_tokens with a continuation are outside the hot path: the "
+                                          "processors' id history holds the prompt only, not the cached context it would have to read")
+        if scores is not None or logits is not None:
+            self._check_score_buffers(scores, logits, max_new, B, eng.cfg.llm.vocab_size)
+        if getattr(eng, "automaton", False):
+            eng.clear_automaton()    # (a constraint of this call enters at its start states: the extension restarts only rows outside an automaton)
+        rules = processing is not None and any(p.rule_enable for p in (processing if isinstance(processing, (list, tuple)) else [processing]))
+        if getattr(eng, "processing", False):
+            eng.clear_processing()   # (history-reading processors are not continued; token rules / the automaton turn their neutral form on again)
+        if rules:
+            eng.set_token_rules(processing, n=B)
+        elif getattr(eng, "token_rules", False):
+            eng.clear_token_rules()
+        if scores is not None or logits is not None:
+            eng.set_scores(scores, logits, max_new, rows=B)
+        elif getattr(eng, "scores_bound", False):
+            eng.set_scores(None, None)
+        self._set_sampling(eng, B, sampling)
+        if top is not None:
+            eng.set_top_logprobs(top[0], top[1], max(max_new, 1))
+        elif getattr(eng, "top_logprobs_bound", False):
+            eng.clear_top_logprobs()
+        if constraint is not None:
+            eng.set_automaton(constraint)
+            eng.set_automaton_starts(constraint.starts(constraint_start, B))
+        eng.extend(rows, max_new_tokens=max(max_new, 1))
+
     @staticmethod
     def _beam_args(num_beams=None, num_return_sequences=None, length_penalty=None, early_stopping=None, do_sample: bool = False,
                    processing=None, output_scores: bool = False) -> Optional[BeamParams]:
@@ -475,6 +531,15 @@ class EmmaXForActionPrediction:
             return EmmaXCausalLMOutputWithPast(logits=logits, past_key_values=past_key_values)
         if input_ids is not None and isinstance(input_ids, torch.Tensor) and input_ids.shape[-1] == 1:
             assert past_key_values is not None, "You must provide `past_key_values` during cached generation!"
+        if past_key_values is not None and pixel_values is None and frames_u8 is None:
+            # n > 1 new ids per row on top of the handle's cache (ragged rows: lists, or a right-padding mask): one pass over the new rows alone
+            self._check_handle(past_key_values, len(rows), "forward")
+            self._set_processing(eng, len(rows), None)   # (as the language-only branch: what an earlier generate left in the session is cleared)
+            eng.extend(rows, max_new_tokens=0)
+            per_row = eng.prefill_logits()
+            past_key_values.lengths = [n + len(r) for n, r in zip(past_key_values.lengths, rows)]
+            same = len({t.shape[0] for t in per_row}) == 1
+            return EmmaXCausalLMOutputWithPast(logits=torch.stack(per_row) if same else per_row, past_key_values=past_key_values)
         if pixel_values is None and frames_u8 is None:
             # unimodal forward (modeling_prismatic.py:343-359): text only, no patch rows
             assert inputs_embeds is None, "Missing `input_ids` in language-only forward!"
@@ -486,12 +551,14 @@ class EmmaXForActionPrediction:
             same = len({t.shape[0] for t in per_row}) == 1
             return EmmaXCausalLMOutputWithPast(logits=torch.stack(per_row) if same else per_row,
                                                past_key_values=KVHandle(eng, eng._last_S) if use_cache else None)
+        if past_key_values is not None:
+            raise ValueError("forward(past_key_values=...) extends the cached rows with text ids: pass no pixel_values / frames_u8 with it")
         patches = self._prefill(rows, pixel_values, frames_u8, max_new=self.cache_reserve if use_cache else 0)
         per_row = eng.prefill_logits()
         same = len({t.shape[0] for t in per_row}) == 1
         logits = torch.stack(per_row) if same else per_row
         return EmmaXCausalLMOutputWithPast(
-            logits=logits, past_key_values=KVHandle(eng, eng._last_S) if use_cache else None,
+            logits=logits, past_key_values=KVHandle(eng, eng._last_S, self.config.n_patches) if use_cache else None,
             projector_features=patches if output_projector_features else None)
 
     __call__ = forward
@@ -500,7 +567,7 @@ class EmmaXForActionPrediction:
     def generate_ids(self, rows: List[List[int]], pixel_values=None, frames_u8=None, max_new_tokens: int = 512,
                      stop_on_eos: bool = True, sampling=None, return_logprobs: bool = False, processing=None, scores=None, logits=None,
                      beams: Optional[BeamParams] = None, num_samples: int = 1, top_logprobs: int = 0, watch_ids: Optional[Sequence[int]] = None,
-                     constraint=None, constraint_start=None):
+                     constraint=None, constraint_start=None, continue_from=None, return_handle: bool = False):
         """Decode every row: greedy, or sampled in the step with `sampling` (one SamplingParams for all rows or one per row; row b draws
         with subseq b).  `processing` (one LogitsProcessing for all rows or one per row) applies HF's repetition penalty / n-gram ban /
         min-new-tokens in the step first.  `scores` / `logits`: fp32 [max_new, B, vocab] device buffers the step fills with HF's scores /
@@ -520,7 +587,19 @@ class EmmaXForActionPrediction:
         `constraint` (constraints.TokenAutomaton): constrained decoding in the step -- a row in automaton state s can only emit the ids that
         state allows (HF's prefix_allowed_tokens_fn, compiled).  `constraint_start`: None = every row enters at the automaton's entry "start"
         (state 0 without one), a name / state = every row there, a list = one per result row (None in it: that row is unconstrained).  Works
-        greedy, sampled and with num_samples; not with beams.  Scores are -inf at the ids the automaton forbids; log-probabilities stay raw."""
+        greedy, sampled and with num_samples; not with beams.  Scores are -inf at the ids the automaton forbids; log-probabilities stay raw.
+        `continue_from` (the KVHandle of an earlier call on the same rows): `rows` are the NEW ids per row, appended to what the handle's rows
+        hold -- no vision, no prefill, one pass over the new rows (engine.extend).  A row's last emitted token is not cached: pass it first.
+        Greedy, sampling, warpers, token rules, top_logprobs / watch_ids, scores and constraint work as after a prefill; beams, num_samples > 1
+        and repetition_penalty / no_repeat_ngram_size / min_new_tokens raise NotImplementedError.
+        `return_handle`: the return gains one trailing KVHandle of what the call leaves cached (lengths read back from the session)."""
+        if continue_from is not None:
+            if beams is not None:
+                raise NotImplementedError("num_beams > 1 with a continuation is outside the hot path (beams fork their rows from a fresh prefill)")
+            if self._check_num_samples(num_samples) > 1:
+                raise NotImplementedError("num_return_sequences > 1 with a continuation is outside the hot path (sample groups fork from a fresh prefill)")
+            if pixel_values is not None or frames_u8 is not None:
+                raise ValueError("a continuation appends text ids to the cached rows: pass no pixel_values / frames_u8 with continue_from")
         cst = self._check_constraint(constraint, constraint_start, beams.num_beams if beams is not None else 1,
                                      len(rows) * self._check_num_samples(num_samples))
         n_top, watch = check_top_logprobs(top_logprobs, watch_ids, self.config.llm.vocab_size, "generate_ids")
@@ -549,16 +628,26 @@ class EmmaXForActionPrediction:
                 raise ValueError("processing must be LogitsProcessing (one, or one per row)")
         self._check_score_buffers(scores, logits, max_new_tokens, len(rows) * (beams.num_beams if beams is not None else N),
                                   self.config.llm.vocab_size)
+        def start(**kw):   # the rows' context: a prefill, or the new ids on top of what continue_from holds
+            if continue_from is not None:
+                return self._continue(continue_from, rows, **kw)
+            return self._prefill(rows, pixel_values, frames_u8, beams=beams, **self._sample_kw(N), **kw)
+
+        def handle():      # what the call leaves cached (the rows of the result: beams / sample groups have B x K of them)
+            if not return_handle:
+                return ()
+            n_pat = continue_from.n_patches if continue_from is not None else self.config.n_patches
+            return (KVHandle(eng, eng.context_lengths(0, eng._last_B * (beams.num_beams if beams is not None else 1)), n_pat),)
+
         if not want_top:
-            self._prefill(rows, pixel_values, frames_u8, max_new=max_new_tokens, sampling=sampling, processing=processing, scores=scores,
-                          logits=logits, beams=beams, **self._sample_kw(N), **cst)
+            start(max_new=max_new_tokens, sampling=sampling, processing=processing, scores=scores, logits=logits, **cst)
             out = eng.generate(max_new_tokens, stop_on_eos, return_logprobs=return_logprobs)
             if scores is not None or logits is not None:
                 eng.set_scores(None, None)   # the buffers are the caller's now: no later step or prefill writes into them
-            return out
+            return tuple(out) + handle() if return_handle else out
         # a greedy caller: temperature-0 sampling underneath (the argmax of the same fp32 rows), so that the logit rows are written
-        self._prefill(rows, pixel_values, frames_u8, max_new=max_new_tokens, sampling=sampling if sampling is not None else SamplingParams(0.0, 0, 1.0, seed=0),
-                      processing=processing, scores=scores, logits=logits, top=(n_top, watch), **self._sample_kw(N), **cst)
+        start(max_new=max_new_tokens, sampling=sampling if sampling is not None else SamplingParams(0.0, 0, 1.0, seed=0),
+              processing=processing, scores=scores, logits=logits, top=(n_top, watch), **cst)
         ids, lens, lp = eng.generate(max_new_tokens, stop_on_eos, return_logprobs=True)
         B = ids.shape[0]
         ti, tl, wl = (t[:B] for t in eng._top_bufs)
@@ -568,7 +657,7 @@ class EmmaXForActionPrediction:
         if sampling is None:
             eng.clear_sampling()
         top = TopLogprobsOutput(top_ids=ti, top_logprobs=tl, watch_logprobs=wl, logprobs=lp)
-        return (ids, lens, lp, top) if return_logprobs else (ids, lens, top)
+        return ((ids, lens, lp, top) if return_logprobs else (ids, lens, top)) + handle()
 
     def _check_constraint(self, constraint, constraint_start, num_beams: int, n_rows: int) -> Dict[str, Any]:
         """`constraint` / `constraint_start` of a call, checked before the engine is touched -> _prefill's keywords ({}: no constraint)."""
@@ -631,7 +720,7 @@ class EmmaXForActionPrediction:
                  top_p: Optional[float] = None, seed: Optional[int] = None, generator: Optional[torch.Generator] = None,
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
                  output_scores: bool = False, output_logits: bool = False, return_dict_in_generate: bool = False, top_logprobs: int = 0,
-                 watch_ids: Optional[Sequence[int]] = None, **kwargs):
+                 watch_ids: Optional[Sequence[int]] = None, past_key_values=None, **kwargs):
         """HF-style: returns LongTensor [B, P + T] = prompt ++ generated (right-padded with pad_token_id).  do_sample=True draws every token
         in the decode step (include/emmax.h: emmax_session_set_sampling) with temperature / top_k / top_p (HF defaults 1.0 / 50 / 1.0 when
         unset); row b draws with (seed, subseq b), seed None = draw_seed(generator).  With num_return_sequences=N the prompt is prefilled once
@@ -641,14 +730,37 @@ class EmmaXForActionPrediction:
         returns an EmmaXGenerateOutput: `sequences` (the tensor), and with output_scores / output_logits a tuple of T = max(lens) fp32
         [B, vocab] device tensors each (NaN past a row's length).  constraint= (a constraints.TokenAutomaton) and constraint_start= constrain the
         rows in the step as generate_ids describes (sample groups are served; num_beams > 1 and prefix_allowed_tokens_fn= raise).  top_logprobs=N / watch_ids=[...] (with return_dict_in_generate; not with
-        num_beams > 1): `top_token_ids` / `top_logprobs` [B, T, N] and `watch_logprobs` [B, T, W] of the output, over the RAW logits."""
+        num_beams > 1): `top_token_ids` / `top_logprobs` [B, T, N] and `watch_logprobs` [B, T, W] of the output, over the RAW logits.
+        past_key_values= (the KVHandle in `past_key_values` of an earlier return_dict_in_generate=True call, or of forward(use_cache=True)):
+        HF-style multi-turn -- input_ids is the FULL text sequence, the part behind the handle's cached length is appended to the cache (no
+        vision, no prefill; at least one id per row, usually the last token of the previous answer); num_beams > 1, num_return_sequences > 1
+        and repetition_penalty / no_repeat_ngram_size raise NotImplementedError with it.  The output's `past_key_values` is the handle of what
+        this call leaves cached."""
         n_top, watch = check_top_logprobs(top_logprobs, watch_ids, self.config.llm.vocab_size, "generate")
         want_top = n_top > 0 or len(watch) > 0
         if want_top and not return_dict_in_generate:
             raise ValueError("top_logprobs / watch_ids are returned in the generate output: pass return_dict_in_generate=True")
         cst = self._kw_constraint(kwargs)   # (before the engine is touched: num_beams > 1 and prefix_allowed_tokens_fn raise here)
         rows = self._rows(input_ids, attention_mask)
-        processing = self._processing_args(rows, repetition_penalty, no_repeat_ngram_size, min_new_tokens, min_length, **self._kw_rules(kwargs))
+        cont = {}
+        full_rows = rows
+        if past_key_values is not None:   # the ids behind what the handle's rows have cached (patch rows are not text)
+            self._check_handle(past_key_values, len(rows), "generate")
+            if (kwargs.get("num_beams") or 1) != 1:
+                raise NotImplementedError("num_beams > 1 with past_key_values is outside the hot path (beams fork their rows from a fresh prefill)")
+            if (kwargs.get("num_return_sequences") or 1) != 1:
+                raise NotImplementedError("num_return_sequences > 1 with past_key_values is outside the hot path (sample groups fork from a fresh prefill)")
+            if (repetition_penalty or 1.0) != 1.0 or (no_repeat_ngram_size or 0) > 0:
+                raise NotImplementedError("repetition_penalty / no_repeat_ngram_size with past_key_values are outside the hot path: the processors' id "
+                                          "history holds the prompt only, not the cached context")
+            if pixel_values is not None or frames_u8 is not None:
+                raise ValueError("generate(past_key_values=...) appends text ids to the cached rows: pass no pixel_values / frames_u8 with it")
+            cached = [n - past_key_values.n_patches for n in past_key_values.lengths]
+            if any(c < 0 or c >= len(r) for c, r in zip(cached, rows)):
+                raise ValueError(f"input_ids must be the full text sequence, longer than what the handle has cached ({cached} text ids per row)")
+            rows = [r[c:] for c, r in zip(cached, rows)]
+            cont = {"continue_from": past_key_values}
+        processing = self._processing_args(full_rows, repetition_penalty, no_repeat_ngram_size, min_new_tokens, min_length, **self._kw_rules(kwargs))
         beams = self._beam_args(kwargs.get("num_beams"), kwargs.get("num_return_sequences"), kwargs.get("length_penalty"),
                                 kwargs.get("early_stopping"), do_sample, processing, bool(return_dict_in_generate and output_scores))
         if want_top and beams is not None:
@@ -657,7 +769,7 @@ class EmmaXForActionPrediction:
         if len(rows) * N > MAX_DECODE_BATCH:
             raise ValueError(f"{len(rows)} prompts x {N} samples exceed the {MAX_DECODE_BATCH} rows of a decode batch")
         sampling = self._sampling_args(do_sample, temperature, top_k, top_p, seed, generator, **self._kw_warpers(kwargs))
-        max_new_tokens = self._max_new(rows, max_new_tokens, kwargs.get("max_length"), None)   # (min_length is in `processing`)
+        max_new_tokens = self._max_new(full_rows, max_new_tokens, kwargs.get("max_length"), None)   # (min_length is in `processing`)
         want_sc, want_lg = bool(return_dict_in_generate and output_scores), bool(return_dict_in_generate and output_logits)
         sc = lg = None
         K = beams.num_beams if beams is not None else N
@@ -667,8 +779,13 @@ class EmmaXForActionPrediction:
             sc = torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device) if want_sc else None
             lg = torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device) if want_lg else None
         res = self.generate_ids(rows, pixel_values, frames_u8, max_new_tokens, sampling=sampling, processing=processing, scores=sc,
-                                logits=lg, **self._beam_kw(beams), **self._sample_kw(N), **self._top_kw(n_top, watch), **cst)
+                                logits=lg, **self._beam_kw(beams), **self._sample_kw(N), **self._top_kw(n_top, watch), **cst, **cont)
         new_ids, lens = res[0], res[1]
+        kvh = None
+        if return_dict_in_generate and self.engine is not None:   # what the call left cached: the lengths are read back from the session
+            n_pat = past_key_values.n_patches if past_key_values is not None else self.config.n_patches
+            kvh = KVHandle(self.engine, self.engine.context_lengths(0, len(rows) * K), n_pat)
+        rows = full_rows
         if beams is not None:   # HF's layout: [B * num_return_sequences, P + T], best first per prompt
             R = beams.num_return_sequences
             keep = [g * K + k for g in range(len(rows)) for k in range(R)]
@@ -684,7 +801,8 @@ class EmmaXForActionPrediction:
             _, _, scores_d, bidx_d = self._need_engine().beam_result()
             Tl = int(torch.isfinite(lg).any(dim=2).any(dim=1).sum()) if want_lg else 0
             return EmmaXGenerateOutput(sequences=out, logits=tuple(lg[t] for t in range(Tl)) if want_lg else None,
-                                       sequences_scores=scores_d[:, :R].reshape(-1), beam_indices=bidx_d[:, :R, :T].reshape(len(keep), T))
+                                       sequences_scores=scores_d[:, :R].reshape(-1), beam_indices=bidx_d[:, :R, :T].reshape(len(keep), T),
+                                       past_key_values=kvh)
         new_ids, lens = new_ids.cpu(), lens.cpu().tolist()
         T = max(lens)
         P = max(len(r) for r in rows)
@@ -698,7 +816,7 @@ class EmmaXForActionPrediction:
         return EmmaXGenerateOutput(sequences=out, scores=tuple(sc[t] for t in range(T)) if want_sc else None,
                                    logits=tuple(lg[t] for t in range(T)) if want_lg else None,
                                    top_token_ids=top.top_ids[:, :T] if n_top else None, top_logprobs=top.top_logprobs[:, :T] if n_top else None,
-                                   watch_logprobs=top.watch_logprobs[:, :T] if watch else None)
+                                   watch_logprobs=top.watch_logprobs[:, :T] if watch else None, past_key_values=kvh)
 
     @staticmethod
     def _top_kw(n_top: int, watch) -> Dict[str, Any]:

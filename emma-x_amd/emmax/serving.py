@@ -8,7 +8,9 @@ slots keep decoding, so a long reasoning chain never holds short ones back.  Wit
 prefix of the full greedy generation, so the parsed action is unchanged.
 
 There is no shareable prompt prefix to cache across requests: the spliced sequence is [BOS] + 256 patch embeddings +
-text[1:] (modeling_prismatic.py:379-384), so everything after BOS depends on the frame.
+text[1:] (modeling_prismatic.py:379-384), so everything after BOS depends on the frame.  What CAN be kept is a request's own context: a
+request submitted with hold=True keeps its slot when it finishes, and a follow-up request on that context appends its ids to the cached rows
+(engine.slot_extend: no frame, no prefill) until the context is released.
 
 The scheduler is host logic only (testable without a GPU against a fake engine); all state it polls lives on the device.
 """
@@ -36,6 +38,10 @@ class Request:
     top_logprobs: int = 0    # N in 1..20: every emitted token comes with the N most likely ids and their log-probabilities (RAW logits); 0 = off
     watch_ids: Optional[Sequence[int]] = None   # ... and with the log-probabilities of these ids (up to 256).  One list per run: the requests
                                                 # that name a list name the same one
+    hold: bool = False       # keep the slot (its KV context) when the request finishes: Result.context names it for a follow-up; it counts
+                             # against n_slots until SlotScheduler.release(context)
+    follow_up: Any = None    # a Result.context: the request's prompt_ids are appended to that held context (frame = None; the finished answer's
+                             # last token is not cached -- pass it first to keep it) and decoding goes on in its slot.  Needs no free slot
     constraint_start: Any = None   # a state or entry name of the scheduler's automaton (SlotScheduler(automaton=...)): the request is decoded
                                    # under that constraint from there; None = unconstrained.  A sample group's samples all enter there
 
@@ -52,10 +58,18 @@ class Result:
     sample: int = 0   # which sample of its request this is (Request.num_samples > 1: one Result per sample)
     top_logprobs: Optional[List[List[tuple]]] = None   # Request.top_logprobs = N: per emitted token its N (id, logprob) pairs, best first
     watch_logprobs: Optional[List[List[float]]] = None   # Request.watch_ids: per emitted token the log-probabilities of those ids
+    context: Any = None   # Request.hold: the held context (opaque: slot + generation counter) for Request(follow_up=...) / SlotScheduler.release
 
     @property
     def latency_s(self) -> float:
         return self.t_done - self.t_submit
+
+
+@dataclass(frozen=True)
+class HeldContext:
+    """What Result.context holds: the slot a finished request kept and the generation counter that tells this hold from later ones of the slot."""
+    slot: int
+    generation: int
 
 
 @dataclass
@@ -124,6 +138,9 @@ class SlotScheduler:
         self._warpers = False                        # ... min_p / typical_p / epsilon_cutoff / eta_cutoff (run)
         self._rules = False                          # ... token rules (run)
         self._top = None                             # (N, watch list) bound for the current run, None when no request asks (run)
+        self.held: Dict[int, int] = {}               # slot -> generation of the context a finished hold=True request keeps there
+        self.followups: Deque[tuple] = deque()       # (request, t_submit) of follow-ups: admitted onto their context's slot, no free slot needed
+        self._generation = 0
         self.automaton = automaton
         self._constrained = False                    # some request of the current run names a constraint_start (run)
         # a staged batch is at most max(stage_batch, free slots) <= n_slots requests: the session needs that many staging rows
@@ -148,6 +165,8 @@ class SlotScheduler:
             raise ValueError(f"num_samples must be an integer >= 1, got {n!r}")
         if n > self.n_slots:
             raise ValueError(f"num_samples {n} exceeds the scheduler's {self.n_slots} slots: a group's samples are admitted together")
+        if getattr(req, "hold", False) and n > 1:
+            raise ValueError("hold=True keeps ONE context: a sample group (num_samples > 1) shares its prompt pages and is not held")
         if n > 1 and (req.sampling is None or float(req.sampling.temperature) == 0.0):
             raise ValueError(f"num_samples {n} needs sampling: {n} greedy samples of one prompt would be identical (set Request.sampling with a temperature > 0)")
         if getattr(req, "top_logprobs", 0) or getattr(req, "watch_ids", None) is not None:
@@ -158,7 +177,55 @@ class SlotScheduler:
             if self.automaton is None:
                 raise ValueError(f"request {req.rid!r} names a constraint_start, but the scheduler has no automaton (SlotScheduler(automaton=...))")
             self.automaton.start_state(req.constraint_start)   # (validates: a ValueError names the entries)
+        if getattr(req, "follow_up", None) is not None:
+            self._check_context(req.follow_up, f"request {req.rid!r}: follow_up")
+            if n > 1:
+                raise ValueError("a follow-up continues ONE context: num_samples > 1 is not served on a held slot")
+            if req.frame is not None:
+                raise ValueError("a follow-up appends text to a cached context: frame must be None")
+            if getattr(req, "processing", None) is not None and not req.processing.neutral:
+                raise NotImplementedError("logits processing with a follow-up is outside the hot path: the processors' id history holds a prompt, not the held context")
+            if any(r.follow_up == req.follow_up for r, _ in self.followups):
+                raise ValueError(f"request {req.rid!r}: another follow-up of this context is already queued")
+            self.followups.append((req, self.clock()))
+            return
         self.queue.append((req, self.clock()))
+
+    def _check_context(self, ctx, what: str) -> None:
+        if not isinstance(ctx, HeldContext) or self.held.get(ctx.slot) != ctx.generation:
+            raise ValueError(f"{what} names a released or unknown context (a Result.context of a hold=True request of this scheduler, not yet released)")
+
+    def release(self, context) -> None:
+        """Free the slot a hold=True request kept: its context is gone and the slot serves queued requests again."""
+        self._check_context(context, "release")
+        if any(r.follow_up == context for r, _ in self.followups):
+            raise ValueError("a follow-up of this context is still queued")
+        self.engine.slot_release(context.slot)
+        del self.held[context.slot]
+
+    def _free(self) -> List[int]:
+        return [s for s in range(self.n_slots) if s not in self.active and s not in self.held]
+
+    def _admit_followups(self) -> int:
+        """Every queued follow-up goes onto its context's slot, between two decode steps: the new ids are appended to the cached rows and the
+        slot decodes again.  The other slots are untouched."""
+        n = 0
+        while self.followups:
+            req, t_sub = self.followups.popleft()
+            slot = req.follow_up.slot
+            self._set_constraint([req], row0=slot)
+            self._set_sampling([req], row0=slot)
+            try:
+                self.engine.slot_extend(slot, list(req.prompt_ids), req.max_new_tokens)
+            except Exception:
+                # refused (the context has no room for the ids and the budget, say): the request is queued again, its context stays held, and the
+                # error reaches the caller, who drops the request (followups.popleft) or releases the context
+                self.followups.appendleft((req, t_sub))
+                raise
+            del self.held[slot]   # active again: its hold (if any) begins anew when it finishes
+            self.active[slot] = _Active(req, t_sub, self.clock())
+            n += 1
+        return n
 
     def _sampling_rows(self, reqs):
         """(params, seeds, subseqs) of requests about to be prefilled: greedy ones at temperature 0, each request with its own seed and subseq 0."""
@@ -243,7 +310,7 @@ class SlotScheduler:
             self.active[slot] = _Active(req, t_sub, t_adm, j)
 
     def _admit(self) -> int:
-        free = [s for s in range(self.n_slots) if s not in self.active]
+        free = self._free()
         mine = self._fit((r for r, _ in self.queue), free)   # sample 0 is prefilled into a request's first slot, the others are forked from it
         take = len(mine)
         if take == 0:
@@ -295,7 +362,7 @@ class SlotScheduler:
         ahead of need, whether or not a slot is free; returns at once (nothing is awaited)."""
         if self._pending is not None or not self.queue:
             return False
-        free = sum(1 for s in range(self.n_slots) if s not in self.active)
+        free = len(self._free())
         take = min(len(self.queue), max(self.stage_batch, free))
         batch = [self.queue.popleft() for _ in range(take)]
         try:
@@ -322,7 +389,7 @@ class SlotScheduler:
         if self._pending is None:
             return 0
         staged, batch, k0 = self._pending
-        free = [s for s in range(self.n_slots) if s not in self.active]
+        free = self._free()
         # the longest in-order prefix of what is still staged whose slots are free now (a group is one staged row and num_samples slots)
         mine = self._fit((r for r, _ in batch[k0:]), free)
         take = len(mine)
@@ -362,20 +429,30 @@ class SlotScheduler:
                         top = [[(int(i), float(v)) for i, v in zip(ri[:n_top], rv[:n_top])] for ri, rv in zip(t_ids, t_lps)]
                     if ask_watch:
                         watch = [[float(v) for v in row] for row in w_lps]
-                self.engine.slot_release(slot)
-                self.results.append(Result(a.req.rid, ids, slot, a.t_submit, a.t_admit, self.clock(), lps, a.sample, top, watch))
+                ctx = None
+                if getattr(a.req, "hold", False):   # the slot stays the request's: a follow-up continues its context
+                    self._generation += 1
+                    self.held[slot] = self._generation
+                    ctx = HeldContext(slot, self._generation)
+                else:
+                    self.engine.slot_release(slot)
+                self.results.append(Result(a.req.rid, ids, slot, a.t_submit, a.t_admit, self.clock(), lps, a.sample, top, watch, ctx))
                 n += 1
         return n
 
     def run(self) -> List[Result]:
         """Serve until the queue is empty and every slot is idle.  Returns the results in completion order.  When some queued request
         samples, the session samples for the whole run (greedy requests at temperature 0: their greedy ids) and is greedy again after it.  Logits processing likewise (requests without it get neutral processors)."""
-        self._sampling = any(r.sampling is not None for r, _ in self.queue)
+        everyone = list(self.queue) + list(self.followups)
+        self._sampling = any(r.sampling is not None for r, _ in everyone)
         self._processing = any(getattr(r, "processing", None) is not None for r, _ in self.queue)
-        self._warpers = any(r.sampling is not None and getattr(r.sampling, "has_warpers", False) for r, _ in self.queue)
+        if self._processing and self.followups:
+            raise NotImplementedError("a run with follow-ups serves no logits processing: the session's processors read an id history that holds "
+                                      "prompts only (serve the follow-ups in a run of their own)")
+        self._warpers = any(r.sampling is not None and getattr(r.sampling, "has_warpers", False) for r, _ in everyone)
         with_rules = [r.processing for r, _ in self.queue if getattr(r, "processing", None) is not None and getattr(r.processing, "rule_enable", 0)]
         self._rules = bool(with_rules)
-        self._constrained = any(getattr(r, "constraint_start", None) is not None for r, _ in self.queue)
+        self._constrained = any(getattr(r, "constraint_start", None) is not None for r, _ in everyone)
         self._top = self._top_of_run()
         if self._top is not None:
             self._sampling = True   # the binding reads the logit rows a sampling session writes: greedy requests at temperature 0
@@ -385,7 +462,7 @@ class SlotScheduler:
 
                 greedy = SamplingParams(temperature=0.0, top_k=0, top_p=1.0, seed=0)
                 self.engine.set_sampling([greedy] * self.n_slots, [0] * self.n_slots, [0] * self.n_slots, row0=0)
-                self.engine.set_top_logprobs(self._top[0], self._top[1], max(int(r.max_new_tokens) for r, _ in self.queue))
+                self.engine.set_top_logprobs(self._top[0], self._top[1], max(int(r.max_new_tokens) for r, _ in everyone))
             if self._rules:   # one rule table for the run (the requests that name a kind name the same rules); every row starts opted out
                 self.engine.set_token_rules(with_rules, enables=False)
                 self.engine.set_rule_enables([0] * self.n_slots)
@@ -410,7 +487,7 @@ class SlotScheduler:
         one watch list the requests name -- two different lists are a ValueError, as two rule tables are.  None: no request asks, and the
         run calls no engine method it did not call before."""
         n, watch = 0, None
-        for r, _ in self.queue:
+        for r, _ in list(self.queue) + list(self.followups):
             n = max(n, int(getattr(r, "top_logprobs", 0) or 0))
             w = getattr(r, "watch_ids", None)
             if w is not None:
@@ -422,24 +499,36 @@ class SlotScheduler:
 
     def _run(self) -> List[Result]:
         if self.overlap:
-            while self.queue or self.active or self._pending is not None:
+            while self.queue or self.active or self._pending is not None or self.followups:
+                self._admit_followups()
                 self._start_admission()
                 if self._join_admission(wait=not self.active):   # (idle decode batch: the admission is all there is to wait for)
                     self._start_admission()                       # staging rows free again: the next batch goes out at once
                 if not self.active:
+                    self._check_not_stuck()
                     continue
                 self.engine.slots_step(self.poll_every)
                 self.steps += self.poll_every
                 self._retire()
             return self.results
-        while self.queue or self.active:
+        while self.queue or self.active or self.followups:
+            self._admit_followups()
             self._admit()
             if not self.active:
+                self._check_not_stuck()
                 continue
             self.engine.slots_step(self.poll_every)
             self.steps += self.poll_every
             self._retire()
         return self.results
+
+
+    def _check_not_stuck(self) -> None:
+        """Nothing decodes: requests that wait while every slot they could take is HELD would wait for ever."""
+        waiting = [r for r, _ in self.queue] + ([r for r, _ in self._pending[1][self._pending[2]:]] if self._pending is not None else [])
+        if waiting and len(self._free()) < self._demand(waiting[0]):
+            raise RuntimeError(f"{len(waiting)} requests wait but {len(self.held)} of the {self.n_slots} slots are held and none decodes: "
+                               "release a held context (SlotScheduler.release) or serve with more slots")
 
 
 def serve_static(engine_generate: Callable[[List[Request]], List[List[int]]], requests: Sequence[Request], batch: int) -> List[List[int]]:

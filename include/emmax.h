@@ -46,7 +46,9 @@ extern "C" {
  *   emmax_op_rope_kv_write, emmax_op_kv_quant_rows, emmax_op_embed_splice, emmax_op_gather_last_rows): new symbols only; still 12: MXFP4 at 17-64 rows
  *   (tuning switch mx4_wide, emmax_model_mxfp4_wide, emmax_op_gemm_wide_mxfp4): new symbols only; still 12: top-N and watched-token
  *   log-probabilities (emmax_op_top_logprobs, emmax_session_set_top_logprobs and the calls around it): new symbols only, the workspace grew
- *   their six device words and the watch list (1.3 KB). */
+ *   their six device words and the watch list (1.3 KB); still 12: extending a cached context (emmax_extend, emmax_slot_extend,
+ *   emmax_session_context, emmax_op_extend_attention(_kv8), emmax_op_rope_kv_write_at, emmax_extend_attn_plan): new symbols only, the workspace
+ *   grew one int32 per decode row. */
 #define EMMAX_ABI_VERSION 12
 
 typedef enum emmax_status {
@@ -266,6 +268,33 @@ int emmax_slots_state(emmax_session* s, int32_t* done_dev, int32_t* n_out_dev, e
 int emmax_slot_output(emmax_session* s, int slot, int32_t* ids_dev, int n, emmax_stream stream);
 /* Mark `slot` idle again (empty context: its share of a batched step then reads no K/V). */
 int emmax_slot_release(emmax_session* s, int slot, emmax_stream stream);
+
+/* ---- extending a cached context (still ABI 12: new symbols only) -------------------------------------------------------
+ * A prefill starts a row at position 0 and a decode step appends one token.  These calls append MANY tokens to what a row has cached -- a follow-up
+ * turn, a teacher-forced continuation, the second chunk of a long prompt -- at the price of one pass over the new rows alone: the prefill's
+ * pipeline on the packed new rows, whose attention reads the cached prefix and the new rows from the paged cache (bf16 or fp8).
+ *   emmax_extend           rows row0 .. row0 + B - 1 of the live batch (after a prefill and any number of steps) each get lens_host[b] >= 1 ids
+ *                          appended at their cached length: ids_dev int32 [B][P_max] (row b: lens_host[b] ids).  A row's pending token -- picked,
+ *                          not yet cached -- is discarded: a caller who wants it passes it as the first id.  Afterwards the rows are as a prefill
+ *                          leaves them: first token of the continuation picked (greedy, or the session's sampling / warpers / token rules /
+ *                          automaton: a row keeps its automaton state, a row outside the automaton -- state -1 -- enters at its start state), context += lens, done / n_out / stop match / token budget reset,
+ *                          output row empty; emmax_prefill_logits returns the logits of the new rows [sum_b lens[b], vocab].  max_new (>= 0): the
+ *                          tokens the caller will generate next, for the capacity check only.  The rows' lengths are read back (the call
+ *                          synchronises the stream and is not capturable); later steps and graph replays need nothing new.
+ *   emmax_slot_extend      the same for ONE request slot whose request has finished (done, not released), between two steps on the serving
+ *                          stream, with its token budget: a follow-up turn on the kept context.  The other slots are untouched.  Like
+ *                          emmax_slot_prefill it runs in the session's prefill scratch, which emmax_slots_prefill_staged uses on its own stream:
+ *                          no staged prefill may be in flight when it is called (wait for it, or commit it, first).
+ *   emmax_session_context  the cached lengths of rows row0 .. row0 + n - 1, read back to the host (synchronises the stream).
+ * EMMAX_ERR_STATE: exact-numerics sessions; beams on; sample groups on, or a slot inside a fork group; history-reading processors on (the
+ * [rows][max_prompt] id history has no room for the extension); no prefill yet; a slot that still decodes or holds nothing.  EMMAX_ERR_NOMEM:
+ * context + lens + max(max_new, 1) beyond max_ctx (= the row's pages); more packed rows than the prefill holds.  A refused call changes nothing.
+ * The automaton (emmax_session_set_automaton) while it is set: a row inside it keeps its state across the extension; a row OUTSIDE it -- state -1:
+ * one that never entered, and equally one that an earlier constrained generation left through a transition to -1 -- enters at its start state
+ * again (a start state of -1 leaves it unconstrained).  A caller who wants such a row to stay outside sets its start to -1 first. */
+int emmax_extend(emmax_session* s, int row0, int B, const int32_t* ids_dev, const int32_t* lens_host, int P_max, int max_new, emmax_stream stream);
+int emmax_slot_extend(emmax_session* s, int slot, const int32_t* ids_dev, int len, int max_new, emmax_stream stream);
+int emmax_session_context(emmax_session* s, int row0, int n, int32_t* ctx_out_host, emmax_stream stream);
 
 /* ---- seeded sampling over rows of logits (ABI 6) --------------------------------------------------------------------
  * emmax_op_sample draws one token per row of logits_dev [B][ld] (fp32, V <= 32768 entries, ld >= V) and returns it with its
@@ -712,6 +741,30 @@ int emmax_op_decode_attention_group_kv8(const void* q_dev, void* kcache8_dev, vo
 int emmax_decode_attn_plan(int B, int Hq, int Hkv, int nsplit, int direct, int kv8, int* G_out, int* nw_out, int* direct_out, int* deep_out,
                            int* nsplit_out);
 int emmax_group_attn_plan(int B, int N, int Hq, int Hkv, int kv8, int* span_width_out, int* span_nsplit_out, int* span_chunks_out, int* tail_G_out);
+/* Extension attention (extend_attn.hip): causal attention of n new query rows per sequence over the paged cache.  q_dev bf16 packed rows
+ * [total_rows, ldq] (head h at q_off + 128 h, already rotated); sequence b owns rows cu[b] .. cu[b + 1] and its row i sits at position base[b] + i
+ * and sees keys 0 .. base[b] + i, ALL read from the cache (kcache / vcache bf16 [pages][Hkv][64][128], or e4m3 bytes + kscale / vscale fp32
+ * [pages][Hkv][64]) through page_table int32 [B][max_pages]: the new rows' K / V must have been appended (emmax_op_rope_kv_write_at).  out bf16
+ * [total_rows, ld_out].  cu_dev [B + 1] / base_dev [B] are device arrays; the op reads them back and checks them first (it synchronises).  nsplit:
+ * 1..16 key splits (kps = ceil((base + n) / nsplit) rounded up to 16; empty splits allowed), 0 = the planner's choice, returned in nsplit_out
+ * (may be NULL); more than one split needs ws_dev, f32 [total_rows][Hq][nsplit][132].  head_dim 128, page 64, GQA group in {1, 2, 4, 8}, B <= 64.
+ * emmax_op_rope_kv_write_at: emmax_op_rope_kv_write with row i of sequence b at position base[b] + i (cos / sin of max_pos rows); the 16-byte kernel
+ * only (head_dim % 16 == 0, 16-byte aligned tables), bit-identical to emmax_op_rope_kv_write at the same positions.
+ * emmax_extend_attn_plan: HOST ONLY -- what the launch dispatches on for B sequences of at most max_n new rows and at most max_L keys: the GQA
+ * group, tokens per block (128 / G), query tiles per sequence, the split count (asked, or for nsplit = 0 the planner's: one split once
+ * B x Hkv x query tiles fill the chip's 256 CUs, else up to one per page and 16) and whether the split form (partials + merge pass) runs. */
+int emmax_op_extend_attention(const void* q_dev, int ldq, int q_off, const void* kcache_dev, const void* vcache_dev, const int32_t* page_table_dev,
+                              const int32_t* cu_dev, const int32_t* base_dev, int B, int total_rows, int Hq, int Hkv, int page, int max_pages, int nsplit,
+                              float scale, void* out_dev, int ld_out, float* ws_dev, long long ws_floats, int* nsplit_out, emmax_stream stream);
+int emmax_op_extend_attention_kv8(const void* q_dev, int ldq, int q_off, const void* kcache8_dev, const void* vcache8_dev, const float* kscale_dev,
+                                  const float* vscale_dev, const int32_t* page_table_dev, const int32_t* cu_dev, const int32_t* base_dev, int B,
+                                  int total_rows, int Hq, int Hkv, int page, int max_pages, int nsplit, float scale, void* out_dev, int ld_out,
+                                  float* ws_dev, long long ws_floats, int* nsplit_out, emmax_stream stream);
+int emmax_op_rope_kv_write_at(void* qkv_dev, int ld, int q_off, int k_off, int v_off, const int32_t* cu_dev, const int32_t* base_dev, int B, int total_rows,
+                              const float* cos_dev, const float* sin_dev, int max_pos, void* kcache_dev, void* vcache_dev, const int32_t* page_table_dev,
+                              int max_pages, int Hq, int Hkv, int head_dim, int page, emmax_stream stream);
+int emmax_extend_attn_plan(int B, int max_n, int max_L, int Hq, int Hkv, int nsplit, int kv8, int* G_out, int* tokens_per_block_out, int* query_tiles_out,
+                           int* nsplit_out, int* split_form_out);
 /* Decode-path weight-streaming GEMV: y[b,n] = sum_k x[b,k] W[n,k]  (bf16 in, fp32 accumulate, bf16 out), B <= 8. */
 int emmax_op_gemv(const void* x_dev, const void* W_dev, void* y_dev, int B, int N, int K, emmax_stream stream);
 
