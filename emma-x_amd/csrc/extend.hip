@@ -44,6 +44,8 @@ int run_extend(emmax_session* s, int r0, int B, const int32_t* ids, const int32_
         max_L = std::max(max_L, ctx[b] + lens[b]);
     }
     if (total > s->max_rows) return fail(EMMAX_ERR_NOMEM, "%s: %d packed new rows exceed the prefill capacity %d", who, total, s->max_rows);
+    if (int r = tap_pass_check(s, max_L, who)) return r;
+    if (!slot) taps_unbind(s, false, true);   // step taps were bound for the rows as the last pass left them
     // the key-split workspace is the split-K scratch (idle between two GEMMs): fewer splits if the partials would not fit
     ExtendAttnPlan plan;
     if (!extend_attn_plan(B, max_n, max_L, c.n_heads, c.n_kv_heads, 0, s->kv8 ? 1 : 0, &plan) || c.head_dim != 128)
@@ -68,6 +70,7 @@ int run_extend(emmax_session* s, int r0, int B, const int32_t* ids, const int32_
     const bool p32 = emmax_tune().resid32 == 1;
     s->p32 = p32;
     KCHK(launch_embed_splice(ids, P_max, s->cu, m->embed, nullptr, s->ph, B, max_n, 0, m->H, m->vocab, st, p32 ? s->ph32 : nullptr));
+    if (int r = tap_pass_hidden(s, 0, total, st)) return r;
     if (int r = run_prefill_layers(s, B, total, max_n, r0, &plan, st)) return r;   // the prefill's layers, their attention over the paged cache
     // the first token of the continuation, as a prefill picks it (greedy, or the session's sampling / warpers / rules / automaton -- a row keeps
     // its automaton state, one outside the automaton entered at its start state above)

@@ -153,6 +153,7 @@ int emmax_slots_open(emmax_session* s, int n_slots, emmax_stream stream) {
     std::fill(s->slot_stg_idx.begin(), s->slot_stg_idx.end(), -1);
     s->slots_open = true;
     s->scores.on = false;   // no scores in slot serving (the bound buffers were a generate call's)
+    taps_unbind(s, true, true);   // ... and no taps
     s->prefilled = true;   // decode steps are legal: idle slots are rows that are already done
     return sc.leave();
 }

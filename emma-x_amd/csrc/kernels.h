@@ -414,6 +414,37 @@ int launch_kv_quant_rows_at(const void* qkv, int ld, int k_off, int v_off, const
                             void* v8, float* kscale, float* vscale, const int32_t* page_table, int max_pages, int Hkv, int hd, int page,
                             hipStream_t stream);
 
+// ---- taps.hip: what a session hands out of a pass it runs anyway ----
+// rows x H of the residual stream (fp32 rows, or bf16 rows: src_f32 = 0) into fp32 [rows][H]; norm_w != nullptr: the RMSNorm of each row, fp32 throughout.
+// gather (may be null): the source row of row r is gather[r], clamped to gather_rows (a step's embedding rows, read by token id).
+// gen_idx (may be null; a decode step): row r lands gen_idx[r] x gen_stride floats further on -- nothing where done[r] != 0 or the index is outside 0 .. max_new - 1
+struct TapRowsParams {
+    const void* src;
+    float* dst;
+    const void* norm_w;
+    const int32_t *gather, *gen_idx, *done;
+    long long gen_stride;
+    int src_f32, ld_src, rows, H, gather_rows, max_new;
+    float eps;
+};
+int launch_tap_rows(const TapRowsParams& p, hipStream_t stream);
+// fp32 softmax(scale q . K^T) of the new query rows over the paged cache: ExtendAttnParams' q / K / tables (base == nullptr: every sequence at 0)
+struct AttnProbsParams {
+    const void* q;               // bf16 packed rows [total, ldq], head h of a row at q_off + h * 128 (already rotated)
+    const void* kcache;          // bf16 [pages][Hkv][64][128], or e4m3 bytes with kscale fp32 [pages][Hkv][64]
+    const float* kscale;
+    const int32_t* page_table;   // [B][max_pages]
+    const int32_t* cu;           // [B + 1], or nullptr: one new row per sequence, packed row b (a decode step)
+    const int32_t* base;         // [B] or nullptr
+    float* probs;                // f32 [total][Hq][ld_keys]: keys 0 .. base + i of row i, zeros behind them
+    const int32_t *gen_idx, *done;   // a decode step (both or neither): sequence b's rows land gen_idx[b] x gen_stride floats further on; nothing where
+    long long gen_stride;            // done[b] != 0 or the index is outside 0 .. max_new - 1
+    int ldq, q_off, B, Hq, Hkv, max_pages, ld_keys, max_new;
+    float scale;
+};
+// max_n: an upper bound of the new rows of any sequence (the grid); page = 64, head_dim = 128, GQA group in {1, 2, 4, 8}, ld_keys % 4 == 0
+int launch_attn_probs(const AttnProbsParams& p, int max_n, int kv8, hipStream_t stream);
+
 // ---- decode.hip: the greedy finish of a step ----
 struct FinishParams {
     const float* part_val;

@@ -445,6 +445,177 @@ int emmax_session_clear_top_logprobs(emmax_session* s, emmax_stream) {
 
 int emmax_session_top_logprobs(const emmax_session* s) { return s ? (s->toplp.on ? 1 : 0) : -1; }
 
+// ---- taps: hidden states and attention maps out of the passes the session runs anyway (new symbols, same ABI; taps.hip) -----------------
+static int tap_sel(uint64_t mask, int bit) { return __builtin_popcountll(mask & ((1ull << bit) - 1)); }   // the entry's place among the selected, lowest first
+
+static int taps_args(const emmax_session* s, const char* who, const float* hidden, uint64_t hl, const float* attn, uint64_t al, int ld_keys) {
+    const auto& c = s->m->cfg;
+    const int nl = c.n_layers;
+    if (nl > 62) return fail(EMMAX_ERR_INVALID, "%s: the layer masks hold up to 62 layers (%d)", who, nl);
+    if ((hidden != nullptr) != (hl != 0) || (attn != nullptr) != (al != 0))
+        return fail(EMMAX_ERR_INVALID, "%s: a buffer and its layer mask go together (hidden %s, mask %llx; attentions %s, mask %llx)", who, hidden ? "set" : "null",
+                    (unsigned long long)hl, attn ? "set" : "null", (unsigned long long)al);
+    if (hl >> (nl + 1)) return fail(EMMAX_ERR_INVALID, "%s: hidden_layers %llx names an entry above %d (bit i = hidden_states[i], bit %d the normed last)", who, (unsigned long long)hl, nl, nl);
+    if (al >> nl) return fail(EMMAX_ERR_INVALID, "%s: attn_layers %llx names a layer above %d", who, (unsigned long long)al, nl - 1);
+    if ((((uintptr_t)hidden | (uintptr_t)attn) & 15)) return fail(EMMAX_ERR_INVALID, "%s: the buffers are 16-byte aligned", who);
+    if (attn) {
+        if (ld_keys < 4 || ld_keys % 4) return fail(EMMAX_ERR_INVALID, "%s: ld_keys %d is not a positive multiple of 4 (16-byte stores)", who, ld_keys);
+        const int G = c.n_kv_heads > 0 ? c.n_heads / c.n_kv_heads : 0;
+        if (c.head_dim != 128 || c.n_heads % c.n_kv_heads || (G != 1 && G != 2 && G != 4 && G != 8))
+            return fail(EMMAX_ERR_INVALID, "%s: the probability kernel takes head_dim 128 and GQA groups of 1 / 2 / 4 / 8 (heads %d / %d, head_dim %d)", who, c.n_heads,
+                        c.n_kv_heads, c.head_dim);
+    }
+    if (s->exact) return fail(EMMAX_ERR_STATE, "%s: exact-numerics sessions serve no taps (their fp32 / 24-bit cache has no probability kernel)", who);
+    if (s->beam.K) return fail(EMMAX_ERR_STATE, "%s: not served while beams are on (emmax_session_clear_beams)", who);
+    if (s->grp_N) return fail(EMMAX_ERR_STATE, "%s: not served while sample groups are on (emmax_session_clear_sample_groups)", who);
+    if (s->slots_open) return fail(EMMAX_ERR_STATE, "%s: not served while request slots are open", who);
+    return 0;
+}
+
+int emmax_session_set_pass_taps(emmax_session* s, float* hidden_dev, uint64_t hidden_layers, float* attn_dev, uint64_t attn_layers, int ld_keys, emmax_stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!hidden_dev && !attn_dev && !hidden_layers && !attn_layers) {
+        taps_unbind(s, true, false);
+        return 0;
+    }
+    if (int r = taps_args(s, "emmax_session_set_pass_taps", hidden_dev, hidden_layers, attn_dev, attn_layers, ld_keys)) return r;
+    s->taps.pass.on = true;
+    s->taps.pass.hidden = hidden_dev; s->taps.pass.hl = hidden_layers; s->taps.pass.attn = attn_dev; s->taps.pass.al = attn_layers;
+    s->taps.pass.ld = attn_dev ? ld_keys : 0;
+    return 0;
+}
+
+int emmax_session_set_step_taps(emmax_session* s, float* hidden_dev, uint64_t hidden_layers, float* attn_dev, uint64_t attn_layers, int ld_keys, int max_new,
+                                emmax_stream stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!hidden_dev && !attn_dev && !hidden_layers && !attn_layers) {
+        taps_unbind(s, false, true);
+        return 0;
+    }
+    const char* who = "emmax_session_set_step_taps";
+    if (int r = taps_args(s, who, hidden_dev, hidden_layers, attn_dev, attn_layers, ld_keys)) return r;
+    if (max_new < 1 || max_new > s->max_ctx) return fail(EMMAX_ERR_INVALID, "%s: max_new %d outside 1..max_ctx = %d", who, max_new, s->max_ctx);
+    if (!s->prefilled) return fail(EMMAX_ERR_STATE, "%s: no prefill yet: the buffers' batch is that of the live rows", who);
+    if (attn_dev) {   // the lengths are known here (read back once: a binding is not part of a captured step): a row sees one key more per step,
+                      // max(1, max_new - 1) steps to come
+        int32_t ctx[EMMAX_MAX_DECODE_BATCH];
+        const int B = std::min(s->cur_B, (int)EMMAX_MAX_DECODE_BATCH);
+        StreamScope sc(s, stream);
+        if (sc.error()) return sc.error();
+        HIPCHK(hipMemcpyAsync(ctx, s->ctx_len, (size_t)B * 4, hipMemcpyDeviceToHost, sc.stream()));
+        HIPCHK(hipStreamSynchronize(sc.stream()));
+        if (int r = sc.leave()) return r;
+        int longest = 0;
+        for (int b = 0; b < B; ++b) longest = std::max(longest, ctx[b]);
+        const int need = longest + std::max(1, max_new - 1);
+        if (ld_keys < need) return fail(EMMAX_ERR_INVALID, "%s: ld_keys %d is smaller than the %d keys a row can see (context %d + the steps to come)", who, ld_keys, need, longest);
+    }
+    s->taps.step.on = true;
+    s->taps.step.hidden = hidden_dev; s->taps.step.hl = hidden_layers; s->taps.step.attn = attn_dev; s->taps.step.al = attn_layers;
+    s->taps.step.ld = attn_dev ? ld_keys : 0;
+    s->taps.step_max_new = max_new; s->taps.step_B = s->cur_B;
+    s->taps.serial += 1;
+    return 0;
+}
+
+int emmax_session_clear_taps(emmax_session* s, emmax_stream) {
+    if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
+    taps_unbind(s, true, true);
+    return 0;
+}
+
+int emmax_session_taps(const emmax_session* s) { return s ? ((s->taps.pass.on ? 1 : 0) | (s->taps.step.on ? 2 : 0)) : -1; }
+
+}  // extern "C"
+
+int tap_pass_check(emmax_session* s, int max_keys, const char* who) {
+    if (s->taps.pass.on && s->taps.pass.attn && s->taps.pass.ld < max_keys)
+        return fail(EMMAX_ERR_INVALID, "%s: the bound attention tap's ld_keys %d is smaller than the %d keys a row of this pass sees (emmax_session_set_pass_taps)", who,
+                    s->taps.pass.ld, max_keys);
+    return 0;
+}
+
+// the stream's rows as the pass / the step holds them now: fp32 where the stream is fp32, else the bf16 rows
+static void tap_stream_src(TapRowsParams& p, const float* h32, const bf16* h16, int H) {
+    p.src = h32 ? (const void*)h32 : (const void*)h16;
+    p.src_f32 = h32 ? 1 : 0;
+    p.ld_src = H;
+}
+
+int tap_pass_hidden(emmax_session* s, int idx, int total, hipStream_t st) {
+    const TapSet& t = s->taps.pass;
+    if (!t.on || !t.hidden || !((t.hl >> idx) & 1)) return 0;
+    emmax_model* m = s->m;
+    TapRowsParams p;
+    memset(&p, 0, sizeof(p));
+    tap_stream_src(p, s->p32 ? s->ph32 : nullptr, s->ph, m->H);
+    p.dst = t.hidden + (size_t)tap_sel(t.hl, idx) * total * m->H;
+    p.rows = total; p.H = m->H; p.eps = m->cfg.rms_eps;
+    if (idx == m->cfg.n_layers) p.norm_w = m->final_norm;
+    KCHK(launch_tap_rows(p, st));
+    return 0;
+}
+
+int tap_pass_attn(emmax_session* s, int li, int B, int total, int max_n, int r0, bool ext, hipStream_t st) {
+    const TapSet& t = s->taps.pass;
+    if (!t.on || !t.attn || !((t.al >> li) & 1)) return 0;
+    emmax_model* m = s->m;
+    const auto& c = m->cfg;
+    AttnProbsParams a;
+    memset(&a, 0, sizeof(a));
+    a.q = s->pqkv; a.ldq = m->qkv_dim; a.q_off = 0; a.kcache = kcache_of(s, li);
+    if (s->kv8) a.kscale = kscale_of(s, li);
+    a.page_table = s->page_table + (size_t)r0 * s->max_pages; a.cu = s->cu; a.base = ext ? s->ext_base : nullptr;
+    a.probs = t.attn + (size_t)tap_sel(t.al, li) * total * c.n_heads * t.ld;
+    a.ld_keys = t.ld; a.B = B; a.Hq = c.n_heads; a.Hkv = c.n_kv_heads; a.max_pages = s->max_pages; a.scale = 1.0f / sqrtf((float)c.head_dim);
+    KCHK(launch_attn_probs(a, max_n, s->kv8 ? 1 : 0, st));
+    return 0;
+}
+
+// A decode step's taps.  At every launch of the step before its finish, ctx_len[b] is the row's cached length BEFORE the step = the position of the
+// step's token: the qkv epilogue rotates at it and writes K / V there (fp8 cache: into kv_stage, appended by the attention launch), the attention
+// covers ctx_len + 1 keys, and only the finish advances it.  So the step's map is the probability kernel at base = ctx_len, one new row
+// per sequence, behind the attention launch.  n_out[b] is the index of the token the step is about to emit: the row's slot
+int tap_step_hidden(emmax_session* s, int idx, int B, hipStream_t st) {
+    const TapSet& t = s->taps.step;
+    if (!t.on || !t.hidden || !((t.hl >> idx) & 1) || B != s->taps.step_B) return 0;
+    emmax_model* m = s->m;
+    const int n_sel = __builtin_popcountll(t.hl);
+    TapRowsParams p;
+    memset(&p, 0, sizeof(p));
+    if (idx == 0) {   // behind the embed: the token's row of the table itself (a step of 1-2 rows folds the gather into layer 0's qkv launch)
+        p.src = m->embed; p.src_f32 = 0; p.ld_src = m->H; p.gather = s->cur_tok; p.gather_rows = m->vocab;
+    } else {
+        tap_stream_src(p, h32_of(s), s->dh, m->H);
+    }
+    p.dst = t.hidden + (size_t)tap_sel(t.hl, idx) * B * m->H;
+    p.rows = B; p.H = m->H; p.eps = m->cfg.rms_eps;
+    p.gen_idx = s->n_out; p.done = s->done; p.gen_stride = (long long)n_sel * B * m->H; p.max_new = s->taps.step_max_new;
+    if (idx == m->cfg.n_layers) p.norm_w = m->final_norm;
+    KCHK(launch_tap_rows(p, st));
+    return 0;
+}
+
+int tap_step_attn(emmax_session* s, int li, int B, hipStream_t st) {
+    const TapSet& t = s->taps.step;
+    if (!t.on || !t.attn || !((t.al >> li) & 1) || B != s->taps.step_B) return 0;
+    emmax_model* m = s->m;
+    const auto& c = m->cfg;
+    const int n_sel = __builtin_popcountll(t.al);
+    AttnProbsParams a;
+    memset(&a, 0, sizeof(a));
+    a.q = s->dq; a.ldq = m->q_dim; a.q_off = 0; a.kcache = kcache_of(s, li);
+    if (s->kv8) a.kscale = kscale_of(s, li);
+    a.page_table = s->page_table; a.cu = nullptr; a.base = s->ctx_len;
+    a.probs = t.attn + (size_t)tap_sel(t.al, li) * B * c.n_heads * t.ld;
+    a.gen_idx = s->n_out; a.done = s->done; a.gen_stride = (long long)n_sel * B * c.n_heads * t.ld; a.max_new = s->taps.step_max_new;
+    a.ld_keys = t.ld; a.B = B; a.Hq = c.n_heads; a.Hkv = c.n_kv_heads; a.max_pages = s->max_pages; a.scale = 1.0f / sqrtf((float)c.head_dim);
+    KCHK(launch_attn_probs(a, 1, s->kv8 ? 1 : 0, st));
+    return 0;
+}
+
+extern "C" {
+
 // ---- beam search in the decode step (ABI 9) ---------------------------------------------------------------------------
 int emmax_session_set_beams(emmax_session* s, int num_beams, double length_penalty, int early_stopping, emmax_stream stream) {
     if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
@@ -468,6 +639,7 @@ int emmax_session_set_beams(emmax_session* s, int num_beams, double length_penal
     for (size_t n = 0; n < pw.size(); ++n) pw[n] = (float)pow((double)n, length_penalty);
     HIPCHK(hipStreamSynchronize(sc.stream()));
     HIPCHK(hipMemcpy(s->beam.pw, pw.data(), pw.size() * 4, hipMemcpyHostToDevice));
+    taps_unbind(s, true, true);   // no taps with beams
     s->beam.K = num_beams; s->beam.es = early_stopping; s->beam.lp_pos = length_penalty > 0.0 ? 1 : 0;
     s->beam.G = 0; s->beam.forked = false; s->beam.ready = false;
     s->prefilled = false;   // rows of an earlier batch do not continue as beams
@@ -515,6 +687,7 @@ int emmax_session_set_sample_groups(emmax_session* s, int n, emmax_stream stream
         if (int r = slots_restore_pages(s, sc.stream())) return r;
         if (int r = sc.leave()) return r;
     }
+    taps_unbind(s, true, true);   // no taps with sample groups
     s->grp_N = n;
     s->prefilled = false;   // rows of an earlier batch do not continue as groups
     return 0;

@@ -366,6 +366,56 @@ int emmax_op_extend_attention_kv8(const void* q, int ldq, int q_off, const void*
     a.page_table = page_table; a.cu = cu; a.base = base; a.part = ws; a.B = B; a.Hq = Hq; a.Hkv = Hkv; a.max_pages = max_pages; a.scale = scale;
     return op_extend_attention("emmax_op_extend_attention_kv8", a, total_rows, page, nsplit, 1, ws_floats, nsplit_out, (hipStream_t)st);
 }
+// ---- taps.hip as pure ops.  The lengths are read back and checked first, as above: ld_keys holds every key a row can see ----
+static int op_attn_probs(const char* who, AttnProbsParams& a, int total_rows, int page, int kv8, hipStream_t st) {
+    if (!a.q || !a.probs || !a.kcache || !a.page_table || !a.cu || !a.base) return fail(EMMAX_ERR_INVALID, "%s: null argument", who);
+    if (page != 64) return fail(EMMAX_ERR_INVALID, "%s: page %d (one K tile is one page of 64 keys)", who, page);
+    if (a.Hkv < 1 || a.Hq < 1 || a.Hq % a.Hkv || a.max_pages < 1) return fail(EMMAX_ERR_INVALID, "%s: heads %d / %d, max_pages %d", who, a.Hq, a.Hkv, a.max_pages);
+    const int G = a.Hq / a.Hkv;
+    if (G != 1 && G != 2 && G != 4 && G != 8) return fail(EMMAX_ERR_INVALID, "%s: unsupported GQA group %d (1, 2, 4 or 8)", who, G);
+    if (a.ldq % 8 || a.q_off % 8 || a.q_off < 0 || a.q_off + a.Hq * 128 > a.ldq)
+        return fail(EMMAX_ERR_INVALID, "%s: ldq %d, q_off %d in multiples of 8, the %d heads of 128 inside a row", who, a.ldq, a.q_off, a.Hq);
+    if (a.ld_keys < 4 || a.ld_keys % 4) return fail(EMMAX_ERR_INVALID, "%s: ld_keys %d is not a positive multiple of 4 (16-byte stores)", who, a.ld_keys);
+    if ((((uintptr_t)a.q | (uintptr_t)a.probs) & 15) || ((uintptr_t)a.kcache & (kv8 ? 7 : 15)) ||
+        (((uintptr_t)a.kscale | (uintptr_t)a.cu | (uintptr_t)a.base | (uintptr_t)a.page_table) & 3))
+        return fail(EMMAX_ERR_INVALID, "%s: q, probs and bf16 pages 16-byte aligned, e4m3 pages 8-byte, scales and tables 4-byte", who);
+    int max_n = 0, max_L = 0;
+    if (int r = extend_op_lengths(who, a.cu, a.base, a.B, total_rows, (long)a.max_pages * page, &max_n, &max_L, st)) return r;
+    if (max_L > a.ld_keys) return fail(EMMAX_ERR_INVALID, "%s: ld_keys %d is smaller than the %d keys a row sees", who, a.ld_keys, max_L);
+    const int r = launch_attn_probs(a, max_n, kv8, st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "%s: launch failure", who);
+    return 0;
+}
+int emmax_op_attn_probs(const void* q, int ldq, int q_off, const void* kcache, const int32_t* page_table, const int32_t* cu, const int32_t* base, int B,
+                        int total_rows, int Hq, int Hkv, int page, int max_pages, float scale, float* probs, int ld_keys, emmax_stream st) {
+    AttnProbsParams a;
+    memset(&a, 0, sizeof(a));
+    a.q = q; a.ldq = ldq; a.q_off = q_off; a.kcache = kcache; a.page_table = page_table; a.cu = cu; a.base = base; a.probs = probs; a.ld_keys = ld_keys;
+    a.B = B; a.Hq = Hq; a.Hkv = Hkv; a.max_pages = max_pages; a.scale = scale;
+    return op_attn_probs("emmax_op_attn_probs", a, total_rows, page, 0, (hipStream_t)st);
+}
+int emmax_op_attn_probs_kv8(const void* q, int ldq, int q_off, const void* kcache8, const float* kscale, const int32_t* page_table, const int32_t* cu,
+                            const int32_t* base, int B, int total_rows, int Hq, int Hkv, int page, int max_pages, float scale, float* probs, int ld_keys,
+                            emmax_stream st) {
+    if (!kscale) return fail(EMMAX_ERR_INVALID, "emmax_op_attn_probs_kv8: null argument");
+    AttnProbsParams a;
+    memset(&a, 0, sizeof(a));
+    a.q = q; a.ldq = ldq; a.q_off = q_off; a.kcache = kcache8; a.kscale = kscale; a.page_table = page_table; a.cu = cu; a.base = base; a.probs = probs;
+    a.ld_keys = ld_keys; a.B = B; a.Hq = Hq; a.Hkv = Hkv; a.max_pages = max_pages; a.scale = scale;
+    return op_attn_probs("emmax_op_attn_probs_kv8", a, total_rows, page, 1, (hipStream_t)st);
+}
+int emmax_op_tap_rows(const void* src, int src_f32, int ld_src, float* dst, int rows, int H, const void* norm_w, float eps, emmax_stream st) {
+    if (!src || !dst) return fail(EMMAX_ERR_INVALID, "emmax_op_tap_rows: null argument");
+    if (rows < 1 || H < 8 || H % 8 || ld_src < H || ld_src % (src_f32 ? 4 : 8) || (((uintptr_t)src | (uintptr_t)dst | (uintptr_t)norm_w) & 15))
+        return fail(EMMAX_ERR_INVALID, "emmax_op_tap_rows: rows %d (>= 1), H %d (a multiple of 8), ld_src %d (>= H, 16-byte rows), 16-byte aligned pointers", rows, H,
+                    ld_src);
+    TapRowsParams p;
+    memset(&p, 0, sizeof(p));
+    p.src = src; p.src_f32 = src_f32 ? 1 : 0; p.ld_src = ld_src; p.dst = dst; p.rows = rows; p.H = H; p.norm_w = norm_w; p.eps = eps;
+    const int r = launch_tap_rows(p, (hipStream_t)st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_tap_rows: launch failure");
+    return 0;
+}
 int emmax_op_rope_kv_write_at(void* qkv, int ld, int q_off, int k_off, int v_off, const int32_t* cu, const int32_t* base, int B, int total_rows, const float* cos_t,
                               const float* sin_t, int max_pos, void* kcache, void* vcache, const int32_t* page_table, int max_pages, int Hq, int Hkv, int head_dim,
                               int page, emmax_stream stream) {

@@ -83,6 +83,7 @@ int run_prefill_layers(emmax_session* s, int B, int total, int maxS, int r0, con
             if (s->kv8)
                 KCHK(launch_kv_quant_rows_at(s->pqkv, m->qkv_dim, m->q_dim, m->q_dim + m->kv_dim, s->cu, s->ext_base, B, total, kcache_of(s, li), vcache_of(s, li),
                                              kscale_of(s, li), vscale_of(s, li), ptab, s->max_pages, c.n_kv_heads, c.head_dim, PAGE, st));
+            if (int r = tap_pass_attn(s, li, B, total, maxS, r0, true, st)) return r;
             ExtendAttnParams a;
             memset(&a, 0, sizeof(a));
             a.q = s->pqkv; a.ldq = m->qkv_dim; a.q_off = 0; a.out = s->patt; a.ld_out = m->q_dim;
@@ -100,6 +101,7 @@ int run_prefill_layers(emmax_session* s, int B, int total, int maxS, int r0, con
                 KCHK(launch_kv_quant_rows(s->pqkv, m->qkv_dim, m->q_dim, m->q_dim + m->kv_dim, s->cu, B, total, kcache_of(s, li), vcache_of(s, li),
                                           kscale_of(s, li), vscale_of(s, li), s->page_table + (size_t)r0 * s->max_pages, s->max_pages, c.n_kv_heads,
                                           c.head_dim, PAGE, st));
+            if (int r = tap_pass_attn(s, li, B, total, maxS, r0, false, st)) return r;   // (the layer's keys are in the cache: the map reads them there)
             AttnParams a;
             a.qkv = s->pqkv; a.out = s->patt; a.cu_seqlens = s->cu;
             a.ld_qkv = m->qkv_dim; a.q_off = 0; a.k_off = m->q_dim; a.v_off = m->q_dim + m->kv_dim; a.ld_out = m->q_dim;
@@ -119,7 +121,9 @@ int run_prefill_layers(emmax_session* s, int B, int total, int maxS, int r0, con
         into_stream(g);
         normed = li + 1 < c.n_layers && with_norm(g, m->layers[li + 1].ln1);
         KCHK(launch_gemm(g, st));
+        if (int r = tap_pass_hidden(s, li + 1, total, st)) return r;
     }
+    taps_unbind(s, true, false);   // consumed by this pass
     KCHK(launch_gather_last_rows(s->ph, s->dh + (size_t)r0 * m->H, s->cu, B, m->H, st, h32_of(s, r0), p32 ? s->ph32 : nullptr));
     return 0;
 }
@@ -192,6 +196,8 @@ int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B
         maxS = std::max(maxS, Sb);
     }
     if (total > s->max_rows) return fail(EMMAX_ERR_NOMEM, "packed prefill rows %d exceed capacity %d", total, s->max_rows);
+    if (int r = tap_pass_check(s, maxS, "prefill")) return r;
+    if (!slot_mode) taps_unbind(s, false, true);   // step taps were bound for the rows of the last pass
     KCHK(launch_prefill_state(ps, s->cu, s->ctx_len + r0, s->done + r0, s->n_out + r0, s->max_new_d + r0, s->stop_m + r0, s->stop_after + r0, st));
     if (s->aut.on) {   // the rows enter the automaton at their start states (sample groups: the B x N rows the prefill forks into)
         const int rows = s->grp_N && !slot_mode ? B * s->grp_N : B;
@@ -224,6 +230,7 @@ int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B
     const bool p32 = emmax_tune().resid32 == 1;
     s->p32 = p32;
     KCHK(launch_embed_splice(ids, P_max, s->cu, m->embed, patches, s->ph, B, maxS, np, m->H, m->vocab, st, p32 ? s->ph32 : nullptr));
+    if (int r = tap_pass_hidden(s, 0, total, st)) return r;
     if (int r = run_prefill_layers(s, B, total, maxS, r0, nullptr, st)) return r;
     if (int r = s->grp_N ? run_group_fork(s, B, st) : run_lm_head_step(s, B, true, nullptr, true, st, r0)) return r;
     s->prefilled = true;

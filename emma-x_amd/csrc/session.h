@@ -196,6 +196,24 @@ struct Beams {
     int32_t *cand_tok, *fin_flag, *fin_t, *fin_par, *fin_tok, *grp, *spare, *csrc, *cdst, *cntok, *tr_tok, *tr_par, *tc_idx, *res_bidx, *res_len;
 };
 
+// TAPS (emmax_session_set_pass_taps / emmax_session_set_step_taps; taps.hip): caller-owned fp32 buffers the session fills while it runs a pass it
+// would run anyway.  hl / al: the selected hidden states (bit i = HF's hidden_states[i], bit n_layers the normed last) and attention layers.
+// pass: consumed by the next prefill or emmax_extend over its packed rows, [n_sel][total_rows][H] and [n_sel][total_rows][Hq][ld];  step: filled by
+// every decode step that follows, [max_new][n_sel][B][H] and [max_new][n_sel][B][Hq][ld], indexed by the row's n_out.  serial: counts every binding
+// and unbinding -- part of the captured graph's key (the buffers are kernel arguments).  Nothing bound: none of it is touched and every pass launches
+// what it launches without
+struct TapSet {
+    bool on = false;
+    float *hidden = nullptr, *attn = nullptr;
+    uint64_t hl = 0, al = 0;
+    int ld = 0;
+};
+struct Taps {
+    TapSet pass, step;
+    int step_max_new = 0, step_B = 0;
+    int serial = 0;
+};
+
 struct emmax_session {
     emmax_model* m;
     int max_batch, max_prompt, max_ctx, max_pages, max_rows /* packed prefill rows */, max_out;
@@ -236,6 +254,7 @@ struct emmax_session {
     Automaton aut;
     Scores scores;
     TopLogprobs toplp;
+    Taps taps;
     Beams beam;
     // SAMPLE GROUPS (emmax_session_set_sample_groups; step.hip: run_group_fork): N sampled rows per prefilled prompt, 0 = off.  Rows g N + j are
     // the samples of prompt g; the fork's copy list lives in the beams' (csrc / cdst / cntok: beams and groups exclude each other)
@@ -305,6 +324,7 @@ struct emmax_session {
     hipEvent_t ev = nullptr;
     int graph_epoch = -1;      // emmax_tune().epoch the graph was captured under (a changed switch re-captures)
     int graph_grp = 0;    // attn_group_rows() the step was captured under (rows per group of the grouped attention route, 0 = today's launch)
+    int graph_taps = 0;   // taps.serial the step was captured under (bound step taps are launches of the step: binding or unbinding re-captures)
     int graph_mode = 0;   // finish_mode() the step was captured under (the parameters and score buffers are device words: a change re-captures nothing)
     hipStream_t own_stream = nullptr;   // where a call made on the (uncapturable) legacy stream runs: StreamScope
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
@@ -368,6 +388,19 @@ private:
 int check_sampling_values(const emmax_session* s, const int32_t* rows, int n, const float* T, const int32_t* top_k, const float* top_p);
 int upload_fork_sampling(emmax_session* s, int n, const float* T, const int32_t* top_k, const float* top_p, const uint64_t* seed, const uint32_t* subseq,
                          hipStream_t st);
+// modes.hip: the taps' hooks.  idx: HF's hidden_states index (0 = behind the embed / patch splice, i = behind layer i's down projection, n_layers = that
+// row normed); each returns 0 at once where its buffer or its bit is not bound.  tap_pass_check: the pass taps against the pass's lengths (EMMAX_ERR_INVALID)
+int tap_pass_check(emmax_session* s, int max_keys, const char* who);
+int tap_pass_hidden(emmax_session* s, int idx, int total, hipStream_t st);
+int tap_pass_attn(emmax_session* s, int li, int B, int total, int max_n, int r0, bool ext, hipStream_t st);
+int tap_step_hidden(emmax_session* s, int idx, int B, hipStream_t st);
+int tap_step_attn(emmax_session* s, int li, int B, hipStream_t st);
+// what ends the mode a binding was made for (slot serving, beams, sample groups, another prefill for the step taps) unbinds
+static inline void taps_unbind(emmax_session* s, bool pass, bool step) {
+    if (step && s->taps.step.on) s->taps.serial += 1;   // (the pass taps are no part of the captured step)
+    if (pass) s->taps.pass = TapSet();
+    if (step) s->taps.step = TapSet();
+}
 // generate.hip: every hidden page back into its row's table (a permutation again), no slot in a group; what ends or restarts slot serving calls it
 int slots_restore_pages(emmax_session* s, hipStream_t st);
 // vision.hip: GEMM parameters -- plain; of a session stage (with the session's split-K scratch); of an exact-numerics stage (HL rows in, fp32 out)

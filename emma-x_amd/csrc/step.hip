@@ -628,9 +628,17 @@ int run_decode_step(emmax_session* s, int B, hipStream_t st) {
     // batch 1-2 on bf16 weights: the embedding row is read by layer 0's qkv launch itself (decode_ks.hip, when it takes the launch) -- one launch fewer
     const bool fold_embed = B < EMMAX_MFMA_MIN_BATCH && !m->fp8 && !m->mx4 && decode_ks_enabled() && emmax_tune().fold_embed != 0;
     if (!fold_embed) KCHK(launch_decode_embed(s->cur_tok, m->embed, s->dh, B, m->H, m->vocab, st, s->exact ? s->dh32 : h32_of(s)));
+    const bool taps = s->taps.step.on;   // (nothing bound: the launches below are all there is)
+    if (taps)
+        if (int r = tap_step_hidden(s, 0, B, st)) return r;
     for (int li = 0; li < m->cfg.n_layers; ++li)
         for (int stage = STAGE_QKV; stage <= STAGE_DOWN; ++stage) {
             if (int r = (li == 0 && stage == STAGE_QKV && fold_embed) ? run_qkv0_with_embed(s, B, st) : run_decode_stage(s, B, li, stage, st)) return r;
+            // the map behind the attention launch (an fp8 cache gets the step's key only there), the stream behind the down projection
+            if (taps && stage == STAGE_ATTN)
+                if (int r = tap_step_attn(s, li, B, st)) return r;
+            if (taps && stage == STAGE_DOWN)
+                if (int r = tap_step_hidden(s, li + 1, B, st)) return r;
         }
     return run_lm_head_step(s, B, false, nullptr, true, st);
 }
@@ -661,7 +669,7 @@ int ensure_graph(emmax_session* s, int B, hipStream_t st) {
     s->last_step_graph = 0;   // set again by launch_graph_step when a replay really runs
     if (!emmax_tune().graph) return 1;   // eager step: a captured graph stays valid for the next caller that wants replay
     if (s->graph_exec && s->graph_B == B && s->graph_stream_cap == st && s->graph_epoch == emmax_tune().epoch && s->graph_mode == finish_mode(s) &&
-        s->graph_grp == attn_group_rows(s, B))
+        s->graph_grp == attn_group_rows(s, B) && s->graph_taps == s->taps.serial)
         return 0;
     drop_graph(s);
     if (s->graph_failed) return 1;
@@ -681,7 +689,7 @@ int ensure_graph(emmax_session* s, int B, hipStream_t st) {
         return graph_fail(s, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
     }
     s->graph = g; s->graph_exec = ge; s->graph_B = B; s->graph_stream_cap = st; s->graph_epoch = emmax_tune().epoch;
-    s->graph_mode = finish_mode(s); s->graph_grp = attn_group_rows(s, B);
+    s->graph_mode = finish_mode(s); s->graph_grp = attn_group_rows(s, B); s->graph_taps = s->taps.serial;
     return 0;
 }
 

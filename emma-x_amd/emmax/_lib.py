@@ -124,6 +124,13 @@ SIGNATURES = {
     "emmax_op_rope_kv_write_at": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp] + [C.c_int] * 5
                                   + [_vp]),
     "emmax_extend_attn_plan": (C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_int)] * 5),
+    "emmax_session_set_pass_taps": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_int, _vp]),
+    "emmax_session_set_step_taps": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_int, C.c_int, _vp]),
+    "emmax_session_clear_taps": (C.c_int, [_vp, _vp]),
+    "emmax_session_taps": (C.c_int, [_vp]),
+    "emmax_op_attn_probs": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp] + [C.c_int] * 6 + [C.c_float, _vp, C.c_int, _vp]),
+    "emmax_op_attn_probs_kv8": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp] + [C.c_int] * 6 + [C.c_float, _vp, C.c_int, _vp]),
+    "emmax_op_tap_rows": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_float, _vp]),
     "emmax_op_gemv": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "emmax_op_resize_bicubic_u8": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp]),
     "emmax_op_quant_fm8": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp]),

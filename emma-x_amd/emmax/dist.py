@@ -98,13 +98,16 @@ MAX_ROWS = 64   # rows of one decode batch (EMMAX_MAX_DECODE_BATCH, emma-x_amd/c
 
 
 def generate_actions_dp(model, frames_u8: torch.Tensor, prompt_rows, max_new_tokens: int = 512, stop_on_eos: bool = True,
-                        tokenizer=None, beams=None):
+                        tokenizer=None, beams=None, output_hidden_states: bool = False, output_attentions: bool = False):
     """Data-parallel `generate_actions_batch` (BASELINE config 3): every rank passes the SAME global batch (frames uint8
     [B,H,W,3], B prompts); rank r computes its contiguous shard on its own GPU (sub-batches of <= 64 rows) and one
     all_gather returns (actions f32 [B,7], ids i32 [B,T], lens i32 [B]) in global order on every rank.  Beams are not built here:
     `beams` other than None is refused."""
     if beams is not None:
         raise NotImplementedError("beam search is not available in the data-parallel call: run model.generate_actions_batch(beams=...) per rank")
+    if output_hidden_states or output_attentions:
+        raise NotImplementedError("hidden states / attention maps are not gathered by the data-parallel call (GBs per rank): run model.generate(..., "
+                                  "return_dict_in_generate=True, output_hidden_states=True / output_attentions=True) per rank")
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
     Btot = frames_u8.shape[0]

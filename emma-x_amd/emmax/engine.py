@@ -136,6 +136,7 @@ class EmmaxEngine:
         assert bool(self.lib.emmax_session_exact(self._session)) == bool(self.exact)
         self._score_bufs = None   # a new session binds no scores
         self._top_bufs = None     # ... and no top / watched log-probability buffers
+        self._tap_bufs = None     # ... and no taps
         self._beam_K = 0          # ... and has beams off
         self._group_N = 0         # ... and sample groups off
         self.session_epoch = getattr(self, "session_epoch", 0) + 1   # which session a KV handle names (modeling.KVHandle)
@@ -361,6 +362,54 @@ class EmmaxEngine:
         out = (C.c_int32 * n)()
         _lib.check(self.lib.emmax_session_context(self._session, int(row0), n, out, _lib.current_stream()), "emmax_session_context")
         return list(out)
+
+    # ---- taps: hidden states and attention maps out of the passes (include/emmax.h: emmax_session_set_pass_taps) ---------------
+    def _tap_refusals(self, who: str) -> None:
+        if self.exact:
+            raise NotImplementedError(f"{who}: exact-numerics models serve no hidden states / attention maps (their fp32 cache has no probability kernel)")
+
+    def _tap_buffers(self, shapes, zero: bool):
+        make = torch.zeros if zero else torch.empty
+        return tuple(make(sh, dtype=torch.float32, device=self.device) if sh is not None else None for sh in shapes)
+
+    def bind_pass_taps(self, spec, total_rows: int, max_keys: int):
+        """Bind fp32 buffers that the NEXT prefill or extend fills over its `total_rows` packed rows (taps.TapSpec; taps.pass_shapes) and that are
+        unbound behind it: (hidden [n_sel, total_rows, H] or None, attentions [n_sel, total_rows, Hq, ld_keys] or None).  max_keys: the keys
+        the longest row of the pass sees.  The kernel writes every entry of every row: the buffers are not cleared."""
+        from . import taps as T
+
+        self._tap_refusals("bind_pass_taps")
+        ld = T.round_keys(max_keys)
+        hid, att = self._tap_buffers(T.pass_shapes(spec, int(total_rows), self.cfg.llm.hidden_size, self.cfg.llm.num_heads, ld), zero=False)
+        _lib.check(self.lib.emmax_session_set_pass_taps(self._session, _lib.ptr(hid), T.layer_mask(spec.hidden), _lib.ptr(att), T.layer_mask(spec.attn), ld,
+                                                        _lib.current_stream()), "emmax_session_set_pass_taps")
+        self._tap_bufs = (hid, att)
+        return hid, att
+
+    def bind_step_taps(self, spec, max_new: int, max_keys: int):
+        """Bind zeroed fp32 buffers that every decode step from now on fills at each row's generation index (after a prefill or extend; unbound
+        by the next one or by clear_taps): (hidden [max_new, n_sel, B, H] or None, attentions [max_new, n_sel, B, Hq, ld_keys] or None), B
+        the live batch.  Slot 0 is the prompt pass's and stays zero, as do the slots of tokens a finished row did not emit; max_new = 1 is the
+        single-step form (every row lands in slot 0).  max_keys: the keys the longest row sees in its last step."""
+        from . import taps as T
+
+        self._tap_refusals("bind_step_taps")
+        ld = T.round_keys(max_keys)
+        hid, att = self._tap_buffers(T.step_shapes(spec, int(max_new), self._last_B, self.cfg.llm.hidden_size, self.cfg.llm.num_heads, ld), zero=True)
+        _lib.check(self.lib.emmax_session_set_step_taps(self._session, _lib.ptr(hid), T.layer_mask(spec.hidden), _lib.ptr(att), T.layer_mask(spec.attn), ld,
+                                                        int(max_new), _lib.current_stream()), "emmax_session_set_step_taps")
+        self._tap_bufs = (hid, att)
+        return hid, att
+
+    def clear_taps(self) -> None:
+        """Unbind: the session launches what it launched before, and the buffers are the caller's."""
+        _lib.check(self.lib.emmax_session_clear_taps(self._session, _lib.current_stream()), "emmax_session_clear_taps")
+        self._tap_bufs = None
+
+    @property
+    def taps_bound(self) -> int:
+        """bit 0: pass taps, bit 1: step taps"""
+        return max(int(self.lib.emmax_session_taps(self._session)), 0)
 
     # ---- sampling inside the decode step (include/emmax.h, ABI 7) -------------------------------------------------------
     @staticmethod

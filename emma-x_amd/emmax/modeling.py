@@ -25,6 +25,7 @@ import torch
 
 from .actions import ActionTokenizer, action_bin_token_ids, token_ids_to_actions, unnormalize
 from .config import EmmaXConfig, check_decode_weight_dtype, default_norm_stats
+from . import taps as _taps
 from .engine import EmmaxEngine
 from .policy_parser import Solver
 from .processing import BatchFeature, EmmaXImageProcessor
@@ -77,6 +78,9 @@ class EmmaXGenerateOutput:
     watch_logprobs: Optional[torch.Tensor] = None
     # what the call left cached (a KVHandle; its lengths are read back from the session): generate(..., past_key_values=it) continues from there
     past_key_values: Optional[Any] = None
+    # output_hidden_states / output_attentions: HF's tuples over the generated tokens (TapsOutput describes them)
+    hidden_states: Optional[Tuple] = None
+    attentions: Optional[Tuple] = None
 
     def __getitem__(self, key: str):
         return getattr(self, key)
@@ -93,6 +97,17 @@ class TopLogprobsOutput:
     top_logprobs: torch.Tensor
     watch_logprobs: torch.Tensor
     logprobs: torch.Tensor
+
+
+@dataclass
+class TapsOutput:
+    """The trailing object of generate_ids(..., hidden=[...], attentions=[...]): HF generate's hidden_states / attentions -- a tuple over the
+    generated tokens (T = the longest row's count); element 0 is the prompt pass, a tuple over the selected entries of fp32 [B, S, H] /
+    [B, Hq, S, S] device tensors (a continuation: the new rows, [B, n, H] / [B, Hq, n, L]); element t >= 1 the decode step that emitted token t,
+    [B, 1, H] / [B, Hq, 1, L + t].  Rows of different lengths: a list per row in place of the stacked tensor.  Entries of tokens a finished row
+    did not emit are zeros.  None: not asked for."""
+    hidden_states: Optional[Tuple] = None
+    attentions: Optional[Tuple] = None
 
 
 class KVHandle:
@@ -279,7 +294,7 @@ class EmmaXForActionPrediction:
 
     def _prefill(self, rows: List[List[int]], pixel_values=None, frames_u8=None, max_new: int = 0, sampling=None, processing=None,
                  scores=None, logits=None, beams: Optional[BeamParams] = None, num_samples: int = 1, top=None, constraint=None,
-                 constraint_start=None) -> torch.Tensor:
+                 constraint_start=None, taps=None) -> torch.Tensor:
         eng = self._need_engine()
         B = len(rows)
         src = pixel_values if pixel_values is not None else frames_u8
@@ -319,6 +334,9 @@ class EmmaXForActionPrediction:
             eng.set_beams(beams)
         if N > 1:   # B prompts prefill once each and fork into B x N sampled rows on the prompt's KV pages
             eng.set_sample_groups(N)
+        if taps is not None:   # (taps.TapSpec) the pass fills them over its packed rows: self._pass_taps, with the rows' lengths
+            S = [self.config.n_patches + len(r) for r in rows]
+            self._pass_taps = eng.bind_pass_taps(taps, sum(S), max(S)) + (S, S)
         eng.prefill(rows, patches)
         return patches
 
@@ -333,7 +351,7 @@ class EmmaXForActionPrediction:
             raise ValueError(f"{who}: {n_rows} rows continue a cache of {len(handle.lengths)} rows: a continuation keeps the batch")
 
     def _continue(self, handle, rows: List[List[int]], max_new: int = 0, sampling=None, processing=None, scores=None, logits=None, top=None,
-                  constraint=None, constraint_start=None) -> None:
+                  constraint=None, constraint_start=None, taps=None) -> None:
         """_prefill for rows that continue a cached context: no vision, no prefill -- the new ids are appended to what the handle's rows hold
         (engine.extend).  The session is never re-created here."""
         eng = self._need_engine()
@@ -371,6 +389,9 @@ class EmmaXForActionPrediction:
         if constraint is not None:
             eng.set_automaton(constraint)
             eng.set_automaton_starts(constraint.starts(constraint_start, B))
+        if taps is not None:   # the new rows alone; row i of sequence b sees the handle's cached keys and the rows up to itself
+            n_new, keys = [len(r) for r in rows], [n + len(r) for n, r in zip(handle.lengths, rows)]
+            self._pass_taps = eng.bind_pass_taps(taps, sum(n_new), max(keys)) + (n_new, keys)
         eng.extend(rows, max_new_tokens=max(max_new, 1))
 
     @staticmethod
@@ -506,16 +527,39 @@ class EmmaXForActionPrediction:
                            eta_cutoff=0.0 if eta_cutoff is None else eta_cutoff)   # (validates)
         return p if seed is not None else dataclasses.replace(p, seed=draw_seed(generator))
 
+    def _tap_args(self, output_hidden_states, output_attentions, tap_layers, num_beams=None, num_samples: int = 1) -> Optional["_taps.TapSpec"]:
+        """output_hidden_states / output_attentions / tap_layers of a call -> taps.TapSpec (None: neither asked for), and what they are not
+        served with, each with its own message, before the engine is touched."""
+        spec = _taps.tap_spec(self.config.llm.num_layers, output_hidden_states, output_attentions, tap_layers)
+        if spec is None:
+            return None
+        if self.engine is not None and getattr(self.engine, "exact", 0):
+            raise NotImplementedError("output_hidden_states / output_attentions are not served by exact-numerics models (their fp32 cache has no "
+                                      "probability kernel): load the model without exact=True for them")
+        if num_beams is not None and num_beams != 1:
+            raise NotImplementedError("output_hidden_states / output_attentions with num_beams > 1 are outside the hot path (the rows of a beam group "
+                                      "reorder every step)")
+        if num_samples != 1:
+            raise NotImplementedError("output_hidden_states / output_attentions with num_return_sequences > 1 are outside the hot path (a sample "
+                                      "group forks its rows behind the prompt pass)")
+        return spec
+
     def forward(self, input_ids=None, attention_mask=None, pixel_values=None, labels=None, inputs_embeds=None,
                 past_key_values=None, use_cache=None, output_attentions=None, output_hidden_states=None,
-                output_projector_features=None, return_dict=None, frames_u8=None):
+                output_projector_features=None, return_dict=None, frames_u8=None, tap_layers=None):
         """Multimodal forward -> logits for every position ([B,S,V] when rows have equal length, else a list), or one
-        cached decode step when `input_ids.shape[1] == 1` and `past_key_values` is the handle of a previous call."""
+        cached decode step when `input_ids.shape[1] == 1` and `past_key_values` is the handle of a previous call.
+        output_hidden_states / output_attentions (every branch): `hidden_states` = a tuple of n_layers + 1 fp32 [B, S, H] tensors (entry 0 the
+        embeddings with the patch rows spliced in -- they count in S, as in the reference -- entry i the residual stream behind layer i, the
+        last one normed, as HF returns it), `attentions` = a tuple of n_layers fp32 [B, Hq, n, L] tensors (n new rows over L keys, zeros above
+        the diagonal, HF's eager maps).  Rows of different lengths: each entry is a list with one tensor per row, the rule `logits` follows.
+        They are written by the session's own pass through taps (include/emmax.h), not recomputed.  tap_layers=[...] (HF indices into those
+        tuples, negative allowed; None = all, HF's meaning) keeps the selected entries only, in ascending order: the maps of all 32 layers of
+        a 7B prompt of 768 rows are 32 x 768 x 32 x 768 x 4 bytes = 2.4 GB.  Not in exact numerics."""
         eng = self._need_engine()
         if labels is not None:
             raise NotImplementedError("loss / labels belong to training, outside the inference hot path")
-        if output_attentions or output_hidden_states:
-            raise NotImplementedError("attention maps / hidden states are not materialised by the fused kernels")
+        spec = self._tap_args(output_hidden_states, output_attentions, tap_layers)
         # `inputs_embeds` is never consumed as data by the reference either: the cached branch hands the language model
         # inputs_embeds=None (modeling_prismatic.py:330-341), the multimodal branch embeds `input_ids` whatever else was passed
         # (:381), and the language-only branch asserts it away (:345).  Same behaviour here.
@@ -525,41 +569,67 @@ class EmmaXForActionPrediction:
         if isinstance(input_ids, torch.Tensor) and input_ids.shape[-1] == 1 and past_key_values is not None:
             assert len(rows) == len(past_key_values.lengths), "cached step must keep the batch of the prefill"
             eng.set_current_tokens([r[0] for r in rows])
+            hs = at = None
+            if spec is not None:   # the single-step form of the step taps: every row lands in slot 0
+                keys = [n + 1 for n in past_key_values.lengths]
+                bufs = eng.bind_step_taps(spec, 1, max(keys))
             eng.decode_step()
+            if spec is not None:
+                eng.clear_taps()
+                hs, at = _taps.cut_step(bufs[0], bufs[1], 0, keys)
             logits = eng.last_logits()[:, None, :]
             past_key_values.lengths = [n + 1 for n in past_key_values.lengths]
-            return EmmaXCausalLMOutputWithPast(logits=logits, past_key_values=past_key_values)
+            return EmmaXCausalLMOutputWithPast(logits=logits, past_key_values=past_key_values, hidden_states=hs, attentions=at)
         if input_ids is not None and isinstance(input_ids, torch.Tensor) and input_ids.shape[-1] == 1:
             assert past_key_values is not None, "You must provide `past_key_values` during cached generation!"
         if past_key_values is not None and pixel_values is None and frames_u8 is None:
             # n > 1 new ids per row on top of the handle's cache (ragged rows: lists, or a right-padding mask): one pass over the new rows alone
             self._check_handle(past_key_values, len(rows), "forward")
             self._set_processing(eng, len(rows), None)   # (as the language-only branch: what an earlier generate left in the session is cleared)
+            hs = at = None
+            if spec is not None:
+                n_new, keys = [len(r) for r in rows], [n + len(r) for n, r in zip(past_key_values.lengths, rows)]
+                bufs = eng.bind_pass_taps(spec, sum(n_new), max(keys))
             eng.extend(rows, max_new_tokens=0)
+            if spec is not None:
+                hs, at = _taps.cut_pass(bufs[0], bufs[1], n_new, keys)
             per_row = eng.prefill_logits()
             past_key_values.lengths = [n + len(r) for n, r in zip(past_key_values.lengths, rows)]
             same = len({t.shape[0] for t in per_row}) == 1
-            return EmmaXCausalLMOutputWithPast(logits=torch.stack(per_row) if same else per_row, past_key_values=past_key_values)
+            return EmmaXCausalLMOutputWithPast(logits=torch.stack(per_row) if same else per_row, past_key_values=past_key_values, hidden_states=hs,
+                                               attentions=at)
         if pixel_values is None and frames_u8 is None:
             # unimodal forward (modeling_prismatic.py:343-359): text only, no patch rows
             assert inputs_embeds is None, "Missing `input_ids` in language-only forward!"
             assert past_key_values is None, "Unexpected key `past_key_values` provided during language-only forward!"
             eng.ensure_capacity(len(rows), max(len(r) for r in rows), self.cache_reserve if use_cache else 1)
             self._set_processing(eng, len(rows), None)   # (as _prefill: what an earlier generate left in the session is cleared)
+            hs = at = None
+            if spec is not None:
+                if getattr(eng, "beams", 0):
+                    eng.clear_beams()
+                if getattr(eng, "sample_groups", 0):
+                    eng.clear_sample_groups()
+                S = [len(r) for r in rows]
+                bufs = eng.bind_pass_taps(spec, sum(S), max(S))
             eng.prefill(rows, None)
+            if spec is not None:
+                hs, at = _taps.cut_pass(bufs[0], bufs[1], S, S)
             per_row = eng.prefill_logits()
             same = len({t.shape[0] for t in per_row}) == 1
             return EmmaXCausalLMOutputWithPast(logits=torch.stack(per_row) if same else per_row,
-                                               past_key_values=KVHandle(eng, eng._last_S) if use_cache else None)
+                                               past_key_values=KVHandle(eng, eng._last_S) if use_cache else None, hidden_states=hs, attentions=at)
         if past_key_values is not None:
             raise ValueError("forward(past_key_values=...) extends the cached rows with text ids: pass no pixel_values / frames_u8 with it")
-        patches = self._prefill(rows, pixel_values, frames_u8, max_new=self.cache_reserve if use_cache else 0)
+        patches = self._prefill(rows, pixel_values, frames_u8, max_new=self.cache_reserve if use_cache else 0, taps=spec)
+        hs, at = _taps.cut_pass(*self._pass_taps) if spec is not None else (None, None)
+        self._pass_taps = None
         per_row = eng.prefill_logits()
         same = len({t.shape[0] for t in per_row}) == 1
         logits = torch.stack(per_row) if same else per_row
         return EmmaXCausalLMOutputWithPast(
             logits=logits, past_key_values=KVHandle(eng, eng._last_S, self.config.n_patches) if use_cache else None,
-            projector_features=patches if output_projector_features else None)
+            hidden_states=hs, attentions=at, projector_features=patches if output_projector_features else None)
 
     __call__ = forward
 
@@ -567,7 +637,8 @@ class EmmaXForActionPrediction:
     def generate_ids(self, rows: List[List[int]], pixel_values=None, frames_u8=None, max_new_tokens: int = 512,
                      stop_on_eos: bool = True, sampling=None, return_logprobs: bool = False, processing=None, scores=None, logits=None,
                      beams: Optional[BeamParams] = None, num_samples: int = 1, top_logprobs: int = 0, watch_ids: Optional[Sequence[int]] = None,
-                     constraint=None, constraint_start=None, continue_from=None, return_handle: bool = False):
+                     constraint=None, constraint_start=None, continue_from=None, return_handle: bool = False, hidden: Optional[Sequence[int]] = None,
+                     attentions: Optional[Sequence[int]] = None):
         """Decode every row: greedy, or sampled in the step with `sampling` (one SamplingParams for all rows or one per row; row b draws
         with subseq b).  `processing` (one LogitsProcessing for all rows or one per row) applies HF's repetition penalty / n-gram ban /
         min-new-tokens in the step first.  `scores` / `logits`: fp32 [max_new, B, vocab] device buffers the step fills with HF's scores /
@@ -592,7 +663,24 @@ class EmmaXForActionPrediction:
         hold -- no vision, no prefill, one pass over the new rows (engine.extend).  A row's last emitted token is not cached: pass it first.
         Greedy, sampling, warpers, token rules, top_logprobs / watch_ids, scores and constraint work as after a prefill; beams, num_samples > 1
         and repetition_penalty / no_repeat_ngram_size / min_new_tokens raise NotImplementedError.
-        `return_handle`: the return gains one trailing KVHandle of what the call leaves cached (lengths read back from the session)."""
+        `return_handle`: the return gains one trailing KVHandle of what the call leaves cached (lengths read back from the session).
+        `hidden` / `attentions` (lists of entries of HF's hidden_states / attentions tuples, ascending; None = off): the return gains one trailing
+        TapsOutput, the LAST element -- per generated token the selected hidden states and attention maps, written by the prompt pass and by
+        every decode step through the session's taps (include/emmax.h).  Greedy, sampled, with processors, warpers, a constraint,
+        top_logprobs and continue_from; not with beams or num_samples > 1, not in exact numerics.  The ids are those of the same call without."""
+        spec = None
+        if hidden is not None or attentions is not None:
+            spec = _taps.TapSpec(sorted(set(int(i) for i in hidden or [])), sorted(set(int(i) for i in attentions or [])))
+            nl = self.config.llm.num_layers
+            if not spec.any or any(not 0 <= i <= nl for i in spec.hidden) or any(not 0 <= i < nl for i in spec.attn):
+                raise ValueError(f"hidden takes entries 0..{nl}, attentions layers 0..{nl - 1}, at least one of them (got {hidden!r}, {attentions!r})")
+            if beams is not None:
+                raise NotImplementedError("hidden states / attention maps with num_beams > 1 are outside the hot path (the rows of a beam group reorder every step)")
+            if self._check_num_samples(num_samples) > 1:
+                raise NotImplementedError("hidden states / attention maps with num_return_sequences > 1 are outside the hot path (a sample group forks its "
+                                          "rows behind the prompt pass)")
+            if self.engine is not None and getattr(self.engine, "exact", 0):
+                raise NotImplementedError("hidden states / attention maps are not served by exact-numerics models")
         if continue_from is not None:
             if beams is not None:
                 raise NotImplementedError("num_beams > 1 with a continuation is outside the hot path (beams fork their rows from a fresh prefill)")
@@ -629,9 +717,26 @@ class EmmaXForActionPrediction:
         self._check_score_buffers(scores, logits, max_new_tokens, len(rows) * (beams.num_beams if beams is not None else N),
                                   self.config.llm.vocab_size)
         def start(**kw):   # the rows' context: a prefill, or the new ids on top of what continue_from holds
+            if spec is not None:
+                kw["taps"] = spec
             if continue_from is not None:
-                return self._continue(continue_from, rows, **kw)
-            return self._prefill(rows, pixel_values, frames_u8, beams=beams, **self._sample_kw(N), **kw)
+                self._continue(continue_from, rows, **kw)
+            else:
+                self._prefill(rows, pixel_values, frames_u8, beams=beams, **self._sample_kw(N), **kw)
+            if spec is not None and max_new_tokens > 1:   # the steps' taps, bound behind the pass: the step emitting token t sees keys[b] + t keys
+                self._step_taps = eng.bind_step_taps(spec, max_new_tokens, max(self._pass_taps[3]) + max_new_tokens - 1)
+
+        def taps_out(lens):   # HF's layout over the generated tokens: element 0 the prompt pass, element t the step that emitted token t
+            if spec is None:
+                return ()
+            ph, pa, n_new, keys = self._pass_taps
+            sh, sa = self._step_taps if max_new_tokens > 1 else (None, None)
+            if max_new_tokens > 1:
+                eng.clear_taps()
+            self._pass_taps = self._step_taps = None
+            steps = [_taps.cut_pass(ph, pa, n_new, keys)] + [_taps.cut_step(sh, sa, t, [k + t for k in keys]) for t in range(1, max(int(lens.max()), 1))]
+            return (TapsOutput(hidden_states=tuple(s[0] for s in steps) if spec.hidden else None,
+                               attentions=tuple(s[1] for s in steps) if spec.attn else None),)
 
         def handle():      # what the call leaves cached (the rows of the result: beams / sample groups have B x K of them)
             if not return_handle:
@@ -644,7 +749,7 @@ class EmmaXForActionPrediction:
             out = eng.generate(max_new_tokens, stop_on_eos, return_logprobs=return_logprobs)
             if scores is not None or logits is not None:
                 eng.set_scores(None, None)   # the buffers are the caller's now: no later step or prefill writes into them
-            return tuple(out) + handle() if return_handle else out
+            return tuple(out) + handle() + taps_out(out[1]) if return_handle or spec is not None else out
         # a greedy caller: temperature-0 sampling underneath (the argmax of the same fp32 rows), so that the logit rows are written
         start(max_new=max_new_tokens, sampling=sampling if sampling is not None else SamplingParams(0.0, 0, 1.0, seed=0),
               processing=processing, scores=scores, logits=logits, top=(n_top, watch), **cst)
@@ -657,7 +762,7 @@ class EmmaXForActionPrediction:
         if sampling is None:
             eng.clear_sampling()
         top = TopLogprobsOutput(top_ids=ti, top_logprobs=tl, watch_logprobs=wl, logprobs=lp)
-        return ((ids, lens, lp, top) if return_logprobs else (ids, lens, top)) + handle()
+        return ((ids, lens, lp, top) if return_logprobs else (ids, lens, top)) + handle() + taps_out(lens)
 
     def _check_constraint(self, constraint, constraint_start, num_beams: int, n_rows: int) -> Dict[str, Any]:
         """`constraint` / `constraint_start` of a call, checked before the engine is touched -> _prefill's keywords ({}: no constraint)."""
@@ -720,7 +825,8 @@ class EmmaXForActionPrediction:
                  top_p: Optional[float] = None, seed: Optional[int] = None, generator: Optional[torch.Generator] = None,
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
                  output_scores: bool = False, output_logits: bool = False, return_dict_in_generate: bool = False, top_logprobs: int = 0,
-                 watch_ids: Optional[Sequence[int]] = None, past_key_values=None, **kwargs):
+                 watch_ids: Optional[Sequence[int]] = None, past_key_values=None, output_hidden_states: bool = False, output_attentions: bool = False,
+                 tap_layers: Optional[Sequence[int]] = None, **kwargs):
         """HF-style: returns LongTensor [B, P + T] = prompt ++ generated (right-padded with pad_token_id).  do_sample=True draws every token
         in the decode step (include/emmax.h: emmax_session_set_sampling) with temperature / top_k / top_p (HF defaults 1.0 / 50 / 1.0 when
         unset); row b draws with (seed, subseq b), seed None = draw_seed(generator).  With num_return_sequences=N the prompt is prefilled once
@@ -735,7 +841,17 @@ class EmmaXForActionPrediction:
         HF-style multi-turn -- input_ids is the FULL text sequence, the part behind the handle's cached length is appended to the cache (no
         vision, no prefill; at least one id per row, usually the last token of the previous answer); num_beams > 1, num_return_sequences > 1
         and repetition_penalty / no_repeat_ngram_size raise NotImplementedError with it.  The output's `past_key_values` is the handle of what
-        this call leaves cached."""
+        this call leaves cached.
+        output_hidden_states / output_attentions (with return_dict_in_generate): HF's `hidden_states` / `attentions` of the output -- a tuple over
+        the generated tokens, element 0 the prompt pass (a tuple over layers of [B, S, H] / [B, Hq, S, S], the patch rows counting in S), element
+        t >= 1 the step that emitted token t ([B, 1, H] / [B, Hq, 1, S + t]); a list per row where rows differ in length; zeros for tokens a
+        finished row did not emit.  Served greedy and sampled, with processors, warpers, a constraint and log-probabilities alongside; the ids and
+        logits are those of the same call without.  tap_layers=[...] keeps the selected entries only (forward() describes it: all maps of a 7B
+        prompt of 768 rows are 2.4 GB, and every step adds 32 x 32 x its context).  num_beams > 1, num_return_sequences > 1 and exact-numerics
+        models raise NotImplementedError with them."""
+        spec = self._tap_args(output_hidden_states and return_dict_in_generate, output_attentions and return_dict_in_generate, tap_layers,
+                              kwargs.get("num_beams"), kwargs.get("num_return_sequences") or 1)
+        tap_kw = {} if spec is None else {"hidden": spec.hidden or None, "attentions": spec.attn or None}
         n_top, watch = check_top_logprobs(top_logprobs, watch_ids, self.config.llm.vocab_size, "generate")
         want_top = n_top > 0 or len(watch) > 0
         if want_top and not return_dict_in_generate:
@@ -779,8 +895,9 @@ class EmmaXForActionPrediction:
             sc = torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device) if want_sc else None
             lg = torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device) if want_lg else None
         res = self.generate_ids(rows, pixel_values, frames_u8, max_new_tokens, sampling=sampling, processing=processing, scores=sc,
-                                logits=lg, **self._beam_kw(beams), **self._sample_kw(N), **self._top_kw(n_top, watch), **cst, **cont)
+                                logits=lg, **self._beam_kw(beams), **self._sample_kw(N), **self._top_kw(n_top, watch), **cst, **cont, **tap_kw)
         new_ids, lens = res[0], res[1]
+        tapped = res[-1] if spec is not None else TapsOutput()
         kvh = None
         if return_dict_in_generate and self.engine is not None:   # what the call left cached: the lengths are read back from the session
             n_pat = past_key_values.n_patches if past_key_values is not None else self.config.n_patches
@@ -816,7 +933,8 @@ class EmmaXForActionPrediction:
         return EmmaXGenerateOutput(sequences=out, scores=tuple(sc[t] for t in range(T)) if want_sc else None,
                                    logits=tuple(lg[t] for t in range(T)) if want_lg else None,
                                    top_token_ids=top.top_ids[:, :T] if n_top else None, top_logprobs=top.top_logprobs[:, :T] if n_top else None,
-                                   watch_logprobs=top.watch_logprobs[:, :T] if watch else None, past_key_values=kvh)
+                                   watch_logprobs=top.watch_logprobs[:, :T] if watch else None, past_key_values=kvh,
+                                   hidden_states=tapped.hidden_states, attentions=tapped.attentions)
 
     @staticmethod
     def _top_kw(n_top: int, watch) -> Dict[str, Any]:
@@ -844,14 +962,17 @@ class EmmaXForActionPrediction:
     # ------------------------------------------------------------------------------------------------------------------
     @torch.inference_mode()
     def predict_action(self, input_ids=None, unnorm_key: Optional[str] = None, return_bin_logprobs: bool = False, constrain_to_bins: bool = False,
-                       **kwargs) -> np.ndarray:
+                       return_hidden_states: bool = False, **kwargs) -> np.ndarray:
         """modeling_prismatic.py:506-537: append 29871 if missing, generate `action_dim` tokens, de-tokenise, un-normalise.
         return_bin_logprobs=True returns (action, fp32 [action_dim, n_action_bins]): at each action token the log-probabilities of the action-bin
         ids, renormalised over the bins, column k = bin k (actions.py: id vocab_size - 1 - k); [N, action_dim, n_action_bins] for a sample
         group.  Not with num_beams > 1.
         constrain_to_bins=True: every one of the `action_dim` tokens is an action-bin id (constraints.action_bins in the decode step; a token
         outside the bins would be mapped to a wrong bin unnoticed).  Also with return_bin_logprobs and num_return_sequences=N; not with
-        num_beams > 1."""
+        num_beams > 1.
+        return_hidden_states=True: the return gains, as its last element, fp32 [action_dim, H] on the device -- the NORMED last-layer state that
+        produced each action token (HF's hidden_states[-1] at the emitting position: what a continuous-action head consumes), written by the
+        prompt pass and the decode steps through the session's taps.  Not with num_beams > 1 or num_return_sequences > 1."""
         rows = self._rows(input_ids, kwargs.pop("attention_mask", None))
         if len(rows) != 1:
             raise ValueError("Generation with batch size > 1 is not currently supported!")   # reference contract
@@ -868,6 +989,10 @@ class EmmaXForActionPrediction:
         bin_ids = action_bin_token_ids(self.vocab_size, self.config.n_action_bins) if return_bin_logprobs else []
         if return_bin_logprobs and beams is not None:
             raise NotImplementedError("return_bin_logprobs with num_beams > 1 is outside the hot path")
+        tap_kw = {}
+        if return_hidden_states:
+            self._tap_args(True, False, [-1], kwargs.get("num_beams"), N)
+            tap_kw = {"hidden": [self.config.llm.num_layers]}
         cst = self._kw_constraint(kwargs)
         if constrain_to_bins:
             if beams is not None:
@@ -876,8 +1001,14 @@ class EmmaXForActionPrediction:
                 raise ValueError("constrain_to_bins builds its own constraint: pass one of constrain_to_bins= and constraint=")
             cst = {"constraint": self._bin_automaton(dim)}
         res = self.generate_ids(rows, kwargs.get("pixel_values"), kwargs.get("frames_u8"), max_new_tokens=dim, sampling=sampling,
-                                processing=processing, **self._beam_kw(beams), **self._sample_kw(N), **self._top_kw(0, bin_ids), **cst)
+                                processing=processing, **self._beam_kw(beams), **self._sample_kw(N), **self._top_kw(0, bin_ids), **cst, **tap_kw)
         new_ids, lens = res[0], res[1]
+        states = None
+        if return_hidden_states:   # element t, its one entry, row 0, the emitting (last) position
+            hs = res[-1].hidden_states
+            states = torch.stack([hs[t][0][0][-1] for t in range(len(hs))])
+            if states.shape[0] < dim:   # (the row stopped early: zeros for what it did not emit)
+                states = torch.cat([states, states.new_zeros(dim - states.shape[0], states.shape[1])])
 
         def action(j):
             full = rows[0] + new_ids[j, : int(lens[j])].cpu().tolist()
@@ -887,9 +1018,9 @@ class EmmaXForActionPrediction:
         # do_sample=True with num_return_sequences=N > 1: the N sampled actions of the one observation, [N, action_dim]
         acts = action(0) if N == 1 else np.stack([action(j) for j in range(N)])
         if not return_bin_logprobs:
-            return acts
+            return (acts, states) if return_hidden_states else acts
         lp = self.renormalize_logprobs(res[2].watch_logprobs[:, :dim].cpu().numpy())   # [N, dim, n_action_bins]
-        return acts, (lp[0] if N == 1 else lp)
+        return (acts, (lp[0] if N == 1 else lp)) + ((states,) if return_hidden_states else ())
 
     @staticmethod
     def renormalize_logprobs(lp: np.ndarray) -> np.ndarray:

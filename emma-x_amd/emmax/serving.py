@@ -44,6 +44,8 @@ class Request:
                              # last token is not cached -- pass it first to keep it) and decoding goes on in its slot.  Needs no free slot
     constraint_start: Any = None   # a state or entry name of the scheduler's automaton (SlotScheduler(automaton=...)): the request is decoded
                                    # under that constraint from there; None = unconstrained.  A sample group's samples all enter there
+    output_hidden_states: bool = False   # hidden states / attention maps are not served as slots: a request that asks for them is refused at submit
+    output_attentions: bool = False
 
 
 @dataclass
@@ -157,6 +159,9 @@ class SlotScheduler:
     def submit(self, req: Request) -> None:
         if len(req.prompt_ids) < 1:
             raise ValueError("empty prompt")
+        if getattr(req, "output_hidden_states", False) or getattr(req, "output_attentions", False):
+            raise NotImplementedError("hidden states / attention maps are not served as request slots (the taps' buffers are a batch's, and slots come "
+                                      "and go): use model.generate(..., return_dict_in_generate=True, output_hidden_states=True / output_attentions=True)")
         if getattr(req, "beams", None) is not None:
             raise NotImplementedError("beam search is not served as request slots: a beam group is num_beams rows that reorder together -- "
                                       "use model.generate(num_beams=...) / generate_ids(beams=...)")

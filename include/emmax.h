@@ -48,7 +48,9 @@ extern "C" {
  *   log-probabilities (emmax_op_top_logprobs, emmax_session_set_top_logprobs and the calls around it): new symbols only, the workspace grew
  *   their six device words and the watch list (1.3 KB); still 12: extending a cached context (emmax_extend, emmax_slot_extend,
  *   emmax_session_context, emmax_op_extend_attention(_kv8), emmax_op_rope_kv_write_at, emmax_extend_attn_plan): new symbols only, the workspace
- *   grew one int32 per decode row. */
+ *   grew one int32 per decode row; still 12: taps -- hidden states and attention maps out of the passes (emmax_session_set_pass_taps,
+ *   emmax_session_set_step_taps, emmax_session_clear_taps, emmax_session_taps, emmax_op_attn_probs(_kv8), emmax_op_tap_rows): new symbols only, the
+ *   workspace did not grow. */
 #define EMMAX_ABI_VERSION 12
 
 typedef enum emmax_status {
@@ -765,6 +767,49 @@ int emmax_op_rope_kv_write_at(void* qkv_dev, int ld, int q_off, int k_off, int v
                               int max_pages, int Hq, int Hkv, int head_dim, int page, emmax_stream stream);
 int emmax_extend_attn_plan(int B, int max_n, int max_L, int Hq, int Hkv, int nsplit, int kv8, int* G_out, int* tokens_per_block_out, int* query_tiles_out,
                            int* nsplit_out, int* split_form_out);
+/* TAPS: HF's output_hidden_states / output_attentions out of the fused path.  A tap is a caller-owned fp32 device buffer that the session fills while
+ * it runs a pass it would run anyway; a session that binds nothing launches exactly what it launched before.
+ * hidden_layers: bit i (0 <= i <= n_layers) selects HF's hidden_states[i] -- bit 0 the rows behind the embed / patch splice, bit i the residual stream
+ * behind layer i's down projection, bit n_layers that of the last layer NORMED (final norm, fp32: HF's last entry is norm(h_L)).  attn_layers: bit i
+ * selects layer i's map softmax(q k^T / sqrt(d)) over the row's keys, exact zeros behind them up to ld_keys.  n_sel = the set bits, lowest first.
+ * emmax_session_set_pass_taps: filled by the NEXT prefill (emmax_prefill / emmax_prefill_text) or emmax_extend over its packed rows -- hidden_dev
+ * [n_sel][total_rows][H], attn_dev [n_sel][total_rows][Hq][ld_keys] -- consumed by that pass and unbound after it.
+ * emmax_session_set_step_taps (after a prefill: the buffers' batch B is that of the live rows): filled by every decode step that follows, eager or
+ * replayed -- hidden_dev [max_new][n_sel][B][H], attn_dev [max_new][n_sel][B][Hq][ld_keys], a row's entry in the slot of its generation index (the
+ * n_out of emmax_session_set_scores: the step that emits token t fills slot t, t >= 1; slot 0 is the prefill's and stays untouched); rows that are done
+ * write nothing.  max_new = 1 is the single-step form: every live row lands in slot 0.  During a step ctx_len[b] is the row's cached length before the
+ * step = the position of its token: the map covers ctx_len + 1 keys.  Unbound by the next prefill or emmax_extend.
+ * A buffer and its mask go together; all NULL / 0 unbinds; emmax_session_clear_taps unbinds both; emmax_session_taps: bit 0 pass taps, bit 1 step
+ * taps, -1 for NULL.  Binding or unbinding step taps re-captures the step's graph.  EMMAX_ERR_INVALID: a bit above n_layers (hidden) / n_layers - 1
+ * (attentions), ld_keys not a multiple of 4 or smaller than the keys a row sees (checked where the lengths are known: by the pass for pass taps,
+ * which then fails before it launches anything; at the binding for step taps), max_new outside 1..max_ctx, head_dim != 128 or a GQA group outside
+ * {1, 2, 4, 8} with a map.  EMMAX_ERR_STATE: exact-numerics sessions, beams on, sample groups on, request slots open, step taps before a prefill.  A
+ * refused call changes nothing.  emmax_slots_open, emmax_session_set_beams and emmax_session_set_sample_groups UNBIND whatever is bound.
+ * What the session cannot check is the caller's: the buffers' SIZES.  A pass fills total_rows = the sum of the pass's row counts (patch rows included)
+ * and trusts the pass-tap buffers to hold that many; the step-tap buffers are trusted to hold max_new slots of the B live rows of the binding.  A
+ * decode step of another batch than that B (there is none between a binding and the prefill or emmax_extend that unbinds it, short of slot
+ * serving, which unbinds) writes NOTHING into the step taps rather than index rows the buffers do not have. */
+int emmax_session_set_pass_taps(emmax_session* s, float* hidden_dev, uint64_t hidden_layers, float* attn_dev, uint64_t attn_layers, int ld_keys, emmax_stream stream);
+int emmax_session_set_step_taps(emmax_session* s, float* hidden_dev, uint64_t hidden_layers, float* attn_dev, uint64_t attn_layers, int ld_keys, int max_new,
+                                emmax_stream stream);
+int emmax_session_clear_taps(emmax_session* s, emmax_stream stream);
+int emmax_session_taps(const emmax_session* s);
+/* Taps (taps.hip): the kernels that hand the residual stream and the attention maps out as fp32, as pure ops.
+ * emmax_op_attn_probs(_kv8): for the sequences of emmax_op_extend_attention (q_dev, cu_dev, base_dev, the page table and the K cache as there; no V)
+ * the fp32 rows softmax(scale q . K^T): probs_dev f32 [total_rows][Hq][ld_keys], row i of sequence b holds its probabilities at keys 0 .. base[b] + i
+ * and EXACT ZEROS from there to ld_keys - 1 -- every entry of every row is written, the caller does not clear the buffer; nothing past total_rows is
+ * touched.  Two passes over the keys (maximum and fp32 sum; then fl(2^(fl(s c - m c)) x fl(1 / l)), c = fl(scale log2 e)).  ld_keys: a multiple of 4,
+ * at least the keys any row sees (checked against the lengths read back: EMMAX_ERR_INVALID); probs_dev 16-byte aligned; head_dim 128, page 64, GQA
+ * group in {1, 2, 4, 8}, B <= 64.  The launch dispatches on the GQA group and the cache format alone: there is no plan to ask for.
+ * emmax_op_tap_rows: rows x H of src_dev (fp32 rows when src_f32, else bf16; row pitch ld_src elements) into dst_dev f32 [rows][H]; norm_w_dev (bf16
+ * [H], may be NULL): the RMSNorm of each row in fp32, y = fl(fl(x rstd) w) with rstd = rsqrt(sum x^2 / H + eps).  H % 8 == 0, 16-byte aligned. */
+int emmax_op_attn_probs(const void* q_dev, int ldq, int q_off, const void* kcache_dev, const int32_t* page_table_dev, const int32_t* cu_dev,
+                        const int32_t* base_dev, int B, int total_rows, int Hq, int Hkv, int page, int max_pages, float scale, float* probs_dev, int ld_keys,
+                        emmax_stream stream);
+int emmax_op_attn_probs_kv8(const void* q_dev, int ldq, int q_off, const void* kcache8_dev, const float* kscale_dev, const int32_t* page_table_dev,
+                            const int32_t* cu_dev, const int32_t* base_dev, int B, int total_rows, int Hq, int Hkv, int page, int max_pages, float scale,
+                            float* probs_dev, int ld_keys, emmax_stream stream);
+int emmax_op_tap_rows(const void* src_dev, int src_f32, int ld_src, float* dst_dev, int rows, int H, const void* norm_w_dev, float eps, emmax_stream stream);
 /* Decode-path weight-streaming GEMV: y[b,n] = sum_k x[b,k] W[n,k]  (bf16 in, fp32 accumulate, bf16 out), B <= 8. */
 int emmax_op_gemv(const void* x_dev, const void* W_dev, void* y_dev, int B, int N, int K, emmax_stream stream);
 
