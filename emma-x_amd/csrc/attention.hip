@@ -844,44 +844,80 @@ static int launch_attention_resident(const AttnParams& p, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
-int launch_attention(const AttnParams& p, int head_dim, hipStream_t stream) {
-    if (p.B <= 0 || p.max_seqlen <= 0) return 0;
-    if (p.Hq % p.Hkv != 0) return -1;
-    if ((p.ld_qkv % 8) || (p.q_off % 8) || (p.k_off % 8) || (p.v_off % 8) || (p.ld_out % 4)) return -1;
-    if (p.ld_qkv >= (1 << 19)) return -1;   // the ring kernel packs a lane's source byte offset inside a row into 20 bits (d_pk)
+// The instantiation a launch takes, from the shape and the tuning switches alone (host only; emmax_attention_plan prints it).  launch_attention
+// dispatches on this struct: it launches the one instantiation whose compile-time constants EQUAL the struct's fields, so what the plan
+// says and what runs cannot differ.  false = a shape the launcher refuses.
+bool attention_form(int B, int max_seqlen, int Hq, int Hkv, int head_dim, int causal, AttnForm* f) {
+    if (B < 1 || max_seqlen < 1 || Hq < 1 || Hkv < 1 || Hq % Hkv != 0) return false;
+    if (head_dim != 64 && head_dim != 72 && head_dim != 128) return false;
     const int force = emmax_tune().attn_resident;   // -1 default; 0 never; 2 = whenever it fits (tests)
-    const bool no_resident = force == 0;
     // short non-causal sequences with enough (sequence, head) items to keep persistent blocks busy: the resident form (see
     // above).  Thresholds from tools/attn_lab.hip and the in-situ kernel trace: head_dim 64 wins from 32 frames on (190 vs 229 us
     // at 256 frames), head_dim 72 -- no room for the pipelined step -- only at the largest batches (174 vs 182 us in situ)
-    const int items = p.B * p.Hq;
-    if (!p.causal && !no_resident) {
-        const bool big64 = force == 2 ? items >= 8 : items >= 512, big72 = force == 2 ? items >= 8 : items >= 2048;
-        if (head_dim == 64 && big64 && p.max_seqlen <= 256) return launch_attention_resident<ResCfg<64, 8, 2>>(p, stream);
-        if (head_dim == 64 && big64 && p.max_seqlen <= 288) return launch_attention_resident<ResCfg<64, 9, 2>>(p, stream);
-        if (head_dim == 72 && big72 && p.max_seqlen <= 256) return launch_attention_resident<ResCfg<72, 8, 2>>(p, stream);
+    const int items = B * Hq;
+    if (!causal && force != 0 && head_dim != 128) {
+        const bool big = force == 2 ? items >= 8 : items >= (head_dim == 64 ? 512 : 2048);
+        if (big && max_seqlen <= (head_dim == 64 ? 288 : 256)) {
+            const int nw = max_seqlen <= 256 ? 8 : 9;      // 256 / 288 resident rows; every resident form has the lazy maximum
+            *f = AttnForm{1, head_dim, nw, 2, 1, 1, nw * 32};
+            return true;
+        }
     }
     // Block shape: 4 waves (128 queries) unless 3 waves (96) waste fewer padded query rows -- DINOv2's 261 tokens are 3 x 96 - 27
     // against 3 x 128 - 123.  One 32-query block per wave and 2-4 light blocks per CU measured best on all three head sizes
     // (tools/attn_probe.py; two query blocks per wave halve the LDS fragment reads but need ~250 registers and lose to spills /
     // occupancy; deeper LDS rings and 8-wave blocks changed nothing: the loop is bound by its VALU softmax work, not by DMA latency).
-    const bool three = cdiv(p.max_seqlen, 96) * 96 < cdiv(p.max_seqlen, 128) * 128;
-    //                                            HD  NW QB NBUF blocks/CU
-    switch (head_dim) {
-        case 64: return three ? launch_attention_t<AttnCfg<64, 3, 1, 2, 4>>(p, stream) : launch_attention_t<AttnCfg<64, 4, 1, 2, 3>>(p, stream);
-        case 72: return three ? launch_attention_t<AttnCfg<72, 3, 1, 2, 4>>(p, stream) : launch_attention_t<AttnCfg<72, 4, 1, 2, 3>>(p, stream);
-        case 128: {
-            // an under-filled causal launch (one frame's prefill: 6 chunks x 32 heads = 192 blocks) lasts as long as its heaviest block:
-            // two key groups per block halve that chain (AttnCfg::KSPL; tuning switch attn_ksplit: -1 = when the grid leaves at most one
-            // block per CU, 0 never, 1 every causal head_dim-128 launch).  Measured: profiles/r05_attn_ksplit_ab.txt
-            const int sw = emmax_tune().attn_ksplit;
-            const int blocks = 8 * cdiv(p.B * p.Hq, 8) * cdiv(p.max_seqlen, 128);
-            if (p.causal && (sw == 1 || (sw < 0 && blocks <= 256))) return launch_attention_t<AttnCfg<128, 8, 1, 2, 1, 2>>(p, stream);
-            // attn_lazy = 0 (tools/regress_bits.py): the running maximum of rounds 1-4 -- with attn_ksplit = 0 as well this launch reproduces the
-            // round-4 kernel bit for bit
-            if (emmax_tune().attn_lazy == 0) return launch_attention_t<AttnCfg<128, 4, 1, 2, 2, 1, false>>(p, stream);
-            return launch_attention_t<AttnCfg<128, 4, 1, 2, 2>>(p, stream);
-        }
-        default: return -1;
+    if (head_dim != 128) {
+        const int nw = cdiv(max_seqlen, 96) * 96 < cdiv(max_seqlen, 128) * 128 ? 3 : 4;
+        *f = AttnForm{0, head_dim, nw, 0, 1, 0, nw * 32};
+        return true;
     }
+    // an under-filled causal launch (one frame's prefill: 6 chunks x 32 heads = 192 blocks) lasts as long as its heaviest block:
+    // two key groups per block halve that chain (AttnCfg::KSPL; tuning switch attn_ksplit: -1 = when the grid leaves at most one
+    // block per CU, 0 never, 1 every causal head_dim-128 launch).  Measured: profiles/r05_attn_ksplit_ab.txt
+    const int sw = emmax_tune().attn_ksplit;
+    const int blocks = 8 * cdiv(B * Hq, 8) * cdiv(max_seqlen, 128);
+    if (causal && (sw == 1 || (sw < 0 && blocks <= 256))) {
+        *f = AttnForm{0, 128, 4, 0, 2, 1, 128};
+        return true;
+    }
+    // attn_lazy = 0 (tools/regress_bits.py): the running maximum of rounds 1-4 -- with attn_ksplit = 0 as well this launch reproduces the
+    // round-4 kernel bit for bit
+    *f = AttnForm{0, 128, 4, 0, 1, emmax_tune().attn_lazy == 0 ? 0 : 1, 128};
+    return true;
+}
+
+template <class DM>
+static bool ring_is(const AttnForm& f) {
+    return !f.resident && f.head_dim == DM::HD && f.qwaves == DM::NQW && f.pwaves == 0 && f.kgroups == DM::KSPL && f.lazy == (DM::LZ ? 1 : 0) &&
+           f.rows == DM::QCH;
+}
+template <class RC>
+static bool resident_is(const AttnForm& f) {
+    return f.resident && f.head_dim == RC::HD && f.qwaves == RC::NW && f.pwaves == RC::NP && f.kgroups == 1 && f.lazy == 1 && f.rows == RC::ROWS;
+}
+
+int launch_attention(const AttnParams& p, int head_dim, hipStream_t stream) {
+    if (p.B <= 0 || p.max_seqlen <= 0) return 0;
+    if ((p.ld_qkv % 8) || (p.q_off % 8) || (p.k_off % 8) || (p.v_off % 8) || (p.ld_out % 4)) return -1;
+    if (p.ld_qkv >= (1 << 19)) return -1;   // the ring kernel packs a lane's source byte offset inside a row into 20 bits (d_pk)
+    AttnForm f;
+    if (!attention_form(p.B, p.max_seqlen, p.Hq, p.Hkv, head_dim, p.causal, &f)) return -1;
+    // the ten instantiations: the one that IS the form runs
+#define EMMAX_ATTN_RESIDENT(...) if (resident_is<ResCfg<__VA_ARGS__>>(f)) return launch_attention_resident<ResCfg<__VA_ARGS__>>(p, stream)
+#define EMMAX_ATTN_RING(...) if (ring_is<AttnCfg<__VA_ARGS__>>(f)) return launch_attention_t<AttnCfg<__VA_ARGS__>>(p, stream)
+    EMMAX_ATTN_RESIDENT(64, 8, 2);
+    EMMAX_ATTN_RESIDENT(64, 9, 2);
+    EMMAX_ATTN_RESIDENT(72, 8, 2);
+    //              HD  NW QB NBUF blocks/CU [key groups, lazy]
+    EMMAX_ATTN_RING(64, 3, 1, 2, 4);
+    EMMAX_ATTN_RING(64, 4, 1, 2, 3);
+    EMMAX_ATTN_RING(72, 3, 1, 2, 4);
+    EMMAX_ATTN_RING(72, 4, 1, 2, 3);
+    EMMAX_ATTN_RING(128, 8, 1, 2, 1, 2);
+    EMMAX_ATTN_RING(128, 4, 1, 2, 2, 1, false);
+    EMMAX_ATTN_RING(128, 4, 1, 2, 2);
+#undef EMMAX_ATTN_RESIDENT
+#undef EMMAX_ATTN_RING
+    return -1;
 }

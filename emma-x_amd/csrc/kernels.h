@@ -81,6 +81,11 @@ struct AttnParams {
     float scale;
     int causal;
 };
+// the instantiation launch_attention takes (it dispatches on this struct; emmax_attention_plan prints it): the resident or the ring kernel, query
+// waves, producer waves (resident), key groups over the same query waves (AttnCfg::KSPL), the lazy reference maximum, query rows per block (ring) /
+// resident rows per item.  Host only, from the shape and the tuning switches attn_resident / attn_ksplit / attn_lazy.  false = a shape refused
+struct AttnForm { int resident, head_dim, qwaves, pwaves, kgroups, lazy, rows; };
+bool attention_form(int B, int max_seqlen, int Hq, int Hkv, int head_dim, int causal, AttnForm* f);
 int launch_attention(const AttnParams& p, int head_dim, hipStream_t stream);
 int launch_x_attention(const AttnParams& p, int head_dim, hipStream_t stream);   // exact.hip: fp32 q / k / v rows in, HL rows out, fp32 MFMA
 

@@ -251,6 +251,20 @@ int emmax_op_decode_attention_kv8(const void* q, void* kcache8, void* vcache8, f
     if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_decode_attention_kv8: unsupported (GQA group in {1,2,4,8}, page = 2^k, max_pages <= 512, nsplit = 2^k)");
     return 0;
 }
+// ---- the form of the prefill / ViT attention, host only (attention.hip: attention_form -- what launch_attention dispatches on) ----
+int emmax_attention_plan(int B, int max_seqlen, int Hq, int Hkv, int head_dim, int causal, int* resident_out, int* query_waves_out, int* producer_waves_out,
+                         int* key_groups_out, int* lazy_out, int* rows_out) {
+    AttnForm f;
+    if (!attention_form(B, max_seqlen, Hq, Hkv, head_dim, causal ? 1 : 0, &f))
+        return fail(EMMAX_ERR_INVALID, "emmax_attention_plan: unsupported (B >= 1, max_seqlen >= 1, Hq a multiple of Hkv, head_dim in {64, 72, 128})");
+    if (resident_out) *resident_out = f.resident;
+    if (query_waves_out) *query_waves_out = f.qwaves;
+    if (producer_waves_out) *producer_waves_out = f.pwaves;
+    if (key_groups_out) *key_groups_out = f.kgroups;
+    if (lazy_out) *lazy_out = f.lazy;
+    if (rows_out) *rows_out = f.rows;
+    return 0;
+}
 // ---- the forms of the decode attention, host only (decode_attn.hip: decode_attn_form / group_attn_form -- what the launchers dispatch on) ----
 static void attn_plan_operands(DecodeAttnParams& a, int Hq, int Hkv, int direct, int kv8) {
     void* const any = (void*)(uintptr_t)256;   // the form looks at which operands exist -- never through a pointer

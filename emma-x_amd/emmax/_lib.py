@@ -112,6 +112,7 @@ SIGNATURES = {
     "emmax_op_decode_attention_group": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _vp, _vp, _vp]),
     "emmax_op_decode_attention_group_kv8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                       _vp, C.c_float, _vp]),
+    "emmax_attention_plan": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int)] * 6),
     "emmax_decode_attn_plan": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int)] * 5),
     "emmax_group_attn_plan": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int)] * 4),
     "emmax_extend": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _c_i32p, C.c_int, C.c_int, _vp]),

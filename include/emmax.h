@@ -690,6 +690,17 @@ int emmax_op_rmsnorm(const void* x_dev, void* y_dev, const void* w_dev, int rows
 int emmax_op_attention(const void* qkv_dev, int ld_qkv, int q_off, int k_off, int v_off, void* out_dev, int ld_out,
                        const int32_t* cu_seqlens_dev, int B, int max_seqlen, int Hq, int Hkv, int head_dim, float scale,
                        int causal, emmax_stream stream);
+/* Which instantiation emmax_op_attention (and every ViT block / prefill layer of a session) launches for B sequences of at most max_seqlen
+ * tokens -- HOST ONLY, launches nothing and needs no device; the launcher dispatches on the very struct this call fills (attention.hip:
+ * attention_form), so the answer cannot differ from the launch.  Outputs (any may be NULL): resident 0 / 1 (the ring kernel: 64-key tiles through
+ * a double-buffered LDS ring, one block per query chunk; the resident kernel: an item's whole K / V in LDS, persistent blocks -- short non-causal
+ * head_dim 64 / 72 sequences, from 512 / 2048 (sequence, head) items and up to 256 / 288 / 256 tokens; tuning switch attn_resident: 0 never, 2
+ * from 8 items), the query waves of a block (3 / 4: whichever wastes fewer padded query rows of max_seqlen; resident 8 / 9), the producer waves
+ * (resident: 2), the key groups over the same query waves (2: causal head_dim 128 when the grid leaves at most one block per CU; attn_ksplit 0
+ * never / 1 always), the lazy reference maximum 0 / 1 (head_dim 128 unless attn_lazy = 0, and every resident form), and the query rows of a block
+ * (resident: the rows an item may hold).  EMMAX_ERR_INVALID: what the launcher refuses for these arguments (B < 1 or max_seqlen < 1 launch nothing). */
+int emmax_attention_plan(int B, int max_seqlen, int Hq, int Hkv, int head_dim, int causal, int* resident_out, int* query_waves_out,
+                         int* producer_waves_out, int* key_groups_out, int* lazy_out, int* rows_out);
 /* Split-KV decode attention over a paged cache (the kernel of emmax_decode_step; HF cached attention at q_len = 1,
  * modeling_prismatic.py:325-341): row b attends to keys 0..ctx_len_dev[b] (inclusive: the key appended by this step's qkv
  * kernel sits at position ctx_len[b]).  q: bf16 [B, Hq*128] rotated queries; k/vcache: bf16 [n_pages][Hkv][page][128];

@@ -199,6 +199,24 @@ def test_decode_attention_plans_of_the_benchmark_steps(lib):
     assert so.emmax_group_attn_plan(7, 2, 32, 32, 0, None, None, None, None) == -1 and b"emmax_group_attn_plan" in so.emmax_last_error()
 
 
+def test_attention_plans_of_the_session_shapes(lib):
+    """emmax_attention_plan (host only; tests/test_attention_plan.py holds the full tables): one frame's DINOv2 and SigLIP blocks take the ring kernel
+    with three / four query waves, 256 frames the resident kernel (288 / 256 rows, two producer waves), one frame's causal prefill two key groups."""
+    import ctypes as C
+
+    _, so = lib
+    o = [C.c_int() for _ in range(6)]
+
+    def plan(*shape):
+        assert so.emmax_attention_plan(*shape, *[C.byref(x) for x in o]) == 0
+        return tuple(x.value for x in o)   # (resident, query waves, producer waves, key groups, lazy, rows)
+
+    assert plan(1, 261, 16, 16, 64, 0) == (0, 3, 0, 1, 0, 96) and plan(1, 256, 16, 16, 72, 0) == (0, 4, 0, 1, 0, 128)
+    assert plan(256, 261, 16, 16, 64, 0) == (1, 9, 2, 1, 1, 288) and plan(256, 256, 16, 16, 72, 0) == (1, 8, 2, 1, 1, 256)
+    assert plan(1, 768, 32, 32, 128, 1) == (0, 4, 0, 2, 1, 128) and plan(8, 768, 32, 32, 128, 1) == (0, 4, 0, 1, 1, 128)
+    assert so.emmax_attention_plan(1, 261, 16, 16, 80, 0, None, None, None, None, None, None) == -1 and b"emmax_attention_plan" in so.emmax_last_error()
+
+
 def test_gemm_launch_plans_of_the_hot_path(lib):
     """emmax_gemm_plan (host only): the launch plans of the GEMM shapes of the hot path, pinned -- one-frame prefill (M = 768: gate/up =
     one round of 256x256 tiles + a K-split column remainder, qkv one under-filled round, o / down K-split with the RMSNorm in the reduce
