@@ -419,9 +419,9 @@ __global__ __launch_bounds__(EMMAX_WAVE) void emmax_group_fork_kernel(GroupForkP
     if (tid == 0) p.grp_shared[g] = min(nfull, mp);
     for (int j = tid; j < N; j += EMMAX_WAVE) {
         const int r = r0 + j;
-        p.ctx_len[r] = L; p.done[r] = 0; p.n_out[r] = 0;
-        p.max_new[r] = 0x7fffffff;   // (as emmax_prefill_state_kernel: no token budget until a generate call sets one)
-        p.stop_m[r] = 0; p.stop_after[r] = -1;
+        p.st.ctx_len[r] = L; p.st.done[r] = 0; p.st.n_out[r] = 0;
+        p.st.max_new[r] = 0x7fffffff;   // (as emmax_prefill_state_kernel: no token budget until a generate call sets one)
+        p.st.stop_m[r] = 0; p.st.stop_after[r] = -1;
         const bool cp = rem > 0 && j > 0 && nfull < mp;
         p.copy_src[r] = cp ? r0 * mp + nfull : -1;
         p.copy_dst[r] = r * mp + nfull;

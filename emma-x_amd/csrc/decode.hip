@@ -704,15 +704,14 @@ __global__ __launch_bounds__(256) void emmax_decode_finish_kernel(FinishParams p
 
 // caller-supplied continuation (teacher forcing / the HF cached forward step): the row decodes again whatever the engine's own
 // greedy prediction was -- clear the done flag and the stop-rule state, lift the token budget
-__global__ void emmax_set_tokens_kernel(int32_t* cur_tok, const int32_t* toks, int B, int32_t* done, int32_t* stop_m, int32_t* stop_after,
-                                        int32_t* max_new, int budget) {
+__global__ void emmax_set_tokens_kernel(RowState r, const int32_t* toks, int B, int budget) {
     const int i = threadIdx.x;
     if (i < B) {
-        cur_tok[i] = toks[i];
-        done[i] = 0;
-        stop_m[i] = 0;
-        stop_after[i] = -1;
-        max_new[i] = budget;
+        r.cur_tok[i] = toks[i];
+        r.done[i] = 0;
+        r.stop_m[i] = 0;
+        r.stop_after[i] = -1;
+        r.max_new[i] = budget;
     }
 }
 
@@ -860,9 +859,8 @@ int launch_decode_finish(const FinishParams& p_in, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
-int launch_set_tokens(int32_t* cur_tok, const int32_t* toks, int B, int32_t* done, int32_t* stop_m, int32_t* stop_after, int32_t* max_new,
-                      int budget, hipStream_t stream) {
-    hipLaunchKernelGGL(emmax_set_tokens_kernel, dim3(1), dim3(64), 0, stream, cur_tok, toks, B, done, stop_m, stop_after, max_new, budget);
+int launch_set_tokens(const RowState& rows, const int32_t* toks, int B, int budget, hipStream_t stream) {
+    hipLaunchKernelGGL(emmax_set_tokens_kernel, dim3(1), dim3(64), 0, stream, rows, toks, B, budget);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

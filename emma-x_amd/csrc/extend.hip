@@ -24,8 +24,8 @@ int run_extend(emmax_session* s, int r0, int B, const int32_t* ids, const int32_
     if ((int)s->S.size() < s->rows_total) s->S.resize(s->rows_total, 0);
     // the rows' cached lengths (and, for a slot, whether its request has finished), read back once: the call is not part of a captured step
     int32_t ctx[EMMAX_MAX_DECODE_BATCH], done[EMMAX_MAX_DECODE_BATCH];
-    HIPCHK(hipMemcpyAsync(ctx, s->ctx_len + r0, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(done, s->done + r0, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(ctx, s->rows.ctx_len + r0, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(done, s->rows.done + r0, (size_t)B * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     PrefillState ps;
     ps.B = B;
@@ -53,8 +53,8 @@ int run_extend(emmax_session* s, int r0, int B, const int32_t* ids, const int32_
     while (plan.nsplit > 1 && (int64_t)total * c.n_heads * plan.nsplit * EMMAX_PSTRIDE * 4 > s->splitk_bytes) plan.nsplit -= 1;
     plan.split = plan.nsplit > 1 ? 1 : 0;
 
-    KCHK(launch_extend_state(ps, s->cu, s->ext_base, s->ctx_len + r0, s->done + r0, s->n_out + r0, s->max_new_d + r0, s->stop_m + r0, s->stop_after + r0,
-                             s->aut.on ? s->aut.state + r0 : nullptr, s->aut.on ? s->aut.start + r0 : nullptr, st));
+    KCHK(launch_extend_state(ps, s->cu, s->ext_base, s->rows.from(r0, s->max_out), s->aut.on ? s->aut.state + r0 : nullptr,
+                             s->aut.on ? s->aut.start + r0 : nullptr, st));
     if (s->scores.on && !slot) {   // the score buffers' rows, as a prefill binds them: the first pass after the binding's; another batch size unbinds them
         if (s->scores.rows == 0) {
             s->scores.rows = B;
@@ -100,7 +100,7 @@ int emmax_slot_extend(emmax_session* s, int slot, const int32_t* ids, int len, i
     StreamScope sc(s, stream);
     if (sc.error()) return sc.error();
     if (int r = run_extend(s, slot, 1, ids, &len, len, max_new, true, sc.stream())) return r;
-    KCHK(launch_set_ints(s->max_new_d + slot, 1, max_new, sc.stream()));
+    KCHK(launch_set_ints(s->rows.max_new + slot, 1, max_new, sc.stream()));
     s->slot_fresh[slot] = s->samp.on ? 1 : 0;   // (sampling on: the extension left its last row's logits in the slot's own row, as a slot prefill does)
     s->slot_stg_idx[slot] = -1;
     return sc.leave();
@@ -111,7 +111,7 @@ int emmax_session_context(emmax_session* s, int row0, int n, int32_t* ctx_out_ho
     if (n < 1 || row0 < 0 || row0 + n > s->rows_total) return fail(EMMAX_ERR_INVALID, "emmax_session_context: rows %d..%d outside 0..%d", row0, row0 + n - 1, s->rows_total - 1);
     StreamScope sc(s, stream);
     if (sc.error()) return sc.error();
-    HIPCHK(hipMemcpyAsync(ctx_out_host, s->ctx_len + row0, (size_t)n * 4, hipMemcpyDeviceToHost, sc.stream()));
+    HIPCHK(hipMemcpyAsync(ctx_out_host, s->rows.ctx_len + row0, (size_t)n * 4, hipMemcpyDeviceToHost, sc.stream()));
     HIPCHK(hipStreamSynchronize(sc.stream()));
     return sc.leave();
 }

@@ -118,21 +118,20 @@ __global__ __launch_bounds__(256) void emmax_kv_quant_rows_at_kernel(const bf16_
 // cached length before, cu = the packed offsets of the new rows, ctx_len += the new rows; done / n_out / token budget / stop match as a prefill
 // leaves them.  aut_state / aut_start (an automaton is set, else null): a row keeps its state; one outside the automaton (state -1) enters at its
 // start state.  Pointers already offset to the first row
-__global__ void emmax_extend_state_kernel(PrefillState st, int32_t* cu, int32_t* base, int32_t* ctx_len, int32_t* done, int32_t* n_out, int32_t* max_new,
-                                          int32_t* stop_m, int32_t* stop_after, int32_t* aut_state, const int32_t* aut_start) {
+__global__ void emmax_extend_state_kernel(PrefillState st, int32_t* cu, int32_t* base, RowState r, int32_t* aut_state, const int32_t* aut_start) {
     if (threadIdx.x == 0) {
         int acc = 0;
         cu[0] = 0;
         for (int b = 0; b < st.B; ++b) {
             acc += st.S[b];
             cu[b + 1] = acc;
-            base[b] = ctx_len[b];
-            ctx_len[b] += st.S[b];
-            done[b] = 0;
-            n_out[b] = 0;
-            max_new[b] = 0x7fffffff;   // no token budget until a generate / slot call sets one
-            stop_m[b] = 0;
-            stop_after[b] = -1;
+            base[b] = r.ctx_len[b];
+            r.ctx_len[b] += st.S[b];
+            r.done[b] = 0;
+            r.n_out[b] = 0;
+            r.max_new[b] = 0x7fffffff;   // no token budget until a generate / slot call sets one
+            r.stop_m[b] = 0;
+            r.stop_after[b] = -1;
             if (aut_state && aut_state[b] < 0) aut_state[b] = aut_start[b];
         }
     }
@@ -457,11 +456,10 @@ int launch_kv_quant_rows_at(const void* qkv, int ld, int k_off, int v_off, const
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
-int launch_extend_state(const PrefillState& st, int32_t* cu, int32_t* base, int32_t* ctx_len, int32_t* done, int32_t* n_out, int32_t* max_new, int32_t* stop_m,
-                        int32_t* stop_after, int32_t* aut_state, const int32_t* aut_start, hipStream_t stream) {
+int launch_extend_state(const PrefillState& st, int32_t* cu, int32_t* base, const RowState& rows, int32_t* aut_state, const int32_t* aut_start,
+                        hipStream_t stream) {
     if (st.B < 1 || st.B > EMMAX_MAX_DECODE_BATCH || (aut_state && !aut_start)) return -1;
-    hipLaunchKernelGGL(emmax_extend_state_kernel, dim3(1), dim3(64), 0, stream, st, cu, base, ctx_len, done, n_out, max_new, stop_m, stop_after, aut_state,
-                       aut_start);
+    hipLaunchKernelGGL(emmax_extend_state_kernel, dim3(1), dim3(64), 0, stream, st, cu, base, rows, aut_state, aut_start);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

@@ -57,7 +57,7 @@ int emmax_set_current_tokens(emmax_session* s, const int32_t* toks, emmax_stream
     for (int b = 0; b < s->cur_B && b < (int)s->S.size(); ++b) maxS = std::max(maxS, s->S[b]);
     if (maxS + s->dec_steps + 1 >= s->max_ctx)
         return fail(EMMAX_ERR_NOMEM, "context %d + 1 reaches max_ctx %d: no room to decode a caller-supplied token", maxS + s->dec_steps, s->max_ctx);
-    KCHK(launch_set_tokens(s->cur_tok, toks, s->cur_B, s->done, s->stop_m, s->stop_after, s->max_new_d, s->max_out, (hipStream_t)st));
+    KCHK(launch_set_tokens(s->rows, toks, s->cur_B, s->max_out, (hipStream_t)st));
     return 0;
 }
 
@@ -79,7 +79,7 @@ int emmax_generate(emmax_session* s, int max_new, int stop_on_eos, int32_t* out_
         const int rows = s->beam.G * s->beam.K, ld = std::min(s->max_batch, EMMAX_MAX_DECODE_BATCH);
         s->beam.eos = stop_on_eos ? s->m->cfg.eos_id : -1;
         s->beam.max_new = max_new;
-        KCHK(launch_set_ints(s->max_new_d, rows, max_new, st));
+        KCHK(launch_set_ints(s->rows.max_new, rows, max_new, st));
         KCHK(launch_beam_reset(rows, s->beam.K, s->beam.run, s->beam.fin_score, s->beam.fin_flag, s->beam.fin_t, s->beam.fin_par, s->beam.fin_tok, s->beam.grp,
                                s->beam.csrc, st));
         const size_t n1 = (size_t)max_new * ld * 4;
@@ -98,7 +98,7 @@ int emmax_generate(emmax_session* s, int max_new, int stop_on_eos, int32_t* out_
         s->beam.ready = false;
     }
     const int B = s->cur_B;
-    if (!s->beam.K) KCHK(launch_set_ints(s->max_new_d, B, max_new, st));
+    if (!s->beam.K) KCHK(launch_set_ints(s->rows.max_new, B, max_new, st));
     const bool use_graph = (max_new > 2) && ensure_graph(s, B, st) == 0;
     const int CHK = 16;
     int32_t* done_host = s->pinned->done;
@@ -113,7 +113,7 @@ int emmax_generate(emmax_session* s, int max_new, int stop_on_eos, int32_t* out_
                 for (int b = 0; b < B; ++b) all = all && (done_host[b] != 0);
                 if (all) { pending = false; break; }
             }
-            HIPCHK(hipMemcpyAsync(done_host, s->done, B * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(done_host, s->rows.done, B * 4, hipMemcpyDeviceToHost, st));
             HIPCHK(hipEventRecord(s->ev, st));
             pending = true;
         }
@@ -124,12 +124,12 @@ int emmax_generate(emmax_session* s, int max_new, int stop_on_eos, int32_t* out_
         q.rows = B; q.K = s->beam.K; q.max_out = s->max_out; q.max_new = max_new; q.tr_ld = std::min(s->max_batch, EMMAX_MAX_DECODE_BATCH);
         q.pad_id = s->m->cfg.pad_id;
         q.fin_t = s->beam.fin_t; q.fin_par = s->beam.fin_par; q.fin_tok = s->beam.fin_tok; q.tr_tok = s->beam.tr_tok; q.tr_par = s->beam.tr_par;
-        q.fin_score = s->beam.fin_score; q.seq = s->out_ids; q.bidx = s->beam.res_bidx; q.len = s->beam.res_len; q.score = s->beam.res_score;
+        q.fin_score = s->beam.fin_score; q.seq = s->rows.out_ids; q.bidx = s->beam.res_bidx; q.len = s->beam.res_len; q.score = s->beam.res_score;
         KCHK(launch_beam_resolve(q, st));
     }
-    HIPCHK(hipMemcpy2DAsync(out_ids, (size_t)max_new * 4, s->out_ids, (size_t)s->max_out * 4, (size_t)max_new * 4, B,
+    HIPCHK(hipMemcpy2DAsync(out_ids, (size_t)max_new * 4, s->rows.out_ids, (size_t)s->max_out * 4, (size_t)max_new * 4, B,
                             hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(out_lens, s->beam.K ? s->beam.res_len : s->n_out, B * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(out_lens, s->beam.K ? s->beam.res_len : s->rows.n_out, B * 4, hipMemcpyDeviceToDevice, st));
     return sc.leave();
 }
 
@@ -146,7 +146,7 @@ int emmax_slots_open(emmax_session* s, int n_slots, emmax_stream stream) {
     StreamScope sc(s, stream);
     if (sc.error()) return sc.error();
     if (int r = slots_restore_pages(s, sc.stream())) return r;   // a group still outstanding from the last serve
-    KCHK(launch_slots_idle(n_slots, s->cur_tok, s->ctx_len, s->done, s->n_out, s->m->cfg.pad_id, sc.stream()));
+    KCHK(launch_slots_idle(n_slots, s->rows, s->m->cfg.pad_id, sc.stream()));
     s->cur_B = n_slots;
     s->S.assign(s->rows_total, 0);
     std::fill(s->slot_fresh.begin(), s->slot_fresh.end(), 0);
@@ -168,7 +168,7 @@ int emmax_slot_prefill(emmax_session* s, int slot, const int32_t* ids, int len, 
     if (sc.error()) return sc.error();
     s->slot_fresh[slot] = 0; s->slot_stg_idx[slot] = -1;
     if (int r = run_prefill(s, ids, &len, 1, len, patches, sc.stream(), slot)) return r;
-    KCHK(launch_set_ints(s->max_new_d + slot, 1, max_new, sc.stream()));
+    KCHK(launch_set_ints(s->rows.max_new + slot, 1, max_new, sc.stream()));
     s->slot_fresh[slot] = s->samp.on ? 1 : 0;   // (sampling on: the prefill left the prompt's logit row in the slot's own)
     return sc.leave();
 }
@@ -187,7 +187,7 @@ int emmax_slots_prefill(emmax_session* s, int slot0, int n, const int32_t* ids, 
     if (sc.error()) return sc.error();
     for (int i = 0; i < n; ++i) { s->slot_fresh[slot0 + i] = 0; s->slot_stg_idx[slot0 + i] = -1; }
     if (int r = run_prefill(s, ids, lens_host, n, P_max, patches, sc.stream(), slot0)) return r;   // one packed pass over the n requests (ragged lengths)
-    for (int i = 0; i < n; ++i) KCHK(launch_set_ints(s->max_new_d + slot0 + i, 1, max_new_host[i], sc.stream()));
+    for (int i = 0; i < n; ++i) KCHK(launch_set_ints(s->rows.max_new + slot0 + i, 1, max_new_host[i], sc.stream()));
     for (int i = 0; i < n; ++i) s->slot_fresh[slot0 + i] = s->samp.on ? 1 : 0;
     return sc.leave();
 }
@@ -208,7 +208,7 @@ int emmax_slots_prefill_staged(emmax_session* s, int n, const int32_t* ids, int 
     s->stg_epoch += 1;   // the staging rows' logit rows are this batch's from here on
     s->stg_logits = s->samp.on;
     if (int r = run_prefill(s, ids, lens_host, n, P_max, patches, st, s->stg0)) return r;
-    for (int i = 0; i < n; ++i) KCHK(launch_set_ints(s->max_new_d + s->stg0 + i, 1, max_new_host[i], st));
+    for (int i = 0; i < n; ++i) KCHK(launch_set_ints(s->rows.max_new + s->stg0 + i, 1, max_new_host[i], st));
     return 0;
 }
 
@@ -227,33 +227,12 @@ int emmax_slots_commit(emmax_session* s, const int32_t* staged_idx_host, const i
         c.slot[i] = slots_host[i];
         c.src[i] = s->stg0 + staged_idx_host[i];
     }
-    c.n = n; c.max_pages = s->max_pages; c.max_out = s->max_out;
-    c.cur_tok = s->cur_tok; c.ctx_len = s->ctx_len; c.done = s->done; c.n_out = s->n_out; c.max_new = s->max_new_d;
-    c.stop_m = s->stop_m; c.stop_after = s->stop_after; c.out_ids = s->out_ids; c.page_table = s->page_table;
-    if (s->samp.on) {
-        c.temperature = s->samp.t; c.top_k = s->samp.k; c.top_p = s->samp.p; c.seed = s->samp.seed; c.subseq = s->samp.sub;
-        c.logprob = s->samp.logprob;
-    }
-    if (s->proc.on) {
-        c.penalty = s->proc.pen; c.ngram = s->proc.ng; c.min_new = s->proc.mn; c.hist = s->proc.hist; c.hist_len = s->proc.hist_len;
-        c.max_prompt = s->max_prompt;
-    }
-    if (s->warp.on) { c.warp[0] = s->warp.minp; c.warp[1] = s->warp.typ; c.warp[2] = s->warp.eps; c.warp[3] = s->warp.eta; }
-    if (s->rules.on) c.rule_en = s->rules.en;
-    if (s->aut.on) { c.aut_start = s->aut.start; c.aut_state = s->aut.state; }
+    c.n = n; c.max_pages = s->max_pages; c.page_table = s->page_table;
+    c.done = s->rows.done; c.ctx_len = s->rows.ctx_len;
+    if (int r = session_row_cols(s, &c.cols)) return r;   // the top-N entries a staged request has written move with it like everything else
     StreamScope sc(s, stream);
     if (sc.error()) return sc.error();
     KCHK(launch_slots_commit(c, sc.stream()));
-    for (int i = 0; i < n && s->toplp.on; ++i) {   // the request's written entries move with it: a staged request has entry 0 only
-        const TopLogprobs& t = s->toplp;
-        const size_t src = (size_t)c.src[i] * t.max_new, dst = (size_t)c.slot[i] * t.max_new;
-        if (t.n_top) {
-            HIPCHK(hipMemcpyAsync(t.ids_out + dst * t.n_top, t.ids_out + src * t.n_top, (size_t)t.n_top * 4, hipMemcpyDeviceToDevice, sc.stream()));
-            HIPCHK(hipMemcpyAsync(t.lp_out + dst * t.n_top, t.lp_out + src * t.n_top, (size_t)t.n_top * 4, hipMemcpyDeviceToDevice, sc.stream()));
-        }
-        if (t.n_watch)
-            HIPCHK(hipMemcpyAsync(t.watch_out + dst * t.n_watch, t.watch_out + src * t.n_watch, (size_t)t.n_watch * 4, hipMemcpyDeviceToDevice, sc.stream()));
-    }
     for (int i = 0; i < n; ++i) {
         const int slot = slots_host[i];
         s->S[slot] = s->S[s->stg0 + staged_idx_host[i]];
@@ -284,8 +263,8 @@ int emmax_slots_state(emmax_session* s, int32_t* done_out, int32_t* n_out_out, e
     if (!s->slots_open) return fail(EMMAX_ERR_STATE, "emmax_slots_state before emmax_slots_open");
     StreamScope sc(s, stream);
     if (sc.error()) return sc.error();
-    HIPCHK(hipMemcpyAsync(done_out, s->done, s->cur_B * 4, hipMemcpyDeviceToDevice, sc.stream()));
-    HIPCHK(hipMemcpyAsync(n_out_out, s->n_out, s->cur_B * 4, hipMemcpyDeviceToDevice, sc.stream()));
+    HIPCHK(hipMemcpyAsync(done_out, s->rows.done, s->cur_B * 4, hipMemcpyDeviceToDevice, sc.stream()));
+    HIPCHK(hipMemcpyAsync(n_out_out, s->rows.n_out, s->cur_B * 4, hipMemcpyDeviceToDevice, sc.stream()));
     return sc.leave();
 }
 
@@ -295,7 +274,7 @@ int emmax_slot_output(emmax_session* s, int slot, int32_t* ids_out, int n, emmax
     if (slot < 0 || slot >= s->cur_B || n < 0 || n > s->max_out) return fail(EMMAX_ERR_INVALID, "slot %d / %d ids out of range", slot, n);
     StreamScope sc(s, stream);
     if (sc.error()) return sc.error();
-    if (n > 0) HIPCHK(hipMemcpyAsync(ids_out, s->out_ids + (size_t)slot * s->max_out, (size_t)n * 4, hipMemcpyDeviceToDevice, sc.stream()));
+    if (n > 0) HIPCHK(hipMemcpyAsync(ids_out, s->rows.out_ids + (size_t)slot * s->max_out, (size_t)n * 4, hipMemcpyDeviceToDevice, sc.stream()));
     return sc.leave();
 }
 
@@ -305,7 +284,7 @@ int emmax_slot_release(emmax_session* s, int slot, emmax_stream stream) {
     if (slot < 0 || slot >= s->cur_B) return fail(EMMAX_ERR_INVALID, "slot %d outside 0..%d", slot, s->cur_B - 1);
     StreamScope sc(s, stream);
     if (sc.error()) return sc.error();
-    KCHK(launch_slots_idle(1, s->cur_tok + slot, s->ctx_len + slot, s->done + slot, s->n_out + slot, s->m->cfg.pad_id, sc.stream()));
+    KCHK(launch_slots_idle(1, s->rows.from(slot, s->max_out), s->m->cfg.pad_id, sc.stream()));
     s->S[slot] = 0;
     s->slot_fresh[slot] = 0; s->slot_stg_idx[slot] = -1;
     if (s->sg_gid[slot] >= 0) {   // a member of a group: a follower takes its hidden pages back; the owner takes its heir's and the heir owns the shared ones

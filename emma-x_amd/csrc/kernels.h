@@ -119,40 +119,51 @@ struct PrefillState {
     int B;
     int S[EMMAX_MAX_DECODE_BATCH];
 };
-// per-row decode state of B fresh sequences (pointers already offset to the first row / slot)
-int launch_prefill_state(const PrefillState& st, int32_t* cu, int32_t* ctx_len, int32_t* done, int32_t* n_out, int32_t* max_new,
-                         int32_t* stop_m, int32_t* stop_after, hipStream_t stream);
-// emmax_slots_commit: staging rows src[i] become slots slot[i]: per-row state and the output row copied, page-table rows swapped (the
-// slot's old pages become the staging row's)
-struct CommitParams {
-    int n, max_pages, max_out;
-    int slot[EMMAX_MAX_DECODE_BATCH], src[EMMAX_MAX_DECODE_BATCH];
-    int32_t *cur_tok, *ctx_len, *done, *n_out, *max_new, *stop_m, *stop_after, *out_ids, *page_table;
-    // sampling on (else all null): the rows' sampling parameters and their log-probability rows [][max_out] move with them
-    float *temperature, *top_p, *logprob;
-    int32_t* top_k;
-    uint64_t* seed;
-    uint32_t* subseq;
-    // logits processing on (else all null): the rows' processor parameters and prompt ids [][max_prompt] (+ their lengths) move too
-    float* penalty;
-    int32_t *ngram, *min_new, *hist, *hist_len;
-    int max_prompt;
-    // warpers / token rules on (else null): the rows' four warper values and their rule enable word move too
-    float* warp[4];
-    uint32_t* rule_en;
-    int32_t *aut_start, *aut_state;   // an automaton is set (else null): the rows' start and state move too
+// ROW STATE: the generation state every row of a session has (session.h: emmax_session::rows), one int32 per row and the output row
+struct RowState {
+    int32_t *cur_tok, *ctx_len, *done, *n_out, *max_new, *stop_m, *stop_after, *out_ids /* [rows][max_out] */;
+    RowState from(int r0, int max_out) const {   // host: the view from row r0 on
+        return {cur_tok + r0, ctx_len + r0, done + r0, n_out + r0, max_new + r0, stop_m + r0, stop_after + r0, out_ids + (size_t)r0 * max_out};
+    }
 };
+// ROW COLUMNS: a session's per-row device arrays as one list (session.hip: session_row_cols) -- row r of a column is the move_bytes bytes at
+// base + r * stride_bytes, both multiples of 4.  A staged commit moves every column of a row, a slot fork the `inherit` ones: an array that
+// is in the list cannot be forgotten by either
+enum { ROWS_CORE = 0, ROWS_SAMPLING, ROWS_PROCESSING, ROWS_WARPERS, ROWS_RULES, ROWS_AUTOMATON, ROWS_TOPLP };
+struct RowCol {
+    char* base;
+    uint32_t stride_bytes, move_bytes;
+    uint8_t owner, inherit;   // ROWS_*; a forked follower takes its source's
+};
+struct RowCols {
+    int n;
+    RowCol col[32];
+};
+// per-row decode state of B fresh sequences (rows: already the view from the first row / slot on)
+int launch_prefill_state(const PrefillState& st, int32_t* cu, const RowState& rows, hipStream_t stream);
+// emmax_slots_commit: staging rows src[i] become slots slot[i]: every column of the row copied, page-table rows swapped (the slot's old
+// pages become the staging row's), the staging row left done with an empty context
+struct CommitParams {
+    int n, max_pages;
+    int slot[EMMAX_MAX_DECODE_BATCH], src[EMMAX_MAX_DECODE_BATCH];
+    int32_t* page_table;
+    RowCols cols;
+    int32_t *done, *ctx_len;
+};
+static_assert(sizeof(CommitParams) <= 2048, "CommitParams travels as a kernel argument (4 KiB in all)");
 int launch_slots_commit(const CommitParams& c, hipStream_t stream);
 // emmax_slots_fork: the freshly prefilled slot `src` forked into the n idle slots dst[] (one block per follower).  Follower f hides its own
 // first nfull pages (hidden[f][i] = table[f][i]) and references the source's (table[f][i] = table[src][i]: the slot table is a permutation,
 // nothing here assumes the identity); from the prompt's partial page on it keeps its own pages, and entry j of the copy list names that
 // page's copy (launch_beam_copy consumes it: src = -1 where the prompt ends on a page boundary).  Fresh decode state as
-// emmax_group_fork_kernel leaves it, the source's token budget, the uploaded sampling parameters in_*[j], and with processing on the
-// source's processors and prompt ids
+// emmax_group_fork_kernel leaves it, the source's inherited columns (cols), the uploaded sampling parameters in_*[j], and with an
+// automaton set (aut_start, else both null) the source's start state as the follower's state
 struct SlotForkParams {
-    int n, rows, src, S, max_pages, max_prompt;
+    int n, rows, src, S, max_pages;
     int dst[EMMAX_MAX_DECODE_BATCH];
-    int32_t *page_table, *hidden, *ctx_len, *done, *n_out, *max_new, *stop_m, *stop_after, *copy_src, *copy_dst, *copy_ntok;
+    int32_t *page_table, *hidden, *copy_src, *copy_dst, *copy_ntok;
+    RowState st;
+    RowCols cols;
     const float *in_t, *in_p;
     const int32_t* in_k;
     const uint64_t* in_seed;
@@ -161,19 +172,16 @@ struct SlotForkParams {
     int32_t* top_k;
     uint64_t* seed;
     uint32_t* subseq;
-    float* penalty;   // processing on (else all null)
-    int32_t *ngram, *min_new, *hist, *hist_len;
-    float* warp[4];   // warpers / token rules on (else null): a follower takes the source's
-    uint32_t* rule_en;
-    int32_t *aut_start, *aut_state;   // an automaton is set (else null): a follower enters at the source's start state
+    int32_t *aut_start, *aut_state;
 };
+static_assert(sizeof(SlotForkParams) <= 2048, "SlotForkParams travels as a kernel argument (4 KiB in all)");
 int launch_slots_fork(const SlotForkParams& p, hipStream_t stream);
 // table[i] = hidden[i], hidden[i] = -1 wherever hidden[i] >= 0, i < n: a released follower takes its own pages back (its two rows), an
 // owner's slot takes its heir's (the owner's table row, the heir's hidden row), and every row at once when slot serving ends
 int launch_slots_unhide(int32_t* table, int32_t* hidden, int n, hipStream_t stream);
 int launch_set_int(int32_t* p, int32_t v, hipStream_t stream);
 int launch_set_ints(int32_t* p, int n, int32_t v, hipStream_t stream);
-int launch_slots_idle(int n, int32_t* cur_tok, int32_t* ctx_len, int32_t* done, int32_t* n_out, int32_t pad_id, hipStream_t stream);
+int launch_slots_idle(int n, const RowState& rows, int32_t pad_id, hipStream_t stream);
 int launch_embed_splice(const int32_t* ids, int P_max, const int32_t* cu, const void* E, const void* patches, void* h, int B,
                         int max_seqlen, int n_patches, int hidden, int vocab, hipStream_t stream, float* h32 = nullptr);   // h32: the rows also as fp32
 int launch_rope_kv_write(void* qkv, int ld, int q_off, int k_off, int v_off, const int32_t* cu, int B, int total_rows,
@@ -413,8 +421,8 @@ int launch_rope_kv_write_at(void* qkv, int ld, int q_off, int k_off, int v_off, 
                             int Hkv, int hd, int page, int max_pos, hipStream_t stream);
 // the rows' state when they grow by st.S[b] tokens: base[b] = ctx_len[b], cu = the packed offsets of the new rows, ctx_len += S; the rest as launch_prefill_state.
 // aut_state / aut_start (both or neither): a row outside the automaton (state -1) enters at its start state, the others keep their state
-int launch_extend_state(const PrefillState& st, int32_t* cu, int32_t* base, int32_t* ctx_len, int32_t* done, int32_t* n_out, int32_t* max_new, int32_t* stop_m,
-                        int32_t* stop_after, int32_t* aut_state, const int32_t* aut_start, hipStream_t stream);
+int launch_extend_state(const PrefillState& st, int32_t* cu, int32_t* base, const RowState& rows, int32_t* aut_state, const int32_t* aut_start,
+                        hipStream_t stream);
 int launch_kv_quant_rows_at(const void* qkv, int ld, int k_off, int v_off, const int32_t* cu, const int32_t* base, int B, int total_rows, void* k8,
                             void* v8, float* kscale, float* vscale, const int32_t* page_table, int max_pages, int Hkv, int hd, int page,
                             hipStream_t stream);
@@ -702,7 +710,8 @@ int launch_beam_resolve(const BeamResolveParams& p, hipStream_t stream);
 // (launch_beam_copy consumes it: src = -1 where nothing is copied)
 struct GroupForkParams {
     int N, max_pages;
-    int32_t *page_table, *ctx_len, *done, *n_out, *max_new, *stop_m, *stop_after, *copy_src, *copy_dst, *copy_ntok;
+    int32_t *page_table, *copy_src, *copy_dst, *copy_ntok;
+    RowState st;
     int32_t* grp_shared;             // [groups]: the complete prompt pages the group's rows share (DecodeAttnParams::grp_shared)
     int S[EMMAX_MAX_DECODE_BATCH];   // the groups' prompt contexts
 };
@@ -718,8 +727,7 @@ struct HistParams {
     int len[EMMAX_MAX_DECODE_BATCH];
 };
 int launch_hist_fill(const HistParams& h, hipStream_t stream);
-int launch_set_tokens(int32_t* cur_tok, const int32_t* toks, int B, int32_t* done, int32_t* stop_m, int32_t* stop_after, int32_t* max_new,
-                      int budget, hipStream_t stream);
+int launch_set_tokens(const RowState& rows, const int32_t* toks, int B, int budget, hipStream_t stream);
 
 
 // ---- decode_km.hip: batch 3-16 projections with K <= 4096 on MFMA, K split across the waves, activations as register fragments ----

@@ -286,20 +286,19 @@ __global__ __launch_bounds__(256) void emmax_resize_pass_kernel(const uint8_t* _
 
 // device-side (re)initialisation of the per-sequence state at prefill: cu_seqlens, ctx_len, done, n_out.
 // Values travel as kernel arguments, so there is no host staging buffer to race with.
-__global__ void emmax_prefill_state_kernel(PrefillState st, int32_t* cu, int32_t* ctx_len, int32_t* done, int32_t* n_out, int32_t* max_new,
-                                           int32_t* stop_m, int32_t* stop_after) {
+__global__ void emmax_prefill_state_kernel(PrefillState st, int32_t* cu, RowState r) {
     if (threadIdx.x == 0) {
         int acc = 0;
         cu[0] = 0;
         for (int b = 0; b < st.B; ++b) {
             acc += st.S[b];
             cu[b + 1] = acc;
-            ctx_len[b] = st.S[b];
-            done[b] = 0;
-            n_out[b] = 0;
-            max_new[b] = 0x7fffffff;   // no token budget until a generate / slot call sets one
-            stop_m[b] = 0;
-            stop_after[b] = -1;
+            r.ctx_len[b] = st.S[b];
+            r.done[b] = 0;
+            r.n_out[b] = 0;
+            r.max_new[b] = 0x7fffffff;   // no token budget until a generate / slot call sets one
+            r.stop_m[b] = 0;
+            r.stop_after[b] = -1;
         }
     }
 }
@@ -308,47 +307,38 @@ __global__ void emmax_set_ints_kernel(int32_t* p, int n, int32_t v) {
     if ((int)threadIdx.x < n) p[threadIdx.x] = v;
 }
 // idle request slots: nothing to decode, empty context (their share of a batched step costs no K/V traffic)
-__global__ void emmax_slots_idle_kernel(int n, int32_t* cur_tok, int32_t* ctx_len, int32_t* done, int32_t* n_out, int32_t pad_id) {
+__global__ void emmax_slots_idle_kernel(int n, RowState r, int32_t pad_id) {
     const int b = threadIdx.x;
     if (b < n) {
-        cur_tok[b] = pad_id;
-        ctx_len[b] = 0;
-        done[b] = 1;
-        n_out[b] = 0;
+        r.cur_tok[b] = pad_id;
+        r.ctx_len[b] = 0;
+        r.done[b] = 1;
+        r.n_out[b] = 0;
+    }
+}
+
+// row `src` of every column (inherit_only: of the inherited ones) into row `dst`, by the 256 threads of a block, dword by dword
+__device__ __forceinline__ void move_row_cols(const RowCols& cols, int src, int dst, bool inherit_only, int tid) {
+    for (int c = 0; c < cols.n; ++c) {
+        const RowCol& col = cols.col[c];
+        if (inherit_only && !col.inherit) continue;
+        const uint32_t* from = (const uint32_t*)(col.base + (size_t)src * col.stride_bytes);
+        uint32_t* to = (uint32_t*)(col.base + (size_t)dst * col.stride_bytes);
+        for (int k = tid; k < (int)(col.move_bytes / 4); k += 256) to[k] = from[k];
     }
 }
 
 // one block per committed request
 __global__ __launch_bounds__(256) void emmax_slots_commit_kernel(CommitParams c) {
     const int i = blockIdx.x, src = c.src[i], dst = c.slot[i], tid = threadIdx.x;
-    for (int k = tid; k < c.max_out; k += 256) c.out_ids[(size_t)dst * c.max_out + k] = c.out_ids[(size_t)src * c.max_out + k];
-    if (c.logprob)
-        for (int k = tid; k < c.max_out; k += 256) c.logprob[(size_t)dst * c.max_out + k] = c.logprob[(size_t)src * c.max_out + k];
-    if (c.penalty)
-        for (int k = tid; k < c.max_prompt; k += 256) c.hist[(size_t)dst * c.max_prompt + k] = c.hist[(size_t)src * c.max_prompt + k];
+    move_row_cols(c.cols, src, dst, false, tid);
     for (int k = tid; k < c.max_pages; k += 256) {
         const int32_t a = c.page_table[(size_t)src * c.max_pages + k], b = c.page_table[(size_t)dst * c.max_pages + k];
         c.page_table[(size_t)dst * c.max_pages + k] = a;
         c.page_table[(size_t)src * c.max_pages + k] = b;
     }
-    if (tid == 0) {
-        c.cur_tok[dst] = c.cur_tok[src]; c.ctx_len[dst] = c.ctx_len[src]; c.n_out[dst] = c.n_out[src]; c.max_new[dst] = c.max_new[src];
-        c.stop_m[dst] = c.stop_m[src]; c.stop_after[dst] = c.stop_after[src];
-        c.done[dst] = c.done[src];
-        if (c.logprob) {
-            c.temperature[dst] = c.temperature[src]; c.top_k[dst] = c.top_k[src]; c.top_p[dst] = c.top_p[src];
-            c.seed[dst] = c.seed[src]; c.subseq[dst] = c.subseq[src];
-        }
-        if (c.penalty) {
-            c.penalty[dst] = c.penalty[src]; c.ngram[dst] = c.ngram[src]; c.min_new[dst] = c.min_new[src];
-            c.hist_len[dst] = c.hist_len[src];
-        }
-        if (c.warp[0])
-            for (int k = 0; k < 4; ++k) c.warp[k][dst] = c.warp[k][src];
-        if (c.rule_en) c.rule_en[dst] = c.rule_en[src];
-        if (c.aut_start) { c.aut_start[dst] = c.aut_start[src]; c.aut_state[dst] = c.aut_state[src]; }
-        c.done[src] = 1; c.ctx_len[src] = 0;
-    }
+    __syncthreads();   // the staging row's done and ctx_len were read by other threads: it goes idle behind them
+    if (tid == 0) { c.done[src] = 1; c.ctx_len[src] = 0; }
 }
 
 // one block per follower (kernels.h: SlotForkParams)
@@ -361,19 +351,12 @@ __global__ __launch_bounds__(256) void emmax_slots_fork_kernel(SlotForkParams p)
         p.hidden[(size_t)f * mp + i] = mine[i];
         mine[i] = theirs[i];
     }
-    if (p.penalty)
-        for (int k = tid; k < p.max_prompt; k += 256) p.hist[(size_t)f * p.max_prompt + k] = p.hist[(size_t)src * p.max_prompt + k];
+    move_row_cols(p.cols, src, f, true, tid);   // the source's token budget, processors, prompt ids, warpers, rule enables, automaton start
     if (tid == 0) {
-        p.ctx_len[f] = p.S; p.done[f] = 0; p.n_out[f] = 0; p.max_new[f] = p.max_new[src];
-        p.stop_m[f] = 0; p.stop_after[f] = -1;
+        p.st.ctx_len[f] = p.S; p.st.done[f] = 0; p.st.n_out[f] = 0;
+        p.st.stop_m[f] = 0; p.st.stop_after[f] = -1;
         p.temperature[f] = p.in_t[j]; p.top_k[f] = p.in_k[j]; p.top_p[f] = p.in_p[j]; p.seed[f] = p.in_seed[j]; p.subseq[f] = p.in_sub[j];
-        if (p.penalty) {
-            p.penalty[f] = p.penalty[src]; p.ngram[f] = p.ngram[src]; p.min_new[f] = p.min_new[src]; p.hist_len[f] = p.hist_len[src];
-        }
-        if (p.warp[0])
-            for (int k = 0; k < 4; ++k) p.warp[k][f] = p.warp[k][src];
-        if (p.rule_en) p.rule_en[f] = p.rule_en[src];
-        if (p.aut_start) { p.aut_start[f] = p.aut_start[src]; p.aut_state[f] = p.aut_start[src]; }
+        if (p.aut_start) p.aut_state[f] = p.aut_start[src];
         const bool cp = rem > 0 && nfull < mp;   // (page nfull is past the shared ones: both rows still hold their own entry there)
         p.copy_src[j] = cp ? theirs[nfull] : -1;
         p.copy_dst[j] = cp ? mine[nfull] : -1;
@@ -408,7 +391,7 @@ int launch_hist_fill(const HistParams& h, hipStream_t stream) {
 }
 
 int launch_slots_commit(const CommitParams& c, hipStream_t stream) {
-    if (c.n < 1 || c.n > EMMAX_MAX_DECODE_BATCH) return -1;
+    if (c.n < 1 || c.n > EMMAX_MAX_DECODE_BATCH || c.cols.n < 0 || c.cols.n > 32) return -1;
     hipLaunchKernelGGL(emmax_slots_commit_kernel, dim3(c.n), dim3(256), 0, stream, c);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
@@ -417,6 +400,7 @@ int launch_slots_fork(const SlotForkParams& p, hipStream_t stream) {
     if (p.n < 1 || p.n > EMMAX_MAX_DECODE_BATCH || p.rows < 1 || p.src < 0 || p.src >= p.rows || p.max_pages < 1 || p.S < 1 || p.S >= p.max_pages * 64) return -1;
     for (int j = 0; j < p.n; ++j)
         if (p.dst[j] < 0 || p.dst[j] >= p.rows || p.dst[j] == p.src) return -1;
+    if (p.cols.n < 0 || p.cols.n > 32) return -1;
     hipLaunchKernelGGL(emmax_slots_fork_kernel, dim3(p.n), dim3(256), 0, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
@@ -427,9 +411,8 @@ int launch_slots_unhide(int32_t* table, int32_t* hidden, int n, hipStream_t stre
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
-int launch_prefill_state(const PrefillState& st, int32_t* cu, int32_t* ctx_len, int32_t* done, int32_t* n_out, int32_t* max_new,
-                         int32_t* stop_m, int32_t* stop_after, hipStream_t stream) {
-    hipLaunchKernelGGL(emmax_prefill_state_kernel, dim3(1), dim3(64), 0, stream, st, cu, ctx_len, done, n_out, max_new, stop_m, stop_after);
+int launch_prefill_state(const PrefillState& st, int32_t* cu, const RowState& rows, hipStream_t stream) {
+    hipLaunchKernelGGL(emmax_prefill_state_kernel, dim3(1), dim3(64), 0, stream, st, cu, rows);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 int launch_set_ints(int32_t* p, int n, int32_t v, hipStream_t stream) {
@@ -437,9 +420,9 @@ int launch_set_ints(int32_t* p, int n, int32_t v, hipStream_t stream) {
     hipLaunchKernelGGL(emmax_set_ints_kernel, dim3(1), dim3(64), 0, stream, p, n, v);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
-int launch_slots_idle(int n, int32_t* cur_tok, int32_t* ctx_len, int32_t* done, int32_t* n_out, int32_t pad_id, hipStream_t stream) {
+int launch_slots_idle(int n, const RowState& rows, int32_t pad_id, hipStream_t stream) {
     if (n < 1 || n > 64) return -1;
-    hipLaunchKernelGGL(emmax_slots_idle_kernel, dim3(1), dim3(64), 0, stream, n, cur_tok, ctx_len, done, n_out, pad_id);
+    hipLaunchKernelGGL(emmax_slots_idle_kernel, dim3(1), dim3(64), 0, stream, n, rows, pad_id);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 int launch_set_int(int32_t* p, int32_t v, hipStream_t stream) {

@@ -144,6 +144,28 @@ static int set_rule_enable_rows(emmax_session* s, int row0, int n, bool staged, 
     return sc.leave();
 }
 
+// The token rules and the automaton are processors that read the history: setting either turns processing on, with neutral values on every row,
+// where it was off.  *implied: the setter's note that the processing is its own to turn off again
+static int neutral_processing_on(emmax_session* s, bool* implied) {
+    if (s->proc.on) return 0;
+    std::vector<float> one((size_t)s->rows_total, 1.f);
+    HIPCHK(hipMemcpy(s->proc.pen, one.data(), one.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(s->proc.ng, 0, (size_t)s->rows_total * 4));
+    HIPCHK(hipMemset(s->proc.mn, 0, (size_t)s->rows_total * 4));
+    s->proc.on = true;
+    *implied = true;
+    return 0;
+}
+// ... and clearing the one whose processing it is (mine) hands it to the other where that is still on -- it is the other's to turn off now --
+// and turns it off otherwise
+static void hand_over_processing(emmax_session* s, bool mine, bool other_on, bool* other_implied) {
+    if (mine) {
+        if (other_on) *other_implied = true;
+        else s->proc.on = false;
+    }
+    if (!s->samp.on && !s->proc.on) (void)emmax_session_clear_top_logprobs(s, nullptr);
+}
+
 extern "C" {
 
 int emmax_session_set_warpers(emmax_session* s, int row0, int n, const float* min_p_host, const float* typical_p_host, const float* epsilon_cutoff_host,
@@ -161,7 +183,10 @@ int emmax_session_clear_warpers(emmax_session* s, emmax_stream stream) {
     if (!s->warp.on) return 0;
     StreamScope sc(s, stream);
     if (sc.error()) return sc.error();
-    for (float* w : {s->warp.minp, s->warp.typ, s->warp.eps, s->warp.eta}) HIPCHK(hipMemsetAsync(w, 0, (size_t)s->rows_total * 4, sc.stream()));
+    RowCols cols;
+    if (int r = session_row_cols(s, &cols)) return r;
+    for (int i = 0; i < cols.n; ++i)
+        if (cols.col[i].owner == ROWS_WARPERS) HIPCHK(hipMemsetAsync(cols.col[i].base, 0, (size_t)s->rows_total * cols.col[i].stride_bytes, sc.stream()));
     s->warp.on = false;
     return sc.leave();
 }
@@ -186,14 +211,7 @@ int emmax_session_set_token_rules(emmax_session* s, int n_rules, const int32_t* 
     if (!s->rules.on) {   // every row starts with every kind enabled; the rules read the history: processing on, neutral where it was off
         std::vector<uint32_t> all((size_t)s->rows_total, 15u);
         HIPCHK(hipMemcpy(s->rules.en, all.data(), all.size() * 4, hipMemcpyHostToDevice));
-        if (!s->proc.on) {
-            std::vector<float> one((size_t)s->rows_total, 1.f);
-            HIPCHK(hipMemcpy(s->proc.pen, one.data(), one.size() * 4, hipMemcpyHostToDevice));
-            HIPCHK(hipMemset(s->proc.ng, 0, (size_t)s->rows_total * 4));
-            HIPCHK(hipMemset(s->proc.mn, 0, (size_t)s->rows_total * 4));
-            s->proc.on = true;
-            s->rules.implied_proc = true;
-        }
+        if (int r = neutral_processing_on(s, &s->rules.implied_proc)) return r;
     }
     s->rules.on = true;
     return sc.leave();
@@ -209,11 +227,7 @@ int emmax_slots_set_rule_enables_staged(emmax_session* s, int n, const uint32_t*
 
 int emmax_session_clear_token_rules(emmax_session* s, emmax_stream) {
     if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (s->rules.on && s->rules.implied_proc) {
-        if (s->aut.on) s->aut.implied_proc = true;   // the automaton still needs the neutral processing: it is its to turn off now
-        else s->proc.on = false;
-    }
-    if (!s->samp.on && !s->proc.on) (void)emmax_session_clear_top_logprobs(s, nullptr);
+    hand_over_processing(s, s->rules.on && s->rules.implied_proc, s->aut.on, &s->aut.implied_proc);
     s->rules.on = s->rules.implied_proc = false;
     return 0;
 }
@@ -269,14 +283,7 @@ int emmax_session_set_automaton(emmax_session* s, int n_states, int n_classes, c
     if (!s->aut.on) {   // every row starts unconstrained; the mask is a processor: processing on, neutral where it was off
         HIPCHK(hipMemset(s->aut.start, 0xff, (size_t)s->rows_total * 4));
         HIPCHK(hipMemset(s->aut.state, 0xff, (size_t)s->rows_total * 4));
-        if (!s->proc.on) {
-            std::vector<float> one((size_t)s->rows_total, 1.f);
-            HIPCHK(hipMemcpy(s->proc.pen, one.data(), one.size() * 4, hipMemcpyHostToDevice));
-            HIPCHK(hipMemset(s->proc.ng, 0, (size_t)s->rows_total * 4));
-            HIPCHK(hipMemset(s->proc.mn, 0, (size_t)s->rows_total * 4));
-            s->proc.on = true;
-            s->aut.implied_proc = true;
-        }
+        if (int r = neutral_processing_on(s, &s->aut.implied_proc)) return r;
     }
     s->aut.on = true;
     s->aut.n_states = n_states; s->aut.n_classes = n_classes;
@@ -293,11 +300,7 @@ int emmax_slots_set_automaton_starts_staged(emmax_session* s, int n, const int32
 
 int emmax_session_clear_automaton(emmax_session* s, emmax_stream) {
     if (!s) return fail(EMMAX_ERR_INVALID, "null argument");
-    if (s->aut.on && s->aut.implied_proc) {
-        if (s->rules.on) s->rules.implied_proc = true;   // the token rules still need the neutral processing: it is theirs to turn off now
-        else s->proc.on = false;
-    }
-    if (!s->samp.on && !s->proc.on) (void)emmax_session_clear_top_logprobs(s, nullptr);
+    hand_over_processing(s, s->aut.on && s->aut.implied_proc, s->rules.on, &s->rules.implied_proc);
     s->aut.on = s->aut.implied_proc = false;
     return 0;
 }
@@ -502,7 +505,7 @@ int emmax_session_set_step_taps(emmax_session* s, float* hidden_dev, uint64_t hi
         const int B = std::min(s->cur_B, (int)EMMAX_MAX_DECODE_BATCH);
         StreamScope sc(s, stream);
         if (sc.error()) return sc.error();
-        HIPCHK(hipMemcpyAsync(ctx, s->ctx_len, (size_t)B * 4, hipMemcpyDeviceToHost, sc.stream()));
+        HIPCHK(hipMemcpyAsync(ctx, s->rows.ctx_len, (size_t)B * 4, hipMemcpyDeviceToHost, sc.stream()));
         HIPCHK(hipStreamSynchronize(sc.stream()));
         if (int r = sc.leave()) return r;
         int longest = 0;
@@ -584,13 +587,13 @@ int tap_step_hidden(emmax_session* s, int idx, int B, hipStream_t st) {
     TapRowsParams p;
     memset(&p, 0, sizeof(p));
     if (idx == 0) {   // behind the embed: the token's row of the table itself (a step of 1-2 rows folds the gather into layer 0's qkv launch)
-        p.src = m->embed; p.src_f32 = 0; p.ld_src = m->H; p.gather = s->cur_tok; p.gather_rows = m->vocab;
+        p.src = m->embed; p.src_f32 = 0; p.ld_src = m->H; p.gather = s->rows.cur_tok; p.gather_rows = m->vocab;
     } else {
         tap_stream_src(p, h32_of(s), s->dh, m->H);
     }
     p.dst = t.hidden + (size_t)tap_sel(t.hl, idx) * B * m->H;
     p.rows = B; p.H = m->H; p.eps = m->cfg.rms_eps;
-    p.gen_idx = s->n_out; p.done = s->done; p.gen_stride = (long long)n_sel * B * m->H; p.max_new = s->taps.step_max_new;
+    p.gen_idx = s->rows.n_out; p.done = s->rows.done; p.gen_stride = (long long)n_sel * B * m->H; p.max_new = s->taps.step_max_new;
     if (idx == m->cfg.n_layers) p.norm_w = m->final_norm;
     KCHK(launch_tap_rows(p, st));
     return 0;
@@ -606,9 +609,9 @@ int tap_step_attn(emmax_session* s, int li, int B, hipStream_t st) {
     memset(&a, 0, sizeof(a));
     a.q = s->dq; a.ldq = m->q_dim; a.q_off = 0; a.kcache = kcache_of(s, li);
     if (s->kv8) a.kscale = kscale_of(s, li);
-    a.page_table = s->page_table; a.cu = nullptr; a.base = s->ctx_len;
+    a.page_table = s->page_table; a.cu = nullptr; a.base = s->rows.ctx_len;
     a.probs = t.attn + (size_t)tap_sel(t.al, li) * B * c.n_heads * t.ld;
-    a.gen_idx = s->n_out; a.done = s->done; a.gen_stride = (long long)n_sel * B * c.n_heads * t.ld; a.max_new = s->taps.step_max_new;
+    a.gen_idx = s->rows.n_out; a.done = s->rows.done; a.gen_stride = (long long)n_sel * B * c.n_heads * t.ld; a.max_new = s->taps.step_max_new;
     a.ld_keys = t.ld; a.B = B; a.Hq = c.n_heads; a.Hkv = c.n_kv_heads; a.max_pages = s->max_pages; a.scale = 1.0f / sqrtf((float)c.head_dim);
     KCHK(launch_attn_probs(a, 1, s->kv8 ? 1 : 0, st));
     return 0;
@@ -667,7 +670,7 @@ int emmax_session_beam_result(emmax_session* s, int max_new, int32_t* seq_dev, i
     if (sc.error()) return sc.error();
     const hipStream_t st = sc.stream();
     const int rows = s->beam.G * s->beam.K;
-    if (seq_dev) HIPCHK(hipMemcpy2DAsync(seq_dev, (size_t)max_new * 4, s->out_ids, (size_t)s->max_out * 4, (size_t)max_new * 4, rows, hipMemcpyDeviceToDevice, st));
+    if (seq_dev) HIPCHK(hipMemcpy2DAsync(seq_dev, (size_t)max_new * 4, s->rows.out_ids, (size_t)s->max_out * 4, (size_t)max_new * 4, rows, hipMemcpyDeviceToDevice, st));
     if (bidx_dev) HIPCHK(hipMemcpy2DAsync(bidx_dev, (size_t)max_new * 4, s->beam.res_bidx, (size_t)s->max_out * 4, (size_t)max_new * 4, rows, hipMemcpyDeviceToDevice, st));
     if (len_dev) HIPCHK(hipMemcpyAsync(len_dev, s->beam.res_len, rows * 4, hipMemcpyDeviceToDevice, st));
     if (score_dev) HIPCHK(hipMemcpyAsync(score_dev, s->beam.res_score, rows * 4, hipMemcpyDeviceToDevice, st));

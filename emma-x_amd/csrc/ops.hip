@@ -583,18 +583,14 @@ static float bits_to_float(uint32_t u) {
 namespace {
 struct OpRows {
     emmax_session* s;
-    int32_t *cur_tok, *ctx_len, *done, *n_out, *out_ids, *max_new_d, *stop_m, *stop_after;
-    explicit OpRows(emmax_session* s_) : s(s_), cur_tok(s_->cur_tok), ctx_len(s_->ctx_len), done(s_->done), n_out(s_->n_out), out_ids(s_->out_ids),
-                                         max_new_d(s_->max_new_d), stop_m(s_->stop_m), stop_after(s_->stop_after) {
+    RowState saved;
+    explicit OpRows(emmax_session* s_) : s(s_), saved(s_->rows) {
+        int32_t* c = s->op_state;   // seven columns of op_rows rows -- ctx_len first, then cur_tok -- and the output rows
         const int R = s->op_rows;
-        s->ctx_len = s->op_state; s->cur_tok = s->op_state + R; s->done = s->op_state + 2 * R; s->n_out = s->op_state + 3 * R;
-        s->max_new_d = s->op_state + 4 * R; s->stop_m = s->op_state + 5 * R; s->stop_after = s->op_state + 6 * R; s->out_ids = s->op_out;
+        s->rows = RowState{/* cur_tok */ c + R, /* ctx_len */ c, c + 2 * R, c + 3 * R, c + 4 * R, c + 5 * R, c + 6 * R, s->op_out};
     }
     OpRows(const OpRows&) = delete;
-    ~OpRows() {
-        s->cur_tok = cur_tok; s->ctx_len = ctx_len; s->done = done; s->n_out = n_out; s->out_ids = out_ids; s->max_new_d = max_new_d;
-        s->stop_m = stop_m; s->stop_after = stop_after;
-    }
+    ~OpRows() { s->rows = saved; }
 };
 }  // namespace
 
@@ -608,12 +604,12 @@ static int decode_stage_run(emmax_session* s, int layer, int stage, int B, const
     if (h32_in) HIPCHK(hipMemcpyAsync(s->dh32, h32_in, (size_t)R * H * 4, hipMemcpyDeviceToDevice, st));
     OpRows swap(s);
     HIPCHK(hipMemsetAsync(s->op_state, 0, (size_t)R * 8 * 4, st));
-    KCHK(launch_set_ints(s->max_new_d, R, 1 << 30, st));
-    KCHK(launch_set_ints(s->stop_after, R, -1, st));
+    KCHK(launch_set_ints(s->rows.max_new, R, 1 << 30, st));
+    KCHK(launch_set_ints(s->rows.stop_after, R, -1, st));
     int r = 0;
     s->last_via = EMMAX_VIA_NONE;
     if (stage == STAGE_QKV) {
-        HIPCHK(hipMemcpyAsync(s->ctx_len, ctx_host, (size_t)B * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(s->rows.ctx_len, ctx_host, (size_t)B * 4, hipMemcpyHostToDevice, st));
         if (pt_host) HIPCHK(hipMemcpyAsync(s->page_table, pt_host, (size_t)B * s->max_pages * 4, hipMemcpyHostToDevice, st));
         r = run_decode_stage(s, B, layer, stage, st);
         if (pt_host) {   // the identity table again, whatever the launch did
@@ -638,7 +634,7 @@ static int decode_stage_run(emmax_session* s, int layer, int stage, int B, const
         r = run_decode_stage(s, B, layer, stage, st);
     } else {   // STAGE_LMHEAD: the logit rows and the greedy finish over the session's partial buffers, against the op's own per-row state
         r = run_lm_head_step(s, B, false, (float*)y_out, true, st, 0);
-        if (r == 0 && tok_out) HIPCHK(hipMemcpyAsync(tok_out, s->cur_tok, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+        if (r == 0 && tok_out) HIPCHK(hipMemcpyAsync(tok_out, s->rows.cur_tok, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
     }
     if (via_out) *via_out = s->last_via;
     if (r) return r;

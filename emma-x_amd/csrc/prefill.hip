@@ -198,7 +198,7 @@ int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B
     if (total > s->max_rows) return fail(EMMAX_ERR_NOMEM, "packed prefill rows %d exceed capacity %d", total, s->max_rows);
     if (int r = tap_pass_check(s, maxS, "prefill")) return r;
     if (!slot_mode) taps_unbind(s, false, true);   // step taps were bound for the rows of the last pass
-    KCHK(launch_prefill_state(ps, s->cu, s->ctx_len + r0, s->done + r0, s->n_out + r0, s->max_new_d + r0, s->stop_m + r0, s->stop_after + r0, st));
+    KCHK(launch_prefill_state(ps, s->cu, s->rows.from(r0, s->max_out), st));
     if (s->aut.on) {   // the rows enter the automaton at their start states (sample groups: the B x N rows the prefill forks into)
         const int rows = s->grp_N && !slot_mode ? B * s->grp_N : B;
         HIPCHK(hipMemcpyAsync(s->aut.state + r0, s->aut.start + r0, (size_t)rows * 4, hipMemcpyDeviceToDevice, st));

@@ -177,7 +177,7 @@ struct Scores {
 };
 // TOP-N / WATCHED-TOKEN LOG-PROBABILITIES (emmax_session_set_top_logprobs; sample.hip: emmax_top_logprobs_kernel): device words {top_ids,
 // top_lp, watch_lp, n_top, n_watch, max_new} naming the caller's buffers, and the session's copy of the watch list.  The host keeps the same
-// values for the copies a commit makes.  Off: none of it is touched and a step launches what it launches without
+// values: the buffers are columns of session_row_cols, so a commit moves a staged request's entry.  Off: none of it is touched and a step launches what it launches without
 struct TopLogprobs {
     bool on = false;
     int n_top = 0, n_watch = 0, max_new = 0;
@@ -278,7 +278,8 @@ struct emmax_session {
     int stg_epoch = 0;          // staged batches so far: a staging row's logit row is its request's until the next emmax_slots_prefill_staged
     bool stg_logits = false;    // ... and was written at all (sampling was on at that staged prefill)
     int32_t *part_idx2;
-    int32_t *part_idx, *cur_tok, *ctx_len, *done, *n_out, *out_ids, *max_new_d /* [max_batch] */, *page_table;
+    int32_t *part_idx, *page_table;
+    RowState rows;              // the generation state of every row, staging rows included (kernels.h); with the optional arrays above: session_row_cols
     // EXACT NUMERICS (round 6; tuning switch `exact` at emmax_session_create): fp32 activations end to end.  x32a: the fp32 result of the GEMM
     // in flight (qkv rows, SwiGLU product, fc1 output ...); xhla / xhlb: the two-term bf16 ("HL") A operands, ping-pong; xtok32: the ViT's fp32
     // token rows; xfeats32 / xpe32: fp32 tower features / projected patch embeddings; dq32 / dact32: the decode step's fp32 q rows and SwiGLU
@@ -294,7 +295,7 @@ struct emmax_session {
     unsigned long long* sk_ws2 = nullptr;    // ... of a STAGED prefill's lm-head: it runs on a second stream beside the live decode steps, and the
                                              // granules are indexed by block id only -- two concurrent launches on one workspace would consume or
                                              // clear each other's partial sums
-    int32_t *stop_ids /* [EMMAX_MAX_STOP_IDS] */, *stop_cfg /* {n_trigger, n_after} */, *stop_m, *stop_after;
+    int32_t *stop_ids /* [EMMAX_MAX_STOP_IDS] */, *stop_cfg /* {n_trigger, n_after} */;
     bool slots_open = false;    // slot serving mode: rows are independent request slots (emmax_slots_open)
     float *cos_t, *sin_t;
     int n_lm_blocks;
@@ -316,7 +317,7 @@ struct emmax_session {
     int graph_failed = 0;
     int last_step_graph = 0;   // the most recent decode step was a graph replay (what emmax_session_graph_active reports)
     int last_via = 0;          // launcher family of the most recent projection launch (step.hip: launch_proj; EMMAX_VIA_*)
-    // emmax_op_decode_stage (ops.hip): per-row state of its own for the rows it runs -- 8 int32 columns of op_rows rows (ctx_len, cur_tok, done,
+    // emmax_op_decode_stage (ops.hip): a RowState of its own for the rows it runs -- 8 int32 columns of op_rows rows (ctx_len, cur_tok, done,
     // n_out, max_new, stop_m, stop_after, -) and an output row each -- so that a single stage never touches the session's generation state
     int op_rows = 0;
     int32_t *op_state = nullptr, *op_out = nullptr;
@@ -401,6 +402,9 @@ static inline void taps_unbind(emmax_session* s, bool pass, bool step) {
     if (pass) s->taps.pass = TapSet();
     if (step) s->taps.step = TapSet();
 }
+// session.hip: the session's per-row device arrays whose owner is on (kernels.h: RowCols) -- what a staged commit moves and, of the inherited
+// ones, what a slot fork copies.  A new per-row array is one more line there.  EMMAX_ERR_STATE when the list would outgrow its capacity
+int session_row_cols(const emmax_session* s, RowCols* out);
 // generate.hip: every hidden page back into its row's table (a permutation again), no slot in a group; what ends or restarts slot serving calls it
 int slots_restore_pages(emmax_session* s, hipStream_t st);
 // vision.hip: GEMM parameters -- plain; of a session stage (with the session's split-K scratch); of an exact-numerics stage (HL rows in, fp32 out)

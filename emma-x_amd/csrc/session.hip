@@ -85,16 +85,16 @@ static void plan_session(emmax_session* s, Bump& b) {
     s->rules.flags = (int32_t*)b.bytes(EMMAX_MAX_RULES * 4);
     s->rules.bias = (float*)b.bytes(EMMAX_MAX_RULES * 4);
     s->rules.en = (uint32_t*)b.bytes(Br * 4);
-    s->cur_tok = (int32_t*)b.bytes(Br * 4);
-    s->ctx_len = (int32_t*)b.bytes(Br * 4);
-    s->done = (int32_t*)b.bytes(Br * 4);
-    s->n_out = (int32_t*)b.bytes(Br * 4);
-    s->out_ids = (int32_t*)b.bytes((int64_t)Br * s->max_out * 4);
-    s->max_new_d = (int32_t*)b.bytes(Br * 4);
+    s->rows.cur_tok = (int32_t*)b.bytes(Br * 4);
+    s->rows.ctx_len = (int32_t*)b.bytes(Br * 4);
+    s->rows.done = (int32_t*)b.bytes(Br * 4);
+    s->rows.n_out = (int32_t*)b.bytes(Br * 4);
+    s->rows.out_ids = (int32_t*)b.bytes((int64_t)Br * s->max_out * 4);
+    s->rows.max_new = (int32_t*)b.bytes(Br * 4);
     s->stop_ids = (int32_t*)b.bytes(EMMAX_MAX_STOP_IDS * 4);
     s->stop_cfg = (int32_t*)b.bytes(2 * 4);
-    s->stop_m = (int32_t*)b.bytes(Br * 4);
-    s->stop_after = (int32_t*)b.bytes(Br * 4);
+    s->rows.stop_m = (int32_t*)b.bytes(Br * 4);
+    s->rows.stop_after = (int32_t*)b.bytes(Br * 4);
     s->page_table = (int32_t*)b.bytes((int64_t)Br * s->max_pages * 4);
     s->sk_ws = (unsigned long long*)b.bytes((int64_t)256 * 2 * 256 * 8);
     s->sk_ws2 = (unsigned long long*)b.bytes((int64_t)256 * 2 * 256 * 8);
@@ -167,6 +167,39 @@ static void plan_session(emmax_session* s, Bump& b) {
     s->aut.next = (int16_t*)b.bytes((int64_t)EMMAX_MAX_AUT_STATES * EMMAX_MAX_AUT_CLASSES * 2);
     s->aut.start = (int32_t*)b.bytes(Br * 4);
     s->aut.state = (int32_t*)b.bytes(Br * 4);
+}
+
+// THE per-row device arrays of a session, by {owner is on, owner, inherited by a forked follower, bytes between rows, bytes of a row that move}.
+// emmax_slots_commit moves all of them (misc.hip: emmax_slots_commit_kernel), emmax_slots_fork the inherited ones, and
+// emmax_session_clear_warpers zeroes its owner's: a per-row array added to plan_session gets its name in here and is served by all three
+int session_row_cols(const emmax_session* s, RowCols* out) {
+    const RowState& r = s->rows;
+    const TopLogprobs& t = s->toplp;
+    const uint32_t out_row = (uint32_t)s->max_out * 4, hist_row = (uint32_t)s->max_prompt * 4;
+    const uint32_t top_row = (uint32_t)t.n_top * 4, watch_row = (uint32_t)t.n_watch * 4;   // caller-owned [rows][max_new][n]: a staged request has entry 0 only
+    bool fits = true;
+    out->n = 0;
+    auto add = [&](bool on, int owner, int inherit, uint32_t stride, uint32_t move, std::initializer_list<const void*> bases) {
+        for (const void* b : bases) {
+            fits = fits && (!on || out->n < (int)(sizeof(out->col) / sizeof(out->col[0])));
+            if (on && fits) out->col[out->n++] = RowCol{(char*)b, stride, move, (uint8_t)owner, (uint8_t)inherit};
+        }
+    };
+    add(true, ROWS_CORE, 0, 4, 4, {r.cur_tok, r.ctx_len, r.done, r.n_out, r.stop_m, r.stop_after});
+    add(true, ROWS_CORE, 1, 4, 4, {r.max_new});
+    add(true, ROWS_CORE, 0, out_row, out_row, {r.out_ids});
+    add(s->samp.on, ROWS_SAMPLING, 0, 4, 4, {s->samp.t, s->samp.k, s->samp.p, s->samp.sub});
+    add(s->samp.on, ROWS_SAMPLING, 0, 8, 8, {s->samp.seed});
+    add(s->samp.on, ROWS_SAMPLING, 0, out_row, out_row, {s->samp.logprob});
+    add(s->proc.on, ROWS_PROCESSING, 1, 4, 4, {s->proc.pen, s->proc.ng, s->proc.mn, s->proc.hist_len});
+    add(s->proc.on, ROWS_PROCESSING, 1, hist_row, hist_row, {s->proc.hist});
+    add(s->warp.on, ROWS_WARPERS, 1, 4, 4, {s->warp.minp, s->warp.typ, s->warp.eps, s->warp.eta});
+    add(s->rules.on, ROWS_RULES, 1, 4, 4, {s->rules.en});
+    add(s->aut.on, ROWS_AUTOMATON, 1, 4, 4, {s->aut.start});
+    add(s->aut.on, ROWS_AUTOMATON, 0, 4, 4, {s->aut.state});   // (a follower's state is its source's START: the fork sets it)
+    add(t.on && t.n_top > 0, ROWS_TOPLP, 0, (uint32_t)t.max_new * top_row, top_row, {t.ids_out, t.lp_out});
+    add(t.on && t.n_watch > 0, ROWS_TOPLP, 0, (uint32_t)t.max_new * watch_row, watch_row, {t.watch_out});
+    return fits ? 0 : fail(EMMAX_ERR_STATE, "a session has more per-row arrays than the %d a commit or a fork carries (kernels.h: RowCols)", out->n);
 }
 
 static int kv_format_now() { return emmax_tune().exact >= 2 ? KV_F32 : emmax_tune().exact == 1 ? KV_X24 : (emmax_tune().kv_fp8 ? KV_FP8 : KV_BF16); }

@@ -226,7 +226,7 @@ static void stage_params(emmax_session* s, int B, int li, int stage, GemvParams&
             p.x = s->dh; p.ldx = m->H; p.ldw = m->H; p.K = m->H; p.norm_w = L.ln1; p.eps = c.rms_eps;
             p.y = s->dq; p.ldy = m->q_dim; p.n_rows = m->qkv_dim;
             p.head_dim = c.head_dim; p.Hq = c.n_heads; p.Hkv = c.n_kv_heads; p.page = PAGE; p.max_pages = s->max_pages;
-            p.ctx_len = s->ctx_len; p.page_table = s->page_table; p.cos_t = s->cos_t; p.sin_t = s->sin_t;
+            p.ctx_len = s->rows.ctx_len; p.page_table = s->page_table; p.cos_t = s->cos_t; p.sin_t = s->sin_t;
             p.kcache = kcache_of(s, li); p.vcache = vcache_of(s, li);
             p.kv_stage = s->kv8 ? s->kv_stage : nullptr;   // fp8 KV cache: the new rows wait as bf16 for the attention launch
             if (s->exact) { p.y = s->dq32; p.kv24 = s->kv24; }   // fp32 q rows; kcache / vcache are the 24-bit (or fp32) cache
@@ -280,11 +280,11 @@ static int finish_mode(const emmax_session* s) {
 // the per-row state of rows slot0 .. slot0 + B that a finish updates
 static void finish_rows(emmax_session* s, int B, bool is_prefill, int slot0, FinishParams& f) {
     emmax_model* m = s->m;
+    const RowState r = s->rows.from(slot0, s->max_out);
     f.B = B;
-    f.cur_tok = s->cur_tok + slot0; f.ctx_len = s->ctx_len + slot0; f.done = s->done + slot0; f.n_out = s->n_out + slot0;
-    f.out_ids = s->out_ids + (size_t)slot0 * s->max_out;
-    f.max_new_p = s->max_new_d + slot0; f.max_out = s->max_out; f.max_ctx = s->max_ctx;
-    f.stop_ids = s->stop_ids; f.stop_cfg = s->stop_cfg; f.stop_m = s->stop_m + slot0; f.stop_after = s->stop_after + slot0;
+    f.cur_tok = r.cur_tok; f.ctx_len = r.ctx_len; f.done = r.done; f.n_out = r.n_out; f.out_ids = r.out_ids;
+    f.max_new_p = r.max_new; f.max_out = s->max_out; f.max_ctx = s->max_ctx;
+    f.stop_ids = s->stop_ids; f.stop_cfg = s->stop_cfg; f.stop_m = r.stop_m; f.stop_after = r.stop_after;
     f.eos_id = m->cfg.eos_id; f.pad_id = m->cfg.pad_id; f.is_prefill = is_prefill ? 1 : 0;
 }
 
@@ -317,7 +317,8 @@ static int launch_top_logprobs_step(emmax_session* s, int B, bool is_prefill, in
     memset(&p, 0, sizeof(p));
     p.logits = logits; p.ld = s->m->vocab; p.V = s->m->vocab;
     p.words = s->toplp.words; p.watch_ids = s->toplp.watch_ids; p.row0 = slot0; p.is_prefill = is_prefill ? 1 : 0;
-    p.n_out = s->n_out + slot0; p.done = s->done + slot0; p.max_new_p = s->max_new_d + slot0;
+    const RowState r = s->rows.from(slot0, s->max_out);
+    p.n_out = r.n_out; p.done = r.done; p.max_new_p = r.max_new;
     KCHK(launch_top_logprobs(p, B, st));
     return 0;
 }
@@ -390,7 +391,7 @@ int launch_beam_finish(emmax_session* s, bool is_prefill, hipStream_t st) {
     BeamRowParams r;
     memset(&r, 0, sizeof(r));
     r.logits = s->logits; r.ld = m->vocab; r.V = m->vocab; r.K = K; r.is_prefill = is_prefill ? 1 : 0;
-    r.run_score = s->beam.run; r.done = s->done; r.n_out = s->n_out;
+    r.run_score = s->beam.run; r.done = s->rows.done; r.n_out = s->rows.n_out;
     r.cand_acc = s->beam.cand_acc; r.cand_tok = s->beam.cand_tok; r.row_lse = s->beam.row_lse;
     r.score_words = s->scores.on ? s->scores.words : nullptr;
     KCHK(launch_beam_rows(r, is_prefill ? G : rows, st));
@@ -401,7 +402,7 @@ int launch_beam_finish(emmax_session* s, bool is_prefill, hipStream_t st) {
     g.pw = s->beam.pw; g.cand_acc = s->beam.cand_acc; g.cand_tok = s->beam.cand_tok; g.row_lse = s->beam.row_lse;
     g.run_score = s->beam.run; g.fin_score = s->beam.fin_score; g.fin_flag = s->beam.fin_flag; g.fin_t = s->beam.fin_t; g.fin_par = s->beam.fin_par;
     g.fin_tok = s->beam.fin_tok; g.grp_state = s->beam.grp;
-    g.cur_tok = s->cur_tok; g.ctx_len = s->ctx_len; g.done = s->done; g.n_out = s->n_out; g.max_new_p = s->max_new_d;
+    g.cur_tok = s->rows.cur_tok; g.ctx_len = s->rows.ctx_len; g.done = s->rows.done; g.n_out = s->rows.n_out; g.max_new_p = s->rows.max_new;
     g.page_table = s->page_table; g.spare = s->beam.spare; g.copy_src = s->beam.csrc; g.copy_dst = s->beam.cdst; g.copy_ntok = s->beam.cntok;
     g.grp_shared = s->grp_shared;
     g.tr_tok = s->beam.tr_tok; g.tr_par = s->beam.tr_par; g.tr_score = s->beam.tr_score; g.tr_lse = s->beam.tr_lse; g.tc_idx = s->beam.tc_idx;
@@ -459,8 +460,7 @@ int run_group_fork(emmax_session* s, int G, hipStream_t st) {
     }
     GroupForkParams f;
     memset(&f, 0, sizeof(f));
-    f.N = N; f.max_pages = s->max_pages; f.page_table = s->page_table;
-    f.ctx_len = s->ctx_len; f.done = s->done; f.n_out = s->n_out; f.max_new = s->max_new_d; f.stop_m = s->stop_m; f.stop_after = s->stop_after;
+    f.N = N; f.max_pages = s->max_pages; f.page_table = s->page_table; f.st = s->rows;
     f.copy_src = s->beam.csrc; f.copy_dst = s->beam.cdst; f.copy_ntok = s->beam.cntok; f.grp_shared = s->grp_shared;
     bool partial = false;
     for (int g = 0; g < G; ++g) {
@@ -488,17 +488,14 @@ int run_group_fork(emmax_session* s, int G, hipStream_t st) {
 int run_slots_fork(emmax_session* s, int src, int logit_row, const int32_t* dst, int n, hipStream_t st) {
     SlotForkParams f;
     memset(&f, 0, sizeof(f));
-    f.n = n; f.rows = s->cur_B; f.src = src; f.S = s->S[src]; f.max_pages = s->max_pages; f.max_prompt = s->max_prompt;
+    f.n = n; f.rows = s->cur_B; f.src = src; f.S = s->S[src]; f.max_pages = s->max_pages;
     for (int j = 0; j < n; ++j) f.dst[j] = dst[j];
-    f.page_table = s->page_table; f.hidden = s->hidden;
-    f.ctx_len = s->ctx_len; f.done = s->done; f.n_out = s->n_out; f.max_new = s->max_new_d; f.stop_m = s->stop_m; f.stop_after = s->stop_after;
+    f.page_table = s->page_table; f.hidden = s->hidden; f.st = s->rows;
+    if (int r = session_row_cols(s, &f.cols)) return r;   // (the kernel copies the inherited ones)
     f.copy_src = s->beam.csrc; f.copy_dst = s->beam.cdst; f.copy_ntok = s->beam.cntok;
     f.in_t = s->fork_t; f.in_p = s->fork_p; f.in_k = s->fork_k; f.in_seed = s->fork_seed; f.in_sub = s->fork_sub;
     f.temperature = s->samp.t; f.top_p = s->samp.p; f.top_k = s->samp.k; f.seed = s->samp.seed; f.subseq = s->samp.sub;
-    if (s->proc.on) { f.penalty = s->proc.pen; f.ngram = s->proc.ng; f.min_new = s->proc.mn; f.hist = s->proc.hist; f.hist_len = s->proc.hist_len; }
-    if (s->warp.on) { f.warp[0] = s->warp.minp; f.warp[1] = s->warp.typ; f.warp[2] = s->warp.eps; f.warp[3] = s->warp.eta; }
-    if (s->rules.on) f.rule_en = s->rules.en;
-    if (s->aut.on) { f.aut_start = s->aut.start; f.aut_state = s->aut.state; }
+    if (s->aut.on) { f.aut_start = s->aut.start; f.aut_state = s->aut.state; }   // a follower enters at the source's start state
     KCHK(launch_slots_fork(f, st));
     if (f.S % PAGE != 0)   // (else the prompt ends on a page boundary: every page is shared by reference, nothing to copy)
         if (int r = launch_page_copies(s, n, st)) return r;
@@ -575,7 +572,7 @@ int run_decode_stage(emmax_session* s, int B, int li, int stage, hipStream_t st)
         memset(&a, 0, sizeof(a));
         a.q = s->dq; a.ldq = m->q_dim; a.kcache = kcache_of(s, li); a.vcache = vcache_of(s, li);
         if (s->kv8) { a.kv_stage = s->kv_stage; a.kscale = kscale_of(s, li); a.vscale = vscale_of(s, li); }
-        a.page_table = s->page_table; a.ctx_len = s->ctx_len; a.done = s->done; a.part = s->part; a.Hkv = c.n_kv_heads; a.page = PAGE;
+        a.page_table = s->page_table; a.ctx_len = s->rows.ctx_len; a.done = s->rows.done; a.part = s->part; a.Hkv = c.n_kv_heads; a.page = PAGE;
         a.max_pages = s->max_pages; a.scale = 1.0f / sqrtf((float)c.head_dim);
         a.o_out = attn_direct_on(s, B) ? s->datt : nullptr;
         const int ns = decode_attn_nsplit(B, c.n_kv_heads);
@@ -614,10 +611,10 @@ static int run_qkv0_with_embed(emmax_session* s, int B, hipStream_t st) {
     GemvParams p;
     stage_params(s, B, 0, STAGE_QKV, p);
     p.W = m->layers[0].proj[STAGE_QKV].rm;
-    p.x = m->embed; p.x_tok = s->cur_tok; p.x_copy = s->dh; p.x_vocab = m->vocab;
+    p.x = m->embed; p.x_tok = s->rows.cur_tok; p.x_copy = s->dh; p.x_vocab = m->vocab;
     const int r = launch_decode_ks(GEMV_QKV, p, B, st, nullptr);
     if (r == -2) {
-        KCHK(launch_decode_embed(s->cur_tok, m->embed, s->dh, B, m->H, m->vocab, st, s->exact ? s->dh32 : h32_of(s)));
+        KCHK(launch_decode_embed(s->rows.cur_tok, m->embed, s->dh, B, m->H, m->vocab, st, s->exact ? s->dh32 : h32_of(s)));
         return run_decode_stage(s, B, 0, STAGE_QKV, st);
     }
     return r ? fail(EMMAX_ERR_HIP, "qkv launch of layer 0 failed (code %d)", r) : 0;
@@ -627,7 +624,7 @@ int run_decode_step(emmax_session* s, int B, hipStream_t st) {
     emmax_model* m = s->m;
     // batch 1-2 on bf16 weights: the embedding row is read by layer 0's qkv launch itself (decode_ks.hip, when it takes the launch) -- one launch fewer
     const bool fold_embed = B < EMMAX_MFMA_MIN_BATCH && !m->fp8 && !m->mx4 && decode_ks_enabled() && emmax_tune().fold_embed != 0;
-    if (!fold_embed) KCHK(launch_decode_embed(s->cur_tok, m->embed, s->dh, B, m->H, m->vocab, st, s->exact ? s->dh32 : h32_of(s)));
+    if (!fold_embed) KCHK(launch_decode_embed(s->rows.cur_tok, m->embed, s->dh, B, m->H, m->vocab, st, s->exact ? s->dh32 : h32_of(s)));
     const bool taps = s->taps.step.on;   // (nothing bound: the launches below are all there is)
     if (taps)
         if (int r = tap_step_hidden(s, 0, B, st)) return r;
