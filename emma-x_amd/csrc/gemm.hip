@@ -34,6 +34,8 @@
 // per row): 2.4x the chip-wide store throughput of accumulator-layout stores, which had made the epilogue of a K = 1024
 // tile a third of its time.  The next tile's first K step is requested before the epilogue, so its latency (and the block
 // re-launch a one-tile-per-block grid would pay) hides under the stores.
+#include <cstdarg>
+#include <cstdio>
 #include <type_traits>
 
 #include "common.h"
@@ -440,9 +442,7 @@ __global__ __launch_bounds__(G::NW * 64, 2) void emmax_gemm_bf16_kernel(GemmPara
     auto ldA = [&](const unsigned char* st, int s_) { return *(const bf16x8_t*)(st + offA + (s_ % MT) * 2048 + ((s_ / MT) ? (c0 ^ 64) : c0)); };
     auto ldB = [&](const unsigned char* st, int kk, int j) { return *(const bf16x8_t*)(st + offB + j * 2048 + (kk ? (c0 ^ 64) : c0)); };
 
-    const bool staged_ok = (p.ldc & 7) == 0 && (((size_t)p.C) & 15) == 0 && !(p.dbg & 8) &&
-                           (ACT == 2 ? (p.N & 15) == 0 : (min(p.N, p.N_store) & 7) == 0) &&   // 16-byte row-layout stores possible
-                           (!p.residual || ((p.ldr & 3) == 0 && (((size_t)p.residual) & 7) == 0));   // ... and 8-byte residual requests
+    const bool staged_ok = gemm_staged_ok(p, ACT);   // (kernels.h: 16-byte row-layout stores and 8-byte residual requests possible)
     int it = blockIdx.x >> 3;
     if (it >= run_n) return;
 #ifdef GEMM_LAB_TRACE
@@ -716,9 +716,7 @@ __global__ __launch_bounds__(256, 2) void emmax_gemm_k32_kernel(GemmParams p) {
     auto ldA = [&](const unsigned char* st, int i) { return *(const bf16x8_t*)(st + offA + i * 1024); };
     auto ldB = [&](const unsigned char* st, int j) { return *(const bf16x8_t*)(st + offB + j * 1024); };
 
-    const bool staged_ok = (p.ldc & 7) == 0 && (((size_t)p.C) & 15) == 0 &&
-                           (ACT == 2 ? (p.N & 15) == 0 : (min(p.N, p.N_store) & 7) == 0) &&
-                           (!p.residual || ((p.ldr & 3) == 0 && (((size_t)p.residual) & 7) == 0));
+    const bool staged_ok = gemm_staged_ok(p, ACT);   // (kernels.h: 16-byte row-layout stores and 8-byte residual requests possible)
     int it = blockIdx.x >> 3;
     if (it >= run_n) return;
     int m0, n0;
@@ -788,9 +786,44 @@ __global__ __launch_bounds__(256, 2) void emmax_gemm_k32_kernel(GemmParams p) {
     }
 }
 
+// gemm_list_launches: while `rec` is set (host only, this thread), every launcher below writes the launch it would make as a line of text
+// instead of making it -- the list comes from the code that launches, so the two cannot disagree.  `root`: the whole problem (part offsets)
+struct GemmRecorder { const GemmParams* root; char* buf; int len, used, count; };
+thread_local GemmRecorder* rec = nullptr;
+
+void rec_line(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    if (rec->used < rec->len) {
+        const int n = vsnprintf(rec->buf + rec->used, rec->len - rec->used, fmt, ap);
+        rec->used = n < 0 || n >= rec->len - rec->used ? rec->len : rec->used + n;   // (full: gemm_list_launches reports it)
+    }
+    va_end(ap);
+    rec->count += 1;
+}
+// a tile kernel: its instantiation (the GemmForm it was dispatched on), the part of the root problem it covers, its K slices in K steps
+void rec_gemm(const GemmForm& f, const GemmParams& q, int bk, int grid) {
+    const GemmParams& r = *rec->root;
+    const long r0 = (long)(((const bf16_t*)q.A - (const bf16_t*)r.A) / r.lda), n0 = (long)(((const bf16_t*)q.W - (const bf16_t*)r.W) / r.ldw);
+    static const char* const geom[] = {"small", "big", "k32"};
+    static const char* const epi[] = {"staged", "direct-vec", "direct-elt"};
+    char sl[160];
+    int u = 0;
+    const int ks = q.ksplit > 1 ? q.ksplit : 1, nk_all = q.K / bk, nk_slice = (nk_all + ks - 1) / ks;
+    for (int s = 0; s < ks && u < (int)sizeof(sl) - 24; ++s) {
+        const int b = s * nk_slice, e = b + nk_slice < nk_all ? b + nk_slice : nk_all;
+        u += snprintf(sl + u, sizeof(sl) - u, "%s%d..%d", s ? "," : "", b, e);
+    }
+    rec_line("gemm geom=%s act=%d out=%s ln=%d deep=%d epi=%s rows=%ld..%ld cols=%ld..%ld ks=%d ksteps=%s hl=%d lnrt=%d res=%s grid=%d\n", geom[f.geom], f.act,
+             f.out_f32 ? "f32" : "bf16", f.ln, f.deep, epi[f.epi], r0, r0 + q.M, n0, n0 + q.N, ks, sl, q.a_hl, q.ln_stats ? 1 : 0,
+             !q.residual ? "none" : q.res_f32 ? "f32" : "bf16", grid);
+}
+
 template <int ACT, bool OUT_F32, bool LN = false>
-int launch_k32_t(const GemmParams& p, hipStream_t stream) {
+int launch_k32_t(const GemmForm& f, const GemmParams& p, hipStream_t stream) {
     auto kern = emmax_gemm_k32_kernel<ACT, OUT_F32, LN>;
+    const int tiles_ = cdiv(p.M, GeomK32::BM) * cdiv(p.N, GeomK32::BN) * (p.ksplit > 1 ? p.ksplit : 1);
+    if (rec) { rec_gemm(f, p, K32_BK, tiles_ < 512 ? (tiles_ + 7) / 8 * 8 : 512); return 0; }
     static bool attr_done = false;   // per instantiation
     if (!attr_done) {
         if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, K32_SMEM) != hipSuccess) return -4;
@@ -804,12 +837,14 @@ int launch_k32_t(const GemmParams& p, hipStream_t stream) {
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), K32_SMEM, stream, q);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
-int launch_k32(const GemmParams& p, hipStream_t stream) {
-    if (p.K % K32_BK) return -1;
-    if (p.act == 2) return p.out_f32 ? -1 : launch_k32_t<2, false>(p, stream);
-    if (p.ln_stats && !p.out_f32) return p.act == 1 ? launch_k32_t<1, false, true>(p, stream) : launch_k32_t<0, false, true>(p, stream);
-    if (p.act == 1) return p.out_f32 ? launch_k32_t<1, true>(p, stream) : launch_k32_t<1, false>(p, stream);
-    return p.out_f32 ? launch_k32_t<0, true>(p, stream) : launch_k32_t<0, false>(p, stream);
+// the one instantiation whose template arguments EQUAL the form's fields (gemm_form never hands out another combination: -1)
+int launch_k32(const GemmForm& f, const GemmParams& p, hipStream_t stream) {
+#define K32_FORM(ACT, F32, LN) if (f.act == ACT && f.out_f32 == (F32 ? 1 : 0) && f.ln == (LN ? 1 : 0)) return launch_k32_t<ACT, F32, LN>(f, p, stream);
+    K32_FORM(2, false, false)
+    K32_FORM(0, false, true) K32_FORM(1, false, true)
+    K32_FORM(0, false, false) K32_FORM(0, true, false) K32_FORM(1, false, false) K32_FORM(1, true, false)
+#undef K32_FORM
+    return -1;
 }
 
 // split-K second pass: C[m, n..n+8) = epi(sum over slices of ws[s][m][..)); one thread per 8 OUTPUT columns, whole rows in order.
@@ -990,28 +1025,15 @@ __global__ __launch_bounds__(256) void emmax_splitk_reduce_norm_kernel(GemmParam
 }
 
 template <class G, int ACT, bool OUT_F32, bool LN = false, int DEEP = 0>
-int launch_t(const GemmParams& p, hipStream_t stream) {
-    if constexpr (DEEP == 0) {
-        // Main-loop variant by geometry (tuning switch gemm_deep = -1; 0 = two stages of both operands, one barrier per K step, as in
-        // rounds 1-3; 1 = deep A ring; 3 = staggered wave groups).  Measured, interleaved A/B per shape on one box
-        // (profiles/r04_gemm_deep_ab.txt, r04_gemm_pp_ab.txt): the 256 x 256 tile gains 1-14 % on EVERY shape with the staggered
-        // schedule (8192^3 1385 -> 1493 TFLOP/s, ViT shapes +7 .. 14 %, LLaMA prefill B = 8 +1 .. 4 %), more than with the deep A ring
-        // (ViT +3 .. 10 %, LLaMA -4 %); the 128 x 128 tile (two blocks of four waves per CU: nothing to stagger) gains 25-30 % per launch
-        // with the deep A ring.
-        int deep = emmax_tune().gemm_deep;
-        constexpr bool big = std::is_same<G, GeomBig>::value;
-        if (deep < 0) deep = big ? 3 : 1;
-        // (round 5: fp32 results take the staggered loop too -- the direct epilogue needs no LDS window; they had been left on the
-        // two-stage loop, which cost the fp32 residual stream of an eight-frame prefill 4 %)
-        if (deep == 3 && !big) deep = 1;
-        if (deep == 1) return launch_t<G, ACT, OUT_F32, LN, 1>(p, stream);
-        if constexpr (big) {
-            if (deep == 3) return launch_t<G, ACT, OUT_F32, LN, 3>(p, stream);
-        }
-    }
+int launch_t(const GemmForm& f, const GemmParams& p, hipStream_t stream) {
     auto kern = emmax_gemm_bf16_kernel<G, ACT, OUT_F32, LN, DEEP>;
     constexpr int SMEM = DEEP ? G::SMEM_A3 : G::SMEM;
     static_assert(DEEP != 2, "the deep W ring (round 4: never faster than the deep A ring) is not instantiated");
+    if (rec) {
+        const int tiles_ = cdiv(p.M, G::BM) * cdiv(p.N, G::BN) * (p.ksplit > 1 ? p.ksplit : 1), resident_ = 256 * (160 * 1024 / SMEM);
+        rec_gemm(f, p, BK, tiles_ < resident_ ? (tiles_ + 7) / 8 * 8 : resident_);
+        return 0;
+    }
     static bool attr_done = false;   // per instantiation
     if (!attr_done) {
         if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess) return -4;
@@ -1027,13 +1049,24 @@ int launch_t(const GemmParams& p, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
+// the one instantiation whose template arguments EQUAL the form's fields (gemm_form never hands out another combination: -1)
+template <class G, int ACT, bool OUT_F32, bool LN>
+int launch_deep(const GemmForm& f, const GemmParams& p, hipStream_t stream) {
+    if (f.deep == 0) return launch_t<G, ACT, OUT_F32, LN, 0>(f, p, stream);
+    if (f.deep == 1) return launch_t<G, ACT, OUT_F32, LN, 1>(f, p, stream);
+    if constexpr (std::is_same<G, GeomBig>::value) {
+        if (f.deep == 3) return launch_t<G, ACT, OUT_F32, LN, 3>(f, p, stream);
+    }
+    return -1;
+}
 template <class G>
-int launch_geom(const GemmParams& p, hipStream_t stream) {
-    if (p.act == 2) return p.out_f32 ? launch_t<G, 2, true>(p, stream) : launch_t<G, 2, false>(p, stream);
-    if (p.ln_stats && !p.out_f32)   // LayerNorm folded in: the staged epilogue's LN form (an unaligned C falls to the direct epilogue, which reads p.ln_*)
-        return p.act == 1 ? launch_t<G, 1, false, true>(p, stream) : launch_t<G, 0, false, true>(p, stream);
-    if (p.act == 1) return p.out_f32 ? launch_t<G, 1, true>(p, stream) : launch_t<G, 1, false>(p, stream);
-    return p.out_f32 ? launch_t<G, 0, true>(p, stream) : launch_t<G, 0, false>(p, stream);
+int launch_geom(const GemmForm& f, const GemmParams& p, hipStream_t stream) {
+#define GEMM_FORM(ACT, F32, LN) if (f.act == ACT && f.out_f32 == (F32 ? 1 : 0) && f.ln == (LN ? 1 : 0)) return launch_deep<G, ACT, F32, LN>(f, p, stream);
+    GEMM_FORM(2, true, false) GEMM_FORM(2, false, false)
+    GEMM_FORM(0, false, true) GEMM_FORM(1, false, true)   // LayerNorm folded in: the staged epilogue's LN form
+    GEMM_FORM(0, false, false) GEMM_FORM(0, true, false) GEMM_FORM(1, false, false) GEMM_FORM(1, true, false)
+#undef GEMM_FORM
+    return -1;
 }
 
 }  // namespace
@@ -1041,15 +1074,46 @@ int launch_geom(const GemmParams& p, hipStream_t stream) {
 // number of 256x256 tiles of the problem
 int gemm_big_tiles(const GemmParams& p) { return cdiv(p.M, GeomBig::BM) * cdiv(p.N, GeomBig::BN); }
 
+// The instantiation a launch takes, from the parameter block and the tuning switches alone (host only; emmax_gemm_launches prints it).
+// launch_gemm_geom dispatches on this struct, so what the plan says and what runs cannot differ.  false = a shape the launcher refuses.
+bool gemm_form(const GemmParams& p, int big, GemmForm* f) {
+    if (p.M <= 0) return false;
+    if (p.K % BK != 0 || p.N % 128 != 0 || p.K <= 0 || p.N <= 0) return false;
+    if ((p.lda % 8) || (p.ldw % 8)) return false;
+    big = big == 2 ? 2 : big ? 1 : 0;
+    if (p.ln_stats && (!p.ln_s || !p.ln_c || p.bias || p.scale || p.residual || p.act == 2 || p.ksplit > 1)) return false;
+    if (p.res_f32 && (!p.out_f32 || !p.residual || p.act == 2)) return false;   // the fp32 residual stream yields an fp32 result
+    if (p.a_hl && (p.a_hl != 1 || p.K % (2 * BK) || p.ln_stats || big == 2)) return false;   // (hi, lo) pairs of K steps; no folded LayerNorm, no 32-deep tile
+    if (big == 2 && (p.K % K32_BK || (p.act == 2 && p.out_f32))) return false;               // 128 x 256 x 32: no fp32 SwiGLU
+    f->geom = big;
+    f->act = p.act == 2 ? 2 : p.act == 1 ? 1 : 0;
+    f->out_f32 = p.out_f32 ? 1 : 0;
+    // LayerNorm folded in: the staged epilogue's LN form (an fp32 or unaligned C falls to the direct epilogue, which reads p.ln_* at run time)
+    f->ln = (p.ln_stats && !p.out_f32) ? 1 : 0;
+    // Main-loop variant by geometry (tuning switch gemm_deep = -1; 0 = two stages of both operands, one barrier per K step, as in
+    // rounds 1-3; 1 = deep A ring; 3 = staggered wave groups).  Measured, interleaved A/B per shape on one box
+    // (profiles/r04_gemm_deep_ab.txt, r04_gemm_pp_ab.txt): the 256 x 256 tile gains 1-14 % on EVERY shape with the staggered
+    // schedule (8192^3 1385 -> 1493 TFLOP/s, ViT shapes +7 .. 14 %, LLaMA prefill B = 8 +1 .. 4 %), more than with the deep A ring
+    // (ViT +3 .. 10 %, LLaMA -4 %); the 128 x 128 tile (two blocks of four waves per CU: nothing to stagger) gains 25-30 % per launch
+    // with the deep A ring.
+    // (round 5: fp32 results take the staggered loop too -- the direct epilogue needs no LDS window; they had been left on the
+    // two-stage loop, which cost the fp32 residual stream of an eight-frame prefill 4 %)
+    int deep = emmax_tune().gemm_deep;
+    if (deep < 0) deep = big == 1 ? 3 : 1;
+    if (deep == 3 && big != 1) deep = 1;
+    f->deep = big == 2 ? 0 : (deep == 1 || deep == 3) ? deep : 0;   // (k32: one main loop)
+    GemmParams q = p;
+    q.dbg |= emmax_tune().gemm_dbg;   // (what the launchers hand to the kernel)
+    f->epi = (!p.out_f32 && gemm_staged_ok(q, f->act)) ? GEMM_EPI_STAGED : (p.ldc & 3) == 0 ? GEMM_EPI_DIRECT_VEC : GEMM_EPI_DIRECT_ELT;
+    return true;
+}
+
 int launch_gemm_geom(const GemmParams& p, int big, hipStream_t stream) {
     if (p.M <= 0) return 0;
-    if (p.K % BK != 0 || p.N % 128 != 0 || p.K <= 0 || p.N <= 0) return -1;
-    if ((p.lda % 8) || (p.ldw % 8)) return -1;
-    if (p.ln_stats && (!p.ln_s || !p.ln_c || p.bias || p.scale || p.residual || p.act == 2 || p.ksplit > 1)) return -1;
-    if (p.res_f32 && (!p.out_f32 || !p.residual || p.act == 2)) return -1;   // the fp32 residual stream yields an fp32 result
-    if (p.a_hl && (p.a_hl != 1 || p.K % (2 * BK) || p.ln_stats || big == 2)) return -1;   // (hi, lo) pairs of K steps; no folded LayerNorm, no 32-deep tile
-    if (big == 2) return launch_k32(p, stream);   // 128 x 256 x 32, two blocks per CU
-    return big ? launch_geom<GeomBig>(p, stream) : launch_geom<GeomSmall>(p, stream);
+    GemmForm f;
+    if (!gemm_form(p, big, &f)) return -1;
+    if (f.geom == 2) return launch_k32(f, p, stream);   // 128 x 256 x 32, two blocks per CU
+    return f.geom ? launch_geom<GeomBig>(f, p, stream) : launch_geom<GeomSmall>(f, p, stream);
 }
 
 // ---- launch plan ------------------------------------------------------------------------------------------------------
@@ -1152,6 +1216,9 @@ int launch_gemm_splitk(const GemmParams& p, int ks, hipStream_t stream, int big)
     if (p.act == 2 && (p.out_f32 || (p.N & 31))) return -1;
     if ((long long)ks * p.M * p.N * 4 > p.ws_bytes) return -1;
     if (p.K / BK < ks) return -1;
+    // every slice needs a K step of its own: slice s starts at s * ceil(nk / ks), and a slice that starts past K (nk = 5, ks = 4: slices of 2
+    // steps, the fourth starts at step 6) would request rows of A and W beyond column K before it finds its step count negative
+    if ((ks - 1) * cdiv(p.K / BK, ks) >= p.K / BK) return -1;
     // (the tools' geometry override gemm_sk_big is applied where the plan is made -- plan_gemm, kind SPLITK -- not here: the HYBRID column
     // remainder is planned for small tiles and its slice count was chosen for them)
     GemmParams a = p;
@@ -1164,8 +1231,21 @@ int launch_gemm_splitk(const GemmParams& p, int ks, hipStream_t stream, int big)
     b.ksplit = ks;
     const size_t groups = (size_t)p.M * ((p.act == 2 ? p.N >> 1 : p.N) >> 3);
     const int grid = (int)((groups + 255) / 256 < 2048 ? (groups + 255) / 256 : 2048);
+    if (p.norm_out && !splitk_norm_ok(p)) return -1;
+    if (rec) {   // the reduce pass of this part: its instantiation and the branch its stores take
+        const GemmParams& r = *rec->root;
+        const long r0 = (long)(((const bf16_t*)p.A - (const bf16_t*)r.A) / r.lda), n0 = (long)(((const bf16_t*)p.W - (const bf16_t*)r.W) / r.ldw);
+        const bool vec = p.out_f32 ? (p.ldc & 3) == 0 && (((size_t)p.C) & 15) == 0 : (p.ldc & 7) == 0 && (((size_t)p.C) & 15) == 0;
+        const bool vec_r = p.residual && (p.res_f32 ? (p.ldr & 3) == 0 : (p.ldr & 7) == 0) && (((size_t)p.residual) & 15) == 0;
+        char name[32];
+        if (p.norm_out) snprintf(name, sizeof name, "reduce_norm_%s", p.res_f32 ? "f32" : "bf16");
+        else snprintf(name, sizeof name, "reduce%d", p.act == 2 ? 2 : p.act == 1 ? 1 : 0);
+        rec_line("%s out=%s store=%s res=%s%s rows=%ld..%ld cols=%ld..%ld ks=%d\n", name, p.out_f32 ? "f32" : "bf16", p.norm_out || vec ? "vec" : "elt",
+                 !p.residual ? "none" : p.res_f32 ? "f32" : "bf16", !p.residual || p.act == 2 ? "" : p.norm_out || vec_r ? "-vec" : "-elt", r0, r0 + p.M, n0,
+                 n0 + p.N, ks);
+        return 0;
+    }
     if (p.norm_out) {
-        if (!splitk_norm_ok(p)) return -1;
         if (p.res_f32) hipLaunchKernelGGL((emmax_splitk_reduce_norm_kernel<8, true>), dim3((p.M + 3) / 4), dim3(256), 0, stream, b);
         else hipLaunchKernelGGL((emmax_splitk_reduce_norm_kernel<8, false>), dim3((p.M + 3) / 4), dim3(256), 0, stream, b);
     } else if (p.act == 2) hipLaunchKernelGGL(emmax_splitk_reduce_kernel<2>, dim3(grid), dim3(256), 0, stream, b);
@@ -1310,4 +1390,15 @@ int launch_gemm(const GemmParams& p, hipStream_t stream) {
     if (r) return r;
     if (pl.kind == GemmPlan::HYBRID) return (p.act == 2 || b.N_store > 0) ? launch_gemm_splitk(b, pl.ks, stream) : 0;
     return b.N_store > 0 ? launch_gemm_geom(b, 0, stream) : 0;
+}
+
+int gemm_list_launches(const GemmParams& p, int ksplit, char* buf, int len) {
+    if (!buf || len < 1) return -1;
+    GemmRecorder r = {&p, buf, len, 0, 0};
+    buf[0] = 0;
+    rec = &r;
+    const int rc = ksplit == 0 ? launch_gemm(p, nullptr) : launch_gemm_splitk(p, ksplit, nullptr, emmax_tune().gemm_sk_big > 0 ? 1 : 0);   // (as the op entry points)
+    rec = nullptr;
+    if (rc || r.used >= len) return -1;   // refused, or the text did not fit
+    return r.count;
 }

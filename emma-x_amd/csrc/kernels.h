@@ -51,6 +51,24 @@ struct GemmParams {
     int dbg;               // tools only: 1 = skip the operand DMA after K step 1 (LDS + MFMA time alone), 2 = skip the stores
     long long* trace;      // tools only (tools/gemm_trace.hip): block 0 writes wall_clock64() stamps per tile phase; null in the product
 };
+// bf16 results leave through the staged epilogue (whole rows through a wave's LDS window, 16-byte stores) when this holds, else through the
+// direct one.  ONE predicate: both GEMM kernels evaluate it on the device, gemm_form on the host (act: the kernel's ACT)
+__host__ __device__ inline bool gemm_staged_ok(const GemmParams& p, int act) {
+    const int n_ok = p.N < p.N_store ? p.N : p.N_store;
+    return (p.ldc & 7) == 0 && (((size_t)p.C) & 15) == 0 && !(p.dbg & 8) &&
+           (act == 2 ? (p.N & 15) == 0 : (n_ok & 7) == 0) &&                                         // 16-byte row-layout stores possible
+           (!p.residual || ((p.ldr & 3) == 0 && (((size_t)p.residual) & 7) == 0));                  // ... and 8-byte residual requests
+}
+// the instantiation launch_gemm_geom takes (it dispatches on this struct; emmax_gemm_launches prints it) and the epilogue the kernel will then
+// take at run time.  Host only, from the parameter block and the tuning switches gemm_deep / gemm_dbg.
+//   geom  0 = 128 x 128 x 64, 1 = 256 x 256 x 64, 2 = 128 x 256 x 32        act, out_f32, ln, deep: the kernel's template arguments
+//   epi   GEMM_EPI_STAGED, or the direct epilogue with 8- / 16-byte stores (ldc % 4 == 0) or element by element
+enum { GEMM_EPI_STAGED = 0, GEMM_EPI_DIRECT_VEC = 1, GEMM_EPI_DIRECT_ELT = 2 };
+struct GemmForm { int geom, act, out_f32, ln, deep, epi; };
+bool gemm_form(const GemmParams& p, int big, GemmForm* f);                   // false = a shape launch_gemm_geom refuses
+// every kernel launch launch_gemm(p) (ksplit = 0) or launch_gemm_splitk(p, ksplit) would make, one line each, WITHOUT launching: the launchers
+// themselves run with their launches diverted into the text.  Returns the number of launches, -1 = refused (host only)
+int gemm_list_launches(const GemmParams& p, int ksplit, char* buf, int len);
 int launch_gemm(const GemmParams& p, hipStream_t stream);                     // picks the 256x256 or the 128x128 tile geometry
 int launch_gemm_geom(const GemmParams& p, int big, hipStream_t stream);       // explicit geometry (tools, tests)
 int gemm_big_tiles(const GemmParams& p);

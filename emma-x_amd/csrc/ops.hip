@@ -172,6 +172,27 @@ int emmax_gemm_plan(int M, int N, int K, int act, int out_f32, int has_ln, int h
     if (r < 0) return fail(EMMAX_ERR_INVALID, "emmax_gemm_plan: unsupported shape (K%%64, N%%128)");
     return 0;
 }
+int emmax_gemm_launches(int M, int N, int K, int act, int out_f32, int has_ln, int has_residual, int with_norm, int64_t ws_bytes, int has_bias, int has_scale,
+                        int lda, int ldw, int ldc, int ldr, int n_store, int a_hl, int c_align, int res_align, int ksplit, char* text_out, int text_len) {
+    if (!text_out || text_len < 16) return fail(EMMAX_ERR_INVALID, "emmax_gemm_launches: text buffer of at least 16 bytes");
+    if (c_align < 0 || c_align > 15 || res_align < 0 || res_align > 15 || lda < 1 || ldw < 1)
+        return fail(EMMAX_ERR_INVALID, "emmax_gemm_launches: alignments are addresses modulo 16 (0..15), pitches positive");
+    // the launchers look at sizes, pitches, alignments and which operands exist -- never through a pointer; A and W get bases of their own
+    // because the parts of a plan are told apart by their offsets from them
+    void* const any = (void*)(uintptr_t)256;
+    GemmParams p = gp((void*)((uintptr_t)1 << 40), lda, (void*)((uintptr_t)1 << 41), ldw, (void*)(((uintptr_t)1 << 42) + c_align), ldc, M, N, K);
+    p.act = act; p.out_f32 = out_f32; p.N_store = n_store; p.a_hl = a_hl;
+    if (has_bias) p.bias = any;
+    if (has_scale) p.scale = any;
+    if (has_residual) { p.residual = (void*)(((uintptr_t)1 << 43) + res_align); p.ldr = ldr; p.res_f32 = has_residual == 2; }
+    if (has_ln) { p.ln_stats = (const float*)any; p.ln_s = (const float*)any; p.ln_c = (const float*)any; }
+    if (ws_bytes > 0) { p.ws = (float*)any; p.ws_bytes = ws_bytes; }
+    if (with_norm) { p.norm_w = any; p.norm_out = any; p.ld_norm = N; p.norm_eps = 1e-5f; }
+    if (with_norm && ksplit == 0 && !gemm_fuses_norm(p)) { p.norm_w = nullptr; p.norm_out = nullptr; }   // (as emmax_gemm_plan: the caller then runs the norm itself)
+    const int n = gemm_list_launches(p, ksplit, text_out, text_len);
+    if (n < 0) return fail(EMMAX_ERR_INVALID, "emmax_gemm_launches: the launchers refuse this problem (or the text buffer is too small)");
+    return n;
+}
 int emmax_op_gemm_ln(const void* X, int ldx, void* W, int ldw, void* C, int ldc, int M, int N, int K, const void* gamma, const void* beta,
                      const void* bias, float eps, int act, float* stats_ws, float* ln_s_ws, float* ln_c_ws, emmax_stream stream) {
     if (!X || !W || !C || !gamma || !stats_ws || !ln_s_ws || !ln_c_ws) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_ln: null argument");

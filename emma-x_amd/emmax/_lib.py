@@ -99,6 +99,7 @@ SIGNATURES = {
     "emmax_op_gemm_splitk": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp,
                                        C.c_int, C.c_int, C.c_int, _vp, C.c_int64, _vp]),
     "emmax_gemm_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_char_p, C.c_int]),
+    "emmax_gemm_launches": (C.c_int, [C.c_int] * 8 + [C.c_int64] + [C.c_int] * 11 + [C.c_char_p, C.c_int]),
     "emmax_op_gemm_ln": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_float, C.c_int, _vp, _vp, _vp, _vp]),
     "emmax_op_layernorm": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_float, _vp]),
     "emmax_op_rmsnorm": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_float, _vp]),
@@ -264,6 +265,21 @@ def gemm_plan(M: int, N: int, K: int, act: int = 0, out_f32: bool = False, ln: b
     buf = C.create_string_buffer(256)
     check(load().emmax_gemm_plan(M, N, K, act, int(out_f32), int(ln), int(residual), int(norm), ws_bytes, buf, 256), "emmax_gemm_plan")
     return buf.value.decode()
+
+
+def gemm_launches(M: int, N: int, K: int, act: int = 0, out_f32: bool = False, ln: bool = False, residual: int = 0, norm: bool = False,
+                  ws_bytes: int = 0, bias: bool = False, scale: bool = False, lda: int = 0, ldw: int = 0, ldc: int = 0, ldr: int = 0,
+                  n_store: int = 0, a_hl: int = 0, c_align: int = 0, res_align: int = 0, ksplit: int = 0):
+    """Every kernel launch of a GEMM call, one line of text each (include/emmax.h: emmax_gemm_launches; host only -- runs without a GPU).
+    Pitches default to the dense ones.  None: the launchers refuse the problem."""
+    buf = C.create_string_buffer(4096)
+    n = load().emmax_gemm_launches(M, N, K, act, int(out_f32), int(ln), int(residual), int(norm), ws_bytes, int(bias), int(scale), lda or K, ldw or (K >> a_hl),
+                                   ldc or (N // 2 if act == 2 else N), ldr or N, n_store or N, a_hl, c_align, res_align, ksplit, buf, 4096)
+    if n < 0:
+        return None
+    lines = buf.value.decode().splitlines()
+    assert len(lines) == n, (n, lines)
+    return lines
 
 
 class tuning:

@@ -50,7 +50,7 @@ extern "C" {
  *   emmax_session_context, emmax_op_extend_attention(_kv8), emmax_op_rope_kv_write_at, emmax_extend_attn_plan): new symbols only, the workspace
  *   grew one int32 per decode row; still 12: taps -- hidden states and attention maps out of the passes (emmax_session_set_pass_taps,
  *   emmax_session_set_step_taps, emmax_session_clear_taps, emmax_session_taps, emmax_op_attn_probs(_kv8), emmax_op_tap_rows): new symbols only, the
- *   workspace did not grow. */
+ *   workspace did not grow; still 12: emmax_gemm_launches (the GEMM's kernel launches as text, host only): a new symbol only. */
 #define EMMAX_ABI_VERSION 12
 
 typedef enum emmax_status {
@@ -674,6 +674,18 @@ int emmax_op_gemm_splitk(const void* A_dev, int lda, const void* W_dev, int ldw,
  * result are fp32 rows -- the prefill's fp32 residual stream (round 5). */
 int emmax_gemm_plan(int M, int N, int K, int act, int out_f32, int has_ln, int has_residual, int with_norm, int64_t ws_bytes, char* text_out,
                     int text_len);
+/* Every kernel launch the same call would make, one line of text each (host only, no device work): the launchers themselves run with
+ * their launches diverted into the text, so the list is what runs.  Beyond emmax_gemm_plan's arguments it takes what the choice of epilogue
+ * looks at -- which of bias / LayerScale exist, the pitches (elements), n_store, a_hl (K is then the width of the two-term rows, 2 x the real
+ * K), the addresses of C and of the residual modulo 16 -- and ksplit (0: the launch plan; >= 2: that many K slices, as emmax_op_gemm_splitk).
+ *   gemm geom=small|big|k32 act=A out=bf16|f32 ln=L deep=D epi=staged|direct-vec|direct-elt rows=a..b cols=c..d ks=S ksteps=b0..e0,b1..e1,...
+ *        hl=H lnrt=R res=none|bf16|f32 grid=G     one tile kernel: its template arguments, the epilogue it takes, the part of the problem it
+ *        covers (weight columns), the K steps of every slice, run-time LayerNorm operands, the residual it reads
+ *   reduce0|reduce1|reduce2|reduce_norm_bf16|reduce_norm_f32 out=.. store=vec|elt res=none|bf16-vec|... rows=.. cols=.. ks=S
+ * Returns the number of launches (>= 0), or EMMAX_ERR_INVALID when the launchers refuse the problem. */
+int emmax_gemm_launches(int M, int N, int K, int act, int out_f32, int has_ln, int has_residual, int with_norm, int64_t ws_bytes, int has_bias,
+                        int has_scale, int lda, int ldw, int ldc, int ldr, int n_store, int a_hl, int c_align, int res_align, int ksplit,
+                        char* text_out, int text_len);
 /* LayerNorm folded into the projection that consumes it, as the ViT qkv / fc1 stages run (timm Block: norm1 -> attn.qkv, norm2 ->
  * mlp.fc1): C[M,N] = act(LN(X; gamma, beta, eps) @ W^T + bias) without materialising LN(X).  W_dev bf16 [N, ldw] is REWRITTEN in
  * place to bf16(W .* gamma) (what emmax_model_finalize does once per model); stats_ws f32 [M][2], ln_s_ws / ln_c_ws f32 [N] are
