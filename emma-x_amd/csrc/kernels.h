@@ -445,6 +445,26 @@ int launch_kv_quant_rows_at(const void* qkv, int ld, int k_off, int v_off, const
                             void* v8, float* kscale, float* vscale, const int32_t* page_table, int max_pages, int Hkv, int hd, int page,
                             hipStream_t stream);
 
+// ---- score.hip: log-sum-exp, one target logit and the argmax of rows x lm-head, no logit stored ----
+struct ScoreParams {
+    const void* X;               // bf16 [rows, ldx]: the finally-normed rows
+    const void* W;               // bf16 [Np, ldw]: the lm-head, Np = V padded to 128
+    const int32_t* targets;      // [rows]: the id whose logit is wanted; outside [0, V) (-100): 0.0f
+    float* ws;                   // three planes [slices][rows]: m, l (fp32), idx (int32)
+    float *lse, *target_logit;   // [rows]
+    int32_t* argmax;             // [rows]
+    int ldx, ldw, rows, V, K;
+    // filled by launch_score_rows from the form
+    float *part_m, *part_l;
+    int32_t* part_i;
+    int row_tiles, col_tiles, slices, tps;
+};
+// what launch_score_rows dispatches on (emmax_score_plan prints it): 128-row tiles, 128-column tiles below V, vocabulary slices, tiles per slice
+struct ScoreForm { int row_tiles, col_tiles, slices, tps; };
+// slices_forced 0: about two blocks per CU, capped by the column tiles and by ws_bytes / (12 rows).  false: a shape, a slice count or a scratch the launcher refuses
+bool score_form(int rows, int V, int K, long long ws_bytes, int slices_forced, ScoreForm* f);
+int launch_score_rows(const ScoreParams& p, const ScoreForm& f, hipStream_t stream);
+
 // ---- taps.hip: what a session hands out of a pass it runs anyway ----
 // rows x H of the residual stream (fp32 rows, or bf16 rows: src_f32 = 0) into fp32 [rows][H]; norm_w != nullptr: the RMSNorm of each row, fp32 throughout.
 // gather (may be null): the source row of row r is gather[r], clamped to gather_rows (a step's embedding rows, read by token id).

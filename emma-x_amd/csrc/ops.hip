@@ -341,6 +341,40 @@ int emmax_extend_attn_plan(int B, int max_n, int max_L, int Hq, int Hkv, int nsp
     if (split_form_out) *split_form_out = f.split;
     return 0;
 }
+// ---- score.hip as a pure op: the scoring launch and its merge ----
+int emmax_score_plan(int rows, int V, int K, int64_t ws_bytes, int* row_tiles_out, int* col_tiles_out, int* slices_out, int* tiles_per_slice_out) {
+    ScoreForm f;
+    if (!score_form(rows, V, K, ws_bytes, 0, &f))
+        return fail(EMMAX_ERR_INVALID, "emmax_score_plan: unsupported (rows >= 1, V >= 1, K a multiple of 64, a scratch of at least 12 x rows bytes)");
+    if (row_tiles_out) *row_tiles_out = f.row_tiles;
+    if (col_tiles_out) *col_tiles_out = f.col_tiles;
+    if (slices_out) *slices_out = f.slices;
+    if (tiles_per_slice_out) *tiles_per_slice_out = f.tps;
+    return 0;
+}
+int emmax_op_score_rows(const void* x_dev, int ldx, const void* W_dev, int ldw, int rows, int V, int Np, int K, const int32_t* targets_dev, int slices, float* ws_dev,
+                        int64_t ws_bytes, float* lse_out_dev, float* target_logit_out_dev, int32_t* argmax_out_dev, emmax_stream st) {
+    const char* who = "emmax_op_score_rows";
+    if (!x_dev || !W_dev || !targets_dev || !ws_dev || !lse_out_dev || !target_logit_out_dev || !argmax_out_dev) return fail(EMMAX_ERR_INVALID, "%s: null argument", who);
+    if (rows < 1 || V < 1) return fail(EMMAX_ERR_INVALID, "%s: rows %d and V %d must be at least 1", who, rows, V);
+    if (K < 64 || K % 64) return fail(EMMAX_ERR_INVALID, "%s: K %d is not a multiple of 64 (one K step of the tile)", who, K);
+    if (Np < V || Np % 128) return fail(EMMAX_ERR_INVALID, "%s: Np %d must be V = %d padded to a multiple of 128 (the kernel reads whole 128-row tiles of W)", who, Np, V);
+    if (ldx < K || ldw < K || ldx % 8 || ldw % 8 || (((uintptr_t)x_dev | (uintptr_t)W_dev) & 15) || ((uintptr_t)ws_dev & 3))
+        return fail(EMMAX_ERR_INVALID, "%s: ldx %d / ldw %d at least K in multiples of 8, x and W 16-byte aligned (16-byte requests)", who, ldx, ldw);
+    const int col_tiles = (V + 127) / 128;
+    if (slices < 0 || slices > col_tiles) return fail(EMMAX_ERR_INVALID, "%s: %d slices outside 0..%d (the 128-column tiles below V = %d)", who, slices, col_tiles, V);
+    ScoreForm f;
+    if (!score_form(rows, V, K, ws_bytes, slices, &f))
+        return fail(EMMAX_ERR_INVALID, "%s: a scratch of %lld bytes is too small for %d slice(s) of %d rows (12 bytes per row and slice)", who, (long long)ws_bytes,
+                    slices ? slices : 1, rows);
+    ScoreParams p;
+    memset(&p, 0, sizeof(p));
+    p.X = x_dev; p.W = W_dev; p.targets = targets_dev; p.ws = ws_dev; p.lse = lse_out_dev; p.target_logit = target_logit_out_dev; p.argmax = argmax_out_dev;
+    p.ldx = ldx; p.ldw = ldw; p.rows = rows; p.V = V; p.K = K;
+    const int r = launch_score_rows(p, f, (hipStream_t)st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "%s: launch failure", who);
+    return 0;
+}
 // cu / base of an extension op on the host: 0 = cu[0] < cu[1] < .. = total_rows, 0 <= base[b], base[b] + n[b] <= limit
 static int extend_op_lengths(const char* who, const int32_t* cu, const int32_t* base, int B, int total_rows, long limit, int* max_n, int* max_L, hipStream_t st) {
     if (B < 1 || B > EMMAX_MAX_DECODE_BATCH || total_rows < B) return fail(EMMAX_ERR_INVALID, "%s: B %d (1..%d), total_rows %d (>= B)", who, B, EMMAX_MAX_DECODE_BATCH, total_rows);

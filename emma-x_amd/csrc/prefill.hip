@@ -272,4 +272,25 @@ int emmax_prefill_logits(emmax_session* s, float* out, emmax_stream stream) {
     return 0;
 }
 
+// the rows emmax_prefill_logits would multiply out, scored in place (score.hip): the same final norm into pxn, then lse / target logit / argmax per
+// row through the split-K scratch (idle between two GEMMs).  Nothing a later step or emmax_prefill_logits reads is touched.
+int emmax_prefill_score(emmax_session* s, const int32_t* targets, float* lse_out, float* target_logit_out, int32_t* argmax_out, emmax_stream stream) {
+    if (!s || !targets || !lse_out || !target_logit_out || !argmax_out) return fail(EMMAX_ERR_INVALID, "null argument");
+    if (!s->prefilled) return fail(EMMAX_ERR_STATE, "emmax_prefill_score: prefill has not run");
+    if (s->exact) return fail(EMMAX_ERR_STATE, "emmax_prefill_score: exact-numerics sessions are not scored (the scoring kernel has no two-term form)");
+    emmax_model* m = s->m;
+    hipStream_t st = (hipStream_t)stream;
+    ScoreForm f;
+    if (!score_form(s->total_rows, m->vocab, m->H, s->splitk_bytes, 0, &f))
+        return fail(EMMAX_ERR_INVALID, "emmax_prefill_score: no scoring plan for %d rows x vocab %d x hidden %d (hidden a multiple of 64)", s->total_rows, m->vocab, m->H);
+    if (s->p32) KCHK(launch_rmsnorm_f32(s->ph32, s->pxn, m->final_norm, s->total_rows, m->H, m->H, m->H, m->cfg.rms_eps, st));
+    else KCHK(launch_rmsnorm(s->ph, s->pxn, m->final_norm, s->total_rows, m->H, m->H, m->H, m->cfg.rms_eps, st));
+    ScoreParams p;
+    memset(&p, 0, sizeof(p));
+    p.X = s->pxn; p.W = m->lm_head_w.rm; p.targets = targets; p.ws = s->splitk_ws; p.lse = lse_out; p.target_logit = target_logit_out; p.argmax = argmax_out;
+    p.ldx = m->H; p.ldw = m->H; p.rows = s->total_rows; p.V = m->vocab; p.K = m->H;
+    KCHK(launch_score_rows(p, f, st));
+    return 0;
+}
+
 }  // extern "C"

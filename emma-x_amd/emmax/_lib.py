@@ -126,6 +126,9 @@ SIGNATURES = {
     "emmax_op_rope_kv_write_at": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp] + [C.c_int] * 5
                                   + [_vp]),
     "emmax_extend_attn_plan": (C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_int)] * 5),
+    "emmax_prefill_score": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "emmax_op_score_rows": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
+    "emmax_score_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64] + [C.POINTER(C.c_int)] * 4),
     "emmax_session_set_pass_taps": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_int, _vp]),
     "emmax_session_set_step_taps": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_int, C.c_int, _vp]),
     "emmax_session_clear_taps": (C.c_int, [_vp, _vp]),

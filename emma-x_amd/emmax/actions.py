@@ -51,6 +51,37 @@ def token_ids_to_actions(ids: np.ndarray, vocab_size: int, centers: np.ndarray) 
     return centers[idx]
 
 
+def _flat_ids(x) -> np.ndarray:
+    """a [B, S] tensor / array, or a list of per-row tensors / arrays / lists -> one flat int64 array"""
+    if hasattr(x, "detach"):
+        return x.detach().cpu().numpy().reshape(-1).astype(np.int64)
+    if isinstance(x, np.ndarray):
+        return x.reshape(-1).astype(np.int64)
+    parts = [_flat_ids(r) if hasattr(r, "__len__") or hasattr(r, "detach") else np.array([r], dtype=np.int64) for r in x]
+    return np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64)
+
+
+def action_token_metrics(predicted_ids, targets, config) -> Dict[str, float]:
+    """The action metrics of the reference's training / validation step (prismatic/training/strategies/base_strategy.py:392-416), from
+    teacher-forced predictions: predicted_ids and targets are aligned row for row (what `score(...).predicted_ids` and `scoring.targets_for`
+    return -- the shift and the patch splice are already in them; [B, S] or per-row lists).  mask = target > action_token_begin_idx (the ids
+    of the action bins); action_accuracy = (prediction == target) over the mask; l1_loss = mean |centre(prediction) - centre(target)| over
+    the mask, de-tokenised as ActionTokenizer.decode_token_ids_to_actions.  NaN where the mask is empty, as the reference's 0 / 0."""
+    pred, gt = _flat_ids(predicted_ids), _flat_ids(targets)
+    if pred.shape != gt.shape:
+        raise ValueError(f"{pred.shape[0]} predictions for {gt.shape[0]} targets: the two are aligned row for row")
+    vocab, bins = int(config.action_vocab_size), int(config.n_action_bins)
+    edges = np.linspace(-1, 1, bins)
+    centers = (edges[:-1] + edges[1:]) / 2.0
+    mask = gt > vocab - (bins + 1)
+    n = int(mask.sum())
+    if n == 0:
+        return dict(action_accuracy=float("nan"), l1_loss=float("nan"), n_action_tokens=0)
+    acc = float(((pred == gt) & mask).sum()) / n
+    l1 = float(np.abs(token_ids_to_actions(pred[mask], vocab, centers) - token_ids_to_actions(gt[mask], vocab, centers)).mean())
+    return dict(action_accuracy=acc, l1_loss=l1, n_action_tokens=n)
+
+
 def action_bin_token_ids(vocab_size: int, n_bins: int = 256) -> List[int]:
     """The token id of every action bin, in bin order: bin k is id vocab_size - 1 - k (the inverse of token_ids_to_actions' index)."""
     return [int(vocab_size) - 1 - k for k in range(int(n_bins))]

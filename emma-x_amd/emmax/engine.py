@@ -290,6 +290,21 @@ class EmmaxEngine:
         _lib.check(self.lib.emmax_prefill_logits(self._session, out.data_ptr(), _lib.current_stream()), "emmax_prefill_logits")
         return list(torch.split(out, self._last_S, dim=0))
 
+    def score(self, targets: Sequence[Sequence[int]]):
+        """The rows prefill_logits would return, scored without their logits (include/emmax.h: emmax_prefill_score).  targets: per row of the
+        last pass one id per position (-100 = not scored), aligned as the pass packed its rows.  -> (lse, target_logit, argmax): lists of
+        per-row device tensors, fp32 / fp32 / int32 [S_b]; target_logit is 0 where the target is -100."""
+        if self.exact:
+            raise NotImplementedError("score: exact-numerics models are not scored (the scoring kernel has no two-term form)")
+        if [len(t) for t in targets] != list(self._last_S):
+            raise ValueError(f"score: targets of lengths {[len(t) for t in targets]} for rows of lengths {list(self._last_S)}")
+        total = sum(self._last_S)
+        tg = torch.tensor([int(x) for t in targets for x in t], dtype=torch.int32).to(self.device)
+        out = torch.empty(3, total, dtype=torch.float32, device=self.device)   # lse | target logit | argmax (int32 bits)
+        _lib.check(self.lib.emmax_prefill_score(self._session, tg.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), _lib.current_stream()),
+                   "emmax_prefill_score")
+        return tuple(list(torch.split(x, self._last_S)) for x in (out[0], out[1], out[2].view(torch.int32)))
+
     def last_logits(self) -> torch.Tensor:
         out = torch.empty(self._last_B, self.cfg.llm.vocab_size, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.emmax_last_logits(self._session, out.data_ptr(), _lib.current_stream()), "emmax_last_logits")

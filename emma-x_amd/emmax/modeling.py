@@ -29,6 +29,7 @@ from . import taps as _taps
 from .engine import EmmaxEngine
 from .policy_parser import Solver
 from .processing import BatchFeature, EmmaXImageProcessor
+from .scoring import IGNORE_INDEX, EmmaXScoreOutput, targets_for
 from .sampling import MAX_DECODE_BATCH, BeamParams, LogitsProcessing, SamplingParams, check_top_logprobs, draw_seed, fold_bad_words
 from .prompting import PurePromptBuilder
 from .tokenizer_stub import StubTokenizer
@@ -555,10 +556,16 @@ class EmmaXForActionPrediction:
         the diagonal, HF's eager maps).  Rows of different lengths: each entry is a list with one tensor per row, the rule `logits` follows.
         They are written by the session's own pass through taps (include/emmax.h), not recomputed.  tap_layers=[...] (HF indices into those
         tuples, negative allowed; None = all, HF's meaning) keeps the selected entries only, in ascending order: the maps of all 32 layers of
-        a 7B prompt of 768 rows are 32 x 768 x 32 x 768 x 4 bytes = 2.4 GB.  Not in exact numerics."""
+        a 7B prompt of 768 rows are 32 x 768 x 32 x 768 x 4 bytes = 2.4 GB.  Not in exact numerics.
+        labels (the three many-row branches; aligned with input_ids, -100 = ignored; on a cached context they cover the new ids): `loss` = HF's
+        shifted mean cross-entropy as an fp32 0-dim device tensor, NaN when nothing is scored, from a fused lm-head pass that reads no logits
+        (`score` is the same without `logits`).  The one-token cached branch asserts them away, as the reference does."""
+        targets = None
+        if labels is not None and input_ids is not None:   # checked before the engine is touched
+            one_token = isinstance(input_ids, torch.Tensor) and input_ids.shape[-1] == 1 and past_key_values is not None
+            assert not one_token, "Unexpected key `labels` provided during cached generation!"   # (modeling_prismatic.py:328)
+            targets = self._targets_of(labels, self._rows(input_ids, attention_mask), attention_mask, pixel_values, frames_u8, past_key_values)
         eng = self._need_engine()
-        if labels is not None:
-            raise NotImplementedError("loss / labels belong to training, outside the inference hot path")
         spec = self._tap_args(output_hidden_states, output_attentions, tap_layers)
         # `inputs_embeds` is never consumed as data by the reference either: the cached branch hands the language model
         # inputs_embeds=None (modeling_prismatic.py:330-341), the multimodal branch embeds `input_ids` whatever else was passed
@@ -582,9 +589,20 @@ class EmmaXForActionPrediction:
             return EmmaXCausalLMOutputWithPast(logits=logits, past_key_values=past_key_values, hidden_states=hs, attentions=at)
         if input_ids is not None and isinstance(input_ids, torch.Tensor) and input_ids.shape[-1] == 1:
             assert past_key_values is not None, "You must provide `past_key_values` during cached generation!"
+        handle, hs, at, patches = self._many_row_pass(rows, pixel_values, frames_u8, past_key_values, use_cache, spec, inputs_embeds, "forward")
+        loss = None if targets is None else self._score_rows(eng, targets)[0]   # the fused pass: lse / target logit / argmax per row, no logits read
+        per_row = eng.prefill_logits()
+        same = len({t.shape[0] for t in per_row}) == 1
+        return EmmaXCausalLMOutputWithPast(loss=loss, logits=torch.stack(per_row) if same else per_row, past_key_values=handle, hidden_states=hs,
+                                           attentions=at, projector_features=patches if output_projector_features else None)
+
+    def _many_row_pass(self, rows, pixel_values, frames_u8, past_key_values, use_cache, spec, inputs_embeds, who: str):
+        """The three many-row branches of forward -- n > 1 new ids on a cached context, language-only, multimodal -- up to and excluding what reads
+        the rows' logits.  -> (the handle the call returns, hidden_states, attentions, the patch embeddings of a multimodal pass)"""
+        eng = self._need_engine()
         if past_key_values is not None and pixel_values is None and frames_u8 is None:
             # n > 1 new ids per row on top of the handle's cache (ragged rows: lists, or a right-padding mask): one pass over the new rows alone
-            self._check_handle(past_key_values, len(rows), "forward")
+            self._check_handle(past_key_values, len(rows), who)
             self._set_processing(eng, len(rows), None)   # (as the language-only branch: what an earlier generate left in the session is cleared)
             hs = at = None
             if spec is not None:
@@ -593,11 +611,8 @@ class EmmaXForActionPrediction:
             eng.extend(rows, max_new_tokens=0)
             if spec is not None:
                 hs, at = _taps.cut_pass(bufs[0], bufs[1], n_new, keys)
-            per_row = eng.prefill_logits()
             past_key_values.lengths = [n + len(r) for n, r in zip(past_key_values.lengths, rows)]
-            same = len({t.shape[0] for t in per_row}) == 1
-            return EmmaXCausalLMOutputWithPast(logits=torch.stack(per_row) if same else per_row, past_key_values=past_key_values, hidden_states=hs,
-                                               attentions=at)
+            return past_key_values, hs, at, None
         if pixel_values is None and frames_u8 is None:
             # unimodal forward (modeling_prismatic.py:343-359): text only, no patch rows
             assert inputs_embeds is None, "Missing `input_ids` in language-only forward!"
@@ -615,21 +630,53 @@ class EmmaXForActionPrediction:
             eng.prefill(rows, None)
             if spec is not None:
                 hs, at = _taps.cut_pass(bufs[0], bufs[1], S, S)
-            per_row = eng.prefill_logits()
-            same = len({t.shape[0] for t in per_row}) == 1
-            return EmmaXCausalLMOutputWithPast(logits=torch.stack(per_row) if same else per_row,
-                                               past_key_values=KVHandle(eng, eng._last_S) if use_cache else None, hidden_states=hs, attentions=at)
+            return (KVHandle(eng, eng._last_S) if use_cache else None), hs, at, None
         if past_key_values is not None:
-            raise ValueError("forward(past_key_values=...) extends the cached rows with text ids: pass no pixel_values / frames_u8 with it")
+            raise ValueError(f"{who}(past_key_values=...) extends the cached rows with text ids: pass no pixel_values / frames_u8 with it")
         patches = self._prefill(rows, pixel_values, frames_u8, max_new=self.cache_reserve if use_cache else 0, taps=spec)
         hs, at = _taps.cut_pass(*self._pass_taps) if spec is not None else (None, None)
         self._pass_taps = None
-        per_row = eng.prefill_logits()
-        same = len({t.shape[0] for t in per_row}) == 1
-        logits = torch.stack(per_row) if same else per_row
-        return EmmaXCausalLMOutputWithPast(
-            logits=logits, past_key_values=KVHandle(eng, eng._last_S, self.config.n_patches) if use_cache else None,
-            hidden_states=hs, attentions=at, projector_features=patches if output_projector_features else None)
+        return (KVHandle(eng, eng._last_S, self.config.n_patches) if use_cache else None), hs, at, patches
+
+    def _targets_of(self, labels, rows, attention_mask, pixel_values, frames_u8, past_key_values) -> List[List[int]]:
+        """labels -> the target id of every logit row of the pass these arguments select (scoring.targets_for), checked before the engine is touched"""
+        multimodal = pixel_values is not None or frames_u8 is not None
+        return targets_for(labels, rows, attention_mask, n_patches=self.config.n_patches if multimodal else 0,
+                           new_rows_only=past_key_values is not None and not multimodal, vocab=self.config.llm.vocab_size)
+
+    @staticmethod
+    def _score_rows(eng, targets):
+        """engine.score on the rows of the last pass -> (loss, token_logprobs, predicted_ids, lse, n_scored); loss = -sum(target_logit - lse) /
+        n_scored as an fp32 0-dim device tensor, NaN when nothing is scored (HF's mean over nothing); per-row lists otherwise, NaN log-probabilities
+        where nothing was scored"""
+        lse, tl, am = eng.score(targets)
+        scored = [torch.tensor([t != IGNORE_INDEX for t in row], dtype=torch.bool).to(lse[0].device) for row in targets]
+        n = sum(int(t != IGNORE_INDEX) for row in targets for t in row)
+        lp = [torch.where(m, a - b, torch.full_like(a, float("nan"))) for m, a, b in zip(scored, tl, lse)]
+        total = torch.stack([torch.where(m, x, torch.zeros_like(x)).sum() for m, x in zip(scored, lp)]).sum()
+        return -total / float(n) if n else torch.full((), float("nan"), device=total.device), lp, am, lse, n
+
+    @torch.inference_mode()
+    def score(self, input_ids, attention_mask=None, pixel_values=None, frames_u8=None, labels=None, past_key_values=None, use_cache=False):
+        """Teacher-forced scoring without logits: the pass `forward` would run -- multimodal, language-only, or n > 1 new ids on the handle of an
+        earlier call -- followed by the fused lm-head pass that keeps three numbers per row.  labels as forward takes them (aligned with input_ids,
+        -100 = ignored; on a cached context they cover the new ids, whose first is not scored); None scores the input itself (perplexity).
+        -> EmmaXScoreOutput.  The action metrics of the reference's evaluation follow from it: actions.action_token_metrics(predicted_ids, targets,
+        config) with targets = scoring.targets_for(...)."""
+        if input_ids is None:
+            raise ValueError("score() needs `input_ids`")
+        rows = self._rows(input_ids, attention_mask)
+        if past_key_values is not None and all(len(r) == 1 for r in rows):
+            raise ValueError("score(past_key_values=...) scores n > 1 new ids per row: the row that predicts a single new id belongs to the earlier pass")
+        targets = self._targets_of(labels, rows, attention_mask, pixel_values, frames_u8, past_key_values)   # (checked before the engine is touched)
+        eng = self._need_engine()
+        if getattr(eng, "exact", 0):
+            raise NotImplementedError("score: exact-numerics models are not scored (the scoring kernel has no two-term form)")
+        handle, _, _, _ = self._many_row_pass(rows, pixel_values, frames_u8, past_key_values, use_cache, None, None, "score")
+        loss, lp, am, lse, n = self._score_rows(eng, targets)
+        same = len({t.shape[0] for t in lp}) == 1
+        st = (lambda xs: torch.stack(xs)) if same else (lambda xs: xs)
+        return EmmaXScoreOutput(loss=loss, token_logprobs=st(lp), predicted_ids=st(am), lse=st(lse), n_scored=n, past_key_values=handle)
 
     __call__ = forward
 

@@ -50,7 +50,8 @@ extern "C" {
  *   emmax_session_context, emmax_op_extend_attention(_kv8), emmax_op_rope_kv_write_at, emmax_extend_attn_plan): new symbols only, the workspace
  *   grew one int32 per decode row; still 12: taps -- hidden states and attention maps out of the passes (emmax_session_set_pass_taps,
  *   emmax_session_set_step_taps, emmax_session_clear_taps, emmax_session_taps, emmax_op_attn_probs(_kv8), emmax_op_tap_rows): new symbols only, the
- *   workspace did not grow; still 12: emmax_gemm_launches (the GEMM's kernel launches as text, host only): a new symbol only. */
+ *   workspace did not grow; still 12: emmax_gemm_launches (the GEMM's kernel launches as text, host only): a new symbol only; still 12: scoring
+ *   without logits (emmax_prefill_score, emmax_op_score_rows, emmax_score_plan): new symbols only, the workspace did not grow. */
 #define EMMAX_ABI_VERSION 12
 
 typedef enum emmax_status {
@@ -199,6 +200,17 @@ int emmax_prefill(emmax_session* s, const int32_t* ids_dev, const int32_t* lens_
 int emmax_prefill_text(emmax_session* s, const int32_t* ids_dev, const int32_t* lens_host, int B, int P_max, emmax_stream stream);
 /* f32 logits of every prefill position, packed rows [sum_b S_b, vocab] (S_b = 256 + lens[b]); valid after prefill. */
 int emmax_prefill_logits(emmax_session* s, float* logits_out_dev, emmax_stream stream);
+/* Teacher-forced scoring of the same rows WITHOUT their logits (still ABI 12: new symbols only): what `forward(labels=...)` needs of
+ * `logits` -- replaces log_softmax / gather / argmax over the [rows, vocab] buffer (HF LlamaForCausalLM.forward's loss,
+ * prismatic/training/strategies/base_strategy.py:392-416).  targets_dev int32 [total_rows], packed as the pass packed its rows: the id whose logit
+ * row r is scored against (the caller applies HF's shift); -100, or anything outside [0, vocab), scores nothing and yields target_logit 0.0f.
+ * Outputs, packed [total_rows]: lse = log sum_c exp(logit[r, c]), target_logit = logit[r, target[r]], argmax (the lowest id wins a tie, as torch).
+ * A token's log-probability is target_logit - lse.  Valid wherever emmax_prefill_logits is (after emmax_prefill, emmax_prefill_text, emmax_extend,
+ * emmax_slot_extend); runs the same final norm, uses the session's split-K scratch and changes nothing a later step or emmax_prefill_logits reads.
+ * EMMAX_ERR_STATE before a prefill and in an exact-numerics session (the scoring kernel has no two-term form).  Models with fp8 / MXFP4 decode
+ * weights score on the bf16 lm-head their own prefill multiplies by (MXFP4: the de-quantised copy). */
+int emmax_prefill_score(emmax_session* s, const int32_t* targets_dev, float* lse_out_dev, float* target_logit_out_dev, int32_t* argmax_out_dev,
+                        emmax_stream stream);
 /* f32 last-position logits [B,vocab] of the most recent prefill/decode step (parity tests; costs one extra pass). */
 int emmax_last_logits(emmax_session* s, float* logits_out_dev, emmax_stream stream);
 
@@ -790,6 +802,19 @@ int emmax_op_rope_kv_write_at(void* qkv_dev, int ld, int q_off, int k_off, int v
                               int max_pages, int Hq, int Hkv, int head_dim, int page, emmax_stream stream);
 int emmax_extend_attn_plan(int B, int max_n, int max_L, int Hq, int Hkv, int nsplit, int kv8, int* G_out, int* tokens_per_block_out, int* query_tiles_out,
                            int* nsplit_out, int* split_form_out);
+/* SCORING as a pure op (score.hip; still ABI 12: new symbols only).  logits[r, c] = sum_k x[r, k] W[c, k] in fp32 are formed tile by tile and never
+ * stored: x bf16 [rows, ldx], W bf16 [Np, ldw] with Np = V padded to a multiple of 128 (rows V .. Np - 1 may hold anything: they never influence an
+ * output), K a multiple of 64, ldx / ldw >= K in multiples of 8, both 16-byte aligned.  Launch 1: row tiles (128 rows) x vocabulary slices (runs of
+ * 128-column tiles); each block leaves (max, sum exp(x - max), index of the max) per row in ws_dev -- three planes [slices][rows], 12 bytes per row
+ * and slice -- and the block whose slice holds targets_dev[r] writes target_logit[r].  Launch 2 merges the slices per row: lse, argmax (the lowest id
+ * wins a tie).  No block waits for another inside a launch.  slices: 0 = the planner's choice (about two blocks per CU, at most one slice per column
+ * tile and ws_bytes / (12 rows)), else 1 .. column tiles (a count that does not divide the tiles yields ceil(tiles / ceil(tiles / slices)) slices).
+ * Outputs as emmax_prefill_score.  EMMAX_ERR_INVALID: K % 64, Np < V or Np % 128, rows < 1 or V < 1, slices above the column tiles, a scratch too
+ * small for the slice count asked for (the planner's: for one slice).
+ * emmax_score_plan: HOST ONLY -- the planner's row tiles, column tiles, slices and tiles per slice for a scratch of ws_bytes. */
+int emmax_op_score_rows(const void* x_dev, int ldx, const void* W_dev, int ldw, int rows, int V, int Np, int K, const int32_t* targets_dev, int slices,
+                        float* ws_dev, int64_t ws_bytes, float* lse_out_dev, float* target_logit_out_dev, int32_t* argmax_out_dev, emmax_stream stream);
+int emmax_score_plan(int rows, int V, int K, int64_t ws_bytes, int* row_tiles_out, int* col_tiles_out, int* slices_out, int* tiles_per_slice_out);
 /* TAPS: HF's output_hidden_states / output_attentions out of the fused path.  A tap is a caller-owned fp32 device buffer that the session fills while
  * it runs a pass it would run anyway; a session that binds nothing launches exactly what it launched before.
  * hidden_layers: bit i (0 <= i <= n_layers) selects HF's hidden_states[i] -- bit 0 the rows behind the embed / patch splice, bit i the residual stream
