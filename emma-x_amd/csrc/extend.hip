@@ -4,7 +4,7 @@
 #include "session.h"
 
 // what a continuation is not served with -- each with its own message.  The session stays as it was
-static int extend_refusals(const emmax_session* s, const char* who) {
+int extend_refusals(const emmax_session* s, const char* who) {
     if (s->exact) return fail(EMMAX_ERR_STATE, "%s: exact-numerics sessions are not extended (their fp32 / 24-bit cache has no extension attention)", who);
     if (s->beam.K) return fail(EMMAX_ERR_STATE, "%s: not served while beams are on (emmax_session_clear_beams)", who);
     if (s->grp_N) return fail(EMMAX_ERR_STATE, "%s: not served while sample groups are on (emmax_session_clear_sample_groups)", who);

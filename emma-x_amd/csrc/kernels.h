@@ -570,6 +570,19 @@ __device__ __forceinline__ void emmax_finish_row(const FinishParams& p, int b, i
     }
     p.cur_tok[b] = tok;
 }
+// ---- verify.hip: a window of guessed tokens per row through the extension pass, and the accept walk behind it ----
+// cu / base of the pass and the rows' token budget; ctx_len / done / n_out / stop match / output row stay (pointers already offset to the first row)
+int launch_verify_state(const PrefillState& st, int32_t* cu, int32_t* base, const int32_t* ctx_len, int32_t* max_new, int budget, hipStream_t stream);
+// one block per sequence of f.B: window row i of sequence b is ids[b][i], argmax[cu[b] + i] the model's token behind it.  The walk emits
+// argmax[cu[b] + i] through emmax_finish_row (f.is_prefill = 0; part_* unused) for i = 0, 1, .. while the row is not done, i + 1 < the window and
+// the token equals ids[b][i + 1].  emitted[b]: tokens emitted; new_ids (may be null) [cu[b] ..]: those tokens
+struct VerifyAcceptParams {
+    FinishParams f;
+    const int32_t *argmax, *ids, *cu;
+    int P_max;
+    int32_t *emitted, *new_ids;
+};
+int launch_verify_accept(const VerifyAcceptParams& p, hipStream_t stream);
 // ---- sample.hip: seeded temperature / top-k / top-p sampling over fp32 logit rows (emmax_op_sample, include/emmax.h) ----
 #define EMMAX_SAMPLE_MAX_V 32768    // entries of one row: 1024 lanes x 32 registers
 struct SampleParams {

@@ -415,6 +415,8 @@ GemmParams gpx(emmax_session* s, const void* A_hl, int Kp, const void* W, int ld
 int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B, int P_max, const void* patches, hipStream_t st, int slot0 = -1);
 // the decoder layers over the packed rows + the gather of the last rows; ext != nullptr: the rows extend a cached context (extend_attn.hip)
 int run_prefill_layers(emmax_session* s, int B, int total, int maxS, int r0, const ExtendAttnPlan* ext, hipStream_t st);
+// extend.hip: what a continuation is not served with, each with its own message (verify.hip refuses the same and more)
+int extend_refusals(const emmax_session* s, const char* who);
 // extend.hip: lens[b] more tokens on top of the cached context of rows r0 .. r0 + B (slot: a request slot, between two steps)
 int run_extend(emmax_session* s, int r0, int B, const int32_t* ids, const int32_t* lens, int P_max, int max_new, bool slot, hipStream_t st);
 // step.hip

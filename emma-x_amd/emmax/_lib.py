@@ -119,6 +119,10 @@ SIGNATURES = {
     "emmax_extend": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _c_i32p, C.c_int, C.c_int, _vp]),
     "emmax_slot_extend": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp]),
     "emmax_session_context": (C.c_int, [_vp, C.c_int, C.c_int, _c_i32p, _vp]),
+    "emmax_verify": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _c_i32p, C.c_int, C.c_int, _c_i32p, _c_i32p, _c_i32p, _vp]),
+    "emmax_session_set_budget": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "emmax_session_output": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _c_i32p, _c_i32p, _c_i32p, _vp]),
+    "emmax_op_verify_accept": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int] + [_vp] * 8 + [C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "emmax_op_extend_attention": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp] + [C.c_int] * 7 + [C.c_float, _vp, C.c_int, _vp, C.c_longlong,
                                             C.POINTER(C.c_int), _vp]),
     "emmax_op_extend_attention_kv8": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp] + [C.c_int] * 7 + [C.c_float, _vp, C.c_int, _vp,

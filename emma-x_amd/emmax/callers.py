@@ -42,8 +42,9 @@ def get_vla_action(vla, processor, base_vla_name, obs, task_label, unnorm_key, c
     return vla.predict_action(**inputs, unnorm_key=unnorm_key, do_sample=False)
 
 
-def get_seq_action(vla, processor, base_vla_name, obs, task_label, unnorm_key, type, center_crop=False):
-    """Emma-X grounded chain-of-thought rollout: (list of 7-DoF policies | proprio target, generated text)."""
+def get_seq_action(vla, processor, base_vla_name, obs, task_label, unnorm_key, type, center_crop=False, draft_ids=None):
+    """Emma-X grounded chain-of-thought rollout: (list of 7-DoF policies | proprio target, generated text).  draft_ids (the ids the previous
+    control step generated: `vla.last_generated_ids`): draft-verified greedy decoding -- the same answer in fewer weight passes."""
     if center_crop:
         raise NotImplementedError("center_crop (TensorFlow crop_and_resize) is outside the MI355X hot path")
     image = _frame(obs)
@@ -53,6 +54,7 @@ def get_seq_action(vla, processor, base_vla_name, obs, task_label, unnorm_key, t
     if getattr(vla, "tokenizer", None) is None:   # a checkpoint directory without tokenizer files: share the processor's
         vla.tokenizer = processor.tokenizer
     # the reference's call, verbatim (experiments/robot/openvla_utils.py:215-217)
+    extra = {} if draft_ids is None else {"draft_ids": draft_ids}
     return vla.generate_actions(
-        image=image, prompt_text=prompt, type=type, temperature=0.0, max_new_tokens=512, min_length=1, do_sample=False
+        image=image, prompt_text=prompt, type=type, temperature=0.0, max_new_tokens=512, min_length=1, do_sample=False, **extra
     )

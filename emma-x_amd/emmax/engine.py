@@ -378,6 +378,41 @@ class EmmaxEngine:
         _lib.check(self.lib.emmax_session_context(self._session, int(row0), n, out, _lib.current_stream()), "emmax_session_context")
         return list(out)
 
+    # ---- draft-verified greedy decoding (include/emmax.h: emmax_verify; drafting.py holds the policy and the loop) ---------------
+    def verify(self, windows: Sequence[Sequence[int]], row0: int = 0, max_new: Optional[int] = None):
+        """One verify pass over live rows row0 .. in mid-generation: windows[b] = the row's pending token, then guessed ids.  Every row emits the
+        model's own greedy tokens as far as the guess agrees with them (1 .. len(windows[b]) tokens; a done row none) and is then as that many
+        decode steps would have left it.  max_new: the rows' token budget (default: the session's output row, max_ctx ids).
+        -> (emitted, new_ids, done): per row the count, the emitted ids and the done flag.  drafting.VerifyRefused when the windows do not fit
+        the rows' cache (nothing changed: fall back to decode_step); prefill_logits() returns the window rows' logits afterwards."""
+        from .drafting import VerifyRefused
+
+        windows = [list(w) for w in windows]
+        B = len(windows)
+        self._check_extension_fits("verify", B, max(len(w) for w in windows))
+        ids_d, lens, P_max, _ = self._pack_prompts("verify", windows, self.cfg.pad_token_id)
+        lens_c = (C.c_int32 * B)(*lens)
+        emitted, done, new_ids = (C.c_int32 * B)(), (C.c_int32 * B)(), (C.c_int32 * (B * P_max))()
+        rc = self.lib.emmax_verify(self._session, int(row0), B, ids_d.data_ptr(), lens_c, P_max, int(max_new if max_new is not None else self.max_ctx),
+                                   emitted, new_ids, done, _lib.current_stream())
+        if rc == -3:   # EMMAX_ERR_NOMEM
+            raise VerifyRefused(self.lib.emmax_last_error().decode("utf-8", "replace"))
+        _lib.check(rc, "emmax_verify")
+        self._last_S = list(lens)   # what prefill_logits splits by: the window rows
+        return list(emitted), [list(new_ids[b * P_max:b * P_max + emitted[b]]) for b in range(B)], list(done)
+
+    def set_budget(self, max_new: int, row0: int = 0, n: Optional[int] = None) -> None:
+        """The token budget of live rows row0 .. row0 + n - 1, as generate sets it before its loop: for a host loop of decode_step / verify."""
+        n = self._last_B if n is None else int(n)
+        _lib.check(self.lib.emmax_session_set_budget(self._session, int(row0), n, int(max_new), _lib.current_stream()), "emmax_session_set_budget")
+
+    def output_tail(self, first: int, n: int, row0: int = 0, rows: Optional[int] = None):
+        """Generated ids first .. first + n - 1 of live rows row0 .. (pad where a row has none), their counts and done flags, read back to the host."""
+        B = self._last_B if rows is None else int(rows)
+        ids, n_out, done = (C.c_int32 * (B * n))(), (C.c_int32 * B)(), (C.c_int32 * B)()
+        _lib.check(self.lib.emmax_session_output(self._session, int(row0), B, int(first), int(n), ids, n_out, done, _lib.current_stream()), "emmax_session_output")
+        return [list(ids[b * n:(b + 1) * n]) for b in range(B)], list(n_out), list(done)
+
     # ---- taps: hidden states and attention maps out of the passes (include/emmax.h: emmax_session_set_pass_taps) ---------------
     def _tap_refusals(self, who: str) -> None:
         if self.exact:

@@ -685,7 +685,7 @@ class EmmaXForActionPrediction:
                      stop_on_eos: bool = True, sampling=None, return_logprobs: bool = False, processing=None, scores=None, logits=None,
                      beams: Optional[BeamParams] = None, num_samples: int = 1, top_logprobs: int = 0, watch_ids: Optional[Sequence[int]] = None,
                      constraint=None, constraint_start=None, continue_from=None, return_handle: bool = False, hidden: Optional[Sequence[int]] = None,
-                     attentions: Optional[Sequence[int]] = None):
+                     attentions: Optional[Sequence[int]] = None, draft=None, draft_params=None, return_draft_stats: bool = False):
         """Decode every row: greedy, or sampled in the step with `sampling` (one SamplingParams for all rows or one per row; row b draws
         with subseq b).  `processing` (one LogitsProcessing for all rows or one per row) applies HF's repetition penalty / n-gram ban /
         min-new-tokens in the step first.  `scores` / `logits`: fp32 [max_new, B, vocab] device buffers the step fills with HF's scores /
@@ -714,7 +714,18 @@ class EmmaXForActionPrediction:
         `hidden` / `attentions` (lists of entries of HF's hidden_states / attentions tuples, ascending; None = off): the return gains one trailing
         TapsOutput, the LAST element -- per generated token the selected hidden states and attention maps, written by the prompt pass and by
         every decode step through the session's taps (include/emmax.h).  Greedy, sampled, with processors, warpers, a constraint,
-        top_logprobs and continue_from; not with beams or num_samples > 1, not in exact numerics.  The ids are those of the same call without."""
+        top_logprobs and continue_from; not with beams or num_samples > 1, not in exact numerics.  The ids are those of the same call without.
+        `draft` (one list of ids or None per row; None = off, today's path): draft-verified greedy decoding (drafting.py) -- each row's draft,
+        typically the ids the previous call on almost the same scene generated, is checked window by window in verify passes and the longest
+        prefix the model's own argmax agrees with is kept: the ids and lens are exactly those of the call without, in fewer weight passes.
+        `draft_params`: drafting.DraftParams.  `return_draft_stats` (with a draft only): the return gains a trailing drafting.DraftStats (behind the handle).
+        `stop_on_eos` has nothing to do with a draft: the loop ends when every row is done on the device (EOS, budget, stop rule), the ids are the same.
+        Greedy only: sampling, processors / warpers / token rules, a constraint, beams, num_samples > 1, scores / logits, top_logprobs /
+        watch_ids, hidden / attentions, fp8 decode weights and exact numerics raise NotImplementedError before the engine is touched."""
+        if draft is not None:
+            self._check_draft(draft, len(rows), sampling=sampling, processing=processing, scores=scores, logits=logits, beams=beams,
+                              num_samples=num_samples, top=bool(top_logprobs) or bool(watch_ids), constraint=constraint,
+                              taps=hidden is not None or attentions is not None, return_logprobs=return_logprobs)
         spec = None
         if hidden is not None or attentions is not None:
             spec = _taps.TapSpec(sorted(set(int(i) for i in hidden or [])), sorted(set(int(i) for i in attentions or [])))
@@ -793,6 +804,9 @@ class EmmaXForActionPrediction:
 
         if not want_top:
             start(max_new=max_new_tokens, sampling=sampling, processing=processing, scores=scores, logits=logits, **cst)
+            if draft is not None:
+                out, dstats = self._drafted_generate(eng, draft, max_new_tokens, draft_params)
+                return tuple(out) + handle() + ((dstats,) if return_draft_stats else ())
             out = eng.generate(max_new_tokens, stop_on_eos, return_logprobs=return_logprobs)
             if scores is not None or logits is not None:
                 eng.set_scores(None, None)   # the buffers are the caller's now: no later step or prefill writes into them
@@ -810,6 +824,62 @@ class EmmaXForActionPrediction:
             eng.clear_sampling()
         top = TopLogprobsOutput(top_ids=ti, top_logprobs=tl, watch_logprobs=wl, logprobs=lp)
         return ((ids, lens, lp, top) if return_logprobs else (ids, lens, top)) + handle() + taps_out(lens)
+
+    def _check_draft(self, draft, n_rows: int, sampling=None, processing=None, scores=None, logits=None, beams=None, num_samples: int = 1,
+                     top: bool = False, constraint=None, taps: bool = False, return_logprobs: bool = False) -> None:
+        """What a draft is not served with (include/emmax.h: emmax_verify refuses the same), checked before the engine is touched."""
+        def no(what):
+            raise NotImplementedError(f"draft-verified decoding is greedy on raw logits: {what} with a draft is outside the hot path")
+        if sampling is not None or return_logprobs:
+            no("do_sample / sampling")
+        if processing is not None:
+            no("logits processors / warpers / token rules")
+        if constraint is not None:
+            no("a constraint (constrain_to_bins included)")
+        if beams is not None:
+            no("num_beams > 1")
+        if self._check_num_samples(num_samples) > 1:
+            no("num_return_sequences > 1")
+        if scores is not None or logits is not None or top:
+            no("output_scores / output_logits / top_logprobs / watch_ids")
+        if taps:
+            no("output_hidden_states / output_attentions")
+        if self.config.decode_weight_dtype == "fp8":
+            no("fp8 decode weights (their prefill multiplies by the unquantised matrices: the pass would verify another model)")
+        if self.engine is not None and getattr(self.engine, "exact", 0):
+            no("an exact-numerics model")
+        if draft is not None and (not isinstance(draft, (list, tuple)) or len(draft) != n_rows):
+            raise ValueError(f"draft takes one list of ids or None per row ({n_rows} rows)")
+
+    @staticmethod
+    def _draft_kw(draft_ids, n_rows: int, draft_params=None) -> Dict[str, Any]:
+        """generate_ids' draft arguments from a caller's draft_ids (None: none -- the call is spelled exactly as before): one list of ids or
+        None per row, a [B, n] tensor, or for one row the flat list of its ids."""
+        if draft_ids is None:
+            return {}
+        if isinstance(draft_ids, torch.Tensor):
+            draft_ids = draft_ids.tolist()
+        draft_ids = list(draft_ids)
+        if n_rows == 1 and draft_ids and not isinstance(draft_ids[0], (list, tuple, type(None))):
+            draft_ids = [draft_ids]
+        draft = [None if d is None else [int(t) for t in d] for d in draft_ids]
+        return {"draft": draft, **({} if draft_params is None else {"draft_params": draft_params})}
+
+    def _drafted_generate(self, eng, draft, max_new_tokens: int, draft_params=None):
+        """drafting.drafted_generate over the rows the call's prefill / extension left, as eng.generate returns them: (ids int32 [B, max_new]
+        pad-filled, lens int32 [B]) on the device, and the DraftStats."""
+        from . import drafting
+
+        params = draft_params or drafting.DraftParams()
+        room = (self.config.n_patches + eng.max_prompt) * eng.max_batch // max(len(draft), 1)   # the packed rows of one pass: the prefill's scratch
+        if params.window > room:
+            params = drafting.DraftParams(max(room, 2), params.ngram, params.burst, params.give_up)
+        ids, lens, stats = drafting.drafted_generate(eng, [None if d is None else [int(t) for t in d] for d in draft], int(max_new_tokens), params)
+        out = torch.full((len(ids), int(max_new_tokens)), int(self.config.pad_token_id), dtype=torch.int32)
+        for b, r in enumerate(ids):
+            out[b, :len(r)] = torch.as_tensor(r, dtype=torch.int32)
+        self.last_draft_stats = stats
+        return (out.to(eng.device), torch.as_tensor(lens, dtype=torch.int32).to(eng.device)), stats
 
     def _check_constraint(self, constraint, constraint_start, num_beams: int, n_rows: int) -> Dict[str, Any]:
         """`constraint` / `constraint_start` of a call, checked before the engine is touched -> _prefill's keywords ({}: no constraint)."""
@@ -873,7 +943,8 @@ class EmmaXForActionPrediction:
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
                  output_scores: bool = False, output_logits: bool = False, return_dict_in_generate: bool = False, top_logprobs: int = 0,
                  watch_ids: Optional[Sequence[int]] = None, past_key_values=None, output_hidden_states: bool = False, output_attentions: bool = False,
-                 tap_layers: Optional[Sequence[int]] = None, **kwargs):
+                 tap_layers: Optional[Sequence[int]] = None, draft_ids=None, prompt_lookup_num_tokens: Optional[int] = None, draft_params=None,
+                 **kwargs):
         """HF-style: returns LongTensor [B, P + T] = prompt ++ generated (right-padded with pad_token_id).  do_sample=True draws every token
         in the decode step (include/emmax.h: emmax_session_set_sampling) with temperature / top_k / top_p (HF defaults 1.0 / 50 / 1.0 when
         unset); row b draws with (seed, subseq b), seed None = draw_seed(generator).  With num_return_sequences=N the prompt is prefilled once
@@ -895,7 +966,23 @@ class EmmaXForActionPrediction:
         finished row did not emit.  Served greedy and sampled, with processors, warpers, a constraint and log-probabilities alongside; the ids and
         logits are those of the same call without.  tap_layers=[...] keeps the selected entries only (forward() describes it: all maps of a 7B
         prompt of 768 rows are 2.4 GB, and every step adds 32 x 32 x its context).  num_beams > 1, num_return_sequences > 1 and exact-numerics
-        models raise NotImplementedError with them."""
+        models raise NotImplementedError with them.
+        draft_ids= (one list of ids or None per row: typically the ids the previous call generated) runs draft-verified greedy decoding
+        (generate_ids describes it): the same sequences in fewer weight passes; `last_draft_stats` holds the call's drafting.DraftStats.
+        prompt_lookup_num_tokens=n (HF's keyword) makes each row's own prompt ids its draft, with a window of n + 1.  Greedy only: everything
+        generate_ids refuses with a draft raises NotImplementedError before the engine is touched."""
+        drafted = draft_ids is not None or prompt_lookup_num_tokens is not None
+        if drafted:
+            if draft_ids is not None and prompt_lookup_num_tokens is not None:
+                raise ValueError("pass one of draft_ids= and prompt_lookup_num_tokens=")
+            # what the arguments alone say; sampling, processors / warpers / token rules and the constraint are refused below, from the very objects
+            # the call builds for them (whatever keyword made them)
+            for k in ("logits_processor", "stopping_criteria", "prefix_allowed_tokens_fn"):
+                if kwargs.get(k) is not None:
+                    raise NotImplementedError(f"draft-verified decoding is greedy on raw logits: {k}= with a draft is outside the hot path")
+            self._check_draft(None, 0, sampling=do_sample or None, beams=((kwargs.get("num_beams") or 1) != 1) or None,
+                              num_samples=kwargs.get("num_return_sequences") or 1, scores=(output_scores or output_logits) or None,
+                              top=bool(top_logprobs) or bool(watch_ids), taps=bool(output_hidden_states or output_attentions))
         spec = self._tap_args(output_hidden_states and return_dict_in_generate, output_attentions and return_dict_in_generate, tap_layers,
                               kwargs.get("num_beams"), kwargs.get("num_return_sequences") or 1)
         tap_kw = {} if spec is None else {"hidden": spec.hidden or None, "attentions": spec.attn or None}
@@ -932,6 +1019,8 @@ class EmmaXForActionPrediction:
         if len(rows) * N > MAX_DECODE_BATCH:
             raise ValueError(f"{len(rows)} prompts x {N} samples exceed the {MAX_DECODE_BATCH} rows of a decode batch")
         sampling = self._sampling_args(do_sample, temperature, top_k, top_p, seed, generator, **self._kw_warpers(kwargs))
+        if drafted:   # (before the engine is touched)
+            self._check_draft(None, 0, sampling=sampling, processing=processing, constraint=cst.get("constraint"), beams=beams, num_samples=N)
         max_new_tokens = self._max_new(full_rows, max_new_tokens, kwargs.get("max_length"), None)   # (min_length is in `processing`)
         want_sc, want_lg = bool(return_dict_in_generate and output_scores), bool(return_dict_in_generate and output_logits)
         sc = lg = None
@@ -941,8 +1030,17 @@ class EmmaXForActionPrediction:
             shape = (max_new_tokens, len(rows) * K, self.config.llm.vocab_size)
             sc = torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device) if want_sc else None
             lg = torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device) if want_lg else None
+        draft_kw = {}
+        if drafted:   # (the prompt's own ids as the draft: HF's prompt lookup, with its window)
+            from .drafting import DraftParams
+
+            if prompt_lookup_num_tokens is not None:
+                if int(prompt_lookup_num_tokens) < 1:
+                    raise ValueError(f"prompt_lookup_num_tokens={prompt_lookup_num_tokens} must be at least 1")
+                draft_ids, draft_params = [list(r) for r in full_rows], DraftParams(window=int(prompt_lookup_num_tokens) + 1)
+            draft_kw = self._draft_kw(draft_ids, len(rows), draft_params)
         res = self.generate_ids(rows, pixel_values, frames_u8, max_new_tokens, sampling=sampling, processing=processing, scores=sc,
-                                logits=lg, **self._beam_kw(beams), **self._sample_kw(N), **self._top_kw(n_top, watch), **cst, **cont, **tap_kw)
+                                logits=lg, **self._beam_kw(beams), **self._sample_kw(N), **self._top_kw(n_top, watch), **cst, **cont, **tap_kw, **draft_kw)
         new_ids, lens = res[0], res[1]
         tapped = res[-1] if spec is not None else TapsOutput()
         kvh = None
@@ -1019,7 +1117,10 @@ class EmmaXForActionPrediction:
         num_beams > 1.
         return_hidden_states=True: the return gains, as its last element, fp32 [action_dim, H] on the device -- the NORMED last-layer state that
         produced each action token (HF's hidden_states[-1] at the emitting position: what a continuous-action head consumes), written by the
-        prompt pass and the decode steps through the session's taps.  Not with num_beams > 1 or num_return_sequences > 1."""
+        prompt pass and the decode steps through the session's taps.  Not with num_beams > 1 or num_return_sequences > 1.
+        draft_ids= (the ids an earlier call generated for almost the same observation): draft-verified greedy decoding, the same action in
+        fewer weight passes (generate_ids: draft); greedy only -- not with sampling, processors, constrain_to_bins, beams or the extras above."""
+        draft_kw = self._draft_kw(kwargs.pop("draft_ids", None), 1, kwargs.pop("draft_params", None))
         rows = self._rows(input_ids, kwargs.pop("attention_mask", None))
         if len(rows) != 1:
             raise ValueError("Generation with batch size > 1 is not currently supported!")   # reference contract
@@ -1048,7 +1149,7 @@ class EmmaXForActionPrediction:
                 raise ValueError("constrain_to_bins builds its own constraint: pass one of constrain_to_bins= and constraint=")
             cst = {"constraint": self._bin_automaton(dim)}
         res = self.generate_ids(rows, kwargs.get("pixel_values"), kwargs.get("frames_u8"), max_new_tokens=dim, sampling=sampling,
-                                processing=processing, **self._beam_kw(beams), **self._sample_kw(N), **self._top_kw(0, bin_ids), **cst, **tap_kw)
+                                processing=processing, **self._beam_kw(beams), **self._sample_kw(N), **self._top_kw(0, bin_ids), **cst, **tap_kw, **draft_kw)
         new_ids, lens = res[0], res[1]
         states = None
         if return_hidden_states:   # element t, its one entry, row 0, the emitting (last) position
@@ -1058,7 +1159,10 @@ class EmmaXForActionPrediction:
                 states = torch.cat([states, states.new_zeros(dim - states.shape[0], states.shape[1])])
 
         def action(j):
-            full = rows[0] + new_ids[j, : int(lens[j])].cpu().tolist()
+            got = new_ids[j, : int(lens[j])].cpu().tolist()
+            if j == 0:
+                self.last_generated_ids = got   # (a caller's next draft_ids: the copy this function makes anyway)
+            full = rows[0] + got
             normalized = token_ids_to_actions(np.array(full[-dim:]), self.vocab_size, self.bin_centers)
             return unnormalize(normalized, self.get_action_stats(unnorm_key))
 
@@ -1172,8 +1276,11 @@ class EmmaXForActionPrediction:
                    type=type, temperature=0.0, max_new_tokens=512, min_length=1, do_sample=False)` by
                    experiments/robot/openvla_utils.py:215-217).  The tokenizer is the model's own (`self.tokenizer`, attached by
                    from_pretrained like the reference's `llm_backbone.tokenizer`); `tokenizer=` overrides it.
+        draft_ids= (either form; the ids of an earlier answer, e.g. `last_generated_ids` of the previous control step): draft-verified greedy
+        decoding -- the same answer in fewer weight passes (generate_ids: draft).
         """
         args = list(args)
+        draft_kw = self._draft_kw(kwargs.pop("draft_ids", None), 1, kwargs.pop("draft_params", None))   # (generate_ids: draft; `last_draft_stats`)
         inputs = kwargs.pop("inputs", None)
         if inputs is None and args and hasattr(args[0], "keys") and "input_ids" in args[0]:
             inputs = args.pop(0)   # dict, our BatchFeature, or transformers.BatchFeature (a UserDict: processing_prismatic.py:216)
@@ -1191,8 +1298,9 @@ class EmmaXForActionPrediction:
             beams = self._kw_beams(kwargs, processing)   # num_beams > 1: the best hypothesis (row 0 of the group) is decoded
             max_new = self._max_new(rows, kwargs.get("max_new_tokens", None if "max_length" in kwargs else 512), kwargs.get("max_length"), None)
             new_ids, lens = self.generate_ids(rows, inputs.get("pixel_values"), inputs.get("frames_u8"), max_new_tokens=max_new,
-                                              processing=processing, **self._beam_kw(beams), **self._kw_constraint(kwargs))
-            actions, text = self._postprocess(new_ids[0, : int(lens[0])].cpu().tolist(), tokenizer, "act")
+                                              processing=processing, **self._beam_kw(beams), **self._kw_constraint(kwargs), **draft_kw)[:2]
+            self.last_generated_ids = new_ids[0, : int(lens[0])].cpu().tolist()   # (a caller's next draft_ids)
+            actions, text = self._postprocess(self.last_generated_ids, tokenizer, "act")
             return actions[0], text
         # native form
         names = ("image", "prompt_text", "type")
@@ -1221,8 +1329,9 @@ class EmmaXForActionPrediction:
         max_new = self._max_new(rows, kwargs.get("max_new_tokens"), kwargs.get("max_length"), None)
         feat = self.image_transform(vals["image"])
         new_ids, lens = self.generate_ids(rows, feat["pixel_values"], feat.get("frames_u8"), max_new_tokens=max_new, processing=processing,
-                                          **self._beam_kw(beams), **self._kw_constraint(kwargs))
-        return self._postprocess(new_ids[0, : int(lens[0])].cpu().tolist(), tokenizer, vals["type"])
+                                          **self._beam_kw(beams), **self._kw_constraint(kwargs), **draft_kw)[:2]
+        self.last_generated_ids = new_ids[0, : int(lens[0])].cpu().tolist()   # (a caller's next draft_ids)
+        return self._postprocess(self.last_generated_ids, tokenizer, vals["type"])
 
     @torch.inference_mode()
     def generate_actions_batch(self, frames_u8: torch.Tensor, prompt_rows: Sequence[Sequence[int]], max_new_tokens: int = 512,

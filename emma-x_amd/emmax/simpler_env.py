@@ -125,7 +125,7 @@ class OpenVLAInference:
     def __init__(self, saved_model_path: str = "openvla/openvla-7b", unnorm_key: Optional[str] = None,
                  policy_setup: str = "widowx_bridge", horizon: int = 1, pred_action_horizon: int = 1, exec_horizon: int = 1,
                  image_size: Sequence[int] = (224, 224), action_scale: float = 1.0, vla=None, processor=None,
-                 device: str = "cuda:0") -> None:
+                 device: str = "cuda:0", reuse_reasoning: bool = False) -> None:
         os.environ["TOKENIZERS_PARALLELISM"] = "false"
         setup = _EMBODIMENTS.get(policy_setup)
         if setup is None:
@@ -142,6 +142,11 @@ class OpenVLAInference:
         self.task = None
         self.task_description: Optional[str] = None
         self.num_image_history = 0
+        # reuse_reasoning: the ids the last control step generated are the next step's draft (draft-verified greedy decoding, modeling.py:
+        # generate_ids) -- the same actions in fewer weight passes while the scene changes little; cleared by reset()
+        self.reuse_reasoning = bool(reuse_reasoning)
+        self._last_ids: Optional[list] = None
+        self.last_draft_stats = None
         self.processor, self.vla = self._load(saved_model_path, processor, vla, device)
 
     @staticmethod
@@ -162,6 +167,7 @@ class OpenVLAInference:
     def reset(self, task_description: str) -> None:
         self.task_description = task_description
         self.num_image_history = 0
+        self._last_ids = None
         if self._gripper is not None:
             self._gripper.clear()
 
@@ -169,7 +175,12 @@ class OpenVLAInference:
         import torch
 
         inputs = self.processor(prompt, image).to(self.device, dtype=torch.bfloat16)
-        return self.vla.predict_action(**inputs, unnorm_key=self.unnorm_key, do_sample=False)
+        if not self.reuse_reasoning:
+            return self.vla.predict_action(**inputs, unnorm_key=self.unnorm_key, do_sample=False)
+        self.vla.last_draft_stats = None
+        action = self.vla.predict_action(**inputs, unnorm_key=self.unnorm_key, do_sample=False, draft_ids=self._last_ids)
+        self._last_ids, self.last_draft_stats = list(self.vla.last_generated_ids), self.vla.last_draft_stats
+        return action
 
     def step(self, image: np.ndarray, task_description: Optional[str] = None, *args, **kwargs) -> Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray]]:
         """image uint8 [H,W,3] -> (raw_action {world_vector[3], rotation_delta[3], open_gripper[1]},

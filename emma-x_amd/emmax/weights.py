@@ -124,6 +124,9 @@ def synthetic_state_dict(cfg: EmmaXConfig, seed: int = 0, device: str = "cpu", d
         succ = planted_successor(cfg)
         for t, nxt in (succ_override or {}).items():
             succ[int(t)] = int(nxt)
+        if int(succ.min()) < 0 or int(succ.max()) >= head.shape[0]:   # (e.g. eos_token_id = -1: turn EOS off AFTER the weights exist)
+            raise ValueError(f"planted weights: the successor map names ids {int(succ.min())}..{int(succ.max())} outside the lm-head's {head.shape[0]} rows "
+                             f"(eos_token_id = {cfg.eos_token_id}: generate the weights with the real EOS id and disable EOS afterwards)")
         # logits[succ(t)] ~= |embed[t]|^2 * gain / rms  >>  sqrt(hidden)-scale background
         gain = 4.0 * std
         head.index_add_(0, succ.to(emb.device), gain * emb)   # row succ[t] += gain * embed[t]

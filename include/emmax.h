@@ -51,7 +51,8 @@ extern "C" {
  *   grew one int32 per decode row; still 12: taps -- hidden states and attention maps out of the passes (emmax_session_set_pass_taps,
  *   emmax_session_set_step_taps, emmax_session_clear_taps, emmax_session_taps, emmax_op_attn_probs(_kv8), emmax_op_tap_rows): new symbols only, the
  *   workspace did not grow; still 12: emmax_gemm_launches (the GEMM's kernel launches as text, host only): a new symbol only; still 12: scoring
- *   without logits (emmax_prefill_score, emmax_op_score_rows, emmax_score_plan): new symbols only, the workspace did not grow. */
+ *   without logits (emmax_prefill_score, emmax_op_score_rows, emmax_score_plan): new symbols only, the workspace did not grow; still 12: draft-verified
+ *   greedy decoding (emmax_verify, emmax_session_set_budget, emmax_session_output, emmax_op_verify_accept): new symbols only, the workspace did not grow. */
 #define EMMAX_ABI_VERSION 12
 
 typedef enum emmax_status {
@@ -309,6 +310,40 @@ int emmax_slot_release(emmax_session* s, int slot, emmax_stream stream);
 int emmax_extend(emmax_session* s, int row0, int B, const int32_t* ids_dev, const int32_t* lens_host, int P_max, int max_new, emmax_stream stream);
 int emmax_slot_extend(emmax_session* s, int slot, const int32_t* ids_dev, int len, int max_new, emmax_stream stream);
 int emmax_session_context(emmax_session* s, int row0, int n, int32_t* ctx_out_host, emmax_stream stream);
+
+/* ---- draft-verified greedy decoding (still ABI 12: new symbols only) ----------------------------------------------------
+ * A greedy generation in flight checks a GUESSED continuation in one pass instead of one decode step per token.  Row b's window is ids_dev[b][0 ..
+ * lens_host[b]): id 0 is the row's pending token (picked, not yet cached: checked against the device, EMMAX_ERR_INVALID on a mismatch), ids 1 .. the guess.
+ *   emmax_verify           rows row0 .. row0 + B - 1 of the live batch: the extension pass of emmax_extend over the windows, the argmax of every window
+ *                          row (the scoring launch of emmax_prefill_score, no logits stored), then the accept walk on the device: the token behind
+ *                          window row i is emitted -- ctx_len + 1, output row, n_out, EOS / token budget / stop rule / cache end, pending token: exactly a
+ *                          decode step's bookkeeping -- and row i + 1 is reached only while the row is not done and that token equals the window's
+ *                          id i + 1.  The rows emit 1 .. lens[b] tokens (emitted_host[b]; new_ids_host [B][P_max]: those tokens, pad behind them;
+ *                          done_host[b]: the row's done flag afterwards) and are then as that many decode steps would have left them; K / V rows the
+ *                          pass wrote beyond a row's new cached length are dead (nothing reads past it, later appends overwrite them).  max_new
+ *                          (1 .. max_out) becomes the rows' token budget, as emmax_generate sets it.  A row that is already done takes part with any
+ *                          window (its pending token alone will do; its first id is not checked) and is left exactly as it is, emitted 0.
+ *                          emmax_prefill_logits returns the window rows' logits afterwards.  The call reads the rows' state back before and its
+ *                          results after the pass: it synchronises the stream and is not capturable; decode steps and graph replays go on behind it.
+ *   emmax_session_set_budget  the token budget of rows row0 .. row0 + B - 1 (what emmax_generate sets before its loop) for a host loop of emmax_decode_step.
+ *   emmax_session_output   out_ids[b][first .. first + n) of those rows into ids_host [B][n], their n_out and done flags (either may be NULL), read
+ *                          back to the host (synchronises the stream).
+ * EMMAX_ERR_STATE, each with its own message: everything emmax_extend refuses; open request slots; sampling, logits processing, warpers, token rules,
+ * a token automaton, bound scores, top / watched log-probabilities or step taps (the accepted ids are argmaxes of raw rows); a model with fp8 decode
+ * weights (its prefill multiplies by the unquantised matrices: the pass would verify another model).  bf16 and MXFP4 weights, bf16 and fp8 KV caches
+ * are served.  EMMAX_ERR_NOMEM: context + lens + 1 (a done row: context + lens) beyond max_ctx or the row's pages; more packed rows than the prefill
+ * holds.  A refused call changes nothing: the caller falls back to plain decode steps.
+ *   emmax_op_verify_accept the accept walk alone on caller-owned device arrays: argmax_dev [cu[B]] packed as cu_dev [B + 1] says, ids_dev [B][P_max],
+ *                          the per-row state arrays [B] and out_ids_dev [B][max_out], stop_ids_dev [16] / stop_cfg_dev {n_trigger, n_after} as
+ *                          emmax_session_set_stop uploads them; emitted_dev [B], new_ids_dev [cu[B]] (packed like argmax; may be NULL). */
+int emmax_verify(emmax_session* s, int row0, int B, const int32_t* ids_dev, const int32_t* lens_host, int P_max, int max_new, int32_t* emitted_host,
+                 int32_t* new_ids_host, int32_t* done_host, emmax_stream stream);
+int emmax_session_set_budget(emmax_session* s, int row0, int B, int max_new, emmax_stream stream);
+int emmax_session_output(emmax_session* s, int row0, int B, int first, int n, int32_t* ids_host, int32_t* n_out_host, int32_t* done_host, emmax_stream stream);
+int emmax_op_verify_accept(const int32_t* argmax_dev, const int32_t* ids_dev, int P_max, const int32_t* cu_dev, int B, int32_t* cur_tok_dev, int32_t* ctx_len_dev,
+                           int32_t* done_dev, int32_t* n_out_dev, const int32_t* max_new_dev, int32_t* stop_m_dev, int32_t* stop_after_dev, int32_t* out_ids_dev,
+                           int max_out, const int32_t* stop_ids_dev, const int32_t* stop_cfg_dev, int eos_id, int pad_id, int max_ctx, int32_t* emitted_dev,
+                           int32_t* new_ids_dev, emmax_stream stream);
 
 /* ---- seeded sampling over rows of logits (ABI 6) --------------------------------------------------------------------
  * emmax_op_sample draws one token per row of logits_dev [B][ld] (fp32, V <= 32768 entries, ld >= V) and returns it with its
