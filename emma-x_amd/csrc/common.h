@@ -223,6 +223,19 @@ __device__ __forceinline__ bf16x8_t mx4x8_to_bf16x8(uint32_t q, float scale) {
                        __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 3))};
     return __builtin_bit_cast(bf16x8_t, v);
 }
+// OCP MXFP6 e2m3 weights -> bf16 in registers (exact: four significant bits times a power of two): v_cvt_scalef32_pk32_bf16_fp6 widens the 32
+// elements of ONE scale block -- six dwords, element i in bits [6 i, 6 i + 6) -- and multiplies by the block scale (e8m0_scale above).  out[j] =
+// elements 8 j .. 8 j + 7: the A fragment of the lane's j-th MFMA of the load step.
+typedef __attribute__((ext_vector_type(6))) uint32_t u32x6_t;
+typedef __attribute__((ext_vector_type(32))) __bf16 bf16x32_t;
+__device__ __forceinline__ void mx6x32_to_bf16x8(const u32x4_t& a, const u32x2_t& b, float scale, bf16x8_t (&out)[4]) {
+    const u32x6_t q = {a[0], a[1], a[2], a[3], b[0], b[1]};
+    const bf16x32_t v = __builtin_amdgcn_cvt_scalef32_pk32_bf16_fp6(q, scale);
+    out[0] = __builtin_shufflevector(v, v, 0, 1, 2, 3, 4, 5, 6, 7);
+    out[1] = __builtin_shufflevector(v, v, 8, 9, 10, 11, 12, 13, 14, 15);
+    out[2] = __builtin_shufflevector(v, v, 16, 17, 18, 19, 20, 21, 22, 23);
+    out[3] = __builtin_shufflevector(v, v, 24, 25, 26, 27, 28, 29, 30, 31);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Split-KV attention partials: per (row, head, split) EMMAX_PSTRIDE floats = { o[0..128) un-normalised, m, l, 2 pad }.

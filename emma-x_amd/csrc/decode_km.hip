@@ -34,7 +34,7 @@ constexpr int KM_NT = KM_WAVES * 64;
 constexpr int KM_STEPS = 16;      // bf16 k-steps (32 elements) per tile and wave: K <= 8 * 16 * 32 = 4096
 constexpr int KM_MAX_TILES = 8;   // tiles per block the LDS partial sums hold
 constexpr int PSTRIDE = EMMAX_PSTRIDE;
-enum { W_BF16 = 0, W_FP8 = 1, W_MX4 = 2 };   // weight format of a tile stream
+enum { W_BF16 = 0, W_FP8 = 1, W_MX4 = 2, W_MX6 = 3 };   // weight format of a tile stream
 
 // row-major [N, ld] -> fragment-major tiles in the km row order (N % 16 == 0, K % 32 == 0)
 __global__ __launch_bounds__(256) void emmax_repack_km_kernel(const bf16_t* __restrict__ src, int ld, u32x4_t* __restrict__ dst, int N, int K,
@@ -126,6 +126,104 @@ __global__ __launch_bounds__(256) void emmax_dequant_mx4_kernel(const uint32_t* 
     }
 }
 
+// ---- MXFP6 e2m3 copies (kernels.h: launch_quant_mx6) -- the same integer arithmetic, blocks, scale rule and scale stream as the MXFP4 pair.
+// x = |w| / 2^e as the fixed-point number x 2^42 (mx4_code above); the grid's step is 1/8 below 2 (subnormals and the first binade), 1/4 in
+// [2, 4), 1/2 in [4, 8): round to nearest in the binade's step, ties to the even multiple -- a carry into the next binade lands on its first
+// code, which is even -- and saturate at code 31 (7.5)
+__device__ __forceinline__ uint32_t mx6_code(uint32_t mag /* bf16 bits without the sign */, int e) {
+    const int E = (int)(mag >> 7);
+    const uint64_t S = E ? (0x80u | (mag & 0x7fu)) : (mag & 0x7fu);
+    const int sh = (E ? E : 1) - 127 - 7 - e + 42;
+    const uint64_t x = sh < 0 ? 0 : (S << min(sh, 50));   // (2^50 and above saturate like anything from 7.75 on)
+    const int b = x < (2ull << 42) ? 39 : x < (4ull << 42) ? 40 : 41;   // log2 of the step in units of 2^-42
+    const uint64_t n = (x + ((1ull << (b - 1)) - 1) + ((x >> b) & 1ull)) >> b;
+    const uint32_t code = (uint32_t)n + (b == 39 ? 0u : b == 40 ? 8u : 16u);   // [2, 4): n = 8 .. 16 -> codes 16 .. 24; [4, 8): -> 24 .. 32
+    return min(code, 31u);
+}
+// bf16 bits of the e2m3 value of the 6-bit code times 2^e, e in [-127, 127]: I 2^t with I = 1 .. 15 (exact, denormal results included; past the
+// largest bf16: infinity)
+__device__ __forceinline__ uint32_t mx6_value_bits(uint32_t code, int e) {
+    const uint32_t c = code & 31u, sign = (code & 32u) << 10;
+    if (!c) return 0u;
+    const uint32_t I = c < 8 ? c : (8u | (c & 7u));
+    const int t = e - 3 + (c < 16 ? 0 : (int)(c >> 3) - 1);
+    const int hb = 31 - __clz((int)I);
+    const int P = t + hb;
+    if (P > 127) return sign | 0x7f80u;
+    if (P >= -126) return sign | ((uint32_t)(P + 127) << 7) | ((I << (7 - hb)) & 0x7fu);
+    return sign | (I << (t + 133));   // t >= -130
+}
+// One thread per (tile, row): 128 k = four blocks; block g of row r is lane 16 g + r of the tile: dwords 0-3 of its six in the tile's first KiB, 4-5 behind it
+__global__ __launch_bounds__(256) void emmax_quant_mx6_kernel(const bf16_t* __restrict__ src, int ld, uint32_t* __restrict__ tiles, uint32_t* __restrict__ scales,
+                                                             int N, int K, int perm, int head_dim) {
+    const int KT = K / 128;
+    const size_t total = (size_t)N * KT;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int r = (int)(i & 15);
+        const size_t tile = i >> 4;
+        const int kt = (int)(tile % KT), nt = (int)(tile / KT);
+        const bf16_t* row = src + (size_t)km_src_row(perm, head_dim, nt, r) * ld + (size_t)kt * 128;
+        uint32_t codes = 0;
+        for (int g = 0; g < 4; ++g) {
+            u32x4_t v[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) v[c] = *(const u32x4_t*)(row + g * 32 + c * 8);
+            uint32_t amax = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int d = 0; d < 4; ++d) amax = max(amax, max(v[c][d] & 0x7fffu, (v[c][d] >> 16) & 0x7fffu));
+            const int E = (int)(amax >> 7);
+            const int code = amax == 0 ? 127 : max(E - 2, 0);
+            const int e = code - 127;
+            codes |= (uint32_t)code << (8 * g);
+            uint32_t q[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int d = 0; d < 8; ++d) {
+                    const uint32_t h = (v[c][d >> 1] >> (16 * (d & 1))) & 0xffffu;
+                    const uint32_t el = mx6_code(h & 0x7fffu, e) | ((h >> 10) & 32u);
+                    const int bit = 6 * (8 * c + d);   // element i of the block in bits [6 i, 6 i + 6) of the 192
+                    q[bit >> 5] |= el << (bit & 31);
+                    if ((bit & 31) > 26) q[(bit >> 5) + 1] |= el >> (32 - (bit & 31));
+                }
+            const size_t lane = (size_t)(g * 16 + r);
+#pragma unroll
+            for (int d = 0; d < 4; ++d) tiles[tile * 384 + lane * 4 + d] = q[d];
+            tiles[tile * 384 + 256 + lane * 2] = q[4];
+            tiles[tile * 384 + 256 + lane * 2 + 1] = q[5];
+        }
+        scales[i] = codes;
+    }
+}
+__global__ __launch_bounds__(256) void emmax_dequant_mx6_kernel(const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ scales, bf16_t* __restrict__ dst,
+                                                               int ld, int N, int K, int perm, int head_dim) {
+    const int KT = K / 128;
+    const size_t total = (size_t)N * KT * 16;   // one thread per (tile, lane, quarter): 8 elements
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int c = (int)(i & 3), lane = (int)((i >> 2) & 63), r = lane & 15, g = lane >> 4;
+        const size_t tile = i >> 8;
+        const int kt = (int)(tile % KT), nt = (int)(tile / KT);
+        uint32_t q[6];
+#pragma unroll
+        for (int d = 0; d < 4; ++d) q[d] = tiles[tile * 384 + (size_t)lane * 4 + d];
+        q[4] = tiles[tile * 384 + 256 + (size_t)lane * 2];
+        q[5] = tiles[tile * 384 + 256 + (size_t)lane * 2 + 1];
+        const int e = (int)((scales[tile * 16 + r] >> (8 * g)) & 0xffu) - 127;
+        uint32_t h[8];
+#pragma unroll
+        for (int d = 0; d < 8; ++d) {
+            const int bit = 6 * (8 * c + d);
+            uint32_t el = q[bit >> 5] >> (bit & 31);
+            if ((bit & 31) > 26) el |= q[(bit >> 5) + 1] << (32 - (bit & 31));
+            h[d] = mx6_value_bits(el & 63u, e);
+        }
+        const u32x4_t o = {h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
+        *(u32x4_t*)(dst + (size_t)km_src_row(perm, head_dim, nt, r) * ld + (size_t)kt * 128 + g * 32 + c * 8) = o;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // grid: one block per CU; block b owns a contiguous range of tiles (launcher: at most KM_MAX_TILES).
 // Dynamic LDS: float part[8 waves][tiles_cap][64][4] + float sumsq[8][16] + the activation staging (XATTN: the merged rows, bf16
@@ -152,21 +250,30 @@ __global__ __launch_bounds__(256) void emmax_dequant_mx4_kernel(const uint32_t* 
 // register state of the MX4 form (WF below): QD sets of a tile's QS load steps and their scale dwords; nothing in the other forms
 template <bool ON, int QD, int QS> struct Mx4Tiles {};
 template <int QD, int QS> struct Mx4Tiles<true, QD, QS> { u32x4_t w[QD][QS]; uint32_t s[QD][QS]; };
+// ... of the MX6 form: per load step the lane's six dwords (a 16-byte and an 8-byte load) and the row's scale dword; nothing in the other forms
+template <bool ON, int QD, int QS> struct Mx6Tiles {};
+template <int QD, int QS> struct Mx6Tiles<true, QD, QS> { u32x4_t w[QD][QS]; u32x2_t h[QD][QS]; uint32_t s[QD][QS]; };
 // WF (weight format of the tiles): W_BF16; W_FP8 (above); W_MX4: OCP MXFP4 -- e2m1 elements, one e8m0 scale per 32 k of a row.  One 1 KiB tile =
 // 16 rows x 128 k: lane l holds row l & 15, dword j of its 16 bytes = the 8 k of group l >> 4 of the tile's j-th 32-wide MFMA step (element e in
 // nibble e), so ONE load feeds four MFMAs; the scales are a second stream in the same tile order, one dword of four e8m0 codes per (tile, row)
 // = 64 B per tile, fetched by the sixteen rows' lanes as one request.  v_cvt_scalef32_pk_bf16_fp4 widens two elements and applies the block
 // scale (the code shifted into an fp32 exponent); a de-quantised value is exact in bf16, so MFMA, prologues and epilogues are the bf16 form's.
 // Four tiles (16 KiB + scales) per wave in flight.
+// W_MX6: OCP MXFP6 e2m3, the same blocks and scale stream.  One tile = 16 rows x 128 k = 1536 B: lane l (row l & 15, g = l >> 4) owns the 32 elements of
+// scale block g of its row -- six dwords, 16 bytes at 16 l of the tile's first KiB and 8 bytes at 8 l of the 512 B behind it, both requests contiguous
+// across the wave -- because v_cvt_scalef32_pk32_bf16_fp6 takes ONE scale for its 32 elements.  One conversion gives the lane the A fragments of the
+// step's four MFMAs: MFMA j takes elements 8 j .. 8 j + 7 = k0 + 32 g + 8 j + (0 .. 7), where the MX4 form has k0 + 32 j + 8 g -- so the activation
+// fragments of these instantiations are fetched with the roles of j and g exchanged (x_chunk below; the blocks stay contiguous in k as OCP defines them).
+// Three tiles (18 KiB + scales) per wave in flight: six dwords a step and the conversion's sixteen result registers leave room for no fourth set.
 template <int MODE, bool NORM, bool XATTN, int WF, bool R32, int NB, bool ROLL, bool EX = false>
 __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p) {
-    constexpr bool FP8 = WF == W_FP8, MX4 = WF == W_MX4;
+    constexpr bool FP8 = WF == W_FP8, MX4 = WF == W_MX4, MX6 = WF == W_MX6;
     static_assert(!EX || (NB == 16 && WF == W_BF16 && !ROLL), "exact numerics: sixteen window rows = eight batch rows x two terms, bf16 weights");
     extern __shared__ __attribute__((aligned(16))) unsigned char km_smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g4 = lane >> 4, c16 = lane & 15;
     const int B = p.batch, K = p.K;
-    constexpr int KS = MX4 ? 128 : FP8 ? 64 : 32;   // elements per load step
+    constexpr int KS = (MX4 || MX6) ? 128 : FP8 ? 64 : 32;   // elements per load step
     constexpr int NSTEP = KM_STEPS * 32 / KS;     // load steps per tile and wave
     const int KT = K / KS;                        // load steps of a whole row
     const int KTW = KT / KM_WAVES;                // ... of this wave's slice (launcher: K % (8 * KS) == 0, KTW <= NSTEP)
@@ -195,7 +302,8 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
     if (e_on) tile4_prefetch<MODE, R32>(p, e_c, e_tile, e_rq, pre_a, pre_b, pre_pos, pre_pg);
 
     // ---- weight stream: buffer loads, the (tile, step) offset in an SGPR, the lane's 16 bytes in the VGPR offset ----
-    const unsigned w_bytes = MX4 ? (unsigned)((size_t)p.n_groups * 8 * (size_t)K) : (unsigned)((size_t)p.n_groups * 16 * (size_t)K * (FP8 ? 1 : 2));
+    const unsigned w_bytes = MX6 ? (unsigned)((size_t)p.n_groups * 12 * (size_t)K)
+                           : MX4 ? (unsigned)((size_t)p.n_groups * 8 * (size_t)K) : (unsigned)((size_t)p.n_groups * 16 * (size_t)K * (FP8 ? 1 : 2));
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (int)w_bytes, 0x00020000);
     const unsigned voff = (unsigned)lane * 16u;
     u32x4_t wa[NSTEP], wb[NSTEP];   // two tiles in flight
@@ -226,7 +334,29 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
 #pragma unroll
         for (int s = 0; s < QS; ++s) issue4_one(d, tl, s);
     };
-    auto issue_first = [&]() { if constexpr (MX4) issue4(0, 0); else issue(wa, 0); };
+    // MX6: three register sets of a tile's four load steps (empty elsewhere: everything that touches it sits under `if constexpr (MX6)`).  A step past
+    // the block's tiles or the wave's slice masks all three offsets past their descriptors: zeros, no traffic, scale code 0
+    constexpr int QD6 = 3;
+    Mx6Tiles<MX6, QD6, QS> q6;
+    auto issue6_one = [&](int d, int tl, int s) {
+        if constexpr (MX6) {
+            const unsigned s_bytes = w_bytes / 24u;   // 64 B of codes per 1536 B tile
+            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w4_scales, 0, (int)s_bytes, 0x00020000);
+            const int ok = (tl < ntb && s < KTW) ? -1 : 0;
+            const unsigned ti = (unsigned)((t_lo + tl) * KT + wave * KTW + s);
+            const unsigned so = ((ti * 1536u) & (unsigned)ok) | (w_bytes & (unsigned)~ok);
+            q6.w[d][s] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, voff, so, 2));
+            q6.h[d][s] = __builtin_bit_cast(u32x2_t, __builtin_amdgcn_raw_buffer_load_b64(wrsrc, 1024u + (unsigned)lane * 8u, so, 2));
+            q6.s[d][s] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(srsrc, (unsigned)c16 * 4u, ((ti * 64u) & (unsigned)ok) | (s_bytes & (unsigned)~ok), 2);
+        }
+    };
+    auto issue6 = [&](int d, int tl) {
+#pragma unroll
+        for (int s = 0; s < QS; ++s) issue6_one(d, tl, s);
+    };
+    auto issue_first = [&]() { if constexpr (MX6) issue6(0, 0); else if constexpr (MX4) issue4(0, 0); else issue(wa, 0); };
+    // 16-byte chunk (8 elements) of the wave's slice that fragment s holds for k-group g: 4 s + g; MX6 (fragment 4 S + j of load step S): 16 S + 4 g + j
+    auto x_chunk = [&](int s, int g) { return MX6 ? (s >> 2) * 16 + g * 4 + (s & 3) : s * 4 + g; };
 
     // ---- activations: this wave's K slice as MFMA B fragments (batch row = lane & 15, k = 8 (lane >> 4) .. + 8 of a 32-step) ----
     // Fetched ROW-shaped -- one contiguous 1 KiB request per batch row, lane l the 8 elements [8 l, 8 l + 8) of the slice -- and
@@ -271,7 +401,9 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
         __syncthreads();
 #pragma unroll
         for (int s = 0; s < KM_STEPS; ++s) {
-            const int k0 = (wave * ksl + s) * 32 + g4 * 8;
+            // (two spellings of one address: written through x_chunk for every format, the fp8 / MX4 forms compile to three scalar instructions in
+            // another order than before -- they keep theirs)
+            const int k0 = MX6 ? wave * ksl * 32 + x_chunk(s, g4) * 8 : (wave * ksl + s) * 32 + g4 * 8;
             const u32x4_t v = (s < ksl && col_live(c16)) ? *(const u32x4_t*)(xlds + ((size_t)c16 * K + k0) * 2) : (u32x4_t){0u, 0u, 0u, 0u};
             xf[s] = __builtin_bit_cast(bf16x8_t, v);
         }
@@ -347,11 +479,14 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
         // wave-private: the reads below only need this wave's own LDS writes to have landed (hipcc's lgkmcnt), no barrier
 #pragma unroll
         for (int s = 0; s < KM_STEPS; ++s) {
-            const u32x4_t v = (s < ksl && col_live(c16)) ? *(const u32x4_t*)(xw + (size_t)c16 * XPITCH + (size_t)(s * 4 + g4) * 16) : (u32x4_t){0u, 0u, 0u, 0u};
+            const u32x4_t v = (s < ksl && col_live(c16)) ? *(const u32x4_t*)(xw + (size_t)c16 * XPITCH + (size_t)x_chunk(s, g4) * 16) : (u32x4_t){0u, 0u, 0u, 0u};
             xf[s] = __builtin_bit_cast(bf16x8_t, v);
         }
     }
-    if constexpr (MX4) {
+    if constexpr (MX6) {
+#pragma unroll
+        for (int d = 1; d < QD6; ++d) issue6(d, d);
+    } else if constexpr (MX4) {
 #pragma unroll
         for (int d = 1; d < QD; ++d) issue4(d, d);
     } else
@@ -391,7 +526,28 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
             if (tl < ntb) *(f32x4_t*)(part_of(wave) + ((size_t)tl * 64 + lane) * 4) = acc;
         }
     };
-    if constexpr (MX4) {
+    // MX6: set d holds tile tl; per load step ONE conversion (the lane's block, byte g of the row's scale dword) and four MFMAs; the set's step is
+    // refilled with the tile three ahead as soon as its MFMAs have issued
+    auto run_tile6 = [&](int d, int tl) {
+        if constexpr (MX6) {
+            f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < QS; ++s) {
+                bf16x8_t a[4];
+                mx6x32_to_bf16x8(q6.w[d][s], q6.h[d][s], e8m0_scale(q6.s[d][s], g4), a);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[j], xf[4 * s + j], acc, 0, 0, 0);
+                issue6_one(d, tl + QD6, s);
+            }
+            if (tl < ntb) *(f32x4_t*)(part_of(wave) + ((size_t)tl * 64 + lane) * 4) = acc;
+        }
+    };
+    if constexpr (MX6) {
+        for (int tl = 0; tl < ntb; tl += QD6) {
+#pragma unroll
+            for (int d = 0; d < QD6; ++d) run_tile6(d, tl + d);
+        }
+    } else if constexpr (MX4) {
         for (int tl = 0; tl < ntb; tl += QD) {
 #pragma unroll
             for (int d = 0; d < QD; ++d) run_tile4(d, tl + d);
@@ -533,9 +689,9 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
 // the start (22 / 12 KiB per wave), every register refilled with the next phase's step as soon as its MFMA has issued.
 // y = h + W x in place (+ the per-row scale with fp8 weights).
 // ---------------------------------------------------------------------------------------------------------------------
-// (MX4 tiles: a load step is four fragments, so eight rows run two phases of 24 -- 97 KiB of windows against 89)
+// (MX4 / MX6 tiles: a load step is four fragments, so eight rows run two phases of 24 -- 97 KiB of windows against 89)
 template <int NB, int WF = 0> struct KdShape {
-    static constexpr int FR = NB == 8 ? (WF == W_MX4 ? 24 : 22) : 12;      // fragments (32 elements) per phase and wave
+    static constexpr int FR = NB == 8 ? ((WF == W_MX4 || WF == W_MX6) ? 24 : 22) : 12;      // fragments (32 elements) per phase and wave
     static constexpr int NPH = NB == 8 ? 2 : 4;       // phases: K <= 8 waves x NPH x FR x 32 = 11264 / 12288
     static constexpr int XP = FR * 64 + 16;           // bytes per staged row slice
     static constexpr int CH = (FR * 4 + 63) / 64;     // 16-byte chunks per lane and row of a phase
@@ -544,7 +700,7 @@ template <int NB, int WF = 0> struct KdShape {
 // emmax_decode_km_kernel); the row registers hold the fp32 chunk as two quads (r[2 b], r[2 b + 1]).
 template <int WF, bool R32, int NB, bool EX = false>
 __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_kmd_kernel(GemvParams p) {
-    constexpr bool FP8 = WF == W_FP8, MX4 = WF == W_MX4;
+    constexpr bool FP8 = WF == W_FP8, MX4 = WF == W_MX4, MX6 = WF == W_MX6;
     static_assert(!EX || (NB == 16 && WF == W_BF16 && R32), "exact numerics: eight batch rows x two terms, bf16 weights, fp32 residual stream");
     extern __shared__ __attribute__((aligned(16))) unsigned char km_smem[];
     using S = KdShape<NB, WF>;
@@ -552,7 +708,7 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_kmd_kernel(GemvParams p
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g4 = lane >> 4, c16 = lane & 15;
     const int B = p.batch, K = p.K;
-    constexpr int FPS = MX4 ? 4 : FP8 ? 2 : 1, KS = 32 * FPS;   // fragments / elements per load step
+    constexpr int FPS = (MX4 || MX6) ? 4 : FP8 ? 2 : 1, KS = 32 * FPS;   // fragments / elements per load step
     constexpr int NST = FR / FPS;                            // load steps per phase
     const int KT = K / KS;
     const int kq = KT / KM_WAVES, kr = KT % KM_WAVES;
@@ -630,16 +786,25 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_kmd_kernel(GemvParams p
     load_rows(1, xb);
 
     // ---- weights: phase 0 in flight now, later phases refilled register by register ----
-    const unsigned w_bytes = MX4 ? (unsigned)((size_t)p.n_groups * 8 * (size_t)K) : (unsigned)((size_t)p.n_groups * 16 * (size_t)K * (FP8 ? 1 : 2));
+    const unsigned w_bytes = MX6 ? (unsigned)((size_t)p.n_groups * 12 * (size_t)K)
+                           : MX4 ? (unsigned)((size_t)p.n_groups * 8 * (size_t)K) : (unsigned)((size_t)p.n_groups * 16 * (size_t)K * (FP8 ? 1 : 2));
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (int)w_bytes, 0x00020000);
     const unsigned voff = (unsigned)lane * 16u;
     u32x4_t w[NST];
     // MX4: the scale dword of each load step (emmax_decode_km_kernel: 64 B per tile in the tiles' order, 4 bytes per row)
     Mx4Tiles<MX4, 1, NST> q4;
+    // MX6: dwords 4-5 of the lane's six (w[s] holds 0-3) and the scale dword of each load step
+    Mx6Tiles<MX6, 1, NST> q6;
     auto issue_w = [&](int ph, int s) {   // load step s of phase ph (past the wave's slice: out of range = zeros, no traffic)
         const int ok = (ph * NST + s < k_n) ? -1 : 0;
-        const unsigned so = ((unsigned)((tile * KT + k_lo + ph * NST + s) * 1024) & (unsigned)ok) | (w_bytes & (unsigned)~ok);
+        const unsigned so = ((unsigned)((tile * KT + k_lo + ph * NST + s) * (MX6 ? 1536 : 1024)) & (unsigned)ok) | (w_bytes & (unsigned)~ok);
         w[s] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, voff, so, 2));
+        if constexpr (MX6) {
+            const unsigned s_bytes = w_bytes / 24u;
+            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w4_scales, 0, (int)s_bytes, 0x00020000);
+            q6.h[0][s] = __builtin_bit_cast(u32x2_t, __builtin_amdgcn_raw_buffer_load_b64(wrsrc, 1024u + (unsigned)lane * 8u, so, 2));
+            q6.s[0][s] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(srsrc, (unsigned)c16 * 4u, ((unsigned)((tile * KT + k_lo + ph * NST + s) * 64) & (unsigned)ok) | (s_bytes & (unsigned)~ok), 2);
+        }
         if constexpr (MX4) {
             const unsigned s_bytes = w_bytes / 16u;
             const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w4_scales, 0, (int)s_bytes, 0x00020000);
@@ -652,13 +817,19 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_kmd_kernel(GemvParams p
 
     f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
     // batch column = lane & 15; columns past the batch are zero (their window rows hold zeros; NB = 8: columns 8-15 have no row at all)
-    const unsigned char* xcol = xw + (size_t)min(c16, NB - 1) * XP + (size_t)g4 * 16;
+    // (MX6: fragment 4 s + j of load step s is the lane's chunk 16 s + 4 g + j of the window row -- the roles of j and g exchanged, emmax_decode_km_kernel)
+    const unsigned char* xcol = xw + (size_t)min(c16, NB - 1) * XP + (size_t)g4 * (MX6 ? 64 : 16);
     auto frag = [&](int f) {
-        const u32x4_t v = *(const u32x4_t*)(xcol + (size_t)f * 64);
+        const u32x4_t v = *(const u32x4_t*)(xcol + (size_t)(MX6 ? (f >> 2) * 256 + (f & 3) * 16 : f * 64));
         return __builtin_bit_cast(bf16x8_t, (EX ? (c16 & 7) < B : c16 < B) ? v : (u32x4_t){0u, 0u, 0u, 0u});
     };
     auto mfma_step = [&](int s) {
-        if constexpr (MX4) {
+        if constexpr (MX6) {
+            bf16x8_t a[4];
+            mx6x32_to_bf16x8(w[s], q6.h[0][s], e8m0_scale(q6.s[0][s], g4), a);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[j], frag(4 * s + j), acc, 0, 0, 0);
+        } else if constexpr (MX4) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(mx4x8_to_bf16x8(w[s][j], e8m0_scale(q4.s[0][s], j)), frag(4 * s + j), acc, 0, 0, 0);
         } else if constexpr (FP8) {
@@ -739,10 +910,10 @@ int km_launch_nb(const GemvParams& p, const ProjGeom& g, hipStream_t stream) {
 }
 template <int MODE, bool NORM, bool XATTN, int WF>
 int km_launch_t(const GemvParams& p, const ProjGeom& g, hipStream_t stream) {
-    if constexpr (WF == W_MX4 && XATTN) {   // split partials of 9-16 rows x K do not fit the LDS stage: those batches exist in the one-split form only
+    if constexpr ((WF == W_MX4 || WF == W_MX6) && XATTN) {   // split partials of 9-16 rows x K do not fit the LDS stage: those batches exist in the one-split form only
         return km_launch_nb<MODE, NORM, XATTN, WF, 8, false>(p, g, stream);
     } else {
-        if constexpr (WF != W_MX4) {   // (the MX4 form always refills step by step: one instantiation per batch width)
+        if constexpr (WF != W_MX4 && WF != W_MX6) {   // (the MX4 / MX6 forms always refill step by step: one instantiation per batch width)
             if (g.roll)
                 return g.nb == 8 ? km_launch_nb<MODE, NORM, XATTN, WF, 8, true>(p, g, stream) : km_launch_nb<MODE, NORM, XATTN, WF, 16, true>(p, g, stream);
         }
@@ -784,14 +955,14 @@ int km_launch_mode(int mode, const GemvParams& p, const ProjGeom& g, hipStream_t
 struct KdDims { int fr, nph, xp; };
 template <int NB, int WF> constexpr KdDims kd_dims() { return {KdShape<NB, WF>::FR, KdShape<NB, WF>::NPH, KdShape<NB, WF>::XP}; }
 KdDims kd_dims_of(int nb, int wf) {
-    if (nb == 8) return wf == W_MX4 ? kd_dims<8, W_MX4>() : wf == W_FP8 ? kd_dims<8, W_FP8>() : kd_dims<8, W_BF16>();
-    return wf == W_MX4 ? kd_dims<16, W_MX4>() : wf == W_FP8 ? kd_dims<16, W_FP8>() : kd_dims<16, W_BF16>();
+    if (nb == 8) return wf == W_MX6 ? kd_dims<8, W_MX6>() : wf == W_MX4 ? kd_dims<8, W_MX4>() : wf == W_FP8 ? kd_dims<8, W_FP8>() : kd_dims<8, W_BF16>();
+    return wf == W_MX6 ? kd_dims<16, W_MX6>() : wf == W_MX4 ? kd_dims<16, W_MX4>() : wf == W_FP8 ? kd_dims<16, W_FP8>() : kd_dims<16, W_BF16>();
 }
 
 // the phased down form (y = h + W x, one 16-row tile per block): K in whole load steps, at least one per wave, a wave's share within
 // NPH phases of FR fragments
 bool kmd_takes(const ProjShape& s, int B, int nb, ProjGeom* g) {
-    const int fps = s.wfmt == PW_MX4 ? 4 : s.wfmt == PW_FP8 ? 2 : 1, ks = 32 * fps;
+    const int fps = (s.wfmt == PW_MX4 || s.wfmt == PW_MX6) ? 4 : s.wfmt == PW_FP8 ? 2 : 1, ks = 32 * fps;
     const KdDims d = kd_dims_of(nb, s.wfmt);
     if (s.K % ks || s.n_rows % 16 || s.attn_part) return false;
     if (cdiv(s.K / ks, KM_WAVES) > d.nph * (d.fr / fps) || s.K / ks < KM_WAVES) return false;
@@ -806,7 +977,7 @@ bool kmd_takes(const ProjShape& s, int B, int nb, ProjGeom* g) {
 // per CU with at most KM_MAX_TILES tiles each, one LDS region per wave (the window [NB][XPITCH] overlaid by the partial tiles) + sumsq
 // (+ with split partials in: the merged rows)
 bool kms_takes(const ProjShape& s, int B, int nb, ProjGeom* g) {
-    const int ks = s.wfmt == PW_MX4 ? 128 : s.wfmt == PW_FP8 ? 64 : 32;
+    const int ks = (s.wfmt == PW_MX4 || s.wfmt == PW_MX6) ? 128 : s.wfmt == PW_FP8 ? 64 : 32;
     if (s.K % (KM_WAVES * ks) || s.K > KM_WAVES * KM_STEPS * 32 || s.n_rows % 16) return false;
     if (s.mode == GEMV_QKV && (s.head_dim % 16 || s.head_dim < 16)) return false;
     g->nb = nb;
@@ -826,13 +997,14 @@ bool kms_takes(const ProjShape& s, int B, int nb, ProjGeom* g) {
 
 }  // namespace
 
-// What this file takes (the km copy of the matrix: launch_repack_km; fp8: decode_mfma.hip's e4m3 tiles of the permuted rows; MXFP4 tiles).
-// 17-64 rows: decode_kmp.hip's answer (bf16 / fp8; MXFP4 under ProjShape::mx4_wide).  Exact numerics: 1-8 rows (two terms per batch row in the sixteen MFMA columns), bf16.
+// What this file takes (the km copy of the matrix: launch_repack_km; fp8: decode_mfma.hip's e4m3 tiles of the permuted rows; MXFP4 / MXFP6 tiles).
+// 17-64 rows: decode_kmp.hip's answer (bf16 / fp8; MXFP4 under ProjShape::mx4_wide; MXFP6: none).  Exact numerics: 1-8 rows (two terms per batch row in the sixteen MFMA columns), bf16.
 bool decode_km_takes(const ProjShape& s, int B, ProjGeom* out) {
     ProjGeom g = {};
     bool ok = false;
     const bool kfits = s.K % (KM_WAVES * 32) == 0 && s.K <= KM_WAVES * KM_STEPS * 32;
     if (B < 1 || B > EMMAX_MAX_DECODE_BATCH || s.mode < GEMV_QKV || s.mode > GEMV_PLAIN) return false;
+    if (B > 16 && s.wfmt == PW_MX6) return false;   // MXFP6 tiles: 1-16 rows, this file's kernels only (decode_kmp.hip has no MX6 form)
     if (B > 16) return decode_kmp_takes(s, B, out);   // two batch tiles: decode_kmp.hip (MXFP4 tiles: only when the shape says wide, else this file's kernels only)
     if (s.attn_part && (s.mode != GEMV_RESID || s.K != s.Hq * 128)) return false;
     if (s.exact) {
@@ -842,13 +1014,14 @@ bool decode_km_takes(const ProjShape& s, int B, ProjGeom* out) {
         ok = (s.mode == GEMV_RESID && !s.attn_part && !kfits) ? kmd_takes(s, B, 16, &g) : kms_takes(s, B, 16, &g);
     } else if (s.mode == GEMV_RESID && !s.attn_part && s.K > KM_WAVES * KM_STEPS * 32) {   // the down projection: the phased form (natural row order copy)
         // tuning switch km_down = 0: decode_mfma.hip, the A/B partner (no other kernel reads MXFP4 tiles: no switch there)
-        ok = (s.wfmt == PW_MX4 || emmax_tune().km_down) && kmd_takes(s, B, B <= 8 ? 8 : 16, &g);
+        ok = (s.wfmt == PW_MX4 || s.wfmt == PW_MX6 || emmax_tune().km_down) && kmd_takes(s, B, B <= 8 ? 8 : 16, &g);
     } else {
         // the bf16 o-proj with the split merge stays on decode_mfma.hip (12.5 against 15.4 us at B = 8: the merge of 8 rows
         // queues behind this kernel's 16 KiB weight heads); with fp8 weights this kernel is the faster one (10.3 against 10.8).
         // MXFP4: split partials of 9-16 rows x K do not fit the LDS stage, those batches exist in the one-split form only
-        if (s.attn_part && (s.wfmt == PW_BF16 || (s.wfmt == PW_MX4 && B > 8))) return false;
-        g.roll = s.wfmt != PW_MX4 && emmax_tune().km_roll;   // (the MX4 form always refills step by step)
+        // MXFP4 / MXFP6: split partials of 9-16 rows x K do not fit the LDS stage, those batches exist in the one-split form only
+        if (s.attn_part && (s.wfmt == PW_BF16 || ((s.wfmt == PW_MX4 || s.wfmt == PW_MX6) && B > 8))) return false;
+        g.roll = s.wfmt != PW_MX4 && s.wfmt != PW_MX6 && emmax_tune().km_roll;   // (the MX4 / MX6 forms always refill step by step)
         ok = kms_takes(s, B, B <= 8 ? 8 : 16, &g);
     }
     if (ok && out) *out = g;
@@ -874,6 +1047,12 @@ int decode_km_init() {
     KM_SETQ(GEMV_QKV, true, false, false); KM_SETQ(GEMV_GATEUP, true, false, false); KM_SETQ(GEMV_LMHEAD, true, false, false); KM_SETQ(GEMV_PLAIN, false, false, false);
     KM_SETQ(GEMV_RESID, false, false, false); KM_SETQ(GEMV_RESID, false, false, true);
     KM_SET4(GEMV_RESID, false, true, W_MX4, false, 8, false); KM_SET4(GEMV_RESID, false, true, W_MX4, true, 8, false);   // (the split merge: 1-8 rows)
+    // the MX6 forms (the same set)
+#define KM_SET6(M, N_, X, R) KM_SET4(M, N_, X, W_MX6, R, 8, false); KM_SET4(M, N_, X, W_MX6, R, 16, false)
+    KM_SET6(GEMV_QKV, true, false, false); KM_SET6(GEMV_GATEUP, true, false, false); KM_SET6(GEMV_LMHEAD, true, false, false); KM_SET6(GEMV_PLAIN, false, false, false);
+    KM_SET6(GEMV_RESID, false, false, false); KM_SET6(GEMV_RESID, false, false, true);
+    KM_SET4(GEMV_RESID, false, true, W_MX6, false, 8, false); KM_SET4(GEMV_RESID, false, true, W_MX6, true, 8, false);
+#undef KM_SET6
 #undef KM_SETQ
 #undef KM_SET
 #undef KM_SET1
@@ -885,6 +1064,7 @@ int decode_km_init() {
     KD_SET(W_BF16, false, 8); KD_SET(W_FP8, false, 8); KD_SET(W_BF16, true, 8); KD_SET(W_FP8, true, 8);
     KD_SET(W_BF16, false, 16); KD_SET(W_FP8, false, 16); KD_SET(W_BF16, true, 16); KD_SET(W_FP8, true, 16);
     KD_SET(W_MX4, false, 8); KD_SET(W_MX4, true, 8); KD_SET(W_MX4, false, 16); KD_SET(W_MX4, true, 16);
+    KD_SET(W_MX6, false, 8); KD_SET(W_MX6, true, 8); KD_SET(W_MX6, false, 16); KD_SET(W_MX6, true, 16);
 #undef KD_SET
 #define KX_SET(M, N_, X) \
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)emmax_decode_km_kernel<M, N_, X, W_BF16, M == GEMV_RESID, 16, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)
@@ -923,6 +1103,17 @@ int launch_dequant_mx4(const void* tiles, const void* scales, void* dst, int ld,
     hipLaunchKernelGGL(emmax_dequant_mx4_kernel, dim3(2048), dim3(256), 0, stream, (const uint32_t*)tiles, (const uint32_t*)scales, (bf16_t*)dst, ld, N, K, perm, head_dim);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
+// (the MXFP6 tiles cover the same 16 rows x 128 k: the shape rules are the MXFP4 pair's)
+int launch_quant_mx6(const void* src, int ld, void* tiles, void* scales, int N, int K, int perm, int head_dim, hipStream_t stream) {
+    if (!mx4_shape_ok(ld, N, K, perm, head_dim)) return -1;
+    hipLaunchKernelGGL(emmax_quant_mx6_kernel, dim3(2048), dim3(256), 0, stream, (const bf16_t*)src, ld, (uint32_t*)tiles, (uint32_t*)scales, N, K, perm, head_dim);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+int launch_dequant_mx6(const void* tiles, const void* scales, void* dst, int ld, int N, int K, int perm, int head_dim, hipStream_t stream) {
+    if (!mx4_shape_ok(ld, N, K, perm, head_dim)) return -1;
+    hipLaunchKernelGGL(emmax_dequant_mx6_kernel, dim3(2048), dim3(256), 0, stream, (const uint32_t*)tiles, (const uint32_t*)scales, (bf16_t*)dst, ld, N, K, perm, head_dim);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
 
 // p.W: the km copy of the matrix (launch_repack_km; fp8: decode_mfma.hip's e4m3 tiles of the permuted rows + p.wscale in the same
 // row order).  -2: decode_km_takes says no (K % 256, K > 4096, more than 8 tiles per block ...) -- the caller uses decode_mfma.hip.
@@ -937,10 +1128,12 @@ int launch_decode_km(int mode, const GemvParams& p_in, int B, hipStream_t stream
     if (grid_out) *grid_out = g.grid;
     if (p.exact) return g.phased ? kmd_launch<W_BF16, 16, true>(p, g, stream) : km_launch_mode_x(mode, p, g, stream);
     if (g.phased) {
+        if (p.w4_scales && p.w_mx6) return g.nb == 8 ? kmd_launch<W_MX6, 8>(p, g, stream) : kmd_launch<W_MX6, 16>(p, g, stream);
         if (p.w4_scales) return g.nb == 8 ? kmd_launch<W_MX4, 8>(p, g, stream) : kmd_launch<W_MX4, 16>(p, g, stream);
         if (g.nb == 8) return p.wscale ? kmd_launch<W_FP8, 8>(p, g, stream) : kmd_launch<W_BF16, 8>(p, g, stream);
         return p.wscale ? kmd_launch<W_FP8, 16>(p, g, stream) : kmd_launch<W_BF16, 16>(p, g, stream);
     }
+    if (p.w4_scales && p.w_mx6) return km_launch_mode<W_MX6>(mode, p, g, stream);
     if (p.w4_scales) return km_launch_mode<W_MX4>(mode, p, g, stream);
     return p.wscale ? km_launch_mode<W_FP8>(mode, p, g, stream) : km_launch_mode<W_BF16>(mode, p, g, stream);
 }

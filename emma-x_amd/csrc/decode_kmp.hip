@@ -480,7 +480,7 @@ int kp_dispatch(int mode, const GemvParams& p, const ProjGeom& g, hipStream_t st
 // tile per block).  33-64 rows (two halves of four waves): qkv (3 tiles per block), the o-proj (1), gate/up (6) with K within eight phases of
 // a four-way split; the down projection and the lm-head run as two launches of <= 32 rows (step.hip: stage_chunk)
 bool decode_kmp_takes(const ProjShape& s, int B, ProjGeom* out) {
-    if (B < 17 || B > 64 || s.mode < GEMV_QKV || s.mode > GEMV_PLAIN || (s.wfmt == PW_MX4 && !s.mx4_wide)) return false;
+    if (B < 17 || B > 64 || s.mode < GEMV_QKV || s.mode > GEMV_PLAIN || (s.wfmt == PW_MX4 && !s.mx4_wide) || s.wfmt == PW_MX6) return false;
     const int ks = s.wfmt == PW_MX4 ? 128 : s.wfmt == PW_FP8 ? 64 : 32, kw = B > 32 ? 4 : KP_WAVES, max_ph = B > 32 ? 8 : 11;
     if (s.K % ks || s.K / ks < kw || cdiv(s.K / ks, kw) * ks > max_ph * KP_PH * 32 || s.n_rows % 16 || s.attn_part) return false;
     if (s.mode == GEMV_QKV && (s.head_dim % 16 || s.head_dim < 16)) return false;

@@ -620,7 +620,7 @@ static int mfma_kc(int B, int K, int tiles, int kstep) {
 // What this file takes: 1-8 rows of the fragment-major copy (bf16, or e4m3 tiles + per-row scales); K in whole k-steps (32 elements; fp8: 64),
 // rows in whole tiles (qkv / gate-up: pairs of tiles); the modes with a norm prologue in ONE K phase; head_dim / 32 a power of two (qkv)
 bool decode_mfma_takes(const ProjShape& s, int B, ProjGeom* out) {
-    if (B < 1 || B > MFMA_MAX_B || s.mode < GEMV_QKV || s.mode > GEMV_PLAIN || s.wfmt == PW_MX4) return false;
+    if (B < 1 || B > MFMA_MAX_B || s.mode < GEMV_QKV || s.mode > GEMV_PLAIN || s.wfmt == PW_MX4 || s.wfmt == PW_MX6) return false;
     const bool fp8 = s.wfmt == PW_FP8, norm = s.mode == GEMV_QKV || s.mode == GEMV_GATEUP || s.mode == GEMV_LMHEAD;
     const int tiles = (s.mode == GEMV_QKV || s.mode == GEMV_GATEUP) ? 2 : 1, kstep = fp8 ? 64 : 32;
     if (s.K % kstep || s.n_rows % (16 * tiles)) {

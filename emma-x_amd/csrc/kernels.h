@@ -317,6 +317,7 @@ struct GemvParams {
     long long kv24;         // exact numerics: > 0 = the K / V caches are 24-bit (common.h: x24) -- kcache / vcache point at the bf16 plane of kv24 elements,
                             //   the 8-bit extension plane follows it; 0 = fp32 rows
     const void* w4_scales;  // decode_km.hip, non-null: W holds MXFP4 tiles (launch_quant_mx4) and this is their scale stream; null: bf16 / fp8 (wscale)
+    int w_mx6;              // decode_km.hip, with w4_scales: 1 = W holds MXFP6 e2m3 tiles (launch_quant_mx6: 1536 B per 16 rows x 128 k), the scale stream is the same
 };
 // (where the QKV epilogues put the new K / V rows: gemv_kv_row / gemv_kv_store_x, decode_epilogue.h -- device code, this is also a host header)
 
@@ -326,7 +327,7 @@ struct GemvParams {
 // <family>_takes(shape, B, geometry out): no HIP call, no stream; it reads emmax_tune() where the launcher did (km_down, km_roll, ks_oproj).
 // The launcher derives the shape, asks its own check and launches from the geometry it returned (or from the one its caller already
 // got from the same check: the `geom` argument of the launchers): a launcher has no shape-based refusal its check does not report.
-enum { PW_BF16 = 0, PW_FP8 = 1, PW_MX4 = 2 };   // weight format (fp8: the row copy for the staged GEMV, the e4m3 tiles for the MFMA families)
+enum { PW_BF16 = 0, PW_FP8 = 1, PW_MX4 = 2, PW_MX6 = 3 };   // weight format (fp8: the row copy for the staged GEMV, the e4m3 tiles for the MFMA families; MX4 / MX6: decode_km.hip's block-scaled tiles)
 struct ProjShape {
     int mode, K, n_rows, head_dim, Hq;
     int wfmt;
@@ -336,7 +337,7 @@ struct ProjShape {
     bool mx4_wide;                       // MXFP4 tiles at 17-64 rows: decode_kmp.hip's MX4 form may take them (the model froze the tuning switch mx4_wide; proj_shape leaves it false)
 };
 static inline ProjShape proj_shape(int mode, const GemvParams& p) {
-    return {mode, p.K, p.n_rows, p.head_dim, p.Hq, p.w4_scales ? PW_MX4 : p.wscale ? PW_FP8 : PW_BF16, p.exact != 0, p.h32 != nullptr,
+    return {mode, p.K, p.n_rows, p.head_dim, p.Hq, p.w4_scales ? (p.w_mx6 ? PW_MX6 : PW_MX4) : p.wscale ? PW_FP8 : PW_BF16, p.exact != 0, p.h32 != nullptr,
             p.attn_part != nullptr, p.x_tok != nullptr, p.nsplit, p.max_parts, p.max_grid, p.ldw % 8 == 0 && p.ldx % 8 == 0};
 }
 // the launch geometry a check hands its launcher (fields a family does not use stay 0)
@@ -793,6 +794,12 @@ int launch_decode_km(int mode, const GemvParams& p, int B, hipStream_t stream, i
 // the copy holds back as bf16 rows (exact), each at the source row the permutation took it from.
 int launch_quant_mx4(const void* src, int ld, void* tiles, void* scales, int N, int K, int perm, int head_dim, hipStream_t stream);
 int launch_dequant_mx4(const void* tiles, const void* scales, void* dst, int ld, int N, int K, int perm, int head_dim, hipStream_t stream);
+// ... as OCP MXFP6 e2m3 (include/emmax.h pins the format): the same blocks, scale rule and scale stream; elements w / 2^e rounded to nearest even onto
+// +-{0, 0.125 .. 0.875, 1 .. 1.875, 2 .. 3.75, 4 .. 7.5}, saturating.  tiles: N K 6 / 8 bytes -- per (16 rows x 128 k) 1536 B: lane (row r, block g) = 16 g + r
+// owns the 32 elements of ONE scale block as six dwords (element i in bits [6 i, 6 i + 6)): dwords 0-3 at byte 16 lane of the tile's first KiB, dwords 4-5 at
+// byte 8 lane of the 512 B behind it (both loads of a wave are contiguous).  Same shape rules and row orders as launch_quant_mx4.
+int launch_quant_mx6(const void* src, int ld, void* tiles, void* scales, int N, int K, int perm, int head_dim, hipStream_t stream);
+int launch_dequant_mx6(const void* tiles, const void* scales, void* dst, int ld, int N, int K, int perm, int head_dim, hipStream_t stream);
 bool decode_km_enabled();
 int decode_km_init();   // raise the dynamic-LDS limit of every instantiation (call once, outside graph capture)
 // decode_kmp.hip: batch 17-32 (two batch tiles per weight tile, the K slice in phases), bf16 weights, same copies; launch_decode_km routes there

@@ -93,9 +93,10 @@ static int check_config(const emmax_config& c, bool format_rules = true) {
     if (G != 1 && G != 2 && G != 4 && G != 8) return fail(EMMAX_ERR_INVALID, "GQA group %d unsupported (1,2,4,8)", G);
     if (c.inter % 16) return fail(EMMAX_ERR_INVALID, "LLM intermediate size must be a multiple of 16");
     if (c.vocab % 8) return fail(EMMAX_ERR_INVALID, "vocab must be a multiple of 8");
-    if (c.decode_fp8 < 0 || c.decode_fp8 > 2) return fail(EMMAX_ERR_INVALID, "decode_fp8 %d: 0 (bf16), 1 (fp8-e4m3) or 2 (MXFP4)", c.decode_fp8);
+    if (c.decode_fp8 < 0 || c.decode_fp8 == 3 || c.decode_fp8 > 4) return fail(EMMAX_ERR_INVALID, "decode_fp8 %d: 0 (bf16), 1 (fp8-e4m3), 2 (MXFP4) or 4 (MXFP6)", c.decode_fp8);
     if (c.decode_fp8 == 1 && (c.hidden % 64 || (c.n_heads * c.head_dim) % 64)) return fail(EMMAX_ERR_INVALID, "fp8 decode needs K % 64 == 0");
-    if (c.decode_fp8 == 2 && format_rules) {
+    if ((c.decode_fp8 == 2 || c.decode_fp8 == 4) && format_rules) {
+        const char* const fmt = c.decode_fp8 == 4 ? "MXFP6" : "MXFP4";   // (MXFP6 tiles cover the same 16 rows x 128 k per load step: one set of rules)
         // MXFP4 tiles are read by decode_km.hip alone, at every batch: the model must be a shape that file takes.  qkv / o-proj / gate-up / lm-head:
         // eight waves x whole load steps of 128 elements, at most sixteen fragments per wave -- K % 1024 == 0 and K <= 4096, at most 8 tiles
         // for each of 256 blocks (N <= 32768); the down projection on the phased kernel: whole load steps (K % 128 == 0), K above 4096 and
@@ -104,11 +105,11 @@ static int check_config(const emmax_config& c, bool format_rules = true) {
         // two together (accepted exactly when the planner serves 8 rows)
         const int q_dim = c.n_heads * c.head_dim, qkv_dim = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim;
         if (c.hidden % 1024 || c.hidden > 4096 || q_dim % 1024 || q_dim > 4096)
-            return fail(EMMAX_ERR_INVALID, "MXFP4 decode weights need hidden (%d) and n_heads * head_dim (%d) in multiples of 1024 up to 4096", c.hidden, q_dim);
+            return fail(EMMAX_ERR_INVALID, "%s decode weights need hidden (%d) and n_heads * head_dim (%d) in multiples of 1024 up to 4096", fmt, c.hidden, q_dim);
         if (c.inter % 128 || c.inter <= 4096 || c.inter > 12288)
-            return fail(EMMAX_ERR_INVALID, "MXFP4 decode weights need an intermediate size (%d) that is a multiple of 128, above 4096 and at most 12288", c.inter);
+            return fail(EMMAX_ERR_INVALID, "%s decode weights need an intermediate size (%d) that is a multiple of 128, above 4096 and at most 12288", fmt, c.inter);
         if (qkv_dim > 32768 || 2 * c.inter > 32768 || pad_to(c.vocab, 128) > 32768)
-            return fail(EMMAX_ERR_INVALID, "MXFP4 decode weights need at most 32768 rows per projection (qkv %d, gate/up %d, vocab %d)", qkv_dim, 2 * c.inter, c.vocab);
+            return fail(EMMAX_ERR_INVALID, "%s decode weights need at most 32768 rows per projection (qkv %d, gate/up %d, vocab %d)", fmt, qkv_dim, 2 * c.inter, c.vocab);
     }
     return 0;
 }
@@ -166,6 +167,10 @@ static void derive(emmax_model* m) {
     for (auto& L : m->layers)
         for (const ProjDim& d : layer_projs(m)) L.proj[d.stage].q4w = m->mx4_wide;
     m->lm_head_w.q4w = m->mx4_wide;
+    m->mx6 = c.decode_fp8 == 4;   // (mx4_wide does not apply: decode_kmp.hip has no MX6 form)
+    for (auto& L : m->layers)
+        for (const ProjDim& d : layer_projs(m)) L.proj[d.stage].q6 = m->mx6;
+    m->lm_head_w.q6 = m->mx6;
 }
 
 static void plan_arena(emmax_model* m, Bump& b) {
@@ -205,6 +210,8 @@ static void plan_arena(emmax_model* m, Bump& b) {
         for (const ProjDim& p : dims) { ProjW& w = L.proj[p.stage]; w.r8 = nullptr; w.sc = w.km_sc = nullptr; w.q4 = w.q4s = nullptr; }
         if (m->mx4)   // 4.25 bits per weight: every batch reads these, so they live in the main arena
             for (const ProjDim& p : dims) { ProjW& w = L.proj[p.stage]; w.q4 = b.bytes(p.N * p.K / 2); w.q4s = b.bytes(p.N * p.K / 32); }
+        if (m->mx6)   // 6.25 bits per weight, main arena for the same reason
+            for (const ProjDim& p : dims) { ProjW& w = L.proj[p.stage]; w.q4 = b.bytes(p.N * p.K / 8 * 6); w.q4s = b.bytes(p.N * p.K / 32); }
         if (m->fp8) {   // fp8 tiles take half the bytes; every batch regime reads some of them, so they live in the main arena
             for (const ProjDim& p : dims) L.proj[p.stage].fm = b.take(p.N * p.K / 2);
             q->km = b.take(dims[0].N * dims[0].K / 2);
@@ -226,6 +233,7 @@ static void plan_arena(emmax_model* m, Bump& b) {
         lm.r8 = b.take((int64_t)m->vocab_p * m->H / 2);
     }
     if (m->mx4) { lm.q4 = b.bytes((int64_t)m->vocab_p * m->H / 2); lm.q4s = b.bytes((int64_t)m->vocab_p * m->H / 32); }
+    if (m->mx6) { lm.q4 = b.bytes((int64_t)m->vocab_p * m->H / 8 * 6); lm.q4s = b.bytes((int64_t)m->vocab_p * m->H / 32); }
 }
 
 // bf16 models: the copies only the batch >= 3 decode kernels read -- row-permuted fragment-major qkv / gate-up (decode_km.hip),
@@ -401,6 +409,12 @@ int emmax_model_finalize(emmax_model* m, void* arena, int64_t arena_bytes, emmax
                 KCHK(launch_quant_mx4(w.rm, (int)d.K, w.q4, w.q4s, (int)d.N, (int)d.K, d.perm, d.perm_hd, st));
                 KCHK(launch_dequant_mx4(w.q4, w.q4s, w.rm, (int)d.K, (int)d.N, (int)d.K, d.perm, d.perm_hd, st));
             }
+        if (m->mx6)   // the same for the e2m3 tiles: prefill, extend, verify, scoring and the taps evaluate the quantised model
+            for (const ProjDim& d : layer_projs(m)) {
+                ProjW& w = L.proj[d.stage];
+                KCHK(launch_quant_mx6(w.rm, (int)d.K, w.q4, w.q4s, (int)d.N, (int)d.K, d.perm, d.perm_hd, st));
+                KCHK(launch_dequant_mx6(w.q4, w.q4s, w.rm, (int)d.K, (int)d.N, (int)d.K, d.perm, d.perm_hd, st));
+            }
     }
     PUT1("language_model.model.norm.weight", m->H, m->final_norm);
     PUT2("language_model.lm_head.weight", m->vocab, m->H, m->lm_head_w.rm, m->H, 0);
@@ -412,12 +426,16 @@ int emmax_model_finalize(emmax_model* m, void* arena, int64_t arena_bytes, emmax
         KCHK(launch_quant_mx4(m->lm_head_w.rm, m->H, m->lm_head_w.q4, m->lm_head_w.q4s, m->vocab_p, m->H, 0, 0, st));
         KCHK(launch_dequant_mx4(m->lm_head_w.q4, m->lm_head_w.q4s, m->lm_head_w.rm, m->H, m->vocab_p, m->H, 0, 0, st));
     }
+    if (m->mx6) {
+        KCHK(launch_quant_mx6(m->lm_head_w.rm, m->H, m->lm_head_w.q4, m->lm_head_w.q4s, m->vocab_p, m->H, 0, 0, st));
+        KCHK(launch_dequant_mx6(m->lm_head_w.q4, m->lm_head_w.q4s, m->lm_head_w.rm, m->H, m->vocab_p, m->H, 0, 0, st));
+    }
 #undef PUT2
 #undef PUT1
     HIPCHK(hipStreamSynchronize(st));
     m->finalized = true;
     m->ln_folded = fold_ln;
-    m->aux_built = m->fp8 || m->mx4;
+    m->aux_built = m->fp8 || m->mxq();
     m->bound.clear();
     return 0;
 }
@@ -436,7 +454,7 @@ int emmax_config_max_decode_batch(const emmax_config* cfg, int exact) {
 
 int64_t emmax_model_aux_bytes(const emmax_model* m) {
     if (!m) return -1;
-    if (m->fp8 || m->mx4) return 0;
+    if (m->fp8 || m->mxq()) return 0;
     // sized on a copy of the layer table: a const query must not move the pointers of a built arena
     emmax_model tmp = *m;
     Bump b{nullptr};
@@ -447,7 +465,7 @@ int64_t emmax_model_aux_bytes(const emmax_model* m) {
 int emmax_model_build_aux(emmax_model* m, void* aux, int64_t aux_bytes, emmax_stream stream) {
     if (!m) return fail(EMMAX_ERR_INVALID, "null argument");
     if (!m->finalized) return fail(EMMAX_ERR_STATE, "emmax_model_build_aux before emmax_model_finalize");
-    if (m->fp8 || m->mx4) return 0;   // nothing to build: the e4m3 / MXFP4 copies of every regime are in the main arena
+    if (m->fp8 || m->mxq()) return 0;   // nothing to build: the e4m3 / MXFP4 / MXFP6 copies of every regime are in the main arena
     if (!aux) return fail(EMMAX_ERR_INVALID, "null argument");
     hipStream_t st = (hipStream_t)stream;
     const bool ab = emmax_tune().km == 0;

@@ -859,6 +859,29 @@ int emmax_op_gemm_small_mxfp4(const void* x, const void* tiles, const void* scal
     if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_gemm_small_mxfp4: unsupported shape (N %% 16 and N <= 32768; K %% 1024 and K <= 4096)");
     return 0;
 }
+int emmax_op_quant_mxfp6(const void* W, int ld, void* tiles, void* scales, int N, int K, int perm, int perm_hd, emmax_stream st) {
+    if (!W || !tiles || !scales) return fail(EMMAX_ERR_INVALID, "emmax_op_quant_mxfp6: null argument");
+    int r = launch_quant_mx6(W, ld, tiles, scales, N, K, perm, perm_hd, (hipStream_t)st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_quant_mxfp6: N %% 16, K %% 128, ld %% 8, ld >= K (perm 1: N %% head_dim, head_dim %% 16; perm 2: N %% 32) required");
+    return 0;
+}
+int emmax_op_dequant_mxfp6(const void* tiles, const void* scales, void* W, int ld, int N, int K, int perm, int perm_hd, emmax_stream st) {
+    if (!W || !tiles || !scales) return fail(EMMAX_ERR_INVALID, "emmax_op_dequant_mxfp6: null argument");
+    int r = launch_dequant_mx6(tiles, scales, W, ld, N, K, perm, perm_hd, (hipStream_t)st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_dequant_mxfp6: N %% 16, K %% 128, ld %% 8, ld >= K (perm 1: N %% head_dim, head_dim %% 16; perm 2: N %% 32) required");
+    return 0;
+}
+int emmax_op_gemm_small_mxfp6(const void* x, const void* tiles, const void* scales, void* y, int B, int N, int K, emmax_stream st) {
+    if (!x || !tiles || !scales || !y) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_small_mxfp6: null argument");
+    GemvParams p = plain_gemv(x, tiles, y, N, K);
+    p.w4_scales = scales;
+    p.w_mx6 = 1;
+    if (B < 1 || B > 16) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_small_mxfp6: batch %d outside 1..16", B);
+    // (the K-split kernel only: the phased kernel of the down projection is reached through emmax_op_decode_stage)
+    const int r = launch_decode_km(GEMV_PLAIN, p, B, (hipStream_t)st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_gemm_small_mxfp6: unsupported shape (N %% 16 and N <= 32768; K %% 1024 and K <= 4096)");
+    return 0;
+}
 int emmax_op_gemm_wide_mxfp4(const void* x, const void* tiles, const void* scales, void* y, int B, int N, int K, emmax_stream st) {
     if (!x || !tiles || !scales || !y) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_wide_mxfp4: null argument");
     if (B < 17 || B > EMMAX_KMP_ROWS) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_wide_mxfp4: batch %d outside 17..%d", B, EMMAX_KMP_ROWS);

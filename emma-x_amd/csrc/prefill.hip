@@ -138,7 +138,9 @@ int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B
     const int max_rows = session_max_rows(s);
     if (B <= 0 || B > s->max_batch || B > max_rows)
         return fail(EMMAX_ERR_INVALID, "prefill batch %d outside 1..min(max_batch=%d, %d) (%s)", B, s->max_batch, max_rows,
-                    (m->mx4 && B >= 1 && B <= s->max_batch)   // (the model's limit binds: it can move after the session was created, with the attention switches)
+                    (m->mx6 && B >= 1 && B <= s->max_batch)
+                        ? "the limit of a model with MXFP6 decode weights, re-read at every prefill: emmax_model_max_decode_batch"
+                    : (m->mx4 && B >= 1 && B <= s->max_batch)   // (the model's limit binds: it can move after the session was created, with the attention switches)
                         ? "the limit of a model with MXFP4 decode weights, re-read at every prefill: emmax_model_max_decode_batch"
                         : "decode batches above 8 need the shapes decode_km.hip takes: emmax_model_max_decode_batch");
     if (B >= EMMAX_MFMA_MIN_BATCH && !m->aux_built)

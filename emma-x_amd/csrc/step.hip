@@ -20,19 +20,19 @@ static int fp8_gemv_mask(int B) {
 // Which copies of a projection's matrix exist -- flags, not pointers: the planner asks before any arena exists.  copies_of: what a
 // ProjW holds now (launch_proj); copies_planned: what the model has or, before emmax_model_build_aux, will have.
 // q4w: the MXFP4 tiles are served at 17-64 rows too (decode_kmp.hip's MX4 form): the model was created under the tuning switch mx4_wide
-struct ProjCopies { bool rm, r8, sc, km, fm, q4; int f8bit; bool q4w; };
-static ProjCopies copies_of(const ProjW& w) { return {w.rm != nullptr, w.r8 != nullptr, w.sc != nullptr, w.km != nullptr, w.fm != nullptr, w.q4 != nullptr, w.f8bit, w.q4 != nullptr && w.q4w}; }
+struct ProjCopies { bool rm, r8, sc, km, fm, q4; int f8bit; bool q4w; bool q6; };   // q4: block-scaled tiles exist; q6: they are MXFP6 (else MXFP4)
+static ProjCopies copies_of(const ProjW& w) { return {w.rm != nullptr, w.r8 != nullptr, w.sc != nullptr, w.km != nullptr, w.fm != nullptr, w.q4 != nullptr, w.f8bit, w.q4 != nullptr && w.q4w, w.q4 != nullptr && w.q6}; }
 static ProjCopies copies_planned(const emmax_model* m, int stage) {
     // decode_mfma.hip's qkv / gate-up pair: fp8 models always, bf16 models when the aux arena was (or would now be) built with the tuning switch km = 0
     const bool pair = stage == STAGE_QKV || stage == STAGE_GATEUP;
-    const bool fm = m->fp8 || (!m->mx4 && (!pair || (m->aux_built ? m->aux_ab : emmax_tune().km == 0)));
+    const bool fm = m->fp8 || (!m->mxq() && (!pair || (m->aux_built ? m->aux_ab : emmax_tune().km == 0)));
     const int bit = stage == STAGE_QKV ? F8_QKV : stage == STAGE_OPROJ ? F8_OPROJ : stage == STAGE_GATEUP ? F8_GATEUP : stage == STAGE_DOWN ? F8_DOWN : F8_LMHEAD;
-    return {true, m->fp8, m->fp8, !m->mx4, fm, m->mx4, bit, m->mx4 && m->mx4_wide};
+    return {true, m->fp8, m->fp8, !m->mxq(), fm, m->mxq(), bit, m->mx4 && m->mx4_wide, m->mx6};
 }
 
 // Which launcher family takes a projection at B rows (EMMAX_VIA_*), EMMAX_VIA_NONE when none does, ROUTE_NO_FM when only decode_mfma.hip's copy
 // (not built) could have.  The order of preference: exact numerics -- the two-term forms or nothing (decode_ks.hip at batch 1-2,
-// decode_km.hip's EX kernels at 3-8); MXFP4 tiles -- decode_km.hip at every batch 1-16, decode_kmp.hip's MX4 form at 17-64 when the model froze mx4_wide, no other kernel reads them; the fp8 row GEMV at batch
+// decode_km.hip's EX kernels at 3-8); MXFP4 / MXFP6 tiles -- decode_km.hip at every batch 1-16, for MXFP4 decode_kmp.hip's MX4 form at 17-64 when the model froze mx4_wide, no other kernel reads them; the fp8 row GEMV at batch
 // 1-2 under the fp8_gemv mask; batch >= 3 and fp8: the K-split MFMA kernels (decode_km.hip, 17-64 rows decode_kmp.hip), else decode_mfma.hip;
 // else (batch 1-2, bf16) decode_ks.hip, else decode.hip's staged GEMV.  Pure: every question goes to a family's own check, and *g is the
 // geometry the chosen family's check returned -- its launcher runs from it without asking again.
@@ -46,12 +46,12 @@ static int proj_route(const ProjCopies& c, ProjShape s, int B, ProjGeom* g) {
         return c.km && decode_km_enabled() && decode_km_takes(s, B, g) ? EMMAX_VIA_KM : EMMAX_VIA_NONE;
     }
     if (c.q4) {
-        s.wfmt = PW_MX4;
+        s.wfmt = c.q6 ? PW_MX6 : PW_MX4;   // (MXFP6 tiles: the same routes at 1-16 rows, no wide form)
         // the MXFP4 down projection runs on the phased kernel only: the K-split form would take K <= 4096, but the format's error lines were
         // measured on the phased kernel alone (policy, not a kernel limit -- the same line emmax_model_create draws)
         if (c.f8bit == F8_DOWN && s.K <= 4096) return EMMAX_VIA_NONE;
         // 17-64 rows: decode_kmp.hip's MX4 form, for a model that froze the tuning switch mx4_wide (decode_km_takes hands them on under the shape's flag)
-        s.mx4_wide = c.q4w;
+        s.mx4_wide = c.q4w && !c.q6;
         if (!decode_km_takes(s, B, g)) return EMMAX_VIA_NONE;
         return B > 16 ? EMMAX_VIA_KMP : EMMAX_VIA_KM;
     }
@@ -86,7 +86,7 @@ static int launch_proj(const ProjW& w, GemvParams& p, int B, hipStream_t st, int
             return launch_decode_gemv_staged(mode, p, B, g, st, grid_out);
         case EMMAX_VIA_KM:
         case EMMAX_VIA_KMP:
-            if (w.q4) { p.W = w.q4; p.w4_scales = w.q4s; }
+            if (w.q4) { p.W = w.q4; p.w4_scales = w.q4s; p.w_mx6 = w.q6 ? 1 : 0; }
             else { p.W = w.km; p.wscale = w.sc ? w.km_sc : nullptr; }
             return launch_decode_km(mode, p, B, st, grid_out, &g);
         case EMMAX_VIA_MFMA:
@@ -97,7 +97,7 @@ static int launch_proj(const ProjW& w, GemvParams& p, int B, hipStream_t st, int
         default: break;
     }
     if (p.exact) return fail(EMMAX_ERR_INVALID, "exact numerics: no two-term kernel for this projection (batch %d, K %d)", B, p.K);
-    if (w.q4) return fail(EMMAX_ERR_INVALID, "MXFP4 decode weights: no kernel for this projection (batch %d of 1-%d, K %d)", B, w.q4w ? EMMAX_MAX_DECODE_BATCH : 16, p.K);
+    if (w.q4) return fail(EMMAX_ERR_INVALID, "%s decode weights: no kernel for this projection (batch %d of 1-%d, K %d)", w.q6 ? "MXFP6" : "MXFP4", B, (w.q4w && !w.q6) ? EMMAX_MAX_DECODE_BATCH : 16, p.K);
     return -1;   // no family takes this shape at this batch
 }
 
@@ -623,7 +623,7 @@ static int run_qkv0_with_embed(emmax_session* s, int B, hipStream_t st) {
 int run_decode_step(emmax_session* s, int B, hipStream_t st) {
     emmax_model* m = s->m;
     // batch 1-2 on bf16 weights: the embedding row is read by layer 0's qkv launch itself (decode_ks.hip, when it takes the launch) -- one launch fewer
-    const bool fold_embed = B < EMMAX_MFMA_MIN_BATCH && !m->fp8 && !m->mx4 && decode_ks_enabled() && emmax_tune().fold_embed != 0;
+    const bool fold_embed = B < EMMAX_MFMA_MIN_BATCH && !m->fp8 && !m->mxq() && decode_ks_enabled() && emmax_tune().fold_embed != 0;
     if (!fold_embed) KCHK(launch_decode_embed(s->rows.cur_tok, m->embed, s->dh, B, m->H, m->vocab, st, s->exact ? s->dh32 : h32_of(s)));
     const bool taps = s->taps.step.on;   // (nothing bound: the launches below are all there is)
     if (taps)

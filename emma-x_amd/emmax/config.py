@@ -73,12 +73,20 @@ class LlmConfig:
 
 # decode_weight_dtype -> emmax_config.decode_fp8 (include/emmax.h)
 DECODE_WEIGHT_DTYPES = {"bf16": 0, "fp8": 1, "mxfp4": 2}
+# ... the formats added since (3 is no format: emmax_model_create refuses it)
+DECODE_WEIGHT_DTYPES_EXT = {"mxfp6": 4}
 
 
 def check_decode_weight_dtype(name: str) -> str:
-    if name not in DECODE_WEIGHT_DTYPES:
-        raise ValueError(f"decode_weight_dtype must be one of {sorted(DECODE_WEIGHT_DTYPES)}, got {name!r}")
+    if not isinstance(name, str) or (name not in DECODE_WEIGHT_DTYPES and name not in DECODE_WEIGHT_DTYPES_EXT):
+        raise ValueError(f"decode_weight_dtype must be one of {sorted({**DECODE_WEIGHT_DTYPES, **DECODE_WEIGHT_DTYPES_EXT})}, got {name!r}")
     return name
+
+
+def decode_weight_code(name: str) -> int:
+    """emmax_config.decode_fp8 of a decode_weight_dtype name"""
+    name = check_decode_weight_dtype(name)
+    return DECODE_WEIGHT_DTYPES[name] if name in DECODE_WEIGHT_DTYPES else DECODE_WEIGHT_DTYPES_EXT[name]
 
 
 @dataclass
@@ -96,7 +104,8 @@ class EmmaXConfig:
     arch_specifier: str = "no-align+fused-gelu-mlp"
     image_resize_strategy: str = "resize-naive"
     # MI355X extension (BASELINE config 5): "fp8" streams an e4m3 per-row-scaled copy of the LLM projections in decode; "mxfp4" an OCP MXFP4
-    # copy (e2m1 elements, one e8m0 scale per 32 elements; decode batches 1-16) -- prefill and decode then both evaluate the quantised model
+    # copy (e2m1 elements, one e8m0 scale per 32 elements; decode batches 1-16) -- prefill and decode then both evaluate the quantised model;
+    # "mxfp6" the same with OCP MXFP6 e2m3 elements (6.25 bits per weight, fp8-class accuracy, one model for every pass; decode batches 1-16)
     decode_weight_dtype: str = "bf16"
 
     # --- derived ---

@@ -14,7 +14,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from .config import DECODE_WEIGHT_DTYPES, EmmaXConfig, check_decode_weight_dtype
+from .config import EmmaXConfig, check_decode_weight_dtype, decode_weight_code
 from .weights import param_shapes, validate_state_dict
 
 
@@ -34,7 +34,7 @@ def _config_c(cfg: EmmaXConfig) -> _lib.ConfigC:
         L.hidden_size, L.intermediate_size, L.num_layers, L.num_heads, L.num_kv_heads, L.head_dim, L.vocab_size)
     c.rms_eps, c.rope_theta = L.rms_eps, L.rope_theta
     c.bos_id, c.eos_id, c.pad_id = cfg.bos_token_id, cfg.eos_token_id, cfg.pad_token_id
-    c.decode_fp8 = DECODE_WEIGHT_DTYPES[check_decode_weight_dtype(getattr(cfg, "decode_weight_dtype", "bf16"))]
+    c.decode_fp8 = decode_weight_code(getattr(cfg, "decode_weight_dtype", "bf16"))
     return c
 
 
@@ -168,8 +168,8 @@ class EmmaxEngine:
         return torch.float32 if self.exact else torch.bfloat16
 
     def max_decode_batch(self) -> int:
-        """Rows of one decode batch this model can run (64 for LLaMA-2-7B shapes, 8 for shapes outside the K-split kernels; MXFP4 weights: 16, or 8
-        when nine rows would split the attention; created with mxfp4_wide: up to 64).  Exact numerics: the two-term kernels take 8 rows per launch and larger batches run in chunks
+        """Rows of one decode batch this model can run (64 for LLaMA-2-7B shapes, 8 for shapes outside the K-split kernels; MXFP4 / MXFP6 weights: 16, or 8
+        when nine rows would split the attention; MXFP4 created with mxfp4_wide: up to 64).  Exact numerics: the two-term kernels take 8 rows per launch and larger batches run in chunks
         of 8 -- 64 on the shapes those kernels take, 2 where only the batch 1-2 kernel does."""
         if self.exact:
             return int(self.lib.emmax_model_max_decode_batch_exact(self._model))

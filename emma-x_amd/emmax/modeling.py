@@ -149,11 +149,11 @@ class EmmaXForActionPrediction:
                         **_) -> "EmmaXForActionPrediction":
         """HF directory (config.json + *.safetensors [+ dataset_statistics.json]) or a native Prismatic `.pt` file.
         (`dtype=` is the transformers >= 5 spelling of `torch_dtype=`; `config=` passed by the Auto classes is ignored: the
-        directory is re-read through EmmaXConfig.from_pretrained.)  `decode_weight_dtype`: "bf16" | "fp8" | "mxfp4", the format the decode
+        directory is re-read through EmmaXConfig.from_pretrained.)  `decode_weight_dtype`: "bf16" | "fp8" | "mxfp4" | "mxfp6", the format the decode
         step streams the LLM projections in (None: the config's, bf16)."""
         if load_in_8bit or load_in_4bit:
             raise NotImplementedError("bitsandbytes quantised loading (int8 / NF4 code books) is outside the MI355X hot path and no other format is "
-                                      "substituted for it; the native quantised decode weights are decode_weight_dtype=\"fp8\" or \"mxfp4\"")
+                                      "substituted for it; the native quantised decode weights are decode_weight_dtype=\"fp8\", \"mxfp4\" or \"mxfp6\"")
         if decode_weight_dtype is not None:
             check_decode_weight_dtype(decode_weight_dtype)
         torch_dtype = dtype if dtype is not None else torch_dtype
@@ -195,7 +195,7 @@ class EmmaXForActionPrediction:
     def from_synthetic(cls, config: Optional[EmmaXConfig] = None, seed: int = 0, device: str = "cuda:0", planted: bool = False,
                        decode_weight_dtype: Optional[str] = None, **engine_kw) -> "EmmaXForActionPrediction":
         """Random-init weights with the real names/shapes, generated directly on `device` (no checkpoint offline).
-        `decode_weight_dtype`: "bf16" | "fp8" | "mxfp4" (None: the config's)."""
+        `decode_weight_dtype`: "bf16" | "fp8" | "mxfp4" | "mxfp6" (None: the config's)."""
         config = config or EmmaXConfig.emma_x_7b()
         if decode_weight_dtype is not None:
             config.decode_weight_dtype = check_decode_weight_dtype(decode_weight_dtype)

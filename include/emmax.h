@@ -52,7 +52,9 @@ extern "C" {
  *   emmax_session_set_step_taps, emmax_session_clear_taps, emmax_session_taps, emmax_op_attn_probs(_kv8), emmax_op_tap_rows): new symbols only, the
  *   workspace did not grow; still 12: emmax_gemm_launches (the GEMM's kernel launches as text, host only): a new symbol only; still 12: scoring
  *   without logits (emmax_prefill_score, emmax_op_score_rows, emmax_score_plan): new symbols only, the workspace did not grow; still 12: draft-verified
- *   greedy decoding (emmax_verify, emmax_session_set_budget, emmax_session_output, emmax_op_verify_accept): new symbols only, the workspace did not grow. */
+ *   greedy decoding (emmax_verify, emmax_session_set_budget, emmax_session_output, emmax_op_verify_accept): new symbols only, the workspace did not grow;
+ *   still 12: emmax_config.decode_fp8 = 4 selects MXFP6 decode weights (the struct keeps its layout; 3 stays refused), emmax_op_quant_mxfp6 /
+ *   emmax_op_dequant_mxfp6 / emmax_op_gemm_small_mxfp6: new symbols only. */
 #define EMMAX_ABI_VERSION 12
 
 typedef enum emmax_status {
@@ -90,7 +92,12 @@ typedef struct emmax_config {
                                           v1.0: e2m1 elements, one e8m0 scale per 32 elements along K; 4.25 bits per weight), widened to bf16 in
                                           registers -- decode batches 1-16 (17-64 too for a model created under the tuning switch mx4_wide), LLM shapes with hidden and n_heads * head_dim in multiples of 1024
                                           up to 4096 and an intermediate size % 128 == 0 in 4097..12288 (emmax_model_create refuses others); the
-                                          prefill reads the de-quantised values, so prefill and decode evaluate the same quantised model        */
+                                          prefill reads the de-quantised values, so prefill and decode evaluate the same quantised model;
+                                          4: MXFP6 (OCP MX v1.0, e2m3 elements: sign, two exponent bits, three mantissa bits -- +-{0, 0.125 .. 0.875,
+                                          1 .. 1.875, 2 .. 3.75, 4 .. 7.5} -- and the same e8m0 scale per 32 elements along K; 6.25 bits per
+                                          weight; e3m2 is not built), widened to bf16 in registers -- decode batches 1-16, the LLM shapes of MXFP4,
+                                          the de-quantised values in the prefill's rows as for MXFP4: one model for every pass (prefill, extend,
+                                          verify, scoring, taps, decode).  3 is no format: refused                                               */
 } emmax_config;
 
 const char* emmax_version(void);
@@ -138,12 +145,14 @@ int64_t emmax_model_arena_bytes(const emmax_model* m);
  * under the tuning switches as they are now.  64 (bf16 or fp8 weights) when every LLM projection is a shape the K-split MFMA kernels take
  * (K % 256 (fp8: % 512) == 0 and <= 4096, N <= 32768, intermediate size % 32 (fp8: % 64) == 0 and <= 11264: LLaMA-2-7B is), else usually 8.
  * emmax_model_max_decode_batch_exact: the same for exact-numerics sessions (8 rows per launch, larger batches in chunks of 8): 64 on the
- * shapes decode_km.hip's two-term kernels take, 2 where only decode_ks.hip's do, 0 on fp8 / MXFP4 weights.
+ * shapes decode_km.hip's two-term kernels take, 2 where only decode_ks.hip's do, 0 on fp8 / MXFP4 / MXFP6 weights.
  * MXFP4 models (decode_fp8 = 2): 16 -- decode_km.hip is the only kernel family that reads the 4-bit tiles -- or 8 when a batch of nine rows would
  * split the attention (the o-proj then reads split partials, which its 16-row form does not take); emmax_session_bytes / create refuse a larger
  * max_batch for such a model, naming the format (a model created under the tuning switch mx4_wide: emmax_model_mxfp4_wide below).  The one-split rule reads the tuning switches attn_direct / attn_nsplit: the limit is checked when a
  * session is sized and created and again at every prefill and emmax_slots_open, not inside a step -- changing those switches between a prefill of
- * 9-16 rows and its decode steps makes the step fail with EMMAX_ERR_INVALID (no other kernel reads the 4-bit tiles: there is no fall-back). */
+ * 9-16 rows and its decode steps makes the step fail with EMMAX_ERR_INVALID (no other kernel reads the 4-bit tiles: there is no fall-back).
+ * MXFP6 models (decode_fp8 = 4): the same -- 16, or 8 when nine rows would split the attention; the refusals name MXFP6; the tuning switch mx4_wide
+ * does not concern them (no 17-64-row form reads the 6-bit tiles). */
 int emmax_model_max_decode_batch(const emmax_model* m);
 int emmax_model_max_decode_batch_exact(const emmax_model* m);
 /* 1: the model was created under the tuning switch mx4_wide = 1 on MXFP4 weights -- decode_kmp.hip's MXFP4 form serves it at 17-64 rows, and
@@ -159,7 +168,8 @@ int emmax_model_finalize(emmax_model* m, void* arena_dev, int64_t arena_bytes, e
  * never reads.  They live in a SECOND caller-owned arena, built on demand from the finalized main arena (no bound tensors
  * needed): 13.2 GB at 7B (main arena 15.1 GB; with the tuning switch km = 0 at build time decode_mfma.hip's qkv / gate-up pair is
  * added, +9 GB).  Until it is built, emmax_prefill / emmax_slots_open with B >= 3 return EMMAX_ERR_STATE.  fp8 models keep every
- * e4m3 copy in the main arena, MXFP4 models their 4-bit copy: aux_bytes is 0 and build_aux a no-op. */
+ * e4m3 copy in the main arena, MXFP4 / MXFP6 models their 4-bit / 6-bit copy (N K 6 / 8 bytes of tiles + N K / 32 of scales per projection):
+ * aux_bytes is 0 and build_aux a no-op. */
 int64_t emmax_model_aux_bytes(const emmax_model* m);
 int emmax_model_build_aux(emmax_model* m, void* aux_arena_dev, int64_t aux_bytes, emmax_stream stream);
 
@@ -330,7 +340,7 @@ int emmax_session_context(emmax_session* s, int row0, int n, int32_t* ctx_out_ho
  *                          back to the host (synchronises the stream).
  * EMMAX_ERR_STATE, each with its own message: everything emmax_extend refuses; open request slots; sampling, logits processing, warpers, token rules,
  * a token automaton, bound scores, top / watched log-probabilities or step taps (the accepted ids are argmaxes of raw rows); a model with fp8 decode
- * weights (its prefill multiplies by the unquantised matrices: the pass would verify another model).  bf16 and MXFP4 weights, bf16 and fp8 KV caches
+ * weights (its prefill multiplies by the unquantised matrices: the pass would verify another model).  bf16, MXFP4 and MXFP6 weights, bf16 and fp8 KV caches
  * are served.  EMMAX_ERR_NOMEM: context + lens + 1 (a done row: context + lens) beyond max_ctx or the row's pages; more packed rows than the prefill
  * holds.  A refused call changes nothing: the caller falls back to plain decode steps.
  *   emmax_op_verify_accept the accept walk alone on caller-owned device arrays: argmax_dev [cu[B]] packed as cu_dev [B + 1] says, ids_dev [B][P_max],
@@ -922,7 +932,20 @@ int emmax_op_dequant_mxfp4(const void* tiles_dev, const void* scales_dev, void* 
  * widened in registers.  K % 1024 == 0 and K <= 4096 (the K-split kernel; the phased kernel of the down projection is reached through
  * emmax_op_decode_stage); N % 16 == 0, N <= 32768.  Test hook: pins what the hardware widening does on every scale code. */
 int emmax_op_gemm_small_mxfp4(const void* x_dev, const void* tiles_dev, const void* scales_dev, void* y_dev, int B, int N, int K, emmax_stream stream);
-/* its sibling for 17 <= B <= 32: decode_kmp.hip's MXFP4 form (what a model created under the tuning switch mx4_wide runs at 17-64 rows), plain
+/* The same three for MXFP6 e2m3 (decode_fp8 = 4).  Blocks, the scale rule (e = floor(log2(amax)) - 2 clamped to [-127, 127], code e + 127, an
+ * all-zero block: code 127) and the scale stream (one dword of four codes per (tile, row): scales_out N K / 32 bytes) are MXFP4's; elements are
+ * w / 2^e rounded to nearest, ties to even, onto +-{0, 0.125 .. 0.875 (subnormals), 1 .. 1.875, 2 .. 3.75, 4 .. 7.5}, saturating at 7.5; the 6-bit
+ * code is sign . exponent (2 bits, bias 1) . mantissa (3 bits).  tiles_out: N K 6 / 8 bytes -- tiles of 16 rows x 128 k = 1536 B in decode_km.hip's row
+ * order, lane l = 16 g + r owns the 32 elements of scale block g of row r (consecutive k, as OCP defines a block) as 192 bits, element i in bits
+ * [6 i, 6 i + 6) little endian -- what v_cvt_scalef32_pk32_bf16_fp6 reads from six registers; bytes 0-15 of the 24 at 16 l of the tile's first KiB,
+ * bytes 16-23 at 8 l of the 512 B behind it.  N % 16 == 0, K % 128 == 0, ld % 8 == 0.  emmax_op_dequant_mxfp6 writes the values back as bf16
+ * (exact: four significant bits times a power of two; zeros are +0; a value past the largest bf16 -- scale codes 253 / 254 with large elements,
+ * out of a bf16 weight's reach -- is infinity).  emmax_op_gemm_small_mxfp6: the plain projection, 1 <= B <= 16, K % 1024 == 0 and K <= 4096,
+ * N % 16 == 0, N <= 32768.  Test hook: pins the hardware widening on every element code at every position of a block and on every scale code. */
+int emmax_op_quant_mxfp6(const void* W_dev, int ld, void* tiles_out_dev, void* scales_out_dev, int N, int K, int perm, int perm_hd, emmax_stream stream);
+int emmax_op_dequant_mxfp6(const void* tiles_dev, const void* scales_dev, void* W_out_dev, int ld, int N, int K, int perm, int perm_hd, emmax_stream stream);
+int emmax_op_gemm_small_mxfp6(const void* x_dev, const void* tiles_dev, const void* scales_dev, void* y_dev, int B, int N, int K, emmax_stream stream);
+/* MXFP4's sibling for 17 <= B <= 32: decode_kmp.hip's MXFP4 form (what a model created under the tuning switch mx4_wide runs at 17-64 rows), plain
  * epilogue.  N % 16 == 0, N <= 32768; K % 128 == 0 and at least 1024 (one load step of 128 k for each of eight waves); K <= 4096 (four phases of
  * 128 k per wave), or K <= 11264 with N <= 4096 (the eleven-phase form of the down projection: one tile per block).  Needs no model and no switch. */
 int emmax_op_gemm_wide_mxfp4(const void* x_dev, const void* tiles_dev, const void* scales_dev, void* y_dev, int B, int N, int K, emmax_stream stream);

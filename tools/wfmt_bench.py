@@ -1,13 +1,13 @@
-"""Decode step time and per-launch projection times of the three decode weight formats (bf16, fp8-e4m3, MXFP4) on ONE box, back to back
+"""Decode step time and per-launch projection times of the four decode weight formats (bf16, fp8-e4m3, MXFP4, MXFP6) on ONE box, back to back
 (not the headline bench): the synthetic 7B model, 512-token prompts over one frame each (context 768), batches 1 / 8 / 16 by default (`--batches 16,32,64`: the MXFP4 model is then created wide -- mxfp4_wide=True, decode_kmp.hip's MX4
-form at 17-64 rows -- which leaves its 1-16-row kernels as they are).  The three models are
+form at 17-64 rows -- which leaves its 1-16-row kernels as they are; an MXFP6 model stops at 16 rows and sits those batches out).  The models are
 built once and kept; every (format, batch) point is measured `--rounds` times with the formats alternating inside a round, so that a drift of
 the box shows up as spread between rounds and not as a difference between formats.
 
   ms/step      emmax_generate over `--steps` greedy steps (EOS ignored), host clock around a device synchronise, the bench's method;
   us/launch    emmax_profile_decode_stage: HIP events around one launch per layer (every launch streams another layer's weights).
 
-usage: python tools/wfmt_bench.py [--formats bf16,fp8,mxfp4] [--batches 1,8,16] [--rounds 3] [--steps 64] [--out FILE]"""
+usage: python tools/wfmt_bench.py [--formats bf16,fp8,mxfp4,mxfp6] [--batches 1,8,16] [--rounds 3] [--steps 64] [--out FILE]"""
 import argparse
 import json
 import os
@@ -27,7 +27,7 @@ STAGES = ["qkv", "attn", "oproj", "gateup", "down", "lmhead"]
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--formats", default="bf16,fp8,mxfp4")
+    ap.add_argument("--formats", default="bf16,fp8,mxfp4,mxfp6")
     ap.add_argument("--batches", default="1,8,16")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--steps", type=int, default=64)
@@ -45,9 +45,10 @@ def main():
     for f in formats:
         t0 = time.perf_counter()
         wide = {"mxfp4_wide": True} if f == "mxfp4" and bmax > 16 else {}   # (opt-in: a narrow MXFP4 model stops at 16 rows)
-        m = EmmaXForActionPrediction.from_synthetic(EmmaXConfig.emma_x_7b(), seed=0, device="cuda:0", decode_weight_dtype=f, max_batch=bmax,
+        cap = min(bmax, 16) if f == "mxfp6" else bmax   # (MXFP6 tiles: 1-16 rows; larger batches are skipped for it below)
+        m = EmmaXForActionPrediction.from_synthetic(EmmaXConfig.emma_x_7b(), seed=0, device="cuda:0", decode_weight_dtype=f, max_batch=cap,
                                                     max_prompt=512, max_ctx=256 + 512 + args.steps + 64, **wide)
-        m.engine.ensure_decode_batch(bmax)
+        m.engine.ensure_decode_batch(cap)
         torch.cuda.synchronize()
         models[f] = m
         info[f] = {"weight_bytes": m.engine.weight_bytes(), "max_decode_batch": m.engine.max_decode_batch(), "mxfp4_wide": bool(m.engine.mxfp4_wide), "build_s": round(time.perf_counter() - t0, 1)}
