@@ -771,7 +771,7 @@ bool decode_gemv_takes(const ProjShape& s, int B, ProjGeom* out) {
     if (s.K % 8 || !s.ld_ok || s.K <= 0) return false;
     if (s.mode < GEMV_QKV || s.mode > GEMV_PLAIN) return false;
     const bool fp8 = s.wfmt == PW_FP8, norm = s.mode == GEMV_QKV || s.mode == GEMV_GATEUP || s.mode == GEMV_LMHEAD;
-    if (B < 1 || B > ((s.mode == GEMV_PLAIN && !fp8) ? 8 : 2) || s.wfmt == PW_MX4 || s.wfmt == PW_MX6) return false;
+    if (B < 1 || B > ((s.mode == GEMV_PLAIN && !fp8) ? 8 : 2) || wfmt_is_mx(s.wfmt)) return false;
     ProjGeom g = {};
     const int cap = (128 * 1024 / 2 / B) & ~511;
     g.kc = s.K <= cap ? s.K : (cdiv(cdiv(s.K, cdiv(s.K, cap)), 512) * 512);

@@ -22,6 +22,7 @@
 // The down projection (K = 11008: 43 k-steps per wave would need 172 activation registers) has its own two-phase kernel below
 // (emmax_decode_kmd_kernel).
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "kernels.h"
@@ -34,7 +35,6 @@ constexpr int KM_NT = KM_WAVES * 64;
 constexpr int KM_STEPS = 16;      // bf16 k-steps (32 elements) per tile and wave: K <= 8 * 16 * 32 = 4096
 constexpr int KM_MAX_TILES = 8;   // tiles per block the LDS partial sums hold
 constexpr int PSTRIDE = EMMAX_PSTRIDE;
-enum { W_BF16 = 0, W_FP8 = 1, W_MX4 = 2, W_MX6 = 3 };   // weight format of a tile stream
 
 // row-major [N, ld] -> fragment-major tiles in the km row order (N % 16 == 0, K % 32 == 0)
 __global__ __launch_bounds__(256) void emmax_repack_km_kernel(const bf16_t* __restrict__ src, int ld, u32x4_t* __restrict__ dst, int N, int K,
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void emmax_repack_km_kernel(const bf16_t* __re
     }
 }
 
-// ---- MXFP4 copies (kernels.h: launch_quant_mx4) -- integer arithmetic only, so that bf16 denormals and the clamped exponent come out as the
+// ---- MXFP4 copies (kernels.h: launch_quant_mx) -- integer arithmetic only, so that bf16 denormals and the clamped exponent come out as the
 // format defines them whatever the float modes are.  One thread per (tile, row): 128 k = four blocks, 16 dwords of elements + one of codes.
 // |w| = S 2^q with S the 8-bit significand; x = |w| / 2^e as the fixed-point number x 2^42, compared with the midpoints of the e2m1 grid
 // (ties to the even code: <= below an even code's upper midpoint, < below an odd one's)
@@ -70,6 +70,21 @@ __device__ __forceinline__ uint32_t mx4_value_bits(uint32_t code, int e) {
     if (p >= -126) return sign | ((uint32_t)(p + 127) << 7) | (man << 6);
     return sign | ((2u + man) << (p + 132));            // p = -127, -128: (2 + man) 2^(p - 1) in units of 2^-133
 }
+// what the block-scaled formats share.  The e8m0 code of a block from its largest magnitude (bf16 bits without the sign): floor(log2(amax)) - 2 clamped at
+// -127 (bf16 cannot reach the upper clamp) -- the exponent field less 2, zero for denormals; an all-zero block: 127
+__device__ __forceinline__ uint32_t mx_block_amax(const u32x4_t (&v)[4]) {
+    uint32_t amax = 0;
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int d = 0; d < 4; ++d) amax = max(amax, max(v[g][d] & 0x7fffu, (v[g][d] >> 16) & 0x7fffu));
+    return amax;
+}
+__device__ __forceinline__ int mx_block_code(uint32_t amax) {
+    const int E = (int)(amax >> 7);
+    return amax == 0 ? 127 : max(E - 2, 0);
+}
+// (the (tile, row) index prologue stays written out in the four kernels below: shared as a device function it changes their instruction streams)
 __global__ __launch_bounds__(256) void emmax_quant_mx4_kernel(const bf16_t* __restrict__ src, int ld, uint32_t* __restrict__ tiles, uint32_t* __restrict__ scales,
                                                              int N, int K, int perm, int head_dim) {
     const int KT = K / 128;
@@ -84,14 +99,7 @@ __global__ __launch_bounds__(256) void emmax_quant_mx4_kernel(const bf16_t* __re
             u32x4_t v[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) v[g] = *(const u32x4_t*)(row + j * 32 + g * 8);
-            uint32_t amax = 0;
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int d = 0; d < 4; ++d) amax = max(amax, max(v[g][d] & 0x7fffu, (v[g][d] >> 16) & 0x7fffu));
-            // floor(log2(amax)) - 2 clamped at -127 (bf16 cannot reach the upper clamp): the exponent field less 2, zero for denormals
-            const int E = (int)(amax >> 7);
-            const int code = amax == 0 ? 127 : max(E - 2, 0);
+            const int code = mx_block_code(mx_block_amax(v));
             const int e = code - 127;
             codes |= (uint32_t)code << (8 * j);
 #pragma unroll
@@ -126,7 +134,7 @@ __global__ __launch_bounds__(256) void emmax_dequant_mx4_kernel(const uint32_t* 
     }
 }
 
-// ---- MXFP6 e2m3 copies (kernels.h: launch_quant_mx6) -- the same integer arithmetic, blocks, scale rule and scale stream as the MXFP4 pair.
+// ---- MXFP6 e2m3 copies (kernels.h: launch_quant_mx) -- the same integer arithmetic, blocks, scale rule and scale stream as the MXFP4 pair.
 // x = |w| / 2^e as the fixed-point number x 2^42 (mx4_code above); the grid's step is 1/8 below 2 (subnormals and the first binade), 1/4 in
 // [2, 4), 1/2 in [4, 8): round to nearest in the binade's step, ties to the even multiple -- a carry into the next binade lands on its first
 // code, which is even -- and saturate at code 31 (7.5)
@@ -168,13 +176,7 @@ __global__ __launch_bounds__(256) void emmax_quant_mx6_kernel(const bf16_t* __re
             u32x4_t v[4];
 #pragma unroll
             for (int c = 0; c < 4; ++c) v[c] = *(const u32x4_t*)(row + g * 32 + c * 8);
-            uint32_t amax = 0;
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int d = 0; d < 4; ++d) amax = max(amax, max(v[c][d] & 0x7fffu, (v[c][d] >> 16) & 0x7fffu));
-            const int E = (int)(amax >> 7);
-            const int code = amax == 0 ? 127 : max(E - 2, 0);
+            const int code = mx_block_code(mx_block_amax(v));
             const int e = code - 127;
             codes |= (uint32_t)code << (8 * g);
             uint32_t q[6] = {0u, 0u, 0u, 0u, 0u, 0u};
@@ -247,19 +249,18 @@ __global__ __launch_bounds__(256) void emmax_dequant_mx6_kernel(const uint32_t* 
 // batch column b, the lo terms in column b + 8: the eight columns a batch <= 8 leaves empty carry the second term, so the weight stream, the
 // MFMA count and the register budget are those of the plain kernel; the epilogue adds columns b and b + 8 and hands fp32 results on (fp32 q rows,
 // fp32 RoPE with torch's per-product rounding, the 24-bit / fp32 cache, the SwiGLU product in fp32) as decode_ks.hip's EX form does at batch 1-2.
-// register state of the MX4 form (WF below): QD sets of a tile's QS load steps and their scale dwords; nothing in the other forms
-template <bool ON, int QD, int QS> struct Mx4Tiles {};
-template <int QD, int QS> struct Mx4Tiles<true, QD, QS> { u32x4_t w[QD][QS]; uint32_t s[QD][QS]; };
-// ... of the MX6 form: per load step the lane's six dwords (a 16-byte and an 8-byte load) and the row's scale dword; nothing in the other forms
-template <bool ON, int QD, int QS> struct Mx6Tiles {};
-template <int QD, int QS> struct Mx6Tiles<true, QD, QS> { u32x4_t w[QD][QS]; u32x2_t h[QD][QS]; uint32_t s[QD][QS]; };
-// WF (weight format of the tiles): W_BF16; W_FP8 (above); W_MX4: OCP MXFP4 -- e2m1 elements, one e8m0 scale per 32 k of a row.  One 1 KiB tile =
+// register state of the block-scaled forms (WF below): QD sets of a tile's QS load steps -- per step the lane's 16 bytes and the row's scale dword; MX6: also
+// dwords 4-5 of the lane's six (an 8-byte load).  Nothing in the other forms: everything that touches it sits under `if constexpr (MX)`
+template <int WF, int QD, int QS> struct MxTiles {};
+template <int QD, int QS> struct MxTiles<PW_MX4, QD, QS> { u32x4_t w[QD][QS]; uint32_t s[QD][QS]; };
+template <int QD, int QS> struct MxTiles<PW_MX6, QD, QS> { u32x4_t w[QD][QS]; u32x2_t h[QD][QS]; uint32_t s[QD][QS]; };
+// WF (weight format of the tiles, kernels.h: WFMT): PW_BF16; PW_FP8 (above); PW_MX4: OCP MXFP4 -- e2m1 elements, one e8m0 scale per 32 k of a row.  One 1 KiB tile =
 // 16 rows x 128 k: lane l holds row l & 15, dword j of its 16 bytes = the 8 k of group l >> 4 of the tile's j-th 32-wide MFMA step (element e in
 // nibble e), so ONE load feeds four MFMAs; the scales are a second stream in the same tile order, one dword of four e8m0 codes per (tile, row)
 // = 64 B per tile, fetched by the sixteen rows' lanes as one request.  v_cvt_scalef32_pk_bf16_fp4 widens two elements and applies the block
 // scale (the code shifted into an fp32 exponent); a de-quantised value is exact in bf16, so MFMA, prologues and epilogues are the bf16 form's.
 // Four tiles (16 KiB + scales) per wave in flight.
-// W_MX6: OCP MXFP6 e2m3, the same blocks and scale stream.  One tile = 16 rows x 128 k = 1536 B: lane l (row l & 15, g = l >> 4) owns the 32 elements of
+// PW_MX6: OCP MXFP6 e2m3, the same blocks and scale stream.  One tile = 16 rows x 128 k = 1536 B: lane l (row l & 15, g = l >> 4) owns the 32 elements of
 // scale block g of its row -- six dwords, 16 bytes at 16 l of the tile's first KiB and 8 bytes at 8 l of the 512 B behind it, both requests contiguous
 // across the wave -- because v_cvt_scalef32_pk32_bf16_fp6 takes ONE scale for its 32 elements.  One conversion gives the lane the A fragments of the
 // step's four MFMAs: MFMA j takes elements 8 j .. 8 j + 7 = k0 + 32 g + 8 j + (0 .. 7), where the MX4 form has k0 + 32 j + 8 g -- so the activation
@@ -267,13 +268,13 @@ template <int QD, int QS> struct Mx6Tiles<true, QD, QS> { u32x4_t w[QD][QS]; u32
 // Three tiles (18 KiB + scales) per wave in flight: six dwords a step and the conversion's sixteen result registers leave room for no fourth set.
 template <int MODE, bool NORM, bool XATTN, int WF, bool R32, int NB, bool ROLL, bool EX = false>
 __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p) {
-    constexpr bool FP8 = WF == W_FP8, MX4 = WF == W_MX4, MX6 = WF == W_MX6;
-    static_assert(!EX || (NB == 16 && WF == W_BF16 && !ROLL), "exact numerics: sixteen window rows = eight batch rows x two terms, bf16 weights");
+    constexpr bool FP8 = WF == PW_FP8, MX4 = WF == PW_MX4, MX6 = WF == PW_MX6, MX = wfmt_is_mx(WF);
+    static_assert(!EX || (NB == 16 && WF == PW_BF16 && !ROLL), "exact numerics: sixteen window rows = eight batch rows x two terms, bf16 weights");
     extern __shared__ __attribute__((aligned(16))) unsigned char km_smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g4 = lane >> 4, c16 = lane & 15;
     const int B = p.batch, K = p.K;
-    constexpr int KS = (MX4 || MX6) ? 128 : FP8 ? 64 : 32;   // elements per load step
+    constexpr int KS = WFMT[WF].ks;               // elements per load step
     constexpr int NSTEP = KM_STEPS * 32 / KS;     // load steps per tile and wave
     const int KT = K / KS;                        // load steps of a whole row
     const int KTW = KT / KM_WAVES;                // ... of this wave's slice (launcher: K % (8 * KS) == 0, KTW <= NSTEP)
@@ -302,59 +303,41 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
     if (e_on) tile4_prefetch<MODE, R32>(p, e_c, e_tile, e_rq, pre_a, pre_b, pre_pos, pre_pg);
 
     // ---- weight stream: buffer loads, the (tile, step) offset in an SGPR, the lane's 16 bytes in the VGPR offset ----
-    const unsigned w_bytes = MX6 ? (unsigned)((size_t)p.n_groups * 12 * (size_t)K)
-                           : MX4 ? (unsigned)((size_t)p.n_groups * 8 * (size_t)K) : (unsigned)((size_t)p.n_groups * 16 * (size_t)K * (FP8 ? 1 : 2));
+    // (16 rows x K x 1 or 2 bytes keeps the parent's spelling: as one factor wfmt_bytes_per_k, or behind a helper, every bf16 kernel's scalar multiplies change operand order)
+    const unsigned w_bytes = wfmt_is_mx(WF) ? (unsigned)((size_t)p.n_groups * wfmt_bytes_per_k(WF) * (size_t)K) : (unsigned)((size_t)p.n_groups * 16 * (size_t)K * (FP8 ? 1 : 2));
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (int)w_bytes, 0x00020000);
     const unsigned voff = (unsigned)lane * 16u;
     u32x4_t wa[NSTEP], wb[NSTEP];   // two tiles in flight
-    // MX4: four register sets of a tile's four load steps, and each step's scale dword (the rows' lanes: 4 bytes at 4 (lane & 15) of the tile's 64).
-    // (An empty struct in the bf16 / fp8 forms: everything that touches it sits under `if constexpr (MX4)`.)
-    constexpr int QD = 4, QS = NSTEP;
-    Mx4Tiles<MX4, QD, QS> q4;
     auto issue_one = [&](u32x4_t (&w)[NSTEP], int tl, int s) {   // step s of tile tl of the block (uniform); past the end: out of range = zeros, no traffic
         const int ok = (tl < ntb && s < KTW) ? -1 : 0;
-        const unsigned so = ((unsigned)(((t_lo + tl) * KT + wave * KTW + s) * 1024) & (unsigned)ok) | (w_bytes & (unsigned)~ok);
+        const unsigned so = ((unsigned)(((t_lo + tl) * KT + wave * KTW + s) * WFMT[WF].tile_bytes) & (unsigned)ok) | (w_bytes & (unsigned)~ok);
         w[s] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, voff, so, 2));   // aux 2 = nt
     };
     auto issue = [&](u32x4_t (&w)[NSTEP], int tl) {
 #pragma unroll
         for (int s = 0; s < NSTEP; ++s) issue_one(w, tl, s);
     };
-    auto issue4_one = [&](int d, int tl, int s) {   // MX4: step s of tile tl of the block into set d (uniform); past the end: zeros, no traffic
-        if constexpr (MX4) {
-            const unsigned s_bytes = w_bytes / 16u;
-            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w4_scales, 0, (int)s_bytes, 0x00020000);
+    // block-scaled tiles: QD register sets of a tile's four load steps (MX4: four; MX6: three -- six dwords a step and the conversion's sixteen result registers
+    // leave room for no fourth), and each step's scale dword (the rows' lanes: 4 bytes at 4 (lane & 15) of the tile's 64)
+    constexpr int QD = MX6 ? 3 : 4, QS = NSTEP;
+    MxTiles<WF, QD, QS> q;
+    auto issue_mx_one = [&](int d, int tl, int s) {   // step s of tile tl of the block into set d (uniform); past the block's tiles or the wave's slice every offset
+        if constexpr (MX) {                            // is masked past its descriptor: zeros, no traffic, scale code 0
+            const unsigned s_bytes = w_bytes / (unsigned)(WFMT[WF].tile_bytes / WFMT_SCALE_BYTES);
+            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_codes, 0, (int)s_bytes, 0x00020000);
             const int ok = (tl < ntb && s < KTW) ? -1 : 0;
             const unsigned ti = (unsigned)((t_lo + tl) * KT + wave * KTW + s);
-            q4.w[d][s] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, voff, ((ti * 1024u) & (unsigned)ok) | (w_bytes & (unsigned)~ok), 2));
-            q4.s[d][s] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(srsrc, (unsigned)c16 * 4u, ((ti * 64u) & (unsigned)ok) | (s_bytes & (unsigned)~ok), 2);
+            const unsigned so = ((ti * (unsigned)WFMT[WF].tile_bytes) & (unsigned)ok) | (w_bytes & (unsigned)~ok);
+            q.w[d][s] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, voff, so, 2));
+            if constexpr (MX6) q.h[d][s] = __builtin_bit_cast(u32x2_t, __builtin_amdgcn_raw_buffer_load_b64(wrsrc, 1024u + (unsigned)lane * 8u, so, 2));
+            q.s[d][s] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(srsrc, (unsigned)c16 * 4u, ((ti * (unsigned)WFMT_SCALE_BYTES) & (unsigned)ok) | (s_bytes & (unsigned)~ok), 2);
         }
     };
-    auto issue4 = [&](int d, int tl) {
+    auto issue_mx = [&](int d, int tl) {
 #pragma unroll
-        for (int s = 0; s < QS; ++s) issue4_one(d, tl, s);
+        for (int s = 0; s < QS; ++s) issue_mx_one(d, tl, s);
     };
-    // MX6: three register sets of a tile's four load steps (empty elsewhere: everything that touches it sits under `if constexpr (MX6)`).  A step past
-    // the block's tiles or the wave's slice masks all three offsets past their descriptors: zeros, no traffic, scale code 0
-    constexpr int QD6 = 3;
-    Mx6Tiles<MX6, QD6, QS> q6;
-    auto issue6_one = [&](int d, int tl, int s) {
-        if constexpr (MX6) {
-            const unsigned s_bytes = w_bytes / 24u;   // 64 B of codes per 1536 B tile
-            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w4_scales, 0, (int)s_bytes, 0x00020000);
-            const int ok = (tl < ntb && s < KTW) ? -1 : 0;
-            const unsigned ti = (unsigned)((t_lo + tl) * KT + wave * KTW + s);
-            const unsigned so = ((ti * 1536u) & (unsigned)ok) | (w_bytes & (unsigned)~ok);
-            q6.w[d][s] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, voff, so, 2));
-            q6.h[d][s] = __builtin_bit_cast(u32x2_t, __builtin_amdgcn_raw_buffer_load_b64(wrsrc, 1024u + (unsigned)lane * 8u, so, 2));
-            q6.s[d][s] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(srsrc, (unsigned)c16 * 4u, ((ti * 64u) & (unsigned)ok) | (s_bytes & (unsigned)~ok), 2);
-        }
-    };
-    auto issue6 = [&](int d, int tl) {
-#pragma unroll
-        for (int s = 0; s < QS; ++s) issue6_one(d, tl, s);
-    };
-    auto issue_first = [&]() { if constexpr (MX6) issue6(0, 0); else if constexpr (MX4) issue4(0, 0); else issue(wa, 0); };
+    auto issue_first = [&]() { if constexpr (MX) issue_mx(0, 0); else issue(wa, 0); };
     // 16-byte chunk (8 elements) of the wave's slice that fragment s holds for k-group g: 4 s + g; MX6 (fragment 4 S + j of load step S): 16 S + 4 g + j
     auto x_chunk = [&](int s, int g) { return MX6 ? (s >> 2) * 16 + g * 4 + (s & 3) : s * 4 + g; };
 
@@ -483,12 +466,9 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
             xf[s] = __builtin_bit_cast(bf16x8_t, v);
         }
     }
-    if constexpr (MX6) {
+    if constexpr (MX) {
 #pragma unroll
-        for (int d = 1; d < QD6; ++d) issue6(d, d);
-    } else if constexpr (MX4) {
-#pragma unroll
-        for (int d = 1; d < QD; ++d) issue4(d, d);
+        for (int d = 1; d < QD; ++d) issue_mx(d, d);
     } else
     issue(wb, 1);   // the second tile once the prologue's temporaries are dead (all of them next to two tiles would not fit 256 VGPRs)
 
@@ -512,45 +492,30 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
         }
         if (tl < ntb) *(f32x4_t*)(part_of(wave) + ((size_t)tl * 64 + lane) * 4) = acc;
     };
-    // MX4: set d holds tile tl; per load step four MFMAs, byte j of the step's scale dword shifted into the exponent of the conversion's scale
-    // operand; the set's step is refilled with the tile four ahead as soon as its MFMAs have issued
-    auto run_tile4 = [&](int d, int tl) {
-        if constexpr (MX4) {
-            f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < QS; ++s) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(mx4x8_to_bf16x8(q4.w[d][s][j], e8m0_scale(q4.s[d][s], j)), xf[4 * s + j], acc, 0, 0, 0);
-                issue4_one(d, tl + QD, s);
-            }
-            if (tl < ntb) *(f32x4_t*)(part_of(wave) + ((size_t)tl * 64 + lane) * 4) = acc;
-        }
-    };
-    // MX6: set d holds tile tl; per load step ONE conversion (the lane's block, byte g of the row's scale dword) and four MFMAs; the set's step is
-    // refilled with the tile three ahead as soon as its MFMAs have issued
-    auto run_tile6 = [&](int d, int tl) {
-        if constexpr (MX6) {
+    // block-scaled tiles: set d holds tile tl; per load step four MFMAs, and the set's step is refilled with the tile QD ahead as soon as they have issued.  Only
+    // the widening differs -- MX4: one conversion per MFMA, byte j of the step's scale dword shifted into the exponent of its scale operand; MX6: ONE conversion
+    // (the lane's block, byte g of the row's scale dword) for the four
+    auto run_tile_mx = [&](int d, int tl) {
+        if constexpr (MX) {
             f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int s = 0; s < QS; ++s) {
                 bf16x8_t a[4];
-                mx6x32_to_bf16x8(q6.w[d][s], q6.h[d][s], e8m0_scale(q6.s[d][s], g4), a);
+                if constexpr (MX6) mx6x32_to_bf16x8(q.w[d][s], q.h[d][s], e8m0_scale(q.s[d][s], g4), a);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[j], xf[4 * s + j], acc, 0, 0, 0);
-                issue6_one(d, tl + QD6, s);
+                for (int j = 0; j < 4; ++j) {
+                    if constexpr (MX4) a[j] = mx4x8_to_bf16x8(q.w[d][s][j], e8m0_scale(q.s[d][s], j));
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[j], xf[4 * s + j], acc, 0, 0, 0);
+                }
+                issue_mx_one(d, tl + QD, s);
             }
             if (tl < ntb) *(f32x4_t*)(part_of(wave) + ((size_t)tl * 64 + lane) * 4) = acc;
         }
     };
-    if constexpr (MX6) {
-        for (int tl = 0; tl < ntb; tl += QD6) {
-#pragma unroll
-            for (int d = 0; d < QD6; ++d) run_tile6(d, tl + d);
-        }
-    } else if constexpr (MX4) {
+    if constexpr (MX) {
         for (int tl = 0; tl < ntb; tl += QD) {
 #pragma unroll
-            for (int d = 0; d < QD; ++d) run_tile4(d, tl + d);
+            for (int d = 0; d < QD; ++d) run_tile_mx(d, tl + d);
         }
     } else {
         for (int tl = 0; tl < ntb; tl += 2) {
@@ -689,9 +654,9 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_km_kernel(GemvParams p)
 // the start (22 / 12 KiB per wave), every register refilled with the next phase's step as soon as its MFMA has issued.
 // y = h + W x in place (+ the per-row scale with fp8 weights).
 // ---------------------------------------------------------------------------------------------------------------------
-// (MX4 / MX6 tiles: a load step is four fragments, so eight rows run two phases of 24 -- 97 KiB of windows against 89)
+// (block-scaled tiles: a load step is four fragments, so eight rows run two phases of 24 -- 97 KiB of windows against 89)
 template <int NB, int WF = 0> struct KdShape {
-    static constexpr int FR = NB == 8 ? ((WF == W_MX4 || WF == W_MX6) ? 24 : 22) : 12;      // fragments (32 elements) per phase and wave
+    static constexpr int FR = NB == 8 ? (22 + wfmt_fps(WF) - 1) / wfmt_fps(WF) * wfmt_fps(WF) : 12;   // fragments (32 elements) per phase and wave: whole load steps
     static constexpr int NPH = NB == 8 ? 2 : 4;       // phases: K <= 8 waves x NPH x FR x 32 = 11264 / 12288
     static constexpr int XP = FR * 64 + 16;           // bytes per staged row slice
     static constexpr int CH = (FR * 4 + 63) / 64;     // 16-byte chunks per lane and row of a phase
@@ -700,15 +665,15 @@ template <int NB, int WF = 0> struct KdShape {
 // emmax_decode_km_kernel); the row registers hold the fp32 chunk as two quads (r[2 b], r[2 b + 1]).
 template <int WF, bool R32, int NB, bool EX = false>
 __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_kmd_kernel(GemvParams p) {
-    constexpr bool FP8 = WF == W_FP8, MX4 = WF == W_MX4, MX6 = WF == W_MX6;
-    static_assert(!EX || (NB == 16 && WF == W_BF16 && R32), "exact numerics: eight batch rows x two terms, bf16 weights, fp32 residual stream");
+    constexpr bool FP8 = WF == PW_FP8, MX4 = WF == PW_MX4, MX6 = WF == PW_MX6, MX = wfmt_is_mx(WF);
+    static_assert(!EX || (NB == 16 && WF == PW_BF16 && R32), "exact numerics: eight batch rows x two terms, bf16 weights, fp32 residual stream");
     extern __shared__ __attribute__((aligned(16))) unsigned char km_smem[];
     using S = KdShape<NB, WF>;
     constexpr int FR = S::FR, NPH = S::NPH, XP = S::XP, CH = S::CH;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g4 = lane >> 4, c16 = lane & 15;
     const int B = p.batch, K = p.K;
-    constexpr int FPS = (MX4 || MX6) ? 4 : FP8 ? 2 : 1, KS = 32 * FPS;   // fragments / elements per load step
+    constexpr int FPS = wfmt_fps(WF), KS = WFMT[WF].ks;      // fragments / elements per load step
     constexpr int NST = FR / FPS;                            // load steps per phase
     const int KT = K / KS;
     const int kq = KT / KM_WAVES, kr = KT % KM_WAVES;
@@ -786,29 +751,23 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_kmd_kernel(GemvParams p
     load_rows(1, xb);
 
     // ---- weights: phase 0 in flight now, later phases refilled register by register ----
-    const unsigned w_bytes = MX6 ? (unsigned)((size_t)p.n_groups * 12 * (size_t)K)
-                           : MX4 ? (unsigned)((size_t)p.n_groups * 8 * (size_t)K) : (unsigned)((size_t)p.n_groups * 16 * (size_t)K * (FP8 ? 1 : 2));
+    // (16 rows x K x 1 or 2 bytes keeps the parent's spelling: as one factor wfmt_bytes_per_k, or behind a helper, every bf16 kernel's scalar multiplies change operand order)
+    const unsigned w_bytes = wfmt_is_mx(WF) ? (unsigned)((size_t)p.n_groups * wfmt_bytes_per_k(WF) * (size_t)K) : (unsigned)((size_t)p.n_groups * 16 * (size_t)K * (FP8 ? 1 : 2));
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (int)w_bytes, 0x00020000);
     const unsigned voff = (unsigned)lane * 16u;
     u32x4_t w[NST];
-    // MX4: the scale dword of each load step (emmax_decode_km_kernel: 64 B per tile in the tiles' order, 4 bytes per row)
-    Mx4Tiles<MX4, 1, NST> q4;
-    // MX6: dwords 4-5 of the lane's six (w[s] holds 0-3) and the scale dword of each load step
-    Mx6Tiles<MX6, 1, NST> q6;
+    // block-scaled tiles: the scale dword of each load step (emmax_decode_km_kernel: 64 B per tile in the tiles' order, 4 bytes per row) and, MX6, dwords 4-5 of
+    // the lane's six; w[s] holds the lane's 16 bytes in every form (the struct's own w stays unused here)
+    MxTiles<WF, 1, NST> q;
     auto issue_w = [&](int ph, int s) {   // load step s of phase ph (past the wave's slice: out of range = zeros, no traffic)
         const int ok = (ph * NST + s < k_n) ? -1 : 0;
-        const unsigned so = ((unsigned)((tile * KT + k_lo + ph * NST + s) * (MX6 ? 1536 : 1024)) & (unsigned)ok) | (w_bytes & (unsigned)~ok);
+        const unsigned so = ((unsigned)((tile * KT + k_lo + ph * NST + s) * WFMT[WF].tile_bytes) & (unsigned)ok) | (w_bytes & (unsigned)~ok);
         w[s] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, voff, so, 2));
-        if constexpr (MX6) {
-            const unsigned s_bytes = w_bytes / 24u;
-            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w4_scales, 0, (int)s_bytes, 0x00020000);
-            q6.h[0][s] = __builtin_bit_cast(u32x2_t, __builtin_amdgcn_raw_buffer_load_b64(wrsrc, 1024u + (unsigned)lane * 8u, so, 2));
-            q6.s[0][s] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(srsrc, (unsigned)c16 * 4u, ((unsigned)((tile * KT + k_lo + ph * NST + s) * 64) & (unsigned)ok) | (s_bytes & (unsigned)~ok), 2);
-        }
-        if constexpr (MX4) {
-            const unsigned s_bytes = w_bytes / 16u;
-            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w4_scales, 0, (int)s_bytes, 0x00020000);
-            q4.s[0][s] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(srsrc, (unsigned)c16 * 4u, ((unsigned)((tile * KT + k_lo + ph * NST + s) * 64) & (unsigned)ok) | (s_bytes & (unsigned)~ok), 2);
+        if constexpr (MX) {
+            const unsigned s_bytes = w_bytes / (unsigned)(WFMT[WF].tile_bytes / WFMT_SCALE_BYTES);
+            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_codes, 0, (int)s_bytes, 0x00020000);
+            if constexpr (MX6) q.h[0][s] = __builtin_bit_cast(u32x2_t, __builtin_amdgcn_raw_buffer_load_b64(wrsrc, 1024u + (unsigned)lane * 8u, so, 2));
+            q.s[0][s] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(srsrc, (unsigned)c16 * 4u, ((unsigned)((tile * KT + k_lo + ph * NST + s) * WFMT_SCALE_BYTES) & (unsigned)ok) | (s_bytes & (unsigned)~ok), 2);
         }
     };
 #pragma unroll
@@ -824,14 +783,14 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_kmd_kernel(GemvParams p
         return __builtin_bit_cast(bf16x8_t, (EX ? (c16 & 7) < B : c16 < B) ? v : (u32x4_t){0u, 0u, 0u, 0u});
     };
     auto mfma_step = [&](int s) {
-        if constexpr (MX6) {
+        if constexpr (MX) {   // (the widening as in emmax_decode_km_kernel's run_tile_mx)
             bf16x8_t a[4];
-            mx6x32_to_bf16x8(w[s], q6.h[0][s], e8m0_scale(q6.s[0][s], g4), a);
+            if constexpr (MX6) mx6x32_to_bf16x8(w[s], q.h[0][s], e8m0_scale(q.s[0][s], g4), a);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[j], frag(4 * s + j), acc, 0, 0, 0);
-        } else if constexpr (MX4) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(mx4x8_to_bf16x8(w[s][j], e8m0_scale(q4.s[0][s], j)), frag(4 * s + j), acc, 0, 0, 0);
+            for (int j = 0; j < 4; ++j) {
+                if constexpr (MX4) a[j] = mx4x8_to_bf16x8(w[s][j], e8m0_scale(q.s[0][s], j));
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[j], frag(4 * s + j), acc, 0, 0, 0);
+            }
         } else if constexpr (FP8) {
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fp8x8_to_bf16x8(w[s][0], w[s][1]), frag(2 * s), acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fp8x8_to_bf16x8(w[s][2], w[s][3]), frag(2 * s + 1), acc, 0, 0, 0);
@@ -885,7 +844,7 @@ __global__ __launch_bounds__(KM_NT, 2) void emmax_decode_kmd_kernel(GemvParams p
 template <int WF, int NB, bool EX = false>
 int kmd_launch(const GemvParams& p, const ProjGeom& g, hipStream_t stream) {
     if constexpr (EX) {
-        hipLaunchKernelGGL((emmax_decode_kmd_kernel<W_BF16, true, 16, true>), dim3(g.grid), dim3(KM_NT), g.smem, stream, p);
+        hipLaunchKernelGGL((emmax_decode_kmd_kernel<PW_BF16, true, 16, true>), dim3(g.grid), dim3(KM_NT), g.smem, stream, p);
     } else {
         if (p.h32) hipLaunchKernelGGL((emmax_decode_kmd_kernel<WF, true, NB>), dim3(g.grid), dim3(KM_NT), g.smem, stream, p);
         else hipLaunchKernelGGL((emmax_decode_kmd_kernel<WF, false, NB>), dim3(g.grid), dim3(KM_NT), g.smem, stream, p);
@@ -896,7 +855,7 @@ int kmd_launch(const GemvParams& p, const ProjGeom& g, hipStream_t stream) {
 template <int MODE, bool NORM, bool XATTN, int WF, int NB, bool ROLL, bool EX = false>
 int km_launch_nb(const GemvParams& p, const ProjGeom& g, hipStream_t stream) {
     if constexpr (EX) {   // exact numerics: fp32 rows in (h32 / p.x / the split partials), two terms per batch row, batch <= 8
-        hipLaunchKernelGGL((emmax_decode_km_kernel<MODE, NORM, XATTN, W_BF16, MODE == GEMV_RESID, 16, false, true>), dim3(g.grid), dim3(KM_NT), g.smem, stream, p);
+        hipLaunchKernelGGL((emmax_decode_km_kernel<MODE, NORM, XATTN, PW_BF16, MODE == GEMV_RESID, 16, false, true>), dim3(g.grid), dim3(KM_NT), g.smem, stream, p);
         return hipGetLastError() == hipSuccess ? 0 : -4;
     }
     if constexpr (MODE == GEMV_RESID) {   // (NORM modes read the bf16 mirror: h32 is ignored there)
@@ -910,10 +869,10 @@ int km_launch_nb(const GemvParams& p, const ProjGeom& g, hipStream_t stream) {
 }
 template <int MODE, bool NORM, bool XATTN, int WF>
 int km_launch_t(const GemvParams& p, const ProjGeom& g, hipStream_t stream) {
-    if constexpr ((WF == W_MX4 || WF == W_MX6) && XATTN) {   // split partials of 9-16 rows x K do not fit the LDS stage: those batches exist in the one-split form only
+    if constexpr (wfmt_is_mx(WF) && XATTN) {   // split partials of 9-16 rows x K do not fit the LDS stage: those batches exist in the one-split form only
         return km_launch_nb<MODE, NORM, XATTN, WF, 8, false>(p, g, stream);
     } else {
-        if constexpr (WF != W_MX4 && WF != W_MX6) {   // (the MX4 / MX6 forms always refill step by step: one instantiation per batch width)
+        if constexpr (!wfmt_is_mx(WF)) {   // (the MX4 / MX6 forms always refill step by step: one instantiation per batch width)
             if (g.roll)
                 return g.nb == 8 ? km_launch_nb<MODE, NORM, XATTN, WF, 8, true>(p, g, stream) : km_launch_nb<MODE, NORM, XATTN, WF, 16, true>(p, g, stream);
         }
@@ -924,12 +883,12 @@ int km_launch_t(const GemvParams& p, const ProjGeom& g, hipStream_t stream) {
 // exact numerics (GemvParams::exact), batch 3-8: the EX forms
 int km_launch_mode_x(int mode, const GemvParams& p, const ProjGeom& g, hipStream_t stream) {
     switch (mode) {
-        case GEMV_QKV: return km_launch_nb<GEMV_QKV, true, false, W_BF16, 16, false, true>(p, g, stream);
+        case GEMV_QKV: return km_launch_nb<GEMV_QKV, true, false, PW_BF16, 16, false, true>(p, g, stream);
         case GEMV_RESID:
-            return p.attn_part ? km_launch_nb<GEMV_RESID, false, true, W_BF16, 16, false, true>(p, g, stream)
-                               : km_launch_nb<GEMV_RESID, false, false, W_BF16, 16, false, true>(p, g, stream);
-        case GEMV_GATEUP: return km_launch_nb<GEMV_GATEUP, true, false, W_BF16, 16, false, true>(p, g, stream);
-        case GEMV_LMHEAD: return km_launch_nb<GEMV_LMHEAD, true, false, W_BF16, 16, false, true>(p, g, stream);
+            return p.attn_part ? km_launch_nb<GEMV_RESID, false, true, PW_BF16, 16, false, true>(p, g, stream)
+                               : km_launch_nb<GEMV_RESID, false, false, PW_BF16, 16, false, true>(p, g, stream);
+        case GEMV_GATEUP: return km_launch_nb<GEMV_GATEUP, true, false, PW_BF16, 16, false, true>(p, g, stream);
+        case GEMV_LMHEAD: return km_launch_nb<GEMV_LMHEAD, true, false, PW_BF16, 16, false, true>(p, g, stream);
         default: return -2;
     }
 }
@@ -939,7 +898,7 @@ int km_launch_mode(int mode, const GemvParams& p, const ProjGeom& g, hipStream_t
     switch (mode) {
         case GEMV_QKV: return km_launch_t<GEMV_QKV, true, false, WF>(p, g, stream);
         case GEMV_RESID:
-            if constexpr (WF == W_BF16) {   // (the bf16 o-proj with the split merge stays on decode_mfma.hip: decode_km_takes)
+            if constexpr (WF == PW_BF16) {   // (the bf16 o-proj with the split merge stays on decode_mfma.hip: decode_km_takes)
                 return km_launch_t<GEMV_RESID, false, false, WF>(p, g, stream);
             } else {
                 return p.attn_part ? km_launch_t<GEMV_RESID, false, true, WF>(p, g, stream) : km_launch_t<GEMV_RESID, false, false, WF>(p, g, stream);
@@ -954,15 +913,26 @@ int km_launch_mode(int mode, const GemvParams& p, const ProjGeom& g, hipStream_t
 // the phased down kernel's shape constants by (staged rows, weight format)
 struct KdDims { int fr, nph, xp; };
 template <int NB, int WF> constexpr KdDims kd_dims() { return {KdShape<NB, WF>::FR, KdShape<NB, WF>::NPH, KdShape<NB, WF>::XP}; }
-KdDims kd_dims_of(int nb, int wf) {
-    if (nb == 8) return wf == W_MX6 ? kd_dims<8, W_MX6>() : wf == W_MX4 ? kd_dims<8, W_MX4>() : wf == W_FP8 ? kd_dims<8, W_FP8>() : kd_dims<8, W_BF16>();
-    return wf == W_MX6 ? kd_dims<16, W_MX6>() : wf == W_MX4 ? kd_dims<16, W_MX4>() : wf == W_FP8 ? kd_dims<16, W_FP8>() : kd_dims<16, W_BF16>();
+// the one step from a runtime weight format to the kernels' template argument: f(std::integral_constant<int, PW_*>)
+template <class F> int with_wfmt(int wfmt, F&& f) {
+    switch (wfmt) {
+        case PW_BF16: return f(std::integral_constant<int, PW_BF16>{});
+        case PW_FP8: return f(std::integral_constant<int, PW_FP8>{});
+        case PW_MX4: return f(std::integral_constant<int, PW_MX4>{});
+        case PW_MX6: return f(std::integral_constant<int, PW_MX6>{});
+        default: return -2;
+    }
+}
+KdDims kd_dims_of(int nb, int wfmt) {
+    KdDims d = {};
+    with_wfmt(wfmt, [&](auto wf) { d = nb == 8 ? kd_dims<8, decltype(wf)::value>() : kd_dims<16, decltype(wf)::value>(); return 0; });
+    return d;
 }
 
 // the phased down form (y = h + W x, one 16-row tile per block): K in whole load steps, at least one per wave, a wave's share within
 // NPH phases of FR fragments
 bool kmd_takes(const ProjShape& s, int B, int nb, ProjGeom* g) {
-    const int fps = (s.wfmt == PW_MX4 || s.wfmt == PW_MX6) ? 4 : s.wfmt == PW_FP8 ? 2 : 1, ks = 32 * fps;
+    const int fps = wfmt_fps(s.wfmt), ks = WFMT[s.wfmt].ks;
     const KdDims d = kd_dims_of(nb, s.wfmt);
     if (s.K % ks || s.n_rows % 16 || s.attn_part) return false;
     if (cdiv(s.K / ks, KM_WAVES) > d.nph * (d.fr / fps) || s.K / ks < KM_WAVES) return false;
@@ -977,7 +947,7 @@ bool kmd_takes(const ProjShape& s, int B, int nb, ProjGeom* g) {
 // per CU with at most KM_MAX_TILES tiles each, one LDS region per wave (the window [NB][XPITCH] overlaid by the partial tiles) + sumsq
 // (+ with split partials in: the merged rows)
 bool kms_takes(const ProjShape& s, int B, int nb, ProjGeom* g) {
-    const int ks = (s.wfmt == PW_MX4 || s.wfmt == PW_MX6) ? 128 : s.wfmt == PW_FP8 ? 64 : 32;
+    const int ks = WFMT[s.wfmt].ks;
     if (s.K % (KM_WAVES * ks) || s.K > KM_WAVES * KM_STEPS * 32 || s.n_rows % 16) return false;
     if (s.mode == GEMV_QKV && (s.head_dim % 16 || s.head_dim < 16)) return false;
     g->nb = nb;
@@ -1014,14 +984,13 @@ bool decode_km_takes(const ProjShape& s, int B, ProjGeom* out) {
         ok = (s.mode == GEMV_RESID && !s.attn_part && !kfits) ? kmd_takes(s, B, 16, &g) : kms_takes(s, B, 16, &g);
     } else if (s.mode == GEMV_RESID && !s.attn_part && s.K > KM_WAVES * KM_STEPS * 32) {   // the down projection: the phased form (natural row order copy)
         // tuning switch km_down = 0: decode_mfma.hip, the A/B partner (no other kernel reads MXFP4 tiles: no switch there)
-        ok = (s.wfmt == PW_MX4 || s.wfmt == PW_MX6 || emmax_tune().km_down) && kmd_takes(s, B, B <= 8 ? 8 : 16, &g);
+        ok = (wfmt_is_mx(s.wfmt) || emmax_tune().km_down) && kmd_takes(s, B, B <= 8 ? 8 : 16, &g);
     } else {
         // the bf16 o-proj with the split merge stays on decode_mfma.hip (12.5 against 15.4 us at B = 8: the merge of 8 rows
         // queues behind this kernel's 16 KiB weight heads); with fp8 weights this kernel is the faster one (10.3 against 10.8).
-        // MXFP4: split partials of 9-16 rows x K do not fit the LDS stage, those batches exist in the one-split form only
         // MXFP4 / MXFP6: split partials of 9-16 rows x K do not fit the LDS stage, those batches exist in the one-split form only
-        if (s.attn_part && (s.wfmt == PW_BF16 || ((s.wfmt == PW_MX4 || s.wfmt == PW_MX6) && B > 8))) return false;
-        g.roll = s.wfmt != PW_MX4 && s.wfmt != PW_MX6 && emmax_tune().km_roll;   // (the MX4 / MX6 forms always refill step by step)
+        if (s.attn_part && (s.wfmt == PW_BF16 || (wfmt_is_mx(s.wfmt) && B > 8))) return false;
+        g.roll = !wfmt_is_mx(s.wfmt) && emmax_tune().km_roll;   // (the MX4 / MX6 forms always refill step by step)
         ok = kms_takes(s, B, B <= 8 ? 8 : 16, &g);
     }
     if (ok && out) *out = g;
@@ -1039,20 +1008,17 @@ int decode_km_init() {
 #define KM_SET3(M, N_, X, F, R, NB_) KM_SET4(M, N_, X, F, R, NB_, false); KM_SET4(M, N_, X, F, R, NB_, true)
 #define KM_SET2(M, N_, X, F, R) KM_SET3(M, N_, X, F, R, 8); KM_SET3(M, N_, X, F, R, 16)
 #define KM_SET1(M, N_, X, F) KM_SET2(M, N_, X, F, false); if (M == GEMV_RESID) KM_SET2(M, N_, X, F, true)
-#define KM_SET(M, N_, X) KM_SET1(M, N_, X, W_BF16); KM_SET1(M, N_, X, W_FP8)
-    KM_SET(GEMV_QKV, true, false); KM_SET1(GEMV_RESID, false, true, W_FP8); KM_SET(GEMV_RESID, false, false); KM_SET(GEMV_GATEUP, true, false);
+#define KM_SET(M, N_, X) KM_SET1(M, N_, X, PW_BF16); KM_SET1(M, N_, X, PW_FP8)
+    KM_SET(GEMV_QKV, true, false); KM_SET1(GEMV_RESID, false, true, PW_FP8); KM_SET(GEMV_RESID, false, false); KM_SET(GEMV_GATEUP, true, false);
     KM_SET(GEMV_LMHEAD, true, false); KM_SET(GEMV_PLAIN, false, false);
-    // the MX4 forms (no rolling variant)
-#define KM_SETQ(M, N_, X, R) KM_SET4(M, N_, X, W_MX4, R, 8, false); KM_SET4(M, N_, X, W_MX4, R, 16, false)
-    KM_SETQ(GEMV_QKV, true, false, false); KM_SETQ(GEMV_GATEUP, true, false, false); KM_SETQ(GEMV_LMHEAD, true, false, false); KM_SETQ(GEMV_PLAIN, false, false, false);
-    KM_SETQ(GEMV_RESID, false, false, false); KM_SETQ(GEMV_RESID, false, false, true);
-    KM_SET4(GEMV_RESID, false, true, W_MX4, false, 8, false); KM_SET4(GEMV_RESID, false, true, W_MX4, true, 8, false);   // (the split merge: 1-8 rows)
-    // the MX6 forms (the same set)
-#define KM_SET6(M, N_, X, R) KM_SET4(M, N_, X, W_MX6, R, 8, false); KM_SET4(M, N_, X, W_MX6, R, 16, false)
-    KM_SET6(GEMV_QKV, true, false, false); KM_SET6(GEMV_GATEUP, true, false, false); KM_SET6(GEMV_LMHEAD, true, false, false); KM_SET6(GEMV_PLAIN, false, false, false);
-    KM_SET6(GEMV_RESID, false, false, false); KM_SET6(GEMV_RESID, false, false, true);
-    KM_SET4(GEMV_RESID, false, true, W_MX6, false, 8, false); KM_SET4(GEMV_RESID, false, true, W_MX6, true, 8, false);
-#undef KM_SET6
+    // the forms of a block-scaled format (no rolling variant; the split merge: 1-8 rows)
+#define KM_SETQ(F, M, N_, X, R) KM_SET4(M, N_, X, F, R, 8, false); KM_SET4(M, N_, X, F, R, 16, false)
+#define KM_SETMX(F) \
+    KM_SETQ(F, GEMV_QKV, true, false, false); KM_SETQ(F, GEMV_GATEUP, true, false, false); KM_SETQ(F, GEMV_LMHEAD, true, false, false); KM_SETQ(F, GEMV_PLAIN, false, false, false); \
+    KM_SETQ(F, GEMV_RESID, false, false, false); KM_SETQ(F, GEMV_RESID, false, false, true);                                                                                     \
+    KM_SET4(GEMV_RESID, false, true, F, false, 8, false); KM_SET4(GEMV_RESID, false, true, F, true, 8, false)
+    KM_SETMX(PW_MX4); KM_SETMX(PW_MX6);
+#undef KM_SETMX
 #undef KM_SETQ
 #undef KM_SET
 #undef KM_SET1
@@ -1061,16 +1027,18 @@ int decode_km_init() {
 #undef KM_SET4
 #define KD_SET(F, R, NB_) \
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)emmax_decode_kmd_kernel<F, R, NB_>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)
-    KD_SET(W_BF16, false, 8); KD_SET(W_FP8, false, 8); KD_SET(W_BF16, true, 8); KD_SET(W_FP8, true, 8);
-    KD_SET(W_BF16, false, 16); KD_SET(W_FP8, false, 16); KD_SET(W_BF16, true, 16); KD_SET(W_FP8, true, 16);
-    KD_SET(W_MX4, false, 8); KD_SET(W_MX4, true, 8); KD_SET(W_MX4, false, 16); KD_SET(W_MX4, true, 16);
-    KD_SET(W_MX6, false, 8); KD_SET(W_MX6, true, 8); KD_SET(W_MX6, false, 16); KD_SET(W_MX6, true, 16);
+    // (bf16 and fp8 stay interleaved: the kernels are emitted in the order of these lines and the assembly's block labels carry their number)
+    KD_SET(PW_BF16, false, 8); KD_SET(PW_FP8, false, 8); KD_SET(PW_BF16, true, 8); KD_SET(PW_FP8, true, 8);
+    KD_SET(PW_BF16, false, 16); KD_SET(PW_FP8, false, 16); KD_SET(PW_BF16, true, 16); KD_SET(PW_FP8, true, 16);
+#define KD_SETF(F) KD_SET(F, false, 8); KD_SET(F, true, 8); KD_SET(F, false, 16); KD_SET(F, true, 16)
+    KD_SETF(PW_MX4); KD_SETF(PW_MX6);
+#undef KD_SETF
 #undef KD_SET
 #define KX_SET(M, N_, X) \
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)emmax_decode_km_kernel<M, N_, X, W_BF16, M == GEMV_RESID, 16, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)emmax_decode_km_kernel<M, N_, X, PW_BF16, M == GEMV_RESID, 16, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim)
     KX_SET(GEMV_QKV, true, false); KX_SET(GEMV_RESID, false, true); KX_SET(GEMV_RESID, false, false); KX_SET(GEMV_GATEUP, true, false); KX_SET(GEMV_LMHEAD, true, false);
 #undef KX_SET
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)emmax_decode_kmd_kernel<W_BF16, true, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)emmax_decode_kmd_kernel<PW_BF16, true, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
     done = (e == hipSuccess) ? 0 : -4;
     return done;
 }
@@ -1087,31 +1055,24 @@ int launch_repack_km(const void* src, int ld, void* dst, int N, int K, int perm,
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
-static bool mx4_shape_ok(int ld, int N, int K, int perm, int head_dim) {
-    if (N < 16 || N % 16 || K < 128 || K % 128 || ld % 8 || ld < K) return false;
+// (every block-scaled tile covers 16 rows x 128 k: one set of shape rules)
+static bool mx_shape_ok(int wfmt, int ld, int N, int K, int perm, int head_dim) {
+    if (wfmt < 0 || wfmt >= PW_COUNT || !wfmt_is_mx(wfmt)) return false;
+    if (N < 16 || N % 16 || K < WFMT[wfmt].ks || K % WFMT[wfmt].ks || ld % 8 || ld < K) return false;
     if (perm == 1 && (head_dim < 16 || head_dim % 16 || N % head_dim)) return false;
     if (perm == 2 && N % 32) return false;
     return perm >= 0 && perm <= 2;
 }
-int launch_quant_mx4(const void* src, int ld, void* tiles, void* scales, int N, int K, int perm, int head_dim, hipStream_t stream) {
-    if (!mx4_shape_ok(ld, N, K, perm, head_dim)) return -1;
-    hipLaunchKernelGGL(emmax_quant_mx4_kernel, dim3(2048), dim3(256), 0, stream, (const bf16_t*)src, ld, (uint32_t*)tiles, (uint32_t*)scales, N, K, perm, head_dim);
+int launch_quant_mx(int wfmt, const void* src, int ld, void* tiles, void* codes, int N, int K, int perm, int head_dim, hipStream_t stream) {
+    if (!mx_shape_ok(wfmt, ld, N, K, perm, head_dim)) return -1;
+    hipLaunchKernelGGL(wfmt == PW_MX6 ? emmax_quant_mx6_kernel : emmax_quant_mx4_kernel, dim3(2048), dim3(256), 0, stream, (const bf16_t*)src, ld, (uint32_t*)tiles,
+                       (uint32_t*)codes, N, K, perm, head_dim);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
-int launch_dequant_mx4(const void* tiles, const void* scales, void* dst, int ld, int N, int K, int perm, int head_dim, hipStream_t stream) {
-    if (!mx4_shape_ok(ld, N, K, perm, head_dim)) return -1;
-    hipLaunchKernelGGL(emmax_dequant_mx4_kernel, dim3(2048), dim3(256), 0, stream, (const uint32_t*)tiles, (const uint32_t*)scales, (bf16_t*)dst, ld, N, K, perm, head_dim);
-    return hipGetLastError() == hipSuccess ? 0 : -4;
-}
-// (the MXFP6 tiles cover the same 16 rows x 128 k: the shape rules are the MXFP4 pair's)
-int launch_quant_mx6(const void* src, int ld, void* tiles, void* scales, int N, int K, int perm, int head_dim, hipStream_t stream) {
-    if (!mx4_shape_ok(ld, N, K, perm, head_dim)) return -1;
-    hipLaunchKernelGGL(emmax_quant_mx6_kernel, dim3(2048), dim3(256), 0, stream, (const bf16_t*)src, ld, (uint32_t*)tiles, (uint32_t*)scales, N, K, perm, head_dim);
-    return hipGetLastError() == hipSuccess ? 0 : -4;
-}
-int launch_dequant_mx6(const void* tiles, const void* scales, void* dst, int ld, int N, int K, int perm, int head_dim, hipStream_t stream) {
-    if (!mx4_shape_ok(ld, N, K, perm, head_dim)) return -1;
-    hipLaunchKernelGGL(emmax_dequant_mx6_kernel, dim3(2048), dim3(256), 0, stream, (const uint32_t*)tiles, (const uint32_t*)scales, (bf16_t*)dst, ld, N, K, perm, head_dim);
+int launch_dequant_mx(int wfmt, const void* tiles, const void* codes, void* dst, int ld, int N, int K, int perm, int head_dim, hipStream_t stream) {
+    if (!mx_shape_ok(wfmt, ld, N, K, perm, head_dim)) return -1;
+    hipLaunchKernelGGL(wfmt == PW_MX6 ? emmax_dequant_mx6_kernel : emmax_dequant_mx4_kernel, dim3(2048), dim3(256), 0, stream, (const uint32_t*)tiles,
+                       (const uint32_t*)codes, (bf16_t*)dst, ld, N, K, perm, head_dim);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
@@ -1126,14 +1087,10 @@ int launch_decode_km(int mode, const GemvParams& p_in, int B, hipStream_t stream
     GemvParams p = p_in;
     p.batch = B; p.n_groups = g.n_groups; p.kc = g.kc;
     if (grid_out) *grid_out = g.grid;
-    if (p.exact) return g.phased ? kmd_launch<W_BF16, 16, true>(p, g, stream) : km_launch_mode_x(mode, p, g, stream);
-    if (g.phased) {
-        if (p.w4_scales && p.w_mx6) return g.nb == 8 ? kmd_launch<W_MX6, 8>(p, g, stream) : kmd_launch<W_MX6, 16>(p, g, stream);
-        if (p.w4_scales) return g.nb == 8 ? kmd_launch<W_MX4, 8>(p, g, stream) : kmd_launch<W_MX4, 16>(p, g, stream);
-        if (g.nb == 8) return p.wscale ? kmd_launch<W_FP8, 8>(p, g, stream) : kmd_launch<W_BF16, 8>(p, g, stream);
-        return p.wscale ? kmd_launch<W_FP8, 16>(p, g, stream) : kmd_launch<W_BF16, 16>(p, g, stream);
-    }
-    if (p.w4_scales && p.w_mx6) return km_launch_mode<W_MX6>(mode, p, g, stream);
-    if (p.w4_scales) return km_launch_mode<W_MX4>(mode, p, g, stream);
-    return p.wscale ? km_launch_mode<W_FP8>(mode, p, g, stream) : km_launch_mode<W_BF16>(mode, p, g, stream);
+    if (p.exact) return g.phased ? kmd_launch<PW_BF16, 16, true>(p, g, stream) : km_launch_mode_x(mode, p, g, stream);
+    return with_wfmt(p.wfmt, [&](auto wf) {
+        constexpr int WF = decltype(wf)::value;
+        if (g.phased) return g.nb == 8 ? kmd_launch<WF, 8>(p, g, stream) : kmd_launch<WF, 16>(p, g, stream);
+        return km_launch_mode<WF>(mode, p, g, stream);
+    });
 }

@@ -43,15 +43,13 @@ constexpr int KP_RPL = KP_ROWS * KP_PH * 4 / 64;   // 16-byte chunks per lane an
 #define KP_HALF_SYNC 1
 #endif
 
-enum { W_BF16 = 0, W_FP8 = 1, W_MX4 = 2 };   // weight format of a tile stream (decode_km.hip's)
-
 // phases of weights in flight (fp8 tiles carry 64 k per KiB: twice the phases for the same bytes).  MXFP4 tiles carry 128 k: a phase is ONE KiB per
 // tile, and every ring register has a scale dword beside it -- 18 KiB per wave (six tiles x 3 phases, three x 6) where the bf16 form holds 24: with
 // 24 KiB + 24 scale dwords the six-tile qkv and gate/up forms spilled; one tile: 16; never more than the kernel has phases -- the whole slice of
 // a wave is then requested up front and nothing is refilled
 template <int TMAX, int WF, int NPH> struct KpLook {
-    static constexpr int BASE = WF == W_MX4 ? (TMAX >= 4 ? 3 : TMAX >= 2 ? 6 : 16) : (TMAX >= 4 ? 1 : TMAX >= 2 ? 2 : 4) * (WF == W_FP8 ? 2 : 1);
-    static constexpr int L = (WF == W_MX4 && BASE > NPH) ? NPH : BASE;
+    static constexpr int BASE = WF == PW_MX4 ? (TMAX >= 4 ? 3 : TMAX >= 2 ? 6 : 16) : (TMAX >= 4 ? 1 : TMAX >= 2 ? 2 : 4) * (WF == PW_FP8 ? 2 : 1);
+    static constexpr int L = (WF == PW_MX4 && BASE > NPH) ? NPH : BASE;
 };
 // the MX4 form's scale dwords, one beside each register of the weight ring (nothing in the other forms)
 template <bool ON, int N> struct KpScales {};
@@ -63,18 +61,18 @@ template <int TMAX, int NPH> struct KpRowSets { static constexpr int N = (NPH > 
 // NH = 2 (round 6, batches of 33-64 rows): the block's eight waves are two HALVES of four -- half h stages rows 32 h .. 32 h + 31 and owns their two batch
 // tiles, its four waves split K four ways (twice the phases per wave); both halves stream the block's weight tiles (the second request is an L2 hit: HBM
 // reads them once), so the registers of a wave are those of the 32-row kernel.  Epilogue slots (tile, half) are dealt to the eight waves in passes.
-// WF (weight format of the tiles): W_BF16, W_FP8, or W_MX4 -- decode_km.hip's MXFP4 tiles (launch_quant_mx4): 16 rows x 128 k per KiB, lane l = row l & 15,
+// WF (weight format of the tiles): PW_BF16, PW_FP8, or PW_MX4 -- decode_km.hip's MXFP4 tiles (launch_quant_mx): 16 rows x 128 k per KiB, lane l = row l & 15,
 // dword j of its 16 bytes = the 8 k of group l >> 4 of the tile's j-th 32-wide step; the scale stream one dword of four e8m0 codes per (tile, row).  A
 // load step is then exactly one phase: one tile register and its scale dword per (phase, tile), four conversions (exact in bf16) and eight MFMAs per KiB.
 template <int MODE, bool NORM, bool R32, int TMAX, int NPH, int WF, int NH = 1>
 __global__ __launch_bounds__(KP_THREADS, 2) void emmax_decode_kmp_kernel(GemvParams p) {
-    constexpr bool FP8 = WF == W_FP8, MX4 = WF == W_MX4;
+    constexpr bool FP8 = WF == PW_FP8, MX4 = WF == PW_MX4;
     static_assert(NH == 1 || (NH == 2 && MODE != GEMV_LMHEAD), "halves: 1 or 2; the lm-head of 33-64 rows runs as two launches");
     constexpr int KW = KP_WAVES / NH;          // K slices = waves of a half
     constexpr int KP_NPH = NPH;
     extern __shared__ __attribute__((aligned(16))) unsigned char kp_smem[];
     constexpr int LOOK = KpLook<TMAX, WF, NPH>::L;
-    constexpr int KS = MX4 ? 128 : FP8 ? 64 : 32;      // elements per load step (one 1 KiB tile)
+    constexpr int KS = WFMT[WF].ks;                  // elements per load step (one 1 KiB tile)
     constexpr int PHS = KP_PH * 32 / KS;               // load steps per phase
     constexpr int RING = TMAX * PHS * LOOK;            // weight registers (16-byte loads of 1 KiB tiles) of a wave
     constexpr int WREG = TMAX * 2048 > KP_ROWS * KP_XP ? TMAX * 2048 : KP_ROWS * KP_XP;   // a wave's LDS region: window, later its partial tiles
@@ -117,7 +115,8 @@ __global__ __launch_bounds__(KP_THREADS, 2) void emmax_decode_kmp_kernel(GemvPar
     }
 
     // ---- weight stream: buffer loads, the (tile, step) offset in an SGPR, the lane's 16 bytes in the VGPR offset ----
-    const unsigned w_bytes = MX4 ? (unsigned)((size_t)p.n_groups * 8 * (size_t)K) : (unsigned)((size_t)p.n_groups * 16 * (size_t)K * (FP8 ? 1 : 2));
+    // (16 rows x K x 1 or 2 bytes keeps the parent's spelling: as one factor wfmt_bytes_per_k, or behind a helper, every bf16 kernel's scalar multiplies change operand order)
+    const unsigned w_bytes = wfmt_is_mx(WF) ? (unsigned)((size_t)p.n_groups * wfmt_bytes_per_k(WF) * (size_t)K) : (unsigned)((size_t)p.n_groups * 16 * (size_t)K * (FP8 ? 1 : 2));
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (int)w_bytes, 0x00020000);
     const unsigned voff = (unsigned)lane * 16u;
     u32x4_t w[RING];
@@ -128,14 +127,14 @@ __global__ __launch_bounds__(KP_THREADS, 2) void emmax_decode_kmp_kernel(GemvPar
     auto issue_w = [&](int ph, int tl, int s) {
         const int ks = ph * PHS + s;
         const int ok = (ph < KP_NPH && tl < ntb && ks < k_n) ? -1 : 0;
-        const unsigned so = ((unsigned)(((t_lo + tl) * KT + k_lo + ks) * 1024) & (unsigned)ok) | (w_bytes & (unsigned)~ok);
+        const unsigned so = ((unsigned)(((t_lo + tl) * KT + k_lo + ks) * WFMT[WF].tile_bytes) & (unsigned)ok) | (w_bytes & (unsigned)~ok);
         // aux 2 = nt (streamed once); NH = 2: the other half of the block requests the same tile -- default policy, so that the second request hits L2
         // (with nt both went to HBM: gate/up at 64 rows 61.8 us = twice the 32-row launch)
         w[((ph % LOOK) * TMAX + tl) * PHS + s] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, voff, so, NH == 2 ? KP_AUX2 : 2));
         if constexpr (MX4) {   // the tile's scale dwords, masked the same way: 64 B per tile in the tiles' order
-            const unsigned s_bytes = w_bytes / 16u;
-            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w4_scales, 0, (int)s_bytes, 0x00020000);
-            const unsigned ss = ((unsigned)(((t_lo + tl) * KT + k_lo + ks) * 64) & (unsigned)ok) | (s_bytes & (unsigned)~ok);
+            const unsigned s_bytes = w_bytes / (unsigned)(WFMT[WF].tile_bytes / WFMT_SCALE_BYTES);
+            const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_codes, 0, (int)s_bytes, 0x00020000);
+            const unsigned ss = ((unsigned)(((t_lo + tl) * KT + k_lo + ks) * WFMT_SCALE_BYTES) & (unsigned)ok) | (s_bytes & (unsigned)~ok);
             q4.s[((ph % LOOK) * TMAX + tl) * PHS + s] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(srsrc, (unsigned)c16 * 4u, ss, NH == 2 ? KP_AUX2 : 2);
         }
     };
@@ -222,7 +221,7 @@ __global__ __launch_bounds__(KP_THREADS, 2) void emmax_decode_kmp_kernel(GemvPar
            so that the second request finds the line in flight or present in L2 instead of reading HBM again (PMC: gate/up  \
            347 -> 201 MB per launch, 55 -> 44 us; qkv 183 -> 107 MB, 37 -> 35 us).  Not for the one-tile o-proj (14.8 -> 16.0 us) \
            nor with fp8 tiles (half the bytes: the launch is bound by the L2 -> CU path either way, the barrier only costs) */ \
-        if constexpr (NH == 2 && KP_HALF_SYNC && WF == W_BF16 && TMAX >= 3) __syncthreads();                           \
+        if constexpr (NH == 2 && KP_HALF_SYNC && WF == PW_BF16 && TMAX >= 3) __syncthreads();                           \
         /* the phase's fragments: batch tile nt, k-step s: row 16 nt + c16, chunk 4 s + g4 (wave-private window: only this  \
            wave's own LDS writes have to have landed, no barrier) */                                                    \
         bf16x8_t xf[KP_PH][2];                                                                                          \
@@ -413,20 +412,21 @@ int kp_launch_tf(const GemvParams& p, int grid, bool r32, bool init_only, hipStr
 }
 template <int MODE, bool NORM, int TMAX, int NPH = 4, int NH = 1>
 int kp_launch_tm(const GemvParams& p, int grid, bool r32, bool init_only, hipStream_t stream) {
-    // (no MX4 form of the six-tile qkv of 17-32 rows: an MXFP4 model has at most 32 heads x 128 = 768 qkv tiles, three per block -- decode_kmp_takes refuses it)
-    if constexpr (!(MODE == GEMV_QKV && TMAX == 6 && NH == 1)) {
-        if (init_only || p.w4_scales) {
-            const int r = kp_launch_tf<MODE, NORM, TMAX, NPH, W_MX4, NH>(p, grid, r32, init_only, stream);
+    // init_only walks every format's instantiation, a launch the one p.wfmt names.  No MX6 form; no MX4 form of the six-tile qkv of 17-32 rows: an MXFP4
+    // model has at most 32 heads x 128 = 768 qkv tiles, three per block -- decode_kmp_takes refuses both
+    constexpr bool has_mx4 = !(MODE == GEMV_QKV && TMAX == 6 && NH == 1);
+    if (!init_only && (p.wfmt == PW_MX6 || (p.wfmt == PW_MX4 && !has_mx4))) return -2;
+    if constexpr (has_mx4) {
+        if (init_only || p.wfmt == PW_MX4) {
+            const int r = kp_launch_tf<MODE, NORM, TMAX, NPH, PW_MX4, NH>(p, grid, r32, init_only, stream);
             if (r || !init_only) return r;
         }
-    } else if (!init_only && p.w4_scales) {
-        return -2;
     }
-    if (init_only || p.wscale) {
-        const int r = kp_launch_tf<MODE, NORM, TMAX, NPH, W_FP8, NH>(p, grid, r32, init_only, stream);
+    if (init_only || p.wfmt == PW_FP8) {
+        const int r = kp_launch_tf<MODE, NORM, TMAX, NPH, PW_FP8, NH>(p, grid, r32, init_only, stream);
         if (r || !init_only) return r;
     }
-    return kp_launch_tf<MODE, NORM, TMAX, NPH, W_BF16, NH>(p, grid, r32, init_only, stream);
+    return kp_launch_tf<MODE, NORM, TMAX, NPH, PW_BF16, NH>(p, grid, r32, init_only, stream);
 }
 
 // g: the geometry decode_kmp_takes returned (TMAX tiles per block, NPH phases, NH halves); init_only: every instantiation's LDS limit
@@ -481,7 +481,7 @@ int kp_dispatch(int mode, const GemvParams& p, const ProjGeom& g, hipStream_t st
 // a four-way split; the down projection and the lm-head run as two launches of <= 32 rows (step.hip: stage_chunk)
 bool decode_kmp_takes(const ProjShape& s, int B, ProjGeom* out) {
     if (B < 17 || B > 64 || s.mode < GEMV_QKV || s.mode > GEMV_PLAIN || (s.wfmt == PW_MX4 && !s.mx4_wide) || s.wfmt == PW_MX6) return false;
-    const int ks = s.wfmt == PW_MX4 ? 128 : s.wfmt == PW_FP8 ? 64 : 32, kw = B > 32 ? 4 : KP_WAVES, max_ph = B > 32 ? 8 : 11;
+    const int ks = WFMT[s.wfmt].ks, kw = B > 32 ? 4 : KP_WAVES, max_ph = B > 32 ? 8 : 11;
     if (s.K % ks || s.K / ks < kw || cdiv(s.K / ks, kw) * ks > max_ph * KP_PH * 32 || s.n_rows % 16 || s.attn_part) return false;
     if (s.mode == GEMV_QKV && (s.head_dim % 16 || s.head_dim < 16)) return false;
     ProjGeom g = {};
@@ -522,7 +522,7 @@ int decode_kmp_init() {
 }
 
 // p.W: the km copy of the matrix (launch_repack_km; fp8: decode_mfma.hip's e4m3 tiles of the permuted rows + p.wscale in the same row
-// order; MXFP4: launch_quant_mx4's tiles + p.w4_scales -- without a geometry from the caller the shape is taken as wide).  -2: decode_kmp_takes says no (K not in whole load steps, a wave's share beyond eleven phases, the o-proj's split merge)
+// order; MXFP4: launch_quant_mx's tiles + p.w_codes -- without a geometry from the caller the shape is taken as wide).  -2: decode_kmp_takes says no (K not in whole load steps, a wave's share beyond eleven phases, the o-proj's split merge)
 int launch_decode_kmp(int mode, const GemvParams& p_in, int B, hipStream_t stream, int* grid_out, const ProjGeom* geom) {
     ProjGeom g;
     if (geom) g = *geom;

@@ -620,9 +620,9 @@ static int mfma_kc(int B, int K, int tiles, int kstep) {
 // What this file takes: 1-8 rows of the fragment-major copy (bf16, or e4m3 tiles + per-row scales); K in whole k-steps (32 elements; fp8: 64),
 // rows in whole tiles (qkv / gate-up: pairs of tiles); the modes with a norm prologue in ONE K phase; head_dim / 32 a power of two (qkv)
 bool decode_mfma_takes(const ProjShape& s, int B, ProjGeom* out) {
-    if (B < 1 || B > MFMA_MAX_B || s.mode < GEMV_QKV || s.mode > GEMV_PLAIN || s.wfmt == PW_MX4 || s.wfmt == PW_MX6) return false;
+    if (B < 1 || B > MFMA_MAX_B || s.mode < GEMV_QKV || s.mode > GEMV_PLAIN || wfmt_is_mx(s.wfmt)) return false;
     const bool fp8 = s.wfmt == PW_FP8, norm = s.mode == GEMV_QKV || s.mode == GEMV_GATEUP || s.mode == GEMV_LMHEAD;
-    const int tiles = (s.mode == GEMV_QKV || s.mode == GEMV_GATEUP) ? 2 : 1, kstep = fp8 ? 64 : 32;
+    const int tiles = (s.mode == GEMV_QKV || s.mode == GEMV_GATEUP) ? 2 : 1, kstep = WFMT[s.wfmt].ks;
     if (s.K % kstep || s.n_rows % (16 * tiles)) {
         if (!(s.mode == GEMV_LMHEAD && s.n_rows % 16 == 0)) return false;
     }
@@ -679,7 +679,7 @@ int launch_decode_mfma(int mode, const GemvParams& p, int B, hipStream_t stream,
     if (geom) g = *geom;
     else if (!decode_mfma_takes(proj_shape(mode, p), B, &g)) return -1;
     if (grid_out) *grid_out = g.grid;
-    return p.wscale ? launch_mfma_mode<true>(mode, p, B, g, stream) : launch_mfma_mode<false>(mode, p, B, g, stream);
+    return p.wfmt == PW_FP8 ? launch_mfma_mode<true>(mode, p, B, g, stream) : launch_mfma_mode<false>(mode, p, B, g, stream);
 }
 
 int launch_quant_fm8(const void* src, int ld, void* dst, float* scales, int N, int K, hipStream_t stream, int perm, int head_dim) {

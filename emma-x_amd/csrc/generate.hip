@@ -138,10 +138,11 @@ int emmax_slots_open(emmax_session* s, int n_slots, emmax_stream stream) {
     if (s->beam.K) return fail(EMMAX_ERR_STATE, "request slots are not served while beams are on (emmax_session_clear_beams)");
     if (s->grp_N) return fail(EMMAX_ERR_STATE, "request slots are not served while sample groups are on (emmax_session_clear_sample_groups)");
     const int max_rows = session_max_rows(s);
-    if (n_slots < 1 || n_slots > s->max_batch || n_slots > max_rows)
-        return fail(EMMAX_ERR_INVALID, "%d slots outside 1..min(max_batch=%d, %d)%s", n_slots, s->max_batch, max_rows,
-                    (s->m->mx6 && n_slots >= 1 && n_slots <= s->max_batch) ? ": the limit of a model with MXFP6 decode weights"
-                    : (s->m->mx4 && n_slots >= 1 && n_slots <= s->max_batch) ? ": the limit of a model with MXFP4 decode weights" : "");
+    if (n_slots < 1 || n_slots > s->max_batch || n_slots > max_rows) {
+        const bool mx_limit = s->m->is_mx() && n_slots >= 1 && n_slots <= s->max_batch;
+        return fail(EMMAX_ERR_INVALID, "%d slots outside 1..min(max_batch=%d, %d)%s%s%s", n_slots, s->max_batch, max_rows, mx_limit ? ": the limit of a model with " : "",
+                    mx_limit ? s->m->wfmt_name() : "", mx_limit ? " decode weights" : "");
+    }
     if (n_slots >= EMMAX_MFMA_MIN_BATCH && !s->m->aux_built)
         return fail(EMMAX_ERR_STATE, "%d slots decode on the fragment-major weight copies: call emmax_model_build_aux first", n_slots);
     StreamScope sc(s, stream);

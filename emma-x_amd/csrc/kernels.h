@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "common.h"
@@ -259,6 +260,29 @@ struct EmmaxTune {
 };
 const EmmaxTune& emmax_tune();
 
+// ---- the weight format of a decode projection: ONE value from emmax_config.decode_fp8 to the kernels' template argument ----
+// fp8: the row copy for the staged GEMV, the e4m3 tiles for the MFMA families; MX4 / MX6: decode_km.hip's block-scaled tiles (MX4 also decode_kmp.hip's)
+enum { PW_BF16 = 0, PW_FP8 = 1, PW_MX4 = 2, PW_MX6 = 3, PW_COUNT = 4 };
+struct WFmt {
+    const char* name;   // as the error texts spell it
+    int code;           // emmax_config.decode_fp8 (3 is no format)
+    int ks;             // elements of a row per load step: one 16-byte load per lane feeds ks / 32 MFMAs
+    int tile_bytes;     // bytes of a 16-row tile of one load step
+    bool mx;            // block-scaled: an e8m0 code stream beside the tiles, WFMT_SCALE_BYTES per tile (one dword of four codes per row)
+};
+constexpr WFmt WFMT[PW_COUNT] = {{"bf16", 0, 32, 1024, false}, {"fp8", 1, 64, 1024, false}, {"MXFP4", 2, 128, 1024, true}, {"MXFP6", 4, 128, 1536, true}};
+constexpr int WFMT_SCALE_BYTES = 64;
+constexpr bool wfmt_is_mx(int f) { return WFMT[f].mx; }
+constexpr int wfmt_fps(int f) { return WFMT[f].ks / 32; }                           // MFMA fragments (32 elements) per load step
+constexpr int wfmt_bytes_per_k(int f) { return WFMT[f].tile_bytes / WFMT[f].ks; }   // bytes of 16 rows x one k: 32 / 16 / 8 / 12
+constexpr size_t wfmt_bytes(int f, size_t N, size_t K) { return N / 16 * K * wfmt_bytes_per_k(f); }                                 // a matrix's tiles
+constexpr size_t wfmt_scale_bytes(int f, size_t N, size_t K) { return WFMT[f].mx ? N / 16 * (K / WFMT[f].ks) * WFMT_SCALE_BYTES : 0; }   // ... its code stream
+inline int wfmt_of_code(int code) {   // -1: no format
+    for (int f = 0; f < PW_COUNT; ++f)
+        if (WFMT[f].code == code) return f;
+    return -1;
+}
+
 // ---- decode.hip: the LDS-staged GEMV, the embedding gather ----
 enum { GEMV_QKV = 0, GEMV_RESID = 1, GEMV_GATEUP = 2, GEMV_LMHEAD = 3, GEMV_PLAIN = 4 };
 struct GemvParams {
@@ -316,9 +340,19 @@ struct GemvParams {
     int exact;
     long long kv24;         // exact numerics: > 0 = the K / V caches are 24-bit (common.h: x24) -- kcache / vcache point at the bf16 plane of kv24 elements,
                             //   the 8-bit extension plane follows it; 0 = fp32 rows
-    const void* w4_scales;  // decode_km.hip, non-null: W holds MXFP4 tiles (launch_quant_mx4) and this is their scale stream; null: bf16 / fp8 (wscale)
-    int w_mx6;              // decode_km.hip, with w4_scales: 1 = W holds MXFP6 e2m3 tiles (launch_quant_mx6: 1536 B per 16 rows x 128 k), the scale stream is the same
+    const void* w_codes;    // block-scaled tiles (WFmt::mx; launch_quant_mx): their e8m0 scale stream; null otherwise
+    int wfmt;               // PW_*: what W holds -- the ONE statement of the format (proj_shape and the launchers' dispatch read it; wscale / w_codes are
+                            //   the operands that go with it).  Written by gemv_set_weights alone; a zero-initialised block is bf16
 };
+static_assert(sizeof(GemvParams) == 312 && offsetof(GemvParams, w_codes) == 296 && offsetof(GemvParams, wfmt) == 304,
+              "GemvParams travels by value: the kernels read it at the offsets they were compiled for");
+// the only writer of (W, wscale, w_codes, wfmt): scales = the per-row fp32 scales of an fp8 copy, or the code stream of block-scaled tiles
+static inline void gemv_set_weights(GemvParams& p, int wfmt, const void* W, const void* scales = nullptr) {
+    p.W = W;
+    p.wfmt = wfmt;
+    p.wscale = wfmt == PW_FP8 ? (const float*)scales : nullptr;
+    p.w_codes = wfmt_is_mx(wfmt) ? scales : nullptr;
+}
 // (where the QKV epilogues put the new K / V rows: gemv_kv_row / gemv_kv_store_x, decode_epilogue.h -- device code, this is also a host header)
 
 // ---- who decides what a launcher takes ----
@@ -327,17 +361,16 @@ struct GemvParams {
 // <family>_takes(shape, B, geometry out): no HIP call, no stream; it reads emmax_tune() where the launcher did (km_down, km_roll, ks_oproj).
 // The launcher derives the shape, asks its own check and launches from the geometry it returned (or from the one its caller already
 // got from the same check: the `geom` argument of the launchers): a launcher has no shape-based refusal its check does not report.
-enum { PW_BF16 = 0, PW_FP8 = 1, PW_MX4 = 2, PW_MX6 = 3 };   // weight format (fp8: the row copy for the staged GEMV, the e4m3 tiles for the MFMA families; MX4 / MX6: decode_km.hip's block-scaled tiles)
 struct ProjShape {
     int mode, K, n_rows, head_dim, Hq;
-    int wfmt;
+    int wfmt;                            // PW_*
     bool exact, h32, attn_part, x_tok;   // exact numerics; the fp32 stream is present; split partials in (nsplit of them); the folded embedding gather
     int nsplit, max_parts, max_grid;
     bool ld_ok;                          // ldw and ldx are multiples of 8
     bool mx4_wide;                       // MXFP4 tiles at 17-64 rows: decode_kmp.hip's MX4 form may take them (the model froze the tuning switch mx4_wide; proj_shape leaves it false)
 };
 static inline ProjShape proj_shape(int mode, const GemvParams& p) {
-    return {mode, p.K, p.n_rows, p.head_dim, p.Hq, p.w4_scales ? (p.w_mx6 ? PW_MX6 : PW_MX4) : p.wscale ? PW_FP8 : PW_BF16, p.exact != 0, p.h32 != nullptr,
+    return {mode, p.K, p.n_rows, p.head_dim, p.Hq, p.wfmt, p.exact != 0, p.h32 != nullptr,
             p.attn_part != nullptr, p.x_tok != nullptr, p.nsplit, p.max_parts, p.max_grid, p.ldw % 8 == 0 && p.ldx % 8 == 0};
 }
 // the launch geometry a check hands its launcher (fields a family does not use stay 0)
@@ -787,19 +820,18 @@ int launch_set_tokens(const RowState& rows, const int32_t* toks, int B, int budg
 // (gate, up) pairs inside one 16-row tile).  -2: shape outside the kernel, the caller falls back to launch_decode_mfma.
 int launch_repack_km(const void* src, int ld, void* dst, int N, int K, int perm, int head_dim, hipStream_t stream);
 int launch_decode_km(int mode, const GemvParams& p, int B, hipStream_t stream, int* grid_out = nullptr, const ProjGeom* geom = nullptr);
-// MXFP4 (OCP MX v1.0) copy of a row-major bf16 matrix in the km row order (perm / head_dim as launch_repack_km): blocks of 32 consecutive k of one
-// row share the exponent e = floor(log2(amax)) - 2 clamped to [-127, 127] (code e + 127; an all-zero block: code 127), elements are w / 2^e rounded
-// to nearest even onto +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}, saturating.  tiles: N K / 2 bytes (1 KiB = 16 rows x 128 k, lane-major: emmax_decode_km_kernel),
-// scales: N K / 32 bytes (one dword of four codes per (tile, row)).  N % 16 == 0, K % 128 == 0, ld % 8 == 0.  launch_dequant_mx4 writes the values
-// the copy holds back as bf16 rows (exact), each at the source row the permutation took it from.
-int launch_quant_mx4(const void* src, int ld, void* tiles, void* scales, int N, int K, int perm, int head_dim, hipStream_t stream);
-int launch_dequant_mx4(const void* tiles, const void* scales, void* dst, int ld, int N, int K, int perm, int head_dim, hipStream_t stream);
-// ... as OCP MXFP6 e2m3 (include/emmax.h pins the format): the same blocks, scale rule and scale stream; elements w / 2^e rounded to nearest even onto
-// +-{0, 0.125 .. 0.875, 1 .. 1.875, 2 .. 3.75, 4 .. 7.5}, saturating.  tiles: N K 6 / 8 bytes -- per (16 rows x 128 k) 1536 B: lane (row r, block g) = 16 g + r
-// owns the 32 elements of ONE scale block as six dwords (element i in bits [6 i, 6 i + 6)): dwords 0-3 at byte 16 lane of the tile's first KiB, dwords 4-5 at
-// byte 8 lane of the 512 B behind it (both loads of a wave are contiguous).  Same shape rules and row orders as launch_quant_mx4.
-int launch_quant_mx6(const void* src, int ld, void* tiles, void* scales, int N, int K, int perm, int head_dim, hipStream_t stream);
-int launch_dequant_mx6(const void* tiles, const void* scales, void* dst, int ld, int N, int K, int perm, int head_dim, hipStream_t stream);
+// The block-scaled copies (WFmt::mx) of a row-major bf16 matrix in the km row order (perm / head_dim as launch_repack_km): blocks of 32 consecutive k of
+// one row share the exponent e = floor(log2(amax)) - 2 clamped to [-127, 127] (code e + 127; an all-zero block: code 127); the scale stream is one dword
+// of four codes per (tile, row), in the tiles' order.  N % 16 == 0, K % 128 == 0, ld % 8 == 0.  launch_dequant_mx writes the values the copy holds back
+// as bf16 rows (exact), each at the source row the permutation took it from.
+//   PW_MX4 (OCP MX v1.0 MXFP4): elements w / 2^e rounded to nearest even onto +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}, saturating.  A tile = 16 rows x 128 k in
+//     1 KiB, lane-major (emmax_decode_km_kernel).
+//   PW_MX6 (OCP MXFP6 e2m3; include/emmax.h pins the format): onto +-{0, 0.125 .. 0.875, 1 .. 1.875, 2 .. 3.75, 4 .. 7.5}, saturating.  A tile = 1536 B:
+//     lane (row r, block g) = 16 g + r owns the 32 elements of ONE scale block as six dwords (element i in bits [6 i, 6 i + 6)): dwords 0-3 at byte
+//     16 lane of the tile's first KiB, dwords 4-5 at byte 8 lane of the 512 B behind it (both loads of a wave are contiguous).
+// -1: a shape outside the rules, or a format that is not block-scaled
+int launch_quant_mx(int wfmt, const void* src, int ld, void* tiles, void* codes, int N, int K, int perm, int head_dim, hipStream_t stream);
+int launch_dequant_mx(int wfmt, const void* tiles, const void* codes, void* dst, int ld, int N, int K, int perm, int head_dim, hipStream_t stream);
 bool decode_km_enabled();
 int decode_km_init();   // raise the dynamic-LDS limit of every instantiation (call once, outside graph capture)
 // decode_kmp.hip: batch 17-32 (two batch tiles per weight tile, the K slice in phases), bf16 weights, same copies; launch_decode_km routes there

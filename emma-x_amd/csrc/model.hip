@@ -93,10 +93,11 @@ static int check_config(const emmax_config& c, bool format_rules = true) {
     if (G != 1 && G != 2 && G != 4 && G != 8) return fail(EMMAX_ERR_INVALID, "GQA group %d unsupported (1,2,4,8)", G);
     if (c.inter % 16) return fail(EMMAX_ERR_INVALID, "LLM intermediate size must be a multiple of 16");
     if (c.vocab % 8) return fail(EMMAX_ERR_INVALID, "vocab must be a multiple of 8");
-    if (c.decode_fp8 < 0 || c.decode_fp8 == 3 || c.decode_fp8 > 4) return fail(EMMAX_ERR_INVALID, "decode_fp8 %d: 0 (bf16), 1 (fp8-e4m3), 2 (MXFP4) or 4 (MXFP6)", c.decode_fp8);
-    if (c.decode_fp8 == 1 && (c.hidden % 64 || (c.n_heads * c.head_dim) % 64)) return fail(EMMAX_ERR_INVALID, "fp8 decode needs K % 64 == 0");
-    if ((c.decode_fp8 == 2 || c.decode_fp8 == 4) && format_rules) {
-        const char* const fmt = c.decode_fp8 == 4 ? "MXFP6" : "MXFP4";   // (MXFP6 tiles cover the same 16 rows x 128 k per load step: one set of rules)
+    const int wfmt = wfmt_of_code(c.decode_fp8);
+    if (wfmt < 0) return fail(EMMAX_ERR_INVALID, "decode_fp8 %d: 0 (bf16), 1 (fp8-e4m3), 2 (MXFP4) or 4 (MXFP6)", c.decode_fp8);
+    if (wfmt == PW_FP8 && (c.hidden % 64 || (c.n_heads * c.head_dim) % 64)) return fail(EMMAX_ERR_INVALID, "fp8 decode needs K % 64 == 0");
+    if (wfmt_is_mx(wfmt) && format_rules) {
+        const char* const fmt = WFMT[wfmt].name;   // (MXFP6 tiles cover the same 16 rows x 128 k per load step: one set of rules)
         // MXFP4 tiles are read by decode_km.hip alone, at every batch: the model must be a shape that file takes.  qkv / o-proj / gate-up / lm-head:
         // eight waves x whole load steps of 128 elements, at most sixteen fragments per wave -- K % 1024 == 0 and K <= 4096, at most 8 tiles
         // for each of 256 blocks (N <= 32768); the down projection on the phased kernel: whole load steps (K % 128 == 0), K above 4096 and
@@ -159,18 +160,13 @@ static void derive(emmax_model* m) {
     }
     m->lm_head_w = ProjW{};
     m->lm_head_w.gemv_mode = GEMV_LMHEAD; m->lm_head_w.f8bit = F8_LMHEAD;
-    m->fp8 = c.decode_fp8 == 1;
-    m->mx4 = c.decode_fp8 == 2;
+    m->wfmt = wfmt_of_code(c.decode_fp8);   // (check_config has refused a code that is no format)
     // the tuning switch mx4_wide is read HERE, once (emmax_model_create; emmax_config_max_decode_batch's model of the moment), and frozen: planner,
     // session checks and launch_proj ask the model, never the live switch
-    m->mx4_wide = m->mx4 && emmax_tune().mx4_wide != 0;
+    m->mx4_wide = m->wfmt == PW_MX4 && emmax_tune().mx4_wide != 0;   // (MXFP6: does not apply, decode_kmp.hip has no MX6 form)
     for (auto& L : m->layers)
-        for (const ProjDim& d : layer_projs(m)) L.proj[d.stage].q4w = m->mx4_wide;
-    m->lm_head_w.q4w = m->mx4_wide;
-    m->mx6 = c.decode_fp8 == 4;   // (mx4_wide does not apply: decode_kmp.hip has no MX6 form)
-    for (auto& L : m->layers)
-        for (const ProjDim& d : layer_projs(m)) L.proj[d.stage].q6 = m->mx6;
-    m->lm_head_w.q6 = m->mx6;
+        for (const ProjDim& d : layer_projs(m)) { L.proj[d.stage].wfmt = m->wfmt; L.proj[d.stage].wide = m->mx4_wide; }
+    m->lm_head_w.wfmt = m->wfmt; m->lm_head_w.wide = m->mx4_wide;
 }
 
 static void plan_arena(emmax_model* m, Bump& b) {
@@ -207,12 +203,10 @@ static void plan_arena(emmax_model* m, Bump& b) {
         L.ln2 = b.take(m->H);
         g->rm = b.take(dims[2].N * dims[2].K);
         d->rm = b.take(dims[3].N * dims[3].K);
-        for (const ProjDim& p : dims) { ProjW& w = L.proj[p.stage]; w.r8 = nullptr; w.sc = w.km_sc = nullptr; w.q4 = w.q4s = nullptr; }
-        if (m->mx4)   // 4.25 bits per weight: every batch reads these, so they live in the main arena
-            for (const ProjDim& p : dims) { ProjW& w = L.proj[p.stage]; w.q4 = b.bytes(p.N * p.K / 2); w.q4s = b.bytes(p.N * p.K / 32); }
-        if (m->mx6)   // 6.25 bits per weight, main arena for the same reason
-            for (const ProjDim& p : dims) { ProjW& w = L.proj[p.stage]; w.q4 = b.bytes(p.N * p.K / 8 * 6); w.q4s = b.bytes(p.N * p.K / 32); }
-        if (m->fp8) {   // fp8 tiles take half the bytes; every batch regime reads some of them, so they live in the main arena
+        for (const ProjDim& p : dims) { ProjW& w = L.proj[p.stage]; w.r8 = nullptr; w.sc = w.km_sc = nullptr; w.tiles = w.codes = nullptr; }
+        if (m->is_mx())   // 4.25 / 6.25 bits per weight: every batch reads these, so they live in the main arena
+            for (const ProjDim& p : dims) { ProjW& w = L.proj[p.stage]; w.tiles = b.bytes(wfmt_bytes(m->wfmt, p.N, p.K)); w.codes = b.bytes(wfmt_scale_bytes(m->wfmt, p.N, p.K)); }
+        if (m->wfmt == PW_FP8) {   // fp8 tiles take half the bytes; every batch regime reads some of them, so they live in the main arena
             for (const ProjDim& p : dims) L.proj[p.stage].fm = b.take(p.N * p.K / 2);
             q->km = b.take(dims[0].N * dims[0].K / 2);
             g->km = b.take(dims[2].N * dims[2].K / 2);
@@ -227,13 +221,12 @@ static void plan_arena(emmax_model* m, Bump& b) {
     m->final_norm = b.take(m->H);
     ProjW& lm = m->lm_head_w;
     lm.rm = b.take((int64_t)m->vocab_p * m->H);
-    if (m->fp8) {
+    if (m->wfmt == PW_FP8) {
         lm.km = lm.fm = b.take((int64_t)m->vocab_p * m->H / 2);
         lm.km_sc = lm.sc = (float*)b.take(2 * (int64_t)m->vocab_p);
         lm.r8 = b.take((int64_t)m->vocab_p * m->H / 2);
     }
-    if (m->mx4) { lm.q4 = b.bytes((int64_t)m->vocab_p * m->H / 2); lm.q4s = b.bytes((int64_t)m->vocab_p * m->H / 32); }
-    if (m->mx6) { lm.q4 = b.bytes((int64_t)m->vocab_p * m->H / 8 * 6); lm.q4s = b.bytes((int64_t)m->vocab_p * m->H / 32); }
+    if (m->is_mx()) { lm.tiles = b.bytes(wfmt_bytes(m->wfmt, m->vocab_p, m->H)); lm.codes = b.bytes(wfmt_scale_bytes(m->wfmt, m->vocab_p, m->H)); }
 }
 
 // bf16 models: the copies only the batch >= 3 decode kernels read -- row-permuted fragment-major qkv / gate-up (decode_km.hip),
@@ -395,7 +388,7 @@ int emmax_model_finalize(emmax_model* m, void* arena, int64_t arena_bytes, emmax
             HIPCHK(hipMemcpy2DAsync((char*)L.proj[STAGE_GATEUP].rm + grp, 2 * grp, iu->second.ptr, grp, grp, m->inter / 16, hipMemcpyDeviceToDevice, st));
         }
         PUT2(P + "mlp.down_proj.weight", m->H, m->inter, L.proj[STAGE_DOWN].rm, m->inter_p, 0);
-        if (m->fp8) {
+        if (m->wfmt == PW_FP8) {
             const auto dims = layer_projs(m);
             for (const ProjDim& d : dims) KCHK(launch_quant_fm8(L.proj[d.stage].rm, (int)d.K, L.proj[d.stage].fm, L.proj[d.stage].sc, (int)d.N, (int)d.K, st));
             for (const ProjDim& d : dims)   // (writes the same scales again)
@@ -403,39 +396,30 @@ int emmax_model_finalize(emmax_model* m, void* arena, int64_t arena_bytes, emmax
             for (const ProjDim& d : dims)
                 if (d.perm) KCHK(launch_quant_fm8(L.proj[d.stage].rm, (int)d.K, L.proj[d.stage].km, L.proj[d.stage].km_sc, (int)d.N, (int)d.K, st, d.perm, d.perm_hd));
         }
-        if (m->mx4)   // quantise, then write the values the copy holds back over the rows the prefill GEMMs read (exact in bf16)
+        if (m->is_mx())   // quantise, then write the values the copy holds back over the rows the prefill GEMMs read (exact in bf16): prefill, extend,
+                          // verify, scoring and the taps evaluate the quantised model
             for (const ProjDim& d : layer_projs(m)) {
                 ProjW& w = L.proj[d.stage];
-                KCHK(launch_quant_mx4(w.rm, (int)d.K, w.q4, w.q4s, (int)d.N, (int)d.K, d.perm, d.perm_hd, st));
-                KCHK(launch_dequant_mx4(w.q4, w.q4s, w.rm, (int)d.K, (int)d.N, (int)d.K, d.perm, d.perm_hd, st));
-            }
-        if (m->mx6)   // the same for the e2m3 tiles: prefill, extend, verify, scoring and the taps evaluate the quantised model
-            for (const ProjDim& d : layer_projs(m)) {
-                ProjW& w = L.proj[d.stage];
-                KCHK(launch_quant_mx6(w.rm, (int)d.K, w.q4, w.q4s, (int)d.N, (int)d.K, d.perm, d.perm_hd, st));
-                KCHK(launch_dequant_mx6(w.q4, w.q4s, w.rm, (int)d.K, (int)d.N, (int)d.K, d.perm, d.perm_hd, st));
+                KCHK(launch_quant_mx(m->wfmt, w.rm, (int)d.K, w.tiles, w.codes, (int)d.N, (int)d.K, d.perm, d.perm_hd, st));
+                KCHK(launch_dequant_mx(m->wfmt, w.tiles, w.codes, w.rm, (int)d.K, (int)d.N, (int)d.K, d.perm, d.perm_hd, st));
             }
     }
     PUT1("language_model.model.norm.weight", m->H, m->final_norm);
     PUT2("language_model.lm_head.weight", m->vocab, m->H, m->lm_head_w.rm, m->H, 0);
-    if (m->fp8) {
+    if (m->wfmt == PW_FP8) {
         KCHK(launch_quant_fm8(m->lm_head_w.rm, m->H, m->lm_head_w.fm, m->lm_head_w.sc, m->vocab_p, m->H, st));
         KCHK(launch_quant_rm8(m->lm_head_w.rm, m->H, m->lm_head_w.r8, m->lm_head_w.sc, m->vocab_p, m->H, st));
     }
-    if (m->mx4) {
-        KCHK(launch_quant_mx4(m->lm_head_w.rm, m->H, m->lm_head_w.q4, m->lm_head_w.q4s, m->vocab_p, m->H, 0, 0, st));
-        KCHK(launch_dequant_mx4(m->lm_head_w.q4, m->lm_head_w.q4s, m->lm_head_w.rm, m->H, m->vocab_p, m->H, 0, 0, st));
-    }
-    if (m->mx6) {
-        KCHK(launch_quant_mx6(m->lm_head_w.rm, m->H, m->lm_head_w.q4, m->lm_head_w.q4s, m->vocab_p, m->H, 0, 0, st));
-        KCHK(launch_dequant_mx6(m->lm_head_w.q4, m->lm_head_w.q4s, m->lm_head_w.rm, m->H, m->vocab_p, m->H, 0, 0, st));
+    if (m->is_mx()) {
+        KCHK(launch_quant_mx(m->wfmt, m->lm_head_w.rm, m->H, m->lm_head_w.tiles, m->lm_head_w.codes, m->vocab_p, m->H, 0, 0, st));
+        KCHK(launch_dequant_mx(m->wfmt, m->lm_head_w.tiles, m->lm_head_w.codes, m->lm_head_w.rm, m->H, m->vocab_p, m->H, 0, 0, st));
     }
 #undef PUT2
 #undef PUT1
     HIPCHK(hipStreamSynchronize(st));
     m->finalized = true;
     m->ln_folded = fold_ln;
-    m->aux_built = m->fp8 || m->mxq();
+    m->aux_built = m->wfmt != PW_BF16;
     m->bound.clear();
     return 0;
 }
@@ -454,7 +438,7 @@ int emmax_config_max_decode_batch(const emmax_config* cfg, int exact) {
 
 int64_t emmax_model_aux_bytes(const emmax_model* m) {
     if (!m) return -1;
-    if (m->fp8 || m->mxq()) return 0;
+    if (m->wfmt != PW_BF16) return 0;
     // sized on a copy of the layer table: a const query must not move the pointers of a built arena
     emmax_model tmp = *m;
     Bump b{nullptr};
@@ -465,7 +449,7 @@ int64_t emmax_model_aux_bytes(const emmax_model* m) {
 int emmax_model_build_aux(emmax_model* m, void* aux, int64_t aux_bytes, emmax_stream stream) {
     if (!m) return fail(EMMAX_ERR_INVALID, "null argument");
     if (!m->finalized) return fail(EMMAX_ERR_STATE, "emmax_model_build_aux before emmax_model_finalize");
-    if (m->fp8 || m->mxq()) return 0;   // nothing to build: the e4m3 / MXFP4 / MXFP6 copies of every regime are in the main arena
+    if (m->wfmt != PW_BF16) return 0;   // nothing to build: the e4m3 / MXFP4 / MXFP6 copies of every regime are in the main arena
     if (!aux) return fail(EMMAX_ERR_INVALID, "null argument");
     hipStream_t st = (hipStream_t)stream;
     const bool ab = emmax_tune().km == 0;

@@ -3,11 +3,35 @@
 #include "session.h"
 
 // y[B, N] = x[B, K] . W^T, nothing fused: the parameters of the single-projection entry points
-static GemvParams plain_gemv(const void* x, const void* W, void* y, int N, int K, const float* wscale = nullptr) {
+static GemvParams plain_gemv(const void* x, const void* W, void* y, int N, int K, int wfmt = PW_BF16, const void* scales = nullptr) {
     GemvParams p;
     memset(&p, 0, sizeof(p));
-    p.x = x; p.ldx = K; p.W = W; p.ldw = K; p.K = K; p.y = y; p.ldy = N; p.n_rows = N; p.wscale = wscale;
+    p.x = x; p.ldx = K; p.ldw = K; p.K = K; p.y = y; p.ldy = N; p.n_rows = N;
+    gemv_set_weights(p, wfmt, W, scales);
     return p;
+}
+
+// the three single-kernel entry points of a block-scaled format (emmax_op_*_mxfp4 / _mxfp6): `op` is the exported name, for the texts
+static int op_quant_mx(int wfmt, const char* op, const void* W, int ld, void* tiles, void* scales, int N, int K, int perm, int perm_hd, emmax_stream st) {
+    if (!W || !tiles || !scales) return fail(EMMAX_ERR_INVALID, "%s: null argument", op);
+    int r = launch_quant_mx(wfmt, W, ld, tiles, scales, N, K, perm, perm_hd, (hipStream_t)st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "%s: N %% 16, K %% 128, ld %% 8, ld >= K (perm 1: N %% head_dim, head_dim %% 16; perm 2: N %% 32) required", op);
+    return 0;
+}
+static int op_dequant_mx(int wfmt, const char* op, const void* tiles, const void* scales, void* W, int ld, int N, int K, int perm, int perm_hd, emmax_stream st) {
+    if (!W || !tiles || !scales) return fail(EMMAX_ERR_INVALID, "%s: null argument", op);
+    int r = launch_dequant_mx(wfmt, tiles, scales, W, ld, N, K, perm, perm_hd, (hipStream_t)st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "%s: N %% 16, K %% 128, ld %% 8, ld >= K (perm 1: N %% head_dim, head_dim %% 16; perm 2: N %% 32) required", op);
+    return 0;
+}
+static int op_gemm_small_mx(int wfmt, const char* op, const void* x, const void* tiles, const void* scales, void* y, int B, int N, int K, emmax_stream st) {
+    if (!x || !tiles || !scales || !y) return fail(EMMAX_ERR_INVALID, "%s: null argument", op);
+    GemvParams p = plain_gemv(x, tiles, y, N, K, wfmt, scales);
+    if (B < 1 || B > 16) return fail(EMMAX_ERR_INVALID, "%s: batch %d outside 1..16", op, B);
+    // (the K-split kernel only: the phased kernel of the down projection is reached through emmax_op_decode_stage)
+    const int r = launch_decode_km(GEMV_PLAIN, p, B, (hipStream_t)st);
+    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "%s: unsupported shape (N %% 16 and N <= 32768; K %% 1024 and K <= 4096)", op);
+    return 0;
 }
 
 extern "C" {
@@ -838,55 +862,27 @@ int emmax_op_quant_rm8(const void* W, int ld, void* W8, float* scales, int N, in
     return 0;
 }
 int emmax_op_quant_mxfp4(const void* W, int ld, void* tiles, void* scales, int N, int K, int perm, int perm_hd, emmax_stream st) {
-    if (!W || !tiles || !scales) return fail(EMMAX_ERR_INVALID, "emmax_op_quant_mxfp4: null argument");
-    int r = launch_quant_mx4(W, ld, tiles, scales, N, K, perm, perm_hd, (hipStream_t)st);
-    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_quant_mxfp4: N %% 16, K %% 128, ld %% 8, ld >= K (perm 1: N %% head_dim, head_dim %% 16; perm 2: N %% 32) required");
-    return 0;
+    return op_quant_mx(PW_MX4, "emmax_op_quant_mxfp4", W, ld, tiles, scales, N, K, perm, perm_hd, st);
 }
 int emmax_op_dequant_mxfp4(const void* tiles, const void* scales, void* W, int ld, int N, int K, int perm, int perm_hd, emmax_stream st) {
-    if (!W || !tiles || !scales) return fail(EMMAX_ERR_INVALID, "emmax_op_dequant_mxfp4: null argument");
-    int r = launch_dequant_mx4(tiles, scales, W, ld, N, K, perm, perm_hd, (hipStream_t)st);
-    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_dequant_mxfp4: N %% 16, K %% 128, ld %% 8, ld >= K (perm 1: N %% head_dim, head_dim %% 16; perm 2: N %% 32) required");
-    return 0;
+    return op_dequant_mx(PW_MX4, "emmax_op_dequant_mxfp4", tiles, scales, W, ld, N, K, perm, perm_hd, st);
 }
 int emmax_op_gemm_small_mxfp4(const void* x, const void* tiles, const void* scales, void* y, int B, int N, int K, emmax_stream st) {
-    if (!x || !tiles || !scales || !y) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_small_mxfp4: null argument");
-    GemvParams p = plain_gemv(x, tiles, y, N, K);
-    p.w4_scales = scales;
-    if (B < 1 || B > 16) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_small_mxfp4: batch %d outside 1..16", B);
-    // (the K-split kernel only: the phased kernel of the down projection is reached through emmax_op_decode_stage)
-    const int r = launch_decode_km(GEMV_PLAIN, p, B, (hipStream_t)st);
-    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_gemm_small_mxfp4: unsupported shape (N %% 16 and N <= 32768; K %% 1024 and K <= 4096)");
-    return 0;
+    return op_gemm_small_mx(PW_MX4, "emmax_op_gemm_small_mxfp4", x, tiles, scales, y, B, N, K, st);
 }
 int emmax_op_quant_mxfp6(const void* W, int ld, void* tiles, void* scales, int N, int K, int perm, int perm_hd, emmax_stream st) {
-    if (!W || !tiles || !scales) return fail(EMMAX_ERR_INVALID, "emmax_op_quant_mxfp6: null argument");
-    int r = launch_quant_mx6(W, ld, tiles, scales, N, K, perm, perm_hd, (hipStream_t)st);
-    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_quant_mxfp6: N %% 16, K %% 128, ld %% 8, ld >= K (perm 1: N %% head_dim, head_dim %% 16; perm 2: N %% 32) required");
-    return 0;
+    return op_quant_mx(PW_MX6, "emmax_op_quant_mxfp6", W, ld, tiles, scales, N, K, perm, perm_hd, st);
 }
 int emmax_op_dequant_mxfp6(const void* tiles, const void* scales, void* W, int ld, int N, int K, int perm, int perm_hd, emmax_stream st) {
-    if (!W || !tiles || !scales) return fail(EMMAX_ERR_INVALID, "emmax_op_dequant_mxfp6: null argument");
-    int r = launch_dequant_mx6(tiles, scales, W, ld, N, K, perm, perm_hd, (hipStream_t)st);
-    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_dequant_mxfp6: N %% 16, K %% 128, ld %% 8, ld >= K (perm 1: N %% head_dim, head_dim %% 16; perm 2: N %% 32) required");
-    return 0;
+    return op_dequant_mx(PW_MX6, "emmax_op_dequant_mxfp6", tiles, scales, W, ld, N, K, perm, perm_hd, st);
 }
 int emmax_op_gemm_small_mxfp6(const void* x, const void* tiles, const void* scales, void* y, int B, int N, int K, emmax_stream st) {
-    if (!x || !tiles || !scales || !y) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_small_mxfp6: null argument");
-    GemvParams p = plain_gemv(x, tiles, y, N, K);
-    p.w4_scales = scales;
-    p.w_mx6 = 1;
-    if (B < 1 || B > 16) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_small_mxfp6: batch %d outside 1..16", B);
-    // (the K-split kernel only: the phased kernel of the down projection is reached through emmax_op_decode_stage)
-    const int r = launch_decode_km(GEMV_PLAIN, p, B, (hipStream_t)st);
-    if (r) return fail(r == -4 ? EMMAX_ERR_HIP : EMMAX_ERR_INVALID, "emmax_op_gemm_small_mxfp6: unsupported shape (N %% 16 and N <= 32768; K %% 1024 and K <= 4096)");
-    return 0;
+    return op_gemm_small_mx(PW_MX6, "emmax_op_gemm_small_mxfp6", x, tiles, scales, y, B, N, K, st);
 }
 int emmax_op_gemm_wide_mxfp4(const void* x, const void* tiles, const void* scales, void* y, int B, int N, int K, emmax_stream st) {
     if (!x || !tiles || !scales || !y) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_wide_mxfp4: null argument");
     if (B < 17 || B > EMMAX_KMP_ROWS) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_wide_mxfp4: batch %d outside 17..%d", B, EMMAX_KMP_ROWS);
-    GemvParams p = plain_gemv(x, tiles, y, N, K);
-    p.w4_scales = scales;
+    GemvParams p = plain_gemv(x, tiles, y, N, K, PW_MX4, scales);
     // decode_kmp.hip's MX4 form as a pure op: the shape is wide by definition here (no model, no switch); its own check decides the rest
     ProjShape s = proj_shape(GEMV_PLAIN, p);
     s.mx4_wide = true;
@@ -900,13 +896,13 @@ int emmax_op_gemv_fp8(const void* x, const void* W8, const float* scales, void* 
     if (B < 1 || B > 2) return fail(EMMAX_ERR_INVALID, "emmax_op_gemv_fp8: batch must be 1..2");
     if (!scales) return fail(EMMAX_ERR_INVALID, "emmax_op_gemv_fp8: scales required");
     if (decode_gemv_init()) return fail(EMMAX_ERR_HIP, "emmax_op_gemv_fp8: init failed");
-    GemvParams p = plain_gemv(x, W8, y, N, K, scales);
+    GemvParams p = plain_gemv(x, W8, y, N, K, scales ? PW_FP8 : PW_BF16, scales);
     int r = launch_decode_gemv(GEMV_PLAIN, p, B, (hipStream_t)st);
     if (r) return fail(EMMAX_ERR_INVALID, "emmax_op_gemv_fp8: unsupported shape (K %% 16, B * K * 2 bytes of LDS)");
     return 0;
 }
 int emmax_op_gemm_small_fp8(const void* x, const void* W8, const float* scales, void* y, int B, int N, int K, emmax_stream st) {
-    GemvParams p = plain_gemv(x, W8, y, N, K, scales);
+    GemvParams p = plain_gemv(x, W8, y, N, K, scales ? PW_FP8 : PW_BF16, scales);
     if (!scales) return fail(EMMAX_ERR_INVALID, "emmax_op_gemm_small_fp8: scales required");
     int r;
     if (B <= 8) {   // decode_mfma.hip stages eight rows

@@ -136,13 +136,14 @@ int run_prefill(emmax_session* s, const int32_t* ids, const int32_t* lens, int B
     if (!m->finalized) return fail(EMMAX_ERR_STATE, "model not finalized");
     // (an exact session was checked against the shapes its two-term kernels take when it was created, and chunks larger batches: check_exact)
     const int max_rows = session_max_rows(s);
-    if (B <= 0 || B > s->max_batch || B > max_rows)
-        return fail(EMMAX_ERR_INVALID, "prefill batch %d outside 1..min(max_batch=%d, %d) (%s)", B, s->max_batch, max_rows,
-                    (m->mx6 && B >= 1 && B <= s->max_batch)
-                        ? "the limit of a model with MXFP6 decode weights, re-read at every prefill: emmax_model_max_decode_batch"
-                    : (m->mx4 && B >= 1 && B <= s->max_batch)   // (the model's limit binds: it can move after the session was created, with the attention switches)
-                        ? "the limit of a model with MXFP4 decode weights, re-read at every prefill: emmax_model_max_decode_batch"
-                        : "decode batches above 8 need the shapes decode_km.hip takes: emmax_model_max_decode_batch");
+    if (B <= 0 || B > s->max_batch || B > max_rows) {
+        // (block-scaled tiles: the model's limit binds -- it can move after the session was created, with the attention switches)
+        const bool mx_limit = m->is_mx() && B >= 1 && B <= s->max_batch;
+        return fail(EMMAX_ERR_INVALID, "prefill batch %d outside 1..min(max_batch=%d, %d) (%s%s%s)", B, s->max_batch, max_rows, mx_limit ? "the limit of a model with " : "",
+                    mx_limit ? m->wfmt_name() : "",
+                    mx_limit ? " decode weights, re-read at every prefill: emmax_model_max_decode_batch"
+                             : "decode batches above 8 need the shapes decode_km.hip takes: emmax_model_max_decode_batch");
+    }
     if (B >= EMMAX_MFMA_MIN_BATCH && !m->aux_built)
         return fail(EMMAX_ERR_STATE, "batch %d decodes on the fragment-major weight copies: call emmax_model_build_aux first", B);
     const int np = patches ? m->tw[0].n_patches : 0;

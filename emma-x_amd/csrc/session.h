@@ -85,11 +85,11 @@ struct ProjW {
                      // lm-head: that kernel reads the natural order -- the same pointer as fm
     bf16* r8;        // fp8 mode: the same e4m3 values as rows in the GEMV's span order (batch 1-2)
     float *sc, *km_sc;      // fp8 mode: per-row scales (null otherwise), and those of km in its row order
-    void *q4, *q4s;         // MXFP4 mode: e2m1 tiles in km's row order and their e8m0 scale stream (launch_quant_mx4); null otherwise.  rm then holds the
-                            // de-quantised values: the prefill evaluates the model the decode step streams
+    void *tiles, *codes;    // block-scaled modes (WFmt::mx): the tiles in km's row order and their e8m0 scale stream (launch_quant_mx); null otherwise.  rm then
+                            // holds the de-quantised values: the prefill evaluates the model the decode step streams
     int gemv_mode, f8bit;   // GEMV_QKV / GEMV_RESID / GEMV_GATEUP / GEMV_LMHEAD, and its bit of the tuning switch fp8_gemv
-    bool q4w;               // MXFP4 mode: the model's mx4_wide (the tiles are served at 17-64 rows too)
-    bool q6;                // MXFP6 mode: q4 / q4s hold e2m3 tiles (launch_quant_mx6: N K 6 / 8 bytes) and the same e8m0 scale stream; rm the de-quantised values
+    int wfmt;               // PW_*: the model's decode weight format
+    bool wide;              // MXFP4 mode: the model's mx4_wide (the tiles are served at 17-64 rows too)
 };
 struct LayerW {
     bf16 *ln1, *ln2;
@@ -106,11 +106,10 @@ struct emmax_model {
     bf16 *pj1_w, *pj1_b, *pj2_w, *pj2_b, *pj3_w, *pj3_b;
     bf16 *embed, *final_norm;
     ProjW lm_head_w = {};
-    bool fp8 = false;            // decode_fp8 == 1: e4m3 decode copies
-    bool mx4 = false;            // decode_fp8 == 2: MXFP4 decode copies (decode_km.hip: batches 1-16)
-    bool mx6 = false;            // decode_fp8 == 4: MXFP6 e2m3 decode copies (decode_km.hip: batches 1-16), in the ProjW fields of the MXFP4 tiles (ProjW::q6)
-    bool mxq() const { return mx4 || mx6; }                        // block-scaled tiles: decode_km.hip alone reads them, at every batch
-    const char* mx_name() const { return mx6 ? "MXFP6" : "MXFP4"; }
+    int wfmt = PW_BF16;          // the decode weight format (kernels.h: WFMT), set once from cfg.decode_fp8.  fp8: e4m3 decode copies; MX4 / MX6:
+                                 // block-scaled tiles that decode_km.hip alone reads at 1-16 rows, at every batch
+    bool is_mx() const { return wfmt_is_mx(wfmt); }
+    const char* wfmt_name() const { return WFMT[wfmt].name; }
     bool mx4_wide = false;       // ... and 17-64 rows on decode_kmp.hip's MX4 form: the tuning switch mx4_wide as it stood at emmax_model_create, frozen
     bool ln_folded = false;      // the ViT LayerNorms are folded into the qkv / fc1 weights (tuning switch gemm_lnfuse at finalize)
     bool aux_built = false;      // the batch >= 3 copies exist (fp8 models: always, they are part of the main arena)

@@ -231,9 +231,7 @@ static int check_stage_rows(int max_batch, int stage_rows) {
 }
 // what an exact-numerics session needs of its model and its shape
 static int check_exact(const emmax_model* m, int max_batch, int stage_rows) {
-    if (m->fp8) return fail(EMMAX_ERR_INVALID, "exact numerics (tuning switch exact) runs on bf16 weights: this model streams fp8 decode weights");
-    if (m->mx4) return fail(EMMAX_ERR_INVALID, "exact numerics (tuning switch exact) runs on bf16 weights: this model streams MXFP4 decode weights");
-    if (m->mx6) return fail(EMMAX_ERR_INVALID, "exact numerics (tuning switch exact) runs on bf16 weights: this model streams MXFP6 decode weights");
+    if (m->wfmt != PW_BF16) return fail(EMMAX_ERR_INVALID, "exact numerics (tuning switch exact) runs on bf16 weights: this model streams %s decode weights", m->wfmt_name());
     if (m->finalized && m->ln_folded)
         return fail(EMMAX_ERR_STATE, "exact numerics needs the ViT LayerNorms unfolded: set the tuning switch exact = 1 BEFORE emmax_model_finalize");
     // batch 1-2: decode_ks.hip's two-term dot products; batch 3-8: decode_km.hip's EX kernels (the two terms of a row in the MFMA's sixteen batch
@@ -263,8 +261,8 @@ int emmax_session_bytes_ex(const emmax_model* m, int max_batch, int max_prompt, 
     tmp.n_stg = stage_rows; tmp.stg0 = max_batch; tmp.rows_total = max_batch + tmp.n_stg;
     tmp.exact = emmax_tune().exact != 0;
     if (tmp.exact && (r = check_exact(m, max_batch, stage_rows))) return r;
-    if (m->mxq() && max_batch > model_max_decode_batch(m))   // no kernel streams the block-scaled tiles for more rows: refused here, not at the first prefill
-        return fail(EMMAX_ERR_INVALID, "%s decode weights serve batches of 1-%d rows; max_batch %d", m->mx_name(), model_max_decode_batch(m), max_batch);
+    if (m->is_mx() && max_batch > model_max_decode_batch(m))   // no kernel streams the block-scaled tiles for more rows: refused here, not at the first prefill
+        return fail(EMMAX_ERR_INVALID, "%s decode weights serve batches of 1-%d rows; max_batch %d", m->wfmt_name(), model_max_decode_batch(m), max_batch);
     Bump b{nullptr};
     plan_session(&tmp, b);
     if (ws) *ws = b.off + 256;

@@ -19,15 +19,17 @@ static int fp8_gemv_mask(int B) {
 
 // Which copies of a projection's matrix exist -- flags, not pointers: the planner asks before any arena exists.  copies_of: what a
 // ProjW holds now (launch_proj); copies_planned: what the model has or, before emmax_model_build_aux, will have.
-// q4w: the MXFP4 tiles are served at 17-64 rows too (decode_kmp.hip's MX4 form): the model was created under the tuning switch mx4_wide
-struct ProjCopies { bool rm, r8, sc, km, fm, q4; int f8bit; bool q4w; bool q6; };   // q4: block-scaled tiles exist; q6: they are MXFP6 (else MXFP4)
-static ProjCopies copies_of(const ProjW& w) { return {w.rm != nullptr, w.r8 != nullptr, w.sc != nullptr, w.km != nullptr, w.fm != nullptr, w.q4 != nullptr, w.f8bit, w.q4 != nullptr && w.q4w, w.q4 != nullptr && w.q6}; }
+// tiles: block-scaled tiles exist, of format wfmt (PW_*); wide: MXFP4 tiles that are served at 17-64 rows too (decode_kmp.hip's MX4 form): the model
+// was created under the tuning switch mx4_wide
+struct ProjCopies { bool rm, r8, sc, km, fm, tiles; int f8bit, wfmt; bool wide; };
+static ProjCopies copies_of(const ProjW& w) { return {w.rm != nullptr, w.r8 != nullptr, w.sc != nullptr, w.km != nullptr, w.fm != nullptr, w.tiles != nullptr, w.f8bit, w.wfmt, w.tiles != nullptr && w.wide}; }
 static ProjCopies copies_planned(const emmax_model* m, int stage) {
     // decode_mfma.hip's qkv / gate-up pair: fp8 models always, bf16 models when the aux arena was (or would now be) built with the tuning switch km = 0
     const bool pair = stage == STAGE_QKV || stage == STAGE_GATEUP;
-    const bool fm = m->fp8 || (!m->mxq() && (!pair || (m->aux_built ? m->aux_ab : emmax_tune().km == 0)));
+    const bool fp8 = m->wfmt == PW_FP8;
+    const bool fm = fp8 || (!m->is_mx() && (!pair || (m->aux_built ? m->aux_ab : emmax_tune().km == 0)));
     const int bit = stage == STAGE_QKV ? F8_QKV : stage == STAGE_OPROJ ? F8_OPROJ : stage == STAGE_GATEUP ? F8_GATEUP : stage == STAGE_DOWN ? F8_DOWN : F8_LMHEAD;
-    return {true, m->fp8, m->fp8, !m->mxq(), fm, m->mxq(), bit, m->mx4 && m->mx4_wide, m->mx6};
+    return {true, fp8, fp8, !m->is_mx(), fm, m->is_mx(), bit, m->wfmt, m->mx4_wide};
 }
 
 // Which launcher family takes a projection at B rows (EMMAX_VIA_*), EMMAX_VIA_NONE when none does, ROUTE_NO_FM when only decode_mfma.hip's copy
@@ -40,18 +42,18 @@ enum { ROUTE_NO_FM = -1 };
 static int proj_route(const ProjCopies& c, ProjShape s, int B, ProjGeom* g) {
     if (s.exact) {
         s.wfmt = PW_BF16;
-        if (c.sc || c.q4) return EMMAX_VIA_NONE;   // (bf16 weights only: check_exact)
+        if (c.sc || c.tiles) return EMMAX_VIA_NONE;   // (bf16 weights only: check_exact)
         if (B < EMMAX_MFMA_MIN_BATCH) return decode_ks_takes(s, B, g) ? EMMAX_VIA_KS : EMMAX_VIA_NONE;
         // (at most 8 rows per launch, never decode_kmp.hip; tuning switch km = 0 names decode_mfma.hip, which has no two-term form: nothing)
         return c.km && decode_km_enabled() && decode_km_takes(s, B, g) ? EMMAX_VIA_KM : EMMAX_VIA_NONE;
     }
-    if (c.q4) {
-        s.wfmt = c.q6 ? PW_MX6 : PW_MX4;   // (MXFP6 tiles: the same routes at 1-16 rows, no wide form)
+    if (c.tiles) {
+        s.wfmt = c.wfmt;   // (MXFP6 tiles: the same routes at 1-16 rows, no wide form)
         // the MXFP4 down projection runs on the phased kernel only: the K-split form would take K <= 4096, but the format's error lines were
         // measured on the phased kernel alone (policy, not a kernel limit -- the same line emmax_model_create draws)
         if (c.f8bit == F8_DOWN && s.K <= 4096) return EMMAX_VIA_NONE;
         // 17-64 rows: decode_kmp.hip's MX4 form, for a model that froze the tuning switch mx4_wide (decode_km_takes hands them on under the shape's flag)
-        s.mx4_wide = c.q4w && !c.q6;
+        s.mx4_wide = c.wide && c.wfmt == PW_MX4;
         if (!decode_km_takes(s, B, g)) return EMMAX_VIA_NONE;
         return B > 16 ? EMMAX_VIA_KMP : EMMAX_VIA_KM;
     }
@@ -75,29 +77,29 @@ static int launch_proj(const ProjW& w, GemvParams& p, int B, hipStream_t st, int
     if (via) *via = route > 0 ? route : EMMAX_VIA_NONE;
     switch (route) {
         case EMMAX_VIA_KS:
-            p.W = w.rm;
+            gemv_set_weights(p, PW_BF16, w.rm);
             return launch_decode_ks(mode, p, B, st, grid_out, &g);
         case EMMAX_VIA_GEMV:
-            p.W = w.rm;
+            gemv_set_weights(p, PW_BF16, w.rm);
             return launch_decode_gemv_staged(mode, p, B, g, st, grid_out);
         case EMMAX_VIA_GEMV_FP8:
-            p.W = w.r8; p.wscale = w.sc;
+            gemv_set_weights(p, PW_FP8, w.r8, w.sc);
             p.ldw = p.K;   // bytes per row
             return launch_decode_gemv_staged(mode, p, B, g, st, grid_out);
         case EMMAX_VIA_KM:
         case EMMAX_VIA_KMP:
-            if (w.q4) { p.W = w.q4; p.w4_scales = w.q4s; p.w_mx6 = w.q6 ? 1 : 0; }
-            else { p.W = w.km; p.wscale = w.sc ? w.km_sc : nullptr; }
+            if (w.tiles) gemv_set_weights(p, w.wfmt, w.tiles, w.codes);
+            else gemv_set_weights(p, w.sc ? PW_FP8 : PW_BF16, w.km, w.km_sc);
             return launch_decode_km(mode, p, B, st, grid_out, &g);
         case EMMAX_VIA_MFMA:
-            p.W = w.fm; p.wscale = w.sc;
+            gemv_set_weights(p, w.sc ? PW_FP8 : PW_BF16, w.fm, w.sc);
             return launch_decode_mfma(mode, p, B, st, grid_out, &g);
         case ROUTE_NO_FM:
             return fail(EMMAX_ERR_STATE, "decode_mfma.hip's copy of this matrix was not built (tuning switch km was 1 at emmax_model_build_aux)");
         default: break;
     }
     if (p.exact) return fail(EMMAX_ERR_INVALID, "exact numerics: no two-term kernel for this projection (batch %d, K %d)", B, p.K);
-    if (w.q4) return fail(EMMAX_ERR_INVALID, "%s decode weights: no kernel for this projection (batch %d of 1-%d, K %d)", w.q6 ? "MXFP6" : "MXFP4", B, (w.q4w && !w.q6) ? EMMAX_MAX_DECODE_BATCH : 16, p.K);
+    if (w.tiles) return fail(EMMAX_ERR_INVALID, "%s decode weights: no kernel for this projection (batch %d of 1-%d, K %d)", WFMT[w.wfmt].name, B, (w.wide && w.wfmt == PW_MX4) ? EMMAX_MAX_DECODE_BATCH : 16, p.K);
     return -1;   // no family takes this shape at this batch
 }
 
@@ -610,7 +612,7 @@ static int run_qkv0_with_embed(emmax_session* s, int B, hipStream_t st) {
     emmax_model* m = s->m;
     GemvParams p;
     stage_params(s, B, 0, STAGE_QKV, p);
-    p.W = m->layers[0].proj[STAGE_QKV].rm;
+    gemv_set_weights(p, PW_BF16, m->layers[0].proj[STAGE_QKV].rm);
     p.x = m->embed; p.x_tok = s->rows.cur_tok; p.x_copy = s->dh; p.x_vocab = m->vocab;
     const int r = launch_decode_ks(GEMV_QKV, p, B, st, nullptr);
     if (r == -2) {
@@ -623,7 +625,7 @@ static int run_qkv0_with_embed(emmax_session* s, int B, hipStream_t st) {
 int run_decode_step(emmax_session* s, int B, hipStream_t st) {
     emmax_model* m = s->m;
     // batch 1-2 on bf16 weights: the embedding row is read by layer 0's qkv launch itself (decode_ks.hip, when it takes the launch) -- one launch fewer
-    const bool fold_embed = B < EMMAX_MFMA_MIN_BATCH && !m->fp8 && !m->mxq() && decode_ks_enabled() && emmax_tune().fold_embed != 0;
+    const bool fold_embed = B < EMMAX_MFMA_MIN_BATCH && m->wfmt == PW_BF16 && decode_ks_enabled() && emmax_tune().fold_embed != 0;
     if (!fold_embed) KCHK(launch_decode_embed(s->rows.cur_tok, m->embed, s->dh, B, m->H, m->vocab, st, s->exact ? s->dh32 : h32_of(s)));
     const bool taps = s->taps.step.on;   // (nothing bound: the launches below are all there is)
     if (taps)

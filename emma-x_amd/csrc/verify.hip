@@ -81,7 +81,7 @@ static int verify_refusals(const emmax_session* s, const char* who) {
     if (s->warp.on) return fail(EMMAX_ERR_STATE, "%s: warpers are on (emmax_session_clear_warpers): the accepted ids are argmaxes of raw rows", who);
     if (s->proc.on) return fail(EMMAX_ERR_STATE, "%s: logits processing is on (emmax_session_clear_processing): the accepted ids are argmaxes of raw rows", who);
     if (s->samp.on) return fail(EMMAX_ERR_STATE, "%s: sampling is on (emmax_session_clear_sampling): a guess is verified against the greedy token", who);
-    if (s->m->fp8)
+    if (s->m->wfmt == PW_FP8)
         return fail(EMMAX_ERR_STATE, "%s: the model decodes on fp8 weights and prefills on the unquantised matrices: the pass would verify another model", who);
     return 0;
 }

@@ -71,22 +71,19 @@ class LlmConfig:
     max_position: int = 2048  # llm_max_length (configuration_prismatic.py:84)
 
 
-# decode_weight_dtype -> emmax_config.decode_fp8 (include/emmax.h)
-DECODE_WEIGHT_DTYPES = {"bf16": 0, "fp8": 1, "mxfp4": 2}
-# ... the formats added since (3 is no format: emmax_model_create refuses it)
-DECODE_WEIGHT_DTYPES_EXT = {"mxfp6": 4}
+# decode_weight_dtype -> emmax_config.decode_fp8 (include/emmax.h; 3 is no format: emmax_model_create refuses it)
+DECODE_WEIGHT_DTYPES = {"bf16": 0, "fp8": 1, "mxfp4": 2, "mxfp6": 4}
 
 
 def check_decode_weight_dtype(name: str) -> str:
-    if not isinstance(name, str) or (name not in DECODE_WEIGHT_DTYPES and name not in DECODE_WEIGHT_DTYPES_EXT):
-        raise ValueError(f"decode_weight_dtype must be one of {sorted({**DECODE_WEIGHT_DTYPES, **DECODE_WEIGHT_DTYPES_EXT})}, got {name!r}")
+    if not isinstance(name, str) or name not in DECODE_WEIGHT_DTYPES:
+        raise ValueError(f"decode_weight_dtype must be one of {sorted(DECODE_WEIGHT_DTYPES)}, got {name!r}")
     return name
 
 
 def decode_weight_code(name: str) -> int:
     """emmax_config.decode_fp8 of a decode_weight_dtype name"""
-    name = check_decode_weight_dtype(name)
-    return DECODE_WEIGHT_DTYPES[name] if name in DECODE_WEIGHT_DTYPES else DECODE_WEIGHT_DTYPES_EXT[name]
+    return DECODE_WEIGHT_DTYPES[check_decode_weight_dtype(name)]
 
 
 @dataclass

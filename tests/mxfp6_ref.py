@@ -62,7 +62,7 @@ def codes_of(q, negative=None):
 
 
 def pack_tiles(codes, scale_codes):
-    """the tile and scale streams of a matrix in the NATURAL row order, as launch_quant_mx6 writes them: codes uint8 [N, K], scale_codes uint8
+    """the tile and scale streams of a matrix in the NATURAL row order, as launch_quant_mx writes them for MXFP6: codes uint8 [N, K], scale_codes uint8
     [N, K / 32] -> (tiles uint8 [N K 6 / 8], scales uint8 [N K / 32]).  Tile (nt, kt) = 16 rows x 128 k at 1536 (nt K / 128 + kt): lane 16 g + r owns
     block g of row r as 192 bits, element i in bits [6 i, 6 i + 6), little endian; bytes 0-15 at 16 lane of the tile's first KiB, bytes 16-23 at
     8 lane of the 512 B behind it.  Scales: one dword per (tile, row), byte g = block g's code."""

@@ -253,18 +253,18 @@ def _grid_cfg(hidden, heads, inter, vocab, fmt):
 
 
 @pytest.mark.parametrize("hidden", [256, 512, 1024, 4096, 5120])
-@pytest.mark.parametrize("fmt", ["bf16", "fp8", "mxfp4"])
+@pytest.mark.parametrize("fmt", ["bf16", "fp8", "mxfp4", "mxfp6"])
 def test_limit_equals_route(lib, hidden, fmt):
     _, so = lib
     for heads, inter, vocab in itertools.product(((4, 2), (32, 32), (32, 8)), (1024, 4096, 4160, 11008, 12288, 13824), (4096, 32064)):
         cfg = _grid_cfg(hidden, heads, inter, vocab, fmt)
         m = Model(so, cfg)
         what = (hidden, heads, inter, vocab, fmt)
-        if fmt == "mxfp4":   # check_config speaks before a model exists: it accepts exactly what the planner serves at 8 rows
+        if fmt in ("mxfp4", "mxfp6"):   # check_config speaks before a model exists: it accepts exactly what the planner serves at 8 rows
             planned = so.emmax_config_max_decode_batch(C.byref(m.cc), 0)
             assert (m.rc == 0) == (planned >= 8), (what, m.rc, m.err, planned)
             if m.rc:
-                assert "MXFP4 decode weights need" in m.err, (what, m.err)
+                assert f"{fmt.upper()} decode weights need" in m.err, (what, m.err)
                 continue
             assert planned == m.limit()
         assert m.rc == 0, (what, m.err)

@@ -82,7 +82,7 @@ def test_decode_weight_dtype_validation_and_c_mapping():
     from emmax.config import DECODE_WEIGHT_DTYPES, EmmaXConfig, check_decode_weight_dtype
     from emmax.engine import _config_c
 
-    assert DECODE_WEIGHT_DTYPES == {"bf16": 0, "fp8": 1, "mxfp4": 2}
+    assert DECODE_WEIGHT_DTYPES == {"bf16": 0, "fp8": 1, "mxfp4": 2, "mxfp6": 4}
     for name, code in DECODE_WEIGHT_DTYPES.items():
         cfg = EmmaXConfig.tiny()
         cfg.decode_weight_dtype = check_decode_weight_dtype(name)

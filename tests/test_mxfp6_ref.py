@@ -127,10 +127,10 @@ def test_error_figure_beside_mxfp4():
 
 # ---- the public surface -----------------------------------------------------------------------------------------------------------------
 def test_decode_weight_dtype_validation_and_c_mapping():
-    from emmax.config import DECODE_WEIGHT_DTYPES, DECODE_WEIGHT_DTYPES_EXT, EmmaXConfig, check_decode_weight_dtype
+    from emmax.config import DECODE_WEIGHT_DTYPES, EmmaXConfig, check_decode_weight_dtype
     from emmax.engine import _config_c
 
-    assert DECODE_WEIGHT_DTYPES == {"bf16": 0, "fp8": 1, "mxfp4": 2} and DECODE_WEIGHT_DTYPES_EXT == {"mxfp6": 4}
+    assert DECODE_WEIGHT_DTYPES == {"bf16": 0, "fp8": 1, "mxfp4": 2, "mxfp6": 4}
     assert check_decode_weight_dtype("mxfp6") == "mxfp6"
     cfg = EmmaXConfig.tiny()
     cfg.decode_weight_dtype = "mxfp6"

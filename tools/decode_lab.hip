@@ -42,7 +42,7 @@ int main(int argc, char** argv) {
             for (int i = 0; i < NBUF; ++i) {
                 GemvParams p;
                 memset(&p, 0, sizeof(p));
-                p.x = x; p.ldx = s.K; p.W = fm[i]; p.ldw = s.K; p.K = s.K; p.y = y; p.ldy = s.N; p.n_rows = s.N;
+                p.x = x; p.ldx = s.K; gemv_set_weights(p, PW_BF16, fm[i]); p.ldw = s.K; p.K = s.K; p.y = y; p.ldy = s.N; p.n_rows = s.N;
                 if (!(getenv("SK") && atoi(getenv("SK")) == 0)) p.sk_ws = (unsigned long long*)skws;
                 if (launch_decode_mfma(GEMV_PLAIN, p, B, 0) != 0) { printf("launch failed\n"); return 1; }
             }

@@ -37,9 +37,9 @@ int main(int argc, char** argv) {
             for (int i = 0; i < NBUF; ++i) {
                 GemvParams p;
                 memset(&p, 0, sizeof(p));
-                p.x = x; p.ldx = s.K; p.W = W[i]; p.ldw = s.K; p.K = s.K; p.y = y; p.ldy = s.mode == GEMV_GATEUP ? s.N / 2 : s.N; p.n_rows = s.N;
+                p.x = x; p.ldx = s.K; p.ldw = s.K; p.K = s.K; p.y = y; p.ldy = s.mode == GEMV_GATEUP ? s.N / 2 : s.N; p.n_rows = s.N;
                 p.norm_w = nwp; p.eps = 1e-5f;
-                if (fp8) p.wscale = (const float*)wsc;
+                gemv_set_weights(p, fp8 ? PW_FP8 : PW_BF16, W[i], fp8 ? wsc : nullptr);
                 if (launch_decode_gemv(s.mode, p, B, 0, &grid) != 0) { printf("launch failed\n"); return 1; }
             }
             CHECK(hipEventRecord(e1, 0));
